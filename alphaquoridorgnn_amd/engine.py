@@ -310,10 +310,11 @@ class MultiSetSelfPlay:
     One set is a strictly serial chain per simulation (step -> trunk -> heads): while its step / heads kernels run, most of
     the chip idles, and the trunk's last boards leave CUs empty.  Games are independent, so splitting them into K sets whose
     move() calls are enqueued round-robin on K streams lets the GPU fill those holes with another set's kernels (2048 games x
-    200 sims, hipGraph replay on: K = 1 / 2 / 3 / 4: ~1,000 / 1,330 / 1,360 / 1,590 games/s).  K = 4 needs
-    GPU_MAX_HW_QUEUES >= 5 (set to 8 by the package unless the user chose a value): with the runtime's default of 4 hardware
-    queues two of the streams share a queue and serialise; K >= 5 collapses (~550-600 games/s): the GPU runs four compute
-    queues concurrently.  What the overlap can and cannot do is measured in DESIGN.md section 4 K4 (a round of the four sets
+    200 sims, hipGraph replay on: K = 1 / 2 / 3 / 4: ~1,000 / 1,330 / 1,360 / 1,590 games/s, one hardware queue per
+    stream).  Streams that share a hardware queue serialise, so the default set count follows the queue count that the
+    environment variable GPU_MAX_HW_QUEUES grants the process:
+    two sets when it grants fewer than five queues, four when it is unset.  K >= 5 collapses (~550-600 games/s): the GPU
+    runs four compute queues concurrently.  What the overlap can and cannot do is measured in DESIGN.md section 4 K4 (a round of the four sets
     costs about the SUM of their trunk launches: two resident trunk workgroups fill a CU's register file, so the other
     sets' kernels run in the trunks' shadow).  Set k is bit-identical to a stand-alone
     BatchedSelfPlay(num_games_k, seed = seed * 64 + k): nothing is shared but the read-only packed weights (and the K
@@ -322,13 +323,14 @@ class MultiSetSelfPlay:
     def __init__(self, model=None, num_games=2048, sims=50, num_sets=None, seed=0, device=None, quota=None, **kw):
         self.dev = _lib.require_gpu(device)
         if num_sets is None:                      # one hardware queue per set + the default stream, or fall back to 2
-            num_sets = 4 if int(os.environ.get("GPU_MAX_HW_QUEUES", "4")) >= 5 else 2
+            queues = os.environ.get("GPU_MAX_HW_QUEUES")
+            num_sets = 4 if queues is None or int(queues) >= 5 else 2
         k = max(1, min(int(num_sets), int(num_games)))
         sizes = [num_games // k + (1 if i < num_games % k else 0) for i in range(k)]
         quota = num_games if quota is None else int(quota)
         quotas = [quota // k + (1 if i < quota % k else 0) for i in range(k)]      # each set refills its own slots
         # The K streams are created once per device and reused by every MultiSetSelfPlay: torch hands out streams from a pool
-        # that is never destroyed, and the runtime maps streams onto GPU_MAX_HW_QUEUES (8) hardware queues -- a second engine
+        # that is never destroyed, and the runtime maps streams onto its hardware queues round-robin -- a second engine
         # with four NEW streams (e.g. the next generation's) would share queues with the first one's idle streams, two of its
         # sets would serialise, and the generation would run 35 % slower (measured: 1,030 vs 1,530 games/s).
         key = (self.dev.index, k)

@@ -38,6 +38,12 @@ it is measured and what bounds it is written HERE and in DESIGN.md section 5 (`n
                  run.  `value` itself never uses the table.
   cpu_baseline : the oracle (CPU restatement, kind "port") on a bounded sample of the same workload -- one sequential self-play
                  loop per host core of the box's share (16), rates summed --, rank 0, N=1.
+
+`--dump-outputs DIR` (rank 0) writes what the last timed step handed its caller, the gathered (s, pi, z) rows of the generation,
+as float32 .npy files: states [R, 72], visits [R, A] (visit counts), z [R], with rows [R] (float64, the indices of the dumped
+rows among all gathered rows) and counters (float64: rank 0's finished games and leaf evaluations, gathered rows, plies).  When all rows
+would take more than DUMP_BYTES, R rows are drawn by a fixed seed.  Weights and game seeds are fixed, so two runs with the
+same arguments play the same games.
 """
 import argparse
 import json
@@ -48,7 +54,6 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # 4 game-set streams + the default stream, one hardware queue each (read at HIP init)
 
 import numpy as np
 import torch
@@ -67,6 +72,7 @@ PEAK_HBM = 8.0e12
 # cannot be collected from inside this process; what a rocprofv3 pass of THIS round measured is in profiles/r03_pmc_summary.csv
 # and quoted in DESIGN.md section 5 -- `roofline.traffic` stays null in the line rather than carrying a constant.
 TRUNK_COMPULSORY_BYTES_PER_BOARD = 72 + 512
+DUMP_BYTES = 48 << 20                                                # --dump-outputs: payload cap (a seeded row sample beyond it)
 LEGAL_BYTES_PER_STATE = 100                                          # 68 B in + 27 B (209 bits) out ~ 100 B/state
 REF_LEGAL_MS_PER_STATE_PY = 4.95                                     # the reference's State.legal_actions(), 1 core (python)
 # training step, per position: forward trunk + the three weight gradients (same contractions) + the two data gradients
@@ -253,6 +259,22 @@ def legal_mask_leg(dev, lib, _lib, synth_states):
     return leg
 
 
+def dump_outputs(path, st, vis, z, counters, plies):
+    """--dump-outputs: the last timed step's gathered rows as float32 .npy files (a seeded sample of rows beyond DUMP_BYTES)."""
+    os.makedirs(path, exist_ok=True)
+    st, vis, z = (x.cpu().numpy() for x in (st, vis, z))
+    P = st.shape[0]
+    row_bytes = 4 * (st.shape[1] + vis.shape[1] + 1) + 8
+    rows = np.arange(P)
+    if P * row_bytes > DUMP_BYTES:
+        rows = np.sort(np.random.RandomState(0).choice(P, DUMP_BYTES // row_bytes, replace=False))
+    arrays = {"states": st[rows].astype(np.float32), "visits": vis[rows].astype(np.float32), "z": z[rows].astype(np.float32),
+              "rows": rows.astype(np.float64),
+              "counters": np.asarray([counters["finished"], counters["leaf_evals"], P, plies], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -274,7 +296,11 @@ def main():
     ap.add_argument("--large-games", type=int, default=16384,
                     help="extra single-GPU leg: one generation at this many concurrent games (north star: >= 10k); 0 = skip")
     ap.add_argument("--rccl-child", default=None, choices=_RCCL_ORDERS, help="internal: one process of the rccl_group_alive leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's gathered (s, pi, z) rows to DIR/<name>.npy (see the docstring)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
     if args.rccl_child:
         return rccl_child(args.rccl_child, args.games, args.sims, args.sets)
 
@@ -324,6 +350,7 @@ def main():
                                       # launches per run of two steps; four plies cost twice that and told nothing more).
     sample_no = [0]
     last_plies = [0]
+    last_rows = [None]                # --dump-outputs: the gathered rows of the last step (fresh tensors, no copy in the timed loop)
 
     def _before(e):
         sampled_boards.sub_(e.t["stat_leaf_evals"].sum())    # boards evaluated by the sampled launches, counted on the device
@@ -352,6 +379,8 @@ def main():
         st, vis, z = eng.history_tensors()
         st, vis, z = gather_history(st, vis, z)       # the generation's one exchange step (RCCL all-gather)
         last_plies[0] = ply
+        if args.dump_outputs and profile:             # timed steps only
+            last_rows[0] = (st, vis, z)
         return eng.counters(), int(st.shape[0])
 
     for _ in range(args.warmup):
@@ -367,6 +396,9 @@ def main():
         positions = npos
     sync_all()
     elapsed = time.time() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last_rows[0], c, last_plies[0])
+    last_rows[0] = None
     trunk_ms, trunk_launches, trunk_rows = _lib.profile_collect(reset=True)
     trunk_boards = int(sampled_boards.sum().item())    # boards evaluated inside the event-bracketed launches
 

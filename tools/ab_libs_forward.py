@@ -29,6 +29,6 @@ print(" | ".join(res))
 libs = sys.argv[1:]
 for rep in range(2):
     for lib in libs:
-        env = dict(os.environ, AQG_LIB_PATH=os.path.abspath(lib), GPU_MAX_HW_QUEUES="8")
+        env = dict(os.environ, AQG_LIB_PATH=os.path.abspath(lib))
         out = subprocess.run([sys.executable, "-c", _WORKER, ROOT], env=env, cwd=ROOT, capture_output=True, text=True)
         print(f"{os.path.basename(lib):28s} {out.stdout.strip().splitlines()[-1] if out.stdout.strip() else out.stderr[-300:]}", flush=True)

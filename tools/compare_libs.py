@@ -58,7 +58,7 @@ np.savez(sys.argv[2], **out)
 
 
 def run(libpath, outpath):
-    env = dict(os.environ, AQG_LIB_PATH=os.path.abspath(libpath), GPU_MAX_HW_QUEUES="8")
+    env = dict(os.environ, AQG_LIB_PATH=os.path.abspath(libpath))
     subprocess.run([sys.executable, "-c", _WORKER, ROOT, outpath], check=True, env=env, cwd=ROOT)
     return np.load(outpath)
 

@@ -2,7 +2,6 @@
 """Wall time of each move of a lock-step generation (2048 games x 200 sims, 4 sets): where in a game the time goes."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 from alphaquoridorgnn_amd import _lib
 from alphaquoridorgnn_amd.engine import MultiSetSelfPlay

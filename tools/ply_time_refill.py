@@ -2,7 +2,6 @@
 """Wall time of each move of a REFILLED generation (6144 games on 2048 slots x 200 sims, 4 sets)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 from alphaquoridorgnn_amd import _lib
 from alphaquoridorgnn_amd.engine import MultiSetSelfPlay

@@ -12,7 +12,6 @@ src = os.path.join(ROOT, "alphaquoridorgnn_amd", "csrc")
 subprocess.check_call(f"cd {src} && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -DAQG_TRACE "
                       f"legal_mask.hip gcn_forward.hip gcn_train.hip mcts.hip capi.hip host_agents.cpp -o {so} 2>/dev/null", shell=True)
 os.environ["AQG_LIB_PATH"] = so
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np, torch
 from collections import defaultdict
 from alphaquoridorgnn_amd import _lib
