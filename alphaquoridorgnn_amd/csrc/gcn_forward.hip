@@ -1914,8 +1914,11 @@ __global__ __launch_bounds__(256) void ell_gather_kernel(const float* __restrict
     *reinterpret_cast<float2*>(out + (size_t)n * HID + 2 * lane) = make_float2(fmaxf(a0, 0.f), fmaxf(a1, 0.f));
 }
 
-__global__ __launch_bounds__(128) void board_pool_kernel(const float* __restrict__ Hn, int V, float* __restrict__ pooled) {
+// (`active`: the engine's leaf mask, as in the heads -- a masked-out board's pooled row is left as it was)
+__global__ __launch_bounds__(128) void board_pool_kernel(const float* __restrict__ Hn, int V, const uint8_t* __restrict__ active,
+                                                         float* __restrict__ pooled) {
     const int b = blockIdx.x;
+    if (active && !active[b]) return;
     float s = 0.f;
     for (int i = 0; i < V; ++i) s += Hn[((size_t)b * V + i) * HID + threadIdx.x];
     pooled[(size_t)b * HID + threadIdx.x] = s / (float)V;
@@ -1951,7 +1954,7 @@ int launch_gcn_forward_boards_any(int N, const void* states, int fmt, int B, con
     hipLaunchKernelGGL(ell_gather_kernel, gg, blk, 0, st, (const float*)work0, R, (const int32_t*)ell_idx, (const float*)ell_w, packed + PackedLayout::B2, work1);
     hipLaunchKernelGGL(graph_linear_kernel<false>, lg, blk, 0, st, (const float*)work1, HID, R, packed + PackedLayout::W3T, work0);
     hipLaunchKernelGGL(ell_gather_kernel, gg, blk, 0, st, (const float*)work0, R, (const int32_t*)ell_idx, (const float*)ell_w, packed + PackedLayout::B3, work1);
-    hipLaunchKernelGGL(board_pool_kernel, dim3(B), dim3(128), 0, st, (const float*)work1, V, pooled);
+    hipLaunchKernelGGL(board_pool_kernel, dim3(B), dim3(128), 0, st, (const float*)work1, V, active, pooled);
     if (int r = check_launch("generic board kernels")) return r;
     if (!logits && !policy && !value_pre && !value) return 0;
     hipLaunchKernelGGL(gcn_heads_kernel, dim3((B + HB - 1) / HB), dim3(256), 0, st, (const float*)pooled, B, A, packed, logits, policy,

@@ -244,50 +244,83 @@ class GraphPolicyValueNetwork(nn.Module):
 
     # ---------------------------------------------------------------- generic (x, edge_index, batch) path
     @staticmethod
-    def _build_csr(edge_index, num_nodes):
-        """gcn_norm (PyG defaults: weight 1, add remaining self loops, symmetric normalisation) -> CSR by destination."""
-        dev = edge_index.device
-        src, dst = edge_index[0].long(), edge_index[1].long()
-        has_loop = torch.zeros(num_nodes, dtype=torch.bool, device=dev)
-        has_loop[src[src == dst]] = True
-        extra = torch.nonzero(~has_loop).flatten()
-        src = torch.cat([src, extra])
-        dst = torch.cat([dst, extra])
-        deg = torch.zeros(num_nodes, dtype=torch.float32, device=dev).index_add_(0, dst, torch.ones_like(dst, dtype=torch.float32))
-        dis = deg.pow(-0.5)
-        dis[torch.isinf(dis)] = 0
+    def _prepare_graph(x, edge_index, batch):
+        """Everything forward(x, edge_index, batch) does before its launch, on x's device (CPU or GPU alike):
+        validation, PyG's gcn_norm as a CSR by destination, and the graph pointer of the mean pool.
+
+        Raises ValueError unless x is [n, 6] floating point, edge_index an integer [2, E] tensor with every id in [0, n),
+        and batch an integer [n] tensor, non-negative and sorted (PyG's Batch convention; unsorted batches are not
+        supported).  The id and batch checks share ONE device-to-host read, made before any tensor is indexed with the ids.
+
+        gcn_norm with GCNConv's defaults: every edge has weight 1; add_remaining_self_loops drops every existing i -> i edge
+        and appends exactly one self loop per node; repeated non-loop edges each count.  deg[i] = number of edges INTO i
+        (flow source_to_target, the self loop included, so deg >= 1), w_e = deg[src]^-1/2 * deg[dst]^-1/2.
+        Returns (ptr int32 [n+1], src int32 [E_nonloop+n], w float32 [E_nonloop+n], gptr int32 [G+1], G): the edges into
+        node i are ptr[i] .. ptr[i+1] (its incoming edges in input order, then its self loop), graph g holds the nodes
+        gptr[g] .. gptr[g+1] and G = batch.max() + 1 (a graph id without nodes pools to 0, as in PyG)."""
+        def integral(t):
+            return not (t.is_floating_point() or t.is_complex() or t.dtype == torch.bool)
+        if x.dim() != 2 or x.shape[1] != NUM_FEATURES or not x.is_floating_point():
+            raise ValueError(f"x must be a floating-point [num_nodes, {NUM_FEATURES}] tensor, got {x.dtype} {tuple(x.shape)}")
+        n = x.shape[0]
+        if edge_index.dim() != 2 or edge_index.shape[0] != 2 or not integral(edge_index):
+            raise ValueError(f"edge_index must be an integer [2, E] tensor, got {edge_index.dtype} {tuple(edge_index.shape)}")
+        if batch.dim() != 1 or batch.shape[0] != n or not integral(batch):
+            raise ValueError(f"batch must be an integer [num_nodes] = [{n}] tensor, got {batch.dtype} {tuple(batch.shape)}")
+        dev = x.device
+        ei = edge_index.to(dev).long()
+        src, dst = ei[0], ei[1]
+        batch = batch.to(dev).long()
+        E = src.shape[0]
+        loop = src == dst
+        # one device-to-host read for every data-dependent check and size
+        stats = [(~loop).sum()]
+        if E:
+            stats += [ei.amin(), ei.amax()]
+        if n:
+            stats += [batch[0], batch[-1], (batch[1:] < batch[:-1]).sum()]
+        stats = torch.stack(stats).tolist()
+        E_nonloop = stats[0]
+        if E and (stats[1] < 0 or stats[2] >= n):
+            raise ValueError(f"edge_index holds node ids outside [0, {n}) (min {stats[1]}, max {stats[2]})")
+        if n and stats[-1]:
+            raise ValueError("batch must be sorted (PyG Batch convention; unsorted batches are not supported)")
+        if n and stats[-3] < 0:
+            raise ValueError(f"batch ids must be non-negative (min {stats[-3]})")
+        G = stats[-2] + 1 if n else 0
+        # add_remaining_self_loops + CSR in one stable sort: existing loops get the key n (sorted past every node and cut
+        # off), one loop per node is appended after the input edges
+        nodes = torch.arange(n, device=dev)
+        src = torch.cat([src, nodes])
+        dst = torch.cat([torch.where(loop, n, dst), nodes])
+        order = torch.argsort(dst, stable=True)[:E_nonloop + n]
+        src, dst = src[order], dst[order]
+        ptr = torch.searchsorted(dst, torch.arange(n + 1, device=dev)).to(torch.int32)
+        dis = (ptr[1:] - ptr[:-1]).to(torch.float32).pow(-0.5)
         w = dis[src] * dis[dst]
-        order = torch.argsort(dst, stable=True)
-        counts = torch.bincount(dst, minlength=num_nodes)
-        ptr = torch.zeros(num_nodes + 1, dtype=torch.int32, device=dev)
-        ptr[1:] = torch.cumsum(counts, 0).to(torch.int32)
-        return ptr, src[order].to(torch.int32).contiguous(), w[order].contiguous()
+        gptr = torch.searchsorted(batch, torch.arange(G + 1, device=dev)).to(torch.int32)
+        return ptr, src.to(torch.int32).contiguous(), w.contiguous(), gptr, G
 
     def forward(self, x, edge_index, batch):
-        """pv_network_gnn.py:53-64.  x [sum V, 6] float32, edge_index [2,E] int64, batch [sum V] int64 (sorted)."""
+        """pv_network_gnn.py:53-64 with PyG's GCNConv / global_mean_pool semantics (_prepare_graph: the self-loop rule and the
+        validated inputs).  x [sum V, 6] floating point, edge_index [2, E] integer ids in [0, sum V), batch [sum V] integer,
+        non-negative and sorted (unsorted raises ValueError).  One device-to-host read per call once the weights are packed."""
         dev = _lib.require_gpu(x.device)
         lib = _lib.load()
+        ptr, csr_src, csr_w, gptr, G = self._prepare_graph(x, edge_index, batch)
         x = x.to(torch.float32).contiguous()
         n = x.shape[0]
-        if x.shape[1] != NUM_FEATURES:
-            raise ValueError(f"x must have {NUM_FEATURES} features")
-        batch = batch.long()
-        if n > 1 and bool((batch[1:] < batch[:-1]).any()):
-            raise ValueError("batch must be sorted (PyG Batch convention)")
-        G = int(batch.max().item()) + 1 if n else 0
-        gptr = torch.zeros(G + 1, dtype=torch.int32, device=dev)
-        gptr[1:] = torch.cumsum(torch.bincount(batch, minlength=G), 0).to(torch.int32)
-        ptr, csr_src, csr_w = self._build_csr(edge_index.to(dev), n)
         A = self.policy_output_size
         f32 = dict(dtype=torch.float32, device=dev)
         w0, w1 = torch.empty((n, HIDDEN_DIM), **f32), torch.empty((n, HIDDEN_DIM), **f32)
         pooled = torch.empty((G, HIDDEN_DIM), **f32)
         policy, value = torch.empty((G, A), **f32), torch.empty((G,), **f32)
         logits, vpre = torch.empty((G, A), **f32), torch.empty((G,), **f32)
-        _lib.check(lib.aqg_gcn_forward_graph(NUM_FEATURES, A, _lib.ptr(x), n, _lib.ptr(ptr), _lib.ptr(csr_src), _lib.ptr(csr_w),
-                                             _lib.ptr(gptr), G, _lib.ptr(self.packed_weights(dev)), _lib.ptr(w0), _lib.ptr(w1),
-                                             _lib.ptr(pooled), _lib.ptr(logits), _lib.ptr(policy), _lib.ptr(vpre), _lib.ptr(value),
-                                             _lib.stream_ptr(dev)), "aqg_gcn_forward_graph")
+        if n:       # (no nodes: no graphs, and the empty buffers have no address to pass)
+            _lib.check(lib.aqg_gcn_forward_graph(NUM_FEATURES, A, _lib.ptr(x), n, _lib.ptr(ptr), _lib.ptr(csr_src), _lib.ptr(csr_w),
+                                                 _lib.ptr(gptr), G, _lib.ptr(self.packed_weights(dev)), _lib.ptr(w0), _lib.ptr(w1),
+                                                 _lib.ptr(pooled), _lib.ptr(logits), _lib.ptr(policy), _lib.ptr(vpre), _lib.ptr(value),
+                                                 _lib.stream_ptr(dev)), "aqg_gcn_forward_graph")
         self.last_logits, self.last_value_pre = logits, vpre
         return policy, value.unsqueeze(1)
 

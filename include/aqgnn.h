@@ -147,8 +147,8 @@ int aqg_gcn_forward_boards_guarded(int board_size, const void* states, int state
                                    int flags, int32_t* saturated, void* stream);
 /* Same network on an arbitrary batched graph: forward(x, edge_index, batch)  pv_network_gnn.py:53.
  *   x [num_nodes, F] f32;  csr_ptr [num_nodes+1] i32 / csr_src [E'] i32 / csr_w [E'] f32 : incoming edges of
- *   each node INCLUDING self loops with the gcn_norm weights already attached (built by the host wrapper
- *   from edge_index with torch ops);  graph_ptr [num_graphs+1] i32 node ranges (batch must be sorted);
+ *   each node INCLUDING its one self loop with the gcn_norm weights already attached (built and validated by the host
+ *   wrapper from edge_index with torch ops: every csr_src in [0, num_nodes), nothing here checks it);  graph_ptr [num_graphs+1] i32 node ranges (batch must be sorted);
  *   work0/work1 [num_nodes,128] f32 scratch. */
 /* The same forward for ANY board size 3/5/7/9: 9x9 dispatches to the fused kernels above (workspace unused), the smaller
  * boards of the reference's constants.py:5-20 run on plain kernels (features + ELL adjacency -> linear / gather x3 -> pool

@@ -7,9 +7,10 @@ outputs for pv_network_gnn.py.  This file therefore restates
   * structure: /root/reference/pv_network_gnn.py:23-64 (3x GCNConv+ReLU -> global_mean_pool ->
     policy MLP 128-64-209 + Softmax, value MLP 128-64-1 + Tanh);
   * the layer: PyG's published GCNConv with its defaults (improved=False, add_self_loops=True,
-    normalize=True, bias=True):  x' = x W^T (no bias in `lin`);  gcn_norm: every edge weight 1, one
-    self-loop of weight 1 added per node that has none, deg[i] = sum of weights of edges INTO i,
-    w_e = deg[src]^-1/2 * deg[dst]^-1/2 (inf -> 0);  out[i] = sum_{e=(j->i)} w_e x'[j];  out += bias;
+    normalize=True, bias=True):  x' = x W^T (no bias in `lin`);  gcn_norm: every edge weight 1,
+    add_remaining_self_loops (every existing i -> i edge is dropped, then exactly one self loop of weight 1 is
+    appended per node; repeated non-loop edges each count), deg[i] = sum of weights of edges INTO i (>= 1),
+    w_e = deg[src]^-1/2 * deg[dst]^-1/2;  out[i] = sum_{e=(j->i)} w_e x'[j];  out += bias;
   * global_mean_pool: per-graph mean of node rows;
   * node features: pv_network_cnn.py:88-114 (the 6 planes read as [81, 6] node features, SURVEY 8a F0);
   * the board graph (absent from the reference): nodes = tiles, directed edges both ways
@@ -76,17 +77,13 @@ def board_edges(rec):
 def gcn_conv(x, edge_index, W, b):
     """One GCNConv (PyG defaults) in fp64.  x [V,F], edge_index [2,E] (src,dst), W [out,in], b [out]."""
     V = x.shape[0]
-    src, dst = edge_index[0], edge_index[1]
-    has_loop = np.zeros(V, dtype=bool)
-    has_loop[src[src == dst]] = True
-    extra = np.nonzero(~has_loop)[0]
-    src = np.concatenate([src, extra])
-    dst = np.concatenate([dst, extra])
+    src, dst = np.asarray(edge_index[0], dtype=np.int64), np.asarray(edge_index[1], dtype=np.int64)
+    keep = src != dst                                 # add_remaining_self_loops: every existing loop goes, one per node comes
+    src = np.concatenate([src[keep], np.arange(V)])
+    dst = np.concatenate([dst[keep], np.arange(V)])
     deg = np.zeros(V, dtype=np.float64)
     np.add.at(deg, dst, 1.0)
-    with np.errstate(divide="ignore"):
-        dis = deg ** -0.5
-    dis[np.isinf(dis)] = 0.0
+    dis = deg ** -0.5
     w = dis[src] * dis[dst]
     xw = x @ W.T
     out = np.zeros((V, W.shape[0]), dtype=np.float64)

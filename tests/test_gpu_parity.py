@@ -115,6 +115,24 @@ def test_legal_actions_large_batch_properties(dev):
     assert e_count.numel() == 0
 
 
+def _wall_heavy_states(N, games, plies, rng):
+    """Every non-terminal position of `games` random games (oracle rules, at most `plies` plies each) that place a wall whenever
+    one is legal and rng.rand() < 0.6: wall-heavy states of a board size without reference fixtures."""
+    from oracle import quoridor as oq
+    recs = []
+    for game in range(games):
+        s = oq.State(N=N)
+        for ply in range(plies):
+            if s.is_done():
+                break
+            recs.append(s.rec.copy())
+            la = s.legal_actions()
+            walls = [a for a in la if a >= N * N]
+            pick = walls if (walls and rng.rand() < 0.6) else la
+            s = s.next(pick[rng.randint(len(pick))])
+    return np.stack(recs)
+
+
 def test_rules_and_mcts_on_7x7_vs_oracle(dev):
     """A board size with no reference fixtures (the reference defines 3x3 / 5x5 / 9x9 constants only): GPU legal lists,
     transitions, terminal flags and lock-step MCTS visit counts against the oracle on random wall-heavy play."""
@@ -123,18 +141,7 @@ def test_rules_and_mcts_on_7x7_vs_oracle(dev):
     from oracle import mcts as om, quoridor as oq
     N = 7
     rng = np.random.RandomState(7)
-    recs = []
-    for game in range(30):
-        s = oq.State(N=N)
-        for ply in range(50):
-            if s.is_done():
-                break
-            recs.append(s.rec.copy())
-            la = s.legal_actions()
-            walls = [a for a in la if a >= N * N]
-            pick = walls if (walls and rng.rand() < 0.6) else la
-            s = s.next(pick[rng.randint(len(pick))])
-    recs = np.stack(recs)
+    recs = _wall_heavy_states(N, 30, 50, rng)
     a, c, m = oq.legal_actions_batch(recs)
     d = torch.from_numpy(recs).to(dev)
     mask, order, count = gl.legal_actions_batch(d, N)
@@ -599,6 +606,271 @@ def test_gnn_forward_generic_graph(dev):
     policy, value = model(torch.from_numpy(xn).float().to(dev), torch.from_numpy(en).to(dev), torch.from_numpy(bn).to(dev))
     np.testing.assert_allclose(model.last_logits.cpu().numpy(), ref["logits"], atol=2e-5, rtol=1e-4)
     np.testing.assert_allclose(value[:, 0].cpu().numpy(), ref["value"], atol=2e-5, rtol=1e-4)
+
+
+# ------------------------------------------------------------------ generic forward(x, edge_index, batch): PyG semantics at the edges
+def _with_gcn_biases(params):
+    """The same weights with non-zero GCN biases (PyG initialises them to zero, which would hide a bias slip)."""
+    p = dict(params)
+    for l in range(3):
+        p[f"gcn_layers.{l}.bias"] = (np.linspace(-0.3, 0.5, 128) * (1 + l)).astype(np.float32)
+    return p
+
+
+def _net(params, N=9):
+    from alphaquoridorgnn_amd.pv_network_gnn import GraphPolicyValueNetwork
+    m = GraphPolicyValueNetwork(6, 128, 3, N * N + 2 * (N - 1) ** 2, board_size=N)
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v).copy()) for k, v in params.items()})
+    return m.to("cuda").eval()
+
+
+def _board_graphs(recs):
+    """The board graphs of `recs` as one numpy (x, edge_index, batch): oracle node features and edges."""
+    from oracle import gnn as og
+    xs, es, bs, off = [], [], [], 0
+    for b, rec in enumerate(recs):
+        xs.append(og.node_features(rec))
+        es.append(og.board_edges(rec) + off)
+        bs.append(np.full(xs[-1].shape[0], b))
+        off += xs[-1].shape[0]
+    return np.concatenate(xs), np.concatenate(es, 1), np.concatenate(bs)
+
+
+def _generic(model, dev, x, edge_index, batch):
+    """forward(x, edge_index, batch) with LDS poisoned first -> (policy, value, logits, value_pre) device tensors."""
+    from alphaquoridorgnn_amd import _lib
+    _lib.poison_lds(dev)
+    policy, value = model(x, edge_index, batch)
+    return policy, value, model.last_logits, model.last_value_pre
+
+
+def _assert_rows_close(got, ref, bar, what=""):
+    """logits / value_pre at atol = rtol-scaled `bar` (the suite's stated bars), policy / value as in the board tests; names the rows."""
+    policy, value, logits, vpre = (t.cpu().numpy().astype(np.float64) for t in got)
+    atol, rtol = bar
+    bad = np.nonzero(~np.isclose(logits, ref["logits"], atol=atol, rtol=rtol).all(1) |
+                     ~np.isclose(vpre, ref["value_pre"], atol=atol, rtol=rtol))[0]
+    assert bad.size == 0, f"{what}: {bad.size} rows off, first {bad[:8]}"
+    np.testing.assert_allclose(policy, ref["policy"], atol=1e-6, rtol=1e-4, err_msg=what)
+    np.testing.assert_allclose(value[:, 0], ref["value"], atol=atol, rtol=rtol, err_msg=what)
+
+
+def _pyg_edge_case_batch(seed=8):
+    """One ragged batch of the graphs where gcn_norm implementations part ways: duplicate edges (x2, x3), repeated self loops,
+    an edgeless graph, single-node graphs (one with two loops), a graph id with no nodes, a hub with 2,100 in-edges; 2,155 nodes
+    in all (neither a multiple of 32 nor of 4: the tails of graph_linear_kernel and graph_gather_kernel run)."""
+    rng = np.random.RandomState(seed)
+    graphs = []                                          # (graph id, n, local edges [2, E])
+    e = rng.randint(0, 7, size=(2, 14))
+    e = np.concatenate([e, e[:, :4], e[:, :2], [[0, 0, 0, 2, 2], [0, 0, 0, 2, 2]]], 1)   # multiplicity 2-3, loops x3 / x2
+    graphs.append((0, 7, e))
+    graphs.append((1, 5, np.zeros((2, 0), np.int64)))   # edgeless
+    graphs.append((2, 1, np.zeros((2, 0), np.int64)))   # single node
+    graphs.append((3, 1, np.zeros((2, 2), np.int64)))   # single node with two self loops
+    # (graph id 4 has no nodes: it pools to zeros, as global_mean_pool does)
+    hub = np.stack([np.arange(1, 2101), np.zeros(2100, np.int64)])
+    graphs.append((5, 2101, np.concatenate([hub, hub[:, :40], rng.randint(0, 2101, size=(2, 300)), [[0], [0]]], 1)))
+    graphs.append((6, 37, rng.randint(0, 37, size=(2, 90))))
+    graphs.append((7, 3, np.asarray([[0, 1], [1, 2]])))
+    xs, es, bs, off = [], [], [], 0
+    for gid, n, ge in graphs:
+        xs.append(rng.randn(n, 6))
+        es.append(np.asarray(ge, np.int64) + off)
+        bs.append(np.full(n, gid))
+        off += n
+    return np.concatenate(xs), np.concatenate(es, 1), np.concatenate(bs), graphs[-1][0] + 1
+
+
+def test_gnn_generic_graph_pyg_edge_cases_and_input_forms(dev):
+    """forward(x, edge_index, batch) against the fp64 oracle (add_remaining_self_loops, in-degree normalisation, mean pool) on
+    the edge-case batch above, randn features at the suite's 2e-5 bar.  Input forms must not change a bit: int32 edge_index /
+    batch, ids on the host, float64 x, a non-contiguous x.  Permuting the edge columns changes only the summation order.  And
+    the call reads the device once (the validation, sizes and graph count share one read)."""
+    import warnings
+    from oracle import gnn as og
+    params = _with_gcn_biases(og.init_params(1))
+    model = _net(params)
+    xn, en, bn, G = _pyg_edge_case_batch()
+    n = xn.shape[0]
+    assert n % 4 and n % 32
+    ref = og.forward_graph(params, xn, en, bn, G)
+    assert np.abs(ref["pooled"][4]).max() == 0.0         # the gap pools to zeros
+    x, ei, bt = torch.from_numpy(xn).float().to(dev), torch.from_numpy(en).to(dev), torch.from_numpy(bn).to(dev)
+    out = _generic(model, dev, x, ei, bt)
+    assert out[0].shape == (G, model.policy_output_size) and out[1].shape == (G, 1)
+    _assert_rows_close(out, ref, (2e-5, 1e-4), "edge cases")
+    xb = torch.zeros((n, 12), dtype=torch.float32, device=dev)
+    xb[:, 1::2] = x
+    forms = {"int32 edge_index": (x, ei.int(), bt), "int32 batch": (x, ei, bt.int()), "host ids": (x, ei.cpu(), bt.cpu()),
+             "float64 x": (torch.from_numpy(xn).to(dev), ei, bt), "non-contiguous x": (xb[:, 1::2], ei, bt)}
+    for name, args in forms.items():
+        got = _generic(model, dev, *args)
+        assert all(torch.equal(a, b) for a, b in zip(got, out)), name
+    perm = torch.from_numpy(np.random.RandomState(3).permutation(en.shape[1])).to(dev)
+    _assert_rows_close(_generic(model, dev, x, ei[:, perm].contiguous(), bt), ref, (2e-5, 1e-4), "permuted edges")
+    # one device-to-host read per call (weights already packed): counted by torch's sync debug mode, calibrated on a known read
+    torch.cuda.synchronize()
+    counts = []
+    for call in (lambda: torch.zeros(1, device=dev).item(), lambda: model(x, ei, bt)):
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            torch.cuda.set_sync_debug_mode("warn")          # (its own "prototype feature" notice is caught here too)
+            try:
+                call()
+            finally:
+                torch.cuda.set_sync_debug_mode("default")
+        counts.append(sum("called a synchronizing" in str(w.message) for w in caught))
+    assert counts == [1, 1], counts
+
+
+def test_gnn_generic_graph_empty_and_unsorted(dev):
+    """n = 0 gives (0, A) / (0, 1); an unsorted batch is refused with ValueError (GPU tensors, valid ids only)."""
+    from oracle import gnn as og
+    model = _net(og.init_params(1))
+    A = model.policy_output_size
+    policy, value = model(torch.zeros((0, 6), device=dev), torch.zeros((2, 0), dtype=torch.long, device=dev),
+                          torch.zeros(0, dtype=torch.long, device=dev))
+    assert policy.shape == (0, A) and value.shape == (0, 1)
+    with pytest.raises(ValueError):
+        model(torch.zeros((4, 6), device=dev), torch.tensor([[0, 1], [1, 2]], device=dev), torch.tensor([0, 1, 0, 1], device=dev))
+
+
+def test_gnn_generic_graph_board_batch_at_scale(dev):
+    """4,096 9x9 board graphs (331,776 nodes) through forward(x, edge_index, batch): every row against the fp64 oracle with
+    non-zero GCN biases (_walk_oracle(11)).  Then the nodes of every board relabelled and the edges remapped (and shuffled):
+    mean pooling makes the labels irrelevant, so the rows must still match."""
+    params, ref = _walk_oracle(11)
+    model = _net(params)
+    g = U.golden("walk_9x9.npz")
+    idx = np.random.RandomState(4096).randint(0, g["states"].shape[0], size=4096)
+    xn, en, bn = _board_graphs(g["states"][idx])
+    want = {k: ref[k][idx] for k in ("logits", "value_pre", "policy", "value")}
+    out = _generic(model, dev, torch.from_numpy(xn).float().to(dev), torch.from_numpy(en).to(dev), torch.from_numpy(bn).to(dev))
+    _assert_rows_close(out, want, (1e-5, 1e-4), "board graphs")
+    rng = np.random.RandomState(5)
+    relabel = np.concatenate([81 * b + rng.permutation(81) for b in range(len(idx))])
+    x2 = np.empty_like(xn)
+    x2[relabel] = xn
+    e2 = relabel[en][:, rng.permutation(en.shape[1])]
+    out2 = _generic(model, dev, torch.from_numpy(x2).float().to(dev), torch.from_numpy(e2).to(dev), torch.from_numpy(bn).to(dev))
+    _assert_rows_close(out2, want, (1e-5, 1e-4), "relabelled board graphs")
+
+
+def test_gnn_generic_graph_scaled_weights(dev):
+    """The x3 trunk weights with non-zero biases of test_gnn_forward_scaled_weights (activations O(10)) on the generic path."""
+    from oracle import gnn as og
+    params = og.init_params(3)
+    big = {k: (v * (3.0 if "gcn" in k and "weight" in k else 1.0)).astype(np.float32) for k, v in params.items()}
+    big["gcn_layers.1.bias"] = np.linspace(-0.5, 0.5, 128).astype(np.float32)
+    big["gcn_layers.2.bias"] = np.linspace(0.3, -0.3, 128).astype(np.float32)
+    model = _net(big)
+    recs = U.golden("walk_9x9.npz")["states"][5000:5064]
+    xn, en, bn = _board_graphs(recs)
+    out = _generic(model, dev, torch.from_numpy(xn).float().to(dev), torch.from_numpy(en).to(dev), torch.from_numpy(bn).to(dev))
+    _assert_rows_close(out, og.forward_states(big, recs), (2e-4, 2e-4), "x3 weights")
+
+
+# ------------------------------------------------------------------ the any-size board forward (3x3 / 5x5 / 7x7) and the engine's launch
+def _small_board_states(N):
+    """All reference-walk states at 3x3 (1,750) and 5x5 (4,666); 3,538 wall-heavy random-play states at 7x7 (no fixtures)."""
+    if N == 7:
+        return _wall_heavy_states(7, 60, 60, np.random.RandomState(17))
+    return U.golden(f"walk_{N}x{N}.npz")["states"]
+
+
+@pytest.mark.parametrize("N", [3, 5, 7])
+def test_gnn_small_boards_forward_vs_dense_oracle(dev, N):
+    """aqg_gcn_forward_boards_any on every state above against the fp64 oracle (non-zero GCN biases), LDS poisoned: logits,
+    value_pre, policy, value.  A row does not depend on the batch around it: batches of 1, 3, 33, 1,001 and a permuted batch give
+    the same bits.  x3 trunk weights at the 2e-4 bar."""
+    from oracle import gnn as og
+    from alphaquoridorgnn_amd import _lib
+    recs = _small_board_states(N)
+    assert recs.shape[0] >= 1750 and (recs[:, 1] != recs[:, 3]).sum() >= 100     # both players' wall counts differ somewhere
+    params = _with_gcn_biases(og.init_params(20 + N, N=N))
+    model = _net(params, N)
+    ref = og.forward_states_dense(params, recs)
+    d = torch.from_numpy(recs).to(dev)
+    _lib.poison_lds(dev)
+    out = model.forward_states(d, want_logits=True)
+    out = (out[0], out[1], out[2], out[3])
+    _assert_rows_close(out, ref, (1e-5, 1e-4), f"{N}x{N}")
+    for B in (1, 3, 33, 1001):
+        _lib.poison_lds(dev)
+        got = model.forward_states(d[:B].contiguous(), want_logits=True)
+        assert all(torch.equal(a, b[:B]) for a, b in zip(got, out)), B
+    perm = torch.from_numpy(np.random.RandomState(N).permutation(recs.shape[0])).to(dev)
+    _lib.poison_lds(dev)
+    got = model.forward_states(d[perm].contiguous(), want_logits=True)
+    assert all(torch.equal(a, b[perm]) for a, b in zip(got, out)), "permuted"
+    big = {k: (v * (3.0 if "gcn" in k and "weight" in k else 1.0)).astype(np.float32) for k, v in params.items()}
+    model = _net(big, N)
+    sub = recs[::7]
+    _lib.poison_lds(dev)
+    got = model.forward_states(torch.from_numpy(sub).to(dev), want_logits=True)
+    _assert_rows_close(got, og.forward_states_dense(big, sub), (2e-4, 2e-4), f"{N}x{N} x3 weights")
+
+
+@pytest.mark.parametrize("N,cache", [(3, None), (5, None), (7, None), (5, 64)])
+def test_engine_masked_small_board_launch(dev, N, cache):
+    """test_engine_masked_trunk_launch on the any-size forward: 1,000 roots of which ~35 % are terminal, one simulation, the
+    engine's 24-byte packed leaf states and its mask (leaf_flag; eval_mask with the evaluation cache on).  Masked rows keep the
+    sentinel in pooled, policy and value; live rows equal the mask-free forward of the same packed states bit for bit and the
+    fp64 oracle within the tolerance."""
+    from alphaquoridorgnn_amd.engine import BatchedSelfPlay
+    from alphaquoridorgnn_amd import _lib
+    from oracle import gnn as og
+    params = _with_gcn_biases(og.init_params(30 + N, N=N))
+    model = _net(params, N)
+    G = 1000
+    pool = _small_board_states(N)
+    rng = np.random.RandomState(77 + N)
+    recs = pool[rng.randint(0, pool.shape[0], size=G)].copy()
+    dead = rng.rand(G) < 0.35
+    dead[:3] = [True, False, True]
+    recs[dead, 2] = recs[dead, 2] % N                     # enemy pawn onto row 0 of its own frame: is_lose()
+    ref = og.forward_states_dense(params, recs[~dead])
+    eng = BatchedSelfPlay(model, num_games=G, sims=1, board_size=N, record_history=False, eval_cache_slots=cache)
+    for name in ("pooled", "policy", "value"):
+        eng.t[name].fill_(-7.25)
+    _lib.poison_lds(dev)
+    eng.search(recs)
+    torch.cuda.synchronize()
+    live = torch.from_numpy(~dead).to(dev)
+    assert int(eng.t["stat_leaf_evals"].sum()) == int((~dead).sum())
+    for name in ("pooled", "policy", "value"):
+        assert bool((eng.t[name][~live] == -7.25).all()), name
+    policy, value = model.forward_states(eng.t["leaf_state"][live].contiguous(), state_fmt=1)
+    assert torch.equal(eng.t["policy"][live], policy) and torch.equal(eng.t["value"][live], value[:, 0])
+    np.testing.assert_allclose(eng.t["policy"][live].cpu().numpy(), ref["policy"], atol=1e-6, rtol=1e-4)
+    np.testing.assert_allclose(eng.t["value"][live].cpu().numpy(), ref["value"], atol=1e-5, rtol=1e-4)
+    np.testing.assert_allclose(eng.t["pooled"][live].cpu().numpy(), ref["pooled"], atol=2e-6, rtol=1e-4)
+
+
+@pytest.mark.parametrize("N", [5, 7])
+def test_engine_priors_and_visits_vs_oracle_gnn_small_boards(dev, N):
+    """test_engine_priors_and_visits_vs_oracle_gnn below 9x9: root priors inside the engine equal OracleModel.predict to 1e-6
+    in legal_actions() order, and a 10-simulation search distributes its visits exactly like oracle.mcts with that model."""
+    from alphaquoridorgnn_amd.engine import BatchedSelfPlay
+    from oracle import gnn as og, mcts as om, quoridor as oq
+    params = og.init_params(40 + N, N=N)
+    model = _net(params, N)
+    oracle = og.OracleModel(params)
+    pool = _small_board_states(N)
+    recs = pool[np.linspace(0, pool.shape[0] - 1, 8).astype(int)]
+    recs = recs[[not oq.State(r).is_done() for r in recs]]
+    sims = 10
+    eng = BatchedSelfPlay(model, num_games=recs.shape[0], sims=sims, board_size=N, record_history=False)
+    eng.search(recs)
+    torch.cuda.synchronize()
+    for rec, (pri, vis, act) in zip(recs, _root_children(eng)):
+        st = oq.State(rec)
+        legal = st.legal_actions()
+        assert [int(a) for a in act] == [int(a) for a in legal]
+        want, _ = oracle.predict(st)
+        np.testing.assert_allclose(pri, want, atol=1e-6, rtol=1e-5)
+        root = om.search(oracle, st, sims)
+        assert [int(v) for v in vis] == [c.n for c in root.children]
 
 
 def test_predict_contract(dev):

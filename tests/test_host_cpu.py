@@ -484,3 +484,135 @@ def test_set_option_names_ranges_and_errors():
     assert lib.aqg_set_option(b"no_such_option", 1) != 0 and b"no_such_option" in lib.aqg_last_error()
     with pytest.raises(RuntimeError):
         _lib.set_option("no_such_option", 1)
+
+
+# ------------------------------------------------------------------ generic GNN operator: graph preparation (PyG's gcn_norm)
+def _dense_gcn_norm(n, edge_index):
+    """A third statement of GCNConv's normalised adjacency, independent of pv_network_gnn and oracle/gnn.py (fp64):
+    A_hat = D^-1/2 (C + I) D^-1/2 with C[i, j] = number of non-loop edges j -> i and D the row sums of C + I."""
+    C = np.zeros((n, n))
+    for j, i in np.asarray(edge_index, dtype=np.int64).T:
+        if i != j:
+            C[i, j] += 1.0
+    M = C + np.eye(n)
+    d = M.sum(1) ** -0.5
+    return d[:, None] * M * d[None, :]
+
+
+def _gcn_norm_graphs():
+    """(name, num_nodes, edge_index [2, E] int64): the places where gcn_norm implementations differ."""
+    rng = np.random.RandomState(21)
+    ring = [[0, 1, 2, 3], [1, 2, 3, 0]]
+    cases = [(f"{k}_loops", 4, np.asarray([ring[0] + [0] * k, ring[1] + [0] * k])) for k in range(4)]
+    cases.append(("issue_example", 3, np.asarray([[0, 0, 1, 2], [0, 0, 0, 1]])))
+    cases.append(("repeated_edges", 4, np.asarray([[0, 0, 0, 1, 1, 3, 2], [1, 1, 1, 2, 2, 0, 2]])))
+    cases.append(("directed_random", 12, rng.randint(0, 12, size=(2, 40))))          # asymmetric, repeats and loops included
+    cases.append(("isolated_nodes", 7, np.asarray([[0, 1, 2], [1, 2, 0]])))
+    cases.append(("no_edges", 5, np.zeros((2, 0), dtype=np.int64)))
+    cases.append(("single_node", 1, np.zeros((2, 0), dtype=np.int64)))
+    cases.append(("single_node_two_loops", 1, np.zeros((2, 2), dtype=np.int64)))
+    star = np.arange(1, 3001)
+    cases.append(("star_3000", 3001, np.stack([np.concatenate([star, [0, 5]]), np.concatenate([np.zeros(3000, np.int64), [7, 5]])])))
+    return cases
+
+
+def _csr_to_dense(n, ptr, src, w):
+    A = np.zeros((n, n))
+    for i in range(n):
+        for e in range(ptr[i], ptr[i + 1]):
+            A[i, src[e]] += w[e]
+    return A
+
+
+@pytest.mark.parametrize("dtype", [torch.int64, torch.int32], ids=["int64", "int32"])
+@pytest.mark.parametrize("case", _gcn_norm_graphs(), ids=lambda c: c[0])
+def test_generic_graph_gcn_norm_matches_dense_statement(case, dtype):
+    """GraphPolicyValueNetwork._prepare_graph (the host half of forward(x, edge_index, batch), on CPU tensors) and
+    oracle.gnn.gcn_conv both against the dense A_hat above: repeated self loops count once (add_remaining_self_loops),
+    repeated non-loop edges each count, degrees are in-degrees (flow source_to_target).  The CSR is grouped by destination,
+    its pointer monotone, ending at E_nonloop + n, and each node's entries are its non-loop sources plus itself."""
+    from alphaquoridorgnn_amd.pv_network_gnn import GraphPolicyValueNetwork
+    from oracle import gnn as og
+    name, n, ei = case
+    want = _dense_gcn_norm(n, ei)
+    x = torch.zeros((n, 6))
+    ptr, src, w, gptr, G = GraphPolicyValueNetwork._prepare_graph(x, torch.from_numpy(ei).to(dtype), torch.zeros(n, dtype=torch.long))
+    assert ptr.dtype == src.dtype == gptr.dtype == torch.int32 and w.dtype == torch.float32, name
+    ptr, src, w = ptr.numpy().astype(np.int64), src.numpy().astype(np.int64), w.numpy().astype(np.float64)
+    nonloop = ei[0] != ei[1]
+    assert ptr[0] == 0 and (np.diff(ptr) >= 1).all() and ptr[-1] == nonloop.sum() + n == len(src) == len(w), name
+    for i in range(n):
+        into = ei[0][nonloop & (ei[1] == i)]
+        assert sorted(src[ptr[i]:ptr[i + 1]]) == sorted(list(into) + [i]), (name, i)
+    np.testing.assert_allclose(_csr_to_dense(n, ptr, src, w), want, rtol=3e-7, atol=0, err_msg=name)
+    assert G == 1 and gptr.tolist() == [0, n], name
+    # the oracle's GCNConv on random features with an identity lin: A_hat @ x to fp64 rounding
+    xr = np.random.RandomState(n).randn(n, 4)
+    got = og.gcn_conv(xr, ei.astype(np.int64) if dtype == torch.int64 else ei.astype(np.int32), np.eye(4), np.zeros(4))
+    np.testing.assert_allclose(got, want @ xr, rtol=1e-12, atol=1e-12, err_msg=name)
+
+
+def test_generic_graph_pyg_self_loop_rule_by_hand():
+    """The issue's worked example: edges 0->0 (twice), 1->0, 2->1.  PyG keeps one loop on node 0, so deg = (2, 2, 1) and the
+    self weight of node 0 is 1/2 -- not 2/3 (two loops of 1/3), which keeping both loops would give."""
+    from alphaquoridorgnn_amd.pv_network_gnn import GraphPolicyValueNetwork
+    ptr, src, w, _, _ = GraphPolicyValueNetwork._prepare_graph(torch.zeros((3, 6)), torch.tensor([[0, 0, 1, 2], [0, 0, 0, 1]]),
+                                                               torch.zeros(3, dtype=torch.long))
+    assert ptr.tolist() == [0, 2, 4, 5] and src.tolist() == [1, 0, 2, 1, 2]
+    np.testing.assert_allclose(w.numpy(), [0.5, 0.5, 0.5 ** 0.5, 0.5, 1.0], rtol=1e-7)   # 1->0, 0->0, 2->1, 1->1, 2->2
+
+
+def test_generic_graph_batch_pointer_and_gaps():
+    """gptr / G from a sorted batch: a graph id without nodes (a gap) gets an empty range, G = max id + 1; empty input -> G = 0."""
+    from alphaquoridorgnn_amd.pv_network_gnn import GraphPolicyValueNetwork
+    batch = torch.tensor([0, 0, 0, 2, 2, 3, 5], dtype=torch.int32)
+    ptr, src, w, gptr, G = GraphPolicyValueNetwork._prepare_graph(torch.zeros((7, 6), dtype=torch.float64),
+                                                                  torch.tensor([[0, 1], [1, 0]], dtype=torch.int32), batch)
+    assert G == 6 and gptr.tolist() == [0, 3, 3, 5, 6, 6, 7]
+    ptr, src, w, gptr, G = GraphPolicyValueNetwork._prepare_graph(torch.zeros((0, 6)), torch.zeros((2, 0), dtype=torch.long),
+                                                                  torch.zeros(0, dtype=torch.long))
+    assert G == 0 and gptr.tolist() == [0] and ptr.tolist() == [0] and src.numel() == 0 and w.numel() == 0
+
+
+@pytest.mark.parametrize("bad", ["negative_id", "id_eq_n", "id_gt_n", "batch_length", "batch_negative", "batch_unsorted",
+                                 "x_5_cols", "x_7_cols", "x_1d", "x_int", "edge_index_3_rows", "edge_index_1d", "edge_index_float",
+                                 "batch_float", "batch_2d"])
+def test_generic_graph_rejects_invalid_inputs(bad):
+    """Every input the hand-written gather must never see is refused on the host with ValueError, before any tensor is indexed with
+    the ids: a negative id would otherwise wrap (Python-style indexing) into a CSR entry reading before the buffer, an id >= n
+    would read past it.  CPU tensors only -- these inputs are never sent to a GPU."""
+    from alphaquoridorgnn_amd.pv_network_gnn import GraphPolicyValueNetwork
+    n = 5
+    x, ei, batch = torch.zeros((n, 6)), torch.tensor([[0, 1, 2, 3], [1, 2, 3, 4]]), torch.tensor([0, 0, 1, 1, 1])
+    if bad == "negative_id":
+        ei = torch.tensor([[0, -1], [1, 0]])
+    elif bad == "id_eq_n":
+        ei = torch.tensor([[0, 1], [n, 0]])
+    elif bad == "id_gt_n":
+        ei = torch.tensor([[0, 1000], [1, 0]], dtype=torch.int32)
+    elif bad == "batch_length":
+        batch = torch.tensor([0, 0, 1, 1])
+    elif bad == "batch_negative":
+        batch = torch.tensor([-1, 0, 0, 1, 1])
+    elif bad == "batch_unsorted":
+        batch = torch.tensor([0, 1, 0, 1, 1])
+    elif bad == "x_5_cols":
+        x = torch.zeros((n, 5))
+    elif bad == "x_7_cols":
+        x = torch.zeros((n, 7))
+    elif bad == "x_1d":
+        x = torch.zeros(n * 6)
+    elif bad == "x_int":
+        x = torch.zeros((n, 6), dtype=torch.int64)
+    elif bad == "edge_index_3_rows":
+        ei = torch.tensor([[0, 1], [1, 2], [2, 3]])
+    elif bad == "edge_index_1d":
+        ei = torch.tensor([0, 1, 1, 2])
+    elif bad == "edge_index_float":
+        ei = ei.float()
+    elif bad == "batch_float":
+        batch = batch.float()
+    elif bad == "batch_2d":
+        batch = batch[None]
+    with pytest.raises(ValueError):
+        GraphPolicyValueNetwork._prepare_graph(x, ei, batch)
