@@ -39,6 +39,16 @@ int launch_gcn_forward_graph(int F, int A, const float* x, int num_nodes, const 
                              const float* csr_w, const int32_t* graph_ptr, int num_graphs, const float* packed,
                              float* work0, float* work1, float* pooled, float* logits, float* policy, float* value_pre,
                              float* value, hipStream_t st);
+int launch_gcn_forward_graph_saved(int F, int A, const float* x, int num_nodes, const int32_t* csr_ptr, const int32_t* csr_src,
+                                   const float* csr_w, const int32_t* graph_ptr, int num_graphs, const float* packed,
+                                   float* work0, float* h1, float* h2, float* h3, float* pooled, float* logits, float* policy,
+                                   float* value_pre, float* value, hipStream_t st);
+size_t graph_backward_workspace_floats(int n, int G);
+int launch_gcn_backward_graph(int F, int A, const float* x, int n, const float* h1, const float* h2, const float* h3,
+                              const int32_t* tptr, const int32_t* tdst, const float* tw, const int32_t* gptr, int G,
+                              const float* pooled, const float* policy, const float* value, const float* dpolicy,
+                              const float* dvalue, const float* const* params, float* workspace, size_t workspace_floats,
+                              float* const* grads, float* dx, hipStream_t st);
 int engine_reset(const aqg_engine& e, hipStream_t st);
 int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st);
 int engine_begin_move(const aqg_engine& e, hipStream_t st);
@@ -149,6 +159,42 @@ int aqg_gcn_forward_graph(int num_features, int num_actions, const float* x, int
         return fail("aqg_gcn_forward_graph: null argument");
     return launch_gcn_forward_graph(num_features, num_actions, x, num_nodes, csr_ptr, csr_src, csr_w, graph_ptr, num_graphs,
                                     packed, work0, work1, pooled, logits, policy, value_pre, value, (hipStream_t)stream);
+}
+
+int aqg_gcn_forward_graph_saved(int num_features, int num_actions, const float* x, int num_nodes, const int32_t* csr_ptr,
+                                const int32_t* csr_src, const float* csr_w, const int32_t* graph_ptr, int num_graphs,
+                                const float* packed, float* work0, float* h1, float* h2, float* h3, float* pooled, float* logits,
+                                float* policy, float* value_pre, float* value, void* stream) {
+    if (num_nodes < 0 || num_graphs < 0) return fail("aqg_gcn_forward_graph_saved: negative size");
+    if (num_nodes == 0) return 0;
+    if (!x || !csr_ptr || !csr_src || !csr_w || !graph_ptr || !packed || !work0 || !h1 || !h2 || !h3 || !pooled)
+        return fail("aqg_gcn_forward_graph_saved: null argument");
+    return launch_gcn_forward_graph_saved(num_features, num_actions, x, num_nodes, csr_ptr, csr_src, csr_w, graph_ptr, num_graphs,
+                                          packed, work0, h1, h2, h3, pooled, logits, policy, value_pre, value, (hipStream_t)stream);
+}
+
+size_t aqg_gcn_backward_graph_workspace_floats(int num_nodes, int num_graphs) {
+    return graph_backward_workspace_floats(num_nodes, num_graphs);
+}
+
+int aqg_gcn_backward_graph(int num_features, int num_actions, const float* x, int num_nodes, const float* h1, const float* h2,
+                           const float* h3, const int32_t* tcsr_ptr, const int32_t* tcsr_dst, const float* tcsr_w,
+                           const int32_t* graph_ptr, int num_graphs, const float* pooled, const float* policy, const float* value,
+                           const float* dpolicy, const float* dvalue, const float* const* params_host, float* workspace,
+                           size_t workspace_floats, float* const* grads_host, float* dx, void* stream) {
+    if (num_nodes < 0 || num_graphs < 0) return fail("aqg_gcn_backward_graph: negative size");
+    if (!params_host || !grads_host) return fail("aqg_gcn_backward_graph: null parameter array");
+    for (int i = 0; i < 14; ++i)
+        if (!params_host[i] || !grads_host[i]) return fail("aqg_gcn_backward_graph: null parameter tensor");
+    if (num_nodes > 0 && num_graphs > 0) {
+        if (!x || !h1 || !h2 || !h3 || !tcsr_ptr || !tcsr_dst || !tcsr_w || !graph_ptr || !pooled || !workspace)
+            return fail("aqg_gcn_backward_graph: null argument");
+        if (dpolicy && !policy) return fail("aqg_gcn_backward_graph: dpolicy needs policy");
+        if (dvalue && !value) return fail("aqg_gcn_backward_graph: dvalue needs value");
+    }
+    return launch_gcn_backward_graph(num_features, num_actions, x, num_nodes, h1, h2, h3, tcsr_ptr, tcsr_dst, tcsr_w, graph_ptr,
+                                     num_graphs, pooled, policy, value, dpolicy, dvalue, params_host, workspace, workspace_floats,
+                                     grads_host, dx, (hipStream_t)stream);
 }
 
 int aqg_engine_reset(const aqg_engine* e, void* stream) {

@@ -1832,30 +1832,50 @@ __global__ __launch_bounds__(128) void graph_pool_kernel(const float* __restrict
     pooled[(size_t)g * HID + threadIdx.x] = (b > a) ? s / (float)(b - a) : 0.f;
 }
 
-int launch_gcn_forward_graph(int F, int A, const float* x, int num_nodes, const int32_t* csr_ptr, const int32_t* csr_src,
-                             const float* csr_w, const int32_t* graph_ptr, int num_graphs, const float* packed,
-                             float* work0, float* work1, float* pooled, float* logits, float* policy, float* value_pre,
-                             float* value, hipStream_t st) {
+// Layer l's output goes to out[l-1]: the eval path passes work1 three times (ping-pong with work0), the recording path of
+// autograd (aqg_gcn_forward_graph_saved) three separate buffers H1, H2, H3 its backward reads.  Same kernels, same values.
+static int graph_forward(int F, int A, const float* x, int num_nodes, const int32_t* csr_ptr, const int32_t* csr_src,
+                         const float* csr_w, const int32_t* graph_ptr, int num_graphs, const float* packed, float* work0,
+                         float* const out[3], float* pooled, float* logits, float* policy, float* value_pre, float* value,
+                         hipStream_t st) {
     if (F != 6) return fail("num_features must be 6 (NUM_FEATURES pv_network_gnn.py:17)");
     if (A > 248) return fail("policy size exceeds 248");
     if (num_nodes <= 0 || num_graphs <= 0) return 0;
     dim3 lg((num_nodes + 31) / 32), gg((num_nodes + 3) / 4);
     hipLaunchKernelGGL(graph_linear_kernel<true>, lg, dim3(256), 0, st, x, F, num_nodes, packed + PackedLayout::W1, work0);
     hipLaunchKernelGGL(graph_gather_kernel, gg, dim3(256), 0, st, (const float*)work0, num_nodes, csr_ptr, csr_src, csr_w,
-                       packed + PackedLayout::B1, work1);
-    hipLaunchKernelGGL(graph_linear_kernel<false>, lg, dim3(256), 0, st, (const float*)work1, HID, num_nodes,
+                       packed + PackedLayout::B1, out[0]);
+    hipLaunchKernelGGL(graph_linear_kernel<false>, lg, dim3(256), 0, st, (const float*)out[0], HID, num_nodes,
                        packed + PackedLayout::W2T, work0);
     hipLaunchKernelGGL(graph_gather_kernel, gg, dim3(256), 0, st, (const float*)work0, num_nodes, csr_ptr, csr_src, csr_w,
-                       packed + PackedLayout::B2, work1);
-    hipLaunchKernelGGL(graph_linear_kernel<false>, lg, dim3(256), 0, st, (const float*)work1, HID, num_nodes,
+                       packed + PackedLayout::B2, out[1]);
+    hipLaunchKernelGGL(graph_linear_kernel<false>, lg, dim3(256), 0, st, (const float*)out[1], HID, num_nodes,
                        packed + PackedLayout::W3T, work0);
     hipLaunchKernelGGL(graph_gather_kernel, gg, dim3(256), 0, st, (const float*)work0, num_nodes, csr_ptr, csr_src, csr_w,
-                       packed + PackedLayout::B3, work1);
-    hipLaunchKernelGGL(graph_pool_kernel, dim3(num_graphs), dim3(128), 0, st, (const float*)work1, graph_ptr, num_graphs, pooled);
+                       packed + PackedLayout::B3, out[2]);
+    hipLaunchKernelGGL(graph_pool_kernel, dim3(num_graphs), dim3(128), 0, st, (const float*)out[2], graph_ptr, num_graphs, pooled);
     if (int r = check_launch("graph kernels")) return r;
     hipLaunchKernelGGL(gcn_heads_kernel, dim3((num_graphs + HB - 1) / HB), dim3(256), 0, st, (const float*)pooled, num_graphs, A,
                        packed, logits, policy, value_pre, value, (const uint8_t*)nullptr);
     return check_launch("gcn_heads_kernel");
+}
+
+int launch_gcn_forward_graph(int F, int A, const float* x, int num_nodes, const int32_t* csr_ptr, const int32_t* csr_src,
+                             const float* csr_w, const int32_t* graph_ptr, int num_graphs, const float* packed,
+                             float* work0, float* work1, float* pooled, float* logits, float* policy, float* value_pre,
+                             float* value, hipStream_t st) {
+    float* const out[3] = {work1, work1, work1};
+    return graph_forward(F, A, x, num_nodes, csr_ptr, csr_src, csr_w, graph_ptr, num_graphs, packed, work0, out, pooled, logits,
+                         policy, value_pre, value, st);
+}
+
+int launch_gcn_forward_graph_saved(int F, int A, const float* x, int num_nodes, const int32_t* csr_ptr, const int32_t* csr_src,
+                                   const float* csr_w, const int32_t* graph_ptr, int num_graphs, const float* packed,
+                                   float* work0, float* h1, float* h2, float* h3, float* pooled, float* logits, float* policy,
+                                   float* value_pre, float* value, hipStream_t st) {
+    float* const out[3] = {h1, h2, h3};
+    return graph_forward(F, A, x, num_nodes, csr_ptr, csr_src, csr_w, graph_ptr, num_graphs, packed, work0, out, pooled, logits,
+                         policy, value_pre, value, st);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -244,7 +244,7 @@ class GraphPolicyValueNetwork(nn.Module):
 
     # ---------------------------------------------------------------- generic (x, edge_index, batch) path
     @staticmethod
-    def _prepare_graph(x, edge_index, batch):
+    def _prepare_graph(x, edge_index, batch, transpose=False):
         """Everything forward(x, edge_index, batch) does before its launch, on x's device (CPU or GPU alike):
         validation, PyG's gcn_norm as a CSR by destination, and the graph pointer of the mean pool.
 
@@ -257,7 +257,10 @@ class GraphPolicyValueNetwork(nn.Module):
         (flow source_to_target, the self loop included, so deg >= 1), w_e = deg[src]^-1/2 * deg[dst]^-1/2.
         Returns (ptr int32 [n+1], src int32 [E_nonloop+n], w float32 [E_nonloop+n], gptr int32 [G+1], G): the edges into
         node i are ptr[i] .. ptr[i+1] (its incoming edges in input order, then its self loop), graph g holds the nodes
-        gptr[g] .. gptr[g+1] and G = batch.max() + 1 (a graph id without nodes pools to 0, as in PyG)."""
+        gptr[g] .. gptr[g+1] and G = batch.max() + 1 (a graph id without nodes pools to 0, as in PyG).
+        transpose=True (the recording forward of autograd) appends the same entries as a CSR by SOURCE, (tptr int32 [n+1],
+        tdst int32, tw float32): the entries leaving node j are tptr[j] .. tptr[j+1], in their order above (a stable sort),
+        built on the device without another host read."""
         def integral(t):
             return not (t.is_floating_point() or t.is_complex() or t.dtype == torch.bool)
         if x.dim() != 2 or x.shape[1] != NUM_FEATURES or not x.is_floating_point():
@@ -299,13 +302,30 @@ class GraphPolicyValueNetwork(nn.Module):
         dis = (ptr[1:] - ptr[:-1]).to(torch.float32).pow(-0.5)
         w = dis[src] * dis[dst]
         gptr = torch.searchsorted(batch, torch.arange(G + 1, device=dev)).to(torch.int32)
-        return ptr, src.to(torch.int32).contiguous(), w.contiguous(), gptr, G
+        if not transpose:
+            return ptr, src.to(torch.int32).contiguous(), w.contiguous(), gptr, G
+        torder = torch.argsort(src, stable=True)
+        tptr = torch.searchsorted(src[torder], torch.arange(n + 1, device=dev)).to(torch.int32)
+        return (ptr, src.to(torch.int32).contiguous(), w.contiguous(), gptr, G,
+                tptr, dst[torder].to(torch.int32).contiguous(), w[torder].contiguous())
 
     def forward(self, x, edge_index, batch):
         """pv_network_gnn.py:53-64 with PyG's GCNConv / global_mean_pool semantics (_prepare_graph: the self-loop rule and the
         validated inputs).  x [sum V, 6] floating point, edge_index [2, E] integer ids in [0, sum V), batch [sum V] integer,
-        non-negative and sorted (unsorted raises ValueError).  One device-to-host read per call once the weights are packed."""
+        non-negative and sorted (unsorted raises ValueError).  One device-to-host read per call once the weights are packed.
+
+        Autograd: in train mode, with grad enabled and x or any parameter requiring grad, the forward is recorded
+        (_GraphForward): the outputs carry a grad_fn and backward() fills the parameters' .grad (and x.grad) from HIP
+        kernels (csrc/gcn_graph_grad.hip).  Its values are bit-identical to the plain forward's.  Otherwise (eval mode,
+        no_grad, inference_mode) the outputs carry no graph."""
         dev = _lib.require_gpu(x.device)
+        params = [p for _, p in self._ordered_params()]
+        if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+            tensors = self._prepare_graph(x, edge_index, batch, transpose=True)
+            xf = x.to(torch.float32).contiguous()            # outside the Function: torch routes x's gradient through the cast
+            policy, value, logits, vpre = _GraphForward.apply(self, tensors, dev, xf, *params)
+            self.last_logits, self.last_value_pre = logits, vpre
+            return policy, value.unsqueeze(1)
         lib = _lib.load()
         ptr, csr_src, csr_w, gptr, G = self._prepare_graph(x, edge_index, batch)
         x = x.to(torch.float32).contiguous()
@@ -323,6 +343,72 @@ class GraphPolicyValueNetwork(nn.Module):
                                                  _lib.stream_ptr(dev)), "aqg_gcn_forward_graph")
         self.last_logits, self.last_value_pre = logits, vpre
         return policy, value.unsqueeze(1)
+
+    def _ordered_params(self):
+        sd = dict(self.named_parameters())
+        return [(k, sd[k]) for k in STATE_DICT_KEYS]
+
+
+class _GraphForward(torch.autograd.Function):
+    """forward(x, edge_index, batch) as one autograd node: the plain forward's kernels with H1, H2, H3 kept
+    (aqg_gcn_forward_graph_saved), and aqg_gcn_backward_graph for the gradients of the 14 parameters and of x.
+    Neither direction reads anything back to the host."""
+
+    @staticmethod
+    def forward(ctx, model, tensors, dev, xf, *params):
+        ptr, csr_src, csr_w, gptr, G, tptr, tdst, tw = tensors
+        lib = _lib.load()
+        n, A = xf.shape[0], model.policy_output_size
+        f32 = dict(dtype=torch.float32, device=dev)
+        h = [torch.empty((n, HIDDEN_DIM), **f32) for _ in range(3)]
+        pooled = torch.empty((G, HIDDEN_DIM), **f32)
+        policy, value = torch.empty((G, A), **f32), torch.empty((G,), **f32)
+        logits, vpre = torch.empty((G, A), **f32), torch.empty((G,), **f32)
+        if n:
+            work = torch.empty((n, HIDDEN_DIM), **f32)
+            _lib.check(lib.aqg_gcn_forward_graph_saved(NUM_FEATURES, A, _lib.ptr(xf), n, _lib.ptr(ptr), _lib.ptr(csr_src),
+                                                       _lib.ptr(csr_w), _lib.ptr(gptr), G, _lib.ptr(model.packed_weights(dev)),
+                                                       _lib.ptr(work), _lib.ptr(h[0]), _lib.ptr(h[1]), _lib.ptr(h[2]),
+                                                       _lib.ptr(pooled), _lib.ptr(logits), _lib.ptr(policy), _lib.ptr(vpre),
+                                                       _lib.ptr(value), _lib.stream_ptr(dev)), "aqg_gcn_forward_graph_saved")
+        ctx.save_for_backward(xf, policy, value, *params)
+        ctx.graph = (tptr, tdst, tw, gptr, G, A, dev)
+        ctx.acts = (h, pooled)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(logits, vpre)
+        return policy, value, logits, vpre
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dpolicy, dvalue, _dlogits, _dvpre):
+        xf, policy, value, *params = ctx.saved_tensors
+        tptr, tdst, tw, gptr, G, A, dev = ctx.graph
+        h, pooled = ctx.acts
+        lib = _lib.load()
+        n = xf.shape[0]
+        pf = [p.detach().to(device=dev, dtype=torch.float32).contiguous() for p in params]
+        grads = [torch.empty_like(p) for p in pf]
+        want_dx = ctx.needs_input_grad[3]
+        dx = torch.empty((n, NUM_FEATURES), dtype=torch.float32, device=dev) if want_dx and n else None
+        dp = dpolicy.to(torch.float32).contiguous() if dpolicy is not None else None
+        dv = dvalue.to(torch.float32).contiguous() if dvalue is not None else None
+        nws = int(lib.aqg_gcn_backward_graph_workspace_floats(n, G))
+        ws = torch.empty((nws,), dtype=torch.float32, device=dev) if nws else None
+        arr = lambda ts: (ctypes.c_void_p * 14)(*[ctypes.c_void_p(t.data_ptr()) for t in ts])
+        if n == 0:
+            for g in grads:
+                g.zero_()
+        else:
+            _lib.check(lib.aqg_gcn_backward_graph(NUM_FEATURES, A, _lib.ptr(xf), n, _lib.ptr(h[0]), _lib.ptr(h[1]), _lib.ptr(h[2]),
+                                                  _lib.ptr(tptr), _lib.ptr(tdst), _lib.ptr(tw), _lib.ptr(gptr), G, _lib.ptr(pooled),
+                                                  _lib.ptr(policy), _lib.ptr(value), _lib.ptr(dp), _lib.ptr(dv), arr(pf),
+                                                  _lib.ptr(ws), nws, arr(grads), _lib.ptr(dx), _lib.stream_ptr(dev)),
+                       "aqg_gcn_backward_graph")
+        if want_dx and n == 0:
+            dx = torch.zeros((0, NUM_FEATURES), dtype=torch.float32, device=dev)
+        out = [g if ctx.needs_input_grad[4 + i] else None for i, g in enumerate(grads)]
+        out = [o.to(params[i].dtype) if o is not None else None for i, o in enumerate(out)]
+        return (None, None, None, dx if want_dx else None, *out)
 
 
 class GNNNetwork(GraphPolicyValueNetwork):

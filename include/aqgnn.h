@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define AQG_MAX_LEGAL 136 /* >= 5 pawn moves + 128 wall placements */
-#define AQG_ABI_VERSION 10
+#define AQG_ABI_VERSION 11
 
 int aqg_abi_version(void);
 const char* aqg_last_error(void);
@@ -163,6 +163,31 @@ int aqg_gcn_forward_graph(int num_features, int num_actions, const float* x, int
                           const int32_t* graph_ptr, int num_graphs, const float* packed, float* work0,
                           float* work1, float* pooled, float* logits, float* policy, float* value_pre,
                           float* value, void* stream);
+
+/* Autograd through forward(x, edge_index, batch) (GraphPolicyValueNetwork in train mode; ABI 11).
+ * aqg_gcn_forward_graph_saved: aqg_gcn_forward_graph with the three post-ReLU GCN outputs written to h1, h2, h3
+ *   [num_nodes,128] f32 (kept for the backward) instead of the work0/work1 ping-pong; work0 [num_nodes,128] f32 scratch.
+ *   The same kernels run in the same order: every output is bit-identical to aqg_gcn_forward_graph's.
+ * aqg_gcn_backward_graph: gradients of a loss with respect to the 14 parameters (and x) given dpolicy [G,A] and dvalue [G]
+ *   (either may be NULL = zero).  Inputs are the forward's x [n,6], h1..h3, pooled [G,128], policy [G,A], value [G]; the
+ *   normalised adjacency as a CSR by SOURCE: the entries leaving node j are tcsr_ptr[j] .. tcsr_ptr[j+1] with destination
+ *   tcsr_dst and weight tcsr_w (the forward's (src, dst, w) entries regrouped); graph_ptr as in the forward.
+ *   params_host / grads_host: HOST arrays of 14 DEVICE pointers in state_dict order (gcn_layers.0.lin.weight, .bias, ...,
+ *   value_head.2.bias; [out,in] weights), f32 contiguous; grads are overwritten, not accumulated.  dx [n,6] may be NULL.
+ *   workspace: aqg_gcn_backward_graph_workspace_floats(num_nodes, num_graphs) floats.  No atomics: the result is a
+ *   deterministic function of the inputs.  num_nodes == 0 writes zero gradients. */
+size_t aqg_gcn_backward_graph_workspace_floats(int num_nodes, int num_graphs);
+int aqg_gcn_forward_graph_saved(int num_features, int num_actions, const float* x, int num_nodes,
+                                const int32_t* csr_ptr, const int32_t* csr_src, const float* csr_w,
+                                const int32_t* graph_ptr, int num_graphs, const float* packed, float* work0,
+                                float* h1, float* h2, float* h3, float* pooled, float* logits, float* policy,
+                                float* value_pre, float* value, void* stream);
+int aqg_gcn_backward_graph(int num_features, int num_actions, const float* x, int num_nodes, const float* h1,
+                           const float* h2, const float* h3, const int32_t* tcsr_ptr, const int32_t* tcsr_dst,
+                           const float* tcsr_w, const int32_t* graph_ptr, int num_graphs, const float* pooled,
+                           const float* policy, const float* value, const float* dpolicy, const float* dvalue,
+                           const float* const* params_host, float* workspace, size_t workspace_floats,
+                           float* const* grads_host, float* dx, void* stream);
 
 /* ------------------------------------------------------------------ batched PV-MCTS self-play (pv_mcts.py, self_play.py) */
 
