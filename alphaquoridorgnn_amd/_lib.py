@@ -14,7 +14,7 @@ MAX_LEGAL = 136
 GNN_EXACT_F32 = 1        # AQG_GNN_EXACT_F32 (include/aqgnn.h)
 GNN_RANGE_PROVEN = 2     # AQG_GNN_RANGE_PROVEN
 GNN_PROVEN_MAX_WALLS = 16
-ABI_VERSION = 11
+ABI_VERSION = 12
 TRAIN_PART_FLOATS = 2 * 128 * 128 + 128 * 6 + 3 * 128    # AQG_TRAIN_PART_FLOATS, per position of the batch
 
 _c = ctypes
@@ -45,7 +45,7 @@ class TrainStruct(_c.Structure):
         [(n, _i32) for n in ("board_size", "batch", "policy_size", "step")]
         + [(n, _f32) for n in ("lr", "beta1", "beta2", "eps")]
         + [(n, _vp * 14) for n in ("params", "grads", "adam_m", "adam_v")]
-        + [(n, _vp) for n in ("h1", "h2", "h3", "zbuf", "dh", "g", "dg", "hp", "hv", "dhp", "dhv",
+        + [(n, _vp) for n in ("h1", "h2", "g", "hp", "hv", "dhp", "dhv",
                               "lg", "pol", "vp", "val", "loss", "part")]
     )
 

@@ -9,30 +9,22 @@
 //   backward  dP = dH' (.) [H' > 0];  db = colsum dP;  dZ = A_hat dP (A_hat symmetric);  dW = dZ^T H;  dH = dZ W
 //   update    torch.optim.Adam (lr, betas, eps; bias-corrected; no weight decay, no amsgrad)
 //
-// The batch is 128 positions (train_network.py:15) = 10,368 graph nodes and 2.2 GFLOP per step.  Three forms of the step
-// (aqg_set_option("train_fused")), all within 2e-5 max|g| of fp64 autograd:
+// The batch is 128 positions (train_network.py:15) = 10,368 graph nodes and 2.2 GFLOP per step.  Two launches per step:
 //
-//   2, split (default on 9x9): train_board_split_kernel -- ONE 8-wave workgroup per position does forward, heads + losses and
-//     backward with every contraction on the 16-bit matrix pipe in fp16 hi/lo split precision (split_mfma.hpp; three fp16 products
-//     per f32 product, f32 accumulation: fp32-equivalent), the neighbourhood aggregation included (banded A_hat blocks as MFMA
-//     operands).  A position whose values leave fp16 range is redone by the f32 body in the same launch.  Then train_final_kernel.
-//   1, fused f32: train_board_kernel -- the same one-workgroup-per-position structure on the f32-input matrix pipe
-//     (v_mfma_f32_16x16x4_f32: exact f32 products), aggregation as a VALU gather over LDS; the default on 3x3 / 5x5 / 7x7.
-//   0, six launches + final: two workgroups per board split the 128 feature columns (all 256 CUs busy at batch 128) and exchange
-//     full rows through memory between launches:
-//       fwd12   (board, column half)  features + graph from the record; layer 1 (K = 6, both halves redundantly), layer 2 half
-//       fwd3    (board, column half)  layer 3 half + the mean pool of that half
-//       heads   (board)               both heads, the two losses, and the head gradients back to dg
-//       bwd<3>  (board, column half)  dP3, db3, dZ3 = A_hat dP3, dW3 = dZ3^T H2 (per-board partial)
-//       bwd<2>  (board, column half)  dH2 = dZ3 W3 (half of the columns), dP2, db2, dZ2, dW2 partial
-//       bwd<1>  (board, column half)  dH1 = dZ2 W2, dP1, db1, dZ1, dW1 partial
-//     The column split is consistent through the chain: the aggregation is per column, and each contraction takes FULL rows of
-//     its input (written by the previous launch) and produces one column half.
+//   board   (position)            forward, heads + losses and backward of one position in one 8-wave workgroup; writes the
+//                                 per-board partial gradients.  Two forms (aqg_set_option("train_fused")), both within 2e-5
+//                                 max|g| of fp64 autograd:
+//     2, split (default on 9x9): train_board_split_kernel -- every contraction on the 16-bit matrix pipe in fp16 hi/lo split
+//       precision (split_mfma.hpp; three fp16 products per f32 product, f32 accumulation: fp32-equivalent), the neighbourhood
+//       aggregation included (banded A_hat blocks as MFMA operands).  A position whose values leave fp16 range is redone by the
+//       f32 body in the same launch (3 = every position sent through that fallback: tests).
+//     1, f32: train_board_kernel -- the same structure on the f32-input matrix pipe (v_mfma_f32_16x16x4_f32: exact f32
+//       products), aggregation as a VALU gather over LDS; the default on 3x3 / 5x5 / 7x7.
 //   final   (parameter element)   sums the per-board partials in a fixed order, forms the head weight gradients as
 //                                 batch dot products, writes the gradient and applies Adam to that element
 //
-// A board's 81 node rows never leave its workgroup (the aggregation needs all of them).  No atomics anywhere: results are
-// run-to-run identical.
+// A board's 81 node rows never leave its workgroup (the aggregation needs all of them).  No atomics on any result (only on the
+// fallback counter): results are run-to-run identical.
 #include "aqg_common.hpp"
 #include "split_mfma.hpp"
 #include "../../include/aqgnn.h"
@@ -41,18 +33,17 @@ namespace aqg {
 
 constexpr int TH = 128;    // HIDDEN_DIM
 constexpr int TF = 6;      // NUM_FEATURES
-constexpr int HH = 64;     // columns per workgroup
+constexpr int HH = 64;     // width of each head's hidden layer
 constexpr int SA = 132;    // LDS row stride of a [rows][128] A operand  (132 = 4 mod 64: 16 rows x 4 k-lanes hit 64 banks)
-constexpr int SZ = 68;     // LDS row stride of a [rows][64] accumulator image (same property for the accumulator layout)
-constexpr int SD = 80;     // LDS row stride of dZ [nodes][64] as the A operand of the weight gradient (80 = 16 mod 64)
 constexpr int SB = 144;    // LDS row stride of H [nodes][128] as its B operand (144 = 16 mod 64)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Diagnostic build only (-DAQG_STAMP, tools/stamp_train.py; never shipped): thread 0 of workgroup 0 adds the cycles between
-// consecutive phase marks of kernel k to g_train_stamp[k][phase].
+// consecutive phase marks of section k to g_train_stamp[k][phase]; k = 0 train_final_kernel, 1 the heads, 2 the f32 body,
+// 3 the split body.
 #ifdef AQG_STAMP
-__device__ unsigned long long g_train_stamp[10][16];
+__device__ unsigned long long g_train_stamp[4][16];
 #define TS_DECL unsigned long long ts_prev = __builtin_readcyclecounter();
 #define TS(k, i) { const unsigned long long ts_now = __builtin_readcyclecounter(); if (blockIdx.x == 0 && threadIdx.x == 0) g_train_stamp[k][i] += ts_now - ts_prev; ts_prev = ts_now; }
 #else
@@ -130,43 +121,9 @@ __device__ __forceinline__ f32x4 agg_row(const float* Zs, const BoardGraph& gr, 
     return a;
 }
 
-// The B operand of a 128-deep contraction for 64 output columns, staged in LDS by coalesced 16-byte loads (the weights
-// were rewritten by the previous step's Adam update: every launch finds them cold in its XCD's L2).
-//   forward   B[k][c] = W[c0 + c][k]      -> image [c][k], stride SA: lane (c, k = 4 ks + q) reads conflict-free
-//   dgrad     B[k][c] = W[k][c0 + c]      -> image [k][c], stride SD: idem
-struct WTile {
-    f32x4 v[8];
-    template <bool FWD> __device__ __forceinline__ void issue(const float* __restrict__ W, int c0, int t) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int i = t + 256 * k;
-            v[k] = FWD ? ld4(W + (size_t)(c0 + (i >> 5)) * TH + (i & 31) * 4) : ld4(W + (size_t)(i >> 4) * TH + c0 + (i & 15) * 4);
-        }
-    }
-    template <bool FWD> __device__ __forceinline__ void land(float* Ws, int t) const {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int i = t + 256 * k;
-            if (FWD) st4(Ws + (i >> 5) * SA + (i & 31) * 4, v[k]);
-            else st4(Ws + (i >> 4) * SD + (i & 15) * 4, v[k]);
-        }
-    }
-};
-
-// acc[rt] += A[16 rt + r16][k] * B[k][16 wave + r16]  over k = 0..127; A an LDS image with stride SA, B a WTile image
-template <int RT, bool FWD>
-__device__ __forceinline__ void mfma_rows(f32x4 (&acc)[RT], const float* As, const float* Ws, int wave, int r16, int q) {
-    const float* bp = FWD ? Ws + (16 * wave + r16) * SA + q : Ws + q * SD + 16 * wave + r16;
-#pragma unroll
-    for (int ks = 0; ks < 32; ++ks) {
-        const float bv = bp[FWD ? 4 * ks : 4 * ks * SD];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) acc[rt] = mfma4(As[(16 * rt + r16) * SA + 4 * ks + q], bv, acc[rt]);
-    }
-}
-
-// The same contraction with the B operand held in registers (the fused per-board kernel: its LDS is full of activations):
-// bw[ks] = W[(4 ks + q) * sk + col * sc], 32 strided dwords per lane, requested one phase ahead of their use.
+// acc[rt] += A[16 rt + r16][k] * B[k][col]  over k = 0..127; A an LDS image with row stride SA, B held in registers (the per-board
+// kernel's LDS is full of activations): bw[ks] = W[(4 ks + q) * sk + col * sc], 32 strided dwords per lane, requested one phase
+// ahead of their use.
 __device__ __forceinline__ void load_bfrag(float (&bw)[32], const float* __restrict__ W, int sk, int sc, int col, int q) {
     const float* p = W + (size_t)col * sc + (size_t)q * sk;
 #pragma unroll
@@ -204,19 +161,9 @@ __device__ __forceinline__ void mfma_rows_reg(f32x4 (&acc)[RT], const float* As,
     }
 }
 
-// accumulator tiles -> LDS image [rows][64] (stride SZ); this wave's 16 columns start at 16 * wave
-template <int RT>
-__device__ __forceinline__ void store_acc(float* Zs, const f32x4 (&acc)[RT], int wave, int r16, int q) {
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) Zs[(16 * rt + 4 * q + i) * SZ + 16 * wave + r16] = acc[rt][i];
-    }
-}
-
 // rows [0, V) x 128 floats of a global [.][128] array -> LDS image with row stride S, rows [V, VZ) zero-filled.  Two
 // halves so that a caller can put other work between the issue of the loads and the LDS writes.
-template <int V, int VZ, int NT = 256> struct RowTile {
+template <int V, int VZ, int NT> struct RowTile {
     static constexpr int IT = (VZ * 32 + NT - 1) / NT;
     f32x4 v[IT];
     __device__ __forceinline__ void issue(const float* __restrict__ src, int t) {
@@ -240,146 +187,12 @@ __device__ __forceinline__ size_t record_of(const int64_t* __restrict__ order, i
 }
 
 // ---------------------------------------------------------------------------------------------
-// forward, layers 1 + 2.   grid = 2 * B: workgroup = (board, column half)
-// ---------------------------------------------------------------------------------------------
-template <int N>
-__global__ __launch_bounds__(256) void train_fwd12_kernel(const uint8_t* __restrict__ states72, const int64_t* __restrict__ order, int first,
-                                                          const float* __restrict__ W1, const float* __restrict__ b1,
-                                                          const float* __restrict__ W2, const float* __restrict__ b2,
-                                                          float* __restrict__ h1, float* __restrict__ h2) {
-    constexpr int V = N * N, RT = (V + 15) / 16;
-    __shared__ float Zs[96 * SA];
-    __shared__ float Hs[96 * SA];
-    __shared__ float Ws[64 * SA];
-    __shared__ BoardGraph gr;
-    const int b = blockIdx.x >> 1, half = blockIdx.x & 1, t = threadIdx.x;
-    const int lane = t & 63, wave = t >> 6, q = lane >> 4, r16 = lane & 15;
-    TS_DECL
-    WTile wt;
-    wt.issue<true>(W2, HH * half, t);
-    board_graph<N>(gr, states72 + record_of(order, first, b) * STATE72, t);
-    __syncthreads();
-    TS(0, 0)
-    // layer 1: Z1 = X0 W1^T, K = 6 padded to 8; this wave's column tiles are 2 wave, 2 wave + 1
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = 16 * (2 * wave + j) + r16;
-        const float w_lo = W1[col * TF + q];                         // k = q      (0..3)
-        const float w_hi = (q < 2) ? W1[col * TF + 4 + q] : 0.f;     // k = 4 + q  (4, 5; 6 and 7 are padding)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            acc = mfma4(gr.x0[(16 * rt + r16) * 8 + q], w_lo, acc);
-            acc = mfma4(gr.x0[(16 * rt + r16) * 8 + 4 + q], w_hi, acc);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) Zs[(16 * rt + 4 * q + i) * SA + col] = acc[i];
-        }
-    }
-    __syncthreads();
-    TS(0, 1)
-    {   // H1 = relu(A_hat Z1 + b1): all 128 columns into LDS (layer 2 contracts over them), this half to memory
-        const int c4 = (t & 31) * 4;
-        const f32x4 bias = ld4(b1 + c4);
-        const bool mine = (c4 >> 6) == half;
-#pragma unroll
-        for (int it = 0; it < (V + 7) / 8; ++it) {
-            const int n = (t >> 5) + 8 * it;
-            if (n < V) {
-                const f32x4 a = relu4(agg_row<SA>(Zs, gr, n, c4) + bias);
-                st4(Hs + n * SA + c4, a);
-                if (mine) st4(h1 + ((size_t)b * V + n) * TH + c4, a);
-            }
-        }
-    }
-    wt.land<true>(Ws, t);
-    __syncthreads();
-    TS(0, 2)
-    f32x4 acc[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) acc[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    mfma_rows<RT, true>(acc, Hs, Ws, wave, r16, q);
-    TS(0, 3)
-    store_acc<RT>(Zs, acc, wave, r16, q);        // Z1 is dead since the barrier above
-    __syncthreads();
-    TS(0, 4)
-    {
-        const int c4 = (t & 15) * 4;
-        const f32x4 bias = ld4(b2 + HH * half + c4);
-#pragma unroll
-        for (int it = 0; it < (V + 15) / 16; ++it) {
-            const int n = (t >> 4) + 16 * it;
-            if (n < V) st4(h2 + ((size_t)b * V + n) * TH + HH * half + c4, relu4(agg_row<SZ>(Zs, gr, n, c4) + bias));
-        }
-    }
-    TS(0, 5)
-}
-
-// ---------------------------------------------------------------------------------------------
-// forward, layer 3 + mean pool.   grid = 2 * B
-// ---------------------------------------------------------------------------------------------
-template <int N>
-__global__ __launch_bounds__(256) void train_fwd3_kernel(const uint8_t* __restrict__ states72, const int64_t* __restrict__ order, int first,
-                                                         const float* __restrict__ W3, const float* __restrict__ b3,
-                                                         const float* __restrict__ h2, float* __restrict__ h3, float* __restrict__ g) {
-    constexpr int V = N * N, RT = (V + 15) / 16;
-    __shared__ float Hs[96 * SA];
-    __shared__ float Zs[96 * SZ];
-    __shared__ float Ws[64 * SA];
-    __shared__ BoardGraph gr;
-    const int b = blockIdx.x >> 1, half = blockIdx.x & 1, t = threadIdx.x;
-    const int lane = t & 63, wave = t >> 6, q = lane >> 4, r16 = lane & 15;
-    TS_DECL
-    RowTile<V, V> hin;
-    hin.issue(h2 + (size_t)b * V * TH, t);
-    WTile wt;
-    wt.issue<true>(W3, HH * half, t);
-    board_graph<N>(gr, states72 + record_of(order, first, b) * STATE72, t);
-    hin.template land<SA>(Hs, t);
-    wt.land<true>(Ws, t);
-    __syncthreads();
-    TS(1, 0)
-    f32x4 acc[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) acc[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    mfma_rows<RT, true>(acc, Hs, Ws, wave, r16, q);
-    TS(1, 1)
-    store_acc<RT>(Zs, acc, wave, r16, q);
-    __syncthreads();
-    TS(1, 2)
-    float* cs = Hs;                              // H2 is dead: every wave finished its MFMAs before the barrier
-    {
-        const int c4 = (t & 15) * 4;
-        const f32x4 bias = ld4(b3 + HH * half + c4);
-        f32x4 colsum = {0.f, 0.f, 0.f, 0.f};     // this thread's rows (t >> 4, + 16, ...) in ascending order
-#pragma unroll
-        for (int it = 0; it < (V + 15) / 16; ++it) {
-            const int n = (t >> 4) + 16 * it;
-            if (n < V) {
-                const f32x4 a = relu4(agg_row<SZ>(Zs, gr, n, c4) + bias);
-                st4(h3 + ((size_t)b * V + n) * TH + HH * half + c4, a);
-                colsum += a;
-            }
-        }
-        st4(cs + (t >> 4) * HH + c4, colsum);
-    }
-    __syncthreads();
-    TS(1, 3)
-    if (t < HH) {                                // global_mean_pool: the 16 row-group sums in fixed order
-        float s = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s += cs[r * HH + t];
-        g[(size_t)b * TH + HH * half + t] = s / (float)V;
-    }
-    TS(1, 4)
-}
-
-// ---------------------------------------------------------------------------------------------
-// heads, losses and the way back to dg.   grid = B, one workgroup per position.
+// heads, losses and the way back to the pooled features, inside the per-board kernels.
 //   train_network.py:54,85: CrossEntropyLoss(policy_pred, policy_target) with policy_pred ALREADY softmaxed
 //   (pv_network_gnn.py:42,62) and probability targets: l_b = -sum_a t_a log_softmax(pol)_a, mean over the batch
 //   train_network.py:55,86: MSELoss(value_pred.squeeze(), value_target), mean over the batch
 // Leaves: pol, val, loss terms; hp, hv (hidden layers); lg = d loss / d logits, vp = d loss / d pre-tanh value;
-// dhp, dhv (gradients at the hidden layers, ReLU applied); dg.
+// dhp, dhv (gradients at the hidden layers, ReLU applied); dg = d loss / d pooled features.
 // ---------------------------------------------------------------------------------------------
 struct HeadParams { const float* p[8]; };        // state_dict tensors 6..13
 template <int CTRL, int ROW_MASK> __device__ __forceinline__ float dpp_f(float old, float x) {
@@ -412,9 +225,9 @@ __device__ __forceinline__ float row16_total(float x) {          // sum over the
     x += dpp_f<0x121, 0xf>(0.f, x);    // row_ror:1
     return x;
 }
-// One position's heads, losses and head gradients by a workgroup of NW wavefronts (all of them load and multiply; the softmax /
-// loss reductions run on the first four).  `sm.gs` = the pooled features if g == nullptr (the fused kernels have them in LDS
-// already); on return sm.dgv = dg, also stored to dg_out if that is not null.
+// One position's heads, losses and head gradients by a workgroup of NW = 8 wavefronts (all of them load and multiply; the softmax /
+// loss reductions run on wave 0).  The caller has put the pooled features into sm.gs (published by the first barrier in here); on
+// return sm.dgv = dg.
 //
 // Weight access.  Every matrix is read ONCE, by 16-byte loads, into registers that serve its forward product AND its transposed
 // product on the way back: a quarter wave (16 lanes = one DPP row) owns a weight row, lane l of it holds columns 4 l .. 4 l + 3 (and
@@ -424,22 +237,20 @@ __device__ __forceinline__ float row16_total(float x) {          // sum over the
 //                                                     quarter waves are added up through LDS in a fixed order.
 // (Before: one row per wave instruction with a 64-lane reduction per row, policy_head.2 and both first layers read twice, the
 //  second time with 4-byte strided loads -- 180 vector-memory instructions and ~100 weight registers per lane; now 15 and 60.)
-template <int NW>
-__device__ __forceinline__ void heads_board(HeadsSmem& sm, int b, const float* __restrict__ g, const HeadParams& Pm,
+__device__ __forceinline__ void heads_board(HeadsSmem& sm, int b, const HeadParams& Pm,
                                             const float* __restrict__ pi_all, const float* __restrict__ z_all,
                                             const int64_t* __restrict__ order, int first, int A, int B,
                                             float* __restrict__ hp, float* __restrict__ hv, float* __restrict__ lg,
                                             float* __restrict__ pol, float* __restrict__ vp, float* __restrict__ val,
-                                            float* __restrict__ loss, float* __restrict__ dhp, float* __restrict__ dhv,
-                                            float* __restrict__ dg) {
+                                            float* __restrict__ loss, float* __restrict__ dhp, float* __restrict__ dhv) {
     float (&gs)[TH] = sm.gs; float (&hs)[TH] = sm.hs; float (&dhs)[TH] = sm.dhs; float (&dl)[256] = sm.dl;
     float (&red)[2][8][2] = sm.red;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, rg = lane >> 4, l = lane & 15;
+    const bool feat = t < TH;                                       // threads 0..127: one pooled feature / hidden unit each
     const float *Wp1 = Pm.p[0], *bp1 = Pm.p[1], *Wp2 = Pm.p[2], *bp2 = Pm.p[3], *Wv1 = Pm.p[4], *bv1 = Pm.p[5], *Wv2 = Pm.p[6], *bv2 = Pm.p[7];
     const size_t rec = record_of(order, first, b);
     TS_DECL
-    constexpr int HEADS_TS = NW == 4 ? 2 : 7;
-    (void)HEADS_TS;
+    constexpr int NW = 8;
     constexpr int HG = TH / (4 * NW);                               // first-layer row groups per wave (4 rows each)
     constexpr int LG = 64 / NW;                                     // policy_head.2 row groups per wave: 64 groups = 256 rows >= A
     f32x4 w1a[HG], w1b[HG], w2[LG];
@@ -467,9 +278,8 @@ __device__ __forceinline__ void heads_board(HeadsSmem& sm, int b, const float* _
         lbq[j] = ok ? bp2[a] : 0.f;
     }
     if (wave == 0) { wv2q = Wv2[lane]; bvq = bv2[0]; ztq = z_all[rec]; }
-    if (g && t < TH) gs[t] = g[(size_t)b * TH + t];
     __syncthreads();
-    TS(HEADS_TS, 0)
+    TS(1, 0)
     {   // hidden layers: hs[0..63] policy, hs[64..127] value
         const f32x4 g0 = ld4(gs + 4 * l), g1 = ld4(gs + 64 + 4 * l);
 #pragma unroll
@@ -483,7 +293,7 @@ __device__ __forceinline__ void heads_board(HeadsSmem& sm, int b, const float* _
         }
     }
     __syncthreads();
-    TS(HEADS_TS, 1)
+    TS(1, 1)
     {
         const f32x4 h4 = ld4(hs + 4 * l);
 #pragma unroll
@@ -494,7 +304,7 @@ __device__ __forceinline__ void heads_board(HeadsSmem& sm, int b, const float* _
         }
     }
     __syncthreads();
-    TS(HEADS_TS, 2)
+    TS(1, 2)
     // softmax, the reference's second softmax inside CrossEntropyLoss, both losses and the way back to the logits: ONE wavefront
     // holds all A <= 256 logits (four per lane) and every reduction is a wave reduction -- no barrier until the results are out
     // (four workgroup-wide reductions with a barrier each took 3.9 k cycles of the 12 k the heads need).
@@ -559,7 +369,7 @@ __device__ __forceinline__ void heads_board(HeadsSmem& sm, int b, const float* _
     }
     __syncthreads();
     const float dvp = red[0][0][0];
-    TS(HEADS_TS, 3)
+    TS(1, 3)
     {   // d loss / d policy hidden layer: this quarter wave's rows of policy_head.2, transposed product
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -567,8 +377,8 @@ __device__ __forceinline__ void heads_board(HeadsSmem& sm, int b, const float* _
         st4(&sm.part[4 * wave + rg][4 * l], acc);
     }
     __syncthreads();
-    TS(HEADS_TS, 4)
-    if (t < TH) {
+    TS(1, 4)
+    if (feat) {
         const int j = t & 63;
         float s;
         if (t < HH) {
@@ -581,7 +391,7 @@ __device__ __forceinline__ void heads_board(HeadsSmem& sm, int b, const float* _
         (t < HH ? dhp : dhv)[(size_t)b * HH + j] = s;
     }
     __syncthreads();
-    TS(HEADS_TS, 5)
+    TS(1, 5)
     {   // dg = dhp W_p1 + dhv W_v1: this quarter wave's rows of the two first layers, transposed product
         f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -593,149 +403,14 @@ __device__ __forceinline__ void heads_board(HeadsSmem& sm, int b, const float* _
         st4(&sm.part[4 * wave + rg][64 + 4 * l], a1);
     }
     __syncthreads();
-    TS(HEADS_TS, 6)
-    if (t < TH) {
+    TS(1, 6)
+    if (feat) {
         float s = 0.f;
 #pragma unroll
         for (int r = 0; r < 4 * NW; ++r) s += sm.part[r][t];
         sm.dgv[t] = s;
-        if (dg) dg[(size_t)b * TH + t] = s;
     }
     __syncthreads();
-}
-
-__global__ __launch_bounds__(256) void train_heads_kernel(const float* __restrict__ g, HeadParams Pm,
-                                                          const float* __restrict__ pi_all, const float* __restrict__ z_all,
-                                                          const int64_t* __restrict__ order, int first, int A, int B,
-                                                          float* __restrict__ hp, float* __restrict__ hv, float* __restrict__ lg,
-                                                          float* __restrict__ pol, float* __restrict__ vp, float* __restrict__ val,
-                                                          float* __restrict__ loss, float* __restrict__ dhp, float* __restrict__ dhv,
-                                                          float* __restrict__ dg) {
-    __shared__ HeadsSmem sm;
-    heads_board<4>(sm, blockIdx.x, g, Pm, pi_all, z_all, order, first, A, B, hp, hv, lg, pol, vp, val, loss, dhp, dhv, dg);
-}
-
-// ---------------------------------------------------------------------------------------------
-// backward through GCN layer L (3, 2, 1).   grid = 2 * B: workgroup = (board, column half of layer L's output)
-//   L == 3: dH = dg / V on every node.        L < 3: dH = dZ_{L+1} W_{L+1}  (this half of the columns)
-//   dP = dH (.) [H_L > 0];  db partial = column sums;  dZ = A_hat dP -> dZout (L > 1: the next launch contracts over it)
-//   dW partial [64 rows of W_L][K] = dZ^T H_{L-1}   (K = 128 on the matrix pipe; K = 6 for layer 1 on the VALU)
-// ---------------------------------------------------------------------------------------------
-template <int N, int L>
-__global__ __launch_bounds__(256) void train_bwd_kernel(const uint8_t* __restrict__ states72, const int64_t* __restrict__ order, int first,
-                                                        const float* __restrict__ dg, const float* __restrict__ dZin,
-                                                        const float* __restrict__ Wnext, const float* __restrict__ Hout,
-                                                        const float* __restrict__ Hin, float* __restrict__ dZout,
-                                                        float* __restrict__ part_dW, float* __restrict__ part_db) {
-    constexpr int V = N * N, RT = (V + 15) / 16, VK = (V + 3) / 4 * 4;
-    constexpr int UN = 96 * SZ + 84 * SD > 96 * SA ? 96 * SZ + 84 * SD : 96 * SA;
-    __shared__ float U[UN];                      // first dZin as an A operand, then dP (stride SZ) and dZ (stride SD)
-    __shared__ float Hb[L > 1 ? 84 * SB : 4];    // H_{L-1}, the B operand of the weight gradient
-    __shared__ float Ws[L < 3 ? 128 * SD : 4];   // W_{L+1}, the B operand of the data gradient
-    __shared__ float cs[4 * HH];
-    __shared__ BoardGraph gr;
-    float* dPs = U;
-    float* dZs = U + 96 * SZ;
-    const int b = blockIdx.x >> 1, half = blockIdx.x & 1, t = threadIdx.x;
-    const int lane = t & 63, wave = t >> 6, q = lane >> 4, r16 = lane & 15;
-    const int col = HH * half + 16 * wave + r16;
-    TS_DECL
-    f32x4 acc[RT];
-    float hm[RT][4];                             // H_L in the accumulator layout (lanes = 16 consecutive columns): the ReLU mask
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = 16 * rt + 4 * q + i;
-            hm[rt][i] = n < V ? Hout[((size_t)b * V + n) * TH + col] : 0.f;
-        }
-    }
-    RowTile<V, VK> hin;                          // H_{L-1}: only the weight gradient at the very end needs it -- requested
-    if (L < 3) {                                 // last, landed after the data-gradient MFMAs
-        RowTile<V, V> zin;
-        zin.issue(dZin + (size_t)b * V * TH, t);
-        WTile wt;
-        wt.issue<false>(Wnext, HH * half, t);
-        if (L > 1) hin.issue(Hin + (size_t)b * V * TH, t);
-        board_graph<N>(gr, states72 + record_of(order, first, b) * STATE72, t);
-        zin.template land<SA>(U, t);
-        wt.land<false>(Ws, t);
-        __syncthreads();
-        TS(6 - L, 0)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) acc[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        mfma_rows<RT, false>(acc, U, Ws, wave, r16, q);
-        if (L > 1) hin.template land<SB>(Hb, t);
-        TS(6 - L, 1)
-    } else {
-        hin.issue(Hin + (size_t)b * V * TH, t);
-        board_graph<N>(gr, states72 + record_of(order, first, b) * STATE72, t);
-        const float v = dg[(size_t)b * TH + col] / (float)V;      // global_mean_pool backward
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) acc[rt] = f32x4{v, v, v, v};
-    }
-    float dbp = 0.f;                             // this lane's share of the bias gradient: its rows in ascending order
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (!(hm[rt][i] > 0.f)) acc[rt][i] = 0.f;             // rows >= V carry hm = 0
-            dbp += acc[rt][i];
-        }
-    }
-    __syncthreads();                             // every wave is done with the A operand in U
-    TS(6 - L, 2)
-    store_acc<RT>(dPs, acc, wave, r16, q);
-    cs[q * HH + 16 * wave + r16] = dbp;
-    for (int i = t; i < (VK - V) * 16; i += 256) st4(dZs + (V + (i >> 4)) * SD + (i & 15) * 4, f32x4{0.f, 0.f, 0.f, 0.f});
-    __syncthreads();
-    TS(6 - L, 3)
-    {
-        const int c4 = (t & 15) * 4;
-#pragma unroll
-        for (int it = 0; it < (V + 15) / 16; ++it) {
-            const int n = (t >> 4) + 16 * it;
-            if (n < V) {
-                const f32x4 a = agg_row<SZ>(dPs, gr, n, c4);       // dZ = A_hat dP (A_hat is symmetric)
-                st4(dZs + n * SD + c4, a);
-                if (L > 1) st4(dZout + ((size_t)b * V + n) * TH + HH * half + c4, a);
-            }
-        }
-        if (t < HH) part_db[(size_t)b * TH + HH * half + t] = (cs[t] + cs[HH + t]) + (cs[2 * HH + t] + cs[3 * HH + t]);
-    }
-    if (L == 3) hin.template land<SB>(Hb, t);
-    __syncthreads();
-    TS(6 - L, 4)
-    // dW[64 half + 16 wave + ..][k] = sum_n dZ[n][j] H_{L-1}[n][k]: this wave's 16 rows of W_L
-    if (L > 1) {
-        f32x4 wacc[8];
-#pragma unroll
-        for (int ct = 0; ct < 8; ++ct) wacc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < VK / 4; ++ks) {
-            const float a = dZs[(4 * ks + q) * SD + 16 * wave + r16];
-#pragma unroll
-            for (int ct = 0; ct < 8; ++ct) wacc[ct] = mfma4(a, Hb[(4 * ks + q) * SB + 16 * ct + r16], wacc[ct]);
-        }
-        float* dst = part_dW + (size_t)b * TH * TH + (size_t)(HH * half + 16 * wave + 4 * q) * TH + r16;
-#pragma unroll
-        for (int ct = 0; ct < 8; ++ct) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) dst[(size_t)i * TH + 16 * ct] = wacc[ct][i];
-        }
-    } else {
-        // layer 1: H_0 = the six features (columns 6..15 of the tile are padding)
-        f32x4 wacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < VK / 4; ++ks)
-            wacc = mfma4(dZs[(4 * ks + q) * SD + 16 * wave + r16], r16 < 8 ? gr.x0[(4 * ks + q) * 8 + r16] : 0.f, wacc);
-        if (r16 < TF) {
-            float* dst = part_dW + (size_t)b * TH * TF + (size_t)(HH * half + 16 * wave + 4 * q) * TF + r16;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) dst[i * TF] = wacc[i];
-        }
-    }
-    TS(6 - L, 5)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -804,7 +479,7 @@ __device__ __forceinline__ void train_board_f32_body(unsigned char* __restrict__
     for (int i = t; i < (96 - V) * 32; i += 512) st4(Hs + (V + (i >> 5)) * SA + (i & 31) * 4, f32x4{0.f, 0.f, 0.f, 0.f});   // rows V..95: zero for good
                                                                      // (the padding rows of every contraction over the nodes)
     __syncthreads();
-    TS(8, 0)
+    TS(2, 0)
     // ---- forward, layer 1 (K = 6 padded to 8)
     {
         const float w_lo = W1[col * TF + q];
@@ -833,21 +508,21 @@ __device__ __forceinline__ void train_board_f32_body(unsigned char* __restrict__
     aggregate_relu(bias1, h1);
     const float warm_sink = ((warm[0] + warm[1]) + (warm[2] + warm[3])) + (warm[4] + warm[5]);
     __syncthreads();
-    TS(8, 1)
+    TS(2, 1)
     // ---- layer 2
     zero_acc();
     mfma_rows_reg4<RT>(acc, Hs, bv4, r16, q);
-    TS(8, 2)
+    TS(2, 2)
     load_bfrag4(bv4, W3, col, q);
     acc_to_Zs();
     __syncthreads();
     aggregate_relu(bias2, h2);
     __syncthreads();
-    TS(8, 3)
+    TS(2, 3)
     // ---- layer 3 + mean pool (H3 stays in LDS: the backward needs only its sign)
     zero_acc();
     mfma_rows_reg4<RT>(acc, Hs, bv4, r16, q);
-    TS(8, 4)
+    TS(2, 4)
     acc_to_Zs();
     __syncthreads();
     {
@@ -873,10 +548,10 @@ __device__ __forceinline__ void train_board_f32_body(unsigned char* __restrict__
         hsm.gs[t] = s;
         g_out[(size_t)b * TH + t] = s;                               // (the head weight gradients are batch dot products with it)
     }
-    TS(8, 5)
+    TS(2, 5)
     // ---- heads, losses, head gradients (its first barrier publishes gs)
-    heads_board<8>(hsm, b, nullptr, hpm, pi_all, z_all, order, first, A, B, hp, hv, lg, pol, vp, val, loss, dhp, dhv, nullptr);
-    TS(8, 6)
+    heads_board(hsm, b, hpm, pi_all, z_all, order, first, A, B, hp, hv, lg, pol, vp, val, loss, dhp, dhv);
+    TS(2, 6)
     load_bfrag(bw, W3, TH, 1, col, q);                               // the data gradient's fragments of W3 (B[j][k] = W3[j][k]): land under layer 3's backward
     // ---- backward.  One layer: dP (accumulator layout) -> Zs;  dZ = A_hat dP -> Hs;  dW partial = dZ^T H_{l-1} (Hb)
     RowTile<V, VK, 512> hin;
@@ -933,15 +608,15 @@ __device__ __forceinline__ void train_board_f32_body(unsigned char* __restrict__
         const float dbp = mask_and_bias_grad(Hs, SA);
         __syncthreads();                                             // everybody has read dg (in Zs) and H3 (in Hs)
         finish_layer(dbp, h2, part_db + (size_t)2 * B * TH);
-        TS(8, 7)
+        TS(2, 7)
         weight_grad(part_dW3);
-        TS(8, 8)
+        TS(2, 8)
     }
     // layer 2: dH2 = dZ3 W3, mask H2 (in Hb)
     {
         zero_acc();
         mfma_rows_reg<RT>(acc, Hs, bw, r16, q);
-        TS(8, 9)
+        TS(2, 9)
         load_bfrag(bw, W2, TH, 1, col, q);
 #ifdef AQG_TRAIN_DEBUG
         for (int rt = 0; rt < RT; ++rt) for (int i = 0; i < 4; ++i) if (16 * rt + 4 * q + i < V) DBG_PUT(1, B, b, 16 * rt + 4 * q + i, col, acc[rt][i])
@@ -953,19 +628,19 @@ __device__ __forceinline__ void train_board_f32_body(unsigned char* __restrict__
 #endif
         __syncthreads();                                             // dZ3 (Hs) and H2 (Hb) are dead
         finish_layer(dbp, h1, part_db + (size_t)B * TH);
-        TS(8, 10)
+        TS(2, 10)
         weight_grad(part_dW2);
-        TS(8, 11)
+        TS(2, 11)
     }
     // layer 1: dH1 = dZ2 W2, mask H1 (in Hb); dW1 = dZ1^T X0 (six feature columns of one padded tile)
     {
         zero_acc();
         mfma_rows_reg<RT>(acc, Hs, bw, r16, q);
-        TS(8, 12)
+        TS(2, 12)
         const float dbp = mask_and_bias_grad(Hb, SB);
         __syncthreads();
         finish_layer(dbp, nullptr, part_db);
-        TS(8, 13)
+        TS(2, 13)
         f32x4 wacc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < VK / 4; ++ks)
@@ -975,7 +650,7 @@ __device__ __forceinline__ void train_board_f32_body(unsigned char* __restrict__
 #pragma unroll
             for (int i = 0; i < 4; ++i) dst[i * TF] = wacc[i];
         }
-        TS(8, 14)
+        TS(2, 14)
     }
     if (warm_sink == -1.2345678e-31f) part_db[0] = warm_sink;          // (keeps the warm-up loads alive; never taken)
 }
@@ -1177,8 +852,8 @@ __device__ __attribute__((noinline)) void heads_board_call(unsigned int sm_lds, 
     HeadParams Pg;
     Pg.p[0] = (const float*)w0; Pg.p[1] = (const float*)w1; Pg.p[2] = (const float*)w2; Pg.p[3] = (const float*)w3;
     Pg.p[4] = (const float*)w4; Pg.p[5] = (const float*)w5; Pg.p[6] = (const float*)w6; Pg.p[7] = (const float*)w7;
-    heads_board<8>(sm, b, nullptr, Pg, (const float*)pi_all, (const float*)z_all, (const int64_t*)order, first, A, B, (float*)hp, (float*)hv, (float*)lg,
-                   (float*)pol, (float*)vp, (float*)val, (float*)loss, (float*)dhp, (float*)dhv, nullptr);
+    heads_board(sm, b, Pg, (const float*)pi_all, (const float*)z_all, (const int64_t*)order, first, A, B, (float*)hp, (float*)hv, (float*)lg,
+                (float*)pol, (float*)vp, (float*)val, (float*)loss, (float*)dhp, (float*)dhv);
 }
 
 // returns false (to every thread of the workgroup) if a value left fp16 range: the caller redoes the board with the f32 body
@@ -1257,7 +932,7 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
         reinterpret_cast<unsigned int*>(&sm.X0T[8][0])[t - 96] = 0u;                     // feature rows 8..15 of the padded tile
     }
     __syncthreads();
-    TS(9, 0)
+    TS(3, 0)
     // ---- A_hat fragments: entry (k-slot e of lane (c, q), block (kb, nt)) = dinv[n] dinv[k] where k is in the closed neighbourhood of n = 16 nt + c
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
@@ -1302,7 +977,7 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
         }
     }
     __syncthreads();                                                   // A_hat fragments complete
-    TS(9, 1)
+    TS(3, 1)
     // ---- forward epilogues
     const int poff = (2 * wave + (q >> 1)) /* 16-byte slot of features 16 w + 4 q .. */, pbyte = 8 * (q & 1);
     auto store_plane_tile = [&](int nt, f32x4 v, bool relu) {          // T form: lane = node c of tile nt, features 16 w + 4 q + r
@@ -1333,19 +1008,19 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
         store_plane_tile(nt, oT, true);
         park_tile(nt, oR, msk[0]);
     });
-    TS(9, 14)
+    TS(3, 14)
     park_store(h1);
     split_w();                                                          // W2 fragments
     request_w(W3);
-    TS(9, 15)
+    TS(3, 15)
     __syncthreads();                                                    // planes of H1 complete
-    TS(9, 2)
+    TS(3, 2)
     // ---- layer 2
     linear_split_post(sm.P, Bh, Bl, lane, zh, zl, mx, [&](int, f32x4&) {});
 #pragma unroll
     for (int kb = 0; kb < 3; ++kb) mfma_fence(zl[kb]);
     __syncthreads();                                                    // everybody has read the planes of H1
-    TS(9, 3)
+    TS(3, 3)
     aggregate_tr<true, true>(sm.AF, zh, zl, bT2, (f32x4){bR2, bR2, bR2, bR2}, lane, [&](int nt, const f32x4& oT, const f32x4& oR) {
         store_plane_tile(nt, oT, true);
         park_tile(nt, oR, msk[1]);
@@ -1353,7 +1028,7 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
     park_store(h2);
     split_w();                                                          // W3 fragments
     __syncthreads();                                                    // planes of H2 complete
-    TS(9, 4)
+    TS(3, 4)
     // ---- layer 3 (R form only: its ReLU mask and the mean pool; H3 itself is not needed again)
     linear_split_post(sm.P, Bh, Bl, lane, zh, zl, mx, [&](int, f32x4&) {});
 #pragma unroll
@@ -1394,16 +1069,16 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
 #pragma unroll
         for (int kb = 0; kb < 3; ++kb) { hh[kb] = src[(2 * kb) * 64]; hl[kb] = src[(2 * kb + 1) * 64]; }
     };
-    TS(9, 5)
+    TS(3, 5)
     // ---- heads, losses, head gradients (its first barrier publishes gs)
 #ifdef AQG_HEADS_INLINE      // developer A/B (tools/ab_train.sh): the heads inlined into this body
-    heads_board<8>(hsm, b, nullptr, hpm, pi_all, z_all, order, first, A, B, hp, hv, lg, pol, vp, val, loss, dhp, dhv, nullptr);
+    heads_board(hsm, b, hpm, pi_all, z_all, order, first, A, B, hp, hv, lg, pol, vp, val, loss, dhp, dhv);
 #else
     heads_board_call((unsigned int)(size_t)(HeadsSmemLds*)&hsm, b, (gcf)hpm.p[0], (gcf)hpm.p[1], (gcf)hpm.p[2], (gcf)hpm.p[3], (gcf)hpm.p[4], (gcf)hpm.p[5],
                      (gcf)hpm.p[6], (gcf)hpm.p[7], (gcf)pi_all, (gcf)z_all, (const __attribute__((address_space(1))) int64_t*)order, first, A, B,
                      (gf)hp, (gf)hv, (gf)lg, (gf)pol, (gf)vp, (gf)val, (gf)loss, (gf)dhp, (gf)dhv);
 #endif
-    TS(9, 6)
+    TS(3, 6)
     {
         // (requested BEHIND the call: hoisted above it -- which the compiler does unless the base pointers pass through this empty
         //  asm statement -- the 56 registers would be loaded, waited for, spilled around the call and reloaded)
@@ -1491,10 +1166,10 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
         split_wt();                                                     // W3^T fragments
         request_wt(W2);
         __syncthreads();                                                // planes and fragments of dZ3 complete
-        TS(9, 7)
+        TS(3, 7)
         weight_grad(part_dW3);
         request_h(h1);
-        TS(9, 8)
+        TS(3, 8)
     }
     // layers 2 and 1: dH_l = dZ_{l+1} W_{l+1}, masked by H_l > 0
     auto masked_linear = [&](unsigned int m, int layer) {
@@ -1522,19 +1197,19 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
     };
     {
         masked_linear(msk[1], 1);
-        TS(9, 9)
+        TS(3, 9)
         __syncthreads();                                                // everybody has read the planes of dZ3 (and FR: weight_grad is behind)
         aggregate_back(true);
         publish_dz();
         split_wt();                                                     // W2^T fragments
         __syncthreads();
-        TS(9, 10)
+        TS(3, 10)
         weight_grad(part_dW2);
-        TS(9, 11)
+        TS(3, 11)
     }
     {
         masked_linear(msk[0], 0);
-        TS(9, 12)
+        TS(3, 12)
         aggregate_back(false);
 #pragma unroll
         for (int kb = 0; kb < 3; ++kb) mfma_fence(al[kb]);
@@ -1553,7 +1228,7 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
 #pragma unroll
             for (int r = 0; r < 4; ++r) dst[r * TF] = o[r] * inv_s;
         }
-        TS(9, 13)
+        TS(3, 13)
     }
     return !__syncthreads_or(out_of_fp16_range(mx));
 }
@@ -1641,7 +1316,7 @@ __global__ __launch_bounds__(FINAL_TEAM_THREADS * FINAL_TEAMS) void train_final_
             for (int b = b0; b < b1; ++b) s += ld4(src + (size_t)b * TH * TH);
             red4[grp][le] = s;
             __syncthreads();
-            TS(6, 1)
+            TS(0, 1)
             if (grp != 0) return;
             gr4 = (red4[0][le] + red4[1][le]) + (red4[2][le] + red4[3][le]);
             if (FINAL_GROUPS >= 8) gr4 += (red4[4][le] + red4[5][le]) + (red4[6][le] + red4[7][le]);
@@ -1664,7 +1339,7 @@ __global__ __launch_bounds__(FINAL_TEAM_THREADS * FINAL_TEAMS) void train_final_
     int i = 0;
     if (live) while (i < 14 && e0 >= jb.end[i]) ++i;
     const unsigned int e = e0 - (i ? jb.end[i - 1] : 0u);
-    TS(6, 0)
+    TS(0, 0)
     AdamOld old{0.f, 0.f, 0.f};
     if (jb.update && grp == 0 && live && i < 14) old = adam_fetch(jb, i, e);
     if (jb.compute) {
@@ -1726,9 +1401,8 @@ __global__ __launch_bounds__(FINAL_TEAM_THREADS * FINAL_TEAMS) void train_final_
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// aqg_set_option("train_fused"): 2 (default) = one workgroup per position, contractions in fp16 split precision on the 9x9 board (other
-// boards: as 1);  1 = one workgroup per position, f32-input MFMA;  0 = six launches;  3 = as 2 with every board sent through the
-// f32 fallback (tests)
+// aqg_set_option("train_fused"): 2 (default) = contractions in fp16 split precision on the 9x9 board (other boards: as 1);
+// 1 = f32-input MFMA;  3 = as 2 with every board sent through the f32 fallback (tests).  capi.hip refuses other values.
 int g_train_fused = 2;
 long long train_fallbacks(int reset) {
     unsigned int v = 0;
@@ -1742,42 +1416,20 @@ static void launch_forward_backward(const aqg_train& t, const uint8_t* states72,
                                     int first, int B, hipStream_t st) {
     const int A = t.policy_size;
     float* const* P = t.params;
-    if (g_train_fused) {
-        float* pdW3 = t.part;
-        float* pdW2 = pdW3 + (size_t)B * TH * TH;
-        float* pdW1 = pdW2 + (size_t)B * TH * TH;
-        float* pdb = pdW1 + (size_t)B * TH * TF;
-        TrunkParams tpm;
-        for (int i = 0; i < 6; ++i) tpm.p[i] = P[i];
-        HeadParams hpm;
-        for (int i = 0; i < 8; ++i) hpm.p[i] = P[6 + i];
-        if (N == 9 && g_train_fused >= 2)      // h1 / h2 hold 96 rows per board here: the parked fragments (and the fallback's rows)
-            hipLaunchKernelGGL(train_board_split_kernel, dim3(B), dim3(512), 0, st, states72, order, first, tpm, hpm, pi, z, A, B, g_train_fused == 3 ? 1 : 0,
-                               t.h1, t.h2, t.g, t.hp, t.hv, t.lg, t.pol, t.vp, t.val, t.loss, t.dhp, t.dhv, pdW3, pdW2, pdW1, pdb);
-        else
-            hipLaunchKernelGGL(train_board_kernel<N>, dim3(B), dim3(512), 0, st, states72, order, first, tpm, hpm, pi, z, A, B, N * N, t.h1, t.h2, t.g,
-                               t.hp, t.hv, t.lg, t.pol, t.vp, t.val, t.loss, t.dhp, t.dhv, pdW3, pdW2, pdW1, pdb);
-        return;
-    }
-    const dim3 grid(2 * B), block(256);
     float* pdW3 = t.part;
     float* pdW2 = pdW3 + (size_t)B * TH * TH;
     float* pdW1 = pdW2 + (size_t)B * TH * TH;
-    float* pdb = pdW1 + (size_t)B * TH * TF;                        // [3][B][128]: layer 1, 2, 3
-    hipLaunchKernelGGL(train_fwd12_kernel<N>, grid, block, 0, st, states72, order, first, (const float*)P[0], (const float*)P[1],
-                       (const float*)P[2], (const float*)P[3], t.h1, t.h2);
-    hipLaunchKernelGGL(train_fwd3_kernel<N>, grid, block, 0, st, states72, order, first, (const float*)P[4], (const float*)P[5],
-                       (const float*)t.h2, t.h3, t.g);
+    float* pdb = pdW1 + (size_t)B * TH * TF;
+    TrunkParams tpm;
+    for (int i = 0; i < 6; ++i) tpm.p[i] = P[i];
     HeadParams hpm;
     for (int i = 0; i < 8; ++i) hpm.p[i] = P[6 + i];
-    hipLaunchKernelGGL(train_heads_kernel, dim3(B), block, 0, st, (const float*)t.g, hpm, pi, z, order, first, A, B,
-                       t.hp, t.hv, t.lg, t.pol, t.vp, t.val, t.loss, t.dhp, t.dhv, t.dg);
-    hipLaunchKernelGGL((train_bwd_kernel<N, 3>), grid, block, 0, st, states72, order, first, (const float*)t.dg, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)t.h3, (const float*)t.h2, t.zbuf, pdW3, pdb + (size_t)2 * B * TH);
-    hipLaunchKernelGGL((train_bwd_kernel<N, 2>), grid, block, 0, st, states72, order, first, (const float*)nullptr, (const float*)t.zbuf,
-                       (const float*)P[4], (const float*)t.h2, (const float*)t.h1, t.dh, pdW2, pdb + (size_t)B * TH);
-    hipLaunchKernelGGL((train_bwd_kernel<N, 1>), grid, block, 0, st, states72, order, first, (const float*)nullptr, (const float*)t.dh,
-                       (const float*)P[2], (const float*)t.h1, (const float*)nullptr, (float*)nullptr, pdW1, pdb);
+    if (N == 9 && g_train_fused >= 2)      // h1 / h2 hold 96 rows per board here: the parked fragments (and the fallback's rows)
+        hipLaunchKernelGGL(train_board_split_kernel, dim3(B), dim3(512), 0, st, states72, order, first, tpm, hpm, pi, z, A, B, g_train_fused == 3 ? 1 : 0,
+                           t.h1, t.h2, t.g, t.hp, t.hv, t.lg, t.pol, t.vp, t.val, t.loss, t.dhp, t.dhv, pdW3, pdW2, pdW1, pdb);
+    else
+        hipLaunchKernelGGL(train_board_kernel<N>, dim3(B), dim3(512), 0, st, states72, order, first, tpm, hpm, pi, z, A, B, N * N, t.h1, t.h2, t.g,
+                           t.hp, t.hv, t.lg, t.pol, t.vp, t.val, t.loss, t.dhp, t.dhv, pdW3, pdW2, pdW1, pdb);
 }
 
 static int launch_final(const aqg_train& t, int B, bool compute, bool update, int step, float* loss_sums, hipStream_t st) {
@@ -1859,8 +1511,8 @@ extern "C" int aqg_debug_train_buf(float* buf) { return hipMemcpyToSymbol(HIP_SY
 #endif
 #ifdef AQG_STAMP
 extern "C" int aqg_debug_train_stamps(unsigned long long* out_host, int reset) {
-    if (hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_train_stamp), sizeof(unsigned long long) * 160) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[160] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_train_stamp), z, sizeof(z)) != hipSuccess) return -1; }
+    if (hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_train_stamp), sizeof(unsigned long long) * 64) != hipSuccess) return -1;
+    if (reset) { unsigned long long z[64] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_train_stamp), z, sizeof(z)) != hipSuccess) return -1; }
     return 0;
 }
 #endif

@@ -64,13 +64,11 @@ class GNNTrainer:
         self.max_batch = int(max_batch)
         self.step_count = 0
         self.betas, self.eps = betas, eps
-        B, V, A, H = self.max_batch, self.V, self.A, HIDDEN_DIM
+        B, A, H = self.max_batch, self.A, HIDDEN_DIM
         f = dict(dtype=torch.float32, device=self.dev)
         w = self.ws = dict(
             h1=torch.empty((B * 96, H), **f), h2=torch.empty((B * 96, H), **f),    # 96 rows per position: include/aqgnn.h
-            h3=torch.empty((B * V, H), **f),
-            zbuf=torch.empty((B * V, H), **f), dh=torch.empty((B * V, H), **f),
-            g=torch.empty((B, H), **f), dg=torch.empty((B, H), **f), hp=torch.empty((B, H // 2), **f),
+            g=torch.empty((B, H), **f), hp=torch.empty((B, H // 2), **f),
             hv=torch.empty((B, H // 2), **f), dhp=torch.empty((B, H // 2), **f), dhv=torch.empty((B, H // 2), **f),
             lg=torch.empty((B, A), **f), pol=torch.empty((B, A), **f), vp=torch.empty((B,), **f), val=torch.empty((B,), **f),
             loss=torch.empty((B, 2), **f), part=torch.empty((B * _lib.TRAIN_PART_FLOATS,), **f))

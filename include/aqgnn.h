@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define AQG_MAX_LEGAL 136 /* >= 5 pawn moves + 128 wall placements */
-#define AQG_ABI_VERSION 11
+#define AQG_ABI_VERSION 12
 
 int aqg_abi_version(void);
 const char* aqg_last_error(void);
@@ -40,8 +40,8 @@ const char* aqg_last_error(void);
  * "train_fused" = form of the training step
  * (csrc/gcn_train.hip): 2 (default) one workgroup per position with every contraction in fp16 split precision on the 16-bit
  * matrix pipe (9x9 board; a position whose values leave fp16 range is redone in f32 inside the same launch, counted by
- * aqg_gcn_train_fallbacks), 1 one workgroup per position with f32-input MFMA, 0 the six-launch column-split chain, 3 = 2 with
- * every position sent through the f32 fallback (tests);
+ * aqg_gcn_train_fallbacks), 1 one workgroup per position with f32-input MFMA, 3 = 2 with every position sent through the
+ * f32 fallback (tests); other values are refused;
  * "trunk_phase_delay" = start offset of the second- / third-resident workgroups in units of 64 cycles, applied to
  * launches of at least "trunk_delay_min_boards" boards; "trunk_grid" = workgroups of a trunk launch (0 = default: min(boards, 512); diagnostics);
  * "use_graph" 0/1 = replay
@@ -298,7 +298,7 @@ int aqg_engine_root_visits(const aqg_engine* e_host, int32_t* visits, uint8_t* a
  * (mode 0), all-reduces them over RCCL, and applies them (mode 2).  The 14 parameter tensors
  * are the state_dict tensors themselves in their PyTorch layouts and in the key order of KEYS in INTEGRATION.md; grads,
  * adam_m, adam_v have the same shapes.  All memory is the caller's (device pointers); nothing allocates or synchronises.
- * B = batch (the capacity the workspace was sized for is the caller's business), V = board_size^2, A = policy size. */
+ * B = batch (the capacity the workspace was sized for is the caller's business), A = policy size. */
 typedef struct aqg_train {
     int32_t board_size, batch, policy_size;
     int32_t step;                 /* Adam step count of THIS update, >= 1 */
@@ -306,10 +306,8 @@ typedef struct aqg_train {
     float* params[14]; float* grads[14]; float* adam_m[14]; float* adam_v[14];
     /* workspace */
     float* h1; float* h2;         /* [B*96, 128] (96 rows per position on every board size): post-ReLU activations of layers 1, 2 -- node
-                                   * rows in the f32 forms, this round's parked fp16 hi / lo fragments in the split form */
-    float* h3;                    /* [B*V, 128] layer 3 (six-launch form only) */
-    float* zbuf; float* dh;       /* [B*V, 128] dZ = A_hat dP of layer 3 / layer 2 (the next launch contracts over full rows) */
-    float* g; float* dg;          /* [B, 128]   pooled features and their gradient */
+                                   * rows in the f32 form, this round's parked fp16 hi / lo fragments in the split form */
+    float* g;                     /* [B, 128]   pooled features */
     float* hp; float* hv; float* dhp; float* dhv;   /* [B, 64] head hidden layers and gradients */
     float* lg;                    /* [B, A]     d loss / d logits */
     float* pol;                   /* [B, A]     softmax policy (the network output) */

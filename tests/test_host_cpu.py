@@ -29,7 +29,7 @@ def test_capi_exports_every_declared_symbol():
     assert lib.aqg_abi_version() == _lib.ABI_VERSION
     assert lib.aqg_gcn_packed_floats(9) > 64082          # all 64,082 parameters + padding + fragment copies
     assert ctypes.sizeof(_lib.EngineStruct) == 11 * 4 + 2 * 4 + 4 + 34 * 8 + 8   # 13 scalars (+4 pad) + 34 pointers (ABI 10: + 7 of the evaluation cache) + eval_cache_log2 (+4 pad)
-    assert ctypes.sizeof(_lib.TrainStruct) == 8 * 4 + 4 * 14 * 8 + 17 * 8      # aqg_train: 8 scalars, 4 x 14 + 17 pointers
+    assert ctypes.sizeof(_lib.TrainStruct) == 8 * 4 + 4 * 14 * 8 + 13 * 8      # aqg_train: 8 scalars, 4 x 14 + 13 pointers
 
 
 def test_no_cpu_fallback_without_gpu():
@@ -478,7 +478,7 @@ def test_set_option_names_ranges_and_errors():
         assert f"`{name}`" in integration, f"{name} is not listed in INTEGRATION.md"
         if value is not None:
             assert lib.aqg_set_option(name.encode(), value) == 0, name
-    for name, bad in (("trunk_variant", 2), ("trunk_variant", 4), ("trunk_variant", 7), ("trunk_variant", 8), ("trunk_phase_delay", -1), ("step_fast_depth", 62), ("train_fused", 4)):
+    for name, bad in (("trunk_variant", 2), ("trunk_variant", 4), ("trunk_variant", 7), ("trunk_variant", 8), ("trunk_phase_delay", -1), ("step_fast_depth", 62), ("train_fused", 0), ("train_fused", 4)):
         assert lib.aqg_set_option(name.encode(), bad) != 0, (name, bad)
         assert lib.aqg_last_error()
     assert lib.aqg_set_option(b"no_such_option", 1) != 0 and b"no_such_option" in lib.aqg_last_error()

@@ -14,8 +14,7 @@ dev = _lib.require_gpu("cuda:0")
 model, params = _model(6)
 recs, pi, z = _train_batch(32, 11, params=params if os.environ.get("AQG_KINK_FILTER", "1") == "1" else None)
 ref = ot.train_steps(params, [(recs, pi.astype(np.float64), z.astype(np.float64))])[0]
-forms = [(1, None), (2, None), (0, None)]
-for fused, sc in forms:
+for fused in (1, 2):
     _lib.set_option("train_fused", fused)
     tr = GNNTrainer(model, max_batch=32)
     tr.step(torch.from_numpy(recs), torch.from_numpy(pi), torch.from_numpy(z), update=False)
