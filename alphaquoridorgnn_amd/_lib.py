@@ -14,8 +14,9 @@ MAX_LEGAL = 136
 GNN_EXACT_F32 = 1        # AQG_GNN_EXACT_F32 (include/aqgnn.h)
 GNN_RANGE_PROVEN = 2     # AQG_GNN_RANGE_PROVEN
 GNN_PROVEN_MAX_WALLS = 16
-ABI_VERSION = 12
+ABI_VERSION = 13
 TRAIN_PART_FLOATS = 2 * 128 * 128 + 128 * 6 + 3 * 128    # AQG_TRAIN_PART_FLOATS, per position of the batch
+LIN_RELU, LIN_W_KN, LIN_ACCUMULATE = 1, 2, 4             # AQG_LIN_* flags of aqg_graph_linear
 
 _c = ctypes
 _vp, _i32, _f32 = _c.c_void_p, _c.c_int32, _c.c_float
@@ -73,6 +74,15 @@ SIGNATURES = {
     "aqg_gcn_backward_graph_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int]),
     "aqg_gcn_backward_graph": (_c.c_int, [_c.c_int, _c.c_int, _vp, _c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int,
                                           _vp, _vp, _vp, _vp, _vp, _c.POINTER(_vp), _vp, _c.c_size_t, _c.POINTER(_vp), _vp, _vp]),
+    "aqg_graph_linear": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp]),
+    "aqg_graph_linear_grad_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "aqg_graph_linear_grad": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _c.c_size_t, _vp, _vp, _vp]),
+    "aqg_graph_aggregate": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp]),
+    "aqg_graph_mean_pool": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _c.c_int, _vp, _vp]),
+    "aqg_graph_mean_pool_backward": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _c.c_int, _vp, _vp, _vp]),
+    "aqg_graph_heads": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "aqg_graph_heads_backward": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aqg_gcn_boards_graph": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp, _vp, _vp, _vp]),
     "aqg_engine_reset": (_c.c_int, [_c.POINTER(EngineStruct), _vp]),
     "aqg_engine_clear_eval_cache": (_c.c_int, [_c.POINTER(EngineStruct), _vp]),
     "aqg_engine_move": (_c.c_int, [_c.POINTER(EngineStruct), _vp, _vp]),

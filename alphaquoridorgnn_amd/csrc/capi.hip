@@ -49,6 +49,20 @@ int launch_gcn_backward_graph(int F, int A, const float* x, int n, const float* 
                               const float* pooled, const float* policy, const float* value, const float* dpolicy,
                               const float* dvalue, const float* const* params, float* workspace, size_t workspace_floats,
                               float* const* grads, float* dx, hipStream_t st);
+int launch_gen_linear(int M, int K, int N, const float* X, const float* W, const float* bias, const float* mask, int flags,
+                      float* Y, hipStream_t st);
+size_t gen_linear_grad_workspace_floats(int M, int N, int K);
+int launch_gen_linear_grad(int M, int K, int N, const float* dY, const float* X, const float* dYb, float* workspace,
+                           size_t workspace_floats, float* dW, float* db, hipStream_t st);
+int launch_gen_aggregate(int n, int N, const float* Y, const int32_t* ptr, const int32_t* src, const float* w, const float* bias,
+                         int relu, float* out, hipStream_t st);
+int launch_gen_mean_pool(int N, const float* H, const int32_t* gptr, int G, float* pooled, hipStream_t st);
+int launch_gen_mean_pool_backward(int n, int N, const float* dpooled, const int32_t* gptr, int G, const float* mask, float* dH,
+                                  hipStream_t st);
+int launch_gen_heads(int G, int A, const float* logits, const float* vpre, float* policy, float* value, hipStream_t st);
+int launch_gen_heads_backward(int G, int A, const float* policy, const float* dpolicy, const float* value, const float* dvalue,
+                              float* dlogits, float* dvpre, hipStream_t st);
+int launch_gcn_boards_graph(int N, const void* states, int fmt, int B, float* x0, int32_t* ell_idx, float* ell_w, hipStream_t st);
 int engine_reset(const aqg_engine& e, hipStream_t st);
 int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st);
 int engine_begin_move(const aqg_engine& e, hipStream_t st);
@@ -195,6 +209,73 @@ int aqg_gcn_backward_graph(int num_features, int num_actions, const float* x, in
     return launch_gcn_backward_graph(num_features, num_actions, x, num_nodes, h1, h2, h3, tcsr_ptr, tcsr_dst, tcsr_w, graph_ptr,
                                      num_graphs, pooled, policy, value, dpolicy, dvalue, params_host, workspace, workspace_floats,
                                      grads_host, dx, (hipStream_t)stream);
+}
+
+int aqg_graph_linear(int M, int K, int N, const float* X, const float* W, const float* bias, const float* mask, int flags,
+                     float* Y, void* stream) {
+    if (M < 0 || K < 0 || N < 0) return fail("aqg_graph_linear: negative size");
+    if (flags & ~(AQG_LIN_RELU | AQG_LIN_W_KN | AQG_LIN_ACCUMULATE)) return fail("aqg_graph_linear: unknown flag");
+    if (M == 0 || N == 0) return 0;
+    if (!Y || (K > 0 && (!X || !W))) return fail("aqg_graph_linear: null argument");
+    return launch_gen_linear(M, K, N, X, W, bias, mask, flags, Y, (hipStream_t)stream);
+}
+
+size_t aqg_graph_linear_grad_workspace_floats(int M, int N, int K) { return gen_linear_grad_workspace_floats(M, N, K); }
+
+int aqg_graph_linear_grad(int M, int K, int N, const float* dY, const float* X, const float* dYb, float* workspace,
+                          size_t workspace_floats, float* dW, float* db, void* stream) {
+    if (M < 0 || K < 0 || N < 0) return fail("aqg_graph_linear_grad: negative size");
+    if (K == 0) return fail("aqg_graph_linear_grad: K must be >= 1");
+    if (N == 0) return 0;
+    if (!dW || (M > 0 && (!dY || !X || !workspace))) return fail("aqg_graph_linear_grad: null argument");
+    return launch_gen_linear_grad(M, K, N, dY, X, dYb, workspace, workspace_floats, dW, db, (hipStream_t)stream);
+}
+
+int aqg_graph_aggregate(int num_nodes, int N, const float* Y, const int32_t* csr_ptr, const int32_t* csr_src, const float* csr_w,
+                        const float* bias, int relu, float* out, void* stream) {
+    if (num_nodes < 0 || N < 0) return fail("aqg_graph_aggregate: negative size");
+    if (num_nodes == 0 || N == 0) return 0;
+    if (!Y || !csr_ptr || !csr_src || !csr_w || !out) return fail("aqg_graph_aggregate: null argument");
+    return launch_gen_aggregate(num_nodes, N, Y, csr_ptr, csr_src, csr_w, bias, relu, out, (hipStream_t)stream);
+}
+
+int aqg_graph_mean_pool(int num_nodes, int N, const float* H, const int32_t* graph_ptr, int num_graphs, float* pooled,
+                        void* stream) {
+    if (num_nodes < 0 || N < 0 || num_graphs < 0) return fail("aqg_graph_mean_pool: negative size");
+    if (num_graphs == 0 || N == 0) return 0;
+    if ((num_nodes > 0 && !H) || !graph_ptr || !pooled) return fail("aqg_graph_mean_pool: null argument");
+    return launch_gen_mean_pool(N, H, graph_ptr, num_graphs, pooled, (hipStream_t)stream);
+}
+
+int aqg_graph_mean_pool_backward(int num_nodes, int N, const float* dpooled, const int32_t* graph_ptr, int num_graphs,
+                                 const float* mask, float* dH, void* stream) {
+    if (num_nodes < 0 || N < 0 || num_graphs < 0) return fail("aqg_graph_mean_pool_backward: negative size");
+    if (num_nodes == 0 || N == 0) return 0;
+    if (num_graphs == 0) return fail("aqg_graph_mean_pool_backward: nodes without graphs");
+    if (!dpooled || !graph_ptr || !dH) return fail("aqg_graph_mean_pool_backward: null argument");
+    return launch_gen_mean_pool_backward(num_nodes, N, dpooled, graph_ptr, num_graphs, mask, dH, (hipStream_t)stream);
+}
+
+int aqg_graph_heads(int num_graphs, int A, const float* logits, const float* value_pre, float* policy, float* value,
+                    void* stream) {
+    if (num_graphs < 0 || A <= 0) return fail("aqg_graph_heads: bad size");
+    if (num_graphs == 0) return 0;
+    if (!logits || !policy || (!value_pre != !value)) return fail("aqg_graph_heads: null argument");
+    return launch_gen_heads(num_graphs, A, logits, value_pre, policy, value, (hipStream_t)stream);
+}
+
+int aqg_graph_heads_backward(int num_graphs, int A, const float* policy, const float* dpolicy, const float* value,
+                             const float* dvalue, float* dlogits, float* dvalue_pre, void* stream) {
+    if (num_graphs < 0 || A <= 0) return fail("aqg_graph_heads_backward: bad size");
+    if (num_graphs == 0) return 0;
+    if ((dpolicy && !policy) || (dvalue && !value)) return fail("aqg_graph_heads_backward: null argument");
+    return launch_gen_heads_backward(num_graphs, A, policy, dpolicy, value, dvalue, dlogits, dvalue_pre, (hipStream_t)stream);
+}
+
+int aqg_gcn_boards_graph(int board_size, const uint8_t* states72, int B, float* x, int32_t* ell_idx, float* ell_w, void* stream) {
+    if (B < 0) return fail("aqg_gcn_boards_graph: negative size");
+    if (B > 0 && (!states72 || !x || !ell_idx || !ell_w)) return fail("aqg_gcn_boards_graph: null argument");
+    return launch_gcn_boards_graph(board_size, states72, 0, B, x, ell_idx, ell_w, (hipStream_t)stream);
 }
 
 int aqg_engine_reset(const aqg_engine* e, void* stream) {

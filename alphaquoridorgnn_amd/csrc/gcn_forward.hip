@@ -1982,4 +1982,20 @@ int launch_gcn_forward_boards_any(int N, const void* states, int fmt, int B, con
     return check_launch("gcn_heads_kernel");
 }
 
+// The board featuriser alone, for the width-generic graph primitives (gcn_general.hip): x0 [B*V,6] node features and the
+// normalised adjacency as ELL rows of 5 (self loop first, then the open neighbours; a closed side has index -1, weight 0).
+int launch_gcn_boards_graph(int N, const void* states, int fmt, int B, float* x0, int32_t* ell_idx, float* ell_w, hipStream_t st) {
+    if (!(N == 3 || N == 5 || N == 7 || N == 9)) return fail("board_size must be 3, 5, 7 or 9");
+    if (B <= 0) return 0;
+    const int R = B * N * N;
+    const dim3 pg((R + 255) / 256), blk(256);
+    switch (N) {
+        case 3: hipLaunchKernelGGL(boards_prep_kernel<3>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
+        case 5: hipLaunchKernelGGL(boards_prep_kernel<5>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
+        case 7: hipLaunchKernelGGL(boards_prep_kernel<7>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
+        default: hipLaunchKernelGGL(boards_prep_kernel<9>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
+    }
+    return check_launch("boards_prep_kernel");
+}
+
 }  // namespace aqg

@@ -31,6 +31,8 @@ class BatchedSelfPlay:
         (include/aqgnn.h, `eval_cache_keys`): a leaf whose position this slot has already sent through the network is expanded from
         the stored priors / value / legal list -- bit-identical searches and game records, fewer network evaluations (736 bytes of
         HBM per entry)."""
+        if evaluator == "gnn" and model is not None and not getattr(model, "fused", True):
+            model._require_fused("evaluator='gnn'")          # before anything is allocated or launched
         self.dev = _lib.require_gpu(device)
         self.lib = _lib.load()
         self.N = board_size

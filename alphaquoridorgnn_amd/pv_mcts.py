@@ -54,9 +54,10 @@ def pv_mcts_policy_batch(model, states72, temperature, sims=None, board_size=Non
 
 
 def evaluator_of(model):
-    """'gnn' for the network the HIP kernels evaluate themselves; 'external' for any other object with the reference's
-    predict(state, device) (BaseNetwork.py:36-40) -- e.g. the CNN the reference wires (self_play.py:16,78)."""
-    return "gnn" if hasattr(model, "packed_weights") else "external"
+    """'gnn' for the network the HIP kernels evaluate themselves (the default 6/128/3 shape); 'external' for any other
+    object with the reference's predict(state, device) (BaseNetwork.py:36-40) -- e.g. the CNN the reference wires
+    (self_play.py:16,78), or a GraphPolicyValueNetwork of another shape."""
+    return "gnn" if hasattr(model, "packed_weights") and getattr(model, "fused", True) else "external"
 
 
 def pv_mcts_policy(model, state, temperature, device=None):

@@ -9,6 +9,11 @@ Added (absent from the reference): `forward_states(states72)` -- the 
 self-play engine uses -- and `GNNNetwork`, the BaseNetwork-style wrapper (BaseNetwork.py:9-54) giving
 `predict / prep_for_inference / preprocess_input / name`.
 
+Any shape: the reference's GraphPolicyValueNetwork takes any (num_features, hidden_dim, num_gcn_layers, policy_output_size).
+The default 6/128/3 network (`fused`) runs the fused kernels; every other shape (within SHAPE_LIMITS) runs the width-generic
+graph primitives of csrc/gcn_general.hip, which also serve `GCNConv.forward(x, edge_index)` and `global_mean_pool(x, batch)`
+-- PyG's calls, on any layer -- forward and backward.
+
 All arithmetic runs in libaqgnn_hip.so (fp32 data; fp16-split or f32-input MFMA, see csrc/gcn_forward.hip); there is no
 torch/CPU forward in this file.
 """
@@ -29,6 +34,9 @@ HIDDEN_DIM = 128      # :18
 NUM_GCN_LAYERS = 3    # :19
 POLICY_OUTPUT_SIZE = BOARD_SIZE ** 2 + 2 * (BOARD_SIZE - 1) ** 2  # :20
 
+# inclusive bounds of the shapes the width-generic kernels take (GraphPolicyValueNetwork raises ValueError outside them)
+SHAPE_LIMITS = {"num_features": (1, 1024), "hidden_dim": (2, 1024), "num_gcn_layers": (1, 32), "policy_output_size": (1, 4096)}
+
 STATE_DICT_KEYS = [
     "gcn_layers.0.lin.weight", "gcn_layers.0.bias", "gcn_layers.1.lin.weight", "gcn_layers.1.bias",
     "gcn_layers.2.lin.weight", "gcn_layers.2.bias", "policy_head.0.weight", "policy_head.0.bias",
@@ -37,9 +45,19 @@ STATE_DICT_KEYS = [
 ]
 
 
+def state_dict_keys(num_gcn_layers):
+    """The parameter names of a network with `num_gcn_layers` GCN layers, in the order of the HIP entry points
+    (STATE_DICT_KEYS for the default 3)."""
+    keys = []
+    for i in range(num_gcn_layers):
+        keys += [f"gcn_layers.{i}.lin.weight", f"gcn_layers.{i}.bias"]
+    return keys + STATE_DICT_KEYS[6:]
+
+
 class GCNConv(nn.Module):
-    """Parameter container with PyG's GCNConv naming and initialisation (lin: Glorot-uniform, no bias; bias: zeros).
-    The layer arithmetic is fused into the network-level HIP kernels, so it has no stand-alone forward."""
+    """PyG's GCNConv with its naming and initialisation (lin: Glorot-uniform, no bias; bias: zeros).  Inside a default
+    6/128/3 network the layer arithmetic is fused into the network-level kernels; forward(x, edge_index) runs the layer alone
+    on the width-generic kernels (any in / out width)."""
 
     def __init__(self, in_channels, out_channels):
         super().__init__()
@@ -51,15 +69,37 @@ class GCNConv(nn.Module):
             self.lin.weight.uniform_(-a, a)
 
     def forward(self, x, edge_index):
-        raise NotImplementedError("GCNConv is evaluated inside GraphPolicyValueNetwork.forward (fused HIP kernels)")
+        """PyG's GCNConv.forward with its defaults: A_hat (x W^T) + b, no ReLU.  x [n, in_channels] floating point,
+        edge_index [2, E] integer ids in [0, n); gcn_norm and validation as GraphPolicyValueNetwork._prepare_graph (one
+        device-to-host read).  Returns f32 [n, out_channels]; differentiable with respect to x, lin.weight and bias."""
+        dev = _lib.require_gpu(x.device)
+        W, b = self.lin.weight, self.bias
+        if x.dim() == 2 and x.shape[1] == self.in_channels:
+            batch = torch.zeros((x.shape[0],), dtype=torch.int64, device=dev)
+        else:
+            batch = torch.zeros((0,), dtype=torch.int64, device=dev)      # (_prepare_graph names the shape error of x)
+        record = torch.is_grad_enabled() and (x.requires_grad or W.requires_grad or b.requires_grad)
+        tensors = GraphPolicyValueNetwork._prepare_graph(x, edge_index, batch, transpose=record, num_features=self.in_channels)
+        xf = x.to(torch.float32).contiguous()
+        if record:
+            return _GCNConvFunction.apply(tensors, dev, xf, W, b)
+        return _gcn_conv(_lib.load(), dev, xf, tensors[:3], _param(W, dev), _param(b, dev))
 
 
 class GraphPolicyValueNetwork(nn.Module):
     def __init__(self, num_features=NUM_FEATURES, hidden_dim=HIDDEN_DIM, num_gcn_layers=NUM_GCN_LAYERS,
                  policy_output_size=POLICY_OUTPUT_SIZE, board_size=BOARD_SIZE):
         super().__init__()
-        if (num_features, hidden_dim, num_gcn_layers) != (NUM_FEATURES, HIDDEN_DIM, NUM_GCN_LAYERS):
-            raise ValueError("the HIP kernels are built for the reference configuration 6/128/3 (pv_network_gnn.py:17-19)")
+        for name, v in (("num_features", num_features), ("hidden_dim", hidden_dim), ("num_gcn_layers", num_gcn_layers),
+                        ("policy_output_size", policy_output_size)):
+            lo, hi = SHAPE_LIMITS[name]
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError(f"{name} must be an integer in [{lo}, {hi}] (the limit of the HIP kernels), got {v!r}")
+        num_features, hidden_dim, num_gcn_layers, policy_output_size = (int(num_features), int(hidden_dim), int(num_gcn_layers),
+                                                                        int(policy_output_size))
+        # the default shape runs the fused kernels (packed weights, engine, GNNTrainer); any other the width-generic primitives
+        self.fused = (num_features, hidden_dim, num_gcn_layers) == (NUM_FEATURES, HIDDEN_DIM, NUM_GCN_LAYERS)
+        self.state_dict_keys = state_dict_keys(num_gcn_layers)
         self.num_features = num_features
         self.hidden_dim = hidden_dim
         self.num_gcn_layers = num_gcn_layers
@@ -82,7 +122,8 @@ class GraphPolicyValueNetwork(nn.Module):
     # ---------------------------------------------------------------- weight packing
     def packed_weights(self, device):
         """float32 device buffer in the kernel layout (include/aqgnn.h); rebuilt when a parameter changes.  Every rebuild
-        also re-runs the fp16-range check of this weight set (`gnn_flags`)."""
+        also re-runs the fp16-range check of this weight set (`gnn_flags`).  Default 6/128/3 shape only."""
+        self._require_fused("packed_weights (the fused kernels' weight layout)")
         sd = self.state_dict()
         key = (str(device),) + tuple((sd[k].data_ptr(), sd[k]._version) for k in STATE_DICT_KEYS)
         if self._packed is None or key != self._packed_key:
@@ -125,6 +166,14 @@ class GraphPolicyValueNetwork(nn.Module):
             h = R * z + b
             worst = max(worst, float(z.max()), float(h.max()), float(W.max()))
         return bool(np.isfinite(worst)) and 2.3 * worst < 65504.0
+
+    def _require_fused(self, what):
+        if not self.fused:
+            raise ValueError(
+                f"{what} exists for the default {NUM_FEATURES}/{HIDDEN_DIM}/{NUM_GCN_LAYERS} network only; this one is "
+                f"{self.num_features}/{self.hidden_dim}/{self.num_gcn_layers}: train it with autograd (forward(x, edge_index, batch), "
+                "loss.backward() and a torch optimiser) instead of GNNTrainer, and search with evaluator='external' (its predict) "
+                "instead of the engine's 'gnn' evaluator")
 
     def invalidate_packed(self):
         """Call after the parameters were changed behind torch's back (train_network.GNNTrainer updates them in place from
@@ -209,6 +258,8 @@ class GraphPolicyValueNetwork(nn.Module):
         host sync); if a value left fp16 range the weight set is marked (mark_saturated) and the call is repeated on the
         exact f32-input kernels, so the caller always receives the network's outputs -- the reference's fp32 has no cliff
         (pv_network_gnn.py:53-64).  False skips the read-back (the engine has its own counter, counters()['gnn_saturated'])."""
+        if not self.fused:
+            return self._forward_states_general(states72, want_logits, state_fmt)
         dev = _lib.require_gpu(states72.device)
         lib = _lib.load()
         B = states72.shape[0]
@@ -242,13 +293,39 @@ class GraphPolicyValueNetwork(nn.Module):
             return policy, value.unsqueeze(1), logits, vpre
         return policy, value.unsqueeze(1)
 
+    def _forward_states_general(self, states72, want_logits, state_fmt):
+        """forward_states of a non-default shape: the board featuriser (aqg_gcn_boards_graph) and the width-generic layers."""
+        if self.num_features != 6:
+            raise ValueError(f"board records have 6 feature planes; this network takes num_features={self.num_features}: "
+                             "use forward(x, edge_index, batch)")
+        if state_fmt != 0:
+            raise ValueError("a network of non-default shape takes state72 records (state_fmt=0) only")
+        dev = _lib.require_gpu(states72.device)
+        lib = _lib.load()
+        N = self.board_size
+        V, B = N * N, states72.shape[0]
+        R = B * V
+        x = torch.empty((R, 6), dtype=torch.float32, device=dev)
+        idx = torch.empty((R * 5,), dtype=torch.int32, device=dev)
+        w = torch.empty((R * 5,), dtype=torch.float32, device=dev)
+        if B:
+            _lib.check(lib.aqg_gcn_boards_graph(N, _lib.ptr(states72.contiguous()), B, _lib.ptr(x), _lib.ptr(idx), _lib.ptr(w),
+                                                _lib.stream_ptr(dev)), "aqg_gcn_boards_graph")
+        csr = (torch.arange(0, 5 * R + 1, 5, dtype=torch.int32, device=dev), idx, w)     # ELL rows of 5 (closed sides: id -1)
+        gptr = torch.arange(0, R + 1, V, dtype=torch.int32, device=dev)
+        pf = [_param(p, dev) for _, p in self._ordered_params()]
+        policy, value, logits, vpre = _general_forward(lib, dev, self, x, csr, gptr, B, pf)[:4]
+        if want_logits:
+            return policy, value.unsqueeze(1), logits, vpre
+        return policy, value.unsqueeze(1)
+
     # ---------------------------------------------------------------- generic (x, edge_index, batch) path
     @staticmethod
-    def _prepare_graph(x, edge_index, batch, transpose=False):
+    def _prepare_graph(x, edge_index, batch, transpose=False, num_features=NUM_FEATURES):
         """Everything forward(x, edge_index, batch) does before its launch, on x's device (CPU or GPU alike):
         validation, PyG's gcn_norm as a CSR by destination, and the graph pointer of the mean pool.
 
-        Raises ValueError unless x is [n, 6] floating point, edge_index an integer [2, E] tensor with every id in [0, n),
+        Raises ValueError unless x is [n, num_features] floating point, edge_index an integer [2, E] tensor with every id in [0, n),
         and batch an integer [n] tensor, non-negative and sorted (PyG's Batch convention; unsorted batches are not
         supported).  The id and batch checks share ONE device-to-host read, made before any tensor is indexed with the ids.
 
@@ -263,8 +340,8 @@ class GraphPolicyValueNetwork(nn.Module):
         built on the device without another host read."""
         def integral(t):
             return not (t.is_floating_point() or t.is_complex() or t.dtype == torch.bool)
-        if x.dim() != 2 or x.shape[1] != NUM_FEATURES or not x.is_floating_point():
-            raise ValueError(f"x must be a floating-point [num_nodes, {NUM_FEATURES}] tensor, got {x.dtype} {tuple(x.shape)}")
+        if x.dim() != 2 or x.shape[1] != num_features or not x.is_floating_point():
+            raise ValueError(f"x must be a floating-point [num_nodes, {num_features}] tensor, got {x.dtype} {tuple(x.shape)}")
         n = x.shape[0]
         if edge_index.dim() != 2 or edge_index.shape[0] != 2 or not integral(edge_index):
             raise ValueError(f"edge_index must be an integer [2, E] tensor, got {edge_index.dtype} {tuple(edge_index.shape)}")
@@ -313,11 +390,15 @@ class GraphPolicyValueNetwork(nn.Module):
         """pv_network_gnn.py:53-64 with PyG's GCNConv / global_mean_pool semantics (_prepare_graph: the self-loop rule and the
         validated inputs).  x [sum V, 6] floating point, edge_index [2, E] integer ids in [0, sum V), batch [sum V] integer,
         non-negative and sorted (unsorted raises ValueError).  One device-to-host read per call once the weights are packed.
+        A network of non-default shape (x [sum V, num_features]) runs the width-generic kernels (csrc/gcn_general.hip) with
+        the same semantics, the same single read and the same autograd contract.
 
         Autograd: in train mode, with grad enabled and x or any parameter requiring grad, the forward is recorded
         (_GraphForward): the outputs carry a grad_fn and backward() fills the parameters' .grad (and x.grad) from HIP
         kernels (csrc/gcn_graph_grad.hip).  Its values are bit-identical to the plain forward's.  Otherwise (eval mode,
         no_grad, inference_mode) the outputs carry no graph."""
+        if not self.fused:
+            return self._forward_general(x, edge_index, batch)
         dev = _lib.require_gpu(x.device)
         params = [p for _, p in self._ordered_params()]
         if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
@@ -344,9 +425,43 @@ class GraphPolicyValueNetwork(nn.Module):
         self.last_logits, self.last_value_pre = logits, vpre
         return policy, value.unsqueeze(1)
 
+    def _forward_general(self, x, edge_index, batch):
+        dev = _lib.require_gpu(x.device)
+        params = [p for _, p in self._ordered_params()]
+        record = self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+        tensors = self._prepare_graph(x, edge_index, batch, transpose=record, num_features=self.num_features)
+        xf = x.to(torch.float32).contiguous()
+        if record:
+            policy, value, logits, vpre = _GeneralForward.apply(self, tensors, dev, xf, *params)
+        else:
+            pf = [_param(p, dev) for p in params]
+            policy, value, logits, vpre = _general_forward(_lib.load(), dev, self, xf, tensors[:3], tensors[3], tensors[4], pf)[:4]
+        self.last_logits, self.last_value_pre = logits, vpre
+        return policy, value.unsqueeze(1)
+
+    def predict_batch(self, states72):
+        """Batched predict: device uint8 [B,72] -> (policy [B,A] over ALL actions, value [B])."""
+        policy, value = self.forward_states(states72)
+        return policy, value[:, 0]
+
+    def predict(self, state, device=None):
+        """pv_network_cnn.py:117-137: PMF over state.legal_actions() (in that order) as float32 numpy + python float."""
+        dev = _lib.require_gpu()
+        rec = torch.from_numpy(state.record() if hasattr(state, "record") else
+                               game_logic.pack_state72(state.player, state.enemy, state.walls, state.plies_played, state.N)
+                               ).to(dev).unsqueeze(0)
+        with torch.inference_mode():
+            policy, value = self.forward_states(rec)
+            _, order, count = game_logic.legal_actions_batch(rec, self.board_size, want_mask=False)
+            n = int(count.item())
+            pol = policy[0][order[0, :n].long()]
+            s = torch.sum(pol)
+            pol = pol / (s if s else 1)
+        return pol.cpu().numpy(), value.item()
+
     def _ordered_params(self):
         sd = dict(self.named_parameters())
-        return [(k, sd[k]) for k in STATE_DICT_KEYS]
+        return [(k, sd[k]) for k in self.state_dict_keys]
 
 
 class _GraphForward(torch.autograd.Function):
@@ -411,6 +526,215 @@ class _GraphForward(torch.autograd.Function):
         return (None, None, None, dx if want_dx else None, *out)
 
 
+# ---------------------------------------------------------------- width-generic graph primitives (csrc/gcn_general.hip)
+def _param(p, dev):
+    """A parameter as the kernels read it: f32, contiguous, on dev (the parameter itself when it already is)."""
+    return p.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _empty(shape, dev):
+    return torch.empty(shape, dtype=torch.float32, device=dev)
+
+
+def _linear(lib, dev, X, W, bias=None, relu=False, mask=None, w_kn=False, out=None, accumulate=False):
+    """aqg_graph_linear: X [M,K] W^T (+ bias) (ReLU) (masked); W [N,K], or [K,N] with w_kn (X W)."""
+    M, K = X.shape
+    N = W.shape[1] if w_kn else W.shape[0]
+    Y = _empty((M, N), dev) if out is None else out
+    flags = (_lib.LIN_RELU if relu else 0) | (_lib.LIN_W_KN if w_kn else 0) | (_lib.LIN_ACCUMULATE if accumulate else 0)
+    _lib.check(lib.aqg_graph_linear(M, K, N, _lib.ptr(X), _lib.ptr(W), _lib.ptr(bias), _lib.ptr(mask), flags, _lib.ptr(Y),
+                                    _lib.stream_ptr(dev)), "aqg_graph_linear")
+    return Y
+
+
+def _linear_grad(lib, dev, dY, X, dYb=None):
+    """aqg_graph_linear_grad: (dW [N,K] = dY^T X, db [N] = column sums of dYb, default dY)."""
+    M, N = dY.shape
+    K = X.shape[1]
+    nws = int(lib.aqg_graph_linear_grad_workspace_floats(M, N, K))
+    ws = _empty((nws,), dev) if nws else None
+    dW, db = _empty((N, K), dev), _empty((N,), dev)
+    _lib.check(lib.aqg_graph_linear_grad(M, K, N, _lib.ptr(dY), _lib.ptr(X), _lib.ptr(dYb), _lib.ptr(ws), nws, _lib.ptr(dW),
+                                         _lib.ptr(db), _lib.stream_ptr(dev)), "aqg_graph_linear_grad")
+    return dW, db
+
+
+def _aggregate(lib, dev, Y, csr, bias=None, relu=False):
+    """aqg_graph_aggregate over csr = (ptr, src, w): the CSR by destination (propagate) or by source (its backward)."""
+    n, N = Y.shape
+    out = _empty((n, N), dev)
+    ptr, src, w = csr
+    _lib.check(lib.aqg_graph_aggregate(n, N, _lib.ptr(Y), _lib.ptr(ptr), _lib.ptr(src), _lib.ptr(w), _lib.ptr(bias), int(relu),
+                                       _lib.ptr(out), _lib.stream_ptr(dev)), "aqg_graph_aggregate")
+    return out
+
+
+def _mean_pool(lib, dev, H, gptr, G):
+    n, N = H.shape
+    pooled = _empty((G, N), dev)
+    _lib.check(lib.aqg_graph_mean_pool(n, N, _lib.ptr(H), _lib.ptr(gptr), G, _lib.ptr(pooled), _lib.stream_ptr(dev)),
+               "aqg_graph_mean_pool")
+    return pooled
+
+
+def _mean_pool_backward(lib, dev, dpooled, gptr, G, n, mask=None):
+    N = dpooled.shape[1]
+    dH = _empty((n, N), dev)
+    _lib.check(lib.aqg_graph_mean_pool_backward(n, N, _lib.ptr(dpooled), _lib.ptr(gptr), G, _lib.ptr(mask), _lib.ptr(dH),
+                                                _lib.stream_ptr(dev)), "aqg_graph_mean_pool_backward")
+    return dH
+
+
+def _gcn_conv(lib, dev, xf, csr, W, b, relu=False):
+    """One GCNConv: A_hat (x W^T) + b (ReLU)."""
+    return _aggregate(lib, dev, _linear(lib, dev, xf, W), csr, bias=b, relu=relu)
+
+
+def _general_forward(lib, dev, model, xf, csr, gptr, G, pf):
+    """The network on the width-generic primitives: L x (linear, aggregate + bias + ReLU) -> mean pool -> the two heads ->
+    softmax / tanh.  Returns (policy [G,A], value [G], logits [G,A], value_pre [G], acts) with acts = (H_0 = x, H_1 .. H_L,
+    pooled, policy hidden, value hidden) -- what the backward reads."""
+    L, A = model.num_gcn_layers, model.policy_output_size
+    hs = [xf]
+    for l in range(L):
+        hs.append(_gcn_conv(lib, dev, hs[-1], csr, pf[2 * l], pf[2 * l + 1], relu=True))
+    pooled = _mean_pool(lib, dev, hs[-1], gptr, G)
+    o = 2 * L
+    hp = _linear(lib, dev, pooled, pf[o], pf[o + 1], relu=True)
+    logits = _linear(lib, dev, hp, pf[o + 2], pf[o + 3])
+    hv = _linear(lib, dev, pooled, pf[o + 4], pf[o + 5], relu=True)
+    vpre = _linear(lib, dev, hv, pf[o + 6], pf[o + 7]).view(G)
+    policy, value = _empty((G, A), dev), _empty((G,), dev)
+    _lib.check(lib.aqg_graph_heads(G, A, _lib.ptr(logits), _lib.ptr(vpre), _lib.ptr(policy), _lib.ptr(value), _lib.stream_ptr(dev)),
+               "aqg_graph_heads")
+    return policy, value, logits, vpre, (hs, pooled, hp, hv)
+
+
+class _GeneralForward(torch.autograd.Function):
+    """forward(x, edge_index, batch) of a non-default shape as one autograd node: _general_forward with its activations kept,
+    and the backward composed from the same primitives.  Neither direction reads anything back to the host."""
+
+    @staticmethod
+    def forward(ctx, model, tensors, dev, xf, *params):
+        ptr, src, w, gptr, G, tptr, tdst, tw = tensors
+        lib = _lib.load()
+        pf = [_param(p, dev) for p in params]
+        policy, value, logits, vpre, acts = _general_forward(lib, dev, model, xf, (ptr, src, w), gptr, G, pf)
+        ctx.save_for_backward(policy, value, *pf)
+        ctx.graph = ((tptr, tdst, tw), gptr, G, dev, model.num_gcn_layers)
+        ctx.param_dtypes = [p.dtype for p in params]
+        ctx.acts = acts
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(logits, vpre)
+        return policy, value, logits, vpre
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dpolicy, dvalue, _dlogits, _dvpre):
+        policy, value, *pf = ctx.saved_tensors
+        tcsr, gptr, G, dev, L = ctx.graph
+        hs, pooled, hp, hv = ctx.acts
+        lib = _lib.load()
+        n, A = hs[0].shape[0], policy.shape[1]
+        grads = [None] * (2 * L + 8)
+        dp = dpolicy.to(torch.float32).contiguous() if dpolicy is not None else None
+        dv = dvalue.to(torch.float32).contiguous() if dvalue is not None else None
+        dlogits, dvpre = _empty((G, A), dev), _empty((G, 1), dev)
+        _lib.check(lib.aqg_graph_heads_backward(G, A, _lib.ptr(policy), _lib.ptr(dp), _lib.ptr(value), _lib.ptr(dv),
+                                                _lib.ptr(dlogits), _lib.ptr(dvpre), _lib.stream_ptr(dev)), "aqg_graph_heads_backward")
+        o = 2 * L
+        grads[o + 2], grads[o + 3] = _linear_grad(lib, dev, dlogits, hp)               # policy_head.2
+        grads[o + 6], grads[o + 7] = _linear_grad(lib, dev, dvpre, hv)                 # value_head.2
+        dhp = _linear(lib, dev, dlogits, pf[o + 2], mask=hp, w_kn=True)
+        dhv = _linear(lib, dev, dvpre, pf[o + 6], mask=hv, w_kn=True)
+        grads[o], grads[o + 1] = _linear_grad(lib, dev, dhp, pooled)                   # policy_head.0
+        grads[o + 4], grads[o + 5] = _linear_grad(lib, dev, dhv, pooled)               # value_head.0
+        dpooled = _linear(lib, dev, dhp, pf[o], w_kn=True)
+        _linear(lib, dev, dhv, pf[o + 4], w_kn=True, out=dpooled, accumulate=True)
+        dP = _mean_pool_backward(lib, dev, dpooled, gptr, G, n, mask=hs[L])
+        dx = None
+        for l in range(L, 0, -1):                 # P_l = A_hat (H_{l-1} W_l^T) + b_l, H_l = relu(P_l)
+            dZ = _aggregate(lib, dev, dP, tcsr)
+            grads[2 * l - 2], grads[2 * l - 1] = _linear_grad(lib, dev, dZ, hs[l - 1], dYb=dP)
+            if l > 1:
+                dP = _linear(lib, dev, dZ, pf[2 * l - 2], mask=hs[l - 1], w_kn=True)
+            elif ctx.needs_input_grad[3]:
+                dx = _linear(lib, dev, dZ, pf[0], w_kn=True)
+        out = [g.view(pf[i].shape) if ctx.needs_input_grad[4 + i] else None for i, g in enumerate(grads)]
+        out = [o.to(ctx.param_dtypes[i]) if o is not None else None for i, o in enumerate(out)]
+        return (None, None, None, dx, *out)
+
+
+class _GCNConvFunction(torch.autograd.Function):
+    """GCNConv.forward as one autograd node: out = A_hat Z + b with Z = x W^T;  dZ = A_hat^T dout, dW = dZ^T x,
+    db = sum_i dout[i], dx = dZ W."""
+
+    @staticmethod
+    def forward(ctx, tensors, dev, xf, W, b):
+        ptr, src, w, _gptr, _G, tptr, tdst, tw = tensors
+        Wf, bf = _param(W, dev), _param(b, dev)
+        out = _gcn_conv(_lib.load(), dev, xf, (ptr, src, w), Wf, bf)
+        ctx.save_for_backward(xf, Wf)
+        ctx.graph = ((tptr, tdst, tw), dev)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        xf, Wf = ctx.saved_tensors
+        tcsr, dev = ctx.graph
+        lib = _lib.load()
+        dout = dout.to(torch.float32).contiguous()
+        dZ = _aggregate(lib, dev, dout, tcsr)
+        dW, db = _linear_grad(lib, dev, dZ, xf, dYb=dout)
+        dx = _linear(lib, dev, dZ, Wf, w_kn=True) if ctx.needs_input_grad[2] else None
+        return (None, None, dx, dW if ctx.needs_input_grad[3] else None, db if ctx.needs_input_grad[4] else None)
+
+
+class _MeanPoolFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gptr, G, dev, xf):
+        ctx.graph = (gptr, G, dev, xf.shape[0])
+        return _mean_pool(_lib.load(), dev, xf, gptr, G)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dpooled):
+        gptr, G, dev, n = ctx.graph
+        dH = _mean_pool_backward(_lib.load(), dev, dpooled.to(torch.float32).contiguous(), gptr, G, n)
+        return None, None, None, dH
+
+
+def global_mean_pool(x, batch, size=None):
+    """PyG's global_mean_pool on the pool kernel: x [n, F] floating point, batch [n] integer graph ids, non-negative and
+    sorted (PyG's Batch convention; None = one graph), size = number of graphs (default batch.max() + 1).  Returns f32
+    [size, F]; a graph id without nodes pools to 0.  Differentiable with respect to x.  At most one device-to-host read."""
+    dev = _lib.require_gpu(x.device)
+    if x.dim() != 2 or not x.is_floating_point():
+        raise ValueError(f"x must be a floating-point [num_nodes, F] tensor, got {x.dtype} {tuple(x.shape)}")
+    n = x.shape[0]
+    if batch is None:
+        batch = torch.zeros((n,), dtype=torch.int64, device=dev)
+        size = 1 if size is None else size
+    if batch.dim() != 1 or batch.shape[0] != n or batch.is_floating_point() or batch.is_complex() or batch.dtype == torch.bool:
+        raise ValueError(f"batch must be an integer [num_nodes] = [{n}] tensor, got {batch.dtype} {tuple(batch.shape)}")
+    batch = batch.to(dev).long()
+    if n:
+        first, last, unsorted = torch.stack([batch[0], batch[-1], (batch[1:] < batch[:-1]).sum()]).tolist()
+        if unsorted:
+            raise ValueError("batch must be sorted (PyG Batch convention; unsorted batches are not supported)")
+        if first < 0:
+            raise ValueError(f"batch ids must be non-negative (min {first})")
+    G = (last + 1 if n else 0) if size is None else int(size)
+    if G < 0 or (n and last >= G):
+        raise ValueError(f"size {G} does not cover the batch ids (max {last if n else None})")
+    gptr = torch.searchsorted(batch, torch.arange(G + 1, device=dev)).to(torch.int32)
+    xf = x.to(torch.float32).contiguous()
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _MeanPoolFunction.apply(gptr, G, dev, xf)
+    return _mean_pool(_lib.load(), dev, xf, gptr, G)
+
+
 class GNNNetwork(GraphPolicyValueNetwork):
     """BaseNetwork-style wrapper (BaseNetwork.py:9-54; reference implementation of the contract:
     pv_network_cnn.py:50-140) around the GNN.  `optimised_model` of the reference (TensorRT) has no counterpart:
@@ -440,26 +764,6 @@ class GNNNetwork(GraphPolicyValueNetwork):
         for i, (player, enemy, walls) in enumerate(game_state_arrays):
             out[i] = game_logic.pack_state72(player, enemy, walls, 0, self.board_size)
         return out
-
-    def predict_batch(self, states72):
-        """Batched predict: device uint8 [B,72] -> (policy [B,A] over ALL actions, value [B])."""
-        policy, value = self.forward_states(states72)
-        return policy, value[:, 0]
-
-    def predict(self, state, device=None):
-        """pv_network_cnn.py:117-137: PMF over state.legal_actions() (in that order) as float32 numpy + python float."""
-        dev = _lib.require_gpu()
-        rec = torch.from_numpy(state.record() if hasattr(state, "record") else
-                               game_logic.pack_state72(state.player, state.enemy, state.walls, state.plies_played, state.N)
-                               ).to(dev).unsqueeze(0)
-        with torch.inference_mode():
-            policy, value = self.forward_states(rec)
-            _, order, count = game_logic.legal_actions_batch(rec, self.board_size, want_mask=False)
-            n = int(count.item())
-            pol = policy[0][order[0, :n].long()]
-            s = torch.sum(pol)
-            pol = pol / (s if s else 1)
-        return pol.cpu().numpy(), value.item()
 
     def train_model(self, data_loader, optimizer, loss_fn, device='cpu', num_epochs=10):
         pass  # stub in the reference as well (pv_network_cnn.py:139-140); training is SURVEY 8(f1), a later row

@@ -42,6 +42,8 @@ class GNNTrainer:
     """Adam state + workspace for optimisation steps of up to `max_batch` positions on `model` (a GNNNetwork on the GPU)."""
 
     def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8):
+        if not getattr(model, "fused", True):
+            model._require_fused("GNNTrainer (the fused training kernels)")
         self.model = model
         self.lib = _lib.load()
         sd = model.state_dict()

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define AQG_MAX_LEGAL 136 /* >= 5 pawn moves + 128 wall placements */
-#define AQG_ABI_VERSION 12
+#define AQG_ABI_VERSION 13
 
 int aqg_abi_version(void);
 const char* aqg_last_error(void);
@@ -188,6 +188,57 @@ int aqg_gcn_backward_graph(int num_features, int num_actions, const float* x, in
                            const float* policy, const float* value, const float* dpolicy, const float* dvalue,
                            const float* const* params_host, float* workspace, size_t workspace_floats,
                            float* const* grads_host, float* dx, void* stream);
+
+/* ------------------------------------------------------------------ width-generic graph primitives (ABI 13)
+ *
+ * The building blocks of GraphPolicyValueNetwork at ANY shape (num_features, hidden_dim, num_gcn_layers, policy_output_size),
+ * of the stand-alone GCNConv.forward(x, edge_index) and of global_mean_pool, forward and backward (csrc/gcn_general.hip; the
+ * composition is pv_network_gnn.py).  The default 6/128/3 network keeps the fused entry points above.  Every buffer is f32 and
+ * contiguous (row-major); sizes are runtime values.  Every contraction runs on the f32-input MFMA (a k-ordered fmaf chain) and
+ * no kernel uses atomics: each sum runs in an order fixed by the sizes, so results are deterministic.  A call with no rows
+ * (M, num_nodes or num_graphs 0) launches nothing (aqg_graph_linear_grad writes zero gradients).
+ *
+ * aqg_graph_linear: Y[M,N] = X[M,K] W^T (+ bias[N]) -- nn.Linear / GCNConv.lin; W [N,K] in PyTorch's [out, in] layout straight
+ *   from the parameter (flags & AQG_LIN_W_KN: W is [K,N] and Y = X W, the backward's dX = dY W).  bias may be NULL.  Then, in
+ *   this order: AQG_LIN_ACCUMULATE adds the result to what Y holds; AQG_LIN_RELU applies max(., 0); a non-NULL mask [M,N]
+ *   zeroes every element whose mask entry is not > 0 (the ReLU backward, with the saved post-ReLU activation as the mask).
+ * aqg_graph_linear_grad: dW[N,K] = dY[M,N]^T X[M,K] and db[N] = sum over m of dYb[M,N] (dYb NULL = dY; db may be NULL):
+ *   per-row-chunk partial tiles, then a fixed-order reduce, in `workspace` of aqg_graph_linear_grad_workspace_floats(M, N, K)
+ *   floats.  Overwrites dW and db.
+ * aqg_graph_aggregate: out[i][c] = (relu) ((bias ? bias[c] : 0) + sum over e = csr_ptr[i] .. csr_ptr[i+1] of
+ *   csr_w[e] Y[csr_src[e]][c]), the entries in CSR order, Y and out [num_nodes, N].  An entry with csr_src < 0 is skipped (the
+ *   board featuriser's ELL rows); every other id must lie in [0, num_nodes): nothing here checks it.  With the CSR by
+ *   DESTINATION of GraphPolicyValueNetwork._prepare_graph it is GCNConv's propagate + bias; with its CSR by SOURCE (transpose=True),
+ *   no bias and no ReLU, it is the backward A_hat^T dP.
+ * aqg_graph_mean_pool: pooled[g] = mean of H[graph_ptr[g] .. graph_ptr[g+1]) (global_mean_pool; an empty graph pools to 0).
+ * aqg_graph_mean_pool_backward: dH[i] = dpooled[g(i)] / |g(i)|, zeroed where mask [num_nodes, N] (may be NULL) is not > 0.
+ *   Every node must lie in some graph: graph_ptr[0] = 0, graph_ptr[num_graphs] = num_nodes.
+ * aqg_graph_heads: policy[g] = softmax(logits[g]) over A; value[g] = tanh(value_pre[g]) (value_pre / value may be NULL).
+ * aqg_graph_heads_backward: dlogits[g] = policy[g] (dpolicy[g] - <dpolicy[g], policy[g]>), dvalue_pre[g] = dvalue[g] (1 - value[g]^2);
+ *   dpolicy / dvalue NULL = zero.
+ * aqg_gcn_boards_graph: the board featuriser of the any-size forward alone, for board_size 3/5/7/9: x [B*V, 6] node features
+ *   (pv_network_cnn.py:88-114 read as [V,6]) and the normalised wall-cut grid adjacency as ELL rows of 5, ell_idx / ell_w
+ *   [B*V, 5] (self loop first, then up / down / left / right; a closed side is index -1, weight 0); node b*V + t is tile t of
+ *   board b.  csr_ptr[i] = 5 i over these rows is a CSR aqg_graph_aggregate accepts. */
+#define AQG_LIN_RELU 1
+#define AQG_LIN_W_KN 2
+#define AQG_LIN_ACCUMULATE 4
+int aqg_graph_linear(int M, int K, int N, const float* X, const float* W, const float* bias, const float* mask, int flags,
+                     float* Y, void* stream);
+size_t aqg_graph_linear_grad_workspace_floats(int M, int N, int K);
+int aqg_graph_linear_grad(int M, int K, int N, const float* dY, const float* X, const float* dYb, float* workspace,
+                          size_t workspace_floats, float* dW, float* db, void* stream);
+int aqg_graph_aggregate(int num_nodes, int N, const float* Y, const int32_t* csr_ptr, const int32_t* csr_src, const float* csr_w,
+                        const float* bias, int relu, float* out, void* stream);
+int aqg_graph_mean_pool(int num_nodes, int N, const float* H, const int32_t* graph_ptr, int num_graphs, float* pooled,
+                        void* stream);
+int aqg_graph_mean_pool_backward(int num_nodes, int N, const float* dpooled, const int32_t* graph_ptr, int num_graphs,
+                                 const float* mask, float* dH, void* stream);
+int aqg_graph_heads(int num_graphs, int A, const float* logits, const float* value_pre, float* policy, float* value,
+                    void* stream);
+int aqg_graph_heads_backward(int num_graphs, int A, const float* policy, const float* dpolicy, const float* value,
+                             const float* dvalue, float* dlogits, float* dvalue_pre, void* stream);
+int aqg_gcn_boards_graph(int board_size, const uint8_t* states72, int B, float* x, int32_t* ell_idx, float* ell_w, void* stream);
 
 /* ------------------------------------------------------------------ batched PV-MCTS self-play (pv_mcts.py, self_play.py) */
 
