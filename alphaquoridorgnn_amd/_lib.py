@@ -14,7 +14,7 @@ MAX_LEGAL = 136
 GNN_EXACT_F32 = 1        # AQG_GNN_EXACT_F32 (include/aqgnn.h)
 GNN_RANGE_PROVEN = 2     # AQG_GNN_RANGE_PROVEN
 GNN_PROVEN_MAX_WALLS = 16
-ABI_VERSION = 13
+ABI_VERSION = 14
 TRAIN_PART_FLOATS = 2 * 128 * 128 + 128 * 6 + 3 * 128    # AQG_TRAIN_PART_FLOATS, per position of the batch
 LIN_RELU, LIN_W_KN, LIN_ACCUMULATE = 1, 2, 4             # AQG_LIN_* flags of aqg_graph_linear
 
@@ -23,7 +23,8 @@ _vp, _i32, _f32 = _c.c_void_p, _c.c_int32, _c.c_float
 
 
 class EngineStruct(_c.Structure):
-    """Mirror of `struct aqg_engine` (include/aqgnn.h)."""
+    """Mirror of `struct aqg_engine` (include/aqgnn.h) up to eval_cache_log2 -- the ABI 10-13 layout; ABI 14 appends general_net
+    (EngineStructGeneral, which the entry points take)."""
     _fields_ = (
         [(n, _i32) for n in ("board_size", "num_walls", "plies_for_draw", "num_games", "quota", "sims", "node_cap",
                              "max_plies", "prior_mode", "fake_bias", "gnn_flags")]
@@ -38,6 +39,21 @@ class EngineStruct(_c.Structure):
                               "eval_cache_keys", "eval_cache_rows", "eval_cache_slot", "eval_mask", "stat_cache_hits", "eval_list", "eval_count")]
         + [("eval_cache_log2", _i32)]
     )
+
+
+GENERAL_MAX_LAYERS = 32   # AQG_GENERAL_MAX_LAYERS
+
+
+class GeneralNetStruct(_c.Structure):
+    """Mirror of `struct aqg_gcn_general_net` (include/aqgnn.h, ABI 14): a network of any shape by reference to its parameters."""
+    _fields_ = ([(n, _i32) for n in ("num_features", "hidden", "num_layers", "policy_size")]
+                + [("params", _vp * (2 * GENERAL_MAX_LAYERS + 8))])
+
+
+class EngineStructGeneral(EngineStruct):
+    """The whole `struct aqg_engine` of ABI 14: EngineStruct's fields (unchanged offsets) followed by `general_net`, the
+    descriptor of prior_mode 3.  The engine entry points take this one."""
+    _fields_ = [("general_net", GeneralNetStruct)]
 
 
 class TrainStruct(_c.Structure):
@@ -83,15 +99,18 @@ SIGNATURES = {
     "aqg_graph_heads": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp]),
     "aqg_graph_heads_backward": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aqg_gcn_boards_graph": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp, _vp, _vp, _vp]),
-    "aqg_engine_reset": (_c.c_int, [_c.POINTER(EngineStruct), _vp]),
-    "aqg_engine_clear_eval_cache": (_c.c_int, [_c.POINTER(EngineStruct), _vp]),
-    "aqg_engine_move": (_c.c_int, [_c.POINTER(EngineStruct), _vp, _vp]),
-    "aqg_engine_search": (_c.c_int, [_c.POINTER(EngineStruct), _vp, _vp]),
-    "aqg_engine_begin_move": (_c.c_int, [_c.POINTER(EngineStruct), _vp]),
-    "aqg_engine_step": (_c.c_int, [_c.POINTER(EngineStruct), _c.c_int, _c.c_int, _vp]),
-    "aqg_engine_finish_move": (_c.c_int, [_c.POINTER(EngineStruct), _vp, _vp]),
-    "aqg_engine_set_roots": (_c.c_int, [_c.POINTER(EngineStruct), _vp, _vp]),
-    "aqg_engine_root_visits": (_c.c_int, [_c.POINTER(EngineStruct), _vp, _vp, _vp, _vp]),
+    "aqg_gcn_boards_general_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "aqg_gcn_forward_boards_general": (_c.c_int, [_c.c_int, _vp, _c.c_int, _c.c_int, _c.POINTER(GeneralNetStruct), _vp, _vp,
+                                                  _c.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aqg_engine_reset": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),
+    "aqg_engine_clear_eval_cache": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),
+    "aqg_engine_move": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
+    "aqg_engine_search": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
+    "aqg_engine_begin_move": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),
+    "aqg_engine_step": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.c_int, _c.c_int, _vp]),
+    "aqg_engine_finish_move": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
+    "aqg_engine_set_roots": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
+    "aqg_engine_root_visits": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp, _vp, _vp]),
     "aqg_gcn_train_step": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _c.c_int, _vp]),
     "aqg_gcn_train_steps": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _vp]),
     "aqg_gcn_train_fallbacks": (_c.c_longlong, [_c.c_int]),

@@ -59,10 +59,15 @@ int launch_gen_aggregate(int n, int N, const float* Y, const int32_t* ptr, const
 int launch_gen_mean_pool(int N, const float* H, const int32_t* gptr, int G, float* pooled, hipStream_t st);
 int launch_gen_mean_pool_backward(int n, int N, const float* dpooled, const int32_t* gptr, int G, const float* mask, float* dH,
                                   hipStream_t st);
-int launch_gen_heads(int G, int A, const float* logits, const float* vpre, float* policy, float* value, hipStream_t st);
+int launch_gen_heads(int G, int A, const float* logits, const float* vpre, float* policy, float* value, hipStream_t st,
+                     const uint8_t* active = nullptr);
 int launch_gen_heads_backward(int G, int A, const float* policy, const float* dpolicy, const float* value, const float* dvalue,
                               float* dlogits, float* dvpre, hipStream_t st);
 int launch_gcn_boards_graph(int N, const void* states, int fmt, int B, float* x0, int32_t* ell_idx, float* ell_w, hipStream_t st);
+size_t boards_general_workspace_floats(int N, int hidden, int A, int B);
+int launch_gcn_forward_boards_general(int N, const void* states, int fmt, int B, const aqg_gcn_general_net* net,
+                                      const uint8_t* active, float* workspace, size_t workspace_floats, float* pooled, float* logits,
+                                      float* policy, float* value_pre, float* value, hipStream_t st);
 int engine_reset(const aqg_engine& e, hipStream_t st);
 int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st);
 int engine_begin_move(const aqg_engine& e, hipStream_t st);
@@ -276,6 +281,17 @@ int aqg_gcn_boards_graph(int board_size, const uint8_t* states72, int B, float* 
     if (B < 0) return fail("aqg_gcn_boards_graph: negative size");
     if (B > 0 && (!states72 || !x || !ell_idx || !ell_w)) return fail("aqg_gcn_boards_graph: null argument");
     return launch_gcn_boards_graph(board_size, states72, 0, B, x, ell_idx, ell_w, (hipStream_t)stream);
+}
+
+size_t aqg_gcn_boards_general_workspace_floats(int board_size, int hidden, int policy_size, int B) {
+    return boards_general_workspace_floats(board_size, hidden, policy_size, B);
+}
+
+int aqg_gcn_forward_boards_general(int board_size, const void* states, int state_fmt, int B, const aqg_gcn_general_net* net,
+                                   const uint8_t* active, float* workspace, size_t workspace_floats, float* pooled, float* logits,
+                                   float* policy, float* value_pre, float* value, void* stream) {
+    return launch_gcn_forward_boards_general(board_size, states, state_fmt, B, net, active, workspace, workspace_floats, pooled,
+                                             logits, policy, value_pre, value, (hipStream_t)stream);
 }
 
 int aqg_engine_reset(const aqg_engine* e, void* stream) {

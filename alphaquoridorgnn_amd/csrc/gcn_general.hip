@@ -250,12 +250,14 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) 
     return is_max ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// policy[g] = softmax(logits[g]) over A; value[g] = tanh(vpre[g]).  One workgroup per row.
+// policy[g] = softmax(logits[g]) over A; value[g] = tanh(vpre[g]).  One workgroup per row; a row with active[g] != 1 is skipped
+// (active may be NULL: every row).
 __global__ __launch_bounds__(256) void gen_heads_kernel(int G, int A, const float* __restrict__ logits, const float* __restrict__ vpre,
-                                                        float* __restrict__ policy, float* __restrict__ value) {
+                                                        float* __restrict__ policy, float* __restrict__ value,
+                                                        const uint8_t* __restrict__ active) {
     __shared__ float red[4];
     const int g = blockIdx.x, tid = threadIdx.x;
-    if (g >= G) return;
+    if (g >= G || (active && active[g] != 1)) return;
     const float* l = logits + (size_t)g * A;
     float m = -INFINITY;
     for (int a = tid; a < A; a += 256) m = fmaxf(m, l[a]);
@@ -354,9 +356,10 @@ int launch_gen_mean_pool_backward(int n, int N, const float* dpooled, const int3
     return check_launch("gen_pool_backward_kernel");
 }
 
-int launch_gen_heads(int G, int A, const float* logits, const float* vpre, float* policy, float* value, hipStream_t st) {
+int launch_gen_heads(int G, int A, const float* logits, const float* vpre, float* policy, float* value, hipStream_t st,
+                     const uint8_t* active) {
     if (G <= 0) return 0;
-    hipLaunchKernelGGL(gen_heads_kernel, dim3(G), dim3(256), 0, st, G, A, logits, vpre, policy, value);
+    hipLaunchKernelGGL(gen_heads_kernel, dim3(G), dim3(256), 0, st, G, A, logits, vpre, policy, value, active);
     return check_launch("gen_heads_kernel");
 }
 

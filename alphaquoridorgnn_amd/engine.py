@@ -25,14 +25,18 @@ class BatchedSelfPlay:
         evaluator used by the parity tests (oracle/mcts.py FakeModel); evaluator='external' calls `model.predict(state,
         device)` -- ANY object honouring the reference's BaseNetwork contract (BaseNetwork.py:36-40), e.g. a stock CNN --
         once per simulation and game from the host, exactly like pv_mcts.py:47 (plumbing path: one host round trip per
-        simulation).
-        eval_cache_slots (evaluator='gnn' only; a power of two >= 64, 0 = off; None = the environment's AQG_EVAL_CACHE_SLOTS, else
+        simulation).  evaluator='general' runs a GraphPolicyValueNetwork of ANY shape (6 input features) on the library's own
+        kernels (prior_mode 3, aqg_gcn_forward_boards_general): the per-move cost of 'gnn', no host work per simulation.
+        eval_cache_slots (evaluator='gnn' or 'general'; a power of two >= 64, 0 = off; None = the environment's AQG_EVAL_CACHE_SLOTS, else
         off): entries per game slot of the evaluation cache
         (include/aqgnn.h, `eval_cache_keys`): a leaf whose position this slot has already sent through the network is expanded from
         the stored priors / value / legal list -- bit-identical searches and game records, fewer network evaluations (736 bytes of
         HBM per entry)."""
         if evaluator == "gnn" and model is not None and not getattr(model, "fused", True):
             model._require_fused("evaluator='gnn'")          # before anything is allocated or launched
+        if evaluator == "general" and model is not None and getattr(model, "num_features", 6) != 6:
+            raise ValueError(f"evaluator='general': board records have 6 feature planes; this network takes "
+                             f"num_features={model.num_features}")
         self.dev = _lib.require_gpu(device)
         self.lib = _lib.load()
         self.N = board_size
@@ -83,7 +87,20 @@ class BatchedSelfPlay:
         t["counters"] = z((8,), torch.int32)
         t["stat_leaf_evals"] = z((G,), torch.int32)
         t["stat_terminal_sims"] = z((G,), torch.int32)
-        if evaluator == "gnn":
+        self._general_key = None
+        if evaluator == "general":
+            if model is None or not hasattr(model, "general_net"):
+                raise ValueError("evaluator='general' needs a GraphPolicyValueNetwork")
+            self._general = model.general_net(dev)          # ValueError: not 6 input features, or parameters not f32 on dev
+            self._general_key = model.general_weights_key()
+            if model.policy_output_size != self.A:
+                raise ValueError(f"evaluator='general': the network's policy_output_size {model.policy_output_size} is not the "
+                                 f"{self.N}x{self.N} board's {self.A} actions")
+            t["packed_weights"] = z((4,), torch.float32)
+            self._gnn_flags = 0
+            t["gnn_workspace"] = z((int(self.lib.aqg_gcn_boards_general_workspace_floats(self.N, model.hidden_dim, self.A, G)),),
+                                   torch.float32)
+        elif evaluator == "gnn":
             if model is None:
                 raise ValueError("evaluator='gnn' needs a model")
             t["packed_weights"] = model.packed_weights(dev)
@@ -97,10 +114,10 @@ class BatchedSelfPlay:
             self._gnn_flags = 0
 
         if eval_cache_slots is None:              # opt-in for whole programs (self_play, train_cycle, pv_mcts): one environment variable
-            eval_cache_slots = int(os.environ.get("AQG_EVAL_CACHE_SLOTS", "0")) if evaluator == "gnn" else 0
+            eval_cache_slots = int(os.environ.get("AQG_EVAL_CACHE_SLOTS", "0")) if evaluator in ("gnn", "general") else 0
         self.eval_cache_slots = int(eval_cache_slots)
         if self.eval_cache_slots:
-            if evaluator != "gnn":
+            if evaluator not in ("gnn", "general"):
                 raise ValueError("eval_cache_slots needs evaluator='gnn' (the table stores network outputs)")
             if self.eval_cache_slots < 64 or self.eval_cache_slots & (self.eval_cache_slots - 1) or self.eval_cache_slots > (1 << 20):
                 raise ValueError("eval_cache_slots must be a power of two in 64 .. 2**20")
@@ -112,11 +129,13 @@ class BatchedSelfPlay:
             t["eval_list"] = z((G,), torch.int32)
             t["eval_count"] = z((self.sims + 1,), torch.int32)
 
-        e = self.e = _lib.EngineStruct()
+        e = self.e = _lib.EngineStructGeneral()
         e.board_size, e.num_walls, e.plies_for_draw = self.N, self.num_walls, self.plies_for_draw
         e.num_games, e.quota, e.sims, e.node_cap = G, Q, self.sims, cap
         e.max_plies = hp if record_history else 0
-        e.prior_mode = {"gnn": 0, "fake": 1, "external": 2}[evaluator]
+        e.prior_mode = {"gnn": 0, "fake": 1, "external": 2, "general": 3}[evaluator]
+        if evaluator == "general":
+            e.general_net = self._general
         e.fake_bias = int(fake_bias)
         e.gnn_flags = int(self._gnn_flags)
         e.c_puct, e.temperature = float(c_puct), float(temperature)
@@ -153,6 +172,15 @@ class BatchedSelfPlay:
             self.e.gnn_flags = flags
             if self.eval_cache_slots and changed:      # the table holds the OLD weights' (or the other kernel build's) outputs
                 _lib.check(self.lib.aqg_engine_clear_eval_cache(ctypes.byref(self.e), self._stream()), "aqg_engine_clear_eval_cache")
+        elif self.evaluator == "general":
+            # the descriptor points at the parameters themselves: rebuilt for a replaced tensor, the same bytes (and the same
+            # captured graph) after an in-place update -- which still makes the cached evaluations stale
+            self._general = self.model.general_net(self.dev)
+            self.e.general_net = self._general
+            key = self.model.general_weights_key()
+            if self.eval_cache_slots and key != self._general_key:
+                _lib.check(self.lib.aqg_engine_clear_eval_cache(ctypes.byref(self.e), self._stream()), "aqg_engine_clear_eval_cache")
+            self._general_key = key
 
     def move(self, uniforms=None):
         """One move for every active game.  uniforms: float64 [G] in [0,1) (default: device RNG stream)."""

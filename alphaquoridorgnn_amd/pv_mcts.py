@@ -23,7 +23,7 @@ def _engine_for(model, num_games, sims, board_size, evaluator="gnn", fake_bias=0
             _engines.clear()
         eng = _engines[key] = BatchedSelfPlay(model, num_games=num_games, sims=sims, board_size=board_size,
                                               evaluator=evaluator, fake_bias=fake_bias, record_history=False)
-    elif evaluator == "gnn":
+    elif evaluator in ("gnn", "general"):
         eng.refresh_weights()
     return eng
 
@@ -43,7 +43,9 @@ def _policy_from_visits(visits, temperature):
 
 
 def pv_mcts_policy_batch(model, states72, temperature, sims=None, board_size=None, evaluator="gnn", fake_bias=0):
-    """states72: uint8 [B,72] -> list of B policies (each aligned with that state's legal_actions())."""
+    """states72: uint8 [B,72] -> list of B policies (each aligned with that state's legal_actions()).
+    evaluator: 'gnn' (the default 6/128/3 network), 'general' (a GraphPolicyValueNetwork of any shape with 6 input features, on
+    the library's kernels), 'external' (model.predict per leaf) or 'fake'."""
     states72 = torch.as_tensor(states72, dtype=torch.uint8)
     B = states72.shape[0]
     N = int(states72[0, 70]) if board_size is None else board_size

@@ -172,8 +172,8 @@ class GraphPolicyValueNetwork(nn.Module):
             raise ValueError(
                 f"{what} exists for the default {NUM_FEATURES}/{HIDDEN_DIM}/{NUM_GCN_LAYERS} network only; this one is "
                 f"{self.num_features}/{self.hidden_dim}/{self.num_gcn_layers}: train it with autograd (forward(x, edge_index, batch), "
-                "loss.backward() and a torch optimiser) instead of GNNTrainer, and search with evaluator='external' (its predict) "
-                "instead of the engine's 'gnn' evaluator")
+                "loss.backward() and a torch optimiser) instead of GNNTrainer, and search with evaluator='general' (the engine's any-shape "
+                "evaluator) or evaluator='external' (its predict) instead of the engine's 'gnn' evaluator")
 
     def invalidate_packed(self):
         """Call after the parameters were changed behind torch's back (train_network.GNNTrainer updates them in place from
@@ -462,6 +462,32 @@ class GraphPolicyValueNetwork(nn.Module):
     def _ordered_params(self):
         sd = dict(self.named_parameters())
         return [(k, sd[k]) for k in self.state_dict_keys]
+
+    # ---------------------------------------------------------------- any-shape descriptor (engine prior_mode 3)
+    def general_net(self, device):
+        """The ctypes descriptor of this network for aqg_gcn_forward_boards_general and the engine's evaluator='general'
+        (include/aqgnn.h aqg_gcn_general_net): its shape and device pointers to the module's OWN parameters, so an in-place
+        optimiser update is seen by the next launch without a repack.  Every parameter must be a contiguous float32 tensor on
+        `device`; works for any shape with 6 input features, the default 6/128/3 included."""
+        if self.num_features != 6:
+            raise ValueError(f"board records have 6 feature planes; this network takes num_features={self.num_features}: "
+                             "use forward(x, edge_index, batch)")
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        net = _lib.GeneralNetStruct()
+        net.num_features, net.hidden, net.num_layers, net.policy_size = (self.num_features, self.hidden_dim, self.num_gcn_layers,
+                                                                         self.policy_output_size)
+        for i, (k, p) in enumerate(self._ordered_params()):
+            if p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
+                raise ValueError(f"{k} must be a contiguous float32 tensor on {dev} for the engine's 'general' evaluator "
+                                 f"(it is {p.dtype} on {p.device}): move the network with .to({str(dev)!r}) first")
+            net.params[i] = p.data_ptr()
+        return net
+
+    def general_weights_key(self):
+        """(data pointer, version counter) of every parameter: changes whenever a parameter is replaced or updated in place."""
+        return tuple((p.data_ptr(), p._version) for _, p in self._ordered_params())
 
 
 class _GraphForward(torch.autograd.Function):

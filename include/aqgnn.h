@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define AQG_MAX_LEGAL 136 /* >= 5 pawn moves + 128 wall placements */
-#define AQG_ABI_VERSION 13
+#define AQG_ABI_VERSION 14
 
 int aqg_abi_version(void);
 const char* aqg_last_error(void);
@@ -240,6 +240,33 @@ int aqg_graph_heads_backward(int num_graphs, int A, const float* policy, const f
                              const float* dvalue, float* dlogits, float* dvalue_pre, void* stream);
 int aqg_gcn_boards_graph(int board_size, const uint8_t* states72, int B, float* x, int32_t* ell_idx, float* ell_w, void* stream);
 
+/* ------------------------------------------------------------------ any-shape network on board records (ABI 14)
+ *
+ * aqg_gcn_general_net: a GraphPolicyValueNetwork of any shape, by reference to its parameters.  num_features must be 6 (the
+ *   board featuriser's planes), hidden 2..1024, num_layers 1..AQG_GENERAL_MAX_LAYERS, policy_size 1..4096.  params[0 .. 2 L + 8)
+ *   are DEVICE pointers to the contiguous f32 parameters in the order of pv_network_gnn.state_dict_keys(L), PyTorch layouts:
+ *   gcn_layers.i.lin.weight [out,in], gcn_layers.i.bias [out] for each layer, then policy_head.0.weight / .bias, policy_head.2.weight
+ *   / .bias, value_head.0.weight / .bias, value_head.2.weight / .bias.  The library reads the weights where they are, at every
+ *   call: an in-place update of the tensors needs no new descriptor.
+ * aqg_gcn_forward_boards_general: the network on B board records (state_fmt 0 = state72, 1 = the engine's 24-byte records) for
+ *   board_size 3/5/7/9: the featuriser of aqg_gcn_boards_graph, then per layer ONE fused launch of GCNConv + bias + ReLU
+ *   (linear map and 5-point stencil in LDS; the last layer writes the mean pool), then the heads of aqg_graph_linear /
+ *   aqg_graph_heads.  Every output equals aqg_gcn_boards_graph followed by aqg_graph_linear / aqg_graph_aggregate (x L),
+ *   aqg_graph_mean_pool and the heads bit for bit.  pooled [B,hidden], logits [B,policy_size] and value_pre [B] may be NULL (then
+ *   they live in the workspace); policy [B,policy_size] is required, value [B] may be NULL.  active [B] (may be NULL): a board
+ *   with active[b] != 1 is skipped -- its policy / value rows are not written, its other rows are unspecified.  `workspace`:
+ *   aqg_gcn_boards_general_workspace_floats(board_size, hidden, policy_size, B) floats.  No allocation, no host synchronisation:
+ *   the call can be captured into a hipGraph. */
+#define AQG_GENERAL_MAX_LAYERS 32
+typedef struct aqg_gcn_general_net {
+    int32_t num_features, hidden, num_layers, policy_size;
+    const float* params[2 * AQG_GENERAL_MAX_LAYERS + 8];
+} aqg_gcn_general_net;
+size_t aqg_gcn_boards_general_workspace_floats(int board_size, int hidden, int policy_size, int B);
+int aqg_gcn_forward_boards_general(int board_size, const void* states, int state_fmt, int B, const aqg_gcn_general_net* net,
+                                   const uint8_t* active, float* workspace, size_t workspace_floats, float* pooled, float* logits,
+                                   float* policy, float* value_pre, float* value, void* stream);
+
 /* ------------------------------------------------------------------ batched PV-MCTS self-play (pv_mcts.py, self_play.py) */
 
 /* All engine memory is owned by the caller (the Python host allocates torch tensors); this struct only
@@ -255,7 +282,8 @@ typedef struct aqg_engine {
     int32_t prior_mode;       /* 0: network policy gathered at legal actions + renormalised (pv_network_cnn.py:129-132)
                                  1: `fake` integer-hash evaluator (tests; oracle/mcts.py FakeModel)
                                  2: external evaluator -- the caller's own model.predict (BaseNetwork.py:36-40) fills policy / value
-                                    between aqg_engine_step calls (see below) */
+                                    between aqg_engine_step calls (see below)
+                                 3: the any-shape network of `general_net` (below), gathered and renormalised like 0 */
     int32_t fake_bias;
     int32_t gnn_flags;        /* flags of the GNN forward for prior_mode 0 (AQG_GNN_EXACT_F32 or 0) */
     float c_puct;             /* 1.25  pv_mcts.py:71 */
@@ -287,7 +315,7 @@ typedef struct aqg_engine {
     /* boards other than 9x9 with prior_mode 0: workspace of the any-size forward, aqg_gcn_boards_any_workspace_floats(N, G)
      * floats (may be NULL for 9x9 and for prior_mode 1) */
     float* gnn_workspace;
-    /* Evaluation cache (ABI 10; prior_mode 0 only; eval_cache_keys == NULL: off).  The reference builds a new tree for every move
+    /* Evaluation cache (ABI 10; prior_mode 0 or 3 (ABI 14); eval_cache_keys == NULL: off).  The reference builds a new tree for every move
      * (pv_mcts.py:84) and keeps no transposition table, so a game asks model.predict (pv_mcts.py:47) for the same position again and
      * again: transpositions inside a search, and the sub-tree of the move that was played in the next search.  The network's output and
      * legal_actions() are pure functions of (walls, pawns, walls in hand) -- not of the ply counter -- and the fused kernels compute every
@@ -306,6 +334,11 @@ typedef struct aqg_engine {
      * launch of simulation s as a compact list -- eval_list[0 .. eval_count[s]) -- instead of a mask to walk */
     int32_t* eval_list /* [G] */; int32_t* eval_count /* [sims + 1] */;
     int32_t eval_cache_log2;
+    /* prior_mode 3 (ABI 14): the network of any shape the engine evaluates itself -- aqg_gcn_forward_boards_general over leaf_state
+     * per simulation, masked by leaf_flag (eval_mask with the evaluation cache), into policy / value, with gnn_workspace of
+     * aqg_gcn_boards_general_workspace_floats(board_size, hidden, A, G) floats; policy_size must be A.  Held BY VALUE: the captured
+     * per-move graphs are keyed by the bytes of this struct, so every weight pointer and the shape are part of the key. */
+    aqg_gcn_general_net general_net;
 } aqg_engine;
 
 /* Reset all G slots to the initial position (State() game_logic.py:25-40) and mark them active; clears the evaluation cache. */
