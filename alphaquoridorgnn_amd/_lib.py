@@ -67,6 +67,17 @@ class TrainStruct(_c.Structure):
     )
 
 
+class TrainGeneralStruct(_c.Structure):
+    """Mirror of `struct aqg_train_general` (include/aqgnn.h): the training step of a network of any shape."""
+    _fields_ = (
+        [(n, _i32) for n in ("board_size", "num_features", "hidden", "num_layers", "policy_size", "batch", "step")]
+        + [(n, _f32) for n in ("lr", "beta1", "beta2", "eps")]
+        + [(n, _vp * (2 * GENERAL_MAX_LAYERS + 8)) for n in ("params", "grads", "adam_m", "adam_v")]
+        + [(n, _vp) for n in ("policy", "value", "loss", "loss_mean", "workspace")]
+        + [("workspace_floats", _c.c_size_t)]
+    )
+
+
 SIGNATURES = {
     "aqg_abi_version": (_c.c_int, []),
     "aqg_last_error": (_c.c_char_p, []),
@@ -114,6 +125,9 @@ SIGNATURES = {
     "aqg_gcn_train_step": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _c.c_int, _vp]),
     "aqg_gcn_train_steps": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _vp]),
     "aqg_gcn_train_fallbacks": (_c.c_longlong, [_c.c_int]),
+    "aqg_gcn_train_general_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "aqg_gcn_train_step_general": (_c.c_int, [_c.POINTER(TrainGeneralStruct), _vp, _vp, _vp, _c.c_int, _vp]),
+    "aqg_gcn_train_steps_general": (_c.c_int, [_c.POINTER(TrainGeneralStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _vp]),
     "aqg_host_legal_actions": (_c.c_int, [_c.c_int, _vp, _vp]),
     "aqg_host_next": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp]),
     "aqg_host_shortest_path": (_c.c_int, [_c.c_int, _vp]),

@@ -81,6 +81,10 @@ int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, con
 long long train_fallbacks(int reset);
 int train_steps(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, long long positions,
                 float* loss_sums, hipStream_t st);
+size_t train_general_workspace_floats(int N, int hidden, int num_layers, int policy_size, int max_batch);
+int train_step_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st);
+int train_steps_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
+                        long long positions, float* loss_sums, hipStream_t st);
 }  // namespace aqg
 
 using namespace aqg;
@@ -348,6 +352,33 @@ int aqg_gcn_train_steps(const aqg_train* t, const uint8_t* states72, const float
         if (!t->params[i] || !t->grads[i] || !t->adam_m[i] || !t->adam_v[i]) return fail("aqg_gcn_train_steps: null parameter tensor");
     if (t->step < 1) return fail("aqg_gcn_train_steps: step must be >= 1");
     return train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream);
+}
+
+static int check_train_general(const aqg_train_general* t, bool adam, const char* what) {
+    if (t->num_layers < 1 || t->num_layers > AQG_GENERAL_MAX_LAYERS) return fail(what, "num_layers must be 1..32");
+    for (int i = 0; i < 2 * t->num_layers + 8; ++i)
+        if (!t->params[i] || !t->grads[i] || (adam && (!t->adam_m[i] || !t->adam_v[i]))) return fail(what, "null parameter tensor");
+    if (adam && t->step < 1) return fail(what, "step must be >= 1");
+    return 0;
+}
+size_t aqg_gcn_train_general_workspace_floats(int board_size, int hidden, int num_layers, int policy_size, int max_batch) {
+    return train_general_workspace_floats(board_size, hidden, num_layers, policy_size, max_batch);
+}
+int aqg_gcn_train_step_general(const aqg_train_general* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                               int mode, void* stream) {
+    const char* what = "aqg_gcn_train_step_general";
+    if (!t || mode < 0 || mode > 2) return fail(what, "bad argument");
+    if (t->batch < 0) return fail(what, "negative batch");
+    if (mode != 2 && t->batch > 0 && (!states72 || !pi_target || !z_target)) return fail(what, "null argument");
+    if (int r = check_train_general(t, mode >= 1, what)) return r;
+    return train_step_general(*t, states72, pi_target, z_target, mode, (hipStream_t)stream);
+}
+int aqg_gcn_train_steps_general(const aqg_train_general* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                                const int64_t* order, long long positions, float* loss_sums, void* stream) {
+    const char* what = "aqg_gcn_train_steps_general";
+    if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
+    if (int r = check_train_general(t, true, what)) return r;
+    return train_steps_general(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream);
 }
 
 }  // extern "C"

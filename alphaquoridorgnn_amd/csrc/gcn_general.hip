@@ -312,6 +312,18 @@ size_t gen_linear_grad_workspace_floats(int M, int N, int K) {
     return (size_t)grad_chunks(M, N, K) * ((size_t)N * K + N);
 }
 
+// An upper bound of gen_linear_grad_workspace_floats(M, N, K) over every M <= max_rows, in closed form: a chunk holds at least 32
+// rows and there are at most the budget's chunk count, so chunks <= min(cmax, ceil(max_rows / 32)) -- monotone in max_rows.
+size_t gen_linear_grad_workspace_floats_bound(long long max_rows, int N, int K) {
+    if (max_rows <= 0 || N <= 0 || K <= 0) return 0;
+    const size_t part = (size_t)N * K + N;
+    size_t cmax = GEN_PART_BUDGET / part;
+    if (cmax < 1) cmax = 1;
+    if (cmax > GEN_MAX_CHUNKS) cmax = GEN_MAX_CHUNKS;
+    const size_t by_rows = (size_t)((max_rows + 31) / 32);
+    return (by_rows < cmax ? by_rows : cmax) * part;
+}
+
 int launch_gen_linear_grad(int M, int K, int N, const float* dY, const float* X, const float* dYb, float* workspace,
                            size_t workspace_floats, float* dW, float* db, hipStream_t st) {
     if (N <= 0 || K <= 0) return 0;

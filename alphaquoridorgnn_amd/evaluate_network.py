@@ -17,7 +17,7 @@ from . import pv_mcts
 from .constants import PV_NETWORK_PATH, BOARD_SIZE
 from .engine import BatchedSelfPlay
 from .game_logic import State
-from .pv_network_gnn import GNNNetwork
+from .pv_network_gnn import GNNNetwork, load_network
 
 EN_GAME_COUNT = 15    # Number of games per evaluation (evaluate_network.py:14; originally 400)
 EN_TEMPERATURE = 1.0  # Temperature of the Boltzmann distribution (evaluate_network.py:15)
@@ -50,8 +50,9 @@ def update_best_player():
 
 class BatchedMatch:
     """`num_games` games of player 0 vs player 1 on the batched engine; game i has player (i % 2) moving first
-    (evaluate_network.py:69-74).  Players are models (evaluator='gnn') or integer biases of the parity tests' hash
-    evaluator (evaluator='fake')."""
+    (evaluate_network.py:69-74).  Players are models (evaluator='gnn': the default 6/128/3 network; evaluator='general':
+    GraphPolicyValueNetworks of any shape with 6 input features, the two players' shapes may differ) or integer biases of the
+    parity tests' hash evaluator (evaluator='fake')."""
 
     def __init__(self, players, num_games, sims=None, board_size=BOARD_SIZE, temperature=EN_TEMPERATURE,
                  evaluator="gnn", seed=0, device=None):
@@ -69,6 +70,10 @@ class BatchedMatch:
                       device=device, eval_cache_slots=0)
             if evaluator == "gnn":
                 eng = BatchedSelfPlay(players[first], **kw)
+            elif evaluator == "general":
+                # built on the wider player (the engine's workspace is sized by the network it is built with), then pointed
+                # at the mover's descriptor before every ply
+                eng = BatchedSelfPlay(self._widest(players), evaluator="general", **kw)
             else:
                 eng = BatchedSelfPlay(None, evaluator="fake", fake_bias=int(players[first]), **kw)
             self.engines.append(eng)
@@ -76,12 +81,25 @@ class BatchedMatch:
             dev = next(e for e in self.engines if e is not None).dev
             self._packed = [m.packed_weights(dev) for m in players]
             self._flags = [int(m.gnn_flags(dev)) for m in players]
+        elif evaluator == "general":
+            dev = next(e for e in self.engines if e is not None).dev
+            for m in players:
+                if m.policy_output_size != players[0].policy_output_size:
+                    raise ValueError("evaluator='general': the two players' policy sizes differ")
+            self._general = [m.general_net(dev) for m in players]
+
+    @staticmethod
+    def _widest(players):
+        """The player whose workspace of aqg_gcn_forward_boards_general is the larger (it grows with hidden_dim only)."""
+        return max(players, key=lambda m: m.hidden_dim)
 
     def _point_at(self, eng, mover):
         if self.evaluator == "gnn":
             eng.t["packed_weights"] = self._packed[mover]
             eng.e.packed_weights = self._packed[mover].data_ptr()
             eng.e.gnn_flags = self._flags[mover]
+        elif self.evaluator == "general":
+            eng.e.general_net = self._general[mover]
         else:
             eng.e.fake_bias = int(self.players[mover])
 
@@ -143,13 +161,17 @@ class BatchedMatch:
 
 
 def evaluate_network():
-    """Network evaluation (evaluate_network.py:52-94): latest vs best, promote when the average point exceeds 0.5."""
-    model0 = GNNNetwork()
-    model0.prep_for_inference(PV_NETWORK_PATH + 'latest.pth')
-    model1 = GNNNetwork()
-    model1.prep_for_inference(PV_NETWORK_PATH + 'best.pth')
+    """Network evaluation (evaluate_network.py:52-94): latest vs best, promote when the average point exceeds 0.5.  Two
+    default 6/128/3 networks play on the engine's fused evaluator ('gnn'); when either file holds another shape, both play on
+    its any-shape evaluator ('general')."""
+    model0 = load_network(PV_NETWORK_PATH + 'latest.pth')
+    model1 = load_network(PV_NETWORK_PATH + 'best.pth')
+    fused = all(isinstance(m, GNNNetwork) for m in (model0, model1))
+    if fused and torch.cuda.is_available():
+        for m in (model0, model1):
+            m.packed_weights(torch.device("cuda", torch.cuda.current_device()))
     match = BatchedMatch((model0, model1), EN_GAME_COUNT, temperature=EN_TEMPERATURE,
-                         seed=int(np.random.randint(0, 2 ** 30)))
+                         seed=int(np.random.randint(0, 2 ** 30)), evaluator="gnn" if fused else "general")
     points = match.play()
     print('Evaluating latest model against current best ({} games, concurrent)'.format(EN_GAME_COUNT))
     average_point = sum(points) / EN_GAME_COUNT

@@ -171,8 +171,9 @@ class GraphPolicyValueNetwork(nn.Module):
         if not self.fused:
             raise ValueError(
                 f"{what} exists for the default {NUM_FEATURES}/{HIDDEN_DIM}/{NUM_GCN_LAYERS} network only; this one is "
-                f"{self.num_features}/{self.hidden_dim}/{self.num_gcn_layers}: train it with autograd (forward(x, edge_index, batch), "
-                "loss.backward() and a torch optimiser) instead of GNNTrainer, and search with evaluator='general' (the engine's any-shape "
+                f"{self.num_features}/{self.hidden_dim}/{self.num_gcn_layers}: train it with train_network.GeneralTrainer (6 input features) "
+                "or autograd (forward(x, edge_index, batch), loss.backward() and a torch optimiser) instead of GNNTrainer, and search "
+                "with evaluator='general' (the engine's any-shape "
                 "evaluator) or evaluator='external' (its predict) instead of the engine's 'gnn' evaluator")
 
     def invalidate_packed(self):
@@ -784,25 +785,59 @@ class GNNNetwork(GraphPolicyValueNetwork):
             self.packed_weights(device)
 
     def preprocess_input(self, game_state_arrays):
-        """List of State.to_array() triples -> uint8 [n,72] state records (the input the GNN kernels accept).
-        plies_played is not part of to_array() and is not a network input; it is stored as 0."""
-        out = np.zeros((len(game_state_arrays), 72), dtype=np.uint8)
-        for i, (player, enemy, walls) in enumerate(game_state_arrays):
-            out[i] = game_logic.pack_state72(player, enemy, walls, 0, self.board_size)
-        return out
+        """List of State.to_array() triples -> uint8 [n,72] state records (the input the GNN kernels accept)."""
+        return pack_states(game_state_arrays, self.board_size)
 
     def train_model(self, data_loader, optimizer, loss_fn, device='cpu', num_epochs=10):
         pass  # stub in the reference as well (pv_network_cnn.py:139-140); training is SURVEY 8(f1), a later row
 
 
-def create_network():
-    """pv_network_gnn.py:68-80 (path taken from constants.PV_NETWORK_PATH like pv_network_cnn.py:144-155)."""
+def pack_states(game_state_arrays, board_size=BOARD_SIZE):
+    """List of State.to_array() triples -> uint8 [n,72] state records, for a network of any shape.  plies_played is not part of
+    to_array() and is not a network input; it is stored as 0."""
+    out = np.zeros((len(game_state_arrays), 72), dtype=np.uint8)
+    for i, (player, enemy, walls) in enumerate(game_state_arrays):
+        out[i] = game_logic.pack_state72(player, enemy, walls, 0, board_size)
+    return out
+
+
+def create_network(hidden_dim=None, num_gcn_layers=None):
+    """pv_network_gnn.py:68-80 (path taken from constants.PV_NETWORK_PATH like pv_network_cnn.py:144-155).  hidden_dim /
+    num_gcn_layers (default HIDDEN_DIM / NUM_GCN_LAYERS) shape the network written when no best.pth exists yet."""
     model_path = PV_NETWORK_PATH + 'best.pth'
     if os.path.exists(model_path):
         return
-    model = GraphPolicyValueNetwork(NUM_FEATURES, HIDDEN_DIM, NUM_GCN_LAYERS, POLICY_OUTPUT_SIZE)
+    model = GraphPolicyValueNetwork(NUM_FEATURES, HIDDEN_DIM if hidden_dim is None else hidden_dim,
+                                    NUM_GCN_LAYERS if num_gcn_layers is None else num_gcn_layers, POLICY_OUTPUT_SIZE)
     os.makedirs(PV_NETWORK_PATH, exist_ok=True)
     torch.save(model.state_dict(), model_path)
+
+
+def shape_of_state_dict(sd):
+    """(num_features, hidden_dim, num_gcn_layers, policy_output_size) of a GraphPolicyValueNetwork state_dict."""
+    L = 0
+    while f"gcn_layers.{L}.lin.weight" in sd:
+        L += 1
+    if L == 0 or "policy_head.2.weight" not in sd:
+        raise ValueError("not a GraphPolicyValueNetwork state_dict (no gcn_layers.0.lin.weight / policy_head.2.weight)")
+    hidden, features = (int(n) for n in sd["gcn_layers.0.lin.weight"].shape)
+    return features, hidden, L, int(sd["policy_head.2.weight"].shape[0])
+
+
+def load_network(path, device=None):
+    """The network a .pth file holds, whatever its shape: GNNNetwork for the default 6/128/3 (the fused kernels), otherwise a
+    GraphPolicyValueNetwork of the shape the state_dict implies.  Loaded onto `device` (default: the current GPU, else the CPU)
+    in eval mode."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    sd = torch.load(path, map_location=device, weights_only=True)
+    shape = shape_of_state_dict(sd)
+    if shape == (NUM_FEATURES, HIDDEN_DIM, NUM_GCN_LAYERS, POLICY_OUTPUT_SIZE):
+        model = GNNNetwork()
+    else:
+        model = GraphPolicyValueNetwork(*shape)
+    model.load_state_dict(sd)
+    return model.to(device).eval()
 
 
 if __name__ == '__main__':

@@ -16,7 +16,7 @@ from . import distributed as aqd
 from . import pv_mcts
 from .constants import PV_NETWORK_PATH, BOARD_SIZE
 from .engine import BatchedSelfPlay, MultiSetSelfPlay, gather_history
-from .pv_network_gnn import GNNNetwork, POLICY_OUTPUT_SIZE
+from .pv_network_gnn import GNNNetwork, POLICY_OUTPUT_SIZE, load_network
 
 SP_GAME_COUNT = 50    # Number of games for self-play (self_play.py:19; 25000 in the original version)
 SP_TEMPERATURE = 1.0  # Temperature parameter for Boltzmann distribution (self_play.py:20)
@@ -82,8 +82,11 @@ def self_play(model=None, games=None, seed=None):
     stream; by default every call draws a fresh one, like the reference's unseeded np.random.choice."""
     import torch.distributed as dist
     if model is None:
-        model = GNNNetwork()
-        model.prep_for_inference(model_path=PV_NETWORK_PATH + 'best.pth')
+        model = load_network(PV_NETWORK_PATH + 'best.pth')       # GNNNetwork (prep_for_inference's path), or the shape best.pth holds
+        if isinstance(model, GNNNetwork) and torch.cuda.is_available():
+            model.packed_weights(torch.device("cuda", torch.cuda.current_device()))
+    # the default 6/128/3 network runs the engine's fused evaluator; any other shape its any-shape evaluator
+    evaluator = "gnn" if getattr(model, "fused", True) else "general"
     total = SP_GAME_COUNT if games is None else games
     distributed = dist.is_available() and dist.is_initialized()
     rank, world = (dist.get_rank(), dist.get_world_size()) if distributed else (0, 1)
@@ -96,7 +99,8 @@ def self_play(model=None, games=None, seed=None):
     if mine > 0:
         # >= 256 games: independent game sets on their own streams fill the holes of each other's serial kernel chains
         eng = MultiSetSelfPlay(model, num_games=mine, sims=pv_mcts.PV_EVALUATE_COUNT, num_sets=None if mine >= 256 else 1,
-                               board_size=BOARD_SIZE, temperature=SP_TEMPERATURE, seed=(base + rank) % (2 ** 31 - 1), device=dev)
+                               board_size=BOARD_SIZE, temperature=SP_TEMPERATURE, seed=(base + rank) % (2 ** 31 - 1), device=dev,
+                               evaluator=evaluator)
         c = eng.play_generation()
         print(f'\rSelf-play (rank {rank}: {c["finished"]}/{mine} games)', end='')
         st, vis, z = eng.history_tensors()

@@ -22,12 +22,12 @@ def _dist():
     return dist, on, (dist.get_rank() if on else 0)
 
 
-def _create_network_once():
+def _create_network_once(hidden_dim=None, num_gcn_layers=None):
     """create_network() draws random weights: under torch.distributed only rank 0 may write best.pth (every rank would
     otherwise save a different random init to the same path); the others wait for the file."""
     dist, on, rank = _dist()
     if rank == 0:
-        create_network()
+        create_network(hidden_dim=hidden_dim, num_gcn_layers=num_gcn_layers)
     if on:
         dist.barrier()
 
@@ -52,11 +52,12 @@ def _evaluate_once():
     return promoted
 
 
-def train_cycle(num_cycles=None):
-    """Run the cycle; returns, per iteration, whether `latest` was promoted to `best`."""
+def train_cycle(num_cycles=None, hidden_dim=None, num_gcn_layers=None):
+    """Run the cycle; returns, per iteration, whether `latest` was promoted to `best`.  hidden_dim / num_gcn_layers shape the
+    best.pth written when none exists (create_network); every stage then follows the shape best.pth holds."""
     total = NUM_TRAIN_CYCLE if num_cycles is None else int(num_cycles)
     print(f'{constants.PV_NETWORK_NAME} network, {constants.BOARD_SIZE}x{constants.BOARD_SIZE} board, {total} training cycle(s)')
-    _create_network_once()
+    _create_network_once(hidden_dim, num_gcn_layers)
     promoted = []
     rank = _dist()[2]
     for cycle in range(1, total + 1):
@@ -85,6 +86,10 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=None, help="epochs per parameter update (default train_network.NUM_EPOCH)")
     ap.add_argument("--eval-games", type=int, default=None, help="games per evaluation (default EN_GAME_COUNT)")
     ap.add_argument("--result-dir", default=None, help="every rank writes train_cycle.rank<r>.json (promotions, sha256 of latest.pth) here")
+    ap.add_argument("--hidden-dim", type=int, default=None,
+                    help="hidden width of the network created when no best.pth exists (default HIDDEN_DIM = 128)")
+    ap.add_argument("--num-gcn-layers", type=int, default=None,
+                    help="GCN layers of the network created when no best.pth exists (default NUM_GCN_LAYERS = 3)")
     args = ap.parse_args(argv)
     rank, world = aqd.init_from_env()
     if args.games is not None:
@@ -96,7 +101,7 @@ def main(argv=None):
     if args.eval_games is not None:
         en.EN_GAME_COUNT = args.eval_games
     try:
-        promoted = train_cycle(args.cycles)
+        promoted = train_cycle(args.cycles, hidden_dim=args.hidden_dim, num_gcn_layers=args.num_gcn_layers)
         if args.result_dir:
             import hashlib
             with open(constants.PV_NETWORK_PATH + 'latest.pth', 'rb') as f:

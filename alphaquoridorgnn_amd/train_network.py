@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .constants import PV_NETWORK_PATH, BOARD_SIZE
-from .pv_network_gnn import GNNNetwork, STATE_DICT_KEYS, HIDDEN_DIM, NUM_FEATURES
+from .pv_network_gnn import STATE_DICT_KEYS, HIDDEN_DIM, NUM_FEATURES, load_network, pack_states
 
 NUM_EPOCH = 100    # train_network.py:14
 BATCH_SIZE = 128   # train_network.py:15
@@ -38,7 +38,93 @@ def lr_lambda(epoch):
     return 1.0
 
 
-class GNNTrainer:
+class _Trainer:
+    """What GNNTrainer and GeneralTrainer share: the Adam state and the flat gradient buffer, step() (single process or data
+    parallel), outputs() and run_epoch().  A subclass provides the library calls (_call, _call_epoch), the batch-mean losses of a
+    single-process step (_batch_losses) and what an update must tell the model (_updated)."""
+
+    def _optimiser_state(self):
+        # all gradient tensors are views of ONE flat buffer: the data-parallel exchange is a single all-reduce
+        self.flat_grads = torch.zeros((sum(p.numel() for p in self.params),), dtype=torch.float32, device=self.dev)
+        self.grads, off = [], 0
+        for p in self.params:
+            self.grads.append(self.flat_grads[off:off + p.numel()].view_as(p))
+            off += p.numel()
+        self.adam_m = [torch.zeros_like(p) for p in self.params]
+        self.adam_v = [torch.zeros_like(p) for p in self.params]
+
+    def step(self, states72, pi_target, z_target, lr=LEARNING_RATE, update=True, group=None):
+        """One optimisation step.  states72 uint8 [B,72], pi_target float32 [B,A], z_target float32 [B] (device tensors).
+        Returns (policy_loss, value_loss) as 0-dim device tensors -- no host synchronisation.
+
+        Data parallel (torch.distributed initialised, world > 1): every rank passes ITS shard of the global batch; the
+        local mean-loss gradients are weighted by B_local / B_global, summed with ONE all-reduce of the flat gradient buffer
+        (RCCL over xGMI with backend nccl) and applied by every rank, so all replicas take the step a single process would
+        take on the whole batch (up to fp32 summation order)."""
+        import torch.distributed as dist
+        B = int(states72.shape[0])
+        if B > self.max_batch:
+            raise ValueError("batch larger than the trainer's workspace")
+        states72 = states72.to(self.dev, torch.uint8).contiguous()
+        pi_target = pi_target.to(self.dev, torch.float32).contiguous()
+        z_target = z_target.to(self.dev, torch.float32).contiguous()
+        world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+        if update:
+            self.step_count += 1
+        self.t.batch, self.t.step, self.t.lr = B, max(self.step_count, 1), float(lr)
+        if world == 1:
+            self._call(states72, pi_target, z_target, 1 if update else 0)
+            loss = self._batch_losses(B) if B else torch.zeros((2,), device=self.dev)
+        else:
+            if B:
+                self._call(states72, pi_target, z_target, 0)
+                lsum = self.ws["loss"][:B].sum(dim=0)
+            else:                                                  # a rank may hold no position of a ragged last batch
+                self.flat_grads.zero_()
+                lsum = torch.zeros((2,), device=self.dev)
+            tot = torch.cat([lsum, torch.tensor([float(B)], device=self.dev)])
+            dist.all_reduce(tot, group=group)                      # global loss sums and global batch size
+            self.flat_grads.mul_(float(B) / tot[2])                # local mean-loss gradient -> its share of the global mean
+            dist.all_reduce(self.flat_grads, group=group)
+            if update:
+                self._call(states72, pi_target, z_target, 2)
+            loss = tot[:2] / tot[2]
+        if update:
+            self._updated()
+        return loss[0], loss[1]
+
+    def outputs(self, B):
+        """(policy [B,A], value [B]) of the last step's forward pass."""
+        return self.ws["pol"][:B], self.ws["val"][:B]
+
+    def run_epoch(self, states72, pi_target, z_target, order, lr=LEARNING_RATE, batch=None, pre_shuffle=True):
+        """All optimisation steps of one epoch in ONE library call (single process): step i trains on the positions
+        order[i*batch:(i+1)*batch] of the resident device arrays (train_network.py:72-95; the short last batch is kept, as
+        DataLoader does).  Returns the epoch's summed (policy_loss, value_loss) as a device tensor [2] -- no host sync."""
+        batch = self.max_batch if batch is None else int(batch)
+        if batch > self.max_batch:
+            raise ValueError("batch larger than the trainer's workspace")
+        n = int(order.shape[0])
+        sums = torch.zeros((2,), dtype=torch.float32, device=self.dev)
+        if n == 0:
+            return sums
+        # The shuffle is applied ONCE per epoch (three gathers, ~1 KB per position) and the steps then index the shuffled
+        # copies directly: every kernel of a step starts with cold loads, and reading order[] first would put one more
+        # HBM round trip in front of each of them.  (The C entry points also take the order itself: order != NULL.)
+        order = order.to(self.dev, torch.int64).contiguous()
+        states72 = states72.to(self.dev, torch.uint8).contiguous()
+        pi_target = pi_target.to(self.dev, torch.float32).contiguous()
+        z_target = z_target.to(self.dev, torch.float32).contiguous()
+        if pre_shuffle:
+            states72, pi_target, z_target = (x.index_select(0, order).contiguous() for x in (states72, pi_target, z_target))
+        self.t.batch, self.t.step, self.t.lr = batch, self.step_count + 1, float(lr)
+        self._call_epoch(states72, pi_target, z_target, None if pre_shuffle else order, n, sums)
+        self.step_count += (n + batch - 1) // batch
+        self._updated()
+        return sums
+
+
+class GNNTrainer(_Trainer):
     """Adam state + workspace for optimisation steps of up to `max_batch` positions on `model` (a GNNNetwork on the GPU)."""
 
     def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8):
@@ -52,14 +138,7 @@ class GNNTrainer:
         for p in self.params:
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise ValueError("training needs contiguous float32 parameters")
-        # all 14 gradient tensors are views of ONE flat buffer: the data-parallel exchange is a single all-reduce
-        self.flat_grads = torch.zeros((sum(p.numel() for p in self.params),), dtype=torch.float32, device=self.dev)
-        self.grads, off = [], 0
-        for p in self.params:
-            self.grads.append(self.flat_grads[off:off + p.numel()].view_as(p))
-            off += p.numel()
-        self.adam_m = [torch.zeros_like(p) for p in self.params]
-        self.adam_v = [torch.zeros_like(p) for p in self.params]
+        self._optimiser_state()
         self.N = model.board_size
         self.V = self.N * self.N
         self.A = model.policy_output_size
@@ -88,74 +167,87 @@ class GNNTrainer:
         _lib.check(self.lib.aqg_gcn_train_step(ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target),
                                                mode, _lib.stream_ptr(self.dev)), "aqg_gcn_train_step")
 
-    def step(self, states72, pi_target, z_target, lr=LEARNING_RATE, update=True, group=None):
-        """One optimisation step.  states72 uint8 [B,72], pi_target float32 [B,A], z_target float32 [B] (device tensors).
-        Returns (policy_loss, value_loss) as 0-dim device tensors -- no host synchronisation.
-
-        Data parallel (torch.distributed initialised, world > 1): every rank passes ITS shard of the global batch; the
-        local mean-loss gradients are weighted by B_local / B_global, summed with ONE all-reduce of the flat gradient buffer
-        (RCCL over xGMI with backend nccl) and applied by every rank, so all replicas take the step a single process would
-        take on the whole batch (up to fp32 summation order)."""
-        import torch.distributed as dist
-        B = int(states72.shape[0])
-        if B > self.max_batch:
-            raise ValueError("batch larger than the trainer's workspace")
-        states72 = states72.to(self.dev, torch.uint8).contiguous()
-        pi_target = pi_target.to(self.dev, torch.float32).contiguous()
-        z_target = z_target.to(self.dev, torch.float32).contiguous()
-        world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
-        if update:
-            self.step_count += 1
-        self.t.batch, self.t.step, self.t.lr = B, max(self.step_count, 1), float(lr)
-        if world == 1:
-            self._call(states72, pi_target, z_target, 1 if update else 0)
-            loss = self.ws["loss"][:B].mean(dim=0) if B else torch.zeros((2,), device=self.dev)
-        else:
-            if B:
-                self._call(states72, pi_target, z_target, 0)
-                lsum = self.ws["loss"][:B].sum(dim=0)
-            else:                                                  # a rank may hold no position of a ragged last batch
-                self.flat_grads.zero_()
-                lsum = torch.zeros((2,), device=self.dev)
-            tot = torch.cat([lsum, torch.tensor([float(B)], device=self.dev)])
-            dist.all_reduce(tot, group=group)                      # global loss sums and global batch size
-            self.flat_grads.mul_(float(B) / tot[2])                # local mean-loss gradient -> its share of the global mean
-            dist.all_reduce(self.flat_grads, group=group)
-            if update:
-                self._call(states72, pi_target, z_target, 2)
-            loss = tot[:2] / tot[2]
-        if update:
-            self.model.invalidate_packed()
-        return loss[0], loss[1]
-
-    def outputs(self, B):
-        """(policy [B,A], value [B]) of the last step's forward pass."""
-        return self.ws["pol"][:B], self.ws["val"][:B]
-
-    def run_epoch(self, states72, pi_target, z_target, order, lr=LEARNING_RATE, batch=None, pre_shuffle=True):
-        """All optimisation steps of one epoch in ONE library call (single process): step i trains on the positions
-        order[i*batch:(i+1)*batch] of the resident device arrays (train_network.py:72-95; the short last batch is kept, as
-        DataLoader does).  Returns the epoch's summed (policy_loss, value_loss) as a device tensor [2] -- no host sync."""
-        batch = self.max_batch if batch is None else int(batch)
-        if batch > self.max_batch:
-            raise ValueError("batch larger than the trainer's workspace")
-        n = int(order.shape[0])
-        sums = torch.zeros((2,), dtype=torch.float32, device=self.dev)
-        if n == 0:
-            return sums
-        # The shuffle is applied ONCE per epoch (three gathers, ~1 KB per position) and the steps then index the shuffled
-        # copies directly: every kernel of a step starts with cold loads, and reading order[] first would put one more
-        # HBM round trip in front of each of them.  (The C entry point also takes the order itself: order != NULL.)
-        order = order.to(self.dev, torch.int64).contiguous()
-        if pre_shuffle:
-            states72, pi_target, z_target = (x.index_select(0, order).contiguous() for x in (states72, pi_target, z_target))
-        self.t.batch, self.t.step, self.t.lr = batch, self.step_count + 1, float(lr)
+    def _call_epoch(self, states72, pi_target, z_target, order, n, sums):
         _lib.check(self.lib.aqg_gcn_train_steps(ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target),
-                                                None if pre_shuffle else _lib.ptr(order), n, _lib.ptr(sums),
-                                                _lib.stream_ptr(self.dev)), "aqg_gcn_train_steps")
-        self.step_count += (n + batch - 1) // batch
+                                                _lib.ptr(order), n, _lib.ptr(sums), _lib.stream_ptr(self.dev)), "aqg_gcn_train_steps")
+
+    def _batch_losses(self, B):
+        return self.ws["loss"][:B].mean(dim=0)
+
+    def _updated(self):
         self.model.invalidate_packed()
-        return sums
+
+
+class GeneralTrainer(_Trainer):
+    """Adam state + workspace for optimisation steps of up to `max_batch` positions on a GraphPolicyValueNetwork of ANY shape with
+    6 input features (the default 6/128/3 included) -- aqg_gcn_train_step_general (csrc/gcn_train_general.hip): the arithmetic
+    of GNNTrainer's step on the width-generic kernels.  The surface is GNNTrainer's.  The module's own parameters are updated in
+    place (and their version counters advanced), so an engine built with evaluator='general' only needs refresh_weights() to
+    search with the new weights -- its evaluation cache included."""
+
+    def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8):
+        if getattr(model, "num_features", NUM_FEATURES) != NUM_FEATURES:
+            raise ValueError(f"GeneralTrainer trains on board records, which have {NUM_FEATURES} feature planes; this network takes "
+                             f"num_features={model.num_features}")
+        self.model = model
+        self.lib = _lib.load()
+        self.params = [p for _, p in model._ordered_params()]
+        for p in self.params:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError("training needs contiguous float32 parameters")
+        self.dev = _lib.require_gpu(self.params[0].device)
+        if any(p.device != self.dev for p in self.params):
+            raise ValueError("every parameter must be on the trainer's GPU")
+        self._optimiser_state()
+        self.N = model.board_size
+        self.A = model.policy_output_size
+        self.max_batch = int(max_batch)
+        if self.max_batch < 1:
+            raise ValueError("max_batch must be >= 1")
+        self.step_count = 0
+        self.betas, self.eps = betas, eps
+        B, A = self.max_batch, self.A
+        f = dict(dtype=torch.float32, device=self.dev)
+        nws = int(self.lib.aqg_gcn_train_general_workspace_floats(self.N, model.hidden_dim, model.num_gcn_layers, A, B))
+        if nws == 0:
+            _lib.check(-1, "aqg_gcn_train_general_workspace_floats (shape or board size outside the kernels' limits)")
+        self.ws = dict(workspace=torch.empty((nws,), **f), pol=torch.empty((B, A), **f), val=torch.empty((B,), **f),
+                       loss=torch.empty((B, 2), **f), loss_mean=torch.zeros((2,), **f))
+        t = self.t = _lib.TrainGeneralStruct()
+        t.board_size, t.num_features, t.hidden, t.num_layers, t.policy_size = (self.N, NUM_FEATURES, model.hidden_dim,
+                                                                               model.num_gcn_layers, A)
+        t.beta1, t.beta2, t.eps = float(betas[0]), float(betas[1]), float(eps)
+        for name, tensors in (("params", self.params), ("grads", self.grads), ("adam_m", self.adam_m), ("adam_v", self.adam_v)):
+            arr = getattr(t, name)
+            for i, x in enumerate(tensors):
+                arr[i] = x.data_ptr()
+        t.policy, t.value, t.loss, t.loss_mean = (self.ws[k].data_ptr() for k in ("pol", "val", "loss", "loss_mean"))
+        t.workspace, t.workspace_floats = self.ws["workspace"].data_ptr(), nws
+
+    def _call(self, states72, pi_target, z_target, mode):
+        _lib.check(self.lib.aqg_gcn_train_step_general(ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target),
+                                                       _lib.ptr(z_target), mode, _lib.stream_ptr(self.dev)),
+                   "aqg_gcn_train_step_general")
+
+    def _call_epoch(self, states72, pi_target, z_target, order, n, sums):
+        _lib.check(self.lib.aqg_gcn_train_steps_general(ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target),
+                                                        _lib.ptr(z_target), _lib.ptr(order), n, _lib.ptr(sums),
+                                                        _lib.stream_ptr(self.dev)), "aqg_gcn_train_steps_general")
+
+    def _batch_losses(self, B):
+        return self.ws["loss_mean"].clone()          # summed in position order by the library
+
+    def _updated(self):
+        # The kernels wrote the parameters behind torch's back: advance their version counters, which general_weights_key()
+        # (and with it a 'general' engine's refresh_weights(), evaluation cache included) reads; drop any packed copy.
+        torch.autograd.graph.increment_version(self.params)
+        if hasattr(self.model, "invalidate_packed"):
+            self.model.invalidate_packed()
+
+
+def trainer_for(model, max_batch=BATCH_SIZE):
+    """GNNTrainer for the default 6/128/3 network (the fused step), GeneralTrainer for every other shape."""
+    return GNNTrainer(model, max_batch=max_batch) if getattr(model, "fused", False) else GeneralTrainer(model, max_batch=max_batch)
 
 
 def train_network():
@@ -191,16 +283,14 @@ def _train_loop(rank, world):
     import torch.distributed as dist
     from . import distributed as aqd
     dev = aqd.device()                                                             # this rank's GPU, explicitly
-    model = GNNNetwork()
-    model.load_state_dict(torch.load(PV_NETWORK_PATH + 'best.pth', map_location=dev, weights_only=True))
-    model = model.to(dev)
+    model = load_network(PV_NETWORK_PATH + 'best.pth', dev)                       # GNNNetwork, or the shape best.pth holds
     history = load_data()
     s, p, v = zip(*history)
-    s = torch.from_numpy(model.preprocess_input(s)).to(dev)                        # uint8 [n,72]
+    s = torch.from_numpy(pack_states(s, model.board_size)).to(dev)                # uint8 [n,72]
     p = torch.tensor(np.array(p), dtype=torch.float32, device=dev)                 # policy targets
     v = torch.tensor(np.array(v), dtype=torch.float32, device=dev)                 # value targets
     n = s.shape[0]
-    trainer = GNNTrainer(model, max_batch=BATCH_SIZE)
+    trainer = trainer_for(model, max_batch=BATCH_SIZE)
     for epoch in range(NUM_EPOCH):
         lr = LEARNING_RATE * lr_lambda(epoch)                                      # LambdaLR, stepped once per epoch (:98)
         perm = torch.randperm(n, device=dev)                                    # DataLoader(shuffle=True), last batch kept

@@ -413,6 +413,46 @@ int aqg_gcn_train_steps(const aqg_train* t_host, const uint8_t* states72, const 
  * -1 on error.  A diagnostic: results do not depend on it. */
 long long aqg_gcn_train_fallbacks(int reset);
 
+/* ------------------------------------------------------------------ training step at any shape (additive to ABI 14)
+ *
+ * The step of aqg_gcn_train_step -- forward, the same two losses, backward, torch.optim.Adam -- for a GraphPolicyValueNetwork of
+ * any shape aqg_gcn_general_net accepts (6 input features, hidden 2..1024, 1..AQG_GENERAL_MAX_LAYERS layers, policy_size 1..4096;
+ * the default 6/128/3 included), on board records (state72, board_size 3/5/7/9), all f32 (csrc/gcn_train_general.hip).  The
+ * forward is aqg_gcn_forward_boards_general's kernels with every layer's output kept: policy and value equal that call's bit for
+ * bit.  The backward runs one fused launch per GCN layer (stencil and f32-input MFMA), the width-generic primitives for the heads
+ * and the weight gradients, and one multi-tensor Adam launch.  No atomics (two runs give bit-identical parameters), no allocation,
+ * no host synchronisation.
+ *
+ * aqg_train_general: num_features .. policy_size = the network's shape (as in aqg_gcn_general_net); params / grads / adam_m /
+ *   adam_v [0 .. 2 L + 8) = device pointers to contiguous f32 tensors indexed like aqg_gcn_general_net.params (grads, adam_m, adam_v
+ *   of the same shapes; the parameters are updated in place).  batch = positions of this step, step = the Adam count of THIS update
+ *   (>= 1), lr / beta1 / beta2 / eps as torch.optim.Adam.  policy [batch, policy_size], value [batch], loss [batch, 2] (per-position
+ *   policy / value loss terms) and loss_mean [2] (their batch means, summed in position order) receive the step's outputs; each may
+ *   be NULL (it then lives in the workspace).  workspace: aqg_gcn_train_general_workspace_floats(board_size, hidden, num_layers,
+ *   policy_size, max_batch) floats serve every batch up to max_batch.
+ * aqg_gcn_train_step_general: mode 0 = gradients only (into grads), 1 = gradients + Adam, 2 = Adam only from whatever grads holds
+ *   (data parallel: local gradients, all-reduce, update), as aqg_gcn_train_step.
+ * aqg_gcn_train_steps_general: one epoch, every step mode 1, as aqg_gcn_train_steps: step i takes the positions
+ *   order[i*batch .. (i+1)*batch) (order NULL = 0 .. positions-1; the last batch may be short), t->step counts up from its entry
+ *   value, and each step adds its two batch-mean losses to loss_sums[2] (device, may be NULL). */
+typedef struct aqg_train_general {
+    int32_t board_size, num_features, hidden, num_layers, policy_size;
+    int32_t batch, step;
+    float lr, beta1, beta2, eps;
+    float* params[2 * AQG_GENERAL_MAX_LAYERS + 8];
+    float* grads[2 * AQG_GENERAL_MAX_LAYERS + 8];
+    float* adam_m[2 * AQG_GENERAL_MAX_LAYERS + 8];
+    float* adam_v[2 * AQG_GENERAL_MAX_LAYERS + 8];
+    float* policy; float* value; float* loss; float* loss_mean;
+    float* workspace;
+    size_t workspace_floats;
+} aqg_train_general;
+size_t aqg_gcn_train_general_workspace_floats(int board_size, int hidden, int num_layers, int policy_size, int max_batch);
+int aqg_gcn_train_step_general(const aqg_train_general* t_host, const uint8_t* states72, const float* pi_target, const float* z_target,
+                               int mode, void* stream);
+int aqg_gcn_train_steps_general(const aqg_train_general* t_host, const uint8_t* states72, const float* pi_target,
+                                const float* z_target, const int64_t* order, long long positions, float* loss_sums, void* stream);
+
 /* ------------------------------------------------------------------ CPU baseline agents (agents.py) -- HOST pointers, host code */
 
 /* The reference's baseline opponents (agents.py:14-214) are CPU code; so are these: the host instantiation of the rule header
