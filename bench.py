@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""bench.py -- self-play games/s (whole job) + GNN boards/s on MI355X, with roofline and CPU baseline.
+"""bench.py -- self-play games/s (whole job) on MI355X with its roofline; --full adds GNN boards/s, the other legs and the CPU baseline.
 
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N > 1 launched by torch.distributed.run with one
 rank per GPU (RCCL).  One STEP = one self-play generation on every rank: `--games` concurrent 9x9 games per GPU
@@ -8,6 +8,12 @@ rank per GPU (RCCL).  One STEP = one self-play generation on every rank: `--game
 all-gather of the (s, pi, z) tuples over RCCL/xGMI (configs[3]).  Weak scaling: per-GPU work is fixed.
 
 `--backend gloo` swaps RCCL for gloo (host tensors) so that the N > 1 path can be rehearsed with several ranks on one GPU.
+
+A plain run sets up, warms up (`--warmup` generations), times `--steps` generations, writes `--dump-outputs` if asked and prints the
+line: the contract keys, `config`, `leaf_evals_per_s`, `mean_plies_per_game`, `positions_gathered_per_step` and `roofline` (its event
+pairs sit inside the timed generations, so it costs nothing more).  `--full` adds every other leg below -- each one a measurement of
+its own after (rccl_group_alive: before) the timed steps -- and `roofline.mfma_busy_pmc`; `--no-extra-legs` / `--no-cpu-baseline` then
+leave out all legs but gnn_forward / the CPU baseline, as before.
 
 Rank 0 prints ONE JSON line, numbers only (< 6 KB, so that a driver keeping an 8 KB tail keeps every leg); what each key means, how
 it is measured and what bounds it is written HERE and in DESIGN.md section 5 (`notes_ref`).  Besides the contract keys it carries
@@ -31,7 +37,8 @@ it is measured and what bounds it is written HERE and in DESIGN.md section 5 (`n
                  boards it processed / its summed launch durations (HIP event pairs recorded inside the library around
                  the trunk launches of sampled moves -- one game set running alone, plain launches --, on the launch stream), against the matrix-pipe roof of the
                  fp32-equivalent fp16-split algorithm; the SURVEY 8(d) HBM figure (169,760 B/board against 8 TB/s) is
-                 reported beside it as hbm_frac_survey_formula
+                 reported beside it as hbm_frac_survey_formula; with --full also mfma_busy_pmc, the matrix pipes' busy share that
+                 separate rocprofv3 --pmc passes recorded in profiles/r04_pmc_trunk.json
   eval_cache   : round 4 -- the evaluation cache (include/aqgnn.h eval_cache_keys): a small generation with the table off
                  and on compared byte for byte in this process (identity_check), then the headline configuration and the large_batch
                  configuration WITH the table, with hit rate, network evaluations/s and the ratio to the cache-less number of the same
@@ -283,18 +290,22 @@ def main():
     ap.add_argument("--games", type=int, default=2048, help="concurrent games per GPU")
     ap.add_argument("--sims", type=int, default=200, help="MCTS simulations per move")
     ap.add_argument("--sets", type=int, default=4, help="independent game sets per GPU, one HIP stream each (engine.MultiSetSelfPlay)")
-    ap.add_argument("--gnn-batch", type=int, default=4096)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (gnn_forward, rccl_group_alive, legal_mask, step_kernel, slot_refill, "
+                         "train_step, large_batch, eval_cache, cpu_baseline, ...); a plain run measures the headline alone")
+    ap.add_argument("--gnn-batch", type=int, default=4096, help="boards per launch of the `gnn_forward` leg (--full)")
     ap.add_argument("--trunk-variant", type=int, default=3, help="developer knob: aqg_set_option trunk_variant (3 = per-launch choice)")
     ap.add_argument("--trunk-grid", type=int, default=0, help="developer knob: cap the trunk's persistent grid (0 = default 512)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                     help="torch.distributed backend for N > 1: nccl = RCCL over xGMI (default); gloo = host tensors, for rehearsing "
                          "several ranks on one GPU")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the step-kernel / slot-refill / training legs (profiling runs)")
+    ap.add_argument("--no-extra-legs", action="store_true",
+                    help="with --full: skip every leg but gnn_forward and the CPU baseline (profiling runs)")
     ap.add_argument("--eval-cache-slots", type=int, default=8192,
-                    help="entries per game slot of the evaluation cache in the `eval_cache` LEG (0 = skip the leg); the headline `value` always runs without it")
+                    help="entries per game slot of the evaluation cache in the `eval_cache` LEG (--full; 0 = skip the leg); the headline `value` always runs without it")
     ap.add_argument("--large-games", type=int, default=16384,
-                    help="extra single-GPU leg: one generation at this many concurrent games (north star: >= 10k); 0 = skip")
+                    help="extra single-GPU leg (--full): one generation at this many concurrent games (north star: >= 10k); 0 = skip")
     ap.add_argument("--rccl-child", default=None, choices=_RCCL_ORDERS, help="internal: one process of the rccl_group_alive leg")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write the last timed step's gathered (s, pi, z) rows to DIR/<name>.npy (see the docstring)")
@@ -310,7 +321,7 @@ def main():
     if world != args.gpus and world > 1:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     rccl_leg = None
-    if world == 1 and not args.no_extra_legs and dist.is_nccl_available():
+    if args.full and world == 1 and not args.no_extra_legs and dist.is_nccl_available():
         rccl_leg = rccl_group_alive_leg(args.games, args.sims, args.sets)     # before this process creates its own GPU context
     local = local % max(torch.cuda.device_count(), 1)        # gloo rehearsal: more ranks than GPUs share the card
     torch.cuda.set_device(local)
@@ -411,46 +422,47 @@ def main():
     total_games, total_evals = float(tt[1]), float(tt[2])
     mean_plies = positions / max(total_games / max(args.steps, 1), 1.0)   # gathered positions of the last step / games per step
 
-    # ---- configs[1]: GNN forward (trunk + heads), B = 4096 synthetic boards, HIP events on the launch stream (rank-local); the same
-    #      at 16,384 and 65,536 boards
-    from tools.microbench import synth_states, time_ms
-    B = args.gnn_batch
-    pk = model.packed_weights(dev)
-    gnn_flags = model.gnn_flags(dev)          # what GraphPolicyValueNetwork.forward_states passes for this weight set (range guard: proven bound / tracking)
-    sat_word = model.saturation_word(dev)
+    if args.full:
+        # ---- configs[1]: GNN forward (trunk + heads), B = 4096 synthetic boards, HIP events on the launch stream (rank-local); the same
+        #      at 16,384 and 65,536 boards
+        from tools.microbench import synth_states, time_ms
+        B = args.gnn_batch
+        pk = model.packed_weights(dev)
+        gnn_flags = model.gnn_flags(dev)          # what GraphPolicyValueNetwork.forward_states passes for this weight set (range guard: proven bound / tracking)
+        sat_word = model.saturation_word(dev)
 
-    def forward_fn(nb, flags):
-        bd = synth_states(nb, seed=0, dev=dev)
-        pooled = torch.empty((nb, 128), device=dev)
-        policy = torch.empty((nb, 209), device=dev)
-        value = torch.empty((nb,), device=dev)
+        def forward_fn(nb, flags):
+            bd = synth_states(nb, seed=0, dev=dev)
+            pooled = torch.empty((nb, 128), device=dev)
+            policy = torch.empty((nb, 209), device=dev)
+            value = torch.empty((nb,), device=dev)
 
-        def fwd():
-            _lib.check(lib.aqg_gcn_forward_boards_guarded(9, _lib.ptr(bd), 0, nb, _lib.ptr(pk), _lib.ptr(pooled), None, _lib.ptr(policy), None,
-                                                          _lib.ptr(value), flags, _lib.ptr(sat_word), _lib.stream_ptr(dev)), "fwd")
-        fwd.keep = (bd, pooled, policy, value)
-        return fwd
-    boards = synth_states(B, seed=0, dev=dev)
-    # the builds are timed three times in interleaved order and the best time kept: a single pass right after the pools were freed
-    # under-reported the exact-f32 kernel by 3.4x in the round-1 driver run (its scratch arena grows on first use)
-    builds = {"proven_build": forward_fn(B, _lib.GNN_RANGE_PROVEN), "tracking_build": forward_fn(B, 0), "f32_mfma_exact": forward_fn(B, _lib.GNN_EXACT_F32)}
-    samples = {k: [] for k in builds}
-    for rep in range(3):
-        for k, fn in builds.items():
-            samples[k].append(time_ms(fn, 60, warmup=10))
-    build_rate = {k: B / (min(v) * 1e-3) for k, v in samples.items()}
-    fwd = forward_fn(B, gnn_flags)
-    fwd_ms = min(time_ms(fwd, 200, warmup=20) for _ in range(2))      # what this weight set runs, after the clocks have settled on this workload
-    fwd_rates = {str(B): B / (fwd_ms * 1e-3)}
-    for nb in (16384, 65536):
-        if world == 1:
-            f2 = forward_fn(nb, gnn_flags)
-            fwd_rates[str(nb)] = nb / (min(time_ms(f2, 30, warmup=5) for _ in range(2)) * 1e-3)
-            del f2
-    del builds
+            def fwd():
+                _lib.check(lib.aqg_gcn_forward_boards_guarded(9, _lib.ptr(bd), 0, nb, _lib.ptr(pk), _lib.ptr(pooled), None, _lib.ptr(policy), None,
+                                                              _lib.ptr(value), flags, _lib.ptr(sat_word), _lib.stream_ptr(dev)), "fwd")
+            fwd.keep = (bd, pooled, policy, value)
+            return fwd
+        boards = synth_states(B, seed=0, dev=dev)
+        # the builds are timed three times in interleaved order and the best time kept: a single pass right after the pools were freed
+        # under-reported the exact-f32 kernel by 3.4x in a round-1 run (its scratch arena grows on first use)
+        builds = {"proven_build": forward_fn(B, _lib.GNN_RANGE_PROVEN), "tracking_build": forward_fn(B, 0), "f32_mfma_exact": forward_fn(B, _lib.GNN_EXACT_F32)}
+        samples = {k: [] for k in builds}
+        for rep in range(3):
+            for k, fn in builds.items():
+                samples[k].append(time_ms(fn, 60, warmup=10))
+        build_rate = {k: B / (min(v) * 1e-3) for k, v in samples.items()}
+        fwd = forward_fn(B, gnn_flags)
+        fwd_ms = min(time_ms(fwd, 200, warmup=20) for _ in range(2))      # what this weight set runs, after the clocks have settled on this workload
+        fwd_rates = {str(B): B / (fwd_ms * 1e-3)}
+        for nb in (16384, 65536):
+            if world == 1:
+                f2 = forward_fn(nb, gnn_flags)
+                fwd_rates[str(nb)] = nb / (min(time_ms(f2, 30, warmup=5) for _ in range(2)) * 1e-3)
+                del f2
+        del builds
 
     step_leg = refill_leg = train_leg = legal_leg = graph_leg = None
-    if world == 1 and not args.no_extra_legs:
+    if args.full and world == 1 and not args.no_extra_legs:
         legal_leg = legal_mask_leg(dev, lib, _lib, synth_states)
         # ---- the reference's literal operator forward(x, edge_index, batch) (pv_network_gnn.py:53-64) on the same boards given as
         #      a PyG-style batch: gcn_norm / CSR built per call with torch ops, then the generic graph kernels (no board structure
@@ -564,7 +576,7 @@ def main():
         del trainer, tr_model
 
     large = None
-    if world == 1 and args.large_games > 0 and not args.no_extra_legs:
+    if args.full and world == 1 and args.large_games > 0 and not args.no_extra_legs:
         torch.cuda.empty_cache()
         eng = MultiSetSelfPlay(model, num_games=args.large_games, sims=args.sims, num_sets=args.sets, seed=77)
         for _ in range(2):                    # two untimed moves: graph capture, first-touch of the 14 GB tree pools
@@ -582,7 +594,7 @@ def main():
     #      per-slot table of already-evaluated positions on.  Reported as a leg, never as `value`: the games and records are bit-identical
     #      (checked here on a small generation, and in tests/test_gpu_parity.py against the oracle), the network simply is not asked twice.
     cache_leg = None
-    if world == 1 and args.eval_cache_slots > 0 and not args.no_extra_legs:
+    if args.full and world == 1 and args.eval_cache_slots > 0 and not args.no_extra_legs:
         del eng
         torch.cuda.empty_cache()
         small = {}
@@ -622,10 +634,9 @@ def main():
         boards_per_s_kernel = trunk_boards / (trunk_ms * 1e-3) if trunk_ms > 0 else 0.0
         pmc = None                               # matrix-pipe busy share: a RECORDED rocprofv3 --pmc measurement (separate passes), read from
         pmc_path = os.path.join(ROOT, "profiles", "r04_pmc_trunk.json")      # the file the profiling recipe wrote, never typed in here
-        if os.path.exists(pmc_path):
+        if args.full and os.path.exists(pmc_path):
             with open(pmc_path) as f:
                 pmc = dict(json.load(f), source="profiles/r04_pmc_trunk.json")
-        fwd_rate = fwd_rates[str(B)]
         out = {
             "metric": "self-play games/sec, 9x9 Quoridor (PV-MCTS, GNN evaluator), whole job",
             "value": total_games / elapsed,
@@ -646,28 +657,30 @@ def main():
             "leaf_evals_per_s": total_evals / elapsed,
             "mean_plies_per_game": mean_plies,
             "positions_gathered_per_step": positions,
-            "gnn_forward": {"workload": "BASELINE configs[1]: pv_network_gnn forward (trunk + heads), synthetic boards", "batch": B,
-                            "fp16_range_guard": "proven" if gnn_flags & _lib.GNN_RANGE_PROVEN else ("exact_f32" if gnn_flags & _lib.GNN_EXACT_F32 else "tracking"),
-                            "range_guard_word_after_run": int(sat_word.item()),
-                            "boards_per_s": fwd_rate, "ms": fwd_ms, "boards_per_s_by_batch": fwd_rates, "boards_per_s_by_build": build_rate,
-                            "mfma_frac": fwd_rate * FWD_FLOP_PER_BOARD / (PEAK_F16_MFMA / SPLIT_TERMS),
-                            "frac_vs_f32_input_mfma_peak": fwd_rate * FWD_FLOP_PER_BOARD / PEAK_F32_MFMA,
-                            "hbm_frac_survey_formula": fwd_rate * HBM_BYTES_PER_BOARD / PEAK_HBM},
-            "roofline": {"kernel": "gcn_trunk_boards_mm_kernel<TRACK> (TRACK 0: fp16 range proven for this weight set)", "bound": "mfma",
-                         "achieved": achieved / 1e12, "peak": PEAK_F16_MFMA / SPLIT_TERMS / 1e12,
-                         "unit": "TFLOP/s", "frac": achieved / (PEAK_F16_MFMA / SPLIT_TERMS),
-                         "traffic": None,
-                         "compulsory_bytes_per_board": TRUNK_COMPULSORY_BYTES_PER_BOARD,
-                         "compulsory_hbm_frac": boards_per_s_kernel * TRUNK_COMPULSORY_BYTES_PER_BOARD / PEAK_HBM,
-                         "frac_vs_dense_f16_peak": achieved / PEAK_F16_MFMA,
-                         "mfma_busy_pmc": pmc,
-                         "launches": trunk_launches, "avg_launch_us": trunk_ms / max(trunk_launches, 1) * 1e3,
-                         "boards_per_launch_avg": trunk_boards / max(trunk_launches, 1),
-                         "flop_per_board": TRUNK_FLOP_PER_BOARD,
-                         "hbm_frac_survey_formula": boards_per_s_kernel * HBM_BYTES_PER_BOARD / PEAK_HBM,
-                         "frac_vs_f32_input_mfma_peak": achieved / PEAK_F32_MFMA,
-                         "f16_mfma_issued_tflops": boards_per_s_kernel * TRUNK_MFMA_PER_BOARD * 16384 / 1e12},
         }
+        if args.full:
+            fwd_rate = fwd_rates[str(B)]
+            out["gnn_forward"] = {"workload": "BASELINE configs[1]: pv_network_gnn forward (trunk + heads), synthetic boards", "batch": B,
+                                  "fp16_range_guard": "proven" if gnn_flags & _lib.GNN_RANGE_PROVEN else ("exact_f32" if gnn_flags & _lib.GNN_EXACT_F32 else "tracking"),
+                                  "range_guard_word_after_run": int(sat_word.item()),
+                                  "boards_per_s": fwd_rate, "ms": fwd_ms, "boards_per_s_by_batch": fwd_rates, "boards_per_s_by_build": build_rate,
+                                  "mfma_frac": fwd_rate * FWD_FLOP_PER_BOARD / (PEAK_F16_MFMA / SPLIT_TERMS),
+                                  "frac_vs_f32_input_mfma_peak": fwd_rate * FWD_FLOP_PER_BOARD / PEAK_F32_MFMA,
+                                  "hbm_frac_survey_formula": fwd_rate * HBM_BYTES_PER_BOARD / PEAK_HBM}
+        out["roofline"] = {"kernel": "gcn_trunk_boards_mm_kernel<TRACK> (TRACK 0: fp16 range proven for this weight set)", "bound": "mfma",
+                           "achieved": achieved / 1e12, "peak": PEAK_F16_MFMA / SPLIT_TERMS / 1e12,
+                           "unit": "TFLOP/s", "frac": achieved / (PEAK_F16_MFMA / SPLIT_TERMS),
+                           "traffic": None,
+                           "compulsory_bytes_per_board": TRUNK_COMPULSORY_BYTES_PER_BOARD,
+                           "compulsory_hbm_frac": boards_per_s_kernel * TRUNK_COMPULSORY_BYTES_PER_BOARD / PEAK_HBM,
+                           "frac_vs_dense_f16_peak": achieved / PEAK_F16_MFMA,
+                           **({"mfma_busy_pmc": pmc} if args.full else {}),
+                           "launches": trunk_launches, "avg_launch_us": trunk_ms / max(trunk_launches, 1) * 1e3,
+                           "boards_per_launch_avg": trunk_boards / max(trunk_launches, 1),
+                           "flop_per_board": TRUNK_FLOP_PER_BOARD,
+                           "hbm_frac_survey_formula": boards_per_s_kernel * HBM_BYTES_PER_BOARD / PEAK_HBM,
+                           "frac_vs_f32_input_mfma_peak": achieved / PEAK_F32_MFMA,
+                           "f16_mfma_issued_tflops": boards_per_s_kernel * TRUNK_MFMA_PER_BOARD * 16384 / 1e12}
         if rccl_leg is not None:
             out["rccl_group_alive"] = rccl_leg
         if cache_leg is not None:
@@ -691,7 +704,7 @@ def main():
             out["train_step"] = train_leg
         if large is not None:
             out["large_batch"] = large
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.sims, mean_plies)
             out["cpu_baseline"]["host_cpus"] = os.cpu_count()
             if legal_sample is not None:

@@ -423,6 +423,14 @@ def test_bench_cpu_baseline_workers():
     assert r["value"] > 0 and abs(r["sims_per_s"] - r["value"] * 100.0 * 8) <= 1e-6 * r["sims_per_s"]
 
 
+def test_bench_full_option():
+    """bench.py keeps every leg beside the headline (the CPU baseline among them) behind --full; a plain run times the headline alone."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert re.search(r"^\s+--full\b", r.stdout, re.M)
+
+
 def test_static_fp16_range_bound_of_a_weight_set():
     """pv_network_gnn._range_proven (what lets the split trunk drop its per-value range tracking, include/aqgnn.h
     AQG_GNN_RANGE_PROVEN): a rigorous bound from the weights alone.  It must hold for initialisation-scale weights, fail once the

@@ -115,7 +115,7 @@ def main():
     if bench:
         for i, so in enumerate(libs):
             env = dict(os.environ, AQG_LIB_PATH=so)
-            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra-legs"],
+            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra-legs"],
                                  env=env, capture_output=True, text=True, timeout=900)
             try:
                 d = json.loads(out.stdout.strip().splitlines()[-1])

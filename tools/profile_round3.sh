@@ -45,6 +45,6 @@ if [ "$STAGE" = all ] || [ "$STAGE" = pmc ]; then
 fi
 if [ "$STAGE" = all ] || [ "$STAGE" = bench ]; then
   echo "[bench kernel trace]"; rm -rf /tmp/p1
-  timeout -k 10 500 rocprofv3 --kernel-trace -d /tmp/p1 -o b -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extra-legs > $OUT/bench_under_rocprof.log 2>&1
+  timeout -k 10 500 rocprofv3 --kernel-trace -d /tmp/p1 -o b -- python3 $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-extra-legs > $OUT/bench_under_rocprof.log 2>&1
   python3 $R/tools/rocpd_stats.py /tmp/p1/b_results.db $OUT/bench_kernel_stats.csv > /dev/null && head -8 $OUT/bench_kernel_stats.csv | cut -c1-170
 fi
