@@ -50,10 +50,18 @@ class GeneralNetStruct(_c.Structure):
                 + [("params", _vp * (2 * GENERAL_MAX_LAYERS + 8))])
 
 
+CNN_MAX_FILTERS, CNN_MAX_BLOCKS = 512, 40   # AQG_CNN_MAX_FILTERS, AQG_CNN_MAX_BLOCKS
+
+
+class CnnNetStruct(_c.Structure):
+    """Mirror of `struct aqg_cnn_net` (include/aqgnn.h): the residual CNN's shape and its packed buffer (aqg_cnn_pack)."""
+    _fields_ = [(n, _i32) for n in ("board_size", "num_filters", "num_blocks", "policy_size")] + [("packed", _vp)]
+
+
 class EngineStructGeneral(EngineStruct):
     """The whole `struct aqg_engine` of ABI 14: EngineStruct's fields (unchanged offsets) followed by `general_net`, the
-    descriptor of prior_mode 3.  The engine entry points take this one."""
-    _fields_ = [("general_net", GeneralNetStruct)]
+    descriptor of prior_mode 3, and `cnn_net`, the descriptor of prior_mode 4.  The engine entry points take this one."""
+    _fields_ = [("general_net", GeneralNetStruct), ("cnn_net", CnnNetStruct)]
 
 
 class TrainStruct(_c.Structure):
@@ -113,6 +121,13 @@ SIGNATURES = {
     "aqg_gcn_boards_general_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "aqg_gcn_forward_boards_general": (_c.c_int, [_c.c_int, _vp, _c.c_int, _c.c_int, _c.POINTER(GeneralNetStruct), _vp, _vp,
                                                   _c.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aqg_cnn_packed_floats": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "aqg_cnn_pack": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.POINTER(_vp), _c.POINTER(_f32), _vp, _vp]),
+    "aqg_cnn_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "aqg_cnn_forward_boards": (_c.c_int, [_c.c_int, _vp, _c.c_int, _c.c_int, _c.POINTER(CnnNetStruct), _vp, _vp, _c.c_size_t, _vp, _vp,
+                                          _vp, _vp, _vp, _vp]),
+    "aqg_cnn_forward_planes": (_c.c_int, [_c.c_int, _vp, _c.c_int, _c.POINTER(CnnNetStruct), _vp, _vp, _c.c_size_t, _vp, _vp, _vp,
+                                          _vp, _vp, _vp]),
     "aqg_engine_reset": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),
     "aqg_engine_clear_eval_cache": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),
     "aqg_engine_move": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),

@@ -68,6 +68,15 @@ size_t boards_general_workspace_floats(int N, int hidden, int A, int B);
 int launch_gcn_forward_boards_general(int N, const void* states, int fmt, int B, const aqg_gcn_general_net* net,
                                       const uint8_t* active, float* workspace, size_t workspace_floats, float* pooled, float* logits,
                                       float* policy, float* value_pre, float* value, hipStream_t st);
+size_t cnn_packed_floats(int F, int L, int A);
+int launch_cnn_pack(int F, int L, int A, const float* const* params, const float* eps, float* packed, hipStream_t st);
+size_t cnn_workspace_floats(int N, int F, int A, int B);
+int launch_cnn_forward_boards(int N, const void* states, int fmt, int B, const aqg_cnn_net* net, const uint8_t* active, float* workspace,
+                              size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre, float* value,
+                              hipStream_t st);
+int launch_cnn_forward_planes(int N, const float* planes, int B, const aqg_cnn_net* net, const uint8_t* active, float* workspace,
+                              size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre, float* value,
+                              hipStream_t st);
 int engine_reset(const aqg_engine& e, hipStream_t st);
 int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st);
 int engine_begin_move(const aqg_engine& e, hipStream_t st);
@@ -296,6 +305,29 @@ int aqg_gcn_forward_boards_general(int board_size, const void* states, int state
                                    float* policy, float* value_pre, float* value, void* stream) {
     return launch_gcn_forward_boards_general(board_size, states, state_fmt, B, net, active, workspace, workspace_floats, pooled,
                                              logits, policy, value_pre, value, (hipStream_t)stream);
+}
+
+size_t aqg_cnn_packed_floats(int num_filters, int num_blocks, int policy_size) {
+    return cnn_packed_floats(num_filters, num_blocks, policy_size);
+}
+int aqg_cnn_pack(int num_filters, int num_blocks, int policy_size, const float* const* params_host, const float* eps_host, float* packed,
+                 void* stream) {
+    return launch_cnn_pack(num_filters, num_blocks, policy_size, params_host, eps_host, packed, (hipStream_t)stream);
+}
+size_t aqg_cnn_workspace_floats(int board_size, int num_filters, int policy_size, int B) {
+    return cnn_workspace_floats(board_size, num_filters, policy_size, B);
+}
+int aqg_cnn_forward_boards(int board_size, const void* states, int state_fmt, int B, const aqg_cnn_net* net, const uint8_t* active,
+                           float* workspace, size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre,
+                           float* value, void* stream) {
+    return launch_cnn_forward_boards(board_size, states, state_fmt, B, net, active, workspace, workspace_floats, pooled, logits, policy,
+                                     value_pre, value, (hipStream_t)stream);
+}
+int aqg_cnn_forward_planes(int board_size, const float* planes, int B, const aqg_cnn_net* net, const uint8_t* active, float* workspace,
+                           size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre, float* value,
+                           void* stream) {
+    return launch_cnn_forward_planes(board_size, planes, B, net, active, workspace, workspace_floats, pooled, logits, policy, value_pre,
+                                     value, (hipStream_t)stream);
 }
 
 int aqg_engine_reset(const aqg_engine* e, void* stream) {

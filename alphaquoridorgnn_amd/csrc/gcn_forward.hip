@@ -1884,7 +1884,8 @@ int launch_gcn_forward_graph_saved(int F, int A, const float* x, int num_nodes, 
 // adjacency in ELL form (<= 5 entries per node) -> 3 x (linear, ELL gather + bias + ReLU) -> mean pool -> exact heads.
 // Correctness-first, fp32 throughout.  Workspace (caller-owned): 272 floats per node.
 // ---------------------------------------------------------------------------------------------
-template <int N>
+// ELL = false: the node features only (the CNN's input planes, csrc/cnn_forward.hip); ell_idx / ell_w are not touched
+template <int N, bool ELL = true>
 __global__ __launch_bounds__(256) void boards_prep_kernel(const void* __restrict__ states, int fmt, int B, float* __restrict__ x0,
                                                           int32_t* __restrict__ ell_idx, float* __restrict__ ell_w) {
     constexpr int V = N * N, S = N - 1;
@@ -1902,6 +1903,7 @@ __global__ __launch_bounds__(256) void boards_prep_kernel(const void* __restrict
     f[3] = (float)s.ewl;
     f[4] = (slot_ok && ((s.hw >> slot) & 1)) ? 1.f : 0.f;
     f[5] = (slot_ok && ((s.vw >> slot) & 1)) ? 1.f : 0.f;
+    if constexpr (!ELL) return;
     const int ob = tile_open_bits<N>(s.hw, s.vw, t);
     const float di = dinv_of_bits(ob);
     const int nb[4] = {t - N, t + N, t - 1, t + 1};
@@ -1994,6 +1996,21 @@ int launch_gcn_boards_graph(int N, const void* states, int fmt, int B, float* x0
         case 5: hipLaunchKernelGGL(boards_prep_kernel<5>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
         case 7: hipLaunchKernelGGL(boards_prep_kernel<7>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
         default: hipLaunchKernelGGL(boards_prep_kernel<9>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
+    }
+    return check_launch("boards_prep_kernel");
+}
+
+// The featuriser's node features alone: x0 [B*V,6], the six planes of pv_network_cnn.py:88-114 tile by tile (the CNN's input).
+int launch_gcn_boards_features(int N, const void* states, int fmt, int B, float* x0, hipStream_t st) {
+    if (!(N == 3 || N == 5 || N == 7 || N == 9)) return fail("board_size must be 3, 5, 7 or 9");
+    if (B <= 0) return 0;
+    const int R = B * N * N;
+    const dim3 pg((R + 255) / 256), blk(256);
+    switch (N) {
+        case 3: hipLaunchKernelGGL((boards_prep_kernel<3, false>), pg, blk, 0, st, states, fmt, B, x0, nullptr, nullptr); break;
+        case 5: hipLaunchKernelGGL((boards_prep_kernel<5, false>), pg, blk, 0, st, states, fmt, B, x0, nullptr, nullptr); break;
+        case 7: hipLaunchKernelGGL((boards_prep_kernel<7, false>), pg, blk, 0, st, states, fmt, B, x0, nullptr, nullptr); break;
+        default: hipLaunchKernelGGL((boards_prep_kernel<9, false>), pg, blk, 0, st, states, fmt, B, x0, nullptr, nullptr); break;
     }
     return check_launch("boards_prep_kernel");
 }

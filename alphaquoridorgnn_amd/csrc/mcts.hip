@@ -42,6 +42,11 @@ int check_general_net(const aqg_gcn_general_net* net, const char** why);
 int launch_gcn_forward_boards_general(int N, const void* states, int fmt, int B, const aqg_gcn_general_net* net,
                                       const uint8_t* active, float* workspace, size_t workspace_floats, float* pooled, float* logits,
                                       float* policy, float* value_pre, float* value, hipStream_t st);
+size_t cnn_workspace_floats(int N, int F, int A, int B);
+int check_cnn_net(const aqg_cnn_net* net, int N, const char** why);
+int launch_cnn_forward_boards(int N, const void* states, int fmt, int B, const aqg_cnn_net* net, const uint8_t* active, float* workspace,
+                              size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre, float* value,
+                              hipStream_t st);
 extern int g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, g_profile_trunk, g_trunk_prio, g_heads_prio;
 void profile_mark(hipStream_t st, long long units);
 int g_use_graph = 1;       // aqg_set_option("use_graph", 0) forces plain launches
@@ -1028,10 +1033,10 @@ __global__ __launch_bounds__(256) void engine_step_kernel(aqg_engine e, int do_e
 
 template <int N>
 static void launch_step(const aqg_engine& e_in, int do_expand, int do_select, hipStream_t st, int list_sim = -1) {
-    // prior_mode 3 leaves the network's dense [G,A] policy in e.policy exactly like prior_mode 0: the step kernels gather,
-    // renormalise and cache it as mode 0 -- they are handed the struct with prior_mode 0, so no step kernel knows mode 3
+    // prior_mode 3 and 4 leave the network's dense [G,A] policy in e.policy exactly like prior_mode 0: the step kernels gather,
+    // renormalise and cache it as mode 0 -- they are handed the struct with prior_mode 0, so no step kernel knows mode 3 or 4
     aqg_engine e = e_in;
-    if (e.prior_mode == 3) e.prior_mode = 0;
+    if (e.prior_mode == 3 || e.prior_mode == 4) e.prior_mode = 0;
     const dim3 grid((e.num_games + 3) / 4), block(256);
     if (g_profile_trunk == 2) profile_mark(st, e.num_games);       // measurement mode 2: the event pairs bracket the step launches
     if (g_step_variant == 1) {
@@ -1205,7 +1210,13 @@ static int validate(const aqg_engine& e) {
     if ((long long)e.node_cap >= (1 << 24)) return fail("node_cap must be < 2^24");
     if (e.node_cap < 1 + MAX_LEGAL) return fail("node_cap too small");
     if (e.prior_mode == 0 && N != 9 && !e.gnn_workspace) return fail("boards other than 9x9 need gnn_workspace for the GNN evaluator");
-    if (e.prior_mode < 0 || e.prior_mode > 3) return fail("prior_mode must be 0, 1, 2 or 3");
+    if (e.prior_mode < 0 || e.prior_mode > 4) return fail("prior_mode must be 0, 1, 2, 3 or 4");
+    if (e.prior_mode == 4) {
+        const char* why = "";
+        if (check_cnn_net(&e.cnn_net, N, &why)) return fail("prior_mode 4 needs a complete cnn_net", why);
+        if (e.cnn_net.policy_size != N * N + 2 * (N - 1) * (N - 1)) return fail("prior_mode 4: cnn_net.policy_size must be the board's action count");
+        if (!e.gnn_workspace) return fail("prior_mode 4 needs gnn_workspace (aqg_cnn_workspace_floats)");
+    }
     if (e.prior_mode == 3) {
         const char* why = "";
         if (check_general_net(&e.general_net, &why)) return fail("prior_mode 3 needs a complete general_net", why);
@@ -1215,7 +1226,7 @@ static int validate(const aqg_engine& e) {
     if (e.quota < e.num_games) return fail("quota must be >= num_games");
     if (!e.slot_game || !e.game_done || !e.game_slot || !e.game_first_move) return fail("slot_game / game_done / game_slot / game_first_move are required");
     if (e.eval_cache_keys) {
-        if (e.prior_mode != 0 && e.prior_mode != 3) return fail("the evaluation cache serves the network evaluators only (prior_mode 0 or 3)");
+        if (e.prior_mode != 0 && e.prior_mode != 3 && e.prior_mode != 4) return fail("the evaluation cache serves the network evaluators only (prior_mode 0, 3 or 4)");
         if (!e.eval_cache_rows || !e.eval_cache_slot || !e.eval_mask || !e.stat_cache_hits) return fail("eval_cache_rows / eval_cache_slot / eval_mask / stat_cache_hits are required with eval_cache_keys");
         if ((e.eval_list == nullptr) != (e.eval_count == nullptr)) return fail("eval_list and eval_count come together");
         if (e.eval_cache_log2 < 6 || e.eval_cache_log2 > 20) return fail("eval_cache_log2 must be 6..20");
@@ -1247,6 +1258,13 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st) {
                                                           boards_general_workspace_floats(N, e.general_net.hidden, e.general_net.policy_size,
                                                                                           e.num_games),
                                                           nullptr, nullptr, e.policy, nullptr, e.value, st))
+                return r;
+        } else if (e.prior_mode == 4) {
+            // the residual CNN: featuriser, one implicit-GEMM launch per conv, heads -- all over e.gnn_workspace
+            if (int r = launch_cnn_forward_boards(N, e.leaf_state, 1, e.num_games, &e.cnn_net, e.eval_cache_keys ? e.eval_mask : e.leaf_flag,
+                                                  e.gnn_workspace,
+                                                  cnn_workspace_floats(N, e.cnn_net.num_filters, e.cnn_net.policy_size, e.num_games),
+                                                  nullptr, nullptr, e.policy, nullptr, e.value, st))
                 return r;
         } else {
             hipLaunchKernelGGL(engine_fake_eval_kernel<N>, grid, block, 0, st, e);

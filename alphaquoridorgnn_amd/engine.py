@@ -25,9 +25,10 @@ class BatchedSelfPlay:
         evaluator used by the parity tests (oracle/mcts.py FakeModel); evaluator='external' calls `model.predict(state,
         device)` -- ANY object honouring the reference's BaseNetwork contract (BaseNetwork.py:36-40), e.g. a stock CNN --
         once per simulation and game from the host, exactly like pv_mcts.py:47 (plumbing path: one host round trip per
-        simulation).  evaluator='general' runs a GraphPolicyValueNetwork of ANY shape (6 input features) on the library's own
+        simulation).  evaluator='cnn' runs the reference's residual CNNNetwork (pv_network_cnn.py) on the library's own kernels
+        (prior_mode 4, aqg_cnn_forward_boards).  evaluator='general' runs a GraphPolicyValueNetwork of ANY shape (6 input features) on the library's own
         kernels (prior_mode 3, aqg_gcn_forward_boards_general): the per-move cost of 'gnn', no host work per simulation.
-        eval_cache_slots (evaluator='gnn' or 'general'; a power of two >= 64, 0 = off; None = the environment's AQG_EVAL_CACHE_SLOTS, else
+        eval_cache_slots (evaluator='gnn', 'general' or 'cnn'; a power of two >= 64, 0 = off; None = the environment's AQG_EVAL_CACHE_SLOTS, else
         off): entries per game slot of the evaluation cache
         (include/aqgnn.h, `eval_cache_keys`): a leaf whose position this slot has already sent through the network is expanded from
         the stored priors / value / legal list -- bit-identical searches and game records, fewer network evaluations (736 bytes of
@@ -100,6 +101,17 @@ class BatchedSelfPlay:
             self._gnn_flags = 0
             t["gnn_workspace"] = z((int(self.lib.aqg_gcn_boards_general_workspace_floats(self.N, model.hidden_dim, self.A, G)),),
                                    torch.float32)
+        elif evaluator == "cnn":
+            if model is None or not hasattr(model, "cnn_net"):
+                raise ValueError("evaluator='cnn' needs a CNNNetwork")
+            if model.policy_output_size != self.A:
+                raise ValueError(f"evaluator='cnn': the network's policy_output_size {model.policy_output_size} is not the "
+                                 f"{self.N}x{self.N} board's {self.A} actions")
+            self._cnn_packed = model.packed_weights(dev)
+            self._cnn = model.cnn_net(dev)
+            t["packed_weights"] = z((4,), torch.float32)
+            self._gnn_flags = 0
+            t["gnn_workspace"] = z((int(self.lib.aqg_cnn_workspace_floats(self.N, model.num_filters, self.A, G)),), torch.float32)
         elif evaluator == "gnn":
             if model is None:
                 raise ValueError("evaluator='gnn' needs a model")
@@ -114,11 +126,11 @@ class BatchedSelfPlay:
             self._gnn_flags = 0
 
         if eval_cache_slots is None:              # opt-in for whole programs (self_play, train_cycle, pv_mcts): one environment variable
-            eval_cache_slots = int(os.environ.get("AQG_EVAL_CACHE_SLOTS", "0")) if evaluator in ("gnn", "general") else 0
+            eval_cache_slots = int(os.environ.get("AQG_EVAL_CACHE_SLOTS", "0")) if evaluator in ("gnn", "general", "cnn") else 0
         self.eval_cache_slots = int(eval_cache_slots)
         if self.eval_cache_slots:
-            if evaluator not in ("gnn", "general"):
-                raise ValueError("eval_cache_slots needs evaluator='gnn' (the table stores network outputs)")
+            if evaluator not in ("gnn", "general", "cnn"):
+                raise ValueError("eval_cache_slots needs evaluator='gnn', 'general' or 'cnn' (the table stores network outputs)")
             if self.eval_cache_slots < 64 or self.eval_cache_slots & (self.eval_cache_slots - 1) or self.eval_cache_slots > (1 << 20):
                 raise ValueError("eval_cache_slots must be a power of two in 64 .. 2**20")
             t["eval_cache_keys"] = z((G * self.eval_cache_slots, 32), torch.uint8)
@@ -133,9 +145,11 @@ class BatchedSelfPlay:
         e.board_size, e.num_walls, e.plies_for_draw = self.N, self.num_walls, self.plies_for_draw
         e.num_games, e.quota, e.sims, e.node_cap = G, Q, self.sims, cap
         e.max_plies = hp if record_history else 0
-        e.prior_mode = {"gnn": 0, "fake": 1, "external": 2, "general": 3}[evaluator]
+        e.prior_mode = {"gnn": 0, "fake": 1, "external": 2, "general": 3, "cnn": 4}[evaluator]
         if evaluator == "general":
             e.general_net = self._general
+        elif evaluator == "cnn":
+            e.cnn_net = self._cnn
         e.fake_bias = int(fake_bias)
         e.gnn_flags = int(self._gnn_flags)
         e.c_puct, e.temperature = float(c_puct), float(temperature)
@@ -181,6 +195,14 @@ class BatchedSelfPlay:
             if self.eval_cache_slots and key != self._general_key:
                 _lib.check(self.lib.aqg_engine_clear_eval_cache(ctypes.byref(self.e), self._stream()), "aqg_engine_clear_eval_cache")
             self._general_key = key
+        elif self.evaluator == "cnn":
+            new = self.model.packed_weights(self.dev)        # the SAME tensor while no parameter or BN statistic has changed
+            changed = new is not self._cnn_packed
+            self._cnn_packed = new
+            self._cnn = self.model.cnn_net(self.dev)
+            self.e.cnn_net = self._cnn
+            if self.eval_cache_slots and changed:
+                _lib.check(self.lib.aqg_engine_clear_eval_cache(ctypes.byref(self.e), self._stream()), "aqg_engine_clear_eval_cache")
 
     def move(self, uniforms=None):
         """One move for every active game.  uniforms: float64 [G] in [0,1) (default: device RNG stream)."""
@@ -367,8 +389,8 @@ class MultiSetSelfPlay:
         if key not in _SET_STREAMS:
             _SET_STREAMS[key] = [torch.cuda.Stream(device=self.dev) for _ in sizes]
         self.streams = _SET_STREAMS[key]
-        if model is not None and kw.get("evaluator", "gnn") == "gnn":
-            model.packed_weights(self.dev)        # pack + calibrate (two forwards and a host sync) on the caller's stream, not inside set 0's
+        if model is not None and kw.get("evaluator", "gnn") in ("gnn", "cnn"):
+            model.packed_weights(self.dev)        # pack (+ calibrate) (two forwards and a host sync) on the caller's stream, not inside set 0's
         self.sets = []
         ready = torch.cuda.current_stream(self.dev).record_event()   # e.g. the model's weight upload on the caller's stream
         for i, g in enumerate(sizes):

@@ -18,6 +18,7 @@ from .constants import PV_NETWORK_PATH, BOARD_SIZE
 from .engine import BatchedSelfPlay
 from .game_logic import State
 from .pv_network_gnn import GNNNetwork, load_network
+from .pv_network_cnn import CNNNetwork
 
 EN_GAME_COUNT = 15    # Number of games per evaluation (evaluate_network.py:14; originally 400)
 EN_TEMPERATURE = 1.0  # Temperature of the Boltzmann distribution (evaluate_network.py:15)
@@ -51,8 +52,8 @@ def update_best_player():
 class BatchedMatch:
     """`num_games` games of player 0 vs player 1 on the batched engine; game i has player (i % 2) moving first
     (evaluate_network.py:69-74).  Players are models (evaluator='gnn': the default 6/128/3 network; evaluator='general':
-    GraphPolicyValueNetworks of any shape with 6 input features, the two players' shapes may differ) or integer biases of the
-    parity tests' hash evaluator (evaluator='fake')."""
+    GraphPolicyValueNetworks of any shape with 6 input features, the two players' shapes may differ; evaluator='cnn': two
+    CNNNetworks, whose shapes may differ too) or integer biases of the parity tests' hash evaluator (evaluator='fake')."""
 
     def __init__(self, players, num_games, sims=None, board_size=BOARD_SIZE, temperature=EN_TEMPERATURE,
                  evaluator="gnn", seed=0, device=None):
@@ -74,6 +75,9 @@ class BatchedMatch:
                 # built on the wider player (the engine's workspace is sized by the network it is built with), then pointed
                 # at the mover's descriptor before every ply
                 eng = BatchedSelfPlay(self._widest(players), evaluator="general", **kw)
+            elif evaluator == "cnn":
+                # likewise: the workspace grows with num_filters only
+                eng = BatchedSelfPlay(max(players, key=lambda m: m.num_filters), evaluator="cnn", **kw)
             else:
                 eng = BatchedSelfPlay(None, evaluator="fake", fake_bias=int(players[first]), **kw)
             self.engines.append(eng)
@@ -87,6 +91,13 @@ class BatchedMatch:
                 if m.policy_output_size != players[0].policy_output_size:
                     raise ValueError("evaluator='general': the two players' policy sizes differ")
             self._general = [m.general_net(dev) for m in players]
+        elif evaluator == "cnn":
+            dev = next(e for e in self.engines if e is not None).dev
+            for m in players:
+                if m.policy_output_size != players[0].policy_output_size:
+                    raise ValueError("evaluator='cnn': the two players' policy sizes differ")
+            self._packed = [m.packed_weights(dev) for m in players]      # kept alive: the descriptors point into them
+            self._cnn = [m.cnn_net(dev) for m in players]
 
     @staticmethod
     def _widest(players):
@@ -100,6 +111,8 @@ class BatchedMatch:
             eng.e.gnn_flags = self._flags[mover]
         elif self.evaluator == "general":
             eng.e.general_net = self._general[mover]
+        elif self.evaluator == "cnn":
+            eng.e.cnn_net = self._cnn[mover]
         else:
             eng.e.fake_bias = int(self.players[mover])
 
@@ -163,15 +176,20 @@ class BatchedMatch:
 def evaluate_network():
     """Network evaluation (evaluate_network.py:52-94): latest vs best, promote when the average point exceeds 0.5.  Two
     default 6/128/3 networks play on the engine's fused evaluator ('gnn'); when either file holds another shape, both play on
-    its any-shape evaluator ('general')."""
+    its any-shape evaluator ('general').  Two CNNs (pv_network_cnn.py) play on the engine's CNN evaluator ('cnn'); a CNN against
+    a GNN is refused (ValueError)."""
     model0 = load_network(PV_NETWORK_PATH + 'latest.pth')
     model1 = load_network(PV_NETWORK_PATH + 'best.pth')
+    cnn = [isinstance(m, CNNNetwork) for m in (model0, model1)]
+    if any(cnn) and not all(cnn):
+        raise ValueError("evaluate_network: latest.pth and best.pth hold different networks (a CNN and a GNN); matches between "
+                         "a CNN and a GNN are not supported")
     fused = all(isinstance(m, GNNNetwork) for m in (model0, model1))
     if fused and torch.cuda.is_available():
         for m in (model0, model1):
             m.packed_weights(torch.device("cuda", torch.cuda.current_device()))
     match = BatchedMatch((model0, model1), EN_GAME_COUNT, temperature=EN_TEMPERATURE,
-                         seed=int(np.random.randint(0, 2 ** 30)), evaluator="gnn" if fused else "general")
+                         seed=int(np.random.randint(0, 2 ** 30)), evaluator="cnn" if all(cnn) else "gnn" if fused else "general")
     points = match.play()
     print('Evaluating latest model against current best ({} games, concurrent)'.format(EN_GAME_COUNT))
     average_point = sum(points) / EN_GAME_COUNT

@@ -23,7 +23,7 @@ def _engine_for(model, num_games, sims, board_size, evaluator="gnn", fake_bias=0
             _engines.clear()
         eng = _engines[key] = BatchedSelfPlay(model, num_games=num_games, sims=sims, board_size=board_size,
                                               evaluator=evaluator, fake_bias=fake_bias, record_history=False)
-    elif evaluator in ("gnn", "general"):
+    elif evaluator in ("gnn", "general", "cnn"):
         eng.refresh_weights()
     return eng
 
@@ -45,7 +45,8 @@ def _policy_from_visits(visits, temperature):
 def pv_mcts_policy_batch(model, states72, temperature, sims=None, board_size=None, evaluator="gnn", fake_bias=0):
     """states72: uint8 [B,72] -> list of B policies (each aligned with that state's legal_actions()).
     evaluator: 'gnn' (the default 6/128/3 network), 'general' (a GraphPolicyValueNetwork of any shape with 6 input features, on
-    the library's kernels), 'external' (model.predict per leaf) or 'fake'."""
+    the library's kernels), 'cnn' (the reference's CNNNetwork, pv_network_cnn.py, on the library's kernels), 'external'
+    (model.predict per leaf) or 'fake'."""
     states72 = torch.as_tensor(states72, dtype=torch.uint8)
     B = states72.shape[0]
     N = int(states72[0, 70]) if board_size is None else board_size
@@ -56,9 +57,12 @@ def pv_mcts_policy_batch(model, states72, temperature, sims=None, board_size=Non
 
 
 def evaluator_of(model):
-    """'gnn' for the network the HIP kernels evaluate themselves (the default 6/128/3 shape); 'external' for any other
-    object with the reference's predict(state, device) (BaseNetwork.py:36-40) -- e.g. the CNN the reference wires
-    (self_play.py:16,78), or a GraphPolicyValueNetwork of another shape."""
+    """'gnn' for the GNN the HIP kernels evaluate themselves (the default 6/128/3 shape); 'cnn' for the reference's CNNNetwork
+    (pv_network_cnn.py, self_play.py:16,78), which they evaluate too; 'external' for any other object with the reference's
+    predict(state, device) (BaseNetwork.py:36-40), e.g. a GraphPolicyValueNetwork of another shape or a stock CNN module."""
+    from .pv_network_cnn import CNNNetwork
+    if isinstance(model, CNNNetwork):
+        return "cnn"
     return "gnn" if hasattr(model, "packed_weights") and getattr(model, "fused", True) else "external"
 
 

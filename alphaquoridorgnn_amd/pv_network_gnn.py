@@ -826,11 +826,16 @@ def shape_of_state_dict(sd):
 
 def load_network(path, device=None):
     """The network a .pth file holds, whatever its shape: GNNNetwork for the default 6/128/3 (the fused kernels), otherwise a
-    GraphPolicyValueNetwork of the shape the state_dict implies.  Loaded onto `device` (default: the current GPU, else the CPU)
-    in eval mode."""
+    GraphPolicyValueNetwork of the shape the state_dict implies -- or, for the reference's CNN state_dict, a CNNNetwork of its
+    shape (pv_network_cnn.py).  Loaded onto `device` (default: the current GPU, else the CPU) in eval mode."""
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
     sd = torch.load(path, map_location=device, weights_only=True)
+    from . import pv_network_cnn
+    if pv_network_cnn.is_cnn_state_dict(sd):
+        model = pv_network_cnn.CNNNetwork(*pv_network_cnn.shape_of_state_dict(sd))
+        model.load_state_dict(sd)
+        return model.to(device).eval()
     shape = shape_of_state_dict(sd)
     if shape == (NUM_FEATURES, HIDDEN_DIM, NUM_GCN_LAYERS, POLICY_OUTPUT_SIZE):
         model = GNNNetwork()

@@ -17,6 +17,7 @@ from . import pv_mcts
 from .constants import PV_NETWORK_PATH, BOARD_SIZE
 from .engine import BatchedSelfPlay, MultiSetSelfPlay, gather_history
 from .pv_network_gnn import GNNNetwork, POLICY_OUTPUT_SIZE, load_network
+from .pv_network_cnn import CNNNetwork
 
 SP_GAME_COUNT = 50    # Number of games for self-play (self_play.py:19; 25000 in the original version)
 SP_TEMPERATURE = 1.0  # Temperature parameter for Boltzmann distribution (self_play.py:20)
@@ -82,11 +83,11 @@ def self_play(model=None, games=None, seed=None):
     stream; by default every call draws a fresh one, like the reference's unseeded np.random.choice."""
     import torch.distributed as dist
     if model is None:
-        model = load_network(PV_NETWORK_PATH + 'best.pth')       # GNNNetwork (prep_for_inference's path), or the shape best.pth holds
-        if isinstance(model, GNNNetwork) and torch.cuda.is_available():
+        model = load_network(PV_NETWORK_PATH + 'best.pth')       # GNNNetwork (prep_for_inference's path), or the network best.pth holds
+        if isinstance(model, (GNNNetwork, CNNNetwork)) and torch.cuda.is_available():
             model.packed_weights(torch.device("cuda", torch.cuda.current_device()))
-    # the default 6/128/3 network runs the engine's fused evaluator; any other shape its any-shape evaluator
-    evaluator = "gnn" if getattr(model, "fused", True) else "general"
+    # the default 6/128/3 network runs the engine's fused evaluator; any other shape its any-shape evaluator; the CNN its own
+    evaluator = "cnn" if isinstance(model, CNNNetwork) else "gnn" if getattr(model, "fused", True) else "general"
     total = SP_GAME_COUNT if games is None else games
     distributed = dist.is_available() and dist.is_initialized()
     rank, world = (dist.get_rank(), dist.get_world_size()) if distributed else (0, 1)

@@ -245,8 +245,15 @@ class GeneralTrainer(_Trainer):
             self.model.invalidate_packed()
 
 
+CNN_TRAINING_NOT_BUILT = ("training the residual CNN (pv_network_cnn.CNNNetwork) is not built yet: its HIP kernels cover inference "
+                          "only (forward, self-play, matches); train a GNN, or train the CNN with the reference's own loop")
+
+
 def trainer_for(model, max_batch=BATCH_SIZE):
     """GNNTrainer for the default 6/128/3 network (the fused step), GeneralTrainer for every other shape."""
+    from .pv_network_cnn import CNNNetwork
+    if isinstance(model, CNNNetwork):
+        raise NotImplementedError(CNN_TRAINING_NOT_BUILT)
     return GNNTrainer(model, max_batch=max_batch) if getattr(model, "fused", False) else GeneralTrainer(model, max_batch=max_batch)
 
 
@@ -260,6 +267,10 @@ def train_network():
     dealt out over the ranks, one all-reduce of the flat gradient buffer per step, GNNTrainer.step); rank 0 writes latest.pth."""
     import os
     import torch.distributed as dist
+    from .pv_network_cnn import is_cnn_state_dict
+    best = PV_NETWORK_PATH + 'best.pth'
+    if os.path.exists(best) and is_cnn_state_dict(torch.load(best, map_location="cpu", weights_only=True)):
+        raise NotImplementedError(CNN_TRAINING_NOT_BUILT)
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
     if world > 1 and os.environ.get("AQG_TRAIN_DATA_PARALLEL", "0") != "1":
         from . import distributed as aqd

@@ -267,6 +267,40 @@ int aqg_gcn_forward_boards_general(int board_size, const void* states, int state
                                    const uint8_t* active, float* workspace, size_t workspace_floats, float* pooled, float* logits,
                                    float* policy, float* value_pre, float* value, void* stream);
 
+/* ------------------------------------------------------------------ the reference's residual CNN (additive to ABI 14)
+ *
+ * CNNNetwork (pv_network_cnn.py:20-84) in eval mode: a 3x3 conv + BatchNorm2d stem, num_blocks residual blocks of two such convs
+ * (ReLU, skip connection, ReLU), AdaptiveAvgPool2d(1), then Linear -> Softmax (policy) and Linear -> Tanh (value), all f32
+ * (csrc/cnn_forward.hip: one implicit-GEMM launch per conv on the f32-input MFMA, BN folded into a per-channel scale / shift).
+ * aqg_cnn_net: the shape (num_filters 1..AQG_CNN_MAX_FILTERS, num_blocks 0..AQG_CNN_MAX_BLOCKS, policy_size 1..4096, 6 input planes)
+ *   and the DEVICE buffer aqg_cnn_pack filled (aqg_cnn_packed_floats(num_filters, num_blocks, policy_size) floats).
+ * aqg_cnn_pack: folds and reorders the module's parameters on the device.  params_host: HOST array of DEVICE pointers to contiguous
+ *   f32 tensors, per conv (the stem, then residual_blocks.i.conv_bn1, .conv_bn2 for each i) {conv.weight [F,Cin,3,3], bn.weight,
+ *   bn.bias, bn.running_mean, bn.running_var}, then policy_head.1.weight [A,F], .bias, value_head.1.weight [1,F], .bias;
+ *   eps_host[2 num_blocks + 1]: each BatchNorm2d's eps.  Capturable; re-run it after the parameters change.
+ * aqg_cnn_forward_boards: the network on B board records (state_fmt 0 = state72, 1 = the engine's 24-byte records; the featuriser
+ *   of aqg_gcn_boards_graph, i.e. pv_network_cnn.py:88-114); aqg_cnn_forward_planes: the same from [B,6,N,N] f32 planes.
+ *   pooled [B,F], logits [B,A] and value_pre [B] may be NULL (then they live in the workspace); policy [B,A] is required, value [B]
+ *   may be NULL.  active [B] (may be NULL): a board with active[b] != 1 is skipped -- its policy / value rows are not written.
+ *   Every board is computed independently of the others: its outputs are bit-identical at any B, position and mask.  workspace:
+ *   aqg_cnn_workspace_floats(board_size, num_filters, policy_size, B) floats.  No allocation, no host synchronisation. */
+#define AQG_CNN_MAX_FILTERS 512
+#define AQG_CNN_MAX_BLOCKS 40
+typedef struct aqg_cnn_net {
+    int32_t board_size, num_filters, num_blocks, policy_size;
+    const float* packed;
+} aqg_cnn_net;
+size_t aqg_cnn_packed_floats(int num_filters, int num_blocks, int policy_size);
+int aqg_cnn_pack(int num_filters, int num_blocks, int policy_size, const float* const* params_host, const float* eps_host, float* packed,
+                 void* stream);
+size_t aqg_cnn_workspace_floats(int board_size, int num_filters, int policy_size, int B);
+int aqg_cnn_forward_boards(int board_size, const void* states, int state_fmt, int B, const aqg_cnn_net* net, const uint8_t* active,
+                           float* workspace, size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre,
+                           float* value, void* stream);
+int aqg_cnn_forward_planes(int board_size, const float* planes, int B, const aqg_cnn_net* net, const uint8_t* active, float* workspace,
+                           size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre, float* value,
+                           void* stream);
+
 /* ------------------------------------------------------------------ batched PV-MCTS self-play (pv_mcts.py, self_play.py) */
 
 /* All engine memory is owned by the caller (the Python host allocates torch tensors); this struct only
@@ -283,7 +317,8 @@ typedef struct aqg_engine {
                                  1: `fake` integer-hash evaluator (tests; oracle/mcts.py FakeModel)
                                  2: external evaluator -- the caller's own model.predict (BaseNetwork.py:36-40) fills policy / value
                                     between aqg_engine_step calls (see below)
-                                 3: the any-shape network of `general_net` (below), gathered and renormalised like 0 */
+                                 3: the any-shape network of `general_net` (below), gathered and renormalised like 0
+                                 4: the residual CNN of `cnn_net` (below), gathered and renormalised like 0 */
     int32_t fake_bias;
     int32_t gnn_flags;        /* flags of the GNN forward for prior_mode 0 (AQG_GNN_EXACT_F32 or 0) */
     float c_puct;             /* 1.25  pv_mcts.py:71 */
@@ -315,7 +350,7 @@ typedef struct aqg_engine {
     /* boards other than 9x9 with prior_mode 0: workspace of the any-size forward, aqg_gcn_boards_any_workspace_floats(N, G)
      * floats (may be NULL for 9x9 and for prior_mode 1) */
     float* gnn_workspace;
-    /* Evaluation cache (ABI 10; prior_mode 0 or 3 (ABI 14); eval_cache_keys == NULL: off).  The reference builds a new tree for every move
+    /* Evaluation cache (ABI 10; prior_mode 0, 3 (ABI 14) or 4; eval_cache_keys == NULL: off).  The reference builds a new tree for every move
      * (pv_mcts.py:84) and keeps no transposition table, so a game asks model.predict (pv_mcts.py:47) for the same position again and
      * again: transpositions inside a search, and the sub-tree of the move that was played in the next search.  The network's output and
      * legal_actions() are pure functions of (walls, pawns, walls in hand) -- not of the ply counter -- and the fused kernels compute every
@@ -339,6 +374,10 @@ typedef struct aqg_engine {
      * aqg_gcn_boards_general_workspace_floats(board_size, hidden, A, G) floats; policy_size must be A.  Held BY VALUE: the captured
      * per-move graphs are keyed by the bytes of this struct, so every weight pointer and the shape are part of the key. */
     aqg_gcn_general_net general_net;
+    /* prior_mode 4 (additive to ABI 14): the residual CNN -- aqg_cnn_forward_boards over leaf_state per simulation, masked like
+     * prior_mode 3, with gnn_workspace of aqg_cnn_workspace_floats(board_size, num_filters, A, G) floats; policy_size must be A.
+     * Held by value like general_net: the captured per-move graphs are keyed by the packed buffer's address and the shape. */
+    aqg_cnn_net cnn_net;
 } aqg_engine;
 
 /* Reset all G slots to the initial position (State() game_logic.py:25-40) and mark them active; clears the evaluation cache. */
