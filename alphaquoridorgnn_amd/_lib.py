@@ -86,6 +86,23 @@ class TrainGeneralStruct(_c.Structure):
     )
 
 
+CNN_TRAIN_CONVS = 2 * 40 + 1            # AQG_CNN_TRAIN_CONVS: convs of the largest CNN (AQG_CNN_MAX_BLOCKS = 40)
+CNN_TRAIN_TENSORS = 3 * CNN_TRAIN_CONVS + 4
+
+
+class CnnTrainStruct(_c.Structure):
+    """Mirror of `struct aqg_cnn_train` (include/aqgnn.h): the residual CNN's training step."""
+    _fields_ = (
+        [(n, _i32) for n in ("board_size", "num_filters", "num_blocks", "policy_size", "batch", "step")]
+        + [(n, _f32) for n in ("lr", "beta1", "beta2", "eps")]
+        + [(n, _f32 * CNN_TRAIN_CONVS) for n in ("bn_eps", "bn_momentum")]
+        + [(n, _vp * CNN_TRAIN_TENSORS) for n in ("params", "grads")]
+        + [(n, _vp * CNN_TRAIN_CONVS) for n in ("running_mean", "running_var")]
+        + [(n, _vp) for n in ("adam_table", "policy", "value", "loss", "loss_mean", "workspace")]
+        + [("workspace_floats", _c.c_size_t)]
+    )
+
+
 SIGNATURES = {
     "aqg_abi_version": (_c.c_int, []),
     "aqg_last_error": (_c.c_char_p, []),
@@ -143,6 +160,9 @@ SIGNATURES = {
     "aqg_gcn_train_general_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "aqg_gcn_train_step_general": (_c.c_int, [_c.POINTER(TrainGeneralStruct), _vp, _vp, _vp, _c.c_int, _vp]),
     "aqg_gcn_train_steps_general": (_c.c_int, [_c.POINTER(TrainGeneralStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _vp]),
+    "aqg_cnn_train_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "aqg_cnn_train_step": (_c.c_int, [_c.POINTER(CnnTrainStruct), _vp, _vp, _vp, _c.c_int, _vp]),
+    "aqg_cnn_train_steps": (_c.c_int, [_c.POINTER(CnnTrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _vp]),
     "aqg_host_legal_actions": (_c.c_int, [_c.c_int, _vp, _vp]),
     "aqg_host_next": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp]),
     "aqg_host_shortest_path": (_c.c_int, [_c.c_int, _vp]),

@@ -94,6 +94,11 @@ size_t train_general_workspace_floats(int N, int hidden, int num_layers, int pol
 int train_step_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st);
 int train_steps_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
                         long long positions, float* loss_sums, hipStream_t st);
+size_t cnn_train_workspace_floats(int N, int F, int L, int A, int max_batch);
+int check_cnn_train(const aqg_cnn_train& t, bool adam, const char* what);
+int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st);
+int cnn_train_steps(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
+                    long long positions, float* loss_sums, hipStream_t st);
 }  // namespace aqg
 
 using namespace aqg;
@@ -411,6 +416,26 @@ int aqg_gcn_train_steps_general(const aqg_train_general* t, const uint8_t* state
     if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
     if (int r = check_train_general(t, true, what)) return r;
     return train_steps_general(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream);
+}
+
+size_t aqg_cnn_train_workspace_floats(int board_size, int num_filters, int num_blocks, int policy_size, int max_batch) {
+    return cnn_train_workspace_floats(board_size, num_filters, num_blocks, policy_size, max_batch);
+}
+int aqg_cnn_train_step(const aqg_cnn_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                       void* stream) {
+    const char* what = "aqg_cnn_train_step";
+    if (!t || mode < 0 || mode > 2) return fail(what, "bad argument");
+    if (t->batch < 0) return fail(what, "negative batch");
+    if (mode != 2 && t->batch > 0 && (!states72 || !pi_target || !z_target)) return fail(what, "null argument");
+    if (int r = check_cnn_train(*t, mode >= 1, what)) return r;
+    return cnn_train_step(*t, states72, pi_target, z_target, mode, (hipStream_t)stream);
+}
+int aqg_cnn_train_steps(const aqg_cnn_train* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                        const int64_t* order, long long positions, float* loss_sums, void* stream) {
+    const char* what = "aqg_cnn_train_steps";
+    if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
+    if (int r = check_cnn_train(*t, true, what)) return r;
+    return cnn_train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -381,6 +381,13 @@ int validate(const aqg_train_general& t, const char* what) {
 
 }  // namespace
 
+// the loss kernel for the residual CNN's step (cnn_train.hip): the same two loss terms and their gradients
+int launch_train_general_loss(int B, int A, const float* policy, const float* value, const float* pi, const float* z,
+                              const int64_t* order, int first, float* loss, float* dpol, float* dval, hipStream_t st) {
+    hipLaunchKernelGGL(train_general_loss_kernel, dim3(B), dim3(256), 0, st, B, A, policy, value, pi, z, order, first, loss, dpol, dval);
+    return check_launch("train_general_loss_kernel");
+}
+
 size_t train_general_workspace_floats(int N, int hidden, int num_layers, int policy_size, int max_batch) {
     if (!(N == 3 || N == 5 || N == 7 || N == 9) || hidden < 2 || hidden > 1024 || num_layers < 1 || num_layers > AQG_GENERAL_MAX_LAYERS ||
         policy_size < 1 || policy_size > 4096 || max_batch < 1)

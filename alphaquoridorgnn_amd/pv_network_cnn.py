@@ -10,7 +10,7 @@ records; `packed_weights(device)` / `cnn_net(device)`, the descriptor of the eng
 
 `forward(x)` on a [B,6,N,N] GPU tensor, in eval mode, with autograd not recording, runs csrc/cnn_forward.hip (eval-mode BatchNorm
 folded at pack time, one implicit-GEMM launch per conv on the f32-input MFMA).  Otherwise -- training-mode BatchNorm, a CPU
-tensor, a recording autograd -- it runs the stock nn modules: the reference's own arithmetic.  Training on HIP is not built yet.
+tensor, a recording autograd -- it runs the stock nn modules: the reference's own arithmetic.  Training on HIP: train_network.CNNTrainer.
 """
 import ctypes
 import os

@@ -2,6 +2,8 @@
 
     create_network()  ->  repeat NUM_TRAIN_CYCLE times:  self_play()  ->  train_network()  ->  evaluate_network()
 
+with the GNN or (--network cnn) the reference's residual CNN: the parameter update dispatches on what best.pth holds.
+
 (The reference's commented-out evaluate_best_player stage -- CPU baseline agents, SURVEY 8f.4 -- is not part of this build.)
 """
 from . import constants
@@ -13,6 +15,20 @@ from .train_network import train_network
 
 NUM_TRAIN_CYCLE = 1000   # train_cycle.py:18
 
+
+def parameter_update():
+    """What the parameter-update stage (train_network in _STAGES) runs: train_network.train_cnn_network() when best.pth holds the
+    residual CNN, train_network.train_network() otherwise (both looked up on the module at call time)."""
+    import os
+    import torch
+    from . import train_network as tn
+    from .pv_network_cnn import is_cnn_state_dict
+    best = constants.PV_NETWORK_PATH + 'best.pth'
+    if os.path.exists(best) and is_cnn_state_dict(torch.load(best, map_location="cpu", weights_only=True)):
+        return tn.train_cnn_network()
+    return tn.train_network()
+
+
 _STAGES = (("self-play", self_play), ("parameter update", train_network), ("evaluation of the new parameters", evaluate_network))
 
 
@@ -22,12 +38,30 @@ def _dist():
     return dist, on, (dist.get_rank() if on else 0)
 
 
-def _create_network_once(hidden_dim=None, num_gcn_layers=None):
+def _create_cnn_network(num_filters=None, num_residual_blocks=None):
+    """A CNNNetwork of the given shape (default 128 x 16, pv_network_cnn.py:14-15) written as best.pth at PV_NETWORK_PATH -- where
+    self-play, training and evaluation look -- unless a best.pth exists."""
+    import os
+    import torch
+    from . import pv_network_cnn as pc
+    path = constants.PV_NETWORK_PATH + 'best.pth'
+    if os.path.exists(path):
+        return
+    model = pc.CNNNetwork(pc.NUM_FILTERS if num_filters is None else num_filters,
+                          pc.NUM_RESIDUAL_BLOCKS if num_residual_blocks is None else num_residual_blocks, constants.BOARD_SIZE)
+    os.makedirs(constants.PV_NETWORK_PATH, exist_ok=True)
+    torch.save(model.state_dict(), path)
+
+
+def _create_network_once(hidden_dim=None, num_gcn_layers=None, network="gnn", num_filters=None, num_residual_blocks=None):
     """create_network() draws random weights: under torch.distributed only rank 0 may write best.pth (every rank would
     otherwise save a different random init to the same path); the others wait for the file."""
     dist, on, rank = _dist()
     if rank == 0:
-        create_network(hidden_dim=hidden_dim, num_gcn_layers=num_gcn_layers)
+        if network == "cnn":
+            _create_cnn_network(num_filters, num_residual_blocks)
+        else:
+            create_network(hidden_dim=hidden_dim, num_gcn_layers=num_gcn_layers)
     if on:
         dist.barrier()
 
@@ -52,12 +86,15 @@ def _evaluate_once():
     return promoted
 
 
-def train_cycle(num_cycles=None, hidden_dim=None, num_gcn_layers=None):
-    """Run the cycle; returns, per iteration, whether `latest` was promoted to `best`.  hidden_dim / num_gcn_layers shape the
-    best.pth written when none exists (create_network); every stage then follows the shape best.pth holds."""
+def train_cycle(num_cycles=None, hidden_dim=None, num_gcn_layers=None, network="gnn", num_filters=None, num_residual_blocks=None):
+    """Run the cycle; returns, per iteration, whether `latest` was promoted to `best`.  network 'gnn' (hidden_dim / num_gcn_layers)
+    or 'cnn' (num_filters / num_residual_blocks) shapes the best.pth written when none exists; every stage then follows the
+    network and shape best.pth holds."""
+    if network not in ("gnn", "cnn"):
+        raise ValueError("network must be 'gnn' or 'cnn'")
     total = NUM_TRAIN_CYCLE if num_cycles is None else int(num_cycles)
     print(f'{constants.PV_NETWORK_NAME} network, {constants.BOARD_SIZE}x{constants.BOARD_SIZE} board, {total} training cycle(s)')
-    _create_network_once(hidden_dim, num_gcn_layers)
+    _create_network_once(hidden_dim, num_gcn_layers, network, num_filters, num_residual_blocks)
     promoted = []
     rank = _dist()[2]
     for cycle in range(1, total + 1):
@@ -65,7 +102,12 @@ def train_cycle(num_cycles=None, hidden_dim=None, num_gcn_layers=None):
         for title, stage in _STAGES:
             if rank == 0:
                 print(f'\n[cycle {cycle}/{total}] {title}')
-            outcome = _evaluate_once() if stage is evaluate_network else stage()
+            if stage is evaluate_network:
+                outcome = _evaluate_once()
+            elif stage is train_network:
+                outcome = parameter_update()           # the GNN's stage, or the CNN's when best.pth holds one
+            else:
+                outcome = stage()
         promoted.append(bool(outcome))
     return promoted
 
@@ -90,6 +132,12 @@ def main(argv=None):
                     help="hidden width of the network created when no best.pth exists (default HIDDEN_DIM = 128)")
     ap.add_argument("--num-gcn-layers", type=int, default=None,
                     help="GCN layers of the network created when no best.pth exists (default NUM_GCN_LAYERS = 3)")
+    ap.add_argument("--network", choices=("gnn", "cnn"), default="gnn",
+                    help="network created when no best.pth exists: the GNN (default) or the reference's residual CNN")
+    ap.add_argument("--num-filters", type=int, default=None,
+                    help="filters of the CNN created when no best.pth exists (default NUM_FILTERS = 128)")
+    ap.add_argument("--num-residual-blocks", type=int, default=None,
+                    help="residual blocks of the CNN created when no best.pth exists (default NUM_RESIDUAL_BLOCKS = 16)")
     args = ap.parse_args(argv)
     rank, world = aqd.init_from_env()
     if args.games is not None:
@@ -101,7 +149,8 @@ def main(argv=None):
     if args.eval_games is not None:
         en.EN_GAME_COUNT = args.eval_games
     try:
-        promoted = train_cycle(args.cycles, hidden_dim=args.hidden_dim, num_gcn_layers=args.num_gcn_layers)
+        promoted = train_cycle(args.cycles, hidden_dim=args.hidden_dim, num_gcn_layers=args.num_gcn_layers, network=args.network,
+                               num_filters=args.num_filters, num_residual_blocks=args.num_residual_blocks)
         if args.result_dir:
             import hashlib
             with open(constants.PV_NETWORK_PATH + 'latest.pth', 'rb') as f:

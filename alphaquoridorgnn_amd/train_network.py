@@ -245,8 +245,113 @@ class GeneralTrainer(_Trainer):
             self.model.invalidate_packed()
 
 
-CNN_TRAINING_NOT_BUILT = ("training the residual CNN (pv_network_cnn.CNNNetwork) is not built yet: its HIP kernels cover inference "
-                          "only (forward, self-play, matches); train a GNN, or train the CNN with the reference's own loop")
+CNN_TRAINING_NOT_BUILT = ("training the residual CNN through train_network() / trainer_for(), the GNN entry points, is not built "
+                          "yet: use CNNTrainer / train_cnn_network(), or train_cycle, which dispatches")
+
+
+class CNNTrainer(_Trainer):
+    """Adam state + workspace for optimisation steps of up to `max_batch` positions on a CNNNetwork (pv_network_cnn.py) on the GPU --
+    aqg_cnn_train_step (csrc/cnn_train.hip): the reference's step (train_network.py:26-107) with every BatchNorm2d in train mode.
+    The surface is GeneralTrainer's.  A step always normalises with the batch statistics, whatever model.training is (the mode is
+    left as it was), and updates every running_mean / running_var in place and num_batches_tracked by one, as the module's own
+    train-mode forward does; parameters are updated in place.  Version counters are advanced, so packed_weights() and a 'cnn'
+    engine's refresh_weights() pick up the new weights.  BatchNorm statistics over a sharded batch would need synchronised
+    BatchNorm: a step under a process group of more than one rank raises ValueError."""
+
+    def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8):
+        from .pv_network_cnn import CNNNetwork
+        if not isinstance(model, CNNNetwork):
+            raise ValueError("CNNTrainer trains a pv_network_cnn.CNNNetwork")
+        self.model = model
+        self.lib = _lib.load()
+        self.params = list(model.parameters())
+        for p in self.params:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError("training needs contiguous float32 parameters")
+        self.bns = [cb.bn for cb in model._convs()]
+        for bn in self.bns:
+            if bn.momentum is None:
+                raise ValueError("BatchNorm2d(momentum=None) (a cumulative moving average) is not supported")
+            if not bn.track_running_stats or bn.running_mean is None:
+                raise ValueError("BatchNorm2d(track_running_stats=False) is not supported")
+        if self.params[0].device.type != "cuda":
+            raise ValueError("CNNTrainer trains a model on the GPU: move it there first (model.to('cuda'))")
+        self.dev = _lib.require_gpu(self.params[0].device)
+        self.buffers = [b for bn in self.bns for b in (bn.running_mean, bn.running_var)]
+        for x in self.params + self.buffers:
+            if x.device != self.dev:
+                raise ValueError("every parameter and running statistic must be on the trainer's GPU")
+            if x.dtype != torch.float32 or not x.is_contiguous():
+                raise ValueError("training needs contiguous float32 parameters and running statistics")
+        self._optimiser_state()
+        self.N = model.board_size
+        self.A = model.policy_output_size
+        self.max_batch = int(max_batch)
+        if self.max_batch < 1:
+            raise ValueError("max_batch must be >= 1")
+        self.step_count = 0
+        self.betas, self.eps = betas, eps
+        B, A = self.max_batch, self.A
+        f = dict(dtype=torch.float32, device=self.dev)
+        F_, L = model.num_filters, model.num_residual_blocks
+        nws = int(self.lib.aqg_cnn_train_workspace_floats(self.N, F_, L, A, B))
+        if nws == 0:
+            _lib.check(-1, "aqg_cnn_train_workspace_floats (shape or board size outside the kernels' limits)")
+        self.ws = dict(workspace=torch.empty((nws,), **f), pol=torch.empty((B, A), **f), val=torch.empty((B,), **f),
+                       loss=torch.empty((B, 2), **f), loss_mean=torch.zeros((2,), **f))
+        # the Adam launch's tensor table, on the device: params | grads | adam_m | adam_v
+        self.table = torch.tensor([x.data_ptr() for x in self.params + self.grads + self.adam_m + self.adam_v], dtype=torch.int64,
+                                  device=self.dev)
+        t = self.t = _lib.CnnTrainStruct()
+        t.board_size, t.num_filters, t.num_blocks, t.policy_size = self.N, F_, L, A
+        t.beta1, t.beta2, t.eps = float(betas[0]), float(betas[1]), float(eps)
+        for i, bn in enumerate(self.bns):
+            t.bn_eps[i], t.bn_momentum[i] = float(bn.eps), float(bn.momentum)
+            t.running_mean[i], t.running_var[i] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+        for i, (p, g) in enumerate(zip(self.params, self.grads)):
+            t.params[i], t.grads[i] = p.data_ptr(), g.data_ptr()
+        t.adam_table = self.table.data_ptr()
+        t.policy, t.value, t.loss, t.loss_mean = (self.ws[k].data_ptr() for k in ("pol", "val", "loss", "loss_mean"))
+        t.workspace, t.workspace_floats = self.ws["workspace"].data_ptr(), nws
+
+    def step(self, states72, pi_target, z_target, lr=LEARNING_RATE, update=True, group=None):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            raise ValueError("CNNTrainer.step: data-parallel CNN training would need synchronised BatchNorm, which is not built; "
+                             "train on one rank")
+        out = super().step(states72, pi_target, z_target, lr=lr, update=update, group=group)
+        if int(states72.shape[0]) > 0:
+            self._forwarded(1)
+        return out
+
+    def run_epoch(self, states72, pi_target, z_target, order, lr=LEARNING_RATE, batch=None, pre_shuffle=True):
+        sums = super().run_epoch(states72, pi_target, z_target, order, lr=lr, batch=batch, pre_shuffle=pre_shuffle)
+        batch = self.max_batch if batch is None else int(batch)
+        self._forwarded((int(order.shape[0]) + batch - 1) // batch)
+        return sums
+
+    def _call(self, states72, pi_target, z_target, mode):
+        _lib.check(self.lib.aqg_cnn_train_step(ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target),
+                                               mode, _lib.stream_ptr(self.dev)), "aqg_cnn_train_step")
+
+    def _call_epoch(self, states72, pi_target, z_target, order, n, sums):
+        _lib.check(self.lib.aqg_cnn_train_steps(ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target),
+                                                _lib.ptr(order), n, _lib.ptr(sums), _lib.stream_ptr(self.dev)), "aqg_cnn_train_steps")
+
+    def _batch_losses(self, B):
+        return self.ws["loss_mean"].clone()          # summed in position order by the library
+
+    def _updated(self):
+        # the kernels wrote the parameters behind torch's back: advance their version counters (CNNNetwork.weights_key())
+        torch.autograd.graph.increment_version(self.params)
+        self.model.invalidate_packed()
+
+    def _forwarded(self, steps):
+        # every train-mode forward updated the running statistics in place and counts in num_batches_tracked
+        torch.autograd.graph.increment_version(self.buffers)
+        for bn in self.bns:
+            bn.num_batches_tracked.add_(steps)
+        self.model.invalidate_packed()
 
 
 def trainer_for(model, max_batch=BATCH_SIZE):
@@ -329,6 +434,46 @@ def _train_loop(rank, world):
         torch.save(model.state_dict(), PV_NETWORK_PATH + 'latest.pth')
     if world > 1:
         dist.barrier()          # latest.pth is complete before any rank moves on to the evaluation stage
+
+
+def train_cnn_network():
+    """train_network.py:26-107 on the reference's residual CNN: best.pth (a CNNNetwork of any shape) -> NUM_EPOCH epochs over the
+    newest .history, every step on HIP (CNNTrainer) -> latest.pth with every state_dict key (202 at 128 filters x 16 blocks).
+    Under torch.distributed rank 0 trains alone and the others wait (synchronised BatchNorm is not built)."""
+    import torch.distributed as dist
+    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
+    if world > 1:
+        from . import distributed as aqd
+        tag = aqd.next_tag("train")
+        if rank == 0:
+            with aqd.single_rank_stage(tag):
+                _train_cnn_loop()
+        else:
+            aqd.wait_for_rank0(tag)
+        dist.barrier()          # latest.pth is complete before any rank moves on to the evaluation stage
+        return
+    _train_cnn_loop()
+
+
+def _train_cnn_loop():
+    from . import distributed as aqd
+    from .pv_network_cnn import load_network as load_cnn
+    dev = aqd.device()
+    model = load_cnn(PV_NETWORK_PATH + 'best.pth', dev)
+    history = load_data()
+    s, p, v = zip(*history)
+    s = torch.from_numpy(pack_states(s, model.board_size)).to(dev)                # uint8 [n,72]
+    p = torch.tensor(np.array(p), dtype=torch.float32, device=dev)
+    v = torch.tensor(np.array(v), dtype=torch.float32, device=dev)
+    n = s.shape[0]
+    trainer = CNNTrainer(model, max_batch=BATCH_SIZE)
+    for epoch in range(NUM_EPOCH):
+        lr = LEARNING_RATE * lr_lambda(epoch)                                      # LambdaLR, stepped once per epoch (:98)
+        perm = torch.randperm(n, device=dev)                                    # DataLoader(shuffle=True), last batch kept
+        epoch_policy_loss, epoch_value_loss = trainer.run_epoch(s, p, v, perm, lr=lr)
+        print(f"\rEpoch {epoch + 1}/{NUM_EPOCH} | Policy Loss: {float(epoch_policy_loss):.4f} | Value Loss: {float(epoch_value_loss):.4f}", end='')
+    print('')
+    torch.save(model.state_dict(), PV_NETWORK_PATH + 'latest.pth')
 
 
 if __name__ == '__main__':

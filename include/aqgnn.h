@@ -492,6 +492,51 @@ int aqg_gcn_train_step_general(const aqg_train_general* t_host, const uint8_t* s
 int aqg_gcn_train_steps_general(const aqg_train_general* t_host, const uint8_t* states72, const float* pi_target,
                                 const float* z_target, const int64_t* order, long long positions, float* loss_sums, void* stream);
 
+/* ------------------------------------------------------------------ training the residual CNN (additive to ABI 14)
+ *
+ * One optimisation step of CNNNetwork (pv_network_cnn.py:20-84) as the reference's train_network.py:26-107 takes it: the module in
+ * train mode (every BatchNorm2d normalises with the batch mean and the biased batch variance over B x N x N per channel, and updates
+ * running_mean / running_var in place with its momentum and the unbiased variance), CrossEntropyLoss on the already-softmaxed policy
+ * + MSELoss on the value, backward, torch.optim.Adam -- on board records (state72, board_size 3/5/7/9), all f32
+ * (csrc/cnn_train.hip).  Each 3x3 conv is an im2col GEMM on the f32-input MFMA, forward, dX and dW alike; every channel statistic
+ * is a per-board partial merged in board order.  No atomics (two runs give bit-identical parameters and running statistics), no
+ * allocation, no host synchronisation.  num_batches_tracked is the caller's to advance.
+ *
+ * Tensor order (T = 3 C + 4 tensors, C = 2 num_blocks + 1 convs: the stem, then conv_bn1 / conv_bn2 of each block): per conv its
+ *   conv.weight [F,Cin,3,3], bn.weight [F], bn.bias [F]; then policy_head.1.weight [A,F], .bias [A], value_head.1.weight [1,F],
+ *   .bias [1] -- the order of CNNNetwork.parameters().
+ * aqg_cnn_train: the shape; batch = positions of this step; step = the Adam count of THIS update (>= 1); lr / beta1 / beta2 / eps as
+ *   torch.optim.Adam; bn_eps / bn_momentum [C] = each BatchNorm2d's eps and momentum.  params / grads [T] = device pointers to
+ *   contiguous f32 tensors (updated in place; grads of the same shapes); running_mean / running_var [C] = each BatchNorm2d's
+ *   buffers (updated in place by every forward, modes 0 and 1).  adam_table: DEVICE array of 4 T pointers -- params, grads, adam_m,
+ *   adam_v, each in tensor order (the same params / grads as above) -- built once by the caller: the single Adam launch reads it
+ *   (247 tensors at 40 blocks would not fit in kernel arguments).  policy / value / loss / loss_mean as in struct aqg_train_general: each
+ *   may be NULL.  workspace: aqg_cnn_train_workspace_floats(board_size, num_filters, num_blocks, policy_size, max_batch) floats.
+ * aqg_cnn_train_step: mode 0 = gradients only, 1 = gradients + Adam, 2 = Adam only, as aqg_gcn_train_step_general; batch 0 = no-op.
+ * aqg_cnn_train_steps: one epoch, every step mode 1, with the order / loss_sums contract of aqg_gcn_train_steps_general. */
+#define AQG_CNN_TRAIN_CONVS (2 * AQG_CNN_MAX_BLOCKS + 1)
+#define AQG_CNN_TRAIN_TENSORS (3 * AQG_CNN_TRAIN_CONVS + 4)
+typedef struct aqg_cnn_train {
+    int32_t board_size, num_filters, num_blocks, policy_size;
+    int32_t batch, step;
+    float lr, beta1, beta2, eps;
+    float bn_eps[AQG_CNN_TRAIN_CONVS];
+    float bn_momentum[AQG_CNN_TRAIN_CONVS];
+    float* params[AQG_CNN_TRAIN_TENSORS];
+    float* grads[AQG_CNN_TRAIN_TENSORS];
+    float* running_mean[AQG_CNN_TRAIN_CONVS];
+    float* running_var[AQG_CNN_TRAIN_CONVS];
+    float* const* adam_table;
+    float* policy; float* value; float* loss; float* loss_mean;
+    float* workspace;
+    size_t workspace_floats;
+} aqg_cnn_train;
+size_t aqg_cnn_train_workspace_floats(int board_size, int num_filters, int num_blocks, int policy_size, int max_batch);
+int aqg_cnn_train_step(const aqg_cnn_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                       void* stream);
+int aqg_cnn_train_steps(const aqg_cnn_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target,
+                        const int64_t* order, long long positions, float* loss_sums, void* stream);
+
 /* ------------------------------------------------------------------ CPU baseline agents (agents.py) -- HOST pointers, host code */
 
 /* The reference's baseline opponents (agents.py:14-214) are CPU code; so are these: the host instantiation of the rule header
