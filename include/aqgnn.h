@@ -197,6 +197,7 @@ int aqg_gcn_backward_graph(int num_features, int num_actions, const float* x, in
  * contiguous (row-major); sizes are runtime values.  Every contraction runs on the f32-input MFMA (a k-ordered fmaf chain) and
  * no kernel uses atomics: each sum runs in an order fixed by the sizes, so results are deterministic.  A call with no rows
  * (M, num_nodes or num_graphs 0) launches nothing (aqg_graph_linear_grad writes zero gradients).
+ * tests/test_graph_primitives.py checks this contract, one primitive at a time (the fmaf chain bit for bit against std::fmaf).
  *
  * aqg_graph_linear: Y[M,N] = X[M,K] W^T (+ bias[N]) -- nn.Linear / GCNConv.lin; W [N,K] in PyTorch's [out, in] layout straight
  *   from the parameter (flags & AQG_LIN_W_KN: W is [K,N] and Y = X W, the backward's dX = dY W).  bias may be NULL.  Then, in
