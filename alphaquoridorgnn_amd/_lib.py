@@ -14,7 +14,7 @@ MAX_LEGAL = 136
 GNN_EXACT_F32 = 1        # AQG_GNN_EXACT_F32 (include/aqgnn.h)
 GNN_RANGE_PROVEN = 2     # AQG_GNN_RANGE_PROVEN
 GNN_PROVEN_MAX_WALLS = 16
-ABI_VERSION = 14
+ABI_VERSION = 15
 TRAIN_PART_FLOATS = 2 * 128 * 128 + 128 * 6 + 3 * 128    # AQG_TRAIN_PART_FLOATS, per position of the batch
 LIN_RELU, LIN_W_KN, LIN_ACCUMULATE = 1, 2, 4             # AQG_LIN_* flags of aqg_graph_linear
 
@@ -119,13 +119,6 @@ SIGNATURES = {
     "aqg_gcn_forward_boards_guarded": (_c.c_int, [_c.c_int, _vp, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp]),
     "aqg_gcn_boards_any_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int]),
     "aqg_gcn_forward_boards_any": (_c.c_int, [_c.c_int, _vp, _c.c_int, _c.c_int, _vp, _vp, _c.c_size_t, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp]),
-    "aqg_gcn_forward_graph": (_c.c_int, [_c.c_int, _c.c_int, _vp, _c.c_int, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp,
-                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "aqg_gcn_forward_graph_saved": (_c.c_int, [_c.c_int, _c.c_int, _vp, _c.c_int, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp,
-                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "aqg_gcn_backward_graph_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int]),
-    "aqg_gcn_backward_graph": (_c.c_int, [_c.c_int, _c.c_int, _vp, _c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int,
-                                          _vp, _vp, _vp, _vp, _vp, _c.POINTER(_vp), _vp, _c.c_size_t, _c.POINTER(_vp), _vp, _vp]),
     "aqg_graph_linear": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp]),
     "aqg_graph_linear_grad_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
     "aqg_graph_linear_grad": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _c.c_size_t, _vp, _vp, _vp]),

@@ -1,104 +1,10 @@
 // capi.hip -- extern "C" entry points of libaqgnn_hip.so (declared in include/aqgnn.h).
 #include "aqg_common.hpp"
 #include "../../include/aqgnn.h"
+#include "launchers.hpp"
 
 namespace aqg {
 thread_local char g_err[512] = "";
-extern int g_trunk_variant;
-extern int g_profile_trunk;
-extern int g_trunk_prio;
-extern int g_heads_prio;
-extern int g_train_fused;
-extern int g_trunk_grid;
-extern int g_trunk_phase_delay;
-extern int g_trunk_delay_min_boards;
-extern int g_use_graph;
-extern int g_step_variant;
-extern int g_step_waves;
-extern int g_step_prio;
-extern int g_step_fast_depth;
-int profile_collect(double* total_ms, long long* launches, long long* boards, int reset);
-int launch_poison_lds(hipStream_t st);
-int set_trace_gcn(void* buf, unsigned int cap);
-int set_trace_mcts(void* buf, unsigned int cap);
-
-size_t packed_floats();
-int pack_weights_host(int N, const float* const* t, float* out);
-int launch_legal_actions(int N, const void* states, int fmt, int B, uint8_t* mask, uint8_t* order, int32_t* count,
-                         const uint8_t* active, hipStream_t st);
-int launch_state_next(int N, const uint8_t* in, const int32_t* actions, int B, uint8_t* out, hipStream_t st);
-int launch_state_status(int N, const uint8_t* in, int B, int draw, uint8_t* flags, hipStream_t st);
-int launch_gcn_forward_boards(int N, const void* states, int fmt, int B, const float* packed, float* pooled,
-                              float* logits, float* policy, float* value_pre, float* value, const uint8_t* active,
-                              int flags, int32_t* saturated, hipStream_t st, const int32_t* list = nullptr, const int32_t* list_count = nullptr);
-size_t boards_any_workspace_floats(int N, int B);
-int launch_gcn_forward_boards_any(int N, const void* states, int fmt, int B, const float* packed, float* workspace,
-                                  size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre,
-                                  float* value, const uint8_t* active, int flags, int32_t* saturated, hipStream_t st, const int32_t* list = nullptr, const int32_t* list_count = nullptr);
-int launch_gcn_forward_graph(int F, int A, const float* x, int num_nodes, const int32_t* csr_ptr, const int32_t* csr_src,
-                             const float* csr_w, const int32_t* graph_ptr, int num_graphs, const float* packed,
-                             float* work0, float* work1, float* pooled, float* logits, float* policy, float* value_pre,
-                             float* value, hipStream_t st);
-int launch_gcn_forward_graph_saved(int F, int A, const float* x, int num_nodes, const int32_t* csr_ptr, const int32_t* csr_src,
-                                   const float* csr_w, const int32_t* graph_ptr, int num_graphs, const float* packed,
-                                   float* work0, float* h1, float* h2, float* h3, float* pooled, float* logits, float* policy,
-                                   float* value_pre, float* value, hipStream_t st);
-size_t graph_backward_workspace_floats(int n, int G);
-int launch_gcn_backward_graph(int F, int A, const float* x, int n, const float* h1, const float* h2, const float* h3,
-                              const int32_t* tptr, const int32_t* tdst, const float* tw, const int32_t* gptr, int G,
-                              const float* pooled, const float* policy, const float* value, const float* dpolicy,
-                              const float* dvalue, const float* const* params, float* workspace, size_t workspace_floats,
-                              float* const* grads, float* dx, hipStream_t st);
-int launch_gen_linear(int M, int K, int N, const float* X, const float* W, const float* bias, const float* mask, int flags,
-                      float* Y, hipStream_t st);
-size_t gen_linear_grad_workspace_floats(int M, int N, int K);
-int launch_gen_linear_grad(int M, int K, int N, const float* dY, const float* X, const float* dYb, float* workspace,
-                           size_t workspace_floats, float* dW, float* db, hipStream_t st);
-int launch_gen_aggregate(int n, int N, const float* Y, const int32_t* ptr, const int32_t* src, const float* w, const float* bias,
-                         int relu, float* out, hipStream_t st);
-int launch_gen_mean_pool(int N, const float* H, const int32_t* gptr, int G, float* pooled, hipStream_t st);
-int launch_gen_mean_pool_backward(int n, int N, const float* dpooled, const int32_t* gptr, int G, const float* mask, float* dH,
-                                  hipStream_t st);
-int launch_gen_heads(int G, int A, const float* logits, const float* vpre, float* policy, float* value, hipStream_t st,
-                     const uint8_t* active = nullptr);
-int launch_gen_heads_backward(int G, int A, const float* policy, const float* dpolicy, const float* value, const float* dvalue,
-                              float* dlogits, float* dvpre, hipStream_t st);
-int launch_gcn_boards_graph(int N, const void* states, int fmt, int B, float* x0, int32_t* ell_idx, float* ell_w, hipStream_t st);
-size_t boards_general_workspace_floats(int N, int hidden, int A, int B);
-int launch_gcn_forward_boards_general(int N, const void* states, int fmt, int B, const aqg_gcn_general_net* net,
-                                      const uint8_t* active, float* workspace, size_t workspace_floats, float* pooled, float* logits,
-                                      float* policy, float* value_pre, float* value, hipStream_t st);
-size_t cnn_packed_floats(int F, int L, int A);
-int launch_cnn_pack(int F, int L, int A, const float* const* params, const float* eps, float* packed, hipStream_t st);
-size_t cnn_workspace_floats(int N, int F, int A, int B);
-int launch_cnn_forward_boards(int N, const void* states, int fmt, int B, const aqg_cnn_net* net, const uint8_t* active, float* workspace,
-                              size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre, float* value,
-                              hipStream_t st);
-int launch_cnn_forward_planes(int N, const float* planes, int B, const aqg_cnn_net* net, const uint8_t* active, float* workspace,
-                              size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre, float* value,
-                              hipStream_t st);
-int engine_reset(const aqg_engine& e, hipStream_t st);
-int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st);
-int engine_begin_move(const aqg_engine& e, hipStream_t st);
-int engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t st);
-int engine_finish_move(const aqg_engine& e, const double* uniforms, hipStream_t st);
-int engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
-int engine_move(const aqg_engine& e, const double* uniforms, hipStream_t st);
-int engine_search(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
-int engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st);
-int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st);
-long long train_fallbacks(int reset);
-int train_steps(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, long long positions,
-                float* loss_sums, hipStream_t st);
-size_t train_general_workspace_floats(int N, int hidden, int num_layers, int policy_size, int max_batch);
-int train_step_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st);
-int train_steps_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
-                        long long positions, float* loss_sums, hipStream_t st);
-size_t cnn_train_workspace_floats(int N, int F, int L, int A, int max_batch);
-int check_cnn_train(const aqg_cnn_train& t, bool adam, const char* what);
-int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st);
-int cnn_train_steps(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
-                    long long positions, float* loss_sums, hipStream_t st);
 }  // namespace aqg
 
 using namespace aqg;
@@ -186,52 +92,6 @@ int aqg_gcn_forward_boards_any(int board_size, const void* states, int state_fmt
     if (state_fmt != 0 && state_fmt != 1) return fail("aqg_gcn_forward_boards_any: state_fmt must be 0 or 1");
     return launch_gcn_forward_boards_any(board_size, states, state_fmt, B, packed, workspace, workspace_floats, pooled, logits, policy,
                                          value_pre, value, nullptr, flags, nullptr, (hipStream_t)stream);
-}
-
-int aqg_gcn_forward_graph(int num_features, int num_actions, const float* x, int num_nodes, const int32_t* csr_ptr,
-                          const int32_t* csr_src, const float* csr_w, const int32_t* graph_ptr, int num_graphs,
-                          const float* packed, float* work0, float* work1, float* pooled, float* logits, float* policy,
-                          float* value_pre, float* value, void* stream) {
-    if (!x || !csr_ptr || !csr_src || !csr_w || !graph_ptr || !packed || !work0 || !work1 || !pooled)
-        return fail("aqg_gcn_forward_graph: null argument");
-    return launch_gcn_forward_graph(num_features, num_actions, x, num_nodes, csr_ptr, csr_src, csr_w, graph_ptr, num_graphs,
-                                    packed, work0, work1, pooled, logits, policy, value_pre, value, (hipStream_t)stream);
-}
-
-int aqg_gcn_forward_graph_saved(int num_features, int num_actions, const float* x, int num_nodes, const int32_t* csr_ptr,
-                                const int32_t* csr_src, const float* csr_w, const int32_t* graph_ptr, int num_graphs,
-                                const float* packed, float* work0, float* h1, float* h2, float* h3, float* pooled, float* logits,
-                                float* policy, float* value_pre, float* value, void* stream) {
-    if (num_nodes < 0 || num_graphs < 0) return fail("aqg_gcn_forward_graph_saved: negative size");
-    if (num_nodes == 0) return 0;
-    if (!x || !csr_ptr || !csr_src || !csr_w || !graph_ptr || !packed || !work0 || !h1 || !h2 || !h3 || !pooled)
-        return fail("aqg_gcn_forward_graph_saved: null argument");
-    return launch_gcn_forward_graph_saved(num_features, num_actions, x, num_nodes, csr_ptr, csr_src, csr_w, graph_ptr, num_graphs,
-                                          packed, work0, h1, h2, h3, pooled, logits, policy, value_pre, value, (hipStream_t)stream);
-}
-
-size_t aqg_gcn_backward_graph_workspace_floats(int num_nodes, int num_graphs) {
-    return graph_backward_workspace_floats(num_nodes, num_graphs);
-}
-
-int aqg_gcn_backward_graph(int num_features, int num_actions, const float* x, int num_nodes, const float* h1, const float* h2,
-                           const float* h3, const int32_t* tcsr_ptr, const int32_t* tcsr_dst, const float* tcsr_w,
-                           const int32_t* graph_ptr, int num_graphs, const float* pooled, const float* policy, const float* value,
-                           const float* dpolicy, const float* dvalue, const float* const* params_host, float* workspace,
-                           size_t workspace_floats, float* const* grads_host, float* dx, void* stream) {
-    if (num_nodes < 0 || num_graphs < 0) return fail("aqg_gcn_backward_graph: negative size");
-    if (!params_host || !grads_host) return fail("aqg_gcn_backward_graph: null parameter array");
-    for (int i = 0; i < 14; ++i)
-        if (!params_host[i] || !grads_host[i]) return fail("aqg_gcn_backward_graph: null parameter tensor");
-    if (num_nodes > 0 && num_graphs > 0) {
-        if (!x || !h1 || !h2 || !h3 || !tcsr_ptr || !tcsr_dst || !tcsr_w || !graph_ptr || !pooled || !workspace)
-            return fail("aqg_gcn_backward_graph: null argument");
-        if (dpolicy && !policy) return fail("aqg_gcn_backward_graph: dpolicy needs policy");
-        if (dvalue && !value) return fail("aqg_gcn_backward_graph: dvalue needs value");
-    }
-    return launch_gcn_backward_graph(num_features, num_actions, x, num_nodes, h1, h2, h3, tcsr_ptr, tcsr_dst, tcsr_w, graph_ptr,
-                                     num_graphs, pooled, policy, value, dpolicy, dvalue, params_host, workspace, workspace_floats,
-                                     grads_host, dx, (hipStream_t)stream);
 }
 
 int aqg_graph_linear(int M, int K, int N, const float* X, const float* W, const float* bias, const float* mask, int flags,

@@ -13,16 +13,11 @@
 // own, so a board's outputs are bit-identical at any batch size, position in the batch and `active` mask.
 #include "aqg_common.hpp"
 #include "../../include/aqgnn.h"
+#include "launchers.hpp"
 
 #include <cmath>
 
 namespace aqg {
-
-int launch_gcn_boards_features(int N, const void* states, int fmt, int B, float* x0, hipStream_t st);
-int launch_gen_linear(int M, int K, int N, const float* X, const float* W, const float* bias, const float* mask, int flags,
-                      float* Y, hipStream_t st);
-int launch_gen_heads(int G, int A, const float* logits, const float* vpre, float* policy, float* value, hipStream_t st,
-                     const uint8_t* active);
 
 namespace {
 

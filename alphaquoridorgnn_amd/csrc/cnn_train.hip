@@ -1,7 +1,7 @@
 // cnn_train.hip -- one optimisation step of the reference's residual CNN (pv_network_cnn.py:20-84, CNNNetwork) as its
 // train_network.py:26-107 takes it, on board records (include/aqgnn.h, aqg_cnn_train_step): every BatchNorm2d in train mode.
 //
-//   prep       cnn_train_prep_kernel: the mean pool's graph pointer (and, with an order, this step's records gathered)
+//   prep       train_general_prep_kernel (gcn_train_general.hip): the mean pool's graph pointer (and, with an order, this step's records gathered)
 //   forward    featuriser (launch_gcn_boards_features: the six planes of pv_network_cnn.py:88-114 per tile), then per conv l:
 //              cnn_im2col_kernel -> col [R, 9 Cin] (column ci * 9 + tap: the module's weight [F, Cin, 3, 3] is the GEMM's [N, K] as
 //              PyTorch stores it), gen_linear -> the raw conv output C_l [R, F] (kept), cnn_bn_partial_kernel + cnn_bn_stats_kernel
@@ -22,44 +22,17 @@
 // synchronisation: the caller owns one workspace of aqg_cnn_train_workspace_floats floats.
 #include "aqg_common.hpp"
 #include "../../include/aqgnn.h"
+#include "launchers.hpp"
 
 #include <cmath>
 
 namespace aqg {
-
-int launch_gcn_boards_features(int N, const void* states, int fmt, int B, float* x0, hipStream_t st);
-int launch_gen_linear(int M, int K, int N, const float* X, const float* W, const float* bias, const float* mask, int flags,
-                      float* Y, hipStream_t st);
-size_t gen_linear_grad_workspace_floats_bound(long long max_rows, int N, int K);
-int launch_gen_linear_grad(int M, int K, int N, const float* dY, const float* X, const float* dYb, float* workspace,
-                           size_t workspace_floats, float* dW, float* db, hipStream_t st);
-int launch_gen_mean_pool(int N, const float* H, const int32_t* gptr, int G, float* pooled, hipStream_t st);
-int launch_gen_mean_pool_backward(int n, int N, const float* dpooled, const int32_t* gptr, int G, const float* mask, float* dH,
-                                  hipStream_t st);
-int launch_gen_heads(int G, int A, const float* logits, const float* vpre, float* policy, float* value, hipStream_t st,
-                     const uint8_t* active);
-int launch_gen_heads_backward(int G, int A, const float* policy, const float* dpolicy, const float* value, const float* dvalue,
-                              float* dlogits, float* dvpre, hipStream_t st);
-int launch_train_general_loss(int B, int A, const float* policy, const float* value, const float* pi, const float* z,
-                              const int64_t* order, int first, float* loss, float* dpol, float* dval, hipStream_t st);
 
 namespace {
 
 inline size_t round64(size_t n) { return (n + 63) & ~(size_t)63; }
 inline unsigned blocks_of(long long items, int per) { return (unsigned)((items + per - 1) / per); }
 inline int conv_cin(int l, int F) { return l == 0 ? 6 : F; }
-
-// gptr[g] = g V for g = 0 .. B; with an order, this step's B records are copied to `gathered` (the featuriser reads them in place)
-__global__ __launch_bounds__(256) void cnn_train_prep_kernel(int V, int B, const uint8_t* __restrict__ states72,
-                                                             const int64_t* __restrict__ order, int first, int32_t* __restrict__ gptr,
-                                                             uint8_t* __restrict__ gathered) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i <= B) gptr[i] = i * V;
-    if (order && i < B * 72) {
-        const int b = i / 72, k = i - 72 * b;
-        gathered[i] = states72[(size_t)order[first + b] * 72 + k];
-    }
-}
 
 // col[r][ci * 9 + tap] = X[the tile at offset (tap / 3 - 1, tap % 3 - 1) from tile r][ci], 0 off the board (padding='same')
 __global__ __launch_bounds__(256) void cnn_im2col_kernel(int N, int Cin, size_t total, const float* __restrict__ X,
@@ -318,9 +291,7 @@ int forward_backward(const aqg_cnn_train& t, const uint8_t* states72, const floa
     float* const* p = t.params;
     float* const* g = t.grads;
     const unsigned fblk = blocks_of(F, 256), eblk = blocks_of((long long)RFn, 256);
-    hipLaunchKernelGGL(cnn_train_prep_kernel, dim3(blocks_of(order ? (long long)B * 72 : (long long)B + 1, 256)), dim3(256), 0, st, V, B,
-                       states72, order, first, ws.gptr, ws.states);
-    if (int r = check_launch("cnn_train_prep_kernel")) return r;
+    if (int r = launch_train_general_prep(V, B, states72, order, first, ws.gptr, ws.states, st)) return r;
     const uint8_t* recs = order ? ws.states : states72 + (size_t)first * 72;
     if (int r = launch_gcn_boards_features(N, recs, 0, B, ws.x0, st)) return r;
     // conv l reads in(l) and writes C_l = conv(l), out(l) = relu(BN(C_l) (+ out(l - 2) for the second conv of a block))

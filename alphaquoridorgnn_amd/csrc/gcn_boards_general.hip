@@ -11,14 +11,9 @@
 // fusion removes is the [B*V, N] round trip of Y through HBM between the two launches.
 #include "aqg_common.hpp"
 #include "../../include/aqgnn.h"
+#include "launchers.hpp"
 
 namespace aqg {
-
-int launch_gcn_boards_graph(int N, const void* states, int fmt, int B, float* x0, int32_t* ell_idx, float* ell_w, hipStream_t st);
-int launch_gen_linear(int M, int K, int N, const float* X, const float* W, const float* bias, const float* mask, int flags,
-                      float* Y, hipStream_t st);
-int launch_gen_heads(int G, int A, const float* logits, const float* vpre, float* policy, float* value, hipStream_t st,
-                     const uint8_t* active);
 
 namespace {
 

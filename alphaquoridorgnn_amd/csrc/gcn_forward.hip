@@ -16,11 +16,12 @@
 //
 // heads kernel: policy MLP 128->64->209 (+Softmax) and value MLP 128->64->1 (+Tanh), 16 boards per workgroup.
 //
-// graph kernels: the same network on an arbitrary (x, CSR, graph_ptr) batch -- generic boundary path.
+// plain kernels: the same network on boards of 3x3 / 5x5 / 7x7 (an arbitrary (x, edge_index, batch) graph runs on gcn_general.hip).
 #define AQG_TRACE_TU gcn
 #include "aqg_common.hpp"
 #include "split_mfma.hpp"
 #include "../../include/aqgnn.h"
+#include "launchers.hpp"
 #include <vector>
 #include <cmath>
 #include <algorithm>
@@ -1730,7 +1731,7 @@ int profile_collect(double* total_ms, long long* launches, long long* boards, in
 int launch_gcn_forward_boards(int N, const void* states, int fmt, int B, const float* packed, float* pooled,
                               float* logits, float* policy, float* value_pre, float* value, const uint8_t* active,
                               int flags, int32_t* saturated, hipStream_t st, const int32_t* list, const int32_t* list_count) {
-    if (N != 9) return fail("fused board trunk is built for 9x9; use aqg_gcn_forward_graph for other sizes");
+    if (N != 9) return fail("fused board trunk is built for 9x9; use aqg_gcn_forward_boards_any for other sizes");
     if (B <= 0) return 0;
     if (!pooled) return fail("pooled workspace is required");
     if (N * N + 2 * (N - 1) * (N - 1) > 248) return fail("policy size exceeds 248");
@@ -1774,7 +1775,7 @@ int launch_gcn_forward_boards(int N, const void* states, int fmt, int B, const f
 }
 
 // ---------------------------------------------------------------------------------------------
-// generic graph path (forward(x, edge_index, batch)): linear -> CSR gather -> pool; correctness-first
+// the VALU linear map of the any-size board path below
 // ---------------------------------------------------------------------------------------------
 // Y[n][HID] = X[n][K] * WT[K][HID]   (WT row stride ldw; K = 6 (padded rows of W1 read as [n][f]) or 128)
 template <bool W_IS_NF>
@@ -1802,80 +1803,6 @@ __global__ __launch_bounds__(256) void graph_linear_kernel(const float* __restri
         const int n = n0 + 16 * half + i;
         if (n < num_nodes) Y[(size_t)n * HID + col] = acc[i];
     }
-}
-
-// out[i] = relu(sum_{e in csr[i]} w_e * Y[src_e] + bias): one wave per node, lane = 2 columns
-__global__ __launch_bounds__(256) void graph_gather_kernel(const float* __restrict__ Y, int num_nodes,
-                                                           const int32_t* __restrict__ ptr, const int32_t* __restrict__ src,
-                                                           const float* __restrict__ w, const float* __restrict__ bias,
-                                                           float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= num_nodes) return;
-    float a0 = bias[2 * lane], a1 = bias[2 * lane + 1];
-    for (int e = ptr[i]; e < ptr[i + 1]; ++e) {
-        const float we = w[e];
-        const float2 y = *reinterpret_cast<const float2*>(Y + (size_t)src[e] * HID + 2 * lane);
-        a0 = fmaf(we, y.x, a0);
-        a1 = fmaf(we, y.y, a1);
-    }
-    *reinterpret_cast<float2*>(out + (size_t)i * HID + 2 * lane) = make_float2(fmaxf(a0, 0.f), fmaxf(a1, 0.f));
-}
-
-__global__ __launch_bounds__(128) void graph_pool_kernel(const float* __restrict__ Hn, const int32_t* __restrict__ gptr,
-                                                         int num_graphs, float* __restrict__ pooled) {
-    const int g = blockIdx.x;
-    if (g >= num_graphs) return;
-    const int a = gptr[g], b = gptr[g + 1];
-    float s = 0.f;
-    for (int i = a; i < b; ++i) s += Hn[(size_t)i * HID + threadIdx.x];
-    pooled[(size_t)g * HID + threadIdx.x] = (b > a) ? s / (float)(b - a) : 0.f;
-}
-
-// Layer l's output goes to out[l-1]: the eval path passes work1 three times (ping-pong with work0), the recording path of
-// autograd (aqg_gcn_forward_graph_saved) three separate buffers H1, H2, H3 its backward reads.  Same kernels, same values.
-static int graph_forward(int F, int A, const float* x, int num_nodes, const int32_t* csr_ptr, const int32_t* csr_src,
-                         const float* csr_w, const int32_t* graph_ptr, int num_graphs, const float* packed, float* work0,
-                         float* const out[3], float* pooled, float* logits, float* policy, float* value_pre, float* value,
-                         hipStream_t st) {
-    if (F != 6) return fail("num_features must be 6 (NUM_FEATURES pv_network_gnn.py:17)");
-    if (A > 248) return fail("policy size exceeds 248");
-    if (num_nodes <= 0 || num_graphs <= 0) return 0;
-    dim3 lg((num_nodes + 31) / 32), gg((num_nodes + 3) / 4);
-    hipLaunchKernelGGL(graph_linear_kernel<true>, lg, dim3(256), 0, st, x, F, num_nodes, packed + PackedLayout::W1, work0);
-    hipLaunchKernelGGL(graph_gather_kernel, gg, dim3(256), 0, st, (const float*)work0, num_nodes, csr_ptr, csr_src, csr_w,
-                       packed + PackedLayout::B1, out[0]);
-    hipLaunchKernelGGL(graph_linear_kernel<false>, lg, dim3(256), 0, st, (const float*)out[0], HID, num_nodes,
-                       packed + PackedLayout::W2T, work0);
-    hipLaunchKernelGGL(graph_gather_kernel, gg, dim3(256), 0, st, (const float*)work0, num_nodes, csr_ptr, csr_src, csr_w,
-                       packed + PackedLayout::B2, out[1]);
-    hipLaunchKernelGGL(graph_linear_kernel<false>, lg, dim3(256), 0, st, (const float*)out[1], HID, num_nodes,
-                       packed + PackedLayout::W3T, work0);
-    hipLaunchKernelGGL(graph_gather_kernel, gg, dim3(256), 0, st, (const float*)work0, num_nodes, csr_ptr, csr_src, csr_w,
-                       packed + PackedLayout::B3, out[2]);
-    hipLaunchKernelGGL(graph_pool_kernel, dim3(num_graphs), dim3(128), 0, st, (const float*)out[2], graph_ptr, num_graphs, pooled);
-    if (int r = check_launch("graph kernels")) return r;
-    hipLaunchKernelGGL(gcn_heads_kernel, dim3((num_graphs + HB - 1) / HB), dim3(256), 0, st, (const float*)pooled, num_graphs, A,
-                       packed, logits, policy, value_pre, value, (const uint8_t*)nullptr);
-    return check_launch("gcn_heads_kernel");
-}
-
-int launch_gcn_forward_graph(int F, int A, const float* x, int num_nodes, const int32_t* csr_ptr, const int32_t* csr_src,
-                             const float* csr_w, const int32_t* graph_ptr, int num_graphs, const float* packed,
-                             float* work0, float* work1, float* pooled, float* logits, float* policy, float* value_pre,
-                             float* value, hipStream_t st) {
-    float* const out[3] = {work1, work1, work1};
-    return graph_forward(F, A, x, num_nodes, csr_ptr, csr_src, csr_w, graph_ptr, num_graphs, packed, work0, out, pooled, logits,
-                         policy, value_pre, value, st);
-}
-
-int launch_gcn_forward_graph_saved(int F, int A, const float* x, int num_nodes, const int32_t* csr_ptr, const int32_t* csr_src,
-                                   const float* csr_w, const int32_t* graph_ptr, int num_graphs, const float* packed,
-                                   float* work0, float* h1, float* h2, float* h3, float* pooled, float* logits, float* policy,
-                                   float* value_pre, float* value, hipStream_t st) {
-    float* const out[3] = {h1, h2, h3};
-    return graph_forward(F, A, x, num_nodes, csr_ptr, csr_src, csr_w, graph_ptr, num_graphs, packed, work0, out, pooled, logits,
-                         policy, value_pre, value, st);
 }
 
 // ---------------------------------------------------------------------------------------------

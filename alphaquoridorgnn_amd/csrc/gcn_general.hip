@@ -13,6 +13,7 @@
 // so every result is a deterministic function of the inputs.
 #include "aqg_common.hpp"
 #include "../../include/aqgnn.h"
+#include "launchers.hpp"
 
 namespace aqg {
 namespace {

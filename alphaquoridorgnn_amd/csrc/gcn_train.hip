@@ -28,6 +28,7 @@
 #include "aqg_common.hpp"
 #include "split_mfma.hpp"
 #include "../../include/aqgnn.h"
+#include "launchers.hpp"
 
 namespace aqg {
 

@@ -16,25 +16,9 @@
 // synchronisation: the caller owns one workspace of aqg_gcn_train_general_workspace_floats floats.
 #include "aqg_common.hpp"
 #include "../../include/aqgnn.h"
+#include "launchers.hpp"
 
 namespace aqg {
-
-int launch_gcn_boards_graph(int N, const void* states, int fmt, int B, float* x0, int32_t* ell_idx, float* ell_w, hipStream_t st);
-int launch_board_gcn_layer(int N, int B, int K, int Nout, const float* X, const float* W, const float* bias, const int32_t* ell_idx,
-                           const float* ell_w, const uint8_t* active, float* H, float* pooled, hipStream_t st);
-int check_general_net(const aqg_gcn_general_net* net, const char** why);
-int launch_gen_linear(int M, int K, int N, const float* X, const float* W, const float* bias, const float* mask, int flags,
-                      float* Y, hipStream_t st);
-size_t gen_linear_grad_workspace_floats_bound(long long max_rows, int N, int K);
-int launch_gen_linear_grad(int M, int K, int N, const float* dY, const float* X, const float* dYb, float* workspace,
-                           size_t workspace_floats, float* dW, float* db, hipStream_t st);
-int launch_gen_mean_pool(int N, const float* H, const int32_t* gptr, int G, float* pooled, hipStream_t st);
-int launch_gen_mean_pool_backward(int n, int N, const float* dpooled, const int32_t* gptr, int G, const float* mask, float* dH,
-                                  hipStream_t st);
-int launch_gen_heads(int G, int A, const float* logits, const float* vpre, float* policy, float* value, hipStream_t st,
-                     const uint8_t* active);
-int launch_gen_heads_backward(int G, int A, const float* policy, const float* dpolicy, const float* value, const float* dvalue,
-                              float* dlogits, float* dvpre, hipStream_t st);
 
 namespace {
 
@@ -292,9 +276,7 @@ int forward_backward(const aqg_train_general& t, const uint8_t* states72, const 
     const int N = t.board_size, V = N * N, Hd = t.hidden, L = t.num_layers, A = t.policy_size, Hh = Hd / 2, R = B * V;
     float* const* p = t.params;
     float* const* g = t.grads;
-    hipLaunchKernelGGL(train_general_prep_kernel, dim3(blocks_of(order ? (long long)B * 72 : (long long)B + 1, 256)), dim3(256), 0, st,
-                       V, B, states72, order, first, ws.gptr, ws.states);
-    if (int r = check_launch("train_general_prep_kernel")) return r;
+    if (int r = launch_train_general_prep(V, B, states72, order, first, ws.gptr, ws.states, st)) return r;
     const uint8_t* recs = order ? ws.states : states72 + (size_t)first * 72;
     if (int r = launch_gcn_boards_graph(N, recs, 0, B, ws.x0, ws.ell_idx, ws.ell_w, st)) return r;
     // forward: every layer's output kept (H_l = ws.h + (l - 1) h_stride), then the pool and the heads of the any-shape forward
@@ -381,7 +363,15 @@ int validate(const aqg_train_general& t, const char* what) {
 
 }  // namespace
 
-// the loss kernel for the residual CNN's step (cnn_train.hip): the same two loss terms and their gradients
+// the prep and loss kernels, shared with the residual CNN's step (cnn_train.hip): the same graph pointer / gathered records and the
+// same two loss terms and their gradients
+int launch_train_general_prep(int V, int B, const uint8_t* states72, const int64_t* order, int first, int32_t* gptr, uint8_t* gathered,
+                              hipStream_t st) {
+    hipLaunchKernelGGL(train_general_prep_kernel, dim3(blocks_of(order ? (long long)B * 72 : (long long)B + 1, 256)), dim3(256), 0, st,
+                       V, B, states72, order, first, gptr, gathered);
+    return check_launch("train_general_prep_kernel");
+}
+
 int launch_train_general_loss(int B, int A, const float* policy, const float* value, const float* pi, const float* z,
                               const int64_t* order, int first, float* loss, float* dpol, float* dval, hipStream_t st) {
     hipLaunchKernelGGL(train_general_loss_kernel, dim3(B), dim3(256), 0, st, B, A, policy, value, pi, z, order, first, loss, dpol, dval);

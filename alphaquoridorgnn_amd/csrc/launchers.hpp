@@ -1,0 +1,110 @@
+// launchers.hpp -- the host functions and option globals one .hip file defines and another calls, declared once.  Included by
+// the defining file as well, so a definition that drifts from its declaration does not compile.  Declarations only.
+#pragma once
+#include "aqg_common.hpp"
+#include "../../include/aqgnn.h"
+
+namespace aqg {
+
+// ---- legal_mask.hip
+int launch_legal_actions(int N, const void* states, int fmt, int B, uint8_t* mask, uint8_t* order, int32_t* count,
+                         const uint8_t* active, hipStream_t st);
+int launch_state_next(int N, const uint8_t* in, const int32_t* actions, int B, uint8_t* out, hipStream_t st);
+int launch_state_status(int N, const uint8_t* in, int B, int draw, uint8_t* flags, hipStream_t st);
+
+// ---- gcn_forward.hip
+extern int g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, g_profile_trunk, g_trunk_prio, g_heads_prio;
+void profile_mark(hipStream_t st, long long units);
+int profile_collect(double* total_ms, long long* launches, long long* boards, int reset);
+int launch_poison_lds(hipStream_t st);
+int set_trace_gcn(void* buf, unsigned int cap);
+size_t packed_floats();
+int pack_weights_host(int N, const float* const* t, float* out);
+int launch_gcn_forward_boards(int N, const void* states, int fmt, int B, const float* packed, float* pooled,
+                              float* logits, float* policy, float* value_pre, float* value, const uint8_t* active,
+                              int flags, int32_t* saturated, hipStream_t st, const int32_t* list = nullptr,
+                              const int32_t* list_count = nullptr);
+size_t boards_any_workspace_floats(int N, int B);
+int launch_gcn_forward_boards_any(int N, const void* states, int fmt, int B, const float* packed, float* workspace,
+                                  size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre,
+                                  float* value, const uint8_t* active, int flags, int32_t* saturated, hipStream_t st,
+                                  const int32_t* list = nullptr, const int32_t* list_count = nullptr);
+int launch_gcn_boards_graph(int N, const void* states, int fmt, int B, float* x0, int32_t* ell_idx, float* ell_w, hipStream_t st);
+int launch_gcn_boards_features(int N, const void* states, int fmt, int B, float* x0, hipStream_t st);
+
+// ---- gcn_general.hip
+int launch_gen_linear(int M, int K, int N, const float* X, const float* W, const float* bias, const float* mask, int flags,
+                      float* Y, hipStream_t st);
+size_t gen_linear_grad_workspace_floats(int M, int N, int K);
+size_t gen_linear_grad_workspace_floats_bound(long long max_rows, int N, int K);
+int launch_gen_linear_grad(int M, int K, int N, const float* dY, const float* X, const float* dYb, float* workspace,
+                           size_t workspace_floats, float* dW, float* db, hipStream_t st);
+int launch_gen_aggregate(int n, int N, const float* Y, const int32_t* ptr, const int32_t* src, const float* w, const float* bias,
+                         int relu, float* out, hipStream_t st);
+int launch_gen_mean_pool(int N, const float* H, const int32_t* gptr, int G, float* pooled, hipStream_t st);
+int launch_gen_mean_pool_backward(int n, int N, const float* dpooled, const int32_t* gptr, int G, const float* mask, float* dH,
+                                  hipStream_t st);
+int launch_gen_heads(int G, int A, const float* logits, const float* vpre, float* policy, float* value, hipStream_t st,
+                     const uint8_t* active = nullptr);
+int launch_gen_heads_backward(int G, int A, const float* policy, const float* dpolicy, const float* value, const float* dvalue,
+                              float* dlogits, float* dvpre, hipStream_t st);
+
+// ---- gcn_boards_general.hip
+int launch_board_gcn_layer(int N, int B, int K, int Nout, const float* X, const float* W, const float* bias, const int32_t* ell_idx,
+                           const float* ell_w, const uint8_t* active, float* H, float* pooled, hipStream_t st);
+size_t boards_general_workspace_floats(int N, int hidden, int A, int B);
+int check_general_net(const aqg_gcn_general_net* net, const char** why);
+int launch_gcn_forward_boards_general(int N, const void* states, int fmt, int B, const aqg_gcn_general_net* net,
+                                      const uint8_t* active, float* workspace, size_t workspace_floats, float* pooled, float* logits,
+                                      float* policy, float* value_pre, float* value, hipStream_t st);
+
+// ---- cnn_forward.hip
+int check_cnn_net(const aqg_cnn_net* net, int N, const char** why);
+size_t cnn_packed_floats(int F, int L, int A);
+int launch_cnn_pack(int F, int L, int A, const float* const* params, const float* eps, float* packed, hipStream_t st);
+size_t cnn_workspace_floats(int N, int F, int A, int B);
+int launch_cnn_forward_boards(int N, const void* states, int fmt, int B, const aqg_cnn_net* net, const uint8_t* active, float* workspace,
+                              size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre, float* value,
+                              hipStream_t st);
+int launch_cnn_forward_planes(int N, const float* planes, int B, const aqg_cnn_net* net, const uint8_t* active, float* workspace,
+                              size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre, float* value,
+                              hipStream_t st);
+
+// ---- mcts.hip
+extern int g_use_graph, g_step_variant, g_step_waves, g_step_prio, g_step_fast_depth;
+int set_trace_mcts(void* buf, unsigned int cap);
+int engine_reset(const aqg_engine& e, hipStream_t st);
+int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st);
+int engine_begin_move(const aqg_engine& e, hipStream_t st);
+int engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t st);
+int engine_finish_move(const aqg_engine& e, const double* uniforms, hipStream_t st);
+int engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
+int engine_move(const aqg_engine& e, const double* uniforms, hipStream_t st);
+int engine_search(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
+int engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st);
+
+// ---- gcn_train.hip
+extern int g_train_fused;
+int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st);
+long long train_fallbacks(int reset);
+int train_steps(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, long long positions,
+                float* loss_sums, hipStream_t st);
+
+// ---- gcn_train_general.hip
+int launch_train_general_prep(int V, int B, const uint8_t* states72, const int64_t* order, int first, int32_t* gptr, uint8_t* gathered,
+                              hipStream_t st);
+int launch_train_general_loss(int B, int A, const float* policy, const float* value, const float* pi, const float* z,
+                              const int64_t* order, int first, float* loss, float* dpol, float* dval, hipStream_t st);
+size_t train_general_workspace_floats(int N, int hidden, int num_layers, int policy_size, int max_batch);
+int train_step_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st);
+int train_steps_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
+                        long long positions, float* loss_sums, hipStream_t st);
+
+// ---- cnn_train.hip
+size_t cnn_train_workspace_floats(int N, int F, int L, int A, int max_batch);
+int check_cnn_train(const aqg_cnn_train& t, bool adam, const char* what);
+int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st);
+int cnn_train_steps(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
+                    long long positions, float* loss_sums, hipStream_t st);
+
+}  // namespace aqg

@@ -8,6 +8,7 @@
 // not HBM (100 algorithmic bytes per state).
 #include "aqg_common.hpp"
 #include "legal_wave.hpp"
+#include "launchers.hpp"
 
 namespace aqg {
 

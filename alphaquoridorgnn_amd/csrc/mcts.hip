@@ -20,6 +20,7 @@
 #include <cstring>
 #include "legal_wave.hpp"
 #include "../../include/aqgnn.h"
+#include "launchers.hpp"
 
 // PUCT scores must be evaluated exactly as written (no fma contraction, IEEE divide/sqrt).
 #pragma clang fp contract(off)
@@ -28,27 +29,6 @@ namespace aqg {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-int launch_legal_actions(int N, const void* states, int fmt, int B, uint8_t* mask, uint8_t* order, int32_t* count,
-                         const uint8_t* active, hipStream_t st);
-int launch_gcn_forward_boards(int N, const void* states, int fmt, int B, const float* packed, float* pooled,
-                              float* logits, float* policy, float* value_pre, float* value, const uint8_t* active,
-                              int flags, int32_t* saturated, hipStream_t st, const int32_t* list = nullptr, const int32_t* list_count = nullptr);
-size_t boards_any_workspace_floats(int N, int B);
-int launch_gcn_forward_boards_any(int N, const void* states, int fmt, int B, const float* packed, float* workspace,
-                                  size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre,
-                                  float* value, const uint8_t* active, int flags, int32_t* saturated, hipStream_t st, const int32_t* list = nullptr, const int32_t* list_count = nullptr);
-size_t boards_general_workspace_floats(int N, int hidden, int A, int B);
-int check_general_net(const aqg_gcn_general_net* net, const char** why);
-int launch_gcn_forward_boards_general(int N, const void* states, int fmt, int B, const aqg_gcn_general_net* net,
-                                      const uint8_t* active, float* workspace, size_t workspace_floats, float* pooled, float* logits,
-                                      float* policy, float* value_pre, float* value, hipStream_t st);
-size_t cnn_workspace_floats(int N, int F, int A, int B);
-int check_cnn_net(const aqg_cnn_net* net, int N, const char** why);
-int launch_cnn_forward_boards(int N, const void* states, int fmt, int B, const aqg_cnn_net* net, const uint8_t* active, float* workspace,
-                              size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre, float* value,
-                              hipStream_t st);
-extern int g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, g_profile_trunk, g_trunk_prio, g_heads_prio;
-void profile_mark(hipStream_t st, long long units);
 int g_use_graph = 1;       // aqg_set_option("use_graph", 0) forces plain launches
 
 __device__ __forceinline__ int wave_sum_i(int v) {

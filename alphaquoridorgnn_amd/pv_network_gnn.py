@@ -10,9 +10,9 @@ self-play engine uses -- and `GNNNetwork`, the BaseNetwork-style wrapper (BaseNe
 `predict / prep_for_inference / preprocess_input / name`.
 
 Any shape: the reference's GraphPolicyValueNetwork takes any (num_features, hidden_dim, num_gcn_layers, policy_output_size).
-The default 6/128/3 network (`fused`) runs the fused kernels; every other shape (within SHAPE_LIMITS) runs the width-generic
-graph primitives of csrc/gcn_general.hip, which also serve `GCNConv.forward(x, edge_index)` and `global_mean_pool(x, batch)`
--- PyG's calls, on any layer -- forward and backward.
+`forward(x, edge_index, batch)` of every shape (within SHAPE_LIMITS) runs the width-generic graph primitives of
+csrc/gcn_general.hip, which also serve `GCNConv.forward(x, edge_index)` and `global_mean_pool(x, batch)` -- PyG's calls, on any
+layer -- forward and backward.  On board records the default 6/128/3 network (`fused`) runs the fused kernels.
 
 All arithmetic runs in libaqgnn_hip.so (fp32 data; fp16-split or f32-input MFMA, see csrc/gcn_forward.hip); there is no
 torch/CPU forward in this file.
@@ -55,9 +55,9 @@ def state_dict_keys(num_gcn_layers):
 
 
 class GCNConv(nn.Module):
-    """PyG's GCNConv with its naming and initialisation (lin: Glorot-uniform, no bias; bias: zeros).  Inside a default
-    6/128/3 network the layer arithmetic is fused into the network-level kernels; forward(x, edge_index) runs the layer alone
-    on the width-generic kernels (any in / out width)."""
+    """PyG's GCNConv with its naming and initialisation (lin: Glorot-uniform, no bias; bias: zeros).  On board records a
+    default 6/128/3 network fuses the layer arithmetic into its network-level kernels; forward(x, edge_index) runs the layer
+    alone on the width-generic kernels (any in / out width)."""
 
     def __init__(self, in_channels, out_channels):
         super().__init__()
@@ -97,7 +97,7 @@ class GraphPolicyValueNetwork(nn.Module):
                 raise ValueError(f"{name} must be an integer in [{lo}, {hi}] (the limit of the HIP kernels), got {v!r}")
         num_features, hidden_dim, num_gcn_layers, policy_output_size = (int(num_features), int(hidden_dim), int(num_gcn_layers),
                                                                         int(policy_output_size))
-        # the default shape runs the fused kernels (packed weights, engine, GNNTrainer); any other the width-generic primitives
+        # the default shape has the fused board kernels (packed weights, forward_states, engine 'gnn' evaluator, GNNTrainer)
         self.fused = (num_features, hidden_dim, num_gcn_layers) == (NUM_FEATURES, HIDDEN_DIM, NUM_GCN_LAYERS)
         self.state_dict_keys = state_dict_keys(num_gcn_layers)
         self.num_features = num_features
@@ -389,49 +389,19 @@ class GraphPolicyValueNetwork(nn.Module):
 
     def forward(self, x, edge_index, batch):
         """pv_network_gnn.py:53-64 with PyG's GCNConv / global_mean_pool semantics (_prepare_graph: the self-loop rule and the
-        validated inputs).  x [sum V, 6] floating point, edge_index [2, E] integer ids in [0, sum V), batch [sum V] integer,
-        non-negative and sorted (unsorted raises ValueError).  One device-to-host read per call once the weights are packed.
-        A network of non-default shape (x [sum V, num_features]) runs the width-generic kernels (csrc/gcn_general.hip) with
-        the same semantics, the same single read and the same autograd contract.
+        validated inputs).  x [sum V, num_features] floating point, edge_index [2, E] integer ids in [0, sum V), batch [sum V]
+        integer, non-negative and sorted (unsorted raises ValueError).  One device-to-host read per call.  Every shape, the
+        default 6/128/3 included, runs the width-generic kernels (csrc/gcn_general.hip) on the module's own parameters.
 
         Autograd: in train mode, with grad enabled and x or any parameter requiring grad, the forward is recorded
-        (_GraphForward): the outputs carry a grad_fn and backward() fills the parameters' .grad (and x.grad) from HIP
-        kernels (csrc/gcn_graph_grad.hip).  Its values are bit-identical to the plain forward's.  Otherwise (eval mode,
-        no_grad, inference_mode) the outputs carry no graph."""
-        if not self.fused:
-            return self._forward_general(x, edge_index, batch)
-        dev = _lib.require_gpu(x.device)
-        params = [p for _, p in self._ordered_params()]
-        if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-            tensors = self._prepare_graph(x, edge_index, batch, transpose=True)
-            xf = x.to(torch.float32).contiguous()            # outside the Function: torch routes x's gradient through the cast
-            policy, value, logits, vpre = _GraphForward.apply(self, tensors, dev, xf, *params)
-            self.last_logits, self.last_value_pre = logits, vpre
-            return policy, value.unsqueeze(1)
-        lib = _lib.load()
-        ptr, csr_src, csr_w, gptr, G = self._prepare_graph(x, edge_index, batch)
-        x = x.to(torch.float32).contiguous()
-        n = x.shape[0]
-        A = self.policy_output_size
-        f32 = dict(dtype=torch.float32, device=dev)
-        w0, w1 = torch.empty((n, HIDDEN_DIM), **f32), torch.empty((n, HIDDEN_DIM), **f32)
-        pooled = torch.empty((G, HIDDEN_DIM), **f32)
-        policy, value = torch.empty((G, A), **f32), torch.empty((G,), **f32)
-        logits, vpre = torch.empty((G, A), **f32), torch.empty((G,), **f32)
-        if n:       # (no nodes: no graphs, and the empty buffers have no address to pass)
-            _lib.check(lib.aqg_gcn_forward_graph(NUM_FEATURES, A, _lib.ptr(x), n, _lib.ptr(ptr), _lib.ptr(csr_src), _lib.ptr(csr_w),
-                                                 _lib.ptr(gptr), G, _lib.ptr(self.packed_weights(dev)), _lib.ptr(w0), _lib.ptr(w1),
-                                                 _lib.ptr(pooled), _lib.ptr(logits), _lib.ptr(policy), _lib.ptr(vpre), _lib.ptr(value),
-                                                 _lib.stream_ptr(dev)), "aqg_gcn_forward_graph")
-        self.last_logits, self.last_value_pre = logits, vpre
-        return policy, value.unsqueeze(1)
-
-    def _forward_general(self, x, edge_index, batch):
+        (_GeneralForward): the outputs carry a grad_fn and backward() fills the parameters' .grad (and x.grad) from the same
+        HIP primitives.  Its values are bit-identical to the plain forward's.  Otherwise (eval mode, no_grad,
+        inference_mode) the outputs carry no graph."""
         dev = _lib.require_gpu(x.device)
         params = [p for _, p in self._ordered_params()]
         record = self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
         tensors = self._prepare_graph(x, edge_index, batch, transpose=record, num_features=self.num_features)
-        xf = x.to(torch.float32).contiguous()
+        xf = x.to(torch.float32).contiguous()            # outside the Function: torch routes x's gradient through the cast
         if record:
             policy, value, logits, vpre = _GeneralForward.apply(self, tensors, dev, xf, *params)
         else:
@@ -489,68 +459,6 @@ class GraphPolicyValueNetwork(nn.Module):
     def general_weights_key(self):
         """(data pointer, version counter) of every parameter: changes whenever a parameter is replaced or updated in place."""
         return tuple((p.data_ptr(), p._version) for _, p in self._ordered_params())
-
-
-class _GraphForward(torch.autograd.Function):
-    """forward(x, edge_index, batch) as one autograd node: the plain forward's kernels with H1, H2, H3 kept
-    (aqg_gcn_forward_graph_saved), and aqg_gcn_backward_graph for the gradients of the 14 parameters and of x.
-    Neither direction reads anything back to the host."""
-
-    @staticmethod
-    def forward(ctx, model, tensors, dev, xf, *params):
-        ptr, csr_src, csr_w, gptr, G, tptr, tdst, tw = tensors
-        lib = _lib.load()
-        n, A = xf.shape[0], model.policy_output_size
-        f32 = dict(dtype=torch.float32, device=dev)
-        h = [torch.empty((n, HIDDEN_DIM), **f32) for _ in range(3)]
-        pooled = torch.empty((G, HIDDEN_DIM), **f32)
-        policy, value = torch.empty((G, A), **f32), torch.empty((G,), **f32)
-        logits, vpre = torch.empty((G, A), **f32), torch.empty((G,), **f32)
-        if n:
-            work = torch.empty((n, HIDDEN_DIM), **f32)
-            _lib.check(lib.aqg_gcn_forward_graph_saved(NUM_FEATURES, A, _lib.ptr(xf), n, _lib.ptr(ptr), _lib.ptr(csr_src),
-                                                       _lib.ptr(csr_w), _lib.ptr(gptr), G, _lib.ptr(model.packed_weights(dev)),
-                                                       _lib.ptr(work), _lib.ptr(h[0]), _lib.ptr(h[1]), _lib.ptr(h[2]),
-                                                       _lib.ptr(pooled), _lib.ptr(logits), _lib.ptr(policy), _lib.ptr(vpre),
-                                                       _lib.ptr(value), _lib.stream_ptr(dev)), "aqg_gcn_forward_graph_saved")
-        ctx.save_for_backward(xf, policy, value, *params)
-        ctx.graph = (tptr, tdst, tw, gptr, G, A, dev)
-        ctx.acts = (h, pooled)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(logits, vpre)
-        return policy, value, logits, vpre
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dpolicy, dvalue, _dlogits, _dvpre):
-        xf, policy, value, *params = ctx.saved_tensors
-        tptr, tdst, tw, gptr, G, A, dev = ctx.graph
-        h, pooled = ctx.acts
-        lib = _lib.load()
-        n = xf.shape[0]
-        pf = [p.detach().to(device=dev, dtype=torch.float32).contiguous() for p in params]
-        grads = [torch.empty_like(p) for p in pf]
-        want_dx = ctx.needs_input_grad[3]
-        dx = torch.empty((n, NUM_FEATURES), dtype=torch.float32, device=dev) if want_dx and n else None
-        dp = dpolicy.to(torch.float32).contiguous() if dpolicy is not None else None
-        dv = dvalue.to(torch.float32).contiguous() if dvalue is not None else None
-        nws = int(lib.aqg_gcn_backward_graph_workspace_floats(n, G))
-        ws = torch.empty((nws,), dtype=torch.float32, device=dev) if nws else None
-        arr = lambda ts: (ctypes.c_void_p * 14)(*[ctypes.c_void_p(t.data_ptr()) for t in ts])
-        if n == 0:
-            for g in grads:
-                g.zero_()
-        else:
-            _lib.check(lib.aqg_gcn_backward_graph(NUM_FEATURES, A, _lib.ptr(xf), n, _lib.ptr(h[0]), _lib.ptr(h[1]), _lib.ptr(h[2]),
-                                                  _lib.ptr(tptr), _lib.ptr(tdst), _lib.ptr(tw), _lib.ptr(gptr), G, _lib.ptr(pooled),
-                                                  _lib.ptr(policy), _lib.ptr(value), _lib.ptr(dp), _lib.ptr(dv), arr(pf),
-                                                  _lib.ptr(ws), nws, arr(grads), _lib.ptr(dx), _lib.stream_ptr(dev)),
-                       "aqg_gcn_backward_graph")
-        if want_dx and n == 0:
-            dx = torch.zeros((0, NUM_FEATURES), dtype=torch.float32, device=dev)
-        out = [g if ctx.needs_input_grad[4 + i] else None for i, g in enumerate(grads)]
-        out = [o.to(params[i].dtype) if o is not None else None for i, o in enumerate(out)]
-        return (None, None, None, dx if want_dx else None, *out)
 
 
 # ---------------------------------------------------------------- width-generic graph primitives (csrc/gcn_general.hip)
@@ -638,7 +546,7 @@ def _general_forward(lib, dev, model, xf, csr, gptr, G, pf):
 
 
 class _GeneralForward(torch.autograd.Function):
-    """forward(x, edge_index, batch) of a non-default shape as one autograd node: _general_forward with its activations kept,
+    """forward(x, edge_index, batch) as one autograd node: _general_forward with its activations kept,
     and the backward composed from the same primitives.  Neither direction reads anything back to the host."""
 
     @staticmethod

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define AQG_MAX_LEGAL 136 /* >= 5 pawn moves + 128 wall placements */
-#define AQG_ABI_VERSION 14
+#define AQG_ABI_VERSION 15
 
 int aqg_abi_version(void);
 const char* aqg_last_error(void);
@@ -145,11 +145,6 @@ int aqg_gcn_forward_boards(int board_size, const void* states, int state_fmt, in
 int aqg_gcn_forward_boards_guarded(int board_size, const void* states, int state_fmt, int B, const float* packed,
                                    float* pooled, float* logits, float* policy, float* value_pre, float* value,
                                    int flags, int32_t* saturated, void* stream);
-/* Same network on an arbitrary batched graph: forward(x, edge_index, batch)  pv_network_gnn.py:53.
- *   x [num_nodes, F] f32;  csr_ptr [num_nodes+1] i32 / csr_src [E'] i32 / csr_w [E'] f32 : incoming edges of
- *   each node INCLUDING its one self loop with the gcn_norm weights already attached (built and validated by the host
- *   wrapper from edge_index with torch ops: every csr_src in [0, num_nodes), nothing here checks it);  graph_ptr [num_graphs+1] i32 node ranges (batch must be sorted);
- *   work0/work1 [num_nodes,128] f32 scratch. */
 /* The same forward for ANY board size 3/5/7/9: 9x9 dispatches to the fused kernels above (workspace unused), the smaller
  * boards of the reference's constants.py:5-20 run on plain kernels (features + ELL adjacency -> linear / gather x3 -> pool
  * -> heads) and need `workspace` of aqg_gcn_boards_any_workspace_floats(board_size, B) floats. */
@@ -158,42 +153,12 @@ int aqg_gcn_forward_boards_any(int board_size, const void* states, int state_fmt
                                size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre, float* value,
                                int flags, void* stream);
 
-int aqg_gcn_forward_graph(int num_features, int num_actions, const float* x, int num_nodes,
-                          const int32_t* csr_ptr, const int32_t* csr_src, const float* csr_w,
-                          const int32_t* graph_ptr, int num_graphs, const float* packed, float* work0,
-                          float* work1, float* pooled, float* logits, float* policy, float* value_pre,
-                          float* value, void* stream);
-
-/* Autograd through forward(x, edge_index, batch) (GraphPolicyValueNetwork in train mode; ABI 11).
- * aqg_gcn_forward_graph_saved: aqg_gcn_forward_graph with the three post-ReLU GCN outputs written to h1, h2, h3
- *   [num_nodes,128] f32 (kept for the backward) instead of the work0/work1 ping-pong; work0 [num_nodes,128] f32 scratch.
- *   The same kernels run in the same order: every output is bit-identical to aqg_gcn_forward_graph's.
- * aqg_gcn_backward_graph: gradients of a loss with respect to the 14 parameters (and x) given dpolicy [G,A] and dvalue [G]
- *   (either may be NULL = zero).  Inputs are the forward's x [n,6], h1..h3, pooled [G,128], policy [G,A], value [G]; the
- *   normalised adjacency as a CSR by SOURCE: the entries leaving node j are tcsr_ptr[j] .. tcsr_ptr[j+1] with destination
- *   tcsr_dst and weight tcsr_w (the forward's (src, dst, w) entries regrouped); graph_ptr as in the forward.
- *   params_host / grads_host: HOST arrays of 14 DEVICE pointers in state_dict order (gcn_layers.0.lin.weight, .bias, ...,
- *   value_head.2.bias; [out,in] weights), f32 contiguous; grads are overwritten, not accumulated.  dx [n,6] may be NULL.
- *   workspace: aqg_gcn_backward_graph_workspace_floats(num_nodes, num_graphs) floats.  No atomics: the result is a
- *   deterministic function of the inputs.  num_nodes == 0 writes zero gradients. */
-size_t aqg_gcn_backward_graph_workspace_floats(int num_nodes, int num_graphs);
-int aqg_gcn_forward_graph_saved(int num_features, int num_actions, const float* x, int num_nodes,
-                                const int32_t* csr_ptr, const int32_t* csr_src, const float* csr_w,
-                                const int32_t* graph_ptr, int num_graphs, const float* packed, float* work0,
-                                float* h1, float* h2, float* h3, float* pooled, float* logits, float* policy,
-                                float* value_pre, float* value, void* stream);
-int aqg_gcn_backward_graph(int num_features, int num_actions, const float* x, int num_nodes, const float* h1,
-                           const float* h2, const float* h3, const int32_t* tcsr_ptr, const int32_t* tcsr_dst,
-                           const float* tcsr_w, const int32_t* graph_ptr, int num_graphs, const float* pooled,
-                           const float* policy, const float* value, const float* dpolicy, const float* dvalue,
-                           const float* const* params_host, float* workspace, size_t workspace_floats,
-                           float* const* grads_host, float* dx, void* stream);
-
 /* ------------------------------------------------------------------ width-generic graph primitives (ABI 13)
  *
  * The building blocks of GraphPolicyValueNetwork at ANY shape (num_features, hidden_dim, num_gcn_layers, policy_output_size),
  * of the stand-alone GCNConv.forward(x, edge_index) and of global_mean_pool, forward and backward (csrc/gcn_general.hip; the
- * composition is pv_network_gnn.py).  The default 6/128/3 network keeps the fused entry points above.  Every buffer is f32 and
+ * composition is pv_network_gnn.py: forward(x, edge_index, batch) of every shape, the default 6/128/3 included -- ABI 15 removed
+ * the four fixed-width entry points aqg_gcn_{forward,backward}_graph* that served that one shape).  Every buffer is f32 and
  * contiguous (row-major); sizes are runtime values.  Every contraction runs on the f32-input MFMA (a k-ordered fmaf chain) and
  * no kernel uses atomics: each sum runs in an order fixed by the sizes, so results are deterministic.  A call with no rows
  * (M, num_nodes or num_graphs 0) launches nothing (aqg_graph_linear_grad writes zero gradients).

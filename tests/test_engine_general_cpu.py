@@ -12,10 +12,10 @@ from tests import _util as U
 REPO = U.REPO
 
 
-def test_abi_version_14():
+def test_abi_version_15():
     from alphaquoridorgnn_amd import _lib
-    assert _lib.ABI_VERSION == 14
-    assert _lib.load().aqg_abi_version() == 14
+    assert _lib.ABI_VERSION == 15
+    assert _lib.load().aqg_abi_version() == 15
 
 
 def test_general_net_layout_matches_header(tmp_path):

@@ -1,6 +1,6 @@
 """GraphPolicyValueNetwork of any shape, GCNConv.forward and global_mean_pool on the width-generic HIP primitives
 (csrc/gcn_general.hip): forward and autograd against an fp64 torch restatement, host reads, the board path, and the
-reference's own layer loop cross-checked against the fused 6/128/3 kernels."""
+reference's own layer loop against forward(x, edge_index, batch), the default 6/128/3 shape included."""
 import os
 import sys
 
@@ -182,7 +182,8 @@ def test_global_mean_pool_vs_fp64(dev):
 @pytest.mark.parametrize("shape", [(8, 96, 4), (6, 128, 3)], ids=SID)
 def test_reference_layer_loop_reproduces_forward(dev, shape):
     """pv_network_gnn.py:53-64 written out by the caller: relu(layer(x, ei)) over gcn_layers, global_mean_pool, the heads as
-    torch modules.  For 6/128/3 net.forward runs the fused kernels, so this cross-checks the new primitives against them."""
+    torch modules, against net.forward at a non-default shape and at the default 6/128/3 (the same primitives, composed by the
+    caller layer by layer)."""
     from alphaquoridorgnn_amd.pv_network_gnn import global_mean_pool
     net = _make_net(shape, 209, 7)
     assert net.fused == (shape == (6, 128, 3))

@@ -1,5 +1,5 @@
 """Autograd through GraphPolicyValueNetwork.forward(x, edge_index, batch): train-mode forwards record a graph and backward()
-runs the HIP backward of csrc/gcn_graph_grad.hip.  Checked against a torch-autograd fp64 restatement of the network on
+runs the HIP backward composed from the width-generic primitives (csrc/gcn_general.hip).  Checked against a torch-autograd fp64 restatement of the network on
 (x, edge_index, batch) (below; its forward is pinned to oracle.gnn.forward_graph first) and against GNNTrainer's fused
 gradients."""
 import os

@@ -658,7 +658,7 @@ def _assert_rows_close(got, ref, bar, what=""):
 def _pyg_edge_case_batch(seed=8):
     """One ragged batch of the graphs where gcn_norm implementations part ways: duplicate edges (x2, x3), repeated self loops,
     an edgeless graph, single-node graphs (one with two loops), a graph id with no nodes, a hub with 2,100 in-edges; 2,155 nodes
-    in all (neither a multiple of 32 nor of 4: the tails of graph_linear_kernel and graph_gather_kernel run)."""
+    in all (neither a multiple of 32 nor of 4: the tails of gen_linear_kernel and gen_aggregate_kernel run)."""
     rng = np.random.RandomState(seed)
     graphs = []                                          # (graph id, n, local edges [2, E])
     e = rng.randint(0, 7, size=(2, 14))

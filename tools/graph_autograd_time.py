@@ -3,7 +3,7 @@
 
 Prints, in ms per call (HIP events, median of REPS after warm-up):
   hip forward (recording)  -- train-mode forward that keeps H1..H3 (host preparation included: one device-to-host read)
-  hip backward             -- loss.backward() through csrc/gcn_graph_grad.hip
+  hip backward             -- loss.backward() through the width-generic primitives (csrc/gcn_general.hip)
   torch eager fwd+bwd      -- the same network restated in fp32 torch ops on the GPU (index_add_ aggregation), for comparison
 """
 import os

@@ -1,7 +1,7 @@
-"""Times the width-generic graph primitives (csrc/gcn_general.hip) at 4,096 9x9 board graphs (331,776 nodes) on one GPU:
-  1. forward, and forward + backward, of GraphPolicyValueNetwork at a non-default shape (default 6/256/3; SHAPE=F,H,L);
-  2. at 6/128/3, the same layers composed from the new primitives through the C ABI next to aqg_gcn_forward_graph (the fused
-     network's generic path on the VALU graph_linear_kernel), and the two outputs' largest difference.
+"""Times the width-generic graph primitives (csrc/gcn_general.hip) at 4,096 9x9 board graphs (331,776 nodes) on one GPU: forward,
+and forward + backward, of GraphPolicyValueNetwork at a non-default shape (default 6/256/3; SHAPE=F,H,L).  The default 6/128/3
+shape runs the same primitives: tools/graph_autograd_time.py times it (profiles/graph_path_unify_ab.log holds its last
+comparison with the fixed-width kernels it replaced).
 Prints one line per measurement (median of REPS timed calls after WARMUP)."""
 import os
 import sys
@@ -70,39 +70,6 @@ def main():
         p, v = net(x, ei, batch)
         (p.sum() + v.sum()).backward()
     print(f"  non-default train forward + backward             {timed(fwd_bwd):8.3f} ms")
-
-    # 6/128/3: the C ABI primitives against aqg_gcn_forward_graph on the same prepared graph
-    lib = _lib.load()
-    ref = P.GraphPolicyValueNetwork().to(dev).eval()
-    ptr, src, w, gptr, G = P.GraphPolicyValueNetwork._prepare_graph(x, ei, batch)
-    pf = [P._param(p, dev) for _, p in ref._ordered_params()]
-    n, A = x.shape[0], 209
-    f32 = dict(dtype=torch.float32, device=dev)
-    w0, w1, pooled = torch.empty((n, 128), **f32), torch.empty((n, 128), **f32), torch.empty((G, 128), **f32)
-    logits, policy, vpre, value = torch.empty((G, A), **f32), torch.empty((G, A), **f32), torch.empty((G,), **f32), torch.empty((G,), **f32)
-    packed = ref.packed_weights(dev)
-
-    def fused_generic():
-        _lib.check(lib.aqg_gcn_forward_graph(6, A, _lib.ptr(x), n, _lib.ptr(ptr), _lib.ptr(src), _lib.ptr(w), _lib.ptr(gptr), G,
-                                             _lib.ptr(packed), _lib.ptr(w0), _lib.ptr(w1), _lib.ptr(pooled), _lib.ptr(logits),
-                                             _lib.ptr(policy), _lib.ptr(vpre), _lib.ptr(value), _lib.stream_ptr(dev)), "forward_graph")
-
-    def primitives():
-        return P._general_forward(lib, dev, ref, x, (ptr, src, w), gptr, G, pf)
-
-    def linears_only():
-        h = x
-        for l in range(3):
-            h = P._linear(lib, dev, h, pf[2 * l])
-
-    print(f"  6/128/3 aqg_gcn_forward_graph (VALU linear)      {timed(fused_generic):8.3f} ms")
-    print(f"  6/128/3 gcn_general primitives (MFMA linear)     {timed(primitives):8.3f} ms")
-    print(f"  6/128/3 the three MFMA linear maps alone         {timed(linears_only):8.3f} ms")
-    fused_generic()
-    got = primitives()
-    torch.cuda.synchronize()
-    print(f"  6/128/3 max |logits diff| {float((got[2] - logits).abs().max()):.3g}, max |value_pre diff| "
-          f"{float((got[3] - vpre).abs().max()):.3g}")
 
 
 if __name__ == "__main__":
