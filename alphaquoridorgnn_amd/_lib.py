@@ -147,6 +147,13 @@ SIGNATURES = {
     "aqg_engine_finish_move": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_engine_set_roots": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_engine_root_visits": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp, _vp, _vp]),
+    "aqg_engine_root_states72": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
+    "aqg_engine_apply_actions": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
+    "aqg_agent_random": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp, _c.c_int, _c.c_uint64, _vp, _vp]),
+    "aqg_playouts": (_c.c_int, [_c.c_int, _vp, _c.c_int, _c.c_int, _vp, _c.c_int, _c.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "aqg_agent_mcts_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "aqg_agent_mcts": (_c.c_int, [_c.c_int, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _c.c_int, _c.c_uint64, _vp, _c.c_size_t,
+                                  _vp, _vp, _vp, _vp, _vp, _vp]),
     "aqg_gcn_train_step": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _c.c_int, _vp]),
     "aqg_gcn_train_steps": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _vp]),
     "aqg_gcn_train_fallbacks": (_c.c_longlong, [_c.c_int]),

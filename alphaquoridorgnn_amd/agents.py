@@ -5,10 +5,19 @@ of the game state that returns an action (agents.py:1-4).  The rules they walk -
 shortest path -- come from the host build of the SAME rule header the GPU kernels compile (csrc/host_agents.cpp over
 csrc/quoridor_core.hpp, inside libaqgnn_hip.so), so no GPU launch per call and no second copy of the rules.
 The random streams are consumed exactly like the reference's: `random.randint` once per random move (agents.py:17).
+
+The *_batch functions serve many states per call -- what a match of a network against a baseline agent asks for every ply
+(evaluate_agents.BatchedAgentMatch): random moves, random playouts and the rollout MCTS on HIP kernels (csrc/agents.hip, one
+wavefront per state; GPU required), alpha-beta on the native host search from a thread pool.  The kernels cannot replay Python's
+`random` stream; their draws come from a caller-supplied table of uniforms or from the counter-based generator `draw_uniforms`
+mirrors (include/aqgnn.h).  The single-state functions above them are untouched.
 """
 import ctypes
+import functools
 import math
+import os
 import random
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -149,6 +158,199 @@ def mcts_action(state, evaluations=100):
         tree.simulate()
     visits = tree.n[tree.first[0]:tree.first[0] + tree.count[0]]
     return _legal(state)[argmax(visits)]
+
+
+# ------------------------------------------------------------------ batched agents (csrc/agents.hip, include/aqgnn.h)
+_MASK64 = (1 << 64) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def _mix64(z):
+    """The splitmix64 finaliser on numpy uint64 (wrapping arithmetic)."""
+    with np.errstate(over="ignore"):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def draw_uniforms(seed, b, n):
+    """The first n draws of state / game b of a call seeded with `seed`: float64 in [0, 1), a pure function of (seed, b, i) -- the
+    generator the kernels use when no table is given (include/aqgnn.h):
+    key = mix(seed + G (b + 1)); u_i = (mix(key + G (i + 1)) >> 11) 2^-53."""
+    key = _mix64(np.uint64((int(seed) + _GOLDEN * (int(b) + 1)) & _MASK64))
+    with np.errstate(over="ignore"):
+        z = _mix64(key + np.uint64(_GOLDEN) * np.arange(1, int(n) + 1, dtype=np.uint64))
+    return (z >> np.uint64(11)).astype(np.float64) * (2.0 ** -53)
+
+
+def default_threads():
+    """Threads of the alpha-beta pool: the CPUs this process may run on, at most 16 (never the machine's CPU count)."""
+    return max(1, min(16, len(os.sched_getaffinity(0))))
+
+
+def _records(states72):
+    """[B,72] uint8 records from an array, a tensor, or a sequence of States / records (host or device, as given)."""
+    import torch
+    if isinstance(states72, torch.Tensor):
+        return states72.to(torch.uint8).reshape(-1, 72)
+    if isinstance(states72, np.ndarray):
+        return np.ascontiguousarray(states72, dtype=np.uint8).reshape(-1, 72)
+    return np.stack([_rec(s) for s in states72]).reshape(-1, 72) if len(states72) else np.zeros((0, 72), np.uint8)
+
+
+def _device_batch(states72, device):
+    import torch
+    dev = _lib.require_gpu(device)
+    recs = _records(states72)
+    d = (recs if isinstance(recs, torch.Tensor) else torch.from_numpy(recs)).to(dev).contiguous()
+    if d.shape[0] == 0:
+        raise ValueError("no states")
+    return dev, d, int(d[0, 70].item())
+
+
+def _draw_source(uniforms, B, dev):
+    """(table tensor or None, stride) of a call.  uniforms: None = the generator; else float64 [B, n], row b = the draws of state b."""
+    import torch
+    if uniforms is None:
+        return None, 0
+    u = torch.as_tensor(np.asarray(uniforms, dtype=np.float64) if not isinstance(uniforms, torch.Tensor) else uniforms,
+                        dtype=torch.float64).to(dev).contiguous()
+    if u.dim() == 1:
+        u = u.view(B, -1)
+    if u.dim() != 2 or u.shape[0] != B:
+        raise ValueError(f"uniforms must be [B, n] with B = {B}, got {tuple(u.shape)}")
+    return u, int(u.shape[1])
+
+
+def _check_draws(draws, stride, what):
+    m = int(draws.max().item()) if draws.numel() else 0
+    if m > stride:
+        raise ValueError(f"{what}: a state consumed {m} draws, the uniforms table holds {stride} per state")
+
+
+def random_action_device(states, N, seed=0, uniforms=None):
+    """aqg_agent_random on device records [B,72]: int32 [B] device tensor, -1 where a state has no legal action."""
+    import torch
+    dev = states.device
+    B = int(states.shape[0])
+    u, stride = _draw_source(uniforms, B, dev)
+    out = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().aqg_agent_random(N, _lib.ptr(states), B, _lib.ptr(u), stride, int(seed) & _MASK64, _lib.ptr(out),
+                                            _lib.stream_ptr(dev)), "aqg_agent_random")
+    return out
+
+
+def random_action_batch(states72, seed=0, uniforms=None, device=None):
+    """random_action for every state at once: legal_actions()[min(count - 1, int(u * count))] with one draw u per state -- from
+    `uniforms` ([B] or [B,1] float64) or from draw_uniforms(seed, b, 1).  Returns int32 [B] (numpy), -1 = no legal action."""
+    dev, d, N = _device_batch(states72, device)
+    return random_action_device(d, N, seed, uniforms).cpu().numpy()
+
+
+def playout_batch(states72, seed=0, uniforms=None, return_final=False, device=None):
+    """playout() from every state at once (aqg_playouts): (value, plies, draws) int32 [B] numpy arrays -- the value from the START
+    state's mover's view, the moves played, the draws consumed -- and the final records uint8 [B,72] with return_final.  Draws:
+    row b of `uniforms` [B, n] in order, or draw_uniforms(seed, b, .)."""
+    import torch
+    dev, d, N = _device_batch(states72, device)
+    B = int(d.shape[0])
+    u, stride = _draw_source(uniforms, B, dev)
+    value, plies, draws = (torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(3))
+    final = torch.empty((B, 72), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().aqg_playouts(N, _lib.ptr(d), B, board_params(N)[1], _lib.ptr(u), stride, int(seed) & _MASK64,
+                                        _lib.ptr(value), _lib.ptr(plies), _lib.ptr(draws), _lib.ptr(final), _lib.stream_ptr(dev)),
+               "aqg_playouts")
+    if u is not None:
+        _check_draws(draws, stride, "playout_batch")
+    out = (value.cpu().numpy(), plies.cpu().numpy(), draws.cpu().numpy())
+    return out + (final.cpu().numpy(),) if return_final else out
+
+
+MCTS_MAX_EVALUATIONS = 2048     # AQG_AGENT_MCTS_MAX_EVALUATIONS: the table below is (evaluations + 1)^2 doubles, 32 MiB at the cap
+
+
+@functools.lru_cache(maxsize=4)
+def explore_table(evaluations):
+    """UCB1's exploration term 2 * (2 * log(t) / n) ** 0.5 for 1 <= n <= t <= evaluations, as CPython evaluates the reference's
+    expression (agents.py:196), float64 [(evaluations + 1), (evaluations + 1)] indexed [t][n]: the kernel looks it up instead of
+    calling a log and a pow of its own, which are not the host's bit for bit."""
+    E = int(evaluations)
+    if not 0 <= E <= MCTS_MAX_EVALUATIONS:
+        raise ValueError(f"evaluations must be 0..{MCTS_MAX_EVALUATIONS}, got {E}")
+    out = np.zeros((E + 1, E + 1), dtype=np.float64)
+    for t in range(1, E + 1):
+        lt = math.log(t)
+        for n in range(1, t + 1):
+            out[t, n] = 2 * (2 * lt / n) ** 0.5
+    return out
+
+
+_explore_dev = {}
+
+
+def mcts_action_device(states, N, evaluations=100, seed=0, uniforms=None):
+    """aqg_agent_mcts on device records [B,72]: (action i32 [B], visits i32 [B,MAX_LEGAL], actions u8 [B,MAX_LEGAL], count i32 [B],
+    draws i32 [B]) device tensors."""
+    import torch
+    dev = states.device
+    lib = _lib.load()
+    B, E = int(states.shape[0]), int(evaluations)
+    u, stride = _draw_source(uniforms, B, dev)
+    key = (E, str(dev))
+    if key not in _explore_dev:
+        while len(_explore_dev) >= 4:                      # a few evaluation counts at most stay resident
+            _explore_dev.pop(next(iter(_explore_dev)))
+        _explore_dev[key] = torch.from_numpy(explore_table(E)).to(dev).contiguous()
+    ws = torch.empty((int(lib.aqg_agent_mcts_workspace_bytes(N, B, E)),), dtype=torch.uint8, device=dev)
+    action, count, draws = (torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(3))
+    visits = torch.empty((B, _lib.MAX_LEGAL), dtype=torch.int32, device=dev)
+    actions = torch.empty((B, _lib.MAX_LEGAL), dtype=torch.uint8, device=dev)
+    _lib.check(lib.aqg_agent_mcts(N, _lib.ptr(states), B, E, board_params(N)[1], _lib.ptr(_explore_dev[key]), _lib.ptr(u), stride,
+                                  int(seed) & _MASK64, _lib.ptr(ws), ws.numel(), _lib.ptr(action), _lib.ptr(visits), _lib.ptr(actions),
+                                  _lib.ptr(count), _lib.ptr(draws), _lib.stream_ptr(dev)), "aqg_agent_mcts")
+    ws.record_stream(torch.cuda.current_stream(dev))
+    return action, visits, actions, count, draws
+
+
+def mcts_action_batch(states72, evaluations=100, seed=0, uniforms=None, return_visits=False, device=None):
+    """mcts_action for every state at once (aqg_agent_mcts; the semantics of _Tree): int32 [B] actions (numpy, -1 = no legal
+    action); with return_visits also the root children's (visits i32 [B,MAX_LEGAL], actions u8 [B,MAX_LEGAL], count i32 [B]) in the
+    layout of aqg_engine_root_visits.  Draws of state b are consumed in evaluation order, one per random move of each playout: row b
+    of `uniforms` [B, n], or draw_uniforms(seed, b, .)."""
+    dev, d, N = _device_batch(states72, device)
+    u, stride = _draw_source(uniforms, int(d.shape[0]), dev)
+    action, visits, actions, count, draws = mcts_action_device(d, N, evaluations, seed, u)
+    if u is not None:
+        _check_draws(draws, stride, "mcts_action_batch")
+    if return_visits:
+        return action.cpu().numpy(), visits.cpu().numpy(), actions.cpu().numpy(), count.cpu().numpy()
+    return action.cpu().numpy()
+
+
+def alpha_beta_action_batch(states72, max_depth=2, threads=None):
+    """alpha_beta_action for every state, in input order, on the native host search from a pool of `threads` threads (default
+    default_threads(); ctypes releases the GIL during a search).  Returns int32 [B] (numpy), -1 = no action."""
+    import torch
+    recs = _records(states72)
+    if isinstance(recs, torch.Tensor):
+        recs = recs.cpu().numpy()
+    recs = np.ascontiguousarray(recs, dtype=np.uint8)
+    lib = _lib.load()
+    threads = default_threads() if threads is None else max(1, int(threads))
+
+    def one(i):
+        r = recs[i]
+        N = int(r[70])
+        walls, draw = board_params(N)
+        return int(lib.aqg_host_alpha_beta_action(N, r.ctypes.data_as(ctypes.c_void_p), draw, draw // 2 - walls, int(max_depth)))
+
+    n = recs.shape[0]
+    if threads == 1 or n <= 1:
+        out = [one(i) for i in range(n)]
+    else:
+        with ThreadPoolExecutor(max_workers=min(threads, n)) as pool:
+            out = list(pool.map(one, range(n)))
+    return np.asarray(out, dtype=np.int32)
 
 
 if __name__ == '__main__':

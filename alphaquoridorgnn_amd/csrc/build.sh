@@ -16,7 +16,7 @@ else
 fi
 objs=()
 pids=()
-for f in legal_mask gcn_forward gcn_general gcn_boards_general gcn_train gcn_train_general cnn_forward cnn_train mcts capi; do
+for f in legal_mask gcn_forward gcn_general gcn_boards_general gcn_train gcn_train_general cnn_forward cnn_train mcts agents capi; do
   $HIPCC $FLAGS -c $f.hip -o "${OBJDIR}/aqg_$f.o" &
   pids+=($!)
   objs+=("${OBJDIR}/aqg_$f.o")

@@ -232,6 +232,51 @@ int aqg_engine_root_visits(const aqg_engine* e, int32_t* visits, uint8_t* action
     return engine_root_visits(*e, visits, actions, count, (hipStream_t)stream);
 }
 
+int aqg_engine_root_states72(const aqg_engine* e, uint8_t* out72, void* stream) {
+    if (!e || !out72) return fail("aqg_engine_root_states72: null argument");
+    return engine_root_states72(*e, out72, (hipStream_t)stream);
+}
+int aqg_engine_apply_actions(const aqg_engine* e, const int32_t* actions, void* stream) {
+    if (!e || !actions) return fail("aqg_engine_apply_actions: null argument");
+    return engine_apply_actions(*e, actions, (hipStream_t)stream);
+}
+
+static int check_draw_source(const char* what, const double* uniforms, int uniforms_stride) {
+    if (uniforms && uniforms_stride < 0) return fail(what, "negative uniforms_stride");
+    return 0;
+}
+int aqg_agent_random(int board_size, const uint8_t* states72, int B, const double* uniforms, int uniforms_stride, uint64_t seed,
+                     int32_t* actions, void* stream) {
+    const char* what = "aqg_agent_random";
+    if (B < 0 || (B > 0 && (!states72 || !actions))) return fail(what, "bad arguments");
+    if (int r = check_draw_source(what, uniforms, uniforms_stride)) return r;
+    return launch_agent_random(board_size, states72, B, uniforms, uniforms_stride, seed, actions, (hipStream_t)stream);
+}
+int aqg_playouts(int board_size, const uint8_t* states72, int B, int plies_for_draw, const double* uniforms, int uniforms_stride,
+                 uint64_t seed, int32_t* value, int32_t* plies, int32_t* draws, uint8_t* final72, void* stream) {
+    const char* what = "aqg_playouts";
+    if (B < 0 || (B > 0 && (!states72 || !value))) return fail(what, "bad arguments");
+    if (plies_for_draw < 0 || plies_for_draw > 65535) return fail(what, "plies_for_draw must be 0..65535");
+    if (int r = check_draw_source(what, uniforms, uniforms_stride)) return r;
+    return launch_playouts(board_size, states72, B, plies_for_draw, uniforms, uniforms_stride, seed, value, plies, draws, final72,
+                           (hipStream_t)stream);
+}
+size_t aqg_agent_mcts_workspace_bytes(int board_size, int B, int evaluations) {
+    (void)board_size;
+    return agent_mcts_workspace_bytes(B, evaluations);
+}
+int aqg_agent_mcts(int board_size, const uint8_t* states72, int B, int evaluations, int plies_for_draw, const double* explore,
+                   const double* uniforms, int uniforms_stride, uint64_t seed, void* workspace, size_t workspace_bytes,
+                   int32_t* action, int32_t* visits, uint8_t* actions, int32_t* count, int32_t* draws, void* stream) {
+    const char* what = "aqg_agent_mcts";
+    if (B < 0 || (B > 0 && (!states72 || !action || !explore || !workspace))) return fail(what, "bad arguments");
+    if (evaluations < 0 || evaluations > AQG_AGENT_MCTS_MAX_EVALUATIONS) return fail(what, "evaluations must be 0..AQG_AGENT_MCTS_MAX_EVALUATIONS (2048)");
+    if (plies_for_draw < 0 || plies_for_draw > 65535) return fail(what, "plies_for_draw must be 0..65535");
+    if (int r = check_draw_source(what, uniforms, uniforms_stride)) return r;
+    return launch_agent_mcts(board_size, states72, B, evaluations, plies_for_draw, explore, uniforms, uniforms_stride, seed, workspace,
+                             workspace_bytes, action, visits, actions, count, draws, (hipStream_t)stream);
+}
+
 int aqg_gcn_train_step(const aqg_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
                        void* stream) {
     if (!t || mode < 0 || mode > 2) return fail("aqg_gcn_train_step: bad argument");

@@ -82,6 +82,19 @@ int engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st
 int engine_move(const aqg_engine& e, const double* uniforms, hipStream_t st);
 int engine_search(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
 int engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st);
+int engine_refill(const aqg_engine& e, hipStream_t st);
+
+// ---- agents.hip
+int launch_agent_random(int N, const uint8_t* states72, int B, const double* uniforms, int stride, uint64_t seed, int32_t* actions,
+                        hipStream_t st);
+int launch_playouts(int N, const uint8_t* states72, int B, int plies_for_draw, const double* uniforms, int stride, uint64_t seed,
+                    int32_t* value, int32_t* plies, int32_t* draws, uint8_t* final72, hipStream_t st);
+size_t agent_mcts_workspace_bytes(int B, int evaluations);
+int launch_agent_mcts(int N, const uint8_t* states72, int B, int evaluations, int plies_for_draw, const double* explore,
+                      const double* uniforms, int stride, uint64_t seed, void* workspace, size_t workspace_bytes, int32_t* action,
+                      int32_t* visits, uint8_t* actions, int32_t* count, int32_t* draws, hipStream_t st);
+int engine_root_states72(const aqg_engine& e, uint8_t* out72, hipStream_t st);
+int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_t st);
 
 // ---- gcn_train.hip
 extern int g_train_fused;

@@ -1393,6 +1393,12 @@ int engine_search(const aqg_engine& e, const uint8_t* roots72, hipStream_t st) {
     }
 }
 
+// the slot refill alone, for a move that was applied rather than searched (csrc/agents.hip)
+int engine_refill(const aqg_engine& e, hipStream_t st) {
+    hipLaunchKernelGGL(engine_refill_kernel, dim3(1), dim3(1024), 0, st, e);
+    return check_launch("engine_refill_kernel");
+}
+
 int engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st) {
     const dim3 grid((e.num_games + 3) / 4), block(256);
     switch (e.board_size) {

@@ -218,6 +218,22 @@ class BatchedSelfPlay:
             _lib.check(self.lib.aqg_engine_move(ctypes.byref(self.e), _lib.ptr(uniforms), self._stream()), "aqg_engine_move")
         self.moves_done += 1
 
+    # ------------------------------------------------------------------ moves the engine does not search (evaluate_agents.py)
+    def root_states72(self):
+        """The current position of every slot: uint8 [G,72] device tensor (rows of inactive slots: valid records, content
+        unspecified)."""
+        out = torch.empty((self.G, 72), dtype=torch.uint8, device=self.dev)
+        _lib.check(self.lib.aqg_engine_root_states72(ctypes.byref(self.e), _lib.ptr(out), self._stream()), "aqg_engine_root_states72")
+        return out
+
+    def apply_actions(self, actions):
+        """Play actions[g] (int32 [G]; -1 = this active slot has no legal action: its game ends as a draw) in every active slot
+        without a search: history row, next(), terminal handling exactly as move() does them."""
+        actions = torch.as_tensor(actions, dtype=torch.int32).to(self.dev).contiguous().view(self.G)
+        self._applied = actions  # keep alive until the stream has consumed it
+        _lib.check(self.lib.aqg_engine_apply_actions(ctypes.byref(self.e), _lib.ptr(actions), self._stream()), "aqg_engine_apply_actions")
+        self.moves_done += 1
+
     # ------------------------------------------------------------------ external evaluator (prior_mode 2)
     def _leaf_states(self, idx):
         """game_logic.State objects of the leaves of games `idx` (24-byte packed records: wall masks, pawns, plies)."""

@@ -4,7 +4,8 @@
 
 with the GNN or (--network cnn) the reference's residual CNN: the parameter update dispatches on what best.pth holds.
 
-(The reference's commented-out evaluate_best_player stage -- CPU baseline agents, SURVEY 8f.4 -- is not part of this build.)
+The reference's commented-out evaluate_best_player stage (the best network against the random, alpha-beta and rollout-MCTS agents,
+evaluate_agents.py) is opt-in: --baseline-games K plays K games per agent after each cycle's evaluation stage, on rank 0.
 """
 from . import constants
 from . import distributed as aqd
@@ -86,10 +87,29 @@ def _evaluate_once():
     return promoted
 
 
-def train_cycle(num_cycles=None, hidden_dim=None, num_gcn_layers=None, network="gnn", num_filters=None, num_residual_blocks=None):
+def _baseline_once(games):
+    """evaluate_best_player(games) on rank 0, inside a single-rank stage like _evaluate_once; the other ranks wait.  Returns the
+    dict of average points on rank 0, None elsewhere."""
+    from .evaluate_agents import evaluate_best_player
+    dist, on, rank = _dist()
+    tag = aqd.next_tag("baseline")
+    result = None
+    if rank == 0:
+        with aqd.single_rank_stage(tag):
+            result = evaluate_best_player(games)
+    else:
+        aqd.wait_for_rank0(tag)
+    if on:
+        dist.barrier()
+    return result
+
+
+def train_cycle(num_cycles=None, hidden_dim=None, num_gcn_layers=None, network="gnn", num_filters=None, num_residual_blocks=None,
+                baseline_games=0, baseline=None):
     """Run the cycle; returns, per iteration, whether `latest` was promoted to `best`.  network 'gnn' (hidden_dim / num_gcn_layers)
     or 'cnn' (num_filters / num_residual_blocks) shapes the best.pth written when none exists; every stage then follows the
-    network and shape best.pth holds."""
+    network and shape best.pth holds.  baseline_games K > 0: after each cycle's evaluation stage rank 0 plays best.pth against the
+    baseline agents, K games each (evaluate_agents.evaluate_best_player), and appends the dict to the list `baseline`."""
     if network not in ("gnn", "cnn"):
         raise ValueError("network must be 'gnn' or 'cnn'")
     total = NUM_TRAIN_CYCLE if num_cycles is None else int(num_cycles)
@@ -109,18 +129,18 @@ def train_cycle(num_cycles=None, hidden_dim=None, num_gcn_layers=None, network="
             else:
                 outcome = stage()
         promoted.append(bool(outcome))
+        if baseline_games and baseline_games > 0:
+            if rank == 0:
+                print(f'\n[cycle {cycle}/{total}] evaluation against the baseline agents')
+            points = _baseline_once(int(baseline_games))
+            if baseline is not None:
+                baseline.append(points)
     return promoted
 
 
-def main(argv=None):
-    """`python -m alphaquoridorgnn_amd.train_cycle` -- also the per-rank program of
-    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P -m
-    alphaquoridorgnn_amd.train_cycle`: every rank binds to GPU LOCAL_RANK and joins the RCCL group (distributed.init_from_env)
-    before anything touches a device; self-play is sharded over the ranks, rank 0 trains / evaluates (module docstrings)."""
+def _parser():
+    """The command line of main()."""
     import argparse
-    import json
-    import os
-    from . import evaluate_network as en, pv_mcts, self_play as sp, train_network as tn
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("--cycles", type=int, default=None, help="training cycles (default NUM_TRAIN_CYCLE = 1000, train_cycle.py:18)")
     ap.add_argument("--games", type=int, default=None, help="self-play games per generation over ALL ranks (default SP_GAME_COUNT)")
@@ -138,7 +158,21 @@ def main(argv=None):
                     help="filters of the CNN created when no best.pth exists (default NUM_FILTERS = 128)")
     ap.add_argument("--num-residual-blocks", type=int, default=None,
                     help="residual blocks of the CNN created when no best.pth exists (default NUM_RESIDUAL_BLOCKS = 16)")
-    args = ap.parse_args(argv)
+    ap.add_argument("--baseline-games", type=int, default=0,
+                    help="games per baseline agent (random, alpha-beta, rollout MCTS) best.pth plays after each cycle's evaluation "
+                         "stage, on rank 0 (default 0: no such stage)")
+    return ap
+
+
+def main(argv=None):
+    """`python -m alphaquoridorgnn_amd.train_cycle` -- also the per-rank program of
+    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P -m
+    alphaquoridorgnn_amd.train_cycle`: every rank binds to GPU LOCAL_RANK and joins the RCCL group (distributed.init_from_env)
+    before anything touches a device; self-play is sharded over the ranks, rank 0 trains / evaluates (module docstrings)."""
+    import json
+    import os
+    from . import evaluate_network as en, pv_mcts, self_play as sp, train_network as tn
+    args = _parser().parse_args(argv)
     rank, world = aqd.init_from_env()
     if args.games is not None:
         sp.SP_GAME_COUNT = args.games
@@ -149,16 +183,21 @@ def main(argv=None):
     if args.eval_games is not None:
         en.EN_GAME_COUNT = args.eval_games
     try:
+        baseline = []
         promoted = train_cycle(args.cycles, hidden_dim=args.hidden_dim, num_gcn_layers=args.num_gcn_layers, network=args.network,
-                               num_filters=args.num_filters, num_residual_blocks=args.num_residual_blocks)
+                               num_filters=args.num_filters, num_residual_blocks=args.num_residual_blocks,
+                               baseline_games=args.baseline_games, baseline=baseline)
         if args.result_dir:
             import hashlib
             with open(constants.PV_NETWORK_PATH + 'latest.pth', 'rb') as f:
                 digest = hashlib.sha256(f.read()).hexdigest()
             import torch
             with open(os.path.join(args.result_dir, f"train_cycle.rank{rank}.json"), "w") as f:
-                json.dump({"rank": rank, "world": world, "promoted": promoted, "latest_sha256": digest,
-                           "device": torch.cuda.current_device()}, f)
+                result = {"rank": rank, "world": world, "promoted": promoted, "latest_sha256": digest,
+                          "device": torch.cuda.current_device()}
+                if args.baseline_games > 0:
+                    result["baseline"] = baseline
+                json.dump(result, f)
     except BaseException:
         aqd.shutdown(ok=False)                      # no barrier on the way out of an exception: the other ranks may never reach one
         raise

@@ -374,6 +374,66 @@ int aqg_engine_search(const aqg_engine* e_host, const uint8_t* root_states72, vo
 /* Read back the root's children after a search: visits [G,AQG_MAX_LEGAL] i32, actions [G,AQG_MAX_LEGAL] u8, count [G]. */
 int aqg_engine_root_visits(const aqg_engine* e_host, int32_t* visits, uint8_t* actions, int32_t* count, void* stream);
 
+/* Matches against an agent the engine does not search for (evaluate_agents.py; additive to ABI 14, csrc/agents.hip).
+ * aqg_engine_root_states72: out72 [G,72] = the current position of every slot as a state72 record (the rows of inactive slots hold
+ *   whatever position the slot was left in: valid bytes, unspecified content).
+ * aqg_engine_apply_actions: the transition half of aqg_engine_move with caller-given actions [G] i32.  For every active slot with
+ *   actions[g] >= 0: the history row (state72, the action, a visit row that is zero except 1 at the action), next(), game_plies + 1,
+ *   and the lose / draw / z / counters / game_active handling of a searched move (and its slot refill when quota > num_games).
+ *   actions[g] < 0 on an active slot is the dead end: the game ends as a draw and counters[2] is incremented.  The action is trusted
+ *   to be legal, as State.next trusts it (one that is not an action of the board at all leaves the slot untouched).  A launch of
+ *   its own: what aqg_engine_move captures and replays does not change, and the next searched move starts from the new root with
+ *   a fresh tree, as every move does. */
+int aqg_engine_root_states72(const aqg_engine* e_host, uint8_t* out72, void* stream);
+int aqg_engine_apply_actions(const aqg_engine* e_host, const int32_t* actions, void* stream);
+
+/* ------------------------------------------------------------------ baseline agents in batch (agents.py; additive to ABI 14)
+ *
+ * The reference's random and rollout-MCTS agents (agents.py:14-18, :111-214) for B states at once, one wavefront per state
+ * (csrc/agents.hip).  Device pointers, stream-ordered, no allocation, no host synchronisation, no atomics: two runs give identical
+ * bytes.  Every device loop ends on an integer cap computed from the arguments; a position without a legal action inside a playout
+ * ends that playout as a draw.
+ *
+ * Random draws.  Every random choice is index = min(count - 1, floor(u * count)) over legal_actions() in the reference's order, for
+ * a float64 u in [0, 1).  u comes from one of two sources:
+ *   uniforms != NULL: a table [B, uniforms_stride] f64; uniforms[b][i] is the i-th draw of state / game b within the call.  A draw
+ *     past the end of a row is 0.0 (never a read out of bounds); the reported draw count tells the caller whether that happened.
+ *   uniforms == NULL: the counter-based generator u = f(seed, b, i), stateless -- the result does not depend on launch geometry,
+ *     wave scheduling or batch size.  With mix(z) the splitmix64 finaliser
+ *         z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^ (z >> 31)
+ *     and G = 0x9E3779B97F4A7C15, all in 64-bit wrapping arithmetic:
+ *         key = mix(seed + G * (b + 1));   f(seed, b, i) = (mix(key + G * (i + 1)) >> 11) * 2^-53.
+ *     agents.draw_uniforms(seed, b, n) is the same function in numpy.
+ * The reference draws with Python's random.randint; that stream is not reproduced.
+ *
+ * aqg_agent_random: actions[b] = legal_actions()[index] for one draw, or -1 (and no draw) where the state has no legal action.
+ * aqg_playouts: playout() of agents.py:111-121 from each state: value [B] i32 = -1 / 0 / +1 from the point of view of the mover of
+ *   the START state, plies [B] = moves played, draws [B] = draws consumed (one per move), final72 [B,72] = the position the playout
+ *   ended in (plies, draws, final72 may be NULL).  A state that is already lost / drawn returns at once with 0 draws.  At most
+ *   plies_for_draw - plies_played moves are played.
+ * aqg_agent_mcts: mcts_action() of agents.py:130-214 for B roots, games in parallel, the evaluations of a game in order.  The root is
+ *   expanded before the first evaluation; a descent takes the first child with n == 0, else the FIRST maximum of UCB1; a childless
+ *   node gets a playout and is expanded on the visit that makes its n 10; a terminal node scores -1 (lost) or 0 (drawn) without a
+ *   playout; the backup negates the value per ply; the answer is the first most-visited root child.  w is an integer.  UCB1 is
+ *   float64, (double)(-w) / n + explore[t][n], with no contraction.  explore [(evaluations + 1)^2] f64 is filled by the HOST:
+ *   explore[t * (evaluations + 1) + n] = 2 * (2 * log(t) / n) ** 0.5 for 1 <= n <= t <= evaluations exactly as the reference's
+ *   CPython evaluates it (agents.py:196) -- the C library's log and pow(x, 0.5), neither of which the device reproduces bit for
+ *   bit (pow(x, 0.5) differs from the correctly rounded sqrt(x) for 53 of the 80,200 pairs up to 400); t is the sum of the
+ *   children's visit counts; evaluations <= AQG_AGENT_MCTS_MAX_EVALUATIONS.  Draws of game b are consumed in evaluation order, one per random move inside each playout.
+ *   action [B] i32 (-1 = no legal action); visits [B,AQG_MAX_LEGAL] i32, actions [B,AQG_MAX_LEGAL] u8 (0xFF past the count) and
+ *   count [B] i32 = the root's children in the layout of aqg_engine_root_visits; draws [B] = draws consumed (the last four may be
+ *   NULL).  workspace: aqg_agent_mcts_workspace_bytes(board_size, B, evaluations) bytes hold the trees: a game expands its root and
+ *   at most evaluations / 10 other nodes, so 1 + (1 + evaluations / 10) * AQG_MAX_LEGAL nodes of 48 bytes bound it. */
+#define AQG_AGENT_MCTS_MAX_EVALUATIONS 2048 /* the explore table is (evaluations + 1)^2 doubles: 32 MiB at the cap */
+int aqg_agent_random(int board_size, const uint8_t* states72, int B, const double* uniforms, int uniforms_stride, uint64_t seed,
+                     int32_t* actions, void* stream);
+int aqg_playouts(int board_size, const uint8_t* states72, int B, int plies_for_draw, const double* uniforms, int uniforms_stride,
+                 uint64_t seed, int32_t* value, int32_t* plies, int32_t* draws, uint8_t* final72, void* stream);
+size_t aqg_agent_mcts_workspace_bytes(int board_size, int B, int evaluations);
+int aqg_agent_mcts(int board_size, const uint8_t* states72, int B, int evaluations, int plies_for_draw, const double* explore,
+                   const double* uniforms, int uniforms_stride, uint64_t seed, void* workspace, size_t workspace_bytes,
+                   int32_t* action, int32_t* visits, uint8_t* actions, int32_t* count, int32_t* draws, void* stream);
+
 /* ------------------------------------------------------------------ training step (train_network.py:68-95 on the GNN) */
 
 /* One optimisation step on a batch of positions: forward, the reference's losses (CrossEntropyLoss applied to the
