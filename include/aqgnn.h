@@ -249,7 +249,9 @@ int aqg_gcn_forward_boards_general(int board_size, const void* states, int state
  *   pooled [B,F], logits [B,A] and value_pre [B] may be NULL (then they live in the workspace); policy [B,A] is required, value [B]
  *   may be NULL.  active [B] (may be NULL): a board with active[b] != 1 is skipped -- its policy / value rows are not written.
  *   Every board is computed independently of the others: its outputs are bit-identical at any B, position and mask.  workspace:
- *   aqg_cnn_workspace_floats(board_size, num_filters, policy_size, B) floats.  No allocation, no host synchronisation. */
+ *   aqg_cnn_workspace_floats(board_size, num_filters, policy_size, B) floats.  No allocation, no host synchronisation.
+ *   tests/test_cnn_conv_edges.py checks this contract on arbitrary planes (exact integer cases bit for bit at every slab and tile
+ *   edge of num_filters, both limits included); tests/test_featuriser.py checks aqg_gcn_boards_graph alone. */
 #define AQG_CNN_MAX_FILTERS 512
 #define AQG_CNN_MAX_BLOCKS 40
 typedef struct aqg_cnn_net {

@@ -1,0 +1,551 @@
+"""CPU half (no GPU) of two contract tests that call a kernel through the public entry points only:
+
+  * the CNN forward's conv kernel and its packing (csrc/cnn_forward.hip: cnn_conv_kernel, cnn_pack_conv_kernel, cnn_pack_bn_kernel)
+    through CNNNetwork on arbitrary [B,6,N,N] planes -- tests/test_cnn_conv_edges.py is the GPU half;
+  * the board featuriser alone (csrc/gcn_forward.hip: boards_prep_kernel through aqg_gcn_boards_graph) -- tests/test_featuriser.py.
+
+Here live the case lists, the input generators and the float64 references; the tests of this file check the references against an
+independent statement (the stock nn modules in float64, oracle.gnn), check that every exact case stays below 2^24 and every
+featuriser input covers what it claims to, and check aqg_cnn_packed_floats, which is host arithmetic.
+
+Exact cases.  Planes are integers in [-2, 2], conv weights are sparse and ternary, and every BatchNorm is the identity up to an
+integer shift: gamma = 1, running_mean = 0, running_var = 0.5 and eps = 0.5, so var + eps = 1 exactly and the folded scale is 1,
+the folded shift the integer beta (negative in some channels: ReLU clips there).  For every conv the largest
+sum |x| |w| + |shift| + |residual| is asserted to stay below 2^24: every partial sum the kernel can form, in any order, is then an
+integer f32 holds exactly, and so is every activation.  pooled = sum / V is the kernel's single rounding; the reference divides
+the exact integer sum in float64 and rounds to f32, which is the same number: a float64 quotient rounded again to f32 equals the
+correctly rounded f32 quotient whenever the wider format has at least 2 p + 2 = 50 bits (Figueroa 1995), and float64 has 53.  So
+pooled must match bit for bit.  The heads (Linear, softmax, tanh on real weights) are not part of the exact claim."""
+import copy
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+from tests import _util as U                                           # noqa: E402
+
+U32 = 2.0 ** -24                 # unit roundoff of f32
+EXACT_LIMIT = 2 ** 24            # integers up to here are f32
+KS, TILE = 32, 64                # cnn_conv_kernel: input channels per K slab, output channels per workgroup
+B_CROSS = 3
+
+# ---------------------------------------------------------------------------------------------------------------- case lists
+# (F, N, L).  F on either side of every slab edge (32) and tile edge (64), on both the scalar (F % 4 != 0) and the vector path; the
+# scalar path with 2, 3, 4 and 5 slabs (33 / 35, 65 / 66, 127, 129); a tail tile of 1, 2 and 65 columns (65 / 129, 66, 129 = 64 + 65);
+# both limits of check_cnn_net (F = 512, L = 40).
+CROSS_F = [1, 3, 4, 6, 31, 32, 33, 35, 63, 64, 65, 66, 127, 129, 512]
+CROSS_N = [3, 5, 7, 9]
+CROSS = ([(f, n, l) for f in CROSS_F for n in CROSS_N for l in (0, 1)] + [(f, n, 2) for f in (33, 65) for n in CROSS_N]
+         + [(5, 3, 40)])
+# the same shapes with one N per F, for real-valued weights
+CROSS_REAL = ([(f, CROSS_N[i % 4], l) for i, f in enumerate(CROSS_F) for l in (0, 1)] + [(33, 9, 2), (65, 7, 2), (5, 3, 40)])
+PROBE_N = [5, 9]
+PROBE_F = 33
+BN_FOLD = (65, 5, 0)
+MASK_CASE = dict(F=33, L=1, N=7, active=[1, 0, 2, 1, 1])
+FEAT_N = [3, 5, 7, 9]
+FEAT_BATCHES = [1, 2, 257, 1025]
+
+
+def fnl_id(c):
+    return "F%d-N%d-L%d" % tuple(c)
+
+
+def policy_size(N):
+    return N * N + 2 * (N - 1) ** 2
+
+
+# ---------------------------------------------------------------------------------------------------------------- exact networks
+def ternary_weight(rng, cout, cin, nnz):
+    """[cout, cin, 3, 3] in {-1, 0, 1}: `nnz` taps per output channel, and one more per input channel so that every input channel
+    (the ones of a later K slab included) reaches some output."""
+    w = np.zeros((cout, cin * 9), dtype=np.float32)
+    for co in range(cout):
+        at = rng.choice(cin * 9, size=min(nnz, cin * 9), replace=False)
+        w[co, at] = rng.choice(np.array([-1.0, 1.0], dtype=np.float32), size=at.size)
+    for ci in range(cin):
+        w[rng.integers(cout), ci * 9 + rng.integers(9)] = rng.choice(np.array([-1.0, 1.0], dtype=np.float32))
+    return w.reshape(cout, cin, 3, 3)
+
+
+def set_identity_bn(bn, beta):
+    """var + eps = 0.5 + 0.5 = 1 exactly: scale = gamma / sqrt(1) = 1, shift = beta - 0 * 1 = beta."""
+    with torch.no_grad():
+        bn.weight.fill_(1.0)
+        bn.running_mean.zero_()
+        bn.running_var.fill_(0.5)
+        bn.bias.copy_(torch.from_numpy(np.asarray(beta, dtype=np.float32)))
+    bn.eps = 0.5
+
+
+def exact_net(F_, L, N, seed=0, nnz=None):
+    """A CNNNetwork (eval, CPU) whose convs are sparse ternary and whose BatchNorms are integer shifts.  The taps per output channel
+    fall as the depth grows (the density falls with F by itself: the count does not depend on F), so activations stay small."""
+    from alphaquoridorgnn_amd.pv_network_cnn import CNNNetwork
+    rng = np.random.default_rng(7919 * seed + 1000003 * F_ + 101 * N + L)
+    torch.manual_seed(seed + F_ + N + L)
+    net = CNNNetwork(F_, L, board_size=N)
+    if nnz is None:
+        nnz = 6 if L <= 2 else 1
+    for cb in net._convs():
+        cout, cin = cb.conv.weight.shape[:2]
+        with torch.no_grad():
+            cb.conv.weight.copy_(torch.from_numpy(ternary_weight(rng, cout, cin, nnz)))
+        beta = rng.integers(-2, 2, size=cout)
+        if cout > 1:
+            beta[rng.integers(cout)] = -2                # ReLU clips somewhere whatever the draw
+        set_identity_bn(cb.bn, beta)
+    return net.eval()
+
+
+def int_planes(rng, B, N):
+    return rng.integers(-2, 3, size=(B, 6, N, N)).astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------- float64 reference
+def fold_bn(bn):
+    """(scale, shift) as cnn_pack_bn_kernel folds them: float64 on the f32 parameters and the f32 eps, each rounded once to f32.
+    Returned as float64 arrays holding f32 values."""
+    g, b, m, v = (t.detach().numpy().astype(np.float64) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
+    sc = g / np.sqrt(v + np.float64(np.float32(bn.eps)))
+    return sc.astype(np.float32).astype(np.float64), (b - m * sc).astype(np.float32).astype(np.float64)
+
+
+def ref_forward(net, planes, folded=False):
+    """The network on [B,6,N,N] planes in float64, conv by conv with torch.nn.functional.conv2d.  folded = False is the module's
+    own arithmetic (BatchNorm in float64 from the f32 statistics); folded = True is the kernel's statement: the per-channel f32
+    scale / shift of fold_bn and one f32 rounding of sum * scale + shift (the kernel's fmaf), everything else exact.
+    -> dict(pooled_sum [B,F] (the V tiles summed), pooled, logits, policy, value, exact_bound: the largest
+    sum |x| |w| + |shift| + |residual| over all outputs of all convs, terms: the last conv's post-ReLU rows [B,F,V])."""
+    x = torch.from_numpy(np.array(planes, dtype=np.float64))
+    convs = net._convs()
+    bound = 0.0
+    res = None
+    for l, cb in enumerate(convs):
+        w = cb.conv.weight.detach().double()
+        y = F.conv2d(x, w, padding=1)
+        if folded:
+            sc, sh = (torch.from_numpy(a).view(1, -1, 1, 1) for a in fold_bn(cb.bn))
+            v = (y * sc + sh).float().double()
+        else:
+            bn = cb.bn
+            g, b, m, var = (t.detach().double().view(1, -1, 1, 1) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
+            sc = g / torch.sqrt(var + bn.eps)
+            sh = b - m * sc
+            v = (y - m) / torch.sqrt(var + bn.eps) * g + b
+        r = res if (l > 0 and l % 2 == 0) else None
+        mag = F.conv2d(x.abs(), w.abs(), padding=1) * sc.abs() + sh.abs()
+        if r is not None:
+            v = v + r
+            mag = mag + r.abs()
+        bound = max(bound, float(mag.max()))
+        x = torch.relu(v)
+        if l % 2 == 0:
+            res = x                     # the stem's output, then every block's: the next block's residual
+    terms = x.flatten(2)
+    pooled_sum = terms.sum(2)
+    pooled = pooled_sum / terms.shape[2]
+    pw, pb = net.policy_head[1].weight.detach().double(), net.policy_head[1].bias.detach().double()
+    vw, vb = net.value_head[1].weight.detach().double(), net.value_head[1].bias.detach().double()
+    logits = pooled @ pw.T + pb
+    return dict(pooled_sum=pooled_sum.numpy(), pooled=pooled.numpy(), logits=logits.numpy(),
+                policy=torch.softmax(logits, 1).numpy(), value=torch.tanh(pooled @ vw.T + vb).numpy()[:, 0],
+                exact_bound=bound, terms=terms.numpy())
+
+
+def module_fp64(net, planes):
+    """The stock nn modules of a copy of `net` in float64 -> dict(pooled, logits, policy, value)."""
+    m = copy.deepcopy(net).cpu().double().eval()
+    x = torch.from_numpy(np.array(planes, dtype=np.float64))
+    with torch.no_grad():
+        h = m.residual_blocks(torch.relu(m.conv(x)))
+        pooled = m.global_avg_pool(h).flatten(1)
+        logits = m.policy_head[1](pooled)
+        policy, value = m._forward_stock(x)
+    return dict(pooled=pooled.numpy(), logits=logits.numpy(), policy=policy.numpy(), value=value.numpy()[:, 0])
+
+
+def expected_pooled_f32(pooled_sum, V):
+    """float32(sum / V) of an exact integer sum below 2^24 (see the module docstring: no double rounding)."""
+    assert np.array_equal(pooled_sum, np.rint(pooled_sum)) and np.abs(pooled_sum).max(initial=0.0) < EXACT_LIMIT
+    return (pooled_sum / float(V)).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(F_, N, L):
+    """-> (net, planes [3,6,N,N], expected pooled as f32 [3,F], the reference dict).  Computed once per shape and shared."""
+    net = exact_net(F_, L, N)
+    planes = int_planes(np.random.default_rng(31 * F_ + 7 * N + L), B_CROSS, N)
+    with torch.no_grad():
+        ref = ref_forward(net, planes)
+    assert ref["exact_bound"] < EXACT_LIMIT, (F_, N, L, ref["exact_bound"])
+    exp = expected_pooled_f32(ref["pooled_sum"], N * N)
+    exp.setflags(write=False)
+    planes.setflags(write=False)
+    return net, planes, exp, ref
+
+
+# ---------------------------------------------------------------------------------------------------------------- position probes
+def probe_positions(N):
+    """The four corners, the four edge midpoints and the centre, as (row, column)."""
+    m, e = N // 2, N - 1
+    return [(0, 0), (0, e), (e, 0), (e, e), (0, m), (m, 0), (m, e), (e, m), (m, m)]
+
+
+@functools.lru_cache(maxsize=None)
+def probe_case(N, tap, where):
+    """One nonzero weight at `tap` (= 3 ky + kx) of one conv of an exact F = 33, L = 1 network, and nine boards whose planes hold one
+    nonzero element each, at the nine probe positions.  where = "stem": the stem conv's only weight is W[co=32, ci=3, tap] (its
+    output is beta everywhere but for the one tile the probe element reaches, or none when the tap carries it off the board);
+    where = "block": the same in conv_bn1, at W[co=5, ci=32, tap], the second K slab of the scalar path, on the stem's output of
+    generic planes with one probe element added.  The two convs after / around it are generic exact convs, so the tile the
+    element lands on matters to pooled, not only whether it stays on the board.  -> (net, planes, expected pooled f32, ref)"""
+    net = exact_net(PROBE_F, 1, N, seed=100 + tap)
+    rng = np.random.default_rng(1000 * N + 10 * tap + (where == "block"))
+    pos = probe_positions(N)
+    with torch.no_grad():
+        if where == "stem":
+            w = net.conv.conv.weight
+            w.zero_()
+            w[32, 3, tap // 3, tap % 3] = -1.0
+            net.conv.bn.bias[32] = 0.0                   # the landing tile holds (-1) (-3) + 0 = 3, every other tile of the channel 0
+            planes = np.zeros((len(pos), 6, N, N), dtype=np.float32)
+            for b, (r, c) in enumerate(pos):
+                planes[b, 3, r, c] = -3.0
+        else:
+            w = net.residual_blocks[0].conv_bn1.conv.weight
+            w.zero_()
+            w[5, 32, tap // 3, tap % 3] = 1.0
+            planes = np.repeat(int_planes(rng, 1, N), len(pos), axis=0)
+            for b, (r, c) in enumerate(pos):
+                planes[b, :, r, c] += 3.0
+        ref = ref_forward(net, planes)
+    assert ref["exact_bound"] < EXACT_LIMIT
+    return net, planes, expected_pooled_f32(ref["pooled_sum"], N * N), ref
+
+
+def transposed_taps(net):
+    """A copy of `net` with every conv's taps transposed (ky <-> kx): what a transposed tap index in cnn_pack_conv_kernel computes."""
+    t = copy.deepcopy(net)
+    with torch.no_grad():
+        for cb in t._convs():
+            cb.conv.weight.copy_(cb.conv.weight.transpose(2, 3).contiguous())
+    return t
+
+
+# ---------------------------------------------------------------------------------------------------------------- BatchNorm fold
+@functools.lru_cache(maxsize=None)
+def bn_fold_case():
+    """F = 65, N = 5, L = 0 with exact integer conv sums and real BatchNorm parameters and statistics at the default eps.
+    -> (net, planes, ref of the kernel's statement (folded = True), bound [B,F]).
+
+    Each of the V terms relu(fmaf(sum, scale, shift)) is one f32 rounding of an exact product-sum (emulated as float64, then
+    rounded to f32: sum * scale is exact in float64, so the float64 add can move the f32 rounding only in a tie within 2^-53).
+    The kernel then adds the V non-negative terms in order, V - 1 roundings, and divides, one more: against the float64 mean of
+    the same terms |pooled - ref| <= (V + 1) 2^-24 sum |terms| / V, which leaves one rounding to spare for the emulated fmaf."""
+    F_, N, L = BN_FOLD
+    net = exact_net(F_, L, N, seed=5)
+    rng = np.random.default_rng(65)
+    bn = net.conv.bn
+    with torch.no_grad():
+        bn.weight.copy_(torch.from_numpy(rng.uniform(0.5, 1.5, F_).astype(np.float32)))
+        bn.bias.copy_(torch.from_numpy(rng.uniform(-0.2, 0.2, F_).astype(np.float32)))
+        bn.running_mean.copy_(torch.from_numpy(rng.uniform(-0.3, 0.3, F_).astype(np.float32)))
+        bn.running_var.copy_(torch.from_numpy(rng.uniform(0.5, 2.0, F_).astype(np.float32)))
+    bn.eps = 1e-5
+    planes = int_planes(rng, B_CROSS, N)
+    with torch.no_grad():
+        ref = ref_forward(net, planes, folded=True)
+    V = N * N
+    bound = (V + 1) * U32 * np.abs(ref["terms"]).sum(2) / V
+    return net, planes, ref, bound
+
+
+# ---------------------------------------------------------------------------------------------------------------- real-valued nets
+def real_net(F_, L, N, seed):
+    """Default (kaiming-uniform) conv and head weights, and the non-trivial BatchNorm statistics, gamma and beta of
+    tests/test_cnn.py::_make_net, in eval mode on the CPU."""
+    from alphaquoridorgnn_amd.pv_network_cnn import CNNNetwork
+    torch.manual_seed(seed)
+    net = CNNNetwork(F_, L, board_size=N)
+    with torch.no_grad():
+        for m in net.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                m.weight.uniform_(0.5, 1.5)
+                m.bias.uniform_(-0.2, 0.2)
+                m.running_mean.uniform_(-0.3, 0.3)
+                m.running_var.uniform_(0.5, 2.0)
+    return net.eval()
+
+
+def real_planes(F_, N, L, B=B_CROSS):
+    return np.random.default_rng(17 * F_ + 3 * N + L).standard_normal((B, 6, N, N)).astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------- packed layout
+def packed_floats(F_, L, A):
+    """include/aqgnn.h / csrc/cnn_forward.hip: per conv the weights [nt][ks][9][8][64][4], scale [Fp], shift [Fp]; then the heads,
+    every region rounded up to 64 floats."""
+    r64 = lambda n: (n + 63) // 64 * 64                                  # noqa: E731
+    nt = (F_ + TILE - 1) // TILE
+    total = 0
+    for l in range(2 * L + 1):
+        cin = 6 if l == 0 else F_
+        total += nt * ((cin + KS - 1) // KS) * 9 * (KS // 4) * TILE * 4 + 2 * nt * TILE
+    return total + r64(A * F_) + r64(A) + r64(F_) + 64
+
+
+def packed_conv(w, F_):
+    """conv weight [Cout, Cin, 3, 3] -> the packed slabs [nt][ks][tap 9][k/4 8][n 64][k%4 4], zero past Cout / Cin."""
+    cout, cin = w.shape[:2]
+    nt, ks = (F_ + TILE - 1) // TILE, (cin + KS - 1) // KS
+    full = np.zeros((nt * TILE, ks * KS, 9), dtype=np.float32)
+    full[:cout, :cin] = w.reshape(cout, cin, 9)
+    # [tile, n, slab, kq, j, tap] -> [tile, slab, tap, kq, n, j]
+    return np.ascontiguousarray(full.reshape(nt, TILE, ks, KS // 4, 4, 9).transpose(0, 2, 5, 3, 1, 4))
+
+
+# ---------------------------------------------------------------------------------------------------------------- featuriser inputs
+def _played_states(N, games, plies, seed):
+    """Positions of random legal play under the oracle's rules that place a wall whenever one is legal and a coin says so."""
+    from oracle import quoridor as oq
+    rng = np.random.RandomState(seed)
+    recs = []
+    for _ in range(games):
+        s = oq.State(N=N)
+        for _ in range(plies):
+            if s.is_done():
+                break
+            recs.append(s.rec.copy())
+            la = s.legal_actions()
+            walls = [a for a in la if a >= N * N]
+            pick = walls if (walls and rng.rand() < 0.5) else la
+            s = s.next(pick[rng.randint(len(pick))])
+    return np.stack(recs)
+
+
+@functools.lru_cache(maxsize=None)
+def feat_states(N):
+    """-> (records [n,72], the reference's recorded planes [n0,6,N,N] of the first n0 records, or None at 7x7).  The fixture's
+    states (all of them), then positions of seeded random play: the recorded games do not put a pawn on every kind of tile."""
+    if N == 7:
+        from tests.test_gpu_parity import _small_board_states
+        recs, planes = _small_board_states(7)[::9], None
+    else:
+        g = U.golden(f"feat_{N}x{N}.npz")
+        recs, planes = g["states"], g["planes"]
+    recs = np.ascontiguousarray(np.concatenate([recs, _played_states(N, 6, 24, 40 + N)]))
+    recs.setflags(write=False)
+    return recs, planes
+
+
+def feat_coverage(recs, N):
+    """What the featuriser's inputs must contain between them -> dict of booleans."""
+    from oracle import quoridor as oq
+    S = N - 1
+    w = recs[:, 4:4 + S * S]
+    edge = np.array([t // N in (0, N - 1) or t % N in (0, N - 1) for t in range(N * N)])
+    start = oq.BOARDS[N][0]
+    return {
+        "a wall in every corner slot": all((w[:, c] != 0).any() for c in (0, S - 1, S * (S - 1), S * S - 1)),
+        "a horizontal wall": bool((w == 1).any()), "a vertical wall": bool((w == 2).any()),
+        "player pawn on an edge tile": bool(edge[recs[:, 0]].any()), "player pawn on an interior tile": bool((~edge[recs[:, 0]]).any()),
+        "enemy pawn on an edge tile": bool(edge[recs[:, 2]].any()), "enemy pawn on an interior tile": bool((~edge[recs[:, 2]]).any()),
+        "player wall counter off its start value": bool((recs[:, 1] != start).any()),
+        "enemy wall counter off its start value": bool((recs[:, 3] != start).any()),
+        "the two wall counters differ": bool((recs[:, 1] != recs[:, 3]).any()),
+    }
+
+
+def expected_features(recs):
+    """oracle.gnn.node_features of every record -> [n, V, 6] float32."""
+    from oracle import gnn as og
+    return np.stack([og.node_features(r) for r in recs]).astype(np.float32)
+
+
+def expected_ell(recs):
+    """The ELL rows aqg_gcn_boards_graph must write, from oracle.gnn.board_edges: slot 0 the node itself, slots 1..4 its up / down /
+    left / right neighbour (tile -N, +N, -1, +1) where board_edges has that edge, else index -1.  -> (idx [n*V,5] int32 with
+    indices b V + tile, w [n*V,5] float64 = 1 / sqrt(d_i d_j), d = 1 + the number of open sides; 0 on a closed side)."""
+    from oracle import gnn as og
+    N = int(recs[0][70])
+    V = N * N
+    idx = np.full((len(recs), V, 5), -1, dtype=np.int64)
+    w = np.zeros((len(recs), V, 5), dtype=np.float64)
+    slot_of = {-N: 1, N: 2, -1: 3, 1: 4}
+    for b, rec in enumerate(recs):
+        src, dst = og.board_edges(rec)
+        deg = 1.0 + np.bincount(src, minlength=V)
+        idx[b, :, 0] = np.arange(V)
+        w[b, :, 0] = 1.0 / deg
+        for s, d in zip(src, dst):
+            k = slot_of[int(d - s)]
+            idx[b, s, k] = d
+            w[b, s, k] = 1.0 / np.sqrt(deg[s] * deg[d])
+    idx = np.where(idx >= 0, idx + V * np.arange(len(recs))[:, None, None], -1)
+    return idx.reshape(-1, 5).astype(np.int32), w.reshape(-1, 5)
+
+
+ELL_REL_BOUND = (1 + U32) ** 3 - 1       # f32(1/sqrt(d_i)) * f32(1/sqrt(d_j)) rounded: three f32 roundings of 1 / sqrt(d_i d_j)
+
+
+# ================================================================================================================ the tests
+def test_case_lists_cover_what_they_claim():
+    fs = set(CROSS_F)
+    assert {31, 32, 33}.issubset(fs) and {63, 64, 65}.issubset(fs) and 512 in fs
+    scalar = sorted({(f + KS - 1) // KS for f in fs if f % 4 and f > KS})
+    assert scalar == [2, 3, 4, 5]                                            # slabs of the scalar path beyond its first
+    assert {f % TILE for f in fs if f > TILE and f % TILE} >= {1, 2} and 129 - TILE == 65
+    assert len(CROSS) == len(set(CROSS)) == 2 * len(CROSS_F) * len(CROSS_N) + 8 + 1
+    assert {(f, l) for f, _, l in CROSS_REAL} == {(f, l) for f, _, l in CROSS}
+    assert all(c in CROSS for c in CROSS_REAL) and (5, 3, 40) in CROSS and MASK_CASE["F"] % 4 == 1
+
+
+@pytest.mark.parametrize("case", CROSS, ids=fnl_id)
+def test_exact_cases_are_exact_and_not_trivial(case):
+    """Every partial sum of every conv stays below 2^24 (asserted in exact_case), the expected pool is an exact quotient, and the
+    case says something: most channels of the pool are alive and the boards differ."""
+    F_, N, L = case
+    net, planes, exp, ref = exact_case(F_, N, L)
+    assert exp.dtype == np.float32 and exp.shape == (B_CROSS, F_)
+    assert np.array_equal(np.abs(planes), np.rint(np.abs(planes))) and np.abs(planes).max() == 2
+    for cb in net._convs():
+        w = cb.conv.weight.detach().numpy()
+        assert set(np.unique(w)) <= {-1.0, 0.0, 1.0} and (np.abs(w).sum((0, 2, 3)) > 0).all()     # every input channel is used
+        sc, sh = fold_bn(cb.bn)
+        assert (sc == 1.0).all() and np.array_equal(sh, np.rint(sh)) and ((sh < 0).any() or F_ == 1)
+    alive = (exp > 0).any(0).mean()
+    assert alive >= (0.5 if F_ > 1 else 0.0), alive
+    assert F_ == 1 or not np.array_equal(exp[0], exp[1])
+    if F_ > KS and L > 0:           # the later K slabs matter: zeroing the input channels past the first slab changes the pool
+        cut = copy.deepcopy(net)
+        with torch.no_grad():
+            for cb in cut._convs()[1:]:
+                cb.conv.weight[:, KS:] = 0
+            assert not np.array_equal(ref_forward(cut, planes)["pooled_sum"], ref["pooled_sum"])
+
+
+@pytest.mark.parametrize("case", [(1, 3, 0), (33, 5, 1), (65, 7, 2), (6, 9, 1), (5, 3, 40)], ids=fnl_id)
+def test_reference_agrees_with_the_stock_module_in_float64(case):
+    """ref_forward against the nn modules themselves, on exact and on real-valued networks, with and without the folded form."""
+    F_, N, L = case
+    net, planes, exp, ref = exact_case(F_, N, L)
+    with torch.no_grad():
+        m = module_fp64(net, planes)
+        for k in ("pooled", "logits", "policy", "value"):
+            np.testing.assert_allclose(ref[k], m[k], rtol=1e-12, atol=1e-12, err_msg=k)
+        assert np.array_equal(ref["pooled"], m["pooled"])                    # exact inputs: the same integers over V
+        assert np.array_equal(ref_forward(net, planes, folded=True)["pooled_sum"], ref["pooled_sum"])
+        rnet, rpl = real_net(F_, L, N, seed=3), real_planes(F_, N, L)
+        r, m = ref_forward(rnet, rpl), module_fp64(rnet, rpl)
+        for k in ("pooled", "logits", "policy", "value"):
+            np.testing.assert_allclose(r[k], m[k], rtol=1e-9, atol=1e-12, err_msg=k)
+        f = ref_forward(rnet, rpl, folded=True)                              # folding moves each value by f32 roundings only
+        np.testing.assert_allclose(f["pooled"], m["pooled"], rtol=1e-4, atol=1e-5)
+
+
+@pytest.mark.parametrize("N", PROBE_N)
+@pytest.mark.parametrize("where", ["stem", "block"])
+def test_position_probes_pin_taps_and_halo(N, where):
+    """The probes are exact (asserted in probe_case), every tap gives another pool, where the probe element sits matters to the
+    pool for every off-centre tap, and a transposed tap index gives another pool for every tap off the diagonal."""
+    pools = []
+    for tap in range(9):
+        net, planes, exp, ref = probe_case(N, tap, where)
+        pools.append(ref["pooled_sum"])
+        if tap != 4:
+            assert len({tuple(r) for r in ref["pooled_sum"]}) > 1, tap           # the probe position matters
+        with torch.no_grad():
+            t = ref_forward(transposed_taps(net), planes)["pooled_sum"]
+        if tap not in (0, 4, 8):                                                 # ky != kx
+            assert not np.array_equal(t, ref["pooled_sum"]), tap
+    assert all(not np.array_equal(pools[i], pools[j]) for i in range(9) for j in range(i))
+
+
+def test_bn_fold_case_is_what_it_says():
+    net, planes, ref, bound = bn_fold_case()
+    V = BN_FOLD[1] ** 2
+    with torch.no_grad():
+        y = F.conv2d(torch.from_numpy(planes).double(), net.conv.conv.weight.double(), padding=1).numpy()
+    assert np.array_equal(y, np.rint(y)) and np.abs(y).max() < EXACT_LIMIT and np.abs(y).max() >= 8        # exact integer sums
+    sc, sh = fold_bn(net.conv.bn)
+    assert len(np.unique(sc)) == BN_FOLD[0] and (sc != 1).all() and (sh != 0).all()
+    terms = ref["terms"]
+    assert np.array_equal(terms, terms.astype(np.float32).astype(np.float64)) and (terms >= 0).all() and (terms == 0).any()
+    assert bound.shape == (B_CROSS, BN_FOLD[0]) and (bound > 0).mean() > 0.9
+    with torch.no_grad():
+        m = module_fp64(net, planes)
+    np.testing.assert_allclose(ref["pooled"], m["pooled"], rtol=1e-5, atol=1e-6)      # the fold is the module's BatchNorm
+    assert (np.abs(ref["pooled"] - m["pooled"]) <= 4 * V * U32 * np.abs(ref["terms"]).sum(2) / V + 1e-30).all()
+
+
+def test_packed_floats_agrees_with_the_layout():
+    from alphaquoridorgnn_amd import _lib
+    lib = _lib.load()
+    for F_ in CROSS_F + [5]:
+        for L in (0, 1, 2, 40):
+            for A in (1, policy_size(3), policy_size(9), 4096):
+                assert int(lib.aqg_cnn_packed_floats(F_, L, A)) == packed_floats(F_, L, A), (F_, L, A)
+
+
+def test_packed_conv_reference_layout():
+    """packed_conv against the kernel's index arithmetic written out element by element."""
+    rng = np.random.default_rng(0)
+    w = rng.standard_normal((66, 35, 3, 3)).astype(np.float32)
+    p = packed_conv(w, 66)
+    assert p.shape == (2, 2, 9, 8, 64, 4)
+    for _ in range(2000):
+        tile, s, tap, kq, n, j = (int(rng.integers(d)) for d in p.shape)
+        co, k = 64 * tile + n, 32 * s + 4 * kq + j
+        assert p[tile, s, tap, kq, n, j] == (w[co, k, tap // 3, tap % 3] if co < 66 and k < 35 else 0.0)
+
+
+@pytest.mark.parametrize("N", FEAT_N)
+def test_featuriser_inputs_cover_the_board(N):
+    recs, planes = feat_states(N)
+    assert (recs[:, 70] == N).all() and recs.shape[0] >= 200
+    assert (planes is None) == (N == 7) and (planes is None or planes.shape == (200, 6, N, N))
+    missing = [k for k, ok in feat_coverage(recs, N).items() if not ok]
+    assert not missing, missing
+
+
+@pytest.mark.parametrize("N", FEAT_N)
+def test_featuriser_references_agree_with_each_other(N):
+    """oracle.gnn.node_features against the reference's recorded planes; expected_ell against the dense normalised adjacency
+    written down independently (walls -> open sides -> D^-1/2 (A + I) D^-1/2), and its shape: symmetric, -1 exactly where closed."""
+    from oracle import gnn as og
+    recs, planes = feat_states(N)
+    V = N * N
+    x = expected_features(recs)
+    if planes is not None:
+        assert np.array_equal(x[:200], planes.reshape(200, 6, V).transpose(0, 2, 1))
+    sub = recs[::7]
+    idx, w = expected_ell(sub)
+    idx, w = idx.reshape(-1, V, 5), w.reshape(-1, V, 5)
+    assert (idx[:, :, 0] == np.arange(len(sub) * V).reshape(-1, V)).all()
+    assert ((idx < 0) == (w == 0)).all() and (idx < 0).any() and (idx[:, :, 1:] >= 0).any()
+    for b, rec in enumerate(sub):
+        A = np.eye(V)
+        for dx, dy in ((1, 0), (0, 1)):
+            for xx in range(N - dx):
+                for yy in range(N - dy):
+                    if not og.blocked(rec, xx, yy, xx + dx, yy + dy):
+                        A[xx * N + yy, (xx + dx) * N + yy + dy] = A[(xx + dx) * N + yy + dy, xx * N + yy] = 1.0
+        dis = A.sum(1) ** -0.5
+        An = dis[:, None] * A * dis[None, :]
+        dense = np.zeros((V, V))
+        for t in range(V):
+            for k in range(5):
+                if idx[b, t, k] >= 0:
+                    dense[t, idx[b, t, k] - b * V] += w[b, t, k]
+        np.testing.assert_allclose(dense, An, rtol=1e-15, atol=0)
+    assert 0 < ELL_REL_BOUND < 3.0000004 * U32
