@@ -15,6 +15,7 @@ GNN_EXACT_F32 = 1        # AQG_GNN_EXACT_F32 (include/aqgnn.h)
 GNN_RANGE_PROVEN = 2     # AQG_GNN_RANGE_PROVEN
 GNN_PROVEN_MAX_WALLS = 16
 ABI_VERSION = 15
+AGENT_AB_MAX_DEPTH = 4     # AQG_AGENT_AB_MAX_DEPTH
 TRAIN_PART_FLOATS = 2 * 128 * 128 + 128 * 6 + 3 * 128    # AQG_TRAIN_PART_FLOATS, per position of the batch
 LIN_RELU, LIN_W_KN, LIN_ACCUMULATE = 1, 2, 4             # AQG_LIN_* flags of aqg_graph_linear
 
@@ -154,6 +155,9 @@ SIGNATURES = {
     "aqg_agent_mcts_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
     "aqg_agent_mcts": (_c.c_int, [_c.c_int, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _c.c_int, _c.c_uint64, _vp, _c.c_size_t,
                                   _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aqg_agent_shortest_paths": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp, _vp]),
+    "aqg_agent_alpha_beta_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "aqg_agent_alpha_beta": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _c.c_size_t, _vp, _vp, _vp]),
     "aqg_gcn_train_step": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _c.c_int, _vp]),
     "aqg_gcn_train_steps": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _vp]),
     "aqg_gcn_train_fallbacks": (_c.c_longlong, [_c.c_int]),

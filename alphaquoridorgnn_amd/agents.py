@@ -8,7 +8,8 @@ The random streams are consumed exactly like the reference's: `random.randint` o
 
 The *_batch functions serve many states per call -- what a match of a network against a baseline agent asks for every ply
 (evaluate_agents.BatchedAgentMatch): random moves, random playouts and the rollout MCTS on HIP kernels (csrc/agents.hip, one
-wavefront per state; GPU required), alpha-beta on the native host search from a thread pool.  The kernels cannot replay Python's
+wavefront per state; GPU required), alpha-beta on the native host search from a thread pool or, with backend='hip', on the
+kernel of the same file (one wavefront per state and root action).  The kernels cannot replay Python's
 `random` stream; their draws come from a caller-supplied table of uniforms or from the counter-based generator `draw_uniforms`
 mirrors (include/aqgnn.h).  The single-state functions above them are untouched.
 """
@@ -327,10 +328,77 @@ def mcts_action_batch(states72, evaluations=100, seed=0, uniforms=None, return_v
     return action.cpu().numpy()
 
 
-def alpha_beta_action_batch(states72, max_depth=2, threads=None):
-    """alpha_beta_action for every state, in input order, on the native host search from a pool of `threads` threads (default
-    default_threads(); ctypes releases the GIL during a search).  Returns int32 [B] (numpy), -1 = no action."""
+AB_MAX_DEPTH = _lib.AGENT_AB_MAX_DEPTH     # the deepest search aqg_agent_alpha_beta serves
+# BatchedAgentMatch's 'auto' backend: slots per engine from which the alpha-beta agent is served by the kernel -- the smallest
+# 9x9 batch at which tools/alpha_beta_time.py measured the device call faster than the 16-thread host pool.  That is the smallest
+# batch of the run in profiles/alpha_beta_device.log (5 positions: 3.6 ms against 18.0 ms); nothing below 5 was measured.
+ALPHA_BETA_DEVICE_MIN_STATES = 5
+
+
+def shortest_paths_batch(states72, device=None):
+    """shortest_path of every state and of its flipped state (aqg_agent_shortest_paths): int32 [B,2] (numpy), column 0 the
+    mover's plies to its goal row, column 1 the other side's; -1 = walled in."""
     import torch
+    dev, d, N = _device_batch(states72, device)
+    out = torch.empty((int(d.shape[0]), 2), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().aqg_agent_shortest_paths(N, _lib.ptr(d), int(d.shape[0]), _lib.ptr(out), _lib.stream_ptr(dev)),
+               "aqg_agent_shortest_paths")
+    return out.cpu().numpy()
+
+
+def heuristic_eval_batch(states72, device=None):
+    """heuristic_eval of every state: float64 [B] (numpy).  The paths come from the kernel, the one division is done here in
+    float64 as the host does it, so the values are heuristic_eval's bit for bit."""
+    recs = _records(states72)
+    if recs.shape[0] == 0:
+        raise ValueError("no states")
+    walls, draw = board_params(int(recs[0, 70]))
+    p = shortest_paths_batch(recs, device).astype(np.int64)
+    return (p[:, 1] - p[:, 0]).astype(np.float64) / np.float64(draw // 2 - walls)
+
+
+def _check_depth(max_depth):
+    if not 0 <= int(max_depth) <= AB_MAX_DEPTH:
+        raise ValueError(f"the alpha-beta kernel serves max_depth 0..{AB_MAX_DEPTH}, got {max_depth}")
+    return int(max_depth)
+
+
+def alpha_beta_action_device(states, N, max_depth=2, active=None, return_nodes=False):
+    """aqg_agent_alpha_beta on device records [B,72]: int32 [B] device tensor, -1 where a state has no legal action, 0 where
+    `active` (uint8 [B] device tensor, an engine's game_active) is 0.  No host synchronisation.  With return_nodes also the
+    positions visited per state, int64 [B]."""
+    import torch
+    dev = states.device
+    lib = _lib.load()
+    B, depth = int(states.shape[0]), _check_depth(max_depth)
+    action = torch.empty((B,), dtype=torch.int32, device=dev)
+    nodes = torch.empty((B,), dtype=torch.int64, device=dev) if return_nodes else None
+    if B > 0:
+        if active is not None and (active.dtype != torch.uint8 or active.numel() != B):
+            raise ValueError("active must be a uint8 tensor with one entry per state")
+        walls, draw = board_params(N)
+        ws = torch.empty((int(lib.aqg_agent_alpha_beta_workspace_bytes(N, B, depth)),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.aqg_agent_alpha_beta(N, _lib.ptr(states), B, _lib.ptr(active), draw, draw // 2 - walls, depth, _lib.ptr(ws),
+                                            ws.numel(), _lib.ptr(action), _lib.ptr(nodes), _lib.stream_ptr(dev)),
+                   "aqg_agent_alpha_beta")
+        ws.record_stream(torch.cuda.current_stream(dev))
+    return (action, nodes) if return_nodes else action
+
+
+def alpha_beta_action_batch(states72, max_depth=2, threads=None, backend="host", device=None):
+    """alpha_beta_action for every state, in input order.  Returns int32 [B] (numpy), -1 = no action.
+    backend 'host' (the default; no GPU needed): the native host search from a pool of `threads` threads (default
+    default_threads(); ctypes releases the GIL during a search).  backend 'hip': the kernel (aqg_agent_alpha_beta, max_depth up to
+    AB_MAX_DEPTH, one board size per call); the same actions."""
+    import torch
+    if backend not in ("host", "hip"):
+        raise ValueError(f"backend must be 'host' or 'hip', got {backend!r}")
+    if backend == "hip":
+        _check_depth(max_depth)
+        if len(states72) == 0:
+            return np.zeros((0,), dtype=np.int32)
+        dev, d, N = _device_batch(states72, device)
+        return alpha_beta_action_device(d, N, max_depth).cpu().numpy()
     recs = _records(states72)
     if isinstance(recs, torch.Tensor):
         recs = recs.cpu().numpy()

@@ -1,5 +1,5 @@
 // agents.hip -- the baseline agents of agents.py in batch, for gfx950: uniformly random moves (agents.py:14-18), random playouts
-// (:111-121) and the rollout MCTS built on them (:130-214), plus the two engine entry points a "network vs agent" match needs:
+// (:111-121), the rollout MCTS built on them (:130-214) and depth-limited alpha-beta (:22-107), plus the two engine entry points a "network vs agent" match needs:
 // read every slot's position, apply a move the engine did not search.
 //
 // One 64-lane wavefront per state / game, as in legal_mask.hip: a playout is legal_actions() -> pick -> next() until the game ends,
@@ -8,6 +8,9 @@
 //
 // Every loop ends on an integer cap computed from the arguments (plies left to the draw limit, evaluations, AQG_MAX_LEGAL, the node
 // cap, the depth cap), never on a game condition alone.  No atomics on results: two runs give identical bytes.
+//
+// Alpha-beta (agents.py:22-107) is served here too: the jump-aware shortest paths of its leaf evaluator, one lane per position, and
+// the search itself, one wavefront per (state, root action) -- see the comment above ab_search's kernels.
 #include "aqg_common.hpp"
 #include "legal_wave.hpp"
 #include "launchers.hpp"
@@ -291,6 +294,253 @@ __global__ __launch_bounds__(64) void agent_mcts_kernel(const uint8_t* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
+// shortest paths (agents.py:27-54): the leaf evaluator of alpha-beta
+// ------------------------------------------------------------------------------------------------
+// Plies each side needs to reach its goal row over legal_actions_pos -- jumps allowed, the other pawn frozen -- or -1 when it is
+// walled in: `sp` for the mover, `se` for the other side.  A level-synchronous fill over the open-edge boards (the three-word form of
+// can_reach2_w3, without a candidate wall): the round in which the fill first touches the goal row is the depth at which the
+// reference's first-in-first-out search pops its first goal tile.  The other side's search runs in the mover's frame -- start, goal
+// row and obstacle rotated by 180 degrees instead of the walls -- which leaves every distance as it is.  At most V rounds.  The state
+// may differ from lane to lane: nothing here is wave-uniform.
+template <int N>
+__device__ __forceinline__ void shortest_paths2(const QState& s, int& sp, int& se) {
+    constexpr int V = Geo<N>::V;
+    const Open o = make_open<N>(s.hw, s.vw);
+    const W3 oU = w3(o.U), oD = w3(o.D), oL = w3(o.L), oR = w3(o.R);
+    const int me = min((int)s.ppos, V - 1), other = V - 1 - min((int)s.epos, V - 1);      // (a malformed record stays on the board)
+    const W3 nA = ~w3_bit(other), nB = ~w3_bit(me);
+    const W3 gA = w3(mask_row<N>(0)), gB = w3(mask_row<N>(N - 1));
+    W3 JA[4], JB[4];
+    int qA[4], qB[4];
+    jump_landings_w3<N>(oU, oD, oL, oR, other, JA, qA);
+    jump_landings_w3<N>(oU, oD, oL, oR, me, JB, qB);
+    W3 rA = w3_bit(me), rB = w3_bit(other);
+    int dA = -1, dB = -1, done = 0;
+    for (int it = 0; it < V; ++it) {
+        if (!(done & 1) && w3_any(rA & gA)) { dA = it; done |= 1; }
+        if (!(done & 2) && w3_any(rB & gB)) { dB = it; done |= 2; }
+        if (done == 3) break;
+        W3 a = (rA | w3_shl<N>(rA & oD) | w3_shr<N>(rA & oU) | w3_shl<1>(rA & oR) | w3_shr<1>(rA & oL)) & nA;
+        W3 b = (rB | w3_shl<N>(rB & oD) | w3_shr<N>(rB & oU) | w3_shl<1>(rB & oR) | w3_shr<1>(rB & oL)) & nB;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const uint32_t mA = w3_mask_of(rA, qA[d]), mB = w3_mask_of(rB, qB[d]);
+            a.a |= JA[d].a & mA; a.b |= JA[d].b & mA; a.c |= JA[d].c & mA;
+            b.a |= JB[d].a & mB; b.b |= JB[d].b & mB; b.c |= JB[d].c & mB;
+        }
+        if (w3_eq(a, rA)) done |= 1;                       // a fixpoint without the goal: walled in
+        if (w3_eq(b, rB)) done |= 2;
+        if (done == 3) break;
+        rA = a; rB = b;
+    }
+    sp = dA; se = dB;
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void agent_shortest_paths_kernel(const uint8_t* __restrict__ states72, int B, int32_t* __restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int sp, se;
+    shortest_paths2<N>(unpack72(states72 + (size_t)b * STATE72), sp, se);
+    out[2 * (size_t)b] = sp;
+    out[2 * (size_t)b + 1] = se;
+}
+
+// ------------------------------------------------------------------------------------------------
+// alpha-beta (agents.py:58-107; the pinned statement is host_agents.cpp): one wavefront per (state, root action)
+// ------------------------------------------------------------------------------------------------
+// What the design rests on:
+//  * Only true negamax values decide the action.  The reference searches root child i with the window (-inf, -alpha), alpha the
+//    running best: the child's score is exact whenever it exceeds alpha and <= alpha otherwise, so the answer is the FIRST root
+//    action with the maximal true depth-limited negamax value -- whatever the order of evaluation, and under any bound that never
+//    exceeds the true running best.  Here: pass 0 searches root child 0 of every state with the full window (one wave per state);
+//    pass 1 searches children 1..n-1 in parallel (one wave each) under the value of child 0; a third launch takes the first
+//    maximum.  Root pruning is weaker than the reference's, parallelism ~130 times larger at 9x9.
+//  * All scores compare as integers.  A leaf scores (se - sp) / max_dist, a lost position -1, a drawn one 0: the tree holds the
+//    numerators se - sp, -max_dist and 0.  Distinct numerators are distinct doubles and negation is exact, so every comparison falls
+//    as the host's float64 one does.  No floating point in the tree.
+//  * The sentinel.  A position that is not over but has no legal action returns its incoming alpha; under a root child searched
+//    from -inf that is -inf, and the root action scores +inf.  -inf is AB_INF here, an integer beyond every numerator, negated like
+//    the others.
+//  * The last ply is data-parallel.  At a node whose children are leaves the value is max over children of -h(child): one lane per
+//    child does next(), lose / draw and the two fills, 64 children a round, and the cut-off is taken between rounds instead of
+//    between children.  A cut-off node returns some value >= beta either way, which its parent discards either way.
+// Above the last ply the search walks the tree with an explicit stack of max_depth frames (position, window, legal list, next
+// child) in LDS.  Every loop ends on an integer cap: MAX_LEGAL, the V rounds of a fill, the step cap of ab_search.
+constexpr int AB_MAX_DEPTH = AQG_AGENT_AB_MAX_DEPTH;
+constexpr int AB_INF = 1 << 20;
+static_assert(AB_MAX_DEPTH >= 1 && AB_MAX_DEPTH <= 4, "the step cap of ab_search is MAX_LEGAL^(depth - 1) in 64 bits; nodes are counted in 32");
+
+struct AbFrame {
+    QState s;
+    int32_t alpha, beta, n, idx;
+};
+
+// the depth-0 value of a position from its mover's point of view, as a numerator over max_dist (per lane)
+template <int N>
+__device__ __forceinline__ int ab_leaf(const QState& t, int plies_for_draw, int max_dist) {
+    if (is_lose<N>(t)) return -max_dist;
+    if (is_draw(t, plies_for_draw)) return 0;
+    int sp, se;
+    shortest_paths2<N>(t, sp, se);
+    return se - sp;
+}
+
+// a node whose children are leaves: alpha after the children, 64 per round; returns as soon as a round lifts it to beta
+template <int N>
+__device__ __forceinline__ int ab_last_ply(const QState& s, const uint8_t* list, int n, int alpha, int beta, int plies_for_draw,
+                                           int max_dist, int lane, uint32_t& visited) {
+    for (int r = 0; r < MAX_LEGAL; r += 64) {
+        if (r >= n) break;
+        const int k = r + lane;
+        int sc = -AB_INF;
+        if (k < n) sc = -ab_leaf<N>(next_state<N>(s, list[k]), plies_for_draw, max_dist);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) sc = max(sc, __shfl_xor(sc, off));
+        sc = __builtin_amdgcn_readfirstlane(sc);
+        visited += (uint32_t)min(64, n - r);
+        alpha = max(alpha, sc);
+        if (alpha >= beta) break;
+    }
+    return alpha;
+}
+
+// alpha_beta(c, alpha, beta, depth) of agents.py:58-86 for a wave-uniform position c.  lists / fr: `depth` rows of this wave's LDS.
+template <int N>
+__device__ __forceinline__ int ab_search(const QState& c, int alpha, int beta, int depth, int plies_for_draw, int max_dist, int lane,
+                                         uint8_t (*lists)[MAX_LEGAL], AbFrame* fr, uint32_t& visited) {
+    visited = 1;
+    if (depth <= 0 || is_lose<N>(c) || is_draw(c, plies_for_draw)) return ab_leaf<N>(c, plies_for_draw, max_dist);
+    auto push = [&](int L, const QState& s, int a, int b) {
+        wave_sync();                                        // the readers of this row's previous list are done
+        const int n = wave_legal_actions<N>(s, lane, nullptr, lists[L]);
+        if (lane == 0) { fr[L].s = s; fr[L].alpha = a; fr[L].beta = b; fr[L].n = n; fr[L].idx = 0; }
+        wave_sync();
+    };
+    push(0, c, alpha, beta);
+    // every step opens a child, closes a node, or takes a returned value: at most three per node above the last ply
+    uint64_t inner = 0, level = 1;
+    for (int j = 0; j < depth; ++j) { inner += level; level *= MAX_LEGAL; }
+    const uint64_t cap = 3 * inner + 3;
+    int L = 0, ret = alpha;
+    bool returned = false;                                  // `ret` holds the value of a child of frame L
+    for (uint64_t step = 0; step < cap; ++step) {
+        int a = __builtin_amdgcn_readfirstlane(fr[L].alpha);
+        const int b = __builtin_amdgcn_readfirstlane(fr[L].beta);
+        bool close = false;
+        if (returned) {
+            returned = false;
+            if (-ret > a) {
+                a = -ret;
+                wave_sync();
+                if (lane == 0) fr[L].alpha = a;
+                wave_sync();
+            }
+            close = a >= b;                                 // beta cut-off
+        }
+        if (!close) {
+            const QState s = uniform_of(fr[L].s);
+            const int n = __builtin_amdgcn_readfirstlane(fr[L].n);
+            if (depth - L == 1) {
+                a = ab_last_ply<N>(s, lists[L], n, a, b, plies_for_draw, max_dist, lane, visited);
+                close = true;
+            } else {
+                const int idx = __builtin_amdgcn_readfirstlane(fr[L].idx);
+                if (idx >= n) {
+                    close = true;
+                } else {
+                    const QState t = uniform_of(next_state<N>(s, lists[L][idx]));
+                    wave_sync();
+                    if (lane == 0) fr[L].idx = idx + 1;
+                    wave_sync();
+                    ++visited;
+                    if (is_lose<N>(t) || is_draw(t, plies_for_draw)) {
+                        ret = ab_leaf<N>(t, plies_for_draw, max_dist);
+                        returned = true;
+                    } else {
+                        ++L;
+                        push(L, t, -b, -a);
+                    }
+                    continue;
+                }
+            }
+        }
+        ret = a;                                            // frame L is done: its value goes to its parent
+        returned = true;
+        if (L == 0) break;
+        --L;
+    }
+    return ret;
+}
+
+// The workspace of one call: per state MAX_LEGAL scores and MAX_LEGAL node counts (32 bits each), the root's legal list, its length.
+struct AbWorkspace {
+    int32_t* score;      // [B, MAX_LEGAL] the root child's negamax score (exact, or a bound <= child 0's)
+    uint32_t* visited;   // [B, MAX_LEGAL] positions visited under it
+    int32_t* count;      // [B]
+    uint8_t* action;     // [B, MAX_LEGAL]
+};
+__host__ __device__ inline size_t ab_workspace_bytes(int B) { return (size_t)B * (MAX_LEGAL * 9 + 4); }
+__host__ __device__ inline AbWorkspace ab_workspace(void* p, int B) {
+    AbWorkspace w;
+    w.score = reinterpret_cast<int32_t*>(p);
+    w.visited = reinterpret_cast<uint32_t*>(w.score + (size_t)B * MAX_LEGAL);
+    w.count = reinterpret_cast<int32_t*>(w.visited + (size_t)B * MAX_LEGAL);
+    w.action = reinterpret_cast<uint8_t*>(w.count + B);
+    return w;
+}
+
+// pass 0: block = state, root child 0, full window.  pass 1: block = state * (MAX_LEGAL - 1) + (root child - 1), under child 0's score.
+template <int N>
+__global__ __launch_bounds__(64) void agent_alpha_beta_kernel(const uint8_t* __restrict__ states72, int B, const uint8_t* __restrict__ active,
+                                                              int plies_for_draw, int max_dist, int max_depth, int pass, AbWorkspace w) {
+    __shared__ uint8_t root_list[MAX_LEGAL];
+    __shared__ uint8_t lists[AB_MAX_DEPTH][MAX_LEGAL];
+    __shared__ AbFrame frames[AB_MAX_DEPTH];
+    const int lane = threadIdx.x;
+    const int b = pass == 0 ? (int)blockIdx.x : (int)(blockIdx.x / (MAX_LEGAL - 1));
+    const int k = pass == 0 ? 0 : 1 + (int)(blockIdx.x % (MAX_LEGAL - 1));
+    if (b >= B || (active && !active[b])) return;
+    const QState root = uniform_of(unpack72(states72 + (size_t)b * STATE72));
+    const int n = wave_legal_actions<N>(root, lane, nullptr, root_list);
+    wave_sync();
+    if (pass == 0) {
+        if (lane == 0) w.count[b] = n;
+        for (int i = lane; i < MAX_LEGAL; i += 64) w.action[(size_t)b * MAX_LEGAL + i] = root_list[i];
+    }
+    if (k >= n || n > MAX_LEGAL) return;
+    const int bound = pass == 0 ? -AB_INF : w.score[(size_t)b * MAX_LEGAL];
+    const QState c = uniform_of(next_state<N>(root, root_list[k]));
+    uint32_t visited;
+    const int v = ab_search<N>(c, -AB_INF, -bound, max_depth, plies_for_draw, max_dist, lane, lists, frames, visited);
+    if (lane == 0) {
+        w.score[(size_t)b * MAX_LEGAL + k] = -v;
+        w.visited[(size_t)b * MAX_LEGAL + k] = visited;
+    }
+}
+
+// the first maximum (agents.py:98-107: strictly greater than the running best, from -inf); 0 on a masked slot, -1 without an action
+__global__ __launch_bounds__(256) void agent_alpha_beta_pick_kernel(int B, const uint8_t* __restrict__ active, AbWorkspace w,
+                                                                    int32_t* __restrict__ action, int64_t* __restrict__ nodes) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int best = -1, alpha = -AB_INF;
+    int64_t total = 0;
+    if (active && !active[b]) {
+        best = 0;
+    } else {
+        const int n = min(w.count[b], MAX_LEGAL);
+        for (int k = 0; k < n; ++k) {
+            const int sc = w.score[(size_t)b * MAX_LEGAL + k];
+            total += w.visited[(size_t)b * MAX_LEGAL + k];
+            if (sc > alpha) { alpha = sc; best = w.action[(size_t)b * MAX_LEGAL + k]; }
+        }
+    }
+    action[b] = best;
+    if (nodes) nodes[b] = total;
+}
+
+// ------------------------------------------------------------------------------------------------
 // engine: the position of every slot, and a move the engine did not search
 // ------------------------------------------------------------------------------------------------
 __global__ void engine_root_states72_kernel(aqg_engine e, uint8_t* __restrict__ out72) {
@@ -384,6 +634,38 @@ int launch_agent_mcts(int N, const uint8_t* states72, int B, int evaluations, in
                                       uniforms, stride, seed, pool, cap, action, visits, actions, count, draws)
     AQG_AGENT_DISPATCH(N, CALL_AM)
     return check_launch("agent_mcts_kernel");
+}
+
+int launch_agent_shortest_paths(int N, const uint8_t* states72, int B, int32_t* out, hipStream_t st) {
+    if (B <= 0) return 0;
+#define CALL_SP(n) hipLaunchKernelGGL(agent_shortest_paths_kernel<n>, dim3((B + 255) / 256), dim3(256), 0, st, states72, B, out)
+    AQG_AGENT_DISPATCH(N, CALL_SP)
+    return check_launch("agent_shortest_paths_kernel");
+}
+
+constexpr int AB_MAX_STATES = 1 << 23;       // B * (MAX_LEGAL - 1) blocks fit a grid
+
+size_t agent_alpha_beta_workspace_bytes(int N, int B, int max_depth) {
+    if (!(N == 3 || N == 5 || N == 7 || N == 9) || B <= 0 || B > AB_MAX_STATES || max_depth < 0 || max_depth > AB_MAX_DEPTH) return 0;
+    return ab_workspace_bytes(B);
+}
+
+int launch_agent_alpha_beta(int N, const uint8_t* states72, int B, const uint8_t* active, int plies_for_draw, int max_dist,
+                            int max_depth, void* workspace, size_t workspace_bytes, int32_t* action, int64_t* nodes, hipStream_t st) {
+    if (B <= 0) return 0;
+    if (B > AB_MAX_STATES) return fail("aqg_agent_alpha_beta: too many states in one call");
+    if (workspace_bytes < ab_workspace_bytes(B)) return fail("aqg_agent_alpha_beta: workspace too small");
+    const AbWorkspace w = ab_workspace(workspace, B);
+#define CALL_AB0(n) hipLaunchKernelGGL(agent_alpha_beta_kernel<n>, dim3(B), dim3(64), 0, st, states72, B, active, plies_for_draw, max_dist, \
+                                       max_depth, 0, w)
+    AQG_AGENT_DISPATCH(N, CALL_AB0)
+    if (int r = check_launch("agent_alpha_beta_kernel (root child 0)")) return r;
+#define CALL_AB1(n) hipLaunchKernelGGL(agent_alpha_beta_kernel<n>, dim3((unsigned)B * (MAX_LEGAL - 1)), dim3(64), 0, st, states72, B, active, \
+                                       plies_for_draw, max_dist, max_depth, 1, w)
+    AQG_AGENT_DISPATCH(N, CALL_AB1)
+    if (int r = check_launch("agent_alpha_beta_kernel (root children 1..)")) return r;
+    hipLaunchKernelGGL(agent_alpha_beta_pick_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, active, w, action, nodes);
+    return check_launch("agent_alpha_beta_pick_kernel");
 }
 
 int engine_root_states72(const aqg_engine& e, uint8_t* out72, hipStream_t st) {

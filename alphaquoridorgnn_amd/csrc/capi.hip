@@ -277,6 +277,25 @@ int aqg_agent_mcts(int board_size, const uint8_t* states72, int B, int evaluatio
                              workspace_bytes, action, visits, actions, count, draws, (hipStream_t)stream);
 }
 
+int aqg_agent_shortest_paths(int board_size, const uint8_t* states72, int B, int32_t* out, void* stream) {
+    if (B < 0 || (B > 0 && (!states72 || !out))) return fail("aqg_agent_shortest_paths", "bad arguments");
+    return launch_agent_shortest_paths(board_size, states72, B, out, (hipStream_t)stream);
+}
+size_t aqg_agent_alpha_beta_workspace_bytes(int board_size, int B, int max_depth) {
+    return agent_alpha_beta_workspace_bytes(board_size, B, max_depth);
+}
+int aqg_agent_alpha_beta(int board_size, const uint8_t* states72, int B, const uint8_t* active, int plies_for_draw,
+                         int max_dist_from_goal, int max_depth, void* workspace, size_t workspace_bytes, int32_t* action,
+                         int64_t* nodes, void* stream) {
+    const char* what = "aqg_agent_alpha_beta";
+    if (B < 0 || (B > 0 && (!states72 || !action || !workspace))) return fail(what, "bad arguments");
+    if (max_depth < 0 || max_depth > AQG_AGENT_AB_MAX_DEPTH) return fail(what, "max_depth must be 0..AQG_AGENT_AB_MAX_DEPTH (4)");
+    if (plies_for_draw < 0 || plies_for_draw > 65535) return fail(what, "plies_for_draw must be 0..65535");
+    if (max_dist_from_goal <= 0 || max_dist_from_goal > 65535) return fail(what, "max_dist_from_goal must be 1..65535");
+    return launch_agent_alpha_beta(board_size, states72, B, active, plies_for_draw, max_dist_from_goal, max_depth, workspace,
+                                   workspace_bytes, action, nodes, (hipStream_t)stream);
+}
+
 int aqg_gcn_train_step(const aqg_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
                        void* stream) {
     if (!t || mode < 0 || mode > 2) return fail("aqg_gcn_train_step: bad argument");

@@ -93,6 +93,10 @@ size_t agent_mcts_workspace_bytes(int B, int evaluations);
 int launch_agent_mcts(int N, const uint8_t* states72, int B, int evaluations, int plies_for_draw, const double* explore,
                       const double* uniforms, int stride, uint64_t seed, void* workspace, size_t workspace_bytes, int32_t* action,
                       int32_t* visits, uint8_t* actions, int32_t* count, int32_t* draws, hipStream_t st);
+int launch_agent_shortest_paths(int N, const uint8_t* states72, int B, int32_t* out, hipStream_t st);
+size_t agent_alpha_beta_workspace_bytes(int N, int B, int max_depth);
+int launch_agent_alpha_beta(int N, const uint8_t* states72, int B, const uint8_t* active, int plies_for_draw, int max_dist,
+                            int max_depth, void* workspace, size_t workspace_bytes, int32_t* action, int64_t* nodes, hipStream_t st);
 int engine_root_states72(const aqg_engine& e, uint8_t* out72, hipStream_t st);
 int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_t st);
 

@@ -5,7 +5,8 @@ Call surface kept (evaluate_agents.py:15-89): EP_GAME_COUNT, first_player_point,
 evaluate_best_player().  `play` / `evaluate_algorithm_of` are the reference's host loops for any two action functions (without its
 per-ply print of the board).  `evaluate_best_player()` plays its three matches with BatchedAgentMatch: the network's plies are
 searched by the engine as in self-play, the agent's plies are served for all games at once -- random moves and the rollout MCTS by
-the kernels of csrc/agents.hip, alpha-beta by the native host search on a thread pool -- and applied to the engine without a search
+the kernels of csrc/agents.hip, alpha-beta by its kernel there too (or, for a handful of slots, by the native host search on a thread
+pool: `backend` below) -- and applied to the engine without a search
 (aqg_engine_apply_actions).  Per game this is the reference's loop: colours alternate with the game index
 (evaluate_agents.py:46-51) and the network moves at temperature 0 (:73).  The kernels' random draws are their own stream
 (agents.draw_uniforms), not Python's `random`.
@@ -64,9 +65,12 @@ class BatchedAgentMatch:
     even (evaluate_agents.py:46-51).  Two engines, as BatchedMatch has them: the network-first games and the agent-first games.
     Each ply, each engine either searches (`move`) or reads its roots, asks the agent for one action per slot and applies them.
 
-    agent: 'random' / 'mcts' (HIP kernels), 'alpha_beta' (native host search, thread pool), or any callable state -> action, served
-    game by game on the host (the slow, general path; while it is called, `self.current` = (engine index, slot, ply)).
-    agent_kwargs: evaluations (mcts, default 100), max_depth / threads (alpha_beta).
+    agent: 'random' / 'mcts' / 'alpha_beta' (HIP kernels), or any callable state -> action, served game by game on the host (the
+    slow, general path; while it is called, `self.current` = (engine index, slot, ply)).
+    agent_kwargs: evaluations (mcts, default 100); max_depth / threads / backend (alpha_beta).  backend 'hip': the positions go
+    from the engine to aqg_agent_alpha_beta and the actions back into the engine without leaving the device; 'host': the records
+    are copied out, searched natively from a thread pool and copied back; 'auto' (the default): 'hip' for engines of at least
+    agents.ALPHA_BETA_DEVICE_MIN_STATES slots and a max_depth the kernel serves, else 'host'.  The games are the same either way.
     evaluator: 'gnn' (the default 6/128/3 network), 'general' (a GraphPolicyValueNetwork of any shape), 'cnn', 'external' (any
     model with predict) or 'fake' (`model` is the integer bias of the parity tests' hash evaluator)."""
 
@@ -78,6 +82,8 @@ class BatchedAgentMatch:
             raise ValueError("evaluator must be 'gnn', 'general', 'cnn', 'fake' or 'external'")
         self.model, self.agent, self.evaluator = model, agent, evaluator
         self.agent_kwargs = dict(agent_kwargs or {})
+        if self.agent_kwargs.get("backend", "auto") not in ("auto", "hip", "host"):
+            raise ValueError("agent_kwargs['backend'] must be 'auto', 'hip' or 'host'")
         self.N, self.seed = int(board_size), int(seed)
         self.num_games = int(num_games)
         sims = pv_mcts.PV_EVALUATE_COUNT if sims is None else sims
@@ -95,6 +101,13 @@ class BatchedAgentMatch:
                 eng = BatchedSelfPlay(model, evaluator=evaluator, **kw)
             self.engines.append(eng)
         self.current = None
+
+    def _alpha_beta_on_device(self, eng):
+        backend = self.agent_kwargs.get("backend", "auto")
+        if backend == "auto":
+            return (eng.G >= agents.ALPHA_BETA_DEVICE_MIN_STATES
+                    and 0 <= int(self.agent_kwargs.get("max_depth", 2)) <= agents.AB_MAX_DEPTH)
+        return backend == "hip"
 
     # ------------------------------------------------------------------ the agent's ply
     def _call_seed(self, first, ply):
@@ -115,6 +128,9 @@ class BatchedAgentMatch:
             if table is not None:
                 agents._check_draws(out[4], width, "agent_uniforms (mcts)")
             return out[0]
+        if self.agent == "alpha_beta" and self._alpha_beta_on_device(eng):
+            return agents.alpha_beta_action_device(states, self.N, int(self.agent_kwargs.get("max_depth", 2)),
+                                                   active=eng.t["game_active"])
         recs = states.cpu().numpy()
         active = eng.t["game_active"].cpu().numpy() != 0
         out = np.zeros((eng.G,), dtype=np.int32)

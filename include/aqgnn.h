@@ -436,6 +436,26 @@ int aqg_agent_mcts(int board_size, const uint8_t* states72, int B, int evaluatio
                    const double* uniforms, int uniforms_stride, uint64_t seed, void* workspace, size_t workspace_bytes,
                    int32_t* action, int32_t* visits, uint8_t* actions, int32_t* count, int32_t* draws, void* stream);
 
+/* Depth-limited alpha-beta (agents.py:22-107) for B states at once (csrc/agents.hip; additive to ABI 15).  Device pointers,
+ * stream-ordered, no allocation, no host synchronisation, no atomics, integer arithmetic only: two runs give identical bytes.
+ * aqg_agent_shortest_paths: out [B,2] i32 = the plies the mover (out[b][0]) and the other side (out[b][1]) need to reach their goal
+ *   rows over legal_actions_pos with the other pawn frozen, -1 = walled in: what aqg_host_shortest_path returns for the record and
+ *   for its flipped record.  heuristic_eval is (out[b][1] - out[b][0]) / max_dist_from_goal, one float64 division by the caller.
+ * aqg_agent_alpha_beta: action [B] i32 = aqg_host_alpha_beta_action of every record (-1 = no legal action), the FIRST root action
+ *   with the maximal depth-limited negamax value.  One wavefront per (state, root action): root child 0 with the full window, the
+ *   others in parallel under its value, then the first maximum; scores are compared as the integer numerators over
+ *   max_dist_from_goal, which orders them exactly as the host's float64 values.  active: NULL, or [B] u8 (an engine's game_active):
+ *   action[b] = 0 where active[b] == 0, without a search.  0 <= max_depth <= AQG_AGENT_AB_MAX_DEPTH, 1 <= max_dist_from_goal.
+ *   nodes: NULL, or [B] i64 = the positions visited below the root (0 on a masked slot); it differs from the host's count because
+ *   the children of a last-ply node are evaluated 64 at a time and root children 1.. do not see each other's scores.
+ *   workspace: aqg_agent_alpha_beta_workspace_bytes(board_size, B, max_depth) bytes (0 = invalid board_size, B or max_depth). */
+#define AQG_AGENT_AB_MAX_DEPTH 4
+int aqg_agent_shortest_paths(int board_size, const uint8_t* states72, int B, int32_t* out, void* stream);
+size_t aqg_agent_alpha_beta_workspace_bytes(int board_size, int B, int max_depth);
+int aqg_agent_alpha_beta(int board_size, const uint8_t* states72, int B, const uint8_t* active, int plies_for_draw,
+                         int max_dist_from_goal, int max_depth, void* workspace, size_t workspace_bytes, int32_t* action,
+                         int64_t* nodes, void* stream);
+
 /* ------------------------------------------------------------------ training step (train_network.py:68-95 on the GNN) */
 
 /* One optimisation step on a batch of positions: forward, the reference's losses (CrossEntropyLoss applied to the
