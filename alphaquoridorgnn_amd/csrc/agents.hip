@@ -592,30 +592,23 @@ __global__ __launch_bounds__(256) void engine_apply_actions_kernel(aqg_engine e,
 // ------------------------------------------------------------------------------------------------
 // host-side enqueue (no sync, no allocation)
 // ------------------------------------------------------------------------------------------------
-#define AQG_AGENT_DISPATCH(N, CALL)                                   \
-    switch (N) {                                                      \
-        case 3: CALL(3); break;                                       \
-        case 5: CALL(5); break;                                       \
-        case 7: CALL(7); break;                                       \
-        case 9: CALL(9); break;                                       \
-        default: return fail("unsupported board_size (odd 3..9)");    \
-    }
-
 int launch_agent_random(int N, const uint8_t* states72, int B, const double* uniforms, int stride, uint64_t seed, int32_t* actions,
                         hipStream_t st) {
     if (B <= 0) return 0;
-#define CALL_AR(n) hipLaunchKernelGGL(agent_random_kernel<n>, dim3(B), dim3(64), 0, st, states72, B, uniforms, stride, seed, actions)
-    AQG_AGENT_DISPATCH(N, CALL_AR)
-    return check_launch("agent_random_kernel");
+    return for_board_size(N, [&](auto n) {
+        hipLaunchKernelGGL(agent_random_kernel<decltype(n)::value>, dim3(B), dim3(64), 0, st, states72, B, uniforms, stride, seed, actions);
+        return check_launch("agent_random_kernel");
+    });
 }
 
 int launch_playouts(int N, const uint8_t* states72, int B, int plies_for_draw, const double* uniforms, int stride, uint64_t seed,
                     int32_t* value, int32_t* plies, int32_t* draws, uint8_t* final72, hipStream_t st) {
     if (B <= 0) return 0;
-#define CALL_PO(n) hipLaunchKernelGGL(playouts_kernel<n>, dim3(B), dim3(64), 0, st, states72, B, plies_for_draw, uniforms, stride, seed, \
-                                      value, plies, draws, final72)
-    AQG_AGENT_DISPATCH(N, CALL_PO)
-    return check_launch("playouts_kernel");
+    return for_board_size(N, [&](auto n) {
+        hipLaunchKernelGGL(playouts_kernel<decltype(n)::value>, dim3(B), dim3(64), 0, st, states72, B, plies_for_draw, uniforms, stride, seed,
+                           value, plies, draws, final72);
+        return check_launch("playouts_kernel");
+    });
 }
 
 size_t agent_mcts_workspace_bytes(int B, int evaluations) {
@@ -630,23 +623,25 @@ int launch_agent_mcts(int N, const uint8_t* states72, int B, int evaluations, in
     if (workspace_bytes < agent_mcts_workspace_bytes(B, evaluations)) return fail("aqg_agent_mcts: workspace too small");
     const int cap = agent_node_cap(evaluations);
     AgentNode* pool = reinterpret_cast<AgentNode*>(workspace);
-#define CALL_AM(n) hipLaunchKernelGGL(agent_mcts_kernel<n>, dim3(B), dim3(64), 0, st, states72, B, evaluations, plies_for_draw, explore, \
-                                      uniforms, stride, seed, pool, cap, action, visits, actions, count, draws)
-    AQG_AGENT_DISPATCH(N, CALL_AM)
-    return check_launch("agent_mcts_kernel");
+    return for_board_size(N, [&](auto n) {
+        hipLaunchKernelGGL(agent_mcts_kernel<decltype(n)::value>, dim3(B), dim3(64), 0, st, states72, B, evaluations, plies_for_draw, explore,
+                           uniforms, stride, seed, pool, cap, action, visits, actions, count, draws);
+        return check_launch("agent_mcts_kernel");
+    });
 }
 
 int launch_agent_shortest_paths(int N, const uint8_t* states72, int B, int32_t* out, hipStream_t st) {
     if (B <= 0) return 0;
-#define CALL_SP(n) hipLaunchKernelGGL(agent_shortest_paths_kernel<n>, dim3((B + 255) / 256), dim3(256), 0, st, states72, B, out)
-    AQG_AGENT_DISPATCH(N, CALL_SP)
-    return check_launch("agent_shortest_paths_kernel");
+    return for_board_size(N, [&](auto n) {
+        hipLaunchKernelGGL(agent_shortest_paths_kernel<decltype(n)::value>, dim3((B + 255) / 256), dim3(256), 0, st, states72, B, out);
+        return check_launch("agent_shortest_paths_kernel");
+    });
 }
 
 constexpr int AB_MAX_STATES = 1 << 23;       // B * (MAX_LEGAL - 1) blocks fit a grid
 
 size_t agent_alpha_beta_workspace_bytes(int N, int B, int max_depth) {
-    if (!(N == 3 || N == 5 || N == 7 || N == 9) || B <= 0 || B > AB_MAX_STATES || max_depth < 0 || max_depth > AB_MAX_DEPTH) return 0;
+    if (!board_size_supported(N) || B <= 0 || B > AB_MAX_STATES || max_depth < 0 || max_depth > AB_MAX_DEPTH) return 0;
     return ab_workspace_bytes(B);
 }
 
@@ -656,21 +651,22 @@ int launch_agent_alpha_beta(int N, const uint8_t* states72, int B, const uint8_t
     if (B > AB_MAX_STATES) return fail("aqg_agent_alpha_beta: too many states in one call");
     if (workspace_bytes < ab_workspace_bytes(B)) return fail("aqg_agent_alpha_beta: workspace too small");
     const AbWorkspace w = ab_workspace(workspace, B);
-#define CALL_AB0(n) hipLaunchKernelGGL(agent_alpha_beta_kernel<n>, dim3(B), dim3(64), 0, st, states72, B, active, plies_for_draw, max_dist, \
-                                       max_depth, 0, w)
-    AQG_AGENT_DISPATCH(N, CALL_AB0)
-    if (int r = check_launch("agent_alpha_beta_kernel (root child 0)")) return r;
-#define CALL_AB1(n) hipLaunchKernelGGL(agent_alpha_beta_kernel<n>, dim3((unsigned)B * (MAX_LEGAL - 1)), dim3(64), 0, st, states72, B, active, \
-                                       plies_for_draw, max_dist, max_depth, 1, w)
-    AQG_AGENT_DISPATCH(N, CALL_AB1)
-    if (int r = check_launch("agent_alpha_beta_kernel (root children 1..)")) return r;
+    const int launched = for_board_size(N, [&](auto n) {
+        constexpr int NN = decltype(n)::value;
+        hipLaunchKernelGGL(agent_alpha_beta_kernel<NN>, dim3(B), dim3(64), 0, st, states72, B, active, plies_for_draw, max_dist, max_depth, 0, w);
+        if (int r = check_launch("agent_alpha_beta_kernel (root child 0)")) return r;
+        hipLaunchKernelGGL(agent_alpha_beta_kernel<NN>, dim3((unsigned)B * (MAX_LEGAL - 1)), dim3(64), 0, st, states72, B, active,
+                           plies_for_draw, max_dist, max_depth, 1, w);
+        return check_launch("agent_alpha_beta_kernel (root children 1..)");
+    });
+    if (launched) return launched;
     hipLaunchKernelGGL(agent_alpha_beta_pick_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, active, w, action, nodes);
     return check_launch("agent_alpha_beta_pick_kernel");
 }
 
 int engine_root_states72(const aqg_engine& e, uint8_t* out72, hipStream_t st) {
     const int N = e.board_size;
-    if (!(N == 3 || N == 5 || N == 7 || N == 9)) return fail("unsupported board_size");
+    if (!board_size_supported(N)) return fail("unsupported board_size");
     if (e.num_games <= 0 || !e.root_state) return fail("aqg_engine_root_states72: incomplete engine");
     hipLaunchKernelGGL(engine_root_states72_kernel, dim3((e.num_games + 255) / 256), dim3(256), 0, st, e, out72);
     return check_launch("engine_root_states72_kernel");
@@ -683,9 +679,11 @@ int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_
     if (e.max_plies > 0 && (!e.hist_state72 || !e.hist_visits || !e.hist_action)) return fail("aqg_engine_apply_actions: history buffers missing");
     if (e.quota < e.num_games) return fail("quota must be >= num_games");
     const dim3 grid((e.num_games + 3) / 4), block(256);
-#define CALL_AA(n) hipLaunchKernelGGL(engine_apply_actions_kernel<n>, grid, block, 0, st, e, actions)
-    AQG_AGENT_DISPATCH(e.board_size, CALL_AA)
-    if (int r = check_launch("engine_apply_actions_kernel")) return r;
+    const int launched = for_board_size(e.board_size, [&](auto n) {
+        hipLaunchKernelGGL(engine_apply_actions_kernel<decltype(n)::value>, grid, block, 0, st, e, actions);
+        return check_launch("engine_apply_actions_kernel");
+    });
+    if (launched) return launched;
     return e.quota > e.num_games ? engine_refill(e, st) : 0;
 }
 

@@ -58,6 +58,14 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 #include "quoridor_core.hpp"
 
 namespace aqg {
+// with_board_size (quoridor_core.hpp) for the launchers: `launch` takes the board size as std::integral_constant and returns the
+// launcher's status; an unsupported size is an error with its message, whatever a validate() in front has already refused
+template <class F>
+inline int for_board_size(int N, F&& launch) {
+    if (!board_size_supported(N)) return fail("unsupported board_size (odd 3..9)");
+    return with_board_size(N, -1, launch);
+}
+
 __device__ __forceinline__ QState load_state(const void* base, int fmt, size_t b) {
     if (fmt == 0) return unpack72(reinterpret_cast<const uint8_t*>(base) + b * STATE72);
     const uint64_t* q = reinterpret_cast<const uint64_t*>(base) + b * 3;

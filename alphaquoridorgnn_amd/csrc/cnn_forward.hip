@@ -197,12 +197,7 @@ int launch_conv_n(int B, int Cin, int Cout, const float* X, const float* Wp, con
 
 int launch_conv(int N, int B, int Cin, int Cout, const float* X, const float* Wp, const float* scale, const float* shift, const float* res,
                 const uint8_t* active, float* H, float* pooled, hipStream_t st) {
-    switch (N) {
-        case 3: return launch_conv_n<3>(B, Cin, Cout, X, Wp, scale, shift, res, active, H, pooled, st);
-        case 5: return launch_conv_n<5>(B, Cin, Cout, X, Wp, scale, shift, res, active, H, pooled, st);
-        case 7: return launch_conv_n<7>(B, Cin, Cout, X, Wp, scale, shift, res, active, H, pooled, st);
-        default: return launch_conv_n<9>(B, Cin, Cout, X, Wp, scale, shift, res, active, H, pooled, st);
-    }
+    return for_board_size(N, [&](auto n) { return launch_conv_n<decltype(n)::value>(B, Cin, Cout, X, Wp, scale, shift, res, active, H, pooled, st); });
 }
 
 struct CnnWorkspace { float* x0; float* xa; float* xt; float* pooled; float* logits; float* vpre; };
@@ -218,8 +213,6 @@ inline size_t cnn_ws_layout(int N, int F, int A, int B, CnnWorkspace* ws, float*
     }
     return total;
 }
-
-bool board_ok(int N) { return N == 3 || N == 5 || N == 7 || N == 9; }
 
 // the network after the input rows: 2 L + 1 convs, pool, heads
 int cnn_trunk_heads(int N, int B, const aqg_cnn_net* net, const uint8_t* active, const CnnWorkspace& ws, float* pooled, float* logits,
@@ -292,7 +285,7 @@ int launch_cnn_pack(int F, int L, int A, const float* const* params, const float
 }
 
 size_t cnn_workspace_floats(int N, int F, int A, int B) {
-    if (!board_ok(N) || F < 1 || F > AQG_CNN_MAX_FILTERS || A < 1 || B <= 0) return 0;
+    if (!board_size_supported(N) || F < 1 || F > AQG_CNN_MAX_FILTERS || A < 1 || B <= 0) return 0;
     return cnn_ws_layout(N, F, A, B, nullptr, nullptr);
 }
 
@@ -301,7 +294,7 @@ static int cnn_forward(const char* what, int N, const void* states, int fmt, con
                        const uint8_t* active, float* workspace, size_t workspace_floats, float* pooled, float* logits, float* policy,
                        float* value_pre, float* value, hipStream_t st) {
     const char* why = "";
-    if (!board_ok(N)) return fail(what, "board_size must be 3, 5, 7 or 9");
+    if (!board_size_supported(N)) return fail(what, "board_size must be 3, 5, 7 or 9");
     if (!planes && fmt != 0 && fmt != 1) return fail(what, "state_fmt must be 0 or 1");
     if (B < 0) return fail(what, "negative size");
     if (check_cnn_net(net, N, &why)) return fail(what, why);

@@ -158,13 +158,7 @@ int launch_layer_n(int B, int K, int Nout, const float* X, const float* W, const
 int launch_board_gcn_layer(int N, int B, int K, int Nout, const float* X, const float* W, const float* bias, const int32_t* ell_idx,
                            const float* ell_w, const uint8_t* active, float* H, float* pooled, hipStream_t st) {
     if (B <= 0 || Nout <= 0) return 0;
-    switch (N) {
-        case 3: return launch_layer_n<3>(B, K, Nout, X, W, bias, ell_idx, ell_w, active, H, pooled, st);
-        case 5: return launch_layer_n<5>(B, K, Nout, X, W, bias, ell_idx, ell_w, active, H, pooled, st);
-        case 7: return launch_layer_n<7>(B, K, Nout, X, W, bias, ell_idx, ell_w, active, H, pooled, st);
-        case 9: return launch_layer_n<9>(B, K, Nout, X, W, bias, ell_idx, ell_w, active, H, pooled, st);
-        default: return fail("board_size must be 3, 5, 7 or 9");
-    }
+    return for_board_size(N, [&](auto n) { return launch_layer_n<decltype(n)::value>(B, K, Nout, X, W, bias, ell_idx, ell_w, active, H, pooled, st); });
 }
 
 size_t boards_general_workspace_floats(int N, int hidden, int A, int B) {
@@ -187,7 +181,7 @@ int launch_gcn_forward_boards_general(int N, const void* states, int fmt, int B,
                                       const uint8_t* active, float* workspace, size_t workspace_floats, float* pooled, float* logits,
                                       float* policy, float* value_pre, float* value, hipStream_t st) {
     const char* why = "";
-    if (!(N == 3 || N == 5 || N == 7 || N == 9)) return fail("aqg_gcn_forward_boards_general: board_size must be 3, 5, 7 or 9");
+    if (!board_size_supported(N)) return fail("aqg_gcn_forward_boards_general: board_size must be 3, 5, 7 or 9");
     if (fmt != 0 && fmt != 1) return fail("aqg_gcn_forward_boards_general: state_fmt must be 0 or 1");
     if (B < 0) return fail("aqg_gcn_forward_boards_general: negative size");
     if (check_general_net(net, &why)) return fail("aqg_gcn_forward_boards_general", why);

@@ -1891,12 +1891,8 @@ int launch_gcn_forward_boards_any(int N, const void* states, int fmt, int B, con
     int32_t* ell_idx = reinterpret_cast<int32_t*>(ell_w + (size_t)R * 5);
     float* work0 = reinterpret_cast<float*>(ell_idx + (size_t)R * 5);
     float* work1 = work0 + (size_t)R * HID;
-    const dim3 pg((R + 255) / 256), lg((R + 31) / 32), gg((R + 3) / 4), blk(256);
-    switch (N) {
-        case 3: hipLaunchKernelGGL(boards_prep_kernel<3>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
-        case 5: hipLaunchKernelGGL(boards_prep_kernel<5>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
-        default: hipLaunchKernelGGL(boards_prep_kernel<7>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
-    }
+    const dim3 lg((R + 31) / 32), gg((R + 3) / 4), blk(256);
+    if (int r = launch_gcn_boards_graph(N, states, fmt, B, x0, ell_idx, ell_w, st)) return r;
     hipLaunchKernelGGL(graph_linear_kernel<true>, lg, blk, 0, st, (const float*)x0, 6, R, packed + PackedLayout::W1, work0);
     hipLaunchKernelGGL(ell_gather_kernel, gg, blk, 0, st, (const float*)work0, R, (const int32_t*)ell_idx, (const float*)ell_w, packed + PackedLayout::B1, work1);
     hipLaunchKernelGGL(graph_linear_kernel<false>, lg, blk, 0, st, (const float*)work1, HID, R, packed + PackedLayout::W2T, work0);
@@ -1914,32 +1910,26 @@ int launch_gcn_forward_boards_any(int N, const void* states, int fmt, int B, con
 // The board featuriser alone, for the width-generic graph primitives (gcn_general.hip): x0 [B*V,6] node features and the
 // normalised adjacency as ELL rows of 5 (self loop first, then the open neighbours; a closed side has index -1, weight 0).
 int launch_gcn_boards_graph(int N, const void* states, int fmt, int B, float* x0, int32_t* ell_idx, float* ell_w, hipStream_t st) {
-    if (!(N == 3 || N == 5 || N == 7 || N == 9)) return fail("board_size must be 3, 5, 7 or 9");
+    if (!board_size_supported(N)) return fail("board_size must be 3, 5, 7 or 9");
     if (B <= 0) return 0;
     const int R = B * N * N;
     const dim3 pg((R + 255) / 256), blk(256);
-    switch (N) {
-        case 3: hipLaunchKernelGGL(boards_prep_kernel<3>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
-        case 5: hipLaunchKernelGGL(boards_prep_kernel<5>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
-        case 7: hipLaunchKernelGGL(boards_prep_kernel<7>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
-        default: hipLaunchKernelGGL(boards_prep_kernel<9>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w); break;
-    }
-    return check_launch("boards_prep_kernel");
+    return for_board_size(N, [&](auto n) {
+        hipLaunchKernelGGL(boards_prep_kernel<decltype(n)::value>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w);
+        return check_launch("boards_prep_kernel");
+    });
 }
 
 // The featuriser's node features alone: x0 [B*V,6], the six planes of pv_network_cnn.py:88-114 tile by tile (the CNN's input).
 int launch_gcn_boards_features(int N, const void* states, int fmt, int B, float* x0, hipStream_t st) {
-    if (!(N == 3 || N == 5 || N == 7 || N == 9)) return fail("board_size must be 3, 5, 7 or 9");
+    if (!board_size_supported(N)) return fail("board_size must be 3, 5, 7 or 9");
     if (B <= 0) return 0;
     const int R = B * N * N;
     const dim3 pg((R + 255) / 256), blk(256);
-    switch (N) {
-        case 3: hipLaunchKernelGGL((boards_prep_kernel<3, false>), pg, blk, 0, st, states, fmt, B, x0, nullptr, nullptr); break;
-        case 5: hipLaunchKernelGGL((boards_prep_kernel<5, false>), pg, blk, 0, st, states, fmt, B, x0, nullptr, nullptr); break;
-        case 7: hipLaunchKernelGGL((boards_prep_kernel<7, false>), pg, blk, 0, st, states, fmt, B, x0, nullptr, nullptr); break;
-        default: hipLaunchKernelGGL((boards_prep_kernel<9, false>), pg, blk, 0, st, states, fmt, B, x0, nullptr, nullptr); break;
-    }
-    return check_launch("boards_prep_kernel");
+    return for_board_size(N, [&](auto n) {
+        hipLaunchKernelGGL((boards_prep_kernel<decltype(n)::value, false>), pg, blk, 0, st, states, fmt, B, x0, nullptr, nullptr);
+        return check_launch("boards_prep_kernel");
+    });
 }
 
 }  // namespace aqg

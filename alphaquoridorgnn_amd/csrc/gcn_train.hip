@@ -1462,18 +1462,15 @@ static int launch_final(const aqg_train& t, int B, bool compute, bool update, in
 
 static int forward_backward(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, int first,
                             int B, hipStream_t st) {
-    switch (t.board_size) {
-        case 3: launch_forward_backward<3>(t, states72, pi, z, order, first, B, st); break;
-        case 5: launch_forward_backward<5>(t, states72, pi, z, order, first, B, st); break;
-        case 7: launch_forward_backward<7>(t, states72, pi, z, order, first, B, st); break;
-        default: launch_forward_backward<9>(t, states72, pi, z, order, first, B, st); break;
-    }
-    return check_launch("training forward/backward kernels");
+    return for_board_size(t.board_size, [&](auto n) {
+        launch_forward_backward<decltype(n)::value>(t, states72, pi, z, order, first, B, st);
+        return check_launch("training forward/backward kernels");
+    });
 }
 
 static int validate(const aqg_train& t) {
     const int N = t.board_size, A = t.policy_size;
-    if (!(N == 3 || N == 5 || N == 7 || N == 9)) return fail("board_size must be 3, 5, 7 or 9");
+    if (!board_size_supported(N)) return fail("board_size must be 3, 5, 7 or 9");
     if (A != N * N + 2 * (N - 1) * (N - 1) || A > 256) return fail("policy_size does not match the board");
     return 0;
 }

@@ -262,12 +262,7 @@ int launch_layer_backward_n(int B, int Hd, int K, const float* dP, const float* 
 
 int launch_layer_backward(int N, int B, int Hd, int K, const float* dP, const float* W, const float* Hprev, const int32_t* ell_idx,
                           const float* ell_w, float* dZ, float* dPprev, hipStream_t st) {
-    switch (N) {
-        case 3: return launch_layer_backward_n<3>(B, Hd, K, dP, W, Hprev, ell_idx, ell_w, dZ, dPprev, st);
-        case 5: return launch_layer_backward_n<5>(B, Hd, K, dP, W, Hprev, ell_idx, ell_w, dZ, dPprev, st);
-        case 7: return launch_layer_backward_n<7>(B, Hd, K, dP, W, Hprev, ell_idx, ell_w, dZ, dPprev, st);
-        default: return launch_layer_backward_n<9>(B, Hd, K, dP, W, Hprev, ell_idx, ell_w, dZ, dPprev, st);
-    }
+    return for_board_size(N, [&](auto n) { return launch_layer_backward_n<decltype(n)::value>(B, Hd, K, dP, W, Hprev, ell_idx, ell_w, dZ, dPprev, st); });
 }
 
 // forward, losses and backward of B positions (rows order[first ..] or first ..): gradients into t.grads, per-position losses
@@ -351,7 +346,7 @@ int launch_finish(const aqg_train_general& t, int B, bool update, int step, cons
 
 int validate(const aqg_train_general& t, const char* what) {
     const int N = t.board_size;
-    if (!(N == 3 || N == 5 || N == 7 || N == 9)) return fail(what, "board_size must be 3, 5, 7 or 9");
+    if (!board_size_supported(N)) return fail(what, "board_size must be 3, 5, 7 or 9");
     aqg_gcn_general_net net{};
     net.num_features = t.num_features; net.hidden = t.hidden; net.num_layers = t.num_layers; net.policy_size = t.policy_size;
     const char* why = "";
@@ -379,7 +374,7 @@ int launch_train_general_loss(int B, int A, const float* policy, const float* va
 }
 
 size_t train_general_workspace_floats(int N, int hidden, int num_layers, int policy_size, int max_batch) {
-    if (!(N == 3 || N == 5 || N == 7 || N == 9) || hidden < 2 || hidden > 1024 || num_layers < 1 || num_layers > AQG_GENERAL_MAX_LAYERS ||
+    if (!board_size_supported(N) || hidden < 2 || hidden > 1024 || num_layers < 1 || num_layers > AQG_GENERAL_MAX_LAYERS ||
         policy_size < 1 || policy_size > 4096 || max_batch < 1)
         return 0;
     return train_layout(N, hidden, num_layers, policy_size, max_batch, nullptr, nullptr);   // monotone in the batch: O(1) host work

@@ -82,64 +82,43 @@ template <int N> int alpha_beta_action(const QState& s, int draw, int max_dist, 
 }
 }  // namespace
 
-#define AQG_HOST_DISPATCH(N, EXPR3, EXPR5, EXPR7, EXPR9) \
-    switch (N) { case 3: return EXPR3; case 5: return EXPR5; case 7: return EXPR7; case 9: return EXPR9; default: return -1; }
-
+// (an unsupported board size returns each entry point's own error value: -1, -2 or NaN)
 extern "C" {
 
 int aqg_host_legal_actions(int board_size, const uint8_t* rec72, uint8_t* out136) {
     if (!rec72 || !out136) return -1;
     const QState s = unpack72(rec72);
-    AQG_HOST_DISPATCH(board_size, legal_actions_serial<3>(s, out136), legal_actions_serial<5>(s, out136), legal_actions_serial<7>(s, out136),
-                      legal_actions_serial<9>(s, out136))
+    return with_board_size(board_size, -1, [&](auto n) { return legal_actions_serial<decltype(n)::value>(s, out136); });
 }
 
 int aqg_host_next(int board_size, const uint8_t* rec72, int action, uint8_t* out72) {
     if (!rec72 || !out72) return -1;
     const QState s = unpack72(rec72);
-    QState t;
-    switch (board_size) {
-        case 3: t = next_state<3>(s, action); break;
-        case 5: t = next_state<5>(s, action); break;
-        case 7: t = next_state<7>(s, action); break;
-        case 9: t = next_state<9>(s, action); break;
-        default: return -1;
-    }
-    pack72(t, board_size, out72);
-    return 0;
+    return with_board_size(board_size, -1, [&](auto n) {
+        pack72(next_state<decltype(n)::value>(s, action), board_size, out72);
+        return 0;
+    });
 }
 
 int aqg_host_shortest_path(int board_size, const uint8_t* rec72) {
     if (!rec72) return -2;
     const QState s = unpack72(rec72);
-    switch (board_size) {
-        case 3: return shortest_path<3>(s);
-        case 5: return shortest_path<5>(s);
-        case 7: return shortest_path<7>(s);
-        case 9: return shortest_path<9>(s);
-        default: return -2;
-    }
+    return with_board_size(board_size, -2, [&](auto n) { return shortest_path<decltype(n)::value>(s); });
 }
 
 double aqg_host_heuristic_eval(int board_size, const uint8_t* rec72, int max_dist_from_goal) {
     if (!rec72 || max_dist_from_goal == 0) return 0.0;
     const QState s = unpack72(rec72);
-    switch (board_size) {
-        case 3: return heuristic<3>(s, max_dist_from_goal);
-        case 5: return heuristic<5>(s, max_dist_from_goal);
-        case 7: return heuristic<7>(s, max_dist_from_goal);
-        case 9: return heuristic<9>(s, max_dist_from_goal);
-        default: return std::numeric_limits<double>::quiet_NaN();      // unsupported board size: an error value, like the siblings' -1 / -2
-    }
+    return with_board_size(board_size, std::numeric_limits<double>::quiet_NaN(),
+                           [&](auto n) { return heuristic<decltype(n)::value>(s, max_dist_from_goal); });
 }
 
 int aqg_host_alpha_beta_action(int board_size, const uint8_t* rec72, int plies_for_draw, int max_dist_from_goal, int max_depth) {
     if (!rec72 || max_dist_from_goal == 0 || max_depth < 0) return -1;
     const QState s = unpack72(rec72);
-    AQG_HOST_DISPATCH(board_size, alpha_beta_action<3>(s, plies_for_draw, max_dist_from_goal, max_depth),
-                      alpha_beta_action<5>(s, plies_for_draw, max_dist_from_goal, max_depth),
-                      alpha_beta_action<7>(s, plies_for_draw, max_dist_from_goal, max_depth),
-                      alpha_beta_action<9>(s, plies_for_draw, max_dist_from_goal, max_depth))
+    return with_board_size(board_size, -1, [&](auto n) {
+        return alpha_beta_action<decltype(n)::value>(s, plies_for_draw, max_dist_from_goal, max_depth);
+    });
 }
 
 }  // extern "C"

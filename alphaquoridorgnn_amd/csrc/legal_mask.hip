@@ -46,38 +46,32 @@ __global__ void state_status_kernel(const uint8_t* __restrict__ in, int B, int d
     flags[b] = (uint8_t)((is_lose<N>(s) ? 1 : 0) | (is_draw(s, draw) ? 2 : 0));
 }
 
-#define AQG_DISPATCH_N(N, CALL)                  \
-    switch (N) {                                 \
-        case 3: CALL(3); break;                  \
-        case 5: CALL(5); break;                  \
-        case 7: CALL(7); break;                  \
-        case 9: CALL(9); break;                  \
-        default: return fail("unsupported board_size (odd 3..9)"); \
-    }
-
 int launch_legal_actions(int N, const void* states, int fmt, int B, uint8_t* mask, uint8_t* order, int32_t* count,
                          const uint8_t* active, hipStream_t st) {
     if (B <= 0) return 0;
     dim3 grid((B + 3) / 4), block(256);
-#define CALL_LA(n) hipLaunchKernelGGL(legal_actions_kernel<n>, grid, block, 0, st, states, fmt, B, mask, order, count, active)
-    AQG_DISPATCH_N(N, CALL_LA)
-    return check_launch("legal_actions_kernel");
+    return for_board_size(N, [&](auto n) {
+        hipLaunchKernelGGL(legal_actions_kernel<decltype(n)::value>, grid, block, 0, st, states, fmt, B, mask, order, count, active);
+        return check_launch("legal_actions_kernel");
+    });
 }
 
 int launch_state_next(int N, const uint8_t* in, const int32_t* actions, int B, uint8_t* out, hipStream_t st) {
     if (B <= 0) return 0;
     dim3 grid((B + 255) / 256), block(256);
-#define CALL_SN(n) hipLaunchKernelGGL(state_next_kernel<n>, grid, block, 0, st, in, actions, B, out)
-    AQG_DISPATCH_N(N, CALL_SN)
-    return check_launch("state_next_kernel");
+    return for_board_size(N, [&](auto n) {
+        hipLaunchKernelGGL(state_next_kernel<decltype(n)::value>, grid, block, 0, st, in, actions, B, out);
+        return check_launch("state_next_kernel");
+    });
 }
 
 int launch_state_status(int N, const uint8_t* in, int B, int draw, uint8_t* flags, hipStream_t st) {
     if (B <= 0) return 0;
     dim3 grid((B + 255) / 256), block(256);
-#define CALL_SS(n) hipLaunchKernelGGL(state_status_kernel<n>, grid, block, 0, st, in, B, draw, flags)
-    AQG_DISPATCH_N(N, CALL_SS)
-    return check_launch("state_status_kernel");
+    return for_board_size(N, [&](auto n) {
+        hipLaunchKernelGGL(state_status_kernel<decltype(n)::value>, grid, block, 0, st, in, B, draw, flags);
+        return check_launch("state_status_kernel");
+    });
 }
 
 }  // namespace aqg

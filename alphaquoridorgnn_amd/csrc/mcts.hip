@@ -204,107 +204,6 @@ __global__ void engine_begin_move_kernel(aqg_engine e) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// select: descend by PUCT to a terminal node (back up at once) or to an unexpanded leaf (emit its state)
-// ------------------------------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ void game_select(const aqg_engine& e, int g, int lane, int active, QState s) {
-    if (!active) { if (lane == 0) e.leaf_flag[g] = 0; return; }
-    if (lane == 0) e.leaf_flag[g] = 0;
-    NodeRec* __restrict__ nodes = game_nodes(e, g);
-    int* path = e.path + (size_t)g * (e.sims + 2);
-    int node = 0, depth = 0;
-    int mynode = 0;                      // lane d keeps the path node at depth d (d < 64) in a register
-    if (lane == 0) path[0] = 0;
-    int terminal = 0;
-    double value = 0.0;
-    uint32_t kids = nodes[0].kids;       // child range of the current node (wave-uniform)
-    for (;;) {
-        const bool lose = is_lose<N>(s), draw = is_draw(s, e.plies_for_draw);
-        if (lose || draw) {                                    // pv_mcts.py:35-42
-            value = lose ? -1.0 : 0.0;
-            terminal = 1;
-            break;
-        }
-        const int cnt = (int)(kids >> 24), first = (int)(kids & 0xFFFFFF);
-        if (cnt == 0) break;                                   // pv_mcts.py:45 unexpanded leaf
-        // pv_mcts.py:69-78 next_child_node: each lane reads up to 3 whole child records
-        NodeRec rec[3];
-        int t = 0;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const int i = lane + 64 * r;
-            if (i < cnt) {
-                rec[r] = nodes[first + i];
-                t += rec[r].n;
-            } else { rec[r].w = 0.0; rec[r].p = 0.f; rec[r].n = 0; rec[r].kids = 0; rec[r].action = 0; }
-        }
-        t = wave_sum_i(t);
-        // f32(math.sqrt(t)): t < 2^24 is exact in f32 and the compiler's f32 square root is correctly rounded
-        // (-fhip-fp32-correctly-rounded-divide-sqrt, the default), and rounding sqrt to 53 bits first never changes the 24-bit
-        // result (a binary64 square root cannot land within half an ulp of a binary32 midpoint unless it IS one: 53 >= 2*24 + 2)
-        // -- so the f64 Newton chain (14 dependent double-rate instructions per level) is not needed.  The reference traces pin it.
-        const float st = sqrtf((float)t);
-        float best = -INFINITY; int besti = 0x7fffffff;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const int i = lane + 64 * r;
-            if (i < cnt) {
-                const float u = ((e.c_puct * rec[r].p) * st) / (float)(1 + rec[r].n);
-                const float q = rec[r].n ? (float)(-rec[r].w / (double)rec[r].n) : 0.0f;
-                const float sc = q + u;
-                if (sc > best) { best = sc; besti = i; }       // strict > keeps the lowest index within a lane
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {               // (max score, min index) across the wave
-            const float ob = __shfl_xor(best, off);
-            const int oi = __shfl_xor(besti, off);
-            if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
-        }
-        if (besti == 0x7fffffff) besti = 0;                    // all-NaN guard (np.argmax would return 0)
-        // the winner's kids / action live in lane (besti & 63), slot (besti >> 6)
-        const int slot = besti >> 6, src = besti & 63;
-        const uint32_t k_sel = slot == 0 ? rec[0].kids : (slot == 1 ? rec[1].kids : rec[2].kids);
-        const uint32_t a_sel = slot == 0 ? rec[0].action : (slot == 1 ? rec[1].action : rec[2].action);
-        kids = (uint32_t)__shfl((int)k_sel, src);
-        const int action = __shfl((int)a_sel, src);
-        node = first + besti;
-        s = next_state<N>(s, action);
-        ++depth;
-        if (lane == 0) path[depth] = node;
-        if (lane == (depth & 63) && depth < 64) mynode = node;
-    }
-    if (terminal) {
-        // backup (pv_mcts.py:36-42): lane d updates the node at depth d from its register copy; the (practically
-        // unreachable) part of a path deeper than 63 is finished by lane 0 from its own path[] stores
-        if (lane <= depth) {
-            NodeRec& r = nodes[mynode];
-            r.w += ((depth - lane) & 1) ? -value : value;
-            r.n += 1;
-            r.q = q_of(r.w, r.n);
-        }
-        if (lane == 0) {
-            e.stat_terminal_sims[g] += 1;
-            for (int d = 64; d <= depth; ++d) {
-                NodeRec& r = nodes[path[d]];
-                r.w += ((depth - d) & 1) ? -value : value;
-                r.n += 1;
-                r.q = q_of(r.w, r.n);
-            }
-        }
-    } else {
-        // unexpanded leaf: its legal actions are computed right here by the same wavefront (one lane per wall slot)
-        const int total = wave_legal_actions<N>(s, lane, nullptr, e.legal_order + (size_t)g * MAX_LEGAL);
-        if (lane == 0) {
-            store_state(e.leaf_state, g, s);
-            e.legal_count[g] = total;
-            e.path_len[g] = depth;
-            e.leaf_flag[g] = 1;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
 // `fake` evaluator (tests): oracle/mcts.py FakeModel, exact integer hash -> f32 priors (written over the
 // first `count` entries of policy[g]) and value.
 // ------------------------------------------------------------------------------------------------
@@ -353,97 +252,33 @@ __global__ __launch_bounds__(256) void engine_fake_eval_kernel(aqg_engine e) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// expand + backup (pv_mcts.py:47-57, :60-66)
-// ------------------------------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ void game_expand_backup(const aqg_engine& e, int g, int lane, int flag, int depth, int cnt, int first,
-                                                   float leaf_value) {
-    constexpr int A = Geo<N>::A;
-    // Round 1 of loads: everything whose address depends on nothing but g and the lane -- the caller's five scalars, this
-    // lane's legal-action bytes and its path entry -- is requested before the first branch, so the wave pays ONE memory
-    // round trip here instead of one per dependent step (the whole kernel is a latency chain).
-    NodeRec* __restrict__ nodes = game_nodes(e, g);
-    const int* path = e.path + (size_t)g * (e.sims + 2);
-    const uint8_t* ord = e.legal_order + (size_t)g * MAX_LEGAL;
-    const float* pol = e.policy + (size_t)g * A;
-    uint8_t oa[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) { const int i = lane + 64 * r; oa[r] = (i < MAX_LEGAL) ? ord[i] : (uint8_t)0; }
-    const int pnode = (lane < e.sims + 2) ? path[lane] : 0;           // path node at depth `lane`
-    if (flag != 1) return;
-    const int leaf = depth < 64 ? __shfl(pnode, depth) : path[depth];
-    float pl[3];
-    if (e.prior_mode == 0) {       // P0: gather at legal actions, divide by the sum unless 0 (pv_network_cnn.py:129-132)
-        float sum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const int i = lane + 64 * r;
-            pl[r] = (i < cnt) ? pol[oa[r]] : 0.f;
-            sum += pl[r];
-        }
-        sum = wave_sum_f(sum);
-        const float den = (sum != 0.f) ? sum : 1.f;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) pl[r] = pl[r] / den;
-    } else {                       // fake evaluator already wrote legal-ordered normalised priors
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const int i = lane + 64 * r;
-            pl[r] = (i < cnt) ? pol[i] : 0.f;
-        }
-    }
-    if (first + cnt <= e.node_cap && cnt > 0) {
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const int i = lane + 64 * r;
-            if (i < cnt) {
-                NodeRec c;
-                c.w = 0.0; c.p = pl[r]; c.n = 0; c.kids = 0; c.action = oa[r]; c.q = 0.f; c.cp = e.c_puct * pl[r];
-                nodes[first + i] = c;
-            }
-        }
-    }
-    if (lane == 0 && first + cnt <= e.node_cap && cnt > 0) {
-        nodes[leaf].kids = (uint32_t)first | ((uint32_t)cnt << 24);
-        e.node_count[g] = first + cnt;
-    }
-    // backup (pv_mcts.py:60-66): lane d updates the path node at depth d from its register copy; deeper parts of a path
-    // (practically unreachable) go through memory
-    {
-        const double v = (double)leaf_value;                       // value.item() -> python float
-        if (lane <= depth) {
-            NodeRec& r = nodes[pnode];
-            r.w += ((depth - lane) & 1) ? -v : v;
-            r.n += 1;
-            r.q = q_of(r.w, r.n);
-        }
-        for (int d = lane + 64; d <= depth; d += 64) {
-            NodeRec& r = nodes[path[d]];
-            r.w += ((depth - d) & 1) ? -v : v;
-            r.n += 1;
-            r.q = q_of(r.w, r.n);
-        }
-    }
-    if (lane == 0) e.stat_leaf_evals[g] += 1;   // per-game slot: a shared counter would serialise 2048 atomics per step
-}
-
-// ------------------------------------------------------------------------------------------------
-// The same step with the dependent memory rounds cut to the minimum (default; aqg_set_option("step_variant", 0) = the
-// two functions above behind one workgroup-scope fence).  The step is a latency chain: above, every phase waits for
-// its own loads -- scalars, legal list, policy gather, path, read-modify-write of the path nodes, root children, one
-// round per tree level -- about ten dependent round trips to L2/HBM per simulation.  Here:
+// The simulation step of one game, run by one wavefront (game_step_fast).  A launch does two things:
+//   expand + backup of the PREVIOUS simulation's leaf (pv_mcts.py:45-57, :59-66): the evaluator's policy is gathered at the
+//             leaf's legal actions and renormalised (pv_network_cnn.py:129-132; the other evaluators deliver priors in legal
+//             order), the children become contiguous NodeRecs, and every node of the old path gets w += +-value, n += 1 with the
+//             sign flipping per ply (:62);
+//   select    (pv_mcts.py:33-45 via next_child_node :69-78): from the root, the child with the largest PUCT score -- the first
+//             one among equals, np.argmax -- until a terminal position (backed up at once, :35-42) or an unexpanded leaf, whose
+//             state and legal actions are written out for the evaluator.
+// The step is a latency chain of one wave, so its dependent memory rounds are cut to the minimum:
 //   round 1   everything whose address follows from (game, lane) alone is requested at once: scalars, root state,
 //             legal list, old path, the whole policy row, the root record AND the root's children (node 1 ...: the root
 //             is expanded first in every move, so its children always start at node 1);
-//   no store -> load dependency inside the kernel: the previous simulation's backup and expansion are APPLIED IN
+//   no store -> load dependency inside a launch: the previous simulation's backup and expansion are APPLIED IN
 //             REGISTERS to whatever the descent loads (a child on the old path gets w += +-v, n += 1 -- the same
 //             float64 addition the store performs; the old leaf's children are the records just built), and written to
-//             memory behind the descent.  Every load therefore sees the state the previous launch left, whatever the
-//             timing, and the descent's only dependent rounds are the child blocks of levels >= 2;
+//             memory behind the descent.  No value the step uses is loaded from bytes this launch has written (the old
+//             leaf's new children are never read back: the descent stops there and takes their first), so every load
+//             sees the state the previous launch left, whatever the timing, and the descent's only dependent rounds are
+//             the child blocks of levels >= 2;
 //   the policy gather at the legal actions goes through 1 KB of LDS instead of a second global round.
-// Identical arithmetic, identical visit order: bit-exact with the reference traces like the variant above.  Paths
-// deeper than `fast_depth` (61; never seen) fall back to that variant mid-flight: pending updates are flushed, fenced,
-// and the descent continues on memory (the tests run the goldens with fast_depth 1 and 2 to exercise every hand-over).
+// Hand-over past `fast_depth` (option "step_fast_depth", 61 by default: never reached in play).  The register form keeps a
+// path in the wave's lanes, so it ends before depth 63: when the old path is deeper than fast_depth, its backup is a plain
+// read-modify-write through memory in front of the descent; when the new descent reaches fast_depth, the pending updates are
+// flushed.  Either way a workgroup-scope release / acquire fence follows -- the wave that stored is the wave that loads --
+// and from there every level reads memory, which is then current; path entries beyond depth 63 live in path[] alone.  Same
+// arithmetic, same visit order on both sides of the hand-over: bit-exact with the reference traces (the tests run the
+// recordings with fast_depth 0, 1, 2 and 5 to exercise every hand-over point).
 // ------------------------------------------------------------------------------------------------
 // Diagnostic build only (-DAQG_STAMP, tools/stamp_step.py; never shipped): lane 0 of every game adds the cycles spent in each
 // phase of the step to pooled[g][2 i .. 2 i + 1] as u64 (the fake-evaluator runs the tool uses never touch `pooled`).
@@ -464,7 +299,6 @@ __device__ __forceinline__ uint32_t eval_cache_misc(const QState& s) {
 int g_step_prio = 1;               // wave priority of the fast step kernel (0..3)
 int g_step_waves = 8;              // games (wavefronts) per workgroup of the fast step kernel (1, 2, 4 or 8).  Round 4: 8 -- at 96 registers two step
                                    // waves per SIMD fit beside one trunk workgroup, half as many workgroups: +0.5-0.8 % games/s at 2,048 and 16,384 games
-int g_step_variant = 1;
 int g_step_fast_depth = 61;
 
 // CACHE: the evaluation cache's code is compiled in (its own kernel instantiation: the cache-less kernel carries none of it)
@@ -575,7 +409,7 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
                 }
             }
         }
-        if (expanded) {
+        if (expanded) {                  // pv_mcts.py:52-56: one child per legal action, in legal_actions() order, with its prior
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
                 const int i = lane + 64 * r;
@@ -594,7 +428,8 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
     }
     const uint32_t kids_new = expanded ? ((uint32_t)first_new | ((uint32_t)cnt_new << 24)) : 0u;
     const double v_old = (double)value;                              // value.item() -> python float
-    // lane d <= depth_old holds the old path node at depth d: its record after the backup (pv_mcts.py:60-66), store pending
+    // lane d <= depth_old holds the old path node at depth d: its record after the backup (pv_mcts.py:49-50 for the leaf, :62-65 above
+    // it: `value = -child.evaluate()`, so the sign flips with every ply between the node and the leaf), store pending
     double bw = 0.0; int bn = 0;
     float bq = 0.f;                   // ... and its exploitation term after the backup: ONE float64 division per step, off the
                                       // descent's per-level chain (the levels below the root read it by v_readlane)
@@ -675,7 +510,11 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
         const bool patch = regs && onpath && depth < depth_old;
         const int pidx = patch ? __builtin_amdgcn_readlane(pnode, (depth + 1) & 63) - first : -1;
         const float pq = (patch && depth > 0) ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bq), (depth + 1) & 63)) : 0.f;
-        const float st = sqrtf((float)(npar - 1));                // == f32(math.sqrt(t)), see game_select; t = npar - 1
+        // f32(math.sqrt(t)) of pv_mcts.py:74, t = npar - 1 (:72): t < 2^24 is exact in f32 and the compiler's f32 square root is
+        // correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt, the default), and rounding sqrt to 53 bits first never changes
+        // the 24-bit result (a binary64 square root cannot land within half an ulp of a binary32 midpoint unless it IS one:
+        // 53 >= 2*24 + 2) -- so no f64 square root is needed on the level's chain.  The reference traces pin it.
+        const float st = sqrtf((float)(npar - 1));
         // At the root the patched child's q cannot come from lane 1 (that lane's record is the second load round): it is formed from
         // the round-1 copy of the child itself -- one float64 division per step, under a scalar branch, in front of the scores
         float q0fix = 0.f;
@@ -695,6 +534,7 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
         // straight-line scores: the slots' chains (patch by selects, int -> float, multiply, IEEE division, add) are independent, so
         // that the in-order issue of a lone wave interleaves them; nodes with at most 64 children (every node once the walls are
         // placed) take the one-slot copy of the same code
+        // PUCT, pv_mcts.py:74: (-w / n if n else 0.0) + C_PUCT * p * sqrt(t) / (1 + n), the exploration term left to right in f32
         auto score = [&](int r) {
             // (elements go through scalars: __builtin_bit_cast of a vector ELEMENT expression reads element 0 with hipcc 7.2)
             const uint32_t nb = hot[r][0], kb = hot[r][1], qb = hot[r][2], cb = hot[r][3];
@@ -711,9 +551,9 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
         } else {
             score(0); score(1); score(2);
         }
-        // np.argmax: the first index of the maximum.  Wave maximum by DPP, then the lowest child index holding it from up to three
+        // np.argmax (pv_mcts.py:78): the first index of the maximum.  Wave maximum by DPP, then the lowest child index holding it from up to three
         // ballots (children lane, lane + 64, lane + 128 in that order), masked to the node's children.  NaN scores never equal the
-        // maximum; if nothing matches (all NaN) child 0 is taken, as before.
+        // maximum; if nothing matches (all NaN) child 0 is taken, as np.argmax does.
         const float best = wave_max_dpp_asm(fmaxf(fmaxf(sc[0], sc[1]), sc[2]));
         const uint64_t v0 = cnt >= 64 ? ~0ull : ((1ull << cnt) - 1ull);
         const uint64_t m0 = __ballot(sc[0] == best) & v0;
@@ -970,9 +810,8 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
 // ------------------------------------------------------------------------------------------------
 // fused simulation step, one wavefront per game:
 //   [expand + backup of the PREVIOUS simulation's leaf]  ->  [select the next leaf + its legal actions]
-// Both halves touch only this game's pools, and the wave that wrote the children is the wave that reads them, so
-// a workgroup-scope fence is all the ordering needed.  Per simulation the engine then launches
-// step -> GNN trunk -> GNN heads (3 kernels instead of select / legal / trunk / heads / expand).
+// Both halves touch only this game's pools, and one wave does both, so no ordering between waves is needed.  Per simulation
+// the engine then launches step -> GNN trunk -> GNN heads (3 kernels instead of select / legal / trunk / heads / expand).
 // ------------------------------------------------------------------------------------------------
 template <int N, bool CACHE>
 __global__ __launch_bounds__(512) void engine_step_fast_kernel(aqg_engine e, int do_expand, int do_select, int fast_depth, int list_sim) {
@@ -990,43 +829,17 @@ __global__ __launch_bounds__(512) void engine_step_fast_kernel(aqg_engine e, int
 AQG_TRACE_SETTER(set_trace_mcts)
 
 template <int N>
-__global__ __launch_bounds__(256) void engine_step_kernel(aqg_engine e, int do_expand, int do_select) {
-    const int lane = threadIdx.x & 63;
-    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (g >= e.num_games) return;
-    // loads that depend on nothing but g: one round for both halves of the step
-    const int active = e.game_active[g];
-    const QState root = load_state(e.root_state, 1, g);
-    int flag = 0, depth = 0, cnt = 0, first = 0;
-    float value = 0.f;
-    if (do_expand) { flag = e.leaf_flag[g]; depth = e.path_len[g]; cnt = e.legal_count[g]; first = e.node_count[g]; value = e.value[g]; }
-    if (do_expand) game_expand_backup<N>(e, g, lane, flag, depth, cnt, first, value);
-    if (do_select) {
-        if (do_expand) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        }
-        game_select<N>(e, g, lane, active, root);
-    }
-}
-
-template <int N>
 static void launch_step(const aqg_engine& e_in, int do_expand, int do_select, hipStream_t st, int list_sim = -1) {
     // prior_mode 3 and 4 leave the network's dense [G,A] policy in e.policy exactly like prior_mode 0: the step kernels gather,
     // renormalise and cache it as mode 0 -- they are handed the struct with prior_mode 0, so no step kernel knows mode 3 or 4
     aqg_engine e = e_in;
     if (e.prior_mode == 3 || e.prior_mode == 4) e.prior_mode = 0;
-    const dim3 grid((e.num_games + 3) / 4), block(256);
     if (g_profile_trunk == 2) profile_mark(st, e.num_games);       // measurement mode 2: the event pairs bracket the step launches
-    if (g_step_variant == 1) {
-        const int wpb = (g_step_waves == 1 || g_step_waves == 2 || g_step_waves == 8) ? g_step_waves : 4;
-        const int fd = g_step_fast_depth | ((g_step_prio & 3) << 8);
-        const dim3 sg((e.num_games + wpb - 1) / wpb), sb(64 * wpb);
-        if (e.eval_cache_keys && e.prior_mode == 0) hipLaunchKernelGGL((engine_step_fast_kernel<N, true>), sg, sb, 0, st, e, do_expand, do_select, fd, list_sim);
-        else hipLaunchKernelGGL((engine_step_fast_kernel<N, false>), sg, sb, 0, st, e, do_expand, do_select, fd, -1);
-    }
-    else hipLaunchKernelGGL(engine_step_kernel<N>, grid, block, 0, st, e, do_expand, do_select);
+    const int wpb = (g_step_waves == 1 || g_step_waves == 2 || g_step_waves == 8) ? g_step_waves : 4;
+    const int fd = g_step_fast_depth | ((g_step_prio & 3) << 8);
+    const dim3 sg((e.num_games + wpb - 1) / wpb), sb(64 * wpb);
+    if (e.eval_cache_keys && e.prior_mode == 0) hipLaunchKernelGGL((engine_step_fast_kernel<N, true>), sg, sb, 0, st, e, do_expand, do_select, fd, list_sim);
+    else hipLaunchKernelGGL((engine_step_fast_kernel<N, false>), sg, sb, 0, st, e, do_expand, do_select, fd, -1);
     if (g_profile_trunk == 2) profile_mark(st, -1);
 }
 
@@ -1185,7 +998,7 @@ __global__ __launch_bounds__(256) void engine_root_visits_kernel(aqg_engine e, i
 // ------------------------------------------------------------------------------------------------
 static int validate(const aqg_engine& e) {
     const int N = e.board_size;
-    if (!(N == 3 || N == 5 || N == 7 || N == 9)) return fail("unsupported board_size");
+    if (!board_size_supported(N)) return fail("unsupported board_size");
     if (e.num_games <= 0 || e.sims <= 0) return fail("num_games and sims must be positive");
     if ((long long)e.node_cap >= (1 << 24)) return fail("node_cap must be < 2^24");
     if (e.node_cap < 1 + MAX_LEGAL) return fail("node_cap too small");
@@ -1210,7 +1023,6 @@ static int validate(const aqg_engine& e) {
         if (!e.eval_cache_rows || !e.eval_cache_slot || !e.eval_mask || !e.stat_cache_hits) return fail("eval_cache_rows / eval_cache_slot / eval_mask / stat_cache_hits are required with eval_cache_keys");
         if ((e.eval_list == nullptr) != (e.eval_count == nullptr)) return fail("eval_list and eval_count come together");
         if (e.eval_cache_log2 < 6 || e.eval_cache_log2 > 20) return fail("eval_cache_log2 must be 6..20");
-        if (g_step_variant != 1) return fail("the evaluation cache needs step_variant 1");
     }
     return 0;
 }
@@ -1221,7 +1033,7 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st) {
     const dim3 grid((e.num_games + 3) / 4), block(256);
     hipLaunchKernelGGL(engine_begin_move_kernel, dim3((e.num_games + 255) / 256), dim3(256), 0, st, e);
     // evaluation cache on a set larger than the trunk's grid: the leaves that miss the cache go to the trunk as a compact list
-    const bool use_list = e.prior_mode == 0 && e.eval_cache_keys && e.eval_list && N == 9 && e.num_games > 512 && g_trunk_variant >= 3 && g_step_variant == 1 && !(e.gnn_flags & AQG_GNN_EXACT_F32);
+    const bool use_list = e.prior_mode == 0 && e.eval_cache_keys && e.eval_list && N == 9 && e.num_games > 512 && g_trunk_variant >= 3 && !(e.gnn_flags & AQG_GNN_EXACT_F32);
     for (int sim = 0; sim < e.sims; ++sim) {
         launch_step<N>(e, sim > 0 ? 1 : 0, 1, st, use_list ? sim : -1);
         if (e.prior_mode == 0) {
@@ -1262,7 +1074,7 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st) {
 // below and the library's other host-side globals are not synchronised.)
 struct SimGraph {
     aqg_engine e;
-    int opts[8];
+    int opts[7];
     hipGraphExec_t exec;
     hipEvent_t last;          // recorded behind every replay: eviction waits for THIS graph's last replay, not for the device
 };
@@ -1279,7 +1091,7 @@ template <int N>
 static int run_sims(const aqg_engine& e, hipStream_t st) {
     if (!g_use_graph || g_profile_trunk || st == nullptr || e.sims < 4) return enqueue_sims<N>(e, st);
     // every option a captured launch bakes in is part of the key: a changed option must never replay a stale graph
-    const int opts[8] = {g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, N, g_step_variant, g_step_fast_depth, ((g_trunk_prio & 0xff) << 8) | (g_step_waves << 16) | (g_step_prio << 24) | (g_heads_prio << 28)};
+    const int opts[7] = {g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, N, g_step_fast_depth, ((g_trunk_prio & 0xff) << 8) | (g_step_waves << 16) | (g_step_prio << 24) | (g_heads_prio << 28)};
     for (SimGraph& g : g_sim_graphs)
         if (!memcmp(&g.e, &e, sizeof(aqg_engine)) && !memcmp(g.opts, opts, sizeof(opts))) return replay(g, st);
     if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
@@ -1330,26 +1142,20 @@ int engine_begin_move(const aqg_engine& e, hipStream_t st) {
 
 int engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t st) {
     if (int r = validate(e)) return r;
-    switch (e.board_size) {
-        case 3: launch_step<3>(e, do_expand, do_select, st); break;
-        case 5: launch_step<5>(e, do_expand, do_select, st); break;
-        case 7: launch_step<7>(e, do_expand, do_select, st); break;
-        default: launch_step<9>(e, do_expand, do_select, st); break;
-    }
-    return check_launch("engine_step_kernel");
+    return for_board_size(e.board_size, [&](auto n) {
+        launch_step<decltype(n)::value>(e, do_expand, do_select, st);
+        return check_launch("engine_step_fast_kernel");
+    });
 }
 
 int engine_finish_move(const aqg_engine& e, const double* uniforms, hipStream_t st) {
     if (int r = validate(e)) return r;
     const dim3 grid((e.num_games + 3) / 4), block(256);
-    switch (e.board_size) {
-        case 3: hipLaunchKernelGGL(engine_finish_move_kernel<3>, grid, block, 0, st, e, uniforms); break;
-        case 5: hipLaunchKernelGGL(engine_finish_move_kernel<5>, grid, block, 0, st, e, uniforms); break;
-        case 7: hipLaunchKernelGGL(engine_finish_move_kernel<7>, grid, block, 0, st, e, uniforms); break;
-        default: hipLaunchKernelGGL(engine_finish_move_kernel<9>, grid, block, 0, st, e, uniforms); break;
-    }
-    if (e.quota > e.num_games) hipLaunchKernelGGL(engine_refill_kernel, dim3(1), dim3(1024), 0, st, e);
-    return check_launch("engine_finish_move_kernel");
+    return for_board_size(e.board_size, [&](auto n) {
+        hipLaunchKernelGGL(engine_finish_move_kernel<decltype(n)::value>, grid, block, 0, st, e, uniforms);
+        if (e.quota > e.num_games) hipLaunchKernelGGL(engine_refill_kernel, dim3(1), dim3(1024), 0, st, e);
+        return check_launch("engine_finish_move_kernel");
+    });
 }
 
 int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st) {
@@ -1368,12 +1174,7 @@ int engine_reset(const aqg_engine& e, hipStream_t st) {
 
 int engine_move(const aqg_engine& e, const double* uniforms, hipStream_t st) {
     if (int r = validate(e)) return r;
-    switch (e.board_size) {
-        case 3: return do_move<3>(e, uniforms, st);
-        case 5: return do_move<5>(e, uniforms, st);
-        case 7: return do_move<7>(e, uniforms, st);
-        default: return do_move<9>(e, uniforms, st);
-    }
+    return for_board_size(e.board_size, [&](auto n) { return do_move<decltype(n)::value>(e, uniforms, st); });
 }
 
 int engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st) {
@@ -1385,12 +1186,7 @@ int engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st
 int engine_search(const aqg_engine& e, const uint8_t* roots72, hipStream_t st) {
     if (int r = validate(e)) return r;
     hipLaunchKernelGGL(engine_set_roots_kernel, dim3((e.num_games + 255) / 256), dim3(256), 0, st, e, roots72);
-    switch (e.board_size) {
-        case 3: return run_sims<3>(e, st);
-        case 5: return run_sims<5>(e, st);
-        case 7: return run_sims<7>(e, st);
-        default: return run_sims<9>(e, st);
-    }
+    return for_board_size(e.board_size, [&](auto n) { return run_sims<decltype(n)::value>(e, st); });
 }
 
 // the slot refill alone, for a move that was applied rather than searched (csrc/agents.hip)
@@ -1401,13 +1197,10 @@ int engine_refill(const aqg_engine& e, hipStream_t st) {
 
 int engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st) {
     const dim3 grid((e.num_games + 3) / 4), block(256);
-    switch (e.board_size) {
-        case 3: hipLaunchKernelGGL(engine_root_visits_kernel<3>, grid, block, 0, st, e, visits, actions, count); break;
-        case 5: hipLaunchKernelGGL(engine_root_visits_kernel<5>, grid, block, 0, st, e, visits, actions, count); break;
-        case 7: hipLaunchKernelGGL(engine_root_visits_kernel<7>, grid, block, 0, st, e, visits, actions, count); break;
-        default: hipLaunchKernelGGL(engine_root_visits_kernel<9>, grid, block, 0, st, e, visits, actions, count); break;
-    }
-    return check_launch("engine_root_visits_kernel");
+    return for_board_size(e.board_size, [&](auto n) {
+        hipLaunchKernelGGL(engine_root_visits_kernel<decltype(n)::value>, grid, block, 0, st, e, visits, actions, count);
+        return check_launch("engine_root_visits_kernel");
+    });
 }
 
 }  // namespace aqg

@@ -18,6 +18,7 @@
 // which is reachability-equivalent to game_logic.py:344-345).
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define QHD __host__ __device__ __forceinline__
@@ -35,6 +36,21 @@ namespace aqg {
 // ---------------------------------------------------------------------------------------------
 constexpr int STATE72 = 72;
 constexpr int MAX_LEGAL = 136;  // >= 5 pawn moves + 128 walls, multiple of 8
+
+// The board sizes every rule template and kernel is instantiated for, written ONCE: a runtime N becomes the compile-time
+// constant of a generic callable -- with_board_size(N, err, [&](auto n) { constexpr int NN = decltype(n)::value; ... }) --
+// whose result is returned; any other N returns `on_unsupported` and calls nothing (never another size's instantiation).
+template <class R, class F>
+inline R with_board_size(int N, R on_unsupported, F&& f) {
+    switch (N) {
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 9: return f(std::integral_constant<int, 9>{});
+        default: return on_unsupported;
+    }
+}
+inline bool board_size_supported(int N) { return with_board_size(N, false, [](auto) { return true; }); }
 
 struct QState {
     uint64_t hw;     // bit i: walls[i] == 1 (horizontal), mover's frame

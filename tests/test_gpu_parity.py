@@ -905,7 +905,7 @@ def _root_children(eng):
 
 
 def test_engine_priors_and_visits_vs_oracle_gnn(dev):
-    """P0 INSIDE the engine (pv_network_cnn.py:129-132 as done by game_expand_backup with prior_mode 0: gather the softmax
+    """P0 INSIDE the engine (pv_network_cnn.py:129-132 as done by the step kernel with prior_mode 0: gather the softmax
     output at legal_actions() in order, divide by the sum): the priors stored in the root's children must equal
     OracleModel.predict (fp64 GNN + C rules) to 1e-6, child i must carry legal action i, and a 10-simulation search must
     distribute its visits exactly like oracle.mcts driven by that model (pv_mcts.py:47-57)."""
@@ -991,16 +991,13 @@ def test_evaluation_games_match_reference(dev, N):
         assert points == [float(g[f"e{i}_point"][0])]
 
 
-@pytest.mark.parametrize("cfg", [(0, 61), (1, 0), (1, 1), (1, 2), (1, 5)])
-def test_step_kernel_variants_bit_identical(dev, cfg):
-    """The simulation step exists in two forms (csrc/mcts.hip): `step_variant` 0 = expand / backup through memory, fence,
-    select; 1 (default) = one load round + the previous simulation's updates applied in registers to whatever the descent
-    loads.  Variant 1 hands over to memory once a path gets deeper than `step_fast_depth` (61 by default, i.e. never in
-    practice): with the limit at 0, 1, 2 and 5 every hand-over point is exercised.  All forms must reproduce the
-    reference's traces, self-play games and evaluation games bit for bit."""
+@pytest.mark.parametrize("depth", [0, 1, 2, 5])
+def test_step_hand_over_points_bit_identical(dev, depth):
+    """The simulation step (csrc/mcts.hip) takes one load round and applies the previous simulation's updates in registers to
+    whatever the descent loads; once a path gets deeper than `step_fast_depth` (61 by default, i.e. never in practice) it
+    flushes them and goes on reading memory.  With the limit at 0 (memory from the root), 1, 2 and 5 every hand-over point
+    is exercised: each must reproduce the reference's traces, self-play games and evaluation games bit for bit."""
     from alphaquoridorgnn_amd import _lib
-    variant, depth = cfg
-    _lib.set_option("step_variant", variant)
     _lib.set_option("step_fast_depth", depth)
     try:
         test_mcts_visit_counts_match_reference_traces(dev, 9)
@@ -1008,10 +1005,9 @@ def test_step_kernel_variants_bit_identical(dev, cfg):
         test_evaluation_games_match_reference(dev, 9)
         test_mcts_visit_counts_match_reference_traces(dev, 5)
         test_mcts_many_games_equal_single_game(dev)
-        if variant == 1 and depth == 2:
+        if depth == 2:
             test_engine_priors_and_visits_vs_oracle_gnn(dev)
     finally:
-        _lib.set_option("step_variant", 1)
         _lib.set_option("step_fast_depth", 61)
 
 

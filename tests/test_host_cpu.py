@@ -477,7 +477,7 @@ def test_set_option_names_ranges_and_errors():
     from alphaquoridorgnn_amd import _lib
     lib = _lib.load()
     defaults = {"trunk_variant": 3, "heads_prio": 3, "trunk_prio": -1, "trunk_grid": 0, "trunk_phase_delay": 100, "trunk_delay_min_boards": 2048,
-                "step_prio": 1, "step_waves": 8, "step_variant": 1, "step_fast_depth": None, "train_fused": 2, "use_graph": 1,
+                "step_prio": 1, "step_waves": 8, "step_fast_depth": None, "train_fused": 2, "use_graph": 1,
                 "profile_trunk": 0}
     header = open(os.path.join(REPO, "include", "aqgnn.h")).read()
     integration = open(os.path.join(REPO, "INTEGRATION.md")).read()
@@ -486,12 +486,37 @@ def test_set_option_names_ranges_and_errors():
         assert f"`{name}`" in integration, f"{name} is not listed in INTEGRATION.md"
         if value is not None:
             assert lib.aqg_set_option(name.encode(), value) == 0, name
-    for name, bad in (("trunk_variant", 2), ("trunk_variant", 4), ("trunk_variant", 7), ("trunk_variant", 8), ("trunk_phase_delay", -1), ("step_fast_depth", 62), ("train_fused", 0), ("train_fused", 4)):
+    for name, bad in (("trunk_variant", 2), ("trunk_variant", 4), ("trunk_variant", 7), ("trunk_variant", 8), ("trunk_phase_delay", -1), ("step_fast_depth", 62), ("train_fused", 0), ("train_fused", 4),
+                      ("step_variant", 0), ("step_variant", 1)):
         assert lib.aqg_set_option(name.encode(), bad) != 0, (name, bad)
         assert lib.aqg_last_error()
     assert lib.aqg_set_option(b"no_such_option", 1) != 0 and b"no_such_option" in lib.aqg_last_error()
+    assert lib.aqg_set_option(b"step_variant", 1) != 0 and b"step_variant" in lib.aqg_last_error()    # retired with the round-1 step kernel
     with pytest.raises(RuntimeError):
         _lib.set_option("no_such_option", 1)
+
+
+@pytest.mark.parametrize("N", [4, 11])
+def test_host_entry_points_refuse_unsupported_board_size(N):
+    """The aqg_host_* entry points on a board size outside 3/5/7/9 run no rule code and return their own error values.  The
+    values are those the library returned before the board-size dispatch was written once (recorded from that build):
+    legal_actions -1, next -1, shortest_path -2, heuristic_eval NaN, alpha_beta_action -1; outputs stay untouched."""
+    import ctypes
+    from alphaquoridorgnn_amd import _lib
+    lib = _lib.load()
+    rec = np.zeros(72, dtype=np.uint8)
+    rec[0], rec[1], rec[2], rec[3], rec[70] = 76, 10, 76, 10, 9          # the 9x9 start position: valid everywhere but in N
+    p = rec.ctypes.data_as(ctypes.c_void_p)
+    out136, out72 = np.full(136, 0xAB, dtype=np.uint8), np.full(72, 0xAB, dtype=np.uint8)
+    assert lib.aqg_host_legal_actions(N, p, out136.ctypes.data_as(ctypes.c_void_p)) == -1
+    assert lib.aqg_host_next(N, p, 0, out72.ctypes.data_as(ctypes.c_void_p)) == -1
+    assert lib.aqg_host_shortest_path(N, p) == -2
+    assert np.isnan(lib.aqg_host_heuristic_eval(N, p, 20))
+    assert lib.aqg_host_alpha_beta_action(N, p, 100, 20, 1) == -1
+    assert (out136 == 0xAB).all() and (out72 == 0xAB).all()
+    # ... and the same record is served at its own size
+    assert lib.aqg_host_legal_actions(9, p, out136.ctypes.data_as(ctypes.c_void_p)) > 0
+    assert lib.aqg_host_shortest_path(9, p) == 8
 
 
 # ------------------------------------------------------------------ generic GNN operator: graph preparation (PyG's gcn_norm)

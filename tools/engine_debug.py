@@ -16,8 +16,8 @@ recs = g["states"][[0, 5, 40, 333, 1200, 2600, 5000]]
 oracle = og.OracleModel(params)
 pol, val = model.forward_states(torch.from_numpy(recs).to(dev))
 pol = pol.cpu().numpy()
-for sv in (0, 1):
-    _lib.set_option("step_variant", sv)
+for fd in (0, 61):             # the step's memory path from the root / its register path (csrc/mcts.hip)
+    _lib.set_option("step_fast_depth", fd)
     eng = BatchedSelfPlay(model, num_games=recs.shape[0], sims=10, record_history=False)
     eng.search(recs); torch.cuda.synchronize()
     G, cap = eng.G, eng.node_cap
@@ -29,8 +29,8 @@ for sv in (0, 1):
         pri = raw[i, first:first + cnt, 8:12].copy().view(np.float32)[:, 0]
         want, _ = oracle.predict(st)
         fwd = pol[i][legal]; fwd = fwd / fwd.sum()
-        print(f"step_variant {sv} state {i}: n_legal {len(legal)} cnt {cnt}  |engine-oracle| {np.abs(pri - want).max():.2e}  |fwd-oracle| {np.abs(fwd - want).max():.2e}")
-_lib.set_option("step_variant", 1)
+        print(f"step_fast_depth {fd} state {i}: n_legal {len(legal)} cnt {cnt}  |engine-oracle| {np.abs(pri - want).max():.2e}  |fwd-oracle| {np.abs(fwd - want).max():.2e}")
+_lib.set_option("step_fast_depth", 61)
 
 # ---- stand-alone forward on 24-byte packed records (state_fmt 1) vs state72 (state_fmt 0)
 def qstate(rec):
