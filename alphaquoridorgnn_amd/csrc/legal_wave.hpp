@@ -55,9 +55,10 @@ __device__ __forceinline__ int wave_legal_finish(const QState& s, const LegalPre
     const Open& base = prep.base;
     const bool needH = prep.needH, needV = prep.needV;
     const uint64_t pH = prep.pH, pV = prep.pV, nH = prep.nH, nV = prep.nV;
-    // Step 2 (lane = task): the k-th candidate that needs the searches (H candidates in slot order, then V) goes to
-    // lane k, which runs the mover's and the enemy's flood fill interleaved (can_reach2: two independent dependency
-    // chains keep a lone wavefront's VALU busy; one fill per lane and twice the rounds measured slower).
+    // Step 2 (lane = task), more than 32 candidates: the k-th candidate that needs the searches (H candidates in slot order,
+    // then V) goes to lane k, which runs the mover's and the enemy's flood fill interleaved (can_reach2: two independent
+    // dependency chains keep a lone wavefront's VALU busy; one fill per lane and twice the ROUNDS measured slower -- with at
+    // most 32 candidates one fill per lane costs no round, see below).
     const int cH = __popcll(nH), cV = __popcll(nV);
     const int ntask = cH + cV;
     // Results go back without any cross-lane reduction: the task of candidate (H, slot L) ran in lane rank = number of
@@ -67,23 +68,49 @@ __device__ __forceinline__ int wave_legal_finish(const QState& s, const LegalPre
     bool myfailH = false, myfailV = false;
     const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     const int rankH = __popcll(nH & below), rankV = cH + __popcll(nV & below);
-    for (int tbase = 0; tbase < ntask; tbase += 64) {
+    // the slot of task k: the k-th candidate that needs the searches (H candidates in slot order, then V)
+    auto task_slot = [&](int k, int& orient) {
+        orient = k < cH ? 1 : 2;
+        const uint64_t m = orient == 1 ? nH : nV;
+        int rank = orient == 1 ? k : k - cH;
+        int slot = 0;                                       // position of the rank-th set bit of m
+#pragma unroll
+        for (int w = 32; w >= 1; w >>= 1) {
+            const uint64_t lowmask = (1ull << w) - 1;
+            const int c = __popcll((m >> slot) & lowmask);
+            if (rank >= c) { rank -= c; slot += w; }
+        }
+        return slot;
+    };
+    // (the pawns are the same in every lane: as scalars, the jump-source positions of the paired searches are scalars too)
+    const int me = __builtin_amdgcn_readfirstlane((int)s.ppos), other = V - 1 - __builtin_amdgcn_readfirstlane((int)s.epos);
+    const bool split = 2 * ntask <= 64;
+    if (split && ntask > 0) {
+        // At most 32 candidates (the touch-count prefilter leaves 16.9 per state on average): each FILL gets a lane -- task k's mover fill runs in lane 2k,
+        // its enemy fill in lane 2k+1, half the instructions per iteration of the interleaved form and still one round.  Same
+        // single ballot; a candidate fails if either of its two bits is set.
+        bool failed = false;
+        const int k = lane >> 1;
+        if (k < ntask) {
+            int orient;
+            const int slot = task_slot(k, orient);
+            const bool enemy = lane & 1;
+            const BB g0 = mask_row<N>(0), g1 = mask_row<N>(N - 1);
+            const BB goal = bb(enemy ? g1.lo : g0.lo, enemy ? g1.hi : g0.hi);
+            failed = !can_reach1_w3<N>(base, orient, slot, enemy ? other : me, enemy ? me : other, goal);
+        }
+        const uint64_t fm = __ballot(failed);               // bits 2k, 2k+1 = task k's mover / enemy fill failed
+        if (needH) myfailH = ((fm >> (2 * rankH)) & 3) != 0;
+        if (needV) myfailV = ((fm >> (2 * rankV)) & 3) != 0;
+    }
+    // 33 or more candidates: the interleaved form, in rounds of 64 tasks.  (No 9x9 position with more than 63 candidates is known --
+    // tools/crowded_search.cpp ends at 63 in every run -- so a second round is not expected; the loop keeps the general form.)
+    for (int tbase = 0; !split && tbase < ntask; tbase += 64) {
         const int task = tbase + lane;
         bool failed = false;
         if (task < ntask) {
-            const int k = task;
-            const int orient = k < cH ? 1 : 2;
-            uint64_t m = orient == 1 ? nH : nV;
-            int rank = orient == 1 ? k : k - cH;
-            int slot = 0;                                   // position of the rank-th set bit of m
-#pragma unroll
-            for (int w = 32; w >= 1; w >>= 1) {
-                const uint64_t lowmask = (1ull << w) - 1;
-                const int c = __popcll((m >> slot) & lowmask);
-                if (rank >= c) { rank -= c; slot += w; }
-            }
-            // (the pawns are the same in every lane: as scalars, the jump-source positions of the searches are scalars too)
-            const int me = __builtin_amdgcn_readfirstlane((int)s.ppos), other = V - 1 - __builtin_amdgcn_readfirstlane((int)s.epos);
+            int orient;
+            const int slot = task_slot(task, orient);
             const int ok = can_reach2_w3<N>(base, orient, slot, me, other, mask_row<N>(0), other, me, mask_row<N>(N - 1));
             failed = ok != 3;
         }

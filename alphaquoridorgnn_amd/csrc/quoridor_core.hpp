@@ -400,6 +400,41 @@ template <int N> QHD int can_reach2_w3(const Open& base, int orient, int slot, i
     return res;
 }
 
+// ONE of the two searches, for a lane that runs a single fill (legal_wave.hpp gives each fill of a candidate a lane of its own when
+// all of them fit into one round): half the instructions per iteration of the paired form, the same decision as its half of it
+// (checked beside it by the host build).  start / obst / goal may differ per lane.
+template <int N> QHD bool can_reach1_w3(const Open& base, int orient, int slot, int start, int obst, BB goal) {
+    constexpr int S = N - 1;
+    W3 oU = w3(base.U), oD = w3(base.D), oL = w3(base.L), oR = w3(base.R);
+    {   // add_wall, branch-free (as in can_reach2_w3)
+        const int t = slot + slot / S;
+        const uint32_t mh = orient == 1 ? ~0u : 0u, mv = orient == 2 ? ~0u : 0u;
+        const W3 b0 = w3_bit(t), b1 = w3_bit(t + 1), bN = w3_bit(t + N), bN1 = w3_bit(t + N + 1);
+        auto clear = [](W3& x, const W3& m, uint32_t on) { x.a &= ~(m.a & on); x.b &= ~(m.b & on); x.c &= ~(m.c & on); };
+        clear(oD, b0 | b1, mh); clear(oU, bN | bN1, mh);
+        clear(oR, b0 | bN, mv); clear(oL, b1 | bN1, mv);
+    }
+    const W3 nO = ~w3_bit(obst), g = w3(goal);
+    W3 J[4];
+    int q[4];
+    jump_landings_w3<N>(oU, oD, oL, oR, obst, J, q);
+    W3 r = w3_bit(start);
+    for (int it = 0; it < N * N; ++it) {
+        if (w3_any(r & g)) return true;
+        W3 a = (r | w3_shl<N>(r & oD) | w3_shr<N>(r & oU) | w3_shl<1>(r & oR) | w3_shr<1>(r & oL)) & nO;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int d = 0; d < 4; ++d) {
+            const uint32_t m = w3_mask_of(r, q[d]);
+            a.a |= J[d].a & m; a.b |= J[d].b & m; a.c |= J[d].c & m;
+        }
+        if (w3_eq(a, r)) return false;                     // fixpoint without the goal
+        r = a;
+    }
+    return w3_any(r & g);
+}
+
 // game_logic.py:120-192 legal_actions_pos(pos) with the enemy pawn on tile `e` (mover's frame).
 // Ordered: U, D, L, R; a jump contributes the straight landing, else (left,right) / (up,down).
 template <int N> QHD int legal_pos_list(const Open& o, int pos, int e, uint8_t* out) {
@@ -511,6 +546,9 @@ template <int N> QHD bool wall_keeps_paths(const QState& s, const Open& base, in
     if (both != ((rp ? 1 : 0) | (re ? 2 : 0))) return !(rp && re);    // a disagreement flips the answer and fails the golden tests
     const int both3 = can_reach2_w3<N>(base, orient, pos, me, other, mask_row<N>(0), other, me, mask_row<N>(N - 1));   // the three-word form the GPU runs
     if (both3 != both) return !(rp && re);
+    const int each3 = (can_reach1_w3<N>(base, orient, pos, me, other, mask_row<N>(0)) ? 1 : 0) |
+                      (can_reach1_w3<N>(base, orient, pos, other, me, mask_row<N>(N - 1)) ? 2 : 0);                        // one fill per lane
+    if (each3 != both) return !(rp && re);
     return rp && re;
 }
 
