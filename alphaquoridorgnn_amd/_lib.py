@@ -62,7 +62,9 @@ class CnnNetStruct(_c.Structure):
 class EngineStructGeneral(EngineStruct):
     """The whole `struct aqg_engine` of ABI 14: EngineStruct's fields (unchanged offsets) followed by `general_net`, the
     descriptor of prior_mode 3, and `cnn_net`, the descriptor of prior_mode 4.  The engine entry points take this one."""
-    _fields_ = [("general_net", GeneralNetStruct), ("cnn_net", CnnNetStruct)]
+    _fields_ = [("general_net", GeneralNetStruct), ("cnn_net", CnnNetStruct),
+                # root exploration noise (appended: every earlier offset is unchanged; all zero = off)
+                ("root_noise_eps", _f32), ("root_noise_alpha", _f32), ("root_noise_seed", _c.c_uint64), ("root_noise", _vp)]
 
 
 class TrainStruct(_c.Structure):
@@ -148,6 +150,8 @@ SIGNATURES = {
     "aqg_engine_finish_move": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_engine_set_roots": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_engine_root_visits": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp, _vp, _vp]),
+    "aqg_engine_root_noise": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),
+    "aqg_engine_root_priors": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp, _vp]),
     "aqg_engine_root_states72": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_engine_apply_actions": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_agent_random": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp, _c.c_int, _c.c_uint64, _vp, _vp]),

@@ -14,21 +14,15 @@
 #include "aqg_common.hpp"
 #include "legal_wave.hpp"
 #include "launchers.hpp"
+#include "counter_rng.hpp"
 
 #pragma clang fp contract(off)
 
 namespace aqg {
 
 // ------------------------------------------------------------------------------------------------
-// random draws: a caller-supplied table, or the counter-based generator documented in include/aqgnn.h
+// random draws: a caller-supplied table, or the counter-based generator documented in include/aqgnn.h (counter_rng.hpp)
 // ------------------------------------------------------------------------------------------------
-constexpr uint64_t GOLDEN = 0x9E3779B97F4A7C15ull;
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {       // the splitmix64 finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 struct Draws {
     const double* row;   // this state's table row, or nullptr = the generator
     int stride;          // entries of the row
@@ -39,7 +33,7 @@ __device__ __forceinline__ Draws make_draws(const double* uniforms, int stride, 
     Draws d;
     d.row = uniforms ? uniforms + (size_t)b * stride : nullptr;
     d.stride = stride;
-    d.key = mix64(seed + GOLDEN * (uint64_t)(b + 1));
+    d.key = stream_key(seed, (uint64_t)b);
     d.used = 0;
     return d;
 }
@@ -47,7 +41,7 @@ __device__ __forceinline__ Draws make_draws(const double* uniforms, int stride, 
 __device__ __forceinline__ double next_uniform(Draws& d) {
     const int i = d.used++;
     if (d.row) return i < d.stride ? d.row[i] : 0.0;
-    return (double)(mix64(d.key + GOLDEN * (uint64_t)(i + 1)) >> 11) * 0x1.0p-53;
+    return counter_uniform(d.key, (uint64_t)i);
 }
 // index = min(count - 1, floor(u * count)); whatever u holds, the result lies in [0, count)
 __device__ __forceinline__ int draw_index(double u, int count) {

@@ -231,6 +231,15 @@ int aqg_engine_root_visits(const aqg_engine* e, int32_t* visits, uint8_t* action
     return engine_root_visits(*e, visits, actions, count, (hipStream_t)stream);
 }
 
+int aqg_engine_root_noise(const aqg_engine* e, void* stream) {
+    if (!e) return fail("aqg_engine_root_noise: null engine");
+    return engine_root_noise(*e, (hipStream_t)stream);
+}
+int aqg_engine_root_priors(const aqg_engine* e, float* priors, int32_t* count, void* stream) {
+    if (!e || !priors || !count) return fail("aqg_engine_root_priors: null argument");
+    return engine_root_priors(*e, priors, count, (hipStream_t)stream);
+}
+
 int aqg_engine_root_states72(const aqg_engine* e, uint8_t* out72, void* stream) {
     if (!e || !out72) return fail("aqg_engine_root_states72: null argument");
     return engine_root_states72(*e, out72, (hipStream_t)stream);

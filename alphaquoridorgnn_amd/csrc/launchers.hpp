@@ -83,6 +83,8 @@ int engine_move(const aqg_engine& e, const double* uniforms, hipStream_t st);
 int engine_search(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
 int engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st);
 int engine_refill(const aqg_engine& e, hipStream_t st);
+int engine_root_noise(const aqg_engine& e, hipStream_t st);
+int engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st);
 
 // ---- agents.hip
 int launch_agent_random(int N, const uint8_t* states72, int B, const double* uniforms, int stride, uint64_t seed, int32_t* actions,

@@ -21,6 +21,8 @@
 #include "legal_wave.hpp"
 #include "../../include/aqgnn.h"
 #include "launchers.hpp"
+#include "counter_rng.hpp"
+#include <cfloat>
 
 // PUCT scores must be evaluated exactly as written (no fma contraction, IEEE divide/sqrt).
 #pragma clang fp contract(off)
@@ -844,6 +846,118 @@ static void launch_step(const aqg_engine& e_in, int do_expand, int do_select, hi
 }
 
 // ------------------------------------------------------------------------------------------------
+// root exploration noise (aqgnn.h, "root exploration noise"): p' = (1 - eps) p + eps eta, eta ~ Dir(alpha), mixed into the root's
+// priors between the evaluation of simulation 0 and the step of simulation 1.  One wavefront per slot; lane i + 64 r owns legal
+// action i + 64 r.  The step kernel is not changed: a root whose priors were mixed is handed to it as leaf_flag 2 -- "the row holds
+// normalised priors in legal order" -- which it expands from the row as it stands and never writes into the evaluation cache, so
+// the table only ever holds the network's own priors.
+// ------------------------------------------------------------------------------------------------
+constexpr int ROOT_NOISE_ATTEMPTS = 64;      // cap of the Marsaglia-Tsang rejection loop (acceptance is above 95 % per attempt)
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+// Gamma(alpha, 1) of one component's sub-stream, the recipe of aqgnn.h (engine.draw_root_noise is the same in numpy)
+__device__ __forceinline__ double root_noise_gamma(uint64_t key, double alpha) {
+    const bool boost = alpha < 1.0;
+    const double a = boost ? alpha + 1.0 : alpha;
+    const double d = a - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
+    double val = d;                          // cap exhausted: the value of v = 1
+    for (int t = 0; t < ROOT_NOISE_ATTEMPTS; ++t) {
+        const double u1 = counter_uniform(key, 1 + 3 * t), u2 = counter_uniform(key, 2 + 3 * t), u3 = counter_uniform(key, 3 + 3 * t);
+        const double x = sqrt(-2.0 * log(1.0 - u1)) * cospi(2.0 * u2);      // Box-Muller
+        const double v1 = 1.0 + c * x;
+        if (v1 <= 0.0) continue;
+        const double v = v1 * v1 * v1;
+        if (log(1.0 - u3) < 0.5 * x * x + d - d * v + d * log(v)) { val = d * v; break; }
+    }
+    if (boost) val = val * pow(1.0 - counter_uniform(key, 0), 1.0 / alpha);
+    return fmax(val, DBL_MIN);               // u ^ (1 / alpha) may underflow: a variate is never 0
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void engine_root_noise_kernel(aqg_engine e) {
+    constexpr int A = Geo<N>::A;
+    static_assert(A <= 256 && MAX_LEGAL <= 192, "three lane rounds cover the legal list, four the dense row");
+    __shared__ float polbuf[4][256];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int g = blockIdx.x * 4 + w;
+    if (g >= e.num_games || !e.game_active[g]) return;
+    const int flag = __builtin_amdgcn_readfirstlane((int)e.leaf_flag[g]);
+    if ((flag != 1 && flag != 2) || e.path_len[g] != 0) return;          // the pending leaf is not the root
+    const int cnt = __builtin_amdgcn_readfirstlane(min(e.legal_count[g], (int)MAX_LEGAL));
+    if (cnt <= 0) return;
+    float* pol = e.policy + (size_t)g * A;
+    const bool gather = e.prior_mode == 0 && flag == 1;
+    float pl[3] = {0.f, 0.f, 0.f};
+    if (gather) {                            // the arithmetic of game_step_fast: gather at the legal actions, divide by the sum unless 0
+        const uint8_t* ord = e.legal_order + (size_t)g * MAX_LEGAL;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { const int a = lane + 64 * r; polbuf[w][a] = (a < A) ? pol[a] : 0.f; }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        float sum = 0.f;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int i = lane + 64 * r;
+            pl[r] = (i < cnt) ? polbuf[w][ord[i]] : 0.f;
+            sum += pl[r];
+        }
+        sum = wave_sum_f(sum);
+        const float den = (sum != 0.f) ? sum : 1.f;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) pl[r] = pl[r] / den;
+    } else {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) { const int i = lane + 64 * r; pl[r] = (i < cnt) ? pol[i] : 0.f; }
+    }
+    // the gamma variates: the caller's table, or the generator's stream of (seed, game, ply), one sub-stream per component
+    double gv[3] = {0.0, 0.0, 0.0};
+    if (e.root_noise) {
+        const double* row = e.root_noise + (size_t)g * MAX_LEGAL;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int i = lane + 64 * r;
+            if (i < cnt) { const double x = row[i]; gv[r] = (x > 0.0 && x <= DBL_MAX) ? x : 0.0; }      // not > 0 or not finite: 0
+        }
+    } else {
+        const QState root = load_state(e.leaf_state, 1, g);
+        const uint64_t key = stream_key(stream_key(e.root_noise_seed, (uint64_t)(uint32_t)e.slot_game[g]), (uint64_t)root.plies);
+        const double alpha = (double)e.root_noise_alpha;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int i = lane + 64 * r;
+            if (i < cnt) gv[r] = root_noise_gamma(stream_key(key, (uint64_t)i), alpha);
+        }
+    }
+    const double S = wave_sum_d((gv[0] + gv[1]) + gv[2]);
+    if (!(S > 0.0 && S <= DBL_MAX)) return;                              // no usable noise: the root keeps its priors, untouched
+    const float eps = e.root_noise_eps, keep = 1.0f - eps;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const int i = lane + 64 * r;
+        if (i < cnt) {
+            const float eta = (float)(gv[r] / S);
+            const float x = keep * pl[r], y = eps * eta;
+            pol[i] = x + y;
+        }
+    }
+    if (lane == 0) {
+        if (gather) e.leaf_flag[g] = 2;                                  // the row is now legal-ordered and normalised
+        if (e.eval_cache_keys) e.eval_cache_slot[g] = -1;                // ... and must never be stored under the position's key
+    }
+}
+
+template <int N>
+static void launch_root_noise(const aqg_engine& e_in, hipStream_t st) {
+    aqg_engine e = e_in;                     // modes 3 and 4 leave a dense row like mode 0 (see launch_step)
+    if (e.prior_mode == 3 || e.prior_mode == 4) e.prior_mode = 0;
+    hipLaunchKernelGGL(engine_root_noise_kernel<N>, dim3((e.num_games + 3) / 4), dim3(256), 0, st, e);
+}
+
+// ------------------------------------------------------------------------------------------------
 // finish move: visits -> policy (pv_mcts.py:88-95), record, np.random.choice, next(), terminal handling
 // ------------------------------------------------------------------------------------------------
 template <int N>
@@ -993,6 +1107,17 @@ __global__ __launch_bounds__(256) void engine_root_visits_kernel(aqg_engine e, i
     if (lane == 0) count[g] = cnt;
 }
 
+__global__ __launch_bounds__(256) void engine_root_priors_kernel(aqg_engine e, float* __restrict__ priors, int32_t* __restrict__ count) {
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= e.num_games) return;
+    const NodeRec* __restrict__ nodes = game_nodes(e, g);
+    const uint32_t kids = nodes[0].kids;
+    const int cnt = (int)(kids >> 24), first = (int)(kids & 0xFFFFFF);
+    for (int i = lane; i < MAX_LEGAL; i += 64) priors[(size_t)g * MAX_LEGAL + i] = (i < cnt) ? nodes[first + i].p : 0.f;
+    if (lane == 0) count[g] = cnt;
+}
+
 // ------------------------------------------------------------------------------------------------
 // host-side enqueue (no sync, no allocation)
 // ------------------------------------------------------------------------------------------------
@@ -1024,6 +1149,8 @@ static int validate(const aqg_engine& e) {
         if ((e.eval_list == nullptr) != (e.eval_count == nullptr)) return fail("eval_list and eval_count come together");
         if (e.eval_cache_log2 < 6 || e.eval_cache_log2 > 20) return fail("eval_cache_log2 must be 6..20");
     }
+    if (!(e.root_noise_eps >= 0.f && e.root_noise_eps < 1.f)) return fail("root_noise_eps must be in [0, 1)");
+    if (e.root_noise_eps > 0.f && !(e.root_noise_alpha > 0.f && e.root_noise_alpha <= 100.f)) return fail("root_noise_alpha must be in (0, 100]");
     return 0;
 }
 
@@ -1061,12 +1188,13 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st) {
         } else {
             hipLaunchKernelGGL(engine_fake_eval_kernel<N>, grid, block, 0, st, e);
         }
+        if (sim == 0 && e.root_noise_eps > 0.f) launch_root_noise<N>(e, st);      // the root's priors, before simulation 1 expands it
     }
     launch_step<N>(e, 1, 0, st);   // expand + backup of the last simulation
     return check_launch("engine simulation kernels");
 }
 
-// One move's search is 3 * sims + 2 launches with constant arguments: on a capturable (non-default) stream it is
+// One move's search is 3 * sims + 2 launches (one more with root noise on) with constant arguments: on a capturable (non-default) stream it is
 // captured once into a hipGraph and replayed per move, so the host cost per move is one graph launch instead of ~600
 // kernel launches (with several game sets on several streams the host is otherwise the bottleneck).  The cache key is
 // the engine struct itself plus the trunk options the launches read.
@@ -1187,6 +1315,22 @@ int engine_search(const aqg_engine& e, const uint8_t* roots72, hipStream_t st) {
     if (int r = validate(e)) return r;
     hipLaunchKernelGGL(engine_set_roots_kernel, dim3((e.num_games + 255) / 256), dim3(256), 0, st, e, roots72);
     return for_board_size(e.board_size, [&](auto n) { return run_sims<decltype(n)::value>(e, st); });
+}
+
+// the noise launch alone: behind the caller's own evaluation of simulation 0 (prior_mode 2), and for tests
+int engine_root_noise(const aqg_engine& e, hipStream_t st) {
+    if (int r = validate(e)) return r;
+    if (!(e.root_noise_eps > 0.f)) return 0;
+    return for_board_size(e.board_size, [&](auto n) {
+        launch_root_noise<decltype(n)::value>(e, st);
+        return check_launch("engine_root_noise_kernel");
+    });
+}
+
+int engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st) {
+    if (int r = validate(e)) return r;
+    hipLaunchKernelGGL(engine_root_priors_kernel, dim3((e.num_games + 3) / 4), dim3(256), 0, st, e, priors, count);
+    return check_launch("engine_root_priors_kernel");
 }
 
 // the slot refill alone, for a move that was applied rather than searched (csrc/agents.hip)

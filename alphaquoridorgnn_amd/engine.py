@@ -18,9 +18,122 @@ from . import _lib
 from .constants import BOARD_SIZE, board_params
 
 
+ROOT_NOISE_ATTEMPTS = 64      # cap of the gamma sampler's rejection loop (csrc/mcts.hip ROOT_NOISE_ATTEMPTS)
+_MASK64 = (1 << 64) - 1
+
+
+def default_root_noise_alpha(board_size):
+    """The usual "10 / typical number of legal moves" rule, with the board's action count N^2 + 2 (N - 1)^2 for the moves."""
+    return 10.0 / (board_size ** 2 + 2 * (board_size - 1) ** 2)
+
+
+def check_root_noise(eps, alpha):
+    """Validate the root-noise options as the library does, on the f32 values its struct holds: eps in [0, 1); alpha in (0, 100]
+    when eps > 0.  Returns them as floats (alpha 0.0 when the noise is off)."""
+    eps = float(np.float32(eps))
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"root_noise_eps must be in [0, 1) as a float32, not {eps}")
+    if eps == 0.0:
+        return 0.0, 0.0
+    alpha = float(np.float32(alpha))
+    if not 0.0 < alpha <= 100.0:
+        raise ValueError(f"root_noise_alpha must be in (0, 100] as a float32, not {alpha}")
+    return eps, alpha
+
+
+def refuse_root_noise(what, **options):
+    """Evaluation paths never add noise: an option that asks for it is a mistake, not something to drop silently."""
+    bad = sorted(k for k, v in options.items() if v is not None)
+    if bad:
+        raise ValueError(f"{what} never adds root exploration noise: {', '.join(bad)} is a self-play option")
+
+
+def _mix64_int(z):
+    """The splitmix64 finaliser on a Python int (include/aqgnn.h)."""
+    z &= _MASK64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return z ^ (z >> 31)
+
+
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def default_root_noise_seed(seed):
+    """The noise seed of an engine that was given none: `seed` through the mixer.  NOT a linear map: the generator's stream of game
+    k is keyed by mix(noise_seed + GOLDEN * (k + 1)), so noise seeds that differ by a multiple of GOLDEN -- what any affine map of
+    consecutive engine seeds onto them risks -- would hand game k of one engine the stream of another game of the next."""
+    return _mix64_int((int(seed) & _MASK64) ^ 0x524F4F544E4F4953)
+
+
+def set_noise_seeds(seed, root_noise_seed, sizes, quotas):
+    """The noise seeds of MultiSetSelfPlay's sets (slots `sizes`, games `quotas`).  The sets' games are numbered through -- set i's
+    game k is game first_i + k of the whole engine -- and the numbering rides in the seed: the stream of game k under
+    base + GOLDEN * first is the stream of game first + k under base.  Every set has a seed of its own and no two games share one."""
+    base = default_root_noise_seed(seed) if root_noise_seed is None else int(root_noise_seed) & _MASK64
+    firsts = [sum(max(q, g) for q, g in zip(quotas[:i], sizes[:i])) for i in range(len(sizes))]
+    return [(base + _GOLDEN * f) & _MASK64 for f in firsts]
+
+
+def root_noise_stream_key(seed, k, ply):
+    """The 64-bit key of the noise stream of game k's root at `ply` under the noise seed `seed` (include/aqgnn.h: K(K(seed, k), ply))."""
+    return _mix64_int(_mix64_int(int(seed) + _GOLDEN * (int(k) + 1)) + _GOLDEN * (int(ply) + 1))
+
+
+def draw_root_noise(seed, k, ply, count, alpha, return_exhausted=False):
+    """The gamma variates g_0 .. g_{count-1} of the root of game k at ply `ply`, float64 [count] -- the generator of
+    engine_root_noise_kernel in numpy (the recipe is in include/aqgnn.h, "root exploration noise").  k may be an array of game
+    indices: the result is then [len(k), count].  Component i draws from its own sub-stream, so the first c components do not
+    depend on count.  return_exhausted: also return how many variates took the fallback of the capped rejection loop."""
+    from .agents import _mix64, _GOLDEN
+    G = np.uint64(_GOLDEN)
+
+    def key_of(base, b):
+        with np.errstate(over="ignore"):
+            return _mix64(base + G * (np.asarray(b, dtype=np.uint64) + np.uint64(1)))
+
+    def uniform(key, j):
+        with np.errstate(over="ignore"):
+            z = _mix64(key + G * np.uint64(j + 1))
+        return (z >> np.uint64(11)).astype(np.float64) * (2.0 ** -53)
+
+    scalar = np.ndim(k) == 0
+    kk = np.atleast_1d(np.asarray(k, dtype=np.int64)).astype(np.uint64)
+    root = np.asarray([root_noise_stream_key(seed, int(x), ply) for x in kk], dtype=np.uint64)
+    key = key_of(root[:, None], np.arange(int(count), dtype=np.uint64)[None, :])
+    alpha = float(np.float32(alpha))          # the struct field is f32
+    boost = alpha < 1.0
+    a = alpha + 1.0 if boost else alpha
+    d = a - 1.0 / 3.0
+    c = 1.0 / np.sqrt(9.0 * d)
+    val = np.full(key.shape, d, dtype=np.float64)
+    todo = np.ones(key.shape, dtype=bool)
+    for t in range(ROOT_NOISE_ATTEMPTS):
+        if not todo.any():
+            break
+        kt = key[todo]
+        u1, u2, u3 = uniform(kt, 1 + 3 * t), uniform(kt, 2 + 3 * t), uniform(kt, 3 + 3 * t)
+        x = np.sqrt(-2.0 * np.log(1.0 - u1)) * np.cos(2.0 * np.pi * u2)
+        v1 = 1.0 + c * x
+        ok = v1 > 0.0
+        v = np.where(ok, v1 * v1 * v1, 1.0)
+        ok &= np.log(1.0 - u3) < 0.5 * x * x + d - d * v + d * np.log(v)
+        idx = np.flatnonzero(todo.ravel())
+        val.ravel()[idx[ok]] = d * v[ok]
+        todo.ravel()[idx[ok]] = False
+    exhausted = int(todo.sum())
+    if boost:
+        val = val * np.power(1.0 - uniform(key, 0), 1.0 / alpha)
+    val = np.maximum(val, np.finfo(np.float64).tiny)
+    if scalar:
+        val = val[0]
+    return (val, exhausted) if return_exhausted else val
+
+
 class BatchedSelfPlay:
     def __init__(self, model=None, num_games=2048, sims=50, board_size=BOARD_SIZE, device=None, temperature=1.0,
-                 c_puct=1.25, evaluator="gnn", fake_bias=0, seed=0, record_history=True, quota=None, eval_cache_slots=None):
+                 c_puct=1.25, evaluator="gnn", fake_bias=0, seed=0, record_history=True, quota=None, eval_cache_slots=None,
+                 root_noise_eps=0.0, root_noise_alpha=None, root_noise_seed=None):
         """model: GraphPolicyValueNetwork/GNNNetwork (evaluator='gnn'); evaluator='fake' runs the integer-hash
         evaluator used by the parity tests (oracle/mcts.py FakeModel); evaluator='external' calls `model.predict(state,
         device)` -- ANY object honouring the reference's BaseNetwork contract (BaseNetwork.py:36-40), e.g. a stock CNN --
@@ -32,7 +145,14 @@ class BatchedSelfPlay:
         off): entries per game slot of the evaluation cache
         (include/aqgnn.h, `eval_cache_keys`): a leaf whose position this slot has already sent through the network is expanded from
         the stored priors / value / legal list -- bit-identical searches and game records, fewer network evaluations (736 bytes of
-        HBM per entry)."""
+        HBM per entry).
+        root_noise_eps (0 = off, the default: nothing changes): every move mixes Dir(root_noise_alpha) into the root's priors on the
+        device, p' = (1 - eps) p + eps eta (include/aqgnn.h, "root exploration noise").  root_noise_alpha None = 10 / (N^2 + 2 (N - 1)^2),
+        the usual "10 / typical number of moves" rule; root_noise_seed None = derived from `seed`.  The noise of a game's root is
+        keyed by (seed, game index, ply) -- draw_root_noise is the generator in numpy -- unless move() / search() are given a table."""
+        self.root_noise_eps, self.root_noise_alpha = check_root_noise(
+            root_noise_eps, default_root_noise_alpha(board_size) if root_noise_alpha is None else root_noise_alpha)
+        self.root_noise_seed = default_root_noise_seed(seed) if root_noise_seed is None else int(root_noise_seed) & _MASK64
         if evaluator == "gnn" and model is not None and not getattr(model, "fused", True):
             model._require_fused("evaluator='gnn'")          # before anything is allocated or launched
         if evaluator == "general" and model is not None and getattr(model, "num_features", 6) != 6:
@@ -164,6 +284,8 @@ class BatchedSelfPlay:
             for name in ("eval_cache_keys", "eval_cache_rows", "eval_cache_slot", "eval_mask", "stat_cache_hits", "eval_list", "eval_count"):
                 setattr(e, name, t[name].data_ptr())
             e.eval_cache_log2 = self.eval_cache_slots.bit_length() - 1
+        e.root_noise_eps, e.root_noise_alpha = self.root_noise_eps, self.root_noise_alpha
+        e.root_noise_seed = self.root_noise_seed if self.root_noise_eps else 0      # off: the four fields are zero
         self.record_history = record_history
         self.moves_done = 0
         self.reset()
@@ -204,8 +326,24 @@ class BatchedSelfPlay:
             if self.eval_cache_slots and changed:
                 _lib.check(self.lib.aqg_engine_clear_eval_cache(ctypes.byref(self.e), self._stream()), "aqg_engine_clear_eval_cache")
 
-    def move(self, uniforms=None):
-        """One move for every active game.  uniforms: float64 [G] in [0,1) (default: device RNG stream)."""
+    def _set_root_noise(self, table):
+        """Table mode: the gamma variates of this move's roots, float64 [G, MAX_LEGAL] (None = the generator).  The table is copied
+        into one buffer the engine keeps, so that the struct -- the captured graph's key -- does not change from move to move."""
+        if table is None:
+            self.e.root_noise = None
+            return
+        if not self.root_noise_eps:
+            raise ValueError("a root_noise table needs root_noise_eps > 0")
+        table = torch.as_tensor(table, dtype=torch.float64).to(self.dev).contiguous().view(self.G, _lib.MAX_LEGAL)
+        if "root_noise" not in self.t:
+            self.t["root_noise"] = torch.zeros((self.G, _lib.MAX_LEGAL), dtype=torch.float64, device=self.dev)
+        self.t["root_noise"].copy_(table)        # stream-ordered behind the previous move's reads
+        self.e.root_noise = self.t["root_noise"].data_ptr()
+
+    def move(self, uniforms=None, root_noise=None):
+        """One move for every active game.  uniforms: float64 [G] in [0,1) (default: device RNG stream).  root_noise: float64
+        [G, MAX_LEGAL] gamma variates of this move's roots (default: the counter-based generator; needs root_noise_eps > 0)."""
+        self._set_root_noise(root_noise)
         if uniforms is None:
             uniforms = torch.rand((self.G,), dtype=torch.float64, device=self.dev, generator=self.gen)
         else:
@@ -270,6 +408,8 @@ class BatchedSelfPlay:
                 val[j] = float(v)
             self.t["policy"][idx] = pol.to(self.dev)
             self.t["value"][idx] = val.to(self.dev)
+            if sim == 0 and self.root_noise_eps:
+                _lib.check(self.lib.aqg_engine_root_noise(e, st), "aqg_engine_root_noise")
         _lib.check(self.lib.aqg_engine_step(e, 1, 0, st), "aqg_engine_step")
 
     def counters(self):
@@ -290,13 +430,14 @@ class BatchedSelfPlay:
         self.e.gnn_flags = _lib.GNN_EXACT_F32
         self.reset()
 
-    def play_generation(self, uniforms=None, check_every=4):
+    def play_generation(self, uniforms=None, check_every=4, root_noise=None):
         """Play the whole quota (== every slot once when quota == num_games: one self_play generation's worth of games
-        on this rank).  uniforms: optional float64 [moves, G] (parity tests).  Returns the counters dict."""
+        on this rank).  uniforms: optional float64 [moves, G]; root_noise: optional float64 [moves, G, MAX_LEGAL] gamma variates
+        (parity tests).  Returns the counters dict."""
         ply = 0
         limit = self.max_plies * (-(-self.quota // self.G))          # every slot plays at most ceil(quota / G) games
         while True:
-            self.move(None if uniforms is None else uniforms[ply])
+            self.move(None if uniforms is None else uniforms[ply], None if root_noise is None else root_noise[ply])
             ply += 1
             if ply >= limit or ply % check_every == 0:
                 c = self.counters()
@@ -309,14 +450,16 @@ class BatchedSelfPlay:
         return self.counters()
 
     # ------------------------------------------------------------------ search only (pv_mcts_policy)
-    def search(self, root_states72, check_saturation=True):
+    def search(self, root_states72, check_saturation=True, root_noise=None):
         """pv_mcts_policy for G roots at once: (visits i32 [G, MAX_LEGAL], actions u8, count i32).
+        root_noise: float64 [G, MAX_LEGAL] gamma variates of the roots (root_noise_eps > 0; default: the generator, keyed by slot).
         check_saturation (GNN evaluator): the fp16-range guard's word (counters[5]) is cleared before the search and read back after it
         (one 4-byte copy: the callers read the visit counts back anyway); if a launch of this search met a value outside fp16 range its
         evaluations were finite but not the network's, so the weight set is marked (model.mark_saturated), the engine switches to the
         exact f32-input kernels and the search is repeated -- the caller never receives visit counts of clamped evaluations."""
         roots = torch.as_tensor(root_states72, dtype=torch.uint8).to(self.dev).contiguous().view(self.G, 72)
         self._roots = roots
+        self._set_root_noise(root_noise)
         for attempt in range(2):
             guarded = check_saturation and self.evaluator == "gnn" and not (self.e.gnn_flags & _lib.GNN_EXACT_F32)
             if guarded:
@@ -341,6 +484,15 @@ class BatchedSelfPlay:
         _lib.check(self.lib.aqg_engine_root_visits(ctypes.byref(self.e), _lib.ptr(visits), _lib.ptr(actions), _lib.ptr(count),
                                                    self._stream()), "aqg_engine_root_visits")
         return visits, actions, count
+
+    def root_priors(self):
+        """The priors the last search or move built the root's children from: (priors f32 [G, MAX_LEGAL] in legal_actions() order,
+        0 past the count; count i32 [G]) -- with root noise on, the mixed priors."""
+        priors = torch.empty((self.G, _lib.MAX_LEGAL), dtype=torch.float32, device=self.dev)
+        count = torch.empty((self.G,), dtype=torch.int32, device=self.dev)
+        _lib.check(self.lib.aqg_engine_root_priors(ctypes.byref(self.e), _lib.ptr(priors), _lib.ptr(count), self._stream()),
+                   "aqg_engine_root_priors")
+        return priors, count
 
     # ------------------------------------------------------------------ history
     def history_tensors(self):
@@ -388,7 +540,7 @@ class MultiSetSelfPlay:
     BatchedSelfPlay(num_games_k, seed = seed * 64 + k): nothing is shared but the read-only packed weights (and the K
     streams, which every engine of the process reuses -- see _SET_STREAMS)."""
 
-    def __init__(self, model=None, num_games=2048, sims=50, num_sets=None, seed=0, device=None, quota=None, **kw):
+    def __init__(self, model=None, num_games=2048, sims=50, num_sets=None, seed=0, device=None, quota=None, root_noise_seed=None, **kw):
         self.dev = _lib.require_gpu(device)
         if num_sets is None:                      # one hardware queue per set + the default stream, or fall back to 2
             queues = os.environ.get("GPU_MAX_HW_QUEUES")
@@ -407,13 +559,15 @@ class MultiSetSelfPlay:
         self.streams = _SET_STREAMS[key]
         if model is not None and kw.get("evaluator", "gnn") in ("gnn", "cnn"):
             model.packed_weights(self.dev)        # pack (+ calibrate) (two forwards and a host sync) on the caller's stream, not inside set 0's
+        noise_seeds = set_noise_seeds(seed, root_noise_seed, sizes, [max(q, g) for q, g in zip(quotas, sizes)])
         self.sets = []
         ready = torch.cuda.current_stream(self.dev).record_event()   # e.g. the model's weight upload on the caller's stream
         for i, g in enumerate(sizes):
             with torch.cuda.stream(self.streams[i]):
                 self.streams[i].wait_event(ready)
                 self.sets.append(BatchedSelfPlay(model, num_games=g, sims=sims, seed=int(seed) * 64 + i, device=self.dev,
-                                                 quota=max(quotas[i], g), **kw))
+                                                 quota=max(quotas[i], g),
+                                                 root_noise_seed=noise_seeds[i], **kw))
         self.G, self.sims = int(num_games), int(sims)
         # quota > G: the slots are refilled -- a slot whose game has ended takes the next game not yet handed out (in slot
         # order, deterministic) until `quota` games have been started: the reference's loop over games (self_play.py:81-84)

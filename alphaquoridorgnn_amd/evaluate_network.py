@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from . import pv_mcts
 from .constants import PV_NETWORK_PATH, BOARD_SIZE
-from .engine import BatchedSelfPlay
+from .engine import BatchedSelfPlay, refuse_root_noise
 from .game_logic import State
 from .pv_network_gnn import GNNNetwork, load_network
 from .pv_network_cnn import CNNNetwork
@@ -56,7 +56,9 @@ class BatchedMatch:
     CNNNetworks, whose shapes may differ too) or integer biases of the parity tests' hash evaluator (evaluator='fake')."""
 
     def __init__(self, players, num_games, sims=None, board_size=BOARD_SIZE, temperature=EN_TEMPERATURE,
-                 evaluator="gnn", seed=0, device=None):
+                 evaluator="gnn", seed=0, device=None, root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None):
+        # (an evaluation match measures the networks as they are: root exploration noise is a self-play option and is refused)
+        refuse_root_noise("BatchedMatch", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
         self.players = players
         self.evaluator = evaluator
         sims = pv_mcts.PV_EVALUATE_COUNT if sims is None else sims
@@ -173,11 +175,12 @@ class BatchedMatch:
         return points
 
 
-def evaluate_network():
+def evaluate_network(root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None):
     """Network evaluation (evaluate_network.py:52-94): latest vs best, promote when the average point exceeds 0.5.  Two
     default 6/128/3 networks play on the engine's fused evaluator ('gnn'); when either file holds another shape, both play on
     its any-shape evaluator ('general').  Two CNNs (pv_network_cnn.py) play on the engine's CNN evaluator ('cnn'); a CNN against
     a GNN is refused (ValueError)."""
+    refuse_root_noise("evaluate_network", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
     model0 = load_network(PV_NETWORK_PATH + 'latest.pth')
     model1 = load_network(PV_NETWORK_PATH + 'best.pth')
     cnn = [isinstance(m, CNNNetwork) for m in (model0, model1)]

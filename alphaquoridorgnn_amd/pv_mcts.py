@@ -72,8 +72,11 @@ def pv_mcts_policy(model, state, temperature, device=None):
     return pv_mcts_policy_batch(model, rec, temperature, PV_EVALUATE_COUNT, state.N, evaluator=evaluator_of(model))[0]
 
 
-def pv_mcts_action(model, temperature=0, device='cpu'):
-    """Returns a function of the game state that selects an action based on PV-MCTS (pv_mcts.py:98-103)."""
+def pv_mcts_action(model, temperature=0, device='cpu', root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None):
+    """Returns a function of the game state that selects an action based on PV-MCTS (pv_mcts.py:98-103).  A player for matches:
+    it never adds root exploration noise, and the self-play options that ask for it are refused (ValueError)."""
+    from .engine import refuse_root_noise
+    refuse_root_noise("pv_mcts_action", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
     def pv_mcts_action(state):
         policy = pv_mcts_policy(model, state, temperature, device)
         return np.random.choice(state.legal_actions(), p=policy)

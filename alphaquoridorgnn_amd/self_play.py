@@ -21,6 +21,9 @@ from .pv_network_cnn import CNNNetwork
 
 SP_GAME_COUNT = 50    # Number of games for self-play (self_play.py:19; 25000 in the original version)
 SP_TEMPERATURE = 1.0  # Temperature parameter for Boltzmann distribution (self_play.py:20)
+# Root exploration noise (the reference has none; engine.BatchedSelfPlay): p' = (1 - eps) p + eps Dir(alpha) at every move's root.
+SP_ROOT_NOISE_EPS = 0.0      # 0 = off: the reference's games
+SP_ROOT_NOISE_ALPHA = None   # None = 10 / (N^2 + 2 (N - 1)^2), the "10 / typical number of moves" rule
 
 
 def first_player_value(ended_state):
@@ -57,7 +60,8 @@ def play(model, device=None, uniforms=None):
     Returns [[state_array, policy list[POLICY_OUTPUT_SIZE], z], ...]."""
     eng = BatchedSelfPlay(model, num_games=1, sims=pv_mcts.PV_EVALUATE_COUNT, board_size=BOARD_SIZE,
                           temperature=SP_TEMPERATURE, seed=int(np.random.randint(0, 2 ** 31 - 1)),
-                          evaluator=pv_mcts.evaluator_of(model))
+                          evaluator=pv_mcts.evaluator_of(model), root_noise_eps=SP_ROOT_NOISE_EPS,
+                          root_noise_alpha=SP_ROOT_NOISE_ALPHA)
     eng.play_generation(uniforms=uniforms, check_every=1)
     return eng.history()
 
@@ -101,7 +105,7 @@ def self_play(model=None, games=None, seed=None):
         # >= 256 games: independent game sets on their own streams fill the holes of each other's serial kernel chains
         eng = MultiSetSelfPlay(model, num_games=mine, sims=pv_mcts.PV_EVALUATE_COUNT, num_sets=None if mine >= 256 else 1,
                                board_size=BOARD_SIZE, temperature=SP_TEMPERATURE, seed=(base + rank) % (2 ** 31 - 1), device=dev,
-                               evaluator=evaluator)
+                               evaluator=evaluator, root_noise_eps=SP_ROOT_NOISE_EPS, root_noise_alpha=SP_ROOT_NOISE_ALPHA)
         c = eng.play_generation()
         print(f'\rSelf-play (rank {rank}: {c["finished"]}/{mine} games)', end='')
         st, vis, z = eng.history_tensors()
@@ -131,7 +135,14 @@ def main(argv=None):
     ap.add_argument("--games", type=int, default=None, help="games of the generation over ALL ranks (default SP_GAME_COUNT)")
     ap.add_argument("--sims", type=int, default=None, help="simulations per move (default pv_mcts.PV_EVALUATE_COUNT)")
     ap.add_argument("--seed", type=int, default=None, help="fix the uniform streams (default: fresh per call, like the reference)")
+    ap.add_argument("--root-noise-eps", type=float, default=None, help="weight of the Dirichlet noise at every root (default SP_ROOT_NOISE_EPS = 0: off)")
+    ap.add_argument("--root-noise-alpha", type=float, default=None, help="Dirichlet concentration (default SP_ROOT_NOISE_ALPHA: 10 / action count)")
     args = ap.parse_args(argv)
+    global SP_ROOT_NOISE_EPS, SP_ROOT_NOISE_ALPHA
+    if args.root_noise_eps is not None:
+        SP_ROOT_NOISE_EPS = args.root_noise_eps
+    if args.root_noise_alpha is not None:
+        SP_ROOT_NOISE_ALPHA = args.root_noise_alpha
     aqd.init_from_env()
     if args.sims is not None:
         pv_mcts.PV_EVALUATE_COUNT = args.sims

@@ -161,6 +161,10 @@ def _parser():
     ap.add_argument("--baseline-games", type=int, default=0,
                     help="games per baseline agent (random, alpha-beta, rollout MCTS) best.pth plays after each cycle's evaluation "
                          "stage, on rank 0 (default 0: no such stage)")
+    ap.add_argument("--root-noise-eps", type=float, default=None,
+                    help="self-play: weight of the Dirichlet noise mixed into every root's priors (default SP_ROOT_NOISE_EPS = 0: off)")
+    ap.add_argument("--root-noise-alpha", type=float, default=None,
+                    help="self-play: Dirichlet concentration (default SP_ROOT_NOISE_ALPHA: 10 / the board's action count)")
     return ap
 
 
@@ -178,6 +182,10 @@ def main(argv=None):
         sp.SP_GAME_COUNT = args.games
     if args.sims is not None:
         pv_mcts.PV_EVALUATE_COUNT = args.sims
+    if args.root_noise_eps is not None:
+        sp.SP_ROOT_NOISE_EPS = args.root_noise_eps
+    if args.root_noise_alpha is not None:
+        sp.SP_ROOT_NOISE_ALPHA = args.root_noise_alpha
     if args.epochs is not None:
         tn.NUM_EPOCH = args.epochs
     if args.eval_games is not None:

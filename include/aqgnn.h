@@ -347,6 +347,13 @@ typedef struct aqg_engine {
      * prior_mode 3, with gnn_workspace of aqg_cnn_workspace_floats(board_size, num_filters, A, G) floats; policy_size must be A.
      * Held by value like general_net: the captured per-move graphs are keyed by the packed buffer's address and the shape. */
     aqg_cnn_net cnn_net;
+    /* Root exploration noise (additive to ABI 15; see "root exploration noise" below).  root_noise_eps 0 = off: no launch, and a
+     * struct whose four fields are zero behaves exactly as before.  eps in [0, 1); alpha in (0, 100] when eps > 0.  root_noise: NULL =
+     * the counter-based generator keyed by root_noise_seed, else a device table f64 [G, AQG_MAX_LEGAL] of gamma variates that the
+     * caller refills before each move.  The four fields are part of the captured graph's key like every other byte of the struct. */
+    float root_noise_eps, root_noise_alpha;
+    uint64_t root_noise_seed;
+    const double* root_noise;
 } aqg_engine;
 
 /* Reset all G slots to the initial position (State() game_logic.py:25-40) and mark them active; clears the evaluation cache. */
@@ -389,6 +396,45 @@ int aqg_engine_root_visits(const aqg_engine* e_host, int32_t* visits, uint8_t* a
  *   a fresh tree, as every move does. */
 int aqg_engine_root_states72(const aqg_engine* e_host, uint8_t* out72, void* stream);
 int aqg_engine_apply_actions(const aqg_engine* e_host, const int32_t* actions, void* stream);
+
+/* ------------------------------------------------------------------ root exploration noise (additive to ABI 15)
+ *
+ * With root_noise_eps > 0 every searched move mixes a Dirichlet sample into the root's priors (the reference has no such step):
+ *     p'_i = (1 - eps) * p_i + eps * eta_i,   eta_i = f32(g_i / S),   S = g_0 + ... + g_{cnt-1} in float64,   g_i ~ Gamma(alpha, 1)
+ * over the root's legal_actions() in order, all in f32 without contraction: 1 - eps is one subtraction, then two products and one
+ * sum, each rounded.  p_i are the priors the step kernel would have taken: for the network evaluators the dense row gathered at the
+ * legal actions and divided by its sum unless that is 0 (one f32 division), otherwise the first cnt entries of the row.  One launch
+ * per move (csrc/mcts.hip, engine_root_noise_kernel), one wavefront per slot, between the evaluation of simulation 0 and the step
+ * of simulation 1, inside the captured graph; it acts on the active slots whose pending leaf is the root (path_len 0, leaf_flag 1
+ * or 2), writes p' to policy[g][0 .. cnt) and marks the leaf with leaf_flag 2 ("normalised priors in legal order").  No atomics, no
+ * allocation, no host synchronisation; S is summed in a fixed order, so two runs give identical bytes.
+ * The evaluation cache never sees p': a leaf_flag 2 leaf is not stored, and the slot's reservation (eval_cache_slot) is dropped, so
+ * the position -- which later turns up as an inner leaf -- is evaluated and stored with the network's own priors then.
+ * If S is 0 or not finite the root keeps its priors untouched; cnt == 0 writes nothing.
+ *
+ * g_i, table mode (root_noise != NULL): g_i = root_noise[g][i].  An entry that is not > 0 or not finite (NaN included) counts as 0:
+ *   that action gets no noise mass; a row without a usable entry leaves the root untouched.
+ * g_i, generator mode (root_noise == NULL): with mix, G and f(key, j) = (mix(key + G * (j + 1)) >> 11) * 2^-53 of the baseline
+ *   agents' generator above, K(s, b) = mix(s + G * (b + 1)):
+ *       root = K(K(root_noise_seed, k), ply)     k = slot_game[g], the GAME's index (the slot in the search-only entry point),
+ *                                                ply = the root's plies_played
+ *       key_i = K(root, i)                        component i draws from its own sub-stream: u_j = f(key_i, j)
+ *   so a game's noise does not depend on num_games, slot refill or launch geometry.  Gamma(alpha, 1) in float64 after Marsaglia and
+ *   Tsang, evaluated left to right without contraction: a = alpha + 1 if alpha < 1 else alpha; d = a - 1/3; c = 1 / sqrt(9 d);
+ *   attempt t = 0 .. 63:  x = sqrt(-2 log(1 - u_{1+3t})) * cospi(2 u_{2+3t});  v1 = 1 + c x;  rejected if v1 <= 0;  v = v1^3;
+ *       accepted if log(1 - u_{3+3t}) < 0.5 x x + d - d v + d log(v), and then g = d v.
+ *   After 64 rejected attempts g = d (the value of v = 1; the chance is below 1e-80).  For alpha < 1, g = g * (1 - u_0)^(1/alpha).
+ *   Finally g = max(g, DBL_MIN): the power may underflow, and a variate is never 0.  alpha is the f32 field widened to float64.
+ *   cospi(y) = cos(pi y) is what the device evaluates (the argument is reduced exactly, before the multiplication by pi).
+ *   engine.draw_root_noise(seed, k, ply, count, alpha) is the same function in numpy, with cos(2 pi u) for that factor (the product
+ *   2 pi u is rounded first); that and the device's log / sqrt / pow differ from the C library's around 1e-15 relative.
+ *
+ * aqg_engine_root_noise: the launch on its own, for the external-evaluator loop -- behind the caller's evaluation of simulation 0,
+ *   in front of aqg_engine_step(1, 1) -- and for tests.  With root_noise_eps == 0 it returns 0 and launches nothing.
+ * aqg_engine_root_priors: priors [G,AQG_MAX_LEGAL] f32 = field p of the root's children (0 past the count), count [G] i32: the
+ *   priors the last search built the root from, in the layout of aqg_engine_root_visits. */
+int aqg_engine_root_noise(const aqg_engine* e_host, void* stream);
+int aqg_engine_root_priors(const aqg_engine* e_host, float* priors, int32_t* count, void* stream);
 
 /* ------------------------------------------------------------------ baseline agents in batch (agents.py; additive to ABI 14)
  *
