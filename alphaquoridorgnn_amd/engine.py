@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from .constants import BOARD_SIZE, board_params
+from .evaluators import BINDINGS
 
 
 ROOT_NOISE_ATTEMPTS = 64      # cap of the gamma sampler's rejection loop (csrc/mcts.hip ROOT_NOISE_ATTEMPTS)
@@ -153,11 +154,8 @@ class BatchedSelfPlay:
         self.root_noise_eps, self.root_noise_alpha = check_root_noise(
             root_noise_eps, default_root_noise_alpha(board_size) if root_noise_alpha is None else root_noise_alpha)
         self.root_noise_seed = default_root_noise_seed(seed) if root_noise_seed is None else int(root_noise_seed) & _MASK64
-        if evaluator == "gnn" and model is not None and not getattr(model, "fused", True):
-            model._require_fused("evaluator='gnn'")          # before anything is allocated or launched
-        if evaluator == "general" and model is not None and getattr(model, "num_features", 6) != 6:
-            raise ValueError(f"evaluator='general': board records have 6 feature planes; this network takes "
-                             f"num_features={model.num_features}")
+        b = self.binding = BINDINGS[evaluator]
+        b.check(model)          # before anything is allocated or launched
         self.dev = _lib.require_gpu(device)
         self.lib = _lib.load()
         self.N = board_size
@@ -208,49 +206,23 @@ class BatchedSelfPlay:
         t["counters"] = z((8,), torch.int32)
         t["stat_leaf_evals"] = z((G,), torch.int32)
         t["stat_terminal_sims"] = z((G,), torch.int32)
-        self._general_key = None
-        if evaluator == "general":
-            if model is None or not hasattr(model, "general_net"):
-                raise ValueError("evaluator='general' needs a GraphPolicyValueNetwork")
-            self._general = model.general_net(dev)          # ValueError: not 6 input features, or parameters not f32 on dev
-            self._general_key = model.general_weights_key()
-            if model.policy_output_size != self.A:
-                raise ValueError(f"evaluator='general': the network's policy_output_size {model.policy_output_size} is not the "
-                                 f"{self.N}x{self.N} board's {self.A} actions")
+        e = self.e = _lib.EngineStructGeneral()
+        e.fake_bias = int(fake_bias)
+        self._handle = b.handle(model, dev, (self.N, self.A))      # kept alive: the struct points into it
+        b.point(self, self._handle)
+        self._gnn_flags = int(e.gnn_flags)
+        if "packed_weights" not in t:
             t["packed_weights"] = z((4,), torch.float32)
-            self._gnn_flags = 0
-            t["gnn_workspace"] = z((int(self.lib.aqg_gcn_boards_general_workspace_floats(self.N, model.hidden_dim, self.A, G)),),
-                                   torch.float32)
-        elif evaluator == "cnn":
-            if model is None or not hasattr(model, "cnn_net"):
-                raise ValueError("evaluator='cnn' needs a CNNNetwork")
-            if model.policy_output_size != self.A:
-                raise ValueError(f"evaluator='cnn': the network's policy_output_size {model.policy_output_size} is not the "
-                                 f"{self.N}x{self.N} board's {self.A} actions")
-            self._cnn_packed = model.packed_weights(dev)
-            self._cnn = model.cnn_net(dev)
-            t["packed_weights"] = z((4,), torch.float32)
-            self._gnn_flags = 0
-            t["gnn_workspace"] = z((int(self.lib.aqg_cnn_workspace_floats(self.N, model.num_filters, self.A, G)),), torch.float32)
-        elif evaluator == "gnn":
-            if model is None:
-                raise ValueError("evaluator='gnn' needs a model")
-            t["packed_weights"] = model.packed_weights(dev)
-            self._gnn_flags = model.gnn_flags(dev)
-            if self.N != 9:      # smaller boards run the any-size forward, which needs a caller-owned workspace
-                t["gnn_workspace"] = z((int(self.lib.aqg_gcn_boards_any_workspace_floats(self.N, G)),), torch.float32)
-        else:
-            if evaluator == "external" and (model is None or not hasattr(model, "predict")):
-                raise ValueError("evaluator='external' needs a model with predict(state, device)")
-            t["packed_weights"] = z((4,), torch.float32)
-            self._gnn_flags = 0
+        floats = b.workspace_floats(self.lib, model, self.N, self.A, G)
+        if floats:
+            t["gnn_workspace"] = z((floats,), torch.float32)
 
         if eval_cache_slots is None:              # opt-in for whole programs (self_play, train_cycle, pv_mcts): one environment variable
-            eval_cache_slots = int(os.environ.get("AQG_EVAL_CACHE_SLOTS", "0")) if evaluator in ("gnn", "general", "cnn") else 0
+            eval_cache_slots = int(os.environ.get("AQG_EVAL_CACHE_SLOTS", "0")) if b.network else 0
         self.eval_cache_slots = int(eval_cache_slots)
         if self.eval_cache_slots:
-            if evaluator not in ("gnn", "general", "cnn"):
-                raise ValueError("eval_cache_slots needs evaluator='gnn', 'general' or 'cnn' (the table stores network outputs)")
+            if not b.network:
+                raise ValueError("eval_cache_slots needs an evaluator of the library's own networks (the table stores network outputs)")
             if self.eval_cache_slots < 64 or self.eval_cache_slots & (self.eval_cache_slots - 1) or self.eval_cache_slots > (1 << 20):
                 raise ValueError("eval_cache_slots must be a power of two in 64 .. 2**20")
             t["eval_cache_keys"] = z((G * self.eval_cache_slots, 32), torch.uint8)
@@ -261,17 +233,10 @@ class BatchedSelfPlay:
             t["eval_list"] = z((G,), torch.int32)
             t["eval_count"] = z((self.sims + 1,), torch.int32)
 
-        e = self.e = _lib.EngineStructGeneral()
         e.board_size, e.num_walls, e.plies_for_draw = self.N, self.num_walls, self.plies_for_draw
         e.num_games, e.quota, e.sims, e.node_cap = G, Q, self.sims, cap
         e.max_plies = hp if record_history else 0
-        e.prior_mode = {"gnn": 0, "fake": 1, "external": 2, "general": 3, "cnn": 4}[evaluator]
-        if evaluator == "general":
-            e.general_net = self._general
-        elif evaluator == "cnn":
-            e.cnn_net = self._cnn
-        e.fake_bias = int(fake_bias)
-        e.gnn_flags = int(self._gnn_flags)
+        e.prior_mode = b.prior_mode
         e.c_puct, e.temperature = float(c_puct), float(temperature)
         for name in ("node_rec", "node_count", "root_state", "path",
                      "path_len", "leaf_flag", "leaf_state", "game_active", "slot_game", "game_plies", "game_result", "game_done",
@@ -299,32 +264,17 @@ class BatchedSelfPlay:
         self.moves_done = 0
 
     def refresh_weights(self):
-        if self.evaluator == "gnn":
-            new = self.model.packed_weights(self.dev)        # the SAME tensor object while no parameter has changed
-            flags = int(self.model.gnn_flags(self.dev))
-            changed = new is not self.t["packed_weights"] or flags != int(self.e.gnn_flags)
-            self.t["packed_weights"] = new
-            self.e.packed_weights = new.data_ptr()
-            self.e.gnn_flags = flags
-            if self.eval_cache_slots and changed:      # the table holds the OLD weights' (or the other kernel build's) outputs
-                _lib.check(self.lib.aqg_engine_clear_eval_cache(ctypes.byref(self.e), self._stream()), "aqg_engine_clear_eval_cache")
-        elif self.evaluator == "general":
-            # the descriptor points at the parameters themselves: rebuilt for a replaced tensor, the same bytes (and the same
-            # captured graph) after an in-place update -- which still makes the cached evaluations stale
-            self._general = self.model.general_net(self.dev)
-            self.e.general_net = self._general
-            key = self.model.general_weights_key()
-            if self.eval_cache_slots and key != self._general_key:
-                _lib.check(self.lib.aqg_engine_clear_eval_cache(ctypes.byref(self.e), self._stream()), "aqg_engine_clear_eval_cache")
-            self._general_key = key
-        elif self.evaluator == "cnn":
-            new = self.model.packed_weights(self.dev)        # the SAME tensor while no parameter or BN statistic has changed
-            changed = new is not self._cnn_packed
-            self._cnn_packed = new
-            self._cnn = self.model.cnn_net(self.dev)
-            self.e.cnn_net = self._cnn
-            if self.eval_cache_slots and changed:
-                _lib.check(self.lib.aqg_engine_clear_eval_cache(ctypes.byref(self.e), self._stream()), "aqg_engine_clear_eval_cache")
+        """Point the engine at the model's current weights; the evaluation cache is cleared when they are not the cached ones."""
+        if not self.binding.network:
+            return
+        handle = self.binding.handle(self.model, self.dev)
+        if self.eval_cache_slots and self.binding.stale(self, handle):      # the table holds the OLD weights' (or the other kernel build's) outputs
+            self._clear_eval_cache()
+        self.binding.point(self, handle)
+        self._handle = handle
+
+    def _clear_eval_cache(self):
+        _lib.check(self.lib.aqg_engine_clear_eval_cache(ctypes.byref(self.e), self._stream()), "aqg_engine_clear_eval_cache")
 
     def _set_root_noise(self, table):
         """Table mode: the gamma variates of this move's roots, float64 [G, MAX_LEGAL] (None = the generator).  The table is copied
@@ -420,15 +370,19 @@ class BatchedSelfPlay:
                     cache_hits=int(self.t["stat_cache_hits"].sum().item()) if self.eval_cache_slots else 0,
                     terminal_sims=int(self.t["stat_terminal_sims"].sum().item()))
 
-    def _fall_back_to_exact_kernels(self):
-        """The range guard fired: this weight set leaves fp16 range on positions of this generation.  Its evaluations so far
-        were finite but not the network's, so the generation is played again from the start on the exact f32-input kernels
-        (the reference's fp32 has no such cliff, pv_network_gnn.py:53-64)."""
+    def switch_to_exact_kernels(self, keep_roots=False):
+        """The range guard fired: this weight set leaves fp16 range on positions of this generation.  Its evaluations so far were
+        finite but not the network's, so the model is marked and the engine moves to the exact f32-input kernels (the reference's fp32
+        has no such cliff, pv_network_gnn.py:53-64).  The play paths then start again from the first ply (reset); search() keeps its
+        roots (keep_roots) and drops only the cached evaluations, which are the split kernels' clamped ones."""
         if self.model is not None and hasattr(self.model, "mark_saturated"):
             self.model.mark_saturated(self.dev)
-        self._gnn_flags = _lib.GNN_EXACT_F32
-        self.e.gnn_flags = _lib.GNN_EXACT_F32
-        self.reset()
+        self._gnn_flags = self.e.gnn_flags = _lib.GNN_EXACT_F32
+        self.t["counters"][5] = 0
+        if not keep_roots:
+            self.reset()
+        elif self.eval_cache_slots:
+            self._clear_eval_cache()
 
     def play_generation(self, uniforms=None, check_every=4, root_noise=None):
         """Play the whole quota (== every slot once when quota == num_games: one self_play generation's worth of games
@@ -442,7 +396,7 @@ class BatchedSelfPlay:
             if ply >= limit or ply % check_every == 0:
                 c = self.counters()
                 if c["gnn_saturated"] and not (self.e.gnn_flags & _lib.GNN_EXACT_F32):
-                    self._fall_back_to_exact_kernels()
+                    self.switch_to_exact_kernels()
                     ply = 0
                     continue
                 if c["active"] == 0 or ply >= limit:
@@ -461,7 +415,7 @@ class BatchedSelfPlay:
         self._roots = roots
         self._set_root_noise(root_noise)
         for attempt in range(2):
-            guarded = check_saturation and self.evaluator == "gnn" and not (self.e.gnn_flags & _lib.GNN_EXACT_F32)
+            guarded = check_saturation and self.binding.guarded and not (self.e.gnn_flags & _lib.GNN_EXACT_F32)
             if guarded:
                 self.t["counters"][5] = 0          # a cached engine (pv_mcts._engines) must not inherit an earlier search's word
             if self.evaluator == "external":
@@ -471,13 +425,7 @@ class BatchedSelfPlay:
                 _lib.check(self.lib.aqg_engine_search(ctypes.byref(self.e), _lib.ptr(roots), self._stream()), "aqg_engine_search")
             if not guarded or int(self.t["counters"][5].item()) == 0:
                 break
-            if self.model is not None and hasattr(self.model, "mark_saturated"):
-                self.model.mark_saturated(self.dev)
-            self._gnn_flags = _lib.GNN_EXACT_F32
-            self.e.gnn_flags = _lib.GNN_EXACT_F32
-            self.t["counters"][5] = 0
-            if self.eval_cache_slots:      # the table holds the clamped evaluations of the split kernels
-                _lib.check(self.lib.aqg_engine_clear_eval_cache(ctypes.byref(self.e), self._stream()), "aqg_engine_clear_eval_cache")
+            self.switch_to_exact_kernels(keep_roots=True)
         visits = torch.empty((self.G, _lib.MAX_LEGAL), dtype=torch.int32, device=self.dev)
         actions = torch.empty((self.G, _lib.MAX_LEGAL), dtype=torch.uint8, device=self.dev)
         count = torch.empty((self.G,), dtype=torch.int32, device=self.dev)
@@ -557,7 +505,7 @@ class MultiSetSelfPlay:
         if key not in _SET_STREAMS:
             _SET_STREAMS[key] = [torch.cuda.Stream(device=self.dev) for _ in sizes]
         self.streams = _SET_STREAMS[key]
-        if model is not None and kw.get("evaluator", "gnn") in ("gnn", "cnn"):
+        if model is not None and BINDINGS[kw.get("evaluator", "gnn")].packed:
             model.packed_weights(self.dev)        # pack (+ calibrate) (two forwards and a host sync) on the caller's stream, not inside set 0's
         noise_seeds = set_noise_seeds(seed, root_noise_seed, sizes, [max(q, g) for q, g in zip(quotas, sizes)])
         self.sets = []
@@ -569,9 +517,6 @@ class MultiSetSelfPlay:
                                                  quota=max(quotas[i], g),
                                                  root_noise_seed=noise_seeds[i], **kw))
         self.G, self.sims = int(num_games), int(sims)
-        # quota > G: the slots are refilled -- a slot whose game has ended takes the next game not yet handed out (in slot
-        # order, deterministic) until `quota` games have been started: the reference's loop over games (self_play.py:81-84)
-        # on G concurrent slots instead of lock-step generations that idle every finished slot until the longest game ends
         self.quota = self.G if quota is None else int(quota)
         if self.quota < self.G:
             raise ValueError("quota must be >= num_games")
@@ -640,7 +585,7 @@ class MultiSetSelfPlay:
                 c = self.counters()
                 if c["gnn_saturated"] and any(not (e.e.gnn_flags & _lib.GNN_EXACT_F32) for e in self.sets):
                     for _, eng in self._each():          # fp16-range guard: replay the generation on the exact f32 kernels
-                        eng._fall_back_to_exact_kernels()
+                        eng.switch_to_exact_kernels()
                     self._live = [True] * len(self.sets)
                     ply = 0
                     continue
@@ -660,6 +605,47 @@ class MultiSetSelfPlay:
             for x in p:
                 x.record_stream(cur)              # the caching allocator must not recycle them under the concatenation
         return tuple(torch.cat([p[j] for p in parts], 0) for j in range(3))
+
+
+class TwoEngineMatch:
+    """`num_games` games between two sides, game i with side (i % 2) moving first, on two engines: engine `first` holds the games
+    in which side `first` moves first.  The loop of evaluate_network.BatchedMatch and evaluate_agents.BatchedAgentMatch; a subclass
+    says how an engine is built (`_engine(first, **kw)`) and how engine `first` makes ply `ply` (`_ply(eng, first, ply, *draws)`)."""
+
+    def _build_engines(self, num_games, seed, **kw):
+        self.num_games = int(num_games)
+        counts = [(self.num_games + 1) // 2, self.num_games // 2]          # games with side 0 first / side 1 first
+        self.engines = [self._engine(first, num_games=g, seed=2 * int(seed) + first, **kw) if g else None
+                        for first, g in enumerate(counts)]
+
+    def _switch_to_exact_kernels(self):
+        for eng in filter(None, self.engines):
+            eng.switch_to_exact_kernels()
+
+    def _play(self, *draws):
+        """Play every game to the end; side 0's points per game in game order.  fp16-range guard: the counters are read after every
+        ply anyway; if a split-kernel launch met a value outside fp16 range (counters()['gnn_saturated']) the moves so far were searched
+        with clamped evaluations, so every evaluation switches to the exact f32-input kernels and the match is replayed from ply 0."""
+        live = [e is not None for e in self.engines]
+        ply = 0
+        while any(live):
+            for first, eng in enumerate(self.engines):      # every live engine moves ...
+                if live[first]:
+                    self._ply(eng, first, ply, *draws)
+            ply += 1
+            for first, eng in enumerate(self.engines):      # ... before any counter is read: the host does not serialise the two
+                if not live[first]:
+                    continue
+                c = eng.counters()
+                if eng.binding.guarded and c["gnn_saturated"] and not (eng.e.gnn_flags & _lib.GNN_EXACT_F32):
+                    self._switch_to_exact_kernels()
+                    return self._play(*draws)               # (once: the exact kernels have no guard to fire)
+                if c["active"] == 0 or ply >= eng.max_plies:
+                    live[first] = False
+        # the first mover's result, +1 / -1 / 0, of every game of each engine
+        z0 = [np.zeros((0,)) if eng is None else eng.t["game_result"].cpu().numpy().astype(np.float64) for eng in self.engines]
+        per = [(z0[0] + 1.0) / 2.0, 1.0 - (z0[1] + 1.0) / 2.0]      # first_player_point, as side 0's (evaluate_network.py:71-74)
+        return [float(per[i % 2][i // 2]) for i in range(self.num_games)]
 
 
 def gather_history(states72, visits, z, group=None, force_collective=None):

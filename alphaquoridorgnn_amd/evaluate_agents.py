@@ -14,10 +14,11 @@ pool: `backend` below) -- and applied to the engine without a search
 import numpy as np
 import torch
 
-from . import _lib, agents, constants
+from . import agents, constants
 from . import pv_mcts
 from .constants import BOARD_SIZE, board_params
-from .engine import BatchedSelfPlay, refuse_root_noise
+from .engine import BatchedSelfPlay, TwoEngineMatch, refuse_root_noise
+from .evaluators import BINDINGS
 from .game_logic import State
 
 EP_GAME_COUNT = 10  # Number of games per evaluation (evaluate_agents.py:15)
@@ -60,7 +61,7 @@ def evaluate_algorithm_of(label, next_actions, games=None, board_size=None):
 AGENTS = ("random", "alpha_beta", "mcts")
 
 
-class BatchedAgentMatch:
+class BatchedAgentMatch(TwoEngineMatch):
     """`num_games` games of a network against a baseline agent on the batched engine; the network moves first in game i when i is
     even (evaluate_agents.py:46-51).  Two engines, as BatchedMatch has them: the network-first games and the agent-first games.
     Each ply, each engine either searches (`move`) or reads its roots, asks the agent for one action per slot and applies them.
@@ -80,29 +81,19 @@ class BatchedAgentMatch:
         refuse_root_noise("BatchedAgentMatch", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
         if not callable(agent) and agent not in AGENTS:
             raise ValueError(f"agent must be one of {AGENTS} or a callable state -> action")
-        if evaluator not in ("gnn", "general", "cnn", "fake", "external"):
-            raise ValueError("evaluator must be 'gnn', 'general', 'cnn', 'fake' or 'external'")
+        if evaluator not in BINDINGS:
+            raise ValueError(f"evaluator must be one of {', '.join(BINDINGS)}")
         self.model, self.agent, self.evaluator = model, agent, evaluator
         self.agent_kwargs = dict(agent_kwargs or {})
         if self.agent_kwargs.get("backend", "auto") not in ("auto", "hip", "host"):
             raise ValueError("agent_kwargs['backend'] must be 'auto', 'hip' or 'host'")
         self.N, self.seed = int(board_size), int(seed)
-        self.num_games = int(num_games)
-        sims = pv_mcts.PV_EVALUATE_COUNT if sims is None else sims
-        counts = [(self.num_games + 1) // 2, self.num_games // 2]     # games with the network first / the agent first
-        self.engines = []
-        for first, g in enumerate(counts):
-            if g == 0:
-                self.engines.append(None)
-                continue
-            kw = dict(num_games=g, sims=sims, board_size=board_size, temperature=temperature, seed=2 * self.seed + first,
-                      device=device)
-            if evaluator == "fake":
-                eng = BatchedSelfPlay(None, evaluator="fake", fake_bias=int(model), **kw)
-            else:
-                eng = BatchedSelfPlay(model, evaluator=evaluator, **kw)
-            self.engines.append(eng)
         self.current = None
+        self._build_engines(num_games, self.seed, sims=pv_mcts.PV_EVALUATE_COUNT if sims is None else sims, board_size=board_size,
+                            temperature=temperature, device=device)
+
+    def _engine(self, first, **kw):
+        return BatchedSelfPlay(self.model, evaluator=self.evaluator, **kw)      # ('fake': the model is the integer bias)
 
     def _alpha_beta_on_device(self, eng):
         backend = self.agent_kwargs.get("backend", "auto")
@@ -156,56 +147,18 @@ class BatchedAgentMatch:
         temperature 0).  agent_uniforms: optional pair of float64 [max_plies, G_engine, n]: [ply][g] is the table of draws of slot
         g's agent move at that ply ('random': n >= 1; 'mcts': n >= evaluations * plies to the draw limit); default: the generator,
         seeded per engine and ply from `seed`.
-        fp16-range guard ('gnn'): as BatchedMatch.play -- if a split-kernel launch met a value outside fp16 range, every evaluation
-        switches to the exact f32-input kernels and the match is replayed from ply 0."""
-        while True:
-            points = self._play_once(uniforms, agent_uniforms)
-            if points is not None:
-                return points
-
-    def _switch_to_exact_kernels(self):
-        if hasattr(self.model, "mark_saturated"):
-            self.model.mark_saturated()
-        for eng in self.engines:
-            if eng is not None:
-                eng._gnn_flags = _lib.GNN_EXACT_F32
-                eng.e.gnn_flags = _lib.GNN_EXACT_F32
+        fp16-range guard ('gnn'): the match is replayed from ply 0 on the exact f32-input kernels (TwoEngineMatch._play)."""
+        for eng in filter(None, self.engines):
+            if eng.moves_done:          # a second play() on the same object plays the match again
                 eng.reset()
+        return self._play(uniforms, agent_uniforms)
 
-    def _play_once(self, uniforms, agent_uniforms):
-        live = [e is not None for e in self.engines]
-        for eng in self.engines:
-            if eng is not None and eng.moves_done:
-                eng.reset()
-        ply = 0
-        while any(live):
-            for first, eng in enumerate(self.engines):
-                if not live[first]:
-                    continue
-                if (ply % 2 == 0) == (first == 0):                       # the network's ply
-                    eng.move(None if uniforms is None else uniforms[first][ply])
-                else:
-                    table = None if agent_uniforms is None else agent_uniforms[first][ply]
-                    eng.apply_actions(self._agent_actions(eng, first, ply, table))
-            ply += 1
-            for first, eng in enumerate(self.engines):
-                if not live[first]:
-                    continue
-                c = eng.counters()
-                if self.evaluator == "gnn" and c["gnn_saturated"] and not (eng.e.gnn_flags & _lib.GNN_EXACT_F32):
-                    self._switch_to_exact_kernels()
-                    return None
-                if c["active"] == 0 or ply >= eng.max_plies:
-                    live[first] = False
-        per = []
-        for first, eng in enumerate(self.engines):
-            if eng is None:
-                per.append(np.zeros((0,)))
-                continue
-            z0 = eng.t["game_result"].cpu().numpy().astype(np.float64)     # first mover's result: +1 / -1 / 0
-            fp = (z0 + 1.0) / 2.0                                          # first_player_point
-            per.append(fp if first == 0 else 1.0 - fp)                    # evaluate_agents.py:48-51
-        return [float(per[i % 2][i // 2]) for i in range(self.num_games)]
+    def _ply(self, eng, first, ply, uniforms, agent_uniforms):
+        if (ply % 2 == 0) == (first == 0):                       # the network's ply
+            eng.move(None if uniforms is None else uniforms[first][ply])
+        else:
+            table = None if agent_uniforms is None else agent_uniforms[first][ply]
+            eng.apply_actions(self._agent_actions(eng, first, ply, table))
 
 
 _LABELS = {"random": "VS_Random", "alpha_beta": "VS_AlphaBeta", "mcts": "VS_MCTS"}
@@ -222,6 +175,7 @@ def evaluate_best_player(games=None, agents=AGENTS, seed=None, root_noise_eps=No
     games = EP_GAME_COUNT if games is None else int(games)
     model = load_network(constants.PV_NETWORK_PATH + 'best.pth')
     board = _BOARD_OF_POLICY.get(int(model.policy_output_size), BOARD_SIZE)
+    # by class: the board follows the file's policy head here, and load_network makes a GNNNetwork only of 6/128/3 WITH the 9x9 head
     evaluator = "cnn" if isinstance(model, CNNNetwork) else "gnn" if isinstance(model, GNNNetwork) else "general"
     seed = int(np.random.randint(0, 2 ** 30)) if seed is None else int(seed)
     out = {}

@@ -15,7 +15,8 @@ import torch
 from . import _lib
 from . import pv_mcts
 from .constants import PV_NETWORK_PATH, BOARD_SIZE
-from .engine import BatchedSelfPlay, refuse_root_noise
+from .engine import BatchedSelfPlay, TwoEngineMatch, refuse_root_noise
+from .evaluators import BINDINGS
 from .game_logic import State
 from .pv_network_gnn import GNNNetwork, load_network
 from .pv_network_cnn import CNNNetwork
@@ -49,7 +50,7 @@ def update_best_player():
     print('Latest model is better than current best. Replacing best model with latest.')
 
 
-class BatchedMatch:
+class BatchedMatch(TwoEngineMatch):
     """`num_games` games of player 0 vs player 1 on the batched engine; game i has player (i % 2) moving first
     (evaluate_network.py:69-74).  Players are models (evaluator='gnn': the default 6/128/3 network; evaluator='general':
     GraphPolicyValueNetworks of any shape with 6 input features, the two players' shapes may differ; evaluator='cnn': two
@@ -59,120 +60,40 @@ class BatchedMatch:
                  evaluator="gnn", seed=0, device=None, root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None):
         # (an evaluation match measures the networks as they are: root exploration noise is a self-play option and is refused)
         refuse_root_noise("BatchedMatch", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
-        self.players = players
-        self.evaluator = evaluator
-        sims = pv_mcts.PV_EVALUATE_COUNT if sims is None else sims
-        counts = [(num_games + 1) // 2, num_games // 2]          # games with player 0 first / player 1 first
-        self.engines = []
-        for first, g in enumerate(counts):
-            if g == 0:
-                self.engines.append(None)
-                continue
-            # (no evaluation cache here: the two players' weights take turns on one engine, a table would mix their outputs)
-            kw = dict(num_games=g, sims=sims, board_size=board_size, temperature=temperature, seed=2 * int(seed) + first,
-                      device=device, eval_cache_slots=0)
-            if evaluator == "gnn":
-                eng = BatchedSelfPlay(players[first], **kw)
-            elif evaluator == "general":
-                # built on the wider player (the engine's workspace is sized by the network it is built with), then pointed
-                # at the mover's descriptor before every ply
-                eng = BatchedSelfPlay(self._widest(players), evaluator="general", **kw)
-            elif evaluator == "cnn":
-                # likewise: the workspace grows with num_filters only
-                eng = BatchedSelfPlay(max(players, key=lambda m: m.num_filters), evaluator="cnn", **kw)
-            else:
-                eng = BatchedSelfPlay(None, evaluator="fake", fake_bias=int(players[first]), **kw)
-            self.engines.append(eng)
-        if evaluator == "gnn":
-            dev = next(e for e in self.engines if e is not None).dev
-            self._packed = [m.packed_weights(dev) for m in players]
-            self._flags = [int(m.gnn_flags(dev)) for m in players]
-        elif evaluator == "general":
-            dev = next(e for e in self.engines if e is not None).dev
-            for m in players:
-                if m.policy_output_size != players[0].policy_output_size:
-                    raise ValueError("evaluator='general': the two players' policy sizes differ")
-            self._general = [m.general_net(dev) for m in players]
-        elif evaluator == "cnn":
-            dev = next(e for e in self.engines if e is not None).dev
-            for m in players:
-                if m.policy_output_size != players[0].policy_output_size:
-                    raise ValueError("evaluator='cnn': the two players' policy sizes differ")
-            self._packed = [m.packed_weights(dev) for m in players]      # kept alive: the descriptors point into them
-            self._cnn = [m.cnn_net(dev) for m in players]
+        if evaluator == "external":
+            raise ValueError("BatchedMatch has no evaluator='external': an engine asks one model, eng.model, from the host")
+        self.players, self.evaluator, self.binding = players, evaluator, BINDINGS[evaluator]
+        # (no evaluation cache here: the two players' weights take turns on one engine, a table would mix their outputs)
+        self._build_engines(num_games, seed, sims=pv_mcts.PV_EVALUATE_COUNT if sims is None else sims, board_size=board_size,
+                            temperature=temperature, device=device, eval_cache_slots=0)
+        eng = self.engines[0]      # (there unless the match has no game at all); the handles are what _ply points an engine at
+        self._handles = [] if eng is None else [self.binding.handle(m, eng.dev, (eng.N, eng.A)) for m in players]
 
-    @staticmethod
-    def _widest(players):
-        """The player whose workspace of aqg_gcn_forward_boards_general is the larger (it grows with hidden_dim only)."""
-        return max(players, key=lambda m: m.hidden_dim)
+    def _engine(self, first, **kw):
+        # built with the player whose workspace is the larger, then pointed at the mover's handle before every ply
+        return BatchedSelfPlay(self.binding.sizing_player(self.players), evaluator=self.evaluator, **kw)
 
-    def _point_at(self, eng, mover):
-        if self.evaluator == "gnn":
-            eng.t["packed_weights"] = self._packed[mover]
-            eng.e.packed_weights = self._packed[mover].data_ptr()
-            eng.e.gnn_flags = self._flags[mover]
-        elif self.evaluator == "general":
-            eng.e.general_net = self._general[mover]
-        elif self.evaluator == "cnn":
-            eng.e.cnn_net = self._cnn[mover]
-        else:
-            eng.e.fake_bias = int(self.players[mover])
+    @property
+    def _flags(self):
+        """evaluator='gnn': the gnn_flags each player's evaluations carry."""
+        return [h[1] for h in self._handles]
+
+    def _ply(self, eng, first, ply, uniforms):
+        self.binding.point(eng, self._handles[first if ply % 2 == 0 else 1 - first])
+        eng.move(None if uniforms is None else uniforms[first][ply])
 
     def play(self, uniforms=None):
-        """Play every game to the end.  uniforms: optional pair of float64 arrays [max_plies, G_first] (parity tests).
-        Returns the per-game points of player 0 in game order.
-        fp16-range guard: the engines' counters are read after every ply anyway; if a split-kernel launch of either player met a value
-        outside fp16 range (counters()['gnn_saturated']) the moves so far were searched with clamped evaluations, so BOTH players are
-        marked (mark_saturated), every evaluation switches to the exact f32-input kernels and the match is replayed from ply 0 -- the
-        promotion decision of evaluate_network (evaluate_network.py:90-94) is never taken on evaluations that are not the networks'."""
-        while True:
-            points = self._play_once(uniforms)
-            if points is not None:
-                return points
+        """Play every game to the end.  uniforms: optional pair of float64 arrays [max_plies, G_first] (parity tests).  Returns the
+        per-game points of player 0 in game order.  fp16-range guard (TwoEngineMatch._play): BOTH players are marked (mark_saturated) before
+        the replay -- the promotion decision (evaluate_network.py:90-94) is never taken on evaluations that are not the networks'."""
+        return self._play(uniforms)
 
     def _switch_to_exact_kernels(self):
         for m in self.players:
             if hasattr(m, "mark_saturated"):
-                m.mark_saturated()
-        self._flags = [_lib.GNN_EXACT_F32 for _ in self.players]
-        for eng in self.engines:
-            if eng is not None:
-                eng._gnn_flags = _lib.GNN_EXACT_F32
-                eng.e.gnn_flags = _lib.GNN_EXACT_F32
-                eng.reset()
-
-    def _play_once(self, uniforms):
-        live = [e is not None for e in self.engines]
-        ply = 0
-        while any(live):
-            for first, eng in enumerate(self.engines):
-                if not live[first]:
-                    continue
-                self._point_at(eng, first if ply % 2 == 0 else 1 - first)
-                eng.move(None if uniforms is None else uniforms[first][ply])
-            ply += 1
-            for first, eng in enumerate(self.engines):
-                if not live[first]:
-                    continue
-                c = eng.counters()
-                if self.evaluator == "gnn" and c["gnn_saturated"] and not all(f & _lib.GNN_EXACT_F32 for f in self._flags):
-                    self._switch_to_exact_kernels()
-                    return None
-                if c["active"] == 0 or ply >= eng.max_plies:
-                    live[first] = False
-        points = []
-        per = []
-        for first, eng in enumerate(self.engines):
-            if eng is None:
-                per.append(np.zeros((0,)))
-                continue
-            z0 = eng.t["game_result"].cpu().numpy().astype(np.float64)     # first mover's result: +1 / -1 / 0
-            fp = (z0 + 1.0) / 2.0                                          # first_player_point
-            per.append(fp if first == 0 else 1.0 - fp)                    # evaluate_network.py:71-74
-        n = len(per[0]) + len(per[1])
-        for i in range(n):
-            points.append(float(per[i % 2][i // 2]))
-        return points
+                m.mark_saturated(self.engines[0].dev)
+        self._handles = [(packed, _lib.GNN_EXACT_F32) for packed, _ in self._handles]
+        super()._switch_to_exact_kernels()
 
 
 def evaluate_network(root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None):
@@ -187,7 +108,7 @@ def evaluate_network(root_noise_eps=None, root_noise_alpha=None, root_noise_seed
     if any(cnn) and not all(cnn):
         raise ValueError("evaluate_network: latest.pth and best.pth hold different networks (a CNN and a GNN); matches between "
                          "a CNN and a GNN are not supported")
-    fused = all(isinstance(m, GNNNetwork) for m in (model0, model1))
+    fused = all(isinstance(m, GNNNetwork) for m in (model0, model1))      # (by class, as evaluate_agents does: both files, or neither)
     if fused and torch.cuda.is_available():
         for m in (model0, model1):
             m.packed_weights(torch.device("cuda", torch.cuda.current_device()))

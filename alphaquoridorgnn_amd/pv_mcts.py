@@ -23,8 +23,8 @@ def _engine_for(model, num_games, sims, board_size, evaluator="gnn", fake_bias=0
             _engines.clear()
         eng = _engines[key] = BatchedSelfPlay(model, num_games=num_games, sims=sims, board_size=board_size,
                                               evaluator=evaluator, fake_bias=fake_bias, record_history=False)
-    elif evaluator in ("gnn", "general", "cnn"):
-        eng.refresh_weights()
+    else:
+        eng.refresh_weights()          # (a network evaluator's weights may have changed since; nothing to do for the others)
     return eng
 
 
@@ -63,6 +63,7 @@ def evaluator_of(model):
     from .pv_network_cnn import CNNNetwork
     if isinstance(model, CNNNetwork):
         return "cnn"
+    # (another GNN shape stays 'external', not 'general': this surface serves ANY object through its predict, as the reference does)
     return "gnn" if hasattr(model, "packed_weights") and getattr(model, "fused", True) else "external"
 
 

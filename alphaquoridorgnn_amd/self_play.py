@@ -90,7 +90,7 @@ def self_play(model=None, games=None, seed=None):
         model = load_network(PV_NETWORK_PATH + 'best.pth')       # GNNNetwork (prep_for_inference's path), or the network best.pth holds
         if isinstance(model, (GNNNetwork, CNNNetwork)) and torch.cuda.is_available():
             model.packed_weights(torch.device("cuda", torch.cuda.current_device()))
-    # the default 6/128/3 network runs the engine's fused evaluator; any other shape its any-shape evaluator; the CNN its own
+    # by the trunk alone (model.fused, whatever the policy head: a caller's model need not come from a file): 6/128/3 runs the fused evaluator; any other shape the any-shape one; the CNN its own
     evaluator = "cnn" if isinstance(model, CNNNetwork) else "gnn" if getattr(model, "fused", True) else "general"
     total = SP_GAME_COUNT if games is None else games
     distributed = dist.is_available() and dist.is_initialized()
