@@ -14,13 +14,21 @@ else
   OBJDIR=$(mktemp -d)
   trap 'rm -rf "$OBJDIR"' EXIT
 fi
+# The one list of translation units: every diagnostic and A/B build goes through this script (AQG_EXTRA_FLAGS, OUT, OBJDIR).
+# AQG_REPLACE="unit=path ..." compiles another version of a unit in its place (absolute paths; e.g. an older gcn_trunk_split.hip).
 objs=()
 pids=()
-for f in legal_mask gcn_forward gcn_general gcn_boards_general gcn_train gcn_train_general cnn_forward cnn_train mcts agents capi; do
-  $HIPCC $FLAGS -c $f.hip -o "${OBJDIR}/aqg_$f.o" &
+replaced=0
+for f in legal_mask board_featuriser gcn_pack gcn_trunk_split gcn_trunk_exact gcn_boards_plain gcn_forward gcn_general gcn_boards_general gcn_train gcn_train_general cnn_forward cnn_train mcts agents capi; do
+  src=$f.hip
+  for pair in ${AQG_REPLACE:-}; do
+    if [ "${pair%%=*}" = "$f" ]; then src=${pair#*=}; replaced=$((replaced + 1)); fi
+  done
+  $HIPCC $FLAGS -I. -c "$src" -o "${OBJDIR}/aqg_$f.o" &
   pids+=($!)
   objs+=("${OBJDIR}/aqg_$f.o")
 done
+if [ "$replaced" -ne "$(echo ${AQG_REPLACE:-} | wc -w)" ]; then echo "build.sh: AQG_REPLACE names a unit that is not built: ${AQG_REPLACE}" >&2; exit 2; fi
 # host-only code (CPU baseline agents over the same rule header): plain C++, no device pass
 ${CXX:-g++} -O2 -std=c++17 -fPIC -Wall -Wno-unknown-pragmas -c host_agents.cpp -o "${OBJDIR}/aqg_host_agents.o" &
 pids+=($!)

@@ -1,7 +1,7 @@
 // cnn_forward.hip -- the reference's residual CNN (pv_network_cnn.py:20-84, CNNNetwork) in eval mode on board records or on
 // [B,6,N,N] planes (include/aqgnn.h, aqg_cnn_*): the forward the engine's prior_mode 4 enqueues per simulation.
 //
-//   featuriser   boards_prep_kernel<N, false> (gcn_forward.hip): x0 [B*V, 6], the six planes of pv_network_cnn.py:88-114 per tile
+//   featuriser   boards_prep_kernel<N, false> (board_featuriser.hip): x0 [B*V, 6], the six planes of pv_network_cnn.py:88-114 per tile
 //                (or, from planes, cnn_planes_kernel: the NCHW input read into the same tile-major rows)
 //   2 L + 1 convs  cnn_conv_kernel: relu(conv3x3(x) * scale + shift (+ residual)), one launch per conv, eval-mode BatchNorm2d
 //                folded into the per-channel scale / shift at pack time; the last conv writes AdaptiveAvgPool2d(1) instead

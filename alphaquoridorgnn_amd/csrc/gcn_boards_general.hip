@@ -1,7 +1,7 @@
 // gcn_boards_general.hip -- GraphPolicyValueNetwork of ANY shape on board records (include/aqgnn.h, aqg_gcn_forward_boards_general):
 // the forward the engine's prior_mode 3 enqueues per simulation, and forward_states of a non-default shape.
 //
-//   featuriser   boards_prep_kernel (gcn_forward.hip): x0 [B*V, 6] + the normalised wall-cut grid as ELL rows of 5
+//   featuriser   boards_prep_kernel (board_featuriser.hip): x0 [B*V, 6] + the normalised wall-cut grid as ELL rows of 5
 //   L layers     board_gcn_layer_kernel: H_out = relu(A_hat (H_in W^T) + b), one launch per layer; the last one writes the mean pool
 //   heads        gen_linear x 4 and gen_heads (gcn_general.hip)
 //

@@ -1,1658 +1,18 @@
-// gcn_forward.hip -- K1/K2: GraphPolicyValueNetwork.forward (pv_network_gnn.py:53-64) for gfx950, fp32.
+// gcn_forward.hip -- the front door of GraphPolicyValueNetwork.forward (hidden width 128) on 9x9 board records
+// (include/aqgnn.h, aqg_gcn_forward_boards*): picks the trunk variant and its instantiation, enqueues trunk and heads through the
+// launchers of the kernel files, and brackets the trunk launch with the optional profiling events.
 //
-// trunk kernel (boards): one 256-thread workgroup walks boards; per board the whole 3-layer GCN trunk runs
-// out of ONE in-place LDS image H[81][132] f32 (HBM traffic: 72/24 B in, 512 B out per board):
-//   setup   : wall masks -> per-node degree / sym-norm coefficients + the 6 node features (pv_network_cnn.py:88-114)
-//   layer 1 : aggregate the 6-wide features over the <=5-point wall-cut stencil, then 6->128 on VALU
-//   layer 2,3: dense 128x128 contraction on f32-input MFMA (v_mfma_f32_16x16x4_f32; rows 0..79 as five
-//             16-row tiles, row 80 on VALU -> no padded MFMA work), accumulators staged in registers and
-//             written back in place; then the normalised neighbour gather (= PyG's scatter-add on this
-//             fixed-degree graph) + bias + ReLU, again register-staged in place
-//   pool    : global_mean_pool fused into the layer-3 gather
-// Each wave owns 32 output columns and keeps its slice of W2^T and W3^T in registers for the whole kernel
-// (128 VGPRs), so weights cost no LDS/L2 traffic per board.  K is permuted (lane quarter q covers
-// k in [kbase[q], kbase[q]+32)) so every A fragment is 8 contiguous ds_read_b128 and the padded row stride
-// (132 floats) keeps each 16-lane ds_read_b128 group on 16 distinct 16-byte bank slots.
+//   packed weights   gcn_packed.hpp (layout), gcn_pack.hip (host packing)
+//   trunk + heads    gcn_trunk_split.hip (default: fp16-split matrix pipe), gcn_trunk_exact.hip (exact f32; the range guard's fallback)
+//   other sizes      gcn_boards_plain.hip (3x3 / 5x5 / 7x7) on board_featuriser.hip; any (x, edge_index, batch) graph: gcn_general.hip
 //
-// heads kernel: policy MLP 128->64->209 (+Softmax) and value MLP 128->64->1 (+Tanh), 16 boards per workgroup.
-//
-// plain kernels: the same network on boards of 3x3 / 5x5 / 7x7 (an arbitrary (x, edge_index, batch) graph runs on gcn_general.hip).
-#define AQG_TRACE_TU gcn
+// Also here: the LDS poisoning kernel of the parity tests.
 #include "aqg_common.hpp"
-#include "split_mfma.hpp"
 #include "../../include/aqgnn.h"
 #include "launchers.hpp"
 #include <vector>
-#include <cmath>
-#include <algorithm>
 
 namespace aqg {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int HID = 128;          // HIDDEN_DIM pv_network_gnn.py:18
-constexpr int FPAD = 8;           // NUM_FEATURES (6) padded
-constexpr int LD = 132;           // LDS row stride in floats (528 B: 33 x 16-B slots, odd -> conflict-free)
-constexpr int APAD = 256;         // policy outputs padded
-
-// packed weight offsets (floats) -- documented in include/aqgnn.h
-struct PackedLayout {
-    static constexpr size_t W1 = 0;                       // [HID][FPAD]
-    static constexpr size_t B1 = W1 + HID * FPAD;         // [HID]
-    static constexpr size_t W2T = B1 + HID;               // [HID k][HID n]
-    static constexpr size_t B2 = W2T + HID * HID;
-    static constexpr size_t W3T = B2 + HID;
-    static constexpr size_t B3 = W3T + HID * HID;
-    static constexpr size_t HW1T = B3 + HID;              // [HID k][HID unit]
-    static constexpr size_t HB1 = HW1T + HID * HID;
-    static constexpr size_t PW2T = HB1 + HID;             // [HID/2 k][APAD]
-    static constexpr size_t PB2 = PW2T + (HID / 2) * APAD;
-    static constexpr size_t VW2 = PB2 + APAD;             // [HID/2]
-    static constexpr size_t VB2 = VW2 + HID / 2;          // [4]
-    // MFMA B-fragment order of W2^T / W3^T: [wave 4][ntile 2][s4 8][lane 64][4]  (see load_wfrag)
-    static constexpr size_t WF2 = VB2 + 4;
-    static constexpr size_t WF3 = WF2 + HID * HID;
-    // fp16 2-way split (hi, lo) of W2^T / W3^T in 16x16x32 MFMA B-fragment order, stored as raw dwords:
-    // [plane 2][tile 8 (16 columns each)][kblock 4][lane 64][4 dwords = 8 fp16]   (see load_bfrag_mm)
-    static constexpr size_t WH2 = WF3 + HID * HID;
-    static constexpr size_t WH3 = WH2 + 2 * HID * HID / 2;
-    // layer-1 weight (times CQ) as fp16 A fragments, rows = output features, the split folded into the k dimension: per lane 8
-    // halves, k-slots 0..7 and 8..15 = hi(c W1[n][0..5]),0,0   16..23 = lo(c W1[n][0..5]),0,0   24..31 = 0:  [tile 8][lane 64][4 dwords]
-    static constexpr size_t WH1 = WH3 + 2 * HID * HID / 2;
-    // heads on the split matrix pipe (gcn_heads_mm_kernel): hidden layer of both heads as A fragments
-    // [plane 2][unit tile 8][kblock 4][lane 64][4 dwords]  (lane = unit 16*ut + c, k = 32*kb + 8*q + 0..7), and
-    // policy_head.2 as B fragments [plane 2][action tile 14][kblock 2][lane 64][4 dwords] (lane = action 16*at + c,
-    // k-slot (q, e) <-> hidden unit 32*kb + 16*(e >> 2) + 4*q + (e & 3): the order the layer-1 accumulators hold them)
-    static constexpr size_t WHH1 = WH1 + 4 * 2 * 64 * 4;
-    static constexpr size_t WHP2 = WHH1 + 2 * 8 * 4 * 64 * 4;
-    // aggregation accumulator init of the default trunk: TB[layer 3][deg-1 5][HID] = CQ * b_layer[f] * sqrt(deg)
-    // (the bias of a node with `deg` neighbours incl. itself, pre-divided by its D^-1/2 factor; see the trunk comment)
-    static constexpr size_t TB = WHP2 + 2 * 14 * 2 * 64 * 4;
-    // range-guard thresholds of the tracking trunk build (GUARD_MODE 2): [0] = largest |U| of layer 2's linear map for which layer 2's
-    // aggregate provably stays below 65504, (65504 - max |TB_2|) / 2.07;  [1] = 65504 (layer 3's U is only split itself);  [2..3] spare
-    static constexpr size_t GUARD = TB + 3 * 5 * HID;
-    static constexpr size_t TOTAL = GUARD + 4;
-};
-
-// Scale of the activation image of the default trunk: the planes hold Q = CQ * relu(...) / D^-1/2.  CQ = 15/16 makes
-// CQ / deg exact in fp16 for every degree 1..5 (0.9375, 0.46875, 0.3125, 0.234375, 0.1875): the normalised adjacency
-// becomes an EXACT fp16 matrix and no activation is ever multiplied by an irrational D^-1/2 factor on the vector unit.
-constexpr double CQ = 15.0 / 16.0;
-
-size_t packed_floats() { return PackedLayout::TOTAL; }
-
-// tensors (host fp32), state_dict order: gcn0.w[H,F] gcn0.b gcn1.w[H,H] gcn1.b gcn2.w gcn2.b
-// pol0.w[H/2,H] pol0.b pol2.w[A,H/2] pol2.b val0.w[H/2,H] val0.b val2.w[1,H/2] val2.b
-int pack_weights_host(int N, const float* const* t, float* out) {
-    const int F = 6, A = N * N + 2 * (N - 1) * (N - 1);
-    if (A > APAD) return fail("policy size exceeds APAD");
-    memset(out, 0, sizeof(float) * PackedLayout::TOTAL);
-    for (int n = 0; n < HID; ++n)
-        for (int f = 0; f < F; ++f) out[PackedLayout::W1 + n * FPAD + f] = t[0][n * F + f];
-    memcpy(out + PackedLayout::B1, t[1], sizeof(float) * HID);
-    for (int n = 0; n < HID; ++n)
-        for (int k = 0; k < HID; ++k) {
-            out[PackedLayout::W2T + k * HID + n] = t[2][n * HID + k];
-            out[PackedLayout::W3T + k * HID + n] = t[4][n * HID + k];
-        }
-    memcpy(out + PackedLayout::B2, t[3], sizeof(float) * HID);
-    memcpy(out + PackedLayout::B3, t[5], sizeof(float) * HID);
-    for (int w = 0; w < 4; ++w)
-        for (int j = 0; j < 2; ++j)
-            for (int s4 = 0; s4 < 8; ++s4)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int i = 0; i < 4; ++i) {
-                        const int c = lane & 15, q = lane >> 4;
-                        const int k = (q & 1) * 64 + (q >> 1) * 32 + 4 * s4 + i, n = 32 * w + 16 * j + c;
-                        const size_t o = ((((size_t)w * 2 + j) * 8 + s4) * 64 + lane) * 4 + i;
-                        out[PackedLayout::WF2 + o] = t[2][n * HID + k];
-                        out[PackedLayout::WF3 + o] = t[4][n * HID + k];
-                    }
-    for (int L = 0; L < 2; ++L) {                                 // fp16 split planes
-        const float* W = t[L == 0 ? 2 : 4];
-        uint32_t* dst = reinterpret_cast<uint32_t*>(out + (L == 0 ? PackedLayout::WH2 : PackedLayout::WH3));
-        auto split2 = [](float x, uint16_t (&pl)[2]) {
-            const _Float16 h = (_Float16)x;                       // RNE
-            const _Float16 l = (_Float16)(x - (float)h);
-            memcpy(&pl[0], &h, 2); memcpy(&pl[1], &l, 2);
-        };
-        for (int w = 0; w < 4; ++w)
-            for (int j = 0; j < 2; ++j)
-                for (int kb = 0; kb < 4; ++kb)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int d = 0; d < 4; ++d) {
-                            const int c = lane & 15, q = lane >> 4, n = 32 * w + 16 * j + c;
-                            uint16_t a[2], b[2];                  // layers 2, 3 see the planes' scale: W / CQ
-                            split2((float)((double)W[n * HID + 32 * kb + 8 * q + 2 * d] / CQ), a);
-                            split2((float)((double)W[n * HID + 32 * kb + 8 * q + 2 * d + 1] / CQ), b);
-                            for (int pl = 0; pl < 2; ++pl) {
-                                const size_t o = (((((size_t)pl * 4 + w) * 2 + j) * 4 + kb) * 64 + lane) * 4 + d;
-                                dst[o] = (uint32_t)a[pl] | ((uint32_t)b[pl] << 16);
-                            }
-                        }
-    }
-    {
-        // layer 1 runs aggregate-first (see the trunk comment): the wave's 16 output features are the ROWS of the A operand, the
-        // k index carries the six input features three times -- k-slots 8 q + j: q = 0 and 1 hold hi(c W1[n][j]) (they meet
-        // hi(G') and lo(G') in the B operand), q = 2 holds lo(c W1[n][j]) (meets hi(G') again), q = 3 is zero
-        uint32_t* dst = reinterpret_cast<uint32_t*>(out + PackedLayout::WH1);
-        for (int w = 0; w < 4; ++w)
-            for (int j = 0; j < 2; ++j)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int d = 0; d < 4; ++d) {
-                        const int c = lane & 15, q = lane >> 4, n = 32 * w + 16 * j + c;
-                        uint16_t h[2] = {0, 0};
-                        for (int e = 0; e < 2; ++e) {
-                            const int k = 2 * d + e;
-                            if (q < 3 && k < F) {
-                                const float x = (float)(CQ * (double)t[0][n * F + k]);
-                                const _Float16 hi = (_Float16)x;
-                                const _Float16 v = (q < 2) ? hi : (_Float16)(x - (float)hi);
-                                memcpy(&h[e], &v, 2);
-                            }
-                        }
-                        dst[((w * 2 + j) * 64 + lane) * 4 + d] = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
-                    }
-    }
-    {
-        auto split2 = [](float x, uint16_t (&pl)[2]) {
-            const _Float16 h = (_Float16)x;
-            const _Float16 l = (_Float16)(x - (float)h);
-            memcpy(&pl[0], &h, 2); memcpy(&pl[1], &l, 2);
-        };
-        uint32_t* d1 = reinterpret_cast<uint32_t*>(out + PackedLayout::WHH1);
-        for (int ut = 0; ut < 8; ++ut)
-            for (int kb = 0; kb < 4; ++kb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int d = 0; d < 4; ++d) {
-                        const int c = lane & 15, q = lane >> 4, u = 16 * ut + c;
-                        uint16_t a[2], b[2];
-                        const int k = 32 * kb + 8 * q + 2 * d;
-                        const float* W = u < HID / 2 ? t[6] + (size_t)u * HID : t[10] + (size_t)(u - HID / 2) * HID;
-                        split2(W[k], a); split2(W[k + 1], b);
-                        for (int pl = 0; pl < 2; ++pl)
-                            d1[((((size_t)pl * 8 + ut) * 4 + kb) * 64 + lane) * 4 + d] = (uint32_t)a[pl] | ((uint32_t)b[pl] << 16);
-                    }
-        uint32_t* d2 = reinterpret_cast<uint32_t*>(out + PackedLayout::WHP2);
-        for (int at = 0; at < 14; ++at)
-            for (int kb = 0; kb < 2; ++kb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int d = 0; d < 4; ++d) {
-                        const int c = lane & 15, q = lane >> 4, act = 16 * at + c;
-                        uint16_t h[2][2] = {{0, 0}, {0, 0}};
-                        for (int e2 = 0; e2 < 2; ++e2) {
-                            const int e = 2 * d + e2, u = 32 * kb + 16 * (e >> 2) + 4 * q + (e & 3);
-                            if (act < A) split2(t[8][(size_t)act * (HID / 2) + u], h[e2]);
-                        }
-                        for (int pl = 0; pl < 2; ++pl)
-                            d2[((((size_t)pl * 14 + at) * 2 + kb) * 64 + lane) * 4 + d] = (uint32_t)h[0][pl] | ((uint32_t)h[1][pl] << 16);
-                    }
-    }
-    for (int L = 0; L < 3; ++L)
-        for (int deg = 1; deg <= 5; ++deg)
-            for (int f = 0; f < HID; ++f)
-                out[PackedLayout::TB + ((size_t)L * 5 + (deg - 1)) * HID + f] = (float)(CQ * (double)t[2 * L + 1][f] * sqrt((double)deg));
-    {
-        // |V[n][f]| <= sum_{k in N[n]} |U[k][f]| CQ / deg_k + |TB| <= max|U| * CQ * (1/d_n + (d_n - 1)/2) + max|TB| <= 2.0625 max|U| + max|TB|
-        // (a neighbour has closed degree >= 2): 2.07 with rounding slack
-        double tbmax = 0.0;
-        for (int deg = 1; deg <= 5; ++deg)
-            for (int f = 0; f < HID; ++f) tbmax = std::max(tbmax, std::fabs((double)out[PackedLayout::TB + ((size_t)1 * 5 + (deg - 1)) * HID + f]));
-        const double t2 = (65504.0 - tbmax) / 2.07;
-        // A weight whose fp16 hi half is not finite (|W| / CQ >= 65504 rounds to inf, or W is inf / NaN) makes every product of its
-        // column inf - inf or 0 x inf = NaN, and the float maxima of the tracking build skip NaNs (v_max3_f32 returns the non-NaN
-        // operand): such a set gets NEGATIVE thresholds, which no maximum satisfies -- every board is reported and the host serves
-        // the set with the exact kernels (include/aqgnn.h promises "inf / NaN included").  The same for a NaN / negative bound.
-        bool hi_finite = true;
-        auto hi_ok = [](double x) { const float h = (float)(_Float16)(float)x; return h == h && std::fabs(h) <= 65504.0f; };
-        for (int i = 0; i < HID * F; ++i) hi_finite = hi_finite && hi_ok(CQ * (double)t[0][i]);
-        for (int i = 0; i < HID * HID; ++i) hi_finite = hi_finite && hi_ok((double)t[2][i] / CQ) && hi_ok((double)t[4][i] / CQ);
-        const bool bound_ok = t2 > 0.0 && t2 == t2;
-        out[PackedLayout::GUARD + 0] = (hi_finite && bound_ok) ? (float)t2 : -1.0f;
-        out[PackedLayout::GUARD + 1] = hi_finite ? 65504.0f : -1.0f;
-        out[PackedLayout::GUARD + 2] = out[PackedLayout::GUARD + 3] = 0.f;
-    }
-    for (int u = 0; u < HID / 2; ++u)
-        for (int k = 0; k < HID; ++k) {
-            out[PackedLayout::HW1T + k * HID + u] = t[6][u * HID + k];
-            out[PackedLayout::HW1T + k * HID + HID / 2 + u] = t[10][u * HID + k];
-        }
-    memcpy(out + PackedLayout::HB1, t[7], sizeof(float) * (HID / 2));
-    memcpy(out + PackedLayout::HB1 + HID / 2, t[11], sizeof(float) * (HID / 2));
-    for (int a = 0; a < A; ++a)
-        for (int k = 0; k < HID / 2; ++k) out[PackedLayout::PW2T + k * APAD + a] = t[8][a * (HID / 2) + k];
-    memcpy(out + PackedLayout::PB2, t[9], sizeof(float) * A);
-    memcpy(out + PackedLayout::VW2, t[12], sizeof(float) * (HID / 2));
-    out[PackedLayout::VB2] = t[13][0];
-    return 0;
-}
-
-// deg^-1/2 for deg 1..5 (self loop + <=4 open neighbours), correctly rounded f32
-__device__ __forceinline__ float dinv_of(int deg) {
-    switch (deg) {
-        case 1: return 1.0f;
-        case 2: return 0.70710678118654752f;
-        case 3: return 0.57735026918962576f;
-        case 4: return 0.5f;
-        default: return 0.44721359549995794f;
-    }
-}
-
-__device__ __forceinline__ float dinv_of_bits(int bits) { return dinv_of(1 + __popc(bits)); }
-// the same as straight selects on deg - 1 (a switch on a per-lane value can compile to divergent branches)
-__device__ __forceinline__ float dinv_of_dm(uint32_t dm) {
-    const float a = dm == 0u ? 1.0f : 0.70710678118654752f, b = dm == 2u ? 0.57735026918962576f : 0.5f;
-    const float ab = dm < 2u ? a : b;
-    return dm < 4u ? ab : 0.44721359549995794f;
-}
-
-// Diagnostic build only (-DAQG_STAMP, never shipped): per-phase s_memtime sums of workgroup 0 / wave 0 are
-// written behind the pooled rows (pooled + B*128, as 16 x u64).  In the real kernel no stamp executes.
-#ifdef AQG_STAMP
-#define AQG_STAMP_DECL unsigned long long st_prev = __builtin_readcyclecounter(), st_sum[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; int st_n = 0;
-#define AQG_STAMP_VMWAIT(i) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); AQG_STAMP_AT(i) }
-#define AQG_STAMP_AT(i) { unsigned long long st_now = __builtin_readcyclecounter(); st_sum[i] += st_now - st_prev; st_prev = st_now; }
-#else
-#define AQG_STAMP_DECL
-#define AQG_STAMP_AT(i)
-#define AQG_STAMP_VMWAIT(i)
-#endif
-
-struct alignas(16) TrunkSmem {
-    alignas(16) float H[81 * LD];      // in-place activation image, [node][channel]
-    alignas(16) float X0[81 * FPAD];   // node features
-    alignas(16) float AX[81 * FPAD];   // A_hat * X0 (layer-1 input after the 6-wide gather)
-    alignas(16) float coef[96][8];     // per node: self, U, D, L, R gather coefficients (0 when the edge is cut), 3 pad
-    int obits[96];                     // per node: open-edge bits (U,D,L,R) -- setup step 1 -> step 2
-};
-
-// Stripe row schedule shared by layer 1 and the stripe gathers: lane -> 4 columns (cg = lane & 7) of one row
-// per iteration (rs = lane >> 3).  Iterations 0..7 take rows it + 8*rs (0..63): with the 132-float row stride
-// the 16-lane ds_read_b128 groups then hit 16 distinct 16-byte bank slots.  Iterations 8..10 take rows
-// 64 + 8*(it-8) + rs (64..80; the last one only row 80).
-__device__ __forceinline__ int stripe_row(int it, int rs) { return it < 8 ? it + 8 * rs : 64 + 8 * (it - 8) + rs; }
-constexpr int STRIPE_ITERS = 11;
-
-// B fragments of W^T for this wave from the fragment-ordered copy: Wf[j][s] = W^T[kb + s][32*wave + 16*j + c].
-// 16 fully coalesced dwordx4 loads (1 KiB per wave-instruction) off one scalar base + one lane offset.
-__device__ __forceinline__ void load_wfrag(float (&Wf)[2][32], const float* __restrict__ WF, int wave, int lane) {
-    const float* base = WF + (size_t)__builtin_amdgcn_readfirstlane(wave) * (2 * 8 * 256) + lane * 4;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int s4 = 0; s4 < 8; ++s4) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(base + (j * 8 + s4) * 256);
-            Wf[j][4 * s4 + 0] = v[0]; Wf[j][4 * s4 + 1] = v[1]; Wf[j][4 * s4 + 2] = v[2]; Wf[j][4 * s4 + 3] = v[3];
-        }
-}
-
-// ---- MFMA phase of one GCN layer: XW[0..79][stripe] = H[0..79][:] x W[:, stripe]  (PyG order: linear first).
-// Wave `wave` owns the 32-column stripe [32*wave, 32*wave+32) for ALL rows; its A operand is the whole image,
-// read as plain ds_read_b128 (no VALU in the MFMA stream).  Node 80 is done on VALU by the same lanes.
-// Half tiles (16 k-steps = 4 x ds_read_b128) are double-buffered; sched_barrier pins the read/MFMA order.
-__device__ __forceinline__ void stripe_matmul(const float* __restrict__ H, const float (&Wf)[2][32], int lane,
-                                              f32x4 (&acc)[5][2], float& r0, float& r1) {
-    const int c = lane & 15, q = lane >> 4;
-    const int kb = (q & 1) * 64 + (q >> 1) * 32;  // kbase = {0, 64, 32, 96}
-#pragma unroll
-    for (int m = 0; m < 5; ++m) {
-        acc[m][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        acc[m][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    const float* arow = H + c * LD + kb;
-    f32x4 cur[4], nxt[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) cur[j] = *reinterpret_cast<const f32x4*>(arow + 4 * j);
-#pragma unroll
-    for (int ht = 0; ht < 10; ++ht) {          // half tile ht: rows 16*(ht/2).., k-steps 16*(ht&1)..
-        const int m = ht >> 1, h = ht & 1;
-        const float* nsrc = (ht < 9) ? arow + 16 * ((ht + 1) >> 1) * LD + 16 * ((ht + 1) & 1) : H + 80 * LD + kb;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) nxt[j] = *reinterpret_cast<const f32x4*>(nsrc + 4 * j);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const float av = cur[s >> 2][s & 3];
-            acc[m][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, Wf[0][16 * h + s], acc[m][0], 0, 0, 0);
-            acc[m][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, Wf[1][16 * h + s], acc[m][1], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) cur[j] = nxt[j];
-    }
-    // node 80: each lane covers its quarter of K for its two columns, quarters combined by xor-shuffles
-    r0 = 0.f; r1 = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) nxt[j] = *reinterpret_cast<const f32x4*>(H + 80 * LD + kb + 16 + 4 * j);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            r0 = fmaf(cur[j][i], Wf[0][4 * j + i], r0);
-            r1 = fmaf(cur[j][i], Wf[1][4 * j + i], r1);
-        }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            r0 = fmaf(nxt[j][i], Wf[0][16 + 4 * j + i], r0);
-            r1 = fmaf(nxt[j][i], Wf[1][16 + 4 * j + i], r1);
-        }
-    r0 += __shfl_xor(r0, 16); r0 += __shfl_xor(r0, 32);
-    r1 += __shfl_xor(r1, 16); r1 += __shfl_xor(r1, 32);
-}
-
-// ---- stripe epilogue: the wave parks its XW stripe in its own columns of H (the image is dead after the
-// barrier), then gathers it back with the normalised neighbour coefficients (= PyG's scatter-add on this
-// fixed-degree graph), + bias, ReLU.  Only this wave touches these columns, so ordering is wave-local.
-// LAST: mean-pool instead of writing back.
-template <bool LAST>
-__device__ __forceinline__ void stripe_gather(TrunkSmem& sm, const f32x4 (&acc)[5][2], float r0, float r1,
-                                              const float* __restrict__ bias_g, int wave, int lane,
-                                              float* __restrict__ pooled_out) {
-    {
-        const int c = lane & 15, q = lane >> 4;
-        float* w = sm.H + (4 * q) * LD + 32 * wave + c;
-#pragma unroll
-        for (int m = 0; m < 5; ++m)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                w[(16 * m + i) * LD] = acc[m][0][i];
-                w[(16 * m + i) * LD + 16] = acc[m][1][i];
-            }
-        if (q == 0) {
-            sm.H[80 * LD + 32 * wave + c] = r0;
-            sm.H[80 * LD + 32 * wave + 16 + c] = r1;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    const int cg = lane & 7, rs = lane >> 3;
-    const int colb = 32 * wave + 4 * cg;
-    const f32x4 bias = *reinterpret_cast<const f32x4*>(bias_g + colb);
-    f32x4 out[STRIPE_ITERS];
-    // Row r's neighbours sit at fixed row offsets (-9, +9, -1, +1); off-board ones are clamped to r itself (their
-    // coefficient is 0 -- but the clamp is REQUIRED: 0 x NaN garbage is NaN, which the ReLU would silently turn into 0).  With the schedule of stripe_row() every clamp is known at compile time except
-    // "up" in iterations 0..7 (only the rs == 0 lanes have r < 9), which is one per-lane offset.
-    const float* p1 = sm.H + colb + rs * 8 * LD;          // iteration it < 8: row it + 8*rs
-    const float* p2 = sm.H + colb + (64 + rs) * LD;       // iteration 8, 9: rows 64+rs, 72+rs
-    const float* k1 = &sm.coef[8 * rs][0];
-    const float* k2 = &sm.coef[64 + rs][0];
-    const int offU1 = rs == 0 ? 0 : -9 * LD;
-#pragma unroll
-    for (int it = 0; it < STRIPE_ITERS; ++it) {
-        const float *ps, *pu, *pd, *pl, *pr, *pk;
-        if (it < 8) {
-            ps = p1 + it * LD; pk = k1 + it * 8;
-            pu = (it == 0) ? (rs <= 1 ? ps : ps - 9 * LD) : ps + offU1;   // rows it + 8*rs < 9: rs == 0, and row 8 (it 0, rs 1)
-            pd = ps + 9 * LD; pr = ps + LD;
-            pl = (it == 0) ? (rs == 0 ? ps : ps - LD) : ps - LD;
-        } else if (it == 8) {
-            ps = p2; pk = k2; pu = ps - 9 * LD; pd = ps + 9 * LD; pl = ps - LD; pr = ps + LD;
-        } else if (it == 9) {
-            ps = p2 + 8 * LD; pk = k2 + 64; pu = ps - 9 * LD; pd = ps; pl = ps - LD; pr = ps + LD;
-        } else {                                             // row 80 (every lane computes it; only rs == 0 is used)
-            ps = sm.H + colb + 80 * LD; pk = &sm.coef[80][0]; pu = ps - 9 * LD; pd = ps; pl = ps - LD; pr = ps;
-        }
-        const f32x4 k4 = *reinterpret_cast<const f32x4*>(pk);
-        const float kr = pk[4];
-        const f32x4 hs = *reinterpret_cast<const f32x4*>(ps);
-        const f32x4 hu = *reinterpret_cast<const f32x4*>(pu);
-        const f32x4 hd = *reinterpret_cast<const f32x4*>(pd);
-        const f32x4 hl = *reinterpret_cast<const f32x4*>(pl);
-        const f32x4 hr = *reinterpret_cast<const f32x4*>(pr);
-        f32x4 v = bias + k4[0] * hs + k4[1] * hu + k4[2] * hd + k4[3] * hl + kr * hr;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-        out[it] = v;
-        if (it & 1) __builtin_amdgcn_sched_barrier(0);   // two iterations' reads (14) in flight, not all 77
-    }
-    if (!LAST) {
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int it = 0; it < STRIPE_ITERS; ++it) {
-            const int r = stripe_row(it, rs);
-            if (r < 81) *reinterpret_cast<f32x4*>(sm.H + r * LD + colb) = out[it];
-        }
-    } else {
-        f32x4 sum = out[0];
-#pragma unroll
-        for (int it = 1; it < STRIPE_ITERS - 1; ++it) sum += out[it];
-        if (rs == 0) sum += out[STRIPE_ITERS - 1];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float x = sum[e];
-            x += __shfl_xor(x, 8); x += __shfl_xor(x, 16); x += __shfl_xor(x, 32);
-            sum[e] = x * (1.0f / 81.0f);
-        }
-        if (rs == 0) *reinterpret_cast<f32x4*>(pooled_out + colb) = sum;
-    }
-}
-
-// RESIDENT = true : one workgroup per CU (512-VGPR budget), both layers' fragments live in registers for the
-//                   whole kernel -> zero per-board weight traffic, but no cross-workgroup phase overlap.
-// RESIDENT = false: two workgroups per CU (256 VGPRs); each layer's fragments are re-fetched per board from
-//                   L2 (128 KB per board per workgroup), issued one phase ahead of use.
-template <bool RESIDENT, int WGS_PER_CU>
-__global__ __launch_bounds__(256, WGS_PER_CU) void gcn_trunk_boards_kernel(const void* __restrict__ states, int fmt,
-                                                                                   int B, const float* __restrict__ pk,
-                                                                                   float* __restrict__ pooled,
-                                                                                   const uint8_t* __restrict__ active) {
-    constexpr int N = 9, V = 81, S = 8;
-    __shared__ TrunkSmem sm;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-
-    float W2f[2][32], W3f[2][32];
-    if (RESIDENT) {
-        load_wfrag(W2f, pk + PackedLayout::WF2, wave, lane);
-        load_wfrag(W3f, pk + PackedLayout::WF3, wave, lane);
-    }
-    // Raw state prefetch: the record's dwords are loaded one board ahead and only unpacked at setup time, so
-    // the global-load latency hides under the previous board's layers (18 dwords for state72, 6 for QState).
-    const int ndw = fmt == 0 ? 18 : 6;
-    auto fetch_raw = [&](uint32_t (&raw)[18], int bb) {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(states) + (size_t)bb * ndw;
-#pragma unroll
-        for (int i = 0; i < 18; ++i) raw[i] = (i < ndw) ? src[i] : 0u;
-    };
-    auto unpack_raw = [&](const uint32_t (&raw)[18]) -> QState {
-        QState s;
-        if (fmt == 0) {
-            uint64_t h = 0, v = 0;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                h |= (uint64_t)gather_bit0_x4(raw[1 + i]) << (4 * i);
-                v |= (uint64_t)gather_bit0_x4(raw[1 + i] >> 1) << (4 * i);
-            }
-            s.hw = h; s.vw = v;
-            s.ppos = (uint8_t)(raw[0] & 0xff); s.pwl = (uint8_t)((raw[0] >> 8) & 0xff);
-            s.epos = (uint8_t)((raw[0] >> 16) & 0xff); s.ewl = (uint8_t)(raw[0] >> 24);
-            s.plies = (uint16_t)(raw[17] & 0xffff);
-        } else {
-            s.hw = (uint64_t)raw[0] | ((uint64_t)raw[1] << 32);
-            s.vw = (uint64_t)raw[2] | ((uint64_t)raw[3] << 32);
-            s.ppos = (uint8_t)(raw[4] & 0xff); s.pwl = (uint8_t)((raw[4] >> 8) & 0xff);
-            s.epos = (uint8_t)((raw[4] >> 16) & 0xff); s.ewl = (uint8_t)(raw[4] >> 24);
-            s.plies = (uint16_t)(raw[5] & 0xffff);
-        }
-        s.pad = 0;
-        return s;
-    };
-    int b = blockIdx.x;
-    while (b < B && active && !active[b]) b += gridDim.x;
-    uint32_t raw[18];
-    if (b < B && tid < V) fetch_raw(raw, b);
-
-    AQG_STAMP_DECL
-    while (b < B) {
-        AQG_STAMP_AT(7)
-        // ---- setup step 1: node features + this tile's open-edge bits
-        if (tid < V) {
-            const QState s = unpack_raw(raw);
-            const int t = tid, x = t / N, y = t % N;
-            sm.obits[t] = tile_open_bits<N>(s.hw, s.vw, t);
-            const bool slot_ok = (x < S) && (y < S);
-            const int slot = x * S + y;
-            f32x4 xa, xb;
-            xa[0] = (t == s.ppos) ? 1.f : 0.f;
-            xa[1] = (float)s.pwl;
-            xa[2] = (t == s.epos) ? 1.f : 0.f;      // enemy's own frame (pv_network_cnn.py:101)
-            xa[3] = (float)s.ewl;
-            xb[0] = (slot_ok && ((s.hw >> slot) & 1)) ? 1.f : 0.f;
-            xb[1] = (slot_ok && ((s.vw >> slot) & 1)) ? 1.f : 0.f;
-            xb[2] = 0.f; xb[3] = 0.f;
-            *reinterpret_cast<f32x4*>(sm.X0 + t * FPAD) = xa;
-            *reinterpret_cast<f32x4*>(sm.X0 + t * FPAD + 4) = xb;
-        }
-        // prefetch the next board's raw record (lands under this board's layers)
-        int bn = b + gridDim.x;
-        while (bn < B && active && !active[bn]) bn += gridDim.x;
-        if (bn < B && tid < V) fetch_raw(raw, bn);
-        if (!RESIDENT) load_wfrag(W2f, pk + PackedLayout::WF2, wave, lane);   // lands under layer 1
-        __syncthreads();
-        AQG_STAMP_AT(0)
-        // ---- setup step 2 + layer 1a: sym-norm coefficients from the neighbours' degrees, AX = A_hat * X0
-        if (tid < V) {
-            const int t = tid;
-            const int ob = sm.obits[t];
-            const int tu = t >= 9 ? t - 9 : t, td = t < 72 ? t + 9 : t, tl = t > 0 ? t - 1 : t, tr = t < 80 ? t + 1 : t;
-            const float di = dinv_of_bits(ob);
-            f32x4 k4;
-            k4[0] = di * di;
-            k4[1] = (ob & 1) ? di * dinv_of_bits(sm.obits[tu]) : 0.f;
-            k4[2] = (ob & 2) ? di * dinv_of_bits(sm.obits[td]) : 0.f;
-            k4[3] = (ob & 4) ? di * dinv_of_bits(sm.obits[tl]) : 0.f;
-            const float kr = (ob & 8) ? di * dinv_of_bits(sm.obits[tr]) : 0.f;
-            *reinterpret_cast<f32x4*>(&sm.coef[t][0]) = k4;
-            sm.coef[t][4] = kr;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const f32x4 v = k4[0] * *reinterpret_cast<const f32x4*>(sm.X0 + t * FPAD + 4 * h) +
-                                k4[1] * *reinterpret_cast<const f32x4*>(sm.X0 + tu * FPAD + 4 * h) +
-                                k4[2] * *reinterpret_cast<const f32x4*>(sm.X0 + td * FPAD + 4 * h) +
-                                k4[3] * *reinterpret_cast<const f32x4*>(sm.X0 + tl * FPAD + 4 * h) +
-                                kr * *reinterpret_cast<const f32x4*>(sm.X0 + tr * FPAD + 4 * h);
-                *reinterpret_cast<f32x4*>(sm.AX + t * FPAD + 4 * h) = v;
-            }
-        }
-        __syncthreads();
-        AQG_STAMP_AT(1)
-        // ---- layer 1b: H1[r][cols] = ReLU(b1 + AX[r] . W1[cols]) on this wave's stripe (4 columns x 1 row per lane-iteration)
-        {
-            const int cg = lane & 7, rs = lane >> 3;
-            const int colb = 32 * wave + 4 * cg;
-            float w1[4][6];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const f32x4 lo = *reinterpret_cast<const f32x4*>(pk + PackedLayout::W1 + (colb + e) * FPAD);
-                const float2 hi = *reinterpret_cast<const float2*>(pk + PackedLayout::W1 + (colb + e) * FPAD + 4);
-                w1[e][0] = lo[0]; w1[e][1] = lo[1]; w1[e][2] = lo[2]; w1[e][3] = lo[3]; w1[e][4] = hi.x; w1[e][5] = hi.y;
-            }
-            const f32x4 b1 = *reinterpret_cast<const f32x4*>(pk + PackedLayout::B1 + colb);
-#pragma unroll
-            for (int it = 0; it < STRIPE_ITERS; ++it) {
-                const int r = stripe_row(it, rs);
-                if (r < V) {
-                    const f32x4 xa = *reinterpret_cast<const f32x4*>(sm.AX + r * FPAD);
-                    const float2 xb = *reinterpret_cast<const float2*>(sm.AX + r * FPAD + 4);
-                    f32x4 v = b1;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float a = v[e];
-                        a = fmaf(xa[0], w1[e][0], a); a = fmaf(xa[1], w1[e][1], a); a = fmaf(xa[2], w1[e][2], a);
-                        a = fmaf(xa[3], w1[e][3], a); a = fmaf(xb.x, w1[e][4], a); a = fmaf(xb.y, w1[e][5], a);
-                        v[e] = fmaxf(a, 0.f);
-                    }
-                    *reinterpret_cast<f32x4*>(sm.H + r * LD + colb) = v;
-                }
-                if ((it & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        __syncthreads();
-        AQG_STAMP_AT(2)
-        // ---- layer 2
-        f32x4 acc[5][2];
-        float r0, r1;
-        stripe_matmul(sm.H, W2f, lane, acc, r0, r1);
-        if (!RESIDENT) load_wfrag(W3f, pk + PackedLayout::WF3, wave, lane);   // lands under the layer-2 epilogue
-        __syncthreads();                       // every wave has finished reading the image
-        AQG_STAMP_AT(3)
-        stripe_gather<false>(sm, acc, r0, r1, pk + PackedLayout::B2, wave, lane, nullptr);
-        __syncthreads();
-        AQG_STAMP_AT(4)
-        // ---- layer 3 + mean pool
-        stripe_matmul(sm.H, W3f, lane, acc, r0, r1);
-        __syncthreads();
-        AQG_STAMP_AT(5)
-        stripe_gather<true>(sm, acc, r0, r1, pk + PackedLayout::B3, wave, lane, pooled + (size_t)b * HID);
-        __syncthreads();                       // coef / image are rewritten by the next board's setup
-        AQG_STAMP_AT(6)
-#ifdef AQG_STAMP
-        ++st_n;
-#endif
-        b = bn;
-    }
-#ifdef AQG_STAMP
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(pooled + (size_t)B * HID);
-        for (int i = 0; i < 16; ++i) o[i] = st_sum[i];
-        o[16] = (unsigned long long)st_n;
-    }
-#endif
-}
-
-// =============================================================================================
-// all-MFMA trunk (default): linear maps AND neighbourhood aggregation on the 16-bit matrix pipe, fp32-equivalent.
-//   GCNConv:  H' = relu( D^-1/2 (A + I) D^-1/2 (H W) + b )          (pv_network_gnn.py:55-57 + PyG gcn_norm)
-// Split precision: every f32 operand x is held as two fp16 numbers, hi = RNE16(x), lo = RNE16(x - hi) (11 + 11
-// mantissa bits), and a product is rebuilt as hi*hi + hi*lo + lo*hi, accumulated in f32 by
-// v_mfma_f32_16x16x32_f16 (16x the f32-input MFMA rate).  The dropped lo*lo term is ~2^-22 |ab|: logits land within
-// 1e-7 of the exact-f32 kernel, i.e. at the distance the exact-f32 kernel itself has from the fp64 oracle.
-// Activations are O(1) after ReLU / normalised aggregation and |W| < 1: far inside fp16 range.
-// 1. Z = H W per wave column stripe: A fragments = fp16 hi/lo planes of H in LDS ([plane][node][feature], read with
-//    ds_read_b128), B fragments = host-split W in registers, 3 terms per 16x16x32 block.
-// 2. Z' = dinv (.) Z in f32, split into fp16 hi/lo IN REGISTERS.  The accumulator layout of a 16x16 tile (lane =
-//    column c, 4 consecutive rows per lane) is also a legal A-operand layout (lane = row of A, 8 consecutive k per
-//    lane) for the TRANSPOSED product  Y^T = Z'^T (A + I): the k index (= node) is simply enumerated in the order
-//    the accumulators hold it, k-slot (q, e) <-> node 32 kb + 16 (e >> 2) + 4 q + (e & 3), and the adjacency B
-//    fragments are built in that same order.  (A + I) is 0/1 -- exact in fp16 -- so the product needs two terms
-//    (hi, lo), and it is banded (|k - n| in {0, 1, 9}): 10 of the 18 (k-block, node-tile) blocks are non-zero.
-// 3. The transposed result has lane = node, 4 consecutive features per lane: exactly the 8-byte packed store of
-//    the plane image (or, for the last layer, the per-lane partial of the mean pool).  No parking of f32 tiles in
-//    LDS, no VALU gather, no separate layer-1 gather: layer 1 is  X0 W1  (one MFMA per tile: the six features and
-//    the hi/lo split of W1 share one 32-deep k block, X0 is exact in fp16) followed by the same aggregation.
-// Per wave and board: 6 + 2 x 72 MFMAs for layer 1 and the linear maps + 2 x 20 for the aggregations.
-// =============================================================================================
-// One 8-wave workgroup walks boards (persistent grid, two workgroups per CU); a wave owns one 16-column feature tile for all 81 nodes.
-// Per board: record decode + bias offsets, the layer-1 input rows G' (built at the top), layer 1, the adjacency fragments (built behind
-// layer 1), linear map / aggregation of layers 2 and 3, mean pool -- four workgroup barriers.  (Forms measured slower and removed in
-// round 4 -- a 4-wave form, a one-workgroup-per-CU pair form, per-board VALU heads, next-board prefetch under layer 3 -- and the
-// timing-only ablation switches that priced this kernel's parts are in the history: git show 8ccbea1:alphaquoridorgnn_amd/csrc/gcn_forward.hip,
-// results in profiles/r03_trunk_ablation.log / r03_trunk_ab_runs.log.)
-constexpr int NWV = 8;                                 // waves per trunk workgroup
-#define AQG_BOARD_BARRIER() __syncthreads()
-struct alignas(16) TrunkSmemM {
-    alignas(16) unsigned char P[2][PPLANE];            // fp16 hi / lo planes of the activation image [node][feature] (scale CQ / D^-1/2)
-    alignas(16) unsigned int AF[AF_BLOCKS][64][4];     // B fragments of (A + I) diag(CQ / deg) of the board (fp16, exact)
-    // layer-1 input, aggregated FIRST: G'[n][f] = sum over the closed neighbourhood k of n of X0[k][f] / sqrt(deg k), as fp16
-    // hi[0..7] | lo[8..15] per node (6 features used, slots 6, 7 stay zero)
-    alignas(16) unsigned short G16[81][16];
-    alignas(16) float Y[NWV][96];                      // per-wave scratch of the setup: X0[k][f] / sqrt(deg k) of the wave's feature
-    alignas(16) unsigned short degv[NWV][2][32];       // per wave and block slot: fp16 CQ / deg of the 32 nodes of a k block
-    alignas(16) float dinvtab[8];                      // 1 / (81 CQ sqrt(deg)), deg = 1..5: the mean pool's weights, read by (deg - 1) * 4 (set once per workgroup)
-    alignas(16) float dinv1[NWV][8];                   // 1 / sqrt(deg): the layer-1 input rows' weights, one copy per wave (written and
-                                                       // read by the same wave: no barrier between kernel start and the first board's setup)
-};
-static_assert(2 * sizeof(TrunkSmemM) <= 160 * 1024, "two 8-wave workgroups per CU");
-
-__device__ __forceinline__ float row16_sum(float x) {     // sum over the 16 lanes of a DPP row, result in every lane
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xf, 0xf, false));   // row_ror:8
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x124, 0xf, 0xf, false));   // row_ror:4
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x122, 0xf, 0xf, false));   // row_ror:2
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x121, 0xf, 0xf, false));   // row_ror:1
-    return x;
-}
-
-// The same for four values at once, as sixteen v_add_f32 with a DPP operand: the four chains are interleaved, so each add's DPP
-// source was written four instructions earlier (a DPP read needs two wait states behind the VALU write of its source; hipcc
-// pads nothing inside an asm statement).  hipcc turns the builtin form into v_mov_b32_dpp + packed adds: 24 instructions.
-__device__ __forceinline__ f32x4 row16_sum4(f32x4 v) {
-    float a = v[0], b = v[1], c = v[2], d = v[3];
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %2, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %3, %3, %3 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %2, %2, %2 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %3, %3, %3 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_ror:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 row_ror:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %2, %2, %2 row_ror:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %3, %3, %3 row_ror:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_ror:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 row_ror:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %2, %2, %2 row_ror:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %3, %3, %3 row_ror:1 row_mask:0xf bank_mask:0xf"
-        : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-    return (f32x4){a, b, c, d};
-}
-
-// Weight fragments are fetched with buffer loads: one SGPR resource for the packed buffer, one shared VGPR (lane * 16)
-// and a scalar offset per load -- no 64-bit address VGPRs (they were the first thing the allocator spilled, and a
-// spilled address is reloaded behind an s_waitcnt vmcnt(0) that serialises the whole prefetch).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t packed_rsrc(const float* pk) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pk), 0, (int)(PackedLayout::TOTAL * sizeof(float)), 0x00020000);
-}
-__device__ __forceinline__ u32x4 load_frag16(__amdgpu_buffer_rsrc_t rs, int lane16, int byte_off) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, byte_off, 0);
-}
-
-// relu on the BIT PATTERN: max(int(x), 0) -- negative floats (sign bit set) are negative integers, non-negative floats order
-// like their bit patterns -- optionally saturating at the largest finite fp16 (0x477FE000 = 65504.0f).  One v_max_i32 /
-// v_med3_i32, and unlike fmaxf() on an MFMA result no canonicalising v_max on top; unlike an asm v_max_f32 the compiler SEES
-// it, so the matrix pipe's write-back latency in front of this first reader is padded by the compiler, wherever it schedules it.
-__device__ __forceinline__ float relu_sat16(float x) {
-    const int i = __builtin_bit_cast(int, x);
-    return __builtin_bit_cast(float, min(max(i, 0), 0x477FE000));
-}
-__device__ __forceinline__ float relu_f(float x) { return __builtin_bit_cast(float, max(__builtin_bit_cast(int, x), 0)); }
-// (The opposite direction -- an MFMA result first read INSIDE an asm statement -- has the same blind spot: the first version of
-// this kernel did its relu in asm and was wrong by different amounts in each of its three forms, depending on what the scheduler
-// happened to put between the last MFMA and the asm.  Every first reader of an accumulator is compiler-visible code now.)
-
-// Runtime fp16-range guard.  The split kernels are fp32-equivalent only while every value they store as fp16 pairs stays inside
-// fp16 range: the post-ReLU activations (clamped at 65504 instead of overflowing) and the linear maps' outputs (converted as they
-// are split).  Where a static bound over all inputs proves that (AQG_GNN_RANGE_PROVEN) only the records' wall counts are checked;
-// otherwise layer 1's pre-clamp outputs are bounded by a float maximum, the linear maps' outputs U by a float maximum of |U| against
-// PackedLayout::GUARD (layer 2's aggregate is then bounded analytically; layer 3's lands in the pooled row, which the heads kernel
-// checks).  A launch that met such a value ORs 1 into the caller's `saturated` word: the host then serves the weight set with the exact
-// f32-input kernels (pv_network_gnn / engine).  The reference's fp32 has no such cliff (pv_network_gnn.py:53-64).
-// tests/test_gpu_parity.py::test_gnn_runtime_saturation_signal / test_gnn_range_guard_watches_every_feature drive it.
-// (__builtin_bit_cast applied to a vector ELEMENT expression -- bit_cast(int, v[1]) -- read element 0 for every index with hipcc 7.2:
-//  the first, per-value form of this guard watched one value in four.  Take the element into a scalar first.)
-__device__ __forceinline__ void report_saturation(bool lane_saw_it, int32_t* __restrict__ saturated) {
-    if (saturated && __builtin_amdgcn_ballot_w64(lane_saw_it) != 0) {            // wave-uniform, practically never taken
-        int l;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-        if (l == 0) atomicOr(saturated, 1);
-    }
-}
-
-// fp16 planes of four consecutive features of one node: hi (11 bits) + lo (next 11 bits) = 22 mantissa bits
-__device__ __forceinline__ void store_split4(TrunkSmemM& sm, int off, const f32x4 v) {
-    const unsigned int h01 = cvt_pk_f16(v[0], v[1]), h23 = cvt_pk_f16(v[2], v[3]);
-    *reinterpret_cast<u32x2*>(&sm.P[0][off]) = (u32x2){h01, h23};
-    *reinterpret_cast<u32x2*>(&sm.P[1][off]) = (u32x2){lo_pair(h01, v[0], v[1]), lo_pair(h23, v[2], v[3])};
-}
-
-__device__ __forceinline__ void load_bfrag_mm(u32x4 (&Bf)[2][4], __amdgpu_buffer_rsrc_t rs, size_t region, int wave, int lane) {
-    const int base = (int)(region * sizeof(float)) + wave * (4 * 64 * 16);
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) Bf[pl][kb] = load_frag16(rs, lane * 16, base + (pl * (8 * 4 * 64) + kb * 64) * 16);
-}
-
-// fp16 hi / lo aggregation fragments of one finished 16-node tile m of U (accumulator layout: lane = feature column, 4
-// consecutive nodes): dwords 2 (m & 1), 2 (m & 1) + 1 of k block m >> 1.  `piece` 0 = the two hi dwords, 1 / 2 = one lo dword each,
-// so that the three pieces can be spread over the MFMA groups of the NEXT tile.
-// largest |x| of two values that are being split: ONE v_max3_f32 with |.| modifiers, as an asm statement ordered behind the
-// compiler-visible v_cvt_pk of the same two values by `dep` (hipcc pads nothing for asm: it must not be the first reader of a
-// matrix-pipe result -- the way lo_pair() is ordered)
-__device__ __forceinline__ void absmax_after(float& m, unsigned int dep, float a, float b) {
-    asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(a), "v"(b), "v"(dep));
-}
-// the signed form for values that are about to be ReLU-ed (a negative excursion becomes a zero: nothing to report), ordered behind the
-// two compiler-visible instructions that have read a and b (their results d0, d1)
-__device__ __forceinline__ void max_after2(float& m, float d0, float d1, float a, float b) {
-    asm("v_max3_f32 %0, %1, %2, %0" : "+v"(m) : "v"(a), "v"(b), "v"(d0), "v"(d1));
-}
-__device__ __forceinline__ void split_tile_piece(const f32x4 z, int m, int piece, u32x4 (&zh)[3], u32x4 (&zl)[3], float* zmax = nullptr) {
-    const int kb = m >> 1, d = 2 * (m & 1);
-    if (piece == 0) {
-        zh[kb][d] = cvt_pk_f16(z[0], z[1]); zh[kb][d + 1] = cvt_pk_f16(z[2], z[3]);
-        if (zmax) { absmax_after(*zmax, zh[kb][d], z[0], z[1]); absmax_after(*zmax, zh[kb][d + 1], z[2], z[3]); }
-    }
-    else if (piece == 1) zl[kb][d] = lo_pair(zh[kb][d], z[0], z[1]);
-    else zl[kb][d + 1] = lo_pair(zh[kb][d + 1], z[2], z[3]);
-}
-
-// U = Q W~ for this wave's columns: six 16-row tiles (tile 5 = row 80 repeated) x four 32-deep k blocks, A fragments
-// double-buffered from the planes, three fp16 terms per block (smallest first).  The fp16 split of tile m - 1 (six vector
-// instructions per feature tile) is issued between the MFMA groups of tile m: it costs no time of its own.
-// mid() is called in front of step 0: the kernel requests the aggregation's bias rows there.
-struct NoMid { __device__ __forceinline__ void operator()() const {} };
-template <class Mid = NoMid>
-__device__ __forceinline__ void linear_split(const TrunkSmemM& sm, const u32x4 (&Bf)[2][4], int lane, u32x4 (&zh)[3], u32x4 (&zl)[3], Mid mid = Mid(),
-                                             float* zmax = nullptr) {
-    const int c = lane & 15, q = lane >> 4;
-    // the fragments of step s + 1 are requested while step s multiplies (two register pairs).  One step ahead is enough with four
-    // waves per SIMD: rings 2 / 3 steps deep measured 48.0 / 45.4 M boards/s against 48.4 at 4,096 boards (round 3).
-    u32x4 ring[2][2];
-    auto frag_off = [&](int step) -> int {                  // step = m*4 + kb
-        const int m = step >> 2, kb = step & 3;
-        const int row = (m < 5) ? 16 * m + c : 80;
-        return plane_off(row, 4 * kb + q);
-    };
-    auto request = [&](int step) {
-        const int o = frag_off(step);
-        ring[step & 1][0] = *reinterpret_cast<const u32x4*>(&sm.P[0][o]);
-        ring[step & 1][1] = *reinterpret_cast<const u32x4*>(&sm.P[1][o]);
-    };
-    request(0);
-    f32x4 acc, done;
-#pragma unroll
-    for (int step = 0; step < 24; ++step) {
-        const int m = step >> 2, kb = step & 3;
-        if (step == 0) mid();
-        if (step + 1 < 24) request(step + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        const u32x4 hi = ring[step & 1][0], lo = ring[step & 1][1];
-        f32x4 a = kb == 0 ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc;
-        a = mfma_f16(lo, Bf[0][kb], a);
-        a = mfma_f16(hi, Bf[1][kb], a);
-        a = mfma_f16(hi, Bf[0][kb], a);
-        acc = a;
-        if (m > 0 && kb < 3) split_tile_piece(done, m - 1, kb, zh, zl, zmax);
-        __builtin_amdgcn_sched_barrier(0);
-        if (kb == 3) done = acc;
-    }
-#pragma unroll
-    for (int piece = 0; piece < 3; ++piece) split_tile_piece(done, 5, piece, zh, zl, zmax);
-}
-
-// The aggregation accumulators start from the bias: out[nt] = TB[layer][deg(node) - 1][this lane's 4 features] = CQ b sqrt(deg),
-// so that relu(out) IS the next plane image -- no multiply, no add on the vector unit.  `toff` packs (deg - 1) * 512 + 16 q per
-// node tile of this lane, 16 bits each.  Requested a whole phase ahead of their use (before the linear map).
-__device__ __forceinline__ void request_bias(f32x4 (&out)[6], __amdgpu_buffer_rsrc_t rs, int layer, const int (&toff)[3], int wave) {
-#pragma unroll
-    for (int nt = 0; nt < 6; ++nt) {
-        const int vo = (nt & 1) ? (int)((unsigned)toff[nt >> 1] >> 16) : (toff[nt >> 1] & 0xFFFF);
-        out[nt] = __builtin_bit_cast(f32x4, load_frag16(rs, vo, (int)((PackedLayout::TB + (size_t)layer * 5 * HID) * sizeof(float)) + 64 * wave));
-    }
-}
-
-// Aggregation + epilogue, node tile by node tile:  V^T = U^T (A + I) diag(CQ / deg) on top of the bias rows, then
-// Q = relu(V) -> split planes (lane = node, 4 consecutive features), or the mean pool of D^-1/2 Q / CQ for the last layer.
-// The blocks of a node tile are consecutive (a dependent 16x16x32 chain issues at the full rate), so tile nt is complete while
-// tile nt + 1 is still on the matrix pipe: its relu / split / stores are vector and LDS work issued under those MFMAs.
-// (No plane byte is read here: the caller has passed the barrier behind the linear map, the stores are free to go.)
-// No range check here: the caller has bounded layer 2's aggregate by its linear map's output (or the weight set's range is proven),
-// layer 3's aggregate is never split (the heads check the pooled row).
-template <bool LAST>
-__device__ __forceinline__ void aggregate_store(TrunkSmemM& sm, const unsigned int (&AF)[AF_BLOCKS][64][4], u32x4 (&zh)[3], u32x4 (&zl)[3], f32x4 (&out)[6], int wave, int lane,
-                                                const int (&toff)[3], __amdgpu_buffer_rsrc_t pooled_rs, int pooled_soff) {
-    constexpr int AHEAD = 3;                                   // adjacency fragments in flight (4 registers each)
-    const int c = lane & 15, q = lane >> 4;
-    const int col0 = 16 * wave + 4 * q;
-    u32x4 af[AF_BLOCKS];
-#pragma unroll
-    for (int i = 0; i < AHEAD; ++i) af[i] = *reinterpret_cast<const u32x4*>(&AF[i][lane][0]);
-    split_fence(zl[0], zl[1], zl[2]);
-    f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f};
-    auto epilogue = [&](int nt) {
-        const int node = 16 * nt + c;
-        const bool live = (nt < 5) || (c == 0);                              // node < 81
-        float dn = 0.f;
-        // deg - 1 sits above the row offset's 9 bits (and the 16 q below them leave bits 7, 8 clear): bits 7..11 = (deg - 1) * 4, the byte
-        // offset into the 1 / sqrt(deg) table -- one v_bfe + one ds_read where the select chain took nine instructions per node tile
-        if (LAST) dn = *reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(sm.dinvtab) + (((unsigned)toff[nt >> 1] >> (7 + 16 * (nt & 1))) & 0x1Cu));
-        f32x4 v = out[nt];
-        if (LAST) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = relu_f(v[e]);
-            if (live) sum += v * dn;
-        } else {
-            // relu, saturating at the largest finite fp16: an overflowing activation stays a (wrong) finite number instead of
-            // becoming inf - inf = NaN that the next relu would silently turn into 0 (it has been REPORTED by the caller's bound on
-            // the linear map's output: the host then serves the weight set with the exact-f32 kernels)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = relu_sat16(v[e]);
-            if (live) store_split4(sm, plane_off(node, col0 >> 3) + ((2 * col0) & 15), v);
-        }
-    };
-    // blocks are numbered in node-tile order already: kb = {0,0,1,0,1,1,2,1,2,2}, nt = {0,1,1,2,2,3,3,4,4,5}
-#pragma unroll
-    for (int blk = 0; blk < AF_BLOCKS; ++blk) {
-        const int kb = af_kb(blk), nt = af_nt(blk);
-        if (blk + AHEAD < AF_BLOCKS) af[blk + AHEAD] = *reinterpret_cast<const u32x4*>(&AF[blk + AHEAD][lane][0]);
-        out[nt] = mfma_f16(zl[kb], af[blk], out[nt]);
-        out[nt] = mfma_f16(zh[kb], af[blk], out[nt]);
-        // tile nt - 1 was finished by the previous block(s): its epilogue goes out under this tile's MFMAs
-        if (nt > 0 && (blk + 1 == AF_BLOCKS || af_nt(blk + 1) != nt)) epilogue(nt - 1);
-    }
-    epilogue(5);
-    if (LAST) {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const int col0 = 16 * wave + 4 * (ln >> 4);
-        const f32x4 t = row16_sum4(sum);                                  // (the table's entries carry the 1 / (81 CQ) of the mean)
-        // (buffer store off an SGPR descriptor + scalar row offset: no 64-bit address registers alive across the board loop)
-        if (c == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, t), pooled_rs, col0 * 4, pooled_soff, 0);
-    }
-}
-
-// Bit `lane` of a wave-uniform 64-bit mask, as 0 / 1 or as 0 / a: ONE v_cndmask with the scalar pair as its lane condition
-// (what `(m >> lane) & 1` means, minus the 64-bit vector shift).  The masks are SALU results: no VALU-SGPR hazard to pad.
-// (readfirstlane: the register allocator must see a scalar pair even where it chose vector registers for a uniform value; it
-// folds away when the value already is one.)
-__device__ __forceinline__ uint64_t uniform64(uint64_t m) {
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m) |
-           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32)) << 32);
-}
-__device__ __forceinline__ uint32_t lane_bit(uint64_t m) {
-    uint32_t r;
-    asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(r) : "s"(uniform64(m)));
-    return r;
-}
-template <int IMM> __device__ __forceinline__ uint32_t lane_val(uint64_t m) {     // bit `lane` of m ? IMM : 0  (IMM an inline constant)
-    uint32_t r;
-    asm("v_cndmask_b32_e64 %0, 0, %2, %1" : "=v"(r) : "s"(uniform64(m)), "n"(IMM));
-    return r;
-}
-__device__ __forceinline__ float lane_sel(uint64_t m, float a) {
-    float r;
-    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(a), "s"(uniform64(m)));
-    return r;
-}
-
-// Layer 1, aggregate-first:  Q1^T = relu( (c W1) G'^T + c sqrt(deg) b )  -- ONE MFMA per node tile and feature tile.  A = the wave's
-// W1 fragment (rows = its 16 output features; k = the six input features three times: hi.hi, hi.lo, lo.hi), B = the node tile's
-// rows of G' (lane = node; k-slots of q = 0 / 2 read the hi half, q = 1 the lo half, q = 3 meets zero weight slots), accumulated on
-// the bias rows.  The result already has the store layout (lane = node, 4 consecutive features): relu, fp16 split, plane stores.
-// 6 MFMAs per wave and feature tile where the linear-first form needed 6 + 20 (X0 W1, then the 128-wide banded aggregation).
-template <int TRACK>
-__device__ __forceinline__ void layer1_store(TrunkSmemM& sm, const unsigned short (&G)[81][16], const u32x4 &w1f, f32x4 (&out)[6],
-                                             int wave, int lane, int32_t* __restrict__ saturated) {
-    const int c = lane & 15, q = lane >> 4;
-    float fmx = 0.f;
-    const int col0 = 16 * wave + 4 * q;
-    u32x4 gf[6];
-#pragma unroll
-    for (int nt = 0; nt < 6; ++nt) gf[nt] = *reinterpret_cast<const u32x4*>(&G[nt < 5 ? 16 * nt + c : 80][8 * (q & 1)]);
-#pragma unroll
-    for (int nt = 0; nt < 6; ++nt) out[nt] = mfma_f16(w1f, gf[nt], out[nt]);
-#pragma unroll
-    for (int nt = 0; nt < 6; ++nt) {
-        const int node = 16 * nt + c;
-        const bool live = (nt < 5) || (c == 0);                              // node < 81
-        f32x4 v = out[nt];
-        // mode 2: the pre-clamp values are finite here (finite weights times bounded layer-1 rows: no inf, no NaN) and only a
-        // POSITIVE excursion is clamped, so the largest value is all there is to watch -- a plain float maximum, two values per
-        // instruction (the first reader of these matrix-pipe results is the compiler-visible v_med3 below: the maxima sit behind it)
-        f32x4 w = v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = relu_sat16(v[e]);
-        if (TRACK == 2 && live) { max_after2(fmx, v[0], v[1], w[0], w[1]); max_after2(fmx, v[2], v[3], w[2], w[3]); }
-        if (live) store_split4(sm, plane_off(node, col0 >> 3) + ((2 * col0) & 15), v);
-    }
-    if (TRACK == 2) report_saturation(!(fmx <= 65504.0f), saturated);
-}
-
-__device__ __forceinline__ uint32_t bit_of64(uint64_t m, int s) {             // bit s of a wave-uniform 64-bit mask
-    const uint32_t w = (s & 32) ? (uint32_t)(m >> 32) : (uint32_t)m;
-    return (w >> (s & 31)) & 1u;
-}
-
-// The lane index, re-derived from the execution mask (two v_mbcnt) wherever it is needed instead of being kept in a register across
-// the board loop (at the 128-register cap the allocator spilled it and reloaded it behind an s_waitcnt vmcnt(0)).
-__device__ __forceinline__ int fresh_lane() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-
-// ---- per-board inputs.  decode: the record becomes wave-uniform scalars (the wall masks by ballot over the 64 wall bytes).
-__device__ __forceinline__ void trunk_decode(int fmt, uint32_t r0, uint32_t r1, uint64_t& hw, uint64_t& vw, uint32_t& hd) {
-    if (fmt == 0) {
-        hw = __ballot((r0 & 1u) != 0);                               // wall byte: bit0 H, bit1 V
-        vw = __ballot((r0 & 2u) != 0);
-        hd = __builtin_amdgcn_readfirstlane(r1);
-    } else {
-        // (readlane returns a SIGNED int: without the uint32_t cast a wall in slot 31 sign-extends into slots 32..63 --
-        //  a round-1 bug that only the in-engine evaluation path could hit; tests/test_gpu_parity.py pins it now)
-        hw = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(r0, 0) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(r0, 1) << 32);
-        vw = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(r0, 2) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(r0, 3) << 32);
-        hd = (uint32_t)__builtin_amdgcn_readlane(r0, 4);
-    }
-}
-// deg - 1 = U + D + L + R of every node as three bit planes (bit-sliced adder on the scalar unit; c1 excludes c3, so
-// c1 + c2 + c3 <= 2 and b2 = c1 & c2), lo = nodes 0..63, hi = nodes 64..80
-struct Planes { uint64_t b0l, b1l, b2l, b0h, b1h, b2h; };
-__device__ __forceinline__ Planes degree_planes(const Open& op) {
-    Planes p;
-    {
-        const uint64_t x = op.U.lo ^ op.D.lo, c1 = op.U.lo & op.D.lo, y = op.L.lo ^ op.R.lo, c2 = op.L.lo & op.R.lo, c3 = x & y;
-        p.b0l = x ^ y; p.b1l = c1 ^ c2 ^ c3; p.b2l = c1 & c2;
-    }
-    {
-        const uint64_t x = op.U.hi ^ op.D.hi, c1 = op.U.hi & op.D.hi, y = op.L.hi ^ op.R.hi, c2 = op.L.hi & op.R.hi, c3 = x & y;
-        p.b0h = x ^ y; p.b1h = c1 ^ c2 ^ c3; p.b2h = c1 & c2;
-    }
-    return p;
-}
-// build_inputs: everything a board's layers read from LDS besides the planes --
-//  (1) layer-1 input, aggregated first (GCNConv is linear before its ReLU: A_hat (X W) = (A_hat X) W, and X has 6 columns where
-//      X W has 128):  G'[n][f] = sum_{k in N[n]} X0[k][f] / sqrt(deg k)  (the 1 / sqrt(deg n) half of the symmetric norm cancels
-//      against the sqrt(deg) scale of the plane image).  Wave f < 6 owns feature f for all 81 nodes (lane = node `lane`, lanes
-//      < 17 also node 64 + lane): the feature is a wave-uniform bitboard times a scalar (pv_network_cnn.py:88-114: pawn tile,
-//      walls in hand, enemy pawn tile in the enemy's frame, its walls, horizontal / vertical wall at the tile's slot), so x = one
-//      v_cndmask; x / sqrt(deg) goes through 384 bytes of the wave's own LDS scratch to reach the four neighbours (no other
-//      wave is involved: no barrier), the sum is split into fp16 hi / lo and stored as the B operand rows of layer 1;
-//  (2) the banded adjacency fragments of layers 2 and 3.
-// `what` & 1: the G' rows (top of a board), & 2: the adjacency fragments (behind layer 1).
-__device__ __forceinline__ void trunk_build_inputs(unsigned short (&G16)[81][16], unsigned int (&AF)[AF_BLOCKS][64][4], float* __restrict__ Yw,
-                                               unsigned short (&degv)[2][32], const float (&dtab)[8], int wave, uint64_t hw, uint64_t vw, uint32_t hd, int what) {
-    constexpr int N = 9, V = 81, NSLOT = 2;
-    const Open op = make_open<N>(hw, vw);
-    const Planes pl = degree_planes(op);
-    if (what & 1) {
-        const int ppos = hd & 0xff, pwl = (hd >> 8) & 0xff, epos = (hd >> 16) & 0xff, ewl = hd >> 24;
-        const BB shb = spread_slots<N>(hw), svb = spread_slots<N>(vw);
-        const int f = __builtin_amdgcn_readfirstlane(wave);        // wave-uniform, and known to be: the masks below stay scalar
-        if (f < 6) {
-            BB m = mask_all<N>();
-            float sc = 1.f;
-            if (f == 0) m = bb_bit(ppos);
-            else if (f == 1) sc = (float)pwl;
-            else if (f == 2) m = bb_bit(epos);
-            else if (f == 3) sc = (float)ewl;
-            else if (f == 4) m = shb;
-            else m = svb;
-            const int ln = fresh_lane(), l1 = min(ln, 16);
-            // 1 / sqrt(deg) of this lane's two nodes from the table: byte offset (deg - 1) * 4 assembled from the three degree bit planes
-            const float dnv0 = *reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(dtab) + (lane_val<4>(pl.b0l) | lane_val<8>(pl.b1l) | lane_val<16>(pl.b2l)));
-            const float dnv1 = *reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(dtab) + (lane_val<4>(pl.b0h) | lane_val<8>(pl.b1h) | lane_val<16>(pl.b2h)));
-            const float y0 = lane_sel(m.lo, sc) * dnv0, y1 = lane_sel(m.hi, sc) * dnv1;
-                            Yw[ln] = y0;
-            if (ln < 17) Yw[64 + ln] = y1;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // (an edge that is open leads to a node of the board: clamped addresses are only ever read by lanes that discard them)
-            const float nu0 = Yw[max(ln - 9, 0)], nd0 = Yw[ln + 9], nl0 = Yw[max(ln - 1, 0)], nr0 = Yw[ln + 1];
-            const float nu1 = Yw[55 + l1], nd1 = Yw[73 + l1], nl1 = Yw[63 + l1], nr1 = Yw[65 + l1];
-            const float g0 = (((y0 + lane_sel(op.U.lo, nu0)) + lane_sel(op.D.lo, nd0)) + lane_sel(op.L.lo, nl0)) + lane_sel(op.R.lo, nr0);
-            const float g1 = (((y1 + lane_sel(op.U.hi, nu1)) + lane_sel(op.D.hi, nd1)) + lane_sel(op.L.hi, nl1)) + lane_sel(op.R.hi, nr1);
-            const _Float16 h0 = (_Float16)g0, h1 = (_Float16)g1;
-            const _Float16 e0 = (_Float16)(g0 - (float)h0), e1 = (_Float16)(g1 - (float)h1);
-            G16[ln][f] = __builtin_bit_cast(unsigned short, h0);
-            G16[ln][8 + f] = __builtin_bit_cast(unsigned short, e0);
-            if (ln < 17) {
-                G16[64 + ln][f] = __builtin_bit_cast(unsigned short, h1);
-                G16[64 + ln][8 + f] = __builtin_bit_cast(unsigned short, e1);
-            }
-        }
-    }
-    if (what & 2) {
-        const int lane = fresh_lane();
-        // the four open-edge boards as 3 x 32-bit words each (word w = nodes 32 w .. 32 w + 31), selected arithmetically
-        // (scalars, not an array: an indexed local array would live in scratch memory)
-        const uint32_t u0 = (uint32_t)op.U.lo, u1 = (uint32_t)(op.U.lo >> 32), u2 = (uint32_t)op.U.hi;
-        const uint32_t d0w = (uint32_t)op.D.lo, d1w = (uint32_t)(op.D.lo >> 32), d2w = (uint32_t)op.D.hi;
-        const uint32_t l0 = (uint32_t)op.L.lo, l1 = (uint32_t)(op.L.lo >> 32), l2 = (uint32_t)op.L.hi;
-        const uint32_t r0w = (uint32_t)op.R.lo, r1w = (uint32_t)(op.R.lo >> 32), r2w = (uint32_t)op.R.hi;
-        auto sel3 = [](uint32_t a0, uint32_t a1, uint32_t a2, int w) -> uint32_t { const uint32_t a = w == 0 ? a0 : a1; return w == 2 ? a2 : a; };
-        auto open_word = [&](int dir, int w) -> uint32_t {
-            return dir == 0 ? sel3(u0, u1, u2, w) : dir == 1 ? sel3(d0w, d1w, d2w, w) : dir == 2 ? sel3(l0, l1, l2, w) : sel3(r0w, r1w, r2w, w);
-        };
-        // ten adjacency blocks over the eight waves:   w0 {8}  w1 {9}  w2 {0,6}  w3 {1,7}  w4..7 {2..5}
-        auto slot_block = [&](int it) -> int {                           // wave-uniform
-            return it == 0 ? (wave >= 2 ? wave - 2 : wave + 8) : ((wave == 2 || wave == 3) ? wave + 4 : AF_BLOCKS);
-        };
-        // step 1: the fp16 values CQ / deg(k) of the 32 source nodes of each block's k range, through this wave's own LDS
-        //         scratch (lane l < 32 = node 32 kb + l; the word of the open-edge boards is wave-uniform)
-#pragma unroll
-        for (int it = 0; it < NSLOT; ++it) {
-            const int blk = slot_block(it);
-            if (blk < AF_BLOCKS && lane < 32) {
-                const int kb = (AF_KB_PACK >> (2 * blk)) & 3;
-                const int l = lane;
-                const uint32_t deg = 1u + ((open_word(0, kb) >> l) & 1u) + ((open_word(1, kb) >> l) & 1u) +
-                                     ((open_word(2, kb) >> l) & 1u) + ((open_word(3, kb) >> l) & 1u);
-                // fp16 of CQ / deg = 0.9375, 0.46875, 0.3125, 0.234375, 0.1875 (all exact)
-                const uint32_t val = deg == 1u ? 0x3B80u : deg == 2u ? 0x3780u : deg == 3u ? 0x3500u : deg == 4u ? 0x3380u : 0x3200u;
-                degv[it][l] = (unsigned short)((32 * kb + l < V) ? val : 0u);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // step 2: the fragments.  k-slot e of lane (c, q) is node 32 kb + 16 (e >> 2) + 4 q + (e & 3); entry = CQ / deg(k) where
-        //         node n = 16 nt + c has k in its closed neighbourhood, else 0
-#pragma unroll
-        for (int it = 0; it < NSLOT; ++it) {
-            const int blk = slot_block(it);
-            if (blk < AF_BLOCKS) {
-                const int kb = (AF_KB_PACK >> (2 * blk)) & 3, nt = (AF_NT_PACK >> (3 * blk)) & 7;
-                const int ln = lane;
-                const int n = 16 * nt + (ln & 15), q = ln >> 4;
-                u32x4 fr = (u32x4){0u, 0u, 0u, 0u};
-                if (n < V) {
-                    const int w = nt >> 1, sft = n & 31;                 // n >> 5 == nt >> 1: the word is wave-uniform
-                    // window of row n of (A + I) around the diagonal: bit (k - n + 9), k = n-9 (U), n-1 (L), n, n+1 (R), n+9 (D)
-                    // (kept four bits up: the four slots of a half then are bits s .. s + 3 of it for s = window position + 4, and a
-                    //  position left of the window (s < 0) or right of it (s > 31) reads zeros once s is clamped to 0..31 -- the low four
-                    //  bits and everything above bit 22 are clear)
-                    const uint32_t win4 = (1u << 13) | (((open_word(0, w) >> sft) & 1u) << 4) | (((open_word(2, w) >> sft) & 1u) << 12) |
-                                          (((open_word(3, w) >> sft) & 1u) << 14) | (((open_word(1, w) >> sft) & 1u) << 22);
-                    const int d0 = 32 * kb + 4 * q - n + 9 + 4;          // window bit of k-slot e = 0 (+ 4); e = 4 sits 16 higher
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const u32x2 dv = *reinterpret_cast<const u32x2*>(&degv[it][16 * h + 4 * q]);   // nodes 32 kb + 16 h + 4 q + 0..3
-                        const uint32_t nib = (win4 >> (uint32_t)min(max(d0 + 16 * h, 0), 31)) & 0xFu;
-                        const uint32_t t2 = nib | (nib << 15);           // b0 -> bit 0, b1 -> bit 16, b2 -> bit 2, b3 -> bit 18
-                        // a packed 16-bit multiply by the 0 / 1 of each half keeps or clears the half (v_pk_mul_lo_u16)
-                        // (scalars first: __builtin_bit_cast of a vector ELEMENT reads element 0 whatever the index -- hipcc 7.2, see the range-guard comment)
-                        typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-                        const uint32_t dv0 = dv[0], dv1 = dv[1], s0 = t2 & 0x00010001u, s1 = (t2 >> 2) & 0x00010001u;
-                        fr[2 * h] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, s0) * __builtin_bit_cast(u16x2, dv0));
-                        fr[2 * h + 1] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, s1) * __builtin_bit_cast(u16x2, dv1));
-                    }
-                }
-                *reinterpret_cast<u32x4*>(&AF[blk][ln][0]) = fr;
-            }
-        }
-    }
-}
-
-
-// Byte offset of a lane's rows in a bias table, (deg - 1) * 512 + 16 q, for its node 16 nt + c of every node tile (first row for
-// the padding nodes 81..95: their plane bits are zero), two node tiles per register; deg - 1 stays readable above bit 9 (the mean
-// pool's 1 / sqrt(deg)).  Straight from the record's degree bit planes: nothing here waits for a barrier.
-__device__ __forceinline__ void trunk_bias_offsets(uint64_t hw, uint64_t vw, int c, int q, int (&toff)[3]) {
-    const Planes pl = degree_planes(make_open<9>(hw, vw));
-    const uint32_t qq = (uint32_t)(16 * q) * 0x00010001u;
-    // two node tiles per 32-bit plane word (nodes 32 p + c and 32 p + 16 + c are bits c and 16 + c): one shift + one mask per plane
-    // serves both tiles of a register
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-        const uint32_t w0 = p < 2 ? (uint32_t)(pl.b0l >> (32 * p)) : (uint32_t)pl.b0h;
-        const uint32_t w1 = p < 2 ? (uint32_t)(pl.b1l >> (32 * p)) : (uint32_t)pl.b1h;
-        const uint32_t w2 = p < 2 ? (uint32_t)(pl.b2l >> (32 * p)) : (uint32_t)pl.b2h;
-        const uint32_t x0 = (w0 >> c) & 0x00010001u, x1 = (w1 >> c) & 0x00010001u, x2 = (w2 >> c) & 0x00010001u;
-        const uint32_t dm2 = x0 | (x1 << 1) | (x2 << 2);                 // deg - 1 of the even tile in bits 0..2, of the odd tile in bits 16..18
-        toff[p] = (int)((dm2 << 9) + qq);                                // (deg - 1) * HID * 4 + 16 q, twice
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// heads on the split matrix pipe: EIGHT waves per 16 boards.  (Round 4 also ran this body inside the trunk launch -- by the workgroup
-// that pools the last board of a 16-board group, agent-scope stores + one atomic per workgroup, nobody waiting for anybody: correct,
-// and slower, 25.7 against 23.4 us per 480-board evaluation; profiles/r04_heads_by_last_finisher_*.log, commit d13f38b in the history.)
-//   layer 1 (transposed):  hid^T[u][board] = HW1[u][k] pooled^T[k][board]   A = host-split weight fragments (wave w: unit tile w),
-//                          B = this lane's 8 consecutive pooled features of board (lane & 15), split in registers
-//   layer 2:               logits[board][a] = hid[board][u] PW2^T[u][a]     A = the layer-1 accumulators of waves 0..3 (lane = board,
-//                          4 consecutive units per tile -> k-slot order of WHP2) through 4 KB of LDS, B = host-split weight
-//                          fragments (wave w: action tiles w and w + 8)
-//   softmax in the accumulator layout (lane = action column, 4 boards per lane): per wave over its action tiles, DPP row
-//   reductions over the 16 lanes of a row, the eight waves' (max, sum) combined through LDS in a fixed order;
-//   value head: waves 4..7 hold its hidden units, wave 4 sums them in a fixed order.
-// Same split precision as the trunk (3 fp16 terms per product, f32 accumulate).  Every wave requests ALL its weight fragments
-// (16 x 16 B per lane) and its pooled features before anything else: 96 registers of operands, inside the trunk's 128-register cap.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void split8(const f32x4 x0, const f32x4 x1, u32x4& hi, u32x4& lo) {
-    hi = (u32x4){cvt_pk_f16(x0[0], x0[1]), cvt_pk_f16(x0[2], x0[3]), cvt_pk_f16(x1[0], x1[1]), cvt_pk_f16(x1[2], x1[3])};
-    const f32x4 r0 = x0 - f16_pairs_to_f32(hi[0], hi[1]), r1 = x1 - f16_pairs_to_f32(hi[2], hi[3]);
-    lo = (u32x4){cvt_pk_f16(r0[0], r0[1]), cvt_pk_f16(r0[2], r0[3]), cvt_pk_f16(r1[0], r1[1]), cvt_pk_f16(r1[2], r1[3])};
-}
-__device__ __forceinline__ float row16_max(float x) {
-    x = fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xf, 0xf, false)));
-    x = fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x124, 0xf, 0xf, false)));
-    x = fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x122, 0xf, 0xf, false)));
-    x = fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x121, 0xf, 0xf, false)));
-    return x;
-}
-
-constexpr int HEADS_WAVES = 8;
-struct alignas(16) HeadsSmem {
-    unsigned int hfrag[2][2][64][4];     // layer-2 A fragments [kb2][plane][lane][unit tile parity x 2 dwords]: written by waves 0..3, read by all
-    float vlane[4][64];                  // value head: per-lane partial dot products of waves 4..7 (unit tiles 4..7)
-    float wmax[HEADS_WAVES][16], wsum[HEADS_WAVES][16];   // per-wave softmax partials per board
-};
-
-// All 512 threads of a workgroup call this for the 16 boards b0 .. b0 + 15 (two internal barriers).  `prs` = buffer resource of the
-// pooled rows [B][128] f32.
-__device__ __forceinline__ void heads_body(HeadsSmem& sm, __amdgpu_buffer_rsrc_t prs, int b0, int B, int A, __amdgpu_buffer_rsrc_t rs,
-                                           const float* __restrict__ pk, float* __restrict__ logits, float* __restrict__ policy,
-                                           float* __restrict__ value_pre, float* __restrict__ value, const uint8_t* __restrict__ active,
-                                           int32_t* __restrict__ saturated, int wave, int lane) {
-    const int c = lane & 15, q = lane >> 4;
-    constexpr int H1 = (int)(PackedLayout::WHH1 * sizeof(float)), P2 = (int)(PackedLayout::WHP2 * sizeof(float));
-    const int ntiles = (A + 15) >> 4;
-    const bool want_policy = logits || policy;
-    // this wave's weight fragments of layer 1: hidden-unit tile `wave`
-    u32x4 af[2][4];                                            // [plane][kb]
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) af[pl][kb] = load_frag16(rs, lane * 16, H1 + ((pl * 8 + wave) * 4 + kb) * (64 * 16));
-    // B operand of layer 1: 32 pooled features of board (b0 + c) -- requested now, split below
-    const bool okc = b0 + c < B;
-    f32x4 x0[4], x1[4];
-    {
-        const int row = (okc ? b0 + c : B - 1) * (HID * 4);
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            x0[kb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(prs, row + (32 * kb + 8 * q) * 4, 0, 0));
-            x1[kb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(prs, row + (32 * kb + 8 * q + 4) * 4, 0, 0));
-        }
-    }
-    // every small operand of the later phases is requested here too, behind the fragments and the pooled rows: behind a barrier each
-    // of them (layer-1 bias, value weights, action biases, the boards' active flags) was a memory round trip of its own in this chain
-    const f32x4 bias = *reinterpret_cast<const f32x4*>(pk + PackedLayout::HB1 + 16 * wave + 4 * q);
-    const f32x4 vw = *reinterpret_cast<const f32x4*>(pk + PackedLayout::VW2 + 16 * (wave & 3) + 4 * q);
-    float pb[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) { const int a = 16 * (wave + 8 * j) + c; pb[j] = pk[PackedLayout::PB2 + (a < A ? a : 0)]; }
-    const float vb2 = pk[PackedLayout::VB2];
-    // the boards' active flags: five unconditional byte loads (clamped indices, through a pointer that is never null), all in flight
-    // with everything else -- written as `brd < B && !(active && !active[brd])` each became a branch around a load with its own
-    // s_waitcnt vmcnt(0): five serial round trips
-    const uint8_t* __restrict__ ap = active ? active : reinterpret_cast<const uint8_t*>(pk);
-    unsigned int af4[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af4[i] = ap[active ? min(b0 + 4 * q + i, B - 1) : 0];
-    const unsigned int afc = ap[active ? min(b0 + c, B - 1) : 0];
-    u32x4 ph[4], pl_[4];
-    bool counted;
-    {
-        float xmax = 0.f;                                              // fp16-range guard (see report_saturation)
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            if (!okc) { x0[kb] = (f32x4){0.f, 0.f, 0.f, 0.f}; x1[kb] = x0[kb]; }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) xmax = fmaxf(fmaxf(fabsf(x0[kb][e]), fabsf(x1[kb][e])), xmax);
-            split8(x0[kb], x1[kb], ph[kb], pl_[kb]);
-        }
-        counted = okc && (!active || afc != 0);                        // (fp16-range guard) a masked-out board's pooled row is whatever the buffer held
-        if (wave == 0) report_saturation(counted && !(xmax <= 65504.0f), saturated);  // (!(<=) also catches a NaN row; every wave sees the same rows)
-    }
-    int live4 = 0;                                             // bit i: board b0 + 4 q + i exists and is not masked out
-#pragma unroll
-    for (int i = 0; i < 4; ++i) live4 |= (b0 + 4 * q + i < B && (!active || af4[i] != 0)) ? (1 << i) : 0;
-    // layer-2 fragments: requested only now, in the registers the raw pooled rows have left (the kernel has to stay inside 128
-    // registers -- eight such waves then fit on a CU beside one trunk workgroup; at 140 registers they did not, and the self-play loop
-    // lost 15 %: 1,468 against 1,720 games/s); they land under layer 1 and the barrier
-    u32x4 bq[2][2][2];                                         // [action tile wave + 8 j][plane][kb2]
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                const int at = wave + 8 * j;
-                bq[j][pl][kb] = (want_policy && at < ntiles) ? load_frag16(rs, lane * 16, P2 + ((pl * 14 + at) * 2 + kb) * (64 * 16)) : (u32x4){0u, 0u, 0u, 0u};
-            }
-    // ---- phase 1: hidden units 16 wave + 4 q + e of board b0 + c
-    {
-        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            acc = mfma_f16(af[1][kb], ph[kb], acc);
-            acc = mfma_f16(af[0][kb], pl_[kb], acc);
-            acc = mfma_f16(af[0][kb], ph[kb], acc);
-        }
-        f32x4 h = acc + bias;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) h[e] = fmaxf(h[e], 0.f);
-        if (wave < 4) {
-            // (stored as fp16 pairs for the policy head's second layer: same range guard)
-            report_saturation(counted && !(fmaxf(fmaxf(h[0], h[1]), fmaxf(h[2], h[3])) <= 65504.0f), saturated);
-            const unsigned int h01 = cvt_pk_f16(h[0], h[1]), h23 = cvt_pk_f16(h[2], h[3]);
-            const f32x4 r = h - f16_pairs_to_f32(h01, h23);
-            const int kb2 = wave >> 1, t = wave & 1;
-            *reinterpret_cast<u32x2*>(&sm.hfrag[kb2][0][lane][2 * t]) = (u32x2){h01, h23};
-            *reinterpret_cast<u32x2*>(&sm.hfrag[kb2][1][lane][2 * t]) = (u32x2){cvt_pk_f16(r[0], r[1]), cvt_pk_f16(r[2], r[3])};
-        } else {
-            sm.vlane[wave - 4][lane] = h[0] * vw[0] + h[1] * vw[1] + h[2] * vw[2] + h[3] * vw[3];
-        }
-    }
-    __syncthreads();
-    if (wave == 4) {                                           // value head: fixed-order sum of the four unit tiles, then of the four lane quarters
-        float v = (sm.vlane[0][lane] + sm.vlane[1][lane]) + (sm.vlane[2][lane] + sm.vlane[3][lane]);
-        v += __shfl_xor(v, 16);
-        v += __shfl_xor(v, 32);
-        if (counted && lane < 16) {                            // (lane < 16: c == lane, board b0 + lane)
-            v += vb2;
-            if (value_pre) value_pre[b0 + lane] = v;
-            if (value) value[b0 + lane] = tanhf(v);
-        }
-    }
-    if (!want_policy) return;
-    // ---- phase 2: this wave's action tiles, lane = action 16 at + c, rows = boards 4 q .. 4 q + 3
-    u32x4 hh[2], hl[2];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-        hh[kb] = *reinterpret_cast<const u32x4*>(&sm.hfrag[kb][0][lane][0]);
-        hl[kb] = *reinterpret_cast<const u32x4*>(&sm.hfrag[kb][1][lane][0]);
-    }
-    f32x4 lg[2];
-    f32x4 m = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int at = wave + 8 * j, a = 16 * at + c;
-        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            acc = mfma_f16(hl[kb], bq[j][0][kb], acc);
-            acc = mfma_f16(hh[kb], bq[j][1][kb], acc);
-            acc = mfma_f16(hh[kb], bq[j][0][kb], acc);
-        }
-        const bool ok = a < A;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            lg[j][i] = ok ? acc[i] + pb[j] : -INFINITY;
-            m[i] = fmaxf(m[i], lg[j][i]);
-        }
-    }
-    f32x4 ssum = (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x4 ex[2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) m[i] = row16_max(m[i]);          // this wave's maximum per board (finite: every wave owns tile w < 14)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            ex[j][i] = __expf(lg[j][i] - m[i]);                // exp(-inf) = 0 for padded columns; ~2 ulp, far inside the tolerance
-            ssum[i] += ex[j][i];
-        }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ssum[i] = row16_sum(ssum[i]);
-    if (c == 0) {
-        *reinterpret_cast<f32x4*>(&sm.wmax[wave][4 * q]) = m;
-        *reinterpret_cast<f32x4*>(&sm.wsum[wave][4 * q]) = ssum;
-    }
-    __syncthreads();
-    // common maximum M, total S = sum_w s_w exp(m_w - M) in wave order; this wave's exponentials are rescaled by exp(m_w - M) / S
-    f32x4 scale;
-    {
-        f32x4 M = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-        for (int w = 0; w < HEADS_WAVES; ++w) {
-            const f32x4 mw = *reinterpret_cast<const f32x4*>(&sm.wmax[w][4 * q]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) M[i] = fmaxf(M[i], mw[i]);
-        }
-        f32x4 S = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int w = 0; w < HEADS_WAVES; ++w) {
-            const f32x4 mw = *reinterpret_cast<const f32x4*>(&sm.wmax[w][4 * q]);
-            const f32x4 sw = *reinterpret_cast<const f32x4*>(&sm.wsum[w][4 * q]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) S[i] += sw[i] * __expf(mw[i] - M[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) scale[i] = __expf(m[i] - M[i]) / S[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int brd = b0 + 4 * q + i;
-        if (!((live4 >> i) & 1)) continue;
-        const size_t row = (size_t)brd * A + 16 * wave + c;     // one 64-bit address per board row, this wave's tiles at +512 B steps
-        if (policy) {
-            float* __restrict__ p = policy + row;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) if (16 * (wave + 8 * j) + c < A) p[128 * j] = ex[j][i] * scale[i];
-        }
-        if (logits) {
-            float* __restrict__ l = logits + row;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) if (16 * (wave + 8 * j) + c < A) l[128 * j] = lg[j][i];
-        }
-    }
-}
-
-__global__ __launch_bounds__(64 * HEADS_WAVES, 4) void gcn_heads_mm_kernel(float* __restrict__ pooled, int B, int A,
-                                                                           const float* __restrict__ pk, float* __restrict__ logits,
-                                                                           float* __restrict__ policy, float* __restrict__ value_pre,
-                                                                           float* __restrict__ value, const uint8_t* __restrict__ active, int prio,
-                                                                           int32_t* __restrict__ saturated) {
-    __shared__ HeadsSmem sm;
-    AQG_TRACE_BEGIN
-    // a short latency chain that shares its CUs with other game sets' trunk workgroups: at a higher wave priority it is out of their
-    // way sooner (option "heads_prio", 0..3)
-    if (prio == 1) __builtin_amdgcn_s_setprio(1); else if (prio == 2) __builtin_amdgcn_s_setprio(2); else if (prio == 3) __builtin_amdgcn_s_setprio(3);
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(pooled, 0, B * (HID * 4), 0x00020000);
-    heads_body(sm, prs, blockIdx.x * 16, B, A, packed_rsrc(pk), pk, logits, policy, value_pre, value, active, saturated, wave, lane);
-    AQG_TRACE_END(3, (unsigned long long)(uintptr_t)pooled)
-}
-
-// (hipcc's second launch-bound argument is waves per SIMD: workgroups per CU x waves per workgroup / 4 SIMDs)
-// TRACK (the range guard's mode): 0 = the caller has PROVEN that no value of this weight set can leave fp16 range on any record with at
-// most AQG_GNN_PROVEN_MAX_WALLS walls in hand (AQG_GNN_RANGE_PROVEN, include/aqgnn.h): nothing is tracked, each record's two wall counts
-// are checked instead, on the scalar unit.  2 (every other weight set) = the values are bounded where that is cheapest: layer 1's
-// pre-clamp outputs by a float maximum; the linear maps' outputs U (which are split themselves) by a float maximum of |U| against the
-// thresholds of PackedLayout::GUARD -- layer 2's aggregate is then below 65504 by  |V| <= 2.0625 max|U| + max|TB|,  layer 3's is not
-// split at all (the heads check the pooled row): one vector instruction per TWO values at three places.
-// LIST: the boards come as a compact list (below); the mask-walking instantiation carries none of that code
-template <int TRACK, bool LIST>
-__global__ __launch_bounds__(64 * NWV, 4) void gcn_trunk_boards_mm_kernel(const void* __restrict__ states, int fmt, int B, const float* __restrict__ pk,
-                                                                          float* __restrict__ pooled, const uint8_t* __restrict__ active,
-                                                                          int phase_delay, int32_t* __restrict__ saturated,
-                                                                          const int32_t* __restrict__ list_arg, const int32_t* __restrict__ list_count) {
-    const int32_t* __restrict__ const list = LIST ? list_arg : nullptr;
-    AQG_TRACE_BEGIN
-    __shared__ TrunkSmemM sm;
-    // The two workgroups resident on a CU run identical phase sequences; a start offset for the second-resident ones
-    // (phase_delay x 64 cycles) keeps one on the matrix pipe while the other does vector work.
-    const int prio_mode = phase_delay >> 16;     // static wave priorities (aqg_set_option("trunk_prio"); chosen by launch size on the host)
-    phase_delay &= 0xFFFF;
-    for (int i = 0; i < (int)(blockIdx.x >> 8) * phase_delay; ++i) __builtin_amdgcn_s_sleep(1);   // 2nd / 3rd resident: 1x / 2x
-    {
-        const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        const bool up = ((prio_mode & 1) && wv >= 4) || ((prio_mode & 2) && blockIdx.x >= 256) || ((prio_mode & 4) && blockIdx.x < 256);
-        if (up) __builtin_amdgcn_s_setprio(1);
-    }
-    // trunk_prio bit 3: the two workgroups of a CU take turns at priority 1, phase by phase, instead of the older one winning
-    // every arbitration (otherwise the younger one's chain is 25 % longer)
-    const int prio_sel = (prio_mode & 8) ? (int)((blockIdx.x >> 8) & 1) : -1;
-    auto phase_prio = [&](int kph) {
-        if (prio_sel >= 0) { if ((kph + prio_sel) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
-    };
-    // The thread index is NOT kept in a register across the board loop (at the 128-register cap the allocator spilled it and
-    // reloaded it behind an s_waitcnt vmcnt(0) that drained the weight prefetches): the wave index is a scalar, the lane index
-    // is re-derived from the execution mask (two v_mbcnt) wherever it is needed.
-    const int wave0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int wave = wave0;
-
-    // `list` (optional): the launch's boards as a COMPACT list of indices, *list_count long -- workgroup w takes entries w, w + grid, ...
-    // The MCTS with its evaluation cache on hands over the ~quarter of a set's leaves that miss the cache this way: walking the
-    // mask instead, a workgroup's share of a 4,096-slot set is Binomial(8, 1/4) boards and the launch lasts as long as the
-    // unluckiest workgroup (38 us against ~22 for the same boards spread evenly).
-    int j = blockIdx.x;
-    const int nlist = list ? __builtin_amdgcn_readfirstlane(*list_count) : 0;
-    int b = list ? (j < nlist ? __builtin_amdgcn_readfirstlane(list[j]) : B) : (int)blockIdx.x;
-    // A board's record lives in two VGPRs of EVERY wave (each wave fetches it itself: 24-72 bytes), one board ahead:
-    //   fmt 0 (state72): rec0 = wall byte of slot `lane`, rec1 = header dword;  fmt 1 (QState): rec0 = dword `lane` (< 5)
-    uint32_t rec0 = 0, rec1 = 0;
-    // buffer loads off one SGPR descriptor + a scalar record offset: no 64-bit address registers to keep alive across the loop
-    const __amdgpu_buffer_rsrc_t rst = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(states), 0, B * (fmt == 0 ? 72 : 24), 0x00020000);
-    auto fetch_record = [&](int bb, uint32_t& r0, uint32_t& r1) {
-        const int ln = fresh_lane();          // offsets are recomputed per fetch, not kept (spilled) across the board loop
-        if (fmt == 0) {
-            r0 = __builtin_amdgcn_raw_buffer_load_b8(rst, 4 + ln, bb * 72, 0);
-            r1 = __builtin_amdgcn_raw_buffer_load_b32(rst, 0, bb * 72, 0);
-        } else {
-            r0 = __builtin_amdgcn_raw_buffer_load_b32(rst, (ln < 5 ? ln : 4) * 4, bb * 24, 0);
-        }
-    };
-    // The first board's record is requested BEFORE its `active` flag is known: the two loads are in flight together instead of
-    // one behind the other (one memory latency off every launch -- the MCTS's launches are one board per workgroup, ~94 % active).
-    if (b < B) {
-        fetch_record(b, rec0, rec1);
-        if (!list && active && !active[b]) {          // (workgroup-uniform) inactive slot: walk on to the next active board
-            do { b += gridDim.x; } while (b < B && !active[b]);
-            if (b < B) fetch_record(b, rec0, rec1);
-        }
-    }
-    // once per workgroup: the k-slots 6, 7 of the hi and lo halves of every G' row, which no board ever writes.  No barrier here:
-    // their first reader sits behind the first board's setup barrier.
-    {
-        const int t0 = (int)threadIdx.x;
-        for (int i = t0; i < 81 * 2; i += 64 * NWV)
-            *reinterpret_cast<unsigned int*>(&sm.G16[0][0] + 16 * (i >> 1) + 6 + 8 * (i & 1)) = 0u;
-        if (t0 < 8) sm.dinvtab[t0] = dinv_of_dm((uint32_t)t0) * (float)(1.0 / (81.0 * CQ));      // (first read behind the layer-3 barriers)
-        if ((t0 & 63) < 8) sm.dinv1[t0 >> 6][t0 & 63] = dinv_of_dm((uint32_t)(t0 & 63));           // each wave its own copy: no barrier here
-    }
-    u32x4 Bf[2][4];
-    const __amdgpu_buffer_rsrc_t rs = packed_rsrc(pk);
-    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(pooled, 0, B * (HID * 4), 0x00020000);
-
-    auto build_inputs = [&](uint64_t hw, uint64_t vw, uint32_t hd, int what) {
-        trunk_build_inputs(sm.G16, sm.AF, sm.Y[wave], sm.degv[wave], sm.dinv1[wave], wave, hw, vw, hd, what);
-    };
-
-    AQG_STAMP_DECL
-    while (b < B) {
-        AQG_STAMP_AT(7)
-        wave = wave0;
-        asm volatile("" : "+s"(wave));         // opaque per board: wave-derived predicates are recomputed (2-3 scalar ops), not
-                                               // hoisted out of the loop into registers that then spill
-        const int lane = fresh_lane(), c = lane & 15, q = lane >> 4;
-        // the small layer-1 weight fragment goes out first
-        const u32x4 w1f = load_frag16(rs, lane * 16, (int)(PackedLayout::WH1 * sizeof(float)) + wave * (64 * 16));
-        __builtin_amdgcn_sched_barrier(0);
-        int toff[3];
-        uint64_t hw, vw;
-        uint32_t hd;
-        trunk_decode(fmt, rec0, rec1, hw, vw, hd);
-        trunk_bias_offsets(hw, vw, c, q, toff);
-        f32x4 out[6];
-        u32x4 zh[3], zl[3];
-        request_bias(out, rs, 0, toff, wave);                            // lands under the input build + barrier
-        AQG_STAMP_AT(6)
-        build_inputs(hw, vw, hd, 1);                                     // the layer-1 input rows G'
-        int bn;
-        if (list) { j += gridDim.x; bn = j < nlist ? __builtin_amdgcn_readfirstlane(list[j]) : B; }
-        else { bn = b + gridDim.x; while (bn < B && active && !active[bn]) bn += gridDim.x; }
-        AQG_BOARD_BARRIER();                     // this board's G' rows are complete; the previous board is done
-        AQG_STAMP_AT(0)
-        phase_prio(1);
-        // ---- layer 1: one MFMA per node tile on top of the bias rows, relu, planes
-        if (TRACK == 0 && (((hd >> 8) & 0xffu) > AQG_GNN_PROVEN_MAX_WALLS || (hd >> 24) > AQG_GNN_PROVEN_MAX_WALLS)) report_saturation(true, saturated);
-        layer1_store<TRACK>(sm, sm.G16, w1f, out, wave, lane, saturated);
-        AQG_STAMP_AT(8)
-        __builtin_amdgcn_sched_barrier(0);
-        load_bfrag_mm(Bf, rs, PackedLayout::WH2, wave, lane);             // layer-2 weights: land under the barrier
-        __builtin_amdgcn_sched_barrier(0);
-        phase_prio(2);
-        build_inputs(hw, vw, hd, 2);                                     // the adjacency fragments of layers 2 and 3
-        AQG_STAMP_AT(9)
-        AQG_BOARD_BARRIER();
-        AQG_STAMP_AT(1)
-        // ---- layer 2
-        phase_prio(3);
-        {
-            float zmax = 0.f;
-            linear_split(sm, Bf, lane, zh, zl, [&]() { request_bias(out, rs, 1, toff, wave); }, TRACK == 2 ? &zmax : nullptr);
-            if (TRACK == 2) report_saturation(!(zmax <= pk[PackedLayout::GUARD + 0]), saturated);
-        }
-        AQG_STAMP_AT(2)
-        AQG_STAMP_AT(11)
-        __builtin_amdgcn_sched_barrier(0);
-        load_bfrag_mm(Bf, rs, PackedLayout::WH3, wave, lane);             // lands under the barrier + aggregation
-        uint32_t nrec0 = 0, nrec1 = 0;
-        if (bn < B) fetch_record(bn, nrec0, nrec1);                         // the next board's record rides behind it
-        __builtin_amdgcn_sched_barrier(0);
-        AQG_STAMP_AT(12)
-        AQG_BOARD_BARRIER();                                                    // every wave is done reading the planes
-        AQG_STAMP_AT(13)
-        phase_prio(4);
-        aggregate_store<false>(sm, sm.AF, zh, zl, out, wave, lane, toff, prs, 0);
-        AQG_STAMP_AT(14)
-        AQG_BOARD_BARRIER();
-        AQG_STAMP_AT(3)
-        // ---- layer 3 + mean pool
-        phase_prio(5);
-        AQG_STAMP_AT(10)
-        {
-            float zmax = 0.f;
-            linear_split(sm, Bf, lane, zh, zl, [&]() { request_bias(out, rs, 2, toff, wave); }, TRACK == 2 ? &zmax : nullptr);
-            if (TRACK == 2) report_saturation(!(zmax <= pk[PackedLayout::GUARD + 1]), saturated);
-        }
-        AQG_STAMP_AT(4)
-        AQG_STAMP_AT(15)
-        phase_prio(6);
-        aggregate_store<true>(sm, sm.AF, zh, zl, out, wave, lane, toff, prs, b * (HID * 4));
-        rec0 = nrec0; rec1 = nrec1;
-        // (No barrier at the end of a board: what the next board writes in front of its top barrier -- the G' rows, wave-private
-        //  scratch -- was last read in layer 1 of this board, three barriers back; its planes and adjacency fragments are written
-        //  behind that barrier, which no wave passes before every wave has finished this board's layer 3.)
-        AQG_STAMP_AT(5)
-#ifdef AQG_STAMP
-        ++st_n;
-#endif
-        b = bn;
-    }
-#ifdef AQG_STAMP
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(pooled + (size_t)B * HID);
-        for (int i = 0; i < 16; ++i) o[i] = st_sum[i];
-        o[16] = (unsigned long long)st_n;
-    }
-#endif
-    AQG_TRACE_END(2, (unsigned long long)(uintptr_t)pooled)
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// heads: 16 boards per workgroup
-// ---------------------------------------------------------------------------------------------
-constexpr int HB = 8;   // boards per workgroup: B = 2048 -> 256 workgroups, one per CU
-
-// Latency-bound small GEMMs: the weights stream from L2 (118 KB, shared by every workgroup), so the loop is built
-// for memory-level parallelism -- 16 independent coalesced weight loads in flight per thread -- and the 8 boards
-// of a workgroup sit transposed in LDS ([k][board]) so one k-step reads them with two broadcast ds_read_b128.
-__global__ __launch_bounds__(256) void gcn_heads_kernel(const float* __restrict__ pooled, int B, int A,
-                                                        const float* __restrict__ pk, float* __restrict__ logits,
-                                                        float* __restrict__ policy, float* __restrict__ value_pre,
-                                                        float* __restrict__ value, const uint8_t* __restrict__ active) {
-    __shared__ alignas(16) float gT[HID][HB];          // pooled features, transposed
-    __shared__ alignas(16) float part[2][HID][HB];     // hidden-layer partial sums of the two k halves
-    __shared__ alignas(16) float hidT[HID][HB];        // hidden activations (0..63 policy, 64..127 value), transposed
-    __shared__ float lg[HB][APAD];
-    const int tid = threadIdx.x;
-    const int b0 = blockIdx.x * HB;
-    const int nb = min(HB, B - b0);
-    for (int i = tid; i < HB * HID; i += 256) {
-        const int r = i / HID, k = i % HID;
-        gT[k][r] = (r < nb) ? pooled[(size_t)(b0 + r) * HID + k] : 0.f;
-    }
-    __syncthreads();
-    {   // hidden layer of both heads: unit u, k half kh (64 k each), all 8 boards
-        const int u = tid & 127, kh = tid >> 7;
-        float acc[HB];
-#pragma unroll
-        for (int i = 0; i < HB; ++i) acc[i] = 0.f;
-        const float* w = pk + PackedLayout::HW1T + (size_t)(64 * kh) * HID + u;
-#pragma unroll
-        for (int k0 = 0; k0 < 64; k0 += 16) {
-            float wk[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) wk[j] = w[(size_t)(k0 + j) * HID];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const f32x4 ga = *reinterpret_cast<const f32x4*>(&gT[64 * kh + k0 + j][0]);
-                const f32x4 gb = *reinterpret_cast<const f32x4*>(&gT[64 * kh + k0 + j][4]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { acc[i] = fmaf(ga[i], wk[j], acc[i]); acc[4 + i] = fmaf(gb[i], wk[j], acc[4 + i]); }
-            }
-        }
-        *reinterpret_cast<f32x4*>(&part[kh][u][0]) = (f32x4){acc[0], acc[1], acc[2], acc[3]};
-        *reinterpret_cast<f32x4*>(&part[kh][u][4]) = (f32x4){acc[4], acc[5], acc[6], acc[7]};
-    }
-    __syncthreads();
-    for (int i = tid; i < HID * HB; i += 256) {
-        const int u = i / HB, r = i % HB;
-        hidT[u][r] = fmaxf(part[0][u][r] + part[1][u][r] + pk[PackedLayout::HB1 + u], 0.f);
-    }
-    __syncthreads();
-    if (tid < A) {
-        float acc[HB];
-        const float bias = pk[PackedLayout::PB2 + tid];
-#pragma unroll
-        for (int i = 0; i < HB; ++i) acc[i] = bias;
-        const float* w = pk + PackedLayout::PW2T + tid;
-#pragma unroll
-        for (int k0 = 0; k0 < HID / 2; k0 += 16) {
-            float wk[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) wk[j] = w[(size_t)(k0 + j) * APAD];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const f32x4 ha = *reinterpret_cast<const f32x4*>(&hidT[k0 + j][0]);
-                const f32x4 hb = *reinterpret_cast<const f32x4*>(&hidT[k0 + j][4]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { acc[i] = fmaf(ha[i], wk[j], acc[i]); acc[4 + i] = fmaf(hb[i], wk[j], acc[4 + i]); }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < HB; ++i) lg[i][tid] = acc[i];
-    } else if (tid >= 248) {   // value head: one thread per board
-        const int i = tid - 248;
-        float acc = pk[PackedLayout::VB2];
-        for (int k = 0; k < HID / 2; ++k) acc = fmaf(hidT[HID / 2 + k][i], pk[PackedLayout::VW2 + k], acc);
-        if (i < nb && !(active && !active[b0 + i])) {
-            if (value_pre) value_pre[b0 + i] = acc;
-            if (value) value[b0 + i] = tanhf(acc);
-        }
-    }
-    __syncthreads();
-    // softmax: wave w handles boards 2w, 2w+1
-    const int lane = tid & 63, wave = tid >> 6;
-    for (int r = 2 * wave; r < 2 * wave + 2; ++r) {
-        if (r >= nb) break;
-        if (active && !active[b0 + r]) continue;
-        float m = -INFINITY;
-        for (int a = lane; a < A; a += 64) m = fmaxf(m, lg[r][a]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-        float e[4];
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int a = lane + 64 * j;
-            e[j] = (a < A) ? expf(lg[r][a] - m) : 0.f;
-            s += e[j];
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int a = lane + 64 * j;
-            if (a < A) {
-                if (logits) logits[(size_t)(b0 + r) * A + a] = lg[r][a];
-                if (policy) policy[(size_t)(b0 + r) * A + a] = e[j] / s;
-            }
-        }
-    }
-}
-
-
-AQG_TRACE_SETTER(set_trace_gcn)
 
 // Trunk variants (aqg_set_option("trunk_variant", v)):
 //   0 exact f32-input MFMA + VALU gather, weights resident, 1 workgroup/CU      1 the same, 2 workgroups/CU
@@ -1660,17 +20,6 @@ AQG_TRACE_SETTER(set_trace_gcn)
 // (Retired: a split kernel with the VALU gather on 16-bit planes -- it read plane bytes no wave had written, see DESIGN.md section 3 --,
 //  the 4-wave x 2 form, the pair form and the per-board VALU heads inside the trunk: all measured slower, all in the history.)
 int g_trunk_variant = 3;
-int g_heads_prio = 3;             // wave priority of the heads kernel (option "heads_prio", 0..3): round 3, same-box runs: 0 -> 1,626 / 1,641 games/s,
-                                  // 1 -> 1,644 / 1,648, 2 -> 1,646, 3 -> 1,657 (profiles/r03_trunk_ab_runs.log)
-int g_trunk_prio = -1;            // wave priorities (bit 0: waves 4-7, bit 1: second-resident workgroups, bit 2: first, bit 3: the two workgroups
-                                  // of a CU alternate at priority 1 phase by phase); -1 = by launch size: alternation at >= 1024 boards
-                                  // (+2-3 %: 45.3 M boards/s at 4,096, 47.9 M at 65,536; tools/prio_scan.py), none below (no gain at 480 and
-                                  // it would outrank the other sets' step kernels: -2 % games/s)
-int g_trunk_phase_delay = 100;   // x 64 cycles: start offset of the second-resident workgroups, applied to launches of
-                                 // >= 8192 boards (+4-11 % there; a wash at the ~2,000-board launches of the MCTS; tools/phase_scan.py)
-int g_trunk_delay_min_boards = 2048;   // launches below this many boards start all workgroups together (tools/phase_scan.py:
-                                       // +4 % at 2,048 boards, +8 % at 4,096, +15-19 % from 8,192 on the three-per-CU form)
-int g_trunk_grid = 0;      // 0 = default persistent grid; otherwise override (diagnostics)
 
 // Diagnostic: fill every CU's LDS with NaN bit patterns so that any read-before-write in a later kernel shows up
 // deterministically (used by the parity tests; LDS contents are otherwise whatever the previous kernel left).
@@ -1736,200 +85,21 @@ int launch_gcn_forward_boards(int N, const void* states, int fmt, int B, const f
     if (!pooled) return fail("pooled workspace is required");
     if (N * N + 2 * (N - 1) * (N - 1) > 248) return fail("policy size exceeds 248");
     const int A = N * N + 2 * (N - 1) * (N - 1);
-    // persistent grid: 256 CUs x resident workgroups per CU, grid-stride over boards
     const int variant = (flags & 1) ? (g_trunk_variant == 0 ? 0 : 1) : g_trunk_variant;   // AQG_GNN_EXACT_F32
     if (g_profile_trunk == 1) { (void)hipEventRecord(prof_event(), st); g_prof_boards += B; }
-    if (variant == 0) {
-        int grid = B < 256 ? B : 256;
-        hipLaunchKernelGGL((gcn_trunk_boards_kernel<true, 1>), dim3(grid), dim3(256), 0, st, states, fmt, B, packed, pooled, active);
-    } else if (variant == 1) {
-        int grid = B < 512 ? B : 512;
-        hipLaunchKernelGGL((gcn_trunk_boards_kernel<false, 2>), dim3(grid), dim3(256), 0, st, states, fmt, B, packed, pooled, active);
+    if (variant == 0 || variant == 1) {
+        launch_gcn_trunk_exact(variant, states, fmt, B, packed, pooled, active, st);
     } else {
-        // two 8-wave workgroups per CU (a wave owns 16 feature columns): shortest latency per board AND, with four waves per
-        // SIMD to hide each other's vector work, the highest throughput at every launch size (tools/trunk_scan.py)
-        int grid = B < 512 ? B : 512;
-        if (g_trunk_grid > 0 && g_trunk_grid < grid) grid = g_trunk_grid;
-        const int opts = ((B >= g_trunk_delay_min_boards && !list) ? g_trunk_phase_delay : 0) |     // (a list is a fraction of B: no start offset)
-                         ((g_trunk_prio >= 0 ? g_trunk_prio : (B >= 1024 ? 8 : 0)) << 16);
-        const dim3 tg(grid), tb(64 * NWV);
-        if ((flags & AQG_GNN_RANGE_PROVEN) && saturated) {
-            if (list) hipLaunchKernelGGL((gcn_trunk_boards_mm_kernel<0, true>), tg, tb, 0, st, states, fmt, B, packed, pooled, active, opts, saturated, list, list_count);
-            else hipLaunchKernelGGL((gcn_trunk_boards_mm_kernel<0, false>), tg, tb, 0, st, states, fmt, B, packed, pooled, active, opts, saturated, list, list_count);
-        } else {
-            if (list) hipLaunchKernelGGL((gcn_trunk_boards_mm_kernel<2, true>), tg, tb, 0, st, states, fmt, B, packed, pooled, active, opts, saturated, list, list_count);
-            else hipLaunchKernelGGL((gcn_trunk_boards_mm_kernel<2, false>), tg, tb, 0, st, states, fmt, B, packed, pooled, active, opts, saturated, list, list_count);
-        }
+        const int track = ((flags & AQG_GNN_RANGE_PROVEN) && saturated) ? 0 : 2;
+        launch_gcn_trunk_split(track, states, fmt, B, packed, pooled, active, saturated, list, list_count, st);
     }
     if (g_profile_trunk == 1) (void)hipEventRecord(prof_event(), st);
     if (int r = check_launch("gcn_trunk_boards_kernel")) return r;
     if (!logits && !policy && !value_pre && !value) return 0;   // trunk only (bench: time the dominant kernel alone)
     if (variant >= 3 && A <= 14 * 16) {
-        hipLaunchKernelGGL(gcn_heads_mm_kernel, dim3((B + 15) / 16), dim3(64 * HEADS_WAVES), 0, st, pooled, B, A, packed,
-                           logits, policy, value_pre, value, active, g_heads_prio, saturated);
-        return check_launch("gcn_heads_mm_kernel");
+        return launch_gcn_heads_split(pooled, B, A, packed, logits, policy, value_pre, value, active, saturated, st);
     }
-    hipLaunchKernelGGL(gcn_heads_kernel, dim3((B + HB - 1) / HB), dim3(256), 0, st, (const float*)pooled, B, A, packed,
-                       logits, policy, value_pre, value, active);
-    return check_launch("gcn_heads_kernel");
-}
-
-// ---------------------------------------------------------------------------------------------
-// the VALU linear map of the any-size board path below
-// ---------------------------------------------------------------------------------------------
-// Y[n][HID] = X[n][K] * WT[K][HID]   (WT row stride ldw; K = 6 (padded rows of W1 read as [n][f]) or 128)
-template <bool W_IS_NF>
-__global__ __launch_bounds__(256) void graph_linear_kernel(const float* __restrict__ X, int K, int num_nodes,
-                                                           const float* __restrict__ W, float* __restrict__ Y) {
-    __shared__ float xs[32][HID + 1];
-    const int tid = threadIdx.x;
-    const int n0 = blockIdx.x * 32;
-    for (int i = tid; i < 32 * K; i += 256) {
-        const int r = i / K, k = i % K;
-        xs[r][k] = (n0 + r < num_nodes) ? X[(size_t)(n0 + r) * K + k] : 0.f;
-    }
-    __syncthreads();
-    const int col = tid & 127, half = tid >> 7;   // 16 nodes per thread
-    float acc[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    for (int k = 0; k < K; ++k) {
-        const float w = W_IS_NF ? W[col * FPAD + k] : W[(size_t)k * HID + col];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = fmaf(xs[16 * half + i][k], w, acc[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int n = n0 + 16 * half + i;
-        if (n < num_nodes) Y[(size_t)n * HID + col] = acc[i];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// boards of ANY size (3x3 .. 9x9) on plain kernels: the fused trunk above is specialised for the 9x9 board of the
-// benchmark; smaller boards (the reference's constants.py:5-20 debugging sizes) go records -> node features + normalised
-// adjacency in ELL form (<= 5 entries per node) -> 3 x (linear, ELL gather + bias + ReLU) -> mean pool -> exact heads.
-// Correctness-first, fp32 throughout.  Workspace (caller-owned): 272 floats per node.
-// ---------------------------------------------------------------------------------------------
-// ELL = false: the node features only (the CNN's input planes, csrc/cnn_forward.hip); ell_idx / ell_w are not touched
-template <int N, bool ELL = true>
-__global__ __launch_bounds__(256) void boards_prep_kernel(const void* __restrict__ states, int fmt, int B, float* __restrict__ x0,
-                                                          int32_t* __restrict__ ell_idx, float* __restrict__ ell_w) {
-    constexpr int V = N * N, S = N - 1;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B * V) return;
-    const int b = i / V, t = i % V;
-    const QState s = load_state(states, fmt, b);
-    const int x = t / N, y = t % N;
-    const bool slot_ok = x < S && y < S;
-    const int slot = x * S + y;
-    float* f = x0 + (size_t)i * 6;
-    f[0] = (t == s.ppos) ? 1.f : 0.f;
-    f[1] = (float)s.pwl;
-    f[2] = (t == s.epos) ? 1.f : 0.f;
-    f[3] = (float)s.ewl;
-    f[4] = (slot_ok && ((s.hw >> slot) & 1)) ? 1.f : 0.f;
-    f[5] = (slot_ok && ((s.vw >> slot) & 1)) ? 1.f : 0.f;
-    if constexpr (!ELL) return;
-    const int ob = tile_open_bits<N>(s.hw, s.vw, t);
-    const float di = dinv_of_bits(ob);
-    const int nb[4] = {t - N, t + N, t - 1, t + 1};
-    ell_idx[(size_t)i * 5] = i;
-    ell_w[(size_t)i * 5] = di * di;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        const bool open = (ob >> d) & 1;
-        ell_idx[(size_t)i * 5 + 1 + d] = open ? b * V + nb[d] : -1;
-        ell_w[(size_t)i * 5 + 1 + d] = open ? di * dinv_of_bits(tile_open_bits<N>(s.hw, s.vw, nb[d])) : 0.f;
-    }
-}
-
-__global__ __launch_bounds__(256) void ell_gather_kernel(const float* __restrict__ Y, int num_nodes, const int32_t* __restrict__ idx,
-                                                         const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= num_nodes) return;
-    float a0 = bias[2 * lane], a1 = bias[2 * lane + 1];
-#pragma unroll
-    for (int e = 0; e < 5; ++e) {
-        const int j = idx[(size_t)n * 5 + e];
-        if (j >= 0) {
-            const float we = w[(size_t)n * 5 + e];
-            const float2 y = *reinterpret_cast<const float2*>(Y + (size_t)j * HID + 2 * lane);
-            a0 = fmaf(we, y.x, a0);
-            a1 = fmaf(we, y.y, a1);
-        }
-    }
-    *reinterpret_cast<float2*>(out + (size_t)n * HID + 2 * lane) = make_float2(fmaxf(a0, 0.f), fmaxf(a1, 0.f));
-}
-
-// (`active`: the engine's leaf mask, as in the heads -- a masked-out board's pooled row is left as it was)
-__global__ __launch_bounds__(128) void board_pool_kernel(const float* __restrict__ Hn, int V, const uint8_t* __restrict__ active,
-                                                         float* __restrict__ pooled) {
-    const int b = blockIdx.x;
-    if (active && !active[b]) return;
-    float s = 0.f;
-    for (int i = 0; i < V; ++i) s += Hn[((size_t)b * V + i) * HID + threadIdx.x];
-    pooled[(size_t)b * HID + threadIdx.x] = s / (float)V;
-}
-
-size_t boards_any_workspace_floats(int N, int B) { return (size_t)B * N * N * 272; }
-
-int launch_gcn_forward_boards_any(int N, const void* states, int fmt, int B, const float* packed, float* workspace,
-                                  size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre,
-                                  float* value, const uint8_t* active, int flags, int32_t* saturated, hipStream_t st,
-                                  const int32_t* list, const int32_t* list_count) {
-    // (`list`: see gcn_trunk_boards_mm_kernel; honoured by the 9x9 split trunk only -- every other path walks the mask, which must agree)
-    if (N == 9) return launch_gcn_forward_boards(N, states, fmt, B, packed, pooled, logits, policy, value_pre, value, active, flags, saturated, st, list, list_count);
-    if (!(N == 3 || N == 5 || N == 7)) return fail("board_size must be 3, 5, 7 or 9");
-    if (B <= 0) return 0;
-    if (!pooled) return fail("pooled workspace is required");
-    if (!workspace || workspace_floats < boards_any_workspace_floats(N, B)) return fail("workspace too small (272 floats per node)");
-    const int V = N * N, R = B * V, A = V + 2 * (N - 1) * (N - 1);
-    float* x0 = workspace;
-    float* ell_w = x0 + (size_t)R * 6;
-    int32_t* ell_idx = reinterpret_cast<int32_t*>(ell_w + (size_t)R * 5);
-    float* work0 = reinterpret_cast<float*>(ell_idx + (size_t)R * 5);
-    float* work1 = work0 + (size_t)R * HID;
-    const dim3 lg((R + 31) / 32), gg((R + 3) / 4), blk(256);
-    if (int r = launch_gcn_boards_graph(N, states, fmt, B, x0, ell_idx, ell_w, st)) return r;
-    hipLaunchKernelGGL(graph_linear_kernel<true>, lg, blk, 0, st, (const float*)x0, 6, R, packed + PackedLayout::W1, work0);
-    hipLaunchKernelGGL(ell_gather_kernel, gg, blk, 0, st, (const float*)work0, R, (const int32_t*)ell_idx, (const float*)ell_w, packed + PackedLayout::B1, work1);
-    hipLaunchKernelGGL(graph_linear_kernel<false>, lg, blk, 0, st, (const float*)work1, HID, R, packed + PackedLayout::W2T, work0);
-    hipLaunchKernelGGL(ell_gather_kernel, gg, blk, 0, st, (const float*)work0, R, (const int32_t*)ell_idx, (const float*)ell_w, packed + PackedLayout::B2, work1);
-    hipLaunchKernelGGL(graph_linear_kernel<false>, lg, blk, 0, st, (const float*)work1, HID, R, packed + PackedLayout::W3T, work0);
-    hipLaunchKernelGGL(ell_gather_kernel, gg, blk, 0, st, (const float*)work0, R, (const int32_t*)ell_idx, (const float*)ell_w, packed + PackedLayout::B3, work1);
-    hipLaunchKernelGGL(board_pool_kernel, dim3(B), dim3(128), 0, st, (const float*)work1, V, active, pooled);
-    if (int r = check_launch("generic board kernels")) return r;
-    if (!logits && !policy && !value_pre && !value) return 0;
-    hipLaunchKernelGGL(gcn_heads_kernel, dim3((B + HB - 1) / HB), dim3(256), 0, st, (const float*)pooled, B, A, packed, logits, policy,
-                       value_pre, value, active);
-    return check_launch("gcn_heads_kernel");
-}
-
-// The board featuriser alone, for the width-generic graph primitives (gcn_general.hip): x0 [B*V,6] node features and the
-// normalised adjacency as ELL rows of 5 (self loop first, then the open neighbours; a closed side has index -1, weight 0).
-int launch_gcn_boards_graph(int N, const void* states, int fmt, int B, float* x0, int32_t* ell_idx, float* ell_w, hipStream_t st) {
-    if (!board_size_supported(N)) return fail("board_size must be 3, 5, 7 or 9");
-    if (B <= 0) return 0;
-    const int R = B * N * N;
-    const dim3 pg((R + 255) / 256), blk(256);
-    return for_board_size(N, [&](auto n) {
-        hipLaunchKernelGGL(boards_prep_kernel<decltype(n)::value>, pg, blk, 0, st, states, fmt, B, x0, ell_idx, ell_w);
-        return check_launch("boards_prep_kernel");
-    });
-}
-
-// The featuriser's node features alone: x0 [B*V,6], the six planes of pv_network_cnn.py:88-114 tile by tile (the CNN's input).
-int launch_gcn_boards_features(int N, const void* states, int fmt, int B, float* x0, hipStream_t st) {
-    if (!board_size_supported(N)) return fail("board_size must be 3, 5, 7 or 9");
-    if (B <= 0) return 0;
-    const int R = B * N * N;
-    const dim3 pg((R + 255) / 256), blk(256);
-    return for_board_size(N, [&](auto n) {
-        hipLaunchKernelGGL((boards_prep_kernel<decltype(n)::value, false>), pg, blk, 0, st, states, fmt, B, x0, nullptr, nullptr);
-        return check_launch("boards_prep_kernel");
-    });
+    return launch_gcn_heads_exact(pooled, B, A, packed, logits, policy, value_pre, value, active, st);
 }
 
 }  // namespace aqg

@@ -1,0 +1,162 @@
+// gcn_pack.hip -- host only: the state_dict tensors of GraphPolicyValueNetwork (hidden width 128) laid out as the packed weight
+// buffer the forward kernels read (PackedLayout, gcn_packed.hpp; include/aqgnn.h, aqg_gcn_pack_weights): the plain f32 matrices of
+// the exact kernels, the MFMA fragment orders, the fp16 hi/lo split planes of the split trunk and heads, its bias rows and the
+// thresholds of its range guard.
+#include "aqg_common.hpp"
+#include "../../include/aqgnn.h"
+#include "launchers.hpp"
+#include "gcn_packed.hpp"
+#include <cmath>
+#include <algorithm>
+
+namespace aqg {
+
+size_t packed_floats() { return PackedLayout::TOTAL; }
+
+// tensors (host fp32), state_dict order: gcn0.w[H,F] gcn0.b gcn1.w[H,H] gcn1.b gcn2.w gcn2.b
+// pol0.w[H/2,H] pol0.b pol2.w[A,H/2] pol2.b val0.w[H/2,H] val0.b val2.w[1,H/2] val2.b
+int pack_weights_host(int N, const float* const* t, float* out) {
+    const int F = 6, A = N * N + 2 * (N - 1) * (N - 1);
+    if (A > APAD) return fail("policy size exceeds APAD");
+    memset(out, 0, sizeof(float) * PackedLayout::TOTAL);
+    for (int n = 0; n < HID; ++n)
+        for (int f = 0; f < F; ++f) out[PackedLayout::W1 + n * FPAD + f] = t[0][n * F + f];
+    memcpy(out + PackedLayout::B1, t[1], sizeof(float) * HID);
+    for (int n = 0; n < HID; ++n)
+        for (int k = 0; k < HID; ++k) {
+            out[PackedLayout::W2T + k * HID + n] = t[2][n * HID + k];
+            out[PackedLayout::W3T + k * HID + n] = t[4][n * HID + k];
+        }
+    memcpy(out + PackedLayout::B2, t[3], sizeof(float) * HID);
+    memcpy(out + PackedLayout::B3, t[5], sizeof(float) * HID);
+    for (int w = 0; w < 4; ++w)
+        for (int j = 0; j < 2; ++j)
+            for (int s4 = 0; s4 < 8; ++s4)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int i = 0; i < 4; ++i) {
+                        const int c = lane & 15, q = lane >> 4;
+                        const int k = (q & 1) * 64 + (q >> 1) * 32 + 4 * s4 + i, n = 32 * w + 16 * j + c;
+                        const size_t o = ((((size_t)w * 2 + j) * 8 + s4) * 64 + lane) * 4 + i;
+                        out[PackedLayout::WF2 + o] = t[2][n * HID + k];
+                        out[PackedLayout::WF3 + o] = t[4][n * HID + k];
+                    }
+    for (int L = 0; L < 2; ++L) {                                 // fp16 split planes
+        const float* W = t[L == 0 ? 2 : 4];
+        uint32_t* dst = reinterpret_cast<uint32_t*>(out + (L == 0 ? PackedLayout::WH2 : PackedLayout::WH3));
+        auto split2 = [](float x, uint16_t (&pl)[2]) {
+            const _Float16 h = (_Float16)x;                       // RNE
+            const _Float16 l = (_Float16)(x - (float)h);
+            memcpy(&pl[0], &h, 2); memcpy(&pl[1], &l, 2);
+        };
+        for (int w = 0; w < 4; ++w)
+            for (int j = 0; j < 2; ++j)
+                for (int kb = 0; kb < 4; ++kb)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int d = 0; d < 4; ++d) {
+                            const int c = lane & 15, q = lane >> 4, n = 32 * w + 16 * j + c;
+                            uint16_t a[2], b[2];                  // layers 2, 3 see the planes' scale: W / CQ
+                            split2((float)((double)W[n * HID + 32 * kb + 8 * q + 2 * d] / CQ), a);
+                            split2((float)((double)W[n * HID + 32 * kb + 8 * q + 2 * d + 1] / CQ), b);
+                            for (int pl = 0; pl < 2; ++pl) {
+                                const size_t o = (((((size_t)pl * 4 + w) * 2 + j) * 4 + kb) * 64 + lane) * 4 + d;
+                                dst[o] = (uint32_t)a[pl] | ((uint32_t)b[pl] << 16);
+                            }
+                        }
+    }
+    {
+        // layer 1 runs aggregate-first (see the trunk comment): the wave's 16 output features are the ROWS of the A operand, the
+        // k index carries the six input features three times -- k-slots 8 q + j: q = 0 and 1 hold hi(c W1[n][j]) (they meet
+        // hi(G') and lo(G') in the B operand), q = 2 holds lo(c W1[n][j]) (meets hi(G') again), q = 3 is zero
+        uint32_t* dst = reinterpret_cast<uint32_t*>(out + PackedLayout::WH1);
+        for (int w = 0; w < 4; ++w)
+            for (int j = 0; j < 2; ++j)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int d = 0; d < 4; ++d) {
+                        const int c = lane & 15, q = lane >> 4, n = 32 * w + 16 * j + c;
+                        uint16_t h[2] = {0, 0};
+                        for (int e = 0; e < 2; ++e) {
+                            const int k = 2 * d + e;
+                            if (q < 3 && k < F) {
+                                const float x = (float)(CQ * (double)t[0][n * F + k]);
+                                const _Float16 hi = (_Float16)x;
+                                const _Float16 v = (q < 2) ? hi : (_Float16)(x - (float)hi);
+                                memcpy(&h[e], &v, 2);
+                            }
+                        }
+                        dst[((w * 2 + j) * 64 + lane) * 4 + d] = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
+                    }
+    }
+    {
+        auto split2 = [](float x, uint16_t (&pl)[2]) {
+            const _Float16 h = (_Float16)x;
+            const _Float16 l = (_Float16)(x - (float)h);
+            memcpy(&pl[0], &h, 2); memcpy(&pl[1], &l, 2);
+        };
+        uint32_t* d1 = reinterpret_cast<uint32_t*>(out + PackedLayout::WHH1);
+        for (int ut = 0; ut < 8; ++ut)
+            for (int kb = 0; kb < 4; ++kb)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int d = 0; d < 4; ++d) {
+                        const int c = lane & 15, q = lane >> 4, u = 16 * ut + c;
+                        uint16_t a[2], b[2];
+                        const int k = 32 * kb + 8 * q + 2 * d;
+                        const float* W = u < HID / 2 ? t[6] + (size_t)u * HID : t[10] + (size_t)(u - HID / 2) * HID;
+                        split2(W[k], a); split2(W[k + 1], b);
+                        for (int pl = 0; pl < 2; ++pl)
+                            d1[((((size_t)pl * 8 + ut) * 4 + kb) * 64 + lane) * 4 + d] = (uint32_t)a[pl] | ((uint32_t)b[pl] << 16);
+                    }
+        uint32_t* d2 = reinterpret_cast<uint32_t*>(out + PackedLayout::WHP2);
+        for (int at = 0; at < 14; ++at)
+            for (int kb = 0; kb < 2; ++kb)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int d = 0; d < 4; ++d) {
+                        const int c = lane & 15, q = lane >> 4, act = 16 * at + c;
+                        uint16_t h[2][2] = {{0, 0}, {0, 0}};
+                        for (int e2 = 0; e2 < 2; ++e2) {
+                            const int e = 2 * d + e2, u = 32 * kb + 16 * (e >> 2) + 4 * q + (e & 3);
+                            if (act < A) split2(t[8][(size_t)act * (HID / 2) + u], h[e2]);
+                        }
+                        for (int pl = 0; pl < 2; ++pl)
+                            d2[((((size_t)pl * 14 + at) * 2 + kb) * 64 + lane) * 4 + d] = (uint32_t)h[0][pl] | ((uint32_t)h[1][pl] << 16);
+                    }
+    }
+    for (int L = 0; L < 3; ++L)
+        for (int deg = 1; deg <= 5; ++deg)
+            for (int f = 0; f < HID; ++f)
+                out[PackedLayout::TB + ((size_t)L * 5 + (deg - 1)) * HID + f] = (float)(CQ * (double)t[2 * L + 1][f] * sqrt((double)deg));
+    {
+        // |V[n][f]| <= sum_{k in N[n]} |U[k][f]| CQ / deg_k + |TB| <= max|U| * CQ * (1/d_n + (d_n - 1)/2) + max|TB| <= 2.0625 max|U| + max|TB|
+        // (a neighbour has closed degree >= 2): 2.07 with rounding slack
+        double tbmax = 0.0;
+        for (int deg = 1; deg <= 5; ++deg)
+            for (int f = 0; f < HID; ++f) tbmax = std::max(tbmax, std::fabs((double)out[PackedLayout::TB + ((size_t)1 * 5 + (deg - 1)) * HID + f]));
+        const double t2 = (65504.0 - tbmax) / 2.07;
+        // A weight whose fp16 hi half is not finite (|W| / CQ >= 65504 rounds to inf, or W is inf / NaN) makes every product of its
+        // column inf - inf or 0 x inf = NaN, and the float maxima of the tracking build skip NaNs (v_max3_f32 returns the non-NaN
+        // operand): such a set gets NEGATIVE thresholds, which no maximum satisfies -- every board is reported and the host serves
+        // the set with the exact kernels (include/aqgnn.h promises "inf / NaN included").  The same for a NaN / negative bound.
+        bool hi_finite = true;
+        auto hi_ok = [](double x) { const float h = (float)(_Float16)(float)x; return h == h && std::fabs(h) <= 65504.0f; };
+        for (int i = 0; i < HID * F; ++i) hi_finite = hi_finite && hi_ok(CQ * (double)t[0][i]);
+        for (int i = 0; i < HID * HID; ++i) hi_finite = hi_finite && hi_ok((double)t[2][i] / CQ) && hi_ok((double)t[4][i] / CQ);
+        const bool bound_ok = t2 > 0.0 && t2 == t2;
+        out[PackedLayout::GUARD + 0] = (hi_finite && bound_ok) ? (float)t2 : -1.0f;
+        out[PackedLayout::GUARD + 1] = hi_finite ? 65504.0f : -1.0f;
+        out[PackedLayout::GUARD + 2] = out[PackedLayout::GUARD + 3] = 0.f;
+    }
+    for (int u = 0; u < HID / 2; ++u)
+        for (int k = 0; k < HID; ++k) {
+            out[PackedLayout::HW1T + k * HID + u] = t[6][u * HID + k];
+            out[PackedLayout::HW1T + k * HID + HID / 2 + u] = t[10][u * HID + k];
+        }
+    memcpy(out + PackedLayout::HB1, t[7], sizeof(float) * (HID / 2));
+    memcpy(out + PackedLayout::HB1 + HID / 2, t[11], sizeof(float) * (HID / 2));
+    for (int a = 0; a < A; ++a)
+        for (int k = 0; k < HID / 2; ++k) out[PackedLayout::PW2T + k * APAD + a] = t[8][a * (HID / 2) + k];
+    memcpy(out + PackedLayout::PB2, t[9], sizeof(float) * A);
+    memcpy(out + PackedLayout::VW2, t[12], sizeof(float) * (HID / 2));
+    out[PackedLayout::VB2] = t[13][0];
+    return 0;
+}
+
+}  // namespace aqg

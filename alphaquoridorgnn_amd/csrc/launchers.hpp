@@ -13,22 +13,41 @@ int launch_state_next(int N, const uint8_t* in, const int32_t* actions, int B, u
 int launch_state_status(int N, const uint8_t* in, int B, int draw, uint8_t* flags, hipStream_t st);
 
 // ---- gcn_forward.hip
-extern int g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, g_profile_trunk, g_trunk_prio, g_heads_prio;
+extern int g_trunk_variant, g_profile_trunk;
 void profile_mark(hipStream_t st, long long units);
 int profile_collect(double* total_ms, long long* launches, long long* boards, int reset);
 int launch_poison_lds(hipStream_t st);
-int set_trace_gcn(void* buf, unsigned int cap);
-size_t packed_floats();
-int pack_weights_host(int N, const float* const* t, float* out);
 int launch_gcn_forward_boards(int N, const void* states, int fmt, int B, const float* packed, float* pooled,
                               float* logits, float* policy, float* value_pre, float* value, const uint8_t* active,
                               int flags, int32_t* saturated, hipStream_t st, const int32_t* list = nullptr,
                               const int32_t* list_count = nullptr);
+
+// ---- gcn_pack.hip
+size_t packed_floats();
+int pack_weights_host(int N, const float* const* t, float* out);
+
+// ---- gcn_trunk_split.hip  (the trunk launchers only enqueue: launch_gcn_forward_boards checks the launch behind its profiling event)
+extern int g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, g_trunk_prio, g_heads_prio;
+int set_trace_gcn(void* buf, unsigned int cap);
+void launch_gcn_trunk_split(int track, const void* states, int fmt, int B, const float* packed, float* pooled, const uint8_t* active,
+                            int32_t* saturated, const int32_t* list, const int32_t* list_count, hipStream_t st);
+int launch_gcn_heads_split(float* pooled, int B, int A, const float* packed, float* logits, float* policy, float* value_pre,
+                           float* value, const uint8_t* active, int32_t* saturated, hipStream_t st);
+
+// ---- gcn_trunk_exact.hip
+void launch_gcn_trunk_exact(int variant, const void* states, int fmt, int B, const float* packed, float* pooled,
+                            const uint8_t* active, hipStream_t st);
+int launch_gcn_heads_exact(const float* pooled, int B, int A, const float* packed, float* logits, float* policy, float* value_pre,
+                           float* value, const uint8_t* active, hipStream_t st);
+
+// ---- gcn_boards_plain.hip
 size_t boards_any_workspace_floats(int N, int B);
 int launch_gcn_forward_boards_any(int N, const void* states, int fmt, int B, const float* packed, float* workspace,
                                   size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre,
                                   float* value, const uint8_t* active, int flags, int32_t* saturated, hipStream_t st,
                                   const int32_t* list = nullptr, const int32_t* list_count = nullptr);
+
+// ---- board_featuriser.hip
 int launch_gcn_boards_graph(int N, const void* states, int fmt, int B, float* x0, int32_t* ell_idx, float* ell_w, hipStream_t st);
 int launch_gcn_boards_features(int N, const void* states, int fmt, int B, float* x0, hipStream_t st);
 

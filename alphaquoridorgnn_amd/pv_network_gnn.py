@@ -14,8 +14,8 @@ Any shape: the reference's GraphPolicyValueNetwork takes any (num_features, hidd
 csrc/gcn_general.hip, which also serve `GCNConv.forward(x, edge_index)` and `global_mean_pool(x, batch)` -- PyG's calls, on any
 layer -- forward and backward.  On board records the default 6/128/3 network (`fused`) runs the fused kernels.
 
-All arithmetic runs in libaqgnn_hip.so (fp32 data; fp16-split or f32-input MFMA, see csrc/gcn_forward.hip); there is no
-torch/CPU forward in this file.
+All arithmetic runs in libaqgnn_hip.so (fp32 data; fp16-split or f32-input MFMA, see csrc/gcn_trunk_split.hip and
+csrc/gcn_trunk_exact.hip); there is no torch/CPU forward in this file.
 """
 import ctypes
 import math

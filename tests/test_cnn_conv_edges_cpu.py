@@ -2,7 +2,7 @@
 
   * the CNN forward's conv kernel and its packing (csrc/cnn_forward.hip: cnn_conv_kernel, cnn_pack_conv_kernel, cnn_pack_bn_kernel)
     through CNNNetwork on arbitrary [B,6,N,N] planes -- tests/test_cnn_conv_edges.py is the GPU half;
-  * the board featuriser alone (csrc/gcn_forward.hip: boards_prep_kernel through aqg_gcn_boards_graph) -- tests/test_featuriser.py.
+  * the board featuriser alone (csrc/board_featuriser.hip: boards_prep_kernel through aqg_gcn_boards_graph) -- tests/test_featuriser.py.
 
 Here live the case lists, the input generators and the float64 references; the tests of this file check the references against an
 independent statement (the stock nn modules in float64, oracle.gnn), check that every exact case stays below 2^24 and every

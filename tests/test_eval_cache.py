@@ -416,7 +416,7 @@ def test_pv_mcts_engine_refresh_after_in_place_update(dev, monkeypatch):
 
 # ------------------------------------------------------------------ D: launch options that change geometry only
 OPTION_DEFAULTS = dict(step_waves=8, trunk_grid=0, trunk_delay_min_boards=2048, trunk_phase_delay=100, trunk_prio=-1, step_prio=1,
-                       heads_prio=3, use_graph=1)     # csrc/mcts.hip, csrc/gcn_forward.hip: the g_* initialisers
+                       heads_prio=3, use_graph=1)     # csrc/mcts.hip, csrc/gcn_trunk_split.hip: the g_* initialisers
 OPTION_SETTINGS = [dict(step_waves=1), dict(step_waves=2), dict(step_waves=4),
                    dict(trunk_grid=1), dict(trunk_grid=7), dict(trunk_grid=100),
                    dict(trunk_delay_min_boards=1, trunk_phase_delay=0), dict(trunk_delay_min_boards=1),

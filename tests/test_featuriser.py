@@ -1,4 +1,4 @@
-"""The board featuriser alone (csrc/gcn_forward.hip: boards_prep_kernel through aqg_gcn_boards_graph; include/aqgnn.h): the six
+"""The board featuriser alone (csrc/board_featuriser.hip: boards_prep_kernel through aqg_gcn_boards_graph; include/aqgnn.h): the six
 planes per tile against the reference's own recorded planes, the ELL adjacency against oracle.gnn.board_edges, independence of
 the batch around a board, guarded outputs and the argument checks.  The states, their coverage conditions and the expected values
 come from tests/test_cnn_conv_edges_cpu.py, where they are checked without a GPU."""

@@ -104,7 +104,7 @@ def test_weight_packing_layout():
     off = 128 * 8 + 128
     W2T = out[off:off + 128 * 128].reshape(128, 128)
     assert np.array_equal(W2T, p["gcn_layers.1.lin.weight"].T)
-    WF2 = 67396                                                            # offsets documented in include/aqgnn.h / gcn_forward.hip
+    WF2 = 67396                                                            # offsets documented in include/aqgnn.h / gcn_packed.hpp
     WH2 = WF2 + 2 * 128 * 128
     WH1 = WH2 + 2 * 2 * 128 * 128 // 2
     WHH1 = WH1 + 4 * 2 * 64 * 4

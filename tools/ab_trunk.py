@@ -3,7 +3,8 @@
 = the defaults); each set is compiled into its own library on the box, then the trunk (no heads) is timed at several launch sizes
 in ONE process with the variants' launches interleaved round by round (guide rule 24); the pooled outputs are compared as well.
   python tools/ab_trunk.py [--sizes 480,4096,65536] [--rounds 2] [--bench] "<flags A>" "<flags B>" ...
-A flag set may start with FILE=<path relative to the repo root> to compile another version of gcn_forward.hip (e.g. last round's).
+A flag set may start with FILE=<path relative to the repo root> to compile another version of gcn_trunk_split.hip in its place (a
+gcn_forward.hip from before the file was split holds six translation units' worth and can no longer stand in).
 --bench also runs bench.py's headline generation (2 timed steps, no extra legs) per variant."""
 import json
 import os
@@ -11,7 +12,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "alphaquoridorgnn_amd", "csrc")
+sys.path.insert(0, ROOT)
+from tools import diag_build
 
 _WORKER = r"""
 # every variant's library is loaded into THIS process (ctypes handles are independent), launches interleaved round by round
@@ -79,30 +81,13 @@ def main():
             raise SystemExit("unknown option " + args[0])
     variants = args or ["-"]
     libs = []
-    procs = []
-    cc = "/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC"
-    common = ["legal_mask", "gcn_train", "mcts", "capi"]        # the flags only touch gcn_forward.hip: everything else is built once
-    for f in common:
-        procs.append((f, subprocess.Popen(f"cd {SRC} && {cc} -c {f}.hip -o /tmp/ab_{f}.o", shell=True, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)))
-    procs.append(("host_agents", subprocess.Popen(f"cd {SRC} && g++ -O2 -std=c++17 -fPIC -c host_agents.cpp -o /tmp/ab_host_agents.o", shell=True,
-                                                  stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)))
     for i, fl in enumerate(variants):
         flags = "" if fl == "-" else fl
-        src = "gcn_forward.hip"
-        if flags.startswith("FILE="):                            # another version of the source file (path relative to the repo root)
+        replace = None
+        if flags.startswith("FILE="):                            # another version of gcn_trunk_split.hip (path relative to the repo root)
             path, _, flags = flags[5:].partition(" ")
-            src = f"-I{SRC} " + os.path.join(ROOT, path)
-        procs.append((f"gcn_forward[{fl}]", subprocess.Popen(f"cd {SRC} && {cc} {flags} -c {src} -o /tmp/ab_gf_{i}.o", shell=True,
-                                                             stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)))
-    for name, p in procs:
-        err = p.communicate()[1].decode()
-        if p.returncode != 0:
-            raise SystemExit(f"build failed for {name}:\n{err[-2000:]}")
-    objs = " ".join(f"/tmp/ab_{f}.o" for f in common + ["host_agents"])
-    for i in range(len(variants)):
-        so = f"/tmp/libaqgnn_ab_{i}.so"
-        subprocess.check_call(f"/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o {so} {objs} /tmp/ab_gf_{i}.o", shell=True)
-        libs.append(so)
+            replace = {"gcn_trunk_split": os.path.join(ROOT, path)}
+        libs.append(diag_build.build(flags, f"/tmp/libaqgnn_ab_{i}.so", replace))
     print("built", len(libs), "variants", flush=True)
     out = subprocess.run([sys.executable, "-c", _WORKER, ROOT, sizes, ",".join(libs), str(rounds)], capture_output=True, text=True, timeout=900)
     line = [l for l in out.stdout.splitlines() if l.startswith("RESULT ")]

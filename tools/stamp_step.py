@@ -3,13 +3,12 @@
 averaged over 512 games x a few moves; fake evaluator).  Read the SHARES, not the absolute run time of this build.
 AQG_LEVELS=1 adds -DAQG_STAMP_LEVELS: four stamps inside every tree level below the root (each is a read-modify-write of global memory
 in the loop: the level then takes ~50 % longer -- read their RATIOS only)."""
-import os, subprocess, sys
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import diag_build
 so = "/tmp/libaqgnn_hip_stamp.so"
-src = os.path.join(ROOT, "alphaquoridorgnn_amd", "csrc")
-subprocess.check_call(f"cd {src} && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -DAQG_STAMP {'-DAQG_STAMP_LEVELS' if os.environ.get('AQG_LEVELS') else ''} "
-                      f"legal_mask.hip gcn_forward.hip gcn_train.hip mcts.hip capi.hip host_agents.cpp -o {so} 2>/dev/null", shell=True)
+diag_build.build("-DAQG_STAMP -DAQG_STAMP_LEVELS" if os.environ.get("AQG_LEVELS") else "-DAQG_STAMP", so)
 os.environ["AQG_LIB_PATH"] = so
 import torch
 from alphaquoridorgnn_amd import _lib

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Diagnostic: build with -DAQG_STAMP and print where workgroup 0 of each training kernel spends its cycles
 (batch 128).  Read the SHARES; never quote this build's run time."""
-import ctypes, os, subprocess, sys
+import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import diag_build
 so = "/tmp/libaqgnn_hip_stamp.so"
-subprocess.check_call(["bash", os.path.join(ROOT, "alphaquoridorgnn_amd", "csrc", "build.sh")],
-                      env=dict(os.environ, AQG_EXTRA_FLAGS="-DAQG_STAMP", OUT=so), stdout=subprocess.DEVNULL)
+diag_build.build("-DAQG_STAMP", so)
 os.environ["AQG_LIB_PATH"] = so
 import torch
 from alphaquoridorgnn_amd import _lib

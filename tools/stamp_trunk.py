@@ -1,13 +1,12 @@
 #!/usr/bin/env python3
 """Diagnostic: build the trunk with -DAQG_STAMP and print the share of cycles per phase (workgroup 0, wave 0).
 Never quote this build's run time -- read its SHARES (guide: in-kernel stamps)."""
-import os, subprocess, sys
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import diag_build
 so = "/tmp/libaqgnn_hip_stamp.so"
-src = os.path.join(ROOT, "alphaquoridorgnn_amd", "csrc")
-subprocess.check_call(f"cd {src} && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -DAQG_STAMP "
-                      f"legal_mask.hip gcn_forward.hip gcn_train.hip mcts.hip capi.hip host_agents.cpp -o {so}", shell=True)
+diag_build.build("-DAQG_STAMP", so)
 os.environ["AQG_LIB_PATH"] = so
 import torch
 from alphaquoridorgnn_amd import _lib

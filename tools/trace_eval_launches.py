@@ -4,13 +4,12 @@ per 16 boards) -- from the -DAQG_TRACE build (every workgroup's start / end on t
 last workgroup end of a whole evaluation, the trunk workgroups' durations, the heads workgroups' durations.
 (At commit d13f38b this tool also traced the one-launch form -- heads by the trunk workgroup that pools a 16-board group's last board --
 whose result is kept in profiles/r04_heads_by_last_finisher_trace.log: 25.7 against 23.4 us per evaluation.)"""
-import os, subprocess, sys
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import diag_build
 so = "/tmp/libaqgnn_hip_trace.so"
-src = os.path.join(ROOT, "alphaquoridorgnn_amd", "csrc")
-subprocess.check_call(f"cd {src} && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -DAQG_TRACE "
-                      f"legal_mask.hip gcn_forward.hip gcn_train.hip mcts.hip capi.hip host_agents.cpp -o {so} 2>/dev/null", shell=True)
+diag_build.build("-DAQG_TRACE", so)
 os.environ["AQG_LIB_PATH"] = so
 import numpy as np, torch
 from alphaquoridorgnn_amd import _lib

@@ -4,13 +4,12 @@ workgroup logs its start / end on the 100 MHz s_memrealtime clock), plays a few 
 prints, for one traced move: launch durations per kernel, the share of wall time with k launches in flight, how the trunk
 launches of the sets overlap, and the idle gaps inside one set's chain.  (rocprofv3 --kernel-trace cannot show this: it
 serialises the dispatches it intercepts -- the same bench runs 2.5x slower under it.)"""
-import os, subprocess, sys
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import diag_build
 so = "/tmp/libaqgnn_hip_trace.so"
-src = os.path.join(ROOT, "alphaquoridorgnn_amd", "csrc")
-subprocess.check_call(f"cd {src} && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -DAQG_TRACE "
-                      f"legal_mask.hip gcn_forward.hip gcn_train.hip mcts.hip capi.hip host_agents.cpp -o {so} 2>/dev/null", shell=True)
+diag_build.build("-DAQG_TRACE", so)
 os.environ["AQG_LIB_PATH"] = so
 import numpy as np, torch
 from collections import defaultdict

@@ -2,14 +2,13 @@
 """Diagnostic: anatomy of ONE trunk launch (AQG_B boards, default 480) from the -DAQG_TRACE build: when each workgroup starts
 and ends on the 100 MHz s_memrealtime clock -- how much of the launch is ramp (staggered starts), chain (a workgroup's own
 time) and tail."""
-import os, subprocess, sys
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import diag_build
 so = "/tmp/libaqgnn_hip_trace.so"
-src = os.path.join(ROOT, "alphaquoridorgnn_amd", "csrc")
 if not (os.environ.get("AQG_TRACE_REUSE") and os.path.exists(so)):      # (scans: build once)
-  subprocess.check_call(f"cd {src} && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -DAQG_TRACE "
-                        f"legal_mask.hip gcn_forward.hip gcn_train.hip mcts.hip capi.hip host_agents.cpp -o {so} 2>/dev/null", shell=True)
+    diag_build.build("-DAQG_TRACE", so)
 os.environ["AQG_LIB_PATH"] = so
 import numpy as np, torch
 from alphaquoridorgnn_amd import _lib

@@ -1,13 +1,12 @@
 #!/usr/bin/env python3
 """Developer diagnostic (-DAQG_TRAIN_DEBUG build): dense dumps of the layer-2 backward intermediates (dZ3, dH2 before / after the ReLU
 mask) of the split-precision training step against the f32 step's, position by position."""
-import ctypes, os, subprocess, sys
+import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+from tools import diag_build
 so = "/tmp/libaqgnn_hip_dbg.so"
-src = os.path.join(ROOT, "alphaquoridorgnn_amd", "csrc")
-subprocess.check_call(f"cd {src} && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -DAQG_TRAIN_DEBUG "
-                      f"legal_mask.hip gcn_forward.hip gcn_train.hip mcts.hip capi.hip host_agents.cpp -o {so} 2>/dev/null", shell=True)
+diag_build.build("-DAQG_TRAIN_DEBUG", so)
 os.environ["AQG_LIB_PATH"] = so
 import numpy as np, torch
 from alphaquoridorgnn_amd import _lib
