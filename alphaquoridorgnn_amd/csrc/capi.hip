@@ -370,4 +370,11 @@ int aqg_cnn_train_steps(const aqg_cnn_train* t, const uint8_t* states72, const f
     return cnn_train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream);
 }
 
+int aqg_augment_gather(int board_size, int policy_size, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
+                       const uint8_t* flips, int use_seed, uint64_t seed, uint64_t epoch, int n, uint8_t* out72, float* out_pi,
+                       float* out_z, void* stream) {
+    return launch_augment_gather(board_size, policy_size, states72, pi, z, order, flips, use_seed, seed, epoch, n, out72, out_pi, out_z,
+                                 (hipStream_t)stream);
+}
+
 }  // extern "C"

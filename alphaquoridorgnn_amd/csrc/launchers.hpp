@@ -145,4 +145,9 @@ int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float*
 int cnn_train_steps(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
                     long long positions, float* loss_sums, hipStream_t st);
 
+// ---- augment.hip
+int launch_augment_gather(int N, int policy_size, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
+                          const uint8_t* flips, int use_seed, uint64_t seed, uint64_t epoch, int n, uint8_t* out72, float* out_pi,
+                          float* out_z, hipStream_t st);
+
 }  // namespace aqg

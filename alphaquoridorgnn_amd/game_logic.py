@@ -54,6 +54,85 @@ def status_batch(states72, board_size=BOARD_SIZE, plies_for_draw=NUM_PLIES_FOR_D
     return out
 
 
+# ------------------------------------------------------------------ the left-right mirror (include/aqgnn.h, "training augmentation")
+def _mirror_cells(cells, width):
+    """Cell i of a grid of lines of `width` cells, mirrored inside its line."""
+    return cells - cells % width + (width - 1 - cells % width)
+
+
+def mirror_actions(actions, board_size=BOARD_SIZE):
+    """The mirror images of an integer array of actions (column y -> N - 1 - y): a pawn action by its tile, a horizontal / vertical
+    wall action by its slot inside its own block.  An involution; int64 of the same shape."""
+    N = int(board_size)
+    if N % 2 == 0 or not 3 <= N <= 9:
+        raise ValueError("board_size must be 3, 5, 7 or 9")
+    a = np.asarray(actions, dtype=np.int64)
+    V, W = N * N, N - 1
+    NW = W * W
+    if a.size and (a.min() < 0 or a.max() >= V + 2 * NW):
+        raise ValueError(f"an action is outside 0..{V + 2 * NW - 1}, the actions of a {N}x{N} board")
+    block = np.where(a < V, 0, np.where(a < V + NW, V, V + NW))
+    return block + np.where(a < V, _mirror_cells(a, N), _mirror_cells(a - block, W))
+
+
+def mirror_action(a, board_size=BOARD_SIZE):
+    return int(mirror_actions(int(a), board_size))
+
+
+def mirror_record(rec72):
+    """The mirror of a state72 record (uint8 [72], or [B,72] of one board size), in numpy; N is read from byte 70.  A position byte
+    that is no tile of the board is copied through, as the kernel does."""
+    rec = np.asarray(rec72, dtype=np.uint8)
+    if rec.shape[-1] != STATE72 or rec.ndim not in (1, 2):
+        raise ValueError("mirror_record takes state72 records: uint8 [72] or [B,72]")
+    out = rec.copy()
+    if rec.size == 0:
+        return out
+    N = int(rec.reshape(-1, STATE72)[0, 70])
+    if N % 2 == 0 or not 3 <= N <= 9 or (rec[..., 70] != N).any():
+        raise ValueError("byte 70 of every record must hold the same board size 3, 5, 7 or 9")
+    for k in (0, 2):
+        p = rec[..., k].astype(np.int64)
+        out[..., k] = np.where(p < N * N, _mirror_cells(p, N), p).astype(np.uint8)
+    nw = (N - 1) ** 2
+    out[..., 4:4 + nw] = rec[..., 4 + _mirror_cells(np.arange(nw), N - 1)]
+    return out
+
+
+_ONES = {}
+
+
+def _mirror_launch(states72, pi, board_size):
+    x = states72 if states72 is not None else pi
+    dev = _lib.require_gpu(x.device)
+    A = num_actions(board_size)
+    if states72 is not None and (states72.dtype != torch.uint8 or states72.dim() != 2 or states72.shape[1] != STATE72):
+        raise ValueError("states72 must be a uint8 [B,72] device tensor")
+    if pi is not None and (pi.dtype != torch.float32 or pi.dim() != 2 or pi.shape[1] != A):
+        raise ValueError(f"pi must be a float32 [B,{A}] device tensor on a {board_size}x{board_size} board")
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    B = x.shape[0]
+    flips = _ONES.get(dev)                      # "every row": one table per device, grown when a larger batch comes
+    if flips is None or flips.shape[0] < B:
+        flips = _ONES[dev] = torch.ones((max(B, 1024),), dtype=torch.uint8, device=dev)
+    s, p = (x, None) if states72 is not None else (None, x)
+    _lib.check(_lib.load().aqg_augment_gather(board_size, A, _lib.ptr(s), _lib.ptr(p), None, None, _lib.ptr(flips), 0, 0, 0, B,
+                                              _lib.ptr(out if s is not None else None), _lib.ptr(out if p is not None else None),
+                                              None, _lib.stream_ptr(dev)), "aqg_augment_gather")
+    return out
+
+
+def mirror_batch(states72, board_size=BOARD_SIZE):
+    """states72: uint8 [B,72] device tensor -> the mirrored records, on the device (aqg_augment_gather, every row flipped)."""
+    return _mirror_launch(states72, None, board_size)
+
+
+def mirror_policy_batch(pi, board_size=BOARD_SIZE):
+    """pi: float32 [B,A] device tensor -> the rows permuted by the mirror, out[b, mirror(a)] = pi[b, a], on the device."""
+    return _mirror_launch(None, pi, board_size)
+
+
 def pack_state72(player, enemy, walls, plies_played, board_size):
     r = np.zeros(STATE72, dtype=np.uint8)
     r[0], r[1] = int(player[0]), int(player[1])
@@ -120,6 +199,10 @@ class State:
         nw = (N - 1) ** 2
         return cls(board_size=N, player=[int(rec[0]), int(rec[1])], enemy=[int(rec[2]), int(rec[3])],
                    walls=[int(x) for x in rec[4:4 + nw]], plies_played=int(rec[68]) | (int(rec[69]) << 8))
+
+    def mirror(self):
+        """The left-right mirror of this state (mirror_record): a symmetry of the rules."""
+        return State.from_record(mirror_record(self.record()))
 
     def next(self, action):
         """game_logic.py:366-391 -- move the pawn or set the wall, turn the board by 180 degrees, swap the players -- by the rule

@@ -55,6 +55,23 @@ def _history_rows(states72, visits, z, board_size):
     return out
 
 
+def mirror_history(history):
+    """The rows of a history followed by their left-right mirrors, in the .history schema [[player, enemy, walls], policy, z] -- on
+    the host, so that write_data(mirror_history(h)) is an augmented file the reference's own train_network.py can read.  The board
+    size is that of the walls list; z is unchanged and a policy is permuted, out[mirror(a)] = in[a]."""
+    from .game_logic import mirror_actions, mirror_record, pack_state72
+    out = list(history)
+    for (player, enemy, walls), pol, z in history:
+        N = int(round(len(walls) ** 0.5)) + 1
+        if (N - 1) ** 2 != len(walls) or len(pol) != N * N + 2 * (N - 1) ** 2:
+            raise ValueError("mirror_history: a row's walls and policy are not those of one board size")
+        m = mirror_record(pack_state72(player, enemy, walls, 0, N))
+        src = mirror_actions(np.arange(len(pol)), N)
+        out.append([[[int(m[0]), int(player[1])], [int(m[2]), int(enemy[1])], [int(x) for x in m[4:4 + len(walls)]]],
+                    [pol[a] for a in src], z])
+    return out
+
+
 def play(model, device=None, uniforms=None):
     """Execute one self-play game (self_play.py:40-68) -- a generation of one game on the engine.
     Returns [[state_array, policy list[POLICY_OUTPUT_SIZE], z], ...]."""

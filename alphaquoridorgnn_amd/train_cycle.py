@@ -165,7 +165,20 @@ def _parser():
                     help="self-play: weight of the Dirichlet noise mixed into every root's priors (default SP_ROOT_NOISE_EPS = 0: off)")
     ap.add_argument("--root-noise-alpha", type=float, default=None,
                     help="self-play: Dirichlet concentration (default SP_ROOT_NOISE_ALPHA: 10 / the board's action count)")
+    ap.add_argument("--mirror-augment", action="store_true",
+                    help="parameter update: train every epoch on positions mirrored left to right at random (default TRAIN_MIRROR = False: off)")
+    ap.add_argument("--mirror-seed", type=int, default=None,
+                    help="parameter update: seed of the mirror draws (default TRAIN_MIRROR_SEED = 0)")
     return ap
+
+
+def _set_mirror_options(args):
+    """--mirror-augment / --mirror-seed onto train_network's constants (the stages read them at call time)."""
+    from . import train_network as tn
+    if args.mirror_augment:
+        tn.TRAIN_MIRROR = True
+    if args.mirror_seed is not None:
+        tn.TRAIN_MIRROR_SEED = args.mirror_seed
 
 
 def main(argv=None):
@@ -188,6 +201,7 @@ def main(argv=None):
         sp.SP_ROOT_NOISE_ALPHA = args.root_noise_alpha
     if args.epochs is not None:
         tn.NUM_EPOCH = args.epochs
+    _set_mirror_options(args)
     if args.eval_games is not None:
         en.EN_GAME_COUNT = args.eval_games
     try:

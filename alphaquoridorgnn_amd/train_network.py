@@ -19,6 +19,10 @@ from .pv_network_gnn import STATE_DICT_KEYS, HIDDEN_DIM, NUM_FEATURES, load_netw
 NUM_EPOCH = 100    # train_network.py:14
 BATCH_SIZE = 128   # train_network.py:15
 LEARNING_RATE = 0.001   # train_network.py:56
+# Mirror-symmetry augmentation (the reference has none): every epoch trains on each position either as recorded or mirrored left
+# to right, drawn per (TRAIN_MIRROR_SEED, epoch, position) -- one fused gather + flip launch in place of the epoch's three gathers.
+TRAIN_MIRROR = False      # False = off: the reference's epochs
+TRAIN_MIRROR_SEED = 0
 
 
 def load_data():
@@ -38,6 +42,76 @@ def lr_lambda(epoch):
     return 1.0
 
 
+def draw_mirror_flips(seed, epoch, n):
+    """The flips of source rows 0 .. n-1 in epoch `epoch` under `seed`, uint8 [n] -- the seeded draw of aqg_augment_gather in numpy
+    (include/aqgnn.h): row r is mirrored iff f(K(seed, epoch), r) < 0.5 with the counter-based generator of agents.draw_uniforms.
+    A pure function of (seed, epoch, r): a prefix of a longer draw is the shorter draw."""
+    from .agents import draw_uniforms
+    return (draw_uniforms(seed, epoch, n) < 0.5).astype(np.uint8)
+
+
+def _mirror_arguments(mirror, rows, dev):
+    """(flips tensor or None, use_seed, seed, epoch) of a `mirror` argument: a uint8 [rows] device table indexed by source row, or
+    (seed, epoch).  Shapes and types only -- nothing is read back from the device."""
+    if isinstance(mirror, torch.Tensor):
+        if mirror.dtype != torch.uint8 or mirror.dim() != 1 or mirror.shape[0] != rows or mirror.device != dev:
+            raise ValueError(f"a mirror table is a uint8 [{rows}] tensor on {dev}, one entry per source row")
+        return mirror.contiguous(), 0, 0, 0
+    try:
+        seed, epoch = mirror
+        seed, epoch = int(seed), int(epoch)
+    except (TypeError, ValueError):
+        raise ValueError("mirror is None, a uint8 device table indexed by source row, or (seed, epoch)") from None
+    if epoch < 0:
+        raise ValueError("mirror: the epoch must be >= 0")
+    return None, 1, seed & ((1 << 64) - 1), epoch
+
+
+def _augment_launch(board_size, states72, pi, z, order, mirror):
+    """The fused launch on contiguous device tensors of one device: (out72, out_pi, out_z), None where the input is None.  order:
+    int64 source rows, NOT checked here (augment_gather checks them); mirror: as _mirror_arguments, or None for a plain gather."""
+    src = next(x for x in (states72, pi, z) if x is not None)
+    dev, rows = src.device, int(src.shape[0])
+    n = rows if order is None else int(order.shape[0])
+    flips, use_seed, seed, epoch = (None, 0, 0, 0) if mirror is None else _mirror_arguments(mirror, rows, dev)
+    outs = [None if x is None else torch.empty((n,) + tuple(x.shape[1:]), dtype=x.dtype, device=dev) for x in (states72, pi, z)]
+    A = board_size ** 2 + 2 * (board_size - 1) ** 2
+    _lib.check(_lib.load().aqg_augment_gather(board_size, A, _lib.ptr(states72), _lib.ptr(pi), _lib.ptr(z), _lib.ptr(order),
+                                              _lib.ptr(flips), use_seed, seed, epoch, n, _lib.ptr(outs[0]), _lib.ptr(outs[1]),
+                                              _lib.ptr(outs[2]), _lib.stream_ptr(dev)), "aqg_augment_gather")
+    return tuple(outs)
+
+
+def augment_gather(states72, pi, z, order=None, flips=None, seed=None, epoch=0, board_size=BOARD_SIZE):
+    """Gather and mirror training rows in one launch (aqg_augment_gather): output row i is source row order[i] (None: row i),
+    mirrored iff flips[that source row] is set -- or, with flips None and a seed, iff draw_mirror_flips(seed, epoch, rows) says so.
+    With neither it is a plain gather.  states72 uint8 [rows,72], pi float32 [rows,A], z float32 [rows]: device tensors, each may be
+    None (and so is its output).  Returns (out72, out_pi, out_z), freshly allocated, with len(order) rows (any number, none
+    included).  order is checked against the row count with one host read."""
+    given = [x for x in (states72, pi, z) if x is not None]
+    if not given:
+        raise ValueError("augment_gather: at least one of states72, pi, z is needed")
+    dev = _lib.require_gpu(given[0].device)
+    rows = int(given[0].shape[0])
+    A = board_size ** 2 + 2 * (board_size - 1) ** 2
+    for x, name, dtype, tail in ((states72, "states72", torch.uint8, (72,)), (pi, "pi", torch.float32, (A,)), (z, "z", torch.float32, ())):
+        if x is not None and (x.device != dev or x.dtype != dtype or tuple(x.shape) != (rows,) + tail):
+            raise ValueError(f"augment_gather: {name} must be a {dtype} {[rows, *tail]} tensor on {dev} ({board_size}x{board_size} board)")
+    states72, pi, z = (None if x is None else x.contiguous() for x in (states72, pi, z))
+    if order is not None:
+        order = order.to(dev, torch.int64).contiguous()
+        if order.dim() != 1:
+            raise ValueError("augment_gather: order is a 1-D tensor of source rows")
+        if order.numel():
+            lo, hi = torch.stack((order.min(), order.max())).tolist()          # the one host read
+            if lo < 0 or hi >= rows:
+                raise ValueError(f"augment_gather: order holds a row outside 0..{rows - 1}")
+    if flips is not None and seed is not None:
+        raise ValueError("augment_gather: give flips or seed, not both")
+    mirror = flips if flips is not None else None if seed is None else (seed, epoch)
+    return _augment_launch(board_size, states72, pi, z, order, mirror)
+
+
 class _Trainer:
     """What GNNTrainer and GeneralTrainer share: the Adam state and the flat gradient buffer, step() (single process or data
     parallel), outputs() and run_epoch().  A subclass provides the library calls (_call, _call_epoch), the batch-mean losses of a
@@ -53,9 +127,11 @@ class _Trainer:
         self.adam_m = [torch.zeros_like(p) for p in self.params]
         self.adam_v = [torch.zeros_like(p) for p in self.params]
 
-    def step(self, states72, pi_target, z_target, lr=LEARNING_RATE, update=True, group=None):
+    def step(self, states72, pi_target, z_target, lr=LEARNING_RATE, update=True, group=None, mirror=None):
         """One optimisation step.  states72 uint8 [B,72], pi_target float32 [B,A], z_target float32 [B] (device tensors).
         Returns (policy_loss, value_loss) as 0-dim device tensors -- no host synchronisation.
+        mirror (None = off): a uint8 [B] device table, or (seed, epoch) for the seeded draw keyed by the row's index in THIS batch:
+        the step trains on the batch with those rows mirrored left to right (one launch in front of it, aqg_augment_gather).
 
         Data parallel (torch.distributed initialised, world > 1): every rank passes ITS shard of the global batch; the
         local mean-loss gradients are weighted by B_local / B_global, summed with ONE all-reduce of the flat gradient buffer
@@ -68,6 +144,8 @@ class _Trainer:
         states72 = states72.to(self.dev, torch.uint8).contiguous()
         pi_target = pi_target.to(self.dev, torch.float32).contiguous()
         z_target = z_target.to(self.dev, torch.float32).contiguous()
+        if mirror is not None:
+            states72, pi_target, z_target = _augment_launch(self.N, states72, pi_target, z_target, None, mirror)
         world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         if update:
             self.step_count += 1
@@ -97,10 +175,15 @@ class _Trainer:
         """(policy [B,A], value [B]) of the last step's forward pass."""
         return self.ws["pol"][:B], self.ws["val"][:B]
 
-    def run_epoch(self, states72, pi_target, z_target, order, lr=LEARNING_RATE, batch=None, pre_shuffle=True):
+    def run_epoch(self, states72, pi_target, z_target, order, lr=LEARNING_RATE, batch=None, pre_shuffle=True, mirror=None):
         """All optimisation steps of one epoch in ONE library call (single process): step i trains on the positions
         order[i*batch:(i+1)*batch] of the resident device arrays (train_network.py:72-95; the short last batch is kept, as
-        DataLoader does).  Returns the epoch's summed (policy_loss, value_loss) as a device tensor [2] -- no host sync."""
+        DataLoader does).  Returns the epoch's summed (policy_loss, value_loss) as a device tensor [2] -- no host sync.
+        mirror (None = off): a uint8 device table with one entry per row of states72, or (seed, epoch) for the seeded draw
+        (draw_mirror_flips): the rows it selects are trained on mirrored left to right.  The epoch's three gathers become one fused
+        gather + flip launch (aqg_augment_gather), so a mirrored epoch needs pre_shuffle=True."""
+        if mirror is not None and not pre_shuffle:
+            raise ValueError("a mirrored epoch trains on the shuffled and flipped copies: it needs pre_shuffle=True")
         batch = self.max_batch if batch is None else int(batch)
         if batch > self.max_batch:
             raise ValueError("batch larger than the trainer's workspace")
@@ -115,7 +198,9 @@ class _Trainer:
         states72 = states72.to(self.dev, torch.uint8).contiguous()
         pi_target = pi_target.to(self.dev, torch.float32).contiguous()
         z_target = z_target.to(self.dev, torch.float32).contiguous()
-        if pre_shuffle:
+        if mirror is not None:
+            states72, pi_target, z_target = _augment_launch(self.N, states72, pi_target, z_target, order, mirror)
+        elif pre_shuffle:
             states72, pi_target, z_target = (x.index_select(0, order).contiguous() for x in (states72, pi_target, z_target))
         self.t.batch, self.t.step, self.t.lr = batch, self.step_count + 1, float(lr)
         self._call_epoch(states72, pi_target, z_target, None if pre_shuffle else order, n, sums)
@@ -314,18 +399,18 @@ class CNNTrainer(_Trainer):
         t.policy, t.value, t.loss, t.loss_mean = (self.ws[k].data_ptr() for k in ("pol", "val", "loss", "loss_mean"))
         t.workspace, t.workspace_floats = self.ws["workspace"].data_ptr(), nws
 
-    def step(self, states72, pi_target, z_target, lr=LEARNING_RATE, update=True, group=None):
+    def step(self, states72, pi_target, z_target, lr=LEARNING_RATE, update=True, group=None, mirror=None):
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
             raise ValueError("CNNTrainer.step: data-parallel CNN training would need synchronised BatchNorm, which is not built; "
                              "train on one rank")
-        out = super().step(states72, pi_target, z_target, lr=lr, update=update, group=group)
+        out = super().step(states72, pi_target, z_target, lr=lr, update=update, group=group, mirror=mirror)
         if int(states72.shape[0]) > 0:
             self._forwarded(1)
         return out
 
-    def run_epoch(self, states72, pi_target, z_target, order, lr=LEARNING_RATE, batch=None, pre_shuffle=True):
-        sums = super().run_epoch(states72, pi_target, z_target, order, lr=lr, batch=batch, pre_shuffle=pre_shuffle)
+    def run_epoch(self, states72, pi_target, z_target, order, lr=LEARNING_RATE, batch=None, pre_shuffle=True, mirror=None):
+        sums = super().run_epoch(states72, pi_target, z_target, order, lr=lr, batch=batch, pre_shuffle=pre_shuffle, mirror=mirror)
         batch = self.max_batch if batch is None else int(batch)
         self._forwarded((int(order.shape[0]) + batch - 1) // batch)
         return sums
@@ -417,14 +502,18 @@ def _train_loop(rank, world):
                 perm_h = perm.cpu()
                 dist.broadcast(perm_h, src=0)
                 perm = perm_h.to(dev)
+        mirror = (TRAIN_MIRROR_SEED, epoch) if TRAIN_MIRROR else None
         if world == 1:
-            epoch_policy_loss, epoch_value_loss = trainer.run_epoch(s, p, v, perm, lr=lr)
+            epoch_policy_loss, epoch_value_loss = trainer.run_epoch(s, p, v, perm, lr=lr, mirror=mirror)
         else:
             epoch_policy_loss = torch.zeros((), device=dev)
             epoch_value_loss = torch.zeros((), device=dev)
             for i in range(0, n, BATCH_SIZE):
                 idx = perm[i:i + BATCH_SIZE][rank::world]
-                pl, vl = trainer.step(s[idx], p[idx], v[idx], lr=lr)
+                if mirror is None:
+                    pl, vl = trainer.step(s[idx], p[idx], v[idx], lr=lr)
+                else:       # this rank's slice, gathered and flipped by SOURCE row under the key every rank shares: no collective
+                    pl, vl = trainer.step(*_augment_launch(model.board_size, s, p, v, idx.contiguous(), mirror), lr=lr)
                 epoch_policy_loss += pl
                 epoch_value_loss += vl
         if rank == 0:
@@ -470,7 +559,8 @@ def _train_cnn_loop():
     for epoch in range(NUM_EPOCH):
         lr = LEARNING_RATE * lr_lambda(epoch)                                      # LambdaLR, stepped once per epoch (:98)
         perm = torch.randperm(n, device=dev)                                    # DataLoader(shuffle=True), last batch kept
-        epoch_policy_loss, epoch_value_loss = trainer.run_epoch(s, p, v, perm, lr=lr)
+        epoch_policy_loss, epoch_value_loss = trainer.run_epoch(s, p, v, perm, lr=lr,
+                                                                 mirror=(TRAIN_MIRROR_SEED, epoch) if TRAIN_MIRROR else None)
         print(f"\rEpoch {epoch + 1}/{NUM_EPOCH} | Policy Loss: {float(epoch_policy_loss):.4f} | Value Loss: {float(epoch_value_loss):.4f}", end='')
     print('')
     torch.save(model.state_dict(), PV_NETWORK_PATH + 'latest.pth')

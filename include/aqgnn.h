@@ -632,6 +632,33 @@ int aqg_cnn_train_step(const aqg_cnn_train* t_host, const uint8_t* states72, con
 int aqg_cnn_train_steps(const aqg_cnn_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target,
                         const int64_t* order, long long positions, float* loss_sums, void* stream);
 
+/* ------------------------------------------------------------------ training augmentation (additive to ABI 15; the reference has none)
+ *
+ * Quoridor is symmetric under the left-right mirror of the board: column y -> N - 1 - y in each player's own frame.  The mirror of a
+ * state72 record: bytes 0 and 2 (the positions p) become (p / N) * N + (N - 1 - p % N); wall slot i < NW moves to
+ * (i / W) * W + (W - 1 - i % W), W = N - 1, with its value; every other byte is copied.  The mirror of an action: a pawn action by the
+ * position formula, a horizontal / vertical wall action by the slot formula inside its own block; a policy row is permuted
+ * accordingly, out[mirror(a)] = in[a].  z is unchanged.  The map is an involution.  A position byte >= N * N has no image and is
+ * copied through; no record byte is used as an address.
+ *
+ * aqg_augment_gather: the shuffle of an epoch and the flips in one launch (csrc/augment.hip).  Output row i < n is source row
+ *   r = order[i] (order == NULL: r = i), mirrored iff the flip of r is set:
+ *     flips != NULL: flips[r] != 0 (a u8 table indexed by SOURCE row);
+ *     flips == NULL, use_seed != 0: f(K(seed, epoch), r) < 0.5 with K and f of the baseline agents' counter-based generator (below) --
+ *       a row's orientation depends on (seed, epoch, source row) alone, never on the shuffle, the batch size or the rank;
+ *       train_network.draw_mirror_flips(seed, epoch, rows) is the same function in numpy;
+ *     neither: a plain gather.
+ *   states72 [rows,72] u8 -> out72 [n,72]; pi [rows,policy_size] f32 -> out_pi [n,policy_size], copied as bit patterns; z [rows] f32 ->
+ *   out_z [n].  Each input may be NULL together with its output (a states-only or policy-only mirror).  order entries are source rows
+ *   the CALLER has checked against its row count; they are not checked here.  Errors: a board_size outside {3,5,7,9}, a policy_size
+ *   that is not the board's A, n < 0, an input without its output or the reverse, an output that overlaps an input.  n == 0 returns 0
+ *   without looking at the pointers.  The overlap check assumes of a source only what is certain -- n rows when order is NULL, one
+ *   row when it is given, since the source's row count is not an argument -- so it never refuses a legitimate call; the outputs must
+ *   lie outside the WHOLE source, and keeping them out of the rows behind that is the caller's part. */
+int aqg_augment_gather(int board_size, int policy_size, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
+                       const uint8_t* flips, int use_seed, uint64_t seed, uint64_t epoch, int n, uint8_t* out72, float* out_pi,
+                       float* out_z, void* stream);
+
 /* ------------------------------------------------------------------ CPU baseline agents (agents.py) -- HOST pointers, host code */
 
 /* The reference's baseline opponents (agents.py:14-214) are CPU code; so are these: the host instantiation of the rule header
