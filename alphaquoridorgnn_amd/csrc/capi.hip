@@ -377,4 +377,11 @@ int aqg_augment_gather(int board_size, int policy_size, const uint8_t* states72,
                                  (hipStream_t)stream);
 }
 
+int aqg_replay_append(int board_size, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8,
+                      const float* pi, const float* z_f32, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
+                      float* ring_z, void* stream) {
+    return launch_replay_append(board_size, policy_size, states72, visits, z_i8, pi, z_f32, n, capacity, head, ring72, ring_pi, ring_z,
+                                (hipStream_t)stream);
+}
+
 }  // extern "C"

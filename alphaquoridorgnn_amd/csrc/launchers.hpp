@@ -150,4 +150,9 @@ int launch_augment_gather(int N, int policy_size, const uint8_t* states72, const
                           const uint8_t* flips, int use_seed, uint64_t seed, uint64_t epoch, int n, uint8_t* out72, float* out_pi,
                           float* out_z, hipStream_t st);
 
+// ---- replay.hip
+int launch_replay_append(int N, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8, const float* pi,
+                         const float* z_f32, int n, int capacity, int head, uint8_t* ring72, float* ring_pi, float* ring_z,
+                         hipStream_t st);
+
 }  // namespace aqg

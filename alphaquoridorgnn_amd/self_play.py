@@ -24,6 +24,10 @@ SP_TEMPERATURE = 1.0  # Temperature parameter for Boltzmann distribution (self_p
 # Root exploration noise (the reference has none; engine.BatchedSelfPlay): p' = (1 - eps) p + eps Dir(alpha) at every move's root.
 SP_ROOT_NOISE_EPS = 0.0      # 0 = off: the reference's games
 SP_ROOT_NOISE_ALPHA = None   # None = 10 / (N^2 + 2 (N - 1)^2), the "10 / typical number of moves" rule
+# Replay window (the reference has none; replay.ReplayWindow): every rank appends the gathered generation to SP_REPLAY, straight from
+# the engine's device tensors, for train_network.TRAIN_WINDOW to train on.  The .history file stays the reference's hand-over.
+SP_REPLAY = None             # None = off
+SP_WRITE_HISTORY = True      # False (needs a window): rank 0 writes no file
 
 
 def first_player_value(ended_state):
@@ -103,6 +107,8 @@ def self_play(model=None, games=None, seed=None):
     """Perform self-play games and save the training data (self_play.py:71-95).  `seed` (tests) fixes the uniform
     stream; by default every call draws a fresh one, like the reference's unseeded np.random.choice."""
     import torch.distributed as dist
+    if not SP_WRITE_HISTORY and SP_REPLAY is None:
+        raise ValueError("SP_WRITE_HISTORY = False without a replay window (SP_REPLAY) would throw the generation away")
     if model is None:
         model = load_network(PV_NETWORK_PATH + 'best.pth')       # GNNNetwork (prep_for_inference's path), or the network best.pth holds
         if isinstance(model, (GNNNetwork, CNNNetwork)) and torch.cuda.is_available():
@@ -133,8 +139,10 @@ def self_play(model=None, games=None, seed=None):
     else:
         st, vis, z = gather_history(st, vis, z)
     print('')
+    if SP_REPLAY is not None:
+        SP_REPLAY.append_counts(st, vis, z)          # every rank: the gathered rows are identical on all of them
     path = None
-    if rank == 0:
+    if rank == 0 and SP_WRITE_HISTORY:
         path = write_data(_history_rows(st, vis, z, BOARD_SIZE))
     if distributed:
         dist.barrier()          # no rank may go on to train_network.load_data() before rank 0 has finished the file

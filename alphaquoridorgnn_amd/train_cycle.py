@@ -169,7 +169,41 @@ def _parser():
                     help="parameter update: train every epoch on positions mirrored left to right at random (default TRAIN_MIRROR = False: off)")
     ap.add_argument("--mirror-seed", type=int, default=None,
                     help="parameter update: seed of the mirror draws (default TRAIN_MIRROR_SEED = 0)")
+    ap.add_argument("--replay-generations", type=int, default=0,
+                    help="train on a replay window of the newest K self-play generations, resident on the GPU (default 0: off, the "
+                         "newest .history file alone); a cycle that finds .history files in ./data resumes from the newest K")
+    ap.add_argument("--replay-rows", type=int, default=None,
+                    help="rows of the replay window's ring (default: K * 1.5 * the first generation's rows)")
+    ap.add_argument("--epoch-rows", type=int, default=None,
+                    help="parameter update: rows an epoch trains on, drawn afresh from the window by every epoch's shuffle (default "
+                         "TRAIN_EPOCH_ROWS = None: all of them)")
+    ap.add_argument("--no-history-file", action="store_true",
+                    help="self-play: write no .history file (needs --replay-generations; default SP_WRITE_HISTORY = True)")
     return ap
+
+
+def _set_replay_options(args):
+    """--replay-generations / --replay-rows / --epoch-rows / --no-history-file onto self_play's and train_network's hooks: one
+    ReplayWindow on this rank's GPU that self-play fills and the parameter update trains on, preloaded from the newest K .history
+    files of ./data, oldest first.  Returns the window (None when off)."""
+    from pathlib import Path
+    from . import self_play as sp, train_network as tn
+    from .replay import ReplayWindow
+    if args.epoch_rows is not None:
+        tn.TRAIN_EPOCH_ROWS = args.epoch_rows
+    if args.replay_generations < 0:
+        raise ValueError("--replay-generations must be >= 0")
+    if args.replay_generations == 0:
+        if args.no_history_file or args.replay_rows is not None:
+            raise ValueError("--no-history-file and --replay-rows need --replay-generations K >= 1")
+        return None
+    window = ReplayWindow(constants.BOARD_SIZE, max_generations=args.replay_generations, capacity_rows=args.replay_rows,
+                          device=aqd.device())
+    window.extend_from_files(sorted(Path('./data').glob('*.history'))[-args.replay_generations:])
+    sp.SP_REPLAY = tn.TRAIN_WINDOW = window
+    if args.no_history_file:
+        sp.SP_WRITE_HISTORY = False
+    return window
 
 
 def _set_mirror_options(args):
@@ -202,6 +236,7 @@ def main(argv=None):
     if args.epochs is not None:
         tn.NUM_EPOCH = args.epochs
     _set_mirror_options(args)
+    _set_replay_options(args)
     if args.eval_games is not None:
         en.EN_GAME_COUNT = args.eval_games
     try:

@@ -23,6 +23,12 @@ LEARNING_RATE = 0.001   # train_network.py:56
 # to right, drawn per (TRAIN_MIRROR_SEED, epoch, position) -- one fused gather + flip launch in place of the epoch's three gathers.
 TRAIN_MIRROR = False      # False = off: the reference's epochs
 TRAIN_MIRROR_SEED = 0
+# Replay window (the reference trains on the newest file alone; replay.ReplayWindow): the rows of the last generations, resident on
+# the GPU.  An epoch shuffles the window's valid slots; with the mirror on, a flip is keyed by SOURCE row, which for a window is the
+# ring slot (so a row keeps its draw for as long as it stays in the ring, and a file route's row i is keyed by i).
+TRAIN_WINDOW = None        # a ReplayWindow (self_play.SP_REPLAY fills it); None or empty = the file route
+TRAIN_GENERATIONS = 1      # K > 1 without a window: a temporary window over the newest K .history files
+TRAIN_EPOCH_ROWS = None    # E: an epoch trains on the first min(E, n) rows of its shuffle, so an update's cost does not grow with K
 
 
 def load_data():
@@ -31,6 +37,37 @@ def load_data():
     history_path = sorted(Path('./data').glob('*.history'))[-1]
     with history_path.open(mode='rb') as f:
         return pickle.load(f)
+
+
+def _training_rows(dev, board_size):
+    """(s, p, v, index) an update trains on, on `dev`: uint8 [rows,72] records, float32 [rows,A] policy and [rows] value targets, and
+    the int64 rows of them that are valid, oldest first -- or None when all are (the file route).  A non-empty TRAIN_WINDOW gives its
+    rings and index(); TRAIN_GENERATIONS = K > 1 without one a temporary window over the newest K files; otherwise the newest file
+    (train_network.py:19-23,:31-39)."""
+    from .replay import ReplayWindow
+    window = TRAIN_WINDOW if TRAIN_WINDOW is not None and len(TRAIN_WINDOW) > 0 else None
+    if window is None and TRAIN_GENERATIONS > 1:
+        window = ReplayWindow(board_size, max_generations=TRAIN_GENERATIONS, device=dev)
+        window.extend_from_files(sorted(Path('./data').glob('*.history'))[-TRAIN_GENERATIONS:])
+    if window is not None:
+        if window.board_size != board_size:
+            raise ValueError(f"the replay window holds {window.board_size}x{window.board_size} rows; the network plays "
+                             f"{board_size}x{board_size}")
+        s, p, v = (x.to(dev) for x in window.tensors())
+        return s, p, v, window.index().to(dev)
+    history = load_data()
+    s, p, v = zip(*history)
+    s = torch.from_numpy(pack_states(s, board_size)).to(dev)                       # uint8 [n,72]
+    p = torch.tensor(np.array(p), dtype=torch.float32, device=dev)                 # policy targets
+    v = torch.tensor(np.array(v), dtype=torch.float32, device=dev)                 # value targets
+    return s, p, v, None
+
+
+def _epoch_order(perm, index):
+    """The rows an epoch trains on, in order, from its shuffle of 0 .. n-1: the first TRAIN_EPOCH_ROWS of it, as rows of the arrays."""
+    if TRAIN_EPOCH_ROWS is not None:
+        perm = perm[:max(int(TRAIN_EPOCH_ROWS), 0)]
+    return perm if index is None else index[perm]
 
 
 def lr_lambda(epoch):
@@ -485,12 +522,8 @@ def _train_loop(rank, world):
     from . import distributed as aqd
     dev = aqd.device()                                                             # this rank's GPU, explicitly
     model = load_network(PV_NETWORK_PATH + 'best.pth', dev)                       # GNNNetwork, or the shape best.pth holds
-    history = load_data()
-    s, p, v = zip(*history)
-    s = torch.from_numpy(pack_states(s, model.board_size)).to(dev)                # uint8 [n,72]
-    p = torch.tensor(np.array(p), dtype=torch.float32, device=dev)                 # policy targets
-    v = torch.tensor(np.array(v), dtype=torch.float32, device=dev)                 # value targets
-    n = s.shape[0]
+    s, p, v, index = _training_rows(dev, model.board_size)
+    n = s.shape[0] if index is None else index.shape[0]
     trainer = trainer_for(model, max_batch=BATCH_SIZE)
     for epoch in range(NUM_EPOCH):
         lr = LEARNING_RATE * lr_lambda(epoch)                                      # LambdaLR, stepped once per epoch (:98)
@@ -503,13 +536,14 @@ def _train_loop(rank, world):
                 dist.broadcast(perm_h, src=0)
                 perm = perm_h.to(dev)
         mirror = (TRAIN_MIRROR_SEED, epoch) if TRAIN_MIRROR else None
+        order = _epoch_order(perm, index)
         if world == 1:
-            epoch_policy_loss, epoch_value_loss = trainer.run_epoch(s, p, v, perm, lr=lr, mirror=mirror)
+            epoch_policy_loss, epoch_value_loss = trainer.run_epoch(s, p, v, order, lr=lr, mirror=mirror)
         else:
             epoch_policy_loss = torch.zeros((), device=dev)
             epoch_value_loss = torch.zeros((), device=dev)
-            for i in range(0, n, BATCH_SIZE):
-                idx = perm[i:i + BATCH_SIZE][rank::world]
+            for i in range(0, int(order.shape[0]), BATCH_SIZE):
+                idx = order[i:i + BATCH_SIZE][rank::world]
                 if mirror is None:
                     pl, vl = trainer.step(s[idx], p[idx], v[idx], lr=lr)
                 else:       # this rank's slice, gathered and flipped by SOURCE row under the key every rank shares: no collective
@@ -549,17 +583,13 @@ def _train_cnn_loop():
     from .pv_network_cnn import load_network as load_cnn
     dev = aqd.device()
     model = load_cnn(PV_NETWORK_PATH + 'best.pth', dev)
-    history = load_data()
-    s, p, v = zip(*history)
-    s = torch.from_numpy(pack_states(s, model.board_size)).to(dev)                # uint8 [n,72]
-    p = torch.tensor(np.array(p), dtype=torch.float32, device=dev)
-    v = torch.tensor(np.array(v), dtype=torch.float32, device=dev)
-    n = s.shape[0]
+    s, p, v, index = _training_rows(dev, model.board_size)
+    n = s.shape[0] if index is None else index.shape[0]
     trainer = CNNTrainer(model, max_batch=BATCH_SIZE)
     for epoch in range(NUM_EPOCH):
         lr = LEARNING_RATE * lr_lambda(epoch)                                      # LambdaLR, stepped once per epoch (:98)
         perm = torch.randperm(n, device=dev)                                    # DataLoader(shuffle=True), last batch kept
-        epoch_policy_loss, epoch_value_loss = trainer.run_epoch(s, p, v, perm, lr=lr,
+        epoch_policy_loss, epoch_value_loss = trainer.run_epoch(s, p, v, _epoch_order(perm, index), lr=lr,
                                                                  mirror=(TRAIN_MIRROR_SEED, epoch) if TRAIN_MIRROR else None)
         print(f"\rEpoch {epoch + 1}/{NUM_EPOCH} | Policy Loss: {float(epoch_policy_loss):.4f} | Value Loss: {float(epoch_value_loss):.4f}", end='')
     print('')

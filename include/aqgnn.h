@@ -659,6 +659,28 @@ int aqg_augment_gather(int board_size, int policy_size, const uint8_t* states72,
                        const uint8_t* flips, int use_seed, uint64_t seed, uint64_t epoch, int n, uint8_t* out72, float* out_pi,
                        float* out_z, void* stream);
 
+/* ------------------------------------------------------------------ replay window (additive to ABI 15; the reference trains on one file)
+ *
+ * A ring of training rows that stays on the device: three arrays of `capacity` rows, ring72 u8 [capacity,72], ring_pi f32 [capacity,A],
+ * ring_z f32 [capacity] -- what the trainers' entry points read.  Which slots hold rows, and of which generation, is the host's
+ * bookkeeping (replay.py).
+ *
+ * aqg_replay_append: one launch (csrc/replay.hip) writes source row i, 0 <= i < n, into ring slot (head + i) % capacity.
+ *   The 72 record bytes are copied verbatim; no byte is interpreted or used as an address.
+ *   Counts form (visits and z_i8 given, pi and z_f32 NULL) -- a generation as the engine leaves it (hist_visits, read as UNSIGNED
+ *     16-bit, and the i8 outcomes): tot = the exact integer sum of the row's A counts; ring_pi[j] = f32(f64(v_j) / f64(tot)), and A
+ *     zeros when tot == 0; ring_z = (float)z.  Those are the bits of the .history route (v / tot in float64, then
+ *     torch.tensor(..., dtype=float32)).  The kernel takes the correctly rounded f32 quotient f32(v_j) / f32(tot), which has the same
+ *     bits for every tot < 2^24 (A * 65,535 is below that): an integer quotient this small is neither an f32 midpoint nor within 2^-53
+ *     relative of one, so rounding once or twice agrees.  The unit is never built with a fast-math flag.
+ *   Rows form (pi and z_f32 given, visits and z_i8 NULL) -- finished rows, e.g. of a .history file: a plain copy into the ring.
+ *   Refused on the host, before any launch (-1, aqg_last_error): an unsupported board size, a policy_size that is not the board's A,
+ *   n < 0, capacity < 1, head outside 0 .. capacity - 1, n > capacity, neither or both forms (or half of one), states72 or a ring
+ *   NULL, a ring (capacity rows) that overlaps a source (n rows).  n == 0 returns 0 without looking at the pointers. */
+int aqg_replay_append(int board_size, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8,
+                      const float* pi, const float* z_f32, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
+                      float* ring_z, void* stream);
+
 /* ------------------------------------------------------------------ CPU baseline agents (agents.py) -- HOST pointers, host code */
 
 /* The reference's baseline opponents (agents.py:14-214) are CPU code; so are these: the host instantiation of the rule header
