@@ -24,7 +24,12 @@ for f in legal_mask board_featuriser gcn_pack gcn_trunk_split gcn_trunk_exact gc
   for pair in ${AQG_REPLACE:-}; do
     if [ "${pair%%=*}" = "$f" ]; then src=${pair#*=}; replaced=$((replaced + 1)); fi
   done
-  $HIPCC $FLAGS -I. -c "$src" -o "${OBJDIR}/aqg_$f.o" &
+  if [ "$f" = mcts ]; then
+    # the step kernel's resource lines are kept: the budget check below reads them
+    $HIPCC $FLAGS -Rpass-analysis=kernel-resource-usage -I. -c "$src" -o "${OBJDIR}/aqg_$f.o" 2> "${OBJDIR}/aqg_$f.remarks" &
+  else
+    $HIPCC $FLAGS -I. -c "$src" -o "${OBJDIR}/aqg_$f.o" &
+  fi
   pids+=($!)
   objs+=("${OBJDIR}/aqg_$f.o")
 done
@@ -38,6 +43,20 @@ failed=0
 for pid in "${pids[@]}"; do
   wait "$pid" || failed=1
 done
-if [ "$failed" -ne 0 ]; then echo "build.sh: a compile job failed" >&2; exit 1; fi
+if [ "$failed" -ne 0 ]; then
+  grep -v "remark:" "${OBJDIR}/aqg_mcts.remarks" >&2 || true      # whatever mcts.hip's compile said besides the remarks
+  echo "build.sh: a compile job failed" >&2; exit 1
+fi
+grep -A3 "warning:" "${OBJDIR}/aqg_mcts.remarks" >&2 || true
+# Register budget of the step kernels with the heads inside (engine_step_fast_kernel<9, CACHE, true>): at most
+# 128 VGPRs and no scratch, or a step workgroup no longer fits beside a trunk workgroup.  The order of their load rounds is steered
+# by scheduling barriers that a compiler update may treat differently: such a build fails here instead of running slower.
+# (The kernels' launch bound already caps them at 128 registers -- the compiler spills rather than exceed it -- so the scratch
+#  test is the one that fires; the register test guards the day the launch bound is changed.)
+awk '/Function Name:/ { k = ($0 ~ /engine_step_fast_kernelILi9ELb[01]ELb1E/) ? $0 : "" }
+     k != "" && / VGPRs: / { n++; v = $0; sub(/.* VGPRs: /, "", v); if (v + 0 > 128) { print "build.sh: over 128 VGPRs: " k > "/dev/stderr"; bad = 1 } }
+     k != "" && /ScratchSize/ { v = $0; sub(/.*: /, "", v); if (v + 0 != 0) { print "build.sh: scratch in use: " k > "/dev/stderr"; bad = 1 } }
+     END { if (n != 2) { print "build.sh: expected two fused step kernels in the resource remarks, found " n + 0 > "/dev/stderr"; bad = 1 } exit bad }' \
+  "${OBJDIR}/aqg_mcts.remarks" || exit 1
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT" "${objs[@]}"
 echo "built $(realpath "$OUT")"

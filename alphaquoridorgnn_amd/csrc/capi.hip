@@ -23,6 +23,7 @@ int aqg_set_option(const char* name, int value) {
     if (name && !strcmp(name, "trunk_delay_min_boards")) { g_trunk_delay_min_boards = value; return 0; }
     if (name && !strcmp(name, "step_prio")) { g_step_prio = value & 3; return 0; }
     if (name && !strcmp(name, "step_waves")) { g_step_waves = value; return 0; }
+    if (name && !strcmp(name, "step_heads")) { g_step_heads = value ? 1 : 0; return 0; }
     if (name && !strcmp(name, "step_fast_depth")) { if (value < 0 || value > 61) return fail("step_fast_depth must be 0..61"); g_step_fast_depth = value; return 0; }
     if (name && !strcmp(name, "train_fused")) { if (value < 1 || value > 3) return fail("train_fused must be 1, 2 or 3"); g_train_fused = value; return 0; }
     if (name && !strcmp(name, "use_graph")) { g_use_graph = value ? 1 : 0; return 0; }

@@ -90,7 +90,7 @@ int launch_cnn_forward_planes(int N, const float* planes, int B, const aqg_cnn_n
                               hipStream_t st);
 
 // ---- mcts.hip
-extern int g_use_graph, g_step_waves, g_step_prio, g_step_fast_depth;
+extern int g_use_graph, g_step_waves, g_step_prio, g_step_fast_depth, g_step_heads;
 int set_trace_mcts(void* buf, unsigned int cap);
 int engine_reset(const aqg_engine& e, hipStream_t st);
 int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st);

@@ -22,14 +22,13 @@
 #include "../../include/aqgnn.h"
 #include "launchers.hpp"
 #include "counter_rng.hpp"
+#include "gcn_heads_split.hpp"
 #include <cfloat>
 
 // PUCT scores must be evaluated exactly as written (no fma contraction, IEEE divide/sqrt).
 #pragma clang fp contract(off)
 
 namespace aqg {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 int g_use_graph = 1;       // aqg_set_option("use_graph", 0) forces plain launches
 
@@ -302,34 +301,72 @@ int g_step_prio = 1;               // wave priority of the fast step kernel (0..
 int g_step_waves = 8;              // games (wavefronts) per workgroup of the fast step kernel (1, 2, 4 or 8).  Round 4: 8 -- at 96 registers two step
                                    // waves per SIMD fit beside one trunk workgroup, half as many workgroups: +0.5-0.8 % games/s at 2,048 and 16,384 games
 int g_step_fast_depth = 61;
+int g_step_heads = 1;              // option "step_heads": 1 = the expanding step launches of the 9x9 split network compute the heads of their own leaves
+                                   // (engine_step_fast_kernel<N, CACHE, true>; enqueue_sims then launches no gcn_heads_mm_kernel), 0 = three launches per simulation
 
-// CACHE: the evaluation cache's code is compiled in (its own kernel instantiation: the cache-less kernel carries none of it)
-template <int N, bool CACHE>
-__device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int lane, int do_expand, int do_select, int fast_depth,
-                                               float* __restrict__ polbuf /* this wave's 256 floats of LDS */, int list_sim) {
+// a packed 24-byte state from its three words (what load_state(base, 1, g) makes of them)
+__device__ __forceinline__ QState state_of_words(uint64_t q0, uint64_t q1, uint64_t m) {
+    QState s;
+    s.hw = q0; s.vw = q1;
+    s.ppos = (uint8_t)(m & 0xff); s.pwl = (uint8_t)((m >> 8) & 0xff);
+    s.epos = (uint8_t)((m >> 16) & 0xff); s.ewl = (uint8_t)((m >> 24) & 0xff);
+    s.plies = (uint16_t)((m >> 32) & 0xffff); s.pad = 0;
+    return s;
+}
+
+// Round 1 of a step (see above): everything whose address follows from (game, lane) alone, requested at once.
+struct StepRound1 {
+    int active, flag, depth_old, cnt_new, first_new, cslot, pnode;
+    float value;
+    // (plain members, no arrays: the struct must dissolve into registers in every instantiation -- and every member is a loaded value AS
+    //  IT ARRIVES, the packed states included: an instruction that reads one inside the loader would wait for the round right there)
+    uint64_t root_q0, root_q1, root_q2, leaf_q0, leaf_q1, leaf_q2;
+    uint32_t oa0, oa1, oa2;
+    float polr0, polr1, polr2, polr3;
+    NodeRec rootrec;
+    u32x4 hot0, hot1, hot2, cold0, cold1, cold2;
+};
+// HEADS: the step kernel has computed the leaves' policy rows itself (they are in LDS); what is left to fetch of e.policy is the
+// legal-ordered row of a leaf_flag 2 leaf (three lane rounds instead of the dense row's four)
+template <int N, bool CACHE, bool HEADS>
+__device__ __forceinline__ void step_round1(const aqg_engine& e, int g, int lane, int do_expand, StepRound1& r1) {
     constexpr int A = Geo<N>::A;
-    NodeRec* __restrict__ nodes = game_nodes(e, g);
-    int* path = e.path + (size_t)g * (e.sims + 2);
+    const NodeRec* __restrict__ nodes = game_nodes(e, g);
+    const int* path = e.path + (size_t)g * (e.sims + 2);
     const uint8_t* ord = e.legal_order + (size_t)g * MAX_LEGAL;
     const float* pol = e.policy + (size_t)g * A;
-    STEP_STAMP_DECL
-    // ---------------- round 1
-    const int active = e.game_active[g];
-    const QState s_loaded = load_state(e.root_state, 1, g);
-    int flag = 0, depth_old = 0, cnt_new = 0, first_new = 0;
+    r1.active = e.game_active[g];
+    const uint64_t* rq = reinterpret_cast<const uint64_t*>(e.root_state) + (size_t)g * 3;
+    r1.root_q0 = rq[0]; r1.root_q1 = rq[1]; r1.root_q2 = rq[2];
+    int flag = 0, depth_old = 0, cnt_new = 0, first_new = 0, cslot = -1, pnode = 0;
     float value = 0.f;
-    uint8_t oa[3] = {0, 0, 0};
-    int pnode = 0;
+    uint32_t oa[3] = {0u, 0u, 0u};
     float polr[4] = {0.f, 0.f, 0.f, 0.f};
-    // evaluation cache (aqgnn.h, ABI 10): a per-slot table of the positions this slot's games have already sent through the network
-    constexpr bool cache_on = CACHE;
-    int cslot = -1;
-    QState leaf_prev = s_loaded;      // the previous simulation's leaf (its key, when its evaluation goes into the table)
-    if (do_expand) {
+    r1.leaf_q0 = r1.leaf_q1 = r1.leaf_q2 = 0;       // the previous simulation's leaf (its key, when its evaluation goes into the table)
+    if (HEADS) {
+        // (always an expanding launch.  No branch around any load -- indices are clamped, and the consumer masks what a clamped index
+        //  fetched -- so that the compiler can COUNT the loads in flight: behind a divergent region its waits become s_waitcnt vmcnt(0),
+        //  and the heads' policy layer in front of the step would wait for this whole round)
         flag = e.leaf_flag[g]; depth_old = e.path_len[g]; cnt_new = e.legal_count[g]; first_new = e.node_count[g]; value = e.value[g];
-        if (cache_on) { cslot = e.eval_cache_slot[g]; leaf_prev = load_state(e.leaf_state, 1, g); }
+        if (CACHE) {
+            cslot = e.eval_cache_slot[g];
+            const uint64_t* lq = reinterpret_cast<const uint64_t*>(e.leaf_state) + (size_t)g * 3;
+            r1.leaf_q0 = lq[0]; r1.leaf_q1 = lq[1]; r1.leaf_q2 = lq[2];
+        }
+        static_assert(!HEADS || MAX_LEGAL <= A, "the legal-ordered row fits the dense one");
+        static_assert(128 < MAX_LEGAL && MAX_LEGAL <= 192, "lane rounds 0 and 1 lie inside the legal list, round 2 is masked by the consumer");
 #pragma unroll
-        for (int r = 0; r < 3; ++r) { const int i = lane + 64 * r; oa[r] = (i < MAX_LEGAL) ? ord[i] : (uint8_t)0; }
+        for (int r = 0; r < 3; ++r) { const int i = min(lane + 64 * r, MAX_LEGAL - 1); oa[r] = (uint32_t)ord[i]; polr[r] = pol[i]; }
+        pnode = path[min(lane, e.sims + 1)];
+    } else if (do_expand) {
+        flag = e.leaf_flag[g]; depth_old = e.path_len[g]; cnt_new = e.legal_count[g]; first_new = e.node_count[g]; value = e.value[g];
+        if (CACHE) {
+            cslot = e.eval_cache_slot[g];
+            const uint64_t* lq = reinterpret_cast<const uint64_t*>(e.leaf_state) + (size_t)g * 3;
+            r1.leaf_q0 = lq[0]; r1.leaf_q1 = lq[1]; r1.leaf_q2 = lq[2];
+        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r) { const int i = lane + 64 * r; oa[r] = (i < MAX_LEGAL) ? (uint32_t)ord[i] : 0u; }
         pnode = (lane < e.sims + 2) ? path[lane] : 0;
         if (e.prior_mode == 0) {
 #pragma unroll
@@ -339,7 +376,10 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
             for (int r = 0; r < 3; ++r) { const int i = lane + 64 * r; polr[r] = (i < MAX_LEGAL && i < A) ? pol[i] : 0.f; }
         }
     }
-    const NodeRec rootrec = nodes[0];
+    r1.flag = flag; r1.depth_old = depth_old; r1.cnt_new = cnt_new; r1.first_new = first_new; r1.cslot = cslot; r1.pnode = pnode; r1.value = value;
+    r1.oa0 = oa[0]; r1.oa1 = oa[1]; r1.oa2 = oa[2];
+    r1.polr0 = polr[0]; r1.polr1 = polr[1]; r1.polr2 = polr[2]; r1.polr3 = polr[3];
+    r1.rootrec = nodes[0];
     // (children travel as the record's two aligned 16-byte halves -- [2 i] = {w.lo, w.hi, p, action}, [2 i + 1] = {n, kids, q, cp} -- and
     //  stay vectors: as separate scalars their loop-carried copies were made behind an s_waitcnt at the descent loop's back edge)
     const u32x4* __restrict__ nhalf = reinterpret_cast<const u32x4*>(nodes);
@@ -349,6 +389,36 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
         const int i = min(1 + lane + 64 * r, e.node_cap - 1);
         cold[r] = nhalf[2 * i]; hot[r] = nhalf[2 * i + 1];
     }
+    r1.hot0 = hot[0]; r1.hot1 = hot[1]; r1.hot2 = hot[2]; r1.cold0 = cold[0]; r1.cold1 = cold[1]; r1.cold2 = cold[2];
+}
+
+// CACHE: the evaluation cache's code is compiled in (its own kernel instantiation: the cache-less kernel carries none of it)
+// HEADS: the kernel ran heads_body for the workgroup's leaves in front of this: a leaf_flag 1 leaf's softmax row is in `polbuf`
+// (dense, by action), its value in `head_value`; nothing of either came through global memory
+template <int N, bool CACHE, bool HEADS>
+__device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int lane, int do_expand, int do_select, int fast_depth,
+                                               float* __restrict__ polbuf /* this wave's 256 floats of LDS */, int list_sim,
+                                               const StepRound1& r1, float head_value) {
+    constexpr int A = Geo<N>::A;
+    NodeRec* __restrict__ nodes = game_nodes(e, g);
+    int* path = e.path + (size_t)g * (e.sims + 2);
+    STEP_STAMP_DECL
+    // ---------------- round 1 (step_round1)
+    const int active = r1.active;
+    const QState s_loaded = state_of_words(r1.root_q0, r1.root_q1, r1.root_q2);
+    int flag = r1.flag, depth_old = r1.depth_old, cnt_new = r1.cnt_new, first_new = r1.first_new;
+    float value = r1.value;
+    // (HEADS: its loader clamps indices instead of branching around loads)
+    const uint8_t oa[3] = {(uint8_t)r1.oa0, (uint8_t)r1.oa1, (uint8_t)((HEADS && lane + 128 >= MAX_LEGAL) ? 0u : r1.oa2)};
+    const int pnode = (HEADS && lane >= e.sims + 2) ? 0 : r1.pnode;
+    const float polr[4] = {r1.polr0, r1.polr1, r1.polr2, r1.polr3};
+    // evaluation cache (aqgnn.h, ABI 10): a per-slot table of the positions this slot's games have already sent through the network
+    constexpr bool cache_on = CACHE;
+    int cslot = r1.cslot;
+    const QState leaf_prev = (cache_on && do_expand) ? state_of_words(r1.leaf_q0, r1.leaf_q1, r1.leaf_q2) : s_loaded;
+    const NodeRec rootrec = r1.rootrec;
+    const u32x4* __restrict__ nhalf = reinterpret_cast<const u32x4*>(nodes);
+    u32x4 hot[3] = {r1.hot0, r1.hot1, r1.hot2}, cold[3] = {r1.cold0, r1.cold1, r1.cold2};
     if (!do_expand) flag = 0;
     // (wave-uniform values the compiler cannot know to be uniform: as scalars they steer branches and v_readlane)
     flag = __builtin_amdgcn_readfirstlane(flag); depth_old = __builtin_amdgcn_readfirstlane(depth_old);
@@ -357,6 +427,7 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
     // legal actions in order (the layout of the other evaluator modes), legal_order / legal_count / value came with them
     const bool hit_old = flag == 2;
     if (hit_old) flag = 1;
+    if (HEADS && !hit_old) value = head_value;
     if (flag != 1 && !do_select) return;
 #ifdef AQG_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -369,11 +440,13 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
     float pl[3] = {0.f, 0.f, 0.f};
     if (flag == 1) {
         if (e.prior_mode == 0 && !hit_old) {     // P0: gather at the legal actions, divide by the sum unless 0 (pv_network_cnn.py:129-132)
+            if (!HEADS) {                        // (HEADS: the row is in polbuf already, behind a workgroup barrier)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) polbuf[lane + 64 * r] = polr[r];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                for (int r = 0; r < 4; ++r) polbuf[lane + 64 * r] = polr[r];
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
             float sum = 0.f;
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
@@ -815,8 +888,16 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
 // Both halves touch only this game's pools, and one wave does both, so no ordering between waves is needed.  Per simulation
 // the engine then launches step -> GNN trunk -> GNN heads (3 kernels instead of select / legal / trunk / heads / expand).
 // ------------------------------------------------------------------------------------------------
-template <int N, bool CACHE>
-__global__ __launch_bounds__(512) void engine_step_fast_kernel(aqg_engine e, int do_expand, int do_select, int fast_depth, int list_sim) {
+// HEADS (expanding launches of the 9x9 split network, eight games per workgroup; option "step_heads"): the workgroup first runs the
+// network's heads (heads_body, gcn_heads_split.hpp) for the leaves of its own eight games -- boards 8 wg .. 8 wg + 7 of the pooled rows
+// the trunk launch in front has written, a half-filled 16-board tile, live where leaf_flag is 1 -- and hands each game's softmax row
+// and value to its wave through LDS: no heads launch, no dispatch gap in front of it, and neither row nor value travels through
+// global memory.  The load rounds are ordered by what 128 registers hold: the heads' fragments and pooled rows go out at kernel entry
+// (96 registers of operands), the step's own round 1 (about 50) as soon as the hidden layer's MFMAs are issued and their operands are
+// dead -- it is in flight under the hidden layer's epilogue, the policy layer, the softmax and three barriers, not behind them.
+// Nothing waits for another workgroup: every input was written by a launch that has finished.
+template <int N, bool CACHE, bool HEADS>
+__global__ __launch_bounds__(512, HEADS ? 4 : 1) void engine_step_fast_kernel(aqg_engine e, int do_expand, int do_select, int fast_depth, int list_sim) {
     __shared__ float polbuf[8][256];
     AQG_TRACE_BEGIN
     const int lane = threadIdx.x & 63;
@@ -825,13 +906,29 @@ __global__ __launch_bounds__(512) void engine_step_fast_kernel(aqg_engine e, int
     // workgroup's vector work, finishes sooner and gives its CU's second trunk slot back sooner (option "step_prio")
     { const int pr = (fast_depth >> 8) & 3; if (pr == 1) __builtin_amdgcn_s_setprio(1); else if (pr == 2) __builtin_amdgcn_s_setprio(2); else if (pr == 3) __builtin_amdgcn_s_setprio(3); }
     fast_depth &= 0xFF;
-    if (g < e.num_games) game_step_fast<N, CACHE>(e, g, lane, do_expand, do_select, fast_depth, polbuf[threadIdx.x >> 6], list_sim);
+    StepRound1 r1;
+    if constexpr (HEADS) {                       // (launched with do_expand set and eight waves only)
+        __shared__ HeadsSmem hsm;
+        __shared__ float hval[16];
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const int b0 = blockIdx.x * 8, bend = min(e.num_games, b0 + 8);
+        const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(e.pooled, 0, e.num_games * (HID * 4), 0x00020000);
+        heads_body<true>(hsm, prs, b0, bend, Geo<N>::A, packed_rsrc(e.packed_weights), e.packed_weights, nullptr, nullptr, nullptr, nullptr,
+                         e.leaf_flag, e.counters + 5, wave, lane, polbuf, hval,
+                         [&]() { step_round1<N, CACHE, true>(e, min(g, e.num_games - 1), lane, 1, r1); });     // (a wave without a game loads the last game's: no branch)
+        __syncthreads();                         // the rows and values are complete: each wave reads its own game's
+        if (g < e.num_games) game_step_fast<N, CACHE, true>(e, g, lane, do_expand, do_select, fast_depth, polbuf[wave], list_sim, r1, hval[wave]);
+    } else if (g < e.num_games) {
+        step_round1<N, CACHE, false>(e, g, lane, do_expand, r1);
+        game_step_fast<N, CACHE, false>(e, g, lane, do_expand, do_select, fast_depth, polbuf[threadIdx.x >> 6], list_sim, r1, 0.f);
+    }
     AQG_TRACE_END(1, (unsigned long long)(uintptr_t)e.pooled)
 }
 AQG_TRACE_SETTER(set_trace_mcts)
 
+// `heads`: the launch computes the heads of its leaves itself (see the kernel; the caller has checked that the form applies)
 template <int N>
-static void launch_step(const aqg_engine& e_in, int do_expand, int do_select, hipStream_t st, int list_sim = -1) {
+static void launch_step(const aqg_engine& e_in, int do_expand, int do_select, hipStream_t st, int list_sim = -1, bool heads = false) {
     // prior_mode 3 and 4 leave the network's dense [G,A] policy in e.policy exactly like prior_mode 0: the step kernels gather,
     // renormalise and cache it as mode 0 -- they are handed the struct with prior_mode 0, so no step kernel knows mode 3 or 4
     aqg_engine e = e_in;
@@ -840,8 +937,15 @@ static void launch_step(const aqg_engine& e_in, int do_expand, int do_select, hi
     const int wpb = (g_step_waves == 1 || g_step_waves == 2 || g_step_waves == 8) ? g_step_waves : 4;
     const int fd = g_step_fast_depth | ((g_step_prio & 3) << 8);
     const dim3 sg((e.num_games + wpb - 1) / wpb), sb(64 * wpb);
-    if (e.eval_cache_keys && e.prior_mode == 0) hipLaunchKernelGGL((engine_step_fast_kernel<N, true>), sg, sb, 0, st, e, do_expand, do_select, fd, list_sim);
-    else hipLaunchKernelGGL((engine_step_fast_kernel<N, false>), sg, sb, 0, st, e, do_expand, do_select, fd, -1);
+    const bool cache = e.eval_cache_keys && e.prior_mode == 0;
+    if (!cache) list_sim = -1;
+    bool fused = false;
+    if constexpr (N == 9) fused = heads && do_expand && wpb == 8 && e.prior_mode == 0;      // (the only board with HEADS instantiations)
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, sg, sb, 0, st, e, do_expand, do_select, fd, list_sim); };
+    if constexpr (N == 9) {
+        if (fused) { if (cache) launch(engine_step_fast_kernel<N, true, true>); else launch(engine_step_fast_kernel<N, false, true>); }
+    }
+    if (!fused) { if (cache) launch(engine_step_fast_kernel<N, true, false>); else launch(engine_step_fast_kernel<N, false, false>); }
     if (g_profile_trunk == 2) profile_mark(st, -1);
 }
 
@@ -1161,13 +1265,23 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st) {
     hipLaunchKernelGGL(engine_begin_move_kernel, dim3((e.num_games + 255) / 256), dim3(256), 0, st, e);
     // evaluation cache on a set larger than the trunk's grid: the leaves that miss the cache go to the trunk as a compact list
     const bool use_list = e.prior_mode == 0 && e.eval_cache_keys && e.eval_list && N == 9 && e.num_games > 512 && g_trunk_variant >= 3 && !(e.gnn_flags & AQG_GNN_EXACT_F32);
+    // heads inside the step (option "step_heads"): the 9x9 split network with eight games per step workgroup -- the NEXT step launch
+    // computes policy and value of this simulation's leaves from the pooled rows, so the simulation is two launches, step -> trunk.
+    // Everything else keeps the heads launch: other boards and evaluators, step_waves != 8, the exact kernels behind a range-guard report.
+    const bool step_heads = g_step_heads && e.prior_mode == 0 && N == 9 && g_trunk_variant >= 3 && !(e.gnn_flags & AQG_GNN_EXACT_F32) && g_step_waves == 8;
     for (int sim = 0; sim < e.sims; ++sim) {
-        launch_step<N>(e, sim > 0 ? 1 : 0, 1, st, use_list ? sim : -1);
+        launch_step<N>(e, sim > 0 ? 1 : 0, 1, st, use_list ? sim : -1, step_heads);
         if (e.prior_mode == 0) {
+            // (simulation 0 -- the root's evaluation -- keeps its heads launch: root noise reads the root's row and value from e.policy /
+            //  e.value, and without noise the launch is there only so that these buffers hold the root's evaluation after a search, as
+            //  they always did after a one-simulation search (tests/test_gpu_parity.py::test_engine_masked_trunk_launch reads them).
+            //  Simulation 1's step computes the same heads again from the same pooled rows -- equal results; 1 launch in `sims`.)
+            const bool heads_launch = !step_heads || sim == 0;
             // 9x9: the fused trunk; smaller boards: plain kernels over e.gnn_workspace
             if (int r = launch_gcn_forward_boards_any(N, e.leaf_state, 1, e.num_games, e.packed_weights, e.gnn_workspace,
                                                       e.gnn_workspace ? boards_any_workspace_floats(N, e.num_games) : 0, e.pooled, nullptr,
-                                                      e.policy, nullptr, e.value, e.eval_cache_keys ? e.eval_mask : e.leaf_flag, e.gnn_flags, e.counters + 5, st,
+                                                      heads_launch ? e.policy : nullptr, nullptr, heads_launch ? e.value : nullptr,
+                                                      e.eval_cache_keys ? e.eval_mask : e.leaf_flag, e.gnn_flags, e.counters + 5, st,
                                                       use_list ? e.eval_list : nullptr, use_list ? e.eval_count + sim : nullptr))
                 return r;
         } else if (e.prior_mode == 3) {
@@ -1190,11 +1304,11 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st) {
         }
         if (sim == 0 && e.root_noise_eps > 0.f) launch_root_noise<N>(e, st);      // the root's priors, before simulation 1 expands it
     }
-    launch_step<N>(e, 1, 0, st);   // expand + backup of the last simulation
+    launch_step<N>(e, 1, 0, st, -1, step_heads);   // expand + backup of the last simulation
     return check_launch("engine simulation kernels");
 }
 
-// One move's search is 3 * sims + 2 launches (one more with root noise on) with constant arguments: on a capturable (non-default) stream it is
+// One move's search is 3 * sims + 2 launches (2 * sims + 3 with the heads inside the step; one more with root noise on) with constant arguments: on a capturable (non-default) stream it is
 // captured once into a hipGraph and replayed per move, so the host cost per move is one graph launch instead of ~600
 // kernel launches (with several game sets on several streams the host is otherwise the bottleneck).  The cache key is
 // the engine struct itself plus the trunk options the launches read.
@@ -1219,7 +1333,7 @@ template <int N>
 static int run_sims(const aqg_engine& e, hipStream_t st) {
     if (!g_use_graph || g_profile_trunk || st == nullptr || e.sims < 4) return enqueue_sims<N>(e, st);
     // every option a captured launch bakes in is part of the key: a changed option must never replay a stale graph
-    const int opts[7] = {g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, N, g_step_fast_depth, ((g_trunk_prio & 0xff) << 8) | (g_step_waves << 16) | (g_step_prio << 24) | (g_heads_prio << 28)};
+    const int opts[7] = {g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, N, g_step_fast_depth, ((g_trunk_prio & 0xff) << 8) | (g_step_waves << 16) | (g_step_prio << 24) | (g_heads_prio << 28) | (g_step_heads & 1)};
     for (SimGraph& g : g_sim_graphs)
         if (!memcmp(&g.e, &e, sizeof(aqg_engine)) && !memcmp(g.opts, opts, sizeof(opts))) return replay(g, st);
     if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {

@@ -38,6 +38,12 @@ const char* aqg_last_error(void);
  * the MCTS step hands over from registers to memory (the round-1 step kernel and its option are gone: no symbol, struct or
  * signature changed with them, so AQG_ABI_VERSION stays 15); "trunk_prio" = static wave priorities in the trunk (-1 = by launch size, default); "step_prio" / "heads_prio" 0..3 = wave
  * priority of the MCTS step / heads kernels (defaults 1 / 3); "step_waves" = games per step workgroup (1, 2, 4 or 8; default 8);
+ * "step_heads" 0/1 = the heads inside the MCTS step kernel (default 1): with prior_mode 0 on the 9x9 board, the fp16-split kernels (not
+ * AQG_GNN_EXACT_F32) and "step_waves" 8, every expanding step launch computes policy and value of its own workgroup's leaves from the
+ * pooled rows, a simulation is two launches (step, trunk) instead of three, and policy / value of those leaves are not written to the
+ * engine's `policy` / `value` buffers: after a move or search these hold the ROOT's evaluation (simulation 0 keeps its heads launch;
+ * root noise reads it there) where the three-launch form leaves the last leaf's.  Bit-identical searches.  0 = three launches per
+ * simulation everywhere (A/B runs, tests); part of the captured graphs' key;
  * "train_fused" = form of the training step
  * (csrc/gcn_train.hip): 2 (default) one workgroup per position with every contraction in fp16 split precision on the 16-bit
  * matrix pipe (9x9 board; a position whose values leave fp16 range is redone in f32 inside the same launch, counted by
@@ -46,7 +52,7 @@ const char* aqg_last_error(void);
  * "trunk_phase_delay" = start offset of the second- / third-resident workgroups in units of 64 cycles, applied to
  * launches of at least "trunk_delay_min_boards" boards; "trunk_grid" = workgroups of a trunk launch (0 = default: min(boards, 512); diagnostics);
  * "use_graph" 0/1 = replay
- * a move's 3*sims+2 launches as one captured hipGraph when the stream is capturable (default 1); "profile_trunk" 0/1/2 = no event pairs / around trunk launches / around MCTS step launches */
+ * a move's 2*sims+3 (3*sims+2 without "step_heads") launches as one captured hipGraph when the stream is capturable (default 1); "profile_trunk" 0/1/2 = no event pairs / around trunk launches / around MCTS step launches */
 int aqg_set_option(const char* name, int value);
 /* Measurement aid (bench.py): with option "profile_trunk" = 1 a HIP event pair is recorded around every launch of the
  * dominant kernel (the GCN trunk) on its launch stream; = 2 brackets the MCTS step kernel's launches instead (`boards` then
