@@ -25,14 +25,14 @@ constexpr int WAVE = 64;
 // kernels logs {kernel id | where it ran, tag, blockIdx, start, end} (s_memrealtime, 100 MHz) into a caller-supplied buffer whose first
 // word is the entry counter -- the only way to see which kernels of different game sets REALLY run side by side (rocprofv3's
 // kernel trace serialises the dispatches it intercepts).
+#define AQG_CAT2(a, b) a##b
+#define AQG_CAT(a, b) AQG_CAT2(a, b)
 #ifdef AQG_TRACE
 #ifndef AQG_TRACE_TU
 #define AQG_TRACE_TU other
 #endif
 // (one copy per translation unit, under a per-file NAME: without relocatable device code every file is its own code object, and
 //  the runtime registers device variables by name -- two statics of the same name end up sharing one registration)
-#define AQG_CAT2(a, b) a##b
-#define AQG_CAT(a, b) AQG_CAT2(a, b)
 #define g_trace_buf AQG_CAT(g_trace_buf_, AQG_TRACE_TU)
 #define g_trace_cap AQG_CAT(g_trace_cap_, AQG_TRACE_TU)
 static __device__ unsigned long long* g_trace_buf = nullptr;

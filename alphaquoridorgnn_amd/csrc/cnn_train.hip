@@ -23,6 +23,7 @@
 #include "aqg_common.hpp"
 #include "../../include/aqgnn.h"
 #include "launchers.hpp"
+#include "train_adam.hpp"
 
 #include <cmath>
 
@@ -190,26 +191,19 @@ __device__ inline int cnn_tensor_of(CnnShape s, size_t e0, size_t* off) {
     *off = h - F; return hc + 3;
 }
 
-// torch.optim.Adam over every parameter element (the formula of gcn_train_general.hip's finish kernel), the tensor pointers read
-// from the device table [params | grads | adam_m | adam_v]; and, in the workgroup after the last element's (when `loss` is set),
-// the two batch means of the per-position loss terms summed in position order -> loss_mean[2], added to loss_sums[2] when set.
+// torch.optim.Adam over every parameter element (train_adam.hpp), the tensor pointers read from the device table
+// [params | grads | adam_m | adam_v]; and, in the workgroup after the last element's (when `loss` is set), its loss_means.
 struct CnnAdamArgs {
     CnnShape s; int T; unsigned adam_blocks; size_t total;
     float* const* table;
-    float lr, beta1, beta2, eps, bc1, bc2_sqrt;
-    int B; const float* loss; float* loss_mean; float* loss_sums;
+    AdamStep adam;
+    int B; LossMeans means;
 };
 
 __global__ __launch_bounds__(256) void cnn_adam_kernel(CnnAdamArgs a) {
     if (blockIdx.x == a.adam_blocks) {
-        if (threadIdx.x < 2) {
-            const int e = threadIdx.x;
-            float s = 0.f;
-            for (int b = 0; b < a.B; ++b) s += a.loss[2 * b + e];
-            const float mean = s / (float)a.B;
-            if (a.loss_mean) a.loss_mean[e] = mean;
-            if (a.loss_sums) a.loss_sums[e] += mean;
-        }
+        const LossMeans means = a.means;
+        loss_means(means, a.B);
         return;
     }
     const size_t e0 = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -221,11 +215,10 @@ __global__ __launch_bounds__(256) void cnn_adam_kernel(CnnAdamArgs a) {
     float* m = a.table[2 * a.T + i];
     float* v = a.table[3 * a.T + i];
     const float gr = g[e], om = m[e], ov = v[e], op = p[e];
-    const float mi = a.beta1 * om + (1.f - a.beta1) * gr;          // exp_avg.lerp_(grad, 1 - beta1)
-    const float vi = a.beta2 * ov + (1.f - a.beta2) * gr * gr;     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-    m[e] = mi; v[e] = vi;
-    const float denom = sqrtf(vi) / a.bc2_sqrt + a.eps;
-    p[e] = op - (a.lr / a.bc1) * (mi / denom);
+    const AdamStep ad = a.adam;                 // (copies, not references into `a`: train_adam.hpp says why)
+    const AdamMoments n = adam_moments(ad, gr, om, ov);
+    m[e] = n.m; v[e] = n.v;
+    p[e] = adam_param(ad, op, n);
 }
 
 struct CnnTrainWorkspace {
@@ -368,9 +361,8 @@ int launch_finish(const aqg_cnn_train& t, int B, bool update, int step, const fl
     a.T = 3 * (2 * t.num_blocks + 1) + 4;
     a.total = cnn_param_count(a.s);
     a.table = t.adam_table;
-    const double bc1 = 1.0 - pow((double)t.beta1, (double)step), bc2 = 1.0 - pow((double)t.beta2, (double)step);
-    a.lr = t.lr; a.beta1 = t.beta1; a.beta2 = t.beta2; a.eps = t.eps; a.bc1 = (float)bc1; a.bc2_sqrt = (float)sqrt(bc2);
-    a.B = B; a.loss = loss; a.loss_mean = loss_mean; a.loss_sums = loss_sums;
+    a.adam = adam_step(t.lr, t.beta1, t.beta2, t.eps, step);
+    a.B = B; a.means = LossMeans{loss, loss_mean, loss_sums};
     a.adam_blocks = update ? blocks_of((long long)a.total, 256) : 0u;
     const unsigned grid = a.adam_blocks + (loss && B > 0 ? 1u : 0u);
     if (grid == 0) return 0;

@@ -17,6 +17,7 @@
 #include "aqg_common.hpp"
 #include "../../include/aqgnn.h"
 #include "launchers.hpp"
+#include "train_adam.hpp"
 
 namespace aqg {
 
@@ -55,7 +56,7 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// One workgroup per position b, train_network.py:54-55,85-86 as in gcn_train.hip:
+// One workgroup per position b, train_network.py:54-55,85-86 as in gcn_train_heads.hpp:
 //   loss[b] = { -sum_a t_a log_softmax(p)_a,  (v - z)^2 },  dpol[b][a] = (softmax(p)_a sum_a t_a - t_a) / B,  dval[b] = 2 (v - z) / B
 // with p = the network's (already softmaxed) policy, v its tanh value; the targets are rows order[first + b] (or first + b).
 __global__ __launch_bounds__(256) void train_general_loss_kernel(int B, int A, const float* __restrict__ policy,
@@ -169,27 +170,19 @@ __global__ __launch_bounds__(256) void board_gcn_layer_backward_kernel(int Hd, i
         }
 }
 
-// torch.optim.Adam over every parameter element of the network (no weight decay, no amsgrad; bias corrections from the host in f64),
-// the formula of gcn_train.hip's adam_update; and, in the workgroup after the last element's (when `loss` is set), the two batch means
-// of the per-position loss terms summed in position order -> loss_mean[2], added to loss_sums[2] when that is set.
+// torch.optim.Adam over every parameter element of the network (train_adam.hpp); and, in the workgroup after the last
+// element's (when `loss` is set), its loss_means.
 struct AdamJobs {
     float* p[MAXT]; const float* g[MAXT]; float* m[MAXT]; float* v[MAXT];
     unsigned int end[MAXT];          // running element count after tensor i
     int tensors, update, B;
-    float lr, beta1, beta2, eps, bc1, bc2_sqrt;
-    const float* loss; float* loss_mean; float* loss_sums;
+    AdamStep adam;
+    LossMeans means;
 };
 
 __global__ __launch_bounds__(256) void train_general_finish_kernel(AdamJobs jb, unsigned int adam_blocks) {
     if (blockIdx.x == adam_blocks) {
-        if (threadIdx.x < 2) {
-            const int e = threadIdx.x;
-            float s = 0.f;
-            for (int b = 0; b < jb.B; ++b) s += jb.loss[2 * b + e];
-            const float mean = s / (float)jb.B;
-            if (jb.loss_mean) jb.loss_mean[e] = mean;
-            if (jb.loss_sums) jb.loss_sums[e] += mean;
-        }
+        loss_means(jb.means, jb.B);
         return;
     }
     const unsigned int e0 = blockIdx.x * 256 + threadIdx.x;
@@ -199,11 +192,9 @@ __global__ __launch_bounds__(256) void train_general_finish_kernel(AdamJobs jb, 
     const int i = lo;
     const unsigned int e = e0 - (i ? jb.end[i - 1] : 0u);
     const float gr = jb.g[i][e], om = jb.m[i][e], ov = jb.v[i][e], op = jb.p[i][e];
-    const float mi = jb.beta1 * om + (1.f - jb.beta1) * gr;          // exp_avg.lerp_(grad, 1 - beta1)
-    const float vi = jb.beta2 * ov + (1.f - jb.beta2) * gr * gr;     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-    jb.m[i][e] = mi; jb.v[i][e] = vi;
-    const float denom = sqrtf(vi) / jb.bc2_sqrt + jb.eps;
-    jb.p[i][e] = op - (jb.lr / jb.bc1) * (mi / denom);
+    const AdamMoments n = adam_moments(jb.adam, gr, om, ov);
+    jb.m[i][e] = n.m; jb.v[i][e] = n.v;
+    jb.p[i][e] = adam_param(jb.adam, op, n);
 }
 
 inline size_t round64(size_t n) { return (n + 63) & ~(size_t)63; }
@@ -334,9 +325,8 @@ int launch_finish(const aqg_train_general& t, int B, bool update, int step, cons
         jb.p[i] = t.params[i]; jb.g[i] = t.grads[i]; jb.m[i] = t.adam_m[i]; jb.v[i] = t.adam_v[i];
     }
     jb.tensors = T; jb.update = update; jb.B = B;
-    const double bc1 = 1.0 - pow((double)t.beta1, (double)step), bc2 = 1.0 - pow((double)t.beta2, (double)step);
-    jb.lr = t.lr; jb.beta1 = t.beta1; jb.beta2 = t.beta2; jb.eps = t.eps; jb.bc1 = (float)bc1; jb.bc2_sqrt = (float)sqrt(bc2);
-    jb.loss = loss; jb.loss_mean = loss_mean; jb.loss_sums = loss_sums;
+    jb.adam = adam_step(t.lr, t.beta1, t.beta2, t.eps, step);
+    jb.means = LossMeans{loss, loss_mean, loss_sums};
     const unsigned int adam_blocks = update ? blocks_of(run, 256) : 0u;
     const unsigned int grid = adam_blocks + (loss && B > 0 ? 1u : 0u);
     if (grid == 0) return 0;

@@ -124,9 +124,25 @@ int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_
 // ---- gcn_train.hip
 extern int g_train_fused;
 int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st);
-long long train_fallbacks(int reset);
 int train_steps(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, long long positions,
                 float* loss_sums, hipStream_t st);
+
+// ---- gcn_train_exact.hip, gcn_train_split.hip, gcn_train_final.hip: the two launches of a fused training step
+int launch_train_board_exact(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, int first,
+                             int B, hipStream_t st);
+int launch_train_board_split(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, int first,
+                             int B, int force_fallback, hipStream_t st);
+long long train_fallbacks(int reset);
+int launch_train_final(const aqg_train& t, int B, bool compute, bool update, int step, float* loss_sums, hipStream_t st);
+#ifdef AQG_STAMP            // diagnostic builds only (gcn_train_common.hpp): each unit's own stamp counters / dump pointer
+int train_stamps_exact(unsigned long long* out, int reset);
+int train_stamps_split(unsigned long long* out, int reset);
+int train_stamps_final(unsigned long long* out, int reset);
+#endif
+#ifdef AQG_TRAIN_DEBUG
+int train_debug_buf_exact(float* buf);
+int train_debug_buf_split(float* buf);
+#endif
 
 // ---- gcn_train_general.hip
 int launch_train_general_prep(int V, int B, const uint8_t* states72, const int64_t* order, int first, int32_t* gptr, uint8_t* gathered,

@@ -1,5 +1,5 @@
 // split_mfma.hpp -- the fp16 hi/lo split arithmetic shared by the inference trunk (gcn_trunk_split.hip) and the training step
-// (gcn_train.hip): every f32 operand x travels as two fp16 numbers hi = RNE16(x), lo = RNE16(x - hi) (11 + 11 mantissa bits), a
+// (gcn_train_split.hip): every f32 operand x travels as two fp16 numbers hi = RNE16(x), lo = RNE16(x - hi) (11 + 11 mantissa bits), a
 // product is rebuilt as hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16 with f32 accumulation (the dropped lo*lo term is
 // ~2^-22 |ab|), and the board's banded adjacency is enumerated in the k-slot order the accumulators hold the nodes in.
 #pragma once

@@ -1,6 +1,7 @@
 #!/usr/bin/env bash
-# Developer A/B of training-step builds on one GPU box: every argument is a set of -D flags for gcn_train.hip ("-" = none); each is
-# built into its own library and timed with tools/train_bench.py (run_epoch ms/step per form).   bash tools/ab_train.sh "-" "-DAQG_HEADS_INLINE"
+# Developer A/B of training-step builds on one GPU box: every argument is a set of -D flags for the training units (gcn_train_*.hip;
+# "-" = none); each is built into its own library and timed with tools/train_bench.py (run_epoch ms/step per form).
+#   bash tools/ab_train.sh "-" "-DMY_SWITCH=2"      (the syntax only: the training units have no timing switch left)
 set -euo pipefail
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 i=0

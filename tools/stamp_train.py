@@ -25,7 +25,7 @@ buf = (ctypes.c_ulonglong * 64)()
 fn = lib.aqg_debug_train_stamps; fn.restype = ctypes.c_int; fn.argtypes = [ctypes.c_void_p, ctypes.c_int]
 tr.run_epoch(st, pi, z, order[:BATCH_SIZE * 5]); torch.cuda.synchronize(); fn(buf, 1)
 tr.run_epoch(st, pi, z, order); torch.cuda.synchronize(); fn(buf, 0)
-# the sections of g_train_stamp (csrc/gcn_train.hip)
+# the sections of g_train_stamp (csrc/gcn_train_common.hpp; aqg_debug_train_stamps sums the arrays of gcn_train_exact / _split / _final.hip)
 names = {0: ("final", ["index", "sums"]),
          1: ("heads inside the fused kernel", ["wait for pooled g", "hidden layers", "logits", "softmax/loss reductions", "dhp partials", "dhs", "dg partials"]),
          2: ("train_board (fused)", ["loads + graph", "layer 1 + aggregate", "layer-2 mfma", "acc->LDS, aggregate 2", "layer-3 mfma", "aggregate 3 + pool", "heads (all)",

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Developer diagnostic (-DAQG_TRAIN_DEBUG build): dense dumps of the layer-2 backward intermediates (dZ3, dH2 before / after the ReLU
-mask) of the split-precision training step against the f32 step's, position by position."""
+mask) of the split-precision training step (csrc/gcn_train_split.hip) against the f32 step's (csrc/gcn_train_exact.hpp), position by
+position."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
