@@ -1,6 +1,6 @@
 // agents.hip -- the baseline agents of agents.py in batch, for gfx950: uniformly random moves (agents.py:14-18), random playouts
-// (:111-121), the rollout MCTS built on them (:130-214) and depth-limited alpha-beta (:22-107), plus the two engine entry points a "network vs agent" match needs:
-// read every slot's position, apply a move the engine did not search.
+// (:111-121), the rollout MCTS built on them (:130-214) and depth-limited alpha-beta (:22-107).  (The two engine entry points a "network
+// vs agent" match needs -- read every slot's position, apply a move the engine did not search -- are the engine's: mcts_move.hip.)
 //
 // One 64-lane wavefront per state / game, as in legal_mask.hip: a playout is legal_actions() -> pick -> next() until the game ends,
 // and legal_actions() is the one-lane-per-wall-slot wave of legal_wave.hpp.  The state is the same in every lane; the legal list
@@ -535,55 +535,6 @@ __global__ __launch_bounds__(256) void agent_alpha_beta_pick_kernel(int B, const
 }
 
 // ------------------------------------------------------------------------------------------------
-// engine: the position of every slot, and a move the engine did not search
-// ------------------------------------------------------------------------------------------------
-__global__ void engine_root_states72_kernel(aqg_engine e, uint8_t* __restrict__ out72) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= e.num_games) return;
-    pack72(load_state(e.root_state, 1, g), e.board_size, out72 + (size_t)g * STATE72);
-}
-
-// The transition half of engine_finish_move_kernel (csrc/mcts.hip) with a caller-given action: history row (state72, the action, a
-// visit row that is zero except 1 at the action), next(), plies, lose / draw / z / counters / game_active.  A negative action on an
-// active slot is the dead end: a draw, counted in counters[2].
-template <int N>
-__global__ __launch_bounds__(256) void engine_apply_actions_kernel(aqg_engine e, const int32_t* __restrict__ actions) {
-    constexpr int A = Geo<N>::A;
-    const int lane = threadIdx.x & 63;
-    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (g >= e.num_games || !e.game_active[g]) return;
-    const int k = e.slot_game[g];
-    const int ply = e.game_plies[k];
-    const int chosen = actions[g];
-    const QState s = load_state(e.root_state, 1, g);
-    if (chosen >= A) return;                                   // not an action of this board: the slot is left as it is
-    if (ply < e.max_plies) {
-        if (lane == 0) pack72(s, N, e.hist_state72 + ((size_t)k * e.max_plies + ply) * STATE72);
-        uint16_t* hv = e.hist_visits + ((size_t)k * e.max_plies + ply) * A;
-        for (int a = lane; a < A; a += 64) hv[a] = (a == chosen) ? 1 : 0;
-    }
-    if (lane != 0) return;
-    if (chosen < 0) {
-        e.game_active[g] = 0; e.game_result[k] = 0; e.game_done[k] = 1;
-        atomicAdd(&e.counters[2], 1); atomicAdd(&e.counters[1], 1); atomicSub(&e.counters[0], 1);
-        return;
-    }
-    if (ply < e.max_plies) e.hist_action[(size_t)k * e.max_plies + ply] = (uint8_t)chosen;
-    const QState t = next_state<N>(s, chosen);
-    store_state(e.root_state, g, t);
-    e.game_plies[k] = ply + 1;
-    const bool lose = is_lose<N>(t), draw = is_draw(t, e.plies_for_draw);
-    if (lose || draw) {
-        int z = 0;
-        if (lose) z = ((t.plies % 2) == 0) ? -1 : 1;          // first_player_value (self_play.py:22-27)
-        e.game_result[k] = (int8_t)z;
-        e.game_done[k] = 1;
-        e.game_active[g] = 0;
-        atomicAdd(&e.counters[1], 1); atomicSub(&e.counters[0], 1);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
 // host-side enqueue (no sync, no allocation)
 // ------------------------------------------------------------------------------------------------
 int launch_agent_random(int N, const uint8_t* states72, int B, const double* uniforms, int stride, uint64_t seed, int32_t* actions,
@@ -656,29 +607,6 @@ int launch_agent_alpha_beta(int N, const uint8_t* states72, int B, const uint8_t
     if (launched) return launched;
     hipLaunchKernelGGL(agent_alpha_beta_pick_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, active, w, action, nodes);
     return check_launch("agent_alpha_beta_pick_kernel");
-}
-
-int engine_root_states72(const aqg_engine& e, uint8_t* out72, hipStream_t st) {
-    const int N = e.board_size;
-    if (!board_size_supported(N)) return fail("unsupported board_size");
-    if (e.num_games <= 0 || !e.root_state) return fail("aqg_engine_root_states72: incomplete engine");
-    hipLaunchKernelGGL(engine_root_states72_kernel, dim3((e.num_games + 255) / 256), dim3(256), 0, st, e, out72);
-    return check_launch("engine_root_states72_kernel");
-}
-
-int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_t st) {
-    if (e.num_games <= 0 || !e.root_state || !e.game_active || !e.slot_game || !e.game_plies || !e.game_result || !e.game_done ||
-        !e.counters)
-        return fail("aqg_engine_apply_actions: incomplete engine");
-    if (e.max_plies > 0 && (!e.hist_state72 || !e.hist_visits || !e.hist_action)) return fail("aqg_engine_apply_actions: history buffers missing");
-    if (e.quota < e.num_games) return fail("quota must be >= num_games");
-    const dim3 grid((e.num_games + 3) / 4), block(256);
-    const int launched = for_board_size(e.board_size, [&](auto n) {
-        hipLaunchKernelGGL(engine_apply_actions_kernel<decltype(n)::value>, grid, block, 0, st, e, actions);
-        return check_launch("engine_apply_actions_kernel");
-    });
-    if (launched) return launched;
-    return e.quota > e.num_games ? engine_refill(e, st) : 0;
 }
 
 }  // namespace aqg

@@ -1,5 +1,5 @@
 // counter_rng.hpp -- the counter-based generator documented in include/aqgnn.h, shared by the baseline agents (agents.hip) and the
-// root exploration noise (mcts.hip): stateless, so a draw depends on (key, index) alone and never on launch geometry.
+// root exploration noise (mcts_move.hip): stateless, so a draw depends on (key, index) alone and never on launch geometry.
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>

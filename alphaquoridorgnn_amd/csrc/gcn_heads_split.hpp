@@ -1,7 +1,7 @@
 // gcn_heads_split.hpp -- the heads of GraphPolicyValueNetwork.forward (pv_network_gnn.py:60-64) on the split matrix pipe, as a workgroup-wide
 // device function: heads_body and what it needs (HeadsSmem, the DPP row reductions, the packed buffer's fragment loads, the fp16-range
 // guard's report).  Two kernels run it: gcn_heads_mm_kernel (gcn_trunk_split.hip: 16 boards per workgroup, results to global memory) and
-// the MCTS step kernel (mcts.hip: the leaves of a step workgroup's own eight games, results to LDS).  __forceinline__ device code only.
+// the MCTS step kernel (mcts_step.hip: the leaves of a step workgroup's own eight games, results to LDS).  __forceinline__ device code only.
 #pragma once
 #include "gcn_packed.hpp"
 #include <cmath>
@@ -81,7 +81,7 @@ struct alignas(16) HeadsSmem {
 
 // All 512 threads of a workgroup call this for the 16 boards b0 .. b0 + 15 (two internal barriers).  `prs` = buffer resource of the
 // pooled rows [B][128] f32.
-// STEP (the MCTS step kernel, mcts.hip): the same arithmetic for the leaves of the workgroup's own games, with three differences
+// STEP (the MCTS step kernel, mcts_step.hip): the same arithmetic for the leaves of the workgroup's own games, with three differences
 // in where things come from and go to -- a board is live where its `active` byte is 1 (the engine's leaf_flag: 2 marks a leaf whose
 // priors are in memory already); the softmax row of board b0 + i goes to lds_policy[i][action] and tanh(value) to lds_value[i]
 // instead of global memory (the caller puts a barrier in front of their readers); and mid() is called once the hidden layer's

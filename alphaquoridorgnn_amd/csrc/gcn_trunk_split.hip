@@ -5,7 +5,7 @@
 //
 //   trunk   gcn_trunk_boards_mm_kernel<TRACK, LIST>: one 8-wave workgroup walks boards, two workgroups per CU
 //   heads   gcn_heads_mm_kernel: policy MLP 128->64->A (+Softmax) and value MLP 128->64->1 (+Tanh), 16 boards per workgroup
-//           (its body, heads_body, lives in gcn_heads_split.hpp: the MCTS step kernel of mcts.hip runs it too)
+//           (its body, heads_body, lives in gcn_heads_split.hpp: the MCTS step kernel of mcts_step.hip runs it too)
 //
 // Both kernels log into this file's trace buffer in the -DAQG_TRACE build (kernel ids 2 and 3; aqg_common.hpp), which is why they
 // share a translation unit.

@@ -89,9 +89,8 @@ int launch_cnn_forward_planes(int N, const float* planes, int B, const aqg_cnn_n
                               size_t workspace_floats, float* pooled, float* logits, float* policy, float* value_pre, float* value,
                               hipStream_t st);
 
-// ---- mcts.hip
-extern int g_use_graph, g_step_waves, g_step_prio, g_step_fast_depth, g_step_heads;
-int set_trace_mcts(void* buf, unsigned int cap);
+// ---- mcts.hip  (the engine's entry points; host code only)
+extern int g_use_graph;
 int engine_reset(const aqg_engine& e, hipStream_t st);
 int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st);
 int engine_begin_move(const aqg_engine& e, hipStream_t st);
@@ -104,6 +103,24 @@ int engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, i
 int engine_refill(const aqg_engine& e, hipStream_t st);
 int engine_root_noise(const aqg_engine& e, hipStream_t st);
 int engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st);
+
+// ---- mcts_step.hip  (launchers of the engine's kernels only enqueue: the entry point checks the launch)
+extern int g_step_waves, g_step_prio, g_step_fast_depth, g_step_heads;
+int set_trace_mcts(void* buf, unsigned int cap);
+int launch_engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t st, int list_sim, bool heads);
+
+// ---- mcts_move.hip
+void launch_engine_reset(const aqg_engine& e, hipStream_t st);
+void launch_engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
+void launch_engine_begin_move(const aqg_engine& e, hipStream_t st);
+int launch_engine_fake_eval(const aqg_engine& e, hipStream_t st);
+int launch_engine_root_noise(const aqg_engine& e, hipStream_t st);
+int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, hipStream_t st);
+void launch_engine_refill(const aqg_engine& e, hipStream_t st);
+int launch_engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st);
+void launch_engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st);
+int engine_root_states72(const aqg_engine& e, uint8_t* out72, hipStream_t st);
+int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_t st);
 
 // ---- agents.hip
 int launch_agent_random(int N, const uint8_t* states72, int B, const double* uniforms, int stride, uint64_t seed, int32_t* actions,
@@ -118,8 +135,6 @@ int launch_agent_shortest_paths(int N, const uint8_t* states72, int B, int32_t* 
 size_t agent_alpha_beta_workspace_bytes(int N, int B, int max_depth);
 int launch_agent_alpha_beta(int N, const uint8_t* states72, int B, const uint8_t* active, int plies_for_draw, int max_dist,
                             int max_depth, void* workspace, size_t workspace_bytes, int32_t* action, int64_t* nodes, hipStream_t st);
-int engine_root_states72(const aqg_engine& e, uint8_t* out72, hipStream_t st);
-int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_t st);
 
 // ---- gcn_train.hip
 extern int g_train_fused;

@@ -1,0 +1,70 @@
+// mcts_tree.hpp -- what the engine's units (mcts_step.hip, mcts_move.hip) share of a game's tree pool: the node record, its
+// accessors, the wave sums and the initial position.  __forceinline__ device code and declarations only.  The including unit
+// sets `#pragma clang fp contract(off)` in front of this header: q_of and the backup are PUCT arithmetic.
+#pragma once
+#include "aqg_common.hpp"
+#include "../../include/aqgnn.h"
+
+namespace aqg {
+
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ float wave_sum_f(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// One reference-"Node" (pv_mcts.py:24-31) per 32-byte record: the statistics, the prior, the action that led here and
+// the child range sit in one cache sector, so a descent level is ONE dependent load round (the chosen child's
+// `kids` and `action` arrive together with its w/n/p) of two aligned 16-byte loads per child.
+struct alignas(32) NodeRec {
+    // cold half (bytes 0..15): what a descent needs only of the child it CHOSE
+    double w;          // cumulative value (python float in the reference)
+    float p;           // prior
+    uint32_t action;   // action that led to this node (0xFF for the root)
+    // hot half (bytes 16..31): what PUCT scores every child with -- one aligned 16-byte load per child
+    int32_t n;         // visit count
+    uint32_t kids;     // first child (24 bits) | child count << 24 ; 0 = unexpanded
+    float q;           // f32(-w / n) as PUCT adds it (pv_mcts.py:74), 0 while n == 0: maintained by every writer of (w, n), so the
+                       // descent reads it with the record instead of doing a float64 division per tree level on its critical path
+    float cp;          // f32(C_PUCT * p), the first product of PUCT's exploration term (pv_mcts.py:75, evaluated left to right in f32):
+                       // written with p, so the descent's per-level chain starts one multiply later
+};
+static_assert(sizeof(NodeRec) == 32, "NodeRec must be 32 bytes");
+
+// The exploitation term exactly as the reference forms it: python float division of the float64 sums, rounded to float32 where it
+// meets the float32 exploration term (pv_mcts.py:74 under NumPy-2 promotion; pinned by the reference traces).
+__device__ __forceinline__ float q_of(double w, int n) { return n ? (float)(-w / (double)n) : 0.0f; }
+
+__device__ __forceinline__ NodeRec* game_nodes(const aqg_engine& e, int g) {
+    return reinterpret_cast<NodeRec*>(e.node_rec) + (size_t)g * e.node_cap;
+}
+
+// Backup (pv_mcts.py:36-42,:49-50,:62-64): every node on the path gets w += value, n += 1 with the sign flipping
+// per ply.  The path nodes are distinct, so lane d updates path[d] independently (one parallel step instead of a
+// serial chain of dependent global read-modify-writes); the sums are the same float64 additions.
+__device__ __forceinline__ void backup_path(NodeRec* __restrict__ nodes, const int* __restrict__ path, int depth,
+                                            double leaf_value, int lane) {
+    for (int d = lane; d <= depth; d += 64) {
+        NodeRec& r = nodes[path[d]];
+        r.w += ((depth - d) & 1) ? -leaf_value : leaf_value;
+        r.n += 1;
+        r.q = q_of(r.w, r.n);
+    }
+}
+
+// the initial position (game_logic.py:25-40): both pawns on the middle of their own back row, no wall placed
+__device__ __forceinline__ QState initial_state(int N, int num_walls) {
+    QState s;
+    s.hw = 0; s.vw = 0;
+    s.ppos = (uint8_t)(N * (N - 1) + N / 2); s.pwl = (uint8_t)num_walls;
+    s.epos = s.ppos; s.ewl = s.pwl;
+    s.plies = 0; s.pad = 0;
+    return s;
+}
+
+}  // namespace aqg

@@ -3,7 +3,7 @@
 Host side of aqg_engine_* (include/aqgnn.h).  All state lives in HBM as torch tensors owned by this object;
 every simulation of every game is enqueued by one C call per move (no per-simulation Python, no host sync
 inside a move).  Per-game semantics equal the reference's sequential `pv_mcts_policy` + `play()`
-(pv_mcts.py:20-95, self_play.py:40-68); see csrc/mcts.hip.
+(pv_mcts.py:20-95, self_play.py:40-68); see csrc/mcts.hip (the map of mcts_step.hip, mcts_move.hip, mcts_tree.hpp).
 
 Sharding: games are independent, so rank r of W simply owns its own BatchedSelfPlay with its own
 uniform stream; `gather_history` is the single exchange step per generation (all-gather over RCCL/xGMI).
@@ -19,7 +19,7 @@ from .constants import BOARD_SIZE, board_params
 from .evaluators import BINDINGS
 
 
-ROOT_NOISE_ATTEMPTS = 64      # cap of the gamma sampler's rejection loop (csrc/mcts.hip ROOT_NOISE_ATTEMPTS)
+ROOT_NOISE_ATTEMPTS = 64      # cap of the gamma sampler's rejection loop (csrc/mcts_move.hip ROOT_NOISE_ATTEMPTS)
 _MASK64 = (1 << 64) - 1
 
 
@@ -180,7 +180,7 @@ class BatchedSelfPlay:
             return torch.zeros(shape, dtype=dtype, device=dev)
 
         t = self.t = {}
-        t["node_rec"] = z((G * cap, 4), torch.float64)     # 32-byte node records (csrc/mcts.hip NodeRec)
+        t["node_rec"] = z((G * cap, 4), torch.float64)     # 32-byte node records (csrc/mcts_tree.hpp NodeRec)
         t["node_count"] = z((G,), torch.int32)
         t["root_state"] = z((G, 24), torch.uint8)
         t["path"] = z((G, self.sims + 2), torch.int32)

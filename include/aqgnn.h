@@ -410,7 +410,7 @@ int aqg_engine_apply_actions(const aqg_engine* e_host, const int32_t* actions, v
  * over the root's legal_actions() in order, all in f32 without contraction: 1 - eps is one subtraction, then two products and one
  * sum, each rounded.  p_i are the priors the step kernel would have taken: for the network evaluators the dense row gathered at the
  * legal actions and divided by its sum unless that is 0 (one f32 division), otherwise the first cnt entries of the row.  One launch
- * per move (csrc/mcts.hip, engine_root_noise_kernel), one wavefront per slot, between the evaluation of simulation 0 and the step
+ * per move (csrc/mcts_move.hip, engine_root_noise_kernel), one wavefront per slot, between the evaluation of simulation 0 and the step
  * of simulation 1, inside the captured graph; it acts on the active slots whose pending leaf is the root (path_len 0, leaf_flag 1
  * or 2), writes p' to policy[g][0 .. cnt) and marks the leaf with leaf_flag 2 ("normalised priors in legal order").  No atomics, no
  * allocation, no host synchronisation; S is summed in a fixed order, so two runs give identical bytes.

@@ -231,6 +231,51 @@ def test_apply_actions_between_searched_moves(dev, N):
     assert int(eng.t["game_plies"][G - 1]) == 1                  # the ended slot stayed out of the third ply
 
 
+@pytest.mark.parametrize("N", [3, 5])
+def test_apply_actions_records_games_as_move_does(dev, N):
+    """The one transition behind engine_finish_move_kernel and engine_apply_actions_kernel (csrc/mcts_move.hip engine_transition),
+    pinned from both sides: engine A plays a quota of 12 games on 8 slots with move(); engine B, built alike, is handed A's
+    recorded action of every active slot ply by ply through apply_actions.  After every ply the two agree in every slot's position,
+    game_active, slot_game and the counters; at the end in every game's record.  The refill runs behind both kernels.
+    (`leaf_evals` and `terminal_sims` of counters() are statistics of the search, which B never runs: every other entry and the
+    whole counters tensor are compared.  oracle/mcts.py's FakeModel plays this setup -- sims 8, temperature 0, bias 0 -- to a decisive
+    game on both boards: 2 plies and z = -1 on 3x3, 7 plies and z = +1 on 5x5, so the quota outlasts the first eight games.)"""
+    from alphaquoridorgnn_amd.engine import BatchedSelfPlay
+    G, Q = 8, 12
+    kw = dict(num_games=G, sims=8, board_size=N, evaluator="fake", temperature=0.0, quota=Q)
+    a, b = BatchedSelfPlay(None, **kw), BatchedSelfPlay(None, **kw)
+    host = lambda eng, name: eng.t[name].cpu().numpy()
+    engine_counters = lambda eng: {k: v for k, v in eng.counters().items() if k not in ("leaf_evals", "terminal_sims")}
+    moves = 0
+    while a.counters()["active"] > 0:
+        assert moves < 2 * Q * a.max_plies
+        active, slot_game, plies = host(a, "game_active"), host(a, "slot_game"), host(a, "game_plies")
+        a.move()
+        recorded = host(a, "hist_action")
+        acts = np.zeros(G, dtype=np.int32)
+        for g in range(G):
+            if active[g]:
+                acts[g] = recorded[slot_game[g], plies[slot_game[g]]]
+        b.apply_actions(acts)
+        moves += 1
+        assert np.array_equal(b.root_states72().cpu().numpy(), a.root_states72().cpu().numpy()), moves
+        for name in ("game_active", "slot_game", "counters"):
+            assert np.array_equal(host(b, name), host(a, name)), (name, moves)
+        assert engine_counters(b) == engine_counters(a), moves
+    c = a.counters()
+    assert c["finished"] == Q and c["started"] == Q and c["dead_ends"] == 0
+    for name in ("game_plies", "game_done", "game_result", "game_first_move", "hist_state72", "hist_action"):
+        assert np.array_equal(host(b, name), host(a, name)), name
+    plies, actions, visits = host(a, "game_plies"), host(a, "hist_action"), host(b, "hist_visits")
+    for k in range(Q):
+        n = int(plies[k])
+        want = np.zeros((n, visits.shape[2]), dtype=visits.dtype)
+        want[np.arange(n), actions[k, :n]] = 1
+        assert np.array_equal(visits[k, :n], want), k
+    assert (host(a, "game_result") != 0).any()                   # a decisive game went through lose / z
+    assert (host(a, "game_first_move") > 0).any()                # a slot was refilled
+
+
 # ---------------------------------------------------------------------------------------------- 11. whole matches
 def _match(agent, N, games, seed=5, **kw):
     from alphaquoridorgnn_amd.evaluate_agents import BatchedAgentMatch

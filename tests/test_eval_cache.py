@@ -1,4 +1,4 @@
-"""The evaluation cache (include/aqgnn.h `eval_cache_keys`, csrc/mcts.hip game_step_fast<N, true>) where the end-to-end cache tests of
+"""The evaluation cache (include/aqgnn.h `eval_cache_keys`, csrc/mcts_step.hip game_step_fast<N, true>) where the end-to-end cache tests of
 test_gpu_parity.py do not reach: the compact miss list of sets larger than 512 games (the trunk's <0, true> / <2, true> builds), the
 table's entries read back and restated on the host (key, hash window, legal list, the fp64 network's priors and value), the table
 after a weight change without a reset (the long-lived pv_mcts engines), and the launch options that change geometry only."""
@@ -112,7 +112,7 @@ def _key_states72(hw, vw, misc, N):
 
 
 def _home(hw, vw, misc, mask):
-    """The probe window's first entry (csrc/mcts.hip, the select step's cache probe), in numpy uint64 arithmetic."""
+    """The probe window's first entry (csrc/mcts_step.hip, the select step's cache probe), in numpy uint64 arithmetic."""
     u = np.uint64
     with np.errstate(over="ignore"):
         h = hw * u(0x9E3779B97F4A7C15) ^ vw * u(0xC2B2AE3D27D4EB4F) ^ misc.astype(np.uint64) * u(0x165667B19E3779F9)
@@ -416,7 +416,7 @@ def test_pv_mcts_engine_refresh_after_in_place_update(dev, monkeypatch):
 
 # ------------------------------------------------------------------ D: launch options that change geometry only
 OPTION_DEFAULTS = dict(step_waves=8, trunk_grid=0, trunk_delay_min_boards=2048, trunk_phase_delay=100, trunk_prio=-1, step_prio=1,
-                       heads_prio=3, use_graph=1)     # csrc/mcts.hip, csrc/gcn_trunk_split.hip: the g_* initialisers
+                       heads_prio=3, use_graph=1)     # csrc/mcts.hip, csrc/mcts_step.hip, csrc/gcn_trunk_split.hip: the g_* initialisers
 OPTION_SETTINGS = [dict(step_waves=1), dict(step_waves=2), dict(step_waves=4),
                    dict(trunk_grid=1), dict(trunk_grid=7), dict(trunk_grid=100),
                    dict(trunk_delay_min_boards=1, trunk_phase_delay=0), dict(trunk_delay_min_boards=1),

@@ -890,7 +890,7 @@ def test_predict_contract(dev):
 
 
 def _root_children(eng):
-    """Root children of every game after a search, straight from the tree pool (csrc/mcts.hip NodeRec, 32 bytes:
+    """Root children of every game after a search, straight from the tree pool (csrc/mcts_tree.hpp NodeRec, 32 bytes:
     f64 w | f32 p | u32 action || i32 n | u32 first_child + (count << 24) | f32 q | f32 C_PUCT * p): (priors, visits, actions) per game."""
     G, cap = eng.G, eng.node_cap
     raw = eng.t["node_rec"].view(torch.uint8).view(G, cap, 32).cpu().numpy()
@@ -993,7 +993,7 @@ def test_evaluation_games_match_reference(dev, N):
 
 @pytest.mark.parametrize("depth", [0, 1, 2, 5])
 def test_step_hand_over_points_bit_identical(dev, depth):
-    """The simulation step (csrc/mcts.hip) takes one load round and applies the previous simulation's updates in registers to
+    """The simulation step (csrc/mcts_step.hip) takes one load round and applies the previous simulation's updates in registers to
     whatever the descent loads; once a path gets deeper than `step_fast_depth` (61 by default, i.e. never in practice) it
     flushes them and goes on reading memory.  With the limit at 0 (memory from the root), 1, 2 and 5 every hand-over point
     is exercised: each must reproduce the reference's traces, self-play games and evaluation games bit for bit."""

@@ -1,4 +1,4 @@
-"""Root exploration noise on the device (csrc/mcts.hip engine_root_noise_kernel; include/aqgnn.h "root exploration noise"): the mix
+"""Root exploration noise on the device (csrc/mcts_move.hip engine_root_noise_kernel; include/aqgnn.h "root exploration noise"): the mix
 bit for bit against its numpy statement, searches and whole games bit for bit against the oracle's PV-MCTS with a model that mixes
 at the root, the generator against its numpy mirror, independence from slots and launch geometry, the evaluation cache kept clean,
 and noise off = the engine as it was."""

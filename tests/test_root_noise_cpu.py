@@ -16,7 +16,7 @@ MAX_LEGAL = 136
 
 # ------------------------------------------------------------------ the mix, stated in numpy (imported by the GPU tests)
 def wave_sum_f32(vals):
-    """The f32 sum as a 64-lane wavefront forms it (csrc/mcts.hip wave_sum_f behind the lanes' own partial sums): lane l adds its
+    """The f32 sum as a 64-lane wavefront forms it (csrc/mcts_tree.hpp wave_sum_f behind the lanes' own partial sums): lane l adds its
     entries l, l + 64, l + 128 in that order, then the xor butterfly from distance 32 down to 1."""
     v = np.zeros(192, dtype=np.float32)
     v[:len(vals)] = np.asarray(vals, dtype=np.float32)

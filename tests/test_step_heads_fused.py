@@ -1,4 +1,4 @@
-"""Heads inside the MCTS step kernel (csrc/mcts.hip engine_step_fast_kernel<N, CACHE, true>, option "step_heads"): the fused form --
+"""Heads inside the MCTS step kernel (csrc/mcts_step.hip engine_step_fast_kernel<N, CACHE, true>, option "step_heads"): the fused form --
 step -> trunk per simulation, each step workgroup computing policy and value of its own eight leaves from the pooled rows -- against
 the three-launch form (step -> trunk -> gcn_heads_mm_kernel) in one process, with the same seeds and weights.  Every comparison is
 exact equality: both forms run the same heads arithmetic (csrc/gcn_heads_split.hpp) on the same pooled rows."""

@@ -306,7 +306,7 @@ def test_trained_weights_reach_the_engine(dev, cache):
 
 
 def _sample(visits, u):
-    """The engine's move rule at temperature 1 (csrc/mcts.hip engine_finish_move_kernel: np.random.choice over n / sum n)."""
+    """The engine's move rule at temperature 1 (csrc/mcts_move.hip engine_finish_move_kernel: np.random.choice over n / sum n)."""
     x = visits.astype(np.float64)
     tot = x.sum()
     last = 0.0

@@ -16,7 +16,7 @@ recs = g["states"][[0, 5, 40, 333, 1200, 2600, 5000]]
 oracle = og.OracleModel(params)
 pol, val = model.forward_states(torch.from_numpy(recs).to(dev))
 pol = pol.cpu().numpy()
-for fd in (0, 61):             # the step's memory path from the root / its register path (csrc/mcts.hip)
+for fd in (0, 61):             # the step's memory path from the root / its register path (csrc/mcts_step.hip)
     _lib.set_option("step_fast_depth", fd)
     eng = BatchedSelfPlay(model, num_games=recs.shape[0], sims=10, record_history=False)
     eng.search(recs); torch.cuda.synchronize()
