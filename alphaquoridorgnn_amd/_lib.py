@@ -144,10 +144,12 @@ SIGNATURES = {
     "aqg_engine_reset": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),
     "aqg_engine_clear_eval_cache": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),
     "aqg_engine_move": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
+    "aqg_engine_move_targets": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _vp]),
     "aqg_engine_search": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_engine_begin_move": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),
     "aqg_engine_step": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.c_int, _c.c_int, _vp]),
     "aqg_engine_finish_move": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
+    "aqg_engine_finish_move_targets": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _vp]),
     "aqg_engine_set_roots": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_engine_root_visits": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp, _vp, _vp]),
     "aqg_engine_root_noise": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),
@@ -174,6 +176,7 @@ SIGNATURES = {
     "aqg_augment_gather": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_int, _vp, _vp, _vp,
                                       _vp]),
     "aqg_replay_append": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
+    "aqg_replay_append_blend": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _f32, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
     "aqg_host_legal_actions": (_c.c_int, [_c.c_int, _vp, _vp]),
     "aqg_host_next": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp]),
     "aqg_host_shortest_path": (_c.c_int, [_c.c_int, _vp]),

@@ -205,7 +205,11 @@ int aqg_engine_clear_eval_cache(const aqg_engine* e, void* stream) {
 }
 int aqg_engine_move(const aqg_engine* e, const double* uniforms, void* stream) {
     if (!e || !uniforms) return fail("aqg_engine_move: null argument");
-    return engine_move(*e, uniforms, (hipStream_t)stream);
+    return engine_move(*e, uniforms, 0, nullptr, (hipStream_t)stream);
+}
+int aqg_engine_move_targets(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value, void* stream) {
+    if (!e || !uniforms) return fail("aqg_engine_move_targets: null argument");
+    return engine_move(*e, uniforms, temperature_plies, hist_value, (hipStream_t)stream);
 }
 int aqg_engine_begin_move(const aqg_engine* e, void* stream) {
     if (!e) return fail("aqg_engine_begin_move: null engine");
@@ -217,7 +221,12 @@ int aqg_engine_step(const aqg_engine* e, int do_expand, int do_select, void* str
 }
 int aqg_engine_finish_move(const aqg_engine* e, const double* uniforms, void* stream) {
     if (!e || !uniforms) return fail("aqg_engine_finish_move: null argument");
-    return engine_finish_move(*e, uniforms, (hipStream_t)stream);
+    return engine_finish_move(*e, uniforms, 0, nullptr, (hipStream_t)stream);
+}
+int aqg_engine_finish_move_targets(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                                   void* stream) {
+    if (!e || !uniforms) return fail("aqg_engine_finish_move_targets: null argument");
+    return engine_finish_move(*e, uniforms, temperature_plies, hist_value, (hipStream_t)stream);
 }
 int aqg_engine_set_roots(const aqg_engine* e, const uint8_t* root_states72, void* stream) {
     if (!e || !root_states72) return fail("aqg_engine_set_roots: null argument");
@@ -383,6 +392,12 @@ int aqg_replay_append(int board_size, int policy_size, const uint8_t* states72, 
                       float* ring_z, void* stream) {
     return launch_replay_append(board_size, policy_size, states72, visits, z_i8, pi, z_f32, n, capacity, head, ring72, ring_pi, ring_z,
                                 (hipStream_t)stream);
+}
+int aqg_replay_append_blend(int board_size, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8,
+                            const float* search_value, float blend, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
+                            float* ring_z, void* stream) {
+    return launch_replay_append_blend(board_size, policy_size, states72, visits, z_i8, search_value, blend, n, capacity, head, ring72,
+                                      ring_pi, ring_z, (hipStream_t)stream);
 }
 
 }  // extern "C"

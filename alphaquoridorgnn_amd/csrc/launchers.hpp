@@ -95,9 +95,9 @@ int engine_reset(const aqg_engine& e, hipStream_t st);
 int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st);
 int engine_begin_move(const aqg_engine& e, hipStream_t st);
 int engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t st);
-int engine_finish_move(const aqg_engine& e, const double* uniforms, hipStream_t st);
+int engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st);
 int engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
-int engine_move(const aqg_engine& e, const double* uniforms, hipStream_t st);
+int engine_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st);
 int engine_search(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
 int engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st);
 int engine_refill(const aqg_engine& e, hipStream_t st);
@@ -115,7 +115,7 @@ void launch_engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStr
 void launch_engine_begin_move(const aqg_engine& e, hipStream_t st);
 int launch_engine_fake_eval(const aqg_engine& e, hipStream_t st);
 int launch_engine_root_noise(const aqg_engine& e, hipStream_t st);
-int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, hipStream_t st);
+int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st);
 void launch_engine_refill(const aqg_engine& e, hipStream_t st);
 int launch_engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st);
 void launch_engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st);
@@ -184,6 +184,9 @@ int launch_augment_gather(int N, int policy_size, const uint8_t* states72, const
 // ---- replay.hip
 int launch_replay_append(int N, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8, const float* pi,
                          const float* z_f32, int n, int capacity, int head, uint8_t* ring72, float* ring_pi, float* ring_z,
-                         hipStream_t st);
+                         hipStream_t st, const float* search_value = nullptr, float blend = 0.f);
+int launch_replay_append_blend(int N, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8,
+                               const float* search_value, float blend, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
+                               float* ring_z, hipStream_t st);
 
 }  // namespace aqg

@@ -177,15 +177,23 @@ static int run_sims(const aqg_engine& e, hipStream_t st) {
 }
 
 // the end of a move: choose and apply (finish_move), then hand the idle slots their next games (refill) while a quota is left to play
-static int finish_and_refill(const aqg_engine& e, const double* uniforms, hipStream_t st) {
-    if (int r = launch_engine_finish_move(e, uniforms, st)) return r;
+// (outside the captured graph, so the two target options are plain arguments: 0 / nullptr = off)
+static int finish_and_refill(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st) {
+    if (int r = launch_engine_finish_move(e, uniforms, temperature_plies, hist_value, st)) return r;
     if (e.quota > e.num_games) launch_engine_refill(e, st);
     return check_launch("engine_finish_move_kernel");
 }
 
-static int do_move(const aqg_engine& e, const double* uniforms, hipStream_t st) {
+// what the _targets entry points refuse, before anything is launched
+static int validate_targets(const aqg_engine& e, int temperature_plies, const float* hist_value) {
+    if (temperature_plies < 0) return fail("temperature_plies must be >= 0");
+    if (hist_value && e.max_plies <= 0) return fail("hist_value needs a history (max_plies > 0)");
+    return 0;
+}
+
+static int do_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st) {
     if (int r = run_sims(e, st)) return r;
-    return finish_and_refill(e, uniforms, st);
+    return finish_and_refill(e, uniforms, temperature_plies, hist_value, st);
 }
 
 // External-evaluator mode (prior_mode 2): the caller runs the simulation loop itself -- begin, then per simulation
@@ -205,9 +213,10 @@ int engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t s
     return check_launch("engine_step_fast_kernel");
 }
 
-int engine_finish_move(const aqg_engine& e, const double* uniforms, hipStream_t st) {
+int engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st) {
     if (int r = validate(e)) return r;
-    return finish_and_refill(e, uniforms, st);
+    if (int r = validate_targets(e, temperature_plies, hist_value)) return r;
+    return finish_and_refill(e, uniforms, temperature_plies, hist_value, st);
 }
 
 int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st) {
@@ -224,9 +233,10 @@ int engine_reset(const aqg_engine& e, hipStream_t st) {
     return check_launch("engine_reset_kernel");
 }
 
-int engine_move(const aqg_engine& e, const double* uniforms, hipStream_t st) {
+int engine_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st) {
     if (int r = validate(e)) return r;
-    return do_move(e, uniforms, st);
+    if (int r = validate_targets(e, temperature_plies, hist_value)) return r;
+    return do_move(e, uniforms, temperature_plies, hist_value, st);
 }
 
 int engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st) {

@@ -257,9 +257,13 @@ __device__ __forceinline__ void engine_transition(const aqg_engine& e, int g, in
 
 // ------------------------------------------------------------------------------------------------
 // finish move: visits -> policy (pv_mcts.py:88-95), record, np.random.choice, next(), terminal handling
+// The two training-target options of aqgnn.h ("self-play targets") are kernel arguments, not engine fields -- this launch is not part
+// of the captured graph: temperature_plies K > 0 = a root at ply >= K takes the first maximum, as temperature 0 does; hist_value !=
+// nullptr = the root's search value w / n from the mover's side, f32 [quota, max_plies] beside hist_action.  (0, nullptr) = neither.
 // ------------------------------------------------------------------------------------------------
 template <int N>
-__global__ __launch_bounds__(256) void engine_finish_move_kernel(aqg_engine e, const double* __restrict__ uniforms) {
+__global__ __launch_bounds__(256) void engine_finish_move_kernel(aqg_engine e, const double* __restrict__ uniforms, int temperature_plies,
+                                                                 float* __restrict__ hist_value) {
     constexpr int A = Geo<N>::A;
     const int lane = threadIdx.x & 63;
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -279,11 +283,17 @@ __global__ __launch_bounds__(256) void engine_finish_move_kernel(aqg_engine e, c
         for (int i = lane; i < cnt; i += 64) hv[nodes[first + i].action] = (uint16_t)nodes[first + i].n;
     }
     if (lane != 0) return;
+    if (hist_value && ply < e.max_plies) {                     // f32(w / n): the bits of -nodes[0].q
+        const double w = nodes[0].w;
+        const int n = nodes[0].n;
+        hist_value[(size_t)k * e.max_plies + ply] = n ? (float)(w / (double)n) : 0.0f;
+    }
 
     int chosen = -1;
     if (cnt > 0) {
         int idx = 0;
-        if (e.temperature == 0.f) {                            // one-hot at the first maximum, then choice(p=one-hot)
+        const bool late = temperature_plies > 0 && (int)s.plies >= temperature_plies;      // the schedule: arg-max from ply K on
+        if (e.temperature == 0.f || late) {                    // one-hot at the first maximum, then choice(p=one-hot)
             int bestn = -1;
             for (int i = 0; i < cnt; ++i) { const int n = nodes[first + i].n; if (n > bestn) { bestn = n; idx = i; } }
         } else {
@@ -453,9 +463,10 @@ int launch_engine_root_noise(const aqg_engine& e_in, hipStream_t st) {
     });
 }
 
-int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, hipStream_t st) {
+int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st) {
     return for_board_size(e.board_size, [&](auto n) {
-        hipLaunchKernelGGL(engine_finish_move_kernel<decltype(n)::value>, dim3((e.num_games + 3) / 4), dim3(256), 0, st, e, uniforms);
+        hipLaunchKernelGGL(engine_finish_move_kernel<decltype(n)::value>, dim3((e.num_games + 3) / 4), dim3(256), 0, st, e, uniforms,
+                           temperature_plies, hist_value);
         return 0;
     });
 }

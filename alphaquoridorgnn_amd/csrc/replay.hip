@@ -11,6 +11,11 @@
 // a fast-math flag.  The 72 record bytes are copied verbatim: no byte is interpreted or used as an address.  No atomics, no scratch;
 // every loop ends on n.
 //
+// Blended value target (aqg_replay_append_blend; template switch BLEND of the one kernel, counts form only): the lanes that write
+// ring_z also load the row's search value v and write keep * f32(z) + blend * v, keep = 1 - blend -- two f32 products and one f32
+// sum, each rounded, which is why this unit is compiled without fma contraction.  BLEND = false is the plain kernel, instruction
+// for instruction.
+//
 // Loads of the counts: per-row 16-bit loads, one count per lane and pass.  The other candidate -- the workgroup's 16 rows read as ONE
 // 32A-byte span with 16-byte loads and staged through LDS -- was timed beside this one on an MI355X (tools/replay_window_time.py with
 // ALT_LIB; profiles/replay_window.log, where it is the "ALT_LIB" line): 62.6 against 67.4 us at 163,840 rows of 9x9 (-7 %), inside
@@ -22,6 +27,8 @@
 #ifdef __FAST_MATH__
 #error "replay.hip: pi = v / tot must be the correctly rounded f32 division (no fast-math)"
 #endif
+// the blend must be evaluated exactly as written: x = keep * z, y = blend * v, x + y (replay.blend_targets is the same in numpy)
+#pragma clang fp contract(off)
 
 namespace aqg {
 
@@ -35,11 +42,12 @@ __device__ __forceinline__ int wave_sum_int(int v) {
     return v;
 }
 
-template <int N>
+template <int N, bool BLEND>
 __global__ __launch_bounds__(RPL_WAVES * WAVE) void replay_append_kernel(
         const uint8_t* __restrict__ states72, const uint16_t* __restrict__ visits, const int8_t* __restrict__ z_i8,
         const float* __restrict__ pi, const float* __restrict__ z_f32, int n, int capacity, int head,
-        uint8_t* __restrict__ ring72, float* __restrict__ ring_pi, float* __restrict__ ring_z) {
+        uint8_t* __restrict__ ring72, float* __restrict__ ring_pi, float* __restrict__ ring_z,
+        const float* __restrict__ search_value, float blend) {
     constexpr int A = Geo<N>::A;
     constexpr int PI_PASSES = (A + WAVE - 1) / WAVE;           // 1, 1, 2, 4 at 3x3 .. 9x9
     const int first = blockIdx.x * RPL_ROWS;                    // < n: the grid is ceil(n / RPL_ROWS)
@@ -50,7 +58,15 @@ __global__ __launch_bounds__(RPL_WAVES * WAVE) void replay_append_kernel(
         const size_t s = (size_t)head + (size_t)(first + q);
         return s >= (size_t)capacity ? s - (size_t)capacity : s;
     };
-    if (t < rows) ring_z[slot_of(t)] = visits ? (float)z_i8[first + t] : z_f32[first + t];
+    if (t < rows) {
+        float zt = visits ? (float)z_i8[first + t] : z_f32[first + t];
+        if (BLEND) {
+            const float keep = 1.0f - blend;
+            const float x = keep * zt, y = blend * search_value[first + t];
+            zt = x + y;
+        }
+        ring_z[slot_of(t)] = zt;
+    }
     const int wave = t >> 6, lane = t & 63;
     for (int q0 = wave * RPL_GROUP; q0 < rows; q0 += RPL_WAVES * RPL_GROUP) {
         uint32_t pv[RPL_GROUP][PI_PASSES];      // a count, or the bits of a finished f32
@@ -100,7 +116,7 @@ static bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes
 
 int launch_replay_append(int N, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8, const float* pi,
                          const float* z_f32, int n, int capacity, int head, uint8_t* ring72, float* ring_pi, float* ring_z,
-                         hipStream_t st) {
+                         hipStream_t st, const float* search_value, float blend) {
     if (!board_size_supported(N)) return fail("aqg_replay_append: unsupported board_size (odd 3..9)");
     const int A = N * N + 2 * (N - 1) * (N - 1);
     if (policy_size != A) return fail("aqg_replay_append: policy_size is not the board's action count N^2 + 2 (N - 1)^2");
@@ -122,12 +138,29 @@ int launch_replay_append(int N, int policy_size, const uint8_t* states72, const 
         for (int i = 0; i < 3; ++i)
             if (overlap(rings[o], (size_t)capacity * ring_bytes[o], srcs[i], (size_t)n * src_bytes[i]))
                 return fail("aqg_replay_append: a ring overlaps a source");
+    for (int o = 0; o < 3; ++o)
+        if (overlap(rings[o], (size_t)capacity * ring_bytes[o], search_value, (size_t)n * sizeof(float)))
+            return fail("aqg_replay_append_blend: a ring overlaps search_value");
     const dim3 grid((unsigned)(((size_t)n + RPL_ROWS - 1) / RPL_ROWS)), block(RPL_WAVES * WAVE);
     return for_board_size(N, [&](auto nn) {
-        hipLaunchKernelGGL(replay_append_kernel<decltype(nn)::value>, grid, block, 0, st, states72, visits, z_i8, pi, z_f32, n, capacity,
-                           head, ring72, ring_pi, ring_z);
+        if (search_value)
+            hipLaunchKernelGGL((replay_append_kernel<decltype(nn)::value, true>), grid, block, 0, st, states72, visits, z_i8, pi, z_f32, n,
+                               capacity, head, ring72, ring_pi, ring_z, search_value, blend);
+        else
+            hipLaunchKernelGGL((replay_append_kernel<decltype(nn)::value, false>), grid, block, 0, st, states72, visits, z_i8, pi, z_f32, n,
+                               capacity, head, ring72, ring_pi, ring_z, nullptr, 0.f);
         return check_launch("replay_append_kernel");
     });
+}
+
+// the counts form with a blended value target: what it refuses of its own, then aqg_replay_append's checks and launch
+int launch_replay_append_blend(int N, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8,
+                               const float* search_value, float blend, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
+                               float* ring_z, hipStream_t st) {
+    if (!(blend >= 0.f && blend <= 1.f)) return fail("aqg_replay_append_blend: blend must be in [0, 1]");      // NaN fails both
+    if (!search_value && n != 0) return fail("aqg_replay_append_blend: search_value must be given");      // n == 0: no pointer is looked at
+    return launch_replay_append(N, policy_size, states72, visits, z_i8, nullptr, nullptr, n, capacity, head, ring72, ring_pi, ring_z, st,
+                                search_value, blend);
 }
 
 }  // namespace aqg

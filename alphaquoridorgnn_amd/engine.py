@@ -49,6 +49,16 @@ def refuse_root_noise(what, **options):
         raise ValueError(f"{what} never adds root exploration noise: {', '.join(bad)} is a self-play option")
 
 
+def check_target_options(temperature_plies, record_search_value=False, record_history=True):
+    """Validate the self-play target options (include/aqgnn.h, "self-play targets"): temperature_plies an integer >= 0 (0 = off);
+    record_search_value needs the history it is a column of.  Returns (temperature_plies, record_search_value)."""
+    if isinstance(temperature_plies, bool) or int(temperature_plies) != temperature_plies or not 0 <= int(temperature_plies) < 2 ** 31:
+        raise ValueError(f"temperature_plies must be an integer >= 0, not {temperature_plies!r}")
+    if record_search_value and not record_history:
+        raise ValueError("record_search_value needs record_history: the search value is a column of the history")
+    return int(temperature_plies), bool(record_search_value)
+
+
 def _mix64_int(z):
     """The splitmix64 finaliser on a Python int (include/aqgnn.h)."""
     z &= _MASK64
@@ -134,7 +144,7 @@ def draw_root_noise(seed, k, ply, count, alpha, return_exhausted=False):
 class BatchedSelfPlay:
     def __init__(self, model=None, num_games=2048, sims=50, board_size=BOARD_SIZE, device=None, temperature=1.0,
                  c_puct=1.25, evaluator="gnn", fake_bias=0, seed=0, record_history=True, quota=None, eval_cache_slots=None,
-                 root_noise_eps=0.0, root_noise_alpha=None, root_noise_seed=None):
+                 root_noise_eps=0.0, root_noise_alpha=None, root_noise_seed=None, temperature_plies=0, record_search_value=False):
         """model: GraphPolicyValueNetwork/GNNNetwork (evaluator='gnn'); evaluator='fake' runs the integer-hash
         evaluator used by the parity tests (oracle/mcts.py FakeModel); evaluator='external' calls `model.predict(state,
         device)` -- ANY object honouring the reference's BaseNetwork contract (BaseNetwork.py:36-40), e.g. a stock CNN --
@@ -150,7 +160,12 @@ class BatchedSelfPlay:
         root_noise_eps (0 = off, the default: nothing changes): every move mixes Dir(root_noise_alpha) into the root's priors on the
         device, p' = (1 - eps) p + eps eta (include/aqgnn.h, "root exploration noise").  root_noise_alpha None = 10 / (N^2 + 2 (N - 1)^2),
         the usual "10 / typical number of moves" rule; root_noise_seed None = derived from `seed`.  The noise of a game's root is
-        keyed by (seed, game index, ply) -- draw_root_noise is the generator in numpy -- unless move() / search() are given a table."""
+        keyed by (seed, game index, ply) -- draw_root_noise is the generator in numpy -- unless move() / search() are given a table.
+        temperature_plies K (0 = off, the default): a root at ply < K is sampled at `temperature` as always, one at ply >= K takes
+        the first maximum of the visit counts; the recorded visit rows do not change, only the choice.  record_search_value (needs
+        record_history): every searched move also records the root's search value w / n from the mover's side, float32, beside its
+        history row -- history_values().  With both off move() makes the calls it always made."""
+        self.temperature_plies, self.record_search_value = check_target_options(temperature_plies, record_search_value, record_history)
         self.root_noise_eps, self.root_noise_alpha = check_root_noise(
             root_noise_eps, default_root_noise_alpha(board_size) if root_noise_alpha is None else root_noise_alpha)
         self.root_noise_seed = default_root_noise_seed(seed) if root_noise_seed is None else int(root_noise_seed) & _MASK64
@@ -203,6 +218,8 @@ class BatchedSelfPlay:
         t["hist_state72"] = z((Q, hp, 72), torch.uint8)
         t["hist_visits"] = z((Q, hp, self.A), torch.int16)
         t["hist_action"] = z((Q, hp), torch.uint8)
+        if self.record_search_value:
+            t["hist_value"] = z((Q, hp), torch.float32)    # rows of apply_actions are never written: they read 0
         t["counters"] = z((8,), torch.int32)
         t["stat_leaf_evals"] = z((G,), torch.int32)
         t["stat_terminal_sims"] = z((G,), torch.int32)
@@ -299,9 +316,18 @@ class BatchedSelfPlay:
         else:
             uniforms = torch.as_tensor(uniforms, dtype=torch.float64).to(self.dev).contiguous()
         self._u = uniforms  # keep alive until the stream has consumed it
+        targets = self.temperature_plies or self.record_search_value          # either option: the _targets entry points
+        extra = (self.temperature_plies, _lib.ptr(self.t.get("hist_value")))
         if self.evaluator == "external":
             self._external_sims()
-            _lib.check(self.lib.aqg_engine_finish_move(ctypes.byref(self.e), _lib.ptr(uniforms), self._stream()), "aqg_engine_finish_move")
+            if targets:
+                _lib.check(self.lib.aqg_engine_finish_move_targets(ctypes.byref(self.e), _lib.ptr(uniforms), *extra, self._stream()),
+                           "aqg_engine_finish_move_targets")
+            else:
+                _lib.check(self.lib.aqg_engine_finish_move(ctypes.byref(self.e), _lib.ptr(uniforms), self._stream()), "aqg_engine_finish_move")
+        elif targets:
+            _lib.check(self.lib.aqg_engine_move_targets(ctypes.byref(self.e), _lib.ptr(uniforms), *extra, self._stream()),
+                       "aqg_engine_move_targets")
         else:
             _lib.check(self.lib.aqg_engine_move(ctypes.byref(self.e), _lib.ptr(uniforms), self._stream()), "aqg_engine_move")
         self.moves_done += 1
@@ -443,13 +469,24 @@ class BatchedSelfPlay:
         return priors, count
 
     # ------------------------------------------------------------------ history
-    def history_tensors(self):
-        """(states72 u8 [P,72], visits i16 [P,A], z i8 [P]) for all finished games on this rank, game-major (game index =
-        order in which the games were started)."""
+    def _history_valid(self):
+        """(valid bool [quota, hp], ply index [1, hp]): the recorded rows of the finished games."""
         plies = self.t["game_plies"].long()
         hp = self.t["hist_state72"].shape[1]
         idx = torch.arange(hp, device=self.dev).unsqueeze(0)
-        valid = (idx < plies.unsqueeze(1)) & (self.t["game_done"] != 0).unsqueeze(1)
+        return (idx < plies.unsqueeze(1)) & (self.t["game_done"] != 0).unsqueeze(1), idx
+
+    def history_values(self):
+        """The recorded search values, float32 [P], row-aligned with history_tensors(): the root's w / n from the mover's side after
+        the move's simulations (0 for a move that was applied, not searched).  Needs record_search_value."""
+        if not self.record_search_value:
+            raise ValueError("history_values needs record_search_value=True")
+        return self.t["hist_value"][self._history_valid()[0]]
+
+    def history_tensors(self):
+        """(states72 u8 [P,72], visits i16 [P,A], z i8 [P]) for all finished games on this rank, game-major (game index =
+        order in which the games were started)."""
+        valid, idx = self._history_valid()
         z0 = self.t["game_result"].to(torch.int8).unsqueeze(1)
         sign = torch.where(idx % 2 == 0, 1, -1).to(torch.int8)      # z alternates down the history (self_play.py:63-66)
         z = (z0 * sign)[valid]
@@ -606,6 +643,19 @@ class MultiSetSelfPlay:
                 x.record_stream(cur)              # the caching allocator must not recycle them under the concatenation
         return tuple(torch.cat([p[j] for p in parts], 0) for j in range(3))
 
+    def history_values(self):
+        """The sets' history_values() in set order: float32 [P], row-aligned with history_tensors()."""
+        parts = []
+        for _, eng in self._each():
+            parts.append(eng.history_values())
+        self.sync()
+        cur = torch.cuda.current_stream(self.dev)
+        for st in self.streams:
+            cur.wait_stream(st)
+        for p in parts:
+            p.record_stream(cur)
+        return torch.cat(parts, 0)
+
 
 class TwoEngineMatch:
     """`num_games` games between two sides, game i with side (i % 2) moving first, on two engines: engine `first` holds the games
@@ -648,20 +698,22 @@ class TwoEngineMatch:
         return [float(per[i % 2][i // 2]) for i in range(self.num_games)]
 
 
-def gather_history(states72, visits, z, group=None, force_collective=None):
+def gather_history(states72, visits, z, group=None, force_collective=None, values=None):
     """The one exchange step per generation: all-gather the ragged (s, pi, z) tuples of every rank.
     Counts are gathered first, payloads are padded to the max count (RCCL needs equal sizes) and trimmed after.
     Works on any torch.distributed backend (nccl == RCCL on ROCm; gloo in the CPU tests).
     force_collective (default: AQG_DIST_FORCE_GROUP=1): run the two collectives at world size 1 as well instead of returning the
-    inputs -- the RCCL code path on the one GPU a developer box has (the result is the same rows, bit for bit)."""
+    inputs -- the RCCL code path on the one GPU a developer box has (the result is the same rows, bit for bit).
+    values (float32 [P], engine.history_values): every packed row carries its four bytes as well, and a fourth tensor is returned."""
     import torch.distributed as dist
+    same = (states72, visits, z) if values is None else (states72, visits, z, values)
     if not (dist.is_available() and dist.is_initialized()):
-        return states72, visits, z
+        return same
     if force_collective is None:
         from .distributed import force_group
         force_collective = force_group()
     if dist.get_world_size(group) == 1 and not force_collective:
-        return states72, visits, z
+        return same
     W = dist.get_world_size(group)
     dev = states72.device
     n = torch.tensor([states72.shape[0]], dtype=torch.int64, device=dev)
@@ -670,13 +722,15 @@ def gather_history(states72, visits, z, group=None, force_collective=None):
     counts = [int(c.item()) for c in counts]
     m = max(counts)
     A = visits.shape[1]
-    row = 72 + 2 * A + 1
+    row = 72 + 2 * A + 1 + (0 if values is None else 4)
     buf = torch.zeros((m, row), dtype=torch.uint8, device=dev)
     k = states72.shape[0]
     if k:
         buf[:k, :72] = states72
         buf[:k, 72:72 + 2 * A] = visits.contiguous().view(torch.uint8).view(k, 2 * A)
         buf[:k, 72 + 2 * A] = z.view(torch.uint8)
+        if values is not None:
+            buf[:k, 73 + 2 * A:] = values.to(torch.float32).contiguous().view(torch.uint8).view(k, 4)
     out = torch.empty((W * m, row), dtype=torch.uint8, device=dev)
     dist.all_gather_into_tensor(out, buf, group=group)
     out = out.view(W, m, row)
@@ -685,4 +739,6 @@ def gather_history(states72, visits, z, group=None, force_collective=None):
     s = allrows[:, :72].contiguous()
     v = allrows[:, 72:72 + 2 * A].contiguous().view(torch.int16).view(-1, A)
     zz = allrows[:, 72 + 2 * A].contiguous().view(torch.int8)
+    if values is not None:
+        return s, v, zz, allrows[:, 73 + 2 * A:].contiguous().view(torch.float32).view(-1)
     return s, v, zz

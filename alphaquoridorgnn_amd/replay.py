@@ -9,6 +9,9 @@ nothing here reads anything back from the device.
 
 `append_reference` is the kernel's statement in numpy on host arrays; a window on the CPU (device None or 'cpu') runs the same
 bookkeeping over it.
+
+Blended value target (`append_counts(..., search_value=q, value_blend=L)`, aqg_replay_append_blend): z' = (1 - L) z + L q with q the
+search value the engine recorded beside the row (engine.history_values).  `blend_targets` is the arithmetic in numpy.
 """
 import pickle
 
@@ -23,13 +26,41 @@ def policy_size(board_size):
     return board_size ** 2 + 2 * (board_size - 1) ** 2
 
 
-def append_reference(board_size, states72, visits, z_i8, pi, z_f32, head, ring72, ring_pi, ring_z):
+def check_value_blend(blend):
+    """Validate a value blend as the library does, on the f32 value the kernel is given: in [0, 1], not NaN.  Returns it as a float."""
+    blend = float(np.float32(blend))
+    if not 0.0 <= blend <= 1.0:
+        raise ValueError(f"value_blend must be in [0, 1] as a float32, not {blend}")
+    return blend
+
+
+def blend_targets(z_i8, search_value, blend):
+    """The blended value target of aqg_replay_append_blend in numpy, float32 [n]: keep * float32(z) + blend * v with keep =
+    float32(1) - blend -- one f32 subtraction, two f32 products and one f32 sum, each rounded (no fused multiply-add).  z_i8 the
+    outcomes (any integer or float array of -1 / 0 / 1), search_value float32 [n]."""
+    b = np.float32(check_value_blend(blend))
+    keep = np.float32(1.0) - b
+    z = np.asarray(z_i8).astype(np.float32)
+    v = np.asarray(search_value)
+    if v.dtype != np.float32 or v.shape != z.shape:
+        raise ValueError("blend_targets: search_value must be float32 with one value per outcome")
+    x = (keep * z).astype(np.float32)
+    y = (b * v).astype(np.float32)
+    return (x + y).astype(np.float32)
+
+
+def append_reference(board_size, states72, visits, z_i8, pi, z_f32, head, ring72, ring_pi, ring_z, search_value=None, value_blend=0.0):
     """aqg_replay_append in numpy, on host arrays, in place (include/aqgnn.h, "replay window"): source row i goes to ring slot
     (head + i) % capacity, n and capacity being the row counts of states72 and ring72.  Counts form (visits [n,A] int16 or uint16,
     read as UNSIGNED, and z_i8 [n] int8; pi and z_f32 None): ring_pi = float32(float64(v) / float64(tot)) with tot the row's integer
     sum, zeros where tot == 0, ring_z = float32(z).  Rows form (pi [n,A] float32, z_f32 [n] float32; the other two None): a copy.
-    The 72 record bytes are copied verbatim.  Refuses what the C entry point refuses, with ValueError."""
+    The 72 record bytes are copied verbatim.  search_value (float32 [n]; counts form only) makes it aqg_replay_append_blend:
+    ring_z = blend_targets(z_i8, search_value, value_blend).  Refuses what the C entry points refuse, with ValueError."""
     A = policy_size(board_size)
+    if search_value is None and value_blend != 0.0:
+        raise ValueError("append_reference: a value_blend needs search_value")
+    if search_value is not None:
+        check_value_blend(value_blend)
     if board_size not in (3, 5, 7, 9):
         raise ValueError("append_reference: unsupported board_size (odd 3..9)")
     n, capacity = int(states72.shape[0]), int(ring72.shape[0])
@@ -37,12 +68,15 @@ def append_reference(board_size, states72, visits, z_i8, pi, z_f32, head, ring72
     finished = pi is not None and z_f32 is not None and visits is None and z_i8 is None
     if not counts and not finished:
         raise ValueError("append_reference: give the counts form (visits, z_i8) or the rows form (pi, z_f32), whole, and not both")
+    if search_value is not None and not counts:
+        raise ValueError("append_reference: search_value goes with the counts form (visits, z_i8)")
     if capacity < 1 or not 0 <= head < capacity or n > capacity:
         raise ValueError("append_reference: needs capacity >= 1, 0 <= head < capacity and n <= capacity")
     for x, name, dtypes, shape in ((states72, "states72", (np.uint8,), (n, 72)), (ring72, "ring72", (np.uint8,), (capacity, 72)),
                                    (ring_pi, "ring_pi", (np.float32,), (capacity, A)), (ring_z, "ring_z", (np.float32,), (capacity,)),
                                    (visits, "visits", (np.int16, np.uint16), (n, A)), (z_i8, "z_i8", (np.int8,), (n,)),
-                                   (pi, "pi", (np.float32,), (n, A)), (z_f32, "z_f32", (np.float32,), (n,))):
+                                   (pi, "pi", (np.float32,), (n, A)), (z_f32, "z_f32", (np.float32,), (n,)),
+                                   (search_value, "search_value", (np.float32,), (n,))):
         if x is not None and (x.dtype not in dtypes or tuple(x.shape) != shape):
             raise ValueError(f"append_reference: {name} must be {np.dtype(dtypes[0]).name} {list(shape)} ({board_size}x{board_size} board)")
     slots = (head + np.arange(n)) % capacity
@@ -52,7 +86,7 @@ def append_reference(board_size, states72, visits, z_i8, pi, z_f32, head, ring72
         tot = v.sum(axis=1, keepdims=True)
         quotient = v.astype(np.float64) / np.where(tot > 0, tot, 1).astype(np.float64)
         ring_pi[slots] = quotient.astype(np.float32)                # a row without a visit: 0 / 1 = A zeros
-        ring_z[slots] = z_i8.astype(np.float32)
+        ring_z[slots] = z_i8.astype(np.float32) if search_value is None else blend_targets(z_i8, search_value, value_blend)
     else:
         ring_pi[slots] = pi
         ring_z[slots] = z_f32
@@ -161,15 +195,22 @@ class ReplayWindow:
         self._valid += keep
         self._index = (self._start + torch.arange(self._valid, dtype=torch.int64, device=self.device)) % self.capacity
 
-    def _append(self, states72, visits, z_i8, pi, z_f32, m):
+    def _append(self, states72, visits, z_i8, pi, z_f32, m, search_value=None, value_blend=0.0):
         skip, head = self._make_room(m)
         if skip:
-            states72, visits, z_i8, pi, z_f32 = (None if x is None else x[skip:].contiguous() for x in (states72, visits, z_i8, pi, z_f32))
+            states72, visits, z_i8, pi, z_f32, search_value = (None if x is None else x[skip:].contiguous()
+                                                               for x in (states72, visits, z_i8, pi, z_f32, search_value))
         n = m - skip
         r72, rpi, rz = self._rings
         if self.device.type == "cpu":
             h = lambda x: None if x is None else x.numpy()          # noqa: E731   (views: the rings are written in place)
-            append_reference(self.board_size, h(states72), h(visits), h(z_i8), h(pi), h(z_f32), head, h(r72), h(rpi), h(rz))
+            append_reference(self.board_size, h(states72), h(visits), h(z_i8), h(pi), h(z_f32), head, h(r72), h(rpi), h(rz),
+                             h(search_value), value_blend)
+        elif search_value is not None:
+            _lib.check(_lib.load().aqg_replay_append_blend(self.board_size, self.policy_size, _lib.ptr(states72), _lib.ptr(visits),
+                                                           _lib.ptr(z_i8), _lib.ptr(search_value), value_blend, n, self.capacity, head,
+                                                           _lib.ptr(r72), _lib.ptr(rpi), _lib.ptr(rz), _lib.stream_ptr(self.device)),
+                       "aqg_replay_append_blend")
         else:
             _lib.check(_lib.load().aqg_replay_append(self.board_size, self.policy_size, _lib.ptr(states72), _lib.ptr(visits),
                                                      _lib.ptr(z_i8), _lib.ptr(pi), _lib.ptr(z_f32), n, self.capacity, head,
@@ -177,11 +218,22 @@ class ReplayWindow:
                        "aqg_replay_append")
         self._appended(n)
 
-    def append_counts(self, states72, visits, z):
+    def append_counts(self, states72, visits, z, search_value=None, value_blend=0.0):
         """One generation as the engine leaves it (engine.history_tensors / gather_history): states72 uint8 [n,72], visit counts
-        int16 (or uint16; read as unsigned) [n,A], z int8 [n].  pi = counts / their sum, with the bits of the .history route."""
+        int16 (or uint16; read as unsigned) [n,A], z int8 [n].  pi = counts / their sum, with the bits of the .history route.
+        search_value (float32 [n], engine.history_values) with value_blend L in [0, 1]: the value target becomes (1 - L) z + L q
+        (blend_targets; one aqg_replay_append_blend launch).  Without search_value the call is the plain append."""
         (s, v, zz), m = self._checked("append_counts", states72, visits, z, (torch.int16, torch.uint16), torch.int8)
-        self._append(s, v, zz, None, None, m)
+        if search_value is None:
+            if value_blend != 0.0:
+                raise ValueError("ReplayWindow.append_counts: a value_blend needs search_value")
+            return self._append(s, v, zz, None, None, m)
+        value_blend = check_value_blend(value_blend)
+        q = torch.as_tensor(search_value)
+        if q.dtype != torch.float32 or tuple(q.shape) != (m,):
+            raise ValueError(f"ReplayWindow.append_counts: search_value must be a torch.float32 ['n'] tensor with one value per "
+                             f"position; got {q.dtype} {list(q.shape)}")
+        self._append(s, v, zz, None, None, m, q.to(self.device).contiguous(), value_blend)
 
     def append_rows(self, states72, pi, z):
         """One generation of finished rows: states72 uint8 [n,72], pi float32 [n,A], z float32 [n]."""

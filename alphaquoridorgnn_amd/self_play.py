@@ -18,12 +18,18 @@ from .constants import PV_NETWORK_PATH, BOARD_SIZE
 from .engine import BatchedSelfPlay, MultiSetSelfPlay, gather_history
 from .pv_network_gnn import GNNNetwork, POLICY_OUTPUT_SIZE, load_network
 from .pv_network_cnn import CNNNetwork
+from .replay import blend_targets, check_value_blend
 
 SP_GAME_COUNT = 50    # Number of games for self-play (self_play.py:19; 25000 in the original version)
 SP_TEMPERATURE = 1.0  # Temperature parameter for Boltzmann distribution (self_play.py:20)
 # Root exploration noise (the reference has none; engine.BatchedSelfPlay): p' = (1 - eps) p + eps Dir(alpha) at every move's root.
 SP_ROOT_NOISE_EPS = 0.0      # 0 = off: the reference's games
 SP_ROOT_NOISE_ALPHA = None   # None = 10 / (N^2 + 2 (N - 1)^2), the "10 / typical number of moves" rule
+# Training targets (the reference has neither; engine.BatchedSelfPlay, replay.blend_targets).  SP_TEMPERATURE_PLIES K > 0: plies 0 .. K - 1
+# of a game are sampled at SP_TEMPERATURE, every later one takes the most visited move.  SP_VALUE_BLEND L > 0: a row's value target is
+# (1 - L) z + L q, q the search value of its root -- a float32 in the window and, with the same bits, a float in the .history file.
+SP_TEMPERATURE_PLIES = 0     # 0 = off: every ply at SP_TEMPERATURE
+SP_VALUE_BLEND = 0.0         # 0 = off: z alone, an int
 # Replay window (the reference has none; replay.ReplayWindow): every rank appends the gathered generation to SP_REPLAY, straight from
 # the engine's device tensors, for train_network.TRAIN_WINDOW to train on.  The .history file stays the reference's hand-over.
 SP_REPLAY = None             # None = off
@@ -48,14 +54,19 @@ def write_data(history):
     return path
 
 
-def _history_rows(states72, visits, z, board_size):
+def _history_rows(states72, visits, z, board_size, values=None, value_blend=0.0):
+    """The rows of a .history file.  values (float32 [P], with value_blend > 0): a row's z is the blended target as a Python float --
+    the float32 the replay window holds, widened -- instead of the int outcome."""
     nw = (board_size - 1) ** 2
     st, vis, zz = states72.cpu().numpy(), visits.cpu().numpy().astype(np.float64), z.cpu().numpy()
+    if values is not None:
+        zz = [float(x) for x in blend_targets(zz, values.cpu().numpy(), value_blend)]
     out = []
     for s, v, r in zip(st, vis, zz):
         tot = v.sum()
         pol = (v / tot).tolist() if tot > 0 else [0.0] * v.shape[0]
-        out.append([[[int(s[0]), int(s[1])], [int(s[2]), int(s[3])], [int(x) for x in s[4:4 + nw]]], pol, int(r)])
+        out.append([[[int(s[0]), int(s[1])], [int(s[2]), int(s[3])], [int(x) for x in s[4:4 + nw]]], pol,
+                    int(r) if values is None else r])
     return out
 
 
@@ -79,11 +90,15 @@ def mirror_history(history):
 def play(model, device=None, uniforms=None):
     """Execute one self-play game (self_play.py:40-68) -- a generation of one game on the engine.
     Returns [[state_array, policy list[POLICY_OUTPUT_SIZE], z], ...]."""
+    blend = check_value_blend(SP_VALUE_BLEND)
     eng = BatchedSelfPlay(model, num_games=1, sims=pv_mcts.PV_EVALUATE_COUNT, board_size=BOARD_SIZE,
                           temperature=SP_TEMPERATURE, seed=int(np.random.randint(0, 2 ** 31 - 1)),
                           evaluator=pv_mcts.evaluator_of(model), root_noise_eps=SP_ROOT_NOISE_EPS,
-                          root_noise_alpha=SP_ROOT_NOISE_ALPHA)
+                          root_noise_alpha=SP_ROOT_NOISE_ALPHA, temperature_plies=SP_TEMPERATURE_PLIES,
+                          record_search_value=blend > 0.0)
     eng.play_generation(uniforms=uniforms, check_every=1)
+    if blend > 0.0:
+        return _history_rows(*eng.history_tensors(), BOARD_SIZE, eng.history_values(), blend)
     return eng.history()
 
 
@@ -124,26 +139,37 @@ def self_play(model=None, games=None, seed=None):
     st = torch.zeros((0, 72), dtype=torch.uint8, device=dev)
     vis = torch.zeros((0, POLICY_OUTPUT_SIZE), dtype=torch.int16, device=dev)
     z = torch.zeros((0,), dtype=torch.int8, device=dev)
+    blend = check_value_blend(SP_VALUE_BLEND)
+    q = torch.zeros((0,), dtype=torch.float32, device=dev) if blend > 0.0 else None       # the rows' search values, with a blend only
     if mine > 0:
         # >= 256 games: independent game sets on their own streams fill the holes of each other's serial kernel chains
         eng = MultiSetSelfPlay(model, num_games=mine, sims=pv_mcts.PV_EVALUATE_COUNT, num_sets=None if mine >= 256 else 1,
                                board_size=BOARD_SIZE, temperature=SP_TEMPERATURE, seed=(base + rank) % (2 ** 31 - 1), device=dev,
-                               evaluator=evaluator, root_noise_eps=SP_ROOT_NOISE_EPS, root_noise_alpha=SP_ROOT_NOISE_ALPHA)
+                               evaluator=evaluator, root_noise_eps=SP_ROOT_NOISE_EPS, root_noise_alpha=SP_ROOT_NOISE_ALPHA,
+                               temperature_plies=SP_TEMPERATURE_PLIES, record_search_value=blend > 0.0)
         c = eng.play_generation()
         print(f'\rSelf-play (rank {rank}: {c["finished"]}/{mine} games)', end='')
         st, vis, z = eng.history_tensors()
+        if q is not None:
+            q = eng.history_values()
     if distributed and os.environ.get("AQG_DIST_LOG") == "1" and rank == 0:
         print(f'exchange step: backend={dist.get_backend()} world={world} collectives={"forced" if aqd.force_group() else "as needed"}')
-    if distributed and dist.get_backend() != 'nccl':          # gloo (CPU tests): the exchange runs on host tensors
-        st, vis, z = (x.cpu() for x in gather_history(st.cpu(), vis.cpu(), z.cpu()))
+    host = distributed and dist.get_backend() != 'nccl'      # gloo (CPU tests): the exchange runs on host tensors
+    if host:
+        st, vis, z = st.cpu(), vis.cpu(), z.cpu()
+    if q is not None:
+        st, vis, z, q = gather_history(st, vis, z, values=q.cpu() if host else q)
     else:
         st, vis, z = gather_history(st, vis, z)
     print('')
-    if SP_REPLAY is not None:
-        SP_REPLAY.append_counts(st, vis, z)          # every rank: the gathered rows are identical on all of them
+    if SP_REPLAY is not None:                        # every rank: the gathered rows are identical on all of them
+        if q is not None:
+            SP_REPLAY.append_counts(st, vis, z, search_value=q, value_blend=blend)
+        else:
+            SP_REPLAY.append_counts(st, vis, z)
     path = None
     if rank == 0 and SP_WRITE_HISTORY:
-        path = write_data(_history_rows(st, vis, z, BOARD_SIZE))
+        path = write_data(_history_rows(st, vis, z, BOARD_SIZE, q, blend))
     if distributed:
         dist.barrier()          # no rank may go on to train_network.load_data() before rank 0 has finished the file
     del model

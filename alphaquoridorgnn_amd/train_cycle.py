@@ -165,6 +165,12 @@ def _parser():
                     help="self-play: weight of the Dirichlet noise mixed into every root's priors (default SP_ROOT_NOISE_EPS = 0: off)")
     ap.add_argument("--root-noise-alpha", type=float, default=None,
                     help="self-play: Dirichlet concentration (default SP_ROOT_NOISE_ALPHA: 10 / the board's action count)")
+    ap.add_argument("--temperature-plies", type=int, default=None,
+                    help="self-play: plies of a game sampled at SP_TEMPERATURE before the most visited move is taken (default "
+                         "SP_TEMPERATURE_PLIES = 0: every ply is sampled)")
+    ap.add_argument("--value-blend", type=float, default=None,
+                    help="self-play: weight L in [0, 1] of the root's search value in the value target, (1 - L) z + L q (default "
+                         "SP_VALUE_BLEND = 0: the game outcome alone)")
     ap.add_argument("--mirror-augment", action="store_true",
                     help="parameter update: train every epoch on positions mirrored left to right at random (default TRAIN_MIRROR = False: off)")
     ap.add_argument("--mirror-seed", type=int, default=None,
@@ -206,6 +212,17 @@ def _set_replay_options(args):
     return window
 
 
+def _set_target_options(args):
+    """--temperature-plies / --value-blend onto self_play's constants, refused here if the engine or the append would refuse them."""
+    from . import self_play as sp
+    from .engine import check_target_options
+    from .replay import check_value_blend
+    if args.temperature_plies is not None:
+        sp.SP_TEMPERATURE_PLIES = check_target_options(args.temperature_plies)[0]
+    if args.value_blend is not None:
+        sp.SP_VALUE_BLEND = check_value_blend(args.value_blend)
+
+
 def _set_mirror_options(args):
     """--mirror-augment / --mirror-seed onto train_network's constants (the stages read them at call time)."""
     from . import train_network as tn
@@ -235,6 +252,7 @@ def main(argv=None):
         sp.SP_ROOT_NOISE_ALPHA = args.root_noise_alpha
     if args.epochs is not None:
         tn.NUM_EPOCH = args.epochs
+    _set_target_options(args)
     _set_mirror_options(args)
     _set_replay_options(args)
     if args.eval_games is not None:

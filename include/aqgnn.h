@@ -442,6 +442,28 @@ int aqg_engine_apply_actions(const aqg_engine* e_host, const int32_t* actions, v
 int aqg_engine_root_noise(const aqg_engine* e_host, void* stream);
 int aqg_engine_root_priors(const aqg_engine* e_host, float* priors, int32_t* count, void* stream);
 
+/* ------------------------------------------------------------------ self-play targets (additive to ABI 15; the reference has neither)
+ *
+ * Two controls of what a self-play game teaches, both off by default and both outside the struct: the end of a move (the finish-move
+ * launch of csrc/mcts_move.hip and the slot refill) is not part of the captured per-move graph, so the options travel as arguments of
+ * two entry points and reach engine_finish_move_kernel as kernel arguments.  The engine struct, the graph cache and its key do not
+ * change.  The two entry points below are the move and the finish-move entry points above with two more arguments, and with
+ * (0, NULL) for them they behave bit for bit like those (which pass exactly that).
+ *
+ * temperature_plies = K > 0: the move of a root whose position has plies_played < K is chosen as always -- by e.temperature and
+ *   uniforms[g] -- and a root with plies_played >= K takes the first maximum of the visit counts, the temperature == 0 branch.
+ *   plies_played is the position's own ply counter, the one the root noise is keyed by.  Only the choice changes: the recorded
+ *   policy target is the visit row at every ply.  uniforms[g] is still the slot's entry on an arg-max ply (it is not read), so a
+ *   caller's stream of uniforms stays aligned.  K == 0: every ply by e.temperature.  K < 0 is refused.  No late temperature other
+ *   than 0 is offered.
+ * hist_value != NULL: f32 [quota, max_plies], indexed like hist_action.  Lane 0 of the slot's wavefront writes the root's search
+ *   value from the mover's side, v = f32(w / n) with w the float64 sum and n the count of the root after the move's simulations
+ *   (the bits of the root record's q, negated), 0 when n == 0; only if ply < max_plies.  Refused when max_plies == 0.  Rows made by
+ *   the apply-actions entry point are not written: in a buffer that starts at zero they read 0. */
+int aqg_engine_move_targets(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value, void* stream);
+int aqg_engine_finish_move_targets(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                                   void* stream);
+
 /* ------------------------------------------------------------------ baseline agents in batch (agents.py; additive to ABI 14)
  *
  * The reference's random and rollout-MCTS agents (agents.py:14-18, :111-214) for B states at once, one wavefront per state
@@ -686,6 +708,18 @@ int aqg_augment_gather(int board_size, int policy_size, const uint8_t* states72,
 int aqg_replay_append(int board_size, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8,
                       const float* pi, const float* z_f32, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
                       float* ring_z, void* stream);
+/* The counts form with a blended value target (additive to ABI 15): the same kernel under a template switch, same geometry, one
+ * launch.  search_value f32 [n] is the search value the engine recorded beside each row (hist_value above); the lanes that write
+ * ring_z load it and write
+ *     ring_z = keep * (float)z + blend * v,   keep = 1.0f - blend
+ * in f32 without contraction: one subtraction, two products and one sum, each rounded (replay.blend_targets is the same in numpy).
+ * blend 0 writes the bits of the plain append for every finite v; blend 1 writes 0 * z + v, which is v (a zero may change its
+ * sign).  ring72 and ring_pi are written
+ * exactly as the plain append writes them.  Refused, besides everything the plain append refuses of the counts form: a blend outside
+ * [0, 1] or NaN, search_value NULL (with n > 0), search_value (n values) overlapping a ring. */
+int aqg_replay_append_blend(int board_size, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8,
+                            const float* search_value, float blend, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
+                            float* ring_z, void* stream);
 
 /* ------------------------------------------------------------------ CPU baseline agents (agents.py) -- HOST pointers, host code */
 
