@@ -19,13 +19,13 @@ fi
 objs=()
 pids=()
 replaced=0
-for f in legal_mask board_featuriser gcn_pack gcn_trunk_split gcn_trunk_exact gcn_boards_plain gcn_forward gcn_general gcn_boards_general gcn_train gcn_train_exact gcn_train_split gcn_train_final gcn_train_general cnn_forward cnn_train mcts mcts_step mcts_move agents augment replay capi; do
+for f in legal_mask board_featuriser gcn_pack gcn_trunk_split gcn_trunk_exact gcn_boards_plain gcn_forward gcn_general gcn_boards_general gcn_train gcn_train_exact gcn_train_split gcn_train_final gcn_train_general cnn_forward cnn_train mcts mcts_step mcts_eval mcts_move agents augment replay capi; do
   src=$f.hip
   for pair in ${AQG_REPLACE:-}; do
     if [ "${pair%%=*}" = "$f" ]; then src=${pair#*=}; replaced=$((replaced + 1)); fi
   done
-  if [ "$f" = mcts_step ]; then
-    # the step kernel's resource lines are kept: the budget check below reads them
+  if [ "$f" = mcts_step ] || [ "$f" = mcts_eval ]; then
+    # the resource lines of the step kernels and of the evaluation launch are kept: the budget checks below read them
     $HIPCC $FLAGS -Rpass-analysis=kernel-resource-usage -I. -c "$src" -o "${OBJDIR}/aqg_$f.o" 2> "${OBJDIR}/aqg_$f.remarks" &
   else
     $HIPCC $FLAGS -I. -c "$src" -o "${OBJDIR}/aqg_$f.o" &
@@ -45,9 +45,10 @@ for pid in "${pids[@]}"; do
 done
 if [ "$failed" -ne 0 ]; then
   grep -v "remark:" "${OBJDIR}/aqg_mcts_step.remarks" >&2 || true      # whatever mcts_step.hip's compile said besides the remarks
+  grep -v "remark:" "${OBJDIR}/aqg_mcts_eval.remarks" >&2 || true
   echo "build.sh: a compile job failed" >&2; exit 1
 fi
-grep -A3 "warning:" "${OBJDIR}/aqg_mcts_step.remarks" >&2 || true
+grep -A3 "warning:" "${OBJDIR}/aqg_mcts_step.remarks" "${OBJDIR}/aqg_mcts_eval.remarks" >&2 || true
 # Register budget of the step kernels with the heads inside (engine_step_fast_kernel<9, CACHE, true>): at most
 # 128 VGPRs and no scratch, or a step workgroup no longer fits beside a trunk workgroup.  The order of their load rounds is steered
 # by scheduling barriers that a compiler update may treat differently: such a build fails here instead of running slower.
@@ -56,7 +57,13 @@ grep -A3 "warning:" "${OBJDIR}/aqg_mcts_step.remarks" >&2 || true
 awk '/Function Name:/ { k = ($0 ~ /engine_step_fast_kernelILi9ELb[01]ELb1E/) ? $0 : "" }
      k != "" && / VGPRs: / { n++; v = $0; sub(/.* VGPRs: /, "", v); if (v + 0 > 128) { print "build.sh: over 128 VGPRs: " k > "/dev/stderr"; bad = 1 } }
      k != "" && /ScratchSize/ { v = $0; sub(/.*: /, "", v); if (v + 0 != 0) { print "build.sh: scratch in use: " k > "/dev/stderr"; bad = 1 } }
-     END { if (n != 2) { print "build.sh: expected two fused step kernels in the resource remarks, found " n + 0 > "/dev/stderr"; bad = 1 } exit bad }' \
+     END { if (n != 3) { print "build.sh: expected three fused step kernels in the resource remarks, found " n + 0 > "/dev/stderr"; bad = 1 } exit bad }' \
   "${OBJDIR}/aqg_mcts_step.remarks" || exit 1
+# The same budget for the evaluation launch (engine_eval_kernel<TRACK>, mcts_eval.hip): its board workgroups are the trunk's, two per CU.
+awk '/Function Name:/ { k = ($0 ~ /engine_eval_kernelILi[02]E/) ? $0 : "" }
+     k != "" && / VGPRs: / { n++; v = $0; sub(/.* VGPRs: /, "", v); if (v + 0 > 128) { print "build.sh: over 128 VGPRs: " k > "/dev/stderr"; bad = 1 } }
+     k != "" && /ScratchSize/ { v = $0; sub(/.*: /, "", v); if (v + 0 != 0) { print "build.sh: scratch in use: " k > "/dev/stderr"; bad = 1 } }
+     END { if (n != 2) { print "build.sh: expected two evaluation kernels in the resource remarks, found " n + 0 > "/dev/stderr"; bad = 1 } exit bad }' \
+  "${OBJDIR}/aqg_mcts_eval.remarks" || exit 1
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT" "${objs[@]}"
 echo "built $(realpath "$OUT")"

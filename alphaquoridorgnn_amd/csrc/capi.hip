@@ -24,6 +24,7 @@ int aqg_set_option(const char* name, int value) {
     if (name && !strcmp(name, "step_prio")) { g_step_prio = value & 3; return 0; }
     if (name && !strcmp(name, "step_waves")) { g_step_waves = value; return 0; }
     if (name && !strcmp(name, "step_heads")) { g_step_heads = value ? 1 : 0; return 0; }
+    if (name && !strcmp(name, "legal_beside_trunk")) { g_legal_beside_trunk = value ? 1 : 0; return 0; }
     if (name && !strcmp(name, "step_fast_depth")) { if (value < 0 || value > 61) return fail("step_fast_depth must be 0..61"); g_step_fast_depth = value; return 0; }
     if (name && !strcmp(name, "train_fused")) { if (value < 1 || value > 3) return fail("train_fused must be 1, 2 or 3"); g_train_fused = value; return 0; }
     if (name && !strcmp(name, "use_graph")) { g_use_graph = value ? 1 : 0; return 0; }
@@ -34,7 +35,7 @@ int aqg_set_option(const char* name, int value) {
 int aqg_debug_poison_lds(void* stream) { return launch_poison_lds((hipStream_t)stream); }
 
 int aqg_debug_trace(void* buffer, unsigned int capacity) {
-    if (set_trace_gcn(buffer, capacity) || set_trace_mcts(buffer, capacity)) return fail("aqg_debug_trace: hipMemcpyToSymbol");
+    if (set_trace_gcn(buffer, capacity) || set_trace_mcts(buffer, capacity) || set_trace_eval(buffer, capacity)) return fail("aqg_debug_trace: hipMemcpyToSymbol");
     return 0;
 }
 

@@ -31,6 +31,7 @@ extern int g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, g_trunk_
 int set_trace_gcn(void* buf, unsigned int cap);
 void launch_gcn_trunk_split(int track, const void* states, int fmt, int B, const float* packed, float* pooled, const uint8_t* active,
                             int32_t* saturated, const int32_t* list, const int32_t* list_count, hipStream_t st);
+void trunk_split_launch_shape(int B, bool list, int& grid, int& opts);
 int launch_gcn_heads_split(float* pooled, int B, int A, const float* packed, float* logits, float* policy, float* value_pre,
                            float* value, const uint8_t* active, int32_t* saturated, hipStream_t st);
 
@@ -107,7 +108,13 @@ int engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipSt
 // ---- mcts_step.hip  (launchers of the engine's kernels only enqueue: the entry point checks the launch)
 extern int g_step_waves, g_step_prio, g_step_fast_depth, g_step_heads;
 int set_trace_mcts(void* buf, unsigned int cap);
-int launch_engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t st, int list_sim, bool heads);
+int launch_engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t st, int list_sim, bool heads, bool defer_legal = false);
+
+// ---- mcts_eval.hip
+extern int g_legal_beside_trunk;
+int set_trace_eval(void* buf, unsigned int cap);
+bool engine_step_defers_legal(const aqg_engine& e, bool step_heads);
+int launch_engine_eval(const aqg_engine& e, hipStream_t st);
 
 // ---- mcts_move.hip
 void launch_engine_reset(const aqg_engine& e, hipStream_t st);

@@ -21,6 +21,8 @@
 //   mcts_step.hip   the simulation step and nothing else: step_round1, game_step_fast, engine_step_fast_kernel, the options
 //                   step_waves / step_prio / step_fast_depth / step_heads, set_trace_mcts, launch_engine_step.  The tuned unit: build.sh
 //                   polices its register budget.
+//   mcts_eval.hip   the evaluation launch behind a step that defers its leaves' legal-move searches: leaf_legal_role, engine_eval_kernel (search
+//                   workgroups in front of the trunk's board workgroups), the option legal_beside_trunk, launch_engine_eval.
 //   mcts_move.hip   once per move or once per engine: reset, set_roots, begin_move, the `fake` evaluator, root noise, finish_move and
 //                   apply_actions (one engine_transition behind both), refill, root_visits / root_priors / root_states72; one plain
 //                   launcher per kernel.
@@ -82,9 +84,16 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st) {
     // computes policy and value of this simulation's leaves from the pooled rows, so the simulation is two launches, step -> trunk.
     // Everything else keeps the heads launch: other boards and evaluators, step_waves != 8, the exact kernels behind a range-guard report.
     const bool step_heads = g_step_heads && e.prior_mode == 0 && N == 9 && g_trunk_variant >= 3 && !(e.gnn_flags & AQG_GNN_EXACT_F32) && g_step_waves == 8;
+    // legal moves beside the trunk (option "legal_beside_trunk"; cache off): such a step ends on its leaf, and the evaluation launch behind
+    // it carries the leaves' legal-move searches in front of the trunk's board workgroups (mcts_eval.hip) -- still two launches, one chain.
+    // Simulation 0's step does not expand, so it is not the form with the heads inside: it searches itself and the plain trunk follows.
+    const bool defer_legal = engine_step_defers_legal(e, step_heads);
     for (int sim = 0; sim < e.sims; ++sim) {
-        if (int r = launch_engine_step(e, sim > 0 ? 1 : 0, 1, st, use_list ? sim : -1, step_heads)) return r;
-        if (e.prior_mode == 0) {
+        const bool defer = defer_legal && sim > 0;
+        if (int r = launch_engine_step(e, sim > 0 ? 1 : 0, 1, st, use_list ? sim : -1, step_heads, defer)) return r;
+        if (defer) {
+            if (int r = launch_engine_eval(e, st)) return r;
+        } else if (e.prior_mode == 0) {
             // (simulation 0 -- the root's evaluation -- keeps its heads launch: root noise reads the root's row and value from e.policy /
             //  e.value, and without noise the launch is there only so that these buffers hold the root's evaluation after a search, as
             //  they always did after a one-simulation search (tests/test_gpu_parity.py::test_engine_masked_trunk_launch reads them).
@@ -146,7 +155,7 @@ static int replay(SimGraph& g, hipStream_t st) {
 static int run_sims(const aqg_engine& e, hipStream_t st) {
     if (!g_use_graph || g_profile_trunk || st == nullptr || e.sims < 4) return enqueue_sims(e, st);
     // every option a captured launch bakes in is part of the key: a changed option must never replay a stale graph
-    const int opts[7] = {g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, e.board_size, g_step_fast_depth, ((g_trunk_prio & 0xff) << 8) | (g_step_waves << 16) | (g_step_prio << 24) | (g_heads_prio << 28) | (g_step_heads & 1)};
+    const int opts[7] = {g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, e.board_size, g_step_fast_depth, ((g_trunk_prio & 0xff) << 8) | (g_step_waves << 16) | (g_step_prio << 24) | (g_heads_prio << 28) | (g_step_heads & 1) | ((g_legal_beside_trunk & 1) << 1)};
     for (SimGraph& g : g_sim_graphs)
         if (!memcmp(&g.e, &e, sizeof(aqg_engine)) && !memcmp(g.opts, opts, sizeof(opts))) return replay(g, st);
     if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {

@@ -39,19 +39,6 @@ __device__ __forceinline__ float wave_max_dpp_asm(float x) {
         : "+v"(x));
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
 }
-__device__ __forceinline__ uint64_t rfl64(uint64_t v) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-}
-// a game's state is the same in every lane of its wavefront: as scalars, next() / is_lose() / is_draw() run on the scalar unit
-__device__ __forceinline__ QState uniform_state(const QState& v) {
-    QState s;
-    s.hw = rfl64(v.hw); s.vw = rfl64(v.vw);
-    const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)v.ppos | ((uint32_t)v.pwl << 8) | ((uint32_t)v.epos << 16) | ((uint32_t)v.ewl << 24)));
-    s.ppos = (uint8_t)(m & 0xff); s.pwl = (uint8_t)((m >> 8) & 0xff); s.epos = (uint8_t)((m >> 16) & 0xff); s.ewl = (uint8_t)(m >> 24);
-    s.plies = (uint16_t)__builtin_amdgcn_readfirstlane((int)v.plies); s.pad = 0;
-    return s;
-}
-
 // ------------------------------------------------------------------------------------------------
 // The simulation step of one game, run by one wavefront (game_step_fast).  A launch does two things:
 //   expand + backup of the PREVIOUS simulation's leaf (pv_mcts.py:45-57, :59-66): the evaluator's policy is gathered at the
@@ -195,7 +182,10 @@ __device__ __forceinline__ void step_round1(const aqg_engine& e, int g, int lane
 // CACHE: the evaluation cache's code is compiled in (its own kernel instantiation: the cache-less kernel carries none of it)
 // HEADS: the kernel ran heads_body for the workgroup's leaves in front of this: a leaf_flag 1 leaf's softmax row is in `polbuf`
 // (dense, by action), its value in `head_value`; nothing of either came through global memory
-template <int N, bool CACHE, bool HEADS>
+// DEFER (cache-less HEADS launches in front of engine_eval_kernel, option "legal_beside_trunk"): the new leaf's legal-move search is
+// left to the evaluation launch that follows on the stream -- nothing in this launch reads its result -- and the step ends on the
+// leaf's state with legal_count = -1, the marker that search looks for (leaf_legal_role, mcts_eval.hip)
+template <int N, bool CACHE, bool HEADS, bool DEFER = false>
 __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int lane, int do_expand, int do_select, int fast_depth,
                                                float* __restrict__ polbuf /* this wave's 256 floats of LDS */, int list_sim,
                                                const StepRound1& r1, float head_value) {
@@ -604,7 +594,7 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
         bool hit = false;
         int newslot = -1;
         LegalPrep prep;
-        if (!cache_on) prep = wave_legal_prepare<N>(s, lane);
+        if (!cache_on && !DEFER) prep = wave_legal_prepare<N>(s, lane);
         if (cache_on) {
             const uint32_t misc = eval_cache_misc(s);
             uint64_t h = s.hw * 0x9E3779B97F4A7C15ull ^ s.vw * 0xC2B2AE3D27D4EB4Full ^ (uint64_t)misc * 0x165667B19E3779F9ull;
@@ -649,7 +639,16 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
                 newslot = (int)((home + (uint32_t)(eb ? __builtin_ctzll(eb) : (int)((h >> 40) & 63u))) & cmask);
             }
         }
-        if (!hit) {
+        if (DEFER) {
+            static_assert(!DEFER || !CACHE, "a cache hit supplies the legal list from the table");
+            STEP_STAMP(3)
+            if (lane == 0) {
+                store_state(e.leaf_state, g, s);
+                e.legal_count[g] = -1;
+                e.path_len[g] = depth;
+                e.leaf_flag[g] = 1;
+            }
+        } else if (!hit) {
             const int total = wave_legal_finish<N>(s, prep, lane, nullptr, e.legal_order + (size_t)g * MAX_LEGAL);
             STEP_STAMP(3)
             if (lane == 0) {
@@ -696,7 +695,7 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
 // (96 registers of operands), the step's own round 1 (about 50) as soon as the hidden layer's MFMAs are issued and their operands are
 // dead -- it is in flight under the hidden layer's epilogue, the policy layer, the softmax and three barriers, not behind them.
 // Nothing waits for another workgroup: every input was written by a launch that has finished.
-template <int N, bool CACHE, bool HEADS>
+template <int N, bool CACHE, bool HEADS, bool DEFER = false>
 __global__ __launch_bounds__(512, HEADS ? 4 : 1) void engine_step_fast_kernel(aqg_engine e, int do_expand, int do_select, int fast_depth, int list_sim) {
     __shared__ float polbuf[8][256];
     AQG_TRACE_BEGIN
@@ -717,7 +716,7 @@ __global__ __launch_bounds__(512, HEADS ? 4 : 1) void engine_step_fast_kernel(aq
                          e.leaf_flag, e.counters + 5, wave, lane, polbuf, hval,
                          [&]() { step_round1<N, CACHE, true>(e, min(g, e.num_games - 1), lane, 1, r1); });     // (a wave without a game loads the last game's: no branch)
         __syncthreads();                         // the rows and values are complete: each wave reads its own game's
-        if (g < e.num_games) game_step_fast<N, CACHE, true>(e, g, lane, do_expand, do_select, fast_depth, polbuf[wave], list_sim, r1, hval[wave]);
+        if (g < e.num_games) game_step_fast<N, CACHE, true, DEFER>(e, g, lane, do_expand, do_select, fast_depth, polbuf[wave], list_sim, r1, hval[wave]);
     } else if (g < e.num_games) {
         step_round1<N, CACHE, false>(e, g, lane, do_expand, r1);
         game_step_fast<N, CACHE, false>(e, g, lane, do_expand, do_select, fast_depth, polbuf[threadIdx.x >> 6], list_sim, r1, 0.f);
@@ -728,8 +727,9 @@ AQG_TRACE_SETTER(set_trace_mcts)
 
 // One step launch; only enqueues (the caller checks the launch).  `heads`: the launch computes the heads of its leaves itself (see the
 // kernel; the caller has checked that the form applies).  `list_sim` >= 0: the leaves that miss the evaluation cache are listed for
-// the trunk launch of that simulation.
-int launch_engine_step(const aqg_engine& e_in, int do_expand, int do_select, hipStream_t st, int list_sim, bool heads) {
+// the trunk launch of that simulation.  `defer_legal`: the caller launches engine_eval_kernel behind this step, which then leaves its
+// leaves' legal-move searches to it (only the cache-less `heads` form of a selecting step does; any other form searches itself).
+int launch_engine_step(const aqg_engine& e_in, int do_expand, int do_select, hipStream_t st, int list_sim, bool heads, bool defer_legal) {
     // prior_mode 3 and 4 leave the network's dense [G,A] policy in e.policy exactly like prior_mode 0: the step kernels gather,
     // renormalise and cache it as mode 0 -- they are handed the struct with prior_mode 0, so no step kernel knows mode 3 or 4
     aqg_engine e = e_in;
@@ -746,7 +746,11 @@ int launch_engine_step(const aqg_engine& e_in, int do_expand, int do_select, hip
         if constexpr (N == 9) fused = heads && do_expand && wpb == 8 && e.prior_mode == 0;      // (the only board with HEADS instantiations)
         auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, sg, sb, 0, st, e, do_expand, do_select, fd, list_sim); };
         if constexpr (N == 9) {
-            if (fused) { if (cache) launch(engine_step_fast_kernel<N, true, true>); else launch(engine_step_fast_kernel<N, false, true>); }
+            if (fused) {
+                if (cache) launch(engine_step_fast_kernel<N, true, true>);
+                else if (defer_legal && do_select) launch(engine_step_fast_kernel<N, false, true, true>);
+                else launch(engine_step_fast_kernel<N, false, true>);
+            }
         }
         if (!fused) { if (cache) launch(engine_step_fast_kernel<N, true, false>); else launch(engine_step_fast_kernel<N, false, false>); }
         if (g_profile_trunk == 2) profile_mark(st, -1);

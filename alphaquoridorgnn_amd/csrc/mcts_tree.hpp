@@ -1,5 +1,5 @@
-// mcts_tree.hpp -- what the engine's units (mcts_step.hip, mcts_move.hip) share of a game's tree pool: the node record, its
-// accessors, the wave sums and the initial position.  __forceinline__ device code and declarations only.  The including unit
+// mcts_tree.hpp -- what the engine's units (mcts_step.hip, mcts_eval.hip, mcts_move.hip) share: of a game's tree pool the node record,
+// its accessors and the wave sums; the initial position; a game's state as wave-uniform scalars (uniform_state).  __forceinline__ device code and declarations only.  The including unit
 // sets `#pragma clang fp contract(off)` in front of this header: q_of and the backup are PUCT arithmetic.
 #pragma once
 #include "aqg_common.hpp"
@@ -64,6 +64,19 @@ __device__ __forceinline__ QState initial_state(int N, int num_walls) {
     s.ppos = (uint8_t)(N * (N - 1) + N / 2); s.pwl = (uint8_t)num_walls;
     s.epos = s.ppos; s.ewl = s.pwl;
     s.plies = 0; s.pad = 0;
+    return s;
+}
+
+__device__ __forceinline__ uint64_t rfl64(uint64_t v) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+// a game's state is the same in every lane of its wavefront: as scalars, next() / is_lose() / is_draw() run on the scalar unit
+__device__ __forceinline__ QState uniform_state(const QState& v) {
+    QState s;
+    s.hw = rfl64(v.hw); s.vw = rfl64(v.vw);
+    const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)v.ppos | ((uint32_t)v.pwl << 8) | ((uint32_t)v.epos << 16) | ((uint32_t)v.ewl << 24)));
+    s.ppos = (uint8_t)(m & 0xff); s.pwl = (uint8_t)((m >> 8) & 0xff); s.epos = (uint8_t)((m >> 16) & 0xff); s.ewl = (uint8_t)(m >> 24);
+    s.plies = (uint16_t)__builtin_amdgcn_readfirstlane((int)v.plies); s.pad = 0;
     return s;
 }
 

@@ -396,6 +396,11 @@ class BatchedSelfPlay:
                     cache_hits=int(self.t["stat_cache_hits"].sum().item()) if self.eval_cache_slots else 0,
                     terminal_sims=int(self.t["stat_terminal_sims"].sum().item()))
 
+    def deferred_legal_searches(self):
+        """Leaves whose legal-move search ran beside the trunk, in the evaluation launch, since the last reset (aqgnn.h counters[6];
+        option "legal_beside_trunk").  0 wherever the step kernel searches itself: option off, evaluation cache on, other evaluators."""
+        return int(self.t["counters"][6].item())
+
     def switch_to_exact_kernels(self, keep_roots=False):
         """The range guard fired: this weight set leaves fp16 range on positions of this generation.  Its evaluations so far were
         finite but not the network's, so the model is marked and the engine moves to the exact f32-input kernels (the reference's fp32
@@ -611,6 +616,9 @@ class MultiSetSelfPlay:
             for key in tot:
                 tot[key] += c[key]
         return tot
+
+    def deferred_legal_searches(self):
+        return sum(eng.deferred_legal_searches() for _, eng in self._each())
 
     def play_generation(self, check_every=4):
         ply = 0

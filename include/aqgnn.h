@@ -44,6 +44,10 @@ const char* aqg_last_error(void);
  * engine's `policy` / `value` buffers: after a move or search these hold the ROOT's evaluation (simulation 0 keeps its heads launch;
  * root noise reads it there) where the three-launch form leaves the last leaf's.  Bit-identical searches.  0 = three launches per
  * simulation everywhere (A/B runs, tests); part of the captured graphs' key;
+ * "legal_beside_trunk" 0/1 (default 1): where "step_heads" applies, the evaluation cache is off and the set has fewer than 1,024 games, an expanding step launch ends on its
+ * new leaf (state, flag, legal_count = -1) and the launch behind it carries ceil(num_games / 8) workgroups that search those leaves' legal
+ * moves in front of the trunk's board workgroups -- the same search on the same state, beside the trunk instead of in front of it; still
+ * two launches per simulation, bit-identical searches; counters[6] counts the leaves searched there; part of the captured graphs' key;
  * "train_fused" = form of the training step
  * (csrc/gcn_train.hip): 2 (default) one workgroup per position with every contraction in fp16 split precision on the 16-bit
  * matrix pipe (9x9 board; a position whose values leave fp16 range is redone in f32 inside the same launch, counted by
@@ -317,7 +321,8 @@ typedef struct aqg_engine {
     uint8_t* hist_action /* [G,max_plies] */;
     /* counters [8] i32: 0 active slots, 1 finished games, 2 dead-end aborts, 3 next game index to hand out, 4 moves made
      * (updated once per move), 5 fp16-range guard: set to 1 by a GNN evaluation of this engine that met a value outside fp16 range
-     * (see aqg_gcn_forward_boards_guarded; cleared by aqg_engine_reset only) */
+     * (see aqg_gcn_forward_boards_guarded; cleared by aqg_engine_reset only), 6 leaves whose legal-move search ran in the evaluation
+     * launch beside the trunk instead of in the step launch (option "legal_beside_trunk"; cleared by aqg_engine_reset only) */
     int32_t* counters;
     /* per-game statistics [G] i32 (summed by the host): network evaluations, simulations that ended on a terminal node */
     int32_t* stat_leaf_evals; int32_t* stat_terminal_sims;
