@@ -67,6 +67,11 @@ class EngineStructGeneral(EngineStruct):
                 ("root_noise_eps", _f32), ("root_noise_alpha", _f32), ("root_noise_seed", _c.c_uint64), ("root_noise", _vp)]
 
 
+class TreeReuseStruct(_c.Structure):
+    """Mirror of `struct aqg_tree_reuse` (include/aqgnn.h, "tree reuse"): the option beside the engine struct."""
+    _fields_ = [("keep_visits", _i32), ("kept", _vp), ("child_index", _vp), ("stat_moves_kept", _vp), ("stat_visits_kept", _vp)]
+
+
 class TrainStruct(_c.Structure):
     """Mirror of `struct aqg_train` (include/aqgnn.h)."""
     _fields_ = (
@@ -150,6 +155,10 @@ SIGNATURES = {
     "aqg_engine_step": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.c_int, _c.c_int, _vp]),
     "aqg_engine_finish_move": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_engine_finish_move_targets": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _vp]),
+    "aqg_engine_move_reuse": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _c.POINTER(TreeReuseStruct), _vp]),
+    "aqg_engine_finish_move_reuse": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _c.POINTER(TreeReuseStruct), _vp]),
+    "aqg_engine_keep_subtrees": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.POINTER(TreeReuseStruct), _vp, _vp]),
+    "aqg_engine_reset_reuse": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.POINTER(TreeReuseStruct), _vp]),
     "aqg_engine_set_roots": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_engine_root_visits": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp, _vp, _vp]),
     "aqg_engine_root_noise": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),

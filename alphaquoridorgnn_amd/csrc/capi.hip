@@ -229,6 +229,24 @@ int aqg_engine_finish_move_targets(const aqg_engine* e, const double* uniforms, 
     if (!e || !uniforms) return fail("aqg_engine_finish_move_targets: null argument");
     return engine_finish_move(*e, uniforms, temperature_plies, hist_value, (hipStream_t)stream);
 }
+int aqg_engine_move_reuse(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                          const aqg_tree_reuse* reuse, void* stream) {
+    if (!e || !uniforms || !reuse) return fail("aqg_engine_move_reuse: null argument");
+    return engine_move_reuse(*e, uniforms, temperature_plies, hist_value, *reuse, (hipStream_t)stream);
+}
+int aqg_engine_finish_move_reuse(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                                 const aqg_tree_reuse* reuse, void* stream) {
+    if (!e || !uniforms || !reuse) return fail("aqg_engine_finish_move_reuse: null argument");
+    return engine_finish_move_reuse(*e, uniforms, temperature_plies, hist_value, *reuse, (hipStream_t)stream);
+}
+int aqg_engine_keep_subtrees(const aqg_engine* e, const aqg_tree_reuse* reuse, const int32_t* child_index, void* stream) {
+    if (!e || !reuse || !child_index) return fail("aqg_engine_keep_subtrees: null argument");
+    return engine_keep_subtrees(*e, *reuse, child_index, (hipStream_t)stream);
+}
+int aqg_engine_reset_reuse(const aqg_engine* e, const aqg_tree_reuse* reuse, void* stream) {
+    if (!e || !reuse) return fail("aqg_engine_reset_reuse: null argument");
+    return engine_reset_reuse(*e, *reuse, (hipStream_t)stream);
+}
 int aqg_engine_set_roots(const aqg_engine* e, const uint8_t* root_states72, void* stream) {
     if (!e || !root_states72) return fail("aqg_engine_set_roots: null argument");
     return engine_set_roots(*e, root_states72, (hipStream_t)stream);

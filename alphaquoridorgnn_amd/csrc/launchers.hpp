@@ -104,6 +104,12 @@ int engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, i
 int engine_refill(const aqg_engine& e, hipStream_t st);
 int engine_root_noise(const aqg_engine& e, hipStream_t st);
 int engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st);
+int engine_move_reuse(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, const aqg_tree_reuse& ru,
+                      hipStream_t st);
+int engine_finish_move_reuse(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value,
+                             const aqg_tree_reuse& ru, hipStream_t st);
+int engine_keep_subtrees(const aqg_engine& e, const aqg_tree_reuse& ru, const int32_t* child_index, hipStream_t st);
+int engine_reset_reuse(const aqg_engine& e, const aqg_tree_reuse& ru, hipStream_t st);
 
 // ---- mcts_step.hip  (launchers of the engine's kernels only enqueue: the entry point checks the launch)
 extern int g_step_waves, g_step_prio, g_step_fast_depth, g_step_heads;
@@ -119,15 +125,20 @@ int launch_engine_eval(const aqg_engine& e, hipStream_t st);
 // ---- mcts_move.hip
 void launch_engine_reset(const aqg_engine& e, hipStream_t st);
 void launch_engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
-void launch_engine_begin_move(const aqg_engine& e, hipStream_t st);
+void launch_engine_begin_move(const aqg_engine& e, hipStream_t st, const uint8_t* kept = nullptr);
+void launch_engine_kept_root_noise(const aqg_engine& e, const uint8_t* kept, hipStream_t st);
 int launch_engine_fake_eval(const aqg_engine& e, hipStream_t st);
 int launch_engine_root_noise(const aqg_engine& e, hipStream_t st);
-int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st);
+int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st,
+                              int32_t* child_index = nullptr, uint8_t* kept = nullptr);
 void launch_engine_refill(const aqg_engine& e, hipStream_t st);
 int launch_engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st);
 void launch_engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st);
 int engine_root_states72(const aqg_engine& e, uint8_t* out72, hipStream_t st);
 int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_t st);
+
+// ---- mcts_reuse.hip
+void launch_engine_keep_subtrees(const aqg_engine& e, const aqg_tree_reuse& ru, const int32_t* child_index, hipStream_t st);
 
 // ---- agents.hip
 int launch_agent_random(int N, const uint8_t* states72, int B, const double* uniforms, int stride, uint64_t seed, int32_t* actions,

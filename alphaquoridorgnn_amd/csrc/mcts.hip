@@ -26,6 +26,7 @@
 //   mcts_move.hip   once per move or once per engine: reset, set_roots, begin_move, the `fake` evaluator, root noise, finish_move and
 //                   apply_actions (one engine_transition behind both), refill, root_visits / root_priors / root_states72; one plain
 //                   launcher per kernel.
+//   mcts_reuse.hip  tree reuse: engine_keep_subtrees_kernel, the in-place re-rooting of a pool at the chosen child, and its launcher.
 //   mcts.hip        this file, host code only: validate, the simulation loop (enqueue_sims), its hipGraph cache (run_sims) and the
 //                   engine_* entry points.  It launches no kernel itself.
 #include "aqg_common.hpp"
@@ -74,10 +75,17 @@ static int validate(const aqg_engine& e) {
     return 0;
 }
 
-static int enqueue_sims(const aqg_engine& e, hipStream_t st) {
+// `reuse` != nullptr (tree reuse, aqgnn.h): begin_move leaves the marked slots' pools alone, a kept root's noise is mixed into its
+// children in front of simulation 0's step, and the step launches get `es`, the struct with sims = keep_visits + sims: the stride of
+// e.path and the bound of the path lanes, which is all the step kernel reads `sims` for.  Every other reader of `sims` -- begin_move's
+// eval_count, this loop, list_sim -- sees the real count.
+static int enqueue_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reuse* reuse = nullptr) {
     if (e.prior_mode == 2) return fail("prior_mode 2 (external evaluator): drive the move with aqg_engine_begin_move / _step / _finish_move");
     const int N = e.board_size;
-    launch_engine_begin_move(e, st);
+    aqg_engine es = e;
+    if (reuse) es.sims = e.sims + reuse->keep_visits;
+    launch_engine_begin_move(e, st, reuse ? reuse->kept : nullptr);
+    if (reuse && e.root_noise_eps > 0.f) launch_engine_kept_root_noise(e, reuse->kept, st);
     // evaluation cache on a set larger than the trunk's grid: the leaves that miss the cache go to the trunk as a compact list
     const bool use_list = e.prior_mode == 0 && e.eval_cache_keys && e.eval_list && N == 9 && e.num_games > 512 && g_trunk_variant >= 3 && !(e.gnn_flags & AQG_GNN_EXACT_F32);
     // heads inside the step (option "step_heads"): the 9x9 split network with eight games per step workgroup -- the NEXT step launch
@@ -90,7 +98,7 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st) {
     const bool defer_legal = engine_step_defers_legal(e, step_heads);
     for (int sim = 0; sim < e.sims; ++sim) {
         const bool defer = defer_legal && sim > 0;
-        if (int r = launch_engine_step(e, sim > 0 ? 1 : 0, 1, st, use_list ? sim : -1, step_heads, defer)) return r;
+        if (int r = launch_engine_step(es, sim > 0 ? 1 : 0, 1, st, use_list ? sim : -1, step_heads, defer)) return r;
         if (defer) {
             if (int r = launch_engine_eval(e, st)) return r;
         } else if (e.prior_mode == 0) {
@@ -127,11 +135,11 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st) {
         if (sim == 0 && e.root_noise_eps > 0.f)                                    // the root's priors, before simulation 1 expands it
             if (int r = launch_engine_root_noise(e, st)) return r;
     }
-    if (int r = launch_engine_step(e, 1, 0, st, -1, step_heads)) return r;   // expand + backup of the last simulation
+    if (int r = launch_engine_step(es, 1, 0, st, -1, step_heads)) return r;  // expand + backup of the last simulation
     return check_launch("engine simulation kernels");
 }
 
-// One move's search is 3 * sims + 2 launches (2 * sims + 3 with the heads inside the step; one more with root noise on) with constant arguments: on a capturable (non-default) stream it is
+// One move's search is 3 * sims + 2 launches (2 * sims + 3 with the heads inside the step; one more with root noise on, and with tree reuse a second one for the kept roots) with constant arguments: on a capturable (non-default) stream it is
 // captured once into a hipGraph and replayed per move, so the host cost per move is one graph launch instead of ~600
 // kernel launches (with several game sets on several streams the host is otherwise the bottleneck).  The cache key is
 // the engine struct itself plus the trunk options the launches read.
@@ -140,6 +148,8 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st) {
 struct SimGraph {
     aqg_engine e;
     int opts[7];
+    const uint8_t* kept;      // tree reuse: the two arguments its captured launches bake in (nullptr, 0 = a plain move)
+    int keep_visits;
     hipGraphExec_t exec;
     hipEvent_t last;          // recorded behind every replay: eviction waits for THIS graph's last replay, not for the device
 };
@@ -152,17 +162,19 @@ static int replay(SimGraph& g, hipStream_t st) {
     return 0;
 }
 
-static int run_sims(const aqg_engine& e, hipStream_t st) {
-    if (!g_use_graph || g_profile_trunk || st == nullptr || e.sims < 4) return enqueue_sims(e, st);
+static int run_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reuse* reuse = nullptr) {
+    if (!g_use_graph || g_profile_trunk || st == nullptr || e.sims < 4) return enqueue_sims(e, st, reuse);
+    const uint8_t* kept = reuse ? reuse->kept : nullptr;
+    const int keep_visits = reuse ? reuse->keep_visits : 0;
     // every option a captured launch bakes in is part of the key: a changed option must never replay a stale graph
     const int opts[7] = {g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, e.board_size, g_step_fast_depth, ((g_trunk_prio & 0xff) << 8) | (g_step_waves << 16) | (g_step_prio << 24) | (g_heads_prio << 28) | (g_step_heads & 1) | ((g_legal_beside_trunk & 1) << 1)};
     for (SimGraph& g : g_sim_graphs)
-        if (!memcmp(&g.e, &e, sizeof(aqg_engine)) && !memcmp(g.opts, opts, sizeof(opts))) return replay(g, st);
+        if (!memcmp(&g.e, &e, sizeof(aqg_engine)) && !memcmp(g.opts, opts, sizeof(opts)) && g.kept == kept && g.keep_visits == keep_visits) return replay(g, st);
     if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
         (void)hipGetLastError();
-        return enqueue_sims(e, st);                          // stream not capturable: plain launches
+        return enqueue_sims(e, st, reuse);                   // stream not capturable: plain launches
     }
-    const int r = enqueue_sims(e, st);
+    const int r = enqueue_sims(e, st, reuse);
     hipGraph_t graph = nullptr;
     const hipError_t ec = hipStreamEndCapture(st, &graph);
     if (r) { if (graph) (void)hipGraphDestroy(graph); return r; }
@@ -170,6 +182,7 @@ static int run_sims(const aqg_engine& e, hipStream_t st) {
     SimGraph g;
     memcpy(&g.e, &e, sizeof(aqg_engine));
     memcpy(g.opts, opts, sizeof(opts));
+    g.kept = kept; g.keep_visits = keep_visits;
     const hipError_t ei = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (ei != hipSuccess) return fail("hipGraphInstantiate");
@@ -187,8 +200,14 @@ static int run_sims(const aqg_engine& e, hipStream_t st) {
 
 // the end of a move: choose and apply (finish_move), then hand the idle slots their next games (refill) while a quota is left to play
 // (outside the captured graph, so the two target options are plain arguments: 0 / nullptr = off)
-static int finish_and_refill(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st) {
-    if (int r = launch_engine_finish_move(e, uniforms, temperature_plies, hist_value, st)) return r;
+// (tree reuse: finish_move leaves the chosen child's index, the keep launch re-roots the pools of the games that go on -- in front of the
+//  refill, whose new games start in slots that are inactive here and therefore never marked)
+static int finish_and_refill(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st,
+                             const aqg_tree_reuse* reuse = nullptr) {
+    if (int r = launch_engine_finish_move(e, uniforms, temperature_plies, hist_value, st, reuse ? reuse->child_index : nullptr,
+                                          reuse ? reuse->kept : nullptr))
+        return r;
+    if (reuse) launch_engine_keep_subtrees(e, *reuse, reuse->child_index, st);
     if (e.quota > e.num_games) launch_engine_refill(e, st);
     return check_launch("engine_finish_move_kernel");
 }
@@ -200,9 +219,20 @@ static int validate_targets(const aqg_engine& e, int temperature_plies, const fl
     return 0;
 }
 
-static int do_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st) {
-    if (int r = run_sims(e, st)) return r;
-    return finish_and_refill(e, uniforms, temperature_plies, hist_value, st);
+static int do_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st,
+                   const aqg_tree_reuse* reuse = nullptr) {
+    if (int r = run_sims(e, st, reuse)) return r;
+    return finish_and_refill(e, uniforms, temperature_plies, hist_value, st, reuse);
+}
+
+// what the tree-reuse entry points refuse, before anything is launched (aqgnn.h, "tree reuse")
+static int validate_reuse(const aqg_engine& e, const aqg_tree_reuse& ru) {
+    if (ru.keep_visits < 0) return fail("tree reuse: keep_visits must be >= 0");
+    if ((long long)ru.keep_visits + e.sims > 32767) return fail("tree reuse: keep_visits + sims must be <= 32767 (the visit row is read out as int16)");
+    if ((long long)e.node_cap < 1 + ((long long)ru.keep_visits + e.sims) * MAX_LEGAL) return fail("tree reuse: node_cap must be >= 1 + (keep_visits + sims) * AQG_MAX_LEGAL");
+    if (e.prior_mode == 2) return fail("tree reuse: not with prior_mode 2 (the external evaluator)");
+    if (!ru.kept || !ru.child_index || !ru.stat_moves_kept || !ru.stat_visits_kept) return fail("tree reuse: kept / child_index / stat_moves_kept / stat_visits_kept are required");
+    return 0;
 }
 
 // External-evaluator mode (prior_mode 2): the caller runs the simulation loop itself -- begin, then per simulation
@@ -246,6 +276,36 @@ int engine_move(const aqg_engine& e, const double* uniforms, int temperature_pli
     if (int r = validate(e)) return r;
     if (int r = validate_targets(e, temperature_plies, hist_value)) return r;
     return do_move(e, uniforms, temperature_plies, hist_value, st);
+}
+
+int engine_move_reuse(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, const aqg_tree_reuse& ru,
+                      hipStream_t st) {
+    if (int r = validate(e)) return r;
+    if (int r = validate_targets(e, temperature_plies, hist_value)) return r;
+    if (int r = validate_reuse(e, ru)) return r;
+    return do_move(e, uniforms, temperature_plies, hist_value, st, &ru);
+}
+
+int engine_finish_move_reuse(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value,
+                             const aqg_tree_reuse& ru, hipStream_t st) {
+    if (int r = validate(e)) return r;
+    if (int r = validate_targets(e, temperature_plies, hist_value)) return r;
+    if (int r = validate_reuse(e, ru)) return r;
+    return finish_and_refill(e, uniforms, temperature_plies, hist_value, st, &ru);
+}
+
+int engine_keep_subtrees(const aqg_engine& e, const aqg_tree_reuse& ru, const int32_t* child_index, hipStream_t st) {
+    if (int r = validate(e)) return r;
+    if (int r = validate_reuse(e, ru)) return r;
+    launch_engine_keep_subtrees(e, ru, child_index, st);
+    return check_launch("engine_keep_subtrees_kernel");
+}
+
+int engine_reset_reuse(const aqg_engine& e, const aqg_tree_reuse& ru, hipStream_t st) {
+    if (int r = validate(e)) return r;
+    if (int r = validate_reuse(e, ru)) return r;
+    if (hipMemsetAsync(ru.kept, 0, (size_t)e.num_games, st) != hipSuccess) return fail("hipMemsetAsync(kept)");
+    return 0;
 }
 
 int engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st) {

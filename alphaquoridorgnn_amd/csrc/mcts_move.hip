@@ -53,16 +53,19 @@ __global__ void engine_set_roots_kernel(aqg_engine e, const uint8_t* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
-// begin move: fresh tree per move (pv_mcts.py:81: no tree reuse)
+// begin move: fresh tree per move (pv_mcts.py:81: no tree reuse) -- except in a slot that engine_keep_subtrees_kernel (mcts_reuse.hip)
+// has marked in `kept` (nullptr = tree reuse off): its pool holds the chosen child's subtree, re-rooted, and node_count its size
 // ------------------------------------------------------------------------------------------------
-__global__ void engine_begin_move_kernel(aqg_engine e) {
+__global__ void engine_begin_move_kernel(aqg_engine e, const uint8_t* __restrict__ kept) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (e.eval_count) for (int i = g; i <= e.sims; i += gridDim.x * blockDim.x) e.eval_count[i] = 0;      // evaluation cache: entries of each simulation's list
     if (g >= e.num_games || !e.game_active[g]) return;
-    NodeRec root;
-    root.w = 0.0; root.p = 0.f; root.n = 0; root.kids = 0; root.action = 0xFF; root.q = 0.f; root.cp = 0.f;
-    game_nodes(e, g)[0] = root;
-    e.node_count[g] = 1;
+    if (!(kept && kept[g])) {
+        NodeRec root;
+        root.w = 0.0; root.p = 0.f; root.n = 0; root.kids = 0; root.action = 0xFF; root.q = 0.f; root.cp = 0.f;
+        game_nodes(e, g)[0] = root;
+        e.node_count[g] = 1;
+    }
     const int k = e.slot_game[g];                  // the game this slot is playing
     const int ply = e.game_plies[k];
     if (e.hist_visits && ply < e.max_plies) {      // clear this ply's dense visit row (filled by finish_move)
@@ -151,6 +154,33 @@ __device__ __forceinline__ double root_noise_gamma(uint64_t key, double alpha) {
     return fmax(val, DBL_MIN);               // u ^ (1 / alpha) may underflow: a variate is never 0
 }
 
+// eta of one root, the recipe of aqgnn.h: lane i + 64 r gets eta[r] = f32(g_i / S) of legal action i + 64 r from the caller's table or
+// from the generator's stream of (seed, game, plies).  false = no usable noise (S is 0 or not finite): the root keeps its priors.
+__device__ __forceinline__ bool root_noise_eta(const aqg_engine& e, int g, int plies, int cnt, int lane, float (&eta)[3]) {
+    double gv[3] = {0.0, 0.0, 0.0};
+    if (e.root_noise) {
+        const double* row = e.root_noise + (size_t)g * MAX_LEGAL;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int i = lane + 64 * r;
+            if (i < cnt) { const double x = row[i]; gv[r] = (x > 0.0 && x <= DBL_MAX) ? x : 0.0; }      // not > 0 or not finite: 0
+        }
+    } else {
+        const uint64_t key = stream_key(stream_key(e.root_noise_seed, (uint64_t)(uint32_t)e.slot_game[g]), (uint64_t)plies);
+        const double alpha = (double)e.root_noise_alpha;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int i = lane + 64 * r;
+            if (i < cnt) gv[r] = root_noise_gamma(stream_key(key, (uint64_t)i), alpha);
+        }
+    }
+    const double S = wave_sum_d((gv[0] + gv[1]) + gv[2]);
+    if (!(S > 0.0 && S <= DBL_MAX)) return false;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) eta[r] = (float)(gv[r] / S);
+    return true;
+}
+
 template <int N>
 __global__ __launch_bounds__(256) void engine_root_noise_kernel(aqg_engine e) {
     constexpr int A = Geo<N>::A;
@@ -189,39 +219,47 @@ __global__ __launch_bounds__(256) void engine_root_noise_kernel(aqg_engine e) {
         for (int r = 0; r < 3; ++r) { const int i = lane + 64 * r; pl[r] = (i < cnt) ? pol[i] : 0.f; }
     }
     // the gamma variates: the caller's table, or the generator's stream of (seed, game, ply), one sub-stream per component
-    double gv[3] = {0.0, 0.0, 0.0};
-    if (e.root_noise) {
-        const double* row = e.root_noise + (size_t)g * MAX_LEGAL;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const int i = lane + 64 * r;
-            if (i < cnt) { const double x = row[i]; gv[r] = (x > 0.0 && x <= DBL_MAX) ? x : 0.0; }      // not > 0 or not finite: 0
-        }
-    } else {
-        const QState root = load_state(e.leaf_state, 1, g);
-        const uint64_t key = stream_key(stream_key(e.root_noise_seed, (uint64_t)(uint32_t)e.slot_game[g]), (uint64_t)root.plies);
-        const double alpha = (double)e.root_noise_alpha;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const int i = lane + 64 * r;
-            if (i < cnt) gv[r] = root_noise_gamma(stream_key(key, (uint64_t)i), alpha);
-        }
-    }
-    const double S = wave_sum_d((gv[0] + gv[1]) + gv[2]);
-    if (!(S > 0.0 && S <= DBL_MAX)) return;                              // no usable noise: the root keeps its priors, untouched
+    float eta[3] = {0.f, 0.f, 0.f};
+    if (!root_noise_eta(e, g, e.root_noise ? 0 : (int)load_state(e.leaf_state, 1, g).plies, cnt, lane, eta)) return;      // the root keeps its priors, untouched
     const float eps = e.root_noise_eps, keep = 1.0f - eps;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         const int i = lane + 64 * r;
         if (i < cnt) {
-            const float eta = (float)(gv[r] / S);
-            const float x = keep * pl[r], y = eps * eta;
+            const float x = keep * pl[r], y = eps * eta[r];
             pol[i] = x + y;
         }
     }
     if (lane == 0) {
         if (gather) e.leaf_flag[g] = 2;                                  // the row is now legal-ordered and normalised
         if (e.eval_cache_keys) e.eval_cache_slot[g] = -1;                // ... and must never be stored under the position's key
+    }
+}
+
+// Root noise of a KEPT root (aqgnn.h, "tree reuse"): the root is expanded already, so the launch above -- which acts on a root that is
+// the pending leaf -- skips it.  Same formula, same key, same table; p' goes into the stored p of the root's children and cp =
+// f32(c_puct * p') is rewritten with it, in front of simulation 0's step, so every selection at the root sees the mixed priors.  These
+// children were an inner node's until the keep launch: no prior is ever mixed twice.  The evaluation cache is not involved.
+__global__ __launch_bounds__(256) void engine_kept_root_noise_kernel(aqg_engine e, const uint8_t* __restrict__ kept) {
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= e.num_games || !e.game_active[g] || !kept[g]) return;
+    NodeRec* __restrict__ nodes = game_nodes(e, g);
+    const uint32_t kids = nodes[0].kids;
+    const int cnt = __builtin_amdgcn_readfirstlane(min((int)(kids >> 24), (int)MAX_LEGAL)), first = (int)(kids & 0xFFFFFF);
+    if (cnt <= 0 || first + cnt > e.node_cap) return;
+    float eta[3] = {0.f, 0.f, 0.f};
+    if (!root_noise_eta(e, g, e.root_noise ? 0 : (int)load_state(e.root_state, 1, g).plies, cnt, lane, eta)) return;
+    const float eps = e.root_noise_eps, keep = 1.0f - eps;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const int i = lane + 64 * r;
+        if (i < cnt) {
+            NodeRec& c = nodes[first + i];
+            const float x = keep * c.p, y = eps * eta[r];
+            const float p = x + y;
+            c.p = p; c.cp = e.c_puct * p;
+        }
     }
 }
 
@@ -260,10 +298,13 @@ __device__ __forceinline__ void engine_transition(const aqg_engine& e, int g, in
 // The two training-target options of aqgnn.h ("self-play targets") are kernel arguments, not engine fields -- this launch is not part
 // of the captured graph: temperature_plies K > 0 = a root at ply >= K takes the first maximum, as temperature 0 does; hist_value !=
 // nullptr = the root's search value w / n from the mover's side, f32 [quota, max_plies] beside hist_action.  (0, nullptr) = neither.
+// Tree reuse (aqgnn.h, "tree reuse"): child_index != nullptr = the slot's marker is cleared -- its root changes -- and the index of the
+// chosen child in the root's block is left for engine_keep_subtrees_kernel, -1 where the game does not go on.
 // ------------------------------------------------------------------------------------------------
 template <int N>
 __global__ __launch_bounds__(256) void engine_finish_move_kernel(aqg_engine e, const double* __restrict__ uniforms, int temperature_plies,
-                                                                 float* __restrict__ hist_value) {
+                                                                 float* __restrict__ hist_value, int32_t* __restrict__ child_index,
+                                                                 uint8_t* __restrict__ kept) {
     constexpr int A = Geo<N>::A;
     const int lane = threadIdx.x & 63;
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -289,9 +330,9 @@ __global__ __launch_bounds__(256) void engine_finish_move_kernel(aqg_engine e, c
         hist_value[(size_t)k * e.max_plies + ply] = n ? (float)(w / (double)n) : 0.0f;
     }
 
-    int chosen = -1;
+    int chosen = -1, idx = -1;
     if (cnt > 0) {
-        int idx = 0;
+        idx = 0;
         const bool late = temperature_plies > 0 && (int)s.plies >= temperature_plies;      // the schedule: arg-max from ply K on
         if (e.temperature == 0.f || late) {                    // one-hot at the first maximum, then choice(p=one-hot)
             int bestn = -1;
@@ -323,6 +364,7 @@ __global__ __launch_bounds__(256) void engine_finish_move_kernel(aqg_engine e, c
         chosen = (int)nodes[first + idx].action;
     }
     engine_transition<N>(e, g, k, ply, s, chosen);
+    if (child_index) { child_index[g] = e.game_active[g] ? idx : -1; kept[g] = 0; }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -443,8 +485,12 @@ void launch_engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStr
     hipLaunchKernelGGL(engine_set_roots_kernel, dim3((e.num_games + 255) / 256), dim3(256), 0, st, e, roots72);
 }
 
-void launch_engine_begin_move(const aqg_engine& e, hipStream_t st) {
-    hipLaunchKernelGGL(engine_begin_move_kernel, dim3((e.num_games + 255) / 256), dim3(256), 0, st, e);
+void launch_engine_begin_move(const aqg_engine& e, hipStream_t st, const uint8_t* kept) {
+    hipLaunchKernelGGL(engine_begin_move_kernel, dim3((e.num_games + 255) / 256), dim3(256), 0, st, e, kept);
+}
+
+void launch_engine_kept_root_noise(const aqg_engine& e, const uint8_t* kept, hipStream_t st) {
+    hipLaunchKernelGGL(engine_kept_root_noise_kernel, dim3((e.num_games + 3) / 4), dim3(256), 0, st, e, kept);
 }
 
 int launch_engine_fake_eval(const aqg_engine& e, hipStream_t st) {
@@ -463,10 +509,11 @@ int launch_engine_root_noise(const aqg_engine& e_in, hipStream_t st) {
     });
 }
 
-int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st) {
+int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st,
+                              int32_t* child_index, uint8_t* kept) {
     return for_board_size(e.board_size, [&](auto n) {
         hipLaunchKernelGGL(engine_finish_move_kernel<decltype(n)::value>, dim3((e.num_games + 3) / 4), dim3(256), 0, st, e, uniforms,
-                           temperature_plies, hist_value);
+                           temperature_plies, hist_value, child_index, kept);
         return 0;
     });
 }

@@ -59,6 +59,81 @@ def check_target_options(temperature_plies, record_search_value=False, record_hi
     return int(temperature_plies), bool(record_search_value)
 
 
+def check_tree_reuse(tree_reuse, tree_reuse_visits, sims, evaluator="gnn"):
+    """Validate the tree-reuse options as the library does (include/aqgnn.h, "tree reuse").  Returns keep_visits, or None when the
+    option is off.  tree_reuse_visits None = `sims`; 0 is legal: on, never keeps."""
+    if not tree_reuse:
+        if tree_reuse_visits is not None:
+            raise ValueError("tree_reuse_visits needs tree_reuse=True")
+        return None
+    if evaluator == "external":
+        raise ValueError("tree_reuse is not offered with evaluator='external': its host loop has no keep step")
+    keep = sims if tree_reuse_visits is None else tree_reuse_visits
+    if isinstance(keep, bool) or int(keep) != keep or int(keep) < 0:
+        raise ValueError(f"tree_reuse_visits must be an integer >= 0, not {tree_reuse_visits!r}")
+    keep = int(keep)
+    if keep + int(sims) > 32767:
+        raise ValueError("tree_reuse_visits + sims must be <= 32767: the visit row is read out as int16")
+    if 1 + (keep + int(sims)) * _lib.MAX_LEGAL >= 1 << 24:
+        raise ValueError("tree_reuse_visits + sims is too large: the tree pool must stay below 2**24 records")
+    return keep
+
+
+def refuse_tree_reuse(what, **options):
+    """Matches and evaluation paths search from a fresh tree every move (two alternating searchers would need a two-ply descent
+    into per-model trees): an option that asks for tree reuse is a mistake, not something to drop silently."""
+    bad = sorted(k for k, v in options.items() if v is not None)
+    if bad:
+        raise ValueError(f"{what} never keeps a subtree between moves: {', '.join(bad)} is a self-play option")
+
+
+NODE_DTYPE = np.dtype([("w", "<f8"), ("p", "<f4"), ("action", "<u4"), ("n", "<i4"), ("kids", "<u4"), ("q", "<f4"), ("cp", "<f4")])
+assert NODE_DTYPE.itemsize == 32      # csrc/mcts_tree.hpp NodeRec
+
+
+def keep_subtree_reference(pool_records, node_count, child_index, keep_visits):
+    """The keep launch (csrc/mcts_reuse.hip) for one slot, in numpy.  pool_records: the slot's pool, NODE_DTYPE [cap] (or anything
+    of 32 bytes per record, e.g. float64 [cap, 4]); node_count: its used records; child_index: index of the chosen child in the root's
+    child block, < 0 = do not keep.  Returns (records, count, kept): kept is True iff the index names a child that is expanded with
+    n <= keep_visits; then records[:count] is the child's subtree re-rooted -- the child at 0 with a fresh root's action / p / cp, every
+    kept child block behind it in ascending order of its old first index, child ranges renamed -- and records[count:] is unspecified
+    (here: the input's).  Not kept: the input's records and count."""
+    src = np.ascontiguousarray(pool_records).view(NODE_DTYPE).reshape(-1)
+    out = src.copy()
+    count = min(int(node_count), src.shape[0])
+    idx = int(child_index)
+    if idx < 0 or count <= 1:
+        return out, int(node_count), False
+    rcnt, rfirst = int(src["kids"][0]) >> 24, int(src["kids"][0]) & 0xFFFFFF
+    if idx >= rcnt or rfirst < 1 or rfirst + rcnt > count:
+        return out, int(node_count), False
+    c = src[rfirst + idx]
+    ccnt, cfirst = int(c["kids"]) >> 24, int(c["kids"]) & 0xFFFFFF
+    if ccnt == 0 or int(c["n"]) > int(keep_visits) or cfirst < rfirst + rcnt or cfirst + ccnt > count:
+        return out, int(node_count), False
+    keep = np.zeros(count, dtype=bool)
+    keep[cfirst:cfirst + ccnt] = True
+    kids = src["kids"][:count].astype(np.int64)
+    for i in range(cfirst, count):            # a node's child block lies behind the node: one ascending pass decides every record
+        if keep[i] and kids[i] >> 24:
+            first, cnt = int(kids[i] & 0xFFFFFF), int(kids[i] >> 24)
+            assert first > i, "a child block lies behind its parent"
+            keep[first:min(first + cnt, count)] = True
+    new_index = np.cumsum(keep)               # 1-based among the kept records == the new index (0 is the new root)
+    old = np.nonzero(keep)[0]
+    moved = src[old].copy()
+    exp = (moved["kids"] >> 24) != 0
+    firsts = (moved["kids"][exp] & 0xFFFFFF).astype(np.int64)
+    moved["kids"][exp] = (new_index[firsts].astype(np.uint32) & 0xFFFFFF) | (moved["kids"][exp] & np.uint32(0xFF000000))
+    total = 1 + old.shape[0]
+    out[1:total] = moved
+    root = np.zeros((), dtype=NODE_DTYPE)
+    root["w"], root["n"], root["q"] = c["w"], c["n"], c["q"]
+    root["action"], root["kids"] = 0xFF, 1 | (ccnt << 24)
+    out[0] = root
+    return out, total, True
+
+
 def _mix64_int(z):
     """The splitmix64 finaliser on a Python int (include/aqgnn.h)."""
     z &= _MASK64
@@ -144,7 +219,8 @@ def draw_root_noise(seed, k, ply, count, alpha, return_exhausted=False):
 class BatchedSelfPlay:
     def __init__(self, model=None, num_games=2048, sims=50, board_size=BOARD_SIZE, device=None, temperature=1.0,
                  c_puct=1.25, evaluator="gnn", fake_bias=0, seed=0, record_history=True, quota=None, eval_cache_slots=None,
-                 root_noise_eps=0.0, root_noise_alpha=None, root_noise_seed=None, temperature_plies=0, record_search_value=False):
+                 root_noise_eps=0.0, root_noise_alpha=None, root_noise_seed=None, temperature_plies=0, record_search_value=False,
+                 tree_reuse=False, tree_reuse_visits=None):
         """model: GraphPolicyValueNetwork/GNNNetwork (evaluator='gnn'); evaluator='fake' runs the integer-hash
         evaluator used by the parity tests (oracle/mcts.py FakeModel); evaluator='external' calls `model.predict(state,
         device)` -- ANY object honouring the reference's BaseNetwork contract (BaseNetwork.py:36-40), e.g. a stock CNN --
@@ -164,7 +240,14 @@ class BatchedSelfPlay:
         temperature_plies K (0 = off, the default): a root at ply < K is sampled at `temperature` as always, one at ply >= K takes
         the first maximum of the visit counts; the recorded visit rows do not change, only the choice.  record_search_value (needs
         record_history): every searched move also records the root's search value w / n from the mover's side, float32, beside its
-        history row -- history_values().  With both off move() makes the calls it always made."""
+        history row -- history_values().  With both off move() makes the calls it always made.
+        tree_reuse (off by default: nothing changes; include/aqgnn.h, "tree reuse"): the next move's search starts from the subtree
+        of the child this move chose -- when the game goes on, the child is expanded and holds at most tree_reuse_visits visits
+        (None = `sims`; 0 = on, never keeps) -- and runs the same `sims` simulations on top.  The recorded visit rows and search
+        values include the kept visits.  The tree pool and the path are sized for tree_reuse_visits + sims.  Not with
+        evaluator='external', and search() refuses it; tree_reuse_stats() counts the kept moves."""
+        self.keep_visits = check_tree_reuse(tree_reuse, tree_reuse_visits, sims, evaluator)
+        self.tree_reuse = self.keep_visits is not None
         self.temperature_plies, self.record_search_value = check_target_options(temperature_plies, record_search_value, record_history)
         self.root_noise_eps, self.root_noise_alpha = check_root_noise(
             root_noise_eps, default_root_noise_alpha(board_size) if root_noise_alpha is None else root_noise_alpha)
@@ -183,7 +266,8 @@ class BatchedSelfPlay:
         self.quota = self.G if quota is None else int(quota)
         if self.quota < self.G:
             raise ValueError("quota must be >= num_games")
-        self.node_cap = 1 + self.sims * _lib.MAX_LEGAL
+        depth = self.sims + (self.keep_visits or 0)                # visits a tree can hold: its expanded nodes and its depth
+        self.node_cap = 1 + depth * _lib.MAX_LEGAL
         self.max_plies = self.plies_for_draw
         self.model = model
         self.evaluator = evaluator
@@ -198,7 +282,7 @@ class BatchedSelfPlay:
         t["node_rec"] = z((G * cap, 4), torch.float64)     # 32-byte node records (csrc/mcts_tree.hpp NodeRec)
         t["node_count"] = z((G,), torch.int32)
         t["root_state"] = z((G, 24), torch.uint8)
-        t["path"] = z((G, self.sims + 2), torch.int32)
+        t["path"] = z((G, depth + 2), torch.int32)
         t["path_len"] = z((G,), torch.int32)
         t["leaf_flag"] = z((G,), torch.uint8)
         t["leaf_state"] = z((G, 24), torch.uint8)
@@ -268,6 +352,16 @@ class BatchedSelfPlay:
             e.eval_cache_log2 = self.eval_cache_slots.bit_length() - 1
         e.root_noise_eps, e.root_noise_alpha = self.root_noise_eps, self.root_noise_alpha
         e.root_noise_seed = self.root_noise_seed if self.root_noise_eps else 0      # off: the four fields are zero
+        self.reuse = None
+        if self.tree_reuse:
+            t["kept"] = z((G,), torch.uint8)
+            t["child_index"] = torch.full((G,), -1, dtype=torch.int32, device=dev)
+            t["stat_moves_kept"] = z((G,), torch.int32)
+            t["stat_visits_kept"] = z((G,), torch.int32)
+            ru = self.reuse = _lib.TreeReuseStruct()
+            ru.keep_visits = self.keep_visits
+            for name in ("kept", "child_index", "stat_moves_kept", "stat_visits_kept"):
+                setattr(ru, name, t[name].data_ptr())
         self.record_history = record_history
         self.moves_done = 0
         self.reset()
@@ -278,7 +372,24 @@ class BatchedSelfPlay:
 
     def reset(self):
         _lib.check(self.lib.aqg_engine_reset(ctypes.byref(self.e), self._stream()), "aqg_engine_reset")
+        if self.tree_reuse:
+            self._forget_kept_trees()
+            self.t["stat_moves_kept"].zero_()
+            self.t["stat_visits_kept"].zero_()
         self.moves_done = 0
+
+    def _forget_kept_trees(self):
+        """Clear the "kept" marker: behind everything but a searched move that changes a slot's root."""
+        _lib.check(self.lib.aqg_engine_reset_reuse(ctypes.byref(self.e), ctypes.byref(self.reuse), self._stream()), "aqg_engine_reset_reuse")
+
+    def tree_reuse_stats(self):
+        """Since the last reset: dict(moves_kept = searched moves that started from a kept subtree, mean_kept_visits = the visits
+        such a subtree held on average, 0.0 without one).  Needs tree_reuse=True."""
+        if not self.tree_reuse:
+            raise ValueError("tree_reuse_stats needs tree_reuse=True")
+        moves = int(self.t["stat_moves_kept"].sum().item())
+        visits = int(self.t["stat_visits_kept"].to(torch.int64).sum().item())
+        return dict(moves_kept=moves, mean_kept_visits=visits / moves if moves else 0.0)
 
     def refresh_weights(self):
         """Point the engine at the model's current weights; the evaluation cache is cleared when they are not the cached ones."""
@@ -325,6 +436,9 @@ class BatchedSelfPlay:
                            "aqg_engine_finish_move_targets")
             else:
                 _lib.check(self.lib.aqg_engine_finish_move(ctypes.byref(self.e), _lib.ptr(uniforms), self._stream()), "aqg_engine_finish_move")
+        elif self.tree_reuse:
+            _lib.check(self.lib.aqg_engine_move_reuse(ctypes.byref(self.e), _lib.ptr(uniforms), *extra, ctypes.byref(self.reuse), self._stream()),
+                       "aqg_engine_move_reuse")
         elif targets:
             _lib.check(self.lib.aqg_engine_move_targets(ctypes.byref(self.e), _lib.ptr(uniforms), *extra, self._stream()),
                        "aqg_engine_move_targets")
@@ -346,6 +460,8 @@ class BatchedSelfPlay:
         actions = torch.as_tensor(actions, dtype=torch.int32).to(self.dev).contiguous().view(self.G)
         self._applied = actions  # keep alive until the stream has consumed it
         _lib.check(self.lib.aqg_engine_apply_actions(ctypes.byref(self.e), _lib.ptr(actions), self._stream()), "aqg_engine_apply_actions")
+        if self.tree_reuse:
+            self._forget_kept_trees()      # the roots changed without a search: the next move starts from fresh trees
         self.moves_done += 1
 
     # ------------------------------------------------------------------ external evaluator (prior_mode 2)
@@ -442,6 +558,8 @@ class BatchedSelfPlay:
         (one 4-byte copy: the callers read the visit counts back anyway); if a launch of this search met a value outside fp16 range its
         evaluations were finite but not the network's, so the weight set is marked (model.mark_saturated), the engine switches to the
         exact f32-input kernels and the search is repeated -- the caller never receives visit counts of clamped evaluations."""
+        if self.tree_reuse:
+            raise ValueError("search() looks at caller-given roots from fresh trees: build the engine without tree_reuse")
         roots = torch.as_tensor(root_states72, dtype=torch.uint8).to(self.dev).contiguous().view(self.G, 72)
         self._roots = roots
         self._set_root_noise(root_noise)
@@ -619,6 +737,13 @@ class MultiSetSelfPlay:
 
     def deferred_legal_searches(self):
         return sum(eng.deferred_legal_searches() for _, eng in self._each())
+
+    def tree_reuse_stats(self):
+        """The sets' tree_reuse_stats() together (needs tree_reuse=True)."""
+        parts = [eng.tree_reuse_stats() for _, eng in self._each()]
+        moves = sum(p["moves_kept"] for p in parts)
+        visits = sum(p["moves_kept"] * p["mean_kept_visits"] for p in parts)
+        return dict(moves_kept=moves, mean_kept_visits=visits / moves if moves else 0.0)
 
     def play_generation(self, check_every=4):
         ply = 0

@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from . import pv_mcts
 from .constants import PV_NETWORK_PATH, BOARD_SIZE
-from .engine import BatchedSelfPlay, TwoEngineMatch, refuse_root_noise
+from .engine import BatchedSelfPlay, TwoEngineMatch, refuse_root_noise, refuse_tree_reuse
 from .evaluators import BINDINGS
 from .game_logic import State
 from .pv_network_gnn import GNNNetwork, load_network
@@ -57,9 +57,11 @@ class BatchedMatch(TwoEngineMatch):
     CNNNetworks, whose shapes may differ too) or integer biases of the parity tests' hash evaluator (evaluator='fake')."""
 
     def __init__(self, players, num_games, sims=None, board_size=BOARD_SIZE, temperature=EN_TEMPERATURE,
-                 evaluator="gnn", seed=0, device=None, root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None):
+                 evaluator="gnn", seed=0, device=None, root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None,
+                 tree_reuse=None, tree_reuse_visits=None):
         # (an evaluation match measures the networks as they are: root exploration noise is a self-play option and is refused)
         refuse_root_noise("BatchedMatch", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
+        refuse_tree_reuse("BatchedMatch", tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits)
         if evaluator == "external":
             raise ValueError("BatchedMatch has no evaluator='external': an engine asks one model, eng.model, from the host")
         self.players, self.evaluator, self.binding = players, evaluator, BINDINGS[evaluator]
@@ -96,12 +98,13 @@ class BatchedMatch(TwoEngineMatch):
         super()._switch_to_exact_kernels()
 
 
-def evaluate_network(root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None):
+def evaluate_network(root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None, tree_reuse=None, tree_reuse_visits=None):
     """Network evaluation (evaluate_network.py:52-94): latest vs best, promote when the average point exceeds 0.5.  Two
     default 6/128/3 networks play on the engine's fused evaluator ('gnn'); when either file holds another shape, both play on
     its any-shape evaluator ('general').  Two CNNs (pv_network_cnn.py) play on the engine's CNN evaluator ('cnn'); a CNN against
     a GNN is refused (ValueError)."""
     refuse_root_noise("evaluate_network", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
+    refuse_tree_reuse("evaluate_network", tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits)
     model0 = load_network(PV_NETWORK_PATH + 'latest.pth')
     model1 = load_network(PV_NETWORK_PATH + 'best.pth')
     cnn = [isinstance(m, CNNNetwork) for m in (model0, model1)]

@@ -30,6 +30,10 @@ SP_ROOT_NOISE_ALPHA = None   # None = 10 / (N^2 + 2 (N - 1)^2), the "10 / typica
 # (1 - L) z + L q, q the search value of its root -- a float32 in the window and, with the same bits, a float in the .history file.
 SP_TEMPERATURE_PLIES = 0     # 0 = off: every ply at SP_TEMPERATURE
 SP_VALUE_BLEND = 0.0         # 0 = off: z alone, an int
+# Tree reuse (the reference has none; engine.BatchedSelfPlay, include/aqgnn.h "tree reuse"): the next move's search starts from the chosen
+# child's subtree when that holds at most SP_TREE_REUSE_VISITS visits (None = the simulation count) and runs the same simulations on top.
+SP_TREE_REUSE = False        # off: a fresh tree every move, the reference's search
+SP_TREE_REUSE_VISITS = None
 # Replay window (the reference has none; replay.ReplayWindow): every rank appends the gathered generation to SP_REPLAY, straight from
 # the engine's device tensors, for train_network.TRAIN_WINDOW to train on.  The .history file stays the reference's hand-over.
 SP_REPLAY = None             # None = off
@@ -95,7 +99,7 @@ def play(model, device=None, uniforms=None):
                           temperature=SP_TEMPERATURE, seed=int(np.random.randint(0, 2 ** 31 - 1)),
                           evaluator=pv_mcts.evaluator_of(model), root_noise_eps=SP_ROOT_NOISE_EPS,
                           root_noise_alpha=SP_ROOT_NOISE_ALPHA, temperature_plies=SP_TEMPERATURE_PLIES,
-                          record_search_value=blend > 0.0)
+                          record_search_value=blend > 0.0, tree_reuse=SP_TREE_REUSE, tree_reuse_visits=SP_TREE_REUSE_VISITS)
     eng.play_generation(uniforms=uniforms, check_every=1)
     if blend > 0.0:
         return _history_rows(*eng.history_tensors(), BOARD_SIZE, eng.history_values(), blend)
@@ -146,7 +150,8 @@ def self_play(model=None, games=None, seed=None):
         eng = MultiSetSelfPlay(model, num_games=mine, sims=pv_mcts.PV_EVALUATE_COUNT, num_sets=None if mine >= 256 else 1,
                                board_size=BOARD_SIZE, temperature=SP_TEMPERATURE, seed=(base + rank) % (2 ** 31 - 1), device=dev,
                                evaluator=evaluator, root_noise_eps=SP_ROOT_NOISE_EPS, root_noise_alpha=SP_ROOT_NOISE_ALPHA,
-                               temperature_plies=SP_TEMPERATURE_PLIES, record_search_value=blend > 0.0)
+                               temperature_plies=SP_TEMPERATURE_PLIES, record_search_value=blend > 0.0,
+                               tree_reuse=SP_TREE_REUSE, tree_reuse_visits=SP_TREE_REUSE_VISITS)
         c = eng.play_generation()
         print(f'\rSelf-play (rank {rank}: {c["finished"]}/{mine} games)', end='')
         st, vis, z = eng.history_tensors()

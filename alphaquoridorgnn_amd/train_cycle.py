@@ -168,6 +168,12 @@ def _parser():
     ap.add_argument("--temperature-plies", type=int, default=None,
                     help="self-play: plies of a game sampled at SP_TEMPERATURE before the most visited move is taken (default "
                          "SP_TEMPERATURE_PLIES = 0: every ply is sampled)")
+    ap.add_argument("--tree-reuse", action="store_true",
+                    help="self-play: start each move's search from the chosen child's subtree (default SP_TREE_REUSE = False: a fresh "
+                         "tree every move)")
+    ap.add_argument("--tree-reuse-visits", type=int, default=None,
+                    help="self-play, with --tree-reuse: keep a subtree of at most this many visits (default SP_TREE_REUSE_VISITS: the "
+                         "simulation count)")
     ap.add_argument("--value-blend", type=float, default=None,
                     help="self-play: weight L in [0, 1] of the root's search value in the value target, (1 - L) z + L q (default "
                          "SP_VALUE_BLEND = 0: the game outcome alone)")
@@ -223,6 +229,15 @@ def _set_target_options(args):
         sp.SP_VALUE_BLEND = check_value_blend(args.value_blend)
 
 
+def _set_tree_reuse_options(args):
+    """--tree-reuse / --tree-reuse-visits onto self_play's constants, refused here if the engine would refuse them."""
+    from . import pv_mcts, self_play as sp
+    from .engine import check_tree_reuse
+    if args.tree_reuse or args.tree_reuse_visits is not None:
+        check_tree_reuse(args.tree_reuse, args.tree_reuse_visits, pv_mcts.PV_EVALUATE_COUNT)
+        sp.SP_TREE_REUSE, sp.SP_TREE_REUSE_VISITS = True, args.tree_reuse_visits
+
+
 def _set_mirror_options(args):
     """--mirror-augment / --mirror-seed onto train_network's constants (the stages read them at call time)."""
     from . import train_network as tn
@@ -253,6 +268,7 @@ def main(argv=None):
     if args.epochs is not None:
         tn.NUM_EPOCH = args.epochs
     _set_target_options(args)
+    _set_tree_reuse_options(args)
     _set_mirror_options(args)
     _set_replay_options(args)
     if args.eval_games is not None:

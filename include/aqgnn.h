@@ -469,6 +469,58 @@ int aqg_engine_move_targets(const aqg_engine* e_host, const double* uniforms, in
 int aqg_engine_finish_move_targets(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value,
                                    void* stream);
 
+/* ------------------------------------------------------------------ tree reuse (additive to ABI 15; the reference has none: pv_mcts.py:81)
+ *
+ * Opt-in: the next move's search starts from the subtree of the child this move chose instead of from an empty tree.  The option
+ * travels as a small struct beside the engine struct, which does not change; the entry points above behave as they always did.
+ *
+ * The rule.  After a searched move at root R whose chosen child is c (index idx in R's child block), the next move's search starts
+ * from c with its subtree as it stands -- every descendant's w, n, q, p, cp, action and child order -- iff
+ *     the game goes on (not lost, not drawn, not the dead end),   c is expanded (kids != 0),   c.n <= keep_visits;
+ * otherwise from a fresh root, exactly as without the option.  On top of either start the move runs the same `sims` simulations.
+ * A node's subtree holds at most n expanded nodes and is at most n deep, so with K = keep_visits the caller sizes
+ *     node_cap >= 1 + (K + sims) * AQG_MAX_LEGAL  (and < 2^24),     path [G, K + sims + 2],     K + sims <= 32767
+ * (a visit count stays <= K + sims, and the visit row is read out as int16).  The step kernels are handed the struct with `sims`
+ * replaced by K + sims -- their path stride -- and are otherwise unchanged; eval_count stays [sims + 1].
+ * The new root record takes c's w, n, q and its renamed child range, and action 0xFF, p 0, cp 0 like a fresh root; n == 1 + the sum
+ * of its children's n holds for it as for any expanded node.  The recorded visit row is the root's children's n and hist_value the
+ * root's w / n, kept visits included.
+ *
+ * The keep launch (csrc/mcts_reuse.hip, engine_keep_subtrees_kernel; one wavefront per slot, no atomics, behind the finish-move
+ * launch and outside the captured graph) re-roots the pool in place and in the old index order: c goes to index 0, then every kept
+ * child block follows in ascending order of its old first index with the kept nodes' child ranges renamed, so c's own block lands at
+ * index 1.  node_count[g] becomes the number of kept records; records behind it are unspecified.  While it runs it keeps its marks in
+ * bits 8..31 of the records' action words, which are zero in every record before and after.  A slot whose tree is not kept, or that
+ * is inactive, has its pool and node_count left byte for byte; the marker of an active slot that is not kept is cleared.
+ * kept [G] u8, the marker: set by the keep launch only; the begin-move launch leaves a marked slot's pool and node_count alone (it
+ * still clears the visit row and the evaluation-cache lists).  The finish-move launch of the _reuse entry points clears it (the root
+ * changes); aqg_engine_reset, _set_roots and _apply_actions do not know it: call aqg_engine_reset_reuse behind them.  Slot refill
+ * only touches inactive slots, which are never marked.
+ * Root noise: a kept root is expanded already, so its noise -- same formula, key (seed, game, ply) and table as above -- is mixed
+ * into its children's stored p, and cp = f32(c_puct * p') is rewritten, by one more launch in front of simulation 0's step (only with
+ * root_noise_eps > 0).  Those children were never a root's before, so no prior is mixed twice.  A fresh root takes the launch above.
+ * A game's kept trees are a function of the game alone: slots, refill order and set count do not change a game's rows.
+ *
+ * Refused before any launch: keep_visits < 0, keep_visits + sims > 32767, node_cap < 1 + (keep_visits + sims) * AQG_MAX_LEGAL,
+ * prior_mode 2 (the external evaluator's loop has no keep step), a NULL buffer.  The per-move hipGraph is keyed by the marker's
+ * address and keep_visits as well, so a reuse move and a plain move of one engine never replay each other's graph. */
+typedef struct aqg_tree_reuse {
+    int32_t keep_visits;            /* K >= 0; 0 = on, never keeps */
+    uint8_t* kept;                  /* [G] the marker */
+    int32_t* child_index;           /* [G] index of the chosen child in the root's block, -1 = do not keep (finish-move -> keep launch) */
+    int32_t* stat_moves_kept;       /* [G] moves that started from a kept subtree ... */
+    int32_t* stat_visits_kept;      /* [G] ... and the visits those subtrees held (summed by the host) */
+} aqg_tree_reuse;
+/* aqg_engine_move_targets / aqg_engine_finish_move_targets with the option: the keep launch follows the finish-move launch. */
+int aqg_engine_move_reuse(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                          const aqg_tree_reuse* reuse, void* stream);
+int aqg_engine_finish_move_reuse(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                                 const aqg_tree_reuse* reuse, void* stream);
+/* The keep launch alone on caller-given child indices [G] i32 (device), -1 = do not keep: for tests.  reuse->child_index is not read. */
+int aqg_engine_keep_subtrees(const aqg_engine* e_host, const aqg_tree_reuse* reuse, const int32_t* child_index, void* stream);
+/* Clear the marker (the statistics are the caller's to clear): behind aqg_engine_reset, aqg_engine_set_roots and aqg_engine_apply_actions. */
+int aqg_engine_reset_reuse(const aqg_engine* e_host, const aqg_tree_reuse* reuse, void* stream);
+
 /* ------------------------------------------------------------------ baseline agents in batch (agents.py; additive to ABI 14)
  *
  * The reference's random and rollout-MCTS agents (agents.py:14-18, :111-214) for B states at once, one wavefront per state
