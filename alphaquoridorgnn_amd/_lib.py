@@ -72,6 +72,12 @@ class TreeReuseStruct(_c.Structure):
     _fields_ = [("keep_visits", _i32), ("kept", _vp), ("child_index", _vp), ("stat_moves_kept", _vp), ("stat_visits_kept", _vp)]
 
 
+class ResignStruct(_c.Structure):
+    """Mirror of `struct aqg_resign` (include/aqgnn.h, "resignation"): the option beside the engine struct."""
+    _fields_ = [("threshold", _c.c_float), ("min_ply", _i32), ("disable_fraction", _c.c_double), ("seed", _c.c_uint64),
+                ("resign_min", _vp), ("game_resigned", _vp)]
+
+
 class TrainStruct(_c.Structure):
     """Mirror of `struct aqg_train` (include/aqgnn.h)."""
     _fields_ = (
@@ -159,6 +165,11 @@ SIGNATURES = {
     "aqg_engine_finish_move_reuse": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _c.POINTER(TreeReuseStruct), _vp]),
     "aqg_engine_keep_subtrees": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.POINTER(TreeReuseStruct), _vp, _vp]),
     "aqg_engine_reset_reuse": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.POINTER(TreeReuseStruct), _vp]),
+    "aqg_engine_move_resign": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _c.POINTER(TreeReuseStruct),
+                                          _c.POINTER(ResignStruct), _vp]),
+    "aqg_engine_finish_move_resign": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _c.POINTER(TreeReuseStruct),
+                                                 _c.POINTER(ResignStruct), _vp]),
+    "aqg_engine_reset_resign": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.POINTER(ResignStruct), _vp]),
     "aqg_engine_set_roots": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_engine_root_visits": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp, _vp, _vp]),
     "aqg_engine_root_noise": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),

@@ -247,6 +247,20 @@ int aqg_engine_reset_reuse(const aqg_engine* e, const aqg_tree_reuse* reuse, voi
     if (!e || !reuse) return fail("aqg_engine_reset_reuse: null argument");
     return engine_reset_reuse(*e, *reuse, (hipStream_t)stream);
 }
+int aqg_engine_move_resign(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                           const aqg_tree_reuse* reuse, const aqg_resign* resign, void* stream) {
+    if (!e || !uniforms || !resign) return fail("aqg_engine_move_resign: null argument");
+    return engine_move_resign(*e, uniforms, temperature_plies, hist_value, reuse, *resign, (hipStream_t)stream);
+}
+int aqg_engine_finish_move_resign(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                                  const aqg_tree_reuse* reuse, const aqg_resign* resign, void* stream) {
+    if (!e || !uniforms || !resign) return fail("aqg_engine_finish_move_resign: null argument");
+    return engine_finish_move_resign(*e, uniforms, temperature_plies, hist_value, reuse, *resign, (hipStream_t)stream);
+}
+int aqg_engine_reset_resign(const aqg_engine* e, const aqg_resign* resign, void* stream) {
+    if (!e || !resign) return fail("aqg_engine_reset_resign: null argument");
+    return engine_reset_resign(*e, *resign, (hipStream_t)stream);
+}
 int aqg_engine_set_roots(const aqg_engine* e, const uint8_t* root_states72, void* stream) {
     if (!e || !root_states72) return fail("aqg_engine_set_roots: null argument");
     return engine_set_roots(*e, root_states72, (hipStream_t)stream);

@@ -110,6 +110,11 @@ int engine_finish_move_reuse(const aqg_engine& e, const double* uniforms, int te
                              const aqg_tree_reuse& ru, hipStream_t st);
 int engine_keep_subtrees(const aqg_engine& e, const aqg_tree_reuse& ru, const int32_t* child_index, hipStream_t st);
 int engine_reset_reuse(const aqg_engine& e, const aqg_tree_reuse& ru, hipStream_t st);
+int engine_move_resign(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, const aqg_tree_reuse* ru,
+                       const aqg_resign& rs, hipStream_t st);
+int engine_finish_move_resign(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value,
+                              const aqg_tree_reuse* ru, const aqg_resign& rs, hipStream_t st);
+int engine_reset_resign(const aqg_engine& e, const aqg_resign& rs, hipStream_t st);
 
 // ---- mcts_step.hip  (launchers of the engine's kernels only enqueue: the entry point checks the launch)
 extern int g_step_waves, g_step_prio, g_step_fast_depth, g_step_heads;
@@ -130,7 +135,7 @@ void launch_engine_kept_root_noise(const aqg_engine& e, const uint8_t* kept, hip
 int launch_engine_fake_eval(const aqg_engine& e, hipStream_t st);
 int launch_engine_root_noise(const aqg_engine& e, hipStream_t st);
 int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st,
-                              int32_t* child_index = nullptr, uint8_t* kept = nullptr);
+                              int32_t* child_index = nullptr, uint8_t* kept = nullptr, const aqg_resign* resign = nullptr);
 void launch_engine_refill(const aqg_engine& e, hipStream_t st);
 int launch_engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st);
 void launch_engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st);

@@ -202,10 +202,11 @@ static int run_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reuse* r
 // (outside the captured graph, so the two target options are plain arguments: 0 / nullptr = off)
 // (tree reuse: finish_move leaves the chosen child's index, the keep launch re-roots the pools of the games that go on -- in front of the
 //  refill, whose new games start in slots that are inactive here and therefore never marked)
+// (resignation: the option is the finish-move launch's last argument; a resigned slot is inactive behind it, like any finished one)
 static int finish_and_refill(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st,
-                             const aqg_tree_reuse* reuse = nullptr) {
+                             const aqg_tree_reuse* reuse = nullptr, const aqg_resign* resign = nullptr) {
     if (int r = launch_engine_finish_move(e, uniforms, temperature_plies, hist_value, st, reuse ? reuse->child_index : nullptr,
-                                          reuse ? reuse->kept : nullptr))
+                                          reuse ? reuse->kept : nullptr, resign))
         return r;
     if (reuse) launch_engine_keep_subtrees(e, *reuse, reuse->child_index, st);
     if (e.quota > e.num_games) launch_engine_refill(e, st);
@@ -220,9 +221,9 @@ static int validate_targets(const aqg_engine& e, int temperature_plies, const fl
 }
 
 static int do_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st,
-                   const aqg_tree_reuse* reuse = nullptr) {
+                   const aqg_tree_reuse* reuse = nullptr, const aqg_resign* resign = nullptr) {
     if (int r = run_sims(e, st, reuse)) return r;
-    return finish_and_refill(e, uniforms, temperature_plies, hist_value, st, reuse);
+    return finish_and_refill(e, uniforms, temperature_plies, hist_value, st, reuse, resign);
 }
 
 // what the tree-reuse entry points refuse, before anything is launched (aqgnn.h, "tree reuse")
@@ -305,6 +306,42 @@ int engine_reset_reuse(const aqg_engine& e, const aqg_tree_reuse& ru, hipStream_
     if (int r = validate(e)) return r;
     if (int r = validate_reuse(e, ru)) return r;
     if (hipMemsetAsync(ru.kept, 0, (size_t)e.num_games, st) != hipSuccess) return fail("hipMemsetAsync(kept)");
+    return 0;
+}
+
+// what the resignation entry points refuse, before anything is launched (aqgnn.h, "resignation")
+static int validate_resign(const aqg_engine& e, const aqg_resign& rs) {
+    if (!(rs.threshold > 0.f && rs.threshold <= 1.f)) return fail("resignation: threshold must be in (0, 1]");
+    if (rs.min_ply < 0) return fail("resignation: min_ply must be >= 0");
+    if (!(rs.disable_fraction >= 0.0 && rs.disable_fraction <= 1.0)) return fail("resignation: disable_fraction must be in [0, 1]");
+    if (!rs.resign_min || !rs.game_resigned) return fail("resignation: resign_min / game_resigned are required");
+    if (e.max_plies <= 0) return fail("resignation needs a history (max_plies > 0)");
+    return 0;
+}
+
+int engine_move_resign(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, const aqg_tree_reuse* ru,
+                       const aqg_resign& rs, hipStream_t st) {
+    if (int r = validate(e)) return r;
+    if (int r = validate_targets(e, temperature_plies, hist_value)) return r;
+    if (ru) if (int r = validate_reuse(e, *ru)) return r;
+    if (int r = validate_resign(e, rs)) return r;
+    return do_move(e, uniforms, temperature_plies, hist_value, st, ru, &rs);
+}
+
+int engine_finish_move_resign(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value,
+                              const aqg_tree_reuse* ru, const aqg_resign& rs, hipStream_t st) {
+    if (int r = validate(e)) return r;
+    if (int r = validate_targets(e, temperature_plies, hist_value)) return r;
+    if (ru) if (int r = validate_reuse(e, *ru)) return r;
+    if (int r = validate_resign(e, rs)) return r;
+    return finish_and_refill(e, uniforms, temperature_plies, hist_value, st, ru, &rs);
+}
+
+int engine_reset_resign(const aqg_engine& e, const aqg_resign& rs, hipStream_t st) {
+    if (int r = validate(e)) return r;
+    if (int r = validate_resign(e, rs)) return r;
+    if (hipMemsetD32Async((hipDeviceptr_t)rs.resign_min, 0x7F800000, (size_t)e.quota * 2, st) != hipSuccess) return fail("hipMemsetD32Async(resign_min)");      // +inf
+    if (hipMemsetAsync(rs.game_resigned, 0, (size_t)e.quota, st) != hipSuccess) return fail("hipMemsetAsync(game_resigned)");
     return 0;
 }
 

@@ -268,8 +268,11 @@ __global__ __launch_bounds__(256) void engine_kept_root_noise_kernel(aqg_engine 
 // (engine_finish_move_kernel) and a caller-given one (engine_apply_actions_kernel) have in common, so that matches and
 // self-play record games the same way.  hist_action, next(), plies, lose / draw / z, the counters, game_active.
 // ------------------------------------------------------------------------------------------------
+// `resigned` (aqgnn.h, "resignation"): the mover gives up at s -- the row's action is 0xFF, no move is applied, and s itself is the
+// ended position, lost for its mover.
 template <int N>
-__device__ __forceinline__ void engine_transition(const aqg_engine& e, int g, int k, int ply, const QState& s, int chosen) {
+__device__ __forceinline__ void engine_transition(const aqg_engine& e, int g, int k, int ply, const QState& s, int chosen,
+                                                  bool resigned = false) {
     if (chosen < 0) {
         // Dead end: legal_actions() is empty.  The reference would re-predict forever-leaf and np.random.choice([])
         // raises; we abort the game as a draw and count it.
@@ -277,11 +280,14 @@ __device__ __forceinline__ void engine_transition(const aqg_engine& e, int g, in
         atomicAdd(&e.counters[2], 1); atomicAdd(&e.counters[1], 1); atomicSub(&e.counters[0], 1);
         return;
     }
-    if (ply < e.max_plies) e.hist_action[(size_t)k * e.max_plies + ply] = (uint8_t)chosen;
-    const QState t = next_state<N>(s, chosen);
-    store_state(e.root_state, g, t);
+    if (ply < e.max_plies) e.hist_action[(size_t)k * e.max_plies + ply] = resigned ? (uint8_t)0xFF : (uint8_t)chosen;
+    QState t = s;
+    if (!resigned) {
+        t = next_state<N>(s, chosen);
+        store_state(e.root_state, g, t);
+    }
     e.game_plies[k] = ply + 1;
-    const bool lose = is_lose<N>(t), draw = is_draw(t, e.plies_for_draw);
+    const bool lose = resigned || is_lose<N>(t), draw = !resigned && is_draw(t, e.plies_for_draw);
     if (lose || draw) {
         // first_player_value (self_play.py:22-27): ended state's mover lost; z of ply 0, alternating afterwards (:63-66)
         int z = 0;
@@ -300,11 +306,15 @@ __device__ __forceinline__ void engine_transition(const aqg_engine& e, int g, in
 // nullptr = the root's search value w / n from the mover's side, f32 [quota, max_plies] beside hist_action.  (0, nullptr) = neither.
 // Tree reuse (aqgnn.h, "tree reuse"): child_index != nullptr = the slot's marker is cleared -- its root changes -- and the index of the
 // chosen child in the root's block is left for engine_keep_subtrees_kernel, -1 where the game does not go on.
+// Resignation (aqgnn.h, "resignation"): rs.resign_min != nullptr = on.  The pass over the children that finds the arg-max / the
+// sampling total also finds the first maximum of the visit counts; m = max(root value, that child's q) goes into the running
+// minimum of (game, side), and an enabled game whose m is below -threshold ends here with the mover as loser.  An all-zero rs =
+// off: nothing below reads or writes through it.
 // ------------------------------------------------------------------------------------------------
 template <int N>
 __global__ __launch_bounds__(256) void engine_finish_move_kernel(aqg_engine e, const double* __restrict__ uniforms, int temperature_plies,
                                                                  float* __restrict__ hist_value, int32_t* __restrict__ child_index,
-                                                                 uint8_t* __restrict__ kept) {
+                                                                 uint8_t* __restrict__ kept, aqg_resign rs) {
     constexpr int A = Geo<N>::A;
     const int lane = threadIdx.x & 63;
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -330,19 +340,23 @@ __global__ __launch_bounds__(256) void engine_finish_move_kernel(aqg_engine e, c
         hist_value[(size_t)k * e.max_plies + ply] = n ? (float)(w / (double)n) : 0.0f;
     }
 
-    int chosen = -1, idx = -1;
+    int chosen = -1, idx = -1, best = 0;                      // best: the first maximum of the visit counts
     if (cnt > 0) {
         idx = 0;
         const bool late = temperature_plies > 0 && (int)s.plies >= temperature_plies;      // the schedule: arg-max from ply K on
         if (e.temperature == 0.f || late) {                    // one-hot at the first maximum, then choice(p=one-hot)
             int bestn = -1;
             for (int i = 0; i < cnt; ++i) { const int n = nodes[first + i].n; if (n > bestn) { bestn = n; idx = i; } }
+            best = idx;
         } else {
             // boltzman (pv_mcts.py:106-109): xs = n ** (1/T); p = x / sum(xs).  T == 1 is exact (n ** 1.0 == float(n)).
             const double invT = 1.0 / (double)e.temperature;
             double tot = 0.0;
+            int bestn = -1;
             for (int i = 0; i < cnt; ++i) {
-                const double x = (double)nodes[first + i].n;
+                const int n = nodes[first + i].n;
+                if (n > bestn) { bestn = n; best = i; }
+                const double x = (double)n;
                 tot += (e.temperature == 1.f) ? x : pow(x, invT);
             }
             // np.random.choice: cdf = cumsum(p); cdf /= cdf[-1]; searchsorted(cdf, u, side='right')
@@ -363,7 +377,21 @@ __global__ __launch_bounds__(256) void engine_finish_move_kernel(aqg_engine e, c
         }
         chosen = (int)nodes[first + idx].action;
     }
-    engine_transition<N>(e, g, k, ply, s, chosen);
+    bool resigned = false;
+    const int p = (int)s.plies;
+    if (rs.resign_min && cnt > 0 && p >= rs.min_ply) {
+        const double rw = nodes[0].w, cw = nodes[first + best].w;
+        const int rn = nodes[0].n, cn = nodes[first + best].n;
+        const float v_root = rn ? (float)(rw / (double)rn) : 0.0f;
+        const float v_best = cn ? (float)(-cw / (double)cn) : 0.0f;
+        const float m = fmaxf(v_root, v_best);
+        float* lo = rs.resign_min + (size_t)k * 2 + (p & 1);   // this game's, this side's: only this lane writes it
+        if (m < *lo) *lo = m;
+        const bool enabled = counter_uniform(stream_key(rs.seed, (uint64_t)(uint32_t)k), 0) >= rs.disable_fraction;
+        resigned = enabled && m < -rs.threshold;
+        if (resigned) rs.game_resigned[k] = 1;
+    }
+    engine_transition<N>(e, g, k, ply, s, chosen, resigned);
     if (child_index) { child_index[g] = e.game_active[g] ? idx : -1; kept[g] = 0; }
 }
 
@@ -510,10 +538,11 @@ int launch_engine_root_noise(const aqg_engine& e_in, hipStream_t st) {
 }
 
 int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st,
-                              int32_t* child_index, uint8_t* kept) {
+                              int32_t* child_index, uint8_t* kept, const aqg_resign* resign) {
+    const aqg_resign rs = resign ? *resign : aqg_resign{};     // all zero = off
     return for_board_size(e.board_size, [&](auto n) {
         hipLaunchKernelGGL(engine_finish_move_kernel<decltype(n)::value>, dim3((e.num_games + 3) / 4), dim3(256), 0, st, e, uniforms,
-                           temperature_plies, hist_value, child_index, kept);
+                           temperature_plies, hist_value, child_index, kept, rs);
         return 0;
     });
 }

@@ -87,6 +87,101 @@ def refuse_tree_reuse(what, **options):
         raise ValueError(f"{what} never keeps a subtree between moves: {', '.join(bad)} is a self-play option")
 
 
+def check_resign(resign_threshold, resign_min_ply=0, resign_disable_fraction=0.1, record_history=True):
+    """Validate the resignation options as the library does (include/aqgnn.h, "resignation"), on the values its struct holds.
+    Returns (threshold, min_ply, disable_fraction), or None when the option is off (resign_threshold None).  A threshold of 1.0 is
+    legal: on, never resigns -- the statistics are still kept."""
+    if resign_threshold is None:
+        return None
+    if isinstance(resign_threshold, (bool, str)):
+        raise ValueError(f"resign_threshold must be a number in (0, 1], not {resign_threshold!r}")
+    thr = float(np.float32(resign_threshold))
+    if not 0.0 < thr <= 1.0:
+        raise ValueError(f"resign_threshold must be in (0, 1] as a float32, not {resign_threshold!r}")
+    if isinstance(resign_min_ply, bool) or int(resign_min_ply) != resign_min_ply or not 0 <= int(resign_min_ply) < 2 ** 31:
+        raise ValueError(f"resign_min_ply must be an integer >= 0, not {resign_min_ply!r}")
+    frac = float(resign_disable_fraction)
+    if not 0.0 <= frac <= 1.0:
+        raise ValueError(f"resign_disable_fraction must be in [0, 1], not {resign_disable_fraction!r}")
+    if not record_history:
+        raise ValueError("resignation needs record_history: a resigned game ends in a history row")
+    return thr, int(resign_min_ply), frac
+
+
+def refuse_resign(what, **options):
+    """Matches, evaluation paths and moves the engine does not search play every game to its rule end: an option that asks for
+    resignation is a mistake, not something to drop silently."""
+    bad = sorted(k for k, v in options.items() if v is not None)
+    if bad:
+        raise ValueError(f"{what} never resigns a game: {', '.join(bad)} is a self-play option")
+
+
+def default_resign_seed(seed):
+    """The resignation seed of an engine that was given none: `seed` through the mixer (see default_root_noise_seed)."""
+    return _mix64_int((int(seed) & _MASK64) ^ 0x52455349474E4544)
+
+
+def draw_resign_enabled(seed, k, disable_fraction=0.1):
+    """Whether game k may resign under the resignation seed `seed`: counter_uniform(stream_key(seed, k), 0) >= disable_fraction --
+    the draw of engine_finish_move_kernel in numpy (include/aqgnn.h, "resignation").  k may be an array of game indices."""
+    from .agents import _mix64
+    G = np.uint64(_GOLDEN)
+    kk = np.asarray(k, dtype=np.int64).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        key = _mix64(np.uint64(int(seed) & _MASK64) + G * (kk + np.uint64(1)))
+        z = _mix64(key + G)
+    u = (z >> np.uint64(11)).astype(np.float64) * (2.0 ** -53)
+    out = u >= float(disable_fraction)
+    return bool(out) if np.ndim(k) == 0 else out
+
+
+def _side_loses(game_result):
+    """bool [K, 2]: side s of game k (s = ply parity: 0 the first player) lost."""
+    z = np.asarray(game_result).astype(np.int64).reshape(-1)
+    return np.stack([z < 0, z > 0], axis=1)
+
+
+def resign_false_positives(resign_min, game_result, enabled, threshold):
+    """The calibration count over the DISABLED games (they were played to their rule end): (would_resign, false_positives,
+    eligible_sides) = the sides whose running minimum is below -threshold (f32), how many of those did not lose, and the number of
+    sides that did not lose.  resign_min [K, 2] f32, game_result [K] the first player's value, enabled [K] bool."""
+    lo = np.asarray(resign_min, dtype=np.float32).reshape(-1, 2)
+    off = ~np.asarray(enabled, dtype=bool).reshape(-1)
+    would = (lo < -np.float32(threshold)) & off[:, None]
+    fine = ~_side_loses(game_result) & off[:, None]
+    return int(would.sum()), int((would & fine).sum()), int(fine.sum())
+
+
+def suggest_resign_threshold(resign_min, game_result, enabled, max_false_positive, min_sides=None, min_threshold=0.05):
+    """The threshold that resigns the most while the false-positive rate of resign_false_positives -- of the played-out (disabled)
+    games' sides that would have resigned, the share that did not lose -- stays at or under `max_false_positive`.  The cut is
+    m < -T, so the candidates are T = -x for every distinct minimum x of those sides in [-1, -min_threshold), and T = min_threshold
+    itself: at T = -x exactly the sides with a minimum below x would have resigned (ties fall on one side of the cut together).  The
+    rate need not fall steadily as T grows, so every candidate is counted and the smallest T that qualifies wins -- the largest cut
+    value -T.  A candidate qualifies only if at least `min_sides` sides would have resigned at it (default max(20, ceil(1 / bound)):
+    with fewer than 1 / bound of them one false positive already exceeds the bound).  None when no candidate qualifies: too few sides
+    to say, or the network's lost-looking games are not lost (a network whose games end in draws never resigns)."""
+    bound = float(max_false_positive)
+    if not 0.0 <= bound < 1.0:
+        raise ValueError(f"max_false_positive must be in [0, 1), not {max_false_positive!r}")
+    floor = np.float32(min_threshold)
+    if not 0.0 < float(floor) <= 1.0:
+        raise ValueError(f"min_threshold must be in (0, 1], not {min_threshold!r}")
+    lo = np.asarray(resign_min, dtype=np.float32).reshape(-1, 2)
+    off = ~np.asarray(enabled, dtype=bool).reshape(-1)
+    every = np.sort(lo[np.broadcast_to(off[:, None], lo.shape)])
+    fine = np.sort(lo[~_side_loses(game_result) & off[:, None]])
+    if min_sides is None:
+        min_sides = max(20, int(np.ceil(1.0 / bound))) if bound > 0.0 else 20
+    cuts = np.unique(np.concatenate([every[every < -floor], np.asarray([-floor], dtype=np.float32)]))
+    would = np.searchsorted(every, cuts, side="left")              # sides with a minimum strictly below the cut
+    wrong = np.searchsorted(fine, cuts, side="left")
+    ok = (would >= max(1, int(min_sides))) & (wrong <= bound * would + 1e-9)
+    if not ok.any():
+        return None
+    return float(np.float32(-cuts[np.flatnonzero(ok)[-1]]))
+
+
 NODE_DTYPE = np.dtype([("w", "<f8"), ("p", "<f4"), ("action", "<u4"), ("n", "<i4"), ("kids", "<u4"), ("q", "<f4"), ("cp", "<f4")])
 assert NODE_DTYPE.itemsize == 32      # csrc/mcts_tree.hpp NodeRec
 
@@ -216,11 +311,28 @@ def draw_root_noise(seed, k, ply, count, alpha, return_exhausted=False):
     return (val, exhausted) if return_exhausted else val
 
 
+def resign_stats_of(parts, threshold):
+    """resign_stats over the (resign_min, game_result, enabled, game_resigned, game_plies, game_done) tuples of one or more engines."""
+    lo, res, enabled, flag, plies, done = (np.concatenate([np.asarray(p[i]) for p in parts], 0) for i in range(6))
+    fin = done != 0
+    would, wrong, fine = resign_false_positives(lo[fin], res[fin], enabled[fin], threshold)
+    return dict(games=int(fin.sum()), games_resigned=int(flag[fin].astype(bool).sum()), plies=int(plies[fin].sum()),
+                disabled_games=int((~enabled[fin]).sum()), would_resign=would, false_positives=wrong,
+                false_positive_rate=wrong / would if would else 0.0, eligible_sides=fine)
+
+
+def suggest_from_arrays(parts, max_false_positive, **kw):
+    lo, res, enabled, _, _, done = (np.concatenate([np.asarray(p[i]) for p in parts], 0) for i in range(6))
+    fin = done != 0
+    return suggest_resign_threshold(lo[fin], res[fin], enabled[fin], max_false_positive, **kw)
+
+
 class BatchedSelfPlay:
     def __init__(self, model=None, num_games=2048, sims=50, board_size=BOARD_SIZE, device=None, temperature=1.0,
                  c_puct=1.25, evaluator="gnn", fake_bias=0, seed=0, record_history=True, quota=None, eval_cache_slots=None,
                  root_noise_eps=0.0, root_noise_alpha=None, root_noise_seed=None, temperature_plies=0, record_search_value=False,
-                 tree_reuse=False, tree_reuse_visits=None):
+                 tree_reuse=False, tree_reuse_visits=None, resign_threshold=None, resign_min_ply=0, resign_disable_fraction=0.1,
+                 resign_seed=None):
         """model: GraphPolicyValueNetwork/GNNNetwork (evaluator='gnn'); evaluator='fake' runs the integer-hash
         evaluator used by the parity tests (oracle/mcts.py FakeModel); evaluator='external' calls `model.predict(state,
         device)` -- ANY object honouring the reference's BaseNetwork contract (BaseNetwork.py:36-40), e.g. a stock CNN --
@@ -245,7 +357,15 @@ class BatchedSelfPlay:
         of the child this move chose -- when the game goes on, the child is expanded and holds at most tree_reuse_visits visits
         (None = `sims`; 0 = on, never keeps) -- and runs the same `sims` simulations on top.  The recorded visit rows and search
         values include the kept visits.  The tree pool and the path are sized for tree_reuse_visits + sims.  Not with
-        evaluator='external', and search() refuses it; tree_reuse_stats() counts the kept moves."""
+        evaluator='external', and search() refuses it; tree_reuse_stats() counts the kept moves.
+        resign_threshold T (None = off, the default: move() makes the calls it makes today; include/aqgnn.h, "resignation"): after a
+        searched move at ply >= resign_min_ply the mover resigns when max(root value, most visited child's q) < -T; the game ends
+        there with the mover as loser, its last row's action 0xFF.  A share resign_disable_fraction of the games -- drawn per GAME
+        index from resign_seed (None = derived from `seed`), draw_resign_enabled -- never resigns, and every game keeps the running
+        minimum of that maximum per side, so resign_stats() can count false positives and suggest_resign_threshold() can pick T.
+        T = 1.0 never resigns and only collects.  apply_actions() and search() refuse the option."""
+        self.resign_options = check_resign(resign_threshold, resign_min_ply, resign_disable_fraction, record_history)
+        self.resign_seed = default_resign_seed(seed) if resign_seed is None else int(resign_seed) & _MASK64
         self.keep_visits = check_tree_reuse(tree_reuse, tree_reuse_visits, sims, evaluator)
         self.tree_reuse = self.keep_visits is not None
         self.temperature_plies, self.record_search_value = check_target_options(temperature_plies, record_search_value, record_history)
@@ -362,6 +482,14 @@ class BatchedSelfPlay:
             ru.keep_visits = self.keep_visits
             for name in ("kept", "child_index", "stat_moves_kept", "stat_visits_kept"):
                 setattr(ru, name, t[name].data_ptr())
+        self.resign = None
+        if self.resign_options:
+            t["resign_min"] = torch.full((Q, 2), float("inf"), dtype=torch.float32, device=dev)
+            t["game_resigned"] = z((Q,), torch.uint8)
+            rs = self.resign = _lib.ResignStruct()
+            rs.threshold, rs.min_ply, rs.disable_fraction = self.resign_options
+            rs.seed = self.resign_seed
+            rs.resign_min, rs.game_resigned = t["resign_min"].data_ptr(), t["game_resigned"].data_ptr()
         self.record_history = record_history
         self.moves_done = 0
         self.reset()
@@ -376,7 +504,36 @@ class BatchedSelfPlay:
             self._forget_kept_trees()
             self.t["stat_moves_kept"].zero_()
             self.t["stat_visits_kept"].zero_()
+        if self.resign is not None:
+            _lib.check(self.lib.aqg_engine_reset_resign(ctypes.byref(self.e), ctypes.byref(self.resign), self._stream()), "aqg_engine_reset_resign")
         self.moves_done = 0
+
+    # ------------------------------------------------------------------ resignation
+    def set_resign_threshold(self, threshold):
+        """Another threshold from the next move on (the option must be on: it is a kernel argument, nothing is rebuilt)."""
+        if self.resign is None:
+            raise ValueError("set_resign_threshold needs resign_threshold")
+        self.resign_options = check_resign(threshold, *self.resign_options[1:])
+        self.resign.threshold = self.resign_options[0]
+
+    def resign_arrays(self):
+        """(resign_min f32 [quota, 2], game_result i8 [quota], enabled bool [quota], game_resigned u8 [quota], game_plies i32 [quota],
+        game_done u8 [quota]) as numpy arrays: what the calibration is computed from.  Needs resign_threshold."""
+        if self.resign is None:
+            raise ValueError("the resignation statistics need resign_threshold")
+        lo, res, flag, plies, done = (self.t[k].cpu().numpy() for k in ("resign_min", "game_result", "game_resigned", "game_plies", "game_done"))
+        enabled = draw_resign_enabled(self.resign_seed, np.arange(self.quota), self.resign_options[2])
+        return lo, res, enabled, flag, plies, done
+
+    def resign_stats(self):
+        """Since the last reset, over the finished games: dict(games, games_resigned, plies = the plies played, disabled_games, and over
+        the disabled games would_resign = the sides whose running minimum fell below -threshold, false_positives = how many of those
+        did not lose, false_positive_rate = their ratio (0.0 without one), eligible_sides = the sides that did not lose)."""
+        return resign_stats_of([self.resign_arrays()], self.resign_options[0])
+
+    def suggest_resign_threshold(self, max_false_positive, **kw):
+        """suggest_resign_threshold (above) on this engine's finished games; None when there are too few sides to say."""
+        return suggest_from_arrays([self.resign_arrays()], max_false_positive, **kw)
 
     def _forget_kept_trees(self):
         """Clear the "kept" marker: behind everything but a searched move that changes a slot's root."""
@@ -431,11 +588,18 @@ class BatchedSelfPlay:
         extra = (self.temperature_plies, _lib.ptr(self.t.get("hist_value")))
         if self.evaluator == "external":
             self._external_sims()
-            if targets:
+            if self.resign is not None:
+                _lib.check(self.lib.aqg_engine_finish_move_resign(ctypes.byref(self.e), _lib.ptr(uniforms), *extra, None,
+                                                                  ctypes.byref(self.resign), self._stream()), "aqg_engine_finish_move_resign")
+            elif targets:
                 _lib.check(self.lib.aqg_engine_finish_move_targets(ctypes.byref(self.e), _lib.ptr(uniforms), *extra, self._stream()),
                            "aqg_engine_finish_move_targets")
             else:
                 _lib.check(self.lib.aqg_engine_finish_move(ctypes.byref(self.e), _lib.ptr(uniforms), self._stream()), "aqg_engine_finish_move")
+        elif self.resign is not None:
+            _lib.check(self.lib.aqg_engine_move_resign(ctypes.byref(self.e), _lib.ptr(uniforms), *extra,
+                                                       ctypes.byref(self.reuse) if self.tree_reuse else None, ctypes.byref(self.resign),
+                                                       self._stream()), "aqg_engine_move_resign")
         elif self.tree_reuse:
             _lib.check(self.lib.aqg_engine_move_reuse(ctypes.byref(self.e), _lib.ptr(uniforms), *extra, ctypes.byref(self.reuse), self._stream()),
                        "aqg_engine_move_reuse")
@@ -457,6 +621,8 @@ class BatchedSelfPlay:
     def apply_actions(self, actions):
         """Play actions[g] (int32 [G]; -1 = this active slot has no legal action: its game ends as a draw) in every active slot
         without a search: history row, next(), terminal handling exactly as move() does them."""
+        if self.resign is not None:
+            raise ValueError("apply_actions() plays moves nobody searched: build the engine without resign_threshold")
         actions = torch.as_tensor(actions, dtype=torch.int32).to(self.dev).contiguous().view(self.G)
         self._applied = actions  # keep alive until the stream has consumed it
         _lib.check(self.lib.aqg_engine_apply_actions(ctypes.byref(self.e), _lib.ptr(actions), self._stream()), "aqg_engine_apply_actions")
@@ -560,6 +726,8 @@ class BatchedSelfPlay:
         exact f32-input kernels and the search is repeated -- the caller never receives visit counts of clamped evaluations."""
         if self.tree_reuse:
             raise ValueError("search() looks at caller-given roots from fresh trees: build the engine without tree_reuse")
+        if self.resign is not None:
+            raise ValueError("search() plays no game: build the engine without resign_threshold")
         roots = torch.as_tensor(root_states72, dtype=torch.uint8).to(self.dev).contiguous().view(self.G, 72)
         self._roots = roots
         self._set_root_noise(root_noise)
@@ -648,7 +816,10 @@ class MultiSetSelfPlay:
     BatchedSelfPlay(num_games_k, seed = seed * 64 + k): nothing is shared but the read-only packed weights (and the K
     streams, which every engine of the process reuses -- see _SET_STREAMS)."""
 
-    def __init__(self, model=None, num_games=2048, sims=50, num_sets=None, seed=0, device=None, quota=None, root_noise_seed=None, **kw):
+    def __init__(self, model=None, num_games=2048, sims=50, num_sets=None, seed=0, device=None, quota=None, root_noise_seed=None,
+                 resign_seed=None, **kw):
+        check_resign(kw.get("resign_threshold"), kw.get("resign_min_ply", 0), kw.get("resign_disable_fraction", 0.1),
+                     kw.get("record_history", True))          # before anything is allocated
         self.dev = _lib.require_gpu(device)
         if num_sets is None:                      # one hardware queue per set + the default stream, or fall back to 2
             queues = os.environ.get("GPU_MAX_HW_QUEUES")
@@ -668,6 +839,9 @@ class MultiSetSelfPlay:
         if model is not None and BINDINGS[kw.get("evaluator", "gnn")].packed:
             model.packed_weights(self.dev)        # pack (+ calibrate) (two forwards and a host sync) on the caller's stream, not inside set 0's
         noise_seeds = set_noise_seeds(seed, root_noise_seed, sizes, [max(q, g) for q, g in zip(quotas, sizes)])
+        # the sets' games are numbered through for the enabled / disabled draw as they are for the noise: the numbering rides in the seed
+        resign_seeds = set_noise_seeds(seed, default_resign_seed(seed) if resign_seed is None else resign_seed, sizes,
+                                       [max(q, g) for q, g in zip(quotas, sizes)])
         self.sets = []
         ready = torch.cuda.current_stream(self.dev).record_event()   # e.g. the model's weight upload on the caller's stream
         for i, g in enumerate(sizes):
@@ -675,7 +849,7 @@ class MultiSetSelfPlay:
                 self.streams[i].wait_event(ready)
                 self.sets.append(BatchedSelfPlay(model, num_games=g, sims=sims, seed=int(seed) * 64 + i, device=self.dev,
                                                  quota=max(quotas[i], g),
-                                                 root_noise_seed=noise_seeds[i], **kw))
+                                                 root_noise_seed=noise_seeds[i], resign_seed=resign_seeds[i], **kw))
         self.G, self.sims = int(num_games), int(sims)
         self.quota = self.G if quota is None else int(quota)
         if self.quota < self.G:
@@ -744,6 +918,22 @@ class MultiSetSelfPlay:
         moves = sum(p["moves_kept"] for p in parts)
         visits = sum(p["moves_kept"] * p["mean_kept_visits"] for p in parts)
         return dict(moves_kept=moves, mean_kept_visits=visits / moves if moves else 0.0)
+
+    def set_resign_threshold(self, threshold):
+        for eng in self.sets:
+            eng.set_resign_threshold(threshold)
+
+    def resign_arrays(self):
+        """The sets' resign_arrays() in set order, concatenated (needs resign_threshold)."""
+        parts = [eng.resign_arrays() for _, eng in self._each()]
+        return tuple(np.concatenate([p[i] for p in parts], 0) for i in range(6))
+
+    def resign_stats(self):
+        """The sets' resign_stats() together (needs resign_threshold)."""
+        return resign_stats_of([self.resign_arrays()], self.sets[0].resign_options[0])
+
+    def suggest_resign_threshold(self, max_false_positive, **kw):
+        return suggest_from_arrays([self.resign_arrays()], max_false_positive, **kw)
 
     def play_generation(self, check_every=4):
         ply = 0
@@ -875,3 +1065,27 @@ def gather_history(states72, visits, z, group=None, force_collective=None, value
     if values is not None:
         return s, v, zz, allrows[:, 73 + 2 * A:].contiguous().view(torch.float32).view(-1)
     return s, v, zz
+
+
+def gather_resign_arrays(arrays, group=None, device="cpu"):
+    """The resignation statistics of every rank, over the exchange of gather_history: a game's record -- its two minima, result,
+    enabled flag, resigned flag, done flag and plies -- rides in the 72 bytes of a state row, one row per game.  arrays: the tuple of
+    resign_arrays(), or None on a rank that played no game.  Returns the tuple over all ranks, in rank order (the inputs when no
+    group is up).  device: where the exchange's tensors live ('cpu' for gloo, the rank's GPU for RCCL)."""
+    if arrays is None:
+        arrays = (np.zeros((0, 2), np.float32), np.zeros((0,), np.int8), np.zeros((0,), bool), np.zeros((0,), np.uint8),
+                  np.zeros((0,), np.int32), np.zeros((0,), np.uint8))
+    lo, res, enabled, flag, plies, done = arrays
+    K = int(np.asarray(res).shape[0])
+    rec = np.zeros((K, 72), dtype=np.uint8)
+    rec[:, 0:8] = np.ascontiguousarray(lo, dtype="<f4").reshape(K, 2).view(np.uint8).reshape(K, 8)
+    rec[:, 8], rec[:, 9], rec[:, 10] = np.asarray(enabled, dtype=np.uint8), np.asarray(flag, dtype=np.uint8), np.asarray(done, dtype=np.uint8)
+    rec[:, 12:16] = np.ascontiguousarray(plies, dtype="<i4").reshape(K, 1).view(np.uint8).reshape(K, 4)
+    st = torch.from_numpy(rec).to(device)
+    vis = torch.zeros((K, 1), dtype=torch.int16, device=device)
+    z = torch.from_numpy(np.ascontiguousarray(res, dtype=np.int8)).to(device)
+    st, _, z = gather_history(st, vis, z, group=group)
+    rec, res = st.cpu().numpy(), z.cpu().numpy()
+    K = rec.shape[0]
+    return (np.ascontiguousarray(rec[:, 0:8]).view("<f4").reshape(K, 2), res.astype(np.int8), rec[:, 8].astype(bool), rec[:, 9].copy(),
+            np.ascontiguousarray(rec[:, 12:16]).view("<i4").reshape(K), rec[:, 10].copy())

@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from . import pv_mcts
 from .constants import PV_NETWORK_PATH, BOARD_SIZE
-from .engine import BatchedSelfPlay, TwoEngineMatch, refuse_root_noise, refuse_tree_reuse
+from .engine import BatchedSelfPlay, TwoEngineMatch, refuse_resign, refuse_root_noise, refuse_tree_reuse
 from .evaluators import BINDINGS
 from .game_logic import State
 from .pv_network_gnn import GNNNetwork, load_network
@@ -58,10 +58,13 @@ class BatchedMatch(TwoEngineMatch):
 
     def __init__(self, players, num_games, sims=None, board_size=BOARD_SIZE, temperature=EN_TEMPERATURE,
                  evaluator="gnn", seed=0, device=None, root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None,
-                 tree_reuse=None, tree_reuse_visits=None):
+                 tree_reuse=None, tree_reuse_visits=None, resign_threshold=None, resign_min_ply=None,
+                 resign_disable_fraction=None, resign_seed=None):
         # (an evaluation match measures the networks as they are: root exploration noise is a self-play option and is refused)
         refuse_root_noise("BatchedMatch", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
         refuse_tree_reuse("BatchedMatch", tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits)
+        refuse_resign("BatchedMatch", resign_threshold=resign_threshold, resign_min_ply=resign_min_ply,
+                      resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
         if evaluator == "external":
             raise ValueError("BatchedMatch has no evaluator='external': an engine asks one model, eng.model, from the host")
         self.players, self.evaluator, self.binding = players, evaluator, BINDINGS[evaluator]
@@ -98,13 +101,16 @@ class BatchedMatch(TwoEngineMatch):
         super()._switch_to_exact_kernels()
 
 
-def evaluate_network(root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None, tree_reuse=None, tree_reuse_visits=None):
+def evaluate_network(root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None, tree_reuse=None, tree_reuse_visits=None, resign_threshold=None,
+                     resign_min_ply=None, resign_disable_fraction=None, resign_seed=None):
     """Network evaluation (evaluate_network.py:52-94): latest vs best, promote when the average point exceeds 0.5.  Two
     default 6/128/3 networks play on the engine's fused evaluator ('gnn'); when either file holds another shape, both play on
     its any-shape evaluator ('general').  Two CNNs (pv_network_cnn.py) play on the engine's CNN evaluator ('cnn'); a CNN against
     a GNN is refused (ValueError)."""
     refuse_root_noise("evaluate_network", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
     refuse_tree_reuse("evaluate_network", tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits)
+    refuse_resign("evaluate_network", resign_threshold=resign_threshold, resign_min_ply=resign_min_ply,
+                  resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
     model0 = load_network(PV_NETWORK_PATH + 'latest.pth')
     model1 = load_network(PV_NETWORK_PATH + 'best.pth')
     cnn = [isinstance(m, CNNNetwork) for m in (model0, model1)]

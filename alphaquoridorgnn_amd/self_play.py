@@ -15,7 +15,7 @@ import torch
 from . import distributed as aqd
 from . import pv_mcts
 from .constants import PV_NETWORK_PATH, BOARD_SIZE
-from .engine import BatchedSelfPlay, MultiSetSelfPlay, gather_history
+from .engine import BatchedSelfPlay, MultiSetSelfPlay, gather_history, gather_resign_arrays, resign_stats_of, suggest_from_arrays
 from .pv_network_gnn import GNNNetwork, POLICY_OUTPUT_SIZE, load_network
 from .pv_network_cnn import CNNNetwork
 from .replay import blend_targets, check_value_blend
@@ -34,6 +34,21 @@ SP_VALUE_BLEND = 0.0         # 0 = off: z alone, an int
 # child's subtree when that holds at most SP_TREE_REUSE_VISITS visits (None = the simulation count) and runs the same simulations on top.
 SP_TREE_REUSE = False        # off: a fresh tree every move, the reference's search
 SP_TREE_REUSE_VISITS = None
+# Resignation (the reference has none; engine.BatchedSelfPlay, include/aqgnn.h "resignation"): a mover whose search value and most visited
+# child's value are both below -SP_RESIGN_THRESHOLD at a ply >= SP_RESIGN_MIN_PLY gives the game up; a share SP_RESIGN_DISABLE_FRACTION of
+# the games never resigns, and from those the false positives are counted.  'auto': the first generation only collects (every game is
+# played out), and after each generation the next threshold is engine.suggest_resign_threshold at SP_RESIGN_MAX_FALSE_POSITIVE over the
+# newest SP_RESIGN_WINDOW generations' statistics (SP_RESIGN_AUTO holds them; no suggestion = the next generation collects again).
+SP_RESIGN_THRESHOLD = None   # None = off: every game is searched to its rule end; a float in (0, 1]; or 'auto'
+SP_RESIGN_MIN_PLY = 0
+SP_RESIGN_DISABLE_FRACTION = 0.1
+SP_RESIGN_MAX_FALSE_POSITIVE = 0.05
+SP_RESIGN_WINDOW = 8
+SP_RESIGN_AUTO = {"threshold": None, "parts": []}
+SP_RESIGN_LAST = None        # the last generation's dict(threshold, stats, arrays, next_threshold), gathered over the ranks
+# Slots (SP_SLOTS G, None = one slot per game: a finished slot idles until the longest game ends): the rank's games run on G slots with
+# the engine's refill, so that a slot freed by a short -- or a resigned -- game takes the next one.
+SP_SLOTS = None
 # Replay window (the reference has none; replay.ReplayWindow): every rank appends the gathered generation to SP_REPLAY, straight from
 # the engine's device tensors, for train_network.TRAIN_WINDOW to train on.  The .history file stays the reference's hand-over.
 SP_REPLAY = None             # None = off
@@ -91,6 +106,41 @@ def mirror_history(history):
     return out
 
 
+def _resign_options():
+    """(keyword arguments of the engine for this generation, the threshold they play at) -- ({}, None) when the option is off."""
+    if SP_RESIGN_THRESHOLD is None:
+        return {}, None
+    if SP_RESIGN_THRESHOLD == "auto":
+        chosen = SP_RESIGN_AUTO["threshold"]
+        # collecting: nothing resigns and every game counts as played out
+        thr, frac = (1.0, 1.0) if chosen is None else (chosen, SP_RESIGN_DISABLE_FRACTION)
+    else:
+        thr, frac = SP_RESIGN_THRESHOLD, SP_RESIGN_DISABLE_FRACTION
+    return dict(resign_threshold=thr, resign_min_ply=SP_RESIGN_MIN_PLY, resign_disable_fraction=frac), thr
+
+
+def _after_resign_generation(arrays, threshold, rank):
+    """The statistics of one generation, already gathered: remembered in SP_RESIGN_LAST, printed on rank 0, and with 'auto' turned
+    into the next generation's threshold.  Every rank holds the same arrays and therefore takes the same decision."""
+    global SP_RESIGN_LAST
+    stats = resign_stats_of([arrays], threshold)
+    nxt = None
+    if SP_RESIGN_THRESHOLD == "auto":
+        parts = SP_RESIGN_AUTO["parts"]
+        parts.append(arrays)
+        del parts[:-SP_RESIGN_WINDOW]
+        nxt = SP_RESIGN_AUTO["threshold"] = suggest_from_arrays(parts, SP_RESIGN_MAX_FALSE_POSITIVE)      # None: collect again
+    SP_RESIGN_LAST = dict(threshold=threshold, stats=stats, arrays=arrays, next_threshold=nxt)
+    if rank == 0:
+        games = max(stats["games"], 1)
+        print(f'resignation: threshold {threshold:.4f}, {stats["games_resigned"]}/{stats["games"]} games resigned, '
+              f'{stats["plies"] / games:.1f} plies per game; played out: {stats["disabled_games"]} games, {stats["would_resign"]} sides '
+              f'would have resigned, {stats["false_positives"]} of them did not lose (false-positive rate '
+              f'{stats["false_positive_rate"]:.3f})'
+              + ('' if SP_RESIGN_THRESHOLD != "auto" else
+                 f'; next threshold: {"none (the next generation only collects)" if nxt is None else format(nxt, ".4f")}'))
+
+
 def play(model, device=None, uniforms=None):
     """Execute one self-play game (self_play.py:40-68) -- a generation of one game on the engine.
     Returns [[state_array, policy list[POLICY_OUTPUT_SIZE], z], ...]."""
@@ -99,7 +149,8 @@ def play(model, device=None, uniforms=None):
                           temperature=SP_TEMPERATURE, seed=int(np.random.randint(0, 2 ** 31 - 1)),
                           evaluator=pv_mcts.evaluator_of(model), root_noise_eps=SP_ROOT_NOISE_EPS,
                           root_noise_alpha=SP_ROOT_NOISE_ALPHA, temperature_plies=SP_TEMPERATURE_PLIES,
-                          record_search_value=blend > 0.0, tree_reuse=SP_TREE_REUSE, tree_reuse_visits=SP_TREE_REUSE_VISITS)
+                          record_search_value=blend > 0.0, tree_reuse=SP_TREE_REUSE, tree_reuse_visits=SP_TREE_REUSE_VISITS,
+                          **_resign_options()[0])
     eng.play_generation(uniforms=uniforms, check_every=1)
     if blend > 0.0:
         return _history_rows(*eng.history_tensors(), BOARD_SIZE, eng.history_values(), blend)
@@ -145,18 +196,27 @@ def self_play(model=None, games=None, seed=None):
     z = torch.zeros((0,), dtype=torch.int8, device=dev)
     blend = check_value_blend(SP_VALUE_BLEND)
     q = torch.zeros((0,), dtype=torch.float32, device=dev) if blend > 0.0 else None       # the rows' search values, with a blend only
+    resign_kw, resign_thr = _resign_options()
+    resign_arrays = None
+    slots = mine
+    if SP_SLOTS is not None:
+        if isinstance(SP_SLOTS, bool) or int(SP_SLOTS) != SP_SLOTS or int(SP_SLOTS) < 1:
+            raise ValueError(f"SP_SLOTS must be an integer >= 1, not {SP_SLOTS!r}")
+        slots = min(int(SP_SLOTS), mine)
     if mine > 0:
         # >= 256 games: independent game sets on their own streams fill the holes of each other's serial kernel chains
-        eng = MultiSetSelfPlay(model, num_games=mine, sims=pv_mcts.PV_EVALUATE_COUNT, num_sets=None if mine >= 256 else 1,
+        eng = MultiSetSelfPlay(model, num_games=slots, quota=mine, sims=pv_mcts.PV_EVALUATE_COUNT, num_sets=None if slots >= 256 else 1,
                                board_size=BOARD_SIZE, temperature=SP_TEMPERATURE, seed=(base + rank) % (2 ** 31 - 1), device=dev,
                                evaluator=evaluator, root_noise_eps=SP_ROOT_NOISE_EPS, root_noise_alpha=SP_ROOT_NOISE_ALPHA,
                                temperature_plies=SP_TEMPERATURE_PLIES, record_search_value=blend > 0.0,
-                               tree_reuse=SP_TREE_REUSE, tree_reuse_visits=SP_TREE_REUSE_VISITS)
+                               tree_reuse=SP_TREE_REUSE, tree_reuse_visits=SP_TREE_REUSE_VISITS, **resign_kw)
         c = eng.play_generation()
         print(f'\rSelf-play (rank {rank}: {c["finished"]}/{mine} games)', end='')
         st, vis, z = eng.history_tensors()
         if q is not None:
             q = eng.history_values()
+        if resign_thr is not None:
+            resign_arrays = eng.resign_arrays()
     if distributed and os.environ.get("AQG_DIST_LOG") == "1" and rank == 0:
         print(f'exchange step: backend={dist.get_backend()} world={world} collectives={"forced" if aqd.force_group() else "as needed"}')
     host = distributed and dist.get_backend() != 'nccl'      # gloo (CPU tests): the exchange runs on host tensors
@@ -167,6 +227,8 @@ def self_play(model=None, games=None, seed=None):
     else:
         st, vis, z = gather_history(st, vis, z)
     print('')
+    if resign_thr is not None:
+        _after_resign_generation(gather_resign_arrays(resign_arrays, device="cpu" if host or not distributed else dev), resign_thr, rank)
     if SP_REPLAY is not None:                        # every rank: the gathered rows are identical on all of them
         if q is not None:
             SP_REPLAY.append_counts(st, vis, z, search_value=q, value_blend=blend)

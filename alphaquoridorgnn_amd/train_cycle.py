@@ -174,6 +174,19 @@ def _parser():
     ap.add_argument("--tree-reuse-visits", type=int, default=None,
                     help="self-play, with --tree-reuse: keep a subtree of at most this many visits (default SP_TREE_REUSE_VISITS: the "
                          "simulation count)")
+    ap.add_argument("--resign-threshold", default=None, metavar="T|auto",
+                    help="self-play: a mover whose search value and most visited child's value are both below -T resigns the game "
+                         "(T in (0, 1]); 'auto': the first generation plays every game out and only collects, and after each "
+                         "generation the next T is the one that resigns the most within --resign-max-false-positive (default "
+                         "SP_RESIGN_THRESHOLD = None: off)")
+    ap.add_argument("--resign-min-ply", type=int, default=None,
+                    help="self-play, with --resign-threshold: no resignation before this ply (default SP_RESIGN_MIN_PLY = 0)")
+    ap.add_argument("--resign-max-false-positive", type=float, default=None, metavar="F",
+                    help="self-play, with --resign-threshold auto: the share of the played-out games' sides that did not lose and "
+                         "may still have resigned (default SP_RESIGN_MAX_FALSE_POSITIVE = 0.05)")
+    ap.add_argument("--slots", type=int, default=None, metavar="G",
+                    help="self-play: play a rank's games on G slots that take the next game when theirs ends (default SP_SLOTS = "
+                         "None: one slot per game)")
     ap.add_argument("--value-blend", type=float, default=None,
                     help="self-play: weight L in [0, 1] of the root's search value in the value target, (1 - L) z + L q (default "
                          "SP_VALUE_BLEND = 0: the game outcome alone)")
@@ -238,6 +251,36 @@ def _set_tree_reuse_options(args):
         sp.SP_TREE_REUSE, sp.SP_TREE_REUSE_VISITS = True, args.tree_reuse_visits
 
 
+def _set_resign_options(args):
+    """--resign-threshold / --resign-min-ply / --resign-max-false-positive / --slots onto self_play's constants, refused here if the
+    engine would refuse them."""
+    from . import self_play as sp
+    from .engine import check_resign
+    if args.slots is not None:
+        if args.slots < 1:
+            raise ValueError("--slots must be >= 1")
+        sp.SP_SLOTS = args.slots
+    if args.resign_threshold is None:
+        if args.resign_min_ply is not None or args.resign_max_false_positive is not None:
+            raise ValueError("--resign-min-ply and --resign-max-false-positive need --resign-threshold")
+        return
+    auto = args.resign_threshold == "auto"
+    try:
+        threshold = 1.0 if auto else float(args.resign_threshold)
+    except ValueError:
+        raise ValueError(f"--resign-threshold must be a number in (0, 1] or 'auto', not {args.resign_threshold!r}") from None
+    min_ply = sp.SP_RESIGN_MIN_PLY if args.resign_min_ply is None else args.resign_min_ply
+    threshold, sp.SP_RESIGN_MIN_PLY, _ = check_resign(threshold, min_ply, sp.SP_RESIGN_DISABLE_FRACTION)
+    if args.resign_max_false_positive is not None:
+        if not auto:
+            raise ValueError("--resign-max-false-positive needs --resign-threshold auto")
+        if not 0.0 <= args.resign_max_false_positive < 1.0:
+            raise ValueError("--resign-max-false-positive must be in [0, 1)")
+        sp.SP_RESIGN_MAX_FALSE_POSITIVE = args.resign_max_false_positive
+    sp.SP_RESIGN_THRESHOLD = "auto" if auto else threshold
+    sp.SP_RESIGN_AUTO = {"threshold": None, "parts": []}
+
+
 def _set_mirror_options(args):
     """--mirror-augment / --mirror-seed onto train_network's constants (the stages read them at call time)."""
     from . import train_network as tn
@@ -269,6 +312,7 @@ def main(argv=None):
         tn.NUM_EPOCH = args.epochs
     _set_target_options(args)
     _set_tree_reuse_options(args)
+    _set_resign_options(args)
     _set_mirror_options(args)
     _set_replay_options(args)
     if args.eval_games is not None:

@@ -521,6 +521,50 @@ int aqg_engine_keep_subtrees(const aqg_engine* e_host, const aqg_tree_reuse* reu
 /* Clear the marker (the statistics are the caller's to clear): behind aqg_engine_reset, aqg_engine_set_roots and aqg_engine_apply_actions. */
 int aqg_engine_reset_reuse(const aqg_engine* e_host, const aqg_tree_reuse* reuse, void* stream);
 
+/* ------------------------------------------------------------------ resignation (additive to ABI 15; the reference plays every game out)
+ *
+ * Opt-in: a self-play game whose mover's search says it is lost ends there, and a fraction of the games is played out regardless so
+ * that the caller can count how often a resignation would have been wrong (AlphaGo Zero's calibration).  Like the two options above
+ * it travels as a small struct beside the engine struct and reaches engine_finish_move_kernel as kernel arguments: the engine
+ * struct, the step kernels, the captured per-move graph and its key do not change, and the entry points above behave as they did.
+ *
+ * The rule.  After the simulations of a searched move at root R with at least one child, by the mover at ply p = the position's
+ * plies_played (== the game's ply counter in self-play from the opening):
+ *     v_root = f32(w / n) of R, from the mover's side (the bits hist_value records; 0 when n == 0),
+ *     v_best = q of the child at the FIRST maximum of the visit counts = f32(-w_c / n_c), 0 when n_c == 0,
+ *     m      = max(v_root, v_best) in f32.
+ * The mover resigns iff   p >= min_ply   and   m < -threshold (an f32 comparison)   and   the game is resign-enabled.
+ * resign_min [quota, 2] f32: for every game and side (p & 1) the running minimum of m over that side's searched plies with
+ *   p >= min_ply, from +inf, kept whether or not the game is enabled -- the only statistic a calibration needs: a side "would have
+ *   resigned" at threshold T iff its minimum is < -T.  Written by lane 0 of the wavefront of the slot that plays the game: no atomics.
+ * Game k is resign-enabled iff counter_uniform(stream_key(seed, k), 0) >= disable_fraction (float64; the generator of the root
+ *   noise, keyed by the GAME index, never by the slot; engine.draw_resign_enabled is the same function in numpy).
+ * A resigned game: the ply's history row is written as for any searched move (state, visit row, search value), its hist_action is
+ *   0xFF, no transition is applied (root_state stays), game_plies[k] = p + 1, game_result[k] = the first player's value with the
+ *   mover as loser (-1 if p is even, else +1), game_done[k] = 1, game_resigned[k] = 1; the slot goes inactive and counters[0] / [1]
+ *   move as for a lost game.  Slot refill treats the slot like any finished one; with tree reuse its child_index is -1, so its next
+ *   game starts from a fresh tree.  A dead end (no child) and a move that ends the game by rule behave as without the option.
+ * z of the rows follows from game_result as always: the resigning row reads -1.
+ *
+ * Refused before any launch: threshold not in (0, 1], min_ply < 0, disable_fraction not in [0, 1], a NULL buffer, max_plies == 0.
+ * threshold == 1 can never trigger (m >= -1): the games are those of the option off, and resign_min is still kept. */
+typedef struct aqg_resign {
+    float threshold;                /* T in (0, 1]: resign when m < -T */
+    int32_t min_ply;                /* >= 0: no resignation and no statistic before this ply */
+    double disable_fraction;        /* in [0, 1]: the share of games that never resign (0 = none, 1 = all) */
+    uint64_t seed;                  /* of the enabled / disabled draw */
+    float* resign_min;              /* [quota, 2] running minimum of m per game and side; +inf = no eligible ply yet */
+    uint8_t* game_resigned;         /* [quota] 1 = the game ended by resignation */
+} aqg_resign;
+/* aqg_engine_move_reuse / aqg_engine_finish_move_reuse with the option; reuse == NULL = tree reuse off (then prior_mode 2 is served
+ * by the finish-move form as by aqg_engine_finish_move_targets). */
+int aqg_engine_move_resign(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                           const aqg_tree_reuse* reuse, const aqg_resign* resign, void* stream);
+int aqg_engine_finish_move_resign(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                                  const aqg_tree_reuse* reuse, const aqg_resign* resign, void* stream);
+/* resign_min = +inf, game_resigned = 0: behind aqg_engine_reset. */
+int aqg_engine_reset_resign(const aqg_engine* e_host, const aqg_resign* resign, void* stream);
+
 /* ------------------------------------------------------------------ baseline agents in batch (agents.py; additive to ABI 14)
  *
  * The reference's random and rollout-MCTS agents (agents.py:14-18, :111-214) for B states at once, one wavefront per state
