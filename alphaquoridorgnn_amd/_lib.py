@@ -117,6 +117,13 @@ class CnnTrainStruct(_c.Structure):
     )
 
 
+class OptimStruct(_c.Structure):
+    """Mirror of `struct aqg_optim` (include/aqgnn.h, "optimiser controls"): the option beside a trainer struct.  weight_decay is a
+    HOST array of num_tensors floats."""
+    _fields_ = [("decoupled", _i32), ("num_tensors", _i32), ("weight_decay", _c.POINTER(_f32)), ("max_grad_norm", _f32),
+                ("grad_norm", _vp), ("workspace", _vp), ("workspace_floats", _c.c_size_t)]
+
+
 SIGNATURES = {
     "aqg_abi_version": (_c.c_int, []),
     "aqg_last_error": (_c.c_char_p, []),
@@ -193,6 +200,18 @@ SIGNATURES = {
     "aqg_cnn_train_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "aqg_cnn_train_step": (_c.c_int, [_c.POINTER(CnnTrainStruct), _vp, _vp, _vp, _c.c_int, _vp]),
     "aqg_cnn_train_steps": (_c.c_int, [_c.POINTER(CnnTrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _vp]),
+    "aqg_optim_workspace_floats": (_c.c_size_t, [_c.c_size_t]),
+    "aqg_grad_norm": (_c.c_int, [_vp, _c.c_size_t, _vp, _vp, _c.c_size_t, _vp]),
+    "aqg_gcn_train_step_optim": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _c.c_int, _c.POINTER(OptimStruct), _vp]),
+    "aqg_gcn_train_steps_optim": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _c.POINTER(OptimStruct),
+                                             _vp]),
+    "aqg_gcn_train_step_general_optim": (_c.c_int, [_c.POINTER(TrainGeneralStruct), _vp, _vp, _vp, _c.c_int, _c.POINTER(OptimStruct),
+                                                    _vp]),
+    "aqg_gcn_train_steps_general_optim": (_c.c_int, [_c.POINTER(TrainGeneralStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp,
+                                                     _c.POINTER(OptimStruct), _vp]),
+    "aqg_cnn_train_step_optim": (_c.c_int, [_c.POINTER(CnnTrainStruct), _vp, _vp, _vp, _c.c_int, _c.POINTER(OptimStruct), _vp]),
+    "aqg_cnn_train_steps_optim": (_c.c_int, [_c.POINTER(CnnTrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _c.POINTER(OptimStruct),
+                                             _vp]),
     "aqg_augment_gather": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_int, _vp, _vp, _vp,
                                       _vp]),
     "aqg_replay_append": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),

@@ -2,6 +2,7 @@
 #include "aqg_common.hpp"
 #include "../../include/aqgnn.h"
 #include "launchers.hpp"
+#include "train_adam.hpp"
 
 namespace aqg {
 thread_local char g_err[512] = "";
@@ -356,6 +357,24 @@ int aqg_gcn_train_step(const aqg_train* t, const uint8_t* states72, const float*
     if (mode >= 1 && t->step < 1) return fail("aqg_gcn_train_step: step must be >= 1");
     return train_step(*t, states72, pi_target, z_target, mode, (hipStream_t)stream);
 }
+// The _optim entry points (include/aqgnn.h "optimiser controls"): the plain call's own checks first (it refuses what it always
+// refused, under its own name), then the controls'; with nothing on, the plain call itself.
+int aqg_gcn_train_step_optim(const aqg_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                             const aqg_optim* optim, void* stream) {
+    if (!optim) return aqg_gcn_train_step(t, states72, pi_target, z_target, mode, stream);
+    const char* what = "aqg_gcn_train_step_optim";
+    if (!t || mode < 0 || mode > 2) return fail(what, "bad argument");
+    if (mode != 2 && (!states72 || !pi_target || !z_target)) return fail(what, "null argument");
+    for (int i = 0; i < 14; ++i)
+        if (!t->params[i] || !t->grads[i] || (mode >= 1 && (!t->adam_m[i] || !t->adam_v[i]))) return fail(what, "null parameter tensor");
+    if (mode >= 1 && t->step < 1) return fail(what, "step must be >= 1");
+    size_t numel[14];
+    train_tensor_sizes(*t, numel);
+    OptimPlan plan;
+    bool on;
+    if (int r = check_optim(optim, 14, numel, t->grads, what, &plan, &on)) return r;
+    return train_step(*t, states72, pi_target, z_target, mode, (hipStream_t)stream, on ? &plan : nullptr);
+}
 long long aqg_gcn_train_fallbacks(int reset) { return train_fallbacks(reset); }
 int aqg_gcn_train_steps(const aqg_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, const int64_t* order,
                         long long positions, float* loss_sums, void* stream) {
@@ -364,6 +383,21 @@ int aqg_gcn_train_steps(const aqg_train* t, const uint8_t* states72, const float
         if (!t->params[i] || !t->grads[i] || !t->adam_m[i] || !t->adam_v[i]) return fail("aqg_gcn_train_steps: null parameter tensor");
     if (t->step < 1) return fail("aqg_gcn_train_steps: step must be >= 1");
     return train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream);
+}
+int aqg_gcn_train_steps_optim(const aqg_train* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                              const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim, void* stream) {
+    if (!optim) return aqg_gcn_train_steps(t, states72, pi_target, z_target, order, positions, loss_sums, stream);
+    const char* what = "aqg_gcn_train_steps_optim";
+    if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
+    for (int i = 0; i < 14; ++i)
+        if (!t->params[i] || !t->grads[i] || !t->adam_m[i] || !t->adam_v[i]) return fail(what, "null parameter tensor");
+    if (t->step < 1) return fail(what, "step must be >= 1");
+    size_t numel[14];
+    train_tensor_sizes(*t, numel);
+    OptimPlan plan;
+    bool on;
+    if (int r = check_optim(optim, 14, numel, t->grads, what, &plan, &on)) return r;
+    return train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream, on ? &plan : nullptr);
 }
 
 static int check_train_general(const aqg_train_general* t, bool adam, const char* what) {
@@ -385,12 +419,43 @@ int aqg_gcn_train_step_general(const aqg_train_general* t, const uint8_t* states
     if (int r = check_train_general(t, mode >= 1, what)) return r;
     return train_step_general(*t, states72, pi_target, z_target, mode, (hipStream_t)stream);
 }
+int aqg_gcn_train_step_general_optim(const aqg_train_general* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                                     int mode, const aqg_optim* optim, void* stream) {
+    if (!optim) return aqg_gcn_train_step_general(t, states72, pi_target, z_target, mode, stream);
+    const char* what = "aqg_gcn_train_step_general_optim";
+    if (!t || mode < 0 || mode > 2) return fail(what, "bad argument");
+    if (t->batch < 0) return fail(what, "negative batch");
+    if (mode != 2 && t->batch > 0 && (!states72 || !pi_target || !z_target)) return fail(what, "null argument");
+    if (int r = check_train_general(t, mode >= 1, what)) return r;
+    if (t->hidden < 2 || t->hidden > 1024 || t->policy_size < 1 || t->policy_size > 4096) return fail(what, "shape outside the kernels' limits");
+    size_t numel[2 * AQG_GENERAL_MAX_LAYERS + 8];
+    train_general_tensor_sizes(*t, numel);
+    OptimPlan plan;
+    bool on;
+    if (int r = check_optim(optim, 2 * t->num_layers + 8, numel, t->grads, what, &plan, &on)) return r;
+    return train_step_general(*t, states72, pi_target, z_target, mode, (hipStream_t)stream, on ? &plan : nullptr);
+}
 int aqg_gcn_train_steps_general(const aqg_train_general* t, const uint8_t* states72, const float* pi_target, const float* z_target,
                                 const int64_t* order, long long positions, float* loss_sums, void* stream) {
     const char* what = "aqg_gcn_train_steps_general";
     if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
     if (int r = check_train_general(t, true, what)) return r;
     return train_steps_general(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream);
+}
+int aqg_gcn_train_steps_general_optim(const aqg_train_general* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                                      const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim,
+                                      void* stream) {
+    if (!optim) return aqg_gcn_train_steps_general(t, states72, pi_target, z_target, order, positions, loss_sums, stream);
+    const char* what = "aqg_gcn_train_steps_general_optim";
+    if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
+    if (int r = check_train_general(t, true, what)) return r;
+    if (t->hidden < 2 || t->hidden > 1024 || t->policy_size < 1 || t->policy_size > 4096) return fail(what, "shape outside the kernels' limits");
+    size_t numel[2 * AQG_GENERAL_MAX_LAYERS + 8];
+    train_general_tensor_sizes(*t, numel);
+    OptimPlan plan;
+    bool on;
+    if (int r = check_optim(optim, 2 * t->num_layers + 8, numel, t->grads, what, &plan, &on)) return r;
+    return train_steps_general(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream, on ? &plan : nullptr);
 }
 
 size_t aqg_cnn_train_workspace_floats(int board_size, int num_filters, int num_blocks, int policy_size, int max_batch) {
@@ -405,12 +470,45 @@ int aqg_cnn_train_step(const aqg_cnn_train* t, const uint8_t* states72, const fl
     if (int r = check_cnn_train(*t, mode >= 1, what)) return r;
     return cnn_train_step(*t, states72, pi_target, z_target, mode, (hipStream_t)stream);
 }
+int aqg_cnn_train_step_optim(const aqg_cnn_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                             const aqg_optim* optim, void* stream) {
+    if (!optim) return aqg_cnn_train_step(t, states72, pi_target, z_target, mode, stream);
+    const char* what = "aqg_cnn_train_step_optim";
+    if (!t || mode < 0 || mode > 2) return fail(what, "bad argument");
+    if (t->batch < 0) return fail(what, "negative batch");
+    if (mode != 2 && t->batch > 0 && (!states72 || !pi_target || !z_target)) return fail(what, "null argument");
+    if (int r = check_cnn_train(*t, mode >= 1, what)) return r;
+    size_t numel[AQG_CNN_TRAIN_TENSORS];
+    cnn_train_tensor_sizes(*t, numel);
+    OptimPlan plan;
+    bool on;
+    if (int r = check_optim(optim, 3 * (2 * t->num_blocks + 1) + 4, numel, t->grads, what, &plan, &on)) return r;
+    return cnn_train_step(*t, states72, pi_target, z_target, mode, (hipStream_t)stream, on ? &plan : nullptr);
+}
 int aqg_cnn_train_steps(const aqg_cnn_train* t, const uint8_t* states72, const float* pi_target, const float* z_target,
                         const int64_t* order, long long positions, float* loss_sums, void* stream) {
     const char* what = "aqg_cnn_train_steps";
     if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
     if (int r = check_cnn_train(*t, true, what)) return r;
     return cnn_train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream);
+}
+int aqg_cnn_train_steps_optim(const aqg_cnn_train* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                              const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim, void* stream) {
+    if (!optim) return aqg_cnn_train_steps(t, states72, pi_target, z_target, order, positions, loss_sums, stream);
+    const char* what = "aqg_cnn_train_steps_optim";
+    if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
+    if (int r = check_cnn_train(*t, true, what)) return r;
+    size_t numel[AQG_CNN_TRAIN_TENSORS];
+    cnn_train_tensor_sizes(*t, numel);
+    OptimPlan plan;
+    bool on;
+    if (int r = check_optim(optim, 3 * (2 * t->num_blocks + 1) + 4, numel, t->grads, what, &plan, &on)) return r;
+    return cnn_train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream, on ? &plan : nullptr);
+}
+
+size_t aqg_optim_workspace_floats(size_t n) { return optim_workspace_floats(n); }
+int aqg_grad_norm(const float* x, size_t n, float* out, float* workspace, size_t workspace_floats, void* stream) {
+    return launch_grad_norm(x, n, out, workspace, workspace_floats, (hipStream_t)stream);
 }
 
 int aqg_augment_gather(int board_size, int policy_size, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,

@@ -200,25 +200,42 @@ struct CnnAdamArgs {
     int B; LossMeans means;
 };
 
-__global__ __launch_bounds__(256) void cnn_adam_kernel(CnnAdamArgs a) {
+// Two instantiations: <>, the launch as it has always been (the same instructions and registers as before the template), and
+// <CnnOptim>, with the optimiser controls of train_adam.hpp as a second argument: every Adam workgroup first adds up the norm's
+// partials and derives the clip coefficient -- AFTER the table's pointers are read: hipcc treats a pointer loaded from the table as
+// a global one only while nothing that may write memory (the prologue's LDS store and barrier) lies in front of the load.
+using CnnOptim = OptimArgs<AQG_CNN_TRAIN_TENSORS>;
+template <class... Optim>
+__global__ __launch_bounds__(256) void cnn_adam_kernel(CnnAdamArgs a, Optim... op) {
+    constexpr bool OPT = sizeof...(Optim) == 1;
     if (blockIdx.x == a.adam_blocks) {
         const LossMeans means = a.means;
         loss_means(means, a.B);
         return;
     }
     const size_t e0 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e0 >= a.total) return;
+    const bool live = e0 < a.total;
+    if (!OPT && !live) return;                  // (OPT: every thread stays for the prologue's barrier, reading element 0)
     size_t e;
-    const int i = cnn_tensor_of(a.s, e0, &e);
+    const int i = cnn_tensor_of(a.s, live ? e0 : 0, &e);
     float* p = a.table[i];
     const float* g = a.table[a.T + i];
     float* m = a.table[2 * a.T + i];
     float* v = a.table[3 * a.T + i];
-    const float gr = g[e], om = m[e], ov = v[e], op = p[e];
+    float gr = g[e], opar = p[e];
+    const float om = m[e], ov = v[e];
     const AdamStep ad = a.adam;                 // (copies, not references into `a`: train_adam.hpp says why)
+    if constexpr (OPT) {
+        __shared__ float norm_red[4];
+        const OptimStep os = (op.s, ...);
+        const float coef = optim_prologue(os, norm_red);
+        if (!live) return;
+        const GradParam gp = optim_apply(coef, (op.wd[i], ...), os.decoupled, ad.lr, gr, opar);
+        gr = gp.g; opar = gp.p;
+    }
     const AdamMoments n = adam_moments(ad, gr, om, ov);
     m[e] = n.m; v[e] = n.v;
-    p[e] = adam_param(ad, op, n);
+    p[e] = adam_param(ad, opar, n);
 }
 
 struct CnnTrainWorkspace {
@@ -355,7 +372,7 @@ int forward_backward(const aqg_cnn_train& t, const uint8_t* states72, const floa
 }
 
 int launch_finish(const aqg_cnn_train& t, int B, bool update, int step, const float* loss, float* loss_mean, float* loss_sums,
-                  hipStream_t st) {
+                  hipStream_t st, const OptimLaunch* ol = nullptr) {
     CnnAdamArgs a{};
     a.s = CnnShape{t.num_filters, t.num_blocks, t.policy_size};
     a.T = 3 * (2 * t.num_blocks + 1) + 4;
@@ -366,7 +383,13 @@ int launch_finish(const aqg_cnn_train& t, int B, bool update, int step, const fl
     a.adam_blocks = update ? blocks_of((long long)a.total, 256) : 0u;
     const unsigned grid = a.adam_blocks + (loss && B > 0 ? 1u : 0u);
     if (grid == 0) return 0;
-    hipLaunchKernelGGL(cnn_adam_kernel, dim3(grid), dim3(256), 0, st, a);
+    if (ol && update) {
+        CnnOptim op{};
+        fill_optim(*ol, a.T, &op.s, op.wd);
+        hipLaunchKernelGGL(cnn_adam_kernel<CnnOptim>, dim3(grid), dim3(256), 0, st, a, op);
+        return check_launch("cnn_adam_kernel<CnnOptim>");
+    }
+    hipLaunchKernelGGL(cnn_adam_kernel<>, dim3(grid), dim3(256), 0, st, a);
     return check_launch("cnn_adam_kernel");
 }
 
@@ -376,6 +399,14 @@ bool shape_ok(int N, int F, int L, int A) {
 }
 
 }  // namespace
+
+// elements of each of the 3 C + 4 tensors, in parameter order (what cnn_tensor_of walks on the device)
+void cnn_train_tensor_sizes(const aqg_cnn_train& t, size_t* numel) {
+    const size_t F = t.num_filters, A = t.policy_size;
+    const int C = 2 * t.num_blocks + 1;
+    for (int l = 0; l < C; ++l) { numel[3 * l] = (l == 0 ? 54 : 9 * F) * F; numel[3 * l + 1] = F; numel[3 * l + 2] = F; }
+    numel[3 * C] = A * F; numel[3 * C + 1] = A; numel[3 * C + 2] = F; numel[3 * C + 3] = 1;
+}
 
 size_t cnn_train_workspace_floats(int N, int F, int L, int A, int max_batch) {
     if (!shape_ok(N, F, L, A) || max_batch < 1) return 0;
@@ -404,8 +435,11 @@ int check_cnn_train(const aqg_cnn_train& t, bool adam, const char* what) {
 }
 
 // mode 0 = gradients only, 1 = gradients + Adam, 2 = Adam only
-int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st) {
+int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
+                   const OptimPlan* plan) {
     const char* what = "aqg_cnn_train_step";
+    OptimLaunch ol;
+    const OptimLaunch* olp = plan && mode >= 1 ? &ol : nullptr;
     const int B = t.batch;
     if (mode != 2 && B > 0) {
         const size_t need = cnn_train_layout(t.board_size, t.num_filters, t.num_blocks, t.policy_size, B, nullptr, nullptr);
@@ -416,14 +450,19 @@ int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float*
         float* value = t.value ? t.value : ws.value;
         float* loss = t.loss ? t.loss : ws.loss;
         if (int r = forward_backward(t, states72, pi, z, nullptr, 0, B, ws, policy, value, loss, st)) return r;
-        return launch_finish(t, B, mode == 1, t.step, loss, t.loss_mean ? t.loss_mean : ws.loss_mean, nullptr, st);
+        if (olp) if (int r = optim_before_finish(*plan, 0, &ol, st)) return r;
+        if (int r = launch_finish(t, B, mode == 1, t.step, loss, t.loss_mean ? t.loss_mean : ws.loss_mean, nullptr, st, olp)) return r;
+        return plan && mode == 0 ? optim_norm_only(*plan, st) : 0;
     }
-    if (mode == 2) return launch_finish(t, B, true, t.step, nullptr, nullptr, nullptr, st);
-    return 0;
+    if (mode == 2) {
+        if (olp) if (int r = optim_before_finish(*plan, 0, &ol, st)) return r;
+        return launch_finish(t, B, true, t.step, nullptr, nullptr, nullptr, st, olp);
+    }
+    return plan && mode == 0 ? optim_norm_only(*plan, st) : 0;
 }
 
 int cnn_train_steps(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
-                    long long positions, float* loss_sums, hipStream_t st) {
+                    long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan) {
     const char* what = "aqg_cnn_train_steps";
     if (t.batch < 1) return fail(what, "batch must be >= 1");
     const size_t need = cnn_train_layout(t.board_size, t.num_filters, t.num_blocks, t.policy_size, t.batch, nullptr, nullptr);
@@ -437,7 +476,10 @@ int cnn_train_steps(const aqg_cnn_train& t, const uint8_t* states72, const float
         float* value = t.value ? t.value : ws.value;
         float* loss = t.loss ? t.loss : ws.loss;
         if (int r = forward_backward(t, states72, pi, z, order, (int)first, B, ws, policy, value, loss, st)) return r;
-        if (int r = launch_finish(t, B, true, step, loss, t.loss_mean ? t.loss_mean : ws.loss_mean, loss_sums, st)) return r;
+        OptimLaunch ol;
+        if (plan) if (int r = optim_before_finish(*plan, step - t.step, &ol, st)) return r;
+        if (int r = launch_finish(t, B, true, step, loss, t.loss_mean ? t.loss_mean : ws.loss_mean, loss_sums, st, plan ? &ol : nullptr))
+            return r;
     }
     return 0;
 }

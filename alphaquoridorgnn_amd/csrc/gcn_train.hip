@@ -7,7 +7,8 @@
 //   loss      Lp = mean_b -sum_a t_a log_softmax(pol)_a   (the reference's double softmax, kept on purpose)
 //             Lv = mean_b (val - z)^2
 //   backward  dP = dH' (.) [H' > 0];  db = colsum dP;  dZ = A_hat dP (A_hat symmetric);  dW = dZ^T H;  dH = dZ W
-//   update    torch.optim.Adam (lr, betas, eps; bias-corrected; no weight decay, no amsgrad)
+//   update    torch.optim.Adam (lr, betas, eps; bias-corrected; no amsgrad); weight decay and global-norm clipping are options of
+//             the _optim entry points (train_adam.hpp, final_optim below), off in every other call
 //
 // The batch is 128 positions (train_network.py:15) = 10,368 graph nodes and 2.2 GFLOP per step.  Two launches per step:
 //
@@ -33,11 +34,13 @@
 //   gcn_train_exact.hip    train_board_kernel<N> and its launcher
 //   gcn_train_split.hip    train_board_split_kernel, heads_board_call, the fallback counter, its launcher
 //   gcn_train_final.hip    train_final_kernel and its launcher
-//   train_adam.hpp         the Adam element update and its step scalars, shared with gcn_train_general.hip and cnn_train.hip
+//   train_adam.hpp         the Adam element update and its step scalars, shared with gcn_train_general.hip and cnn_train.hip;
+//                          the optimiser controls (weight decay, global-norm clipping) in front of it
 //   gcn_train.hip          this map; the option, the choice between the two board launchers, train_step, train_steps
 #include "aqg_common.hpp"
 #include "../../include/aqgnn.h"
 #include "launchers.hpp"
+#include "train_adam.hpp"
 
 namespace aqg {
 
@@ -59,16 +62,38 @@ static int validate(const aqg_train& t) {
     return 0;
 }
 
+// The final launch(es) of a step with the optimiser controls.  train_final_kernel forms a gradient element and updates it in the same
+// thread, so a step that needs the norm of ALL elements first runs it with `compute` alone, then stage 1 of the norm, then the clip
+// of the stored gradients in place (train_adam.hpp says why not inside the update), then the update alone (the mode-2 form): the
+// plain kernel, or with decay its second instantiation.  Decay without a norm stays the one launch.
+static int final_optim(const aqg_train& t, int B, bool compute, int step, int step_index, float* loss_sums, const OptimPlan& plan,
+                       hipStream_t st) {
+    OptimLaunch ol;
+    if (!plan.norm()) {
+        if (int r = optim_before_finish(plan, step_index, &ol, st)) return r;
+        return launch_train_final(t, B, compute, true, step, loss_sums, st, &ol);
+    }
+    if (compute)
+        if (int r = launch_train_final(t, B, true, false, step, loss_sums, st)) return r;
+    if (int r = optim_before_finish(plan, step_index, &ol, st)) return r;
+    if (int r = launch_clip_scale(plan, ol, st)) return r;
+    ol.s.partials = nullptr; ol.s.P = 0; ol.s.norm_out = nullptr;        // clipped already
+    return launch_train_final(t, B, false, true, step, nullptr, st, plan.wd ? &ol : nullptr);
+}
+
 // mode 0 = gradients only, 1 = gradients + Adam, 2 = Adam only (data-parallel: local gradients, all-reduce, update)
-int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st) {
+int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
+               const OptimPlan* plan) {
     if (int r = validate(t)) return r;
     const int B = t.batch;
     if (mode != 2 && B > 0) {
         if (int r = forward_backward(t, states72, pi, z, nullptr, 0, B, st)) return r;
-        return launch_train_final(t, B, true, mode == 1, t.step, nullptr, st);
+        if (plan && mode == 1) return final_optim(t, B, true, t.step, 0, nullptr, *plan, st);
+        if (int r = launch_train_final(t, B, true, mode == 1, t.step, nullptr, st)) return r;
+        return plan ? optim_norm_only(*plan, st) : 0;
     }
-    if (mode >= 1) return launch_train_final(t, B, false, true, t.step, nullptr, st);
-    return 0;
+    if (mode >= 1) return plan ? final_optim(t, B, false, t.step, 0, nullptr, *plan, st) : launch_train_final(t, B, false, true, t.step, nullptr, st);
+    return plan ? optim_norm_only(*plan, st) : 0;
 }
 
 // A run of consecutive single-process steps over a shuffled data set, no host work in between: step i takes the positions
@@ -76,13 +101,14 @@ int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, con
 // resident arrays, t.step counts up from its entry value, and each step's loss terms are added to loss_sums[2]
 // (policy, value: the per-step batch means, what train_network.py:89-90 accumulates per epoch).
 int train_steps(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, long long positions,
-                float* loss_sums, hipStream_t st) {
+                float* loss_sums, hipStream_t st, const OptimPlan* plan) {
     if (int r = validate(t)) return r;
     if (t.batch < 1) return fail("aqg_gcn_train_steps: batch must be >= 1");
     int step = t.step;
     for (long long first = 0; first < positions; first += t.batch, ++step) {
         const int B = (int)(positions - first < t.batch ? positions - first : t.batch);
         if (int r = forward_backward(t, states72, pi, z, order, (int)first, B, st)) return r;
+        if (plan) { if (int r = final_optim(t, B, true, step, step - t.step, loss_sums, *plan, st)) return r; continue; }
         if (int r = launch_train_final(t, B, true, true, step, loss_sums, st)) return r;
     }
     return 0;

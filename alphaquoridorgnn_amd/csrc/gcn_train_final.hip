@@ -3,6 +3,7 @@
 #define AQG_TRAIN_TU final
 #include "gcn_train_common.hpp"
 #include "train_adam.hpp"
+#include <type_traits>
 
 namespace aqg {
 
@@ -30,6 +31,17 @@ __device__ __forceinline__ void adam_update(const FinalJobs& jb, int i, unsigned
     jb.m[i][e] = n.m; jb.v[i][e] = n.v;
     jb.p[i][e] = adam_param(jb.adam, o.p, n);
 }
+// the same with the optimiser controls in front (train_adam.hpp): the argument block of the kernel's second instantiation
+struct FinalOptimJobs : FinalJobs { OptimArgs<14> op; };
+template <class Jobs>
+__device__ __forceinline__ void adam_update(const Jobs& jb, float coef, int i, unsigned int e, float gr, const AdamOld& o) {
+    if constexpr (std::is_same_v<Jobs, FinalOptimJobs>) {
+        const GradParam gp = optim_apply(coef, jb.op.wd[i], jb.op.s.decoupled, jb.adam.lr, gr, o.p);
+        adam_update(jb, i, e, gp.g, AdamOld{o.m, o.v, gp.p});
+    } else {
+        adam_update(jb, i, e, gr, o);
+    }
+}
 // A team = 32 lanes x FINAL_GROUPS board groups: a thread sums its group's boards in order, the group sums are added pairwise in
 // group order -- a fixed summation order with FINAL_GROUPS x the loads in flight of one thread per element.  The first
 // FINAL_BIG_BLOCKS teams ("rows") take the two [128,128] trunk weights four elements per lane (16-byte loads of the 16 MB of
@@ -39,8 +51,17 @@ constexpr int FINAL_BIG_BLOCKS = 2 * TH * TH / 128;
 constexpr int FINAL_GROUPS = 4;     // board groups per element: a thread sums B / groups boards (4 / 8 / 16 groups: 0.0467 / 0.0473 / 0.0527 ms per step)
 constexpr int FINAL_TEAM_THREADS = 32 * FINAL_GROUPS;
 constexpr int FINAL_TEAMS = 1024 / FINAL_TEAM_THREADS;
-__global__ __launch_bounds__(FINAL_TEAM_THREADS * FINAL_TEAMS) void train_final_kernel(FinalJobs jb) {
+// Two instantiations: <FinalJobs>, the step as it has always been (the same instructions and registers as before the template), and
+// <FinalOptimJobs>: every workgroup first adds up the norm's partials and derives the clip coefficient, and every update goes through
+// optim_apply.
+template <class Jobs>
+__global__ __launch_bounds__(FINAL_TEAM_THREADS * FINAL_TEAMS) void train_final_kernel(Jobs jb) {
     __shared__ f32x4 red4s[FINAL_TEAMS][FINAL_GROUPS][33];
+    float coef = 1.f;
+    if constexpr (std::is_same_v<Jobs, FinalOptimJobs>) {
+        __shared__ float norm_red[4];
+        coef = optim_prologue(jb.op.s, norm_red);
+    }
     TS_DECL
     const int team = threadIdx.x / FINAL_TEAM_THREADS, tt = threadIdx.x % FINAL_TEAM_THREADS;
     const unsigned int row = blockIdx.x * FINAL_TEAMS + team;
@@ -75,7 +96,7 @@ __global__ __launch_bounds__(FINAL_TEAM_THREADS * FINAL_TEAMS) void train_final_
         }
         if (jb.update) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) adam_update(jb, i, e + k, gr4[k], old[k]);
+            for (int k = 0; k < 4; ++k) adam_update(jb, coef, i, e + k, gr4[k], old[k]);
         }
         return;
     }
@@ -140,15 +161,23 @@ __global__ __launch_bounds__(FINAL_TEAM_THREADS * FINAL_TEAMS) void train_final_
         if (i == 14) return;
         gr = jb.g[i][e];
     }
-    if (jb.update) adam_update(jb, i, e, gr, old);
+    if (jb.update) adam_update(jb, coef, i, e, gr, old);
 }
 
 AQG_TRAIN_STAMP_READER(train_stamps_final)
 
-int launch_train_final(const aqg_train& t, int B, bool compute, bool update, int step, float* loss_sums, hipStream_t st) {
+void train_tensor_sizes(const aqg_train& t, size_t* numel) {
     const int A = t.policy_size;
     const size_t sizes[14] = {(size_t)TH * TF, TH, (size_t)TH * TH, TH, (size_t)TH * TH, TH, (size_t)HH * TH, (size_t)HH, (size_t)A * HH, (size_t)A,
                               (size_t)HH * TH, (size_t)HH, (size_t)HH, 1};
+    for (int i = 0; i < 14; ++i) numel[i] = sizes[i];
+}
+
+int launch_train_final(const aqg_train& t, int B, bool compute, bool update, int step, float* loss_sums, hipStream_t st,
+                       const OptimLaunch* ol) {
+    const int A = t.policy_size;
+    size_t sizes[14];
+    train_tensor_sizes(t, sizes);
     FinalJobs jb{};
     unsigned int run = 0;
     for (int i = 0; i < 14; ++i) {
@@ -167,7 +196,15 @@ int launch_train_final(const aqg_train& t, int B, bool compute, bool update, int
     jb.B = B; jb.A = A; jb.compute = compute; jb.update = update;
     jb.adam = adam_step(t.lr, t.beta1, t.beta2, t.eps, step);
     const unsigned int rows = FINAL_BIG_BLOCKS + (run + 2 + 31) / 32;
-    hipLaunchKernelGGL(train_final_kernel, dim3((rows + FINAL_TEAMS - 1) / FINAL_TEAMS), dim3(FINAL_TEAM_THREADS * FINAL_TEAMS), 0, st, jb);
+    const dim3 grid((rows + FINAL_TEAMS - 1) / FINAL_TEAMS), blk(FINAL_TEAM_THREADS * FINAL_TEAMS);
+    if (ol) {
+        FinalOptimJobs jo{};
+        static_cast<FinalJobs&>(jo) = jb;
+        fill_optim(*ol, 14, &jo.op.s, jo.op.wd);
+        hipLaunchKernelGGL(train_final_kernel<FinalOptimJobs>, grid, blk, 0, st, jo);
+        return check_launch("train_final_kernel<FinalOptimJobs>");
+    }
+    hipLaunchKernelGGL(train_final_kernel<FinalJobs>, grid, blk, 0, st, jb);
     return check_launch("train_final_kernel");
 }
 

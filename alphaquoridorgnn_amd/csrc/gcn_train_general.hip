@@ -18,6 +18,7 @@
 #include "../../include/aqgnn.h"
 #include "launchers.hpp"
 #include "train_adam.hpp"
+#include <type_traits>
 
 namespace aqg {
 
@@ -180,10 +181,21 @@ struct AdamJobs {
     LossMeans means;
 };
 
-__global__ __launch_bounds__(256) void train_general_finish_kernel(AdamJobs jb, unsigned int adam_blocks) {
+// Two instantiations: <AdamJobs>, the launch as it has always been (the same instructions and registers as before the template), and
+// <AdamOptimJobs>, with the optimiser controls of train_adam.hpp: every Adam workgroup first adds up the norm's partials and derives
+// the clip coefficient.
+struct AdamOptimJobs : AdamJobs { OptimArgs<MAXT> op; };
+template <class Jobs>
+__global__ __launch_bounds__(256) void train_general_finish_kernel(Jobs jb, unsigned int adam_blocks) {
+    constexpr bool OPT = std::is_same_v<Jobs, AdamOptimJobs>;
     if (blockIdx.x == adam_blocks) {
         loss_means(jb.means, jb.B);
         return;
+    }
+    float coef = 1.f;
+    if constexpr (OPT) {
+        __shared__ float norm_red[4];
+        coef = optim_prologue(jb.op.s, norm_red);
     }
     const unsigned int e0 = blockIdx.x * 256 + threadIdx.x;
     if (e0 >= jb.end[jb.tensors - 1]) return;
@@ -191,10 +203,15 @@ __global__ __launch_bounds__(256) void train_general_finish_kernel(AdamJobs jb, 
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (e0 < jb.end[mid]) hi = mid; else lo = mid + 1; }
     const int i = lo;
     const unsigned int e = e0 - (i ? jb.end[i - 1] : 0u);
-    const float gr = jb.g[i][e], om = jb.m[i][e], ov = jb.v[i][e], op = jb.p[i][e];
+    float gr = jb.g[i][e], opar = jb.p[i][e];
+    const float om = jb.m[i][e], ov = jb.v[i][e];
+    if constexpr (OPT) {
+        const GradParam gp = optim_apply(coef, jb.op.wd[i], jb.op.s.decoupled, jb.adam.lr, gr, opar);
+        gr = gp.g; opar = gp.p;
+    }
     const AdamMoments n = adam_moments(jb.adam, gr, om, ov);
     jb.m[i][e] = n.m; jb.v[i][e] = n.v;
-    jb.p[i][e] = adam_param(jb.adam, op, n);
+    jb.p[i][e] = adam_param(jb.adam, opar, n);
 }
 
 inline size_t round64(size_t n) { return (n + 63) & ~(size_t)63; }
@@ -309,18 +326,14 @@ int forward_backward(const aqg_train_general& t, const uint8_t* states72, const 
 }
 
 int launch_finish(const aqg_train_general& t, int B, bool update, int step, const float* loss, float* loss_mean, float* loss_sums,
-                  hipStream_t st) {
-    const int L = t.num_layers, Hd = t.hidden, Hh = Hd / 2, A = t.policy_size, T = 2 * L + 8;
+                  hipStream_t st, const OptimLaunch* ol = nullptr) {
+    const int T = 2 * t.num_layers + 8;
     AdamJobs jb{};
     unsigned int run = 0;
+    size_t numel[MAXT];
+    train_general_tensor_sizes(t, numel);
     for (int i = 0; i < T; ++i) {
-        size_t n;
-        if (i < 2 * L) n = (i & 1) ? (size_t)Hd : (size_t)Hd * (i == 0 ? 6 : Hd);
-        else {
-            const size_t hs[8] = {(size_t)Hh * Hd, (size_t)Hh, (size_t)A * Hh, (size_t)A, (size_t)Hh * Hd, (size_t)Hh, (size_t)Hh, 1};
-            n = hs[i - 2 * L];
-        }
-        run += (unsigned int)n;
+        run += (unsigned int)numel[i];
         jb.end[i] = run;
         jb.p[i] = t.params[i]; jb.g[i] = t.grads[i]; jb.m[i] = t.adam_m[i]; jb.v[i] = t.adam_v[i];
     }
@@ -330,7 +343,14 @@ int launch_finish(const aqg_train_general& t, int B, bool update, int step, cons
     const unsigned int adam_blocks = update ? blocks_of(run, 256) : 0u;
     const unsigned int grid = adam_blocks + (loss && B > 0 ? 1u : 0u);
     if (grid == 0) return 0;
-    hipLaunchKernelGGL(train_general_finish_kernel, dim3(grid), dim3(256), 0, st, jb, adam_blocks);
+    if (ol && update) {
+        AdamOptimJobs jo{};
+        static_cast<AdamJobs&>(jo) = jb;
+        fill_optim(*ol, T, &jo.op.s, jo.op.wd);
+        hipLaunchKernelGGL(train_general_finish_kernel<AdamOptimJobs>, dim3(grid), dim3(256), 0, st, jo, adam_blocks);
+        return check_launch("train_general_finish_kernel<AdamOptimJobs>");
+    }
+    hipLaunchKernelGGL(train_general_finish_kernel<AdamJobs>, dim3(grid), dim3(256), 0, st, jb, adam_blocks);
     return check_launch("train_general_finish_kernel");
 }
 
@@ -347,6 +367,14 @@ int validate(const aqg_train_general& t, const char* what) {
 }
 
 }  // namespace
+
+// elements of each of the 2 L + 8 tensors, in parameter order
+void train_general_tensor_sizes(const aqg_train_general& t, size_t* numel) {
+    const int L = t.num_layers, Hd = t.hidden, Hh = Hd / 2, A = t.policy_size;
+    const size_t hs[8] = {(size_t)Hh * Hd, (size_t)Hh, (size_t)A * Hh, (size_t)A, (size_t)Hh * Hd, (size_t)Hh, (size_t)Hh, 1};
+    for (int i = 0; i < 2 * L + 8; ++i)
+        numel[i] = i >= 2 * L ? hs[i - 2 * L] : (i & 1) ? (size_t)Hd : (size_t)Hd * (i == 0 ? 6 : Hd);
+}
 
 // the prep and loss kernels, shared with the residual CNN's step (cnn_train.hip): the same graph pointer / gathered records and the
 // same two loss terms and their gradients
@@ -371,8 +399,11 @@ size_t train_general_workspace_floats(int N, int hidden, int num_layers, int pol
 }
 
 // mode 0 = gradients only, 1 = gradients + Adam, 2 = Adam only (data-parallel: local gradients, all-reduce, update)
-int train_step_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st) {
+int train_step_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
+                       const OptimPlan* plan) {
     const char* what = "aqg_gcn_train_step_general";
+    OptimLaunch ol;
+    const OptimLaunch* olp = plan && mode >= 1 ? &ol : nullptr;
     if (int r = validate(t, what)) return r;
     const int B = t.batch;
     if (mode != 2 && B > 0) {
@@ -384,14 +415,19 @@ int train_step_general(const aqg_train_general& t, const uint8_t* states72, cons
         float* value = t.value ? t.value : ws.value;
         float* loss = t.loss ? t.loss : ws.loss;
         if (int r = forward_backward(t, states72, pi, z, nullptr, 0, B, ws, policy, value, loss, st)) return r;
-        return launch_finish(t, B, mode == 1, t.step, loss, t.loss_mean ? t.loss_mean : ws.loss_mean, nullptr, st);
+        if (olp) if (int r = optim_before_finish(*plan, 0, &ol, st)) return r;
+        if (int r = launch_finish(t, B, mode == 1, t.step, loss, t.loss_mean ? t.loss_mean : ws.loss_mean, nullptr, st, olp)) return r;
+        return plan && mode == 0 ? optim_norm_only(*plan, st) : 0;
     }
-    if (mode >= 1) return launch_finish(t, B, true, t.step, nullptr, nullptr, nullptr, st);
-    return 0;
+    if (mode >= 1) {
+        if (olp) if (int r = optim_before_finish(*plan, 0, &ol, st)) return r;
+        return launch_finish(t, B, true, t.step, nullptr, nullptr, nullptr, st, olp);
+    }
+    return plan ? optim_norm_only(*plan, st) : 0;
 }
 
 int train_steps_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
-                        long long positions, float* loss_sums, hipStream_t st) {
+                        long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan) {
     const char* what = "aqg_gcn_train_steps_general";
     if (int r = validate(t, what)) return r;
     if (t.batch < 1) return fail(what, "batch must be >= 1");
@@ -407,7 +443,10 @@ int train_steps_general(const aqg_train_general& t, const uint8_t* states72, con
         float* value = t.value ? t.value : ws.value;
         float* loss = t.loss ? t.loss : ws.loss;
         if (int r = forward_backward(t, states72, pi, z, order, (int)first, B, ws, policy, value, loss, st)) return r;
-        if (int r = launch_finish(t, B, true, step, loss, t.loss_mean ? t.loss_mean : ws.loss_mean, loss_sums, st)) return r;
+        OptimLaunch ol;
+        if (plan) if (int r = optim_before_finish(*plan, step - t.step, &ol, st)) return r;
+        if (int r = launch_finish(t, B, true, step, loss, t.loss_mean ? t.loss_mean : ws.loss_mean, loss_sums, st, plan ? &ol : nullptr))
+            return r;
     }
     return 0;
 }

@@ -159,11 +159,25 @@ size_t agent_alpha_beta_workspace_bytes(int N, int B, int max_depth);
 int launch_agent_alpha_beta(int N, const uint8_t* states72, int B, const uint8_t* active, int plies_for_draw, int max_dist,
                             int max_depth, void* workspace, size_t workspace_bytes, int32_t* action, int64_t* nodes, hipStream_t st);
 
-// ---- gcn_train.hip
+// ---- grad_norm.hip  (the optimiser controls: train_adam.hpp defines OptimPlan and OptimLaunch)
+struct OptimPlan;
+struct OptimLaunch;
+size_t optim_workspace_floats(size_t n);
+int launch_grad_norm(const float* x, size_t n, float* out, float* workspace, size_t workspace_floats, hipStream_t st);
+// the checks of a step entry point: 0 with *on = whether any control is on and *plan filled, or a refusal.  numel[tensors].
+int check_optim(const aqg_optim* o, int tensors, const size_t* numel, float* const* grads, const char* what, OptimPlan* plan,
+                bool* on);
+int optim_before_finish(const OptimPlan& plan, int step_index, OptimLaunch* ol, hipStream_t st);   // stage 1 (when a norm is wanted)
+int launch_clip_scale(const OptimPlan& plan, const OptimLaunch& ol, hipStream_t st);               // the fused step: g <- coef g in place
+int optim_norm_only(const OptimPlan& plan, hipStream_t st);                                        // mode 0: stage 1 + combine
+
+// ---- gcn_train.hip  (plan: null = the step as it has always been)
 extern int g_train_fused;
-int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st);
+int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
+               const OptimPlan* plan = nullptr);
 int train_steps(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, long long positions,
-                float* loss_sums, hipStream_t st);
+                float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr);
+void train_tensor_sizes(const aqg_train& t, size_t* numel);
 
 // ---- gcn_train_exact.hip, gcn_train_split.hip, gcn_train_final.hip: the two launches of a fused training step
 int launch_train_board_exact(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, int first,
@@ -171,7 +185,8 @@ int launch_train_board_exact(const aqg_train& t, const uint8_t* states72, const 
 int launch_train_board_split(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, int first,
                              int B, int force_fallback, hipStream_t st);
 long long train_fallbacks(int reset);
-int launch_train_final(const aqg_train& t, int B, bool compute, bool update, int step, float* loss_sums, hipStream_t st);
+int launch_train_final(const aqg_train& t, int B, bool compute, bool update, int step, float* loss_sums, hipStream_t st,
+                       const OptimLaunch* ol = nullptr);
 #ifdef AQG_STAMP            // diagnostic builds only (gcn_train_common.hpp): each unit's own stamp counters / dump pointer
 int train_stamps_exact(unsigned long long* out, int reset);
 int train_stamps_split(unsigned long long* out, int reset);
@@ -188,16 +203,20 @@ int launch_train_general_prep(int V, int B, const uint8_t* states72, const int64
 int launch_train_general_loss(int B, int A, const float* policy, const float* value, const float* pi, const float* z,
                               const int64_t* order, int first, float* loss, float* dpol, float* dval, hipStream_t st);
 size_t train_general_workspace_floats(int N, int hidden, int num_layers, int policy_size, int max_batch);
-int train_step_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st);
+int train_step_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
+                       const OptimPlan* plan = nullptr);
 int train_steps_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
-                        long long positions, float* loss_sums, hipStream_t st);
+                        long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr);
+void train_general_tensor_sizes(const aqg_train_general& t, size_t* numel);
 
 // ---- cnn_train.hip
 size_t cnn_train_workspace_floats(int N, int F, int L, int A, int max_batch);
 int check_cnn_train(const aqg_cnn_train& t, bool adam, const char* what);
-int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st);
+int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
+                   const OptimPlan* plan = nullptr);
 int cnn_train_steps(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
-                    long long positions, float* loss_sums, hipStream_t st);
+                    long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr);
+void cnn_train_tensor_sizes(const aqg_cnn_train& t, size_t* numel);
 
 // ---- augment.hip
 int launch_augment_gather(int N, int policy_size, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,

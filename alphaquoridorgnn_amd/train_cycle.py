@@ -194,6 +194,14 @@ def _parser():
                     help="parameter update: train every epoch on positions mirrored left to right at random (default TRAIN_MIRROR = False: off)")
     ap.add_argument("--mirror-seed", type=int, default=None,
                     help="parameter update: seed of the mirror draws (default TRAIN_MIRROR_SEED = 0)")
+    ap.add_argument("--weight-decay", type=float, default=None, metavar="W",
+                    help="parameter update: weight decay W on the weight matrices and conv kernels, inside the HIP step (default "
+                         "TRAIN_WEIGHT_DECAY = 0: none); decoupled as torch.optim.AdamW unless --coupled-weight-decay")
+    ap.add_argument("--coupled-weight-decay", action="store_true",
+                    help="parameter update: add W * p to the gradient, as torch.optim.Adam(weight_decay=W) (needs --weight-decay)")
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="M",
+                    help="parameter update: scale every step's gradient to a global L2 norm of at most M, as "
+                         "torch.nn.utils.clip_grad_norm_ (default TRAIN_MAX_GRAD_NORM = None: off)")
     ap.add_argument("--replay-generations", type=int, default=0,
                     help="train on a replay window of the newest K self-play generations, resident on the GPU (default 0: off, the "
                          "newest .history file alone); a cycle that finds .history files in ./data resumes from the newest K")
@@ -290,6 +298,23 @@ def _set_mirror_options(args):
         tn.TRAIN_MIRROR_SEED = args.mirror_seed
 
 
+def _set_optimiser_options(args):
+    """--weight-decay / --coupled-weight-decay / --max-grad-norm onto train_network's constants, refused here if the step would
+    refuse them."""
+    import math
+    from . import train_network as tn
+    if args.weight_decay is None and args.coupled_weight_decay:
+        raise ValueError("--coupled-weight-decay needs --weight-decay")
+    if args.weight_decay is not None:
+        if not math.isfinite(args.weight_decay) or args.weight_decay < 0.0:
+            raise ValueError("--weight-decay must be finite and >= 0")
+        tn.TRAIN_WEIGHT_DECAY, tn.TRAIN_DECOUPLED = args.weight_decay, not args.coupled_weight_decay
+    if args.max_grad_norm is not None:
+        if not math.isfinite(args.max_grad_norm) or args.max_grad_norm <= 0.0:
+            raise ValueError("--max-grad-norm must be finite and > 0")
+        tn.TRAIN_MAX_GRAD_NORM = args.max_grad_norm
+
+
 def main(argv=None):
     """`python -m alphaquoridorgnn_amd.train_cycle` -- also the per-rank program of
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P -m
@@ -314,6 +339,7 @@ def main(argv=None):
     _set_tree_reuse_options(args)
     _set_resign_options(args)
     _set_mirror_options(args)
+    _set_optimiser_options(args)
     _set_replay_options(args)
     if args.eval_games is not None:
         en.EN_GAME_COUNT = args.eval_games

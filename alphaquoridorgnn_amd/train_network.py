@@ -29,6 +29,11 @@ TRAIN_MIRROR_SEED = 0
 TRAIN_WINDOW = None        # a ReplayWindow (self_play.SP_REPLAY fills it); None or empty = the file route
 TRAIN_GENERATIONS = 1      # K > 1 without a window: a temporary window over the newest K .history files
 TRAIN_EPOCH_ROWS = None    # E: an epoch trains on the first min(E, n) rows of its shuffle, so an update's cost does not grow with K
+# Optimiser controls (the reference's optimiser is a bare Adam(lr=0.001)): weight decay on the weight matrices and conv kernels, and
+# global-norm gradient clipping, both inside the HIP step (include/aqgnn.h "optimiser controls").  All off = the reference's update.
+TRAIN_WEIGHT_DECAY = 0.0      # c of the AlphaZero loss term c * ||theta||^2, as torch's weight_decay
+TRAIN_DECOUPLED = True        # True: torch.optim.AdamW's decay; False: torch.optim.Adam(weight_decay=)'s
+TRAIN_MAX_GRAD_NORM = None    # M: torch.nn.utils.clip_grad_norm_(params, M) in front of every update; None = off
 
 
 def load_data():
@@ -149,10 +154,118 @@ def augment_gather(states72, pi, z, order=None, flips=None, seed=None, epoch=0, 
     return _augment_launch(board_size, states72, pi, z, order, mirror)
 
 
+def clip_coefficient(norm, max_norm):
+    """The factor torch.nn.utils.clip_grad_norm_(params, max_norm) multiplies every gradient by, in float32 as the kernels take it:
+    min(1, max_norm / (norm + 1e-6)) -- exactly 1.0 when nothing is clipped; a NaN norm gives NaN (torch.clamp's minimum)."""
+    c = np.float32(max_norm) / (np.float32(norm) + np.float32(1e-6))
+    return np.float32(1.0) if c > np.float32(1.0) else np.float32(c)
+
+
+def adam_reference(p, g, m, v, step, lr=LEARNING_RATE, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, coef=1.0):
+    """One update of one tensor as the finish kernels take it (csrc/train_adam.hpp), in numpy float32: clip (g <- coef g), weight
+    decay (decoupled, torch.optim.AdamW: p <- p (1 - lr wd); coupled, torch.optim.Adam(weight_decay=): g <- g + wd p), then
+    torch.optim.Adam's update with the bias corrections of `step` (1-based) computed in float64.  Returns (p, m, v), new arrays."""
+    f = np.float32
+    p, g, m, v = (np.asarray(x, dtype=f) for x in (p, g, m, v))
+    lr, b1, b2, eps, wd = f(lr), f(betas[0]), f(betas[1]), f(eps), f(weight_decay)
+    g = f(coef) * g
+    if wd != 0:
+        if decoupled:
+            p = p * (f(1) - lr * wd)
+        else:
+            g = g + wd * p
+    bc1 = f(1.0 - float(b1) ** step)
+    bc2_sqrt = f(np.sqrt(1.0 - float(b2) ** step))
+    m = b1 * m + (f(1) - b1) * g
+    v = b2 * v + (f(1) - b2) * g * g
+    denom = np.sqrt(v) / bc2_sqrt + eps
+    return p - (lr / bc1) * (m / denom), m, v
+
+
+def default_decay_mask(params, decay_all=False):
+    """Which tensors weight decay applies to: those of two or more dimensions (GCN and linear weights, conv kernels) -- not biases,
+    not BatchNorm weight and bias -- unless decay_all."""
+    return [bool(decay_all) or p.dim() >= 2 for p in params]
+
+
+def grad_norm(t):
+    """The L2 norm of a contiguous float32 device tensor (or view), as a 0-dim device tensor: the deterministic two-stage reduction
+    of gradient clipping (aqg_grad_norm, csrc/grad_norm.hip), no host read."""
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < 1:
+        raise ValueError("grad_norm takes a non-empty contiguous float32 tensor")
+    dev = _lib.require_gpu(t.device)
+    lib = _lib.load()
+    n = int(t.numel())
+    nws = int(lib.aqg_optim_workspace_floats(n))
+    if nws == 0:
+        _lib.check(-1, "aqg_optim_workspace_floats (more elements than the reduction takes)")
+    ws = torch.empty((nws,), dtype=torch.float32, device=dev)
+    out = torch.empty((1,), dtype=torch.float32, device=dev)
+    _lib.check(lib.aqg_grad_norm(_lib.ptr(t), n, _lib.ptr(out), _lib.ptr(ws), nws, _lib.stream_ptr(dev)), "aqg_grad_norm")
+    return out[0]
+
+
 class _Trainer:
-    """What GNNTrainer and GeneralTrainer share: the Adam state and the flat gradient buffer, step() (single process or data
-    parallel), outputs() and run_epoch().  A subclass provides the library calls (_call, _call_epoch), the batch-mean losses of a
-    single-process step (_batch_losses) and what an update must tell the model (_updated)."""
+    """What the three trainers share: the Adam state and the flat gradient buffer, the optimiser controls, step() (single process or
+    data parallel), outputs() and run_epoch().  A subclass names its library calls (_STEP, _STEPS) and provides the batch-mean losses
+    of a single-process step (_batch_losses) and what an update must tell the model (_updated).
+
+    Optimiser controls (all off by default: the plain entry points, the same launches as ever): weight_decay (torch's coefficient) on
+    the tensors default_decay_mask picks (every tensor with decay_all), decoupled as torch.optim.AdamW (True) or coupled as
+    torch.optim.Adam(weight_decay=) (False), and max_grad_norm = torch.nn.utils.clip_grad_norm_'s max_norm (None or 0 = off).  They
+    are plain attributes read at every call, so a schedule may change them between steps.  With clipping on, last_grad_norm is the
+    unclipped global gradient norm of the last step (0-dim device tensor) and grad_norms that of every step of the last run_epoch
+    (device tensor [steps]); neither is read by the host."""
+
+    def _optimiser_controls(self, weight_decay, decoupled, decay_all, max_grad_norm):
+        self.weight_decay, self.decoupled, self.decay_all, self.max_grad_norm = weight_decay, decoupled, decay_all, max_grad_norm
+        self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=self.dev)
+        self.grad_norms = torch.zeros((0,), dtype=torch.float32, device=self.dev)
+        self._optim_ws = None
+
+    def _optim(self, steps):
+        """(aqg_optim for a call of `steps` steps, the device tensor its norms go to) -- (None, None) with every control off."""
+        wd = float(self.weight_decay or 0.0)
+        clip = float(self.max_grad_norm or 0.0)
+        if wd == 0.0 and clip == 0.0:
+            return None, None
+        o = _lib.OptimStruct()
+        o.decoupled = 1 if self.decoupled else 0
+        if wd != 0.0:
+            mask = default_decay_mask(self.params, self.decay_all)
+            o.num_tensors = len(mask)
+            o._wd = (ctypes.c_float * len(mask))(*[wd if d else 0.0 for d in mask])       # kept alive by the struct object
+            o.weight_decay = ctypes.cast(o._wd, ctypes.POINTER(ctypes.c_float))
+        norms = None
+        if clip != 0.0:
+            if self._optim_ws is None:
+                nws = int(self.lib.aqg_optim_workspace_floats(self.flat_grads.numel()))
+                self._optim_ws = torch.empty((nws,), dtype=torch.float32, device=self.dev)
+            norms = torch.zeros((steps,), dtype=torch.float32, device=self.dev)
+            o.max_grad_norm = clip
+            o.grad_norm = norms.data_ptr()
+            o.workspace, o.workspace_floats = self._optim_ws.data_ptr(), self._optim_ws.numel()
+        return o, norms
+
+    def _call(self, states72, pi_target, z_target, mode, plain=False):
+        o, norms = (None, None) if plain else self._optim(1)
+        args = (ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target), mode)
+        if o is None:
+            _lib.check(getattr(self.lib, self._STEP)(*args, _lib.stream_ptr(self.dev)), self._STEP)
+        else:
+            _lib.check(getattr(self.lib, self._STEP + "_optim")(*args, ctypes.byref(o), _lib.stream_ptr(self.dev)), self._STEP + "_optim")
+        if norms is not None:
+            self.last_grad_norm = norms[0]
+
+    def _call_epoch(self, states72, pi_target, z_target, order, n, sums):
+        o, norms = self._optim((n + self.t.batch - 1) // self.t.batch)
+        args = (ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target), _lib.ptr(order), n, _lib.ptr(sums))
+        if o is None:
+            _lib.check(getattr(self.lib, self._STEPS)(*args, _lib.stream_ptr(self.dev)), self._STEPS)
+        else:
+            _lib.check(getattr(self.lib, self._STEPS + "_optim")(*args, ctypes.byref(o), _lib.stream_ptr(self.dev)), self._STEPS + "_optim")
+        if norms is not None:
+            self.grad_norms, self.last_grad_norm = norms, norms[-1]
 
     def _optimiser_state(self):
         # all gradient tensors are views of ONE flat buffer: the data-parallel exchange is a single all-reduce
@@ -192,7 +305,7 @@ class _Trainer:
             loss = self._batch_losses(B) if B else torch.zeros((2,), device=self.dev)
         else:
             if B:
-                self._call(states72, pi_target, z_target, 0)
+                self._call(states72, pi_target, z_target, 0, plain=True)      # the norm that counts is the all-reduced gradient's
                 lsum = self.ws["loss"][:B].sum(dim=0)
             else:                                                  # a rank may hold no position of a ragged last batch
                 self.flat_grads.zero_()
@@ -249,7 +362,10 @@ class _Trainer:
 class GNNTrainer(_Trainer):
     """Adam state + workspace for optimisation steps of up to `max_batch` positions on `model` (a GNNNetwork on the GPU)."""
 
-    def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8):
+    _STEP, _STEPS = "aqg_gcn_train_step", "aqg_gcn_train_steps"
+
+    def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, decay_all=False,
+                 max_grad_norm=None):
         if not getattr(model, "fused", True):
             model._require_fused("GNNTrainer (the fused training kernels)")
         self.model = model
@@ -261,6 +377,7 @@ class GNNTrainer(_Trainer):
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise ValueError("training needs contiguous float32 parameters")
         self._optimiser_state()
+        self._optimiser_controls(weight_decay, decoupled, decay_all, max_grad_norm)
         self.N = model.board_size
         self.V = self.N * self.N
         self.A = model.policy_output_size
@@ -285,14 +402,6 @@ class GNNTrainer(_Trainer):
         for name, x in w.items():
             setattr(t, name, x.data_ptr())
 
-    def _call(self, states72, pi_target, z_target, mode):
-        _lib.check(self.lib.aqg_gcn_train_step(ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target),
-                                               mode, _lib.stream_ptr(self.dev)), "aqg_gcn_train_step")
-
-    def _call_epoch(self, states72, pi_target, z_target, order, n, sums):
-        _lib.check(self.lib.aqg_gcn_train_steps(ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target),
-                                                _lib.ptr(order), n, _lib.ptr(sums), _lib.stream_ptr(self.dev)), "aqg_gcn_train_steps")
-
     def _batch_losses(self, B):
         return self.ws["loss"][:B].mean(dim=0)
 
@@ -307,7 +416,10 @@ class GeneralTrainer(_Trainer):
     place (and their version counters advanced), so an engine built with evaluator='general' only needs refresh_weights() to
     search with the new weights -- its evaluation cache included."""
 
-    def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8):
+    _STEP, _STEPS = "aqg_gcn_train_step_general", "aqg_gcn_train_steps_general"
+
+    def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, decay_all=False,
+                 max_grad_norm=None):
         if getattr(model, "num_features", NUM_FEATURES) != NUM_FEATURES:
             raise ValueError(f"GeneralTrainer trains on board records, which have {NUM_FEATURES} feature planes; this network takes "
                              f"num_features={model.num_features}")
@@ -321,6 +433,7 @@ class GeneralTrainer(_Trainer):
         if any(p.device != self.dev for p in self.params):
             raise ValueError("every parameter must be on the trainer's GPU")
         self._optimiser_state()
+        self._optimiser_controls(weight_decay, decoupled, decay_all, max_grad_norm)
         self.N = model.board_size
         self.A = model.policy_output_size
         self.max_batch = int(max_batch)
@@ -346,16 +459,6 @@ class GeneralTrainer(_Trainer):
         t.policy, t.value, t.loss, t.loss_mean = (self.ws[k].data_ptr() for k in ("pol", "val", "loss", "loss_mean"))
         t.workspace, t.workspace_floats = self.ws["workspace"].data_ptr(), nws
 
-    def _call(self, states72, pi_target, z_target, mode):
-        _lib.check(self.lib.aqg_gcn_train_step_general(ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target),
-                                                       _lib.ptr(z_target), mode, _lib.stream_ptr(self.dev)),
-                   "aqg_gcn_train_step_general")
-
-    def _call_epoch(self, states72, pi_target, z_target, order, n, sums):
-        _lib.check(self.lib.aqg_gcn_train_steps_general(ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target),
-                                                        _lib.ptr(z_target), _lib.ptr(order), n, _lib.ptr(sums),
-                                                        _lib.stream_ptr(self.dev)), "aqg_gcn_train_steps_general")
-
     def _batch_losses(self, B):
         return self.ws["loss_mean"].clone()          # summed in position order by the library
 
@@ -380,7 +483,10 @@ class CNNTrainer(_Trainer):
     engine's refresh_weights() pick up the new weights.  BatchNorm statistics over a sharded batch would need synchronised
     BatchNorm: a step under a process group of more than one rank raises ValueError."""
 
-    def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8):
+    _STEP, _STEPS = "aqg_cnn_train_step", "aqg_cnn_train_steps"
+
+    def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, decay_all=False,
+                 max_grad_norm=None):
         from .pv_network_cnn import CNNNetwork
         if not isinstance(model, CNNNetwork):
             raise ValueError("CNNTrainer trains a pv_network_cnn.CNNNetwork")
@@ -406,6 +512,7 @@ class CNNTrainer(_Trainer):
             if x.dtype != torch.float32 or not x.is_contiguous():
                 raise ValueError("training needs contiguous float32 parameters and running statistics")
         self._optimiser_state()
+        self._optimiser_controls(weight_decay, decoupled, decay_all, max_grad_norm)
         self.N = model.board_size
         self.A = model.policy_output_size
         self.max_batch = int(max_batch)
@@ -452,14 +559,6 @@ class CNNTrainer(_Trainer):
         self._forwarded((int(order.shape[0]) + batch - 1) // batch)
         return sums
 
-    def _call(self, states72, pi_target, z_target, mode):
-        _lib.check(self.lib.aqg_cnn_train_step(ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target),
-                                               mode, _lib.stream_ptr(self.dev)), "aqg_cnn_train_step")
-
-    def _call_epoch(self, states72, pi_target, z_target, order, n, sums):
-        _lib.check(self.lib.aqg_cnn_train_steps(ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target),
-                                                _lib.ptr(order), n, _lib.ptr(sums), _lib.stream_ptr(self.dev)), "aqg_cnn_train_steps")
-
     def _batch_losses(self, B):
         return self.ws["loss_mean"].clone()          # summed in position order by the library
 
@@ -476,12 +575,28 @@ class CNNTrainer(_Trainer):
         self.model.invalidate_packed()
 
 
+def _configured_controls():
+    """The trainers' optimiser keyword arguments from TRAIN_WEIGHT_DECAY, TRAIN_DECOUPLED and TRAIN_MAX_GRAD_NORM."""
+    return dict(weight_decay=TRAIN_WEIGHT_DECAY, decoupled=TRAIN_DECOUPLED, max_grad_norm=TRAIN_MAX_GRAD_NORM)
+
+
+def _progress_line(epoch, policy_loss, value_loss, trainer):
+    """The per-epoch progress line (train_network.py:100); with clipping on, the epoch's mean gradient norm beside it (one host read of
+    grad_norms per epoch)."""
+    line = f"\rEpoch {epoch + 1}/{NUM_EPOCH} | Policy Loss: {float(policy_loss):.4f} | Value Loss: {float(value_loss):.4f}"
+    if trainer.max_grad_norm and trainer.grad_norms.numel():
+        line += f" | Grad Norm: {float(trainer.grad_norms.mean()):.4f}"
+    return line
+
+
 def trainer_for(model, max_batch=BATCH_SIZE):
-    """GNNTrainer for the default 6/128/3 network (the fused step), GeneralTrainer for every other shape."""
+    """GNNTrainer for the default 6/128/3 network (the fused step), GeneralTrainer for every other shape, with the configured
+    optimiser controls (TRAIN_WEIGHT_DECAY, TRAIN_DECOUPLED, TRAIN_MAX_GRAD_NORM)."""
     from .pv_network_cnn import CNNNetwork
     if isinstance(model, CNNNetwork):
         raise NotImplementedError(CNN_TRAINING_NOT_BUILT)
-    return GNNTrainer(model, max_batch=max_batch) if getattr(model, "fused", False) else GeneralTrainer(model, max_batch=max_batch)
+    kind = GNNTrainer if getattr(model, "fused", False) else GeneralTrainer
+    return kind(model, max_batch=max_batch, **_configured_controls())
 
 
 def train_network():
@@ -551,7 +666,7 @@ def _train_loop(rank, world):
                 epoch_policy_loss += pl
                 epoch_value_loss += vl
         if rank == 0:
-            print(f"\rEpoch {epoch + 1}/{NUM_EPOCH} | Policy Loss: {float(epoch_policy_loss):.4f} | Value Loss: {float(epoch_value_loss):.4f}", end='')
+            print(_progress_line(epoch, epoch_policy_loss, epoch_value_loss, trainer), end='')
     if rank == 0:
         print('')
         torch.save(model.state_dict(), PV_NETWORK_PATH + 'latest.pth')
@@ -585,13 +700,13 @@ def _train_cnn_loop():
     model = load_cnn(PV_NETWORK_PATH + 'best.pth', dev)
     s, p, v, index = _training_rows(dev, model.board_size)
     n = s.shape[0] if index is None else index.shape[0]
-    trainer = CNNTrainer(model, max_batch=BATCH_SIZE)
+    trainer = CNNTrainer(model, max_batch=BATCH_SIZE, **_configured_controls())
     for epoch in range(NUM_EPOCH):
         lr = LEARNING_RATE * lr_lambda(epoch)                                      # LambdaLR, stepped once per epoch (:98)
         perm = torch.randperm(n, device=dev)                                    # DataLoader(shuffle=True), last batch kept
         epoch_policy_loss, epoch_value_loss = trainer.run_epoch(s, p, v, _epoch_order(perm, index), lr=lr,
                                                                  mirror=(TRAIN_MIRROR_SEED, epoch) if TRAIN_MIRROR else None)
-        print(f"\rEpoch {epoch + 1}/{NUM_EPOCH} | Policy Loss: {float(epoch_policy_loss):.4f} | Value Loss: {float(epoch_value_loss):.4f}", end='')
+        print(_progress_line(epoch, epoch_policy_loss, epoch_value_loss, trainer), end='')
     print('')
     torch.save(model.state_dict(), PV_NETWORK_PATH + 'latest.pth')
 

@@ -761,6 +761,65 @@ int aqg_cnn_train_step(const aqg_cnn_train* t_host, const uint8_t* states72, con
 int aqg_cnn_train_steps(const aqg_cnn_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target,
                         const int64_t* order, long long positions, float* loss_sums, void* stream);
 
+/* ------------------------------------------------------------------ optimiser controls (additive to ABI 15; the reference has none)
+ *
+ * Weight decay and global-norm gradient clipping for the three training steps above, pinned to torch.  With g the gradient of an
+ * element and p its parameter, in this order (csrc/train_adam.hpp):
+ *   1. clip, torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2): norm = the L2 norm over every gradient element of every
+ *      tensor, coef = min(1, max_norm / (norm + 1e-6)) in f32, g <- coef g.  Nothing clipped: coef is exactly 1.0f.  A non-finite
+ *      norm gets NO special treatment (torch's default, error_if_nonfinite=False): a NaN norm makes coef, the moments and the
+ *      parameters NaN; an infinite one makes coef 0.  Nothing skips the step.
+ *   2. weight decay, one coefficient per tensor (0 = none): decoupled != 0, torch.optim.AdamW: p <- p (1 - lr wd), then the unchanged
+ *      Adam update on that p; decoupled == 0, torch.optim.Adam(weight_decay=wd): g <- g + wd p before the moments.
+ *   3. the Adam update as before.
+ * The norm is computed on the device with no host read and no float atomics (csrc/grad_norm.hip): one launch leaves a partial sum of
+ * squares per 8,192 elements, and every workgroup of the step's Adam launch adds the partials up in a fixed order before it updates
+ * (no combine launch).  Two runs give identical bits; at most 90 additions lie between any term and the total (relative error of the
+ * norm below 5e-6).  The general and CNN steps go from one Adam launch to two launches and leave grads as computed.  The fused
+ * 6/128/3 step, whose final launch forms and consumes each gradient element in one thread, goes to four (gradients, partials, clip
+ * of the stored gradients in place, update) and leaves the CLIPPED gradient in grads, as clip_grad_norm_ leaves it in .grad; a
+ * coefficient of exactly 1 writes nothing.  Decay alone adds no launch.
+ *
+ * aqg_optim: decoupled; weight_decay = HOST array of num_tensors coefficients in the trainer's tensor order (NULL = no decay;
+ *   num_tensors must then equal the trainer's tensor count: 14, 2 L + 8, 3 C + 4); max_grad_norm (0 = no clipping); grad_norm =
+ *   device float(s) that receive the UNCLIPPED norm (NULL = not wanted; asking for it alone runs the norm without clipping);
+ *   workspace / workspace_floats = device floats for the partials, aqg_optim_workspace_floats(total gradient elements) of them
+ *   (only looked at when a norm is taken).
+ * aqg_optim_workspace_floats(n): partials for n elements at any 4-byte-aligned base; 0 = n is 0 or above 134,217,725.
+ * aqg_grad_norm: out[0] = the L2 norm of x[0 .. n) (device f32, 4-byte aligned, n >= 1); reads nothing outside the buffer.
+ * The six _optim entry points take the plain call's struct and arguments plus the controls.  optim == NULL, or a struct with every
+ *   control off (no non-zero decay, max_grad_norm 0, grad_norm NULL), IS the plain call: the same launches.  Otherwise
+ *   mode 0: gradients as always, never scaled; grad_norm[0], if given, receives their norm;
+ *   mode 1: gradients, norm, update;   mode 2: norm of whatever grads holds (the all-reduced gradient under data parallelism), update.
+ *   _steps: every step mode 1; step i writes grad_norm[i] (the caller provides one float per step).
+ *   Refused on the host before any launch (-1, aqg_last_error), besides all the plain call refuses: a negative or non-finite decay,
+ *   a num_tensors that is not the trainer's, a negative or non-finite max_grad_norm, and -- when a norm is taken -- a workspace that is
+ *   NULL or too small, or grads[] that are not consecutive views of one flat buffer (grads[i + 1] == grads[i] + numel(i)). */
+typedef struct aqg_optim {
+    int32_t decoupled;
+    int32_t num_tensors;
+    const float* weight_decay;
+    float max_grad_norm;
+    float* grad_norm;
+    float* workspace;
+    size_t workspace_floats;
+} aqg_optim;
+size_t aqg_optim_workspace_floats(size_t n);
+int aqg_grad_norm(const float* x, size_t n, float* out, float* workspace, size_t workspace_floats, void* stream);
+int aqg_gcn_train_step_optim(const aqg_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                             const aqg_optim* optim, void* stream);
+int aqg_gcn_train_steps_optim(const aqg_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target,
+                              const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim, void* stream);
+int aqg_gcn_train_step_general_optim(const aqg_train_general* t_host, const uint8_t* states72, const float* pi_target,
+                                     const float* z_target, int mode, const aqg_optim* optim, void* stream);
+int aqg_gcn_train_steps_general_optim(const aqg_train_general* t_host, const uint8_t* states72, const float* pi_target,
+                                      const float* z_target, const int64_t* order, long long positions, float* loss_sums,
+                                      const aqg_optim* optim, void* stream);
+int aqg_cnn_train_step_optim(const aqg_cnn_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                             const aqg_optim* optim, void* stream);
+int aqg_cnn_train_steps_optim(const aqg_cnn_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target,
+                              const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim, void* stream);
+
 /* ------------------------------------------------------------------ training augmentation (additive to ABI 15; the reference has none)
  *
  * Quoridor is symmetric under the left-right mirror of the board: column y -> N - 1 - y in each player's own frame.  The mirror of a
