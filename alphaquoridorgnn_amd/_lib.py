@@ -216,6 +216,11 @@ SIGNATURES = {
                                       _vp]),
     "aqg_replay_append": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
     "aqg_replay_append_blend": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _f32, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
+    "aqg_replay_position_keys": (_c.c_int, [_vp, _vp, _c.c_int, _vp, _vp]),
+    "aqg_replay_run_heads": (_c.c_int, [_vp, _vp, _c.c_int, _vp, _vp]),
+    "aqg_replay_merge_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "aqg_replay_merge_runs": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_size_t,
+                                         _vp]),
     "aqg_host_legal_actions": (_c.c_int, [_c.c_int, _vp, _vp]),
     "aqg_host_next": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp]),
     "aqg_host_shortest_path": (_c.c_int, [_c.c_int, _vp]),

@@ -531,4 +531,18 @@ int aqg_replay_append_blend(int board_size, int policy_size, const uint8_t* stat
                                       ring_pi, ring_z, (hipStream_t)stream);
 }
 
+int aqg_replay_position_keys(const uint8_t* states72, const int64_t* index, int n, int64_t* keys, void* stream) {
+    return launch_replay_position_keys(states72, index, n, keys, (hipStream_t)stream);
+}
+int aqg_replay_run_heads(const uint8_t* states72, const int64_t* perm, int n, uint8_t* heads, void* stream) {
+    return launch_replay_run_heads(states72, perm, n, heads, (hipStream_t)stream);
+}
+size_t aqg_replay_merge_workspace_floats(int board_size, int n, int u) { return replay_merge_workspace_floats(board_size, n, u); }
+int aqg_replay_merge_runs(int board_size, int policy_size, const uint8_t* states72, const float* pi, const float* z, const int64_t* perm,
+                          const int64_t* starts, int n, int u, uint8_t* out72, float* out_pi, float* out_z, int32_t* count,
+                          float* workspace, size_t workspace_floats, void* stream) {
+    return launch_replay_merge_runs(board_size, policy_size, states72, pi, z, perm, starts, n, u, out72, out_pi, out_z, count, workspace,
+                                    workspace_floats, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -231,4 +231,12 @@ int launch_replay_append_blend(int N, int policy_size, const uint8_t* states72, 
                                const float* search_value, float blend, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
                                float* ring_z, hipStream_t st);
 
+// ---- replay_merge.hip
+int launch_replay_position_keys(const uint8_t* states72, const int64_t* index, int n, int64_t* keys, hipStream_t st);
+int launch_replay_run_heads(const uint8_t* states72, const int64_t* perm, int n, uint8_t* heads, hipStream_t st);
+size_t replay_merge_workspace_floats(int N, int n, int u);
+int launch_replay_merge_runs(int N, int policy_size, const uint8_t* states72, const float* pi, const float* z, const int64_t* perm,
+                             const int64_t* starts, int n, int u, uint8_t* out72, float* out_pi, float* out_z, int32_t* count,
+                             float* workspace, size_t workspace_floats, hipStream_t st);
+
 }  // namespace aqg

@@ -12,6 +12,11 @@ bookkeeping over it.
 
 Blended value target (`append_counts(..., search_value=q, value_blend=L)`, aqg_replay_append_blend): z' = (1 - L) z + L q with q the
 search value the engine recorded beside the row (engine.history_values).  `blend_targets` is the arithmetic in numpy.
+
+Position merge (`ReplayWindow.merged()`, `merge_positions`; csrc/replay_merge.hip): the window holds one row per OCCURRENCE of a
+position -- every game's opening, and on the small boards many plies after it, thousands of times.  Merged, each distinct position is
+one row whose targets are the mean of its occurrences' (each position then weighs the same; `count` is returned for another
+weighting).  A position and its left-right mirror are NOT merged.  `merge_reference` and `position_keys` are the statements in numpy.
 """
 import pickle
 
@@ -92,6 +97,172 @@ def append_reference(board_size, states72, visits, z_i8, pi, z_f32, head, ring72
         ring_z[slots] = z_f32
 
 
+# ---- position merge: rows that hold the same position become one row with the mean targets (csrc/replay_merge.hip)
+
+KEY_BYTES = np.array([k for k in range(72) if k not in (68, 69, 71)])      # 68-69: the ply counter; 71: spare
+MERGE_CHUNK = 64        # rows of one chunk of the summation order (MRG_CHUNK)
+
+
+def _splitmix64(x):
+    x = (np.asarray(x, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15))
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def position_keys(states72, index=None):
+    """aqg_replay_position_keys in numpy, bit for bit: int64 [n], one hash of the key bytes (0..67 and 70) of each row index[i]
+    (index None: every row): sum_k (b_k + 1) * (splitmix64(k) | 1) mod 2^64, then one splitmix64 step.  Changing one key byte always
+    changes the key; bytes 68, 69 and 71 never do.  The hash only groups rows: merge_reference compares the bytes."""
+    s = np.asarray(states72)
+    if s.dtype != np.uint8 or s.ndim != 2 or s.shape[1] != 72:
+        raise ValueError("position_keys: states72 must be uint8 [rows,72]")
+    if index is not None:
+        s = s[np.asarray(index, dtype=np.int64)]
+    with np.errstate(over="ignore"):
+        m = _splitmix64(KEY_BYTES.astype(np.uint64)) | np.uint64(1)
+        h = ((s[:, KEY_BYTES].astype(np.uint64) + np.uint64(1)) * m[None, :]).sum(axis=1, dtype=np.uint64)
+        return _splitmix64(h).view(np.int64)
+
+
+def merge_depth(length):
+    """The largest number of additions between a term and its run's total in the merge's summation order, for a run of `length`
+    rows: min(L, 64) - 1 inside its chunk, ceil(L / 64) - 1 across the chunk sums."""
+    length = int(length)
+    return min(length, MERGE_CHUNK) - 1 + -(-length // MERGE_CHUNK) - 1
+
+
+def _sum_in_order(x):
+    """((x[0] + x[1]) + x[2]) + ... over the first axis, every sum rounded to f32."""
+    acc = x[0].copy()
+    for k in range(1, x.shape[0]):
+        acc = acc + x[k]
+    return acc
+
+
+def merge_reference(states72, pi, z, index=None, perm=None):
+    """The position merge in numpy on host arrays -- the kernels' statement, and what a CPU window runs.  Returns (out72, out_pi,
+    out_z, count).
+
+    The input is the rows index[0..n) of (states72 uint8 [rows,72], pi float32 [rows,A], z float32 [rows]) in the order given (index
+    None: all rows).  perm (int64 [n], places of that input; None: the stable sort of position_keys) brings equal positions
+    together; a run is a maximal stretch of perm whose rows have equal key bytes (bytes 0..67 and 70 -- a full compare, so rows that
+    merely share a hash never merge).  One output row per run, the runs ordered by the place of their first row in the input: the
+    record is the run's first row's 72 bytes verbatim, count (int32) its length L, pi and z the mean of its rows' in f32.  L == 1 is a
+    copy.  Summation order: chunks of 64 rows of the run, each summed left to right from its first row, the chunk sums summed left
+    to right, the total divided by float32(L) -- merge_depth(L) additions at most between a term and the total."""
+    s, p, v = np.asarray(states72), np.asarray(pi), np.asarray(z)
+    if s.dtype != np.uint8 or s.ndim != 2 or s.shape[1] != 72:
+        raise ValueError("merge_reference: states72 must be uint8 [rows,72]")
+    if p.dtype != np.float32 or p.ndim != 2 or p.shape[0] != s.shape[0] or v.dtype != np.float32 or v.shape != (s.shape[0],):
+        raise ValueError("merge_reference: pi must be float32 [rows,A] and z float32 [rows]")
+    rows = np.arange(s.shape[0], dtype=np.int64) if index is None else np.asarray(index, dtype=np.int64)
+    n = rows.shape[0]
+    if n and (rows.min() < 0 or rows.max() >= s.shape[0]):
+        raise ValueError("merge_reference: index names a row the arrays do not have")
+    if perm is None:
+        perm = np.argsort(position_keys(s, rows), kind="stable")
+    perm = np.asarray(perm, dtype=np.int64)
+    if perm.shape != (n,) or not np.array_equal(np.sort(perm), np.arange(n)):
+        raise ValueError("merge_reference: perm must be a permutation of the input's places")
+    if n == 0:
+        return s[:0].copy(), p[:0].copy(), v[:0].copy(), np.zeros((0,), dtype=np.int32)
+    src = rows[perm]
+    kb = s[src][:, KEY_BYTES]
+    heads = np.ones((n,), dtype=bool)
+    heads[1:] = (kb[1:] != kb[:-1]).any(axis=1)
+    starts = np.flatnonzero(heads)
+    lengths = np.diff(np.append(starts, n))
+    rank = np.argsort(perm[starts], kind="stable")          # runs by the place of their first row (a stable sort's perm: the least)
+    moved = np.concatenate([src[starts[r]:starts[r] + lengths[r]] for r in rank])
+    return merge_runs_reference(s, p, v, moved, np.cumsum(lengths[rank]) - lengths[rank])
+
+
+def merge_runs_reference(states72, pi, z, perm, starts):
+    """aqg_replay_merge_runs in numpy: output row o is the run of rows perm[starts[o]], ..., perm[starts[o + 1] - 1] (the last run
+    ends at len(perm)), summed in the order perm gives them.  Returns (out72, out_pi, out_z, count); merge_reference states the order."""
+    perm, starts = np.asarray(perm, dtype=np.int64), np.asarray(starts, dtype=np.int64)
+    ends = np.append(starts[1:], perm.shape[0])
+    u = starts.shape[0]
+    out72 = np.empty((u, 72), dtype=np.uint8)
+    out_pi = np.empty((u, pi.shape[1]), dtype=np.float32)
+    out_z = np.empty((u,), dtype=np.float32)
+    count = (ends - starts).astype(np.int32)
+    single = count == 1
+    out72[:], out_pi[single], out_z[single] = states72[perm[starts]], pi[perm[starts[single]]], z[perm[starts[single]]]
+    for o in np.flatnonzero(~single):
+        run = perm[starts[o]:ends[o]]
+        x = np.concatenate([pi[run], z[run][:, None]], axis=1)                                 # z is column A of the row
+        if run.shape[0] > MERGE_CHUNK:
+            x = np.stack([_sum_in_order(x[c:c + MERGE_CHUNK]) for c in range(0, run.shape[0], MERGE_CHUNK)])
+        mean = _sum_in_order(x) / np.float32(run.shape[0])
+        out_pi[o], out_z[o] = mean[:-1], mean[-1]
+    return out72, out_pi, out_z, count
+
+
+def merge_positions(states72, pi, z, index=None, board_size=BOARD_SIZE):
+    """The position merge on the GPU: (out72 uint8 [u,72], out_pi float32 [u,A], out_z float32 [u], count int32 [u]) of the rows
+    index[0..n) (int64, on the tensors' device; None: all rows) of the device tensors (states72, pi, z) -- merge_reference's result bit
+    for bit.  aqg_replay_position_keys hashes the rows, torch sorts the keys (stable), aqg_replay_run_heads marks where the key BYTES
+    change, torch turns that into runs in first-occurrence order, aqg_replay_merge_runs writes the rows.  Host reads: the bounds of
+    index, and the run starts (whose number sizes the outputs)."""
+    if board_size not in (3, 5, 7, 9):
+        raise ValueError("merge_positions: unsupported board_size (odd 3..9)")
+    A = policy_size(board_size)
+    rows = int(states72.shape[0]) if states72.dim() == 2 else -1
+    for x, name, dtype, shape in ((states72, "states72", torch.uint8, (rows, 72)), (pi, "pi", torch.float32, (rows, A)),
+                                  (z, "z", torch.float32, (rows,))):
+        if x.dtype != dtype or tuple(x.shape) != shape or not x.is_cuda or x.device != states72.device:
+            raise ValueError(f"merge_positions: {name} must be a {dtype} {list(shape)} tensor on the GPU ({board_size}x{board_size} board)")
+    dev = states72.device
+    states72, pi, z = states72.contiguous(), pi.contiguous(), z.contiguous()
+    if index is not None:
+        if index.dtype != torch.int64 or index.dim() != 1 or index.device != dev:
+            raise ValueError("merge_positions: index must be an int64 [n] tensor on the rows' device")
+        index = index.contiguous()
+        if index.numel():
+            lo, hi = torch.stack((index.min(), index.max())).tolist()
+            if lo < 0 or hi >= rows:
+                raise ValueError("merge_positions: index names a row the arrays do not have")
+    n = rows if index is None else int(index.numel())
+    lib, st = _lib.load(), _lib.stream_ptr(dev)
+    with torch.cuda.device(dev):
+        if n == 0:
+            return (torch.zeros((0, 72), dtype=torch.uint8, device=dev), torch.zeros((0, A), dtype=torch.float32, device=dev),
+                    torch.zeros((0,), dtype=torch.float32, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev))
+        keys = torch.empty((n,), dtype=torch.int64, device=dev)
+        _lib.check(lib.aqg_replay_position_keys(_lib.ptr(states72), _lib.ptr(index), n, _lib.ptr(keys), st), "aqg_replay_position_keys")
+        perm = torch.sort(keys, stable=True).indices                    # places of the input; equal keys stay in input order
+        src = perm if index is None else index[perm]                    # the same, as rows of the arrays
+        heads = torch.empty((n,), dtype=torch.uint8, device=dev)
+        _lib.check(lib.aqg_replay_run_heads(_lib.ptr(states72), _lib.ptr(src), n, _lib.ptr(heads), st), "aqg_replay_run_heads")
+        starts = heads.nonzero().squeeze(1)                             # the one device-to-host read: u sizes the outputs
+        u = int(starts.numel())
+        if u == n:                                                      # no repeats: every run is its own row, in input order
+            src = torch.arange(n, dtype=torch.int64, device=dev) if index is None else index
+            starts = torch.arange(n, dtype=torch.int64, device=dev)
+        else:
+            # runs into first-occurrence order (a stable sort keeps a run's rows in input order, so its first place is perm[start])
+            lengths = torch.diff(starts, append=torch.tensor([n], dtype=torch.int64, device=dev))
+            rank = torch.sort(perm[starts]).indices                     # rank[o] = the run that becomes output row o
+            lengths_out = lengths[rank]
+            starts_out = torch.cumsum(lengths_out, 0) - lengths_out
+            where = torch.empty_like(rank)
+            where[rank] = starts_out                                    # where[r] = the first place of run r in the new order
+            run_of = torch.cumsum(heads, 0, dtype=torch.int64) - 1
+            place = where[run_of] + (torch.arange(n, dtype=torch.int64, device=dev) - starts[run_of])
+            moved = torch.empty_like(src)
+            moved[place] = src
+            src, starts = moved, starts_out.contiguous()
+        out = (torch.empty((u, 72), dtype=torch.uint8, device=dev), torch.empty((u, A), dtype=torch.float32, device=dev),
+               torch.empty((u,), dtype=torch.float32, device=dev), torch.empty((u,), dtype=torch.int32, device=dev))
+        floats = int(lib.aqg_replay_merge_workspace_floats(board_size, n, u))
+        work = torch.empty((floats,), dtype=torch.float32, device=dev) if floats else None
+        _lib.check(lib.aqg_replay_merge_runs(board_size, A, _lib.ptr(states72), _lib.ptr(pi), _lib.ptr(z), _lib.ptr(src), _lib.ptr(starts),
+                                             n, u, *(_lib.ptr(x) for x in out), _lib.ptr(work), floats, st), "aqg_replay_merge_runs")
+    return out
+
+
 class ReplayWindow:
     """A ring of training rows holding the newest generations, with per-generation bookkeeping on the host.
 
@@ -158,6 +329,17 @@ class ReplayWindow:
                     torch.zeros((0, self.policy_size), dtype=torch.float32, device=self.device),
                     torch.zeros((0,), dtype=torch.float32, device=self.device))
         return tuple(x.index_select(0, self._index) for x in self._rings)
+
+    def merged(self):
+        """The valid rows with repeated positions merged: (states72, pi, z, count) tensors on the window's device, one row per distinct
+        position in the order of its oldest row, pi and z the mean over the position's rows, count (int32) how many there were
+        (merge_positions; merge_reference on a host window).  Without repeats it is rows(), bit for bit, with a count of ones.  The
+        ring, the bookkeeping and rows() are unchanged; stale slots are never read."""
+        if self._rings is None or self._valid == 0:
+            return self.rows() + (torch.zeros((0,), dtype=torch.int32, device=self.device),)
+        if self.device.type == "cpu":
+            return tuple(torch.from_numpy(x) for x in merge_reference(*(x.numpy() for x in self._rings), index=self._index.numpy()))
+        return merge_positions(*self._rings, index=self._index, board_size=self.board_size)
 
     def clear(self):
         """Empty the window; the ring keeps its size."""

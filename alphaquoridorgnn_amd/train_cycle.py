@@ -210,13 +210,16 @@ def _parser():
     ap.add_argument("--epoch-rows", type=int, default=None,
                     help="parameter update: rows an epoch trains on, drawn afresh from the window by every epoch's shuffle (default "
                          "TRAIN_EPOCH_ROWS = None: all of them)")
+    ap.add_argument("--merge-positions", action="store_true",
+                    help="parameter update: merge the rows that hold the same position into one row with the mean policy and value "
+                         "target, once per update (default TRAIN_MERGE_POSITIONS = False: one row per occurrence)")
     ap.add_argument("--no-history-file", action="store_true",
                     help="self-play: write no .history file (needs --replay-generations; default SP_WRITE_HISTORY = True)")
     return ap
 
 
 def _set_replay_options(args):
-    """--replay-generations / --replay-rows / --epoch-rows / --no-history-file onto self_play's and train_network's hooks: one
+    """--replay-generations / --replay-rows / --epoch-rows / --merge-positions / --no-history-file onto self_play's and train_network's hooks: one
     ReplayWindow on this rank's GPU that self-play fills and the parameter update trains on, preloaded from the newest K .history
     files of ./data, oldest first.  Returns the window (None when off)."""
     from pathlib import Path
@@ -224,6 +227,8 @@ def _set_replay_options(args):
     from .replay import ReplayWindow
     if args.epoch_rows is not None:
         tn.TRAIN_EPOCH_ROWS = args.epoch_rows
+    if args.merge_positions:
+        tn.TRAIN_MERGE_POSITIONS = True
     if args.replay_generations < 0:
         raise ValueError("--replay-generations must be >= 0")
     if args.replay_generations == 0:

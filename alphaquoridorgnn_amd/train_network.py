@@ -29,6 +29,10 @@ TRAIN_MIRROR_SEED = 0
 TRAIN_WINDOW = None        # a ReplayWindow (self_play.SP_REPLAY fills it); None or empty = the file route
 TRAIN_GENERATIONS = 1      # K > 1 without a window: a temporary window over the newest K .history files
 TRAIN_EPOCH_ROWS = None    # E: an epoch trains on the first min(E, n) rows of its shuffle, so an update's cost does not grow with K
+# Position merge (replay.merge_positions): the rows of an update that hold the same position -- every game's opening, and much of the
+# early game on small boards -- become ONE row with the mean policy and value target, once per update; the epochs, TRAIN_EPOCH_ROWS and
+# the mirror then run on the merged rows (a flip is keyed by merged row).  Every position weighs the same.
+TRAIN_MERGE_POSITIONS = False    # False = off: one row per occurrence
 # Optimiser controls (the reference's optimiser is a bare Adam(lr=0.001)): weight decay on the weight matrices and conv kernels, and
 # global-norm gradient clipping, both inside the HIP step (include/aqgnn.h "optimiser controls").  All off = the reference's update.
 TRAIN_WEIGHT_DECAY = 0.0      # c of the AlphaZero loss term c * ||theta||^2, as torch's weight_decay
@@ -48,7 +52,22 @@ def _training_rows(dev, board_size):
     """(s, p, v, index) an update trains on, on `dev`: uint8 [rows,72] records, float32 [rows,A] policy and [rows] value targets, and
     the int64 rows of them that are valid, oldest first -- or None when all are (the file route).  A non-empty TRAIN_WINDOW gives its
     rings and index(); TRAIN_GENERATIONS = K > 1 without one a temporary window over the newest K files; otherwise the newest file
-    (train_network.py:19-23,:31-39)."""
+    (train_network.py:19-23,:31-39).  TRAIN_MERGE_POSITIONS: whichever of the three it is, merged once (replay.merge_positions) into
+    compact rows, one per distinct position, with index None; every rank merges the same rows to the same result."""
+    s, p, v, index = _recorded_rows(dev, board_size)
+    if not TRAIN_MERGE_POSITIONS:
+        return s, p, v, index
+    import torch.distributed as dist
+    from .replay import merge_positions
+    n = int(s.shape[0] if index is None else index.shape[0])
+    s, p, v, count = merge_positions(s, p, v, index=index, board_size=board_size)
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0:
+        print(f"merged positions: {n} rows, {int(s.shape[0])} positions, longest run {int(count.max()) if n else 0}")
+    return s, p, v, None
+
+
+def _recorded_rows(dev, board_size):
+    """_training_rows before any merge: one row per occurrence."""
     from .replay import ReplayWindow
     window = TRAIN_WINDOW if TRAIN_WINDOW is not None and len(TRAIN_WINDOW) > 0 else None
     if window is None and TRAIN_GENERATIONS > 1:

@@ -881,6 +881,38 @@ int aqg_replay_append_blend(int board_size, int policy_size, const uint8_t* stat
                             const float* search_value, float blend, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
                             float* ring_z, void* stream);
 
+/* ------------------------------------------------------------------ position merge (additive to ABI 15; the reference has none)
+ *
+ * Rows of (states72, pi, z) that hold the same position merged into one row with the mean targets (csrc/replay_merge.hip;
+ * replay.merge_positions drives the three entry points, replay.merge_reference states them in numpy).  The KEY BYTES of a record are
+ * bytes 0..67 and 70: two rows hold the same position iff their key bytes are equal; bytes 68-69 (the ply counter) and 71 (spare)
+ * never matter.  perm, index and starts hold rows and places the CALLER has checked; they are not checked here.  Every entry refuses
+ * on the host, before any launch (-1, aqg_last_error), and returns 0 for n == 0 without looking at a pointer.  Of a gathered source
+ * the overlap checks assume one row, as aqg_augment_gather does.
+ *
+ * aqg_replay_position_keys: keys[i] = the 64-bit hash of the key bytes of row index[i] (index == NULL: row i), 0 <= i < n:
+ *   h = sum over the key bytes k of (b_k + 1) * (splitmix64(k) | 1) mod 2^64, keys[i] = splitmix64(h) (replay.position_keys).  A single
+ *   changed key byte always changes the key.  The hash only groups rows for the sort; nothing is merged on it.
+ *   Refused: n < 0, states72 or keys NULL, keys overlapping states72 or index.
+ * aqg_replay_run_heads: heads[i] = 1 iff i == 0 or the key bytes of row perm[i] differ from those of row perm[i - 1], else 0 -- a full
+ *   compare, so two positions with one hash split a run and never merge.  Refused: n < 0, a NULL array, heads overlapping a source.
+ * aqg_replay_merge_runs: output row o < u is the run of rows perm[starts[o]], ..., perm[starts[o + 1] - 1] (starts[u] = n; starts is
+ *   increasing from 0): out72 = the run's FIRST row's 72 bytes verbatim, count = its length L, out_pi / out_z = the mean of its policy
+ *   rows / values in f32.  L == 1 is a bit-for-bit copy.  Summation order, a function of L and the order within the run alone: chunks of
+ *   64 rows, each summed left to right from its first row; the chunk sums summed left to right; then the correctly rounded division by
+ *   (float)L.  A term passes through at most min(L, 64) - 1 + ceil(L / 64) - 1 additions.  No atomics.  Chunks of runs longer than 64
+ *   rows are summed by a launch of their own in front (into `workspace`), so that a run of thousands of rows is read by many wavefronts.
+ *   workspace: aqg_replay_merge_workspace_floats(board_size, n, u) floats -- 0 when n - u < 64 (no run can be longer than one chunk;
+ *   workspace may then be NULL), else 2 * ceil(n / 64) * (A + 1).
+ *   Refused: an unsupported board size, a policy_size that is not the board's A, n < 0, u < 0, u > n, u == 0 with n > 0, a NULL array,
+ *   a workspace that is needed and NULL or too small, an output (u rows; the workspace) that overlaps a source or another output. */
+int aqg_replay_position_keys(const uint8_t* states72, const int64_t* index, int n, int64_t* keys, void* stream);
+int aqg_replay_run_heads(const uint8_t* states72, const int64_t* perm, int n, uint8_t* heads, void* stream);
+size_t aqg_replay_merge_workspace_floats(int board_size, int n, int u);
+int aqg_replay_merge_runs(int board_size, int policy_size, const uint8_t* states72, const float* pi, const float* z, const int64_t* perm,
+                          const int64_t* starts, int n, int u, uint8_t* out72, float* out_pi, float* out_z, int32_t* count,
+                          float* workspace, size_t workspace_floats, void* stream);
+
 /* ------------------------------------------------------------------ CPU baseline agents (agents.py) -- HOST pointers, host code */
 
 /* The reference's baseline opponents (agents.py:14-214) are CPU code; so are these: the host instantiation of the rule header
