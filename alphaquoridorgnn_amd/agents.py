@@ -24,6 +24,7 @@ import numpy as np
 
 from . import _lib
 from .constants import NUM_PLIES_FOR_DRAW, NUM_WALLS, board_params
+from .counter_rng import MASK64, counter_uniform, stream_key
 
 MAX_DIST_FROM_GOAL = NUM_PLIES_FOR_DRAW // 2 - NUM_WALLS   # agents.py:11
 
@@ -162,26 +163,11 @@ def mcts_action(state, evaluations=100):
 
 
 # ------------------------------------------------------------------ batched agents (csrc/agents.hip, include/aqgnn.h)
-_MASK64 = (1 << 64) - 1
-_GOLDEN = 0x9E3779B97F4A7C15
-
-
-def _mix64(z):
-    """The splitmix64 finaliser on numpy uint64 (wrapping arithmetic)."""
-    with np.errstate(over="ignore"):
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        return z ^ (z >> np.uint64(31))
-
-
 def draw_uniforms(seed, b, n):
     """The first n draws of state / game b of a call seeded with `seed`: float64 in [0, 1), a pure function of (seed, b, i) -- the
     generator the kernels use when no table is given (include/aqgnn.h):
     key = mix(seed + G (b + 1)); u_i = (mix(key + G (i + 1)) >> 11) 2^-53."""
-    key = _mix64(np.uint64((int(seed) + _GOLDEN * (int(b) + 1)) & _MASK64))
-    with np.errstate(over="ignore"):
-        z = _mix64(key + np.uint64(_GOLDEN) * np.arange(1, int(n) + 1, dtype=np.uint64))
-    return (z >> np.uint64(11)).astype(np.float64) * (2.0 ** -53)
+    return counter_uniform(stream_key(int(seed), int(b)), np.arange(int(n)))
 
 
 def default_threads():
@@ -236,7 +222,7 @@ def random_action_device(states, N, seed=0, uniforms=None):
     B = int(states.shape[0])
     u, stride = _draw_source(uniforms, B, dev)
     out = torch.empty((B,), dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().aqg_agent_random(N, _lib.ptr(states), B, _lib.ptr(u), stride, int(seed) & _MASK64, _lib.ptr(out),
+    _lib.check(_lib.load().aqg_agent_random(N, _lib.ptr(states), B, _lib.ptr(u), stride, int(seed) & MASK64, _lib.ptr(out),
                                             _lib.stream_ptr(dev)), "aqg_agent_random")
     return out
 
@@ -258,7 +244,7 @@ def playout_batch(states72, seed=0, uniforms=None, return_final=False, device=No
     u, stride = _draw_source(uniforms, B, dev)
     value, plies, draws = (torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(3))
     final = torch.empty((B, 72), dtype=torch.uint8, device=dev)
-    _lib.check(_lib.load().aqg_playouts(N, _lib.ptr(d), B, board_params(N)[1], _lib.ptr(u), stride, int(seed) & _MASK64,
+    _lib.check(_lib.load().aqg_playouts(N, _lib.ptr(d), B, board_params(N)[1], _lib.ptr(u), stride, int(seed) & MASK64,
                                         _lib.ptr(value), _lib.ptr(plies), _lib.ptr(draws), _lib.ptr(final), _lib.stream_ptr(dev)),
                "aqg_playouts")
     if u is not None:
@@ -307,7 +293,7 @@ def mcts_action_device(states, N, evaluations=100, seed=0, uniforms=None):
     visits = torch.empty((B, _lib.MAX_LEGAL), dtype=torch.int32, device=dev)
     actions = torch.empty((B, _lib.MAX_LEGAL), dtype=torch.uint8, device=dev)
     _lib.check(lib.aqg_agent_mcts(N, _lib.ptr(states), B, E, board_params(N)[1], _lib.ptr(_explore_dev[key]), _lib.ptr(u), stride,
-                                  int(seed) & _MASK64, _lib.ptr(ws), ws.numel(), _lib.ptr(action), _lib.ptr(visits), _lib.ptr(actions),
+                                  int(seed) & MASK64, _lib.ptr(ws), ws.numel(), _lib.ptr(action), _lib.ptr(visits), _lib.ptr(actions),
                                   _lib.ptr(count), _lib.ptr(draws), _lib.stream_ptr(dev)), "aqg_agent_mcts")
     ws.record_stream(torch.cuda.current_stream(dev))
     return action, visits, actions, count, draws

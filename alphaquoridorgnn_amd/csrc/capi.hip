@@ -207,11 +207,11 @@ int aqg_engine_clear_eval_cache(const aqg_engine* e, void* stream) {
 }
 int aqg_engine_move(const aqg_engine* e, const double* uniforms, void* stream) {
     if (!e || !uniforms) return fail("aqg_engine_move: null argument");
-    return engine_move(*e, uniforms, 0, nullptr, (hipStream_t)stream);
+    return engine_move(*e, uniforms, MoveOptions{}, (hipStream_t)stream);
 }
 int aqg_engine_move_targets(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value, void* stream) {
     if (!e || !uniforms) return fail("aqg_engine_move_targets: null argument");
-    return engine_move(*e, uniforms, temperature_plies, hist_value, (hipStream_t)stream);
+    return engine_move(*e, uniforms, MoveOptions{temperature_plies, hist_value, nullptr, nullptr}, (hipStream_t)stream);
 }
 int aqg_engine_begin_move(const aqg_engine* e, void* stream) {
     if (!e) return fail("aqg_engine_begin_move: null engine");
@@ -223,22 +223,22 @@ int aqg_engine_step(const aqg_engine* e, int do_expand, int do_select, void* str
 }
 int aqg_engine_finish_move(const aqg_engine* e, const double* uniforms, void* stream) {
     if (!e || !uniforms) return fail("aqg_engine_finish_move: null argument");
-    return engine_finish_move(*e, uniforms, 0, nullptr, (hipStream_t)stream);
+    return engine_finish_move(*e, uniforms, MoveOptions{}, (hipStream_t)stream);
 }
 int aqg_engine_finish_move_targets(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
                                    void* stream) {
     if (!e || !uniforms) return fail("aqg_engine_finish_move_targets: null argument");
-    return engine_finish_move(*e, uniforms, temperature_plies, hist_value, (hipStream_t)stream);
+    return engine_finish_move(*e, uniforms, MoveOptions{temperature_plies, hist_value, nullptr, nullptr}, (hipStream_t)stream);
 }
 int aqg_engine_move_reuse(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
                           const aqg_tree_reuse* reuse, void* stream) {
     if (!e || !uniforms || !reuse) return fail("aqg_engine_move_reuse: null argument");
-    return engine_move_reuse(*e, uniforms, temperature_plies, hist_value, *reuse, (hipStream_t)stream);
+    return engine_move(*e, uniforms, MoveOptions{temperature_plies, hist_value, reuse, nullptr}, (hipStream_t)stream);
 }
 int aqg_engine_finish_move_reuse(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
                                  const aqg_tree_reuse* reuse, void* stream) {
     if (!e || !uniforms || !reuse) return fail("aqg_engine_finish_move_reuse: null argument");
-    return engine_finish_move_reuse(*e, uniforms, temperature_plies, hist_value, *reuse, (hipStream_t)stream);
+    return engine_finish_move(*e, uniforms, MoveOptions{temperature_plies, hist_value, reuse, nullptr}, (hipStream_t)stream);
 }
 int aqg_engine_keep_subtrees(const aqg_engine* e, const aqg_tree_reuse* reuse, const int32_t* child_index, void* stream) {
     if (!e || !reuse || !child_index) return fail("aqg_engine_keep_subtrees: null argument");
@@ -251,12 +251,12 @@ int aqg_engine_reset_reuse(const aqg_engine* e, const aqg_tree_reuse* reuse, voi
 int aqg_engine_move_resign(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
                            const aqg_tree_reuse* reuse, const aqg_resign* resign, void* stream) {
     if (!e || !uniforms || !resign) return fail("aqg_engine_move_resign: null argument");
-    return engine_move_resign(*e, uniforms, temperature_plies, hist_value, reuse, *resign, (hipStream_t)stream);
+    return engine_move(*e, uniforms, MoveOptions{temperature_plies, hist_value, reuse, resign}, (hipStream_t)stream);
 }
 int aqg_engine_finish_move_resign(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
                                   const aqg_tree_reuse* reuse, const aqg_resign* resign, void* stream) {
     if (!e || !uniforms || !resign) return fail("aqg_engine_finish_move_resign: null argument");
-    return engine_finish_move_resign(*e, uniforms, temperature_plies, hist_value, reuse, *resign, (hipStream_t)stream);
+    return engine_finish_move(*e, uniforms, MoveOptions{temperature_plies, hist_value, reuse, resign}, (hipStream_t)stream);
 }
 int aqg_engine_reset_resign(const aqg_engine* e, const aqg_resign* resign, void* stream) {
     if (!e || !resign) return fail("aqg_engine_reset_resign: null argument");

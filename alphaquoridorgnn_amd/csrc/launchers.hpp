@@ -92,28 +92,27 @@ int launch_cnn_forward_planes(int N, const float* planes, int B, const aqg_cnn_n
 
 // ---- mcts.hip  (the engine's entry points; host code only)
 extern int g_use_graph;
+// the options of one move, all zero = the plain move: the self-play targets (aqgnn.h, "self-play targets"), tree reuse and resignation
+struct MoveOptions {
+    int temperature_plies;
+    float* hist_value;
+    const aqg_tree_reuse* reuse;
+    const aqg_resign* resign;
+};
 int engine_reset(const aqg_engine& e, hipStream_t st);
 int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st);
 int engine_begin_move(const aqg_engine& e, hipStream_t st);
 int engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t st);
-int engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st);
+int engine_finish_move(const aqg_engine& e, const double* uniforms, const MoveOptions& opts, hipStream_t st);
 int engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
-int engine_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st);
+int engine_move(const aqg_engine& e, const double* uniforms, const MoveOptions& opts, hipStream_t st);
 int engine_search(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
 int engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st);
 int engine_refill(const aqg_engine& e, hipStream_t st);
 int engine_root_noise(const aqg_engine& e, hipStream_t st);
 int engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st);
-int engine_move_reuse(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, const aqg_tree_reuse& ru,
-                      hipStream_t st);
-int engine_finish_move_reuse(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value,
-                             const aqg_tree_reuse& ru, hipStream_t st);
 int engine_keep_subtrees(const aqg_engine& e, const aqg_tree_reuse& ru, const int32_t* child_index, hipStream_t st);
 int engine_reset_reuse(const aqg_engine& e, const aqg_tree_reuse& ru, hipStream_t st);
-int engine_move_resign(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, const aqg_tree_reuse* ru,
-                       const aqg_resign& rs, hipStream_t st);
-int engine_finish_move_resign(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value,
-                              const aqg_tree_reuse* ru, const aqg_resign& rs, hipStream_t st);
 int engine_reset_resign(const aqg_engine& e, const aqg_resign& rs, hipStream_t st);
 
 // ---- mcts_step.hip  (launchers of the engine's kernels only enqueue: the entry point checks the launch)
@@ -134,8 +133,7 @@ void launch_engine_begin_move(const aqg_engine& e, hipStream_t st, const uint8_t
 void launch_engine_kept_root_noise(const aqg_engine& e, const uint8_t* kept, hipStream_t st);
 int launch_engine_fake_eval(const aqg_engine& e, hipStream_t st);
 int launch_engine_root_noise(const aqg_engine& e, hipStream_t st);
-int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st,
-                              int32_t* child_index = nullptr, uint8_t* kept = nullptr, const aqg_resign* resign = nullptr);
+int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, const MoveOptions& opts, hipStream_t st);
 void launch_engine_refill(const aqg_engine& e, hipStream_t st);
 int launch_engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st);
 void launch_engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st);

@@ -27,8 +27,10 @@
 //                   apply_actions (one engine_transition behind both), refill, root_visits / root_priors / root_states72; one plain
 //                   launcher per kernel.
 //   mcts_reuse.hip  tree reuse: engine_keep_subtrees_kernel, the in-place re-rooting of a pool at the chosen child, and its launcher.
-//   mcts.hip        this file, host code only: validate, the simulation loop (enqueue_sims), its hipGraph cache (run_sims) and the
-//                   engine_* entry points.  It launches no kernel itself.
+//   mcts.hip        this file, host code only: validate and validate_move (every refusal of a move, in one order), the simulation loop
+//                   (enqueue_sims), its hipGraph cache (run_sims), the end of a move (finish_and_refill) and the engine_* entry points:
+//                   engine_move and engine_finish_move take the move's options as one MoveOptions value (launchers.hpp).  It launches
+//                   no kernel itself.
 #include "aqg_common.hpp"
 #include <vector>
 #include <cstring>
@@ -72,6 +74,37 @@ static int validate(const aqg_engine& e) {
     }
     if (!(e.root_noise_eps >= 0.f && e.root_noise_eps < 1.f)) return fail("root_noise_eps must be in [0, 1)");
     if (e.root_noise_eps > 0.f && !(e.root_noise_alpha > 0.f && e.root_noise_alpha <= 100.f)) return fail("root_noise_alpha must be in (0, 100]");
+    return 0;
+}
+
+// what the tree-reuse entry points refuse, before anything is launched (aqgnn.h, "tree reuse")
+static int validate_reuse(const aqg_engine& e, const aqg_tree_reuse& ru) {
+    if (ru.keep_visits < 0) return fail("tree reuse: keep_visits must be >= 0");
+    if ((long long)ru.keep_visits + e.sims > 32767) return fail("tree reuse: keep_visits + sims must be <= 32767 (the visit row is read out as int16)");
+    if ((long long)e.node_cap < 1 + ((long long)ru.keep_visits + e.sims) * MAX_LEGAL) return fail("tree reuse: node_cap must be >= 1 + (keep_visits + sims) * AQG_MAX_LEGAL");
+    if (e.prior_mode == 2) return fail("tree reuse: not with prior_mode 2 (the external evaluator)");
+    if (!ru.kept || !ru.child_index || !ru.stat_moves_kept || !ru.stat_visits_kept) return fail("tree reuse: kept / child_index / stat_moves_kept / stat_visits_kept are required");
+    return 0;
+}
+
+// what the resignation entry points refuse, before anything is launched (aqgnn.h, "resignation")
+static int validate_resign(const aqg_engine& e, const aqg_resign& rs) {
+    if (!(rs.threshold > 0.f && rs.threshold <= 1.f)) return fail("resignation: threshold must be in (0, 1]");
+    if (rs.min_ply < 0) return fail("resignation: min_ply must be >= 0");
+    if (!(rs.disable_fraction >= 0.0 && rs.disable_fraction <= 1.0)) return fail("resignation: disable_fraction must be in [0, 1]");
+    if (!rs.resign_min || !rs.game_resigned) return fail("resignation: resign_min / game_resigned are required");
+    if (e.max_plies <= 0) return fail("resignation needs a history (max_plies > 0)");
+    return 0;
+}
+
+// Everything a move refuses, before anything is launched.  The order is part of the interface -- the first failing check names the
+// error: the engine, the two targets, tree reuse if it is on, resignation if it is on.
+static int validate_move(const aqg_engine& e, const MoveOptions& o) {
+    if (int r = validate(e)) return r;
+    if (o.temperature_plies < 0) return fail("temperature_plies must be >= 0");
+    if (o.hist_value && e.max_plies <= 0) return fail("hist_value needs a history (max_plies > 0)");
+    if (o.reuse) if (int r = validate_reuse(e, *o.reuse)) return r;
+    if (o.resign) if (int r = validate_resign(e, *o.resign)) return r;
     return 0;
 }
 
@@ -199,41 +232,15 @@ static int run_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reuse* r
 }
 
 // the end of a move: choose and apply (finish_move), then hand the idle slots their next games (refill) while a quota is left to play
-// (outside the captured graph, so the two target options are plain arguments: 0 / nullptr = off)
+// (outside the captured graph, so the two target options are plain kernel arguments: 0 / nullptr = off)
 // (tree reuse: finish_move leaves the chosen child's index, the keep launch re-roots the pools of the games that go on -- in front of the
 //  refill, whose new games start in slots that are inactive here and therefore never marked)
 // (resignation: the option is the finish-move launch's last argument; a resigned slot is inactive behind it, like any finished one)
-static int finish_and_refill(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st,
-                             const aqg_tree_reuse* reuse = nullptr, const aqg_resign* resign = nullptr) {
-    if (int r = launch_engine_finish_move(e, uniforms, temperature_plies, hist_value, st, reuse ? reuse->child_index : nullptr,
-                                          reuse ? reuse->kept : nullptr, resign))
-        return r;
-    if (reuse) launch_engine_keep_subtrees(e, *reuse, reuse->child_index, st);
+static int finish_and_refill(const aqg_engine& e, const double* uniforms, const MoveOptions& o, hipStream_t st) {
+    if (int r = launch_engine_finish_move(e, uniforms, o, st)) return r;
+    if (o.reuse) launch_engine_keep_subtrees(e, *o.reuse, o.reuse->child_index, st);
     if (e.quota > e.num_games) launch_engine_refill(e, st);
     return check_launch("engine_finish_move_kernel");
-}
-
-// what the _targets entry points refuse, before anything is launched
-static int validate_targets(const aqg_engine& e, int temperature_plies, const float* hist_value) {
-    if (temperature_plies < 0) return fail("temperature_plies must be >= 0");
-    if (hist_value && e.max_plies <= 0) return fail("hist_value needs a history (max_plies > 0)");
-    return 0;
-}
-
-static int do_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st,
-                   const aqg_tree_reuse* reuse = nullptr, const aqg_resign* resign = nullptr) {
-    if (int r = run_sims(e, st, reuse)) return r;
-    return finish_and_refill(e, uniforms, temperature_plies, hist_value, st, reuse, resign);
-}
-
-// what the tree-reuse entry points refuse, before anything is launched (aqgnn.h, "tree reuse")
-static int validate_reuse(const aqg_engine& e, const aqg_tree_reuse& ru) {
-    if (ru.keep_visits < 0) return fail("tree reuse: keep_visits must be >= 0");
-    if ((long long)ru.keep_visits + e.sims > 32767) return fail("tree reuse: keep_visits + sims must be <= 32767 (the visit row is read out as int16)");
-    if ((long long)e.node_cap < 1 + ((long long)ru.keep_visits + e.sims) * MAX_LEGAL) return fail("tree reuse: node_cap must be >= 1 + (keep_visits + sims) * AQG_MAX_LEGAL");
-    if (e.prior_mode == 2) return fail("tree reuse: not with prior_mode 2 (the external evaluator)");
-    if (!ru.kept || !ru.child_index || !ru.stat_moves_kept || !ru.stat_visits_kept) return fail("tree reuse: kept / child_index / stat_moves_kept / stat_visits_kept are required");
-    return 0;
 }
 
 // External-evaluator mode (prior_mode 2): the caller runs the simulation loop itself -- begin, then per simulation
@@ -253,10 +260,9 @@ int engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t s
     return check_launch("engine_step_fast_kernel");
 }
 
-int engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st) {
-    if (int r = validate(e)) return r;
-    if (int r = validate_targets(e, temperature_plies, hist_value)) return r;
-    return finish_and_refill(e, uniforms, temperature_plies, hist_value, st);
+int engine_finish_move(const aqg_engine& e, const double* uniforms, const MoveOptions& o, hipStream_t st) {
+    if (int r = validate_move(e, o)) return r;
+    return finish_and_refill(e, uniforms, o, st);
 }
 
 int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st) {
@@ -273,26 +279,10 @@ int engine_reset(const aqg_engine& e, hipStream_t st) {
     return check_launch("engine_reset_kernel");
 }
 
-int engine_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st) {
-    if (int r = validate(e)) return r;
-    if (int r = validate_targets(e, temperature_plies, hist_value)) return r;
-    return do_move(e, uniforms, temperature_plies, hist_value, st);
-}
-
-int engine_move_reuse(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, const aqg_tree_reuse& ru,
-                      hipStream_t st) {
-    if (int r = validate(e)) return r;
-    if (int r = validate_targets(e, temperature_plies, hist_value)) return r;
-    if (int r = validate_reuse(e, ru)) return r;
-    return do_move(e, uniforms, temperature_plies, hist_value, st, &ru);
-}
-
-int engine_finish_move_reuse(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value,
-                             const aqg_tree_reuse& ru, hipStream_t st) {
-    if (int r = validate(e)) return r;
-    if (int r = validate_targets(e, temperature_plies, hist_value)) return r;
-    if (int r = validate_reuse(e, ru)) return r;
-    return finish_and_refill(e, uniforms, temperature_plies, hist_value, st, &ru);
+int engine_move(const aqg_engine& e, const double* uniforms, const MoveOptions& o, hipStream_t st) {
+    if (int r = validate_move(e, o)) return r;
+    if (int r = run_sims(e, st, o.reuse)) return r;
+    return finish_and_refill(e, uniforms, o, st);
 }
 
 int engine_keep_subtrees(const aqg_engine& e, const aqg_tree_reuse& ru, const int32_t* child_index, hipStream_t st) {
@@ -307,34 +297,6 @@ int engine_reset_reuse(const aqg_engine& e, const aqg_tree_reuse& ru, hipStream_
     if (int r = validate_reuse(e, ru)) return r;
     if (hipMemsetAsync(ru.kept, 0, (size_t)e.num_games, st) != hipSuccess) return fail("hipMemsetAsync(kept)");
     return 0;
-}
-
-// what the resignation entry points refuse, before anything is launched (aqgnn.h, "resignation")
-static int validate_resign(const aqg_engine& e, const aqg_resign& rs) {
-    if (!(rs.threshold > 0.f && rs.threshold <= 1.f)) return fail("resignation: threshold must be in (0, 1]");
-    if (rs.min_ply < 0) return fail("resignation: min_ply must be >= 0");
-    if (!(rs.disable_fraction >= 0.0 && rs.disable_fraction <= 1.0)) return fail("resignation: disable_fraction must be in [0, 1]");
-    if (!rs.resign_min || !rs.game_resigned) return fail("resignation: resign_min / game_resigned are required");
-    if (e.max_plies <= 0) return fail("resignation needs a history (max_plies > 0)");
-    return 0;
-}
-
-int engine_move_resign(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, const aqg_tree_reuse* ru,
-                       const aqg_resign& rs, hipStream_t st) {
-    if (int r = validate(e)) return r;
-    if (int r = validate_targets(e, temperature_plies, hist_value)) return r;
-    if (ru) if (int r = validate_reuse(e, *ru)) return r;
-    if (int r = validate_resign(e, rs)) return r;
-    return do_move(e, uniforms, temperature_plies, hist_value, st, ru, &rs);
-}
-
-int engine_finish_move_resign(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value,
-                              const aqg_tree_reuse* ru, const aqg_resign& rs, hipStream_t st) {
-    if (int r = validate(e)) return r;
-    if (int r = validate_targets(e, temperature_plies, hist_value)) return r;
-    if (ru) if (int r = validate_reuse(e, *ru)) return r;
-    if (int r = validate_resign(e, rs)) return r;
-    return finish_and_refill(e, uniforms, temperature_plies, hist_value, st, ru, &rs);
 }
 
 int engine_reset_resign(const aqg_engine& e, const aqg_resign& rs, hipStream_t st) {

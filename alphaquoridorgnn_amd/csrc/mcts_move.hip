@@ -537,12 +537,13 @@ int launch_engine_root_noise(const aqg_engine& e_in, hipStream_t st) {
     });
 }
 
-int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, int temperature_plies, float* hist_value, hipStream_t st,
-                              int32_t* child_index, uint8_t* kept, const aqg_resign* resign) {
-    const aqg_resign rs = resign ? *resign : aqg_resign{};     // all zero = off
+int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, const MoveOptions& opts, hipStream_t st) {
+    const aqg_resign rs = opts.resign ? *opts.resign : aqg_resign{};     // all zero = off
+    int32_t* child_index = opts.reuse ? opts.reuse->child_index : nullptr;
+    uint8_t* kept = opts.reuse ? opts.reuse->kept : nullptr;
     return for_board_size(e.board_size, [&](auto n) {
         hipLaunchKernelGGL(engine_finish_move_kernel<decltype(n)::value>, dim3((e.num_games + 3) / 4), dim3(256), 0, st, e, uniforms,
-                           temperature_plies, hist_value, child_index, kept, rs);
+                           opts.temperature_plies, opts.hist_value, child_index, kept, rs);
         return 0;
     });
 }

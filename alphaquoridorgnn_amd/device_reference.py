@@ -1,0 +1,101 @@
+"""The device code of the self-play options in numpy: the references the GPU tests hold the kernels to."""
+import numpy as np
+
+from .counter_rng import counter_uniform, stream_key
+from .selfplay_options import ROOT_NOISE_ATTEMPTS
+
+
+def draw_resign_enabled(seed, k, disable_fraction=0.1):
+    """Whether game k may resign under the resignation seed `seed`: counter_uniform(stream_key(seed, k), 0) >= disable_fraction --
+    the draw of engine_finish_move_kernel in numpy (include/aqgnn.h, "resignation").  k may be an array of game indices."""
+    out = counter_uniform(stream_key(int(seed), np.asarray(k, dtype=np.int64)), 0) >= float(disable_fraction)
+    return bool(out) if np.ndim(k) == 0 else out
+
+
+def root_noise_stream_key(seed, k, ply):
+    """The 64-bit key of the noise stream of game k's root at `ply` under the noise seed `seed` (include/aqgnn.h: K(K(seed, k), ply))."""
+    return int(stream_key(stream_key(int(seed), int(k)), int(ply)))
+
+
+def draw_root_noise(seed, k, ply, count, alpha, return_exhausted=False):
+    """The gamma variates g_0 .. g_{count-1} of the root of game k at ply `ply`, float64 [count] -- the generator of
+    engine_root_noise_kernel in numpy (the recipe is in include/aqgnn.h, "root exploration noise").  k may be an array of game
+    indices: the result is then [len(k), count].  Component i draws from its own sub-stream, so the first c components do not
+    depend on count.  return_exhausted: also return how many variates took the fallback of the capped rejection loop."""
+    scalar = np.ndim(k) == 0
+    root = stream_key(stream_key(int(seed), np.atleast_1d(np.asarray(k, dtype=np.int64))), int(ply))
+    key = stream_key(root[:, None], np.arange(int(count))[None, :])
+    alpha = float(np.float32(alpha))          # the struct field is f32
+    boost = alpha < 1.0
+    a = alpha + 1.0 if boost else alpha
+    d = a - 1.0 / 3.0
+    c = 1.0 / np.sqrt(9.0 * d)
+    val = np.full(key.shape, d, dtype=np.float64)
+    todo = np.ones(key.shape, dtype=bool)
+    for t in range(ROOT_NOISE_ATTEMPTS):
+        if not todo.any():
+            break
+        kt = key[todo]
+        u1, u2, u3 = (counter_uniform(kt, j + 3 * t) for j in (1, 2, 3))
+        x = np.sqrt(-2.0 * np.log(1.0 - u1)) * np.cos(2.0 * np.pi * u2)
+        v1 = 1.0 + c * x
+        ok = v1 > 0.0
+        v = np.where(ok, v1 * v1 * v1, 1.0)
+        ok &= np.log(1.0 - u3) < 0.5 * x * x + d - d * v + d * np.log(v)
+        idx = np.flatnonzero(todo.ravel())
+        val.ravel()[idx[ok]] = d * v[ok]
+        todo.ravel()[idx[ok]] = False
+    exhausted = int(todo.sum())
+    if boost:
+        val = val * np.power(1.0 - counter_uniform(key, 0), 1.0 / alpha)
+    val = np.maximum(val, np.finfo(np.float64).tiny)
+    if scalar:
+        val = val[0]
+    return (val, exhausted) if return_exhausted else val
+
+
+NODE_DTYPE = np.dtype([("w", "<f8"), ("p", "<f4"), ("action", "<u4"), ("n", "<i4"), ("kids", "<u4"), ("q", "<f4"), ("cp", "<f4")])
+assert NODE_DTYPE.itemsize == 32      # csrc/mcts_tree.hpp NodeRec
+
+
+def keep_subtree_reference(pool_records, node_count, child_index, keep_visits):
+    """The keep launch (csrc/mcts_reuse.hip) for one slot, in numpy.  pool_records: the slot's pool, NODE_DTYPE [cap] (or anything
+    of 32 bytes per record, e.g. float64 [cap, 4]); node_count: its used records; child_index: index of the chosen child in the root's
+    child block, < 0 = do not keep.  Returns (records, count, kept): kept is True iff the index names a child that is expanded with
+    n <= keep_visits; then records[:count] is the child's subtree re-rooted -- the child at 0 with a fresh root's action / p / cp, every
+    kept child block behind it in ascending order of its old first index, child ranges renamed -- and records[count:] is unspecified
+    (here: the input's).  Not kept: the input's records and count."""
+    src = np.ascontiguousarray(pool_records).view(NODE_DTYPE).reshape(-1)
+    out = src.copy()
+    count = min(int(node_count), src.shape[0])
+    idx = int(child_index)
+    if idx < 0 or count <= 1:
+        return out, int(node_count), False
+    rcnt, rfirst = int(src["kids"][0]) >> 24, int(src["kids"][0]) & 0xFFFFFF
+    if idx >= rcnt or rfirst < 1 or rfirst + rcnt > count:
+        return out, int(node_count), False
+    c = src[rfirst + idx]
+    ccnt, cfirst = int(c["kids"]) >> 24, int(c["kids"]) & 0xFFFFFF
+    if ccnt == 0 or int(c["n"]) > int(keep_visits) or cfirst < rfirst + rcnt or cfirst + ccnt > count:
+        return out, int(node_count), False
+    keep = np.zeros(count, dtype=bool)
+    keep[cfirst:cfirst + ccnt] = True
+    kids = src["kids"][:count].astype(np.int64)
+    for i in range(cfirst, count):            # a node's child block lies behind the node: one ascending pass decides every record
+        if keep[i] and kids[i] >> 24:
+            first, cnt = int(kids[i] & 0xFFFFFF), int(kids[i] >> 24)
+            assert first > i, "a child block lies behind its parent"
+            keep[first:min(first + cnt, count)] = True
+    new_index = np.cumsum(keep)               # 1-based among the kept records == the new index (0 is the new root)
+    old = np.nonzero(keep)[0]
+    moved = src[old].copy()
+    exp = (moved["kids"] >> 24) != 0
+    firsts = (moved["kids"][exp] & 0xFFFFFF).astype(np.int64)
+    moved["kids"][exp] = (new_index[firsts].astype(np.uint32) & 0xFFFFFF) | (moved["kids"][exp] & np.uint32(0xFF000000))
+    total = 1 + old.shape[0]
+    out[1:total] = moved
+    root = np.zeros((), dtype=NODE_DTYPE)
+    root["w"], root["n"], root["q"] = c["w"], c["n"], c["q"]
+    root["action"], root["kids"] = 0xFF, 1 | (ccnt << 24)
+    out[0] = root
+    return out, total, True

@@ -18,313 +18,16 @@ from . import _lib
 from .constants import BOARD_SIZE, board_params
 from .evaluators import BINDINGS
 
-
-ROOT_NOISE_ATTEMPTS = 64      # cap of the gamma sampler's rejection loop (csrc/mcts_move.hip ROOT_NOISE_ATTEMPTS)
-_MASK64 = (1 << 64) - 1
-
-
-def default_root_noise_alpha(board_size):
-    """The usual "10 / typical number of legal moves" rule, with the board's action count N^2 + 2 (N - 1)^2 for the moves."""
-    return 10.0 / (board_size ** 2 + 2 * (board_size - 1) ** 2)
-
-
-def check_root_noise(eps, alpha):
-    """Validate the root-noise options as the library does, on the f32 values its struct holds: eps in [0, 1); alpha in (0, 100]
-    when eps > 0.  Returns them as floats (alpha 0.0 when the noise is off)."""
-    eps = float(np.float32(eps))
-    if not 0.0 <= eps < 1.0:
-        raise ValueError(f"root_noise_eps must be in [0, 1) as a float32, not {eps}")
-    if eps == 0.0:
-        return 0.0, 0.0
-    alpha = float(np.float32(alpha))
-    if not 0.0 < alpha <= 100.0:
-        raise ValueError(f"root_noise_alpha must be in (0, 100] as a float32, not {alpha}")
-    return eps, alpha
-
-
-def refuse_root_noise(what, **options):
-    """Evaluation paths never add noise: an option that asks for it is a mistake, not something to drop silently."""
-    bad = sorted(k for k, v in options.items() if v is not None)
-    if bad:
-        raise ValueError(f"{what} never adds root exploration noise: {', '.join(bad)} is a self-play option")
-
-
-def check_target_options(temperature_plies, record_search_value=False, record_history=True):
-    """Validate the self-play target options (include/aqgnn.h, "self-play targets"): temperature_plies an integer >= 0 (0 = off);
-    record_search_value needs the history it is a column of.  Returns (temperature_plies, record_search_value)."""
-    if isinstance(temperature_plies, bool) or int(temperature_plies) != temperature_plies or not 0 <= int(temperature_plies) < 2 ** 31:
-        raise ValueError(f"temperature_plies must be an integer >= 0, not {temperature_plies!r}")
-    if record_search_value and not record_history:
-        raise ValueError("record_search_value needs record_history: the search value is a column of the history")
-    return int(temperature_plies), bool(record_search_value)
-
-
-def check_tree_reuse(tree_reuse, tree_reuse_visits, sims, evaluator="gnn"):
-    """Validate the tree-reuse options as the library does (include/aqgnn.h, "tree reuse").  Returns keep_visits, or None when the
-    option is off.  tree_reuse_visits None = `sims`; 0 is legal: on, never keeps."""
-    if not tree_reuse:
-        if tree_reuse_visits is not None:
-            raise ValueError("tree_reuse_visits needs tree_reuse=True")
-        return None
-    if evaluator == "external":
-        raise ValueError("tree_reuse is not offered with evaluator='external': its host loop has no keep step")
-    keep = sims if tree_reuse_visits is None else tree_reuse_visits
-    if isinstance(keep, bool) or int(keep) != keep or int(keep) < 0:
-        raise ValueError(f"tree_reuse_visits must be an integer >= 0, not {tree_reuse_visits!r}")
-    keep = int(keep)
-    if keep + int(sims) > 32767:
-        raise ValueError("tree_reuse_visits + sims must be <= 32767: the visit row is read out as int16")
-    if 1 + (keep + int(sims)) * _lib.MAX_LEGAL >= 1 << 24:
-        raise ValueError("tree_reuse_visits + sims is too large: the tree pool must stay below 2**24 records")
-    return keep
-
-
-def refuse_tree_reuse(what, **options):
-    """Matches and evaluation paths search from a fresh tree every move (two alternating searchers would need a two-ply descent
-    into per-model trees): an option that asks for tree reuse is a mistake, not something to drop silently."""
-    bad = sorted(k for k, v in options.items() if v is not None)
-    if bad:
-        raise ValueError(f"{what} never keeps a subtree between moves: {', '.join(bad)} is a self-play option")
-
-
-def check_resign(resign_threshold, resign_min_ply=0, resign_disable_fraction=0.1, record_history=True):
-    """Validate the resignation options as the library does (include/aqgnn.h, "resignation"), on the values its struct holds.
-    Returns (threshold, min_ply, disable_fraction), or None when the option is off (resign_threshold None).  A threshold of 1.0 is
-    legal: on, never resigns -- the statistics are still kept."""
-    if resign_threshold is None:
-        return None
-    if isinstance(resign_threshold, (bool, str)):
-        raise ValueError(f"resign_threshold must be a number in (0, 1], not {resign_threshold!r}")
-    thr = float(np.float32(resign_threshold))
-    if not 0.0 < thr <= 1.0:
-        raise ValueError(f"resign_threshold must be in (0, 1] as a float32, not {resign_threshold!r}")
-    if isinstance(resign_min_ply, bool) or int(resign_min_ply) != resign_min_ply or not 0 <= int(resign_min_ply) < 2 ** 31:
-        raise ValueError(f"resign_min_ply must be an integer >= 0, not {resign_min_ply!r}")
-    frac = float(resign_disable_fraction)
-    if not 0.0 <= frac <= 1.0:
-        raise ValueError(f"resign_disable_fraction must be in [0, 1], not {resign_disable_fraction!r}")
-    if not record_history:
-        raise ValueError("resignation needs record_history: a resigned game ends in a history row")
-    return thr, int(resign_min_ply), frac
-
-
-def refuse_resign(what, **options):
-    """Matches, evaluation paths and moves the engine does not search play every game to its rule end: an option that asks for
-    resignation is a mistake, not something to drop silently."""
-    bad = sorted(k for k, v in options.items() if v is not None)
-    if bad:
-        raise ValueError(f"{what} never resigns a game: {', '.join(bad)} is a self-play option")
-
-
-def default_resign_seed(seed):
-    """The resignation seed of an engine that was given none: `seed` through the mixer (see default_root_noise_seed)."""
-    return _mix64_int((int(seed) & _MASK64) ^ 0x52455349474E4544)
-
-
-def draw_resign_enabled(seed, k, disable_fraction=0.1):
-    """Whether game k may resign under the resignation seed `seed`: counter_uniform(stream_key(seed, k), 0) >= disable_fraction --
-    the draw of engine_finish_move_kernel in numpy (include/aqgnn.h, "resignation").  k may be an array of game indices."""
-    from .agents import _mix64
-    G = np.uint64(_GOLDEN)
-    kk = np.asarray(k, dtype=np.int64).astype(np.uint64)
-    with np.errstate(over="ignore"):
-        key = _mix64(np.uint64(int(seed) & _MASK64) + G * (kk + np.uint64(1)))
-        z = _mix64(key + G)
-    u = (z >> np.uint64(11)).astype(np.float64) * (2.0 ** -53)
-    out = u >= float(disable_fraction)
-    return bool(out) if np.ndim(k) == 0 else out
-
-
-def _side_loses(game_result):
-    """bool [K, 2]: side s of game k (s = ply parity: 0 the first player) lost."""
-    z = np.asarray(game_result).astype(np.int64).reshape(-1)
-    return np.stack([z < 0, z > 0], axis=1)
-
-
-def resign_false_positives(resign_min, game_result, enabled, threshold):
-    """The calibration count over the DISABLED games (they were played to their rule end): (would_resign, false_positives,
-    eligible_sides) = the sides whose running minimum is below -threshold (f32), how many of those did not lose, and the number of
-    sides that did not lose.  resign_min [K, 2] f32, game_result [K] the first player's value, enabled [K] bool."""
-    lo = np.asarray(resign_min, dtype=np.float32).reshape(-1, 2)
-    off = ~np.asarray(enabled, dtype=bool).reshape(-1)
-    would = (lo < -np.float32(threshold)) & off[:, None]
-    fine = ~_side_loses(game_result) & off[:, None]
-    return int(would.sum()), int((would & fine).sum()), int(fine.sum())
-
-
-def suggest_resign_threshold(resign_min, game_result, enabled, max_false_positive, min_sides=None, min_threshold=0.05):
-    """The threshold that resigns the most while the false-positive rate of resign_false_positives -- of the played-out (disabled)
-    games' sides that would have resigned, the share that did not lose -- stays at or under `max_false_positive`.  The cut is
-    m < -T, so the candidates are T = -x for every distinct minimum x of those sides in [-1, -min_threshold), and T = min_threshold
-    itself: at T = -x exactly the sides with a minimum below x would have resigned (ties fall on one side of the cut together).  The
-    rate need not fall steadily as T grows, so every candidate is counted and the smallest T that qualifies wins -- the largest cut
-    value -T.  A candidate qualifies only if at least `min_sides` sides would have resigned at it (default max(20, ceil(1 / bound)):
-    with fewer than 1 / bound of them one false positive already exceeds the bound).  None when no candidate qualifies: too few sides
-    to say, or the network's lost-looking games are not lost (a network whose games end in draws never resigns)."""
-    bound = float(max_false_positive)
-    if not 0.0 <= bound < 1.0:
-        raise ValueError(f"max_false_positive must be in [0, 1), not {max_false_positive!r}")
-    floor = np.float32(min_threshold)
-    if not 0.0 < float(floor) <= 1.0:
-        raise ValueError(f"min_threshold must be in (0, 1], not {min_threshold!r}")
-    lo = np.asarray(resign_min, dtype=np.float32).reshape(-1, 2)
-    off = ~np.asarray(enabled, dtype=bool).reshape(-1)
-    every = np.sort(lo[np.broadcast_to(off[:, None], lo.shape)])
-    fine = np.sort(lo[~_side_loses(game_result) & off[:, None]])
-    if min_sides is None:
-        min_sides = max(20, int(np.ceil(1.0 / bound))) if bound > 0.0 else 20
-    cuts = np.unique(np.concatenate([every[every < -floor], np.asarray([-floor], dtype=np.float32)]))
-    would = np.searchsorted(every, cuts, side="left")              # sides with a minimum strictly below the cut
-    wrong = np.searchsorted(fine, cuts, side="left")
-    ok = (would >= max(1, int(min_sides))) & (wrong <= bound * would + 1e-9)
-    if not ok.any():
-        return None
-    return float(np.float32(-cuts[np.flatnonzero(ok)[-1]]))
-
-
-NODE_DTYPE = np.dtype([("w", "<f8"), ("p", "<f4"), ("action", "<u4"), ("n", "<i4"), ("kids", "<u4"), ("q", "<f4"), ("cp", "<f4")])
-assert NODE_DTYPE.itemsize == 32      # csrc/mcts_tree.hpp NodeRec
-
-
-def keep_subtree_reference(pool_records, node_count, child_index, keep_visits):
-    """The keep launch (csrc/mcts_reuse.hip) for one slot, in numpy.  pool_records: the slot's pool, NODE_DTYPE [cap] (or anything
-    of 32 bytes per record, e.g. float64 [cap, 4]); node_count: its used records; child_index: index of the chosen child in the root's
-    child block, < 0 = do not keep.  Returns (records, count, kept): kept is True iff the index names a child that is expanded with
-    n <= keep_visits; then records[:count] is the child's subtree re-rooted -- the child at 0 with a fresh root's action / p / cp, every
-    kept child block behind it in ascending order of its old first index, child ranges renamed -- and records[count:] is unspecified
-    (here: the input's).  Not kept: the input's records and count."""
-    src = np.ascontiguousarray(pool_records).view(NODE_DTYPE).reshape(-1)
-    out = src.copy()
-    count = min(int(node_count), src.shape[0])
-    idx = int(child_index)
-    if idx < 0 or count <= 1:
-        return out, int(node_count), False
-    rcnt, rfirst = int(src["kids"][0]) >> 24, int(src["kids"][0]) & 0xFFFFFF
-    if idx >= rcnt or rfirst < 1 or rfirst + rcnt > count:
-        return out, int(node_count), False
-    c = src[rfirst + idx]
-    ccnt, cfirst = int(c["kids"]) >> 24, int(c["kids"]) & 0xFFFFFF
-    if ccnt == 0 or int(c["n"]) > int(keep_visits) or cfirst < rfirst + rcnt or cfirst + ccnt > count:
-        return out, int(node_count), False
-    keep = np.zeros(count, dtype=bool)
-    keep[cfirst:cfirst + ccnt] = True
-    kids = src["kids"][:count].astype(np.int64)
-    for i in range(cfirst, count):            # a node's child block lies behind the node: one ascending pass decides every record
-        if keep[i] and kids[i] >> 24:
-            first, cnt = int(kids[i] & 0xFFFFFF), int(kids[i] >> 24)
-            assert first > i, "a child block lies behind its parent"
-            keep[first:min(first + cnt, count)] = True
-    new_index = np.cumsum(keep)               # 1-based among the kept records == the new index (0 is the new root)
-    old = np.nonzero(keep)[0]
-    moved = src[old].copy()
-    exp = (moved["kids"] >> 24) != 0
-    firsts = (moved["kids"][exp] & 0xFFFFFF).astype(np.int64)
-    moved["kids"][exp] = (new_index[firsts].astype(np.uint32) & 0xFFFFFF) | (moved["kids"][exp] & np.uint32(0xFF000000))
-    total = 1 + old.shape[0]
-    out[1:total] = moved
-    root = np.zeros((), dtype=NODE_DTYPE)
-    root["w"], root["n"], root["q"] = c["w"], c["n"], c["q"]
-    root["action"], root["kids"] = 0xFF, 1 | (ccnt << 24)
-    out[0] = root
-    return out, total, True
-
-
-def _mix64_int(z):
-    """The splitmix64 finaliser on a Python int (include/aqgnn.h)."""
-    z &= _MASK64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
-    return z ^ (z >> 31)
-
-
-_GOLDEN = 0x9E3779B97F4A7C15
-
-
-def default_root_noise_seed(seed):
-    """The noise seed of an engine that was given none: `seed` through the mixer.  NOT a linear map: the generator's stream of game
-    k is keyed by mix(noise_seed + GOLDEN * (k + 1)), so noise seeds that differ by a multiple of GOLDEN -- what any affine map of
-    consecutive engine seeds onto them risks -- would hand game k of one engine the stream of another game of the next."""
-    return _mix64_int((int(seed) & _MASK64) ^ 0x524F4F544E4F4953)
-
-
-def set_noise_seeds(seed, root_noise_seed, sizes, quotas):
-    """The noise seeds of MultiSetSelfPlay's sets (slots `sizes`, games `quotas`).  The sets' games are numbered through -- set i's
-    game k is game first_i + k of the whole engine -- and the numbering rides in the seed: the stream of game k under
-    base + GOLDEN * first is the stream of game first + k under base.  Every set has a seed of its own and no two games share one."""
-    base = default_root_noise_seed(seed) if root_noise_seed is None else int(root_noise_seed) & _MASK64
-    firsts = [sum(max(q, g) for q, g in zip(quotas[:i], sizes[:i])) for i in range(len(sizes))]
-    return [(base + _GOLDEN * f) & _MASK64 for f in firsts]
-
-
-def root_noise_stream_key(seed, k, ply):
-    """The 64-bit key of the noise stream of game k's root at `ply` under the noise seed `seed` (include/aqgnn.h: K(K(seed, k), ply))."""
-    return _mix64_int(_mix64_int(int(seed) + _GOLDEN * (int(k) + 1)) + _GOLDEN * (int(ply) + 1))
-
-
-def draw_root_noise(seed, k, ply, count, alpha, return_exhausted=False):
-    """The gamma variates g_0 .. g_{count-1} of the root of game k at ply `ply`, float64 [count] -- the generator of
-    engine_root_noise_kernel in numpy (the recipe is in include/aqgnn.h, "root exploration noise").  k may be an array of game
-    indices: the result is then [len(k), count].  Component i draws from its own sub-stream, so the first c components do not
-    depend on count.  return_exhausted: also return how many variates took the fallback of the capped rejection loop."""
-    from .agents import _mix64, _GOLDEN
-    G = np.uint64(_GOLDEN)
-
-    def key_of(base, b):
-        with np.errstate(over="ignore"):
-            return _mix64(base + G * (np.asarray(b, dtype=np.uint64) + np.uint64(1)))
-
-    def uniform(key, j):
-        with np.errstate(over="ignore"):
-            z = _mix64(key + G * np.uint64(j + 1))
-        return (z >> np.uint64(11)).astype(np.float64) * (2.0 ** -53)
-
-    scalar = np.ndim(k) == 0
-    kk = np.atleast_1d(np.asarray(k, dtype=np.int64)).astype(np.uint64)
-    root = np.asarray([root_noise_stream_key(seed, int(x), ply) for x in kk], dtype=np.uint64)
-    key = key_of(root[:, None], np.arange(int(count), dtype=np.uint64)[None, :])
-    alpha = float(np.float32(alpha))          # the struct field is f32
-    boost = alpha < 1.0
-    a = alpha + 1.0 if boost else alpha
-    d = a - 1.0 / 3.0
-    c = 1.0 / np.sqrt(9.0 * d)
-    val = np.full(key.shape, d, dtype=np.float64)
-    todo = np.ones(key.shape, dtype=bool)
-    for t in range(ROOT_NOISE_ATTEMPTS):
-        if not todo.any():
-            break
-        kt = key[todo]
-        u1, u2, u3 = uniform(kt, 1 + 3 * t), uniform(kt, 2 + 3 * t), uniform(kt, 3 + 3 * t)
-        x = np.sqrt(-2.0 * np.log(1.0 - u1)) * np.cos(2.0 * np.pi * u2)
-        v1 = 1.0 + c * x
-        ok = v1 > 0.0
-        v = np.where(ok, v1 * v1 * v1, 1.0)
-        ok &= np.log(1.0 - u3) < 0.5 * x * x + d - d * v + d * np.log(v)
-        idx = np.flatnonzero(todo.ravel())
-        val.ravel()[idx[ok]] = d * v[ok]
-        todo.ravel()[idx[ok]] = False
-    exhausted = int(todo.sum())
-    if boost:
-        val = val * np.power(1.0 - uniform(key, 0), 1.0 / alpha)
-    val = np.maximum(val, np.finfo(np.float64).tiny)
-    if scalar:
-        val = val[0]
-    return (val, exhausted) if return_exhausted else val
-
-
-def resign_stats_of(parts, threshold):
-    """resign_stats over the (resign_min, game_result, enabled, game_resigned, game_plies, game_done) tuples of one or more engines."""
-    lo, res, enabled, flag, plies, done = (np.concatenate([np.asarray(p[i]) for p in parts], 0) for i in range(6))
-    fin = done != 0
-    would, wrong, fine = resign_false_positives(lo[fin], res[fin], enabled[fin], threshold)
-    return dict(games=int(fin.sum()), games_resigned=int(flag[fin].astype(bool).sum()), plies=int(plies[fin].sum()),
-                disabled_games=int((~enabled[fin]).sum()), would_resign=would, false_positives=wrong,
-                false_positive_rate=wrong / would if would else 0.0, eligible_sides=fine)
-
-
-def suggest_from_arrays(parts, max_false_positive, **kw):
-    lo, res, enabled, _, _, done = (np.concatenate([np.asarray(p[i]) for p in parts], 0) for i in range(6))
-    fin = done != 0
-    return suggest_resign_threshold(lo[fin], res[fin], enabled[fin], max_false_positive, **kw)
+# The engine's companions, one concern per module, importable from this path as well: the tests, README.md and include/aqgnn.h
+# name them as engine.<name>.  counter_rng: the generator of csrc/counter_rng.hpp; selfplay_options: the option checks and the derived
+# seeds; device_reference: numpy statements of device code; resign_calibration: the resignation statistics; two_engine_match: the
+# match loop.
+from .counter_rng import GOLDEN as _GOLDEN, MASK64, mix64 as _mix64_int  # noqa: F401
+from .device_reference import NODE_DTYPE, draw_resign_enabled, draw_root_noise, keep_subtree_reference, root_noise_stream_key  # noqa: F401
+from .resign_calibration import resign_false_positives, resign_stats_of, suggest_from_arrays, suggest_resign_threshold  # noqa: F401
+from .selfplay_options import (ROOT_NOISE_ATTEMPTS, check_resign, check_root_noise, check_target_options,  # noqa: F401
+                               check_tree_reuse, default_resign_seed, default_root_noise_alpha, default_root_noise_seed, set_noise_seeds)
+from .two_engine_match import TwoEngineMatch  # noqa: F401
 
 
 class BatchedSelfPlay:
@@ -365,13 +68,13 @@ class BatchedSelfPlay:
         minimum of that maximum per side, so resign_stats() can count false positives and suggest_resign_threshold() can pick T.
         T = 1.0 never resigns and only collects.  apply_actions() and search() refuse the option."""
         self.resign_options = check_resign(resign_threshold, resign_min_ply, resign_disable_fraction, record_history)
-        self.resign_seed = default_resign_seed(seed) if resign_seed is None else int(resign_seed) & _MASK64
+        self.resign_seed = default_resign_seed(seed) if resign_seed is None else int(resign_seed) & MASK64
         self.keep_visits = check_tree_reuse(tree_reuse, tree_reuse_visits, sims, evaluator)
         self.tree_reuse = self.keep_visits is not None
         self.temperature_plies, self.record_search_value = check_target_options(temperature_plies, record_search_value, record_history)
         self.root_noise_eps, self.root_noise_alpha = check_root_noise(
             root_noise_eps, default_root_noise_alpha(board_size) if root_noise_alpha is None else root_noise_alpha)
-        self.root_noise_seed = default_root_noise_seed(seed) if root_noise_seed is None else int(root_noise_seed) & _MASK64
+        self.root_noise_seed = default_root_noise_seed(seed) if root_noise_seed is None else int(root_noise_seed) & MASK64
         b = self.binding = BINDINGS[evaluator]
         b.check(model)          # before anything is allocated or launched
         self.dev = _lib.require_gpu(device)
@@ -459,16 +162,7 @@ class BatchedSelfPlay:
         e.max_plies = hp if record_history else 0
         e.prior_mode = b.prior_mode
         e.c_puct, e.temperature = float(c_puct), float(temperature)
-        for name in ("node_rec", "node_count", "root_state", "path",
-                     "path_len", "leaf_flag", "leaf_state", "game_active", "slot_game", "game_plies", "game_result", "game_done",
-                     "game_slot", "game_first_move", "legal_order",
-                     "legal_count", "pooled", "policy", "value", "hist_state72", "hist_visits", "hist_action", "counters",
-                     "stat_leaf_evals", "stat_terminal_sims", "packed_weights"):
-            setattr(e, name, t[name].data_ptr())
-        e.gnn_workspace = t["gnn_workspace"].data_ptr() if "gnn_workspace" in t else None
         if self.eval_cache_slots:
-            for name in ("eval_cache_keys", "eval_cache_rows", "eval_cache_slot", "eval_mask", "stat_cache_hits", "eval_list", "eval_count"):
-                setattr(e, name, t[name].data_ptr())
             e.eval_cache_log2 = self.eval_cache_slots.bit_length() - 1
         e.root_noise_eps, e.root_noise_alpha = self.root_noise_eps, self.root_noise_alpha
         e.root_noise_seed = self.root_noise_seed if self.root_noise_eps else 0      # off: the four fields are zero
@@ -478,10 +172,8 @@ class BatchedSelfPlay:
             t["child_index"] = torch.full((G,), -1, dtype=torch.int32, device=dev)
             t["stat_moves_kept"] = z((G,), torch.int32)
             t["stat_visits_kept"] = z((G,), torch.int32)
-            ru = self.reuse = _lib.TreeReuseStruct()
-            ru.keep_visits = self.keep_visits
-            for name in ("kept", "child_index", "stat_moves_kept", "stat_visits_kept"):
-                setattr(ru, name, t[name].data_ptr())
+            self.reuse = _lib.TreeReuseStruct()
+            self.reuse.keep_visits = self.keep_visits
         self.resign = None
         if self.resign_options:
             t["resign_min"] = torch.full((Q, 2), float("inf"), dtype=torch.float32, device=dev)
@@ -489,7 +181,12 @@ class BatchedSelfPlay:
             rs = self.resign = _lib.ResignStruct()
             rs.threshold, rs.min_ply, rs.disable_fraction = self.resign_options
             rs.seed = self.resign_seed
-            rs.resign_min, rs.game_resigned = t["resign_min"].data_ptr(), t["game_resigned"].data_ptr()
+        # every tensor is pointed at the struct field of its name (hist_value has none: it is an argument of the move; an absent
+        # tensor -- gnn_workspace, the cache's -- leaves its field NULL)
+        for name, tensor in t.items():
+            for struct in (e, self.reuse, self.resign):
+                if hasattr(struct, name):
+                    setattr(struct, name, tensor.data_ptr())
         self.record_history = record_history
         self.moves_done = 0
         self.reset()
@@ -584,30 +281,22 @@ class BatchedSelfPlay:
         else:
             uniforms = torch.as_tensor(uniforms, dtype=torch.float64).to(self.dev).contiguous()
         self._u = uniforms  # keep alive until the stream has consumed it
-        targets = self.temperature_plies or self.record_search_value          # either option: the _targets entry points
-        extra = (self.temperature_plies, _lib.ptr(self.t.get("hist_value")))
-        if self.evaluator == "external":
-            self._external_sims()
-            if self.resign is not None:
-                _lib.check(self.lib.aqg_engine_finish_move_resign(ctypes.byref(self.e), _lib.ptr(uniforms), *extra, None,
-                                                                  ctypes.byref(self.resign), self._stream()), "aqg_engine_finish_move_resign")
-            elif targets:
-                _lib.check(self.lib.aqg_engine_finish_move_targets(ctypes.byref(self.e), _lib.ptr(uniforms), *extra, self._stream()),
-                           "aqg_engine_finish_move_targets")
-            else:
-                _lib.check(self.lib.aqg_engine_finish_move(ctypes.byref(self.e), _lib.ptr(uniforms), self._stream()), "aqg_engine_finish_move")
-        elif self.resign is not None:
-            _lib.check(self.lib.aqg_engine_move_resign(ctypes.byref(self.e), _lib.ptr(uniforms), *extra,
-                                                       ctypes.byref(self.reuse) if self.tree_reuse else None, ctypes.byref(self.resign),
-                                                       self._stream()), "aqg_engine_move_resign")
+        # the entry point and what follows the uniforms: the plain form while every option is off, else the first form that takes
+        # all that is on -- resignation's takes a tree-reuse struct or none, tree reuse's takes the targets, and so does _targets
+        external = self.evaluator == "external"                  # (check_tree_reuse: never with tree reuse)
+        tail = [self.temperature_plies, _lib.ptr(self.t.get("hist_value"))]
+        if self.resign is not None:
+            form, tail = "_resign", tail + [ctypes.byref(self.reuse) if self.tree_reuse else None, ctypes.byref(self.resign)]
         elif self.tree_reuse:
-            _lib.check(self.lib.aqg_engine_move_reuse(ctypes.byref(self.e), _lib.ptr(uniforms), *extra, ctypes.byref(self.reuse), self._stream()),
-                       "aqg_engine_move_reuse")
-        elif targets:
-            _lib.check(self.lib.aqg_engine_move_targets(ctypes.byref(self.e), _lib.ptr(uniforms), *extra, self._stream()),
-                       "aqg_engine_move_targets")
+            form, tail = "_reuse", tail + [ctypes.byref(self.reuse)]
+        elif self.temperature_plies or self.record_search_value:
+            form = "_targets"
         else:
-            _lib.check(self.lib.aqg_engine_move(ctypes.byref(self.e), _lib.ptr(uniforms), self._stream()), "aqg_engine_move")
+            form, tail = "", []
+        name = ("aqg_engine_finish_move" if external else "aqg_engine_move") + form
+        if external:
+            self._external_sims()
+        _lib.check(getattr(self.lib, name)(ctypes.byref(self.e), _lib.ptr(uniforms), *tail, self._stream()), name)
         self.moves_done += 1
 
     # ------------------------------------------------------------------ moves the engine does not search (evaluate_agents.py)
@@ -953,10 +642,9 @@ class MultiSetSelfPlay:
                     break
         return self.counters()
 
-    def history_tensors(self):
-        parts = []
-        for _, eng in self._each():
-            parts.append(eng.history_tensors())
+    def _joined(self, get):
+        """get(set) -- a tuple of tensors -- on every set's stream, joined in set order on the current stream."""
+        parts = [get(eng) for _, eng in self._each()]
         self.sync()
         cur = torch.cuda.current_stream(self.dev)
         for st in self.streams:
@@ -964,61 +652,14 @@ class MultiSetSelfPlay:
         for p in parts:
             for x in p:
                 x.record_stream(cur)              # the caching allocator must not recycle them under the concatenation
-        return tuple(torch.cat([p[j] for p in parts], 0) for j in range(3))
+        return tuple(torch.cat(col, 0) for col in zip(*parts))
+
+    def history_tensors(self):
+        return self._joined(lambda eng: eng.history_tensors())
 
     def history_values(self):
         """The sets' history_values() in set order: float32 [P], row-aligned with history_tensors()."""
-        parts = []
-        for _, eng in self._each():
-            parts.append(eng.history_values())
-        self.sync()
-        cur = torch.cuda.current_stream(self.dev)
-        for st in self.streams:
-            cur.wait_stream(st)
-        for p in parts:
-            p.record_stream(cur)
-        return torch.cat(parts, 0)
-
-
-class TwoEngineMatch:
-    """`num_games` games between two sides, game i with side (i % 2) moving first, on two engines: engine `first` holds the games
-    in which side `first` moves first.  The loop of evaluate_network.BatchedMatch and evaluate_agents.BatchedAgentMatch; a subclass
-    says how an engine is built (`_engine(first, **kw)`) and how engine `first` makes ply `ply` (`_ply(eng, first, ply, *draws)`)."""
-
-    def _build_engines(self, num_games, seed, **kw):
-        self.num_games = int(num_games)
-        counts = [(self.num_games + 1) // 2, self.num_games // 2]          # games with side 0 first / side 1 first
-        self.engines = [self._engine(first, num_games=g, seed=2 * int(seed) + first, **kw) if g else None
-                        for first, g in enumerate(counts)]
-
-    def _switch_to_exact_kernels(self):
-        for eng in filter(None, self.engines):
-            eng.switch_to_exact_kernels()
-
-    def _play(self, *draws):
-        """Play every game to the end; side 0's points per game in game order.  fp16-range guard: the counters are read after every
-        ply anyway; if a split-kernel launch met a value outside fp16 range (counters()['gnn_saturated']) the moves so far were searched
-        with clamped evaluations, so every evaluation switches to the exact f32-input kernels and the match is replayed from ply 0."""
-        live = [e is not None for e in self.engines]
-        ply = 0
-        while any(live):
-            for first, eng in enumerate(self.engines):      # every live engine moves ...
-                if live[first]:
-                    self._ply(eng, first, ply, *draws)
-            ply += 1
-            for first, eng in enumerate(self.engines):      # ... before any counter is read: the host does not serialise the two
-                if not live[first]:
-                    continue
-                c = eng.counters()
-                if eng.binding.guarded and c["gnn_saturated"] and not (eng.e.gnn_flags & _lib.GNN_EXACT_F32):
-                    self._switch_to_exact_kernels()
-                    return self._play(*draws)               # (once: the exact kernels have no guard to fire)
-                if c["active"] == 0 or ply >= eng.max_plies:
-                    live[first] = False
-        # the first mover's result, +1 / -1 / 0, of every game of each engine
-        z0 = [np.zeros((0,)) if eng is None else eng.t["game_result"].cpu().numpy().astype(np.float64) for eng in self.engines]
-        per = [(z0[0] + 1.0) / 2.0, 1.0 - (z0[1] + 1.0) / 2.0]      # first_player_point, as side 0's (evaluate_network.py:71-74)
-        return [float(per[i % 2][i // 2]) for i in range(self.num_games)]
+        return self._joined(lambda eng: (eng.history_values(),))[0]
 
 
 def gather_history(states72, visits, z, group=None, force_collective=None, values=None):

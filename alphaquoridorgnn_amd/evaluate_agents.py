@@ -17,9 +17,11 @@ import torch
 from . import agents, constants
 from . import pv_mcts
 from .constants import BOARD_SIZE, board_params
-from .engine import BatchedSelfPlay, TwoEngineMatch, refuse_resign, refuse_root_noise, refuse_tree_reuse
+from .engine import BatchedSelfPlay
 from .evaluators import BINDINGS
 from .game_logic import State
+from .selfplay_options import refuse_self_play_options
+from .two_engine_match import TwoEngineMatch
 
 EP_GAME_COUNT = 10  # Number of games per evaluation (evaluate_agents.py:15)
 
@@ -80,10 +82,9 @@ class BatchedAgentMatch(TwoEngineMatch):
                  tree_reuse=None, tree_reuse_visits=None, resign_threshold=None, resign_min_ply=None,
                  resign_disable_fraction=None, resign_seed=None):
         # (a strength measurement plays the network as it is: root exploration noise is a self-play option and is refused)
-        refuse_root_noise("BatchedAgentMatch", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
-        refuse_tree_reuse("BatchedAgentMatch", tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits)
-        refuse_resign("BatchedAgentMatch", resign_threshold=resign_threshold, resign_min_ply=resign_min_ply,
-                      resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
+        refuse_self_play_options("BatchedAgentMatch", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed,
+                                 tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits, resign_threshold=resign_threshold,
+                                 resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
         if not callable(agent) and agent not in AGENTS:
             raise ValueError(f"agent must be one of {AGENTS} or a callable state -> action")
         if evaluator not in BINDINGS:
@@ -176,10 +177,9 @@ def evaluate_best_player(games=None, agents=AGENTS, seed=None, root_noise_eps=No
     """Evaluation of the best player (evaluate_agents.py:62-89): best.pth -- a GNN of any shape or the residual CNN, on the board its
     policy head is sized for -- against each of `agents`, `games` games each (default EP_GAME_COUNT), all games of a match at once.
     Prints the reference's lines (label, average point) and returns {label: average point}."""
-    refuse_root_noise("evaluate_best_player", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
-    refuse_tree_reuse("evaluate_best_player", tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits)
-    refuse_resign("evaluate_best_player", resign_threshold=resign_threshold, resign_min_ply=resign_min_ply,
-                  resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
+    refuse_self_play_options("evaluate_best_player", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed,
+                             tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits, resign_threshold=resign_threshold,
+                             resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
     from .pv_network_cnn import CNNNetwork
     from .pv_network_gnn import GNNNetwork, load_network
     games = EP_GAME_COUNT if games is None else int(games)

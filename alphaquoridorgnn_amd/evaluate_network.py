@@ -15,11 +15,13 @@ import torch
 from . import _lib
 from . import pv_mcts
 from .constants import PV_NETWORK_PATH, BOARD_SIZE
-from .engine import BatchedSelfPlay, TwoEngineMatch, refuse_resign, refuse_root_noise, refuse_tree_reuse
+from .engine import BatchedSelfPlay
 from .evaluators import BINDINGS
 from .game_logic import State
 from .pv_network_gnn import GNNNetwork, load_network
 from .pv_network_cnn import CNNNetwork
+from .selfplay_options import refuse_self_play_options
+from .two_engine_match import TwoEngineMatch
 
 EN_GAME_COUNT = 15    # Number of games per evaluation (evaluate_network.py:14; originally 400)
 EN_TEMPERATURE = 1.0  # Temperature of the Boltzmann distribution (evaluate_network.py:15)
@@ -61,10 +63,9 @@ class BatchedMatch(TwoEngineMatch):
                  tree_reuse=None, tree_reuse_visits=None, resign_threshold=None, resign_min_ply=None,
                  resign_disable_fraction=None, resign_seed=None):
         # (an evaluation match measures the networks as they are: root exploration noise is a self-play option and is refused)
-        refuse_root_noise("BatchedMatch", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
-        refuse_tree_reuse("BatchedMatch", tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits)
-        refuse_resign("BatchedMatch", resign_threshold=resign_threshold, resign_min_ply=resign_min_ply,
-                      resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
+        refuse_self_play_options("BatchedMatch", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed,
+                                 tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits, resign_threshold=resign_threshold,
+                                 resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
         if evaluator == "external":
             raise ValueError("BatchedMatch has no evaluator='external': an engine asks one model, eng.model, from the host")
         self.players, self.evaluator, self.binding = players, evaluator, BINDINGS[evaluator]
@@ -107,10 +108,9 @@ def evaluate_network(root_noise_eps=None, root_noise_alpha=None, root_noise_seed
     default 6/128/3 networks play on the engine's fused evaluator ('gnn'); when either file holds another shape, both play on
     its any-shape evaluator ('general').  Two CNNs (pv_network_cnn.py) play on the engine's CNN evaluator ('cnn'); a CNN against
     a GNN is refused (ValueError)."""
-    refuse_root_noise("evaluate_network", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
-    refuse_tree_reuse("evaluate_network", tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits)
-    refuse_resign("evaluate_network", resign_threshold=resign_threshold, resign_min_ply=resign_min_ply,
-                  resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
+    refuse_self_play_options("evaluate_network", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed,
+                             tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits, resign_threshold=resign_threshold,
+                             resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
     model0 = load_network(PV_NETWORK_PATH + 'latest.pth')
     model1 = load_network(PV_NETWORK_PATH + 'best.pth')
     cnn = [isinstance(m, CNNNetwork) for m in (model0, model1)]

@@ -50,10 +50,9 @@ def pv_mcts_policy_batch(model, states72, temperature, sims=None, board_size=Non
     the library's kernels), 'cnn' (the reference's CNNNetwork, pv_network_cnn.py, on the library's kernels), 'external'
     (model.predict per leaf) or 'fake'.  Every call searches caller-given roots from fresh trees: the self-play options that ask for
     tree reuse are refused (ValueError)."""
-    from .engine import refuse_resign, refuse_tree_reuse
-    refuse_tree_reuse("pv_mcts_policy_batch", tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits)
-    refuse_resign("pv_mcts_policy_batch", resign_threshold=resign_threshold, resign_min_ply=resign_min_ply,
-                  resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
+    from .selfplay_options import refuse_self_play_options
+    refuse_self_play_options("pv_mcts_policy_batch", tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits, resign_threshold=resign_threshold,
+                             resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
     states72 = torch.as_tensor(states72, dtype=torch.uint8)
     B = states72.shape[0]
     N = int(states72[0, 70]) if board_size is None else board_size
@@ -85,11 +84,10 @@ def pv_mcts_action(model, temperature=0, device='cpu', root_noise_eps=None, root
                    resign_disable_fraction=None, resign_seed=None):
     """Returns a function of the game state that selects an action based on PV-MCTS (pv_mcts.py:98-103).  A player for matches:
     it never adds root exploration noise, and the self-play options that ask for it are refused (ValueError)."""
-    from .engine import refuse_resign, refuse_root_noise, refuse_tree_reuse
-    refuse_root_noise("pv_mcts_action", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed)
-    refuse_tree_reuse("pv_mcts_action", tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits)
-    refuse_resign("pv_mcts_action", resign_threshold=resign_threshold, resign_min_ply=resign_min_ply,
-                  resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
+    from .selfplay_options import refuse_self_play_options
+    refuse_self_play_options("pv_mcts_action", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed,
+                             tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits, resign_threshold=resign_threshold,
+                             resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
     def pv_mcts_action(state):
         policy = pv_mcts_policy(model, state, temperature, device)
         return np.random.choice(state.legal_actions(), p=policy)

@@ -15,10 +15,11 @@ import torch
 from . import distributed as aqd
 from . import pv_mcts
 from .constants import PV_NETWORK_PATH, BOARD_SIZE
-from .engine import BatchedSelfPlay, MultiSetSelfPlay, gather_history, gather_resign_arrays, resign_stats_of, suggest_from_arrays
+from .engine import BatchedSelfPlay, MultiSetSelfPlay, gather_history, gather_resign_arrays
 from .pv_network_gnn import GNNNetwork, POLICY_OUTPUT_SIZE, load_network
 from .pv_network_cnn import CNNNetwork
 from .replay import blend_targets, check_value_blend
+from .resign_calibration import resign_stats_of, suggest_from_arrays
 
 SP_GAME_COUNT = 50    # Number of games for self-play (self_play.py:19; 25000 in the original version)
 SP_TEMPERATURE = 1.0  # Temperature parameter for Boltzmann distribution (self_play.py:20)

@@ -1,0 +1,116 @@
+"""The self-play options of the engine -- root noise, the target options, tree reuse, resignation -- on the host: their validation
+as the library does it, the seeds an engine derives when it is given none, and the one refusal of the paths that play no self-play."""
+import numpy as np
+
+from . import _lib
+from .counter_rng import GOLDEN, MASK64, mix64
+
+ROOT_NOISE_ATTEMPTS = 64      # cap of the gamma sampler's rejection loop (csrc/mcts_move.hip ROOT_NOISE_ATTEMPTS)
+
+
+def default_root_noise_alpha(board_size):
+    """The usual "10 / typical number of legal moves" rule, with the board's action count N^2 + 2 (N - 1)^2 for the moves."""
+    return 10.0 / (board_size ** 2 + 2 * (board_size - 1) ** 2)
+
+
+def check_root_noise(eps, alpha):
+    """Validate the root-noise options as the library does, on the f32 values its struct holds: eps in [0, 1); alpha in (0, 100]
+    when eps > 0.  Returns them as floats (alpha 0.0 when the noise is off)."""
+    eps = float(np.float32(eps))
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"root_noise_eps must be in [0, 1) as a float32, not {eps}")
+    if eps == 0.0:
+        return 0.0, 0.0
+    alpha = float(np.float32(alpha))
+    if not 0.0 < alpha <= 100.0:
+        raise ValueError(f"root_noise_alpha must be in (0, 100] as a float32, not {alpha}")
+    return eps, alpha
+
+
+def check_target_options(temperature_plies, record_search_value=False, record_history=True):
+    """Validate the self-play target options (include/aqgnn.h, "self-play targets"): temperature_plies an integer >= 0 (0 = off);
+    record_search_value needs the history it is a column of.  Returns (temperature_plies, record_search_value)."""
+    if isinstance(temperature_plies, bool) or int(temperature_plies) != temperature_plies or not 0 <= int(temperature_plies) < 2 ** 31:
+        raise ValueError(f"temperature_plies must be an integer >= 0, not {temperature_plies!r}")
+    if record_search_value and not record_history:
+        raise ValueError("record_search_value needs record_history: the search value is a column of the history")
+    return int(temperature_plies), bool(record_search_value)
+
+
+def check_tree_reuse(tree_reuse, tree_reuse_visits, sims, evaluator="gnn"):
+    """Validate the tree-reuse options as the library does (include/aqgnn.h, "tree reuse").  Returns keep_visits, or None when the
+    option is off.  tree_reuse_visits None = `sims`; 0 is legal: on, never keeps."""
+    if not tree_reuse:
+        if tree_reuse_visits is not None:
+            raise ValueError("tree_reuse_visits needs tree_reuse=True")
+        return None
+    if evaluator == "external":
+        raise ValueError("tree_reuse is not offered with evaluator='external': its host loop has no keep step")
+    keep = sims if tree_reuse_visits is None else tree_reuse_visits
+    if isinstance(keep, bool) or int(keep) != keep or int(keep) < 0:
+        raise ValueError(f"tree_reuse_visits must be an integer >= 0, not {tree_reuse_visits!r}")
+    keep = int(keep)
+    if keep + int(sims) > 32767:
+        raise ValueError("tree_reuse_visits + sims must be <= 32767: the visit row is read out as int16")
+    if 1 + (keep + int(sims)) * _lib.MAX_LEGAL >= 1 << 24:
+        raise ValueError("tree_reuse_visits + sims is too large: the tree pool must stay below 2**24 records")
+    return keep
+
+
+def check_resign(resign_threshold, resign_min_ply=0, resign_disable_fraction=0.1, record_history=True):
+    """Validate the resignation options as the library does (include/aqgnn.h, "resignation"), on the values its struct holds.
+    Returns (threshold, min_ply, disable_fraction), or None when the option is off (resign_threshold None).  A threshold of 1.0 is
+    legal: on, never resigns -- the statistics are still kept."""
+    if resign_threshold is None:
+        return None
+    if isinstance(resign_threshold, (bool, str)):
+        raise ValueError(f"resign_threshold must be a number in (0, 1], not {resign_threshold!r}")
+    thr = float(np.float32(resign_threshold))
+    if not 0.0 < thr <= 1.0:
+        raise ValueError(f"resign_threshold must be in (0, 1] as a float32, not {resign_threshold!r}")
+    if isinstance(resign_min_ply, bool) or int(resign_min_ply) != resign_min_ply or not 0 <= int(resign_min_ply) < 2 ** 31:
+        raise ValueError(f"resign_min_ply must be an integer >= 0, not {resign_min_ply!r}")
+    frac = float(resign_disable_fraction)
+    if not 0.0 <= frac <= 1.0:
+        raise ValueError(f"resign_disable_fraction must be in [0, 1], not {resign_disable_fraction!r}")
+    if not record_history:
+        raise ValueError("resignation needs record_history: a resigned game ends in a history row")
+    return thr, int(resign_min_ply), frac
+
+
+def default_root_noise_seed(seed):
+    """The noise seed of an engine that was given none: `seed` through the mixer.  NOT a linear map: the generator's stream of game
+    k is keyed by mix(noise_seed + GOLDEN * (k + 1)), so noise seeds that differ by a multiple of GOLDEN -- what any affine map of
+    consecutive engine seeds onto them risks -- would hand game k of one engine the stream of another game of the next."""
+    return mix64((int(seed) & MASK64) ^ 0x524F4F544E4F4953)
+
+
+def default_resign_seed(seed):
+    """The resignation seed of an engine that was given none: `seed` through the mixer (see default_root_noise_seed)."""
+    return mix64((int(seed) & MASK64) ^ 0x52455349474E4544)
+
+
+def set_noise_seeds(seed, root_noise_seed, sizes, quotas):
+    """The noise seeds of MultiSetSelfPlay's sets (slots `sizes`, games `quotas`).  The sets' games are numbered through -- set i's
+    game k is game first_i + k of the whole engine -- and the numbering rides in the seed: the stream of game k under
+    base + GOLDEN * first is the stream of game first + k under base.  Every set has a seed of its own and no two games share one."""
+    base = default_root_noise_seed(seed) if root_noise_seed is None else int(root_noise_seed) & MASK64
+    firsts = [sum(max(q, g) for q, g in zip(quotas[:i], sizes[:i])) for i in range(len(sizes))]
+    return [(base + GOLDEN * f) & MASK64 for f in firsts]
+
+
+# Matches, evaluation paths and single searches add no noise (they measure strength), search from a fresh tree every move (two
+# alternating searchers would need a two-ply descent into per-model trees) and play every game to its rule end.
+_NOISE, _REUSE, _RESIGN = "never adds root exploration noise", "never keeps a subtree between moves", "never resigns a game"
+SELF_PLAY_ONLY = {"root_noise_eps": _NOISE, "root_noise_alpha": _NOISE, "root_noise_seed": _NOISE,
+                  "tree_reuse": _REUSE, "tree_reuse_visits": _REUSE,
+                  "resign_threshold": _RESIGN, "resign_min_ply": _RESIGN, "resign_disable_fraction": _RESIGN, "resign_seed": _RESIGN}
+
+
+def refuse_self_play_options(what, **options):
+    """`what` is no self-play: a self-play option that is given (not None -- False and 0.0 are given) is a mistake, not something
+    to drop silently.  The groups are refused in the table's order, each with its own sentence."""
+    for sentence in dict.fromkeys(SELF_PLAY_ONLY.values()):
+        bad = sorted(k for k, v in options.items() if v is not None and SELF_PLAY_ONLY[k] == sentence)
+        if bad:
+            raise ValueError(f"{what} {sentence}: {', '.join(bad)} is a self-play option")

@@ -247,7 +247,7 @@ def _set_replay_options(args):
 def _set_target_options(args):
     """--temperature-plies / --value-blend onto self_play's constants, refused here if the engine or the append would refuse them."""
     from . import self_play as sp
-    from .engine import check_target_options
+    from .selfplay_options import check_target_options
     from .replay import check_value_blend
     if args.temperature_plies is not None:
         sp.SP_TEMPERATURE_PLIES = check_target_options(args.temperature_plies)[0]
@@ -258,7 +258,7 @@ def _set_target_options(args):
 def _set_tree_reuse_options(args):
     """--tree-reuse / --tree-reuse-visits onto self_play's constants, refused here if the engine would refuse them."""
     from . import pv_mcts, self_play as sp
-    from .engine import check_tree_reuse
+    from .selfplay_options import check_tree_reuse
     if args.tree_reuse or args.tree_reuse_visits is not None:
         check_tree_reuse(args.tree_reuse, args.tree_reuse_visits, pv_mcts.PV_EVALUATE_COUNT)
         sp.SP_TREE_REUSE, sp.SP_TREE_REUSE_VISITS = True, args.tree_reuse_visits
@@ -268,7 +268,7 @@ def _set_resign_options(args):
     """--resign-threshold / --resign-min-ply / --resign-max-false-positive / --slots onto self_play's constants, refused here if the
     engine would refuse them."""
     from . import self_play as sp
-    from .engine import check_resign
+    from .selfplay_options import check_resign
     if args.slots is not None:
         if args.slots < 1:
             raise ValueError("--slots must be >= 1")
