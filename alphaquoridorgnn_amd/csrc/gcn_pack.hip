@@ -140,8 +140,21 @@ int pack_weights_host(int N, const float* const* t, float* out) {
         for (int i = 0; i < HID * F; ++i) hi_finite = hi_finite && hi_ok(CQ * (double)t[0][i]);
         for (int i = 0; i < HID * HID; ++i) hi_finite = hi_finite && hi_ok((double)t[2][i] / CQ) && hi_ok((double)t[4][i] / CQ);
         const bool bound_ok = t2 > 0.0 && t2 == t2;
-        out[PackedLayout::GUARD + 0] = (hi_finite && bound_ok) ? (float)t2 : -1.0f;
-        out[PackedLayout::GUARD + 1] = hi_finite ? 65504.0f : -1.0f;
+        // The low side (split_mfma.hpp, SPLIT_MIN_PLANE_SCALE): each weight matrix the split kernels carry as hi / lo planes -- the
+        // three GCN layers, the hidden layer of each head on its own, policy_head.2 -- is held to 2^-25 ABSOLUTE once its lo halves
+        // are subnormal, whatever its own scale.  A matrix that is not all zero (that one is exact) and whose largest entry is
+        // below the scale gets the same negative thresholds.  Static, over the weights alone, like the test above; inputs that
+        // make a sanely scaled set's ACTIVATIONS small are for the calibration.
+        auto scale_ok = [](const float* w, size_t n) {
+            float m = 0.f;
+            for (size_t i = 0; i < n; ++i) m = std::max(m, std::fabs(w[i]));          // (a NaN is skipped: hi_finite has it)
+            return m == 0.f || m >= SPLIT_MIN_PLANE_SCALE;
+        };
+        const bool low_ok = scale_ok(t[0], (size_t)HID * F) && scale_ok(t[2], (size_t)HID * HID) && scale_ok(t[4], (size_t)HID * HID) &&
+                            scale_ok(t[6], (size_t)(HID / 2) * HID) && scale_ok(t[10], (size_t)(HID / 2) * HID) &&
+                            scale_ok(t[8], (size_t)A * (HID / 2));
+        out[PackedLayout::GUARD + 0] = (hi_finite && bound_ok && low_ok) ? (float)t2 : -1.0f;
+        out[PackedLayout::GUARD + 1] = (hi_finite && low_ok) ? 65504.0f : -1.0f;
         out[PackedLayout::GUARD + 2] = out[PackedLayout::GUARD + 3] = 0.f;
     }
     for (int u = 0; u < HID / 2; ++u)

@@ -46,7 +46,9 @@ struct PackedLayout {
     // (the bias of a node with `deg` neighbours incl. itself, pre-divided by its D^-1/2 factor; see the trunk comment)
     static constexpr size_t TB = WHP2 + 2 * 14 * 2 * 64 * 4;
     // range-guard thresholds of the tracking trunk build (GUARD_MODE 2): [0] = largest |U| of layer 2's linear map for which layer 2's
-    // aggregate provably stays below 65504, (65504 - max |TB_2|) / 2.07;  [1] = 65504 (layer 3's U is only split itself);  [2..3] spare
+    // aggregate provably stays below 65504, (65504 - max |TB_2|) / 2.07;  [1] = 65504 (layer 3's U is only split itself);  both are -1
+    // (no maximum satisfies them: every board is reported) for a set the split kernels cannot serve -- a weight outside fp16 range, or
+    // a split weight matrix below SPLIT_MIN_PLANE_SCALE;  [2..3] spare
     static constexpr size_t GUARD = TB + 3 * 5 * HID;
     static constexpr size_t TOTAL = GUARD + 4;
 };

@@ -26,10 +26,16 @@ namespace aqg {
 //                                    through 48 KB of LDS, lane-linear (form R of the backward pass)
 // so a layer costs 72 (linear) + 30 + 30 (both forms) MFMAs per wave going forward, and 72 (data gradient) + 60 + 72 (weight
 // gradient) going back; nothing is ever transposed.  ReLU masks are 24 bits per lane and layer, kept in registers.
-// Range: forward values are O(1); the backward pass is scaled per board by a power of two that puts max |dg| at 128..256 (the
-// gradients of a mean loss over 128 positions would otherwise sit in fp16's subnormals) and unscaled, exactly, at the stores of
-// the partial sums.  Every f32 value is range-checked before it is split; a board that meets |x| > 65504 anywhere is redone
-// by the exact-f32 body in the same launch (counted in g_train_fallbacks) -- the reference's fp32 has no such cliff.
+// Range: the backward pass is scaled per board by a power of two that puts max |dg| at 128..256 (the gradients of a mean loss over
+// 128 positions would otherwise sit in fp16's subnormals) and unscaled, exactly, at the stores of the partial sums.  Forward values
+// are NOT scaled: they are O(1) for weights of ordinary scale only.  Two checks send a board to the exact-f32 body in the same launch
+// (counted in g_train_fallbacks) -- the reference's fp32 has neither cliff:
+//   high side  every f32 value is range-checked before it is split; a board that meets |x| > 65504 anywhere is redone;
+//   low side   a block of a GCN weight matrix -- the 16 output features of one wave -- that is not all zero and whose largest entry
+//              is below SPLIT_MIN_TRAIN_SCALE (split_mfma.hpp: its lo halves are subnormal, it is carried to 2^-25 absolute
+//              whatever its own scale, and the ReLU masks of those features are decided by that error) counts as a value out of
+//              range -- a static test on the weights, so it redoes every board of the step.  Activations that are small under
+//              weights of ordinary scale are not tested.
 // ---------------------------------------------------------------------------------------------
 struct alignas(16) SplitSmem {
     alignas(16) unsigned char P[2][PPLANE];                 // fp16 hi / lo planes [node][feature]: H_l going forward, dZ_l going back
@@ -171,7 +177,8 @@ __device__ __attribute__((noinline)) void heads_board_call(unsigned int sm_lds, 
                 (float*)pol, (float*)vp, (float*)val, (float*)loss, (float*)dhp, (float*)dhv);
 }
 
-// returns false (to every thread of the workgroup) if a value left fp16 range: the caller redoes the board with the f32 body
+// returns false (to every thread of the workgroup) if a value left fp16 range or a block of weights sits below the split's scale
+// (header): the caller redoes the board with the f32 body
 __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict__ smem, const uint8_t* __restrict__ states72,
                                                        const int64_t* __restrict__ order, int first,
                                                        const TrunkParams& tp, const HeadParams& hpm, const float* __restrict__ pi_all,
@@ -190,6 +197,14 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
     const int col = 16 * wave + c;
     const float *W1 = tp.p[0], *b1 = tp.p[1], *W2 = tp.p[2], *b2 = tp.p[3], *W3 = tp.p[4], *b3 = tp.p[5];
     Rng mx;                                                            // range guard over everything this lane splits
+    // low side (header): m = the largest |entry| this lane holds of its wave's 16 rows of a GCN weight matrix.  Two ballots, nothing
+    // kept, no branch (one would end the block the weight loads are scheduled in): a block below the scale poisons the range
+    // guard's maximum, which also takes in m itself
+    auto weight_block_scale = [&](float m) {
+        const unsigned int none_at_scale = __builtin_amdgcn_ballot_w64(m >= SPLIT_MIN_TRAIN_SCALE) == 0 ? 1u : 0u;
+        const unsigned int some_nonzero = __builtin_amdgcn_ballot_w64(m > 0.f) != 0 ? 1u : 0u;
+        mx.m = fmaxf(mx.m, __builtin_bit_cast(float, (none_at_scale & some_nonzero) * 0x7f800000u) + m);      // + inf, or m itself
+    };
     TS_DECL
     // ---- loads that do not depend on the board: biases (both layouts), W1, W2 rows of this wave's columns
     const f32x4 bT1 = ld4(b1 + 16 * wave + 4 * q), bT2 = ld4(b2 + 16 * wave + 4 * q);
@@ -204,15 +219,17 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
     };
     u32x4 Bh[4], Bl[4];
     auto split_w = [&]() {
+        Rng wm;                                                         // the block's own maximum: the low-side test (header)
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
             const f32x4 a = wf[2 * kb], bb = wf[2 * kb + 1];
             Bh[kb] = (u32x4){cvt_pk_f16(a[0], a[1]), cvt_pk_f16(a[2], a[3]), cvt_pk_f16(bb[0], bb[1]), cvt_pk_f16(bb[2], bb[3])};
-            trk_after(mx, Bh[kb][0], a[0], a[1]); trk_after(mx, Bh[kb][1], a[2], a[3]);
-            trk_after(mx, Bh[kb][2], bb[0], bb[1]); trk_after(mx, Bh[kb][3], bb[2], bb[3]);
+            trk_after(wm, Bh[kb][0], a[0], a[1]); trk_after(wm, Bh[kb][1], a[2], a[3]);
+            trk_after(wm, Bh[kb][2], bb[0], bb[1]); trk_after(wm, Bh[kb][3], bb[2], bb[3]);
             Bl[kb] = (u32x4){lo_pair(Bh[kb][0], a[0], a[1]), lo_pair(Bh[kb][1], a[2], a[3]), lo_pair(Bh[kb][2], bb[0], bb[1]), lo_pair(Bh[kb][3], bb[2], bb[3])};
             mfma_fence(Bl[kb]);
         }
+        weight_block_scale(wm.m);
     };
     request_w(W2);
     // (warming the heads' matrices into this XCD's L2 from here -- one load per 64-byte line, as the f32 body does -- measured 6 % SLOWER
@@ -282,6 +299,9 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
         u32x4 w1h = {cvt_pk_f16(w1v[0], w1v[1]), cvt_pk_f16(w1v[2], w1v[3]), cvt_pk_f16(w1v[4], w1v[5]), 0u};
         u32x4 w1l = {lo_pair(w1h[0], w1v[0], w1v[1]), lo_pair(w1h[1], w1v[2], w1v[3]), lo_pair(w1h[2], w1v[4], w1v[5]), 0u};
         mfma_fence(w1l);
+        Rng w1m;
+        trk_after(w1m, w1h[0], w1v[0], w1v[1]); trk_after(w1m, w1h[1], w1v[2], w1v[3]); trk_after(w1m, w1h[2], w1v[4], w1v[5]);
+        weight_block_scale(w1m.m);
 #pragma unroll
         for (int m = 0; m < 6; ++m) {
             u32x4 xa = *reinterpret_cast<const u32x4*>(&sm.X0A[m < 5 ? 16 * m + c : 80][0]);

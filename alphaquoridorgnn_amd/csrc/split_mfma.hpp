@@ -14,7 +14,24 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int PROW = 256;                    // plane row = 128 fp16, unpadded: 16 slots of 16 B, XOR-swizzled by the row
+// The low side of the pair.  lo is a normal fp16 number only while |x| >= 2^-3 (|lo| <= 2^-11 |x| against fp16's smallest normal
+// 2^-14); below that lo is a subnormal with spacing 2^-24, and the pair's ABSOLUTE error stops shrinking at 2^-25 whatever |x| is.
+// A whole operand matrix whose largest entry is m is therefore carried to 2^-25 / m of its own scale: 2^-21.5 at initialisation
+// scale (m ~ 2^-3.5), and past the 1e-5 / 1e-4 bar of the forward pass once m falls below about 2^-11 (the numpy statement of the
+// split in tests/test_split_low_side_cpu.py derives the figures).  A split weight matrix whose largest entry is non-zero and below
+// this scale -- where that arithmetic still has the split within a third of the bar -- is not split: the packed set is served by the exact kernels
+// (gcn_pack.hip, negative GUARD thresholds).
+constexpr float SPLIT_MIN_PLANE_SCALE = 0x1p-8f;
+// The training step needs more.  Its backward pass is gated by the SIGNS of the pre-activations, and a pre-activation shrinks with
+// its layer while the split's absolute error (~2^-25 x the row sums, ~3e-8) does not: scaled down by 2^-k, the ReLU branches of
+// pre-activations within 3e-8 x 2^k of zero are decided by the split, not by the network -- a whole element of the gradient each,
+// where f32's error shrinks with the layer.  Measured on the rescaled networks of tests/test_split_low_side.py, batch 48
+// (profiles/split_low_side.log): gradients within 0.08 of the 2e-5 max|g| bar through k = 3, 0.9 at k = 4, 50 x the bar at k = 5.
+// A step in which the 16 output features of one wave have, in a GCN weight matrix, a largest entry that is non-zero and below this
+// scale (k = 4 at initialisation scale, 2^-2.3 .. 2^-2.7) is redone by the f32 body (gcn_train_split.hip).
+constexpr float SPLIT_MIN_TRAIN_SCALE = 0x1p-6f;
+
+constexpr int PROW = 256;                   // plane row = 128 fp16, unpadded: 16 slots of 16 B, XOR-swizzled by the row
 constexpr int PPLANE = 81 * PROW;            // plane stride (20,736 B)
 // Byte offset of 16-byte slot `slot` (0..15) of plane row `row`: slot ^ (row & 15).  The 16 rows an A-fragment
 // ds_read_b128 lane group touches (same slot, rows 16m + 0..15) land on 16 distinct bank slots, and so do the 16 rows of

@@ -424,6 +424,14 @@ class GNNTrainer(_Trainer):
     def _batch_losses(self, B):
         return self.ws["loss"][:B].mean(dim=0)
 
+    def positions_redone_in_f32(self, reset=False):
+        """How many positions the split-precision step (9x9, train_fused 2) has handed to its f32 body since the count was last reset
+        (aqg_gcn_train_fallbacks; one count per process, not per trainer).  Zero for weights of ordinary scale.  A count that grows
+        by the batch size every step means the weights left the split's range -- a value beyond 65504, or 16 consecutive output
+        features of a GCN layer with no weight of 2^-6 or more, as weight decay can leave them -- and every step runs both bodies:
+        correct, and about twice the time.  One host read (a device synchronise)."""
+        return int(self.lib.aqg_gcn_train_fallbacks(1 if reset else 0))
+
     def _updated(self):
         self.model.invalidate_packed()
 

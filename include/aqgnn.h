@@ -109,7 +109,10 @@ int aqg_state_status(int board_size, const uint8_t* states72, int B, int plies_f
  *   GUARD [4]    thresholds of the trunk's fp16-range guard on the linear maps' outputs: [0] = (65504 - max |TB of layer 2|) / 2.07
  *                (below it layer 2's aggregate provably stays under 65504), [1] = 65504, [2..3] spare (ABI 8: the last four floats);
  *                both are -1 (no maximum passes: every board is reported) when a trunk weight's fp16 hi half is not finite
- *                (|W| (16/15) >= 65504, inf or NaN)
+ *                (|W| (16/15) >= 65504, inf or NaN), or when a weight matrix that travels as hi/lo planes (gcn_layers.0/1/2,
+ *                policy_head.0, value_head.0, policy_head.2; each on its own) is not all zero and has no entry of magnitude 2^-8 or
+ *                more: its lo halves are fp16 subnormals and it would be carried to 2^-25 absolute, whatever its own scale
+ *                (same layout, same ABI number: only the values of [0] and [1] for such sets changed)
  * aqg_gcn_packed_floats() returns the total; aqg_gcn_pack_weights_host() fills a HOST buffer from the 14
  * state_dict tensors given as HOST float32 pointers in the key order of KEYS in INTEGRATION.md. */
 size_t aqg_gcn_packed_floats(int board_size);
@@ -127,9 +130,17 @@ int aqg_gcn_pack_weights_host(int board_size, const float* const* tensors_host, 
  *   value     [B]      Tanh output == module output (may be NULL)
  * state_fmt: 0 = state72 records, 1 = 24-byte packed QState (engine-internal).
  * flags: AQG_GNN_EXACT_F32 forces the exact f32-input MFMA trunk and the f32 heads for this call whatever "trunk_variant" says.
- *   The fp16-split kernels hold every activation as two fp16 numbers: they are fp32-equivalent while all activations stay
- *   inside fp16 range (|x| < 65504 -- true for any sanely scaled network, saturating instead of overflowing beyond), and the
- *   host wrapper checks each weight set once against the exact kernels on calibration boards and sets this flag when they
+ *   The fp16-split kernels hold every weight and activation as two fp16 numbers, hi + lo.  That is fp32-equivalent while the
+ *   values stay inside fp16 range (|x| < 65504, saturating instead of overflowing beyond) AND the lo halves stay normal fp16
+ *   numbers: a value below 2^-3 has a subnormal lo and is carried to 2^-25 absolute, so a matrix or an activation image whose whole
+ *   scale is m is carried to 2^-25 / m of it -- fp32-equivalent at m ~ 1, past the stated tolerance (atol 1e-5, rtol 1e-4) below
+ *   m ~ 2^-11.  Both hold for a network of ordinary scale, neither for every network the reference's fp32 serves (a ReLU network
+ *   computes the same function with one layer scaled down and the next scaled up).  The packing refuses weight matrices below
+ *   2^-8 (GUARD above).  That test looks at the LARGEST entry only: a matrix that is tiny but for one entry of 2^-8 passes it, and
+ *   neither such a matrix nor small ACTIVATIONS under weights of ordinary scale have a run-time signal -- a raw caller of the guarded
+ *   entry gets none.  (The split training step applies the same kind of test, at 2^-6 per block of 16 output features of a GCN
+ *   matrix, with the same blind spot and nothing behind it.)  For the forward pass the host wrapper checks each
+ *   weight set once against the exact kernels on calibration boards, at the stated tolerance taken relative to each board's output scale, and sets this flag when they
  *   disagree (pv_network_gnn.GraphPolicyValueNetwork.packed_weights). */
 #define AQG_GNN_EXACT_F32 1
 /* AQG_GNN_RANGE_PROVEN (with a non-NULL `saturated` word, ignored together with AQG_GNN_EXACT_F32): the caller has PROVEN -- by a
@@ -149,7 +160,9 @@ int aqg_gcn_forward_boards(int board_size, const void* states, int state_fmt, in
 /* The same call with the runtime fp16-range guard: `saturated` (device int32, may be NULL) is OR-ed with 1 by any fp16-split
  * kernel of the call that met a value it cannot hold as an fp16 pair -- a linear-map output or a post-ReLU activation beyond
  * 65504 (the activation is clamped there, never inf / NaN), a pooled feature or head hidden unit beyond it -- or could not rule one
- * out (the trunk bounds layer 2's aggregate by its linear map's output: a linear-map output beyond GUARD[0], about 31,600, is reported).  The results of such
+ * out (the trunk bounds layer 2's aggregate by its linear map's output: a linear-map output beyond GUARD[0], about 31,600, is reported;
+ * a weight set the packing refused -- a matrix outside fp16 range, or below the split's scale on the low side -- has negative GUARD
+ * thresholds, and every board of it is reported).  The results of such
  * a call are finite but not the network's: the caller repeats it with AQG_GNN_EXACT_F32 and keeps that flag for the weight set
  * (GraphPolicyValueNetwork.forward_states / predict do; the engine reports the same event in counters[5]).  The word is never
  * cleared by the library.  Exact-f32 calls never set it.  Reference behaviour: fp32 throughout, no cliff (pv_network_gnn.py:53-64). */
