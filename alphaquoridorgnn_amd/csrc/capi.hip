@@ -283,6 +283,10 @@ int aqg_engine_root_priors(const aqg_engine* e, float* priors, int32_t* count, v
     if (!e || !priors || !count) return fail("aqg_engine_root_priors: null argument");
     return engine_root_priors(*e, priors, count, (hipStream_t)stream);
 }
+int aqg_engine_root_values(const aqg_engine* e, float* value, void* stream) {
+    if (!e || !value) return fail("aqg_engine_root_values: null argument");
+    return engine_root_values(*e, value, (hipStream_t)stream);
+}
 
 int aqg_engine_root_states72(const aqg_engine* e, uint8_t* out72, void* stream) {
     if (!e || !out72) return fail("aqg_engine_root_states72: null argument");
@@ -529,6 +533,12 @@ int aqg_replay_append_blend(int board_size, int policy_size, const uint8_t* stat
                             float* ring_z, void* stream) {
     return launch_replay_append_blend(board_size, policy_size, states72, visits, z_i8, search_value, blend, n, capacity, head, ring72,
                                       ring_pi, ring_z, (hipStream_t)stream);
+}
+int aqg_replay_refresh(int board_size, int policy_size, const int32_t* visits, const uint8_t* actions, const int32_t* count,
+                       const float* search_value, float blend, const int64_t* slots, int n, int capacity, float* ring_pi,
+                       float* ring_z, void* stream) {
+    return launch_replay_refresh(board_size, policy_size, visits, actions, count, search_value, blend, slots, n, capacity, ring_pi,
+                                 ring_z, (hipStream_t)stream);
 }
 
 int aqg_replay_position_keys(const uint8_t* states72, const int64_t* index, int n, int64_t* keys, void* stream) {

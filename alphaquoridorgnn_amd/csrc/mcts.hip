@@ -333,6 +333,12 @@ int engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipSt
     return check_launch("engine_root_priors_kernel");
 }
 
+int engine_root_values(const aqg_engine& e, float* value, hipStream_t st) {
+    if (int r = validate(e)) return r;
+    launch_engine_root_values(e, value, st);
+    return check_launch("engine_root_values_kernel");
+}
+
 // the slot refill alone, for a move that was applied rather than searched (engine_apply_actions, mcts_move.hip)
 int engine_refill(const aqg_engine& e, hipStream_t st) {
     launch_engine_refill(e, st);

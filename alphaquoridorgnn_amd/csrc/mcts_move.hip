@@ -470,6 +470,16 @@ __global__ __launch_bounds__(256) void engine_root_priors_kernel(aqg_engine e, f
     if (lane == 0) count[g] = cnt;
 }
 
+// the root's search value from the mover's side, one lane per slot: the expression engine_finish_move_kernel stores into hist_value
+__global__ __launch_bounds__(256) void engine_root_values_kernel(aqg_engine e, float* __restrict__ value) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= e.num_games) return;
+    const NodeRec* __restrict__ nodes = game_nodes(e, g);
+    const double w = nodes[0].w;
+    const int n = nodes[0].n;
+    value[g] = n ? (float)(w / (double)n) : 0.0f;
+}
+
 // ------------------------------------------------------------------------------------------------
 // engine: the position of every slot, and a move the engine did not search
 // ------------------------------------------------------------------------------------------------
@@ -561,6 +571,10 @@ int launch_engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* act
 
 void launch_engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st) {
     hipLaunchKernelGGL(engine_root_priors_kernel, dim3((e.num_games + 3) / 4), dim3(256), 0, st, e, priors, count);
+}
+
+void launch_engine_root_values(const aqg_engine& e, float* value, hipStream_t st) {
+    hipLaunchKernelGGL(engine_root_values_kernel, dim3((e.num_games + 255) / 256), dim3(256), 0, st, e, value);
 }
 
 // the two entry points a "network vs agent" match needs, with their own argument checks: read every slot's position, apply a move

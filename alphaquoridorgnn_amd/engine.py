@@ -448,6 +448,13 @@ class BatchedSelfPlay:
                    "aqg_engine_root_priors")
         return priors, count
 
+    def root_values(self):
+        """The search value of every slot's root after the last search, float32 [G]: w / n of node 0 from the mover's side, the
+        expression a played move records as its search value (history_values); 0 for a root without a visit."""
+        value = torch.empty((self.G,), dtype=torch.float32, device=self.dev)
+        _lib.check(self.lib.aqg_engine_root_values(ctypes.byref(self.e), _lib.ptr(value), self._stream()), "aqg_engine_root_values")
+        return value
+
     # ------------------------------------------------------------------ history
     def _history_valid(self):
         """(valid bool [quota, hp], ply index [1, hp]): the recorded rows of the finished games."""

@@ -28,6 +28,12 @@ def _engine_for(model, num_games, sims, board_size, evaluator="gnn", fake_bias=0
     return eng
 
 
+def _drop_engine(eng):
+    """Forget a cached engine (reanalyse: its tree pool must not stay resident beside the next generation's self-play engine)."""
+    for key in [k for k, v in _engines.items() if v is eng]:
+        del _engines[key]
+
+
 def boltzman(xs, temperature):
     """Boltzmann distribution (pv_mcts.py:106-109)."""
     xs = [x ** (1 / temperature) for x in xs]

@@ -17,6 +17,10 @@ Position merge (`ReplayWindow.merged()`, `merge_positions`; csrc/replay_merge.hi
 position -- every game's opening, and on the small boards many plies after it, thousands of times.  Merged, each distinct position is
 one row whose targets are the mean of its occurrences' (each position then weighs the same; `count` is returned for another
 weighting).  A position and its left-right mirror are NOT merged.  `merge_reference` and `position_keys` are the statements in numpy.
+
+Reanalyse (`ReplayWindow.refresh_counts`, aqg_replay_refresh, csrc/replay_refresh.hip; the stage is reanalyse.reanalyse): the targets
+of chosen valid rows overwritten, in one launch, by the results of a fresh search of their positions.  `refresh_reference` is the
+kernel in numpy, `draw_reanalyse_rows` picks the rows of one pass.
 """
 import pickle
 
@@ -95,6 +99,67 @@ def append_reference(board_size, states72, visits, z_i8, pi, z_f32, head, ring72
     else:
         ring_pi[slots] = pi
         ring_z[slots] = z_f32
+
+
+# ---- reanalyse: chosen slots' targets overwritten by fresh search results (csrc/replay_refresh.hip)
+
+def refresh_reference(board_size, visits, actions, count, search_value, blend, slots, ring_pi, ring_z):
+    """aqg_replay_refresh in numpy, on host arrays, in place (include/aqgnn.h, "reanalyse") -- the kernel's statement and the backend
+    of a host window.  Source row i is a searched root as engine.search returns it: visits int32 [n,MAX_LEGAL] and actions uint8
+    [n,MAX_LEGAL] in legal_actions() order, count int32 [n]; slots int64 [n], distinct.  With c = count[i] and tot = the sum of
+    visits[i, :c]: a row with c <= 0, c > MAX_LEGAL, tot <= 0 or a slot outside the ring is skipped; otherwise the whole row
+    ring_pi[slots[i]] becomes zeros with float32(float64(v_j) / float64(tot)) at actions[i, j], j < c (an action >= A is dropped).
+    search_value (float32 [n]) with blend L != 0: ring_z[slot] = blend_targets' arithmetic on the value the ring holds NOW --
+    keep * ring_z[slot] + L * search_value[i], keep = float32(1) - L, every operation rounded to f32; search_value None or L == 0:
+    ring_z is neither read nor written (and may be None).  Refuses what the C entry point refuses, with ValueError."""
+    if board_size not in (3, 5, 7, 9):
+        raise ValueError("refresh_reference: unsupported board_size (odd 3..9)")
+    A = policy_size(board_size)
+    b = np.float32(check_value_blend(blend))
+    if search_value is None and b != 0:
+        raise ValueError("refresh_reference: a blend needs search_value")
+    blended = search_value is not None and b != 0
+    n, capacity = int(np.shape(slots)[0]), int(ring_pi.shape[0])
+    if capacity < 1:
+        raise ValueError("refresh_reference: capacity must be >= 1")
+    if blended and ring_z is None:
+        raise ValueError("refresh_reference: a blend needs ring_z")
+    for x, name, dtype, shape in ((visits, "visits", np.int32, (n, _lib.MAX_LEGAL)), (actions, "actions", np.uint8, (n, _lib.MAX_LEGAL)),
+                                  (count, "count", np.int32, (n,)), (slots, "slots", np.int64, (n,)),
+                                  (search_value, "search_value", np.float32, (n,)), (ring_pi, "ring_pi", np.float32, (capacity, A)),
+                                  (ring_z, "ring_z", np.float32, (capacity,))):
+        if x is not None and (x.dtype != dtype or tuple(x.shape) != shape):
+            raise ValueError(f"refresh_reference: {name} must be {np.dtype(dtype).name} {list(shape)} ({board_size}x{board_size} board)")
+    keep = np.float32(1.0) - b
+    for i in range(n):
+        c, slot = int(count[i]), int(slots[i])
+        if c <= 0 or c > _lib.MAX_LEGAL or not 0 <= slot < capacity:
+            continue
+        v = visits[i, :c].astype(np.int64)
+        tot = int(v.sum())
+        if tot <= 0:
+            continue
+        row = np.zeros((A,), dtype=np.float32)
+        inside = actions[i, :c] < A
+        row[actions[i, :c][inside]] = (v[inside].astype(np.float64) / np.float64(tot)).astype(np.float32)
+        ring_pi[slot] = row
+        if blended:
+            x, y = np.float32(keep * ring_z[slot]), np.float32(b * search_value[i])
+            ring_z[slot] = np.float32(x + y)
+
+
+def draw_reanalyse_rows(seed, update, eligible, rows):
+    """Which of the `eligible` oldest valid rows of a window one reanalyse pass refreshes: int64 positions in age order, ascending.
+    Row i's key is u_i = counter_uniform(stream_key(seed, update), i); the min(rows, eligible) rows of the smallest keys are taken
+    (stable argsort).  A row's key depends on (seed, update, i) alone -- not on how many rows are asked for, nor on rank or slot
+    count -- so the draw for R rows is a subset of the draw for R + 1, and every caller draws the same rows."""
+    from .counter_rng import counter_uniform, stream_key
+    eligible, rows = int(eligible), int(rows)
+    if eligible < 0 or rows < 0:
+        raise ValueError("draw_reanalyse_rows: eligible and rows must be >= 0")
+    keys = counter_uniform(stream_key(int(seed), int(update)), np.arange(eligible, dtype=np.uint64))
+    order = np.argsort(np.asarray(keys, dtype=np.float64).reshape(eligible), kind="stable")
+    return np.sort(order[:min(rows, eligible)]).astype(np.int64)
 
 
 # ---- position merge: rows that hold the same position become one row with the mean targets (csrc/replay_merge.hip)
@@ -294,6 +359,7 @@ class ReplayWindow:
         self._start = 0                 # slot of the oldest valid row
         self._valid = 0
         self._index = torch.zeros((0,), dtype=torch.int64, device=self.device)
+        self.reanalyse_updates = 0      # reanalyse passes self_play() has run on this window: the `update` of draw_reanalyse_rows
         if self.capacity is not None:
             self._allocate()
 
@@ -436,6 +502,56 @@ class ReplayWindow:
         self.append_rows(torch.from_numpy(pack_states(s, self.board_size)),
                          torch.tensor(np.array(p, dtype=np.float64).reshape(len(history), self.policy_size), dtype=torch.float32),
                          torch.tensor(np.array(v, dtype=np.float64).reshape(len(history)), dtype=torch.float32))
+
+    # ---- reanalyse
+    def refresh_counts(self, slots, visits, actions, count, search_value=None, value_blend=0.0):
+        """Overwrite the targets of the valid rows in ring slots `slots` (int64 [n], distinct; e.g. index()[positions]) with fresh
+        search results as engine.search returns them -- visits int32 [n,MAX_LEGAL], actions uint8 [n,MAX_LEGAL], count int32 [n]:
+        pi = counts / their sum scattered by action, with the bits of the append.  search_value (float32 [n], engine.root_values)
+        with value_blend L in (0, 1]: the value target becomes (1 - L) z + L q, z being the value the ring holds now -- which may
+        already be a blend.  One aqg_replay_refresh launch on the window's stream (refresh_reference on a host window); a row without
+        a visit keeps its targets.  Shapes, dtypes and the slots -- each a valid slot, none twice: one device-to-host read -- are
+        checked before anything is written.  The records, the bookkeeping, index() and rows() do not change."""
+        xs = [torch.as_tensor(x) for x in (slots, visits, actions, count)]
+        n = int(xs[0].shape[0]) if xs[0].dim() == 1 else -1
+        specs = (("slots", torch.int64, ()), ("visits", torch.int32, (_lib.MAX_LEGAL,)), ("actions", torch.uint8, (_lib.MAX_LEGAL,)),
+                 ("count", torch.int32, ()))
+        if search_value is not None:
+            xs.append(torch.as_tensor(search_value))
+            specs += (("search_value", torch.float32, ()),)
+        for x, (name, dtype, tail) in zip(xs, specs):
+            if x.dtype != dtype or tuple(x.shape) != (n,) + tail:
+                raise ValueError(f"ReplayWindow.refresh_counts: {name} must be a {dtype} {['n', *tail]} tensor with one row per slot; "
+                                 f"got {x.dtype} {list(x.shape)}")
+        value_blend = check_value_blend(value_blend)
+        if search_value is None and value_blend != 0.0:
+            raise ValueError("ReplayWindow.refresh_counts: a value_blend needs search_value")
+        if n == 0:
+            return
+        if self._rings is None or self._valid == 0:
+            raise ValueError("ReplayWindow.refresh_counts: the window holds no row")
+        xs = [x.to(self.device).contiguous() for x in xs]
+        s = xs[0]
+        valid = torch.zeros((self.capacity,), dtype=torch.bool, device=self.device)
+        valid[self._index] = True
+        inside = (s >= 0) & (s < self.capacity)
+        stale = ~(inside & valid[s.clamp(0, self.capacity - 1)])
+        ordered = torch.sort(s).values
+        bad_slot, repeated = torch.stack((stale.any(), (ordered[1:] == ordered[:-1]).any())).tolist()      # the one read
+        if bad_slot:
+            raise ValueError("ReplayWindow.refresh_counts: a slot holds no valid row of the window")
+        if repeated:
+            raise ValueError("ReplayWindow.refresh_counts: a slot is named twice")
+        q = xs[4] if search_value is not None and value_blend != 0.0 else None
+        _, rpi, rz = self._rings
+        if self.device.type == "cpu":
+            refresh_reference(self.board_size, xs[1].numpy(), xs[2].numpy(), xs[3].numpy(), None if q is None else q.numpy(), value_blend,
+                              s.numpy(), rpi.numpy(), rz.numpy())
+            return
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().aqg_replay_refresh(self.board_size, self.policy_size, _lib.ptr(xs[1]), _lib.ptr(xs[2]), _lib.ptr(xs[3]),
+                                                      _lib.ptr(q), value_blend, _lib.ptr(s), n, self.capacity, _lib.ptr(rpi), _lib.ptr(rz),
+                                                      _lib.stream_ptr(self.device)), "aqg_replay_refresh")
 
     def extend_from_files(self, paths):
         """Each .history file as one generation, in the order given: oldest first."""

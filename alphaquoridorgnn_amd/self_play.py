@@ -18,6 +18,7 @@ from .constants import PV_NETWORK_PATH, BOARD_SIZE
 from .engine import BatchedSelfPlay, MultiSetSelfPlay, gather_history, gather_resign_arrays
 from .pv_network_gnn import GNNNetwork, POLICY_OUTPUT_SIZE, load_network
 from .pv_network_cnn import CNNNetwork
+from .reanalyse import check_reanalyse_options, eligible_rows, reanalyse
 from .replay import blend_targets, check_value_blend
 from .resign_calibration import resign_stats_of, suggest_from_arrays
 
@@ -54,6 +55,13 @@ SP_SLOTS = None
 # the engine's device tensors, for train_network.TRAIN_WINDOW to train on.  The .history file stays the reference's hand-over.
 SP_REPLAY = None             # None = off
 SP_WRITE_HISTORY = True      # False (needs a window): rank 0 writes no file
+# Reanalyse (the reference has none; reanalyse.reanalyse, include/aqgnn.h "reanalyse"): after the generation is appended, every rank
+# searches SP_REANALYSE_ROWS of the window's older rows again with the model that just played and overwrites their targets.  The
+# .history file never changes: it holds the generation as it was played.
+SP_REANALYSE_ROWS = 0        # 0 = off: no search engine is built
+SP_REANALYSE_SIMS = None     # None = pv_mcts.PV_EVALUATE_COUNT
+SP_REANALYSE_VALUE_BLEND = 0.0      # L in [0, 1]: a refreshed row's value target becomes (1 - L) z + L q of the fresh search; 0 = z stays
+SP_REANALYSE_SLOTS = 2048    # roots searched at once
 
 
 def first_player_value(ended_state):
@@ -180,6 +188,9 @@ def self_play(model=None, games=None, seed=None):
     import torch.distributed as dist
     if not SP_WRITE_HISTORY and SP_REPLAY is None:
         raise ValueError("SP_WRITE_HISTORY = False without a replay window (SP_REPLAY) would throw the generation away")
+    reanalyse_rows = check_reanalyse_options(SP_REANALYSE_ROWS, SP_REANALYSE_SIMS, SP_REANALYSE_VALUE_BLEND, SP_REANALYSE_SLOTS)[0]
+    if reanalyse_rows and SP_REPLAY is None:
+        raise ValueError("SP_REANALYSE_ROWS > 0 needs a replay window (SP_REPLAY): there is no older row to search again")
     if model is None:
         model = load_network(PV_NETWORK_PATH + 'best.pth')       # GNNNetwork (prep_for_inference's path), or the network best.pth holds
         if isinstance(model, (GNNNetwork, CNNNetwork)) and torch.cuda.is_available():
@@ -218,6 +229,7 @@ def self_play(model=None, games=None, seed=None):
             q = eng.history_values()
         if resign_thr is not None:
             resign_arrays = eng.resign_arrays()
+        del eng                                          # its tree pools go before a reanalyse pass builds its search engine
     if distributed and os.environ.get("AQG_DIST_LOG") == "1" and rank == 0:
         print(f'exchange step: backend={dist.get_backend()} world={world} collectives={"forced" if aqd.force_group() else "as needed"}')
     host = distributed and dist.get_backend() != 'nccl'      # gloo (CPU tests): the exchange runs on host tensors
@@ -235,6 +247,15 @@ def self_play(model=None, games=None, seed=None):
             SP_REPLAY.append_counts(st, vis, z, search_value=q, value_blend=blend)
         else:
             SP_REPLAY.append_counts(st, vis, z)
+    if reanalyse_rows:
+        # every rank searches the same rows (the seed is the call's base seed, not base + rank) and the search is deterministic: the
+        # ranks' windows stay identical without a collective
+        sims = pv_mcts.PV_EVALUATE_COUNT if SP_REANALYSE_SIMS is None else SP_REANALYSE_SIMS
+        done = reanalyse(SP_REPLAY, model, reanalyse_rows, sims=sims, value_blend=SP_REANALYSE_VALUE_BLEND, seed=base,
+                         update=SP_REPLAY.reanalyse_updates, slots=SP_REANALYSE_SLOTS, evaluator=evaluator)
+        SP_REPLAY.reanalyse_updates += 1
+        if rank == 0:
+            print(f'reanalysed {done} of {eligible_rows(SP_REPLAY)} rows at {sims} simulations')
     path = None
     if rank == 0 and SP_WRITE_HISTORY:
         path = write_data(_history_rows(st, vis, z, BOARD_SIZE, q, blend))

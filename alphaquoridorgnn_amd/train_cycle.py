@@ -215,7 +215,44 @@ def _parser():
                          "target, once per update (default TRAIN_MERGE_POSITIONS = False: one row per occurrence)")
     ap.add_argument("--no-history-file", action="store_true",
                     help="self-play: write no .history file (needs --replay-generations; default SP_WRITE_HISTORY = True)")
+    ap.add_argument("--reanalyse-rows", type=int, default=None, metavar="R",
+                    help="self-play: after each generation, search R of the replay window's older rows again with the network that "
+                         "just played and overwrite their policy targets (needs --replay-generations K >= 2; default "
+                         "SP_REANALYSE_ROWS = 0: off)")
+    ap.add_argument("--reanalyse-sims", type=int, default=None, metavar="S",
+                    help="self-play, with --reanalyse-rows: simulations of the fresh searches (default SP_REANALYSE_SIMS: those of a move)")
+    ap.add_argument("--reanalyse-value-blend", type=float, default=None, metavar="L",
+                    help="self-play, with --reanalyse-rows: weight L in [0, 1] of the fresh search value in a refreshed row's value "
+                         "target, (1 - L) z + L q (default SP_REANALYSE_VALUE_BLEND = 0: the value target stays)")
     return ap
+
+
+def _check_reanalyse_args(args):
+    """--reanalyse-rows / --reanalyse-sims / --reanalyse-value-blend, refused at parse time: values the stage would refuse, the two
+    dependent flags without --reanalyse-rows, and a window that can hold no older generation."""
+    from .reanalyse import check_reanalyse_options
+    if args.reanalyse_rows is None:
+        if args.reanalyse_sims is not None or args.reanalyse_value_blend is not None:
+            raise ValueError("--reanalyse-sims and --reanalyse-value-blend need --reanalyse-rows")
+        return None
+    if args.reanalyse_rows < 0:
+        raise ValueError("--reanalyse-rows must be >= 0")
+    if args.reanalyse_sims is not None and args.reanalyse_sims < 1:
+        raise ValueError("--reanalyse-sims must be >= 1")
+    blend = 0.0 if args.reanalyse_value_blend is None else args.reanalyse_value_blend
+    if not 0.0 <= blend <= 1.0:                             # NaN fails both
+        raise ValueError("--reanalyse-value-blend must be in [0, 1]")
+    if args.replay_generations < 2:
+        raise ValueError("--reanalyse-rows needs --replay-generations K >= 2: the newest generation is never searched again")
+    return check_reanalyse_options(args.reanalyse_rows, args.reanalyse_sims, blend)[:3]
+
+
+def _set_reanalyse_options(args):
+    """The checked reanalyse flags onto self_play's constants (after _set_replay_options: the window exists)."""
+    from . import self_play as sp
+    checked = _check_reanalyse_args(args)
+    if checked is not None:
+        sp.SP_REANALYSE_ROWS, sp.SP_REANALYSE_SIMS, sp.SP_REANALYSE_VALUE_BLEND = checked
 
 
 def _set_replay_options(args):
@@ -329,6 +366,7 @@ def main(argv=None):
     import os
     from . import evaluate_network as en, pv_mcts, self_play as sp, train_network as tn
     args = _parser().parse_args(argv)
+    _check_reanalyse_args(args)                         # in front of anything that touches a device or the process group
     rank, world = aqd.init_from_env()
     if args.games is not None:
         sp.SP_GAME_COUNT = args.games
@@ -346,6 +384,7 @@ def main(argv=None):
     _set_mirror_options(args)
     _set_optimiser_options(args)
     _set_replay_options(args)
+    _set_reanalyse_options(args)
     if args.eval_games is not None:
         en.EN_GAME_COUNT = args.eval_games
     try:

@@ -459,6 +459,11 @@ int aqg_engine_apply_actions(const aqg_engine* e_host, const int32_t* actions, v
  *   priors the last search built the root from, in the layout of aqg_engine_root_visits. */
 int aqg_engine_root_noise(const aqg_engine* e_host, void* stream);
 int aqg_engine_root_priors(const aqg_engine* e_host, float* priors, int32_t* count, void* stream);
+/* aqg_engine_root_values (additive to ABI 15): value [G] f32 = the search value of every slot's root (node 0) after a search or in
+ *   front of a finish-move, from the mover's side: n ? (float)(w / (double)n) : 0.0f -- the expression the finish-move launch stores
+ *   into hist_value ("self-play targets" below), f32 of the f64 quotient.  One lane per slot (csrc/mcts_move.hip); a NULL argument is
+ *   refused before any launch.  aqg_engine_search is unchanged: a caller asks for the values afterwards, as for the priors. */
+int aqg_engine_root_values(const aqg_engine* e_host, float* value, void* stream);
 
 /* ------------------------------------------------------------------ self-play targets (additive to ABI 15; the reference has neither)
  *
@@ -893,6 +898,34 @@ int aqg_replay_append(int board_size, int policy_size, const uint8_t* states72, 
 int aqg_replay_append_blend(int board_size, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8,
                             const float* search_value, float blend, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
                             float* ring_z, void* stream);
+
+/* ------------------------------------------------------------------ reanalyse (additive to ABI 15; the reference has none)
+ *
+ * aqg_replay_refresh: one launch (csrc/replay_refresh.hip) overwrites the targets of chosen ring slots with fresh search results.
+ * Source row i, 0 <= i < n, is a searched root as aqg_engine_root_visits writes it: visits [n,AQG_MAX_LEGAL] i32 and actions
+ * [n,AQG_MAX_LEGAL] u8 in legal_actions() order, count [n] i32 their number.  With c = count[i] and tot = the integer sum of
+ * visits[i][0 .. c):
+ *   - c <= 0, c > AQG_MAX_LEGAL, tot <= 0 or slots[i] outside [0, capacity): the row is skipped and the ring is not touched for it;
+ *   - otherwise the WHOLE policy row of slot slots[i] is written once: f32(visits[i][j]) / f32(tot) at actions[i][j] for j < c, 0.0f
+ *     everywhere else.  The quotient is the correctly rounded f32 division of aqg_replay_append, with the bits of
+ *     f32(f64(v) / f64(tot)) for tot < 2^24; counts are >= 0 and their total below 2^24 (the caller's part: the engine's simulation
+ *     cap sees to it), and the unit is never built with a fast-math flag.  An action byte >= policy_size inside the count is dropped;
+ *     the ids of one row are distinct, as a legal list's are (of a repeated id one quotient is kept).  No input byte is used as an
+ *     address unguarded.
+ *   - with search_value (f32 [n], aqg_engine_root_values) and blend != 0:
+ *         ring_z[slot] = keep * ring_z[slot] + blend * search_value[i],   keep = 1.0f - blend
+ *     in f32 without contraction -- two products and one sum, each rounded, as aqg_replay_append_blend's.  The blend acts on the value
+ *     the ring holds NOW, which may already be a blend (of an append with a blend, or of an earlier refresh): refreshing a row k times
+ *     leaves keep^k of its first value target.  search_value NULL or blend 0: ring_z is neither read nor written (and may be NULL).
+ * slots [n] i64 are distinct (the caller's part, replay.ReplayWindow.refresh_counts checks it); the ring's record bytes are not an
+ * argument and are never touched.  No atomics; every output row is stored once, lane-contiguous.
+ * Refused on the host, before any launch (-1, aqg_last_error): an unsupported board size, a policy_size that is not the board's A,
+ * n < 0, capacity < 1, a blend outside [0, 1] or NaN, a blend != 0 without search_value, and with n > 0: visits, actions, count,
+ * slots or ring_pi NULL, ring_z NULL with a blend, a ring (capacity rows) that overlaps a source (n rows) or the other ring.
+ * n == 0 returns 0 without looking at the pointers.  replay.refresh_reference is the same in numpy. */
+int aqg_replay_refresh(int board_size, int policy_size, const int32_t* visits, const uint8_t* actions, const int32_t* count,
+                       const float* search_value, float blend, const int64_t* slots, int n, int capacity, float* ring_pi,
+                       float* ring_z, void* stream);
 
 /* ------------------------------------------------------------------ position merge (additive to ABI 15; the reference has none)
  *
