@@ -10,6 +10,59 @@ thread_local char g_err[512] = "";
 
 using namespace aqg;
 
+// ---- training.  Per kind (the fused 6/128/3 GNN, the any-shape GNN, the residual CNN): check_net = the checks of its struct,
+// plan_optim = the checks of a call's optimiser controls against its tensors.  check_step / check_steps are an entry point's argument
+// checks under `what`, the name of the entry point that was called; a plain call and its _optim form make the same ones.
+template <class Net>
+static int check_tensors(const Net& t, int tensors, bool adam, const char* what) {
+    for (int i = 0; i < tensors; ++i)
+        if (!t.params[i] || !t.grads[i] || (adam && (!t.adam_m[i] || !t.adam_v[i]))) return fail(what, "null parameter tensor");
+    return adam && t.step < 1 ? fail(what, "step must be >= 1") : 0;
+}
+static int check_net(const aqg_train& t, bool adam, const char* what) { return check_tensors(t, 14, adam, what); }
+static int check_net(const aqg_train_general& t, bool adam, const char* what) {
+    if (t.num_layers < 1 || t.num_layers > AQG_GENERAL_MAX_LAYERS) return fail(what, "num_layers must be 1..32");
+    return check_tensors(t, 2 * t.num_layers + 8, adam, what);
+}
+static int check_net(const aqg_cnn_train& t, bool adam, const char* what) { return check_cnn_train(t, adam, what); }
+
+static int plan_optim(const aqg_train& t, const aqg_optim* optim, const char* what, OptimPlan* plan, bool* on) {
+    size_t numel[14];
+    train_tensor_sizes(t, numel);
+    return check_optim(optim, 14, numel, t.grads, what, plan, on);
+}
+static int plan_optim(const aqg_train_general& t, const aqg_optim* optim, const char* what, OptimPlan* plan, bool* on) {
+    // sizes are taken of a shape inside the kernels' limits only, refused in the words of the plain call (check_general_net)
+    if (t.hidden < 2 || t.hidden > 1024) return fail(what, "hidden must be 2..1024");
+    if (t.policy_size < 1 || t.policy_size > 4096) return fail(what, "policy_size must be 1..4096");
+    size_t numel[2 * AQG_GENERAL_MAX_LAYERS + 8];
+    train_general_tensor_sizes(t, numel);
+    return check_optim(optim, 2 * t.num_layers + 8, numel, t.grads, what, plan, on);
+}
+static int plan_optim(const aqg_cnn_train& t, const aqg_optim* optim, const char* what, OptimPlan* plan, bool* on) {
+    size_t numel[AQG_CNN_TRAIN_TENSORS];
+    cnn_train_tensor_sizes(t, numel);
+    return check_optim(optim, 3 * (2 * t.num_blocks + 1) + 4, numel, t.grads, what, plan, on);
+}
+
+static int check_step(const aqg_train* t, const uint8_t* states72, const float* pi, const float* z, int mode, const char* what) {
+    if (!t || mode < 0 || mode > 2) return fail(what, "bad argument");
+    if (mode != 2 && (!states72 || !pi || !z)) return fail(what, "null argument");
+    return check_net(*t, mode >= 1, what);
+}
+template <class Net>      // the two workspace trainers: the batch is the struct's, and an empty one needs no arrays
+static int check_step(const Net* t, const uint8_t* states72, const float* pi, const float* z, int mode, const char* what) {
+    if (!t || mode < 0 || mode > 2) return fail(what, "bad argument");
+    if (t->batch < 0) return fail(what, "negative batch");
+    if (mode != 2 && t->batch > 0 && (!states72 || !pi || !z)) return fail(what, "null argument");
+    return check_net(*t, mode >= 1, what);
+}
+template <class Net>
+static int check_steps(const Net* t, const uint8_t* states72, const float* pi, const float* z, long long positions, const char* what) {
+    if (!t || !states72 || !pi || !z || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
+    return check_net(*t, true, what);
+}
+
 extern "C" {
 
 int aqg_abi_version(void) { return AQG_ABI_VERSION; }
@@ -352,98 +405,61 @@ int aqg_agent_alpha_beta(int board_size, const uint8_t* states72, int B, const u
                                    workspace_bytes, action, nodes, (hipStream_t)stream);
 }
 
+// The _optim entry points (include/aqgnn.h "optimiser controls"): the plain call's own checks first (it refuses what it always
+// refused, under the name that was called), then the controls'; with optim NULL, the plain call itself.
 int aqg_gcn_train_step(const aqg_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
                        void* stream) {
-    if (!t || mode < 0 || mode > 2) return fail("aqg_gcn_train_step: bad argument");
-    if (mode != 2 && (!states72 || !pi_target || !z_target)) return fail("aqg_gcn_train_step: null argument");
-    for (int i = 0; i < 14; ++i)
-        if (!t->params[i] || !t->grads[i] || (mode >= 1 && (!t->adam_m[i] || !t->adam_v[i]))) return fail("aqg_gcn_train_step: null parameter tensor");
-    if (mode >= 1 && t->step < 1) return fail("aqg_gcn_train_step: step must be >= 1");
+    if (int r = check_step(t, states72, pi_target, z_target, mode, "aqg_gcn_train_step")) return r;
     return train_step(*t, states72, pi_target, z_target, mode, (hipStream_t)stream);
 }
-// The _optim entry points (include/aqgnn.h "optimiser controls"): the plain call's own checks first (it refuses what it always
-// refused, under its own name), then the controls'; with nothing on, the plain call itself.
 int aqg_gcn_train_step_optim(const aqg_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
                              const aqg_optim* optim, void* stream) {
     if (!optim) return aqg_gcn_train_step(t, states72, pi_target, z_target, mode, stream);
     const char* what = "aqg_gcn_train_step_optim";
-    if (!t || mode < 0 || mode > 2) return fail(what, "bad argument");
-    if (mode != 2 && (!states72 || !pi_target || !z_target)) return fail(what, "null argument");
-    for (int i = 0; i < 14; ++i)
-        if (!t->params[i] || !t->grads[i] || (mode >= 1 && (!t->adam_m[i] || !t->adam_v[i]))) return fail(what, "null parameter tensor");
-    if (mode >= 1 && t->step < 1) return fail(what, "step must be >= 1");
-    size_t numel[14];
-    train_tensor_sizes(*t, numel);
     OptimPlan plan;
     bool on;
-    if (int r = check_optim(optim, 14, numel, t->grads, what, &plan, &on)) return r;
+    if (int r = check_step(t, states72, pi_target, z_target, mode, what)) return r;
+    if (int r = plan_optim(*t, optim, what, &plan, &on)) return r;
     return train_step(*t, states72, pi_target, z_target, mode, (hipStream_t)stream, on ? &plan : nullptr);
 }
 long long aqg_gcn_train_fallbacks(int reset) { return train_fallbacks(reset); }
 int aqg_gcn_train_steps(const aqg_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, const int64_t* order,
                         long long positions, float* loss_sums, void* stream) {
-    if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail("aqg_gcn_train_steps: bad argument");
-    for (int i = 0; i < 14; ++i)
-        if (!t->params[i] || !t->grads[i] || !t->adam_m[i] || !t->adam_v[i]) return fail("aqg_gcn_train_steps: null parameter tensor");
-    if (t->step < 1) return fail("aqg_gcn_train_steps: step must be >= 1");
+    if (int r = check_steps(t, states72, pi_target, z_target, positions, "aqg_gcn_train_steps")) return r;
     return train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream);
 }
 int aqg_gcn_train_steps_optim(const aqg_train* t, const uint8_t* states72, const float* pi_target, const float* z_target,
                               const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim, void* stream) {
     if (!optim) return aqg_gcn_train_steps(t, states72, pi_target, z_target, order, positions, loss_sums, stream);
     const char* what = "aqg_gcn_train_steps_optim";
-    if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
-    for (int i = 0; i < 14; ++i)
-        if (!t->params[i] || !t->grads[i] || !t->adam_m[i] || !t->adam_v[i]) return fail(what, "null parameter tensor");
-    if (t->step < 1) return fail(what, "step must be >= 1");
-    size_t numel[14];
-    train_tensor_sizes(*t, numel);
     OptimPlan plan;
     bool on;
-    if (int r = check_optim(optim, 14, numel, t->grads, what, &plan, &on)) return r;
+    if (int r = check_steps(t, states72, pi_target, z_target, positions, what)) return r;
+    if (int r = plan_optim(*t, optim, what, &plan, &on)) return r;
     return train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream, on ? &plan : nullptr);
 }
 
-static int check_train_general(const aqg_train_general* t, bool adam, const char* what) {
-    if (t->num_layers < 1 || t->num_layers > AQG_GENERAL_MAX_LAYERS) return fail(what, "num_layers must be 1..32");
-    for (int i = 0; i < 2 * t->num_layers + 8; ++i)
-        if (!t->params[i] || !t->grads[i] || (adam && (!t->adam_m[i] || !t->adam_v[i]))) return fail(what, "null parameter tensor");
-    if (adam && t->step < 1) return fail(what, "step must be >= 1");
-    return 0;
-}
 size_t aqg_gcn_train_general_workspace_floats(int board_size, int hidden, int num_layers, int policy_size, int max_batch) {
     return train_general_workspace_floats(board_size, hidden, num_layers, policy_size, max_batch);
 }
 int aqg_gcn_train_step_general(const aqg_train_general* t, const uint8_t* states72, const float* pi_target, const float* z_target,
                                int mode, void* stream) {
-    const char* what = "aqg_gcn_train_step_general";
-    if (!t || mode < 0 || mode > 2) return fail(what, "bad argument");
-    if (t->batch < 0) return fail(what, "negative batch");
-    if (mode != 2 && t->batch > 0 && (!states72 || !pi_target || !z_target)) return fail(what, "null argument");
-    if (int r = check_train_general(t, mode >= 1, what)) return r;
+    if (int r = check_step(t, states72, pi_target, z_target, mode, "aqg_gcn_train_step_general")) return r;
     return train_step_general(*t, states72, pi_target, z_target, mode, (hipStream_t)stream);
 }
 int aqg_gcn_train_step_general_optim(const aqg_train_general* t, const uint8_t* states72, const float* pi_target, const float* z_target,
                                      int mode, const aqg_optim* optim, void* stream) {
     if (!optim) return aqg_gcn_train_step_general(t, states72, pi_target, z_target, mode, stream);
     const char* what = "aqg_gcn_train_step_general_optim";
-    if (!t || mode < 0 || mode > 2) return fail(what, "bad argument");
-    if (t->batch < 0) return fail(what, "negative batch");
-    if (mode != 2 && t->batch > 0 && (!states72 || !pi_target || !z_target)) return fail(what, "null argument");
-    if (int r = check_train_general(t, mode >= 1, what)) return r;
-    if (t->hidden < 2 || t->hidden > 1024 || t->policy_size < 1 || t->policy_size > 4096) return fail(what, "shape outside the kernels' limits");
-    size_t numel[2 * AQG_GENERAL_MAX_LAYERS + 8];
-    train_general_tensor_sizes(*t, numel);
     OptimPlan plan;
     bool on;
-    if (int r = check_optim(optim, 2 * t->num_layers + 8, numel, t->grads, what, &plan, &on)) return r;
+    if (int r = check_step(t, states72, pi_target, z_target, mode, what)) return r;
+    if (int r = plan_optim(*t, optim, what, &plan, &on)) return r;
     return train_step_general(*t, states72, pi_target, z_target, mode, (hipStream_t)stream, on ? &plan : nullptr);
 }
 int aqg_gcn_train_steps_general(const aqg_train_general* t, const uint8_t* states72, const float* pi_target, const float* z_target,
                                 const int64_t* order, long long positions, float* loss_sums, void* stream) {
-    const char* what = "aqg_gcn_train_steps_general";
-    if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
-    if (int r = check_train_general(t, true, what)) return r;
+    if (int r = check_steps(t, states72, pi_target, z_target, positions, "aqg_gcn_train_steps_general")) return r;
     return train_steps_general(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream);
 }
 int aqg_gcn_train_steps_general_optim(const aqg_train_general* t, const uint8_t* states72, const float* pi_target, const float* z_target,
@@ -451,14 +467,10 @@ int aqg_gcn_train_steps_general_optim(const aqg_train_general* t, const uint8_t*
                                       void* stream) {
     if (!optim) return aqg_gcn_train_steps_general(t, states72, pi_target, z_target, order, positions, loss_sums, stream);
     const char* what = "aqg_gcn_train_steps_general_optim";
-    if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
-    if (int r = check_train_general(t, true, what)) return r;
-    if (t->hidden < 2 || t->hidden > 1024 || t->policy_size < 1 || t->policy_size > 4096) return fail(what, "shape outside the kernels' limits");
-    size_t numel[2 * AQG_GENERAL_MAX_LAYERS + 8];
-    train_general_tensor_sizes(*t, numel);
     OptimPlan plan;
     bool on;
-    if (int r = check_optim(optim, 2 * t->num_layers + 8, numel, t->grads, what, &plan, &on)) return r;
+    if (int r = check_steps(t, states72, pi_target, z_target, positions, what)) return r;
+    if (int r = plan_optim(*t, optim, what, &plan, &on)) return r;
     return train_steps_general(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream, on ? &plan : nullptr);
 }
 
@@ -467,46 +479,32 @@ size_t aqg_cnn_train_workspace_floats(int board_size, int num_filters, int num_b
 }
 int aqg_cnn_train_step(const aqg_cnn_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
                        void* stream) {
-    const char* what = "aqg_cnn_train_step";
-    if (!t || mode < 0 || mode > 2) return fail(what, "bad argument");
-    if (t->batch < 0) return fail(what, "negative batch");
-    if (mode != 2 && t->batch > 0 && (!states72 || !pi_target || !z_target)) return fail(what, "null argument");
-    if (int r = check_cnn_train(*t, mode >= 1, what)) return r;
+    if (int r = check_step(t, states72, pi_target, z_target, mode, "aqg_cnn_train_step")) return r;
     return cnn_train_step(*t, states72, pi_target, z_target, mode, (hipStream_t)stream);
 }
 int aqg_cnn_train_step_optim(const aqg_cnn_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
                              const aqg_optim* optim, void* stream) {
     if (!optim) return aqg_cnn_train_step(t, states72, pi_target, z_target, mode, stream);
     const char* what = "aqg_cnn_train_step_optim";
-    if (!t || mode < 0 || mode > 2) return fail(what, "bad argument");
-    if (t->batch < 0) return fail(what, "negative batch");
-    if (mode != 2 && t->batch > 0 && (!states72 || !pi_target || !z_target)) return fail(what, "null argument");
-    if (int r = check_cnn_train(*t, mode >= 1, what)) return r;
-    size_t numel[AQG_CNN_TRAIN_TENSORS];
-    cnn_train_tensor_sizes(*t, numel);
     OptimPlan plan;
     bool on;
-    if (int r = check_optim(optim, 3 * (2 * t->num_blocks + 1) + 4, numel, t->grads, what, &plan, &on)) return r;
+    if (int r = check_step(t, states72, pi_target, z_target, mode, what)) return r;
+    if (int r = plan_optim(*t, optim, what, &plan, &on)) return r;
     return cnn_train_step(*t, states72, pi_target, z_target, mode, (hipStream_t)stream, on ? &plan : nullptr);
 }
 int aqg_cnn_train_steps(const aqg_cnn_train* t, const uint8_t* states72, const float* pi_target, const float* z_target,
                         const int64_t* order, long long positions, float* loss_sums, void* stream) {
-    const char* what = "aqg_cnn_train_steps";
-    if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
-    if (int r = check_cnn_train(*t, true, what)) return r;
+    if (int r = check_steps(t, states72, pi_target, z_target, positions, "aqg_cnn_train_steps")) return r;
     return cnn_train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream);
 }
 int aqg_cnn_train_steps_optim(const aqg_cnn_train* t, const uint8_t* states72, const float* pi_target, const float* z_target,
                               const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim, void* stream) {
     if (!optim) return aqg_cnn_train_steps(t, states72, pi_target, z_target, order, positions, loss_sums, stream);
     const char* what = "aqg_cnn_train_steps_optim";
-    if (!t || !states72 || !pi_target || !z_target || positions < 0 || positions > 0x7fffffffLL) return fail(what, "bad argument");
-    if (int r = check_cnn_train(*t, true, what)) return r;
-    size_t numel[AQG_CNN_TRAIN_TENSORS];
-    cnn_train_tensor_sizes(*t, numel);
     OptimPlan plan;
     bool on;
-    if (int r = check_optim(optim, 3 * (2 * t->num_blocks + 1) + 4, numel, t->grads, what, &plan, &on)) return r;
+    if (int r = check_steps(t, states72, pi_target, z_target, positions, what)) return r;
+    if (int r = plan_optim(*t, optim, what, &plan, &on)) return r;
     return cnn_train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream, on ? &plan : nullptr);
 }
 

@@ -24,8 +24,7 @@
 #include "../../include/aqgnn.h"
 #include "launchers.hpp"
 #include "train_adam.hpp"
-
-#include <cmath>
+#include "train_driver.hpp"
 
 namespace aqg {
 
@@ -394,7 +393,7 @@ int launch_finish(const aqg_cnn_train& t, int B, bool update, int step, const fl
 }
 
 bool shape_ok(int N, int F, int L, int A) {
-    return (N == 3 || N == 5 || N == 7 || N == 9) && F >= 1 && F <= AQG_CNN_MAX_FILTERS && L >= 0 && L <= AQG_CNN_MAX_BLOCKS &&
+    return board_size_supported(N) && F >= 1 && F <= AQG_CNN_MAX_FILTERS && L >= 0 && L <= AQG_CNN_MAX_BLOCKS &&
            A == N * N + 2 * (N - 1) * (N - 1);
 }
 
@@ -415,8 +414,7 @@ size_t cnn_train_workspace_floats(int N, int F, int L, int A, int max_batch) {
 
 // the host-side checks of both entry points (include/aqgnn.h aqg_cnn_train): shape, tensors, BatchNorm settings, Adam table
 int check_cnn_train(const aqg_cnn_train& t, bool adam, const char* what) {
-    if (!(t.board_size == 3 || t.board_size == 5 || t.board_size == 7 || t.board_size == 9))
-        return fail(what, "board_size must be 3, 5, 7 or 9");
+    if (!board_size_supported(t.board_size)) return fail(what, "board_size must be 3, 5, 7 or 9");
     if (t.num_filters < 1 || t.num_filters > AQG_CNN_MAX_FILTERS) return fail(what, "num_filters must be 1..512");
     if (t.num_blocks < 0 || t.num_blocks > AQG_CNN_MAX_BLOCKS) return fail(what, "num_blocks must be 0..40");
     if (!shape_ok(t.board_size, t.num_filters, t.num_blocks, t.policy_size))
@@ -434,54 +432,27 @@ int check_cnn_train(const aqg_cnn_train& t, bool adam, const char* what) {
     return 0;
 }
 
-// mode 0 = gradients only, 1 = gradients + Adam, 2 = Adam only
+// the residual CNN as a kind of train_driver.hpp; check_cnn_train, called by capi.hip, has validated t
+struct CnnKind {
+    using Workspace = CnnTrainWorkspace;
+    static constexpr const char *step_name = "aqg_cnn_train_step", *steps_name = "aqg_cnn_train_steps";
+    static constexpr const char* workspace_refusal = "workspace too small (aqg_cnn_train_workspace_floats)";
+    static constexpr bool empty_batch_mode1_updates = false;    // batch 0: a no-op unless mode is 2
+    static constexpr auto forward_backward = aqg::forward_backward;
+    static constexpr auto launch_finish = aqg::launch_finish;
+    static int validate(const aqg_cnn_train&, const char*) { return 0; }
+    static size_t layout(const aqg_cnn_train& t, int B, CnnTrainWorkspace* ws) {
+        return cnn_train_layout(t.board_size, t.num_filters, t.num_blocks, t.policy_size, B, ws, ws ? t.workspace : nullptr);
+    }
+};
+
 int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
                    const OptimPlan* plan) {
-    const char* what = "aqg_cnn_train_step";
-    OptimLaunch ol;
-    const OptimLaunch* olp = plan && mode >= 1 ? &ol : nullptr;
-    const int B = t.batch;
-    if (mode != 2 && B > 0) {
-        const size_t need = cnn_train_layout(t.board_size, t.num_filters, t.num_blocks, t.policy_size, B, nullptr, nullptr);
-        if (!t.workspace || t.workspace_floats < need) return fail(what, "workspace too small (aqg_cnn_train_workspace_floats)");
-        CnnTrainWorkspace ws;
-        cnn_train_layout(t.board_size, t.num_filters, t.num_blocks, t.policy_size, B, &ws, t.workspace);
-        float* policy = t.policy ? t.policy : ws.policy;
-        float* value = t.value ? t.value : ws.value;
-        float* loss = t.loss ? t.loss : ws.loss;
-        if (int r = forward_backward(t, states72, pi, z, nullptr, 0, B, ws, policy, value, loss, st)) return r;
-        if (olp) if (int r = optim_before_finish(*plan, 0, &ol, st)) return r;
-        if (int r = launch_finish(t, B, mode == 1, t.step, loss, t.loss_mean ? t.loss_mean : ws.loss_mean, nullptr, st, olp)) return r;
-        return plan && mode == 0 ? optim_norm_only(*plan, st) : 0;
-    }
-    if (mode == 2) {
-        if (olp) if (int r = optim_before_finish(*plan, 0, &ol, st)) return r;
-        return launch_finish(t, B, true, t.step, nullptr, nullptr, nullptr, st, olp);
-    }
-    return plan && mode == 0 ? optim_norm_only(*plan, st) : 0;
+    return train_driver_step<CnnKind>(t, states72, pi, z, mode, st, plan);
 }
-
 int cnn_train_steps(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
                     long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan) {
-    const char* what = "aqg_cnn_train_steps";
-    if (t.batch < 1) return fail(what, "batch must be >= 1");
-    const size_t need = cnn_train_layout(t.board_size, t.num_filters, t.num_blocks, t.policy_size, t.batch, nullptr, nullptr);
-    if (!t.workspace || t.workspace_floats < need) return fail(what, "workspace too small (aqg_cnn_train_workspace_floats)");
-    int step = t.step;
-    for (long long first = 0; first < positions; first += t.batch, ++step) {
-        const int B = (int)(positions - first < t.batch ? positions - first : t.batch);
-        CnnTrainWorkspace ws;
-        cnn_train_layout(t.board_size, t.num_filters, t.num_blocks, t.policy_size, B, &ws, t.workspace);
-        float* policy = t.policy ? t.policy : ws.policy;
-        float* value = t.value ? t.value : ws.value;
-        float* loss = t.loss ? t.loss : ws.loss;
-        if (int r = forward_backward(t, states72, pi, z, order, (int)first, B, ws, policy, value, loss, st)) return r;
-        OptimLaunch ol;
-        if (plan) if (int r = optim_before_finish(*plan, step - t.step, &ol, st)) return r;
-        if (int r = launch_finish(t, B, true, step, loss, t.loss_mean ? t.loss_mean : ws.loss_mean, loss_sums, st, plan ? &ol : nullptr))
-            return r;
-    }
-    return 0;
+    return train_driver_steps<CnnKind>(t, states72, pi, z, order, positions, loss_sums, st, plan);
 }
 
 }  // namespace aqg

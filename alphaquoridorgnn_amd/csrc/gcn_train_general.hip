@@ -18,6 +18,7 @@
 #include "../../include/aqgnn.h"
 #include "launchers.hpp"
 #include "train_adam.hpp"
+#include "train_driver.hpp"
 #include <type_traits>
 
 namespace aqg {
@@ -296,9 +297,7 @@ int forward_backward(const aqg_train_general& t, const uint8_t* states72, const 
     if (int r = launch_gen_linear(B, Hh, 1, ws.hv, p[o + 6], p[o + 7], nullptr, 0, ws.vpre, st)) return r;
     if (int r = launch_gen_heads(B, A, ws.logits, ws.vpre, policy, value, st, nullptr)) return r;
     // losses and the way back to the logits / the pre-tanh value
-    hipLaunchKernelGGL(train_general_loss_kernel, dim3(B), dim3(256), 0, st, B, A, policy, value, pi, z, order, first, loss, ws.dpol,
-                       ws.dval);
-    if (int r = check_launch("train_general_loss_kernel")) return r;
+    if (int r = launch_train_general_loss(B, A, policy, value, pi, z, order, first, loss, ws.dpol, ws.dval, st)) return r;
     if (int r = launch_gen_heads_backward(B, A, policy, ws.dpol, value, ws.dval, ws.dlogits, ws.dvpre, st)) return r;
     // heads: second layers, the hidden layers' gradients (ReLU mask = the saved activations), first layers, d loss / d pooled
     float* part = ws.part;
@@ -355,8 +354,7 @@ int launch_finish(const aqg_train_general& t, int B, bool update, int step, cons
 }
 
 int validate(const aqg_train_general& t, const char* what) {
-    const int N = t.board_size;
-    if (!board_size_supported(N)) return fail(what, "board_size must be 3, 5, 7 or 9");
+    if (!board_size_supported(t.board_size)) return fail(what, "board_size must be 3, 5, 7 or 9");
     aqg_gcn_general_net net{};
     net.num_features = t.num_features; net.hidden = t.hidden; net.num_layers = t.num_layers; net.policy_size = t.policy_size;
     const char* why = "";
@@ -398,57 +396,27 @@ size_t train_general_workspace_floats(int N, int hidden, int num_layers, int pol
     return train_layout(N, hidden, num_layers, policy_size, max_batch, nullptr, nullptr);   // monotone in the batch: O(1) host work
 }
 
-// mode 0 = gradients only, 1 = gradients + Adam, 2 = Adam only (data-parallel: local gradients, all-reduce, update)
+// the any-shape GNN as a kind of train_driver.hpp
+struct GeneralKind {
+    using Workspace = TrainWorkspace;
+    static constexpr const char *step_name = "aqg_gcn_train_step_general", *steps_name = "aqg_gcn_train_steps_general";
+    static constexpr const char* workspace_refusal = "workspace too small (aqg_gcn_train_general_workspace_floats)";
+    static constexpr bool empty_batch_mode1_updates = true;     // batch 0, mode 1: Adam still runs, on whatever grads holds
+    static constexpr auto validate = aqg::validate;
+    static constexpr auto forward_backward = aqg::forward_backward;
+    static constexpr auto launch_finish = aqg::launch_finish;
+    static size_t layout(const aqg_train_general& t, int B, TrainWorkspace* ws) {
+        return train_layout(t.board_size, t.hidden, t.num_layers, t.policy_size, B, ws, ws ? t.workspace : nullptr);
+    }
+};
+
 int train_step_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
                        const OptimPlan* plan) {
-    const char* what = "aqg_gcn_train_step_general";
-    OptimLaunch ol;
-    const OptimLaunch* olp = plan && mode >= 1 ? &ol : nullptr;
-    if (int r = validate(t, what)) return r;
-    const int B = t.batch;
-    if (mode != 2 && B > 0) {
-        const size_t need = train_layout(t.board_size, t.hidden, t.num_layers, t.policy_size, B, nullptr, nullptr);
-        if (!t.workspace || t.workspace_floats < need) return fail(what, "workspace too small (aqg_gcn_train_general_workspace_floats)");
-        TrainWorkspace ws;
-        train_layout(t.board_size, t.hidden, t.num_layers, t.policy_size, B, &ws, t.workspace);
-        float* policy = t.policy ? t.policy : ws.policy;
-        float* value = t.value ? t.value : ws.value;
-        float* loss = t.loss ? t.loss : ws.loss;
-        if (int r = forward_backward(t, states72, pi, z, nullptr, 0, B, ws, policy, value, loss, st)) return r;
-        if (olp) if (int r = optim_before_finish(*plan, 0, &ol, st)) return r;
-        if (int r = launch_finish(t, B, mode == 1, t.step, loss, t.loss_mean ? t.loss_mean : ws.loss_mean, nullptr, st, olp)) return r;
-        return plan && mode == 0 ? optim_norm_only(*plan, st) : 0;
-    }
-    if (mode >= 1) {
-        if (olp) if (int r = optim_before_finish(*plan, 0, &ol, st)) return r;
-        return launch_finish(t, B, true, t.step, nullptr, nullptr, nullptr, st, olp);
-    }
-    return plan ? optim_norm_only(*plan, st) : 0;
+    return train_driver_step<GeneralKind>(t, states72, pi, z, mode, st, plan);
 }
-
 int train_steps_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
                         long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan) {
-    const char* what = "aqg_gcn_train_steps_general";
-    if (int r = validate(t, what)) return r;
-    if (t.batch < 1) return fail(what, "batch must be >= 1");
-    const size_t need = train_layout(t.board_size, t.hidden, t.num_layers, t.policy_size, t.batch, nullptr, nullptr);   // serves the short last batch too
-    if (!t.workspace || t.workspace_floats < need)
-        return fail(what, "workspace too small (aqg_gcn_train_general_workspace_floats)");
-    int step = t.step;
-    for (long long first = 0; first < positions; first += t.batch, ++step) {
-        const int B = (int)(positions - first < t.batch ? positions - first : t.batch);
-        TrainWorkspace ws;
-        train_layout(t.board_size, t.hidden, t.num_layers, t.policy_size, B, &ws, t.workspace);
-        float* policy = t.policy ? t.policy : ws.policy;
-        float* value = t.value ? t.value : ws.value;
-        float* loss = t.loss ? t.loss : ws.loss;
-        if (int r = forward_backward(t, states72, pi, z, order, (int)first, B, ws, policy, value, loss, st)) return r;
-        OptimLaunch ol;
-        if (plan) if (int r = optim_before_finish(*plan, step - t.step, &ol, st)) return r;
-        if (int r = launch_finish(t, B, true, step, loss, t.loss_mean ? t.loss_mean : ws.loss_mean, loss_sums, st, plan ? &ol : nullptr))
-            return r;
-    }
-    return 0;
+    return train_driver_steps<GeneralKind>(t, states72, pi, z, order, positions, loss_sums, st, plan);
 }
 
 }  // namespace aqg

@@ -236,11 +236,61 @@ class _Trainer:
     unclipped global gradient norm of the last step (0-dim device tensor) and grad_norms that of every step of the last run_epoch
     (device tensor [steps]); neither is read by the host."""
 
-    def _optimiser_controls(self, weight_decay, decoupled, decay_all, max_grad_norm):
-        self.weight_decay, self.decoupled, self.decay_all, self.max_grad_norm = weight_decay, decoupled, decay_all, max_grad_norm
+    _GPU_REFUSAL = None       # a subclass's own words for a model that is not on the GPU (raised in front of require_gpu's)
+
+    def _setup(self, model, params, max_batch, betas, eps, controls, buffers=(), workspace=None):
+        """The constructors' shared part: the checks of `params` (and `buffers`, tensors the kernels write besides them), the Adam
+        state with every gradient a view of ONE flat buffer (the data-parallel exchange is a single all-reduce), the optimiser
+        controls and the counters.  workspace, for the two workspace trainers: (the library's workspace-size call, its shape
+        arguments in front of the batch); their outputs and workspace are allocated here."""
+        self.model, self.lib, self.params, self.buffers = model, _lib.load(), list(params), list(buffers)
+        what = "parameters and running statistics" if self.buffers else "parameters"
+        for x in self.params + self.buffers:
+            if x.dtype != torch.float32 or not x.is_contiguous():
+                raise ValueError(f"training needs contiguous float32 {what}")
+        if self._GPU_REFUSAL and self.params[0].device.type != "cuda":
+            raise ValueError(self._GPU_REFUSAL)
+        self.dev = _lib.require_gpu(self.params[0].device)
+        if any(x.device != self.dev for x in self.params + self.buffers):
+            raise ValueError(f"every {'parameter and running statistic' if self.buffers else 'parameter'} must be on the trainer's GPU")
+        self.flat_grads = torch.zeros((sum(p.numel() for p in self.params),), dtype=torch.float32, device=self.dev)
+        self.grads, off = [], 0
+        for p in self.params:
+            self.grads.append(self.flat_grads[off:off + p.numel()].view_as(p))
+            off += p.numel()
+        self.adam_m = [torch.zeros_like(p) for p in self.params]
+        self.adam_v = [torch.zeros_like(p) for p in self.params]
+        self.weight_decay, self.decoupled, self.decay_all, self.max_grad_norm = controls
         self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=self.dev)
         self.grad_norms = torch.zeros((0,), dtype=torch.float32, device=self.dev)
         self._optim_ws = None
+        self.N, self.A = model.board_size, model.policy_output_size
+        self.max_batch, self.step_count = int(max_batch), 0
+        self.betas, self.eps = betas, eps
+        if workspace is not None:
+            if self.max_batch < 1:
+                raise ValueError("max_batch must be >= 1")
+            name, shape = workspace
+            nws = int(getattr(self.lib, name)(self.N, *shape, self.A, self.max_batch))
+            if nws == 0:
+                _lib.check(-1, f"{name} (shape or board size outside the kernels' limits)")
+            f = dict(dtype=torch.float32, device=self.dev)
+            self.ws = dict(workspace=torch.empty((nws,), **f), pol=torch.empty((self.max_batch, self.A), **f),
+                           val=torch.empty((self.max_batch,), **f), loss=torch.empty((self.max_batch, 2), **f),
+                           loss_mean=torch.zeros((2,), **f))
+
+    def _fill(self, t):
+        """What every trainer's struct takes the same way: the board, Adam's constants, the params / grads / adam_m / adam_v pointer
+        arrays where the struct has them, and the workspace trainers' outputs and workspace."""
+        self.t = t
+        t.board_size, t.policy_size = self.N, self.A
+        t.beta1, t.beta2, t.eps = float(self.betas[0]), float(self.betas[1]), float(self.eps)
+        for name in ("params", "grads", "adam_m", "adam_v"):
+            for i, x in enumerate(getattr(self, name) if hasattr(t, name) else ()):
+                getattr(t, name)[i] = x.data_ptr()
+        if "workspace" in self.ws:
+            t.policy, t.value, t.loss, t.loss_mean = (self.ws[k].data_ptr() for k in ("pol", "val", "loss", "loss_mean"))
+            t.workspace, t.workspace_floats = self.ws["workspace"].data_ptr(), self.ws["workspace"].numel()
 
     def _optim(self, steps):
         """(aqg_optim for a call of `steps` steps, the device tensor its norms go to) -- (None, None) with every control off."""
@@ -266,35 +316,18 @@ class _Trainer:
             o.workspace, o.workspace_floats = self._optim_ws.data_ptr(), self._optim_ws.numel()
         return o, norms
 
+    def _invoke(self, name, args, steps, plain=False):
+        """One library call of `steps` steps: `name` itself when plain or with every control off (no aqg_optim is built), its
+        _optim form otherwise.  Returns the device tensor the call's norms went to, or None."""
+        o, norms = (None, None) if plain else self._optim(steps)
+        name, controls = (name, ()) if o is None else (name + "_optim", (ctypes.byref(o),))
+        _lib.check(getattr(self.lib, name)(ctypes.byref(self.t), *args, *controls, _lib.stream_ptr(self.dev)), name)
+        return norms
+
     def _call(self, states72, pi_target, z_target, mode, plain=False):
-        o, norms = (None, None) if plain else self._optim(1)
-        args = (ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target), mode)
-        if o is None:
-            _lib.check(getattr(self.lib, self._STEP)(*args, _lib.stream_ptr(self.dev)), self._STEP)
-        else:
-            _lib.check(getattr(self.lib, self._STEP + "_optim")(*args, ctypes.byref(o), _lib.stream_ptr(self.dev)), self._STEP + "_optim")
+        norms = self._invoke(self._STEP, (_lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target), mode), 1, plain)
         if norms is not None:
             self.last_grad_norm = norms[0]
-
-    def _call_epoch(self, states72, pi_target, z_target, order, n, sums):
-        o, norms = self._optim((n + self.t.batch - 1) // self.t.batch)
-        args = (ctypes.byref(self.t), _lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target), _lib.ptr(order), n, _lib.ptr(sums))
-        if o is None:
-            _lib.check(getattr(self.lib, self._STEPS)(*args, _lib.stream_ptr(self.dev)), self._STEPS)
-        else:
-            _lib.check(getattr(self.lib, self._STEPS + "_optim")(*args, ctypes.byref(o), _lib.stream_ptr(self.dev)), self._STEPS + "_optim")
-        if norms is not None:
-            self.grad_norms, self.last_grad_norm = norms, norms[-1]
-
-    def _optimiser_state(self):
-        # all gradient tensors are views of ONE flat buffer: the data-parallel exchange is a single all-reduce
-        self.flat_grads = torch.zeros((sum(p.numel() for p in self.params),), dtype=torch.float32, device=self.dev)
-        self.grads, off = [], 0
-        for p in self.params:
-            self.grads.append(self.flat_grads[off:off + p.numel()].view_as(p))
-            off += p.numel()
-        self.adam_m = [torch.zeros_like(p) for p in self.params]
-        self.adam_v = [torch.zeros_like(p) for p in self.params]
 
     def step(self, states72, pi_target, z_target, lr=LEARNING_RATE, update=True, group=None, mirror=None):
         """One optimisation step.  states72 uint8 [B,72], pi_target float32 [B,A], z_target float32 [B] (device tensors).
@@ -372,8 +405,12 @@ class _Trainer:
         elif pre_shuffle:
             states72, pi_target, z_target = (x.index_select(0, order).contiguous() for x in (states72, pi_target, z_target))
         self.t.batch, self.t.step, self.t.lr = batch, self.step_count + 1, float(lr)
-        self._call_epoch(states72, pi_target, z_target, None if pre_shuffle else order, n, sums)
-        self.step_count += (n + batch - 1) // batch
+        steps = (n + batch - 1) // batch
+        norms = self._invoke(self._STEPS, (_lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target),
+                                           _lib.ptr(None if pre_shuffle else order), n, _lib.ptr(sums)), steps)
+        if norms is not None:
+            self.grad_norms, self.last_grad_norm = norms, norms[-1]
+        self.step_count += steps
         self._updated()
         return sums
 
@@ -387,39 +424,20 @@ class GNNTrainer(_Trainer):
                  max_grad_norm=None):
         if not getattr(model, "fused", True):
             model._require_fused("GNNTrainer (the fused training kernels)")
-        self.model = model
-        self.lib = _lib.load()
         sd = model.state_dict()
-        self.params = [sd[k] for k in STATE_DICT_KEYS]
-        self.dev = _lib.require_gpu(self.params[0].device)
-        for p in self.params:
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise ValueError("training needs contiguous float32 parameters")
-        self._optimiser_state()
-        self._optimiser_controls(weight_decay, decoupled, decay_all, max_grad_norm)
-        self.N = model.board_size
+        self._setup(model, [sd[k] for k in STATE_DICT_KEYS], max_batch, betas, eps, (weight_decay, decoupled, decay_all, max_grad_norm))
         self.V = self.N * self.N
-        self.A = model.policy_output_size
-        self.max_batch = int(max_batch)
-        self.step_count = 0
-        self.betas, self.eps = betas, eps
         B, A, H = self.max_batch, self.A, HIDDEN_DIM
         f = dict(dtype=torch.float32, device=self.dev)
-        w = self.ws = dict(
+        self.ws = dict(
             h1=torch.empty((B * 96, H), **f), h2=torch.empty((B * 96, H), **f),    # 96 rows per position: include/aqgnn.h
             g=torch.empty((B, H), **f), hp=torch.empty((B, H // 2), **f),
             hv=torch.empty((B, H // 2), **f), dhp=torch.empty((B, H // 2), **f), dhv=torch.empty((B, H // 2), **f),
             lg=torch.empty((B, A), **f), pol=torch.empty((B, A), **f), vp=torch.empty((B,), **f), val=torch.empty((B,), **f),
             loss=torch.empty((B, 2), **f), part=torch.empty((B * _lib.TRAIN_PART_FLOATS,), **f))
-        t = self.t = _lib.TrainStruct()
-        t.board_size, t.policy_size = self.N, self.A
-        t.beta1, t.beta2, t.eps = float(betas[0]), float(betas[1]), float(eps)
-        for name, tensors in (("params", self.params), ("grads", self.grads), ("adam_m", self.adam_m), ("adam_v", self.adam_v)):
-            arr = getattr(t, name)
-            for i, x in enumerate(tensors):
-                arr[i] = x.data_ptr()
-        for name, x in w.items():
-            setattr(t, name, x.data_ptr())
+        self._fill(_lib.TrainStruct())
+        for name, x in self.ws.items():
+            setattr(self.t, name, x.data_ptr())
 
     def _batch_losses(self, B):
         return self.ws["loss"][:B].mean(dim=0)
@@ -450,41 +468,11 @@ class GeneralTrainer(_Trainer):
         if getattr(model, "num_features", NUM_FEATURES) != NUM_FEATURES:
             raise ValueError(f"GeneralTrainer trains on board records, which have {NUM_FEATURES} feature planes; this network takes "
                              f"num_features={model.num_features}")
-        self.model = model
-        self.lib = _lib.load()
-        self.params = [p for _, p in model._ordered_params()]
-        for p in self.params:
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise ValueError("training needs contiguous float32 parameters")
-        self.dev = _lib.require_gpu(self.params[0].device)
-        if any(p.device != self.dev for p in self.params):
-            raise ValueError("every parameter must be on the trainer's GPU")
-        self._optimiser_state()
-        self._optimiser_controls(weight_decay, decoupled, decay_all, max_grad_norm)
-        self.N = model.board_size
-        self.A = model.policy_output_size
-        self.max_batch = int(max_batch)
-        if self.max_batch < 1:
-            raise ValueError("max_batch must be >= 1")
-        self.step_count = 0
-        self.betas, self.eps = betas, eps
-        B, A = self.max_batch, self.A
-        f = dict(dtype=torch.float32, device=self.dev)
-        nws = int(self.lib.aqg_gcn_train_general_workspace_floats(self.N, model.hidden_dim, model.num_gcn_layers, A, B))
-        if nws == 0:
-            _lib.check(-1, "aqg_gcn_train_general_workspace_floats (shape or board size outside the kernels' limits)")
-        self.ws = dict(workspace=torch.empty((nws,), **f), pol=torch.empty((B, A), **f), val=torch.empty((B,), **f),
-                       loss=torch.empty((B, 2), **f), loss_mean=torch.zeros((2,), **f))
-        t = self.t = _lib.TrainGeneralStruct()
-        t.board_size, t.num_features, t.hidden, t.num_layers, t.policy_size = (self.N, NUM_FEATURES, model.hidden_dim,
-                                                                               model.num_gcn_layers, A)
-        t.beta1, t.beta2, t.eps = float(betas[0]), float(betas[1]), float(eps)
-        for name, tensors in (("params", self.params), ("grads", self.grads), ("adam_m", self.adam_m), ("adam_v", self.adam_v)):
-            arr = getattr(t, name)
-            for i, x in enumerate(tensors):
-                arr[i] = x.data_ptr()
-        t.policy, t.value, t.loss, t.loss_mean = (self.ws[k].data_ptr() for k in ("pol", "val", "loss", "loss_mean"))
-        t.workspace, t.workspace_floats = self.ws["workspace"].data_ptr(), nws
+        self._setup(model, [p for _, p in model._ordered_params()], max_batch, betas, eps,
+                    (weight_decay, decoupled, decay_all, max_grad_norm),
+                    workspace=("aqg_gcn_train_general_workspace_floats", (model.hidden_dim, model.num_gcn_layers)))
+        self._fill(_lib.TrainGeneralStruct())
+        self.t.num_features, self.t.hidden, self.t.num_layers = NUM_FEATURES, model.hidden_dim, model.num_gcn_layers
 
     def _batch_losses(self, B):
         return self.ws["loss_mean"].clone()          # summed in position order by the library
@@ -511,64 +499,31 @@ class CNNTrainer(_Trainer):
     BatchNorm: a step under a process group of more than one rank raises ValueError."""
 
     _STEP, _STEPS = "aqg_cnn_train_step", "aqg_cnn_train_steps"
+    _GPU_REFUSAL = "CNNTrainer trains a model on the GPU: move it there first (model.to('cuda'))"
 
     def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, decay_all=False,
                  max_grad_norm=None):
         from .pv_network_cnn import CNNNetwork
         if not isinstance(model, CNNNetwork):
             raise ValueError("CNNTrainer trains a pv_network_cnn.CNNNetwork")
-        self.model = model
-        self.lib = _lib.load()
-        self.params = list(model.parameters())
-        for p in self.params:
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise ValueError("training needs contiguous float32 parameters")
         self.bns = [cb.bn for cb in model._convs()]
         for bn in self.bns:
             if bn.momentum is None:
                 raise ValueError("BatchNorm2d(momentum=None) (a cumulative moving average) is not supported")
             if not bn.track_running_stats or bn.running_mean is None:
                 raise ValueError("BatchNorm2d(track_running_stats=False) is not supported")
-        if self.params[0].device.type != "cuda":
-            raise ValueError("CNNTrainer trains a model on the GPU: move it there first (model.to('cuda'))")
-        self.dev = _lib.require_gpu(self.params[0].device)
-        self.buffers = [b for bn in self.bns for b in (bn.running_mean, bn.running_var)]
-        for x in self.params + self.buffers:
-            if x.device != self.dev:
-                raise ValueError("every parameter and running statistic must be on the trainer's GPU")
-            if x.dtype != torch.float32 or not x.is_contiguous():
-                raise ValueError("training needs contiguous float32 parameters and running statistics")
-        self._optimiser_state()
-        self._optimiser_controls(weight_decay, decoupled, decay_all, max_grad_norm)
-        self.N = model.board_size
-        self.A = model.policy_output_size
-        self.max_batch = int(max_batch)
-        if self.max_batch < 1:
-            raise ValueError("max_batch must be >= 1")
-        self.step_count = 0
-        self.betas, self.eps = betas, eps
-        B, A = self.max_batch, self.A
-        f = dict(dtype=torch.float32, device=self.dev)
-        F_, L = model.num_filters, model.num_residual_blocks
-        nws = int(self.lib.aqg_cnn_train_workspace_floats(self.N, F_, L, A, B))
-        if nws == 0:
-            _lib.check(-1, "aqg_cnn_train_workspace_floats (shape or board size outside the kernels' limits)")
-        self.ws = dict(workspace=torch.empty((nws,), **f), pol=torch.empty((B, A), **f), val=torch.empty((B,), **f),
-                       loss=torch.empty((B, 2), **f), loss_mean=torch.zeros((2,), **f))
+        self._setup(model, model.parameters(), max_batch, betas, eps, (weight_decay, decoupled, decay_all, max_grad_norm),
+                    buffers=[b for bn in self.bns for b in (bn.running_mean, bn.running_var)],
+                    workspace=("aqg_cnn_train_workspace_floats", (model.num_filters, model.num_residual_blocks)))
         # the Adam launch's tensor table, on the device: params | grads | adam_m | adam_v
         self.table = torch.tensor([x.data_ptr() for x in self.params + self.grads + self.adam_m + self.adam_v], dtype=torch.int64,
                                   device=self.dev)
-        t = self.t = _lib.CnnTrainStruct()
-        t.board_size, t.num_filters, t.num_blocks, t.policy_size = self.N, F_, L, A
-        t.beta1, t.beta2, t.eps = float(betas[0]), float(betas[1]), float(eps)
+        t = _lib.CnnTrainStruct()
+        self._fill(t)
+        t.num_filters, t.num_blocks, t.adam_table = model.num_filters, model.num_residual_blocks, self.table.data_ptr()
         for i, bn in enumerate(self.bns):
             t.bn_eps[i], t.bn_momentum[i] = float(bn.eps), float(bn.momentum)
             t.running_mean[i], t.running_var[i] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-        for i, (p, g) in enumerate(zip(self.params, self.grads)):
-            t.params[i], t.grads[i] = p.data_ptr(), g.data_ptr()
-        t.adam_table = self.table.data_ptr()
-        t.policy, t.value, t.loss, t.loss_mean = (self.ws[k].data_ptr() for k in ("pol", "val", "loss", "loss_mean"))
-        t.workspace, t.workspace_floats = self.ws["workspace"].data_ptr(), nws
 
     def step(self, states72, pi_target, z_target, lr=LEARNING_RATE, update=True, group=None, mirror=None):
         import torch.distributed as dist
@@ -635,38 +590,49 @@ def train_network():
     AQG_TRAIN_DATA_PARALLEL=1 selects the data-parallel form anyway (same shuffle on all ranks, the positions of every batch
     dealt out over the ranks, one all-reduce of the flat gradient buffer per step, GNNTrainer.step); rank 0 writes latest.pth."""
     import os
-    import torch.distributed as dist
     from .pv_network_cnn import is_cnn_state_dict
     best = PV_NETWORK_PATH + 'best.pth'
     if os.path.exists(best) and is_cnn_state_dict(torch.load(best, map_location="cpu", weights_only=True)):
         raise NotImplementedError(CNN_TRAINING_NOT_BUILT)
+    _train(load_network, trainer_for, data_parallel=os.environ.get("AQG_TRAIN_DATA_PARALLEL", "0") == "1")
+
+
+def train_cnn_network():
+    """train_network.py:26-107 on the reference's residual CNN: best.pth (a CNNNetwork of any shape) -> NUM_EPOCH epochs over the
+    newest .history, every step on HIP (CNNTrainer) -> latest.pth with every state_dict key (202 at 128 filters x 16 blocks).
+    Under torch.distributed rank 0 trains alone and the others wait (synchronised BatchNorm is not built)."""
+    from .pv_network_cnn import load_network as load_cnn
+    _train(load_cnn, lambda model, max_batch: CNNTrainer(model, max_batch=max_batch, **_configured_controls()), data_parallel=False)
+
+
+def _train(load, make_trainer, data_parallel):
+    """The epochs of _train_loop on this process alone, on every rank of the process group (data_parallel), or else on rank 0 ALONE
+    while the other ranks wait."""
+    import torch.distributed as dist
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
-    if world > 1 and os.environ.get("AQG_TRAIN_DATA_PARALLEL", "0") != "1":
-        from . import distributed as aqd
-        tag = aqd.next_tag("train")
-        if rank == 0:
-            with aqd.single_rank_stage(tag):       # published on failure too (value b"fail"): the idle ranks raise instead of waiting
-                _train_single_process()
-        else:
-            aqd.wait_for_rank0(tag)     # host-side wait on the rendezvous store: no collective is pending while rank 0 trains, so
-                                        # the stage may outlast the process group's watchdog timeout (distributed.py)
-        dist.barrier()          # latest.pth is complete before any rank moves on to the evaluation stage
-        return
-    _train_loop(rank, world)
+    if world == 1 or data_parallel:
+        return _train_loop(load, make_trainer, rank, world)
+    from . import distributed as aqd
+    tag = aqd.next_tag("train")
+    if rank == 0:
+        with aqd.single_rank_stage(tag):       # published on failure too (value b"fail"): the idle ranks raise instead of waiting
+            _train_loop(load, make_trainer, 0, 1)
+    else:
+        aqd.wait_for_rank0(tag)     # host-side wait on the rendezvous store: no collective is pending while rank 0 trains, so
+                                    # the stage may outlast the process group's watchdog timeout (distributed.py)
+    dist.barrier()          # latest.pth is complete before any rank moves on to the evaluation stage
 
 
-def _train_single_process():
-    _train_loop(0, 1)
-
-
-def _train_loop(rank, world):
+def _train_loop(load, make_trainer, rank, world):
+    """best.pth through `load`, NUM_EPOCH epochs on the trainer `make_trainer(model, max_batch=)` gives, latest.pth.  world > 1: the
+    data-parallel form, every batch dealt out over the ranks."""
     import torch.distributed as dist
     from . import distributed as aqd
     dev = aqd.device()                                                             # this rank's GPU, explicitly
-    model = load_network(PV_NETWORK_PATH + 'best.pth', dev)                       # GNNNetwork, or the shape best.pth holds
+    model = load(PV_NETWORK_PATH + 'best.pth', dev)                                # GNNNetwork, or the shape best.pth holds
     s, p, v, index = _training_rows(dev, model.board_size)
     n = s.shape[0] if index is None else index.shape[0]
-    trainer = trainer_for(model, max_batch=BATCH_SIZE)
+    trainer = make_trainer(model, max_batch=BATCH_SIZE)
     for epoch in range(NUM_EPOCH):
         lr = LEARNING_RATE * lr_lambda(epoch)                                      # LambdaLR, stepped once per epoch (:98)
         perm = torch.randperm(n, device=dev)                                    # DataLoader(shuffle=True), last batch kept
@@ -699,43 +665,6 @@ def _train_loop(rank, world):
         torch.save(model.state_dict(), PV_NETWORK_PATH + 'latest.pth')
     if world > 1:
         dist.barrier()          # latest.pth is complete before any rank moves on to the evaluation stage
-
-
-def train_cnn_network():
-    """train_network.py:26-107 on the reference's residual CNN: best.pth (a CNNNetwork of any shape) -> NUM_EPOCH epochs over the
-    newest .history, every step on HIP (CNNTrainer) -> latest.pth with every state_dict key (202 at 128 filters x 16 blocks).
-    Under torch.distributed rank 0 trains alone and the others wait (synchronised BatchNorm is not built)."""
-    import torch.distributed as dist
-    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
-    if world > 1:
-        from . import distributed as aqd
-        tag = aqd.next_tag("train")
-        if rank == 0:
-            with aqd.single_rank_stage(tag):
-                _train_cnn_loop()
-        else:
-            aqd.wait_for_rank0(tag)
-        dist.barrier()          # latest.pth is complete before any rank moves on to the evaluation stage
-        return
-    _train_cnn_loop()
-
-
-def _train_cnn_loop():
-    from . import distributed as aqd
-    from .pv_network_cnn import load_network as load_cnn
-    dev = aqd.device()
-    model = load_cnn(PV_NETWORK_PATH + 'best.pth', dev)
-    s, p, v, index = _training_rows(dev, model.board_size)
-    n = s.shape[0] if index is None else index.shape[0]
-    trainer = CNNTrainer(model, max_batch=BATCH_SIZE, **_configured_controls())
-    for epoch in range(NUM_EPOCH):
-        lr = LEARNING_RATE * lr_lambda(epoch)                                      # LambdaLR, stepped once per epoch (:98)
-        perm = torch.randperm(n, device=dev)                                    # DataLoader(shuffle=True), last batch kept
-        epoch_policy_loss, epoch_value_loss = trainer.run_epoch(s, p, v, _epoch_order(perm, index), lr=lr,
-                                                                 mirror=(TRAIN_MIRROR_SEED, epoch) if TRAIN_MIRROR else None)
-        print(_progress_line(epoch, epoch_policy_loss, epoch_value_loss, trainer), end='')
-    print('')
-    torch.save(model.state_dict(), PV_NETWORK_PATH + 'latest.pth')
 
 
 if __name__ == '__main__':

@@ -712,7 +712,8 @@ long long aqg_gcn_train_fallbacks(int reset);
  *   be NULL (it then lives in the workspace).  workspace: aqg_gcn_train_general_workspace_floats(board_size, hidden, num_layers,
  *   policy_size, max_batch) floats serve every batch up to max_batch.
  * aqg_gcn_train_step_general: mode 0 = gradients only (into grads), 1 = gradients + Adam, 2 = Adam only from whatever grads holds
- *   (data parallel: local gradients, all-reduce, update), as aqg_gcn_train_step.
+ *   (data parallel: local gradients, all-reduce, update), as aqg_gcn_train_step.  batch 0: no gradients are formed, and mode 1
+ *   still applies Adam from whatever grads holds, as mode 2 does (the CNN's step differs: below).
  * aqg_gcn_train_steps_general: one epoch, every step mode 1, as aqg_gcn_train_steps: step i takes the positions
  *   order[i*batch .. (i+1)*batch) (order NULL = 0 .. positions-1; the last batch may be short), t->step counts up from its entry
  *   value, and each step adds its two batch-mean losses to loss_sums[2] (device, may be NULL). */
@@ -754,7 +755,8 @@ int aqg_gcn_train_steps_general(const aqg_train_general* t_host, const uint8_t* 
  *   adam_v, each in tensor order (the same params / grads as above) -- built once by the caller: the single Adam launch reads it
  *   (247 tensors at 40 blocks would not fit in kernel arguments).  policy / value / loss / loss_mean as in struct aqg_train_general: each
  *   may be NULL.  workspace: aqg_cnn_train_workspace_floats(board_size, num_filters, num_blocks, policy_size, max_batch) floats.
- * aqg_cnn_train_step: mode 0 = gradients only, 1 = gradients + Adam, 2 = Adam only, as aqg_gcn_train_step_general; batch 0 = no-op.
+ * aqg_cnn_train_step: mode 0 = gradients only, 1 = gradients + Adam, 2 = Adam only, as aqg_gcn_train_step_general; batch 0 = no-op
+ *   (modes 0 and 1; mode 2 never reads the batch).
  * aqg_cnn_train_steps: one epoch, every step mode 1, with the order / loss_sums contract of aqg_gcn_train_steps_general. */
 #define AQG_CNN_TRAIN_CONVS (2 * AQG_CNN_MAX_BLOCKS + 1)
 #define AQG_CNN_TRAIN_TENSORS (3 * AQG_CNN_TRAIN_CONVS + 4)

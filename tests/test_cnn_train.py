@@ -235,6 +235,46 @@ def test_run_epoch_equals_single_steps_and_is_deterministic(dev):
     assert _sync_count(lambda: tb.step(s, p, zz)) == 0
 
 
+def test_empty_batch_rule_of_each_workspace_trainer(dev):
+    """What a mode-1 step does with batch == 0 (include/aqgnn.h; the one trait in which the two kinds of csrc/train_driver.hpp differ),
+    bit for bit on 3x3 boards.  The any-shape GNN (6, 8, 1): it applies Adam from whatever grads holds, as mode 2 does.  The CNN
+    (2 filters, no block): it is a no-op -- parameters, moments and running statistics stay as they were."""
+    from alphaquoridorgnn_amd.train_network import CNNTrainer, GeneralTrainer
+    from tests.test_gnn_any_shape import _make_net as _make_gnn
+    N, B = 3, 2
+    pi, z = _targets(B, _A(N), 4)
+    S, P, Z = torch.from_numpy(_states(N, B)).to(dev), torch.from_numpy(pi).to(dev), torch.from_numpy(z).to(dev)
+
+    def general(second_mode, second_batch):
+        net = _make_gnn((6, 8, 1), _A(N), seed=17, N=N)
+        tr = GeneralTrainer(net, max_batch=B)
+        before = [p.detach().clone() for p in tr.params]
+        tr.t.batch, tr.t.step, tr.t.lr = B, 1, 1e-3
+        tr._call(S, P, Z, 0)
+        tr.t.batch = second_batch
+        tr._call(S, P, Z, second_mode)
+        return tr, before
+
+    a, before = general(2, B)
+    b, _ = general(1, 0)
+    assert any(not torch.equal(x, y) for x, y in zip(a.params, before))           # the update happened
+    for x, y in zip(a.params + a.adam_m + a.adam_v, b.params + b.adam_m + b.adam_v):
+        assert torch.equal(x, y)
+
+    net = _make_net(2, 0, N, seed=6).to(dev)
+    tr = CNNTrainer(net, max_batch=B)
+    tr.t.batch, tr.t.step, tr.t.lr = B, 1, 1e-3
+    tr._call(S, P, Z, 0)
+    kept = tr.params + tr.adam_m + tr.adam_v + tr.buffers
+    was = [x.detach().clone() for x in kept]
+    tr.t.batch = 0
+    tr._call(S, P, Z, 1)
+    torch.cuda.synchronize()
+    for x, y in zip(kept, was):
+        assert torch.equal(x, y)
+    assert float(tr.flat_grads.abs().max()) > 0                                    # there were gradients to apply
+
+
 @pytest.mark.parametrize("cache", [0, 64])
 def test_trained_weights_reach_the_engine(dev, cache):
     """After a step (and after an epoch call) and refresh_weights(), a 'cnn' engine's root priors are those of the eval-mode forward

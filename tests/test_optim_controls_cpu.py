@@ -245,6 +245,87 @@ def test_optim_entry_points_refuse_on_the_host(kind):
     assert "step must be >= 1" in lib.aqg_last_error().decode()
 
 
+def _set(**fields):
+    def change(t):
+        for k, v in fields.items():
+            setattr(t, k, v)
+    return change
+
+
+def _no_tensors(t):
+    for i in range(len(t.params)):
+        t.params[i] = None
+
+
+def _index(name, i, value):
+    def change(t):
+        getattr(t, name)[i] = value
+    return change
+
+
+# (change to a good struct, mode, states72 given, message): what the plain step entry refuses on the host in
+# test_train_general_cpu / test_cnn_train_cpu (test_entry_points_check_arguments_on_the_host), and the fused kind's own three
+_BAD_MODE, _NO_STATES = (_set(), 3, True, "bad argument"), (_set(), 1, False, "null argument")
+STEP_REFUSALS = {
+    "fused": [_BAD_MODE, _NO_STATES, (_no_tensors, 1, True, "null parameter tensor"), (_set(step=0), 1, True, "step must be >= 1")],
+    "general": [_BAD_MODE, _NO_STATES, (_set(board_size=4), 1, True, "board_size"), (_set(hidden=1), 1, True, "hidden"),
+                (_set(hidden=2048), 1, True, "hidden"), (_set(num_layers=0), 1, True, "num_layers"),
+                (_set(num_layers=33), 1, True, "num_layers"), (_set(policy_size=0), 1, True, "policy_size"),
+                (_set(policy_size=5000), 1, True, "policy_size"), (_set(step=0), 1, True, "step"),
+                (_no_tensors, 1, True, "null parameter"), (_set(num_features=8), 1, True, "num_features"),
+                (_set(batch=-1), 0, True, "negative batch"), (_set(), 1, True, "workspace too small")],
+    "cnn": [_BAD_MODE, _NO_STATES, (_set(board_size=4), 1, True, "board_size"), (_set(num_filters=0), 1, True, "num_filters"),
+            (_set(num_filters=513), 1, True, "num_filters"), (_set(num_blocks=41), 1, True, "num_blocks"),
+            (_set(num_blocks=-1), 1, True, "num_blocks"), (_set(policy_size=40), 1, True, "policy_size"),
+            (_no_tensors, 1, True, "null parameter"), (_index("running_var", 2, None), 1, True, "running statistics"),
+            (_index("bn_momentum", 0, 1.5), 1, True, "bn_momentum"), (_index("bn_eps", 2, 0.0), 1, True, "bn_eps"),
+            (_set(adam_table=None), 1, True, "adam_table"), (_set(step=0), 1, True, "step"),
+            (_set(), 1, True, "workspace too small"), (_set(batch=-1), 0, True, "negative batch")],
+}
+# (change, positions, states72 given, message) of the steps entry
+STEPS_REFUSALS = {
+    "fused": [(_set(), -1, True, "bad argument"), (_set(), 8, False, "bad argument"), (_no_tensors, 8, True, "null parameter tensor"),
+              (_set(step=0), 8, True, "step must be >= 1")],
+    "general": [(_set(), 10, True, "workspace too small"), (_set(batch=0), 10, True, "batch"), (_set(), -1, True, "bad argument"),
+                (_set(), 10, False, "bad argument")],
+    "cnn": [(_set(), -1, True, "bad argument"), (_set(), 4, False, "bad argument"), (_set(batch=0), 4, True, "batch"),
+            (_set(), 4, True, "workspace too small"), (_no_tensors, 4, True, "null parameter")],
+}
+
+
+@pytest.mark.parametrize("kind", list(ENTRY))
+def test_optim_forms_make_the_plain_calls_refusals(kind):
+    """Every host-side refusal of a plain step / steps entry comes out of its _optim form too, with an all-off (zeroed) aqg_optim:
+    the same sign and the same words.  Never-dereferenced pointers: each call returns on the host before any launch."""
+    _lib, lib = _lib_or_fail()
+    step_name, steps_name, make = ENTRY[kind]
+    dummy, off = ctypes.c_void_p(4096), _lib.OptimStruct()
+
+    def both(name, change, args, msg):
+        t, _ = make(_lib)
+        change(t)
+        plain = getattr(lib, name[:-len("_optim")])(ctypes.byref(t), *args, None)
+        plain_said = lib.aqg_last_error().decode()
+        optim = getattr(lib, name)(ctypes.byref(t), *args, ctypes.byref(off), None)
+        optim_said = lib.aqg_last_error().decode()
+        if msg is None:
+            assert plain == 0 and optim == 0, (name, plain, optim)
+        else:
+            assert plain < 0 and optim < 0, (name, msg, plain, optim)
+            assert msg in plain_said and msg in optim_said, (name, msg, plain_said, optim_said)
+
+    for change, mode, states, msg in STEP_REFUSALS[kind]:
+        both(step_name, change, (dummy if states else None, dummy, dummy, mode), msg)
+    for change, positions, states, msg in STEPS_REFUSALS[kind]:
+        both(steps_name, change, (dummy if states else None, dummy, dummy, None, positions, None), msg)
+    for name in (step_name, steps_name):                       # a null struct, through both forms
+        args = (dummy, dummy, dummy, 1) if name == step_name else (dummy, dummy, dummy, None, 8, None)
+        assert getattr(lib, name[:-len("_optim")])(None, *args, None) < 0 and getattr(lib, name)(None, *args, ctypes.byref(off), None) < 0
+    if kind == "cnn":                                          # batch 0, mode 0: nothing to do, nothing launched
+        both(step_name, _set(batch=0), (dummy, dummy, dummy, 0), None)
+        both(step_name, _set(batch=0), (None, dummy, dummy, 0), None)
+
+
 def test_grad_norm_refusals_and_workspace():
     _lib, lib = _lib_or_fail()
     f = lib.aqg_optim_workspace_floats

@@ -1,10 +1,13 @@
 """Bit-identity of two builds of libaqgnn_hip.so on the same inputs (cleanup / refactoring check).
 
-    python tools/compare_libs.py tools/ubench/bin/libaqgnn_r3.so alphaquoridorgnn_amd/libaqgnn_hip.so
+    OUT=/tmp/parent/libaqgnn_hip.so <checkout of the parent commit>/alphaquoridorgnn_amd/csrc/build.sh
+    python tools/compare_libs.py /tmp/parent/libaqgnn_hip.so alphaquoridorgnn_amd/libaqgnn_hip.so
 
 Each library runs in its own process (AQG_LIB_PATH): the GNN forward at 300 / 4,096 / 1,001 boards in both guard modes, a masked engine
-launch inside a 64-game GNN-evaluated generation (history rows), and three training steps.  Prints one line per item; exit code 1
-on any difference."""
+launch inside a 64-game GNN-evaluated generation (history rows), three training steps, and then every trainer (GeneralTrainer (6, 32, 2)
+and CNNTrainer 8 filters x 1 block on 5x5, GNNTrainer on 9x9 and on 5x5) at max_batch 4 through steps of 4, 4 and 3 positions, a shuffled
+epoch of 10, both again with weight decay and clipping on, and a mode-0 then a mode-2 call: parameters, Adam moments, losses, gradient
+norms and running statistics.  Prints one line per item; exit code 1 on any difference."""
 import os
 import subprocess
 import sys
@@ -18,8 +21,9 @@ sys.path.insert(0, sys.argv[1])
 import numpy as np, torch
 from alphaquoridorgnn_amd import _lib
 from alphaquoridorgnn_amd.engine import BatchedSelfPlay
-from alphaquoridorgnn_amd.pv_network_gnn import GNNNetwork
-from alphaquoridorgnn_amd.train_network import GNNTrainer
+from alphaquoridorgnn_amd.pv_network_cnn import CNNNetwork
+from alphaquoridorgnn_amd.pv_network_gnn import GNNNetwork, GraphPolicyValueNetwork
+from alphaquoridorgnn_amd.train_network import CNNTrainer, GeneralTrainer, GNNTrainer
 from tools.microbench import synth_states
 from oracle import gnn as og
 dev = torch.device("cuda", 0)
@@ -53,6 +57,39 @@ for i in range(3):
     tr.step(st, pi, zz)
 for k, t in tm.state_dict().items():
     out["param_" + k] = t.cpu().numpy()
+# every trainer at max_batch 4: single steps, an epoch, both again with the controls on, modes 0 and 2
+walk5 = torch.from_numpy(np.load(os.path.join(sys.argv[1], "tests", "golden", "walk_5x5.npz"))["states"]).to(dev)
+def trainers(controls):
+    torch.manual_seed(7)
+    yield "general", 5, GeneralTrainer(GraphPolicyValueNetwork(6, 32, 2, 57, board_size=5).to(dev), max_batch=4, **controls)
+    yield "cnn", 5, CNNTrainer(CNNNetwork(8, 1, board_size=5).to(dev), max_batch=4, **controls)
+    yield "fused9", 9, GNNTrainer(GNNNetwork().to(dev), max_batch=4, **controls)
+    yield "fused5", 5, GNNTrainer(GraphPolicyValueNetwork(6, 128, 3, 57, board_size=5).to(dev), max_batch=4, **controls)
+def dump(tag, tr):
+    for i, tensors in enumerate(zip(tr.params, tr.adam_m, tr.adam_v)):
+        for name, t in zip(("param", "adam_m", "adam_v"), tensors):
+            out[f"{tag}_{name}{i}"] = t.detach().cpu().numpy()
+    for i, t in enumerate(getattr(tr, "buffers", [])):
+        out[f"{tag}_running{i}"] = t.cpu().numpy()
+    out[tag + "_loss"], out[tag + "_last_norm"], out[tag + "_norms"] = (t.cpu().numpy() for t in (tr.ws["loss"], tr.last_grad_norm, tr.grad_norms))
+for ctag, controls in (("plain", {}), ("optim", dict(weight_decay=1e-2, max_grad_norm=0.5))):
+    for kind, N, tr in trainers(controls):
+        A, tag = N * N + 2 * (N - 1) ** 2, f"{kind}_{ctag}"
+        rng = np.random.RandomState(N)
+        S = synth_states(10, seed=70, dev=dev) if N == 9 else walk5[::max(1, walk5.shape[0] // 10)][:10].contiguous()
+        P = torch.softmax(torch.from_numpy(rng.randn(10, A).astype(np.float32)), 1).to(dev)
+        Z = torch.from_numpy(rng.choice([-1.0, 0.0, 1.0], 10).astype(np.float32)).to(dev)
+        for lo, hi in ((0, 4), (4, 8), (7, 10)):
+            pl, vl = tr.step(S[lo:hi], P[lo:hi], Z[lo:hi])
+            out[f"{tag}_step_losses_{lo}"] = torch.stack([pl, vl]).cpu().numpy()
+        dump(tag + "_steps", tr)
+        out[tag + "_epoch_sums"] = tr.run_epoch(S, P, Z, torch.from_numpy(np.random.RandomState(3).permutation(10))).cpu().numpy()
+        dump(tag + "_epoch", tr)
+        tr.t.batch, tr.t.step = 4, tr.step_count + 1
+        tr._call(S[:4].contiguous(), P[:4].contiguous(), Z[:4].contiguous(), 0)
+        out[tag + "_mode0_grads"] = tr.flat_grads.cpu().numpy()
+        tr._call(S[:4].contiguous(), P[:4].contiguous(), Z[:4].contiguous(), 2)
+        dump(tag + "_modes", tr)
 np.savez(sys.argv[2], **out)
 '''
 
@@ -71,7 +108,7 @@ def main():
     for k in ra.files:
         same = np.array_equal(ra[k], rb[k], equal_nan=True)
         d = 0.0 if same else float(np.abs(ra[k].astype(np.float64) - rb[k].astype(np.float64)).max())
-        print(f"{k:32s} {'identical' if same else 'DIFFERENT  max |d| = %g' % d}")
+        print(f"{k:40s} {'identical' if same else 'DIFFERENT  max |d| = %g' % d}")
         bad += 0 if same else 1
     print("all identical" if not bad else f"{bad} items differ")
     return 1 if bad else 0
