@@ -182,6 +182,7 @@ SIGNATURES = {
     "aqg_engine_root_noise": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),
     "aqg_engine_root_priors": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp, _vp]),
     "aqg_engine_root_values": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
+    "aqg_engine_root_improved_policy": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.c_double, _c.c_double, _vp, _vp, _vp, _vp, _vp]),
     "aqg_engine_root_states72": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_engine_apply_actions": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_agent_random": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp, _c.c_int, _c.c_uint64, _vp, _vp]),
@@ -218,6 +219,7 @@ SIGNATURES = {
     "aqg_replay_append": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
     "aqg_replay_append_blend": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _f32, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
     "aqg_replay_refresh": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _f32, _vp, _c.c_int, _c.c_int, _vp, _vp, _vp]),
+    "aqg_replay_refresh_policy": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _f32, _vp, _c.c_int, _c.c_int, _vp, _vp, _vp]),
     "aqg_replay_position_keys": (_c.c_int, [_vp, _vp, _c.c_int, _vp, _vp]),
     "aqg_replay_run_heads": (_c.c_int, [_vp, _vp, _c.c_int, _vp, _vp]),
     "aqg_replay_merge_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),

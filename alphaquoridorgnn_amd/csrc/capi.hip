@@ -340,6 +340,11 @@ int aqg_engine_root_values(const aqg_engine* e, float* value, void* stream) {
     if (!e || !value) return fail("aqg_engine_root_values: null argument");
     return engine_root_values(*e, value, (hipStream_t)stream);
 }
+int aqg_engine_root_improved_policy(const aqg_engine* e, double c_visit, double c_scale, float* policy, uint8_t* actions, int32_t* count,
+                                    float* vmix, void* stream) {
+    if (!e || !policy || !actions || !count || !vmix) return fail("aqg_engine_root_improved_policy: null argument");
+    return engine_root_improved_policy(*e, c_visit, c_scale, policy, actions, count, vmix, (hipStream_t)stream);
+}
 
 int aqg_engine_root_states72(const aqg_engine* e, uint8_t* out72, void* stream) {
     if (!e || !out72) return fail("aqg_engine_root_states72: null argument");
@@ -537,6 +542,12 @@ int aqg_replay_refresh(int board_size, int policy_size, const int32_t* visits, c
                        float* ring_z, void* stream) {
     return launch_replay_refresh(board_size, policy_size, visits, actions, count, search_value, blend, slots, n, capacity, ring_pi,
                                  ring_z, (hipStream_t)stream);
+}
+int aqg_replay_refresh_policy(int board_size, int policy_size, const float* policy, const uint8_t* actions, const int32_t* count,
+                              const float* search_value, float blend, const int64_t* slots, int n, int capacity, float* ring_pi,
+                              float* ring_z, void* stream) {
+    return launch_replay_refresh_policy(board_size, policy_size, policy, actions, count, search_value, blend, slots, n, capacity, ring_pi,
+                                        ring_z, (hipStream_t)stream);
 }
 
 int aqg_replay_position_keys(const uint8_t* states72, const int64_t* index, int n, int64_t* keys, void* stream) {

@@ -112,6 +112,8 @@ int engine_refill(const aqg_engine& e, hipStream_t st);
 int engine_root_noise(const aqg_engine& e, hipStream_t st);
 int engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st);
 int engine_root_values(const aqg_engine& e, float* value, hipStream_t st);
+int engine_root_improved_policy(const aqg_engine& e, double c_visit, double c_scale, float* policy, uint8_t* actions, int32_t* count,
+                                float* vmix, hipStream_t st);
 int engine_keep_subtrees(const aqg_engine& e, const aqg_tree_reuse& ru, const int32_t* child_index, hipStream_t st);
 int engine_reset_reuse(const aqg_engine& e, const aqg_tree_reuse& ru, hipStream_t st);
 int engine_reset_resign(const aqg_engine& e, const aqg_resign& rs, hipStream_t st);
@@ -141,6 +143,10 @@ void launch_engine_root_priors(const aqg_engine& e, float* priors, int32_t* coun
 void launch_engine_root_values(const aqg_engine& e, float* value, hipStream_t st);
 int engine_root_states72(const aqg_engine& e, uint8_t* out72, hipStream_t st);
 int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_t st);
+
+// ---- mcts_improve.hip
+void launch_engine_root_improved_policy(const aqg_engine& e, double c_visit, double c_scale, float* policy, uint8_t* actions,
+                                        int32_t* count, float* vmix, hipStream_t st);
 
 // ---- mcts_reuse.hip
 void launch_engine_keep_subtrees(const aqg_engine& e, const aqg_tree_reuse& ru, const int32_t* child_index, hipStream_t st);
@@ -235,6 +241,9 @@ int launch_replay_append_blend(int N, int policy_size, const uint8_t* states72, 
 int launch_replay_refresh(int N, int policy_size, const int32_t* visits, const uint8_t* actions, const int32_t* count,
                           const float* search_value, float blend, const int64_t* slots, int n, int capacity, float* ring_pi,
                           float* ring_z, hipStream_t st);
+int launch_replay_refresh_policy(int N, int policy_size, const float* policy, const uint8_t* actions, const int32_t* count,
+                                 const float* search_value, float blend, const int64_t* slots, int n, int capacity, float* ring_pi,
+                                 float* ring_z, hipStream_t st);
 
 // ---- replay_merge.hip
 int launch_replay_position_keys(const uint8_t* states72, const int64_t* index, int n, int64_t* keys, hipStream_t st);

@@ -27,12 +27,15 @@
 //                   apply_actions (one engine_transition behind both), refill, root_visits / root_priors / root_states72; one plain
 //                   launcher per kernel.
 //   mcts_reuse.hip  tree reuse: engine_keep_subtrees_kernel, the in-place re-rooting of a pool at the chosen child, and its launcher.
+//   mcts_improve.hip  the completed-Q improved policy of the roots: engine_root_improved_policy_kernel, a read-out of the pool in
+//                   float64 (aqgnn.h, "completed-Q policy targets"), and its launcher.  It changes nothing the search reads.
 //   mcts.hip        this file, host code only: validate and validate_move (every refusal of a move, in one order), the simulation loop
 //                   (enqueue_sims), its hipGraph cache (run_sims), the end of a move (finish_and_refill) and the engine_* entry points:
 //                   engine_move and engine_finish_move take the move's options as one MoveOptions value (launchers.hpp).  It launches
 //                   no kernel itself.
 #include "aqg_common.hpp"
 #include <vector>
+#include <cmath>
 #include <cstring>
 #include "../../include/aqgnn.h"
 #include "launchers.hpp"
@@ -337,6 +340,16 @@ int engine_root_values(const aqg_engine& e, float* value, hipStream_t st) {
     if (int r = validate(e)) return r;
     launch_engine_root_values(e, value, st);
     return check_launch("engine_root_values_kernel");
+}
+
+// the completed-Q improved policy of the roots (mcts_improve.hip): the constants are refused here, before the launch
+int engine_root_improved_policy(const aqg_engine& e, double c_visit, double c_scale, float* policy, uint8_t* actions, int32_t* count,
+                                float* vmix, hipStream_t st) {
+    if (int r = validate(e)) return r;
+    if (!(c_visit >= 0.0) || std::isinf(c_visit)) return fail("aqg_engine_root_improved_policy: c_visit must be finite and >= 0");      // NaN fails the first
+    if (!(c_scale >= 0.0) || std::isinf(c_scale)) return fail("aqg_engine_root_improved_policy: c_scale must be finite and >= 0");
+    launch_engine_root_improved_policy(e, c_visit, c_scale, policy, actions, count, vmix, st);
+    return check_launch("engine_root_improved_policy_kernel");
 }
 
 // the slot refill alone, for a move that was applied rather than searched (engine_apply_actions, mcts_move.hip)

@@ -21,6 +21,7 @@
 // id with A.  Every loop is bounded by a constant.
 #include "aqg_common.hpp"
 #include "launchers.hpp"
+#include <cfloat>
 
 #ifdef __FAST_MATH__
 #error "replay_refresh.hip: pi = v / tot must be the correctly rounded f32 division (no fast-math)"
@@ -48,7 +49,10 @@ __device__ __forceinline__ void refresh_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int N, bool BLEND>
+// POLICY (aqg_replay_refresh_policy; aqgnn.h, "completed-Q policy targets"): the source words are f32 policy entries, not counts -- they
+// arrive through the same loads as their bits and are copied VERBATIM to their action ids: no total, no division.  A row is written
+// iff every entry j < count is finite and >= 0 and one is > 0 -- pure predicates, wave-uniform by ballot, so no order is involved.
+template <int N, bool BLEND, bool POLICY>
 __global__ __launch_bounds__(RFR_WAVES * WAVE) void replay_refresh_kernel(
         const int32_t* __restrict__ visits, const uint8_t* __restrict__ actions, const int32_t* __restrict__ count,
         const float* __restrict__ search_value, float blend, const int64_t* __restrict__ slots, int n, int capacity,
@@ -85,15 +89,28 @@ __global__ __launch_bounds__(RFR_WAVES * WAVE) void replay_refresh_kernel(
     float tot[RFR_GROUP];
 #pragma unroll
     for (int g = 0; g < RFR_GROUP; ++g) {
-        int part = 0;
+        if constexpr (POLICY) {
+            bool bad = false, some = false;
 #pragma unroll
-        for (int p = 0; p < RFR_SRC_PASSES; ++p) {
-            if (p * WAVE + lane >= c[g]) v[g][p] = 0;           // past the count (and every entry of a row with count <= 0)
-            part += v[g][p];
+            for (int p = 0; p < RFR_SRC_PASSES; ++p) {
+                if (p * WAVE + lane >= c[g]) v[g][p] = 0;       // past the count: +0.0f
+                const float f = __int_as_float(v[g][p]);
+                bad = bad || !(f >= 0.f && f <= FLT_MAX);       // negative, infinite or NaN
+                some = some || f > 0.f;
+            }
+            ok[g] = c[g] > 0 && c[g] <= MAX_LEGAL && __ballot(bad) == 0 && __ballot(some) != 0 && s[g] >= 0 && s[g] < (int64_t)capacity;
+            tot[g] = 1.f;                                       // not used
+        } else {
+            int part = 0;
+#pragma unroll
+            for (int p = 0; p < RFR_SRC_PASSES; ++p) {
+                if (p * WAVE + lane >= c[g]) v[g][p] = 0;       // past the count (and every entry of a row with count <= 0)
+                part += v[g][p];
+            }
+            const int t = refresh_wave_sum_int(part);
+            ok[g] = c[g] > 0 && c[g] <= MAX_LEGAL && t > 0 && s[g] >= 0 && s[g] < (int64_t)capacity;
+            tot[g] = (float)t;                                  // exact: < 2^24
         }
-        const int t = refresh_wave_sum_int(part);
-        ok[g] = c[g] > 0 && c[g] <= MAX_LEGAL && t > 0 && s[g] >= 0 && s[g] < (int64_t)capacity;
-        tot[g] = (float)t;                                      // exact: < 2^24
     }
     // ---- the dense rows in LDS: zeros, then the quotients at their action ids
 #pragma unroll
@@ -107,7 +124,7 @@ __global__ __launch_bounds__(RFR_WAVES * WAVE) void replay_refresh_kernel(
 #pragma unroll
         for (int p = 0; p < RFR_SRC_PASSES; ++p) {
             const int j = p * WAVE + lane;
-            if (j < c[g] && a[g][p] < (uint32_t)A) stage[wave][g][a[g][p]] = (float)v[g][p] / tot[g];
+            if (j < c[g] && a[g][p] < (uint32_t)A) stage[wave][g][a[g][p]] = POLICY ? __int_as_float(v[g][p]) : (float)v[g][p] / tot[g];
         }
     }
     refresh_wave_sync();
@@ -134,40 +151,58 @@ static bool refresh_overlap(const void* a, size_t a_bytes, const void* b, size_t
     return a && b && x < y + b_bytes && y < x + a_bytes;
 }
 
-int launch_replay_refresh(int N, int policy_size, const int32_t* visits, const uint8_t* actions, const int32_t* count,
+// both forms of the launch behind one set of checks: `rows` is visits (i32) or, POLICY, the f32 policy rows read through the same loads
+template <bool POLICY>
+static int refresh_launch(int N, int policy_size, const int32_t* rows, const uint8_t* actions, const int32_t* count,
                           const float* search_value, float blend, const int64_t* slots, int n, int capacity, float* ring_pi,
                           float* ring_z, hipStream_t st) {
-    if (!board_size_supported(N)) return fail("aqg_replay_refresh: unsupported board_size (odd 3..9)");
+    const char* what = POLICY ? "aqg_replay_refresh_policy" : "aqg_replay_refresh";
+    if (!board_size_supported(N)) return fail(what, "unsupported board_size (odd 3..9)");
     const int A = N * N + 2 * (N - 1) * (N - 1);
-    if (policy_size != A) return fail("aqg_replay_refresh: policy_size is not the board's action count N^2 + 2 (N - 1)^2");
-    if (n < 0) return fail("aqg_replay_refresh: negative row count");
-    if (capacity < 1) return fail("aqg_replay_refresh: capacity must be >= 1");
-    if (!(blend >= 0.f && blend <= 1.f)) return fail("aqg_replay_refresh: blend must be in [0, 1]");      // NaN fails both
-    if (blend != 0.f && !search_value) return fail("aqg_replay_refresh: a blend needs search_value");
+    if (policy_size != A) return fail(what, "policy_size is not the board's action count N^2 + 2 (N - 1)^2");
+    if (n < 0) return fail(what, "negative row count");
+    if (capacity < 1) return fail(what, "capacity must be >= 1");
+    if (!(blend >= 0.f && blend <= 1.f)) return fail(what, "blend must be in [0, 1]");      // NaN fails both
+    if (blend != 0.f && !search_value) return fail(what, "a blend needs search_value");
     if (n == 0) return 0;                   // nothing to write: the pointers are not looked at
     const bool blended = search_value && blend != 0.f;
-    if (!visits || !actions || !count || !slots || !ring_pi) return fail("aqg_replay_refresh: visits, actions, count, slots and ring_pi must be given");
-    if (blended && !ring_z) return fail("aqg_replay_refresh: a blend needs ring_z");
+    if (!rows || !actions || !count || !slots || !ring_pi)
+        return fail(what, POLICY ? "policy, actions, count, slots and ring_pi must be given" : "visits, actions, count, slots and ring_pi must be given");
+    if (blended && !ring_z) return fail(what, "a blend needs ring_z");
     const void* rings[2] = {ring_pi, blended ? ring_z : nullptr};
     const size_t ring_bytes[2] = {(size_t)A * sizeof(float), sizeof(float)};
-    const void* srcs[5] = {visits, actions, count, slots, blended ? search_value : nullptr};
+    const void* srcs[5] = {rows, actions, count, slots, blended ? search_value : nullptr};
     const size_t src_bytes[5] = {(size_t)MAX_LEGAL * sizeof(int32_t), (size_t)MAX_LEGAL, sizeof(int32_t), sizeof(int64_t), sizeof(float)};
     for (int o = 0; o < 2; ++o)
         for (int i = 0; i < 5; ++i)
             if (refresh_overlap(rings[o], (size_t)capacity * ring_bytes[o], srcs[i], (size_t)n * src_bytes[i]))
-                return fail("aqg_replay_refresh: a ring overlaps a source");
+                return fail(what, "a ring overlaps a source");
     if (refresh_overlap(rings[0], (size_t)capacity * ring_bytes[0], rings[1], (size_t)capacity * ring_bytes[1]))
-        return fail("aqg_replay_refresh: ring_pi overlaps ring_z");
+        return fail(what, "ring_pi overlaps ring_z");
     const dim3 grid((unsigned)(((size_t)n + RFR_ROWS - 1) / RFR_ROWS)), block(RFR_WAVES * WAVE);
     return for_board_size(N, [&](auto nn) {
         if (blended)
-            hipLaunchKernelGGL((replay_refresh_kernel<decltype(nn)::value, true>), grid, block, 0, st, visits, actions, count, search_value,
-                               blend, slots, n, capacity, ring_pi, ring_z);
+            hipLaunchKernelGGL((replay_refresh_kernel<decltype(nn)::value, true, POLICY>), grid, block, 0, st, rows, actions, count,
+                               search_value, blend, slots, n, capacity, ring_pi, ring_z);
         else
-            hipLaunchKernelGGL((replay_refresh_kernel<decltype(nn)::value, false>), grid, block, 0, st, visits, actions, count, nullptr, 0.f,
-                               slots, n, capacity, ring_pi, nullptr);
+            hipLaunchKernelGGL((replay_refresh_kernel<decltype(nn)::value, false, POLICY>), grid, block, 0, st, rows, actions, count, nullptr,
+                               0.f, slots, n, capacity, ring_pi, nullptr);
         return check_launch("replay_refresh_kernel");
     });
+}
+
+int launch_replay_refresh(int N, int policy_size, const int32_t* visits, const uint8_t* actions, const int32_t* count,
+                          const float* search_value, float blend, const int64_t* slots, int n, int capacity, float* ring_pi,
+                          float* ring_z, hipStream_t st) {
+    return refresh_launch<false>(N, policy_size, visits, actions, count, search_value, blend, slots, n, capacity, ring_pi, ring_z, st);
+}
+
+static_assert(sizeof(float) == sizeof(int32_t), "a policy row is read through the loads of a visit row");
+int launch_replay_refresh_policy(int N, int policy_size, const float* policy, const uint8_t* actions, const int32_t* count,
+                                 const float* search_value, float blend, const int64_t* slots, int n, int capacity, float* ring_pi,
+                                 float* ring_z, hipStream_t st) {
+    return refresh_launch<true>(N, policy_size, reinterpret_cast<const int32_t*>(policy), actions, count, search_value, blend, slots, n,
+                                capacity, ring_pi, ring_z, st);
 }
 
 }  // namespace aqg

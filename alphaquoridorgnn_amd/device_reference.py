@@ -2,7 +2,7 @@
 import numpy as np
 
 from .counter_rng import counter_uniform, stream_key
-from .selfplay_options import ROOT_NOISE_ATTEMPTS
+from .selfplay_options import ROOT_NOISE_ATTEMPTS, check_completed_q
 
 
 def draw_resign_enabled(seed, k, disable_fraction=0.1):
@@ -56,6 +56,58 @@ def draw_root_noise(seed, k, ply, count, alpha, return_exhausted=False):
 
 NODE_DTYPE = np.dtype([("w", "<f8"), ("p", "<f4"), ("action", "<u4"), ("n", "<i4"), ("kids", "<u4"), ("q", "<f4"), ("cp", "<f4")])
 assert NODE_DTYPE.itemsize == 32      # csrc/mcts_tree.hpp NodeRec
+
+
+def improved_policy_reference(p, n, q, w, root_w, c_visit=50.0, c_scale=1.0):
+    """The completed-Q improved policy of ONE root in numpy (include/aqgnn.h, "completed-Q policy targets"; Danihelka et al., ICLR 2022,
+    section 4 and appendix D) -- the statement csrc/mcts_improve.hip is held to.  Of the root's cnt children in legal_actions() order, as
+    their records hold them: p float32 [cnt] priors, n int32 [cnt] visits, q float32 [cnt] = f32(-w_i / n_i) (0 while n_i == 0), w
+    float64 [cnt]; root_w the root's own w.  All arithmetic is float64:
+        vhat = root_w + sum w;  vmix = (vhat + Nsum * (QV / PV)) / (1 + Nsum) over the visited children (vhat when PV is not > 0)
+        c_i = q_i if n_i > 0 else vmix;  sigma_i = (c_visit + max n) * c_scale * ((c_i + 1) / 2)
+        pi' = softmax(log p + sigma) over the entries with p_i > 0, 0 elsewhere
+    Returns (pi' float32 [cnt], vmix float32); a root without a prior above 0 (cnt == 0 included) gets zeros."""
+    c_visit, c_scale = check_completed_q(c_visit, c_scale)
+    p, q = np.asarray(p, dtype=np.float32).reshape(-1), np.asarray(q, dtype=np.float32).reshape(-1)
+    n, w = np.asarray(n, dtype=np.int64).reshape(-1), np.asarray(w, dtype=np.float64).reshape(-1)
+    cnt = p.shape[0]
+    if not n.shape[0] == q.shape[0] == w.shape[0] == cnt:
+        raise ValueError("improved_policy_reference: p, n, q and w must have one entry per child")
+    p64, q64 = p.astype(np.float64), q.astype(np.float64)
+    nsum = int(n.sum())
+    nmax = int(n.max()) if cnt else 0
+    nmax = max(nmax, 0)
+    vhat = np.float64(root_w) + np.float64(w.sum())
+    visited = n > 0
+    pv, qv = np.float64(p64[visited].sum()), np.float64((p64[visited] * q64[visited]).sum())
+    vmix = (vhat + np.float64(nsum) * (qv / pv)) / (np.float64(1.0) + np.float64(nsum)) if pv > 0 else vhat
+    pi = np.zeros((cnt,), dtype=np.float32)
+    live = p > 0                                               # p <= 0 or NaN: excluded
+    if live.any():
+        c = np.where(visited, q64, vmix)
+        sigma = ((np.float64(c_visit) + np.float64(nmax)) * np.float64(c_scale)) * ((c + 1.0) / 2.0)
+        x = np.log(p64[live]) + sigma[live]
+        e = np.exp(x - x.max())
+        pi[live] = (e / e.sum()).astype(np.float32)
+    return pi, np.float32(vmix)
+
+
+def root_improved_policy_reference(pool_records, c_visit=50.0, c_scale=1.0):
+    """The row aqg_engine_root_improved_policy writes for one slot, from its pool (NODE_DTYPE [node_cap], or anything of 32 bytes per
+    record): (policy float32 [MAX_LEGAL], actions uint8 [MAX_LEGAL], count, vmix float32) -- improved_policy_reference on the root's
+    child block, 0 and 0xFF past the count.  A count above MAX_LEGAL or a child range that leaves the pool gives the zero row: count
+    0, vmix 0."""
+    from ._lib import MAX_LEGAL
+    src = np.ascontiguousarray(pool_records).view(NODE_DTYPE).reshape(-1)
+    policy, actions = np.zeros((MAX_LEGAL,), dtype=np.float32), np.full((MAX_LEGAL,), 0xFF, dtype=np.uint8)
+    cnt, first = int(src["kids"][0]) >> 24, int(src["kids"][0]) & 0xFFFFFF
+    if cnt > MAX_LEGAL or first + cnt > src.shape[0]:
+        check_completed_q(c_visit, c_scale)
+        return policy, actions, 0, np.float32(0.0)
+    kids = src[first:first + cnt]
+    policy[:cnt], vmix = improved_policy_reference(kids["p"], kids["n"], kids["q"], kids["w"], src["w"][0], c_visit, c_scale)
+    actions[:cnt] = kids["action"].astype(np.uint8)
+    return policy, actions, cnt, vmix
 
 
 def keep_subtree_reference(pool_records, node_count, child_index, keep_visits):

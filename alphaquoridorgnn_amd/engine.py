@@ -23,9 +23,10 @@ from .evaluators import BINDINGS
 # seeds; device_reference: numpy statements of device code; resign_calibration: the resignation statistics; two_engine_match: the
 # match loop.
 from .counter_rng import GOLDEN as _GOLDEN, MASK64, mix64 as _mix64_int  # noqa: F401
-from .device_reference import NODE_DTYPE, draw_resign_enabled, draw_root_noise, keep_subtree_reference, root_noise_stream_key  # noqa: F401
+from .device_reference import (NODE_DTYPE, draw_resign_enabled, draw_root_noise, improved_policy_reference,  # noqa: F401
+                               keep_subtree_reference, root_improved_policy_reference, root_noise_stream_key)
 from .resign_calibration import resign_false_positives, resign_stats_of, suggest_from_arrays, suggest_resign_threshold  # noqa: F401
-from .selfplay_options import (ROOT_NOISE_ATTEMPTS, check_resign, check_root_noise, check_target_options,  # noqa: F401
+from .selfplay_options import (ROOT_NOISE_ATTEMPTS, check_completed_q, check_resign, check_root_noise, check_target_options,  # noqa: F401
                                check_tree_reuse, default_resign_seed, default_root_noise_alpha, default_root_noise_seed, set_noise_seeds)
 from .two_engine_match import TwoEngineMatch  # noqa: F401
 
@@ -454,6 +455,23 @@ class BatchedSelfPlay:
         value = torch.empty((self.G,), dtype=torch.float32, device=self.dev)
         _lib.check(self.lib.aqg_engine_root_values(ctypes.byref(self.e), _lib.ptr(value), self._stream()), "aqg_engine_root_values")
         return value
+
+    def root_improved_policy(self, c_visit=50.0, c_scale=1.0):
+        """The completed-Q improved policy of every slot's root, pi' = softmax(log p + sigma(completedQ)) (include/aqgnn.h,
+        "completed-Q policy targets"; improved_policy_reference is the statement): (policy f32 [G, MAX_LEGAL] in legal_actions() order,
+        actions u8 [G, MAX_LEGAL], count i32 [G] -- the layout of search()'s visits, 0 and 0xFF past the count -- and vmix f32 [G], the
+        mixed value that completes the unvisited children).  Valid after search() and in front of a finish-move, on every evaluator and
+        with tree reuse; one launch (csrc/mcts_improve.hip) that reads the tree pool and changes nothing.  c_visit and c_scale must
+        be finite and >= 0 (ValueError, before any launch)."""
+        c_visit, c_scale = check_completed_q(c_visit, c_scale)
+        policy = torch.empty((self.G, _lib.MAX_LEGAL), dtype=torch.float32, device=self.dev)
+        actions = torch.empty((self.G, _lib.MAX_LEGAL), dtype=torch.uint8, device=self.dev)
+        count = torch.empty((self.G,), dtype=torch.int32, device=self.dev)
+        vmix = torch.empty((self.G,), dtype=torch.float32, device=self.dev)
+        _lib.check(self.lib.aqg_engine_root_improved_policy(ctypes.byref(self.e), c_visit, c_scale, _lib.ptr(policy), _lib.ptr(actions),
+                                                            _lib.ptr(count), _lib.ptr(vmix), self._stream()),
+                   "aqg_engine_root_improved_policy")
+        return policy, actions, count, vmix
 
     # ------------------------------------------------------------------ history
     def _history_valid(self):

@@ -68,6 +68,26 @@ def pv_mcts_policy_batch(model, states72, temperature, sims=None, board_size=Non
     return [_policy_from_visits([int(v) for v in visits[b, :count[b]]], temperature) for b in range(B)]
 
 
+def pv_mcts_improved_policy_batch(model, states72, sims=None, board_size=None, evaluator="gnn", fake_bias=0, c_visit=50.0, c_scale=1.0):
+    """states72: uint8 [B,72] -> (pi' float32 [B, A], vmix float32 [B]) on the engine's device: the completed-Q improved policy of a
+    fresh search of every position, pi' = softmax(log p + sigma(completedQ)) over its legal actions (Danihelka et al., ICLR 2022;
+    engine.improved_policy_reference), as dense rows over the board's A actions -- 0 at the others -- and the mixed value of each root.
+    Non-zero on unvisited legal actions, unlike the visit counts of pv_mcts_policy_batch.  evaluator, sims and fake_bias as there."""
+    from .selfplay_options import check_completed_q
+    c_visit, c_scale = check_completed_q(c_visit, c_scale)
+    states72 = torch.as_tensor(states72, dtype=torch.uint8)
+    B = states72.shape[0]
+    N = int(states72[0, 70]) if board_size is None else board_size
+    eng = _engine_for(model, B, PV_EVALUATE_COUNT if sims is None else sims, N, evaluator, fake_bias)
+    eng.search(states72)
+    policy, actions, count, vmix = eng.root_improved_policy(c_visit, c_scale)
+    A = N * N + 2 * (N - 1) ** 2
+    inside = (torch.arange(_lib.MAX_LEGAL, device=policy.device).unsqueeze(0) < count.unsqueeze(1)) & (actions < A)
+    dense = torch.zeros((B, A + 1), dtype=torch.float32, device=policy.device)       # column A takes what lies past the count
+    dense.scatter_(1, torch.where(inside, actions.long(), A), torch.where(inside, policy, 0.0))
+    return dense[:, :A].contiguous(), vmix
+
+
 def evaluator_of(model):
     """'gnn' for the GNN the HIP kernels evaluate themselves (the default 6/128/3 shape); 'cnn' for the reference's CNNNetwork
     (pv_network_cnn.py, self_play.py:16,78), which they evaluate too; 'external' for any other object with the reference's

@@ -7,11 +7,17 @@ Everything runs on the device: the rows' 72-byte records are gathered from the r
 (BatchedSelfPlay.search on the engine pv_mcts keeps for searches), read out (root_visits, root_values) and written into their slots
 by one aqg_replay_refresh launch per chunk (ReplayWindow.refresh_counts).  The newest generation is never touched: its targets are
 the current network's already.
+
+policy_target='completed_q' (Danihelka et al., "Policy improvement by planning with Gumbel", ICLR 2022; include/aqgnn.h, "completed-Q
+policy targets"): the policy target is pi' = softmax(log p + sigma(completedQ)) of the searched root instead of its normalised visit
+counts -- non-zero on unvisited actions and smooth in the values, which matters at the small simulation counts a pass runs at.  The
+read-out pair becomes root_improved_policy -> ReplayWindow.refresh_policy; the search itself is the same.
 """
 import torch
 
 from . import pv_mcts
 from .replay import check_value_blend, draw_reanalyse_rows
+from .selfplay_options import check_policy_target
 
 
 def eligible_rows(window):
@@ -20,9 +26,11 @@ def eligible_rows(window):
     return len(window) - generations[-1] if generations else 0
 
 
-def check_reanalyse_options(rows, sims=None, value_blend=0.0, slots=None):
-    """Validate the options of a pass as reanalyse() does: rows >= 0, sims >= 1 (None: the default), a blend in [0, 1], slots >= 1.
-    Returns (rows, sims, value_blend, slots) as ints / float."""
+def check_reanalyse_options(rows, sims=None, value_blend=0.0, slots=None, policy_target="visits", c_visit=50.0, c_scale=1.0):
+    """Validate the options of a pass as reanalyse() does: rows >= 0, sims >= 1 (None: the default), a blend in [0, 1], slots >= 1,
+    policy_target 'visits' or 'completed_q' with c_visit and c_scale finite and >= 0 (selfplay_options.check_policy_target returns
+    those three).  Returns (rows, sims, value_blend, slots) as ints / float."""
+    check_policy_target(policy_target, c_visit, c_scale)
     for name, x, low in (("rows", rows, 0), ("sims", sims, 1), ("slots", slots, 1)):
         if x is None:
             continue
@@ -31,7 +39,8 @@ def check_reanalyse_options(rows, sims=None, value_blend=0.0, slots=None):
     return (int(rows), None if sims is None else int(sims), check_value_blend(value_blend), None if slots is None else int(slots))
 
 
-def reanalyse(window, model, rows, sims=None, value_blend=0.0, seed=0, update=0, slots=2048, evaluator=None, fake_bias=0):
+def reanalyse(window, model, rows, sims=None, value_blend=0.0, seed=0, update=0, slots=2048, evaluator=None, fake_bias=0,
+              policy_target="visits", c_visit=50.0, c_scale=1.0):
     """Search `rows` of the window's rows again with `model` and overwrite their targets; returns how many were refreshed.
 
     Eligible are the valid rows except the newest generation, index()[: len(window) - generations[-1]]; draw_reanalyse_rows(seed,
@@ -40,10 +49,13 @@ def reanalyse(window, model, rows, sims=None, value_blend=0.0, seed=0, update=0,
     last chunk is padded with copies of its first record, whose results are dropped -- and after each chunk one refresh_counts
     writes pi = visits / their sum into the rows' slots and, with value_blend L > 0, z' = (1 - L) z + L q with q the root's search
     value and z the value the ring holds now.  evaluator None: by the model, as self_play() chooses ('cnn', 'gnn', 'general');
-    'fake' (tests) takes fake_bias.  The search is deterministic: two windows with equal rings stay equal under equal calls.
+    'fake' (tests) takes fake_bias.  policy_target 'completed_q': after each chunk root_improved_policy(c_visit, c_scale) and one
+    refresh_policy write pi' = softmax(log p + sigma(completedQ)) instead; q of the blend stays root_values().  The search is
+    deterministic: two windows with equal rings stay equal under equal calls.
     The engine is dropped when the pass is done, so its tree pool does not stay resident beside a self-play engine's."""
     from .pv_network_cnn import CNNNetwork
-    rows, sims, value_blend, slots = check_reanalyse_options(rows, sims, value_blend, slots)
+    rows, sims, value_blend, slots = check_reanalyse_options(rows, sims, value_blend, slots, policy_target, c_visit, c_scale)
+    policy_target, c_visit, c_scale = check_policy_target(policy_target, c_visit, c_scale)
     sims = pv_mcts.PV_EVALUATE_COUNT if sims is None else sims
     N = window.board_size
     if evaluator is None:
@@ -70,7 +82,11 @@ def reanalyse(window, model, rows, sims=None, value_blend=0.0, seed=0, update=0,
                 roots = torch.cat((roots, roots[:1].expand(chunk - m, 72)))
             visits, actions, count = eng.search(roots)
             q = eng.root_values()
-            window.refresh_counts(chosen[first:first + m], visits[:m], actions[:m], count[:m], search_value=q[:m], value_blend=value_blend)
+            if policy_target == "completed_q":
+                policy, actions, count, _ = eng.root_improved_policy(c_visit, c_scale)
+                window.refresh_policy(chosen[first:first + m], policy[:m], actions[:m], count[:m], search_value=q[:m], value_blend=value_blend)
+            else:
+                window.refresh_counts(chosen[first:first + m], visits[:m], actions[:m], count[:m], search_value=q[:m], value_blend=value_blend)
     finally:
         pv_mcts._drop_engine(eng)
     return R

@@ -20,7 +20,9 @@ weighting).  A position and its left-right mirror are NOT merged.  `merge_refere
 
 Reanalyse (`ReplayWindow.refresh_counts`, aqg_replay_refresh, csrc/replay_refresh.hip; the stage is reanalyse.reanalyse): the targets
 of chosen valid rows overwritten, in one launch, by the results of a fresh search of their positions.  `refresh_reference` is the
-kernel in numpy, `draw_reanalyse_rows` picks the rows of one pass.
+kernel in numpy, `draw_reanalyse_rows` picks the rows of one pass.  `ReplayWindow.refresh_policy` (aqg_replay_refresh_policy,
+`refresh_policy_reference`) is the same launch with finished f32 policy entries for the source, copied verbatim: the completed-Q
+targets of engine.root_improved_policy.
 """
 import pickle
 
@@ -142,6 +144,47 @@ def refresh_reference(board_size, visits, actions, count, search_value, blend, s
         row = np.zeros((A,), dtype=np.float32)
         inside = actions[i, :c] < A
         row[actions[i, :c][inside]] = (v[inside].astype(np.float64) / np.float64(tot)).astype(np.float32)
+        ring_pi[slot] = row
+        if blended:
+            x, y = np.float32(keep * ring_z[slot]), np.float32(b * search_value[i])
+            ring_z[slot] = np.float32(x + y)
+
+
+def refresh_policy_reference(board_size, policy, actions, count, search_value, blend, slots, ring_pi, ring_z):
+    """aqg_replay_refresh_policy in numpy, on host arrays, in place (include/aqgnn.h, "completed-Q policy targets") -- refresh_reference
+    with finished policy entries for the source: policy float32 [n,MAX_LEGAL] in legal_actions() order (engine.root_improved_policy),
+    copied VERBATIM to their action ids over a zero row, no total and no division.  With c = count[i], a row is written iff 1 <= c <=
+    MAX_LEGAL, the slot is inside the ring, every entry j < c is finite and >= 0, and one of them is > 0 (an action >= A is dropped,
+    but its entry counts in these tests).  The blend is refresh_reference's.  Refuses what the C entry point refuses, with ValueError."""
+    if board_size not in (3, 5, 7, 9):
+        raise ValueError("refresh_policy_reference: unsupported board_size (odd 3..9)")
+    A = policy_size(board_size)
+    b = np.float32(check_value_blend(blend))
+    if search_value is None and b != 0:
+        raise ValueError("refresh_policy_reference: a blend needs search_value")
+    blended = search_value is not None and b != 0
+    n, capacity = int(np.shape(slots)[0]), int(ring_pi.shape[0])
+    if capacity < 1:
+        raise ValueError("refresh_policy_reference: capacity must be >= 1")
+    if blended and ring_z is None:
+        raise ValueError("refresh_policy_reference: a blend needs ring_z")
+    for x, name, dtype, shape in ((policy, "policy", np.float32, (n, _lib.MAX_LEGAL)), (actions, "actions", np.uint8, (n, _lib.MAX_LEGAL)),
+                                  (count, "count", np.int32, (n,)), (slots, "slots", np.int64, (n,)),
+                                  (search_value, "search_value", np.float32, (n,)), (ring_pi, "ring_pi", np.float32, (capacity, A)),
+                                  (ring_z, "ring_z", np.float32, (capacity,))):
+        if x is not None and (x.dtype != dtype or tuple(x.shape) != shape):
+            raise ValueError(f"refresh_policy_reference: {name} must be {np.dtype(dtype).name} {list(shape)} ({board_size}x{board_size} board)")
+    keep = np.float32(1.0) - b
+    for i in range(n):
+        c, slot = int(count[i]), int(slots[i])
+        if c <= 0 or c > _lib.MAX_LEGAL or not 0 <= slot < capacity:
+            continue
+        v = policy[i, :c]
+        if not (np.isfinite(v) & (v >= 0)).all() or not (v > 0).any():
+            continue
+        row = np.zeros((A,), dtype=np.float32)
+        inside = actions[i, :c] < A
+        row[actions[i, :c][inside]] = v[inside]
         ring_pi[slot] = row
         if blended:
             x, y = np.float32(keep * ring_z[slot]), np.float32(b * search_value[i])
@@ -512,24 +555,36 @@ class ReplayWindow:
         already be a blend.  One aqg_replay_refresh launch on the window's stream (refresh_reference on a host window); a row without
         a visit keeps its targets.  Shapes, dtypes and the slots -- each a valid slot, none twice: one device-to-host read -- are
         checked before anything is written.  The records, the bookkeeping, index() and rows() do not change."""
-        xs = [torch.as_tensor(x) for x in (slots, visits, actions, count)]
+        self._refresh("refresh_counts", "visits", torch.int32, slots, visits, actions, count, search_value, value_blend)
+
+    def refresh_policy(self, slots, policy, actions, count, search_value=None, value_blend=0.0):
+        """refresh_counts with finished policy entries for the source: policy float32 [n,MAX_LEGAL] in legal_actions() order, as
+        engine.root_improved_policy returns it, copied verbatim to the action ids of a zero row -- no total, no division.  A row is
+        written iff 1 <= count <= MAX_LEGAL, every entry inside the count is finite and >= 0 and one is > 0; any other row keeps
+        its targets.  One aqg_replay_refresh_policy launch on the window's stream (refresh_policy_reference on a host window); the
+        checks, the blend and everything that does not change are refresh_counts'."""
+        self._refresh("refresh_policy", "policy", torch.float32, slots, policy, actions, count, search_value, value_blend)
+
+    def _refresh(self, what, source, source_dtype, slots, rows, actions, count, search_value, value_blend):
+        """refresh_counts and refresh_policy behind one set of checks: `rows` is the visit rows or the policy rows."""
+        xs = [torch.as_tensor(x) for x in (slots, rows, actions, count)]
         n = int(xs[0].shape[0]) if xs[0].dim() == 1 else -1
-        specs = (("slots", torch.int64, ()), ("visits", torch.int32, (_lib.MAX_LEGAL,)), ("actions", torch.uint8, (_lib.MAX_LEGAL,)),
+        specs = (("slots", torch.int64, ()), (source, source_dtype, (_lib.MAX_LEGAL,)), ("actions", torch.uint8, (_lib.MAX_LEGAL,)),
                  ("count", torch.int32, ()))
         if search_value is not None:
             xs.append(torch.as_tensor(search_value))
             specs += (("search_value", torch.float32, ()),)
         for x, (name, dtype, tail) in zip(xs, specs):
             if x.dtype != dtype or tuple(x.shape) != (n,) + tail:
-                raise ValueError(f"ReplayWindow.refresh_counts: {name} must be a {dtype} {['n', *tail]} tensor with one row per slot; "
+                raise ValueError(f"ReplayWindow.{what}: {name} must be a {dtype} {['n', *tail]} tensor with one row per slot; "
                                  f"got {x.dtype} {list(x.shape)}")
         value_blend = check_value_blend(value_blend)
         if search_value is None and value_blend != 0.0:
-            raise ValueError("ReplayWindow.refresh_counts: a value_blend needs search_value")
+            raise ValueError(f"ReplayWindow.{what}: a value_blend needs search_value")
         if n == 0:
             return
         if self._rings is None or self._valid == 0:
-            raise ValueError("ReplayWindow.refresh_counts: the window holds no row")
+            raise ValueError(f"ReplayWindow.{what}: the window holds no row")
         xs = [x.to(self.device).contiguous() for x in xs]
         s = xs[0]
         valid = torch.zeros((self.capacity,), dtype=torch.bool, device=self.device)
@@ -539,19 +594,22 @@ class ReplayWindow:
         ordered = torch.sort(s).values
         bad_slot, repeated = torch.stack((stale.any(), (ordered[1:] == ordered[:-1]).any())).tolist()      # the one read
         if bad_slot:
-            raise ValueError("ReplayWindow.refresh_counts: a slot holds no valid row of the window")
+            raise ValueError(f"ReplayWindow.{what}: a slot holds no valid row of the window")
         if repeated:
-            raise ValueError("ReplayWindow.refresh_counts: a slot is named twice")
+            raise ValueError(f"ReplayWindow.{what}: a slot is named twice")
         q = xs[4] if search_value is not None and value_blend != 0.0 else None
         _, rpi, rz = self._rings
+        as_policy = source == "policy"
         if self.device.type == "cpu":
-            refresh_reference(self.board_size, xs[1].numpy(), xs[2].numpy(), xs[3].numpy(), None if q is None else q.numpy(), value_blend,
-                              s.numpy(), rpi.numpy(), rz.numpy())
+            (refresh_policy_reference if as_policy else refresh_reference)(
+                self.board_size, xs[1].numpy(), xs[2].numpy(), xs[3].numpy(), None if q is None else q.numpy(), value_blend, s.numpy(),
+                rpi.numpy(), rz.numpy())
             return
+        name = "aqg_replay_refresh_policy" if as_policy else "aqg_replay_refresh"
+        entry = getattr(_lib.load(), name)
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().aqg_replay_refresh(self.board_size, self.policy_size, _lib.ptr(xs[1]), _lib.ptr(xs[2]), _lib.ptr(xs[3]),
-                                                      _lib.ptr(q), value_blend, _lib.ptr(s), n, self.capacity, _lib.ptr(rpi), _lib.ptr(rz),
-                                                      _lib.stream_ptr(self.device)), "aqg_replay_refresh")
+            _lib.check(entry(self.board_size, self.policy_size, _lib.ptr(xs[1]), _lib.ptr(xs[2]), _lib.ptr(xs[3]), _lib.ptr(q), value_blend,
+                             _lib.ptr(s), n, self.capacity, _lib.ptr(rpi), _lib.ptr(rz), _lib.stream_ptr(self.device)), name)
 
     def extend_from_files(self, paths):
         """Each .history file as one generation, in the order given: oldest first."""

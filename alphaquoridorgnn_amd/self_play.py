@@ -19,6 +19,7 @@ from .engine import BatchedSelfPlay, MultiSetSelfPlay, gather_history, gather_re
 from .pv_network_gnn import GNNNetwork, POLICY_OUTPUT_SIZE, load_network
 from .pv_network_cnn import CNNNetwork
 from .reanalyse import check_reanalyse_options, eligible_rows, reanalyse
+from .selfplay_options import check_policy_target
 from .replay import blend_targets, check_value_blend
 from .resign_calibration import resign_stats_of, suggest_from_arrays
 
@@ -62,6 +63,11 @@ SP_REANALYSE_ROWS = 0        # 0 = off: no search engine is built
 SP_REANALYSE_SIMS = None     # None = pv_mcts.PV_EVALUATE_COUNT
 SP_REANALYSE_VALUE_BLEND = 0.0      # L in [0, 1]: a refreshed row's value target becomes (1 - L) z + L q of the fresh search; 0 = z stays
 SP_REANALYSE_SLOTS = 2048    # roots searched at once
+# how a refreshed row's policy target is formed: 'visits' = the normalised visit counts; 'completed_q' = the improved policy
+# softmax(log p + sigma(completedQ)) of the searched root (include/aqgnn.h "completed-Q policy targets"), with the transform's constants
+SP_REANALYSE_POLICY_TARGET = 'visits'
+SP_REANALYSE_C_VISIT = 50.0
+SP_REANALYSE_C_SCALE = 1.0
 
 
 def first_player_value(ended_state):
@@ -188,7 +194,8 @@ def self_play(model=None, games=None, seed=None):
     import torch.distributed as dist
     if not SP_WRITE_HISTORY and SP_REPLAY is None:
         raise ValueError("SP_WRITE_HISTORY = False without a replay window (SP_REPLAY) would throw the generation away")
-    reanalyse_rows = check_reanalyse_options(SP_REANALYSE_ROWS, SP_REANALYSE_SIMS, SP_REANALYSE_VALUE_BLEND, SP_REANALYSE_SLOTS)[0]
+    reanalyse_rows = check_reanalyse_options(SP_REANALYSE_ROWS, SP_REANALYSE_SIMS, SP_REANALYSE_VALUE_BLEND, SP_REANALYSE_SLOTS,
+                                             SP_REANALYSE_POLICY_TARGET, SP_REANALYSE_C_VISIT, SP_REANALYSE_C_SCALE)[0]
     if reanalyse_rows and SP_REPLAY is None:
         raise ValueError("SP_REANALYSE_ROWS > 0 needs a replay window (SP_REPLAY): there is no older row to search again")
     if model is None:
@@ -252,10 +259,12 @@ def self_play(model=None, games=None, seed=None):
         # ranks' windows stay identical without a collective
         sims = pv_mcts.PV_EVALUATE_COUNT if SP_REANALYSE_SIMS is None else SP_REANALYSE_SIMS
         done = reanalyse(SP_REPLAY, model, reanalyse_rows, sims=sims, value_blend=SP_REANALYSE_VALUE_BLEND, seed=base,
-                         update=SP_REPLAY.reanalyse_updates, slots=SP_REANALYSE_SLOTS, evaluator=evaluator)
+                         update=SP_REPLAY.reanalyse_updates, slots=SP_REANALYSE_SLOTS, evaluator=evaluator,
+                         policy_target=SP_REANALYSE_POLICY_TARGET, c_visit=SP_REANALYSE_C_VISIT, c_scale=SP_REANALYSE_C_SCALE)
         SP_REPLAY.reanalyse_updates += 1
         if rank == 0:
-            print(f'reanalysed {done} of {eligible_rows(SP_REPLAY)} rows at {sims} simulations')
+            print(f'reanalysed {done} of {eligible_rows(SP_REPLAY)} rows at {sims} simulations, policy target: '
+                  f'{check_policy_target(SP_REANALYSE_POLICY_TARGET)[0]}')
     path = None
     if rank == 0 and SP_WRITE_HISTORY:
         path = write_data(_history_rows(st, vis, z, BOARD_SIZE, q, blend))

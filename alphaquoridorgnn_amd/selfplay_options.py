@@ -27,6 +27,32 @@ def check_root_noise(eps, alpha):
     return eps, alpha
 
 
+POLICY_TARGETS = ("visits", "completed_q")      # how a reanalyse pass forms a row's policy target (reanalyse.reanalyse)
+
+
+def check_completed_q(c_visit=50.0, c_scale=1.0):
+    """Validate the constants of the completed-Q transform (include/aqgnn.h, "completed-Q policy targets") as the library does, on the
+    float64 values it is given: both finite and >= 0.  Returns them as floats."""
+    out = []
+    for name, x in (("c_visit", c_visit), ("c_scale", c_scale)):
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a finite number >= 0, not {x!r}")
+        x = float(x)
+        if not (x >= 0.0 and x != float("inf")):                # NaN fails the first
+            raise ValueError(f"{name} must be a finite number >= 0, not {x!r}")
+        out.append(x)
+    return tuple(out)
+
+
+def check_policy_target(policy_target="visits", c_visit=50.0, c_scale=1.0):
+    """Validate the policy-target options of a reanalyse pass: 'visits' (normalised visit counts) or 'completed_q' (the improved policy
+    of the completed-Q transform; 'completed-q' is accepted, as the command line spells it).  Returns (policy_target, c_visit, c_scale)."""
+    name = policy_target.replace("-", "_") if isinstance(policy_target, str) else policy_target
+    if name not in POLICY_TARGETS:
+        raise ValueError(f"policy_target must be one of {POLICY_TARGETS}, not {policy_target!r}")
+    return (name,) + check_completed_q(c_visit, c_scale)
+
+
 def check_target_options(temperature_plies, record_search_value=False, record_history=True):
     """Validate the self-play target options (include/aqgnn.h, "self-play targets"): temperature_plies an integer >= 0 (0 = off);
     record_search_value needs the history it is a column of.  Returns (temperature_plies, record_search_value)."""

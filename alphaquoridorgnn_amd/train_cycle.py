@@ -224,6 +224,16 @@ def _parser():
     ap.add_argument("--reanalyse-value-blend", type=float, default=None, metavar="L",
                     help="self-play, with --reanalyse-rows: weight L in [0, 1] of the fresh search value in a refreshed row's value "
                          "target, (1 - L) z + L q (default SP_REANALYSE_VALUE_BLEND = 0: the value target stays)")
+    ap.add_argument("--reanalyse-policy-target", choices=("visits", "completed-q"), default=None,
+                    help="self-play, with --reanalyse-rows: a refreshed row's policy target -- the normalised visit counts, or the "
+                         "completed-Q improved policy softmax(log p + sigma(completedQ)) of the fresh search (default "
+                         "SP_REANALYSE_POLICY_TARGET = visits)")
+    ap.add_argument("--reanalyse-c-visit", type=float, default=None, metavar="X",
+                    help="self-play, with --reanalyse-policy-target completed-q: c_visit of the transform, >= 0 (default "
+                         "SP_REANALYSE_C_VISIT = 50)")
+    ap.add_argument("--reanalyse-c-scale", type=float, default=None, metavar="Y",
+                    help="self-play, with --reanalyse-policy-target completed-q: c_scale of the transform, >= 0 (default "
+                         "SP_REANALYSE_C_SCALE = 1)")
     return ap
 
 
@@ -247,12 +257,32 @@ def _check_reanalyse_args(args):
     return check_reanalyse_options(args.reanalyse_rows, args.reanalyse_sims, blend)[:3]
 
 
+def _check_reanalyse_policy_args(args):
+    """--reanalyse-policy-target / --reanalyse-c-visit / --reanalyse-c-scale, refused at parse time: any of them without
+    --reanalyse-rows, and constants the stage would refuse.  Returns (policy_target, c_visit, c_scale) with the defaults filled in, or
+    None when none of the three is given."""
+    from . import self_play as sp
+    from .selfplay_options import check_policy_target
+    given = (args.reanalyse_policy_target, args.reanalyse_c_visit, args.reanalyse_c_scale)
+    if all(x is None for x in given):
+        return None
+    if args.reanalyse_rows is None:
+        raise ValueError("--reanalyse-policy-target, --reanalyse-c-visit and --reanalyse-c-scale need --reanalyse-rows")
+    try:
+        return check_policy_target(*(d if x is None else x for x, d in zip(given, ("visits", sp.SP_REANALYSE_C_VISIT, sp.SP_REANALYSE_C_SCALE))))
+    except ValueError as err:
+        raise ValueError(f"--reanalyse-policy-target / --reanalyse-c-visit / --reanalyse-c-scale: {err}") from None
+
+
 def _set_reanalyse_options(args):
     """The checked reanalyse flags onto self_play's constants (after _set_replay_options: the window exists)."""
     from . import self_play as sp
     checked = _check_reanalyse_args(args)
     if checked is not None:
         sp.SP_REANALYSE_ROWS, sp.SP_REANALYSE_SIMS, sp.SP_REANALYSE_VALUE_BLEND = checked
+    target = _check_reanalyse_policy_args(args)
+    if target is not None:
+        sp.SP_REANALYSE_POLICY_TARGET, sp.SP_REANALYSE_C_VISIT, sp.SP_REANALYSE_C_SCALE = target
 
 
 def _set_replay_options(args):
@@ -367,6 +397,7 @@ def main(argv=None):
     from . import evaluate_network as en, pv_mcts, self_play as sp, train_network as tn
     args = _parser().parse_args(argv)
     _check_reanalyse_args(args)                         # in front of anything that touches a device or the process group
+    _check_reanalyse_policy_args(args)
     rank, world = aqd.init_from_env()
     if args.games is not None:
         sp.SP_GAME_COUNT = args.games

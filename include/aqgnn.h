@@ -929,6 +929,53 @@ int aqg_replay_refresh(int board_size, int policy_size, const int32_t* visits, c
                        const float* search_value, float blend, const int64_t* slots, int n, int capacity, float* ring_pi,
                        float* ring_z, void* stream);
 
+/* ------------------------------------------------------------------ completed-Q policy targets (additive to ABI 15; the reference has none)
+ *
+ * The improved policy of "Policy improvement by planning with Gumbel" (Danihelka et al., ICLR 2022, section 4 and appendix D),
+ *     pi' = softmax(log p + sigma(completedQ)),
+ * as a policy target besides the normalised visit counts: a policy improvement at any simulation count, non-zero on unvisited
+ * actions, smooth in the values, and a function of the root's child block alone -- the step kernels, the captured per-move graph and
+ * the engine struct are untouched.
+ *
+ * The definition.  For a root (node 0 of a slot's pool) with cnt children i = 0 .. cnt-1 in legal_actions() order, read as their
+ * records hold them: p_i f32 (the priors the root was built from: the mixed ones with root noise on), n_i i32, q_i f32 = f32(-w_i / n_i)
+ * from the root mover's side (0 while n_i == 0), w_i f64, and the root's own w.  All arithmetic is float64 without contraction;
+ * values are rounded to f32 only where stated.
+ *   1. Nsum = sum n_i, nmax = max(0, max n_i): integers.
+ *   2. vhat = root.w + sum_i w_i -- the root's own network value: a backup adds each simulation's value to a child and its negation to
+ *      the root, and simulation 0 adds vhat to the root alone, so the identity is exact up to f64 rounding.
+ *   3. With V = {i : n_i > 0}, PV = sum_{i in V} p_i and QV = sum_{i in V} p_i q_i:
+ *          vmix = (vhat + Nsum * (QV / PV)) / (1 + Nsum)   if PV > 0,   else vmix = vhat.
+ *   4. c_i = q_i if n_i > 0, else vmix.
+ *   5. sigma_i = ((c_visit + nmax) * c_scale) * ((c_i + 1) / 2): the values lie in [-1, 1] and the fixed affine map to [0, 1] is the
+ *      paper's setting (no min-max rescaling).
+ *   6. x_i = log(p_i) + sigma_i for p_i > 0; an entry with p_i <= 0 or NaN is excluded and gets pi'_i = 0.  m = max x_i,
+ *      e_i = exp(x_i - m), pi'_i = f32(e_i / sum e).  f32(vmix) is returned too.
+ *   7. A root with cnt == 0 or without a p_i > 0 gets an all-zero row (its vmix is still the one above: vhat for cnt == 0).  A root
+ *      with cnt > AQG_MAX_LEGAL, or whose child range leaves the pool (first + cnt > node_cap: checked before it is used as an
+ *      address), gets the zero row: count 0, actions 0xFF, vmix 0.  Rows are zero past cnt.
+ * The sums and maxima are wave reductions and log / exp are the device library's, so the outputs are not the bits of another
+ * evaluation order: every f64 intermediate is good to far better than 2^-40 relative, so an f32 output differs from
+ * engine.improved_policy_reference (the same in numpy) at most by landing on the other side of a rounding boundary -- one f32 ulp,
+ * plus for vmix the absolute floor (cnt + 1) * (Nsum + 1) * 2^-53 of the cancellation in vhat.
+ *
+ * aqg_engine_root_improved_policy: one launch (csrc/mcts_improve.hip), one wavefront per slot, no LDS, no atomics.  policy
+ *   [G,AQG_MAX_LEGAL] f32, actions [G,AQG_MAX_LEGAL] u8 and count [G] i32 in the layout of aqg_engine_root_visits (0 and 0xFF past the
+ *   count), vmix [G] f32.  Valid after a search and in front of a finish-move, on every evaluator and with tree reuse (a kept root
+ *   satisfies the same identity).  The paper's board-game constants are c_visit = 50, c_scale = 1.  Refused before the launch: a NULL
+ *   argument, c_visit or c_scale negative or not finite.
+ * aqg_replay_refresh_policy: aqg_replay_refresh with finished f32 policy entries for the source -- policy [n,AQG_MAX_LEGAL] f32 as the
+ *   entry above writes it -- copied VERBATIM to their action ids over a zero row: no total, no division, so the launch is bit for bit
+ *   replay.refresh_policy_reference.  Geometry, staging, fences, the slot and action guards, the refusals and the blend are
+ *   aqg_replay_refresh's.  A row is written iff 1 <= count <= AQG_MAX_LEGAL, the slot is inside the ring, every entry j < count is
+ *   finite and >= 0 and at least one is > 0 -- pure predicates, wave-uniform by ballot: no sum is involved, so the decision does not
+ *   depend on an order.  (An entry whose action byte is >= policy_size is dropped but counts in these predicates.) */
+int aqg_engine_root_improved_policy(const aqg_engine* e_host, double c_visit, double c_scale, float* policy, uint8_t* actions,
+                                    int32_t* count, float* vmix, void* stream);
+int aqg_replay_refresh_policy(int board_size, int policy_size, const float* policy, const uint8_t* actions, const int32_t* count,
+                              const float* search_value, float blend, const int64_t* slots, int n, int capacity, float* ring_pi,
+                              float* ring_z, void* stream);
+
 /* ------------------------------------------------------------------ position merge (additive to ABI 15; the reference has none)
  *
  * Rows of (states72, pi, z) that hold the same position merged into one row with the mean targets (csrc/replay_merge.hip;
