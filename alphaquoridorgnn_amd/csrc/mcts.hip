@@ -47,10 +47,22 @@ int g_use_graph = 1;       // aqg_set_option("use_graph", 0) forces plain launch
 // ------------------------------------------------------------------------------------------------
 // host-side enqueue (no sync, no allocation)
 // ------------------------------------------------------------------------------------------------
+// The temperature a move can sample at (aqgnn.h, `temperature`): finite and >= 0, and when > 0 small enough an exponent that every
+// term n ** (1 / T) of boltzman (pv_mcts.py:106-109), n <= `visits`, is below 2^1016 -- the sum of at most AQG_MAX_LEGAL < 2^8 of them
+// is then finite.  The reference raises for a negative one (0 ** negative) and for a too small one (OverflowError); the kernel would
+// form inf / inf and play child 0 without a word.
+static int validate_temperature(float temperature, long long visits) {
+    if (!(temperature >= 0.f) || std::isinf(temperature)) return fail("temperature must be finite and >= 0");      // NaN fails the first
+    if (temperature > 0.f && !(std::log2((double)visits) / (double)temperature <= 1016.0))
+        return fail("temperature is too small for sims (+ keep_visits): log2(visits) / temperature must be <= 1016");
+    return 0;
+}
+
 static int validate(const aqg_engine& e) {
     const int N = e.board_size;
     if (!board_size_supported(N)) return fail("unsupported board_size");
     if (e.num_games <= 0 || e.sims <= 0) return fail("num_games and sims must be positive");
+    if (int r = validate_temperature(e.temperature, e.sims)) return r;
     if ((long long)e.node_cap >= (1 << 24)) return fail("node_cap must be < 2^24");
     if (e.node_cap < 1 + MAX_LEGAL) return fail("node_cap too small");
     if (e.prior_mode == 0 && N != 9 && !e.gnn_workspace) return fail("boards other than 9x9 need gnn_workspace for the GNN evaluator");
@@ -84,6 +96,7 @@ static int validate(const aqg_engine& e) {
 static int validate_reuse(const aqg_engine& e, const aqg_tree_reuse& ru) {
     if (ru.keep_visits < 0) return fail("tree reuse: keep_visits must be >= 0");
     if ((long long)ru.keep_visits + e.sims > 32767) return fail("tree reuse: keep_visits + sims must be <= 32767 (the visit row is read out as int16)");
+    if (int r = validate_temperature(e.temperature, (long long)ru.keep_visits + e.sims)) return r;
     if ((long long)e.node_cap < 1 + ((long long)ru.keep_visits + e.sims) * MAX_LEGAL) return fail("tree reuse: node_cap must be >= 1 + (keep_visits + sims) * AQG_MAX_LEGAL");
     if (e.prior_mode == 2) return fail("tree reuse: not with prior_mode 2 (the external evaluator)");
     if (!ru.kept || !ru.child_index || !ru.stat_moves_kept || !ru.stat_visits_kept) return fail("tree reuse: kept / child_index / stat_moves_kept / stat_visits_kept are required");

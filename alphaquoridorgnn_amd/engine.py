@@ -27,7 +27,7 @@ from .device_reference import (NODE_DTYPE, draw_resign_enabled, draw_root_noise,
                                keep_subtree_reference, root_improved_policy_reference, root_noise_stream_key)
 from .resign_calibration import resign_false_positives, resign_stats_of, suggest_from_arrays, suggest_resign_threshold  # noqa: F401
 from .selfplay_options import (ROOT_NOISE_ATTEMPTS, check_completed_q, check_resign, check_root_noise, check_target_options,  # noqa: F401
-                               check_tree_reuse, default_resign_seed, default_root_noise_alpha, default_root_noise_seed, set_noise_seeds)
+                               check_temperature, check_tree_reuse, default_resign_seed, default_root_noise_alpha, default_root_noise_seed, set_noise_seeds)
 from .two_engine_match import TwoEngineMatch  # noqa: F401
 
 
@@ -53,6 +53,8 @@ class BatchedSelfPlay:
         device, p' = (1 - eps) p + eps eta (include/aqgnn.h, "root exploration noise").  root_noise_alpha None = 10 / (N^2 + 2 (N - 1)^2),
         the usual "10 / typical number of moves" rule; root_noise_seed None = derived from `seed`.  The noise of a game's root is
         keyed by (seed, game index, ply) -- draw_root_noise is the generator in numpy -- unless move() / search() are given a table.
+        temperature: 1.0 samples the move from the visit counts, 0 takes their first maximum, T > 0 samples from n ** (1 / T); finite
+        and >= 0, and log2(sims + tree_reuse_visits) / T <= 1016 so that no term overflows (check_temperature; ValueError otherwise).
         temperature_plies K (0 = off, the default): a root at ply < K is sampled at `temperature` as always, one at ply >= K takes
         the first maximum of the visit counts; the recorded visit rows do not change, only the choice.  record_search_value (needs
         record_history): every searched move also records the root's search value w / n from the mover's side, float32, beside its
@@ -72,6 +74,7 @@ class BatchedSelfPlay:
         self.resign_seed = default_resign_seed(seed) if resign_seed is None else int(resign_seed) & MASK64
         self.keep_visits = check_tree_reuse(tree_reuse, tree_reuse_visits, sims, evaluator)
         self.tree_reuse = self.keep_visits is not None
+        self.temperature = check_temperature(temperature, sims, self.keep_visits)
         self.temperature_plies, self.record_search_value = check_target_options(temperature_plies, record_search_value, record_history)
         self.root_noise_eps, self.root_noise_alpha = check_root_noise(
             root_noise_eps, default_root_noise_alpha(board_size) if root_noise_alpha is None else root_noise_alpha)
@@ -162,7 +165,7 @@ class BatchedSelfPlay:
         e.num_games, e.quota, e.sims, e.node_cap = G, Q, self.sims, cap
         e.max_plies = hp if record_history else 0
         e.prior_mode = b.prior_mode
-        e.c_puct, e.temperature = float(c_puct), float(temperature)
+        e.c_puct, e.temperature = float(c_puct), self.temperature
         if self.eval_cache_slots:
             e.eval_cache_log2 = self.eval_cache_slots.bit_length() - 1
         e.root_noise_eps, e.root_noise_alpha = self.root_noise_eps, self.root_noise_alpha

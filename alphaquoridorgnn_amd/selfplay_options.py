@@ -63,6 +63,26 @@ def check_target_options(temperature_plies, record_search_value=False, record_hi
     return int(temperature_plies), bool(record_search_value)
 
 
+def check_temperature(temperature, sims, keep_visits=None):
+    """Validate the sampling temperature as the library does (include/aqgnn.h, `temperature`), on the f32 value its struct holds:
+    finite and >= 0 (0 = the first maximum); when > 0, log2(sims + keep_visits) / temperature <= 1016, so that every term
+    n ** (1 / temperature) of boltzman is below 2**1016 and the sum of at most MAX_LEGAL < 2**8 of them is finite.  The reference raises
+    for a negative one (ZeroDivisionError for 0 ** negative) and for a too small one (OverflowError); the kernel would form inf / inf
+    and play child 0 without a word.
+    keep_visits: check_tree_reuse's (None = tree reuse off).  Returns the temperature as a float."""
+    if isinstance(temperature, (bool, str)) or not isinstance(temperature, (int, float, np.integer, np.floating)):
+        raise ValueError(f"temperature must be a finite number >= 0, not {temperature!r}")
+    with np.errstate(over="ignore"):
+        t = float(np.float32(temperature))
+    if not (t >= 0.0 and t != float("inf")):                     # NaN fails the first
+        raise ValueError(f"temperature must be a finite number >= 0 as a float32, not {temperature!r}")
+    visits = int(sims) + int(keep_visits or 0)
+    if t > 0.0 and visits > 0 and not np.log2(float(visits)) / t <= 1016.0:
+        raise ValueError(f"temperature {temperature!r} is too small for {visits} visits: log2(sims + keep_visits) / temperature must be "
+                         f"<= 1016 (n ** (1 / temperature) overflows)")
+    return t
+
+
 def check_tree_reuse(tree_reuse, tree_reuse_visits, sims, evaluator="gnn"):
     """Validate the tree-reuse options as the library does (include/aqgnn.h, "tree reuse").  Returns keep_visits, or None when the
     option is off.  tree_reuse_visits None = `sims`; 0 is legal: on, never keeps."""

@@ -314,7 +314,11 @@ typedef struct aqg_engine {
     int32_t fake_bias;
     int32_t gnn_flags;        /* flags of the GNN forward for prior_mode 0 (AQG_GNN_EXACT_F32 or 0) */
     float c_puct;             /* 1.25  pv_mcts.py:71 */
-    float temperature;        /* SP_TEMPERATURE self_play.py:20; 1.0 exact, 0 = argmax */
+    float temperature;        /* SP_TEMPERATURE self_play.py:20; 1.0 exact, 0 = argmax.  Finite and >= 0, and when > 0:
+                                 log2(sims + keep_visits) / temperature <= 1016 (keep_visits: tree reuse's, else 0), so that every term
+                                 n ** (1 / temperature) of boltzman (pv_mcts.py:106-109) is below 2^1016 and the sum of at most
+                                 AQG_MAX_LEGAL < 2^8 of them is finite.  Anything else is refused by every entry point that takes
+                                 the engine, before a launch (the reference raises for a negative and for a too small one) */
     /* tree pool: [G * node_cap] 32-byte node records, two aligned 16-byte halves (ABI 9): {f64 w, f32 p, u32 action} -- read only of the
      * child a descent chooses -- and {i32 n, u32 first_child|count<<24, f32 q = f32(-w/n), f32 cp = f32(c_puct * p)} -- what PUCT
      * scores every child with (pv_mcts.py:69-78) */

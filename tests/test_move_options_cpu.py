@@ -3,6 +3,7 @@ the first failing check names the error: the engine, the two targets, tree reuse
 host before anything is launched."""
 import ctypes
 
+import numpy as np
 import pytest
 
 FORMS = ("aqg_engine_move_targets", "aqg_engine_finish_move_targets", "aqg_engine_move_reuse", "aqg_engine_finish_move_reuse",
@@ -38,6 +39,72 @@ def _call(form, e, ru, rs, temperature_plies=0, hist_value=None):
     if form.endswith("_resign"):
         args.append(ctypes.byref(rs))
     rc = getattr(lib, form)(*args, None)
+    return rc, lib.aqg_last_error().decode()
+
+
+REFUSED_TEMPERATURES = [(-1.0, 50), (float("nan"), 50), (float("inf"), 50), (0.005, 200)]      # (temperature, simulations)
+ACCEPTED_TEMPERATURES = [(0.0, 50), (1.0, 50), (0.25, 50), (2.0, 50), (0.02, 200)]
+
+
+@pytest.mark.parametrize("temperature,sims", REFUSED_TEMPERATURES)
+def test_a_temperature_the_kernel_cannot_use_is_refused(temperature, sims):
+    """include/aqgnn.h, `temperature`: finite and >= 0, and log2(sims + keep_visits) / temperature <= 1016 -- by the host check, by
+    the engine's constructor in front of any allocation (no GPU is asked for), and by every move form of the library.  The reference
+    raises for the negative and for the too small one."""
+    from alphaquoridorgnn_amd.engine import BatchedSelfPlay
+    from alphaquoridorgnn_amd.selfplay_options import check_temperature
+    from oracle import mcts as om
+    with pytest.raises(ValueError, match="temperature"):
+        check_temperature(temperature, sims)
+    with pytest.raises(ValueError, match="temperature"):
+        BatchedSelfPlay(None, num_games=4, sims=sims, board_size=5, evaluator="fake", temperature=temperature)
+    if temperature == temperature and abs(temperature) != float("inf"):
+        with pytest.raises((ZeroDivisionError, OverflowError)):
+            om.boltzman([0, sims - 1], temperature)
+    for form in FORMS + ("aqg_engine_move", "aqg_engine_finish_move"):
+        e, ru, rs = _structs()
+        e.temperature, e.sims, e.node_cap = temperature, sims, 1 + 2 * sims * 136
+        rc, err = _call(form, e, ru, rs) if form in FORMS else _plain(form, e)
+        assert rc != 0 and "temperature" in err and "temperature_plies" not in err, (form, err)
+
+
+@pytest.mark.parametrize("temperature,sims", ACCEPTED_TEMPERATURES)
+def test_a_usable_temperature_is_accepted(temperature, sims):
+    from alphaquoridorgnn_amd.selfplay_options import check_temperature
+    from oracle import mcts as om
+    assert check_temperature(temperature, sims) == float(np.float32(temperature))
+    if temperature:
+        assert np.isfinite(om.boltzman([sims] * 136, float(np.float32(temperature)))).all()
+    # the library's check passes it on to the next one: a negative temperature_plies is what these calls are refused for
+    for form in FORMS:
+        e, ru, rs = _structs()
+        e.temperature, e.sims, e.node_cap = temperature, sims, 1 + 2 * sims * 136
+        rc, err = _call(form, e, ru, rs, temperature_plies=-1)
+        assert rc != 0 and "temperature_plies" in err, (form, err)
+
+
+def test_the_temperature_rule_counts_the_kept_visits():
+    """With tree reuse a child can hold keep_visits + sims visits: 0.01 passes at 200 simulations (log2(200) / 0.01 = 765) and is
+    refused with 800 kept ones beside them (log2(1000) / 0.01 = 997 is fine, log2(1200) / 0.01 = 1023 is not)."""
+    from alphaquoridorgnn_amd.selfplay_options import check_temperature
+    assert check_temperature(0.01, 200) == check_temperature(0.01, 200, 800) == float(np.float32(0.01))
+    with pytest.raises(ValueError, match="temperature"):
+        check_temperature(0.01, 200, 1000)
+    for bad in ("1.0", None, True):
+        with pytest.raises(ValueError, match="temperature"):
+            check_temperature(bad, 50)
+    for keep, refused in ((800, False), (1000, True)):
+        e, ru, rs = _structs()
+        e.temperature, e.sims, ru.keep_visits, e.node_cap = 0.01, 200, keep, 1 + (200 + keep) * 136
+        # (the accepted struct is stopped by the next check, a negative temperature_plies, which stands in front of tree reuse's own)
+        rc, err = _call("aqg_engine_move_reuse", e, ru, rs, temperature_plies=0 if refused else -1)
+        assert rc != 0 and ("temperature_plies" in err) == (not refused) and "temperature" in err, err
+
+
+def _plain(form, e):
+    from alphaquoridorgnn_amd import _lib
+    lib = _lib.load()
+    rc = getattr(lib, form)(ctypes.byref(e), ctypes.c_void_p(0x1000), None)
     return rc, lib.aqg_last_error().decode()
 
 
