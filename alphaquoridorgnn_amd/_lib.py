@@ -78,6 +78,12 @@ class ResignStruct(_c.Structure):
                 ("resign_min", _vp), ("game_resigned", _vp)]
 
 
+class PolicyRecordStruct(_c.Structure):
+    """Mirror of `struct aqg_policy_record` (include/aqgnn.h, "recording completed-Q targets during self-play"): the option beside
+    the engine struct."""
+    _fields_ = [("c_visit", _c.c_double), ("c_scale", _c.c_double), ("hist_policy", _vp)]
+
+
 class TrainStruct(_c.Structure):
     """Mirror of `struct aqg_train` (include/aqgnn.h)."""
     _fields_ = (
@@ -177,6 +183,11 @@ SIGNATURES = {
     "aqg_engine_finish_move_resign": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _c.POINTER(TreeReuseStruct),
                                                  _c.POINTER(ResignStruct), _vp]),
     "aqg_engine_reset_resign": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.POINTER(ResignStruct), _vp]),
+    "aqg_engine_move_policy": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _c.POINTER(TreeReuseStruct),
+                                          _c.POINTER(ResignStruct), _c.POINTER(PolicyRecordStruct), _vp]),
+    "aqg_engine_finish_move_policy": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _c.POINTER(TreeReuseStruct),
+                                                 _c.POINTER(ResignStruct), _c.POINTER(PolicyRecordStruct), _vp]),
+    "aqg_engine_record_improved_policy": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.POINTER(PolicyRecordStruct), _vp]),
     "aqg_engine_set_roots": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_engine_root_visits": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp, _vp, _vp]),
     "aqg_engine_root_noise": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp]),
@@ -218,6 +229,7 @@ SIGNATURES = {
                                       _vp]),
     "aqg_replay_append": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
     "aqg_replay_append_blend": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _f32, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
+    "aqg_replay_append_policy": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _f32, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
     "aqg_replay_refresh": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _f32, _vp, _c.c_int, _c.c_int, _vp, _vp, _vp]),
     "aqg_replay_refresh_policy": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _f32, _vp, _c.c_int, _c.c_int, _vp, _vp, _vp]),
     "aqg_replay_position_keys": (_c.c_int, [_vp, _vp, _c.c_int, _vp, _vp]),

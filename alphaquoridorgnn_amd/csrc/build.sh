@@ -19,7 +19,7 @@ fi
 objs=()
 pids=()
 replaced=0
-for f in legal_mask board_featuriser gcn_pack gcn_trunk_split gcn_trunk_exact gcn_boards_plain gcn_forward gcn_general gcn_boards_general gcn_train gcn_train_exact gcn_train_split gcn_train_final gcn_train_general grad_norm cnn_forward cnn_train mcts mcts_step mcts_eval mcts_move mcts_reuse mcts_improve agents augment replay replay_refresh replay_merge capi; do
+for f in legal_mask board_featuriser gcn_pack gcn_trunk_split gcn_trunk_exact gcn_boards_plain gcn_forward gcn_general gcn_boards_general gcn_train gcn_train_exact gcn_train_split gcn_train_final gcn_train_general grad_norm cnn_forward cnn_train mcts mcts_step mcts_eval mcts_move mcts_reuse mcts_improve mcts_record agents augment replay replay_refresh replay_merge capi; do
   src=$f.hip
   for pair in ${AQG_REPLACE:-}; do
     if [ "${pair%%=*}" = "$f" ]; then src=${pair#*=}; replaced=$((replaced + 1)); fi

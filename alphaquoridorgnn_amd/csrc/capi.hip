@@ -311,6 +311,20 @@ int aqg_engine_finish_move_resign(const aqg_engine* e, const double* uniforms, i
     if (!e || !uniforms || !resign) return fail("aqg_engine_finish_move_resign: null argument");
     return engine_finish_move(*e, uniforms, MoveOptions{temperature_plies, hist_value, reuse, resign}, (hipStream_t)stream);
 }
+int aqg_engine_move_policy(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                           const aqg_tree_reuse* reuse, const aqg_resign* resign, const aqg_policy_record* policy, void* stream) {
+    if (!e || !uniforms) return fail("aqg_engine_move_policy: null argument");
+    return engine_move(*e, uniforms, MoveOptions{temperature_plies, hist_value, reuse, resign, policy}, (hipStream_t)stream);
+}
+int aqg_engine_finish_move_policy(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                                  const aqg_tree_reuse* reuse, const aqg_resign* resign, const aqg_policy_record* policy, void* stream) {
+    if (!e || !uniforms) return fail("aqg_engine_finish_move_policy: null argument");
+    return engine_finish_move(*e, uniforms, MoveOptions{temperature_plies, hist_value, reuse, resign, policy}, (hipStream_t)stream);
+}
+int aqg_engine_record_improved_policy(const aqg_engine* e, const aqg_policy_record* policy, void* stream) {
+    if (!e || !policy) return fail("aqg_engine_record_improved_policy: null argument");
+    return engine_record_improved_policy(*e, *policy, (hipStream_t)stream);
+}
 int aqg_engine_reset_resign(const aqg_engine* e, const aqg_resign* resign, void* stream) {
     if (!e || !resign) return fail("aqg_engine_reset_resign: null argument");
     return engine_reset_resign(*e, *resign, (hipStream_t)stream);
@@ -536,6 +550,12 @@ int aqg_replay_append_blend(int board_size, int policy_size, const uint8_t* stat
                             float* ring_z, void* stream) {
     return launch_replay_append_blend(board_size, policy_size, states72, visits, z_i8, search_value, blend, n, capacity, head, ring72,
                                       ring_pi, ring_z, (hipStream_t)stream);
+}
+int aqg_replay_append_policy(int board_size, int policy_size, const uint8_t* states72, const float* pi, const int8_t* z_i8,
+                             const float* search_value, float blend, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
+                             float* ring_z, void* stream) {
+    return launch_replay_append_policy(board_size, policy_size, states72, pi, z_i8, search_value, blend, n, capacity, head, ring72,
+                                       ring_pi, ring_z, (hipStream_t)stream);
 }
 int aqg_replay_refresh(int board_size, int policy_size, const int32_t* visits, const uint8_t* actions, const int32_t* count,
                        const float* search_value, float blend, const int64_t* slots, int n, int capacity, float* ring_pi,

@@ -92,12 +92,14 @@ int launch_cnn_forward_planes(int N, const float* planes, int B, const aqg_cnn_n
 
 // ---- mcts.hip  (the engine's entry points; host code only)
 extern int g_use_graph;
-// the options of one move, all zero = the plain move: the self-play targets (aqgnn.h, "self-play targets"), tree reuse and resignation
+// the options of one move, all zero = the plain move: the self-play targets (aqgnn.h, "self-play targets"), tree reuse, resignation
+// and the recorded completed-Q policy target
 struct MoveOptions {
     int temperature_plies;
     float* hist_value;
     const aqg_tree_reuse* reuse;
     const aqg_resign* resign;
+    const aqg_policy_record* policy = nullptr;
 };
 int engine_reset(const aqg_engine& e, hipStream_t st);
 int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st);
@@ -114,6 +116,7 @@ int engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipSt
 int engine_root_values(const aqg_engine& e, float* value, hipStream_t st);
 int engine_root_improved_policy(const aqg_engine& e, double c_visit, double c_scale, float* policy, uint8_t* actions, int32_t* count,
                                 float* vmix, hipStream_t st);
+int engine_record_improved_policy(const aqg_engine& e, const aqg_policy_record& pr, hipStream_t st);
 int engine_keep_subtrees(const aqg_engine& e, const aqg_tree_reuse& ru, const int32_t* child_index, hipStream_t st);
 int engine_reset_reuse(const aqg_engine& e, const aqg_tree_reuse& ru, hipStream_t st);
 int engine_reset_resign(const aqg_engine& e, const aqg_resign& rs, hipStream_t st);
@@ -147,6 +150,9 @@ int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_
 // ---- mcts_improve.hip
 void launch_engine_root_improved_policy(const aqg_engine& e, double c_visit, double c_scale, float* policy, uint8_t* actions,
                                         int32_t* count, float* vmix, hipStream_t st);
+
+// ---- mcts_record.hip
+int launch_engine_record_improved_policy(const aqg_engine& e, const aqg_policy_record& pr, hipStream_t st);
 
 // ---- mcts_reuse.hip
 void launch_engine_keep_subtrees(const aqg_engine& e, const aqg_tree_reuse& ru, const int32_t* child_index, hipStream_t st);
@@ -232,7 +238,10 @@ int launch_augment_gather(int N, int policy_size, const uint8_t* states72, const
 // ---- replay.hip
 int launch_replay_append(int N, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8, const float* pi,
                          const float* z_f32, int n, int capacity, int head, uint8_t* ring72, float* ring_pi, float* ring_z,
-                         hipStream_t st, const float* search_value = nullptr, float blend = 0.f);
+                         hipStream_t st, const float* search_value = nullptr, float blend = 0.f, bool policy_form = false);
+int launch_replay_append_policy(int N, int policy_size, const uint8_t* states72, const float* pi, const int8_t* z_i8,
+                                const float* search_value, float blend, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
+                                float* ring_z, hipStream_t st);
 int launch_replay_append_blend(int N, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8,
                                const float* search_value, float blend, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
                                float* ring_z, hipStream_t st);

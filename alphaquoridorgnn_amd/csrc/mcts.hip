@@ -29,6 +29,9 @@
 //   mcts_reuse.hip  tree reuse: engine_keep_subtrees_kernel, the in-place re-rooting of a pool at the chosen child, and its launcher.
 //   mcts_improve.hip  the completed-Q improved policy of the roots: engine_root_improved_policy_kernel, a read-out of the pool in
 //                   float64 (aqgnn.h, "completed-Q policy targets"), and its launcher.  It changes nothing the search reads.
+//   mcts_record.hip   the same rows recorded during self-play: engine_record_improved_policy_kernel writes them dense by action id
+//                   into the f32 history, between a move's search and its finish-move launch; the arithmetic of both units is
+//                   mcts_improve_row.hpp's.
 //   mcts.hip        this file, host code only: validate and validate_move (every refusal of a move, in one order), the simulation loop
 //                   (enqueue_sims), its hipGraph cache (run_sims), the end of a move (finish_and_refill) and the engine_* entry points:
 //                   engine_move and engine_finish_move take the move's options as one MoveOptions value (launchers.hpp).  It launches
@@ -113,14 +116,24 @@ static int validate_resign(const aqg_engine& e, const aqg_resign& rs) {
     return 0;
 }
 
+// what the policy-record entry points refuse, before anything is launched (aqgnn.h, "recording completed-Q targets during self-play")
+static int validate_policy_record(const aqg_engine& e, const aqg_policy_record& pr) {
+    if (!pr.hist_policy) return fail("policy record: hist_policy is required");
+    if (e.max_plies <= 0) return fail("policy record needs a history (max_plies > 0)");
+    if (!(pr.c_visit >= 0.0) || std::isinf(pr.c_visit)) return fail("policy record: c_visit must be finite and >= 0");      // NaN fails the first
+    if (!(pr.c_scale >= 0.0) || std::isinf(pr.c_scale)) return fail("policy record: c_scale must be finite and >= 0");
+    return 0;
+}
+
 // Everything a move refuses, before anything is launched.  The order is part of the interface -- the first failing check names the
-// error: the engine, the two targets, tree reuse if it is on, resignation if it is on.
+// error: the engine, the two targets, tree reuse if it is on, resignation if it is on, the policy record if it is on.
 static int validate_move(const aqg_engine& e, const MoveOptions& o) {
     if (int r = validate(e)) return r;
     if (o.temperature_plies < 0) return fail("temperature_plies must be >= 0");
     if (o.hist_value && e.max_plies <= 0) return fail("hist_value needs a history (max_plies > 0)");
     if (o.reuse) if (int r = validate_reuse(e, *o.reuse)) return r;
     if (o.resign) if (int r = validate_resign(e, *o.resign)) return r;
+    if (o.policy) if (int r = validate_policy_record(e, *o.policy)) return r;
     return 0;
 }
 
@@ -252,7 +265,9 @@ static int run_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reuse* r
 // (tree reuse: finish_move leaves the chosen child's index, the keep launch re-roots the pools of the games that go on -- in front of the
 //  refill, whose new games start in slots that are inactive here and therefore never marked)
 // (resignation: the option is the finish-move launch's last argument; a resigned slot is inactive behind it, like any finished one)
+// (policy record: one launch in front of the finish-move launch, which still sees the slot active and its ply unchanged)
 static int finish_and_refill(const aqg_engine& e, const double* uniforms, const MoveOptions& o, hipStream_t st) {
+    if (o.policy) if (int r = launch_engine_record_improved_policy(e, *o.policy, st)) return r;
     if (int r = launch_engine_finish_move(e, uniforms, o, st)) return r;
     if (o.reuse) launch_engine_keep_subtrees(e, *o.reuse, o.reuse->child_index, st);
     if (e.quota > e.num_games) launch_engine_refill(e, st);
@@ -363,6 +378,14 @@ int engine_root_improved_policy(const aqg_engine& e, double c_visit, double c_sc
     if (!(c_scale >= 0.0) || std::isinf(c_scale)) return fail("aqg_engine_root_improved_policy: c_scale must be finite and >= 0");
     launch_engine_root_improved_policy(e, c_visit, c_scale, policy, actions, count, vmix, st);
     return check_launch("engine_root_improved_policy_kernel");
+}
+
+// the record launch alone (mcts_record.hip), for the tests: what a move with the option refuses, then the one launch
+int engine_record_improved_policy(const aqg_engine& e, const aqg_policy_record& pr, hipStream_t st) {
+    if (int r = validate(e)) return r;
+    if (int r = validate_policy_record(e, pr)) return r;
+    if (int r = launch_engine_record_improved_policy(e, pr, st)) return r;
+    return check_launch("engine_record_improved_policy_kernel");
 }
 
 // the slot refill alone, for a move that was applied rather than searched (engine_apply_actions, mcts_move.hip)

@@ -16,6 +16,11 @@
 // sum, each rounded, which is why this unit is compiled without fma contraction.  BLEND = false is the plain kernel, instruction
 // for instruction.
 //
+// Policy form (aqg_replay_append_policy; aqgnn.h, "recording completed-Q targets during self-play"): the engine's f32 policy rows with
+// its i8 outcomes -- pi of the rows form, z of the counts form, selected by which pointers are given: the row is copied verbatim as
+// the rows form copies it, and the lanes that write ring_z convert z_i8 (whichever of z_i8 / z_f32 is given is the one read).  BLEND
+// applies as in the counts form.  No further instantiation.
+//
 // Loads of the counts: per-row 16-bit loads, one count per lane and pass.  The other candidate -- the workgroup's 16 rows read as ONE
 // 32A-byte span with 16-byte loads and staged through LDS -- was timed beside this one on an MI355X (tools/replay_window_time.py with
 // ALT_LIB; profiles/replay_window.log, where it is the "ALT_LIB" line): 62.6 against 67.4 us at 163,840 rows of 9x9 (-7 %), inside
@@ -59,7 +64,7 @@ __global__ __launch_bounds__(RPL_WAVES * WAVE) void replay_append_kernel(
         return s >= (size_t)capacity ? s - (size_t)capacity : s;
     };
     if (t < rows) {
-        float zt = visits ? (float)z_i8[first + t] : z_f32[first + t];
+        float zt = z_i8 ? (float)z_i8[first + t] : z_f32[first + t];
         if (BLEND) {
             const float keep = 1.0f - blend;
             const float x = keep * zt, y = blend * search_value[first + t];
@@ -116,7 +121,7 @@ static bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes
 
 int launch_replay_append(int N, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8, const float* pi,
                          const float* z_f32, int n, int capacity, int head, uint8_t* ring72, float* ring_pi, float* ring_z,
-                         hipStream_t st, const float* search_value, float blend) {
+                         hipStream_t st, const float* search_value, float blend, bool policy_form) {
     if (!board_size_supported(N)) return fail("aqg_replay_append: unsupported board_size (odd 3..9)");
     const int A = N * N + 2 * (N - 1) * (N - 1);
     if (policy_size != A) return fail("aqg_replay_append: policy_size is not the board's action count N^2 + 2 (N - 1)^2");
@@ -126,14 +131,16 @@ int launch_replay_append(int N, int policy_size, const uint8_t* states72, const 
     if (n > capacity) return fail("aqg_replay_append: more rows than the ring holds (n > capacity)");
     if (n == 0) return 0;                   // nothing to write: the pointers are not looked at (an empty array's may be NULL)
     const bool counts = visits && z_i8 && !pi && !z_f32, finished = pi && z_f32 && !visits && !z_i8;
-    if (!counts && !finished)
+    if (policy_form) {                      // aqg_replay_append_policy: f32 rows with i8 outcomes, and nothing else
+        if (!pi || !z_i8 || visits || z_f32) return fail("aqg_replay_append_policy: pi and z_i8 must be given");
+    } else if (!counts && !finished)
         return fail("aqg_replay_append: give the counts form (visits, z_i8) or the rows form (pi, z_f32), whole, and not both");
     if (!states72 || !ring72 || !ring_pi || !ring_z) return fail("aqg_replay_append: states72 and the three rings must be given");
     const size_t ring_bytes[3] = {STATE72, (size_t)A * sizeof(float), sizeof(float)};
     const void* rings[3] = {ring72, ring_pi, ring_z};
-    const void* srcs[3] = {states72, counts ? (const void*)visits : (const void*)pi, counts ? (const void*)z_i8 : (const void*)z_f32};
+    const void* srcs[3] = {states72, counts ? (const void*)visits : (const void*)pi, z_i8 ? (const void*)z_i8 : (const void*)z_f32};
     const size_t src_bytes[3] = {STATE72, counts ? (size_t)A * sizeof(uint16_t) : (size_t)A * sizeof(float),
-                                 counts ? sizeof(int8_t) : sizeof(float)};
+                                 z_i8 ? sizeof(int8_t) : sizeof(float)};
     for (int o = 0; o < 3; ++o)
         for (int i = 0; i < 3; ++i)
             if (overlap(rings[o], (size_t)capacity * ring_bytes[o], srcs[i], (size_t)n * src_bytes[i]))
@@ -161,6 +168,16 @@ int launch_replay_append_blend(int N, int policy_size, const uint8_t* states72, 
     if (!search_value && n != 0) return fail("aqg_replay_append_blend: search_value must be given");      // n == 0: no pointer is looked at
     return launch_replay_append(N, policy_size, states72, visits, z_i8, nullptr, nullptr, n, capacity, head, ring72, ring_pi, ring_z, st,
                                 search_value, blend);
+}
+
+// the policy form: what it refuses of its own, then aqg_replay_append's checks and launch
+int launch_replay_append_policy(int N, int policy_size, const uint8_t* states72, const float* pi, const int8_t* z_i8,
+                                const float* search_value, float blend, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
+                                float* ring_z, hipStream_t st) {
+    if (!(blend >= 0.f && blend <= 1.f)) return fail("aqg_replay_append_policy: blend must be in [0, 1]");      // NaN fails both
+    if (!search_value && blend != 0.f && n != 0) return fail("aqg_replay_append_policy: a blend needs search_value");      // n == 0: no pointer is looked at
+    return launch_replay_append(N, policy_size, states72, nullptr, z_i8, pi, nullptr, n, capacity, head, ring72, ring_pi, ring_z, st,
+                                search_value, blend, true);
 }
 
 }  // namespace aqg

@@ -26,7 +26,7 @@ from .counter_rng import GOLDEN as _GOLDEN, MASK64, mix64 as _mix64_int  # noqa:
 from .device_reference import (NODE_DTYPE, draw_resign_enabled, draw_root_noise, improved_policy_reference,  # noqa: F401
                                keep_subtree_reference, root_improved_policy_reference, root_noise_stream_key)
 from .resign_calibration import resign_false_positives, resign_stats_of, suggest_from_arrays, suggest_resign_threshold  # noqa: F401
-from .selfplay_options import (ROOT_NOISE_ATTEMPTS, check_completed_q, check_resign, check_root_noise, check_target_options,  # noqa: F401
+from .selfplay_options import (ROOT_NOISE_ATTEMPTS, check_completed_q, check_policy_record, check_resign, check_root_noise, check_target_options,  # noqa: F401
                                check_temperature, check_tree_reuse, default_resign_seed, default_root_noise_alpha, default_root_noise_seed, set_noise_seeds)
 from .two_engine_match import TwoEngineMatch  # noqa: F401
 
@@ -36,7 +36,7 @@ class BatchedSelfPlay:
                  c_puct=1.25, evaluator="gnn", fake_bias=0, seed=0, record_history=True, quota=None, eval_cache_slots=None,
                  root_noise_eps=0.0, root_noise_alpha=None, root_noise_seed=None, temperature_plies=0, record_search_value=False,
                  tree_reuse=False, tree_reuse_visits=None, resign_threshold=None, resign_min_ply=0, resign_disable_fraction=0.1,
-                 resign_seed=None):
+                 resign_seed=None, policy_target="visits", policy_c_visit=50.0, policy_c_scale=1.0):
         """model: GraphPolicyValueNetwork/GNNNetwork (evaluator='gnn'); evaluator='fake' runs the integer-hash
         evaluator used by the parity tests (oracle/mcts.py FakeModel); evaluator='external' calls `model.predict(state,
         device)` -- ANY object honouring the reference's BaseNetwork contract (BaseNetwork.py:36-40), e.g. a stock CNN --
@@ -69,7 +69,18 @@ class BatchedSelfPlay:
         there with the mover as loser, its last row's action 0xFF.  A share resign_disable_fraction of the games -- drawn per GAME
         index from resign_seed (None = derived from `seed`), draw_resign_enabled -- never resigns, and every game keeps the running
         minimum of that maximum per side, so resign_stats() can count false positives and suggest_resign_threshold() can pick T.
-        T = 1.0 never resigns and only collects.  apply_actions() and search() refuse the option."""
+        T = 1.0 never resigns and only collects.  apply_actions() and search() refuse the option.
+        policy_target 'visits' (the default: move() makes the calls it makes today) or 'completed_q' (needs record_history;
+        include/aqgnn.h, "recording completed-Q targets during self-play"): every searched move also records the completed-Q improved
+        policy of its root, pi' = softmax(log p + sigma(completedQ)) with policy_c_visit and policy_c_scale (finite, >= 0), as a dense
+        float32 row beside its visit row -- history_policies(); history() then returns it as the policy list.  One more launch per
+        move, between the search and the finish-move launch.  The move is still chosen from the visit counts, under `temperature` and
+        temperature_plies, and hist_visits is still written: only the recorded target changes, no game does.  Works with tree reuse
+        (a kept root is valid for the read-out), with resignation (the resigning row is written like any other) and with
+        evaluator='external'.  With root noise on, the root's stored priors are the MIXED ones, so the target is
+        softmax(log p_mixed + sigma): the noise is not taken out again.  apply_actions() and search() refuse the option."""
+        self.policy_target, self.policy_c_visit, self.policy_c_scale = check_policy_record(policy_target, policy_c_visit, policy_c_scale,
+                                                                                           record_history)
         self.resign_options = check_resign(resign_threshold, resign_min_ply, resign_disable_fraction, record_history)
         self.resign_seed = default_resign_seed(seed) if resign_seed is None else int(resign_seed) & MASK64
         self.keep_visits = check_tree_reuse(tree_reuse, tree_reuse_visits, sims, evaluator)
@@ -131,6 +142,8 @@ class BatchedSelfPlay:
         t["hist_action"] = z((Q, hp), torch.uint8)
         if self.record_search_value:
             t["hist_value"] = z((Q, hp), torch.float32)    # rows of apply_actions are never written: they read 0
+        if self.policy_target == "completed_q":
+            t["hist_policy"] = z((Q, hp, self.A), torch.float32)    # rows of apply_actions are never written: they read 0
         t["counters"] = z((8,), torch.int32)
         t["stat_leaf_evals"] = z((G,), torch.int32)
         t["stat_terminal_sims"] = z((G,), torch.int32)
@@ -185,10 +198,14 @@ class BatchedSelfPlay:
             rs = self.resign = _lib.ResignStruct()
             rs.threshold, rs.min_ply, rs.disable_fraction = self.resign_options
             rs.seed = self.resign_seed
+        self.policy_record = None
+        if self.policy_target == "completed_q":
+            pr = self.policy_record = _lib.PolicyRecordStruct()
+            pr.c_visit, pr.c_scale = self.policy_c_visit, self.policy_c_scale
         # every tensor is pointed at the struct field of its name (hist_value has none: it is an argument of the move; an absent
         # tensor -- gnn_workspace, the cache's -- leaves its field NULL)
         for name, tensor in t.items():
-            for struct in (e, self.reuse, self.resign):
+            for struct in (e, self.reuse, self.resign, self.policy_record):
                 if hasattr(struct, name):
                     setattr(struct, name, tensor.data_ptr())
         self.record_history = record_history
@@ -286,10 +303,15 @@ class BatchedSelfPlay:
             uniforms = torch.as_tensor(uniforms, dtype=torch.float64).to(self.dev).contiguous()
         self._u = uniforms  # keep alive until the stream has consumed it
         # the entry point and what follows the uniforms: the plain form while every option is off, else the first form that takes
-        # all that is on -- resignation's takes a tree-reuse struct or none, tree reuse's takes the targets, and so does _targets
+        # all that is on -- the policy record's takes the other two structs or none, resignation's takes a tree-reuse struct or none,
+        # tree reuse's takes the targets, and so does _targets
         external = self.evaluator == "external"                  # (check_tree_reuse: never with tree reuse)
         tail = [self.temperature_plies, _lib.ptr(self.t.get("hist_value"))]
-        if self.resign is not None:
+        if self.policy_record is not None:
+            form, tail = "_policy", tail + [ctypes.byref(self.reuse) if self.tree_reuse else None,
+                                            ctypes.byref(self.resign) if self.resign is not None else None,
+                                            ctypes.byref(self.policy_record)]
+        elif self.resign is not None:
             form, tail = "_resign", tail + [ctypes.byref(self.reuse) if self.tree_reuse else None, ctypes.byref(self.resign)]
         elif self.tree_reuse:
             form, tail = "_reuse", tail + [ctypes.byref(self.reuse)]
@@ -316,6 +338,8 @@ class BatchedSelfPlay:
         without a search: history row, next(), terminal handling exactly as move() does them."""
         if self.resign is not None:
             raise ValueError("apply_actions() plays moves nobody searched: build the engine without resign_threshold")
+        if self.policy_record is not None:
+            raise ValueError("apply_actions() plays moves nobody searched: build the engine without policy_target='completed_q'")
         actions = torch.as_tensor(actions, dtype=torch.int32).to(self.dev).contiguous().view(self.G)
         self._applied = actions  # keep alive until the stream has consumed it
         _lib.check(self.lib.aqg_engine_apply_actions(ctypes.byref(self.e), _lib.ptr(actions), self._stream()), "aqg_engine_apply_actions")
@@ -421,6 +445,9 @@ class BatchedSelfPlay:
             raise ValueError("search() looks at caller-given roots from fresh trees: build the engine without tree_reuse")
         if self.resign is not None:
             raise ValueError("search() plays no game: build the engine without resign_threshold")
+        if self.policy_record is not None:
+            raise ValueError("search() records no history: build the engine without policy_target='completed_q' (root_improved_policy() "
+                             "reads the same target out of a searched root)")
         roots = torch.as_tensor(root_states72, dtype=torch.uint8).to(self.dev).contiguous().view(self.G, 72)
         self._roots = roots
         self._set_root_noise(root_noise)
@@ -491,6 +518,14 @@ class BatchedSelfPlay:
             raise ValueError("history_values needs record_search_value=True")
         return self.t["hist_value"][self._history_valid()[0]]
 
+    def history_policies(self):
+        """The recorded completed-Q policy targets, float32 [P, A], row-aligned with history_tensors(): dense by action id, 0 on
+        every action that was not legal at the row's root (and a zero row for a move that was applied, not searched).  Needs
+        policy_target='completed_q'."""
+        if self.policy_record is None:
+            raise ValueError("history_policies needs policy_target='completed_q'")
+        return self.t["hist_policy"][self._history_valid()[0]]
+
     def history_tensors(self):
         """(states72 u8 [P,72], visits i16 [P,A], z i8 [P]) for all finished games on this rank, game-major (game index =
         order in which the games were started)."""
@@ -502,14 +537,16 @@ class BatchedSelfPlay:
 
     def history(self):
         """Reference-format history: list of [[player, enemy, walls], policy list[A] (python floats), z]
-        (self_play.py:51-54,:63-66).  policy_i = n_i / sum(n) in float64, exactly like boltzman at T=1."""
+        (self_play.py:51-54,:63-66).  policy_i = n_i / sum(n) in float64, exactly like boltzman at T=1; with
+        policy_target='completed_q' the recorded float32 row, widened to Python floats."""
         st, vis, z = (x.cpu().numpy() for x in self.history_tensors())
+        rec = self.history_policies().cpu().numpy() if self.policy_record is not None else None
         nw = (self.N - 1) ** 2
         out = []
-        for s, v, zz in zip(st, vis, z):
+        for i, (s, v, zz) in enumerate(zip(st, vis, z)):
             v = v.astype(np.float64)
             tot = v.sum()
-            pol = (v / tot).tolist() if tot > 0 else [0.0] * self.A
+            pol = rec[i].astype(np.float64).tolist() if rec is not None else (v / tot).tolist() if tot > 0 else [0.0] * self.A
             out.append([[[int(s[0]), int(s[1])], [int(s[2]), int(s[3])], [int(x) for x in s[4:4 + nw]]], pol, int(zz)])
         return out
 
@@ -537,6 +574,8 @@ class MultiSetSelfPlay:
                  resign_seed=None, **kw):
         check_resign(kw.get("resign_threshold"), kw.get("resign_min_ply", 0), kw.get("resign_disable_fraction", 0.1),
                      kw.get("record_history", True))          # before anything is allocated
+        check_policy_record(kw.get("policy_target", "visits"), kw.get("policy_c_visit", 50.0), kw.get("policy_c_scale", 1.0),
+                            kw.get("record_history", True))
         self.dev = _lib.require_gpu(device)
         if num_sets is None:                      # one hardware queue per set + the default stream, or fall back to 2
             queues = os.environ.get("GPU_MAX_HW_QUEUES")
@@ -689,16 +728,22 @@ class MultiSetSelfPlay:
         """The sets' history_values() in set order: float32 [P], row-aligned with history_tensors()."""
         return self._joined(lambda eng: (eng.history_values(),))[0]
 
+    def history_policies(self):
+        """The sets' history_policies() in set order: float32 [P, A], row-aligned with history_tensors()."""
+        return self._joined(lambda eng: (eng.history_policies(),))[0]
 
-def gather_history(states72, visits, z, group=None, force_collective=None, values=None):
+
+def gather_history(states72, visits, z, group=None, force_collective=None, values=None, policies=None):
     """The one exchange step per generation: all-gather the ragged (s, pi, z) tuples of every rank.
     Counts are gathered first, payloads are padded to the max count (RCCL needs equal sizes) and trimmed after.
     Works on any torch.distributed backend (nccl == RCCL on ROCm; gloo in the CPU tests).
     force_collective (default: AQG_DIST_FORCE_GROUP=1): run the two collectives at world size 1 as well instead of returning the
     inputs -- the RCCL code path on the one GPU a developer box has (the result is the same rows, bit for bit).
-    values (float32 [P], engine.history_values): every packed row carries its four bytes as well, and a fourth tensor is returned."""
+    values (float32 [P], engine.history_values): every packed row carries its four bytes as well, and a fourth tensor is returned.
+    policies (float32 [P, A], engine.history_policies): every packed row carries its 4 A bytes as well, behind the value's, and one
+    more tensor is returned, last.  Without these two the layout and the return value are what they always were."""
     import torch.distributed as dist
-    same = (states72, visits, z) if values is None else (states72, visits, z, values)
+    same = (states72, visits, z) + (() if values is None else (values,)) + (() if policies is None else (policies,))
     if not (dist.is_available() and dist.is_initialized()):
         return same
     if force_collective is None:
@@ -714,7 +759,8 @@ def gather_history(states72, visits, z, group=None, force_collective=None, value
     counts = [int(c.item()) for c in counts]
     m = max(counts)
     A = visits.shape[1]
-    row = 72 + 2 * A + 1 + (0 if values is None else 4)
+    vb = 0 if values is None else 4
+    row = 72 + 2 * A + 1 + vb + (0 if policies is None else 4 * A)
     buf = torch.zeros((m, row), dtype=torch.uint8, device=dev)
     k = states72.shape[0]
     if k:
@@ -722,7 +768,9 @@ def gather_history(states72, visits, z, group=None, force_collective=None, value
         buf[:k, 72:72 + 2 * A] = visits.contiguous().view(torch.uint8).view(k, 2 * A)
         buf[:k, 72 + 2 * A] = z.view(torch.uint8)
         if values is not None:
-            buf[:k, 73 + 2 * A:] = values.to(torch.float32).contiguous().view(torch.uint8).view(k, 4)
+            buf[:k, 73 + 2 * A:73 + 2 * A + 4] = values.to(torch.float32).contiguous().view(torch.uint8).view(k, 4)
+        if policies is not None:
+            buf[:k, 73 + 2 * A + vb:] = policies.to(torch.float32).contiguous().view(torch.uint8).view(k, 4 * A)
     out = torch.empty((W * m, row), dtype=torch.uint8, device=dev)
     dist.all_gather_into_tensor(out, buf, group=group)
     out = out.view(W, m, row)
@@ -731,9 +779,12 @@ def gather_history(states72, visits, z, group=None, force_collective=None, value
     s = allrows[:, :72].contiguous()
     v = allrows[:, 72:72 + 2 * A].contiguous().view(torch.int16).view(-1, A)
     zz = allrows[:, 72 + 2 * A].contiguous().view(torch.int8)
+    out = (s, v, zz)
     if values is not None:
-        return s, v, zz, allrows[:, 73 + 2 * A:].contiguous().view(torch.float32).view(-1)
-    return s, v, zz
+        out += (allrows[:, 73 + 2 * A:73 + 2 * A + 4].contiguous().view(torch.float32).view(-1),)
+    if policies is not None:
+        out += (allrows[:, 73 + 2 * A + vb:].contiguous().view(torch.float32).view(-1, A),)
+    return out
 
 
 def gather_resign_arrays(arrays, group=None, device="cpu"):

@@ -13,6 +13,10 @@ bookkeeping over it.
 Blended value target (`append_counts(..., search_value=q, value_blend=L)`, aqg_replay_append_blend): z' = (1 - L) z + L q with q the
 search value the engine recorded beside the row (engine.history_values).  `blend_targets` is the arithmetic in numpy.
 
+Policy rows (`append_policy`, aqg_replay_append_policy): a generation whose policy target the engine recorded itself, as f32 rows
+(engine.history_policies, the completed-Q target of self-play) -- the row is copied verbatim, z is converted or blended as the counts
+form's.  `append_reference(..., policy=)` is the statement.
+
 Position merge (`ReplayWindow.merged()`, `merge_positions`; csrc/replay_merge.hip): the window holds one row per OCCURRENCE of a
 position -- every game's opening, and on the small boards many plies after it, thousands of times.  Merged, each distinct position is
 one row whose targets are the mean of its occurrences' (each position then weighs the same; `count` is returned for another
@@ -60,13 +64,16 @@ def blend_targets(z_i8, search_value, blend):
     return (x + y).astype(np.float32)
 
 
-def append_reference(board_size, states72, visits, z_i8, pi, z_f32, head, ring72, ring_pi, ring_z, search_value=None, value_blend=0.0):
+def append_reference(board_size, states72, visits, z_i8, pi, z_f32, head, ring72, ring_pi, ring_z, search_value=None, value_blend=0.0,
+                     policy=None):
     """aqg_replay_append in numpy, on host arrays, in place (include/aqgnn.h, "replay window"): source row i goes to ring slot
     (head + i) % capacity, n and capacity being the row counts of states72 and ring72.  Counts form (visits [n,A] int16 or uint16,
     read as UNSIGNED, and z_i8 [n] int8; pi and z_f32 None): ring_pi = float32(float64(v) / float64(tot)) with tot the row's integer
     sum, zeros where tot == 0, ring_z = float32(z).  Rows form (pi [n,A] float32, z_f32 [n] float32; the other two None): a copy.
     The 72 record bytes are copied verbatim.  search_value (float32 [n]; counts form only) makes it aqg_replay_append_blend:
-    ring_z = blend_targets(z_i8, search_value, value_blend).  Refuses what the C entry points refuse, with ValueError."""
+    ring_z = blend_targets(z_i8, search_value, value_blend).  policy (float32 [n,A], with z_i8; visits, pi and z_f32 None) makes it
+    aqg_replay_append_policy: ring_pi takes the row verbatim, ring_z is the counts form's, blended when search_value is given.
+    Refuses what the C entry points refuse, with ValueError."""
     A = policy_size(board_size)
     if search_value is None and value_blend != 0.0:
         raise ValueError("append_reference: a value_blend needs search_value")
@@ -77,22 +84,28 @@ def append_reference(board_size, states72, visits, z_i8, pi, z_f32, head, ring72
     n, capacity = int(states72.shape[0]), int(ring72.shape[0])
     counts = visits is not None and z_i8 is not None and pi is None and z_f32 is None
     finished = pi is not None and z_f32 is not None and visits is None and z_i8 is None
-    if not counts and not finished:
+    if policy is not None:
+        if z_i8 is None or visits is not None or pi is not None or z_f32 is not None:
+            raise ValueError("append_reference: policy goes with z_i8 alone (visits, pi and z_f32 None)")
+    elif not counts and not finished:
         raise ValueError("append_reference: give the counts form (visits, z_i8) or the rows form (pi, z_f32), whole, and not both")
-    if search_value is not None and not counts:
-        raise ValueError("append_reference: search_value goes with the counts form (visits, z_i8)")
+    if search_value is not None and not counts and policy is None:
+        raise ValueError("append_reference: search_value goes with the counts form (visits, z_i8) or with policy")
     if capacity < 1 or not 0 <= head < capacity or n > capacity:
         raise ValueError("append_reference: needs capacity >= 1, 0 <= head < capacity and n <= capacity")
     for x, name, dtypes, shape in ((states72, "states72", (np.uint8,), (n, 72)), (ring72, "ring72", (np.uint8,), (capacity, 72)),
                                    (ring_pi, "ring_pi", (np.float32,), (capacity, A)), (ring_z, "ring_z", (np.float32,), (capacity,)),
                                    (visits, "visits", (np.int16, np.uint16), (n, A)), (z_i8, "z_i8", (np.int8,), (n,)),
                                    (pi, "pi", (np.float32,), (n, A)), (z_f32, "z_f32", (np.float32,), (n,)),
-                                   (search_value, "search_value", (np.float32,), (n,))):
+                                   (search_value, "search_value", (np.float32,), (n,)), (policy, "policy", (np.float32,), (n, A))):
         if x is not None and (x.dtype not in dtypes or tuple(x.shape) != shape):
             raise ValueError(f"append_reference: {name} must be {np.dtype(dtypes[0]).name} {list(shape)} ({board_size}x{board_size} board)")
     slots = (head + np.arange(n)) % capacity
     ring72[slots] = states72
-    if counts:
+    if policy is not None:
+        ring_pi[slots] = policy
+        ring_z[slots] = z_i8.astype(np.float32) if search_value is None else blend_targets(z_i8, search_value, value_blend)
+    elif counts:
         v = visits.view(np.uint16).astype(np.int64)
         tot = v.sum(axis=1, keepdims=True)
         quotient = v.astype(np.float64) / np.where(tot > 0, tot, 1).astype(np.float64)
@@ -458,7 +471,7 @@ class ReplayWindow:
     # ---- appending
     def _checked(self, what, states72, second, third, second_dtypes, third_dtype):
         """Shapes and dtypes against the board, before anything is written; returns contiguous tensors on the window's device."""
-        names = ("states72",) + (("visits", "z") if what == "append_counts" else ("pi", "z"))
+        names = ("states72",) + {"append_counts": ("visits", "z"), "append_policy": ("policy", "z")}.get(what, ("pi", "z"))
         xs = [torch.as_tensor(x) for x in (states72, second, third)]
         m = int(xs[0].shape[0]) if xs[0].dim() else -1
         for x, name, dtypes, tail in zip(xs, names, ((torch.uint8,), second_dtypes, (third_dtype,)), ((72,), (self.policy_size,), ())):
@@ -486,17 +499,22 @@ class ReplayWindow:
         self._valid += keep
         self._index = (self._start + torch.arange(self._valid, dtype=torch.int64, device=self.device)) % self.capacity
 
-    def _append(self, states72, visits, z_i8, pi, z_f32, m, search_value=None, value_blend=0.0):
+    def _append(self, states72, visits, z_i8, pi, z_f32, m, search_value=None, value_blend=0.0, policy=None):
         skip, head = self._make_room(m)
         if skip:
-            states72, visits, z_i8, pi, z_f32, search_value = (None if x is None else x[skip:].contiguous()
-                                                               for x in (states72, visits, z_i8, pi, z_f32, search_value))
+            states72, visits, z_i8, pi, z_f32, search_value, policy = (None if x is None else x[skip:].contiguous()
+                                                                       for x in (states72, visits, z_i8, pi, z_f32, search_value, policy))
         n = m - skip
         r72, rpi, rz = self._rings
         if self.device.type == "cpu":
             h = lambda x: None if x is None else x.numpy()          # noqa: E731   (views: the rings are written in place)
             append_reference(self.board_size, h(states72), h(visits), h(z_i8), h(pi), h(z_f32), head, h(r72), h(rpi), h(rz),
-                             h(search_value), value_blend)
+                             h(search_value), value_blend, h(policy))
+        elif policy is not None:
+            _lib.check(_lib.load().aqg_replay_append_policy(self.board_size, self.policy_size, _lib.ptr(states72), _lib.ptr(policy),
+                                                            _lib.ptr(z_i8), _lib.ptr(search_value), value_blend, n, self.capacity, head,
+                                                            _lib.ptr(r72), _lib.ptr(rpi), _lib.ptr(rz), _lib.stream_ptr(self.device)),
+                       "aqg_replay_append_policy")
         elif search_value is not None:
             _lib.check(_lib.load().aqg_replay_append_blend(self.board_size, self.policy_size, _lib.ptr(states72), _lib.ptr(visits),
                                                            _lib.ptr(z_i8), _lib.ptr(search_value), value_blend, n, self.capacity, head,
@@ -515,16 +533,29 @@ class ReplayWindow:
         search_value (float32 [n], engine.history_values) with value_blend L in [0, 1]: the value target becomes (1 - L) z + L q
         (blend_targets; one aqg_replay_append_blend launch).  Without search_value the call is the plain append."""
         (s, v, zz), m = self._checked("append_counts", states72, visits, z, (torch.int16, torch.uint16), torch.int8)
+        q, value_blend = self._checked_blend("append_counts", m, search_value, value_blend)
+        self._append(s, v, zz, None, None, m, q, value_blend)
+
+    def append_policy(self, states72, policy, z, search_value=None, value_blend=0.0):
+        """One generation whose policy target the engine recorded itself (engine.history_policies): states72 uint8 [n,72], policy
+        float32 [n,A] -- copied verbatim -- and z int8 [n].  The value target, search_value and value_blend, the eviction and the
+        bookkeeping are append_counts'.  One aqg_replay_append_policy launch (append_reference(policy=) on a host window)."""
+        (s, p, zz), m = self._checked("append_policy", states72, policy, z, (torch.float32,), torch.int8)
+        q, value_blend = self._checked_blend("append_policy", m, search_value, value_blend)
+        self._append(s, None, zz, None, None, m, q, value_blend, policy=p)
+
+    def _checked_blend(self, what, m, search_value, value_blend):
+        """The blend arguments of an append of m rows: (search_value on the window's device or None, the blend as the kernel gets it)."""
         if search_value is None:
             if value_blend != 0.0:
-                raise ValueError("ReplayWindow.append_counts: a value_blend needs search_value")
-            return self._append(s, v, zz, None, None, m)
+                raise ValueError(f"ReplayWindow.{what}: a value_blend needs search_value")
+            return None, 0.0
         value_blend = check_value_blend(value_blend)
         q = torch.as_tensor(search_value)
         if q.dtype != torch.float32 or tuple(q.shape) != (m,):
-            raise ValueError(f"ReplayWindow.append_counts: search_value must be a torch.float32 ['n'] tensor with one value per "
+            raise ValueError(f"ReplayWindow.{what}: search_value must be a torch.float32 ['n'] tensor with one value per "
                              f"position; got {q.dtype} {list(q.shape)}")
-        self._append(s, v, zz, None, None, m, q.to(self.device).contiguous(), value_blend)
+        return q.to(self.device).contiguous(), value_blend
 
     def append_rows(self, states72, pi, z):
         """One generation of finished rows: states72 uint8 [n,72], pi float32 [n,A], z float32 [n]."""

@@ -19,7 +19,7 @@ from .engine import BatchedSelfPlay, MultiSetSelfPlay, gather_history, gather_re
 from .pv_network_gnn import GNNNetwork, POLICY_OUTPUT_SIZE, load_network
 from .pv_network_cnn import CNNNetwork
 from .reanalyse import check_reanalyse_options, eligible_rows, reanalyse
-from .selfplay_options import check_policy_target
+from .selfplay_options import check_policy_record, check_policy_target
 from .replay import blend_targets, check_value_blend
 from .resign_calibration import resign_stats_of, suggest_from_arrays
 
@@ -68,6 +68,13 @@ SP_REANALYSE_SLOTS = 2048    # roots searched at once
 SP_REANALYSE_POLICY_TARGET = 'visits'
 SP_REANALYSE_C_VISIT = 50.0
 SP_REANALYSE_C_SCALE = 1.0
+# The policy target of the generation's OWN rows (the reference has one: the normalised visit counts; engine.BatchedSelfPlay, include/aqgnn.h
+# "recording completed-Q targets during self-play"): 'completed_q' records the improved policy softmax(log p + sigma(completedQ)) of every
+# searched root as a float32 row, which the window takes verbatim and the .history file holds widened to Python floats (float32(float(x))
+# gives the bits back).  The move is still chosen from the visit counts.  With root noise on, p is the MIXED prior.
+SP_POLICY_TARGET = 'visits'  # the reference's rows
+SP_POLICY_C_VISIT = 50.0
+SP_POLICY_C_SCALE = 1.0
 
 
 def first_player_value(ended_state):
@@ -88,17 +95,19 @@ def write_data(history):
     return path
 
 
-def _history_rows(states72, visits, z, board_size, values=None, value_blend=0.0):
+def _history_rows(states72, visits, z, board_size, values=None, value_blend=0.0, policy=None):
     """The rows of a .history file.  values (float32 [P], with value_blend > 0): a row's z is the blended target as a Python float --
-    the float32 the replay window holds, widened -- instead of the int outcome."""
+    the float32 the replay window holds, widened -- instead of the int outcome.  policy (float32 [P, A], engine.history_policies): a
+    row's policy is the recorded row widened to Python floats instead of the normalised visit counts."""
     nw = (board_size - 1) ** 2
     st, vis, zz = states72.cpu().numpy(), visits.cpu().numpy().astype(np.float64), z.cpu().numpy()
     if values is not None:
         zz = [float(x) for x in blend_targets(zz, values.cpu().numpy(), value_blend)]
+    rec = None if policy is None else policy.cpu().numpy().astype(np.float64)
     out = []
-    for s, v, r in zip(st, vis, zz):
+    for i, (s, v, r) in enumerate(zip(st, vis, zz)):
         tot = v.sum()
-        pol = (v / tot).tolist() if tot > 0 else [0.0] * v.shape[0]
+        pol = rec[i].tolist() if rec is not None else (v / tot).tolist() if tot > 0 else [0.0] * v.shape[0]
         out.append([[[int(s[0]), int(s[1])], [int(s[2]), int(s[3])], [int(x) for x in s[4:4 + nw]]], pol,
                     int(r) if values is None else r])
     return out
@@ -160,15 +169,17 @@ def play(model, device=None, uniforms=None):
     """Execute one self-play game (self_play.py:40-68) -- a generation of one game on the engine.
     Returns [[state_array, policy list[POLICY_OUTPUT_SIZE], z], ...]."""
     blend = check_value_blend(SP_VALUE_BLEND)
+    target, c_visit, c_scale = check_policy_record(SP_POLICY_TARGET, SP_POLICY_C_VISIT, SP_POLICY_C_SCALE)
     eng = BatchedSelfPlay(model, num_games=1, sims=pv_mcts.PV_EVALUATE_COUNT, board_size=BOARD_SIZE,
                           temperature=SP_TEMPERATURE, seed=int(np.random.randint(0, 2 ** 31 - 1)),
                           evaluator=pv_mcts.evaluator_of(model), root_noise_eps=SP_ROOT_NOISE_EPS,
                           root_noise_alpha=SP_ROOT_NOISE_ALPHA, temperature_plies=SP_TEMPERATURE_PLIES,
                           record_search_value=blend > 0.0, tree_reuse=SP_TREE_REUSE, tree_reuse_visits=SP_TREE_REUSE_VISITS,
-                          **_resign_options()[0])
+                          policy_target=target, policy_c_visit=c_visit, policy_c_scale=c_scale, **_resign_options()[0])
     eng.play_generation(uniforms=uniforms, check_every=1)
     if blend > 0.0:
-        return _history_rows(*eng.history_tensors(), BOARD_SIZE, eng.history_values(), blend)
+        return _history_rows(*eng.history_tensors(), BOARD_SIZE, eng.history_values(), blend,
+                             policy=eng.history_policies() if target == "completed_q" else None)
     return eng.history()
 
 
@@ -198,6 +209,7 @@ def self_play(model=None, games=None, seed=None):
                                              SP_REANALYSE_POLICY_TARGET, SP_REANALYSE_C_VISIT, SP_REANALYSE_C_SCALE)[0]
     if reanalyse_rows and SP_REPLAY is None:
         raise ValueError("SP_REANALYSE_ROWS > 0 needs a replay window (SP_REPLAY): there is no older row to search again")
+    target, c_visit, c_scale = check_policy_record(SP_POLICY_TARGET, SP_POLICY_C_VISIT, SP_POLICY_C_SCALE)
     if model is None:
         model = load_network(PV_NETWORK_PATH + 'best.pth')       # GNNNetwork (prep_for_inference's path), or the network best.pth holds
         if isinstance(model, (GNNNetwork, CNNNetwork)) and torch.cuda.is_available():
@@ -215,6 +227,7 @@ def self_play(model=None, games=None, seed=None):
     z = torch.zeros((0,), dtype=torch.int8, device=dev)
     blend = check_value_blend(SP_VALUE_BLEND)
     q = torch.zeros((0,), dtype=torch.float32, device=dev) if blend > 0.0 else None       # the rows' search values, with a blend only
+    pol = torch.zeros((0, POLICY_OUTPUT_SIZE), dtype=torch.float32, device=dev) if target == "completed_q" else None      # the recorded targets
     resign_kw, resign_thr = _resign_options()
     resign_arrays = None
     slots = mine
@@ -228,12 +241,15 @@ def self_play(model=None, games=None, seed=None):
                                board_size=BOARD_SIZE, temperature=SP_TEMPERATURE, seed=(base + rank) % (2 ** 31 - 1), device=dev,
                                evaluator=evaluator, root_noise_eps=SP_ROOT_NOISE_EPS, root_noise_alpha=SP_ROOT_NOISE_ALPHA,
                                temperature_plies=SP_TEMPERATURE_PLIES, record_search_value=blend > 0.0,
-                               tree_reuse=SP_TREE_REUSE, tree_reuse_visits=SP_TREE_REUSE_VISITS, **resign_kw)
+                               tree_reuse=SP_TREE_REUSE, tree_reuse_visits=SP_TREE_REUSE_VISITS,
+                               policy_target=target, policy_c_visit=c_visit, policy_c_scale=c_scale, **resign_kw)
         c = eng.play_generation()
-        print(f'\rSelf-play (rank {rank}: {c["finished"]}/{mine} games)', end='')
+        print(f'\rSelf-play (rank {rank}: {c["finished"]}/{mine} games, policy target: {target})', end='')
         st, vis, z = eng.history_tensors()
         if q is not None:
             q = eng.history_values()
+        if pol is not None:
+            pol = eng.history_policies()
         if resign_thr is not None:
             resign_arrays = eng.resign_arrays()
         del eng                                          # its tree pools go before a reanalyse pass builds its search engine
@@ -242,15 +258,21 @@ def self_play(model=None, games=None, seed=None):
     host = distributed and dist.get_backend() != 'nccl'      # gloo (CPU tests): the exchange runs on host tensors
     if host:
         st, vis, z = st.cpu(), vis.cpu(), z.cpu()
+    if host and pol is not None:
+        pol = pol.cpu()
     if q is not None:
-        st, vis, z, q = gather_history(st, vis, z, values=q.cpu() if host else q)
+        st, vis, z, q, *rest = gather_history(st, vis, z, values=q.cpu() if host else q, policies=pol)
     else:
-        st, vis, z = gather_history(st, vis, z)
+        st, vis, z, *rest = gather_history(st, vis, z, policies=pol)
+    if pol is not None:
+        pol = rest[0]
     print('')
     if resign_thr is not None:
         _after_resign_generation(gather_resign_arrays(resign_arrays, device="cpu" if host or not distributed else dev), resign_thr, rank)
     if SP_REPLAY is not None:                        # every rank: the gathered rows are identical on all of them
-        if q is not None:
+        if pol is not None:
+            SP_REPLAY.append_policy(st, pol, z, search_value=q, value_blend=blend if q is not None else 0.0)
+        elif q is not None:
             SP_REPLAY.append_counts(st, vis, z, search_value=q, value_blend=blend)
         else:
             SP_REPLAY.append_counts(st, vis, z)
@@ -267,7 +289,7 @@ def self_play(model=None, games=None, seed=None):
                   f'{check_policy_target(SP_REANALYSE_POLICY_TARGET)[0]}')
     path = None
     if rank == 0 and SP_WRITE_HISTORY:
-        path = write_data(_history_rows(st, vis, z, BOARD_SIZE, q, blend))
+        path = write_data(_history_rows(st, vis, z, BOARD_SIZE, q, blend, policy=pol))
     if distributed:
         dist.barrier()          # no rank may go on to train_network.load_data() before rank 0 has finished the file
     del model

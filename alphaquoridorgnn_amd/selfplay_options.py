@@ -53,6 +53,16 @@ def check_policy_target(policy_target="visits", c_visit=50.0, c_scale=1.0):
     return (name,) + check_completed_q(c_visit, c_scale)
 
 
+def check_policy_record(policy_target="visits", policy_c_visit=50.0, policy_c_scale=1.0, record_history=True):
+    """Validate the recorded policy target of a self-play engine (include/aqgnn.h, "recording completed-Q targets during self-play"):
+    check_policy_target's names and constants; 'completed_q' needs the history its rows are a column of.  Returns (policy_target,
+    c_visit, c_scale)."""
+    name, c_visit, c_scale = check_policy_target(policy_target, policy_c_visit, policy_c_scale)
+    if name == "completed_q" and not record_history:
+        raise ValueError("policy_target='completed_q' needs record_history: the recorded rows are a column of the history")
+    return name, c_visit, c_scale
+
+
 def check_target_options(temperature_plies, record_search_value=False, record_history=True):
     """Validate the self-play target options (include/aqgnn.h, "self-play targets"): temperature_plies an integer >= 0 (0 = off);
     record_search_value needs the history it is a column of.  Returns (temperature_plies, record_search_value)."""

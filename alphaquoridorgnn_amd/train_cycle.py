@@ -234,7 +234,40 @@ def _parser():
     ap.add_argument("--reanalyse-c-scale", type=float, default=None, metavar="Y",
                     help="self-play, with --reanalyse-policy-target completed-q: c_scale of the transform, >= 0 (default "
                          "SP_REANALYSE_C_SCALE = 1)")
+    ap.add_argument("--policy-target", choices=("visits", "completed-q"), default=None,
+                    help="self-play: the policy target of the generation's own rows -- the normalised visit counts, or the completed-Q "
+                         "improved policy softmax(log p + sigma(completedQ)) of every searched root, recorded move by move (the move "
+                         "is still chosen from the visit counts; default SP_POLICY_TARGET = visits)")
+    ap.add_argument("--policy-c-visit", type=float, default=None, metavar="X",
+                    help="self-play, with --policy-target completed-q: c_visit of the transform, >= 0 (default SP_POLICY_C_VISIT = 50)")
+    ap.add_argument("--policy-c-scale", type=float, default=None, metavar="Y",
+                    help="self-play, with --policy-target completed-q: c_scale of the transform, >= 0 (default SP_POLICY_C_SCALE = 1)")
     return ap
+
+
+def _check_policy_args(args):
+    """--policy-target / --policy-c-visit / --policy-c-scale, refused at parse time: a coefficient without --policy-target completed-q,
+    and constants the engine would refuse.  Returns (policy_target, c_visit, c_scale) with the defaults filled in, or None when none
+    of the three is given."""
+    from . import self_play as sp
+    from .selfplay_options import check_policy_record
+    given = (args.policy_target, args.policy_c_visit, args.policy_c_scale)
+    if all(x is None for x in given):
+        return None
+    if args.policy_target != "completed-q" and (args.policy_c_visit is not None or args.policy_c_scale is not None):
+        raise ValueError("--policy-c-visit and --policy-c-scale need --policy-target completed-q")
+    try:
+        return check_policy_record(*(d if x is None else x for x, d in zip(given, ("visits", sp.SP_POLICY_C_VISIT, sp.SP_POLICY_C_SCALE))))
+    except ValueError as err:
+        raise ValueError(f"--policy-target / --policy-c-visit / --policy-c-scale: {err}") from None
+
+
+def _set_policy_options(args):
+    """The checked policy-target flags onto self_play's constants."""
+    from . import self_play as sp
+    target = _check_policy_args(args)
+    if target is not None:
+        sp.SP_POLICY_TARGET, sp.SP_POLICY_C_VISIT, sp.SP_POLICY_C_SCALE = target
 
 
 def _check_reanalyse_args(args):
@@ -398,6 +431,7 @@ def main(argv=None):
     args = _parser().parse_args(argv)
     _check_reanalyse_args(args)                         # in front of anything that touches a device or the process group
     _check_reanalyse_policy_args(args)
+    _check_policy_args(args)
     rank, world = aqd.init_from_env()
     if args.games is not None:
         sp.SP_GAME_COUNT = args.games
@@ -416,6 +450,7 @@ def main(argv=None):
     _set_optimiser_options(args)
     _set_replay_options(args)
     _set_reanalyse_options(args)
+    _set_policy_options(args)
     if args.eval_games is not None:
         en.EN_GAME_COUNT = args.eval_games
     try:

@@ -980,6 +980,52 @@ int aqg_replay_refresh_policy(int board_size, int policy_size, const float* poli
                               const float* search_value, float blend, const int64_t* slots, int n, int capacity, float* ring_pi,
                               float* ring_z, void* stream);
 
+/* ------------------------------------------------------------------ recording completed-Q targets during self-play (additive to ABI 15)
+ *
+ * The same target for the rows a generation itself produces: an f32 history beside hist_visits, written move by move.  Off by
+ * default; with the option off every call launches what it launched before.  The engine struct, the step kernels and the captured
+ * per-move graph (and its cache key) are untouched: the option is a struct beside the engine's, like tree reuse and resignation,
+ * and one launch outside the graph.
+ *
+ * The row.  hist_policy f32 [quota, max_plies, A], indexed like hist_visits: row (k, ply) is the improved policy pi' of the section
+ * above (steps 1 .. 7, with this struct's c_visit and c_scale) of the root the move at ply `ply` of game k was searched from,
+ * scattered DENSE by action id -- pi'_i at action_i for i < cnt, 0.0f everywhere else.  An action byte >= A is dropped; a root
+ * without children, or one that fails step 7's guard, gives the zero row.  With root noise on, the root's stored priors are the
+ * mixed ones and the row is softmax(log p_mixed + sigma); the noise is not taken out again.
+ *
+ * The launch (csrc/mcts_record.hip, engine_record_improved_policy_kernel): one wavefront per slot, four per workgroup, the
+ * arithmetic of aqg_engine_root_improved_policy in the same device function (csrc/mcts_improve_row.hpp) -- so a recorded row is that read-out scattered, bit for
+ * bit.  It acts on a slot g with game_active[g] set, k = slot_game[g] inside [0, quota) and ply = game_plies[k] inside [0, max_plies):
+ * the indices the finish-move launch uses for hist_visits.  The whole row is written, every address once, 64 consecutive floats per
+ * store, staged through LDS per wavefront; no other byte of hist_policy is touched.  Rows of aqg_engine_apply_actions are never
+ * written: in a zeroed buffer they read 0, like hist_value's.
+ *
+ * aqg_engine_move_policy / aqg_engine_finish_move_policy: aqg_engine_move_resign / aqg_engine_finish_move_resign with the option as
+ *   one more argument; here reuse, resign and policy may each be NULL (= that option off).  The record launch goes behind the last
+ *   step of the move's search and in front of the finish-move launch, on the same stream: the move is still chosen from the visit
+ *   counts, hist_visits is still written, and no game changes.
+ * aqg_engine_record_improved_policy: the launch alone.
+ * Refused before any launch, behind everything the move refuses: hist_policy NULL, max_plies == 0, c_visit or c_scale negative or
+ * not finite. */
+typedef struct aqg_policy_record {
+    double c_visit;      /* finite, >= 0 */
+    double c_scale;      /* finite, >= 0 */
+    float* hist_policy;  /* [quota, max_plies, A] */
+} aqg_policy_record;
+int aqg_engine_move_policy(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                           const aqg_tree_reuse* reuse, const aqg_resign* resign, const aqg_policy_record* policy, void* stream);
+int aqg_engine_finish_move_policy(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                                  const aqg_tree_reuse* reuse, const aqg_resign* resign, const aqg_policy_record* policy, void* stream);
+int aqg_engine_record_improved_policy(const aqg_engine* e_host, const aqg_policy_record* policy, void* stream);
+/* aqg_replay_append_policy: the hand-over of such rows to the ring -- aqg_replay_append's kernel and geometry, one launch, with the
+ *   policy of the rows form (pi f32 [n,A], copied verbatim) and the outcome of the counts form (z_i8): ring_z = (float)z, or with
+ *   search_value != NULL aqg_replay_append_blend's uncontracted keep * (float)z + blend * v.  The 72 record bytes are copied verbatim.
+ *   Refused: everything aqg_replay_append refuses, pi or z_i8 NULL (with n > 0), a blend outside [0, 1] or NaN, a blend != 0 without
+ *   search_value, search_value overlapping a ring.  replay.append_reference(policy=) is the same in numpy. */
+int aqg_replay_append_policy(int board_size, int policy_size, const uint8_t* states72, const float* pi, const int8_t* z_i8,
+                             const float* search_value, float blend, int n, int capacity, int head, uint8_t* ring72, float* ring_pi,
+                             float* ring_z, void* stream);
+
 /* ------------------------------------------------------------------ position merge (additive to ABI 15; the reference has none)
  *
  * Rows of (states72, pi, z) that hold the same position merged into one row with the mean targets (csrc/replay_merge.hip;
