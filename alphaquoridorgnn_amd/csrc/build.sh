@@ -49,7 +49,8 @@ if [ "$failed" -ne 0 ]; then
   echo "build.sh: a compile job failed" >&2; exit 1
 fi
 grep -A3 "warning:" "${OBJDIR}/aqg_mcts_step.remarks" "${OBJDIR}/aqg_mcts_eval.remarks" >&2 || true
-# Register budget of the step kernels with the heads inside (engine_step_fast_kernel<9, CACHE, true>): at most
+# Register budget of the step kernels with the heads inside (engine_step_fast_kernel<9, CACHE, true, ..>, the form with policy workgroups
+# included: both kinds of its workgroups take step-sized slots): at most
 # 128 VGPRs and no scratch, or a step workgroup no longer fits beside a trunk workgroup.  The order of their load rounds is steered
 # by scheduling barriers that a compiler update may treat differently: such a build fails here instead of running slower.
 # (The kernels' launch bound already caps them at 128 registers -- the compiler spills rather than exceed it -- so the scratch
@@ -57,7 +58,7 @@ grep -A3 "warning:" "${OBJDIR}/aqg_mcts_step.remarks" "${OBJDIR}/aqg_mcts_eval.r
 awk '/Function Name:/ { k = ($0 ~ /engine_step_fast_kernelILi9ELb[01]ELb1E/) ? $0 : "" }
      k != "" && / VGPRs: / { n++; v = $0; sub(/.* VGPRs: /, "", v); if (v + 0 > 128) { print "build.sh: over 128 VGPRs: " k > "/dev/stderr"; bad = 1 } }
      k != "" && /ScratchSize/ { v = $0; sub(/.*: /, "", v); if (v + 0 != 0) { print "build.sh: scratch in use: " k > "/dev/stderr"; bad = 1 } }
-     END { if (n != 3) { print "build.sh: expected three fused step kernels in the resource remarks, found " n + 0 > "/dev/stderr"; bad = 1 } exit bad }' \
+     END { if (n != 4) { print "build.sh: expected four fused step kernels in the resource remarks, found " n + 0 > "/dev/stderr"; bad = 1 } exit bad }' \
   "${OBJDIR}/aqg_mcts_step.remarks" || exit 1
 # The same budget for the evaluation launch (engine_eval_kernel<TRACK>, mcts_eval.hip): its board workgroups are the trunk's, two per CU.
 awk '/Function Name:/ { k = ($0 ~ /engine_eval_kernelILi[02]E/) ? $0 : "" }

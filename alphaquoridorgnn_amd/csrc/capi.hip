@@ -79,6 +79,7 @@ int aqg_set_option(const char* name, int value) {
     if (name && !strcmp(name, "step_waves")) { g_step_waves = value; return 0; }
     if (name && !strcmp(name, "step_heads")) { g_step_heads = value ? 1 : 0; return 0; }
     if (name && !strcmp(name, "legal_beside_trunk")) { g_legal_beside_trunk = value ? 1 : 0; return 0; }
+    if (name && !strcmp(name, "policy_beside_step")) { g_policy_beside_step = value ? 1 : 0; return 0; }
     if (name && !strcmp(name, "step_fast_depth")) { if (value < 0 || value > 61) return fail("step_fast_depth must be 0..61"); g_step_fast_depth = value; return 0; }
     if (name && !strcmp(name, "train_fused")) { if (value < 1 || value > 3) return fail("train_fused must be 1, 2 or 3"); g_train_fused = value; return 0; }
     if (name && !strcmp(name, "use_graph")) { g_use_graph = value ? 1 : 0; return 0; }

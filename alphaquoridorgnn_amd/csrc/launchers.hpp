@@ -124,13 +124,15 @@ int engine_reset_resign(const aqg_engine& e, const aqg_resign& rs, hipStream_t s
 // ---- mcts_step.hip  (launchers of the engine's kernels only enqueue: the entry point checks the launch)
 extern int g_step_waves, g_step_prio, g_step_fast_depth, g_step_heads;
 int set_trace_mcts(void* buf, unsigned int cap);
-int launch_engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t st, int list_sim, bool heads, bool defer_legal = false);
+int launch_engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t st, int list_sim, bool heads, bool defer_legal = false,
+                       bool policy_beside = false);
 
 // ---- mcts_eval.hip
-extern int g_legal_beside_trunk;
+extern int g_legal_beside_trunk, g_policy_beside_step;
 int set_trace_eval(void* buf, unsigned int cap);
 bool engine_step_defers_legal(const aqg_engine& e, bool step_heads);
-int launch_engine_eval(const aqg_engine& e, hipStream_t st);
+bool engine_policy_beside_step(const aqg_engine& e, bool defer_legal);
+int launch_engine_eval(const aqg_engine& e, hipStream_t st, bool policy_jobs = false);
 
 // ---- mcts_move.hip
 void launch_engine_reset(const aqg_engine& e, hipStream_t st);

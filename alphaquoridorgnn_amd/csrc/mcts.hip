@@ -158,11 +158,15 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reus
     // it carries the leaves' legal-move searches in front of the trunk's board workgroups (mcts_eval.hip) -- still two launches, one chain.
     // Simulation 0's step does not expand, so it is not the form with the heads inside: it searches itself and the plain trunk follows.
     const bool defer_legal = engine_step_defers_legal(e, step_heads);
+    // the policy head beside the step (option "policy_beside_step"): every evaluation launch leaves its marked leaves' expansion jobs, and
+    // the step launch behind it -- simulations 2 .. sims - 1 and the last expansion -- expands them in policy workgroups beside its step
+    // workgroups.  Simulation 1's step follows the plain trunk and searched its leaf (the root) itself: no job, today's form.
+    const bool policy_beside = engine_policy_beside_step(e, defer_legal);
     for (int sim = 0; sim < e.sims; ++sim) {
         const bool defer = defer_legal && sim > 0;
-        if (int r = launch_engine_step(es, sim > 0 ? 1 : 0, 1, st, use_list ? sim : -1, step_heads, defer)) return r;
+        if (int r = launch_engine_step(es, sim > 0 ? 1 : 0, 1, st, use_list ? sim : -1, step_heads, defer, policy_beside && sim > 1)) return r;
         if (defer) {
-            if (int r = launch_engine_eval(e, st)) return r;
+            if (int r = launch_engine_eval(e, st, policy_beside)) return r;
         } else if (e.prior_mode == 0) {
             // (simulation 0 -- the root's evaluation -- keeps its heads launch: root noise reads the root's row and value from e.policy /
             //  e.value, and without noise the launch is there only so that these buffers hold the root's evaluation after a search, as
@@ -197,7 +201,7 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reus
         if (sim == 0 && e.root_noise_eps > 0.f)                                    // the root's priors, before simulation 1 expands it
             if (int r = launch_engine_root_noise(e, st)) return r;
     }
-    if (int r = launch_engine_step(es, 1, 0, st, -1, step_heads)) return r;  // expand + backup of the last simulation
+    if (int r = launch_engine_step(es, 1, 0, st, -1, step_heads, false, policy_beside && e.sims > 1)) return r;  // expand + backup of the last simulation
     return check_launch("engine simulation kernels");
 }
 
@@ -229,7 +233,7 @@ static int run_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reuse* r
     const uint8_t* kept = reuse ? reuse->kept : nullptr;
     const int keep_visits = reuse ? reuse->keep_visits : 0;
     // every option a captured launch bakes in is part of the key: a changed option must never replay a stale graph
-    const int opts[7] = {g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, e.board_size, g_step_fast_depth, ((g_trunk_prio & 0xff) << 8) | (g_step_waves << 16) | (g_step_prio << 24) | (g_heads_prio << 28) | (g_step_heads & 1) | ((g_legal_beside_trunk & 1) << 1)};
+    const int opts[7] = {g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, e.board_size, g_step_fast_depth, ((g_trunk_prio & 0xff) << 8) | (g_step_waves << 16) | (g_step_prio << 24) | (g_heads_prio << 28) | (g_step_heads & 1) | ((g_legal_beside_trunk & 1) << 1) | ((g_policy_beside_step & 1) << 2)};
     for (SimGraph& g : g_sim_graphs)
         if (!memcmp(&g.e, &e, sizeof(aqg_engine)) && !memcmp(g.opts, opts, sizeof(opts)) && g.kept == kept && g.keep_visits == keep_visits) return replay(g, st);
     if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {

@@ -22,6 +22,7 @@ struct LeafLegalArgs {
     const uint8_t* leaf_flag; const uint8_t* leaf_state;
     uint8_t* legal_order; int32_t* legal_count;
     int32_t* searched;            // counters[6]: leaves searched here
+    const int32_t* node_count; PolicyJob* jobs;      // option "policy_beside_step" (jobs == nullptr: off): see leaf_legal_role
     int32_t num_games, prio;
 };
 
@@ -29,6 +30,10 @@ struct LeafLegalArgs {
 // game g with leaf_flag[g] == 1 and the step's marker legal_count[g] == -1 gets legal_order[g][..] and legal_count[g] exactly as the
 // step would have written them -- the same wave_legal_prepare + wave_legal_finish on the same state.  A game whose step searched itself
 // (no marker), an idle game and a wave beyond num_games do nothing.
+// Option "policy_beside_step": the step launch behind this one expands a marked leaf in a workgroup of its own, beside the game's step
+// workgroup -- which overwrites leaf_flag, legal_count and node_count while that workgroup may still be starting.  So the search leaves
+// what the expansion needs of the three in the game's job record: {node_count[g], total} for a marked leaf -- node_count does not change
+// during an evaluation launch -- and {0, 0} for every other game of the set, whatever an earlier launch left there.
 // One workgroup barrier, at the start and for the counter only: wave 0 counts the workgroup's marked games for counters[6] (one atomic
 // per workgroup instead of one per game on one address), and behind the barrier no wave has overwritten a marker yet.
 template <int N>
@@ -36,6 +41,7 @@ __device__ __forceinline__ void leaf_legal_role(const LeafLegalArgs& a, int blk,
     if (a.prio == 1) __builtin_amdgcn_s_setprio(1); else if (a.prio == 2) __builtin_amdgcn_s_setprio(2); else if (a.prio == 3) __builtin_amdgcn_s_setprio(3);
     const int g = blk * NWV + wave, gc = min(g, a.num_games - 1);              // (a wave without a game loads the last game's: no branch)
     const int flag = a.leaf_flag[gc], cnt = a.legal_count[gc];
+    const int first_new = a.jobs ? a.node_count[gc] : 0;
     const uint64_t* lq = reinterpret_cast<const uint64_t*>(a.leaf_state) + (size_t)gc * 3;
     const uint64_t q0 = lq[0], q1 = lq[1], q2 = lq[2];
     int marked = 0;
@@ -47,7 +53,10 @@ __device__ __forceinline__ void leaf_legal_role(const LeafLegalArgs& a, int blk,
     const bool mine = g < a.num_games && __builtin_amdgcn_readfirstlane(flag) == 1 && __builtin_amdgcn_readfirstlane(cnt) == -1;
     __syncthreads();
     if (wave == 0 && lane == 0 && marked) atomicAdd(a.searched, marked);
-    if (!mine) return;
+    if (!mine) {
+        if (a.jobs && g < a.num_games && lane == 0) a.jobs[g] = PolicyJob{0, 0};
+        return;
+    }
     QState v;
     v.hw = q0; v.vw = q1;
     v.ppos = (uint8_t)(q2 & 0xff); v.pwl = (uint8_t)((q2 >> 8) & 0xff); v.epos = (uint8_t)((q2 >> 16) & 0xff); v.ewl = (uint8_t)((q2 >> 24) & 0xff);
@@ -55,7 +64,10 @@ __device__ __forceinline__ void leaf_legal_role(const LeafLegalArgs& a, int blk,
     const QState s = uniform_state(v);
     const LegalPrep prep = wave_legal_prepare<N>(s, lane);
     const int total = wave_legal_finish<N>(s, prep, lane, nullptr, a.legal_order + (size_t)g * MAX_LEGAL);
-    if (lane == 0) a.legal_count[g] = total;
+    if (lane == 0) {
+        a.legal_count[g] = total;
+        if (a.jobs) a.jobs[g] = PolicyJob{first_new, total};
+    }
 }
 
 // Workgroups [0, legal_blocks) search, workgroups [legal_blocks, gridDim.x) are the trunk's: the searches come first so that they
@@ -91,15 +103,25 @@ bool engine_step_defers_legal(const aqg_engine& e, bool step_heads) {
            e.num_games < LEGAL_BESIDE_TRUNK_BELOW;
 }
 
+// Option "policy_beside_step" (mcts_step.hip): the step launches behind an evaluation launch split the expansion off into policy workgroups.
+// Wherever the searches are deferred and the engine has a workspace for the jobs (aqgnn.h, gnn_workspace); no set-size gate of its own:
+// deferring ends at 1,024 games.
+int g_policy_beside_step = 1;
+bool engine_policy_beside_step(const aqg_engine& e, bool defer_legal) {
+    return g_policy_beside_step && defer_legal && e.gnn_workspace;
+}
+
 // The evaluation launch behind a deferring step: what launch_gcn_forward_boards launches for the engine's leaves without heads -- same
 // board workgroups, same options, same profiling bracket -- with ceil(num_games / 8) search workgroups in front.
-int launch_engine_eval(const aqg_engine& e, hipStream_t st) {
+// `policy_jobs`: the step launch behind this one has policy workgroups, the searches leave them their jobs.
+int launch_engine_eval(const aqg_engine& e, hipStream_t st, bool policy_jobs) {
     const int B = e.num_games;
     if (!e.pooled) return fail("pooled workspace is required");
     int grid, opts;
     trunk_split_launch_shape(B, false, grid, opts);
     const unsigned int legal_blocks = (unsigned int)((B + NWV - 1) / NWV);
-    const LeafLegalArgs la = {e.leaf_flag, e.leaf_state, e.legal_order, e.legal_count, e.counters + 6, B, g_step_prio & 3};
+    const LeafLegalArgs la = {e.leaf_flag, e.leaf_state, e.legal_order, e.legal_count, e.counters + 6,
+                              e.node_count, policy_jobs ? aqg::policy_jobs(e) : nullptr, B, g_step_prio & 3};
     const dim3 tg(legal_blocks + grid), tb(64 * NWV);
     int32_t* saturated = e.counters + 5;
     if (g_profile_trunk == 1) profile_mark(st, B);

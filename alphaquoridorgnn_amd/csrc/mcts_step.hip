@@ -115,7 +115,10 @@ struct StepRound1 {
 };
 // HEADS: the step kernel has computed the leaves' policy rows itself (they are in LDS); what is left to fetch of e.policy is the
 // legal-ordered row of a leaf_flag 2 leaf (three lane rounds instead of the dense row's four)
-template <int N, bool CACHE, bool HEADS>
+// LEAN (the step workgroups of option "policy_beside_step", whose round 1 is in flight beside the value head's operands): without what only
+// a leaf_flag 2 leaf needs -- its value, its legal-ordered row, the legal list beyond the first action; such a leaf is never seen there,
+// and game_step_fast<.., PB> fetches them itself if it meets one
+template <int N, bool CACHE, bool HEADS, bool LEAN = false>
 __device__ __forceinline__ void step_round1(const aqg_engine& e, int g, int lane, int do_expand, StepRound1& r1) {
     constexpr int A = Geo<N>::A;
     const NodeRec* __restrict__ nodes = game_nodes(e, g);
@@ -134,7 +137,8 @@ __device__ __forceinline__ void step_round1(const aqg_engine& e, int g, int lane
         // (always an expanding launch.  No branch around any load -- indices are clamped, and the consumer masks what a clamped index
         //  fetched -- so that the compiler can COUNT the loads in flight: behind a divergent region its waits become s_waitcnt vmcnt(0),
         //  and the heads' policy layer in front of the step would wait for this whole round)
-        flag = e.leaf_flag[g]; depth_old = e.path_len[g]; cnt_new = e.legal_count[g]; first_new = e.node_count[g]; value = e.value[g];
+        flag = e.leaf_flag[g]; depth_old = e.path_len[g]; cnt_new = e.legal_count[g]; first_new = e.node_count[g];
+        if (!LEAN) value = e.value[g];
         if (CACHE) {
             cslot = e.eval_cache_slot[g];
             const uint64_t* lq = reinterpret_cast<const uint64_t*>(e.leaf_state) + (size_t)g * 3;
@@ -142,8 +146,11 @@ __device__ __forceinline__ void step_round1(const aqg_engine& e, int g, int lane
         }
         static_assert(!HEADS || MAX_LEGAL <= A, "the legal-ordered row fits the dense one");
         static_assert(128 < MAX_LEGAL && MAX_LEGAL <= 192, "lane rounds 0 and 1 lie inside the legal list, round 2 is masked by the consumer");
+        if (LEAN) oa[0] = (uint32_t)ord[lane];
+        else {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) { const int i = min(lane + 64 * r, MAX_LEGAL - 1); oa[r] = (uint32_t)ord[i]; polr[r] = pol[i]; }
+            for (int r = 0; r < 3; ++r) { const int i = min(lane + 64 * r, MAX_LEGAL - 1); oa[r] = (uint32_t)ord[i]; polr[r] = pol[i]; }
+        }
         pnode = path[min(lane, e.sims + 1)];
     } else if (do_expand) {
         flag = e.leaf_flag[g]; depth_old = e.path_len[g]; cnt_new = e.legal_count[g]; first_new = e.node_count[g]; value = e.value[g];
@@ -185,7 +192,16 @@ __device__ __forceinline__ void step_round1(const aqg_engine& e, int g, int lane
 // DEFER (cache-less HEADS launches in front of engine_eval_kernel, option "legal_beside_trunk"): the new leaf's legal-move search is
 // left to the evaluation launch that follows on the stream -- nothing in this launch reads its result -- and the step ends on the
 // leaf's state with legal_count = -1, the marker that search looks for (leaf_legal_role, mcts_eval.hip)
-template <int N, bool CACHE, bool HEADS, bool DEFER = false>
+// PB (cache-less HEADS launches behind engine_eval_kernel, option "policy_beside_step"): the workgroup computed the value head only, and
+// the expansion of the old leaf is split with the game's policy workgroup (policy_beside_role below), which gathers the priors and
+// writes the new children.  This wave keeps what the descent and the backup need: the old leaf's `kids`, node_count, and -- of the
+// FIRST new child alone -- the fields w, n, kids, q: a descent that reaches the old leaf takes that child, and if its position is
+// terminal this launch backs the simulation up into its record.  The policy workgroup writes that record's other fields (p, action,
+// cp: disjoint bytes) and the other children's whole records, which nothing in this launch touches.  Whatever the timing of the two
+// workgroups, memory ends as the one-workgroup form leaves it.  No value the step uses is loaded from those records: past the
+// hand-over to memory, too, the old leaf is recognised by its node index and its first child taken without a look at the records.
+// A leaf_flag 2 leaf (never seen behind an evaluation launch) has no job and is expanded here as ever.
+template <int N, bool CACHE, bool HEADS, bool DEFER = false, bool PB = false>
 __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int lane, int do_expand, int do_select, int fast_depth,
                                                float* __restrict__ polbuf /* this wave's 256 floats of LDS */, int list_sim,
                                                const StepRound1& r1, float head_value) {
@@ -199,9 +215,9 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
     int flag = r1.flag, depth_old = r1.depth_old, cnt_new = r1.cnt_new, first_new = r1.first_new;
     float value = r1.value;
     // (HEADS: its loader clamps indices instead of branching around loads)
-    const uint8_t oa[3] = {(uint8_t)r1.oa0, (uint8_t)r1.oa1, (uint8_t)((HEADS && lane + 128 >= MAX_LEGAL) ? 0u : r1.oa2)};
+    uint8_t oa[3] = {(uint8_t)r1.oa0, (uint8_t)r1.oa1, (uint8_t)((HEADS && lane + 128 >= MAX_LEGAL) ? 0u : r1.oa2)};
     const int pnode = (HEADS && lane >= e.sims + 2) ? 0 : r1.pnode;
-    const float polr[4] = {r1.polr0, r1.polr1, r1.polr2, r1.polr3};
+    float polr[4] = {r1.polr0, r1.polr1, r1.polr2, r1.polr3};
     // evaluation cache (aqgnn.h, ABI 10): a per-slot table of the positions this slot's games have already sent through the network
     constexpr bool cache_on = CACHE;
     int cslot = r1.cslot;
@@ -217,6 +233,17 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
     // legal actions in order (the layout of the other evaluator modes), legal_order / legal_count / value came with them
     const bool hit_old = flag == 2;
     if (hit_old) flag = 1;
+    if (PB && hit_old) {             // (the lean round 1 left these out)
+        const uint8_t* ord = e.legal_order + (size_t)g * MAX_LEGAL;
+        const float* pol = e.policy + (size_t)g * A;
+        value = e.value[g];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int i = min(lane + 64 * r, MAX_LEGAL - 1);
+            oa[r] = (lane + 64 * r < MAX_LEGAL) ? ord[i] : (uint8_t)0;
+            polr[r] = pol[i];
+        }
+    }
     if (HEADS && !hit_old) value = head_value;
     if (flag != 1 && !do_select) return;
 #ifdef AQG_STAMP
@@ -237,17 +264,19 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             }
-            float sum = 0.f;
+            if (!PB) {                           // (PB: the policy workgroup's, policy_beside_role)
+                float sum = 0.f;
 #pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const int i = lane + 64 * r;
-                pl[r] = (i < cnt_new) ? polbuf[oa[r]] : 0.f;
-                sum += pl[r];
+                for (int r = 0; r < 3; ++r) {
+                    const int i = lane + 64 * r;
+                    pl[r] = (i < cnt_new) ? polbuf[oa[r]] : 0.f;
+                    sum += pl[r];
+                }
+                sum = wave_sum_f(sum);
+                const float den = (sum != 0.f) ? sum : 1.f;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) pl[r] = pl[r] / den;
             }
-            sum = wave_sum_f(sum);
-            const float den = (sum != 0.f) ? sum : 1.f;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) pl[r] = pl[r] / den;
         } else {                     // fake / external evaluator, or a leaf served from the evaluation cache: legal-ordered normalised priors
 #pragma unroll
             for (int r = 0; r < 3; ++r) { const int i = lane + 64 * r; pl[r] = (i < cnt_new) ? polr[r] : 0.f; }
@@ -275,14 +304,19 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
             }
         }
         if (expanded) {                  // pv_mcts.py:52-56: one child per legal action, in legal_actions() order, with its prior
+            if (!PB || hit_old) {
 #pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const int i = lane + 64 * r;
-                if (i < cnt_new) {
-                    NodeRec c;
-                    c.w = 0.0; c.p = pl[r]; c.n = 0; c.kids = 0; c.action = oa[r]; c.q = 0.f; c.cp = e.c_puct * pl[r];
-                    nodes[first_new + i] = c;
+                for (int r = 0; r < 3; ++r) {
+                    const int i = lane + 64 * r;
+                    if (i < cnt_new) {
+                        NodeRec c;
+                        c.w = 0.0; c.p = pl[r]; c.n = 0; c.kids = 0; c.action = oa[r]; c.q = 0.f; c.cp = e.c_puct * pl[r];
+                        nodes[first_new + i] = c;
+                    }
                 }
+            } else if (lane == 0) {      // the first child's statistics: this wave's (see PB above)
+                NodeRec& c = nodes[first_new];
+                c.w = 0.0; c.n = 0; c.kids = 0; c.q = 0.f;
             }
             if (lane == 0) {
                 nodes[leaf_old].kids = (uint32_t)first_new | ((uint32_t)cnt_new << 24);
@@ -461,6 +495,7 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
         if (lose || draw) { tvalue = lose ? -1.0 : 0.0; terminal = 1; return 1; }   // pv_mcts.py:35-42
         if ((kids >> 24) == 0) return 2;                                            // pv_mcts.py:45 unexpanded leaf
         if (regs && onpath && depth == depth_old) return 3;
+        if (PB && !regs && node == leaf_old) return 3;                              // (PB: the new children are another workgroup's to write)
         return 0;
     };
     // Children travel as the record's two aligned 16-byte halves and are requested for all three slots whatever the child count (lanes /
@@ -681,6 +716,67 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
 #endif
 }
 
+// The policy workgroup of eight games (engine_step_fast_kernel<.., PB>, option "policy_beside_step"; workgroup `blk` of the launch's policy
+// range, same grouping as the step workgroups): the policy half of heads_body for the games' leaves, then -- one wave per game -- the
+// expansion the one-workgroup form does in game_step_fast: the gather at the legal actions, wave_sum_f, the division, the child records,
+// in the same order of operations.  Its per-game inputs are the job record the evaluation launch's search left (leaf_legal_role,
+// mcts_eval.hip), legal_order[g] and the pooled row: nothing the step workgroups of this launch write.  leaf_flag, legal_count and
+// node_count, which they overwrite, are not read here.  Of the first child it writes p, action and cp only (see PB above).
+// Nothing waits for another workgroup; the job is cleared behind its use; counters[7] counts the jobs taken.
+template <int N>
+__device__ __forceinline__ void policy_beside_role(const aqg_engine& e, int blk, int wave, int lane, HeadsSmem& hsm, float (*polbuf)[256]) {
+    PolicyJob* jobs = policy_jobs(e);
+    const int g = blk * 8 + wave, gc = min(g, e.num_games - 1);                    // (a wave without a game loads the last game's: no branch)
+    const int b0 = blk * 8, bend = min(e.num_games, b0 + 8);
+    // requested in front of the heads' operands: the job and the legal list
+    const PolicyJob job = jobs[gc];
+    // counters[7]: the jobs taken here, one atomic per workgroup -- wave 0 counts them from loads of its own, requested with everything
+    // else (every job of the workgroup is cleared behind the barriers below, not before)
+    int taken = 0;
+    if (wave == 0) {
+        const int gi = min(b0 + (lane & 7), e.num_games - 1);
+        taken = __popcll(__ballot(lane < 8 && b0 + lane < e.num_games && jobs[gi].first_new > 0));
+    }
+    const uint8_t* ord = e.legal_order + (size_t)gc * MAX_LEGAL;
+    uint32_t oa[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) oa[r] = (uint32_t)ord[min(lane + 64 * r, MAX_LEGAL - 1)];
+    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(e.pooled, 0, e.num_games * (HID * 4), 0x00020000);
+    heads_half<HEADS_POLICY>(hsm, prs, b0, bend, Geo<N>::A, packed_rsrc(e.packed_weights), e.packed_weights, nullptr, nullptr, nullptr, nullptr,
+                                   (const PolicyJob*)jobs, e.counters + 5, wave, lane, polbuf, nullptr);
+    __syncthreads();                             // the rows are complete: each wave reads its own game's
+    if (wave == 0 && lane == 0 && taken) atomicAdd(e.counters + 7, taken);
+    const int first_new = __builtin_amdgcn_readfirstlane(job.first_new), cnt_new = __builtin_amdgcn_readfirstlane(job.cnt);
+    if (g >= e.num_games || first_new <= 0) return;
+    NodeRec* __restrict__ nodes = game_nodes(e, g);
+    const float* row = polbuf[wave];
+    float pl[3];
+    float sum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {                // P0: gather at the legal actions, divide by the sum unless 0 (pv_network_cnn.py:129-132)
+        const int i = lane + 64 * r;
+        pl[r] = (i < cnt_new) ? row[oa[r] & 0xFF] : 0.f;
+        sum += pl[r];
+    }
+    sum = wave_sum_f(sum);
+    const float den = (sum != 0.f) ? sum : 1.f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) pl[r] = pl[r] / den;
+    if (cnt_new > 0 && first_new + cnt_new <= e.node_cap) {      // `expanded`, from the numbers the step workgroup has
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int i = lane + 64 * r;
+            if (i < cnt_new) {
+                NodeRec c;
+                c.w = 0.0; c.p = pl[r]; c.n = 0; c.kids = 0; c.action = oa[r]; c.q = 0.f; c.cp = e.c_puct * pl[r];
+                if (i == 0) { NodeRec& d = nodes[first_new]; d.p = c.p; d.action = c.action; d.cp = c.cp; }
+                else nodes[first_new + i] = c;
+            }
+        }
+    }
+    if (lane == 0) jobs[g] = PolicyJob{0, 0};
+}
+
 // ------------------------------------------------------------------------------------------------
 // fused simulation step, one wavefront per game:
 //   [expand + backup of the PREVIOUS simulation's leaf]  ->  [select the next leaf + its legal actions]
@@ -695,8 +791,15 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
 // (96 registers of operands), the step's own round 1 (about 50) as soon as the hidden layer's MFMAs are issued and their operands are
 // dead -- it is in flight under the hidden layer's epilogue, the policy layer, the softmax and three barriers, not behind them.
 // Nothing waits for another workgroup: every input was written by a launch that has finished.
-template <int N, bool CACHE, bool HEADS, bool DEFER = false>
+// PB (cache-less HEADS launches behind engine_eval_kernel; option "policy_beside_step"): two kinds of workgroup, selected by block range
+// like engine_eval_kernel's.  Workgroups [0, gridDim.x / 2) are the step's: they compute the VALUE half of the heads only -- waves 4..7
+// one hidden tile each, a quarter of the operands, so the step's own round 1 is requested beside them at entry -- and leave the policy
+// layer, the softmax with its barriers, the gather and the child records to workgroups [gridDim.x / 2, gridDim.x), one per eight games
+// in the same grouping (policy_beside_role): nothing of that is on the way to the next leaf.  The step workgroups come first, so that
+// they start at once.
+template <int N, bool CACHE, bool HEADS, bool DEFER = false, bool PB = false>
 __global__ __launch_bounds__(512, HEADS ? 4 : 1) void engine_step_fast_kernel(aqg_engine e, int do_expand, int do_select, int fast_depth, int list_sim) {
+    static_assert(!PB || (HEADS && !CACHE), "policy workgroups: the cache-less form with the heads inside");
     __shared__ float polbuf[8][256];
     AQG_TRACE_BEGIN
     const int lane = threadIdx.x & 63;
@@ -706,7 +809,21 @@ __global__ __launch_bounds__(512, HEADS ? 4 : 1) void engine_step_fast_kernel(aq
     { const int pr = (fast_depth >> 8) & 3; if (pr == 1) __builtin_amdgcn_s_setprio(1); else if (pr == 2) __builtin_amdgcn_s_setprio(2); else if (pr == 3) __builtin_amdgcn_s_setprio(3); }
     fast_depth &= 0xFF;
     StepRound1 r1;
-    if constexpr (HEADS) {                       // (launched with do_expand set and eight waves only)
+    if constexpr (PB) {                          // (launched with do_expand set, eight waves and twice the step's workgroups)
+        __shared__ HeadsSmem hsm;
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const int nstep = (int)(gridDim.x >> 1);
+        if ((int)blockIdx.x >= nstep) {
+            policy_beside_role<N>(e, (int)blockIdx.x - nstep, wave, lane, hsm, polbuf);
+        } else {
+            const int b0 = blockIdx.x * 8, bend = min(e.num_games, b0 + 8);
+            const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(e.pooled, 0, e.num_games * (HID * 4), 0x00020000);
+            const float hv = heads_half<HEADS_VALUE>(hsm, prs, b0, bend, Geo<N>::A, packed_rsrc(e.packed_weights), e.packed_weights, nullptr, nullptr,
+                                                           nullptr, nullptr, (const uint8_t*)e.leaf_flag, nullptr, wave, lane, nullptr, nullptr,
+                                                           [&]() { step_round1<N, CACHE, true, true>(e, min(g, e.num_games - 1), lane, 1, r1); });
+            if (g < e.num_games) game_step_fast<N, CACHE, true, DEFER, true>(e, g, lane, do_expand, do_select, fast_depth, polbuf[wave], list_sim, r1, hv);
+        }
+    } else if constexpr (HEADS) {                // (launched with do_expand set and eight waves only)
         __shared__ HeadsSmem hsm;
         __shared__ float hval[16];
         const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -729,7 +846,10 @@ AQG_TRACE_SETTER(set_trace_mcts)
 // kernel; the caller has checked that the form applies).  `list_sim` >= 0: the leaves that miss the evaluation cache are listed for
 // the trunk launch of that simulation.  `defer_legal`: the caller launches engine_eval_kernel behind this step, which then leaves its
 // leaves' legal-move searches to it (only the cache-less `heads` form of a selecting step does; any other form searches itself).
-int launch_engine_step(const aqg_engine& e_in, int do_expand, int do_select, hipStream_t st, int list_sim, bool heads, bool defer_legal) {
+// `policy_beside`: the launch in front was engine_eval_kernel with the expansion jobs (the caller has checked that the form applies): the
+// fused cache-less launch gets its policy workgroups behind the step's.
+int launch_engine_step(const aqg_engine& e_in, int do_expand, int do_select, hipStream_t st, int list_sim, bool heads, bool defer_legal,
+                       bool policy_beside) {
     // prior_mode 3 and 4 leave the network's dense [G,A] policy in e.policy exactly like prior_mode 0: the step kernels gather,
     // renormalise and cache it as mode 0 -- they are handed the struct with prior_mode 0, so no step kernel knows mode 3 or 4
     aqg_engine e = e_in;
@@ -748,6 +868,8 @@ int launch_engine_step(const aqg_engine& e_in, int do_expand, int do_select, hip
         if constexpr (N == 9) {
             if (fused) {
                 if (cache) launch(engine_step_fast_kernel<N, true, true>);
+                else if (policy_beside)          // (DEFER shapes the select half only: the last expansion, which selects nothing, runs the same kernel)
+                    hipLaunchKernelGGL((engine_step_fast_kernel<N, false, true, true, true>), dim3(2 * sg.x), sb, 0, st, e, do_expand, do_select, fd, list_sim);
                 else if (defer_legal && do_select) launch(engine_step_fast_kernel<N, false, true, true>);
                 else launch(engine_step_fast_kernel<N, false, true>);
             }

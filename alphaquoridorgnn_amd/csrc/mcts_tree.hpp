@@ -44,6 +44,15 @@ __device__ __forceinline__ NodeRec* game_nodes(const aqg_engine& e, int g) {
     return reinterpret_cast<NodeRec*>(e.node_rec) + (size_t)g * e.node_cap;
 }
 
+// The expansion job of a game (option "policy_beside_step"; the jobs live in the engine's gnn_workspace, which the 9x9 forward leaves
+// alone: aqgnn.h): written by the evaluation launch's search of a marked leaf, read and cleared by the policy workgroup of the step
+// launch behind it.  first_new = the game's node_count at the time of the
+// search (>= 1: the root is node 0; 0 = no job), cnt = the leaf's legal actions.  The step workgroup of the same launch reads the same
+// two numbers from node_count / legal_count, so both decide `expanded` alike.
+struct PolicyJob { int32_t first_new, cnt; };
+__host__ __device__ __forceinline__ PolicyJob* policy_jobs(const aqg_engine& e) { return reinterpret_cast<PolicyJob*>(e.gnn_workspace); }
+__device__ __forceinline__ unsigned int head_live(const PolicyJob* jobs, int i) { return jobs[i].first_new > 0 ? 1u : 0u; }    // (heads_body's board mask)
+
 // Backup (pv_mcts.py:36-42,:49-50,:62-64): every node on the path gets w += value, n += 1 with the sign flipping
 // per ply.  The path nodes are distinct, so lane d updates path[d] independently (one parallel step instead of a
 // serial chain of dependent global read-modify-writes); the sums are the same float64 additions.

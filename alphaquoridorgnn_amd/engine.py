@@ -400,6 +400,11 @@ class BatchedSelfPlay:
         option "legal_beside_trunk").  0 wherever the step kernel searches itself: option off, evaluation cache on, other evaluators."""
         return int(self.t["counters"][6].item())
 
+    def policy_beside_expansions(self):
+        """Leaves expanded by the policy workgroups of a step launch, beside its step workgroups, since the last reset (aqgnn.h
+        counters[7]; option "policy_beside_step").  0 wherever the step workgroup expands itself."""
+        return int(self.t["counters"][7].item())
+
     def switch_to_exact_kernels(self, keep_roots=False):
         """The range guard fired: this weight set leaves fp16 range on positions of this generation.  Its evaluations so far were
         finite but not the network's, so the model is marked and the engine moves to the exact f32-input kernels (the reference's fp32

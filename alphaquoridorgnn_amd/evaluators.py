@@ -52,8 +52,9 @@ class _Gnn(Evaluator):
         if model is not None and not getattr(model, "fused", True):
             model._require_fused("evaluator='gnn'")
 
-    def workspace_floats(self, lib, model, N, A, G):      # smaller boards run the any-size forward, which needs a caller-owned workspace
-        return int(lib.aqg_gcn_boards_any_workspace_floats(N, G)) if N != 9 else 0
+    def workspace_floats(self, lib, model, N, A, G):      # smaller boards run the any-size forward, which needs a caller-owned workspace;
+        # 9x9: the forward needs none -- two words per slot for the expansion jobs of option "policy_beside_step" (aqgnn.h, gnn_workspace)
+        return int(lib.aqg_gcn_boards_any_workspace_floats(N, G)) if N != 9 else 2 * G
 
     def handle(self, model, dev, board=None):
         if model is None:

@@ -48,6 +48,13 @@ const char* aqg_last_error(void);
  * new leaf (state, flag, legal_count = -1) and the launch behind it carries ceil(num_games / 8) workgroups that search those leaves' legal
  * moves in front of the trunk's board workgroups -- the same search on the same state, beside the trunk instead of in front of it; still
  * two launches per simulation, bit-identical searches; counters[6] counts the leaves searched there; part of the captured graphs' key;
+ * "policy_beside_step" 0/1 (default 1; additive to ABI 15): where "legal_beside_trunk" applies and the engine has a `gnn_workspace` (the expansion jobs live there: see the field), the step launches
+ * behind an evaluation launch (simulations 2 .. sims - 1 and the move's last expansion) carry a second kind of workgroup, one per eight
+ * games behind the step workgroups: it computes the leaves' policy rows, gathers and renormalises them at the legal actions and writes
+ * the new child records, while the step workgroup of the same games computes only the value head, backs up and descends -- nothing in
+ * a step launch reads the children it creates.  The evaluation launch's search leaves each marked leaf's {node_count, legal count} in
+ * its job record, the only per-game input of the policy workgroups that the step workgroups do not overwrite; counters[7] counts the leaves expanded there.  No new launch, stream or
+ * graph branch; bit-identical searches; part of the captured graphs' key;
  * "train_fused" = form of the training step
  * (csrc/gcn_train.hip): 2 (default) one workgroup per position with every contraction in fp16 split precision on the 16-bit
  * matrix pipe (9x9 board; a position whose values leave fp16 range is redone in f32 inside the same launch, counted by
@@ -339,13 +346,19 @@ typedef struct aqg_engine {
     /* counters [8] i32: 0 active slots, 1 finished games, 2 dead-end aborts, 3 next game index to hand out, 4 moves made
      * (updated once per move), 5 fp16-range guard: set to 1 by a GNN evaluation of this engine that met a value outside fp16 range
      * (see aqg_gcn_forward_boards_guarded; cleared by aqg_engine_reset only), 6 leaves whose legal-move search ran in the evaluation
-     * launch beside the trunk instead of in the step launch (option "legal_beside_trunk"; cleared by aqg_engine_reset only) */
+     * launch beside the trunk instead of in the step launch (option "legal_beside_trunk"; cleared by aqg_engine_reset only), 7 leaves
+     * expanded by the policy workgroups of a step launch (option "policy_beside_step"; cleared by aqg_engine_reset only) */
     int32_t* counters;
     /* per-game statistics [G] i32 (summed by the host): network evaluations, simulations that ended on a terminal node */
     int32_t* stat_leaf_evals; int32_t* stat_terminal_sims;
     const float* packed_weights;
     /* boards other than 9x9 with prior_mode 0: workspace of the any-size forward, aqg_gcn_boards_any_workspace_floats(N, G)
-     * floats (may be NULL for 9x9 and for prior_mode 1) */
+     * floats (may be NULL for 9x9 and for prior_mode 1).
+     * 9x9 with prior_mode 0: the forward uses none of it; NULL, or at least 2 * num_games words -- a workspace of the size above is
+     * larger -- whose first 2 G words are [G, 2] i32 expansion jobs {first_new, cnt} of option "policy_beside_step": what the evaluation
+     * launch's legal-move search leaves for the policy workgroups of the step launch behind it ({0, 0} = none; every job is rewritten
+     * by each evaluation launch and cleared by the step launch that used it, so the content the caller leaves there does not matter).
+     * NULL: the option does not apply. */
     float* gnn_workspace;
     /* Evaluation cache (ABI 10; prior_mode 0, 3 (ABI 14) or 4; eval_cache_keys == NULL: off).  The reference builds a new tree for every move
      * (pv_mcts.py:84) and keeps no transposition table, so a game asks model.predict (pv_mcts.py:47) for the same position again and
