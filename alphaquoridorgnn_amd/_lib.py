@@ -237,6 +237,9 @@ SIGNATURES = {
     "aqg_replay_merge_workspace_floats": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
     "aqg_replay_merge_runs": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_size_t,
                                          _vp]),
+    "aqg_replay_surprise_rows": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp]),
+    "aqg_replay_surprise_counts": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_longlong, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint64, _vp,
+                                              _vp]),
     "aqg_host_legal_actions": (_c.c_int, [_c.c_int, _vp, _vp]),
     "aqg_host_next": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp]),
     "aqg_host_shortest_path": (_c.c_int, [_c.c_int, _vp]),

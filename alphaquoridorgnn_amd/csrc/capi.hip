@@ -585,4 +585,14 @@ int aqg_replay_merge_runs(int board_size, int policy_size, const uint8_t* states
                                     workspace_floats, (hipStream_t)stream);
 }
 
+int aqg_replay_surprise_rows(int board_size, int policy_size, const float* net_policy, const float* ring_pi, const int64_t* index,
+                             int rows, int m, int offset, int n, float* k, int32_t* q, void* stream) {
+    return launch_replay_surprise_rows(board_size, policy_size, net_policy, ring_pi, index, rows, m, offset, n, k, q, (hipStream_t)stream);
+}
+int aqg_replay_surprise_counts(const int32_t* q, const int64_t* index, const int64_t* total, int m, long long expected_rows,
+                               double uniform_share, int max_copies, uint64_t seed, uint64_t update, int32_t* count, void* stream) {
+    return launch_replay_surprise_counts(q, index, total, m, expected_rows, uniform_share, max_copies, seed, update, count,
+                                         (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -264,4 +264,10 @@ int launch_replay_merge_runs(int N, int policy_size, const uint8_t* states72, co
                              const int64_t* starts, int n, int u, uint8_t* out72, float* out_pi, float* out_z, int32_t* count,
                              float* workspace, size_t workspace_floats, hipStream_t st);
 
+// ---- replay_surprise.hip
+int launch_replay_surprise_rows(int N, int policy_size, const float* net_policy, const float* ring_pi, const int64_t* index, int rows,
+                                int m, int offset, int n, float* k, int32_t* q, hipStream_t st);
+int launch_replay_surprise_counts(const int32_t* q, const int64_t* index, const int64_t* total, int m, long long expected_rows,
+                                  double uniform_share, int max_copies, uint64_t seed, uint64_t update, int32_t* count, hipStream_t st);
+
 }  // namespace aqg

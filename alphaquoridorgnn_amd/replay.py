@@ -27,6 +27,13 @@ of chosen valid rows overwritten, in one launch, by the results of a fresh searc
 kernel in numpy, `draw_reanalyse_rows` picks the rows of one pass.  `ReplayWindow.refresh_policy` (aqg_replay_refresh_policy,
 `refresh_policy_reference`) is the same launch with finished f32 policy entries for the source, copied verbatim: the completed-Q
 targets of engine.root_improved_policy.
+
+Policy surprise weighting (`surprise_index`, `ReplayWindow.surprise_index`; csrc/replay_surprise.hip): which rows an update trains
+on.  k = KL(the row's policy target || the policy of the network the update starts from), taken at training time -- so it is always
+about the target the row holds now, whatever Reanalyse, the merge or a blend did to it -- becomes an expected number of copies, half
+of the update's rows dealt out evenly and half in proportion to k (KataGo's policy surprise weighting); a counter-based draw per ring
+slot rounds it to a count, and the update's `index` names each row that many times.  `surprise_reference` and
+`surprise_counts_reference` are the two launches in numpy; the definition is in include/aqgnn.h.
 """
 import pickle
 
@@ -384,6 +391,182 @@ def merge_positions(states72, pi, z, index=None, board_size=BOARD_SIZE):
     return out
 
 
+# ---- policy surprise weighting: the rows of an update drawn by KL(target || network) (csrc/replay_surprise.hip)
+
+SURPRISE_MAX_ROWS = 1 << 24         # m at most (SPR_MAX_ROWS): S = sum q < 2^51
+SURPRISE_TINY = np.float32(2.0 ** -126)     # the least p a logarithm is taken of (SPR_TINY)
+SURPRISE_K_MAX = 88.0               # > 126 ln 2 (SPR_K_MAX): never reached by a row whose target sums to 1
+SURPRISE_Q_SCALE = 2.0 ** 20
+
+
+def check_surprise_options(expected_rows, uniform_share, max_copies):
+    """Validate the options of steps 3 and 4 as the library does: expected_rows None or an int >= 1, uniform_share in [0, 1] and not
+    NaN, max_copies an int in 1..255.  Returns them as (int or None, float, int)."""
+    share = float(uniform_share)
+    if not 0.0 <= share <= 1.0:
+        raise ValueError(f"uniform_share must be in [0, 1], not {uniform_share}")
+    if int(max_copies) != max_copies or not 1 <= int(max_copies) <= 255:
+        raise ValueError(f"max_copies must be an integer in 1 .. 255, not {max_copies}")
+    if expected_rows is not None and (int(expected_rows) != expected_rows or not 1 <= int(expected_rows) <= 1 << 40):
+        raise ValueError(f"expected_rows must be an integer in 1 .. 2^40, not {expected_rows}")
+    return None if expected_rows is None else int(expected_rows), share, int(max_copies)
+
+
+def surprise_reference(pi, net_policy, index=None):
+    """aqg_replay_surprise_rows in numpy (include/aqgnn.h, "policy surprise weighting", steps 1 and 2): (k float32 [m], q int32 [m]) of
+    the rows index[0..m) of pi float32 [rows,A] (index None: rows 0..m-1) against net_policy float32 [m,A], the network's softmaxed
+    policy of each of those rows.  KL = sum over t_a > 0 of t_a (ln t_a - ln max(p_a, 2^-126)) in float64, in the kernel's order: a
+    lane's own entries a = lane, lane + 64, ... in ascending order, then the xor-shuffle reduction 32, 16, ..., 1; k = f32(min(max(KL,
+    0), 88)), q = floor(k 2^20).  k = q = 0 for a row with a non-finite entry in t or p, a negative target entry, no positive target
+    entry, or an index entry outside pi."""
+    t_all, p = np.asarray(pi), np.asarray(net_policy)
+    if t_all.dtype != np.float32 or t_all.ndim != 2 or p.dtype != np.float32 or p.ndim != 2 or p.shape[1] != t_all.shape[1]:
+        raise ValueError("surprise_reference: pi must be float32 [rows,A] and net_policy float32 [m,A]")
+    m, A = p.shape
+    rows = np.arange(m, dtype=np.int64) if index is None else np.asarray(index, dtype=np.int64)
+    if rows.shape != (m,) or m > SURPRISE_MAX_ROWS or (index is None and m > t_all.shape[0]):
+        raise ValueError("surprise_reference: one network policy row per row of index (or of pi), 2^24 at most")
+    inside = (rows >= 0) & (rows < t_all.shape[0])
+    t = np.zeros((m, A), dtype=np.float32)
+    t[inside] = t_all[rows[inside]]
+    with np.errstate(all="ignore"):
+        bad = ~np.isfinite(t).all(axis=1) | ~np.isfinite(p).all(axis=1) | (t < 0).any(axis=1)
+        positive = t > 0
+        ok = inside & ~bad & positive.any(axis=1)
+        pc = np.where(p > SURPRISE_TINY, p, SURPRISE_TINY)
+        ts = np.where(positive, t, np.float32(1.0)).astype(np.float64)
+        d = np.log(ts) - np.log(pc.astype(np.float64))
+        term = np.where(positive, ts * d, 0.0)
+        passes = -(-A // 64)
+        lanes = np.zeros((m, passes * 64), dtype=np.float64)
+        lanes[:, :A] = term
+        lanes = lanes.reshape(m, passes, 64)
+        acc = np.zeros((m, 64), dtype=np.float64)
+        for s in range(passes):                                 # +0.0 + term is the term: an entry that adds nothing changes nothing
+            acc = acc + lanes[:, s]
+        lane = np.arange(64)
+        for off in (32, 16, 8, 4, 2, 1):
+            acc = acc + acc[:, lane ^ off]
+        kl = np.where(ok, acc[:, 0], 0.0)
+        k = np.minimum(np.maximum(kl, 0.0), SURPRISE_K_MAX).astype(np.float32)
+    k[~ok] = 0                                                  # (a NaN sum of a rejected row)
+    return k, surprise_weights(k)
+
+
+def surprise_weights(k):
+    """Step 2 in numpy: q = floor(float64(k) * 2^20) as int32, for k float32 in [0, 88] -- an exact product, q < 2^27."""
+    k = np.asarray(k)
+    if k.dtype != np.float32:
+        raise ValueError("surprise_weights: k must be float32")
+    return np.floor(k.astype(np.float64) * SURPRISE_Q_SCALE).astype(np.int32)
+
+
+def expand_rows(base, count, total=None):
+    """Step 5 on torch tensors of one device: base int64 [m] (the rows in input order) with row j repeated count[j] times.  total: the
+    sum of count when the caller has it (it then costs no read of the device)."""
+    return torch.repeat_interleave(base, count.to(torch.int64), output_size=None if total is None else int(total))
+
+
+def surprise_counts_reference(q, rows_of_q, seed, update, expected_rows, uniform_share, max_copies):
+    """aqg_replay_surprise_counts in numpy (steps 3 and 4), int32 [m]: q int32 [m], rows_of_q the place of each of its rows in the
+    arrays (int64 [m]; for a window the ring slots; None: 0..m-1), which keys the row's draw.  f = (E U) / m + ((E (1 - U)) q) / S
+    in float64 in that order (S = sum q; S == 0: f = E / m), count = min(floor(f) + [u < f - floor(f)], C) with u =
+    counter_uniform(stream_key(seed, update), row)."""
+    from .counter_rng import counter_uniform, stream_key
+    q = np.asarray(q)
+    if q.dtype != np.int32 or q.ndim != 1 or q.shape[0] > SURPRISE_MAX_ROWS:
+        raise ValueError("surprise_counts_reference: q must be int32 [m], m <= 2^24")
+    m = q.shape[0]
+    rows = np.arange(m, dtype=np.int64) if rows_of_q is None else np.asarray(rows_of_q, dtype=np.int64)
+    if rows.shape != (m,):
+        raise ValueError("surprise_counts_reference: one row per entry of q")
+    E, U, C = check_surprise_options(expected_rows, uniform_share, max_copies)
+    if E is None:
+        raise ValueError("surprise_counts_reference: expected_rows must be given")
+    if m == 0:
+        return np.zeros((0,), dtype=np.int32)
+    E, U, md = np.float64(E), np.float64(U), np.float64(m)
+    S = int(q.astype(np.int64).sum())
+    if S > 0:
+        uniform = (E * U) / md
+        rest = E * (np.float64(1.0) - U)
+        f = uniform + (rest * q.astype(np.float64)) / np.float64(S)
+    else:
+        f = np.full((m,), E / md, dtype=np.float64)
+    whole = np.floor(f)
+    u = counter_uniform(stream_key(int(seed), int(update)), rows.astype(np.uint64))
+    c = whole + (np.asarray(u, dtype=np.float64).reshape(m) < f - whole)
+    return np.minimum(c, np.float64(C)).astype(np.int32)
+
+
+def surprise_index(model, states72, pi, index=None, *, seed, update, expected_rows=None, uniform_share=0.5, max_copies=8,
+                   chunk_rows=16384, stats=None):
+    """The rows an update trains on, drawn by policy surprise, on the GPU: (index int64 [M], k float32 [m], count int32 [m]) for the rows
+    index[0..m) (int64, on the tensors' device; None: all rows) of the device tensors states72 uint8 [rows,72] and pi float32 [rows,A].
+    The returned index names those rows in input order, row j count[j] times -- a valid `index` for every trainer's epoch.
+
+    model.forward_states runs over the records in chunks of at most chunk_rows rows (the policy buffer stays at most chunk_rows * 4A
+    bytes), in eval mode, without autograd, with its fp16-range guard, and the module's mode is left as it was; one
+    aqg_replay_surprise_rows launch per chunk, the exact integer sum of q on the device, one aqg_replay_surprise_counts launch, and
+    torch.cumsum / torch.repeat_interleave for the expansion.  expected_rows None: m.  One device-to-host read of its own (besides the
+    forward's guard): M with the statistics, which a dict given as `stats` receives -- rows, expanded, left_out, most_copies, mean_kl.
+    surprise_reference and surprise_counts_reference are the two launches in numpy."""
+    E, U, C = check_surprise_options(expected_rows, uniform_share, max_copies)
+    if int(chunk_rows) < 1:
+        raise ValueError("surprise_index: chunk_rows must be >= 1")
+    board_size, A = int(model.board_size), int(model.policy_output_size)
+    if board_size not in (3, 5, 7, 9) or A != policy_size(board_size):
+        raise ValueError("surprise_index: unsupported board_size (odd 3..9)")
+    rows = int(states72.shape[0]) if states72.dim() == 2 else -1
+    for x, name, dtype, shape in ((states72, "states72", torch.uint8, (rows, 72)), (pi, "pi", torch.float32, (rows, A))):
+        if x.dtype != dtype or tuple(x.shape) != shape or not x.is_cuda or x.device != states72.device:
+            raise ValueError(f"surprise_index: {name} must be a {dtype} {list(shape)} tensor on the GPU ({board_size}x{board_size} board)")
+    dev = states72.device
+    states72, pi = states72.contiguous(), pi.contiguous()
+    if index is not None:
+        if index.dtype != torch.int64 or index.dim() != 1 or index.device != dev:
+            raise ValueError("surprise_index: index must be an int64 [m] tensor on the rows' device")
+        index = index.contiguous()
+    m = rows if index is None else int(index.numel())
+    if m > SURPRISE_MAX_ROWS:
+        raise ValueError(f"surprise_index: {m} rows; 2^24 at most")
+    if m == 0:
+        if stats is not None:
+            stats.update(rows=0, expanded=0, left_out=0, most_copies=0, mean_kl=0.0)
+        return (torch.zeros((0,), dtype=torch.int64, device=dev), torch.zeros((0,), dtype=torch.float32, device=dev),
+                torch.zeros((0,), dtype=torch.int32, device=dev))
+    E = m if E is None else E
+    lib, st = _lib.load(), _lib.stream_ptr(dev)
+    chunk = int(chunk_rows)
+    was_training = bool(getattr(model, "training", False))
+    with torch.cuda.device(dev):
+        k = torch.empty((m,), dtype=torch.float32, device=dev)
+        q = torch.empty((m,), dtype=torch.int32, device=dev)
+        count = torch.empty((m,), dtype=torch.int32, device=dev)
+        model.eval()
+        try:
+            with torch.no_grad():
+                for off in range(0, m, chunk):
+                    n = min(chunk, m - off)
+                    records = states72[off:off + n] if index is None else states72.index_select(0, index[off:off + n])
+                    net_policy = model.forward_states(records.contiguous())[0].contiguous()
+                    _lib.check(lib.aqg_replay_surprise_rows(board_size, A, _lib.ptr(net_policy), _lib.ptr(pi), _lib.ptr(index), rows, m, off, n,
+                                                            _lib.ptr(k), _lib.ptr(q), st), "aqg_replay_surprise_rows")
+        finally:
+            model.train(was_training)
+        total = q.sum(dtype=torch.int64).reshape(1)                    # exact, and it stays on the device
+        _lib.check(lib.aqg_replay_surprise_counts(_lib.ptr(q), _lib.ptr(index), _lib.ptr(total), m, E, U, C, int(seed) & ((1 << 64) - 1),
+                                                  int(update) & ((1 << 64) - 1), _lib.ptr(count), st), "aqg_replay_surprise_counts")
+        ends = torch.cumsum(count, 0, dtype=torch.int64)
+        M, left_out, most, kl_sum = torch.stack((ends[-1].double(), (count == 0).sum().double(), count.max().double(),
+                                                 k.sum(dtype=torch.float64))).tolist()          # the one read
+        base = torch.arange(m, dtype=torch.int64, device=dev) if index is None else index
+        expanded = expand_rows(base, count, M)
+    if stats is not None:
+        stats.update(rows=m, expanded=int(M), left_out=int(left_out), most_copies=int(most), mean_kl=kl_sum / m)
+    return expanded, k, count
+
+
 class ReplayWindow:
     """A ring of training rows holding the newest generations, with per-generation bookkeeping on the host.
 
@@ -416,6 +599,7 @@ class ReplayWindow:
         self._valid = 0
         self._index = torch.zeros((0,), dtype=torch.int64, device=self.device)
         self.reanalyse_updates = 0      # reanalyse passes self_play() has run on this window: the `update` of draw_reanalyse_rows
+        self.surprise_updates = 0       # surprise-weighted updates drawn on this window: the `update` of surprise_index's key
         if self.capacity is not None:
             self._allocate()
 
@@ -462,6 +646,25 @@ class ReplayWindow:
         if self.device.type == "cpu":
             return tuple(torch.from_numpy(x) for x in merge_reference(*(x.numpy() for x in self._rings), index=self._index.numpy()))
         return merge_positions(*self._rings, index=self._index, board_size=self.board_size)
+
+    def surprise_index(self, model, *, seed, update=None, expected_rows=None, uniform_share=0.5, max_copies=8, chunk_rows=16384,
+                       stats=None):
+        """surprise_index on the ring: (index int64 [M], k float32 [m], count int32 [m]) over the m valid rows in age order, the index
+        naming ring slots -- a row's draw is keyed by its slot, so it keeps it for as long as it stays in the ring.  update None: the
+        window's own counter surprise_updates, which the call then advances.  A window on the GPU only; the ring, the bookkeeping and
+        rows() are unchanged."""
+        if self.device.type == "cpu":
+            raise ValueError("ReplayWindow.surprise_index: the network's forward runs on the GPU; this window is in host memory")
+        if update is None:
+            update = self.surprise_updates
+            self.surprise_updates += 1
+        if self._rings is None or self._valid == 0:
+            s72 = torch.zeros((0, 72), dtype=torch.uint8, device=self.device)
+            pi = torch.zeros((0, self.policy_size), dtype=torch.float32, device=self.device)
+            return surprise_index(model, s72, pi, seed=seed, update=update, expected_rows=expected_rows, uniform_share=uniform_share,
+                                  max_copies=max_copies, chunk_rows=chunk_rows, stats=stats)
+        return surprise_index(model, self._rings[0], self._rings[1], self._index, seed=seed, update=update, expected_rows=expected_rows,
+                              uniform_share=uniform_share, max_copies=max_copies, chunk_rows=chunk_rows, stats=stats)
 
     def clear(self):
         """Empty the window; the ring keeps its size."""

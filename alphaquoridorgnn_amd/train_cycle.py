@@ -213,6 +213,19 @@ def _parser():
     ap.add_argument("--merge-positions", action="store_true",
                     help="parameter update: merge the rows that hold the same position into one row with the mean policy and value "
                          "target, once per update (default TRAIN_MERGE_POSITIONS = False: one row per occurrence)")
+    ap.add_argument("--surprise-weighting", action="store_true",
+                    help="parameter update: draw the rows of an update by policy surprise, KL(row's policy target || the network the "
+                         "update starts from), once per update and behind --merge-positions (default TRAIN_SURPRISE_WEIGHTING = False: "
+                         "every row once)")
+    ap.add_argument("--surprise-uniform-share", type=float, default=None, metavar="U",
+                    help="parameter update, with --surprise-weighting: the share U in [0, 1] of an update's rows dealt out evenly, the "
+                         "rest in proportion to the surprise (default TRAIN_SURPRISE_UNIFORM_SHARE = 0.5)")
+    ap.add_argument("--surprise-max-copies", type=int, default=None, metavar="C",
+                    help="parameter update, with --surprise-weighting: the most copies of one row, 1..255 (default "
+                         "TRAIN_SURPRISE_MAX_COPIES = 8)")
+    ap.add_argument("--surprise-seed", type=int, default=None, metavar="S",
+                    help="parameter update, with --surprise-weighting: seed of the draws that round a row's expected copies (default "
+                         "TRAIN_SURPRISE_SEED = 0)")
     ap.add_argument("--no-history-file", action="store_true",
                     help="self-play: write no .history file (needs --replay-generations; default SP_WRITE_HISTORY = True)")
     ap.add_argument("--reanalyse-rows", type=int, default=None, metavar="R",
@@ -316,6 +329,35 @@ def _set_reanalyse_options(args):
     target = _check_reanalyse_policy_args(args)
     if target is not None:
         sp.SP_REANALYSE_POLICY_TARGET, sp.SP_REANALYSE_C_VISIT, sp.SP_REANALYSE_C_SCALE = target
+
+
+def _check_surprise_args(args):
+    """--surprise-weighting / --surprise-uniform-share / --surprise-max-copies / --surprise-seed, refused at parse time: a coefficient
+    without the main flag, and values the stage would refuse.  Returns (uniform_share, max_copies, seed) with the defaults filled in,
+    or None when the option is off."""
+    from . import train_network as tn
+    from .replay import check_surprise_options
+    given = (args.surprise_uniform_share, args.surprise_max_copies, args.surprise_seed)
+    if not args.surprise_weighting:
+        if any(x is not None for x in given):
+            raise ValueError("--surprise-uniform-share, --surprise-max-copies and --surprise-seed need --surprise-weighting")
+        return None
+    share, copies, seed = (d if x is None else x for x, d in
+                           zip(given, (tn.TRAIN_SURPRISE_UNIFORM_SHARE, tn.TRAIN_SURPRISE_MAX_COPIES, tn.TRAIN_SURPRISE_SEED)))
+    try:
+        _, share, copies = check_surprise_options(None, share, copies)
+    except ValueError as err:
+        raise ValueError(f"--surprise-uniform-share / --surprise-max-copies: {err}") from None
+    return share, copies, int(seed)
+
+
+def _set_surprise_options(args):
+    """The checked surprise-weighting flags onto train_network's constants (the stage reads them at call time)."""
+    from . import train_network as tn
+    checked = _check_surprise_args(args)
+    if checked is not None:
+        tn.TRAIN_SURPRISE_WEIGHTING = True
+        tn.TRAIN_SURPRISE_UNIFORM_SHARE, tn.TRAIN_SURPRISE_MAX_COPIES, tn.TRAIN_SURPRISE_SEED = checked
 
 
 def _set_replay_options(args):
@@ -432,6 +474,7 @@ def main(argv=None):
     _check_reanalyse_args(args)                         # in front of anything that touches a device or the process group
     _check_reanalyse_policy_args(args)
     _check_policy_args(args)
+    _check_surprise_args(args)
     rank, world = aqd.init_from_env()
     if args.games is not None:
         sp.SP_GAME_COUNT = args.games
@@ -449,6 +492,7 @@ def main(argv=None):
     _set_mirror_options(args)
     _set_optimiser_options(args)
     _set_replay_options(args)
+    _set_surprise_options(args)
     _set_reanalyse_options(args)
     _set_policy_options(args)
     if args.eval_games is not None:

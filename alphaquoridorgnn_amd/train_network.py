@@ -33,6 +33,15 @@ TRAIN_EPOCH_ROWS = None    # E: an epoch trains on the first min(E, n) rows of i
 # early game on small boards -- become ONE row with the mean policy and value target, once per update; the epochs, TRAIN_EPOCH_ROWS and
 # the mirror then run on the merged rows (a flip is keyed by merged row).  Every position weighs the same.
 TRAIN_MERGE_POSITIONS = False    # False = off: one row per occurrence
+# Policy surprise weighting (replay.surprise_index): the rows of an update drawn by KL(row's policy target || the network the update
+# starts from), once per update, after the merge when that is on: an expected number of copies per row -- the uniform share dealt out
+# evenly, the rest in proportion to the surprise -- rounded by a draw keyed by (seed, update, ring slot), at most MAX_COPIES of a row.
+# The epochs, TRAIN_EPOCH_ROWS, the mirror and the data-parallel deal then run on the expanded index.
+TRAIN_SURPRISE_WEIGHTING = False         # False = off: nothing is launched
+TRAIN_SURPRISE_UNIFORM_SHARE = 0.5       # U: the share of the rows dealt out evenly (1 = every row once: the option off)
+TRAIN_SURPRISE_MAX_COPIES = 8            # C: the most copies of one row, 1..255
+TRAIN_SURPRISE_SEED = 0
+_surprise_updates = 0                    # surprise-weighted updates drawn without a window: the `update` of the draw's key
 # Optimiser controls (the reference's optimiser is a bare Adam(lr=0.001)): weight decay on the weight matrices and conv kernels, and
 # global-norm gradient clipping, both inside the HIP step (include/aqgnn.h "optimiser controls").  All off = the reference's update.
 TRAIN_WEIGHT_DECAY = 0.0      # c of the AlphaZero loss term c * ||theta||^2, as torch's weight_decay
@@ -48,22 +57,50 @@ def load_data():
         return pickle.load(f)
 
 
-def _training_rows(dev, board_size):
+def _training_rows(dev, board_size, model=None):
     """(s, p, v, index) an update trains on, on `dev`: uint8 [rows,72] records, float32 [rows,A] policy and [rows] value targets, and
     the int64 rows of them that are valid, oldest first -- or None when all are (the file route).  A non-empty TRAIN_WINDOW gives its
     rings and index(); TRAIN_GENERATIONS = K > 1 without one a temporary window over the newest K files; otherwise the newest file
     (train_network.py:19-23,:31-39).  TRAIN_MERGE_POSITIONS: whichever of the three it is, merged once (replay.merge_positions) into
-    compact rows, one per distinct position, with index None; every rank merges the same rows to the same result."""
-    s, p, v, index = _recorded_rows(dev, board_size)
-    if not TRAIN_MERGE_POSITIONS:
-        return s, p, v, index
+    compact rows, one per distinct position, with index None; every rank merges the same rows to the same result.
+    TRAIN_SURPRISE_WEIGHTING (needs `model`, the network the update starts from): behind the merge, the index expanded by policy
+    surprise (replay.surprise_index) -- some rows named several times, some not at all; every rank draws the same index, with no
+    collective, and advances the update counter (the window's when one is trained on, else the module's) alike."""
     import torch.distributed as dist
-    from .replay import merge_positions
-    n = int(s.shape[0] if index is None else index.shape[0])
-    s, p, v, count = merge_positions(s, p, v, index=index, board_size=board_size)
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0:
-        print(f"merged positions: {n} rows, {int(s.shape[0])} positions, longest run {int(count.max()) if n else 0}")
-    return s, p, v, None
+    s, p, v, index = _recorded_rows(dev, board_size)
+    rank0 = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+    if TRAIN_MERGE_POSITIONS:
+        from .replay import merge_positions
+        n = int(s.shape[0] if index is None else index.shape[0])
+        s, p, v, count = merge_positions(s, p, v, index=index, board_size=board_size)
+        index = None
+        if rank0:
+            print(f"merged positions: {n} rows, {int(s.shape[0])} positions, longest run {int(count.max()) if n else 0}")
+    if TRAIN_SURPRISE_WEIGHTING:
+        index = _surprise_rows(model, s, p, index, rank0)
+    return s, p, v, index
+
+
+def _surprise_rows(model, s, p, index, rank0):
+    """The surprise-weighted index of the rows (s, p, index), drawn under the next update number of the window or of the module."""
+    global _surprise_updates
+    from .replay import surprise_index
+    if model is None:
+        raise ValueError("TRAIN_SURPRISE_WEIGHTING: _training_rows needs the network the update starts from (model=)")
+    window = TRAIN_WINDOW if TRAIN_WINDOW is not None and len(TRAIN_WINDOW) > 0 else None
+    if window is not None:
+        update = window.surprise_updates
+        window.surprise_updates += 1
+    else:
+        update = _surprise_updates
+        _surprise_updates += 1
+    stats = {}
+    index, _, _ = surprise_index(model, s, p, index, seed=TRAIN_SURPRISE_SEED, update=update, uniform_share=TRAIN_SURPRISE_UNIFORM_SHARE,
+                                 max_copies=TRAIN_SURPRISE_MAX_COPIES, stats=stats)
+    if rank0:
+        print(f"surprise weighting: {stats['rows']} rows -> {stats['expanded']} rows, {stats['left_out']} left out, most copies "
+              f"{stats['most_copies']}, mean KL {stats['mean_kl']:.4f}")
+    return index
 
 
 def _recorded_rows(dev, board_size):
@@ -630,7 +667,7 @@ def _train_loop(load, make_trainer, rank, world):
     from . import distributed as aqd
     dev = aqd.device()                                                             # this rank's GPU, explicitly
     model = load(PV_NETWORK_PATH + 'best.pth', dev)                                # GNNNetwork, or the shape best.pth holds
-    s, p, v, index = _training_rows(dev, model.board_size)
+    s, p, v, index = _training_rows(dev, model.board_size, model=model)
     n = s.shape[0] if index is None else index.shape[0]
     trainer = make_trainer(model, max_batch=BATCH_SIZE)
     for epoch in range(NUM_EPOCH):

@@ -1071,6 +1071,45 @@ int aqg_replay_merge_runs(int board_size, int policy_size, const uint8_t* states
                           const int64_t* starts, int n, int u, uint8_t* out72, float* out_pi, float* out_z, int32_t* count,
                           float* workspace, size_t workspace_floats, void* stream);
 
+/* ------------------------------------------------------------------ policy surprise weighting (additive to ABI 15; the reference has none)
+ *
+ * Which rows an update trains on, drawn by how far the network is from each row's policy target (csrc/replay_surprise.hip;
+ * replay.surprise_index drives the two entry points, replay.surprise_reference and replay.surprise_counts_reference state them in
+ * numpy).  For the m rows an update trains on (index[0..m), or rows 0..m-1 of the arrays), t a row's f32 policy target [A] and p the
+ * f32 softmaxed policy the network the update STARTS from gives for the row's record:
+ *
+ * 1. Surprise, in float64, no operation contracted:  KL = sum over {a : t_a > 0} of t_a * (ln t_a - ln max(p_a, 2^-126)).
+ *    Summation order: lane l of 64 adds its own entries a = l, l + 64, ... in ascending order to +0.0 (an entry with t_a <= 0 adds
+ *    nothing), then the xor-shuffle wave reduction 32, 16, ..., 1 (v_l += v_{l xor off}).  k = f32(min(max(KL, 0), 88)); the upper
+ *    clamp never acts on a row whose target sums to 1 (KL <= 126 ln 2 = 87.34) and keeps q below 2^27 whatever a row holds.
+ *    k = 0 for a row with a non-finite entry in t or p, a negative target entry (-0.0 is not one), no positive target entry, or an
+ *    index entry outside the arrays (such a row is not read).  t == p bitwise gives k = 0 exactly.
+ * 2. Integer weight: q = floor(k * 2^20) -- an exact f64 product, q < 2^27.  S = sum q is an exact integer whatever the order; m <=
+ *    2^24 (more is refused), so S < 2^51.
+ * 3. Expected copies for an update that wants E rows with uniform share U, in float64 in this order:
+ *    f = (E * U) / m + ((E * (1 - U)) * q) / S  when S > 0,  f = E / m  when S <= 0.  U = 1, E = c m gives f = c exactly.
+ * 4. Copies: count = min(floor(f) + [u < f - floor(f)], C), u = counter_uniform(stream_key(seed, update), r) of the generator above,
+ *    r the row's place in the arrays (index[j], or j) -- for a replay window the ring slot -- so a row's draw does not depend on m, on
+ *    the chunking or on the rank.  C = the most copies of one row, 1..255.
+ * 5. The update's index: the rows in input order, row j count_j times (torch.repeat_interleave; no kernel).
+ *
+ * aqg_replay_surprise_rows: steps 1 and 2 for one chunk of n rows whose network policy the caller has just computed -- net_policy f32
+ *   [n,A], row i of the chunk being training row offset + i: its target is row index[offset + i] of ring_pi f32 [rows,A] (index ==
+ *   NULL: row offset + i), its results go to k[offset + i] (f32) and q[offset + i] (i32); index, k and q have m entries.  16 rows per
+ *   workgroup, 4 per wavefront, all their loads in flight before the first use; no LDS, no atomics, no scratch.
+ *   Refused: an unsupported board size, a policy_size that is not the board's A, m < 0 or m > 2^24, rows < 0, m > rows without an
+ *   index, a chunk outside the m rows (offset < 0, n < 0, offset + n > m), a NULL array (with n > 0), an output overlapping a source
+ *   (of a gathered ring one row is assumed, as aqg_augment_gather does) or the other output.
+ * aqg_replay_surprise_counts: steps 3 and 4, one lane per row: q i32 [m], index i64 [m] or NULL, total = a DEVICE int64 holding S
+ *   (the caller's exact integer sum of q; it is read by the kernel, never by the host), count i32 [m].
+ *   Refused: m < 0 or m > 2^24, uniform_share outside [0, 1] or NaN, max_copies outside 1..255, expected_rows < 1 (or > 2^40), q,
+ *   total or count NULL (with m > 0), count overlapping a source.
+ * Both refuse on the host, before any launch (-1, aqg_last_error), and return 0 for an empty launch without looking at a pointer. */
+int aqg_replay_surprise_rows(int board_size, int policy_size, const float* net_policy, const float* ring_pi, const int64_t* index,
+                             int rows, int m, int offset, int n, float* k, int32_t* q, void* stream);
+int aqg_replay_surprise_counts(const int32_t* q, const int64_t* index, const int64_t* total, int m, long long expected_rows,
+                               double uniform_share, int max_copies, uint64_t seed, uint64_t update, int32_t* count, void* stream);
+
 /* ------------------------------------------------------------------ CPU baseline agents (agents.py) -- HOST pointers, host code */
 
 /* The reference's baseline opponents (agents.py:14-214) are CPU code; so are these: the host instantiation of the rule header
