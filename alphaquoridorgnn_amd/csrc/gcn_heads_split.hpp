@@ -8,13 +8,7 @@
 
 namespace aqg {
 
-__device__ __forceinline__ float row16_sum(float x) {     // sum over the 16 lanes of a DPP row, result in every lane
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xf, 0xf, false));   // row_ror:8
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x124, 0xf, 0xf, false));   // row_ror:4
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x122, 0xf, 0xf, false));   // row_ror:2
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x121, 0xf, 0xf, false));   // row_ror:1
-    return x;
-}
+// (row16_sum, the sum over the 16 lanes of a DPP row, is in split_mfma.hpp: the training heads use it too.)
 
 // Weight fragments are fetched with buffer loads: one SGPR resource for the packed buffer, one shared VGPR (lane * 16)
 // and a scalar offset per load -- no 64-bit address VGPRs (they were the first thing the allocator spilled, and a
@@ -314,6 +308,8 @@ __device__ __forceinline__ void heads_body(HeadsSmem& sm, __amdgpu_buffer_rsrc_t
 // heads_half (the step kernel's two kinds of workgroup, option "policy_beside_step"): heads_body<STEP> cut into its two halves, each exactly
 // what the whole body computes for its outputs -- the same fragments, the same MFMA sequence per output, the same order of every sum.
 // A function of its own, so that the whole body above and the kernels built from it stay instruction for instruction what they were.
+// (Serving the whole body from these pieces too was built and measured, profiles/heads_one_body.log: the stand-alone kernel keeps its
+//  speed, the three older fused step forms lose half a per cent in every order of the pieces tried -- so the two functions stay.)
 // The phases are written once, as pieces, and put in order at the end: the hidden tile's pieces run as ONE region of the waves that
 // have a tile (separate regions made the allocator carry 64 registers of operands through their joins, and spill).
 //   HEADS_VALUE   waves 4..7 run their hidden tiles; behind the one barrier EVERY wave forms the fixed-order sum wave 4 forms in the

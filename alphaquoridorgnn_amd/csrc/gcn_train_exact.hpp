@@ -154,8 +154,8 @@ __device__ __forceinline__ void train_board_f32_body(unsigned char* __restrict__
     float* const Hb = Zs + 96 * SA;
     float* const cs = Hb + 84 * SB;
     BoardGraph& gr = *reinterpret_cast<BoardGraph*>(cs + 4 * TH);
-    HeadsSmem& hsm = *reinterpret_cast<HeadsSmem*>(Zs);
-    static_assert(sizeof(HeadsSmem) <= sizeof(float) * 96 * SA && 16 * TH <= 84 * SB, "scratch aliases");
+    TrainHeadsSmem& hsm = *reinterpret_cast<TrainHeadsSmem*>(Zs);
+    static_assert(sizeof(TrainHeadsSmem) <= sizeof(float) * 96 * SA && 16 * TH <= 84 * SB, "scratch aliases");
     const int b = blockIdx.x, t = threadIdx.x;
     const int lane = t & 63, wave = t >> 6, q = lane >> 4, r16 = lane & 15;
     const int col = 16 * wave + r16;

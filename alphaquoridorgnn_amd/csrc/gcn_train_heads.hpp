@@ -32,19 +32,12 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
-struct HeadsSmem {
+struct TrainHeadsSmem {
     float gs[TH], hs[TH], dhs[TH], dl[256], red[2][8][2];
     float dgv[TH];                       // d loss / d pooled features: the result the backward pass starts from
     alignas(16) float part[32][TH];      // per (wave, row group): partial sums over that group's weight rows
 };
 __device__ __forceinline__ float dot4(const f32x4 a, const f32x4 b) { return fmaf(a[3], b[3], fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0]))); }
-__device__ __forceinline__ float row16_total(float x) {          // sum over the 16 lanes of a DPP row, in every lane of the row
-    x += dpp_f<0x128, 0xf>(0.f, x);    // row_ror:8
-    x += dpp_f<0x124, 0xf>(0.f, x);    // row_ror:4
-    x += dpp_f<0x122, 0xf>(0.f, x);    // row_ror:2
-    x += dpp_f<0x121, 0xf>(0.f, x);    // row_ror:1
-    return x;
-}
 // One position's heads, losses and head gradients by a workgroup of NW = 8 wavefronts (all of them load and multiply; the softmax /
 // loss reductions run on wave 0).  The caller has put the pooled features into sm.gs (published by the first barrier in here); on
 // return sm.dgv = dg.
@@ -57,7 +50,7 @@ __device__ __forceinline__ float row16_total(float x) {          // sum over the
 //                                                     quarter waves are added up through LDS in a fixed order.
 // (Before: one row per wave instruction with a 64-lane reduction per row, policy_head.2 and both first layers read twice, the
 //  second time with 4-byte strided loads -- 180 vector-memory instructions and ~100 weight registers per lane; now 15 and 60.)
-__device__ __forceinline__ void heads_board(HeadsSmem& sm, int b, const HeadParams& Pm,
+__device__ __forceinline__ void heads_board(TrainHeadsSmem& sm, int b, const HeadParams& Pm,
                                             const float* __restrict__ pi_all, const float* __restrict__ z_all,
                                             const int64_t* __restrict__ order, int first, int A, int B,
                                             float* __restrict__ hp, float* __restrict__ hv, float* __restrict__ lg,
@@ -105,7 +98,7 @@ __device__ __forceinline__ void heads_board(HeadsSmem& sm, int b, const HeadPara
 #pragma unroll
         for (int i = 0; i < HG; ++i) {
             const int o = 4 * (wave + NW * i) + rg;
-            const float s = fmaxf(row16_total(dot4(w1a[i], g0) + dot4(w1b[i], g1)) + hb[i], 0.f);
+            const float s = fmaxf(row16_sum(dot4(w1a[i], g0) + dot4(w1b[i], g1)) + hb[i], 0.f);
             if (l == 0) {
                 hs[o] = s;
                 (o < HH ? hp : hv)[(size_t)b * HH + (o & 63)] = s;
@@ -119,7 +112,7 @@ __device__ __forceinline__ void heads_board(HeadsSmem& sm, int b, const HeadPara
 #pragma unroll
         for (int i = 0; i < LG; ++i) {
             const int a = 4 * (wave + NW * i) + rg;
-            const float s = row16_total(dot4(w2[i], h4));
+            const float s = row16_sum(dot4(w2[i], h4));
             if (l == 0 && a < A) dl[a] = s;                          // (dl is reused for d loss / d logits below)
         }
     }

@@ -46,7 +46,7 @@ struct alignas(16) SplitSmem {
     alignas(16) float dinv[96];                             // deg^-1/2 (self loop included), 0 for the padding nodes
     unsigned char ob[96];                                   // open sides of a tile: bit 0 up (n - 9), 1 down, 2 left, 3 right
 };
-static_assert(sizeof(HeadsSmem) <= sizeof(unsigned int) * 8 * 3 * 2 * 64 * 4, "heads scratch aliases FR");
+static_assert(sizeof(TrainHeadsSmem) <= sizeof(unsigned int) * 8 * 3 * 2 * 64 * 4, "heads scratch aliases FR");
 constexpr int SPLIT_KERNEL_SMEM = (int)sizeof(SplitSmem) > F32_BODY_SMEM ? (int)sizeof(SplitSmem) : F32_BODY_SMEM;
 static_assert(SPLIT_KERNEL_SMEM <= 160 * 1024, "one workgroup per CU");
 __device__ unsigned int g_train_fallbacks = 0;
@@ -163,13 +163,13 @@ __device__ __forceinline__ void aggregate_tr(const unsigned int (&AF)[2][AF_BLOC
 //  heads alone then take 124 k cycles instead of 25 k; as a callee they get a register allocation of their own)
 //  (the scratch travels as its LDS byte offset and is cast back from the LDS address space inside, so that the callee's accesses are
 //  ds_ instructions, not flat ones)
-typedef __attribute__((address_space(3))) HeadsSmem HeadsSmemLds;
+typedef __attribute__((address_space(3))) TrainHeadsSmem TrainHeadsSmemLds;
 typedef const __attribute__((address_space(1))) float* gcf;           // pointer arguments in the global address space: global_, not flat_
 typedef __attribute__((address_space(1))) float* gf;
 __device__ __attribute__((noinline)) void heads_board_call(unsigned int sm_lds, int b, gcf w0, gcf w1, gcf w2, gcf w3, gcf w4, gcf w5, gcf w6, gcf w7,
                                                            gcf pi_all, gcf z_all, const __attribute__((address_space(1))) int64_t* order, int first,
                                                            int A, int B, gf hp, gf hv, gf lg, gf pol, gf vp, gf val, gf loss, gf dhp, gf dhv) {
-    HeadsSmem& sm = *(HeadsSmem*)reinterpret_cast<HeadsSmemLds*>((size_t)sm_lds);
+    TrainHeadsSmem& sm = *(TrainHeadsSmem*)reinterpret_cast<TrainHeadsSmemLds*>((size_t)sm_lds);
     HeadParams Pg;
     Pg.p[0] = (const float*)w0; Pg.p[1] = (const float*)w1; Pg.p[2] = (const float*)w2; Pg.p[3] = (const float*)w3;
     Pg.p[4] = (const float*)w4; Pg.p[5] = (const float*)w5; Pg.p[6] = (const float*)w6; Pg.p[7] = (const float*)w7;
@@ -191,7 +191,7 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
                                                        float* __restrict__ part_dW1, float* __restrict__ part_db) {
     constexpr int N = 9, V = 81;
     SplitSmem& sm = *reinterpret_cast<SplitSmem*>(smem);
-    HeadsSmem& hsm = *reinterpret_cast<HeadsSmem*>(&sm.FR[0][0][0][0][0]);
+    TrainHeadsSmem& hsm = *reinterpret_cast<TrainHeadsSmem*>(&sm.FR[0][0][0][0][0]);
     const int b = blockIdx.x, t = threadIdx.x;
     const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), q = lane >> 4, c = lane & 15;
     const int col = 16 * wave + c;
@@ -406,7 +406,7 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
     };
     TS(3, 5)
     // ---- heads, losses, head gradients (its first barrier publishes gs)
-    heads_board_call((unsigned int)(size_t)(HeadsSmemLds*)&hsm, b, (gcf)hpm.p[0], (gcf)hpm.p[1], (gcf)hpm.p[2], (gcf)hpm.p[3], (gcf)hpm.p[4], (gcf)hpm.p[5],
+    heads_board_call((unsigned int)(size_t)(TrainHeadsSmemLds*)&hsm, b, (gcf)hpm.p[0], (gcf)hpm.p[1], (gcf)hpm.p[2], (gcf)hpm.p[3], (gcf)hpm.p[4], (gcf)hpm.p[5],
                      (gcf)hpm.p[6], (gcf)hpm.p[7], (gcf)pi_all, (gcf)z_all, (const __attribute__((address_space(1))) int64_t*)order, first, A, B,
                      (gf)hp, (gf)hv, (gf)lg, (gf)pol, (gf)vp, (gf)val, (gf)loss, (gf)dhp, (gf)dhv);
     TS(3, 6)

@@ -55,7 +55,7 @@ struct alignas(16) TrunkSmemM {
 };
 static_assert(2 * sizeof(TrunkSmemM) <= 160 * 1024, "two 8-wave workgroups per CU");
 
-// (row16_sum, the sum over the 16 lanes of a DPP row, is in gcn_heads_split.hpp.)
+// (row16_sum, the sum over the 16 lanes of a DPP row, is in split_mfma.hpp.)
 // The same for four values at once, as sixteen v_add_f32 with a DPP operand: the four chains are interleaved, so each add's DPP
 // source was written four instructions earlier (a DPP read needs two wait states behind the VALU write of its source; hipcc
 // pads nothing inside an asm statement).  hipcc turns the builtin form into v_mov_b32_dpp + packed adds: 24 instructions.

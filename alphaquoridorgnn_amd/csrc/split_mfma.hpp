@@ -50,6 +50,16 @@ __device__ __forceinline__ f32x4 mfma_f16(const u32x4 a, const u32x4 b, const f3
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
+// Sum over the 16 lanes of a DPP row, result in every lane of the row (the inference heads' softmax and the training heads' row
+// products).
+__device__ __forceinline__ float row16_sum(float x) {
+    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xf, 0xf, false));   // row_ror:8
+    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x124, 0xf, 0xf, false));   // row_ror:4
+    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x122, 0xf, 0xf, false));   // row_ror:2
+    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x121, 0xf, 0xf, false));   // row_ror:1
+    return x;
+}
+
 // Low part of the fp16 split of two f32 values whose high parts are the halves of h01: f16(x0 - h01.lo) | f16(x1 - h01.hi) << 16.
 // v_fma_mix{lo,hi}_f16 reads the fp16 half directly and rounds the f32 difference (exact: h is x rounded to 11 bits) to
 // fp16 in ONE instruction per value, where convert-back / subtract / convert-pair took 2.5.  hipcc does not select the
