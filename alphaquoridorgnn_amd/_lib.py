@@ -84,6 +84,15 @@ class PolicyRecordStruct(_c.Structure):
     _fields_ = [("c_visit", _c.c_double), ("c_scale", _c.c_double), ("hist_policy", _vp)]
 
 
+class StartTableStruct(_c.Structure):
+    """Mirror of `struct aqg_start_table` (include/aqgnn.h, "start positions"): the option beside the engine struct."""
+    _fields_ = [("states72", _vp), ("index", _vp), ("count", _i32)]
+
+
+# the checker's flag bits (AQG_CHECK_*)
+CHECK_BOARD, CHECK_WALLS, CHECK_WALL_COUNT, CHECK_SAME_SQUARE, CHECK_OVER, CHECK_ODD_PLY, CHECK_NO_PATH = 1, 2, 4, 8, 16, 32, 64
+
+
 class TrainStruct(_c.Structure):
     """Mirror of `struct aqg_train` (include/aqgnn.h)."""
     _fields_ = (
@@ -196,6 +205,14 @@ SIGNATURES = {
     "aqg_engine_root_improved_policy": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.c_double, _c.c_double, _vp, _vp, _vp, _vp, _vp]),
     "aqg_engine_root_states72": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
     "aqg_engine_apply_actions": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _vp]),
+    "aqg_states72_check": (_c.c_int, [_c.c_int, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp]),
+    "aqg_host_check_state": (_c.c_int, [_c.c_int, _vp, _c.c_int, _c.c_int]),
+    "aqg_engine_reset_start": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.POINTER(StartTableStruct), _vp]),
+    "aqg_engine_move_start": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _c.POINTER(TreeReuseStruct),
+                                         _c.POINTER(ResignStruct), _c.POINTER(PolicyRecordStruct), _c.POINTER(StartTableStruct), _vp]),
+    "aqg_engine_finish_move_start": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _c.POINTER(TreeReuseStruct),
+                                                _c.POINTER(ResignStruct), _c.POINTER(PolicyRecordStruct), _c.POINTER(StartTableStruct), _vp]),
+    "aqg_engine_apply_actions_start": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _c.POINTER(StartTableStruct), _vp]),
     "aqg_agent_random": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp, _c.c_int, _c.c_uint64, _vp, _vp]),
     "aqg_playouts": (_c.c_int, [_c.c_int, _vp, _c.c_int, _c.c_int, _vp, _c.c_int, _c.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "aqg_agent_mcts_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),

@@ -370,6 +370,39 @@ int aqg_engine_apply_actions(const aqg_engine* e, const int32_t* actions, void* 
     return engine_apply_actions(*e, actions, (hipStream_t)stream);
 }
 
+// start positions (include/aqgnn.h, "start positions"): start NULL = the call without the table
+int aqg_states72_check(int board_size, const uint8_t* states72, int B, int num_walls, int plies_for_draw, uint8_t* flags, void* stream) {
+    if (B < 0 || (B > 0 && (!states72 || !flags))) return fail("aqg_states72_check: bad arguments");
+    if (num_walls < 0 || num_walls > 127) return fail("aqg_states72_check: num_walls must be 0..127");
+    if (plies_for_draw < 0 || plies_for_draw > 65535) return fail("aqg_states72_check: plies_for_draw must be 0..65535");
+    return launch_states72_check(board_size, states72, B, num_walls, plies_for_draw, flags, (hipStream_t)stream);
+}
+int aqg_host_check_state(int board_size, const uint8_t* rec72_host, int num_walls, int plies_for_draw) {
+    if (!rec72_host || num_walls < 0 || num_walls > 127 || plies_for_draw < 0 || plies_for_draw > 65535) return -1;
+    return host_check_state(board_size, rec72_host, num_walls, plies_for_draw);
+}
+int aqg_engine_reset_start(const aqg_engine* e, const aqg_start_table* start, void* stream) {
+    if (!e) return fail("aqg_engine_reset_start: null engine");
+    return engine_reset(*e, (hipStream_t)stream, start);
+}
+int aqg_engine_move_start(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                          const aqg_tree_reuse* reuse, const aqg_resign* resign, const aqg_policy_record* policy,
+                          const aqg_start_table* start, void* stream) {
+    if (!e || !uniforms) return fail("aqg_engine_move_start: null argument");
+    return engine_move(*e, uniforms, MoveOptions{temperature_plies, hist_value, reuse, resign, policy, start}, (hipStream_t)stream);
+}
+int aqg_engine_finish_move_start(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                                 const aqg_tree_reuse* reuse, const aqg_resign* resign, const aqg_policy_record* policy,
+                                 const aqg_start_table* start, void* stream) {
+    if (!e || !uniforms) return fail("aqg_engine_finish_move_start: null argument");
+    return engine_finish_move(*e, uniforms, MoveOptions{temperature_plies, hist_value, reuse, resign, policy, start}, (hipStream_t)stream);
+}
+int aqg_engine_apply_actions_start(const aqg_engine* e, const int32_t* actions, const aqg_start_table* start, void* stream) {
+    if (!e || !actions) return fail("aqg_engine_apply_actions_start: null argument");
+    if (int r = validate_start_table(*e, start, "aqg_engine_apply_actions_start")) return r;
+    return engine_apply_actions(*e, actions, (hipStream_t)stream, start);
+}
+
 static int check_draw_source(const char* what, const double* uniforms, int uniforms_stride) {
     if (uniforms && uniforms_stride < 0) return fail(what, "negative uniforms_stride");
     return 0;

@@ -12,6 +12,10 @@ int launch_legal_actions(int N, const void* states, int fmt, int B, uint8_t* mas
 int launch_state_next(int N, const uint8_t* in, const int32_t* actions, int B, uint8_t* out, hipStream_t st);
 int launch_state_status(int N, const uint8_t* in, int B, int draw, uint8_t* flags, hipStream_t st);
 
+// ---- state_check.hip
+int launch_states72_check(int N, const uint8_t* in, int B, int num_walls, int draw, uint8_t* flags, hipStream_t st);
+int host_check_state(int N, const uint8_t* rec72, int num_walls, int draw);
+
 // ---- gcn_forward.hip
 extern int g_trunk_variant, g_profile_trunk;
 void profile_mark(hipStream_t st, long long units);
@@ -100,8 +104,10 @@ struct MoveOptions {
     const aqg_tree_reuse* reuse;
     const aqg_resign* resign;
     const aqg_policy_record* policy = nullptr;
+    const aqg_start_table* start = nullptr;      // the refill behind the move starts its games from the table (aqgnn.h, "start positions")
 };
-int engine_reset(const aqg_engine& e, hipStream_t st);
+int engine_reset(const aqg_engine& e, hipStream_t st, const aqg_start_table* start = nullptr);
+int validate_start_table(const aqg_engine& e, const aqg_start_table* start, const char* what);
 int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st);
 int engine_begin_move(const aqg_engine& e, hipStream_t st);
 int engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t st);
@@ -110,7 +116,7 @@ int engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st
 int engine_move(const aqg_engine& e, const double* uniforms, const MoveOptions& opts, hipStream_t st);
 int engine_search(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
 int engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st);
-int engine_refill(const aqg_engine& e, hipStream_t st);
+int engine_refill(const aqg_engine& e, hipStream_t st, const aqg_start_table* start = nullptr);
 int engine_root_noise(const aqg_engine& e, hipStream_t st);
 int engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st);
 int engine_root_values(const aqg_engine& e, float* value, hipStream_t st);
@@ -135,19 +141,19 @@ bool engine_policy_beside_step(const aqg_engine& e, bool defer_legal);
 int launch_engine_eval(const aqg_engine& e, hipStream_t st, bool policy_jobs = false);
 
 // ---- mcts_move.hip
-void launch_engine_reset(const aqg_engine& e, hipStream_t st);
+void launch_engine_reset(const aqg_engine& e, hipStream_t st, const aqg_start_table* start = nullptr);
 void launch_engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st);
 void launch_engine_begin_move(const aqg_engine& e, hipStream_t st, const uint8_t* kept = nullptr);
 void launch_engine_kept_root_noise(const aqg_engine& e, const uint8_t* kept, hipStream_t st);
 int launch_engine_fake_eval(const aqg_engine& e, hipStream_t st);
 int launch_engine_root_noise(const aqg_engine& e, hipStream_t st);
 int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, const MoveOptions& opts, hipStream_t st);
-void launch_engine_refill(const aqg_engine& e, hipStream_t st);
+void launch_engine_refill(const aqg_engine& e, hipStream_t st, const aqg_start_table* start = nullptr);
 int launch_engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st);
 void launch_engine_root_priors(const aqg_engine& e, float* priors, int32_t* count, hipStream_t st);
 void launch_engine_root_values(const aqg_engine& e, float* value, hipStream_t st);
 int engine_root_states72(const aqg_engine& e, uint8_t* out72, hipStream_t st);
-int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_t st);
+int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_t st, const aqg_start_table* start = nullptr);
 
 // ---- mcts_improve.hip
 void launch_engine_root_improved_policy(const aqg_engine& e, double c_visit, double c_scale, float* policy, uint8_t* actions,

@@ -125,6 +125,17 @@ static int validate_policy_record(const aqg_engine& e, const aqg_policy_record& 
     return 0;
 }
 
+// what the start-position entry points refuse, before anything is launched (aqgnn.h, "start positions"): the rows and the index are
+// device memory and were checked by the caller (aqg_states72_check; index[k] in [0, count)) -- the kernels fall back to the opening record
+// on a row number outside the table
+int validate_start_table(const aqg_engine& e, const aqg_start_table* start, const char* what) {
+    (void)e;
+    if (!start) return 0;
+    if (!start->states72) return fail(what, "states72 is required");
+    if (start->count <= 0) return fail(what, "count must be >= 1");
+    return 0;
+}
+
 // Everything a move refuses, before anything is launched.  The order is part of the interface -- the first failing check names the
 // error: the engine, the two targets, tree reuse if it is on, resignation if it is on, the policy record if it is on.
 static int validate_move(const aqg_engine& e, const MoveOptions& o) {
@@ -134,6 +145,7 @@ static int validate_move(const aqg_engine& e, const MoveOptions& o) {
     if (o.reuse) if (int r = validate_reuse(e, *o.reuse)) return r;
     if (o.resign) if (int r = validate_resign(e, *o.resign)) return r;
     if (o.policy) if (int r = validate_policy_record(e, *o.policy)) return r;
+    if (o.start) if (int r = validate_start_table(e, o.start, "start positions")) return r;
     return 0;
 }
 
@@ -274,7 +286,7 @@ static int finish_and_refill(const aqg_engine& e, const double* uniforms, const 
     if (o.policy) if (int r = launch_engine_record_improved_policy(e, *o.policy, st)) return r;
     if (int r = launch_engine_finish_move(e, uniforms, o, st)) return r;
     if (o.reuse) launch_engine_keep_subtrees(e, *o.reuse, o.reuse->child_index, st);
-    if (e.quota > e.num_games) launch_engine_refill(e, st);
+    if (e.quota > e.num_games) launch_engine_refill(e, st, o.start);
     return check_launch("engine_finish_move_kernel");
 }
 
@@ -307,10 +319,11 @@ int engine_clear_eval_cache(const aqg_engine& e, hipStream_t st) {
     return 0;
 }
 
-int engine_reset(const aqg_engine& e, hipStream_t st) {
+int engine_reset(const aqg_engine& e, hipStream_t st, const aqg_start_table* start) {
     if (int r = validate(e)) return r;
+    if (int r = validate_start_table(e, start, "aqg_engine_reset_start")) return r;
     if (int r = engine_clear_eval_cache(e, st)) return r;
-    launch_engine_reset(e, st);
+    launch_engine_reset(e, st, start);
     return check_launch("engine_reset_kernel");
 }
 
@@ -393,8 +406,8 @@ int engine_record_improved_policy(const aqg_engine& e, const aqg_policy_record& 
 }
 
 // the slot refill alone, for a move that was applied rather than searched (engine_apply_actions, mcts_move.hip)
-int engine_refill(const aqg_engine& e, hipStream_t st) {
-    launch_engine_refill(e, st);
+int engine_refill(const aqg_engine& e, hipStream_t st, const aqg_start_table* start) {
+    launch_engine_refill(e, st, start);
     return check_launch("engine_refill_kernel");
 }
 

@@ -16,7 +16,18 @@ namespace aqg {
 // ------------------------------------------------------------------------------------------------
 // reset: every slot -> initial position (game_logic.py:25-40), active
 // ------------------------------------------------------------------------------------------------
-__global__ void engine_reset_kernel(aqg_engine e) {
+// (aqgnn.h, "start positions") START = the game's first position comes from the caller's table: row index[k], or k % count, of game k;
+// a row number outside the table -- the host refuses such an index before any launch -- starts from the opening record.  The plain
+// instantiations are the kernels as they were.
+__device__ __forceinline__ QState start_state(const aqg_engine& e, const aqg_start_table& t, int k) {
+    if (t.count <= 0) return initial_state(e.board_size, e.num_walls);
+    const int row = t.index ? t.index[k] : k % t.count;
+    if (row < 0 || row >= t.count) return initial_state(e.board_size, e.num_walls);
+    return unpack72(t.states72 + (size_t)row * STATE72);
+}
+
+template <class... Table>      // <> = the plain kernel, <aqg_start_table> = with the table as a second argument
+__global__ void engine_reset_kernel(aqg_engine e, Table... table) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g == 0) {
         e.counters[0] = e.num_games;          // active slots
@@ -33,7 +44,8 @@ __global__ void engine_reset_kernel(aqg_engine e) {
         e.game_first_move[g] = 0;
     }
     if (g >= e.num_games) return;
-    store_state(e.root_state, g, initial_state(e.board_size, e.num_walls));
+    if constexpr (sizeof...(Table) != 0) store_state(e.root_state, g, start_state(e, table..., g));
+    else store_state(e.root_state, g, initial_state(e.board_size, e.num_walls));
     e.game_active[g] = 1;
     e.slot_game[g] = g;
     e.node_count[g] = 0;
@@ -311,7 +323,10 @@ __device__ __forceinline__ void engine_transition(const aqg_engine& e, int g, in
 // minimum of (game, side), and an enabled game whose m is below -threshold ends here with the mover as loser.  An all-zero rs =
 // off: nothing below reads or writes through it.
 // ------------------------------------------------------------------------------------------------
-template <int N>
+// Start positions (aqgnn.h, "start positions"): GAME_PLY = the two ply tests below -- the temperature schedule's and resign_min_ply's --
+// count the plies played in THIS game (game_plies) instead of reading the record's counter; from the opening the two are one number,
+// and the plain instantiation is the kernel as it was.
+template <int N, bool GAME_PLY = false>
 __global__ __launch_bounds__(256) void engine_finish_move_kernel(aqg_engine e, const double* __restrict__ uniforms, int temperature_plies,
                                                                  float* __restrict__ hist_value, int32_t* __restrict__ child_index,
                                                                  uint8_t* __restrict__ kept, aqg_resign rs) {
@@ -343,7 +358,7 @@ __global__ __launch_bounds__(256) void engine_finish_move_kernel(aqg_engine e, c
     int chosen = -1, idx = -1, best = 0;                      // best: the first maximum of the visit counts
     if (cnt > 0) {
         idx = 0;
-        const bool late = temperature_plies > 0 && (int)s.plies >= temperature_plies;      // the schedule: arg-max from ply K on
+        const bool late = temperature_plies > 0 && (GAME_PLY ? ply : (int)s.plies) >= temperature_plies;      // the schedule: arg-max from ply K on
         if (e.temperature == 0.f || late) {                    // one-hot at the first maximum, then choice(p=one-hot)
             int bestn = -1;
             for (int i = 0; i < cnt; ++i) { const int n = nodes[first + i].n; if (n > bestn) { bestn = n; idx = i; } }
@@ -379,7 +394,7 @@ __global__ __launch_bounds__(256) void engine_finish_move_kernel(aqg_engine e, c
     }
     bool resigned = false;
     const int p = (int)s.plies;
-    if (rs.resign_min && cnt > 0 && p >= rs.min_ply) {
+    if (rs.resign_min && cnt > 0 && (GAME_PLY ? ply : p) >= rs.min_ply) {
         const double rw = nodes[0].w, cw = nodes[first + best].w;
         const int rn = nodes[0].n, cn = nodes[first + best].n;
         const float v_root = rn ? (float)(rw / (double)rn) : 0.0f;
@@ -401,7 +416,8 @@ __global__ __launch_bounds__(256) void engine_finish_move_kernel(aqg_engine e, c
 // indices not yet handed out and start from the initial position; once the quota is exhausted a finished slot stays
 // idle.  One workgroup: a block-wide exclusive scan over the slots' "idle" flags.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void engine_refill_kernel(aqg_engine e) {
+template <class... Table>
+__global__ __launch_bounds__(1024) void engine_refill_kernel(aqg_engine e, Table... table) {
     __shared__ int wsum[16];
     __shared__ int base;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -422,7 +438,8 @@ __global__ __launch_bounds__(1024) void engine_refill_kernel(aqg_engine e) {
         const int k = base + before + x - idle;              // this slot's next game, if any is left
         if (idle) {
             if (k < e.quota) {
-                store_state(e.root_state, g, initial_state(e.board_size, e.num_walls));
+                if constexpr (sizeof...(Table) != 0) store_state(e.root_state, g, start_state(e, table..., k));
+                else store_state(e.root_state, g, initial_state(e.board_size, e.num_walls));
                 e.slot_game[g] = k;
                 e.game_slot[k] = g;
                 e.game_first_move[k] = move_index;
@@ -515,8 +532,10 @@ __global__ __launch_bounds__(256) void engine_apply_actions_kernel(aqg_engine e,
 // host-side enqueue (no sync, no allocation): one launcher per kernel.  The entry points of mcts.hip validate in front of them and
 // check the launch behind them; a launcher's own status is the board-size dispatch's.
 // ------------------------------------------------------------------------------------------------
-void launch_engine_reset(const aqg_engine& e, hipStream_t st) {
-    hipLaunchKernelGGL(engine_reset_kernel, dim3((max(e.num_games, e.quota) + 255) / 256), dim3(256), 0, st, e);
+void launch_engine_reset(const aqg_engine& e, hipStream_t st, const aqg_start_table* start) {
+    const dim3 grid((max(e.num_games, e.quota) + 255) / 256), block(256);
+    if (start) hipLaunchKernelGGL(engine_reset_kernel<aqg_start_table>, grid, block, 0, st, e, *start);
+    else hipLaunchKernelGGL(engine_reset_kernel<>, grid, block, 0, st, e);
 }
 
 void launch_engine_set_roots(const aqg_engine& e, const uint8_t* roots72, hipStream_t st) {
@@ -552,14 +571,19 @@ int launch_engine_finish_move(const aqg_engine& e, const double* uniforms, const
     int32_t* child_index = opts.reuse ? opts.reuse->child_index : nullptr;
     uint8_t* kept = opts.reuse ? opts.reuse->kept : nullptr;
     return for_board_size(e.board_size, [&](auto n) {
-        hipLaunchKernelGGL(engine_finish_move_kernel<decltype(n)::value>, dim3((e.num_games + 3) / 4), dim3(256), 0, st, e, uniforms,
-                           opts.temperature_plies, opts.hist_value, child_index, kept, rs);
+        if (opts.start)
+            hipLaunchKernelGGL((engine_finish_move_kernel<decltype(n)::value, true>), dim3((e.num_games + 3) / 4), dim3(256), 0, st, e, uniforms,
+                               opts.temperature_plies, opts.hist_value, child_index, kept, rs);
+        else
+            hipLaunchKernelGGL(engine_finish_move_kernel<decltype(n)::value>, dim3((e.num_games + 3) / 4), dim3(256), 0, st, e, uniforms,
+                               opts.temperature_plies, opts.hist_value, child_index, kept, rs);
         return 0;
     });
 }
 
-void launch_engine_refill(const aqg_engine& e, hipStream_t st) {
-    hipLaunchKernelGGL(engine_refill_kernel, dim3(1), dim3(1024), 0, st, e);
+void launch_engine_refill(const aqg_engine& e, hipStream_t st, const aqg_start_table* start) {
+    if (start) hipLaunchKernelGGL(engine_refill_kernel<aqg_start_table>, dim3(1), dim3(1024), 0, st, e, *start);
+    else hipLaunchKernelGGL(engine_refill_kernel<>, dim3(1), dim3(1024), 0, st, e);
 }
 
 int launch_engine_root_visits(const aqg_engine& e, int32_t* visits, uint8_t* actions, int32_t* count, hipStream_t st) {
@@ -587,7 +611,7 @@ int engine_root_states72(const aqg_engine& e, uint8_t* out72, hipStream_t st) {
     return check_launch("engine_root_states72_kernel");
 }
 
-int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_t st) {
+int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_t st, const aqg_start_table* start) {
     if (e.num_games <= 0 || !e.root_state || !e.game_active || !e.slot_game || !e.game_plies || !e.game_result || !e.game_done ||
         !e.counters)
         return fail("aqg_engine_apply_actions: incomplete engine");
@@ -599,7 +623,7 @@ int engine_apply_actions(const aqg_engine& e, const int32_t* actions, hipStream_
         return check_launch("engine_apply_actions_kernel");
     });
     if (launched) return launched;
-    return e.quota > e.num_games ? engine_refill(e, st) : 0;
+    return e.quota > e.num_games ? engine_refill(e, st, start) : 0;
 }
 
 }  // namespace aqg

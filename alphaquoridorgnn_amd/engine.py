@@ -27,7 +27,8 @@ from .device_reference import (NODE_DTYPE, draw_resign_enabled, draw_root_noise,
                                keep_subtree_reference, root_improved_policy_reference, root_noise_stream_key)
 from .resign_calibration import resign_false_positives, resign_stats_of, suggest_from_arrays, suggest_resign_threshold  # noqa: F401
 from .selfplay_options import (ROOT_NOISE_ATTEMPTS, check_completed_q, check_policy_record, check_resign, check_root_noise, check_target_options,  # noqa: F401
-                               check_temperature, check_tree_reuse, default_resign_seed, default_root_noise_alpha, default_root_noise_seed, set_noise_seeds)
+                               check_start_table, check_temperature, check_tree_reuse, default_resign_seed, default_root_noise_alpha,
+                               default_root_noise_seed, set_noise_seeds, set_start_indices)
 from .two_engine_match import TwoEngineMatch  # noqa: F401
 
 
@@ -36,7 +37,7 @@ class BatchedSelfPlay:
                  c_puct=1.25, evaluator="gnn", fake_bias=0, seed=0, record_history=True, quota=None, eval_cache_slots=None,
                  root_noise_eps=0.0, root_noise_alpha=None, root_noise_seed=None, temperature_plies=0, record_search_value=False,
                  tree_reuse=False, tree_reuse_visits=None, resign_threshold=None, resign_min_ply=0, resign_disable_fraction=0.1,
-                 resign_seed=None, policy_target="visits", policy_c_visit=50.0, policy_c_scale=1.0):
+                 resign_seed=None, policy_target="visits", policy_c_visit=50.0, policy_c_scale=1.0, start_states=None, start_index=None):
         """model: GraphPolicyValueNetwork/GNNNetwork (evaluator='gnn'); evaluator='fake' runs the integer-hash
         evaluator used by the parity tests (oracle/mcts.py FakeModel); evaluator='external' calls `model.predict(state,
         device)` -- ANY object honouring the reference's BaseNetwork contract (BaseNetwork.py:36-40), e.g. a stock CNN --
@@ -78,7 +79,14 @@ class BatchedSelfPlay:
         temperature_plies, and hist_visits is still written: only the recorded target changes, no game does.  Works with tree reuse
         (a kept root is valid for the read-out), with resignation (the resigning row is written like any other) and with
         evaluator='external'.  With root noise on, the root's stored priors are the MIXED ones, so the target is
-        softmax(log p_mixed + sigma): the noise is not taken out again.  apply_actions() and search() refuse the option."""
+        softmax(log p_mixed + sigma): the noise is not taken out again.  apply_actions() and search() refuse the option.
+        start_states (None = off, the default: every call is the one made today; include/aqgnn.h, "start positions"): a uint8 [S, 72]
+        tensor or array of records the games start from instead of the opening record, copied to the device once.  Game k -- the
+        engine's game index, whatever slot plays it -- starts from row start_index[k] (int [quota], each in [0, S)), by default from
+        row k % S.  The table goes through the checker here (game_logic.check_states_batch: one device-to-host read, in the
+        constructor only) and any flagged row raises ValueError; so does an index that is short, long or out of range.  A start
+        record has an even ply counter.  game_plies, the history rows, temperature_plies and resign_min_ply count the plies played in
+        the game; the draw rule reads the record's own counter.  reset() and every refill start from the table; search() refuses it."""
         self.policy_target, self.policy_c_visit, self.policy_c_scale = check_policy_record(policy_target, policy_c_visit, policy_c_scale,
                                                                                            record_history)
         self.resign_options = check_resign(resign_threshold, resign_min_ply, resign_disable_fraction, record_history)
@@ -104,6 +112,7 @@ class BatchedSelfPlay:
         self.quota = self.G if quota is None else int(quota)
         if self.quota < self.G:
             raise ValueError("quota must be >= num_games")
+        start_table = check_start_table(start_states, start_index, self.N, self.quota, self.dev)      # before anything else is allocated
         depth = self.sims + (self.keep_visits or 0)                # visits a tree can hold: its expanded nodes and its depth
         self.node_cap = 1 + depth * _lib.MAX_LEGAL
         self.max_plies = self.plies_for_draw
@@ -202,6 +211,14 @@ class BatchedSelfPlay:
         if self.policy_target == "completed_q":
             pr = self.policy_record = _lib.PolicyRecordStruct()
             pr.c_visit, pr.c_scale = self.policy_c_visit, self.policy_c_scale
+        self.start = None
+        if start_table is not None:
+            t["start_states72"], index = start_table
+            st = self.start = _lib.StartTableStruct()
+            st.states72, st.count = t["start_states72"].data_ptr(), t["start_states72"].shape[0]
+            if index is not None:
+                t["start_index"] = index
+                st.index = index.data_ptr()
         # every tensor is pointed at the struct field of its name (hist_value has none: it is an argument of the move; an absent
         # tensor -- gnn_workspace, the cache's -- leaves its field NULL)
         for name, tensor in t.items():
@@ -217,7 +234,10 @@ class BatchedSelfPlay:
         return _lib.stream_ptr(self.dev)
 
     def reset(self):
-        _lib.check(self.lib.aqg_engine_reset(ctypes.byref(self.e), self._stream()), "aqg_engine_reset")
+        if self.start is not None:
+            _lib.check(self.lib.aqg_engine_reset_start(ctypes.byref(self.e), ctypes.byref(self.start), self._stream()), "aqg_engine_reset_start")
+        else:
+            _lib.check(self.lib.aqg_engine_reset(ctypes.byref(self.e), self._stream()), "aqg_engine_reset")
         if self.tree_reuse:
             self._forget_kept_trees()
             self.t["stat_moves_kept"].zero_()
@@ -303,11 +323,16 @@ class BatchedSelfPlay:
             uniforms = torch.as_tensor(uniforms, dtype=torch.float64).to(self.dev).contiguous()
         self._u = uniforms  # keep alive until the stream has consumed it
         # the entry point and what follows the uniforms: the plain form while every option is off, else the first form that takes
-        # all that is on -- the policy record's takes the other two structs or none, resignation's takes a tree-reuse struct or none,
-        # tree reuse's takes the targets, and so does _targets
+        # all that is on -- the start table's takes the other three structs or none, the policy record's takes the other two structs or
+        # none, resignation's takes a tree-reuse struct or none, tree reuse's takes the targets, and so does _targets
         external = self.evaluator == "external"                  # (check_tree_reuse: never with tree reuse)
         tail = [self.temperature_plies, _lib.ptr(self.t.get("hist_value"))]
-        if self.policy_record is not None:
+        if self.start is not None:
+            form, tail = "_start", tail + [ctypes.byref(self.reuse) if self.tree_reuse else None,
+                                           ctypes.byref(self.resign) if self.resign is not None else None,
+                                           ctypes.byref(self.policy_record) if self.policy_record is not None else None,
+                                           ctypes.byref(self.start)]
+        elif self.policy_record is not None:
             form, tail = "_policy", tail + [ctypes.byref(self.reuse) if self.tree_reuse else None,
                                             ctypes.byref(self.resign) if self.resign is not None else None,
                                             ctypes.byref(self.policy_record)]
@@ -342,7 +367,11 @@ class BatchedSelfPlay:
             raise ValueError("apply_actions() plays moves nobody searched: build the engine without policy_target='completed_q'")
         actions = torch.as_tensor(actions, dtype=torch.int32).to(self.dev).contiguous().view(self.G)
         self._applied = actions  # keep alive until the stream has consumed it
-        _lib.check(self.lib.aqg_engine_apply_actions(ctypes.byref(self.e), _lib.ptr(actions), self._stream()), "aqg_engine_apply_actions")
+        if self.start is not None:
+            _lib.check(self.lib.aqg_engine_apply_actions_start(ctypes.byref(self.e), _lib.ptr(actions), ctypes.byref(self.start), self._stream()),
+                       "aqg_engine_apply_actions_start")
+        else:
+            _lib.check(self.lib.aqg_engine_apply_actions(ctypes.byref(self.e), _lib.ptr(actions), self._stream()), "aqg_engine_apply_actions")
         if self.tree_reuse:
             self._forget_kept_trees()      # the roots changed without a search: the next move starts from fresh trees
         self.moves_done += 1
@@ -453,6 +482,8 @@ class BatchedSelfPlay:
         if self.policy_record is not None:
             raise ValueError("search() records no history: build the engine without policy_target='completed_q' (root_improved_policy() "
                              "reads the same target out of a searched root)")
+        if self.start is not None:
+            raise ValueError("search() looks at caller-given roots already: build the engine without start_states")
         roots = torch.as_tensor(root_states72, dtype=torch.uint8).to(self.dev).contiguous().view(self.G, 72)
         self._roots = roots
         self._set_root_noise(root_noise)
@@ -576,7 +607,7 @@ class MultiSetSelfPlay:
     streams, which every engine of the process reuses -- see _SET_STREAMS)."""
 
     def __init__(self, model=None, num_games=2048, sims=50, num_sets=None, seed=0, device=None, quota=None, root_noise_seed=None,
-                 resign_seed=None, **kw):
+                 resign_seed=None, start_states=None, start_index=None, **kw):
         check_resign(kw.get("resign_threshold"), kw.get("resign_min_ply", 0), kw.get("resign_disable_fraction", 0.1),
                      kw.get("record_history", True))          # before anything is allocated
         check_policy_record(kw.get("policy_target", "visits"), kw.get("policy_c_visit", 50.0), kw.get("policy_c_scale", 1.0),
@@ -603,6 +634,12 @@ class MultiSetSelfPlay:
         # the sets' games are numbered through for the enabled / disabled draw as they are for the noise: the numbering rides in the seed
         resign_seeds = set_noise_seeds(seed, default_resign_seed(seed) if resign_seed is None else resign_seed, sizes,
                                        [max(q, g) for q, g in zip(quotas, sizes)])
+        # start positions: set i plays the games [sum of the quotas before it, + its own quota) of history_tensors()' order, and is handed
+        # that slice of the index -- of the caller's, or of the default k % S written out, so that a game's start never depends on the sets
+        set_quotas = [max(q, g) for q, g in zip(quotas, sizes)]
+        start_indices = set_start_indices(start_states, start_index, set_quotas)
+        if start_states is not None:
+            kw = dict(kw, start_states=start_states)
         self.sets = []
         ready = torch.cuda.current_stream(self.dev).record_event()   # e.g. the model's weight upload on the caller's stream
         for i, g in enumerate(sizes):
@@ -610,7 +647,8 @@ class MultiSetSelfPlay:
                 self.streams[i].wait_event(ready)
                 self.sets.append(BatchedSelfPlay(model, num_games=g, sims=sims, seed=int(seed) * 64 + i, device=self.dev,
                                                  quota=max(quotas[i], g),
-                                                 root_noise_seed=noise_seeds[i], resign_seed=resign_seeds[i], **kw))
+                                                 root_noise_seed=noise_seeds[i], resign_seed=resign_seeds[i],
+                                                 **(dict(kw, start_index=start_indices[i]) if start_states is not None else kw)))
         self.G, self.sims = int(num_games), int(sims)
         self.quota = self.G if quota is None else int(quota)
         if self.quota < self.G:

@@ -54,6 +54,114 @@ def status_batch(states72, board_size=BOARD_SIZE, plies_for_draw=NUM_PLIES_FOR_D
     return out
 
 
+# ------------------------------------------------------------------ may a record start a game?  (include/aqgnn.h, "start positions")
+def _check_constants(board_size, num_walls, plies_for_draw):
+    from .constants import board_params
+    walls, draw = board_params(board_size)
+    return int(walls if num_walls is None else num_walls), int(draw if plies_for_draw is None else plies_for_draw)
+
+
+def check_states_batch(states72, board_size=BOARD_SIZE, num_walls=None, plies_for_draw=None):
+    """flags u8 [B] of states72 (uint8 [B,72] device tensor): 0 = the record may start a game, else the AQG_CHECK_* bits
+    (_lib.CHECK_BOARD ... _lib.CHECK_NO_PATH).  num_walls / plies_for_draw: the board's own unless given."""
+    dev = _lib.require_gpu(states72.device)
+    if states72.dtype != torch.uint8 or states72.dim() != 2 or states72.shape[1] != STATE72:
+        raise ValueError("states72 must be a uint8 [B,72] device tensor")
+    walls, draw = _check_constants(board_size, num_walls, plies_for_draw)
+    states72 = states72.contiguous()
+    out = torch.empty((states72.shape[0],), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().aqg_states72_check(board_size, _lib.ptr(states72), states72.shape[0], walls, draw, _lib.ptr(out),
+                                              _lib.stream_ptr(dev)), "aqg_states72_check")
+    return out
+
+
+def check_state_host(rec72, board_size=BOARD_SIZE, num_walls=None, plies_for_draw=None):
+    """The checker's byte for one record in host memory, by the host build of the kernel's own predicate (aqg_host_check_state)."""
+    import ctypes
+    walls, draw = _check_constants(board_size, num_walls, plies_for_draw)
+    rec = np.ascontiguousarray(rec72, dtype=np.uint8).reshape(STATE72)
+    flags = _lib.load().aqg_host_check_state(board_size, rec.ctypes.data_as(ctypes.c_void_p), walls, draw)
+    if flags < 0:
+        raise ValueError(f"aqg_host_check_state refuses board_size {board_size}, num_walls {walls}, plies_for_draw {draw}")
+    return flags
+
+
+def _reaches_row(N, walls, start, obstacle, goal_row):
+    """Can a pawn on `start` reach row `goal_row` while the other pawn stands on `obstacle` (None = no other pawn: the walls alone)?
+    Breadth-first over the pawn moves of game_logic.py:120-192 (steps, straight jumps, side jumps), in plain Python."""
+    S = N - 1
+
+    def wall(sx, sy, kind):
+        return 0 <= sx < S and 0 <= sy < S and walls[sx * S + sy] == kind
+
+    def is_open(t, d):          # d: 0 up, 1 down, 2 left, 3 right
+        x, y = divmod(t, N)
+        if d == 0:
+            return x > 0 and not (wall(x - 1, y, 1) or wall(x - 1, y - 1, 1))
+        if d == 1:
+            return x < N - 1 and not (wall(x, y, 1) or wall(x, y - 1, 1))
+        if d == 2:
+            return y > 0 and not (wall(x, y - 1, 2) or wall(x - 1, y - 1, 2))
+        return y < N - 1 and not (wall(x, y, 2) or wall(x - 1, y, 2))
+
+    step = (-N, N, -1, 1)
+    seen, queue = {start}, [start]
+    while queue:
+        t = queue.pop(0)
+        if t // N == goal_row:
+            return True
+        nxt = []
+        for d in range(4):
+            if not is_open(t, d):
+                continue
+            n = t + step[d]
+            if n != obstacle:
+                nxt.append(n)
+            elif is_open(n, d):
+                nxt.append(n + step[d])
+            else:
+                nxt += [n + step[s] for s in ((2, 3) if d < 2 else (0, 1)) if is_open(n, s)]
+        for n in nxt:
+            if n not in seen:
+                seen.add(n)
+                queue.append(n)
+    return False
+
+
+def check_state_reference(rec72, board_size=BOARD_SIZE, num_walls=None, plies_for_draw=None):
+    """The checker, stated in plain Python/numpy (include/aqgnn.h, "start positions"): the byte aqg_states72_check and
+    aqg_host_check_state give for this record."""
+    N = int(board_size)
+    num_walls, draw = _check_constants(N, num_walls, plies_for_draw)
+    rec = np.asarray(rec72, dtype=np.uint8).reshape(STATE72)
+    V, S = N * N, N - 1
+    ppos, pleft, epos, eleft = (int(x) for x in rec[:4])
+    walls = [int(x) for x in rec[4:4 + S * S]]
+    plies = int(rec[68]) | (int(rec[69]) << 8)
+    flags = 0
+    if int(rec[70]) != N or ppos >= V or epos >= V:
+        flags |= _lib.CHECK_BOARD
+    overlap = any(walls[i] == 1 and walls[i + 1] == 1 for i in range(S * S - 1) if i % S != S - 1) or \
+        any(walls[i] == 2 and walls[i + S] == 2 for i in range(S * S - S))
+    if any(w > 2 for w in walls) or overlap:
+        flags |= _lib.CHECK_WALLS
+    placed = sum(1 for w in walls if w in (1, 2))
+    if pleft > num_walls or eleft > num_walls or pleft + eleft + placed != 2 * num_walls:
+        flags |= _lib.CHECK_WALL_COUNT
+    if ppos == V - 1 - epos:
+        flags |= _lib.CHECK_SAME_SQUARE
+    if epos // N == 0 or ppos // N == 0 or plies >= draw:
+        flags |= _lib.CHECK_OVER
+    if plies % 2:
+        flags |= _lib.CHECK_ODD_PLY
+    if not flags & (_lib.CHECK_BOARD | _lib.CHECK_WALLS | _lib.CHECK_SAME_SQUARE):
+        other = V - 1 - epos
+        # through the walls alone: a pawn standing in the other's only corridor is a position of real games, not a bad record
+        if not (_reaches_row(N, walls, ppos, None, 0) and _reaches_row(N, walls, other, None, N - 1)):
+            flags |= _lib.CHECK_NO_PATH
+    return flags
+
+
 # ------------------------------------------------------------------ the left-right mirror (include/aqgnn.h, "training augmentation")
 def _mirror_cells(cells, width):
     """Cell i of a grid of lines of `width` cells, mirrored inside its line."""

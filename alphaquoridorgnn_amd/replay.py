@@ -600,6 +600,7 @@ class ReplayWindow:
         self._index = torch.zeros((0,), dtype=torch.int64, device=self.device)
         self.reanalyse_updates = 0      # reanalyse passes self_play() has run on this window: the `update` of draw_reanalyse_rows
         self.surprise_updates = 0       # surprise-weighted updates drawn on this window: the `update` of surprise_index's key
+        self.fork_updates = 0           # generations self_play() has forked from this window: the `update` of openings.fork_table
         if self.capacity is not None:
             self._allocate()
 

@@ -75,6 +75,11 @@ SP_REANALYSE_C_SCALE = 1.0
 SP_POLICY_TARGET = 'visits'  # the reference's rows
 SP_POLICY_C_VISIT = 50.0
 SP_POLICY_C_SCALE = 1.0
+# Forked self-play (the reference has none; openings.fork_table, include/aqgnn.h "start positions"): a share of every generation's games
+# starts from positions the replay window already holds instead of from the opening record.  Which games, and from which row, is drawn
+# per (seed, generation, game index over all ranks): every rank builds the same table from its own window, with no collective.
+SP_START_FROM_WINDOW_SHARE = 0.0     # 0 = off (or an empty window): no table is built and every call is the one made today
+SP_FORKED_LAST = 0                   # games of the last generation that started from a window row, over all ranks
 
 
 def first_player_value(ended_state):
@@ -230,6 +235,17 @@ def self_play(model=None, games=None, seed=None):
     pol = torch.zeros((0, POLICY_OUTPUT_SIZE), dtype=torch.float32, device=dev) if target == "completed_q" else None      # the recorded targets
     resign_kw, resign_thr = _resign_options()
     resign_arrays = None
+    # forked self-play: the table of the whole generation, and this rank's slice of its index (the ranks' games are numbered through)
+    global SP_FORKED_LAST
+    from .openings import check_window_share, fork_table
+    SP_FORKED_LAST, start_kw = 0, {}
+    if check_window_share(SP_START_FROM_WINDOW_SHARE) > 0.0 and SP_REPLAY is not None:
+        forked = fork_table(SP_REPLAY, total, SP_START_FROM_WINDOW_SHARE, base, SP_REPLAY.fork_updates)
+        SP_REPLAY.fork_updates += 1
+        if forked is not None:
+            first = sum(total // world + (1 if r < total % world else 0) for r in range(rank))
+            start_kw = dict(start_states=forked[0], start_index=forked[1][first:first + mine])
+            SP_FORKED_LAST = int((forked[1] > 0).sum())
     slots = mine
     if SP_SLOTS is not None:
         if isinstance(SP_SLOTS, bool) or int(SP_SLOTS) != SP_SLOTS or int(SP_SLOTS) < 1:
@@ -242,9 +258,10 @@ def self_play(model=None, games=None, seed=None):
                                evaluator=evaluator, root_noise_eps=SP_ROOT_NOISE_EPS, root_noise_alpha=SP_ROOT_NOISE_ALPHA,
                                temperature_plies=SP_TEMPERATURE_PLIES, record_search_value=blend > 0.0,
                                tree_reuse=SP_TREE_REUSE, tree_reuse_visits=SP_TREE_REUSE_VISITS,
-                               policy_target=target, policy_c_visit=c_visit, policy_c_scale=c_scale, **resign_kw)
+                               policy_target=target, policy_c_visit=c_visit, policy_c_scale=c_scale, **resign_kw, **start_kw)
         c = eng.play_generation()
-        print(f'\rSelf-play (rank {rank}: {c["finished"]}/{mine} games, policy target: {target})', end='')
+        print(f'\rSelf-play (rank {rank}: {c["finished"]}/{mine} games, policy target: {target}'
+              + (f', {SP_FORKED_LAST}/{total} games forked from the window' if start_kw else '') + ')', end='')
         st, vis, z = eng.history_tensors()
         if q is not None:
             q = eng.history_values()

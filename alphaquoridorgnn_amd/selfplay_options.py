@@ -155,6 +155,70 @@ def set_noise_seeds(seed, root_noise_seed, sizes, quotas):
     return [(base + GOLDEN * f) & MASK64 for f in firsts]
 
 
+# ------------------------------------------------------------------ start positions (include/aqgnn.h, "start positions")
+def _start_rows(start_states):
+    """The table as a uint8 [S, 72] numpy array or torch tensor, S >= 1 (ValueError otherwise)."""
+    import torch
+    rows = start_states if isinstance(start_states, torch.Tensor) else np.asarray(start_states)
+    if str(rows.dtype) not in ("uint8", "torch.uint8") or len(rows.shape) != 2 or rows.shape[1] != 72 or rows.shape[0] < 1:
+        raise ValueError("start_states must be a uint8 [S, 72] tensor or array of state72 records, S >= 1")
+    return rows
+
+
+def check_start_index(start_index, rows, quota):
+    """start_index as an int32 numpy array [quota] with every entry in [0, rows) (ValueError otherwise); None stays None."""
+    if start_index is None:
+        return None
+    import torch
+    index = start_index.cpu().numpy() if isinstance(start_index, torch.Tensor) else np.asarray(start_index)
+    if index.ndim != 1 or index.dtype.kind not in "iu":
+        raise ValueError("start_index must be a one-dimensional integer array")
+    if index.shape[0] != quota:
+        raise ValueError(f"start_index has {index.shape[0]} entries for {quota} games: one row number per game of the quota")
+    bad = np.flatnonzero((index < 0) | (index >= rows))
+    if bad.size:
+        raise ValueError(f"start_index[{int(bad[0])}] = {int(index[bad[0]])} is outside the {rows} rows of start_states")
+    return index.astype(np.int32)
+
+
+def check_start_table(start_states, start_index, board_size, quota, device):
+    """None without a table, else (rows u8 [S,72], index i32 [quota] or None) on `device`, checked: the rows by the device checker
+    (one device-to-host read), the index for length and range.  ValueError names the first bad row and its flags."""
+    import torch
+    if start_states is None:
+        if start_index is not None:
+            raise ValueError("start_index needs start_states")
+        return None
+    rows = _start_rows(start_states)
+    index = check_start_index(start_index, rows.shape[0], quota)
+    from .game_logic import check_states_batch
+    if not isinstance(rows, torch.Tensor):
+        rows = torch.from_numpy(np.array(rows, dtype=np.uint8))       # (a copy: the caller's array may be read-only)
+    rows = rows.to(device).contiguous().clone()                        # the engine's own copy
+    flags = check_states_batch(rows, board_size).cpu().numpy()
+    bad = np.flatnonzero(flags)
+    if bad.size:
+        raise ValueError(f"start_states row {int(bad[0])} cannot start a game: checker flags {int(flags[bad[0]])} "
+                         f"({bad.size} of {rows.shape[0]} rows are flagged; game_logic.check_state_reference names the bits)")
+    return rows, None if index is None else torch.from_numpy(index).to(device)
+
+
+def set_start_indices(start_states, start_index, set_quotas):
+    """The start indices of MultiSetSelfPlay's sets (games `set_quotas`): the sets' games are numbered through in history_tensors()'
+    order, and set i is handed the slice of its block -- of the caller's index, or of the default k % S written out."""
+    if start_states is None:
+        if start_index is not None:
+            raise ValueError("start_index needs start_states")
+        return [None] * len(set_quotas)
+    rows = _start_rows(start_states).shape[0]
+    total = int(sum(set_quotas))
+    index = check_start_index(start_index, rows, total)
+    if index is None:
+        index = (np.arange(total) % rows).astype(np.int32)
+    firsts = np.concatenate([[0], np.cumsum(set_quotas)]).astype(int)
+    return [index[firsts[i]:firsts[i + 1]] for i in range(len(set_quotas))]
+
+
 # Matches, evaluation paths and single searches add no noise (they measure strength), search from a fresh tree every move (two
 # alternating searchers would need a two-ply descent into per-model trees) and play every game to its rule end.
 _NOISE, _REUSE, _RESIGN = "never adds root exploration noise", "never keeps a subtree between moves", "never resigns a game"

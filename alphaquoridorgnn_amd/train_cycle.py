@@ -255,7 +255,52 @@ def _parser():
                     help="self-play, with --policy-target completed-q: c_visit of the transform, >= 0 (default SP_POLICY_C_VISIT = 50)")
     ap.add_argument("--policy-c-scale", type=float, default=None, metavar="Y",
                     help="self-play, with --policy-target completed-q: c_scale of the transform, >= 0 (default SP_POLICY_C_SCALE = 1)")
+    ap.add_argument("--eval-opening-plies", type=int, default=None, metavar="K",
+                    help="evaluation: play the match from a book of paired openings K random plies deep (K even, an even game count), "
+                         "each opening twice with the colours exchanged, and print the paired report (default EN_OPENING_PLIES = 0: off)")
+    ap.add_argument("--eval-opening-seed", type=int, default=None, metavar="S",
+                    help="evaluation, with --eval-opening-plies: the seed of the book (default EN_OPENING_SEED = 0)")
+    ap.add_argument("--start-from-window", type=float, default=None, metavar="S",
+                    help="self-play: start a share S in [0, 1] of every generation's games from positions of the replay window instead of "
+                         "the opening record (needs --replay-generations; default SP_START_FROM_WINDOW_SHARE = 0: off)")
     return ap
+
+
+def _check_start_args(args):
+    """--eval-opening-plies / --eval-opening-seed / --start-from-window, refused at parse time: an odd depth, an odd game count with a
+    depth, a seed without a depth, a share outside [0, 1], a share without a window.  Returns (plies or None, seed or None, share or
+    None)."""
+    from . import evaluate_network as en
+    from .openings import check_window_share
+    if args.eval_opening_plies is None and args.eval_opening_seed is not None:
+        raise ValueError("--eval-opening-seed needs --eval-opening-plies")
+    if args.eval_opening_plies is not None:
+        games = en.EN_GAME_COUNT if args.eval_games is None else args.eval_games
+        try:
+            en.check_opening_options(args.eval_opening_plies, games)
+        except ValueError as err:
+            raise ValueError(f"--eval-opening-plies / --eval-games: {err}") from None
+    share = None
+    if args.start_from_window is not None:
+        try:
+            share = check_window_share(args.start_from_window)
+        except ValueError as err:
+            raise ValueError(f"--start-from-window: {err}") from None
+        if args.replay_generations < 1:
+            raise ValueError("--start-from-window needs --replay-generations K >= 1: there is no window to start from")
+    return args.eval_opening_plies, args.eval_opening_seed, share
+
+
+def _set_start_options(args):
+    """The checked start-position flags onto evaluate_network's and self_play's constants."""
+    from . import evaluate_network as en, self_play as sp
+    plies, seed, share = _check_start_args(args)
+    if plies is not None:
+        en.EN_OPENING_PLIES = plies
+    if seed is not None:
+        en.EN_OPENING_SEED = seed
+    if share is not None:
+        sp.SP_START_FROM_WINDOW_SHARE = share
 
 
 def _check_policy_args(args):
@@ -475,6 +520,7 @@ def main(argv=None):
     _check_reanalyse_policy_args(args)
     _check_policy_args(args)
     _check_surprise_args(args)
+    _check_start_args(args)
     rank, world = aqd.init_from_env()
     if args.games is not None:
         sp.SP_GAME_COUNT = args.games
@@ -495,6 +541,7 @@ def main(argv=None):
     _set_surprise_options(args)
     _set_reanalyse_options(args)
     _set_policy_options(args)
+    _set_start_options(args)
     if args.eval_games is not None:
         en.EN_GAME_COUNT = args.eval_games
     try:

@@ -1110,6 +1110,76 @@ int aqg_replay_surprise_rows(int board_size, int policy_size, const float* net_p
 int aqg_replay_surprise_counts(const int32_t* q, const int64_t* index, const int64_t* total, int m, long long expected_rows,
                                double uniform_share, int max_copies, uint64_t seed, uint64_t update, int32_t* count, void* stream);
 
+/* ------------------------------------------------------------------ start positions (additive to ABI 15; the reference starts every game from the opening)
+ *
+ * Games that start from caller-given records: opening books, paired matches, forks of recorded positions.  Off by default: without
+ * a table every call launches what it launched before.  The engine struct, the ABI number, the step kernels, the captured per-move
+ * graph and its key do not change: the table is a struct beside the engine's, an argument of the reset and refill launches.
+ *
+ * The checker (csrc/state_check.hip; one predicate on the rule header, compiled for the device and for the host).  flags[i] == 0:
+ * record i may start a game.  Bits:
+ *   AQG_CHECK_BOARD        byte 70 is not board_size, or a pawn cell is >= N*N
+ *   AQG_CHECK_WALLS        a wall byte > 2 among the first (N-1)^2, or two walls that overlap: two horizontal walls in neighbouring
+ *                          slots of one row, or two vertical walls in neighbouring slots of one column (what can_place_wall refuses,
+ *                          game_logic.py:199-223)
+ *   AQG_CHECK_WALL_COUNT   a walls-left byte > num_walls, or player_left + enemy_left + placed != 2 * num_walls; placed = the wall bytes
+ *                          that are 1 or 2 (a byte > 2 is no wall)
+ *   AQG_CHECK_SAME_SQUARE  both pawns on one square: ppos == N*N - 1 - epos
+ *   AQG_CHECK_OVER         the game is over: is_lose (epos / N == 0), the mover on its own goal row (ppos / N == 0), plies >= plies_for_draw
+ *   AQG_CHECK_ODD_PLY      the ply counter is odd.  history z, the resignation side and the match loops take the side from a game's own
+ *                          ply index; game_result takes it from the record.  With an even start they agree, so a start must be even.
+ *   AQG_CHECK_NO_PATH      a pawn has no path to its goal row through the walls: the fill of the wall-legality search with no candidate
+ *                          wall and the other pawn taken off the board.  (With the other pawn as an obstacle, positions of real games
+ *                          would be flagged: a wall is legal while both jump-aware paths exist, but a pawn may later step into the
+ *                          other's only corridor.  The path through the walls alone is what the rules keep invariant.)
+ *                          Evaluated only when BOARD, WALLS and SAME_SQUARE are clear, else 0
+ * Bytes past the board's wall slots and byte 71 are not read; nothing outside the record is read; every index formed from a record
+ * byte is bounded first; no atomics; every loop is bounded by a constant of N.  Reachability from the opening is NOT a condition.
+ *   aqg_states72_check     device: states72 u8 [B,72], flags u8 [B]; one thread per record.  Refused: an unsupported board size, B < 0,
+ *                          a NULL array with B > 0, num_walls outside 0..127, plies_for_draw outside 0..65535.
+ *   aqg_host_check_state   the same byte for one record in HOST memory; -1 for a NULL record, an unsupported board size or a constant
+ *                          outside those ranges.  game_logic.check_state_reference is the statement in numpy.
+ *
+ * The table.  Game k -- the engine's game index, slot_game -- starts from row index ? index[k] : k % count of states72 u8 [count,72]
+ * (device); index i32 [quota] (device) or NULL.  A game's start is a function of its game index alone, never of slot, refill order or
+ * set count.  The caller has run the rows through the checker and the index through a range check: the entry points refuse a NULL
+ * states72 and count < 1 only, and the kernels start a game whose row number is outside [0, count) from the opening record.
+ * engine_reset_kernel / engine_refill_kernel (csrc/mcts_move.hip) take the table under a template switch:
+ * store_state(root_state, g, unpack72(row)) replaces the initial_state store and nothing else changes; the plain instantiations are
+ * the kernels as they were.  The table is only read.
+ * Everything per game keeps counting plies played in THIS game: game_plies and the history rows as always, and with a table the
+ * finish-move launch (its GAME_PLY instantiation) compares temperature_plies and resign min_ply with game_plies[k] instead of the
+ * record's counter -- from the opening the two are one number.  The root-noise key of a move stays (seed, game, the record's ply
+ * counter): it is formed inside the captured graph, which does not change, and it is still unique per game and ply.  The draw rule
+ * reads the record's own counter: a start at ply p has plies_for_draw - p plies left and fits the existing history.
+ *   aqg_engine_reset_start          aqg_engine_reset with the table (NULL = aqg_engine_reset)
+ *   aqg_engine_move_start / aqg_engine_finish_move_start   aqg_engine_move_policy / aqg_engine_finish_move_policy with the table as one
+ *                                   more nullable pointer: the refill behind the move starts its games from it
+ *   aqg_engine_apply_actions_start  aqg_engine_apply_actions, likewise */
+#define AQG_CHECK_BOARD 1
+#define AQG_CHECK_WALLS 2
+#define AQG_CHECK_WALL_COUNT 4
+#define AQG_CHECK_SAME_SQUARE 8
+#define AQG_CHECK_OVER 16
+#define AQG_CHECK_ODD_PLY 32
+#define AQG_CHECK_NO_PATH 64
+int aqg_states72_check(int board_size, const uint8_t* states72, int B, int num_walls, int plies_for_draw, uint8_t* flags,
+                       void* stream);
+int aqg_host_check_state(int board_size, const uint8_t* rec72_host, int num_walls, int plies_for_draw);
+typedef struct aqg_start_table {
+    const uint8_t* states72;        /* [count, 72] checked records */
+    const int32_t* index;           /* [quota] row of every game, or NULL = game k starts from row k % count */
+    int32_t count;                  /* >= 1 */
+} aqg_start_table;
+int aqg_engine_reset_start(const aqg_engine* e_host, const aqg_start_table* start, void* stream);
+int aqg_engine_move_start(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                          const aqg_tree_reuse* reuse, const aqg_resign* resign, const aqg_policy_record* policy,
+                          const aqg_start_table* start, void* stream);
+int aqg_engine_finish_move_start(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                                 const aqg_tree_reuse* reuse, const aqg_resign* resign, const aqg_policy_record* policy,
+                                 const aqg_start_table* start, void* stream);
+int aqg_engine_apply_actions_start(const aqg_engine* e_host, const int32_t* actions, const aqg_start_table* start, void* stream);
+
 /* ------------------------------------------------------------------ CPU baseline agents (agents.py) -- HOST pointers, host code */
 
 /* The reference's baseline opponents (agents.py:14-214) are CPU code; so are these: the host instantiation of the rule header
