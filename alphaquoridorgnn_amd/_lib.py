@@ -8,9 +8,10 @@ import os
 
 import torch
 
+from .constants import MAX_LEGAL  # noqa: F401   (the numpy statements import it from there, without ctypes)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AQG_LIB_PATH", os.path.join(_HERE, "libaqgnn_hip.so"))  # override: diagnostic builds only
-MAX_LEGAL = 136
 GNN_EXACT_F32 = 1        # AQG_GNN_EXACT_F32 (include/aqgnn.h)
 GNN_RANGE_PROVEN = 2     # AQG_GNN_RANGE_PROVEN
 GNN_PROVEN_MAX_WALLS = 16

@@ -14,5 +14,18 @@ PV_NETWORK_NAME = "GNN"  # which network to use (the reference ships 'CNN'; this
 PV_NETWORK_PATH = f"models/{PV_NETWORK_NAME}/{BOARD_SIZE}x{BOARD_SIZE}/"  # path for network weights
 
 
+MAX_LEGAL = 136  # the longest legal-action list of any position (MAX_LEGAL of include/aqgnn.h): the row length of search results
+
+
 def board_params(board_size):
     return _BOARDS[board_size]
+
+
+def num_actions(board_size=BOARD_SIZE):
+    """The action count of a board: N^2 pawn targets and two orientations of (N - 1)^2 wall slots (209 at 9x9)."""
+    return board_size ** 2 + 2 * (board_size - 1) ** 2
+
+
+def check_board_size(board_size, what):
+    if board_size not in (3, 5, 7, 9):
+        raise ValueError(f"{what}: unsupported board_size (odd 3..9)")

@@ -19,6 +19,12 @@ inline int check_launch(const char* kernel) {
     return 0;
 }
 
+// do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte?  A NULL pointer is an argument not given: it never overlaps.
+inline bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && x < y + b_bytes && y < x + a_bytes;
+}
+
 constexpr int WAVE = 64;
 
 // Diagnostic build only (-DAQG_TRACE, tools/trace_overlap.py; never shipped): every workgroup of the three per-simulation

@@ -105,16 +105,11 @@ __global__ __launch_bounds__(AUG_WAVES * WAVE) void augment_gather_kernel(
     }
 }
 
-static bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + b_bytes && y < x + a_bytes;
-}
-
 int launch_augment_gather(int N, int policy_size, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
                           const uint8_t* flips, int use_seed, uint64_t seed, uint64_t epoch, int n, uint8_t* out72, float* out_pi,
                           float* out_z, hipStream_t st) {
     if (!board_size_supported(N)) return fail("aqg_augment_gather: unsupported board_size (odd 3..9)");
-    const int A = N * N + 2 * (N - 1) * (N - 1);
+    const int A = action_count(N);
     if (policy_size != A) return fail("aqg_augment_gather: policy_size is not the board's action count N^2 + 2 (N - 1)^2");
     if (n < 0) return fail("aqg_augment_gather: negative row count");
     if (n == 0) return 0;                   // nothing to write: the pointers are not looked at (an empty array's may be NULL)

@@ -17,6 +17,7 @@
 #include "aqg_common.hpp"
 #include "../../include/aqgnn.h"
 #include "launchers.hpp"
+#include "wave_ops.hpp"
 #include "train_adam.hpp"
 #include "train_driver.hpp"
 #include <type_traits>
@@ -50,8 +51,7 @@ __global__ __launch_bounds__(256) void train_general_prep_kernel(int V, int B, c
 
 // sum over the workgroup's 256 threads in a fixed order (a shuffle tree in each wave, then the 4 waves in order)
 __device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    v = wave_xor_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();

@@ -20,6 +20,7 @@
 #include "aqg_common.hpp"
 #include "../../include/aqgnn.h"
 #include "launchers.hpp"
+#include "wave_ops.hpp"
 #include "gcn_packed.hpp"
 
 namespace aqg {
@@ -457,8 +458,7 @@ __global__ __launch_bounds__(256) void gcn_heads_kernel(const float* __restrict_
         if (active && !active[b0 + r]) continue;
         float m = -INFINITY;
         for (int a = lane; a < A; a += 64) m = fmaxf(m, lg[r][a]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+        m = wave_xor_max(m);
         float e[4];
         float s = 0.f;
 #pragma unroll
@@ -467,8 +467,7 @@ __global__ __launch_bounds__(256) void gcn_heads_kernel(const float* __restrict_
             e[j] = (a < A) ? expf(lg[r][a] - m) : 0.f;
             s += e[j];
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        s = wave_xor_sum(s);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int a = lane + 64 * j;

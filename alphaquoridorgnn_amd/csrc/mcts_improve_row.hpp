@@ -21,27 +21,6 @@ namespace aqg {
 
 constexpr int IMP_ROUNDS = (MAX_LEGAL + WAVE - 1) / WAVE;      // 3 lane rounds cover a legal list
 
-__device__ __forceinline__ long long improve_wave_sum_ll(long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-__device__ __forceinline__ int improve_wave_max_i(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ double improve_wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-__device__ __forceinline__ double improve_wave_max_d(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    return v;
-}
-
 // one root's improved policy in the lanes of its wavefront: entry r of a lane is child r * 64 + lane of the root's block
 struct ImprovedRow {
     float pi[IMP_ROUNDS];           // pi' of the child, 0 past the count
@@ -95,10 +74,10 @@ __device__ __forceinline__ ImprovedRow improved_policy_row(const aqg_engine& e, 
         }
     }
     // ---- 1 .. 3: the visit totals, the root's network value, the mixed value (wave-uniform)
-    const long long nsum = improve_wave_sum_ll(nsum_part);
-    const int nmax = improve_wave_max_i(nmax_part);
-    const double vhat = __hiloint2double((int)root_cold.y, (int)root_cold.x) + improve_wave_sum_d(wsum_part);
-    const double pv = improve_wave_sum_d(pv_part), qv = improve_wave_sum_d(qv_part);
+    const long long nsum = wave_xor_sum(nsum_part);
+    const int nmax = wave_xor_max(nmax_part);
+    const double vhat = __hiloint2double((int)root_cold.y, (int)root_cold.x) + wave_xor_sum(wsum_part);
+    const double pv = wave_xor_sum(pv_part), qv = wave_xor_sum(qv_part);
     const double vmix = inside ? (pv > 0.0 ? (vhat + (double)nsum * (qv / pv)) / (1.0 + (double)nsum) : vhat) : 0.0;
     // ---- 4 .. 6: completed value, transform, softmax
     const double scale = (c_visit + (double)nmax) * c_scale;
@@ -112,7 +91,7 @@ __device__ __forceinline__ ImprovedRow improved_policy_row(const aqg_engine& e, 
         x[r] = in ? log((double)p[r]) + sigma : -INFINITY;
         m_part = fmax(m_part, x[r]);
     }
-    const double m = improve_wave_max_d(m_part);
+    const double m = wave_xor_max(m_part);
     const bool any = m > -INFINITY;                             // a prior above 0 exists (wave-uniform)
     double ex[IMP_ROUNDS];
     double s_part = 0.0;
@@ -121,7 +100,7 @@ __device__ __forceinline__ ImprovedRow improved_policy_row(const aqg_engine& e, 
         ex[r] = (any && x[r] > -INFINITY) ? exp(x[r] - m) : 0.0;
         s_part += ex[r];
     }
-    const double s = improve_wave_sum_d(s_part);
+    const double s = wave_xor_sum(s_part);
     ImprovedRow row;
 #pragma unroll
     for (int r = 0; r < IMP_ROUNDS; ++r) {

@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void engine_fake_eval_kernel(aqg_engine e) {
             rl[r] = rr; tot += rr;
         }
     }
-    tot = wave_sum_i(tot);
+    tot = wave_xor_sum(tot);
     float* pol = e.policy + (size_t)g * A;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -143,11 +143,6 @@ __global__ __launch_bounds__(256) void engine_fake_eval_kernel(aqg_engine e) {
 // the table only ever holds the network's own priors.
 // ------------------------------------------------------------------------------------------------
 constexpr int ROOT_NOISE_ATTEMPTS = 64;      // cap of the Marsaglia-Tsang rejection loop (acceptance is above 95 % per attempt)
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 // Gamma(alpha, 1) of one component's sub-stream, the recipe of aqgnn.h (engine.draw_root_noise is the same in numpy)
 __device__ __forceinline__ double root_noise_gamma(uint64_t key, double alpha) {
     const bool boost = alpha < 1.0;
@@ -186,7 +181,7 @@ __device__ __forceinline__ bool root_noise_eta(const aqg_engine& e, int g, int p
             if (i < cnt) gv[r] = root_noise_gamma(stream_key(key, (uint64_t)i), alpha);
         }
     }
-    const double S = wave_sum_d((gv[0] + gv[1]) + gv[2]);
+    const double S = wave_xor_sum((gv[0] + gv[1]) + gv[2]);
     if (!(S > 0.0 && S <= DBL_MAX)) return false;
 #pragma unroll
     for (int r = 0; r < 3; ++r) eta[r] = (float)(gv[r] / S);
@@ -212,9 +207,7 @@ __global__ __launch_bounds__(256) void engine_root_noise_kernel(aqg_engine e) {
         const uint8_t* ord = e.legal_order + (size_t)g * MAX_LEGAL;
 #pragma unroll
         for (int r = 0; r < 4; ++r) { const int a = lane + 64 * r; polbuf[w][a] = (a < A) ? pol[a] : 0.f; }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         float sum = 0.f;
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
@@ -222,7 +215,7 @@ __global__ __launch_bounds__(256) void engine_root_noise_kernel(aqg_engine e) {
             pl[r] = (i < cnt) ? polbuf[w][ord[i]] : 0.f;
             sum += pl[r];
         }
-        sum = wave_sum_f(sum);
+        sum = wave_xor_sum(sum);
         const float den = (sum != 0.f) ? sum : 1.f;
 #pragma unroll
         for (int r = 0; r < 3; ++r) pl[r] = pl[r] / den;

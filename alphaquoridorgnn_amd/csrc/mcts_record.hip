@@ -9,13 +9,6 @@
 
 namespace aqg {
 
-// orders a wavefront's LDS writes in front of its own later LDS reads (the pattern of replay_refresh_kernel)
-__device__ __forceinline__ void improve_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // The record launch (aqgnn.h, "recording completed-Q targets during self-play"): the same row, written dense by action id into the
 // history row engine_finish_move_kernel is about to fill -- slot g's game k = slot_game[g] at ply = game_plies[k] -- for every ACTIVE
 // slot whose ply is inside the history.  Behind the last step of the move's search and in front of the finish-move launch, on its
@@ -42,11 +35,11 @@ __global__ __launch_bounds__(256) void engine_record_improved_policy_kernel(aqg_
     float* __restrict__ mine = stage[wave];
 #pragma unroll
     for (int p = 0; p < PASSES; ++p) mine[p * WAVE + lane] = 0.0f;
-    improve_wave_sync();
+    wave_lds_sync();
 #pragma unroll
     for (int r = 0; r < IMP_ROUNDS; ++r)
         if (r * WAVE + lane < row.cnt && row.act[r] < (uint32_t)A) mine[row.act[r]] = row.pi[r];
-    improve_wave_sync();
+    wave_lds_sync();
     float* __restrict__ out = hist_policy + ((size_t)k * e.max_plies + ply) * A;
 #pragma unroll
     for (int p = 0; p < PASSES; ++p) {

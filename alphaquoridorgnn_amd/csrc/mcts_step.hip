@@ -260,9 +260,7 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
             if (!HEADS) {                        // (HEADS: the row is in polbuf already, behind a workgroup barrier)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) polbuf[lane + 64 * r] = polr[r];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
             }
             if (!PB) {                           // (PB: the policy workgroup's, policy_beside_role)
                 float sum = 0.f;
@@ -272,7 +270,7 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
                     pl[r] = (i < cnt_new) ? polbuf[oa[r]] : 0.f;
                     sum += pl[r];
                 }
-                sum = wave_sum_f(sum);
+                sum = wave_xor_sum(sum);
                 const float den = (sum != 0.f) ? sum : 1.f;
 #pragma unroll
                 for (int r = 0; r < 3; ++r) pl[r] = pl[r] / den;
@@ -718,7 +716,7 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
 
 // The policy workgroup of eight games (engine_step_fast_kernel<.., PB>, option "policy_beside_step"; workgroup `blk` of the launch's policy
 // range, same grouping as the step workgroups): the policy half of heads_body for the games' leaves, then -- one wave per game -- the
-// expansion the one-workgroup form does in game_step_fast: the gather at the legal actions, wave_sum_f, the division, the child records,
+// expansion the one-workgroup form does in game_step_fast: the gather at the legal actions, wave_xor_sum, the division, the child records,
 // in the same order of operations.  Its per-game inputs are the job record the evaluation launch's search left (leaf_legal_role,
 // mcts_eval.hip), legal_order[g] and the pooled row: nothing the step workgroups of this launch write.  leaf_flag, legal_count and
 // node_count, which they overwrite, are not read here.  Of the first child it writes p, action and cp only (see PB above).
@@ -758,7 +756,7 @@ __device__ __forceinline__ void policy_beside_role(const aqg_engine& e, int blk,
         pl[r] = (i < cnt_new) ? row[oa[r] & 0xFF] : 0.f;
         sum += pl[r];
     }
-    sum = wave_sum_f(sum);
+    sum = wave_xor_sum(sum);
     const float den = (sum != 0.f) ? sum : 1.f;
 #pragma unroll
     for (int r = 0; r < 3; ++r) pl[r] = pl[r] / den;

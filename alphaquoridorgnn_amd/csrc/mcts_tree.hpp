@@ -1,22 +1,12 @@
 // mcts_tree.hpp -- what the engine's units (mcts_step.hip, mcts_eval.hip, mcts_move.hip) share: of a game's tree pool the node record,
-// its accessors and the wave sums; the initial position; a game's state as wave-uniform scalars (uniform_state).  __forceinline__ device code and declarations only.  The including unit
+// its accessors and the wave sums (wave_ops.hpp); the initial position; a game's state as wave-uniform scalars (uniform_state).  __forceinline__ device code and declarations only.  The including unit
 // sets `#pragma clang fp contract(off)` in front of this header: q_of and the backup are PUCT arithmetic.
 #pragma once
 #include "aqg_common.hpp"
+#include "wave_ops.hpp"
 #include "../../include/aqgnn.h"
 
 namespace aqg {
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // One reference-"Node" (pv_mcts.py:24-31) per 32-byte record: the statistics, the prior, the action that led here and
 // the child range sit in one cache sector, so a descent level is ONE dependent load round (the chosen child's

@@ -51,6 +51,8 @@ inline R with_board_size(int N, R on_unsupported, F&& f) {
     }
 }
 inline bool board_size_supported(int N) { return with_board_size(N, false, [](auto) { return true; }); }
+// the action count of an N x N board on the host: N^2 pawn targets and two orientations of (N - 1)^2 wall slots (Geo<N>::A in a kernel)
+constexpr int action_count(int N) { return N * N + 2 * (N - 1) * (N - 1); }
 
 struct QState {
     uint64_t hw;     // bit i: walls[i] == 1 (horizontal), mover's frame

@@ -28,6 +28,7 @@
 // 16-byte aligned have not been through the bit-for-bit tests on the GPU, and this form has, at every edge.
 #include "aqg_common.hpp"
 #include "launchers.hpp"
+#include "wave_ops.hpp"
 
 #ifdef __FAST_MATH__
 #error "replay.hip: pi = v / tot must be the correctly rounded f32 division (no fast-math)"
@@ -40,12 +41,6 @@ namespace aqg {
 constexpr int RPL_WAVES = 4;
 constexpr int RPL_GROUP = 4;    // rows a wavefront loads before it stores any (rows per wavefront group)
 constexpr int RPL_ROWS = RPL_WAVES * RPL_GROUP;     // source rows of one workgroup
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 template <int N, bool BLEND>
 __global__ __launch_bounds__(RPL_WAVES * WAVE) void replay_append_kernel(
@@ -99,7 +94,7 @@ __global__ __launch_bounds__(RPL_WAVES * WAVE) void replay_append_kernel(
                 int part = 0;
 #pragma unroll
                 for (int p = 0; p < PI_PASSES; ++p) part += (int)pv[g][p];
-                tot = (float)wave_sum_int(part);                // exact: < 2^24
+                tot = (float)wave_xor_sum(part);                // exact: < 2^24
             }
 #pragma unroll
             for (int p = 0; p < PI_PASSES; ++p) {
@@ -114,16 +109,11 @@ __global__ __launch_bounds__(RPL_WAVES * WAVE) void replay_append_kernel(
     }
 }
 
-static bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + b_bytes && y < x + a_bytes;
-}
-
 int launch_replay_append(int N, int policy_size, const uint8_t* states72, const uint16_t* visits, const int8_t* z_i8, const float* pi,
                          const float* z_f32, int n, int capacity, int head, uint8_t* ring72, float* ring_pi, float* ring_z,
                          hipStream_t st, const float* search_value, float blend, bool policy_form) {
     if (!board_size_supported(N)) return fail("aqg_replay_append: unsupported board_size (odd 3..9)");
-    const int A = N * N + 2 * (N - 1) * (N - 1);
+    const int A = action_count(N);
     if (policy_size != A) return fail("aqg_replay_append: policy_size is not the board's action count N^2 + 2 (N - 1)^2");
     if (n < 0) return fail("aqg_replay_append: negative row count");
     if (capacity < 1) return fail("aqg_replay_append: capacity must be >= 1");

@@ -38,6 +38,7 @@
 // 34.5 us at 5x5; without the flush the two were equal.  Neither is the one kept.
 #include "aqg_common.hpp"
 #include "launchers.hpp"
+#include "wave_ops.hpp"
 
 #ifdef __FAST_MATH__
 #error "replay_merge.hip: the mean must be the correctly rounded f32 division (no fast-math)"
@@ -69,15 +70,6 @@ __device__ __forceinline__ uint64_t place_multiplier(int k) {
 }
 __device__ __forceinline__ bool is_key_byte(int k) { return k != 68 && k != 69 && k != 71; }
 
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off);
-        v += ((uint64_t)hi << 32) | lo;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(MRG_WAVES * WAVE) void position_keys_kernel(const uint8_t* __restrict__ states72,
                                                                         const int64_t* __restrict__ index, int n,
                                                                         int64_t* __restrict__ keys) {
@@ -98,7 +90,7 @@ __global__ __launch_bounds__(MRG_WAVES * WAVE) void position_keys_kernel(const u
     for (int g = 0; g < MRG_GROUP; ++g) {
         const int q = wave * MRG_GROUP + g;
         if (q >= rows) continue;                                // wave-uniform: the reduction runs on whole wavefronts
-        const uint64_t h = wave_sum_u64(((uint64_t)b[g][0] + 1) * m0 + ((uint64_t)b[g][1] + 1) * m1);
+        const uint64_t h = wave_xor_sum(((uint64_t)b[g][0] + 1) * m0 + ((uint64_t)b[g][1] + 1) * m1);
         if (lane == 0) keys[first + q] = (int64_t)splitmix64(h);
     }
 }
@@ -314,11 +306,6 @@ __global__ __launch_bounds__(MRG_WAVES * WAVE) void merge_runs_kernel(
     }
 }
 
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + b_bytes && y < x + a_bytes;
-}
-
 }  // namespace
 
 int launch_replay_position_keys(const uint8_t* states72, const int64_t* index, int n, int64_t* keys, hipStream_t st) {
@@ -347,7 +334,7 @@ int launch_replay_run_heads(const uint8_t* states72, const int64_t* perm, int n,
 
 size_t replay_merge_workspace_floats(int N, int n, int u) {
     if (!board_size_supported(N) || n < 0 || u < 0 || u > n || n - u < MRG_CHUNK) return 0;    // no run longer than one chunk
-    const size_t A = (size_t)(N * N + 2 * (N - 1) * (N - 1));
+    const size_t A = (size_t)action_count(N);
     return 2 * (((size_t)n + MRG_CHUNK - 1) / MRG_CHUNK) * (A + 1);
 }
 
@@ -355,7 +342,7 @@ int launch_replay_merge_runs(int N, int policy_size, const uint8_t* states72, co
                              const int64_t* starts, int n, int u, uint8_t* out72, float* out_pi, float* out_z, int32_t* count,
                              float* workspace, size_t workspace_floats, hipStream_t st) {
     if (!board_size_supported(N)) return fail("aqg_replay_merge_runs: unsupported board_size (odd 3..9)");
-    const int A = N * N + 2 * (N - 1) * (N - 1);
+    const int A = action_count(N);
     if (policy_size != A) return fail("aqg_replay_merge_runs: policy_size is not the board's action count N^2 + 2 (N - 1)^2");
     if (n < 0 || u < 0) return fail("aqg_replay_merge_runs: negative row count");
     if (u > n) return fail("aqg_replay_merge_runs: more runs than rows (u > n)");

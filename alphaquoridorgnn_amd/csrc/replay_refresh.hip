@@ -21,6 +21,7 @@
 // id with A.  Every loop is bounded by a constant.
 #include "aqg_common.hpp"
 #include "launchers.hpp"
+#include "wave_ops.hpp"
 #include <cfloat>
 
 #ifdef __FAST_MATH__
@@ -35,19 +36,6 @@ constexpr int RFR_WAVES = 4;
 constexpr int RFR_GROUP = 4;    // rows a wavefront loads before it stores any
 constexpr int RFR_ROWS = RFR_WAVES * RFR_GROUP;     // source rows of one workgroup
 constexpr int RFR_SRC_PASSES = (MAX_LEGAL + WAVE - 1) / WAVE;      // 3 lane rounds cover a legal list
-
-__device__ __forceinline__ int refresh_wave_sum_int(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// orders a wavefront's LDS writes in front of its own later LDS reads (the pattern of engine_root_noise_kernel)
-__device__ __forceinline__ void refresh_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // POLICY (aqg_replay_refresh_policy; aqgnn.h, "completed-Q policy targets"): the source words are f32 policy entries, not counts -- they
 // arrive through the same loads as their bits and are copied VERBATIM to their action ids: no total, no division.  A row is written
@@ -107,7 +95,7 @@ __global__ __launch_bounds__(RFR_WAVES * WAVE) void replay_refresh_kernel(
                 if (p * WAVE + lane >= c[g]) v[g][p] = 0;       // past the count (and every entry of a row with count <= 0)
                 part += v[g][p];
             }
-            const int t = refresh_wave_sum_int(part);
+            const int t = wave_xor_sum(part);
             ok[g] = c[g] > 0 && c[g] <= MAX_LEGAL && t > 0 && s[g] >= 0 && s[g] < (int64_t)capacity;
             tot[g] = (float)t;                                  // exact: < 2^24
         }
@@ -117,7 +105,7 @@ __global__ __launch_bounds__(RFR_WAVES * WAVE) void replay_refresh_kernel(
     for (int g = 0; g < RFR_GROUP; ++g)
 #pragma unroll
         for (int p = 0; p < PI_PASSES; ++p) stage[wave][g][p * WAVE + lane] = 0.f;
-    refresh_wave_sync();
+    wave_lds_sync();
 #pragma unroll
     for (int g = 0; g < RFR_GROUP; ++g) {
         if (!ok[g]) continue;
@@ -127,7 +115,7 @@ __global__ __launch_bounds__(RFR_WAVES * WAVE) void replay_refresh_kernel(
             if (j < c[g] && a[g][p] < (uint32_t)A) stage[wave][g][a[g][p]] = POLICY ? __int_as_float(v[g][p]) : (float)v[g][p] / tot[g];
         }
     }
-    refresh_wave_sync();
+    wave_lds_sync();
     // ---- each row stored once, lane-contiguous; the value target by the row's first lane
 #pragma unroll
     for (int g = 0; g < RFR_GROUP; ++g) {
@@ -146,11 +134,6 @@ __global__ __launch_bounds__(RFR_WAVES * WAVE) void replay_refresh_kernel(
     }
 }
 
-static bool refresh_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + b_bytes && y < x + a_bytes;
-}
-
 // both forms of the launch behind one set of checks: `rows` is visits (i32) or, POLICY, the f32 policy rows read through the same loads
 template <bool POLICY>
 static int refresh_launch(int N, int policy_size, const int32_t* rows, const uint8_t* actions, const int32_t* count,
@@ -158,7 +141,7 @@ static int refresh_launch(int N, int policy_size, const int32_t* rows, const uin
                           float* ring_z, hipStream_t st) {
     const char* what = POLICY ? "aqg_replay_refresh_policy" : "aqg_replay_refresh";
     if (!board_size_supported(N)) return fail(what, "unsupported board_size (odd 3..9)");
-    const int A = N * N + 2 * (N - 1) * (N - 1);
+    const int A = action_count(N);
     if (policy_size != A) return fail(what, "policy_size is not the board's action count N^2 + 2 (N - 1)^2");
     if (n < 0) return fail(what, "negative row count");
     if (capacity < 1) return fail(what, "capacity must be >= 1");
@@ -175,9 +158,9 @@ static int refresh_launch(int N, int policy_size, const int32_t* rows, const uin
     const size_t src_bytes[5] = {(size_t)MAX_LEGAL * sizeof(int32_t), (size_t)MAX_LEGAL, sizeof(int32_t), sizeof(int64_t), sizeof(float)};
     for (int o = 0; o < 2; ++o)
         for (int i = 0; i < 5; ++i)
-            if (refresh_overlap(rings[o], (size_t)capacity * ring_bytes[o], srcs[i], (size_t)n * src_bytes[i]))
+            if (overlap(rings[o], (size_t)capacity * ring_bytes[o], srcs[i], (size_t)n * src_bytes[i]))
                 return fail(what, "a ring overlaps a source");
-    if (refresh_overlap(rings[0], (size_t)capacity * ring_bytes[0], rings[1], (size_t)capacity * ring_bytes[1]))
+    if (overlap(rings[0], (size_t)capacity * ring_bytes[0], rings[1], (size_t)capacity * ring_bytes[1]))
         return fail(what, "ring_pi overlaps ring_z");
     const dim3 grid((unsigned)(((size_t)n + RFR_ROWS - 1) / RFR_ROWS)), block(RFR_WAVES * WAVE);
     return for_board_size(N, [&](auto nn) {

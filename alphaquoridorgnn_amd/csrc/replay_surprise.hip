@@ -22,6 +22,7 @@
 #include "aqg_common.hpp"
 #include "counter_rng.hpp"
 #include "launchers.hpp"
+#include "wave_ops.hpp"
 #include <cfloat>
 #include <cmath>
 
@@ -41,12 +42,6 @@ constexpr int SPR_MAX_ROWS = 1 << 24;      // m at most: S = sum q < 2^24 * 2^27
 constexpr float SPR_TINY = 0x1.0p-126f;    // the least p a logarithm is taken of
 constexpr double SPR_K_MAX = 88.0;         // > 126 ln 2, the most a row whose target sums to 1 can reach: q < 2^27 whatever the row holds
 constexpr double SPR_Q_SCALE = 0x1.0p20;
-
-__device__ __forceinline__ double surprise_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 template <int N>
 __global__ __launch_bounds__(SPR_WAVES * WAVE) void replay_surprise_rows_kernel(
@@ -92,7 +87,7 @@ __global__ __launch_bounds__(SPR_WAVES * WAVE) void replay_surprise_rows_kernel(
                 acc = acc + term;
             }
         }
-        const double kl = surprise_wave_sum(acc);
+        const double kl = wave_xor_sum(acc);
         const bool ok = r[g] >= 0 && r[g] < (int64_t)rows && __ballot(bad) == 0 && __ballot(some) != 0;
         const float kk = ok ? (float)fmin(fmax(kl, 0.0), SPR_K_MAX) : 0.f;
         if (lane == 0) {
@@ -124,16 +119,11 @@ __global__ __launch_bounds__(SPR_LANES) void replay_surprise_counts_kernel(
     count[j] = (int32_t)fmin(c, (double)max_copies);
 }
 
-static bool surprise_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + b_bytes && y < x + a_bytes;
-}
-
 int launch_replay_surprise_rows(int N, int policy_size, const float* net_policy, const float* ring_pi, const int64_t* index, int rows,
                                 int m, int offset, int n, float* k, int32_t* q, hipStream_t st) {
     const char* what = "aqg_replay_surprise_rows";
     if (!board_size_supported(N)) return fail(what, "unsupported board_size (odd 3..9)");
-    const int A = N * N + 2 * (N - 1) * (N - 1);
+    const int A = action_count(N);
     if (policy_size != A) return fail(what, "policy_size is not the board's action count N^2 + 2 (N - 1)^2");
     if (m < 0 || m > SPR_MAX_ROWS) return fail(what, "m out of range (0 .. 2^24 rows)");
     if (rows < 0) return fail(what, "negative row count of the ring");
@@ -146,8 +136,8 @@ int launch_replay_surprise_rows(int N, int policy_size, const float* net_policy,
     const size_t src_bytes[3] = {(size_t)n * A * sizeof(float), (size_t)(index ? 1 : rows) * A * sizeof(float), (size_t)m * sizeof(int64_t)};
     for (int o = 0; o < 2; ++o)
         for (int i = 0; i < 3; ++i)
-            if (surprise_overlap(outs[o], (size_t)m * 4, srcs[i], src_bytes[i])) return fail(what, "an output overlaps a source");
-    if (surprise_overlap(k, (size_t)m * 4, q, (size_t)m * 4)) return fail(what, "k overlaps q");
+            if (overlap(outs[o], (size_t)m * 4, srcs[i], src_bytes[i])) return fail(what, "an output overlaps a source");
+    if (overlap(k, (size_t)m * 4, q, (size_t)m * 4)) return fail(what, "k overlaps q");
     const dim3 grid((unsigned)(((size_t)n + SPR_ROWS - 1) / SPR_ROWS)), block(SPR_WAVES * WAVE);
     return for_board_size(N, [&](auto nn) {
         hipLaunchKernelGGL((replay_surprise_rows_kernel<decltype(nn)::value>), grid, block, 0, st, net_policy, ring_pi, index, rows, offset, n,
@@ -168,7 +158,7 @@ int launch_replay_surprise_counts(const int32_t* q, const int64_t* index, const 
     const void* srcs[3] = {q, index, total};
     const size_t src_bytes[3] = {(size_t)m * sizeof(int32_t), (size_t)m * sizeof(int64_t), sizeof(int64_t)};
     for (int i = 0; i < 3; ++i)
-        if (surprise_overlap(count, (size_t)m * sizeof(int32_t), srcs[i], src_bytes[i])) return fail(what, "count overlaps a source");
+        if (overlap(count, (size_t)m * sizeof(int32_t), srcs[i], src_bytes[i])) return fail(what, "count overlaps a source");
     const dim3 grid((unsigned)(((size_t)m + SPR_LANES - 1) / SPR_LANES)), block(SPR_LANES);
     hipLaunchKernelGGL(replay_surprise_counts_kernel, grid, block, 0, st, q, index, total, m, (double)expected_rows, uniform_share,
                        max_copies, stream_key(seed, update), count);

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .constants import BOARD_SIZE, board_params
+from .constants import BOARD_SIZE, board_params, num_actions
 from .evaluators import BINDINGS
 
 # The engine's companions, one concern per module, importable from this path as well: the tests, README.md and include/aqgnn.h
@@ -103,7 +103,7 @@ class BatchedSelfPlay:
         self.dev = _lib.require_gpu(device)
         self.lib = _lib.load()
         self.N = board_size
-        self.A = board_size ** 2 + 2 * (board_size - 1) ** 2
+        self.A = num_actions(board_size)
         self.num_walls, self.plies_for_draw = board_params(board_size)
         self.G, self.sims = int(num_games), int(sims)
         # quota > G: the slots are refilled -- a slot whose game has ended takes the next game not yet handed out (in slot

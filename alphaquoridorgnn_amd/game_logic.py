@@ -10,15 +10,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from .constants import BOARD_SIZE, NUM_WALLS, NUM_PLIES_FOR_DRAW
+from .constants import BOARD_SIZE, NUM_WALLS, NUM_PLIES_FOR_DRAW, num_actions  # noqa: F401
 
 MOVEMENT_DIRECTIONS = [(-1, 0), (1, 0), (0, -1), (0, 1)]  # U, D, L, R (game_logic.py:11)
 STATE72 = 72
 MAX_LEGAL = _lib.MAX_LEGAL
-
-
-def num_actions(board_size=BOARD_SIZE):
-    return board_size ** 2 + 2 * (board_size - 1) ** 2
 
 
 # ------------------------------------------------------------------ batched device API

@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from .constants import board_params
 from .counter_rng import counter_uniform, stream_key
-from .replay import KEY_BYTES
+from .replay_reference import KEY_BYTES
 
 CANDIDATES_PER_ROW = 16        # random_book looks at 16 * count candidates at most
 

@@ -22,21 +22,17 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import game_logic
-from .constants import BOARD_SIZE
+from .constants import BOARD_SIZE, num_actions as policy_size_of
 
 NUM_FILTERS = 128          # pv_network_cnn.py:14
 NUM_RESIDUAL_BLOCKS = 16   # :15
 INPUT_SHAPE = (6, BOARD_SIZE, BOARD_SIZE)                           # :16
-POLICY_OUTPUT_SIZE = BOARD_SIZE ** 2 + 2 * (BOARD_SIZE - 1) ** 2   # :17
+POLICY_OUTPUT_SIZE = policy_size_of(BOARD_SIZE)                    # :17
 CNN_NETWORK_PATH = f"models/CNN/{BOARD_SIZE}x{BOARD_SIZE}/"        # the reference's PV_NETWORK_PATH with PV_NETWORK_NAME = 'CNN'
 
 # inclusive bounds of the shapes the HIP kernels take (CNNNetwork raises ValueError outside them)
 SHAPE_LIMITS = {"num_filters": (1, 512), "num_residual_blocks": (0, 40), "policy_output_size": (1, 4096)}
 BOARD_SIZES = (3, 5, 7, 9)
-
-
-def policy_size_of(board_size):
-    return board_size ** 2 + 2 * (board_size - 1) ** 2
 
 
 # Convolutional layer with batch normalization (pv_network_cnn.py:21-31)

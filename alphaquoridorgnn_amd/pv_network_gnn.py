@@ -26,13 +26,13 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .constants import BOARD_SIZE, PV_NETWORK_PATH
+from .constants import BOARD_SIZE, PV_NETWORK_PATH, num_actions
 from . import game_logic
 
 NUM_FEATURES = 6      # pv_network_gnn.py:17
 HIDDEN_DIM = 128      # :18
 NUM_GCN_LAYERS = 3    # :19
-POLICY_OUTPUT_SIZE = BOARD_SIZE ** 2 + 2 * (BOARD_SIZE - 1) ** 2  # :20
+POLICY_OUTPUT_SIZE = num_actions(BOARD_SIZE)  # :20
 
 # inclusive bounds of the shapes the width-generic kernels take (GraphPolicyValueNetwork raises ValueError outside them)
 SHAPE_LIMITS = {"num_features": (1, 1024), "hidden_dim": (2, 1024), "num_gcn_layers": (1, 32), "policy_output_size": (1, 4096)}

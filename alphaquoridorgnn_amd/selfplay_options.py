@@ -3,6 +3,7 @@ as the library does it, the seeds an engine derives when it is given none, and t
 import numpy as np
 
 from . import _lib
+from .constants import num_actions
 from .counter_rng import GOLDEN, MASK64, mix64
 
 ROOT_NOISE_ATTEMPTS = 64      # cap of the gamma sampler's rejection loop (csrc/mcts_move.hip ROOT_NOISE_ATTEMPTS)
@@ -10,7 +11,7 @@ ROOT_NOISE_ATTEMPTS = 64      # cap of the gamma sampler's rejection loop (csrc/
 
 def default_root_noise_alpha(board_size):
     """The usual "10 / typical number of legal moves" rule, with the board's action count N^2 + 2 (N - 1)^2 for the moves."""
-    return 10.0 / (board_size ** 2 + 2 * (board_size - 1) ** 2)
+    return 10.0 / num_actions(board_size)
 
 
 def check_root_noise(eps, alpha):

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .constants import PV_NETWORK_PATH, BOARD_SIZE
+from .constants import PV_NETWORK_PATH, BOARD_SIZE, num_actions
 from .pv_network_gnn import STATE_DICT_KEYS, HIDDEN_DIM, NUM_FEATURES, load_network, pack_states
 
 NUM_EPOCH = 100    # train_network.py:14
@@ -173,7 +173,7 @@ def _augment_launch(board_size, states72, pi, z, order, mirror):
     n = rows if order is None else int(order.shape[0])
     flips, use_seed, seed, epoch = (None, 0, 0, 0) if mirror is None else _mirror_arguments(mirror, rows, dev)
     outs = [None if x is None else torch.empty((n,) + tuple(x.shape[1:]), dtype=x.dtype, device=dev) for x in (states72, pi, z)]
-    A = board_size ** 2 + 2 * (board_size - 1) ** 2
+    A = num_actions(board_size)
     _lib.check(_lib.load().aqg_augment_gather(board_size, A, _lib.ptr(states72), _lib.ptr(pi), _lib.ptr(z), _lib.ptr(order),
                                               _lib.ptr(flips), use_seed, seed, epoch, n, _lib.ptr(outs[0]), _lib.ptr(outs[1]),
                                               _lib.ptr(outs[2]), _lib.stream_ptr(dev)), "aqg_augment_gather")
@@ -191,7 +191,7 @@ def augment_gather(states72, pi, z, order=None, flips=None, seed=None, epoch=0, 
         raise ValueError("augment_gather: at least one of states72, pi, z is needed")
     dev = _lib.require_gpu(given[0].device)
     rows = int(given[0].shape[0])
-    A = board_size ** 2 + 2 * (board_size - 1) ** 2
+    A = num_actions(board_size)
     for x, name, dtype, tail in ((states72, "states72", torch.uint8, (72,)), (pi, "pi", torch.float32, (A,)), (z, "z", torch.float32, ())):
         if x is not None and (x.device != dev or x.dtype != dtype or tuple(x.shape) != (rows,) + tail):
             raise ValueError(f"augment_gather: {name} must be a {dtype} {[rows, *tail]} tensor on {dev} ({board_size}x{board_size} board)")
