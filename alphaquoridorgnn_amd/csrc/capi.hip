@@ -628,4 +628,9 @@ int aqg_replay_surprise_counts(const int32_t* q, const int64_t* index, const int
                                          (hipStream_t)stream);
 }
 
+int aqg_lambda_values(int quota, int hp, const int32_t* game_plies, const int8_t* game_result, const uint8_t* game_done,
+                      const float* hist_value, float lambda, float* out, void* stream) {
+    return launch_lambda_values(quota, hp, game_plies, game_result, game_done, hist_value, lambda, out, (hipStream_t)stream);
+}
+
 }  // extern "C"

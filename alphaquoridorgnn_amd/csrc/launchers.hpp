@@ -276,4 +276,8 @@ int launch_replay_surprise_rows(int N, int policy_size, const float* net_policy,
 int launch_replay_surprise_counts(const int32_t* q, const int64_t* index, const int64_t* total, int m, long long expected_rows,
                                   double uniform_share, int max_copies, uint64_t seed, uint64_t update, int32_t* count, hipStream_t st);
 
+// ---- value_targets.hip
+int launch_lambda_values(int quota, int hp, const int32_t* game_plies, const int8_t* game_result, const uint8_t* game_done,
+                         const float* hist_value, float lambda, float* out, hipStream_t st);
+
 }  // namespace aqg

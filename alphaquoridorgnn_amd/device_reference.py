@@ -2,7 +2,7 @@
 import numpy as np
 
 from .counter_rng import counter_uniform, stream_key
-from .selfplay_options import ROOT_NOISE_ATTEMPTS, check_completed_q
+from .selfplay_options import ROOT_NOISE_ATTEMPTS, check_completed_q, check_value_lambda
 
 
 def draw_resign_enabled(seed, k, disable_fraction=0.1):
@@ -10,6 +10,42 @@ def draw_resign_enabled(seed, k, disable_fraction=0.1):
     the draw of engine_finish_move_kernel in numpy (include/aqgnn.h, "resignation").  k may be an array of game indices."""
     out = counter_uniform(stream_key(int(seed), np.asarray(k, dtype=np.int64)), 0) >= float(disable_fraction)
     return bool(out) if np.ndim(k) == 0 else out
+
+
+def lambda_values_reference(game_plies, game_result, game_done, hist_value, lam, out):
+    """aqg_lambda_values in numpy, on host arrays, in place (include/aqgnn.h, "lambda-return value targets"): game_plies int [quota],
+    game_result int [quota] (-1 / 0 / 1 from the side of ply 0), game_done [quota], hist_value float32 [quota, hp], out float32
+    [quota, hp].  Game k is processed iff game_done[k] != 0 and 1 <= game_plies[k] <= hp; out[k, t] is then written for
+    t < game_plies[k] and nothing else is.  With a = float32(1) - lam, from the last ply T - 1 down,
+    G_t = a * q_t + lam * (-G_{t+1}), and lam * z_{T-1} at the top -- two f32 products and one f32 sum per ply, each rounded, no
+    fused multiply-add; z_t is float32(r) at an even ply and -float32(r) at an odd one.  Returns out."""
+    lam = np.float32(check_value_lambda(lam))
+    a = np.float32(1.0) - lam
+    q, plies = np.asarray(hist_value), np.asarray(game_plies).astype(np.int64)
+    if q.dtype != np.float32 or q.ndim != 2 or q.shape[1] < 1:
+        raise ValueError("lambda_values_reference: hist_value must be float32 [quota, hp] with hp >= 1")
+    quota, hp = q.shape
+    if not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.shape != q.shape:
+        raise ValueError("lambda_values_reference: out must be a float32 array of hist_value's shape")
+    if any(np.asarray(x).shape != (quota,) for x in (game_plies, game_result, game_done)):
+        raise ValueError("lambda_values_reference: game_plies, game_result and game_done must hold one entry per row of hist_value")
+    live = np.nonzero((np.asarray(game_done) != 0) & (plies >= 1) & (plies <= hp))[0]
+    if live.size == 0:
+        return out
+    T = plies[live]
+    r = np.asarray(game_result)[live].astype(np.float32)
+    z_last = np.where((T - 1) % 2 == 0, r, -r).astype(np.float32)          # -float32(0) is -0.0, as on the device
+    after = np.zeros(live.shape, dtype=np.float32)                          # -G_{t+1}, or z_{T-1} at a game's last ply
+    with np.errstate(all="ignore"):         # a shorter game's columns past its end are computed and dropped, whatever they hold
+        for t in range(int(T.max()) - 1, -1, -1):
+            after = np.where(T - 1 == t, z_last, after)
+            x = (a * q[live, t]).astype(np.float32)
+            y = (lam * after).astype(np.float32)
+            g = (x + y).astype(np.float32)
+            on = t < T
+            out[live[on], t] = g[on]
+            after = -g
+    return out
 
 
 def root_noise_stream_key(seed, k, ply):

@@ -24,10 +24,10 @@ from .evaluators import BINDINGS
 # match loop.
 from .counter_rng import GOLDEN as _GOLDEN, MASK64, mix64 as _mix64_int  # noqa: F401
 from .device_reference import (NODE_DTYPE, draw_resign_enabled, draw_root_noise, improved_policy_reference,  # noqa: F401
-                               keep_subtree_reference, root_improved_policy_reference, root_noise_stream_key)
+                               keep_subtree_reference, lambda_values_reference, root_improved_policy_reference, root_noise_stream_key)
 from .resign_calibration import resign_false_positives, resign_stats_of, suggest_from_arrays, suggest_resign_threshold  # noqa: F401
 from .selfplay_options import (ROOT_NOISE_ATTEMPTS, check_completed_q, check_policy_record, check_resign, check_root_noise, check_target_options,  # noqa: F401
-                               check_start_table, check_temperature, check_tree_reuse, default_resign_seed, default_root_noise_alpha,
+                               check_start_table, check_temperature, check_tree_reuse, check_value_lambda, default_resign_seed, default_root_noise_alpha,
                                default_root_noise_seed, set_noise_seeds, set_start_indices)
 from .two_engine_match import TwoEngineMatch  # noqa: F401
 
@@ -245,6 +245,7 @@ class BatchedSelfPlay:
         if self.resign is not None:
             _lib.check(self.lib.aqg_engine_reset_resign(ctypes.byref(self.e), ctypes.byref(self.resign), self._stream()), "aqg_engine_reset_resign")
         self.moves_done = 0
+        self._applied_moves = False        # no history row without a search value yet (history_lambda_values)
 
     # ------------------------------------------------------------------ resignation
     def set_resign_threshold(self, threshold):
@@ -374,6 +375,7 @@ class BatchedSelfPlay:
             _lib.check(self.lib.aqg_engine_apply_actions(ctypes.byref(self.e), _lib.ptr(actions), self._stream()), "aqg_engine_apply_actions")
         if self.tree_reuse:
             self._forget_kept_trees()      # the roots changed without a search: the next move starts from fresh trees
+        self._applied_moves = True
         self.moves_done += 1
 
     # ------------------------------------------------------------------ external evaluator (prior_mode 2)
@@ -553,6 +555,26 @@ class BatchedSelfPlay:
         if not self.record_search_value:
             raise ValueError("history_values needs record_search_value=True")
         return self.t["hist_value"][self._history_valid()[0]]
+
+    def history_lambda_values(self, lam):
+        """The lambda-returns of the recorded search values, float32 [P], row-aligned with history_tensors() and history_values()
+        (include/aqgnn.h, "lambda-return value targets"; lambda_values_reference is the statement): row t of a finished game holds
+        G_t = (1 - lam) q_t + lam (-G_{t+1}), bootstrapped into the game's outcome at its last ply -- q_t at lam = 0, z_t at lam = 1.
+        One aqg_lambda_values launch into a fresh [quota, max_plies] tensor, then the mask of the finished games' rows.  lam: a
+        float32 in [0, 1] (check_value_lambda).  Needs record_search_value; ValueError once apply_actions() has played a move since
+        the last reset(): such a row holds no search value, and 0 in its place would be a silent wrong target."""
+        lam = check_value_lambda(lam)
+        if not self.record_search_value:
+            raise ValueError("history_lambda_values needs record_search_value=True")
+        if self._applied_moves:
+            raise ValueError("history_lambda_values: apply_actions() has played moves nobody searched since the last reset(); their "
+                             "rows hold no search value")
+        q = self.t["hist_value"]
+        out = torch.empty_like(q)                 # every float the mask below keeps is written by the launch
+        _lib.check(self.lib.aqg_lambda_values(q.shape[0], q.shape[1], _lib.ptr(self.t["game_plies"]), _lib.ptr(self.t["game_result"]),
+                                              _lib.ptr(self.t["game_done"]), _lib.ptr(q), lam, _lib.ptr(out), self._stream()),
+                   "aqg_lambda_values")
+        return out[self._history_valid()[0]]
 
     def history_policies(self):
         """The recorded completed-Q policy targets, float32 [P, A], row-aligned with history_tensors(): dense by action id, 0 on
@@ -770,6 +792,11 @@ class MultiSetSelfPlay:
     def history_values(self):
         """The sets' history_values() in set order: float32 [P], row-aligned with history_tensors()."""
         return self._joined(lambda eng: (eng.history_values(),))[0]
+
+    def history_lambda_values(self, lam):
+        """The sets' history_lambda_values(lam) in set order: float32 [P], row-aligned with history_tensors()."""
+        lam = check_value_lambda(lam)             # before any set launches
+        return self._joined(lambda eng: (eng.history_lambda_values(lam),))[0]
 
     def history_policies(self):
         """The sets' history_policies() in set order: float32 [P, A], row-aligned with history_tensors()."""

@@ -19,7 +19,7 @@ from .engine import BatchedSelfPlay, MultiSetSelfPlay, gather_history, gather_re
 from .pv_network_gnn import GNNNetwork, POLICY_OUTPUT_SIZE, load_network
 from .pv_network_cnn import CNNNetwork
 from .reanalyse import check_reanalyse_options, eligible_rows, reanalyse
-from .selfplay_options import check_policy_record, check_policy_target
+from .selfplay_options import check_policy_record, check_policy_target, check_value_lambda
 from .replay import blend_targets, check_value_blend
 from .resign_calibration import resign_stats_of, suggest_from_arrays
 
@@ -33,6 +33,9 @@ SP_ROOT_NOISE_ALPHA = None   # None = 10 / (N^2 + 2 (N - 1)^2), the "10 / typica
 # (1 - L) z + L q, q the search value of its root -- a float32 in the window and, with the same bits, a float in the .history file.
 SP_TEMPERATURE_PLIES = 0     # 0 = off: every ply at SP_TEMPERATURE
 SP_VALUE_BLEND = 0.0         # 0 = off: z alone, an int
+# SP_VALUE_LAMBDA X in [0, 1] (needs SP_VALUE_BLEND > 0; include/aqgnn.h "lambda-return value targets"): q in that target becomes the
+# lambda-return G of the game's later search values, G_t = (1 - X) q_t + X (-G_{t+1}), bootstrapped into the outcome -- q at 0, z at 1.
+SP_VALUE_LAMBDA = None       # None = off: q is the search value of the row's own root, and no launch is added
 # Tree reuse (the reference has none; engine.BatchedSelfPlay, include/aqgnn.h "tree reuse"): the next move's search starts from the chosen
 # child's subtree when that holds at most SP_TREE_REUSE_VISITS visits (None = the simulation count) and runs the same simulations on top.
 SP_TREE_REUSE = False        # off: a fresh tree every move, the reference's search
@@ -170,10 +173,27 @@ def _after_resign_generation(arrays, threshold, rank):
                  f'; next threshold: {"none (the next generation only collects)" if nxt is None else format(nxt, ".4f")}'))
 
 
+def _value_lambda(blend):
+    """SP_VALUE_LAMBDA as a float, or None when it is off; refused without a value blend, because nothing would read it."""
+    if SP_VALUE_LAMBDA is None:
+        return None
+    lam = check_value_lambda(SP_VALUE_LAMBDA)
+    if not blend > 0.0:
+        raise ValueError("SP_VALUE_LAMBDA needs SP_VALUE_BLEND > 0: the lambda-return takes the place of q in (1 - L) z + L q")
+    return lam
+
+
+def _search_values(eng, lam):
+    """The q of the blended value target, row-aligned with the engine's history: the rows' own search values, or with a lambda their
+    lambda-returns (one more launch)."""
+    return eng.history_values() if lam is None else eng.history_lambda_values(lam)
+
+
 def play(model, device=None, uniforms=None):
     """Execute one self-play game (self_play.py:40-68) -- a generation of one game on the engine.
     Returns [[state_array, policy list[POLICY_OUTPUT_SIZE], z], ...]."""
     blend = check_value_blend(SP_VALUE_BLEND)
+    lam = _value_lambda(blend)
     target, c_visit, c_scale = check_policy_record(SP_POLICY_TARGET, SP_POLICY_C_VISIT, SP_POLICY_C_SCALE)
     eng = BatchedSelfPlay(model, num_games=1, sims=pv_mcts.PV_EVALUATE_COUNT, board_size=BOARD_SIZE,
                           temperature=SP_TEMPERATURE, seed=int(np.random.randint(0, 2 ** 31 - 1)),
@@ -183,7 +203,7 @@ def play(model, device=None, uniforms=None):
                           policy_target=target, policy_c_visit=c_visit, policy_c_scale=c_scale, **_resign_options()[0])
     eng.play_generation(uniforms=uniforms, check_every=1)
     if blend > 0.0:
-        return _history_rows(*eng.history_tensors(), BOARD_SIZE, eng.history_values(), blend,
+        return _history_rows(*eng.history_tensors(), BOARD_SIZE, _search_values(eng, lam), blend,
                              policy=eng.history_policies() if target == "completed_q" else None)
     return eng.history()
 
@@ -215,6 +235,8 @@ def self_play(model=None, games=None, seed=None):
     if reanalyse_rows and SP_REPLAY is None:
         raise ValueError("SP_REANALYSE_ROWS > 0 needs a replay window (SP_REPLAY): there is no older row to search again")
     target, c_visit, c_scale = check_policy_record(SP_POLICY_TARGET, SP_POLICY_C_VISIT, SP_POLICY_C_SCALE)
+    blend = check_value_blend(SP_VALUE_BLEND)
+    lam = _value_lambda(blend)
     if model is None:
         model = load_network(PV_NETWORK_PATH + 'best.pth')       # GNNNetwork (prep_for_inference's path), or the network best.pth holds
         if isinstance(model, (GNNNetwork, CNNNetwork)) and torch.cuda.is_available():
@@ -230,7 +252,6 @@ def self_play(model=None, games=None, seed=None):
     st = torch.zeros((0, 72), dtype=torch.uint8, device=dev)
     vis = torch.zeros((0, POLICY_OUTPUT_SIZE), dtype=torch.int16, device=dev)
     z = torch.zeros((0,), dtype=torch.int8, device=dev)
-    blend = check_value_blend(SP_VALUE_BLEND)
     q = torch.zeros((0,), dtype=torch.float32, device=dev) if blend > 0.0 else None       # the rows' search values, with a blend only
     pol = torch.zeros((0, POLICY_OUTPUT_SIZE), dtype=torch.float32, device=dev) if target == "completed_q" else None      # the recorded targets
     resign_kw, resign_thr = _resign_options()
@@ -261,10 +282,11 @@ def self_play(model=None, games=None, seed=None):
                                policy_target=target, policy_c_visit=c_visit, policy_c_scale=c_scale, **resign_kw, **start_kw)
         c = eng.play_generation()
         print(f'\rSelf-play (rank {rank}: {c["finished"]}/{mine} games, policy target: {target}'
+              + (f', value lambda: {lam:g}' if lam is not None else '')
               + (f', {SP_FORKED_LAST}/{total} games forked from the window' if start_kw else '') + ')', end='')
         st, vis, z = eng.history_tensors()
         if q is not None:
-            q = eng.history_values()
+            q = _search_values(eng, lam)
         if pol is not None:
             pol = eng.history_policies()
         if resign_thr is not None:

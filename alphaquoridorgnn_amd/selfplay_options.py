@@ -94,6 +94,17 @@ def check_temperature(temperature, sims, keep_visits=None):
     return t
 
 
+def check_value_lambda(lam):
+    """Validate the lambda of the lambda-return value targets as the library does (include/aqgnn.h, "lambda-return value targets"), on
+    the f32 value the kernel is given: a number in [0, 1], not NaN (ValueError otherwise).  Returns it as a float."""
+    if isinstance(lam, (bool, str)) or not isinstance(lam, (int, float, np.integer, np.floating)):
+        raise ValueError(f"value_lambda must be a number in [0, 1], not {lam!r}")
+    value = float(np.float32(lam))
+    if not 0.0 <= value <= 1.0:                                  # NaN fails both
+        raise ValueError(f"value_lambda must be in [0, 1] as a float32, not {lam!r}")
+    return value
+
+
 def check_tree_reuse(tree_reuse, tree_reuse_visits, sims, evaluator="gnn"):
     """Validate the tree-reuse options as the library does (include/aqgnn.h, "tree reuse").  Returns keep_visits, or None when the
     option is off.  tree_reuse_visits None = `sims`; 0 is legal: on, never keeps."""

@@ -190,6 +190,9 @@ def _parser():
     ap.add_argument("--value-blend", type=float, default=None,
                     help="self-play: weight L in [0, 1] of the root's search value in the value target, (1 - L) z + L q (default "
                          "SP_VALUE_BLEND = 0: the game outcome alone)")
+    ap.add_argument("--value-lambda", type=float, default=None, metavar="X",
+                    help="self-play, with --value-blend L > 0: q becomes the lambda-return G of the game's later search values, "
+                         "bootstrapped into its outcome -- X in [0, 1], 0 = q, 1 = z (default SP_VALUE_LAMBDA = None: q itself)")
     ap.add_argument("--mirror-augment", action="store_true",
                     help="parameter update: train every epoch on positions mirrored left to right at random (default TRAIN_MIRROR = False: off)")
     ap.add_argument("--mirror-seed", type=int, default=None,
@@ -431,15 +434,35 @@ def _set_replay_options(args):
     return window
 
 
+def _check_value_lambda_args(args):
+    """--value-lambda, refused at parse time: a value outside [0, 1], and the flag without --value-blend L > 0 (nothing would read
+    the lambda-returns).  Returns the lambda as a float, or None when the flag is not given."""
+    from .selfplay_options import check_value_lambda
+    from .replay import check_value_blend
+    if args.value_lambda is None:
+        return None
+    if not 0.0 <= args.value_lambda <= 1.0:                     # NaN fails both
+        raise ValueError("--value-lambda must be in [0, 1]")
+    if args.value_blend is None or not check_value_blend(args.value_blend) > 0.0:
+        raise ValueError("--value-lambda needs --value-blend L > 0: the lambda-return takes the place of q in (1 - L) z + L q")
+    return check_value_lambda(args.value_lambda)
+
+
 def _set_target_options(args):
-    """--temperature-plies / --value-blend onto self_play's constants, refused here if the engine or the append would refuse them."""
+    """--temperature-plies / --value-blend / --value-lambda onto self_play's constants, refused here if the engine or the append would
+    refuse them."""
     from . import self_play as sp
     from .selfplay_options import check_target_options
     from .replay import check_value_blend
-    if args.temperature_plies is not None:
-        sp.SP_TEMPERATURE_PLIES = check_target_options(args.temperature_plies)[0]
-    if args.value_blend is not None:
-        sp.SP_VALUE_BLEND = check_value_blend(args.value_blend)
+    plies = None if args.temperature_plies is None else check_target_options(args.temperature_plies)[0]
+    blend = None if args.value_blend is None else check_value_blend(args.value_blend)
+    lam = _check_value_lambda_args(args)                          # a refused option sets nothing
+    if plies is not None:
+        sp.SP_TEMPERATURE_PLIES = plies
+    if blend is not None:
+        sp.SP_VALUE_BLEND = blend
+    if lam is not None:
+        sp.SP_VALUE_LAMBDA = lam
 
 
 def _set_tree_reuse_options(args):
@@ -521,6 +544,7 @@ def main(argv=None):
     _check_policy_args(args)
     _check_surprise_args(args)
     _check_start_args(args)
+    _check_value_lambda_args(args)
     rank, world = aqd.init_from_env()
     if args.games is not None:
         sp.SP_GAME_COUNT = args.games

@@ -504,6 +504,32 @@ int aqg_engine_move_targets(const aqg_engine* e_host, const double* uniforms, in
 int aqg_engine_finish_move_targets(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value,
                                    void* stream);
 
+/* ------------------------------------------------------------------ lambda-return value targets (additive to ABI 15; the reference has none)
+ *
+ * The TD(lambda) return of a finished game's recorded search values, bootstrapped into the game's outcome: the value that takes the
+ * place of q in the blended target above, ring_z = (1 - L) z + L G_t.  One launch (csrc/value_targets.hip) over the arrays the
+ * engine already holds, given as plain pointers: hist_value is no field of the struct, and any arrays of this layout will do.
+ *
+ * A finished game k has T = game_plies[k] recorded rows; q_t = hist_value[k * hp + t] is the search value of ply t from the mover's
+ * side, r = game_result[k] the result from the side of ply index 0, and z_t = (float)r at an even t, -(float)r at an odd t (the sign
+ * of history_tensors(); a draw's z_t is -0.0f at an odd t).  lambda is an f32 in [0, 1] and a = 1.0f - lambda.  In f32, without
+ * contraction:
+ *     G_{T-1} = a * q_{T-1} + lambda * z_{T-1}
+ *     G_t     = a * q_t     + lambda * (-G_{t+1})        for t = T - 2 .. 0
+ * -- two products and one sum per ply, each rounded, in the order of the blend (x = a * q, y = lambda * (..), x + y).  The side to
+ * move changes every ply, hence -G_{t+1}.  lambda == 1 gives z_t (exactly for r != 0; a draw's zero may change its sign);
+ * lambda == 0 gives q_t as a number (a zero may change its sign).  engine.lambda_values_reference is the same function in numpy,
+ * bit for bit.
+ *
+ * Game k < quota is processed iff game_done[k] != 0 and 1 <= game_plies[k] <= hp; out[k * hp + t] is then written for
+ * t < game_plies[k].  No other float of out is touched: not a skipped game's row, not the plies past a game's end.  One wavefront
+ * per game, four per workgroup; the row is loaded and stored 64 consecutive floats at a time and the recurrence runs as one
+ * wave-uniform chain from the last ply down; no LDS, no atomics, no workgroup barrier.  Any hp >= 1.
+ * Refused on the host, before any launch (-1, aqg_last_error): quota < 0, hp < 1, a lambda outside [0, 1] or NaN, a NULL pointer,
+ * out (quota * hp floats) overlapping hist_value.  quota == 0 returns 0 without a launch and without looking at the pointers. */
+int aqg_lambda_values(int quota, int hp, const int32_t* game_plies, const int8_t* game_result, const uint8_t* game_done,
+                      const float* hist_value, float lambda, float* out, void* stream);
+
 /* ------------------------------------------------------------------ tree reuse (additive to ABI 15; the reference has none: pv_mcts.py:81)
  *
  * Opt-in: the next move's search starts from the subtree of the child this move chose instead of from an empty tree.  The option
