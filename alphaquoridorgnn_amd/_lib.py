@@ -140,6 +140,16 @@ class OptimStruct(_c.Structure):
                 ("grad_norm", _vp), ("workspace", _vp), ("workspace_floats", _c.c_size_t)]
 
 
+class WeightAverageStruct(_c.Structure):
+    """Mirror of `struct aqg_weight_average` (include/aqgnn.h, "weight averaging"): the option beside a trainer struct.  table is the
+    device copy of the 4 T + 1 words, host_table the host copy the library's checks read."""
+    _fields_ = [("table", _vp), ("host_table", _c.POINTER(_c.c_int64)), ("num_tensors", _i32), ("every", _i32),
+                ("total_chunks", _c.c_int64), ("decay", _f32)]
+
+
+WEIGHT_AVERAGE_CHUNK = 4096          # AQG_WEIGHT_AVERAGE_CHUNK
+WEIGHT_AVERAGE_MAX_TENSORS = 1024    # AQG_WEIGHT_AVERAGE_MAX_TENSORS
+
 SIGNATURES = {
     "aqg_abi_version": (_c.c_int, []),
     "aqg_last_error": (_c.c_char_p, []),
@@ -243,6 +253,19 @@ SIGNATURES = {
     "aqg_cnn_train_step_optim": (_c.c_int, [_c.POINTER(CnnTrainStruct), _vp, _vp, _vp, _c.c_int, _c.POINTER(OptimStruct), _vp]),
     "aqg_cnn_train_steps_optim": (_c.c_int, [_c.POINTER(CnnTrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _c.POINTER(OptimStruct),
                                              _vp]),
+    "aqg_weight_average_update": (_c.c_int, [_c.POINTER(WeightAverageStruct), _vp]),
+    "aqg_gcn_train_step_avg": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _c.c_int, _c.POINTER(OptimStruct),
+                                          _c.POINTER(WeightAverageStruct), _vp]),
+    "aqg_gcn_train_steps_avg": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _c.POINTER(OptimStruct),
+                                           _c.POINTER(WeightAverageStruct), _vp]),
+    "aqg_gcn_train_step_general_avg": (_c.c_int, [_c.POINTER(TrainGeneralStruct), _vp, _vp, _vp, _c.c_int, _c.POINTER(OptimStruct),
+                                                  _c.POINTER(WeightAverageStruct), _vp]),
+    "aqg_gcn_train_steps_general_avg": (_c.c_int, [_c.POINTER(TrainGeneralStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp,
+                                                   _c.POINTER(OptimStruct), _c.POINTER(WeightAverageStruct), _vp]),
+    "aqg_cnn_train_step_avg": (_c.c_int, [_c.POINTER(CnnTrainStruct), _vp, _vp, _vp, _c.c_int, _c.POINTER(OptimStruct),
+                                          _c.POINTER(WeightAverageStruct), _vp]),
+    "aqg_cnn_train_steps_avg": (_c.c_int, [_c.POINTER(CnnTrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _c.POINTER(OptimStruct),
+                                           _c.POINTER(WeightAverageStruct), _vp]),
     "aqg_augment_gather": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_int, _vp, _vp, _vp,
                                       _vp]),
     "aqg_replay_append": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),

@@ -566,6 +566,83 @@ int aqg_grad_norm(const float* x, size_t n, float* out, float* workspace, size_t
     return launch_grad_norm(x, n, out, workspace, workspace_floats, (hipStream_t)stream);
 }
 
+// The _avg entry points (include/aqgnn.h "weight averaging"): avg NULL is the _optim call itself; otherwise the call's own checks,
+// the controls' (optim may be NULL) and the average's, all in front of the first launch.
+int aqg_weight_average_update(const aqg_weight_average* avg, void* stream) {
+    if (int r = check_weight_average(avg, "aqg_weight_average_update")) return r;
+    return launch_weight_average(*avg, (hipStream_t)stream);
+}
+int aqg_gcn_train_step_avg(const aqg_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                           const aqg_optim* optim, const aqg_weight_average* avg, void* stream) {
+    if (!avg) return aqg_gcn_train_step_optim(t, states72, pi_target, z_target, mode, optim, stream);
+    const char* what = "aqg_gcn_train_step_avg";
+    OptimPlan plan;
+    bool on;
+    if (int r = check_step(t, states72, pi_target, z_target, mode, what)) return r;
+    if (int r = plan_optim(*t, optim, what, &plan, &on)) return r;
+    if (int r = check_weight_average(avg, what)) return r;
+    return train_step(*t, states72, pi_target, z_target, mode, (hipStream_t)stream, on ? &plan : nullptr, avg);
+}
+int aqg_gcn_train_steps_avg(const aqg_train* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                            const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim,
+                            const aqg_weight_average* avg, void* stream) {
+    if (!avg) return aqg_gcn_train_steps_optim(t, states72, pi_target, z_target, order, positions, loss_sums, optim, stream);
+    const char* what = "aqg_gcn_train_steps_avg";
+    OptimPlan plan;
+    bool on;
+    if (int r = check_steps(t, states72, pi_target, z_target, positions, what)) return r;
+    if (int r = plan_optim(*t, optim, what, &plan, &on)) return r;
+    if (int r = check_weight_average(avg, what)) return r;
+    return train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream, on ? &plan : nullptr, avg);
+}
+int aqg_gcn_train_step_general_avg(const aqg_train_general* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                                   int mode, const aqg_optim* optim, const aqg_weight_average* avg, void* stream) {
+    if (!avg) return aqg_gcn_train_step_general_optim(t, states72, pi_target, z_target, mode, optim, stream);
+    const char* what = "aqg_gcn_train_step_general_avg";
+    OptimPlan plan;
+    bool on;
+    if (int r = check_step(t, states72, pi_target, z_target, mode, what)) return r;
+    if (int r = plan_optim(*t, optim, what, &plan, &on)) return r;
+    if (int r = check_weight_average(avg, what)) return r;
+    return train_step_general(*t, states72, pi_target, z_target, mode, (hipStream_t)stream, on ? &plan : nullptr, avg);
+}
+int aqg_gcn_train_steps_general_avg(const aqg_train_general* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                                    const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim,
+                                    const aqg_weight_average* avg, void* stream) {
+    if (!avg) return aqg_gcn_train_steps_general_optim(t, states72, pi_target, z_target, order, positions, loss_sums, optim, stream);
+    const char* what = "aqg_gcn_train_steps_general_avg";
+    OptimPlan plan;
+    bool on;
+    if (int r = check_steps(t, states72, pi_target, z_target, positions, what)) return r;
+    if (int r = plan_optim(*t, optim, what, &plan, &on)) return r;
+    if (int r = check_weight_average(avg, what)) return r;
+    return train_steps_general(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream, on ? &plan : nullptr,
+                               avg);
+}
+int aqg_cnn_train_step_avg(const aqg_cnn_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                           const aqg_optim* optim, const aqg_weight_average* avg, void* stream) {
+    if (!avg) return aqg_cnn_train_step_optim(t, states72, pi_target, z_target, mode, optim, stream);
+    const char* what = "aqg_cnn_train_step_avg";
+    OptimPlan plan;
+    bool on;
+    if (int r = check_step(t, states72, pi_target, z_target, mode, what)) return r;
+    if (int r = plan_optim(*t, optim, what, &plan, &on)) return r;
+    if (int r = check_weight_average(avg, what)) return r;
+    return cnn_train_step(*t, states72, pi_target, z_target, mode, (hipStream_t)stream, on ? &plan : nullptr, avg);
+}
+int aqg_cnn_train_steps_avg(const aqg_cnn_train* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                            const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim,
+                            const aqg_weight_average* avg, void* stream) {
+    if (!avg) return aqg_cnn_train_steps_optim(t, states72, pi_target, z_target, order, positions, loss_sums, optim, stream);
+    const char* what = "aqg_cnn_train_steps_avg";
+    OptimPlan plan;
+    bool on;
+    if (int r = check_steps(t, states72, pi_target, z_target, positions, what)) return r;
+    if (int r = plan_optim(*t, optim, what, &plan, &on)) return r;
+    if (int r = check_weight_average(avg, what)) return r;
+    return cnn_train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream, on ? &plan : nullptr, avg);
+}
+
 int aqg_augment_gather(int board_size, int policy_size, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
                        const uint8_t* flips, int use_seed, uint64_t seed, uint64_t epoch, int n, uint8_t* out72, float* out_pi,
                        float* out_z, void* stream) {

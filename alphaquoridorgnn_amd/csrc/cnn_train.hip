@@ -447,12 +447,13 @@ struct CnnKind {
 };
 
 int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
-                   const OptimPlan* plan) {
-    return train_driver_step<CnnKind>(t, states72, pi, z, mode, st, plan);
+                   const OptimPlan* plan, const aqg_weight_average* avg) {
+    return train_driver_step<CnnKind>(t, states72, pi, z, mode, st, plan, avg);
 }
 int cnn_train_steps(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
-                    long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan) {
-    return train_driver_steps<CnnKind>(t, states72, pi, z, order, positions, loss_sums, st, plan);
+                    long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan,
+                    const aqg_weight_average* avg) {
+    return train_driver_steps<CnnKind>(t, states72, pi, z, order, positions, loss_sums, st, plan, avg);
 }
 
 }  // namespace aqg

@@ -82,9 +82,8 @@ static int final_optim(const aqg_train& t, int B, bool compute, int step, int st
 }
 
 // mode 0 = gradients only, 1 = gradients + Adam, 2 = Adam only (data-parallel: local gradients, all-reduce, update)
-int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
-               const OptimPlan* plan) {
-    if (int r = validate(t)) return r;
+static int train_step_launches(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
+                               const OptimPlan* plan) {
     const int B = t.batch;
     if (mode != 2 && B > 0) {
         if (int r = forward_backward(t, states72, pi, z, nullptr, 0, B, st)) return r;
@@ -95,21 +94,29 @@ int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, con
     if (mode >= 1) return plan ? final_optim(t, B, false, t.step, 0, nullptr, *plan, st) : launch_train_final(t, B, false, true, t.step, nullptr, st);
     return plan ? optim_norm_only(*plan, st) : 0;
 }
+// avg (may be null; include/aqgnn.h "weight averaging"): the averaging launch behind the last launch of an updating step
+int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
+               const OptimPlan* plan, const aqg_weight_average* avg) {
+    if (int r = validate(t)) return r;
+    if (int r = train_step_launches(t, states72, pi, z, mode, st, plan)) return r;
+    return mode >= 1 ? average_after_update(avg, t.step, st) : 0;
+}
 
 // A run of consecutive single-process steps over a shuffled data set, no host work in between: step i takes the positions
 // order[i * batch .. (i + 1) * batch) (the last batch may be short, train_network.py's DataLoader keeps it) of the
 // resident arrays, t.step counts up from its entry value, and each step's loss terms are added to loss_sums[2]
 // (policy, value: the per-step batch means, what train_network.py:89-90 accumulates per epoch).
 int train_steps(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, long long positions,
-                float* loss_sums, hipStream_t st, const OptimPlan* plan) {
+                float* loss_sums, hipStream_t st, const OptimPlan* plan, const aqg_weight_average* avg) {
     if (int r = validate(t)) return r;
     if (t.batch < 1) return fail("aqg_gcn_train_steps: batch must be >= 1");
     int step = t.step;
     for (long long first = 0; first < positions; first += t.batch, ++step) {
         const int B = (int)(positions - first < t.batch ? positions - first : t.batch);
         if (int r = forward_backward(t, states72, pi, z, order, (int)first, B, st)) return r;
-        if (plan) { if (int r = final_optim(t, B, true, step, step - t.step, loss_sums, *plan, st)) return r; continue; }
-        if (int r = launch_train_final(t, B, true, true, step, loss_sums, st)) return r;
+        if (plan) { if (int r = final_optim(t, B, true, step, step - t.step, loss_sums, *plan, st)) return r; }
+        else if (int r = launch_train_final(t, B, true, true, step, loss_sums, st)) return r;
+        if (int r = average_after_update(avg, step, st)) return r;
     }
     return 0;
 }

@@ -411,12 +411,13 @@ struct GeneralKind {
 };
 
 int train_step_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
-                       const OptimPlan* plan) {
-    return train_driver_step<GeneralKind>(t, states72, pi, z, mode, st, plan);
+                       const OptimPlan* plan, const aqg_weight_average* avg) {
+    return train_driver_step<GeneralKind>(t, states72, pi, z, mode, st, plan, avg);
 }
 int train_steps_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
-                        long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan) {
-    return train_driver_steps<GeneralKind>(t, states72, pi, z, order, positions, loss_sums, st, plan);
+                        long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan,
+                        const aqg_weight_average* avg) {
+    return train_driver_steps<GeneralKind>(t, states72, pi, z, order, positions, loss_sums, st, plan, avg);
 }
 
 }  // namespace aqg

@@ -191,12 +191,20 @@ int optim_before_finish(const OptimPlan& plan, int step_index, OptimLaunch* ol, 
 int launch_clip_scale(const OptimPlan& plan, const OptimLaunch& ol, hipStream_t st);               // the fused step: g <- coef g in place
 int optim_norm_only(const OptimPlan& plan, hipStream_t st);                                        // mode 0: stage 1 + combine
 
-// ---- gcn_train.hip  (plan: null = the step as it has always been)
+// ---- weight_average.hip  (include/aqgnn.h "weight averaging")
+int check_weight_average(const aqg_weight_average* a, const char* what);           // every refusal, on the host; nothing launched
+int launch_weight_average(const aqg_weight_average& a, hipStream_t st);             // of a checked struct
+// behind the Adam launch of 1-based step `step`: the averaging launch when an average is kept and the step is a multiple of `every`
+inline int average_after_update(const aqg_weight_average* avg, int step, hipStream_t st) {
+    return avg && step % avg->every == 0 ? launch_weight_average(*avg, st) : 0;
+}
+
+// ---- gcn_train.hip  (plan: null = the step as it has always been; avg: null = no average is kept)
 extern int g_train_fused;
 int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
-               const OptimPlan* plan = nullptr);
+               const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr);
 int train_steps(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, long long positions,
-                float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr);
+                float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr);
 void train_tensor_sizes(const aqg_train& t, size_t* numel);
 
 // ---- gcn_train_exact.hip, gcn_train_split.hip, gcn_train_final.hip: the two launches of a fused training step
@@ -224,18 +232,18 @@ int launch_train_general_loss(int B, int A, const float* policy, const float* va
                               const int64_t* order, int first, float* loss, float* dpol, float* dval, hipStream_t st);
 size_t train_general_workspace_floats(int N, int hidden, int num_layers, int policy_size, int max_batch);
 int train_step_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
-                       const OptimPlan* plan = nullptr);
+                       const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr);
 int train_steps_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
-                        long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr);
+                        long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr);
 void train_general_tensor_sizes(const aqg_train_general& t, size_t* numel);
 
 // ---- cnn_train.hip
 size_t cnn_train_workspace_floats(int N, int F, int L, int A, int max_batch);
 int check_cnn_train(const aqg_cnn_train& t, bool adam, const char* what);
 int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
-                   const OptimPlan* plan = nullptr);
+                   const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr);
 int cnn_train_steps(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
-                    long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr);
+                    long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr);
 void cnn_train_tensor_sizes(const aqg_cnn_train& t, size_t* numel);
 
 // ---- augment.hip

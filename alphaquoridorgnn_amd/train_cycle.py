@@ -205,6 +205,12 @@ def _parser():
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="M",
                     help="parameter update: scale every step's gradient to a global L2 norm of at most M, as "
                          "torch.nn.utils.clip_grad_norm_ (default TRAIN_MAX_GRAD_NORM = None: off)")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                    help="parameter update: keep an exponential moving average of the parameters with decay D in [0, 1), updated "
+                         "inside the HIP steps, and save IT as latest.pth (default TRAIN_EMA_DECAY = None: off, the last iterate)")
+    ap.add_argument("--ema-every", type=int, default=None, metavar="K",
+                    help="parameter update: update the average at the Adam steps whose number is a multiple of K (default "
+                         "TRAIN_EMA_EVERY = 1; needs --ema-decay)")
     ap.add_argument("--replay-generations", type=int, default=0,
                     help="train on a replay window of the newest K self-play generations, resident on the GPU (default 0: off, the "
                          "newest .history file alone); a cycle that finds .history files in ./data resumes from the newest K")
@@ -530,6 +536,29 @@ def _set_optimiser_options(args):
         tn.TRAIN_MAX_GRAD_NORM = args.max_grad_norm
 
 
+def _check_average_args(args):
+    """--ema-decay / --ema-every, refused as the library refuses them."""
+    import numpy as np
+    if args.ema_every is not None and args.ema_decay is None:
+        raise ValueError("--ema-every needs --ema-decay")
+    if args.ema_decay is not None:
+        d = np.float32(args.ema_decay)
+        if not (d >= 0 and d < 1):
+            raise ValueError("--ema-decay must be in [0, 1) as a float32")
+    if args.ema_every is not None and args.ema_every < 1:
+        raise ValueError("--ema-every must be >= 1")
+
+
+def _set_average_options(args):
+    """--ema-decay / --ema-every onto train_network's constants."""
+    from . import train_network as tn
+    _check_average_args(args)
+    if args.ema_decay is not None:
+        tn.TRAIN_EMA_DECAY = args.ema_decay
+    if args.ema_every is not None:
+        tn.TRAIN_EMA_EVERY = args.ema_every
+
+
 def main(argv=None):
     """`python -m alphaquoridorgnn_amd.train_cycle` -- also the per-rank program of
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P -m
@@ -545,6 +574,7 @@ def main(argv=None):
     _check_surprise_args(args)
     _check_start_args(args)
     _check_value_lambda_args(args)
+    _check_average_args(args)
     rank, world = aqd.init_from_env()
     if args.games is not None:
         sp.SP_GAME_COUNT = args.games
@@ -561,6 +591,7 @@ def main(argv=None):
     _set_resign_options(args)
     _set_mirror_options(args)
     _set_optimiser_options(args)
+    _set_average_options(args)
     _set_replay_options(args)
     _set_surprise_options(args)
     _set_reanalyse_options(args)

@@ -47,6 +47,10 @@ _surprise_updates = 0                    # surprise-weighted updates drawn witho
 TRAIN_WEIGHT_DECAY = 0.0      # c of the AlphaZero loss term c * ||theta||^2, as torch's weight_decay
 TRAIN_DECOUPLED = True        # True: torch.optim.AdamW's decay; False: torch.optim.Adam(weight_decay=)'s
 TRAIN_MAX_GRAD_NORM = None    # M: torch.nn.utils.clip_grad_norm_(params, M) in front of every update; None = off
+# Weight averaging (the reference saves the last Adam iterate): an exponential moving average of the parameters, updated inside the
+# HIP steps (include/aqgnn.h "weight averaging", WeightAverage below) and saved as latest.pth in place of the last iterate.
+TRAIN_EMA_DECAY = None        # d in [0, 1): e <- d e + (1 - d) p behind every TRAIN_EMA_EVERY-th Adam update; None = off, no object built
+TRAIN_EMA_EVERY = 1           # K >= 1: the updates are made at the Adam steps whose number is a multiple of K
 
 
 def load_data():
@@ -261,6 +265,47 @@ def grad_norm(t):
     return out[0]
 
 
+def weight_average_reference(avg, src, decay):
+    """One update of the weight average (include/aqgnn.h "weight averaging") in numpy float32: with d = float32(decay) and
+    w = float32(1.0 - float(d)), e' = f32(d * e) + f32(w * p) -- two rounded products and one rounded sum, bit for bit
+    torch.optim.swa_utils.get_ema_avg_fn(float(d)) on CPU tensors.  Returns a new array."""
+    f = np.float32
+    d = f(decay)
+    w = f(1.0 - float(d))
+    return d * np.asarray(avg, dtype=f) + w * np.asarray(src, dtype=f)
+
+
+def weight_average_due(step, every):
+    """Whether the average is updated behind the Adam update of 1-based step `step`: at the multiples of `every`, wherever an epoch
+    or a library call ends."""
+    return int(step) % int(every) == 0
+
+
+def weight_average_table(averages, sources):
+    """The launch's tensor table (include/aqgnn.h "weight averaging") of device tensors averages[i] <- sources[i]: (the host copy, a
+    ctypes int64 array of 4 T + 1 words; the device copy, an int64 tensor; the total number of chunks).  Pointers, element counts
+    and the prefix of the per-tensor chunk counts, a chunk being 4,096 floats of the 16-byte grid the average's base sits in."""
+    T, C = len(averages), _lib.WEIGHT_AVERAGE_CHUNK
+    prefix = [0]
+    for e in averages:
+        prefix.append(prefix[-1] + (e.numel() + ((e.data_ptr() >> 2) & 3) + C - 1) // C)
+    words = [e.data_ptr() for e in averages] + [p.data_ptr() for p in sources] + [p.numel() for p in sources] + prefix
+    return (ctypes.c_int64 * (4 * T + 1))(*words), torch.tensor(words, dtype=torch.int64, device=averages[0].device), prefix[-1]
+
+
+def _checked_average_controls(decay, every):
+    """(decay as the float32 the kernel takes, every as int), refused as the library refuses them."""
+    try:
+        d = np.float32(decay)
+    except (TypeError, ValueError):
+        raise ValueError("the weight average's decay is a number in [0, 1)") from None
+    if not (d >= 0 and d < 1):                               # a NaN fails both; a decay that rounds to 1.0f is refused too
+        raise ValueError(f"the weight average's decay must be in [0, 1) as a float32 (got {decay!r})")
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
+        raise ValueError(f"the weight average's every must be an integer >= 1 (got {every!r})")
+    return float(d), int(every)
+
+
 class _Trainer:
     """What the three trainers share: the Adam state and the flat gradient buffer, the optimiser controls, step() (single process or
     data parallel), outputs() and run_epoch().  A subclass names its library calls (_STEP, _STEPS) and provides the batch-mean losses
@@ -301,6 +346,7 @@ class _Trainer:
         self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=self.dev)
         self.grad_norms = torch.zeros((0,), dtype=torch.float32, device=self.dev)
         self._optim_ws = None
+        self.average = None                       # a WeightAverage attaches itself here: the calls then take their _avg forms
         self.N, self.A = model.board_size, model.policy_output_size
         self.max_batch, self.step_count = int(max_batch), 0
         self.betas, self.eps = betas, eps
@@ -353,16 +399,25 @@ class _Trainer:
             o.workspace, o.workspace_floats = self._optim_ws.data_ptr(), self._optim_ws.numel()
         return o, norms
 
-    def _invoke(self, name, args, steps, plain=False):
+    def _invoke(self, name, args, steps, plain=False, updating=True):
         """One library call of `steps` steps: `name` itself when plain or with every control off (no aqg_optim is built), its
-        _optim form otherwise.  Returns the device tensor the call's norms went to, or None."""
+        _optim form otherwise -- or, with a weight average attached and a call that updates, its _avg form (the controls' struct or
+        NULL beside the average's).  Returns the device tensor the call's norms went to, or None."""
         o, norms = (None, None) if plain else self._optim(steps)
-        name, controls = (name, ()) if o is None else (name + "_optim", (ctypes.byref(o),))
+        average = None if plain or not updating else self.average
+        if average is not None:
+            a = average._struct()
+            name, controls = name + "_avg", (None if o is None else ctypes.byref(o), ctypes.byref(a))
+        else:
+            name, controls = (name, ()) if o is None else (name + "_optim", (ctypes.byref(o),))
         _lib.check(getattr(self.lib, name)(ctypes.byref(self.t), *args, *controls, _lib.stream_ptr(self.dev)), name)
+        if average is not None:
+            average._stepped(int(self.t.step), steps, a.every)
         return norms
 
     def _call(self, states72, pi_target, z_target, mode, plain=False):
-        norms = self._invoke(self._STEP, (_lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target), mode), 1, plain)
+        norms = self._invoke(self._STEP, (_lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target), mode), 1, plain,
+                             updating=mode >= 1)
         if norms is not None:
             self.last_grad_norm = norms[0]
 
@@ -594,6 +649,118 @@ class CNNTrainer(_Trainer):
         self.model.invalidate_packed()
 
 
+class WeightAverage:
+    """An exponential moving average of a trainer's parameters, updated inside its HIP steps (include/aqgnn.h "weight averaging",
+    csrc/weight_average.hip): e <- f32(d e) + f32(w p) with d = float32(decay), w = float32(1 - d), behind the Adam update of every
+    step whose 1-based number is a multiple of `every` -- weight_average_reference in numpy, torch.optim.swa_utils.AveragedModel
+    (get_ema_avg_fn, use_buffers=True) in torch.  The average starts as a copy of the parameters: no bias correction, no warm-up.
+
+    WeightAverage(trainer) allocates the shadow tensors, builds the launch's tensor table once and attaches itself as
+    trainer.average; from then on step(update=True) and run_epoch call the library's _avg entry points.  For a CNNTrainer every
+    running_mean / running_var is shadowed too, with the same d.  decay and every are plain attributes read at every call.
+    Nothing the trainer computes changes: parameters, moments and losses are those of a trainer without an average."""
+
+    def __init__(self, trainer, decay=0.999, every=1):
+        if getattr(trainer, "average", None) is not None:
+            raise ValueError("this trainer already keeps a weight average (trainer.average)")
+        self._build(trainer.model, list(trainer.params) + list(trainer.buffers), decay, every)
+        self.trainer = trainer
+        trainer.average = self
+
+    @classmethod
+    def for_module(cls, module, decay=0.999, every=1):
+        """The average of any module's float32 parameters, updated by update() alone (every call is an update; `every` is kept for
+        the caller's own schedule).  A module on the GPU is averaged by the HIP launch, a CPU module by weight_average_reference."""
+        self = cls.__new__(cls)
+        sources = [p.detach() for p in module.parameters() if p.dtype == torch.float32]
+        if not sources:
+            raise ValueError("WeightAverage.for_module: the module has no float32 parameter")
+        self._build(module, sources, decay, every)
+        self.trainer = None
+        return self
+
+    def _build(self, model, sources, decay, every):
+        self.decay, self.every = decay, every
+        _checked_average_controls(decay, every)
+        if not 1 <= len(sources) <= _lib.WEIGHT_AVERAGE_MAX_TENSORS:
+            raise ValueError(f"a weight average takes 1..{_lib.WEIGHT_AVERAGE_MAX_TENSORS} tensors (got {len(sources)})")
+        for x in sources:
+            if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < 1:
+                raise ValueError("a weight average takes non-empty contiguous float32 tensors")
+        if any(x.device != sources[0].device for x in sources):
+            raise ValueError("every tensor of a weight average must be on one device")
+        names = {t.data_ptr(): k for k, t in model.state_dict().items() if t.numel()}
+        self.keys = [names.get(x.data_ptr()) for x in sources]
+        if any(k is None for k in self.keys) or len(set(self.keys)) != len(self.keys):
+            raise ValueError("every averaged tensor must be an entry of the model's state_dict, each once")
+        self.model, self.sources, self.dev, self.updates = model, sources, sources[0].device, 0
+        self.shadows = [x.detach().clone() for x in sources]
+        self.host = self.dev.type != "cuda"                    # the numpy statement as the backend of a CPU module
+        if self.host:
+            return
+        self.lib = _lib.load()
+        _lib.require_gpu(self.dev)
+        self._host_table, self.table, self.total_chunks = weight_average_table(self.shadows, sources)
+
+    def _struct(self):
+        """aqg_weight_average of the next call, with decay and every as they are now."""
+        d, k = _checked_average_controls(self.decay, self.every)
+        a = _lib.WeightAverageStruct()
+        a.table, a.host_table = self.table.data_ptr(), ctypes.cast(self._host_table, ctypes.POINTER(ctypes.c_int64))
+        a.num_tensors, a.every, a.total_chunks, a.decay = len(self.shadows), k, self.total_chunks, d
+        return a
+
+    def _stepped(self, first_step, steps, every):
+        """Count the averaging launches of a library call over the steps first_step .. first_step + steps - 1."""
+        self.updates += (first_step + steps - 1) // every - (first_step - 1) // every
+
+    def update(self):
+        """The stand-alone update, now: one launch over all tensors (aqg_weight_average_update), or numpy for a CPU module."""
+        if self.host:
+            d, _ = _checked_average_controls(self.decay, self.every)
+            for e, p in zip(self.shadows, self.sources):
+                e.copy_(torch.from_numpy(weight_average_reference(e.numpy(), p.detach().numpy(), d)))
+        else:
+            a = self._struct()
+            _lib.check(self.lib.aqg_weight_average_update(ctypes.byref(a), _lib.stream_ptr(self.dev)), "aqg_weight_average_update")
+        self.updates += 1
+
+    def tensors(self):
+        """The shadow tensors, in the order of the trainer's parameters (then its running statistics)."""
+        return list(self.shadows)
+
+    def state_dict(self):
+        """The model's state_dict with every shadowed entry replaced by a copy of its average -- same keys, same order; what is not
+        averaged (a BatchNorm's num_batches_tracked) is copied from the model as it is now."""
+        from collections import OrderedDict
+        shadow = dict(zip(self.keys, self.shadows))
+        return OrderedDict((k, (shadow[k] if k in shadow else v).detach().clone()) for k, v in self.model.state_dict().items())
+
+    def copy_to(self, model):
+        """Write the average into `model`, a module of the averaged model's shape (the averaged model itself included); entries that
+        are not averaged are left alone.  Version counters advance and any packed copy of the weights is dropped, as after a step."""
+        target = model.state_dict()
+        for k, e in zip(self.keys, self.shadows):
+            if k not in target or tuple(target[k].shape) != tuple(e.shape) or target[k].dtype != e.dtype:
+                raise ValueError(f"copy_to: the module has no float32 entry {k!r} of shape {tuple(e.shape)}")
+        with torch.no_grad():
+            for k, e in zip(self.keys, self.shadows):
+                target[k].copy_(e)                               # (an in-place torch op: the version counter advances)
+        if hasattr(model, "invalidate_packed"):
+            model.invalidate_packed()
+
+    def distance(self):
+        """|avg - raw| / |raw| over all averaged tensors, as a float: one host read."""
+        with torch.no_grad():
+            diff = torch.stack([(e - p).double().pow(2).sum() for e, p in zip(self.shadows, self.sources)]).sum()
+            raw = torch.stack([p.double().pow(2).sum() for p in self.sources]).sum()
+            return float((diff / raw).sqrt())
+
+    def summary_line(self):
+        d, k = _checked_average_controls(self.decay, self.every)
+        return f"weight average: decay {d:g}, every {k}, {self.updates} updates, |avg - raw| / |raw| = {self.distance():.3e}"
+
+
 def _configured_controls():
     """The trainers' optimiser keyword arguments from TRAIN_WEIGHT_DECAY, TRAIN_DECOUPLED and TRAIN_MAX_GRAD_NORM."""
     return dict(weight_decay=TRAIN_WEIGHT_DECAY, decoupled=TRAIN_DECOUPLED, max_grad_norm=TRAIN_MAX_GRAD_NORM)
@@ -670,6 +837,8 @@ def _train_loop(load, make_trainer, rank, world):
     s, p, v, index = _training_rows(dev, model.board_size, model=model)
     n = s.shape[0] if index is None else index.shape[0]
     trainer = make_trainer(model, max_batch=BATCH_SIZE)
+    # every rank keeps its own average of its own (identical) parameters: no collective
+    average = None if TRAIN_EMA_DECAY is None else WeightAverage(trainer, decay=TRAIN_EMA_DECAY, every=TRAIN_EMA_EVERY)
     for epoch in range(NUM_EPOCH):
         lr = LEARNING_RATE * lr_lambda(epoch)                                      # LambdaLR, stepped once per epoch (:98)
         perm = torch.randperm(n, device=dev)                                    # DataLoader(shuffle=True), last batch kept
@@ -699,7 +868,9 @@ def _train_loop(load, make_trainer, rank, world):
             print(_progress_line(epoch, epoch_policy_loss, epoch_value_loss, trainer), end='')
     if rank == 0:
         print('')
-        torch.save(model.state_dict(), PV_NETWORK_PATH + 'latest.pth')
+        if average is not None:
+            print(average.summary_line())
+        torch.save(model.state_dict() if average is None else average.state_dict(), PV_NETWORK_PATH + 'latest.pth')
     if world > 1:
         dist.barrier()          # latest.pth is complete before any rank moves on to the evaluation stage
 

@@ -883,6 +883,63 @@ int aqg_cnn_train_step_optim(const aqg_cnn_train* t_host, const uint8_t* states7
 int aqg_cnn_train_steps_optim(const aqg_cnn_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target,
                               const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim, void* stream);
 
+/* ------------------------------------------------------------------ weight averaging (additive to ABI 15; the reference has none)
+ *
+ * An exponential moving average of the parameters, kept beside the three training steps above (csrc/weight_average.hip).  For a
+ * decay d (float32, 0 <= d < 1) let w = float32(1.0 - (double)d), formed on the host.  An update of one element of the average e
+ * from its source element p is
+ *     e' = f32(d * e) + f32(w * p)
+ * -- two f32 products and one f32 sum, each rounded, never contracted into a fused multiply-add.  On the CPU that is bit for bit
+ * torch.optim.swa_utils.get_ema_avg_fn(float(d)), what AveragedModel applies.  The average starts as a copy of the parameters (the
+ * caller makes it): no bias correction, no warm-up.  every = K: inside the steps an update is made behind the Adam update of every
+ * step whose 1-based Adam step number (t.step, the number the bias corrections use) is a multiple of K -- the step number alone
+ * decides, not where an epoch or a library call ends.
+ *
+ * One launch serves all tensors: a workgroup owns one chunk of AQG_WEIGHT_AVERAGE_CHUNK floats of one tensor, cut on the 16-byte grid
+ * the AVERAGE's base sits in (tensor i with its average `mis` = 0..3 floats behind that grid has ceil((mis + numel) / CHUNK) chunks).
+ * Where average and source sit alike on that grid, the words wholly inside the tensor are 16-byte accesses; any other float is taken
+ * alone, each access guarded by the range: nothing outside either tensor is touched, and the source is only read.  No atomics.
+ *
+ * The tensor table is 4 T + 1 int64 words, T = num_tensors:
+ *     [0, T) average pointers | [T, 2 T) source pointers | [2 T, 3 T) element counts | [3 T, 4 T] the prefix of the chunk counts
+ * (prefix[0] = 0, prefix[T] = total_chunks).  The kernel reads `table`, on the device; the checks below read `host_table`, the same
+ * words on the host (the caller keeps the two equal: a check that read the device copy would stop the stream at every call).
+ *
+ * aqg_weight_average_update: the launch alone, on `stream`.  Refused on the host before any launch (-1, aqg_last_error), the average
+ *   untouched: a NULL struct or table (either copy); num_tensors < 1 or > AQG_WEIGHT_AVERAGE_MAX_TENSORS; a NULL or not 4-byte-aligned
+ *   tensor; a tensor of fewer than 1 element; a chunk prefix or total_chunks that is not the one stated above, or more than 2^31 - 1
+ *   chunks; decay outside [0, 1) or NaN; every < 1; any average range that overlaps any source range or another average range.
+ * The six _avg entry points take the _optim call's arguments plus the average.  optim may be NULL: the plain step.  avg == NULL is the
+ *   _optim call itself.  Otherwise the call refuses what aqg_weight_average_update refuses, in front of every launch, and enqueues the
+ *   averaging launch on the same stream behind the finish / Adam launch of a step of mode 1 or 2 (mode 2: the data-parallel update;
+ *   the empty-batch update included) whose step number is a multiple of `every`.  Mode 0 never averages.  No other launch changes. */
+#define AQG_WEIGHT_AVERAGE_MAX_TENSORS 1024
+#define AQG_WEIGHT_AVERAGE_CHUNK 4096
+typedef struct aqg_weight_average {
+    const int64_t* table;          /* device */
+    const int64_t* host_table;     /* host: the same 4 T + 1 words */
+    int32_t num_tensors;
+    int32_t every;
+    int64_t total_chunks;
+    float decay;
+} aqg_weight_average;
+int aqg_weight_average_update(const aqg_weight_average* avg, void* stream);
+int aqg_gcn_train_step_avg(const aqg_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                           const aqg_optim* optim, const aqg_weight_average* avg, void* stream);
+int aqg_gcn_train_steps_avg(const aqg_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target,
+                            const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim,
+                            const aqg_weight_average* avg, void* stream);
+int aqg_gcn_train_step_general_avg(const aqg_train_general* t_host, const uint8_t* states72, const float* pi_target,
+                                   const float* z_target, int mode, const aqg_optim* optim, const aqg_weight_average* avg, void* stream);
+int aqg_gcn_train_steps_general_avg(const aqg_train_general* t_host, const uint8_t* states72, const float* pi_target,
+                                    const float* z_target, const int64_t* order, long long positions, float* loss_sums,
+                                    const aqg_optim* optim, const aqg_weight_average* avg, void* stream);
+int aqg_cnn_train_step_avg(const aqg_cnn_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                           const aqg_optim* optim, const aqg_weight_average* avg, void* stream);
+int aqg_cnn_train_steps_avg(const aqg_cnn_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target,
+                            const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim,
+                            const aqg_weight_average* avg, void* stream);
+
 /* ------------------------------------------------------------------ training augmentation (additive to ABI 15; the reference has none)
  *
  * Quoridor is symmetric under the left-right mirror of the board: column y -> N - 1 - y in each player's own frame.  The mirror of a
