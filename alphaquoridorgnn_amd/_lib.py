@@ -281,6 +281,11 @@ SIGNATURES = {
     "aqg_replay_surprise_rows": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp]),
     "aqg_replay_surprise_counts": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_longlong, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint64, _vp,
                                               _vp]),
+    "aqg_replay_row_metrics": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                          _c.c_int, _vp, _vp, _vp]),
+    "aqg_row_metrics_workspace_doubles": (_c.c_size_t, [_c.c_int, _c.c_int]),
+    "aqg_row_metrics_reduce": (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
+    "aqg_replay_holdout_mask": (_c.c_int, [_vp, _c.c_int, _c.c_uint64, _c.c_double, _vp, _vp]),
     "aqg_lambda_values": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _f32, _vp, _vp]),
     "aqg_host_legal_actions": (_c.c_int, [_c.c_int, _vp, _vp]),
     "aqg_host_next": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp]),

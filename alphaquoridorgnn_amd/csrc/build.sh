@@ -19,13 +19,13 @@ fi
 objs=()
 pids=()
 replaced=0
-for f in legal_mask state_check board_featuriser gcn_pack gcn_trunk_split gcn_trunk_exact gcn_boards_plain gcn_forward gcn_general gcn_boards_general gcn_train gcn_train_exact gcn_train_split gcn_train_final gcn_train_general grad_norm weight_average cnn_forward cnn_train mcts mcts_step mcts_eval mcts_move mcts_reuse mcts_improve mcts_record agents augment replay replay_refresh replay_merge replay_surprise value_targets capi; do
+for f in legal_mask state_check board_featuriser gcn_pack gcn_trunk_split gcn_trunk_exact gcn_boards_plain gcn_forward gcn_general gcn_boards_general gcn_train gcn_train_exact gcn_train_split gcn_train_final gcn_train_general grad_norm weight_average cnn_forward cnn_train mcts mcts_step mcts_eval mcts_move mcts_reuse mcts_improve mcts_record agents augment replay replay_refresh replay_merge replay_surprise row_metrics value_targets capi; do
   src=$f.hip
   for pair in ${AQG_REPLACE:-}; do
     if [ "${pair%%=*}" = "$f" ]; then src=${pair#*=}; replaced=$((replaced + 1)); fi
   done
-  if [ "$f" = mcts_step ] || [ "$f" = mcts_eval ] || [ "$f" = replay_surprise ] || [ "$f" = state_check ] || [ "$f" = value_targets ] || [ "$f" = weight_average ]; then
-    # the resource lines of the step kernels, of the evaluation launch, of the surprise kernels, of the record checker, of the lambda-return kernel and of the averaging kernel are kept: the budget checks below read them
+  if [ "$f" = mcts_step ] || [ "$f" = mcts_eval ] || [ "$f" = replay_surprise ] || [ "$f" = row_metrics ] || [ "$f" = state_check ] || [ "$f" = value_targets ] || [ "$f" = weight_average ]; then
+    # the resource lines of the step kernels, of the evaluation launch, of the surprise kernels, of the row-metrics kernels, of the record checker, of the lambda-return kernel and of the averaging kernel are kept: the budget checks below read them
     $HIPCC $FLAGS -Rpass-analysis=kernel-resource-usage -I. -c "$src" -o "${OBJDIR}/aqg_$f.o" 2> "${OBJDIR}/aqg_$f.remarks" &
   else
     $HIPCC $FLAGS -I. -c "$src" -o "${OBJDIR}/aqg_$f.o" &
@@ -47,12 +47,13 @@ if [ "$failed" -ne 0 ]; then
   grep -v "remark:" "${OBJDIR}/aqg_mcts_step.remarks" >&2 || true      # whatever mcts_step.hip's compile said besides the remarks
   grep -v "remark:" "${OBJDIR}/aqg_mcts_eval.remarks" >&2 || true
   grep -v "remark:" "${OBJDIR}/aqg_replay_surprise.remarks" >&2 || true
+  grep -v "remark:" "${OBJDIR}/aqg_row_metrics.remarks" >&2 || true
   grep -v "remark:" "${OBJDIR}/aqg_state_check.remarks" >&2 || true
   grep -v "remark:" "${OBJDIR}/aqg_value_targets.remarks" >&2 || true
   grep -v "remark:" "${OBJDIR}/aqg_weight_average.remarks" >&2 || true
   echo "build.sh: a compile job failed" >&2; exit 1
 fi
-grep -A3 "warning:" "${OBJDIR}/aqg_mcts_step.remarks" "${OBJDIR}/aqg_mcts_eval.remarks" "${OBJDIR}/aqg_replay_surprise.remarks" "${OBJDIR}/aqg_state_check.remarks" "${OBJDIR}/aqg_value_targets.remarks" "${OBJDIR}/aqg_weight_average.remarks" >&2 || true
+grep -A3 "warning:" "${OBJDIR}/aqg_mcts_step.remarks" "${OBJDIR}/aqg_mcts_eval.remarks" "${OBJDIR}/aqg_replay_surprise.remarks" "${OBJDIR}/aqg_row_metrics.remarks" "${OBJDIR}/aqg_state_check.remarks" "${OBJDIR}/aqg_value_targets.remarks" "${OBJDIR}/aqg_weight_average.remarks" >&2 || true
 # Register budget of the step kernels with the heads inside (engine_step_fast_kernel<9, CACHE, true, ..>, the form with policy workgroups
 # included: both kinds of its workgroups take step-sized slots): at most
 # 128 VGPRs and no scratch, or a step workgroup no longer fits beside a trunk workgroup.  The order of their load rounds is steered
@@ -76,6 +77,12 @@ awk '/Function Name:/ { k = ($0 ~ /replay_surprise_(rows|counts)_kernel/) ? $0 :
      k != "" && /ScratchSize/ { n++; v = $0; sub(/.*: /, "", v); if (v + 0 != 0) { print "build.sh: scratch in use: " k > "/dev/stderr"; bad = 1 } }
      END { if (n != 5) { print "build.sh: expected five surprise kernels in the resource remarks, found " n + 0 > "/dev/stderr"; bad = 1 } exit bad }' \
   "${OBJDIR}/aqg_replay_surprise.remarks" || exit 1
+# The row-metrics kernels (row_metrics.hip: four board sizes of the rows kernel, the two launches of the reduction and the hold-out
+# mask) carry float64 logarithms and exponentials in fully unrolled register arrays: no scratch, or the arrays have gone to memory.
+awk '/Function Name:/ { k = ($0 ~ /replay_row_metrics_kernel|row_metrics_(partial|total)_kernel|replay_holdout_mask_kernel/) ? $0 : "" }
+     k != "" && /ScratchSize/ { n++; v = $0; sub(/.*: /, "", v); if (v + 0 != 0) { print "build.sh: scratch in use: " k > "/dev/stderr"; bad = 1 } }
+     END { if (n != 7) { print "build.sh: expected seven row-metrics kernels in the resource remarks, found " n + 0 > "/dev/stderr"; bad = 1 } exit bad }' \
+  "${OBJDIR}/aqg_row_metrics.remarks" || exit 1
 # The record checker (state_check.hip, four board sizes): its wall masks and fill boards live in registers, no scratch.
 awk '/Function Name:/ { k = ($0 ~ /states72_check_kernel/) ? $0 : "" }
      k != "" && /ScratchSize/ { n++; v = $0; sub(/.*: /, "", v); if (v + 0 != 0) { print "build.sh: scratch in use: " k > "/dev/stderr"; bad = 1 } }

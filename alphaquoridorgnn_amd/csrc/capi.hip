@@ -705,6 +705,21 @@ int aqg_replay_surprise_counts(const int32_t* q, const int64_t* index, const int
                                          (hipStream_t)stream);
 }
 
+int aqg_replay_row_metrics(int board_size, int policy_size, const float* net_policy, const float* net_value, const uint8_t* states72,
+                           const float* ring_pi, const float* ring_z, const int64_t* index, int rows, int m, int offset, int n,
+                           int bucket_plies, int buckets, double* vals, int32_t* tag, void* stream) {
+    return launch_replay_row_metrics(board_size, policy_size, net_policy, net_value, states72, ring_pi, ring_z, index, rows, m, offset, n,
+                                     bucket_plies, buckets, vals, tag, (hipStream_t)stream);
+}
+size_t aqg_row_metrics_workspace_doubles(int m, int buckets) { return row_metrics_workspace_doubles(m, buckets); }
+int aqg_row_metrics_reduce(const double* vals, const int32_t* tag, int m, int buckets, double* partial, double* sums, int64_t* counts,
+                           void* stream) {
+    return launch_row_metrics_reduce(vals, tag, m, buckets, partial, sums, reinterpret_cast<long long*>(counts), (hipStream_t)stream);
+}
+int aqg_replay_holdout_mask(const int64_t* keys, int n, uint64_t seed, double share, uint8_t* mask, void* stream) {
+    return launch_replay_holdout_mask(keys, n, seed, share, mask, (hipStream_t)stream);
+}
+
 int aqg_lambda_values(int quota, int hp, const int32_t* game_plies, const int8_t* game_result, const uint8_t* game_done,
                       const float* hist_value, float lambda, float* out, void* stream) {
     return launch_lambda_values(quota, hp, game_plies, game_result, game_done, hist_value, lambda, out, (hipStream_t)stream);

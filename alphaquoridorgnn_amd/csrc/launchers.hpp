@@ -284,6 +284,15 @@ int launch_replay_surprise_rows(int N, int policy_size, const float* net_policy,
 int launch_replay_surprise_counts(const int32_t* q, const int64_t* index, const int64_t* total, int m, long long expected_rows,
                                   double uniform_share, int max_copies, uint64_t seed, uint64_t update, int32_t* count, hipStream_t st);
 
+// ---- row_metrics.hip
+int launch_replay_row_metrics(int N, int policy_size, const float* net_policy, const float* net_value, const uint8_t* states72,
+                              const float* ring_pi, const float* ring_z, const int64_t* index, int rows, int m, int offset, int n,
+                              int bucket_plies, int buckets, double* vals, int32_t* tag, hipStream_t st);
+size_t row_metrics_workspace_doubles(int m, int buckets);
+int launch_row_metrics_reduce(const double* vals, const int32_t* tag, int m, int buckets, double* partial, double* sums,
+                              long long* counts, hipStream_t st);
+int launch_replay_holdout_mask(const int64_t* keys, int n, uint64_t seed, double share, uint8_t* mask, hipStream_t st);
+
 // ---- value_targets.hip
 int launch_lambda_values(int quota, int hp, const int32_t* game_plies, const int8_t* game_result, const uint8_t* game_done,
                          const float* hist_value, float lambda, float* out, hipStream_t st);

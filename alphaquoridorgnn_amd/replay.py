@@ -7,7 +7,9 @@ This module holds ReplayWindow.  The rest of the family, every name importable f
                        Reanalyse's refresh in both forms and the draw of its rows (csrc/replay_refresh.hip), the position merge
                        (csrc/replay_merge.hip), policy surprise weighting (csrc/replay_surprise.hip), with their option checks;
   replay_merge.py      merge_positions, the position merge on the GPU (ReplayWindow.merged());
-  replay_surprise.py   surprise_index, the rows of an update drawn by KL(target || network) on the GPU (ReplayWindow.surprise_index).
+  replay_surprise.py   surprise_index, the rows of an update drawn by KL(target || network) on the GPU (ReplayWindow.surprise_index);
+  validation.py        row_metrics and holdout_split (csrc/row_metrics.hip): a network's held-out metrics per ply bucket, and the
+                       split of rows by position (ReplayWindow.row_metrics, ReplayWindow.holdout_split).
 The definitions are in include/aqgnn.h.
 """
 import pickle
@@ -22,7 +24,12 @@ from .replay_reference import (KEY_BYTES, MERGE_CHUNK, SURPRISE_K_MAX, SURPRISE_
                                append_reference, blend_targets, check_surprise_options, check_value_blend, draw_reanalyse_rows,
                                merge_depth, merge_reference, merge_runs_reference, position_keys, refresh_policy_reference,
                                refresh_reference, surprise_counts_reference, surprise_reference, surprise_weights)
+from .replay_reference import (HOLDOUT_STREAM, ROW_METRICS_CHUNK, ROW_METRICS_MAX_BUCKETS, ROW_METRICS_MAX_ROWS,  # noqa: F401
+                               ROW_METRICS_TINY, TAG_HIT, TAG_SIGN_AGREES, TAG_SIGN_COUNTED, check_holdout_options,
+                               check_row_metrics_options, holdout_reference, holdout_split_reference, row_metrics_reduce_reference,
+                               row_metrics_reference, row_metrics_workspace_doubles)
 from .replay_surprise import expand_rows, surprise_index  # noqa: F401
+from .validation import holdout_split, row_metrics
 
 
 class ReplayWindow:
@@ -123,6 +130,22 @@ class ReplayWindow:
             s72, pi, index = self._rings[0], self._rings[1], self._index
         return surprise_index(model, s72, pi, index, seed=seed, update=update, expected_rows=expected_rows, uniform_share=uniform_share,
                               max_copies=max_copies, chunk_rows=chunk_rows, stats=stats)
+
+    def holdout_split(self, share, seed=0):
+        """validation.holdout_split on the ring: (train_index, holdout_index) of the valid rows in age order, both naming ring slots.
+        A position held out under a seed is held out in every update, wherever it sits in the ring.  A host window runs the numpy
+        statements.  The ring, the bookkeeping and rows() are unchanged."""
+        if self._rings is None or self._valid == 0:
+            check_holdout_options(share, seed)
+            return self._index.clone(), self._index.clone()
+        return holdout_split(self._rings[0], self._index, share, seed, self.board_size)
+
+    def row_metrics(self, model, index=None, *, bucket_plies=8, buckets=16, chunk_rows=16384):
+        """validation.row_metrics on the ring: the Metrics of `model` on the ring slots `index` (None: every valid row, in age order)."""
+        s72, pi, z = self.rows() if self._rings is None else self._rings
+        if index is None and self._rings is not None:
+            index = self._index
+        return row_metrics(model, s72, pi, z, index, bucket_plies=bucket_plies, buckets=buckets, chunk_rows=chunk_rows)
 
     def clear(self):
         """Empty the window; the ring keeps its size."""

@@ -1,7 +1,7 @@
 """The replay window's kernels stated in numpy, on host arrays (numpy only: neither torch nor the library is imported) -- what the tests
 hold the launches to bit for bit, and what a ReplayWindow in host memory runs.  In the order of csrc/: the append and its blend
 (replay.hip), Reanalyse's refresh in both forms and the draw of its rows (replay_refresh.hip), the position merge (replay_merge.hip),
-policy surprise weighting (replay_surprise.hip).  Every name here is importable from alphaquoridorgnn_amd.replay as well."""
+policy surprise weighting (replay_surprise.hip), row metrics and the hold-out split (row_metrics.hip).  Every name here is importable from alphaquoridorgnn_amd.replay as well."""
 import numpy as np
 
 from .constants import MAX_LEGAL, check_board_size, num_actions
@@ -374,3 +374,186 @@ def surprise_counts_reference(q, rows_of_q, seed, update, expected_rows, uniform
     u = counter_uniform(stream_key(int(seed), int(update)), rows.astype(np.uint64))
     c = whole + (np.asarray(u, dtype=np.float64).reshape(m) < f - whole)
     return np.minimum(c, np.float64(C)).astype(np.int32)
+
+
+# ---- row metrics: what a network scores on held-out rows, and the split by position (csrc/row_metrics.hip)
+
+ROW_METRICS_MAX_ROWS = 1 << 24      # m at most (RM_MAX_ROWS)
+ROW_METRICS_MAX_BUCKETS = 64        # buckets at most (RM_MAX_BUCKETS); the tag's bucket field is 8 bits
+ROW_METRICS_TINY = np.float32(2.0 ** -126)      # the least p a logarithm is taken of (RM_TINY)
+ROW_METRICS_CHUNK = 4096            # rows of one workgroup column of the reduction's first launch (RMR_CHUNK)
+ROW_METRICS_LANES = 256             # lanes of such a workgroup (RMR_LANES)
+TAG_HIT, TAG_SIGN_COUNTED, TAG_SIGN_AGREES = 1 << 8, 1 << 9, 1 << 10
+HOLDOUT_STREAM = 0x686F6C646F7574   # AQG_HOLDOUT_STREAM: the sub-stream of a seed that splits positions
+
+
+def check_row_metrics_options(bucket_plies, buckets):
+    """Validate the bucket options as the library does: bucket_plies an int >= 1 (below 2^31), buckets an int in 1 .. 64.  Returns
+    them as ints."""
+    if int(bucket_plies) != bucket_plies or not 1 <= int(bucket_plies) < 1 << 31:
+        raise ValueError(f"bucket_plies must be an integer >= 1, not {bucket_plies}")
+    if int(buckets) != buckets or not 1 <= int(buckets) <= ROW_METRICS_MAX_BUCKETS:
+        raise ValueError(f"buckets must be an integer in 1 .. 64, not {buckets}")
+    return int(bucket_plies), int(buckets)
+
+
+def check_holdout_options(share, seed=0, every=1):
+    """Validate the hold-out options as the library and the loop do: share a float strictly inside (0, 1) and not NaN, seed an
+    integer (taken mod 2^64), every an integer >= 1.  Returns them as (float, int, int)."""
+    s = float(share)
+    if not 0.0 < s < 1.0:
+        raise ValueError(f"holdout share must be in (0, 1), not {share}")
+    if int(seed) != seed:
+        raise ValueError(f"holdout seed must be an integer, not {seed}")
+    if int(every) != every or int(every) < 1:
+        raise ValueError(f"holdout every must be an integer >= 1, not {every}")
+    return s, int(seed) & ((1 << 64) - 1), int(every)
+
+
+def _lane_sums(term):
+    """The kernel's sum of each row of term float64 [m,A]: lane l adds its entries l, l + 64, ... ascending to +0.0, then the
+    xor-shuffle reduction 32, 16, ..., 1.  float64 [m]."""
+    m, A = term.shape
+    passes = -(-A // 64)
+    lanes = np.zeros((m, passes * 64), dtype=np.float64)
+    lanes[:, :A] = term
+    lanes = lanes.reshape(m, passes, 64)
+    acc = np.zeros((m, 64), dtype=np.float64)
+    for s in range(passes):                                     # +0.0 + term is the term: an entry that adds nothing changes nothing
+        acc = acc + lanes[:, s]
+    lane = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[:, lane ^ off]
+    return acc[:, 0]
+
+
+def row_metrics_reference(states72, pi, z, net_policy, net_value, index=None, bucket_plies=8, buckets=16):
+    """aqg_replay_row_metrics in numpy (include/aqgnn.h, "row metrics"): (vals float64 [m,4], tag int32 [m]) of the rows index[0..m) of
+    (states72 uint8 [rows,72], pi float32 [rows,A], z float32 [rows]) (index None: rows 0..m-1) against net_policy float32 [m,A] and
+    net_value float32 [m], the network's outputs for each of those rows.  vals = {ce, ent, lp, se}, tag = bucket | hit << 8 | sign
+    counted << 9 | sign agrees << 10; a rejected row -- a non-finite entry in t, p, v or z, a negative target entry, no positive target
+    entry, an index entry outside the arrays -- has zeros and the tag `buckets`.  Every sum in float64 in the kernel's order
+    (_lane_sums); where the kernel's libm and numpy's differ (ln, exp) the results differ by their rounding, everything else is the
+    kernel's bits."""
+    bucket_plies, buckets = check_row_metrics_options(bucket_plies, buckets)
+    s72, t_all, z_all, p, v = np.asarray(states72), np.asarray(pi), np.asarray(z), np.asarray(net_policy), np.asarray(net_value)
+    if s72.dtype != np.uint8 or s72.ndim != 2 or s72.shape[1] != 72:
+        raise ValueError("row_metrics_reference: states72 must be uint8 [rows,72]")
+    rows = s72.shape[0]
+    if (t_all.dtype != np.float32 or t_all.ndim != 2 or t_all.shape[0] != rows or z_all.dtype != np.float32 or z_all.shape != (rows,)
+            or p.dtype != np.float32 or p.ndim != 2 or p.shape[1] != t_all.shape[1] or v.dtype != np.float32 or v.shape != p.shape[:1]):
+        raise ValueError("row_metrics_reference: pi float32 [rows,A], z float32 [rows], net_policy float32 [m,A], net_value float32 [m]")
+    m, A = p.shape
+    where = np.arange(m, dtype=np.int64) if index is None else np.asarray(index, dtype=np.int64)
+    if where.shape != (m,) or m > ROW_METRICS_MAX_ROWS or (index is None and m > rows):
+        raise ValueError("row_metrics_reference: one network row per row of index (or of pi), 2^24 at most")
+    inside = (where >= 0) & (where < rows)
+    t = np.zeros((m, A), dtype=np.float32)
+    zz = np.zeros((m,), dtype=np.float32)
+    ply = np.zeros((m,), dtype=np.int64)
+    t[inside], zz[inside] = t_all[where[inside]], z_all[where[inside]]
+    ply[inside] = s72[where[inside], 68].astype(np.int64) | (s72[where[inside], 69].astype(np.int64) << 8)
+    vals, tag = np.zeros((m, 4), dtype=np.float64), np.full((m,), buckets, dtype=np.int32)
+    if m == 0:
+        return vals, tag
+    with np.errstate(all="ignore"):
+        bad = (~np.isfinite(t).all(axis=1) | ~np.isfinite(p).all(axis=1) | (t < 0).any(axis=1) | ~np.isfinite(v) | ~np.isfinite(zz))
+        positive = t > 0
+        ok = inside & ~bad & positive.any(axis=1)
+        pc = np.where(p > ROW_METRICS_TINY, p, ROW_METRICS_TINY).astype(np.float64)
+        td, pd = t.astype(np.float64), p.astype(np.float64)
+        ts = np.where(positive, td, 1.0)
+        s_ce = _lane_sums(np.where(positive, ts * np.log(pc), 0.0))
+        s_ent = _lane_sums(np.where(positive, ts * np.log(ts), 0.0))
+        s_t, s_e, s_tp = _lane_sums(td), _lane_sums(np.exp(pd)), _lane_sums(td * pd)
+        lp = s_t * np.log(s_e)
+        d = v.astype(np.float64) - zz.astype(np.float64)
+        full = np.stack((0.0 - s_ce, 0.0 - s_ent, lp - s_tp, d * d), axis=1)
+        first = (p == p.max(axis=1, keepdims=True)).argmax(axis=1)         # the least index that holds the maximum
+        hit = t[np.arange(m), first] == t.max(axis=1)
+        counted = zz != 0
+        agrees = counted & (v.astype(np.float64) * zz.astype(np.float64) > 0)
+    bucket = np.minimum(ply // bucket_plies, buckets - 1)
+    word = bucket | np.where(hit, TAG_HIT, 0) | np.where(counted, TAG_SIGN_COUNTED, 0) | np.where(agrees, TAG_SIGN_AGREES, 0)
+    vals[ok], tag[ok] = full[ok], word[ok].astype(np.int32)
+    return vals, tag
+
+
+def row_metrics_workspace_doubles(m, buckets):
+    """aqg_row_metrics_workspace_doubles: ceil(m / 4096) * (buckets + 1) * 8, or 0 for m == 0 or an argument out of range."""
+    if not 1 <= m <= ROW_METRICS_MAX_ROWS or not 1 <= buckets <= ROW_METRICS_MAX_BUCKETS:
+        return 0
+    return -(-m // ROW_METRICS_CHUNK) * (buckets + 1) * 8
+
+
+def row_metrics_reduce_reference(vals, tag, buckets=16):
+    """aqg_row_metrics_reduce in numpy, both launches: (sums float64 [buckets+1,4], counts int64 [buckets+1,4]) -- per bucket the sums
+    of vals {ce, ent, lp, se} and the counts {rows, hits, signs counted, signs agreeing}; row `buckets` is the rejected rows'.
+    Launch one: for every chunk of 4,096 rows and every bucket, lane l of 256 adds the rows l, l + 256, ... of the chunk in ascending
+    order whose tag names the bucket to +0.0; each wavefront's 64 lanes reduce by the xor-shuffle 32, 16, ..., 1; the four wave results
+    are added in wave order.  Launch two: per bucket, lane l of 64 adds the chunk partials l, l + 64, ... ascending to +0.0, then the
+    same shuffle.  A tag whose bucket field is above `buckets` belongs to no bucket."""
+    _, buckets = check_row_metrics_options(1, buckets)
+    x, w = np.asarray(vals), np.asarray(tag)
+    if x.dtype != np.float64 or x.ndim != 2 or x.shape[1] != 4 or w.dtype != np.int32 or w.shape != x.shape[:1]:
+        raise ValueError("row_metrics_reduce_reference: vals must be float64 [m,4] and tag int32 [m]")
+    m = x.shape[0]
+    if m > ROW_METRICS_MAX_ROWS:
+        raise ValueError("row_metrics_reduce_reference: 2^24 rows at most")
+    C, L = ROW_METRICS_CHUNK, ROW_METRICS_LANES
+    chunks = -(-m // C)
+    field = w & 255
+    flags = np.stack((np.ones((m,), np.int64), (w >> 8) & 1, (w >> 9) & 1, (w >> 10) & 1), axis=1).astype(np.int64)
+    lane64 = np.arange(64)
+    partial = np.zeros((chunks, buckets + 1, 4), dtype=np.float64)
+    counts = np.zeros((buckets + 1, 4), dtype=np.int64)
+    with np.errstate(all="ignore"):
+        for c in range(chunks):
+            xs = np.zeros((C, 4), dtype=np.float64)
+            fs = np.full((C,), -1, dtype=np.int64)
+            k = min(C, m - c * C)
+            xs[:k], fs[:k] = x[c * C:c * C + k], field[c * C:c * C + k]
+            xs, fs = xs.reshape(C // L, L, 4), fs.reshape(C // L, L)
+            for b in np.unique(fs[fs >= 0]):
+                if b > buckets:
+                    continue
+                acc = np.zeros((L, 4), dtype=np.float64)
+                for r in range(C // L):                         # a row of another bucket adds nothing: the accumulator keeps its bits
+                    acc = np.where((fs[r] == b)[:, None], acc + xs[r], acc)
+                acc = acc.reshape(L // 64, 64, 4)
+                for off in (32, 16, 8, 4, 2, 1):
+                    acc = acc + acc[:, lane64 ^ off]
+                waves = acc[:, 0]
+                partial[c, b] = ((waves[0] + waves[1]) + waves[2]) + waves[3]
+        sums = np.zeros((buckets + 1, 4), dtype=np.float64)
+        for b in range(buckets + 1):
+            padded = np.zeros((-(-max(chunks, 1) // 64) * 64, 4), dtype=np.float64)
+            padded[:chunks] = partial[:, b]
+            acc = np.zeros((64, 4), dtype=np.float64)
+            for r in range(padded.shape[0] // 64):
+                acc = acc + padded[r * 64:(r + 1) * 64]
+            for off in (32, 16, 8, 4, 2, 1):
+                acc = acc + acc[lane64 ^ off]
+            sums[b] = acc[0]
+            counts[b] = flags[field == b].sum(axis=0)
+    return sums, counts
+
+
+def holdout_reference(keys, seed, share):
+    """aqg_replay_holdout_mask in numpy, bit for bit: uint8 [n], 1 where counter_uniform(stream_key(seed, HOLDOUT_STREAM), key) <
+    share -- keys int64 [n] from position_keys, read as unsigned.  A position's side depends on (seed, its key bytes) alone."""
+    share, seed, _ = check_holdout_options(share, seed)
+    k = np.asarray(keys)
+    if k.dtype != np.int64 or k.ndim != 1:
+        raise ValueError("holdout_reference: keys must be int64 [n]")
+    u = counter_uniform(stream_key(seed, HOLDOUT_STREAM), k.view(np.uint64))
+    return (np.asarray(u, dtype=np.float64).reshape(k.shape) < share).astype(np.uint8)
+
+
+def holdout_split_reference(states72, index, share, seed):
+    """The split on host arrays: (train_index, holdout_index), both int64 in input order, of the rows index[0..n) (None: all rows)
+    of states72 uint8 [rows,72] -- position_keys, holdout_reference and two nonzeros."""
+    s = np.asarray(states72)
+    rows = np.arange(s.shape[0], dtype=np.int64) if index is None else np.asarray(index, dtype=np.int64)
+    mask = holdout_reference(position_keys(s, rows), seed, share).astype(bool)
+    return rows[~mask], rows[mask]

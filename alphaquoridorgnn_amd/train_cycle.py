@@ -235,6 +235,22 @@ def _parser():
     ap.add_argument("--surprise-seed", type=int, default=None, metavar="S",
                     help="parameter update, with --surprise-weighting: seed of the draws that round a row's expected copies (default "
                          "TRAIN_SURPRISE_SEED = 0)")
+    ap.add_argument("--holdout-share", type=float, default=None, metavar="S",
+                    help="parameter update: hold a share S in (0, 1) of the POSITIONS out of every update -- a position's side is a "
+                         "function of (--holdout-seed, its record) alone -- and validate the network on them after the epochs "
+                         "(default TRAIN_HOLDOUT_SHARE = None: off, nothing is launched)")
+    ap.add_argument("--holdout-seed", type=int, default=None, metavar="K",
+                    help="parameter update, with --holdout-share: seed of the split (default TRAIN_HOLDOUT_SEED = 0); a run that "
+                         "changes it between cycles trains on positions it held out before")
+    ap.add_argument("--holdout-every", type=int, default=None, metavar="V",
+                    help="parameter update, with --holdout-share: validate after every V-th epoch, and always after the last (default "
+                         "TRAIN_HOLDOUT_EVERY = 1)")
+    ap.add_argument("--keep-best-epoch", action="store_true",
+                    help="parameter update, with --holdout-share: save as latest.pth the network of the validated epoch with the "
+                         "least held-out policy loss + value MSE (default TRAIN_HOLDOUT_KEEP_BEST = False: the last epoch's)")
+    ap.add_argument("--holdout-log", default=None, metavar="PATH",
+                    help="parameter update, with --holdout-share: append one JSON line per update to PATH -- the validation curve, the "
+                         "per-bucket table of the saved network, the split's counts and the options in force")
     ap.add_argument("--no-history-file", action="store_true",
                     help="self-play: write no .history file (needs --replay-generations; default SP_WRITE_HISTORY = True)")
     ap.add_argument("--reanalyse-rows", type=int, default=None, metavar="R",
@@ -414,6 +430,34 @@ def _set_surprise_options(args):
         tn.TRAIN_SURPRISE_UNIFORM_SHARE, tn.TRAIN_SURPRISE_MAX_COPIES, tn.TRAIN_SURPRISE_SEED = checked
 
 
+def _check_holdout_args(args):
+    """--holdout-share / --holdout-seed / --holdout-every / --keep-best-epoch / --holdout-log, refused at parse time: a share outside
+    (0, 1), V < 1, and any of the others without --holdout-share.  Returns (share, seed, every) with the defaults filled in, or None
+    when the option is off."""
+    from . import train_network as tn
+    from .replay import check_holdout_options
+    if args.holdout_share is None:
+        if args.holdout_seed is not None or args.holdout_every is not None or args.keep_best_epoch or args.holdout_log is not None:
+            raise ValueError("--holdout-seed, --holdout-every, --keep-best-epoch and --holdout-log need --holdout-share")
+        return None
+    seed = tn.TRAIN_HOLDOUT_SEED if args.holdout_seed is None else args.holdout_seed
+    every = tn.TRAIN_HOLDOUT_EVERY if args.holdout_every is None else args.holdout_every
+    try:
+        share, _, every = check_holdout_options(args.holdout_share, seed, every)
+    except ValueError as err:
+        raise ValueError(f"--holdout-share / --holdout-seed / --holdout-every: {err}") from None
+    return share, int(seed), every
+
+
+def _set_holdout_options(args):
+    """The checked hold-out flags onto train_network's constants (the stage reads them at call time)."""
+    from . import train_network as tn
+    checked = _check_holdout_args(args)
+    if checked is not None:
+        tn.TRAIN_HOLDOUT_SHARE, tn.TRAIN_HOLDOUT_SEED, tn.TRAIN_HOLDOUT_EVERY = checked
+        tn.TRAIN_HOLDOUT_KEEP_BEST, tn.TRAIN_HOLDOUT_LOG = bool(args.keep_best_epoch), args.holdout_log
+
+
 def _set_replay_options(args):
     """--replay-generations / --replay-rows / --epoch-rows / --merge-positions / --no-history-file onto self_play's and train_network's hooks: one
     ReplayWindow on this rank's GPU that self-play fills and the parameter update trains on, preloaded from the newest K .history
@@ -572,6 +616,7 @@ def main(argv=None):
     _check_reanalyse_policy_args(args)
     _check_policy_args(args)
     _check_surprise_args(args)
+    _check_holdout_args(args)
     _check_start_args(args)
     _check_value_lambda_args(args)
     _check_average_args(args)
@@ -594,6 +639,7 @@ def main(argv=None):
     _set_average_options(args)
     _set_replay_options(args)
     _set_surprise_options(args)
+    _set_holdout_options(args)
     _set_reanalyse_options(args)
     _set_policy_options(args)
     _set_start_options(args)

@@ -51,6 +51,15 @@ TRAIN_MAX_GRAD_NORM = None    # M: torch.nn.utils.clip_grad_norm_(params, M) in 
 # HIP steps (include/aqgnn.h "weight averaging", WeightAverage below) and saved as latest.pth in place of the last iterate.
 TRAIN_EMA_DECAY = None        # d in [0, 1): e <- d e + (1 - d) p behind every TRAIN_EMA_EVERY-th Adam update; None = off, no object built
 TRAIN_EMA_EVERY = 1           # K >= 1: the updates are made at the Adam steps whose number is a multiple of K
+# Held-out validation (validation.row_metrics / holdout_split; the reference has no held-out set): a share of the POSITIONS -- a
+# position's side is a function of (TRAIN_HOLDOUT_SEED, its record's key bytes) alone, so it is the same in every update and every
+# generation -- is kept out of the update, split off the recorded rows before the merge and the surprise draw, and the network that
+# would be saved now is measured on those rows (one row per occurrence, unmerged, unmirrored) after the epochs.
+TRAIN_HOLDOUT_SHARE = None        # S in (0, 1); None = off: nothing is launched, latest.pth is what it was
+TRAIN_HOLDOUT_SEED = 0
+TRAIN_HOLDOUT_EVERY = 1           # V >= 1: validate after every V-th epoch, and always after the last
+TRAIN_HOLDOUT_KEEP_BEST = False   # True: save the snapshot of the validated epoch with the least policy_loss + value_mse (first minimum)
+TRAIN_HOLDOUT_LOG = None          # a path: one JSON line per update is appended (curve, table, counts, options)
 
 
 def load_data():
@@ -70,9 +79,44 @@ def _training_rows(dev, board_size, model=None):
     TRAIN_SURPRISE_WEIGHTING (needs `model`, the network the update starts from): behind the merge, the index expanded by policy
     surprise (replay.surprise_index) -- some rows named several times, some not at all; every rank draws the same index, with no
     collective, and advances the update counter (the window's when one is trained on, else the module's) alike."""
+    return _update_rows(dev, board_size, model)[:4]
+
+
+def _update_rows(dev, board_size, model=None):
+    """_training_rows with the held-out side beside it: (s, p, v, index, held).  TRAIN_HOLDOUT_SHARE None: held is None and nothing
+    is launched.  Otherwise the recorded rows' index is split by position (validation.holdout_split) BEFORE the merge and the surprise
+    draw, which -- like TRAIN_EPOCH_ROWS, the mirror and the trainers -- then act on the training side alone; held = dict(rows=(s, p,
+    v) as recorded, index=the held-out rows of them in input order, one per occurrence, counts=dict(rows, held, train, distinct)).
+    Every rank splits alike, with no collective.  An empty side is a ValueError naming the share."""
     import torch.distributed as dist
     s, p, v, index = _recorded_rows(dev, board_size)
     rank0 = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+    held = None
+    if TRAIN_HOLDOUT_SHARE is not None:
+        index, held = _held_out_rows(s, p, v, index, board_size, rank0)
+    s, p, v, index = _merged_and_drawn(s, p, v, index, board_size, model, rank0)
+    return s, p, v, index, held
+
+
+def _held_out_rows(s, p, v, index, board_size, rank0):
+    """(the training side's index, the held dict of _update_rows) of the recorded rows (s, p, v, index)."""
+    from .replay_reference import KEY_BYTES
+    from .validation import holdout_split
+    n = int(s.shape[0] if index is None else index.shape[0])
+    train_index, held_index = holdout_split(s, index, TRAIN_HOLDOUT_SHARE, TRAIN_HOLDOUT_SEED, board_size)
+    h = int(held_index.shape[0])
+    if h == 0 or h == n:
+        raise ValueError(f"TRAIN_HOLDOUT_SHARE = {TRAIN_HOLDOUT_SHARE}: of {n} rows {h} are held out and {n - h} trained on under seed "
+                         f"{TRAIN_HOLDOUT_SEED}; both sides need a row")
+    key_bytes = torch.from_numpy(KEY_BYTES).to(s.device)
+    distinct = int(torch.unique(s.index_select(0, held_index).index_select(1, key_bytes), dim=0).shape[0])
+    if rank0:
+        print(f"held out: {h} of {n} rows ({distinct} distinct positions)")
+    return train_index, dict(rows=(s, p, v), index=held_index, counts=dict(rows=n, held=h, train=n - h, distinct=distinct))
+
+
+def _merged_and_drawn(s, p, v, index, board_size, model, rank0):
+    """The merge and the surprise draw of _training_rows, on the rows (s, p, v, index)."""
     if TRAIN_MERGE_POSITIONS:
         from .replay import merge_positions
         n = int(s.shape[0] if index is None else index.shape[0])
@@ -766,13 +810,92 @@ def _configured_controls():
     return dict(weight_decay=TRAIN_WEIGHT_DECAY, decoupled=TRAIN_DECOUPLED, max_grad_norm=TRAIN_MAX_GRAD_NORM)
 
 
-def _progress_line(epoch, policy_loss, value_loss, trainer):
+def _progress_line(epoch, policy_loss, value_loss, trainer, val=None):
     """The per-epoch progress line (train_network.py:100); with clipping on, the epoch's mean gradient norm beside it (one host read of
-    grad_norms per epoch)."""
+    grad_norms per epoch); val (a validation.Metrics of this epoch): the held-out numbers behind it."""
     line = f"\rEpoch {epoch + 1}/{NUM_EPOCH} | Policy Loss: {float(policy_loss):.4f} | Value Loss: {float(value_loss):.4f}"
     if trainer.max_grad_norm and trainer.grad_norms.numel():
         line += f" | Grad Norm: {float(trainer.grad_norms.mean()):.4f}"
+    if val is not None:
+        line += f" | Val Loss: {val.policy_loss:.4f} / {val.value_mse:.4f} | Val KL: {val.kl:.4f} | Top-1: {val.top1:.3f}"
     return line
+
+
+class _Holdout:
+    """The held-out side of one update (_update_rows' held dict): validates the network that would be saved now, keeps the curve and,
+    with TRAIN_HOLDOUT_KEEP_BEST, the snapshot of the best validated epoch.  With a weight average the network validated is a twin
+    module, built once through `load` and filled by average.copy_to(twin) at every validation; otherwise the model itself.  Every rank
+    holds one and decides alike: no collective."""
+
+    def __init__(self, held, model, average, load, dev):
+        from .replay_reference import check_holdout_options
+        self.share, self.seed, self.every = check_holdout_options(TRAIN_HOLDOUT_SHARE, TRAIN_HOLDOUT_SEED, TRAIN_HOLDOUT_EVERY)
+        self.keep_best = bool(TRAIN_HOLDOUT_KEEP_BEST)
+        self.rows, self.index, self.counts = held["rows"], held["index"], held["counts"]
+        self.model, self.average = model, average
+        self.twin = None if average is None else load(PV_NETWORK_PATH + 'best.pth', dev)
+        self.curve, self.last, self.best, self.best_epoch, self.best_score, self.snapshot = [], None, None, None, None, None
+
+    def due(self, epoch):
+        return (epoch + 1) % self.every == 0 or epoch + 1 == NUM_EPOCH
+
+    def validate(self, epoch):
+        """The Metrics of the network that would be saved after `epoch` (0-based), added to the curve."""
+        from .validation import row_metrics
+        target = self.model
+        if self.average is not None:
+            self.average.copy_to(self.twin)
+            target = self.twin
+        self.last = row_metrics(target, *self.rows, self.index)
+        score = self.last.policy_loss + self.last.value_mse             # the loss the update minimises
+        self.curve.append(dict(epoch=epoch + 1, score=score, **self.last.totals()))
+        if self.best_score is None or score < self.best_score:          # on ties the first minimum stays
+            self.best, self.best_epoch, self.best_score = self.last, epoch + 1, score
+            if self.keep_best:
+                self.snapshot = self._saved_now()
+        return self.last
+
+    def _saved_now(self):
+        """What torch.save would write now, as device clones: the average's tensors with a weight average, else the model's."""
+        if self.average is not None:
+            return self.average.state_dict()
+        state = self.model.state_dict()                                  # the OrderedDict itself is kept: its _metadata is saved too
+        for k in state:
+            state[k] = state[k].detach().clone()
+        return state
+
+    def saved(self):
+        """The Metrics of the network that is saved: the kept epoch's with TRAIN_HOLDOUT_KEEP_BEST, else the last validation's."""
+        return self.best if self.keep_best else self.last
+
+    def report(self):
+        lines = []
+        if self.keep_best:
+            lines.append(f"kept epoch {self.best_epoch}/{NUM_EPOCH}: held-out policy loss + value MSE = {self.best_score:.4f}")
+        lines.append(self.saved().table())
+        return "\n".join(lines)
+
+    def log_line(self):
+        """The JSON line of TRAIN_HOLDOUT_LOG: the curve, the per-bucket table of the saved network, the split's counts, the options
+        in force.  A number that is not finite (a ratio over no row) is written as null."""
+        import json
+        options = dict(share=self.share, seed=self.seed, every=self.every, keep_best=self.keep_best, epochs=NUM_EPOCH,
+                       ema_decay=TRAIN_EMA_DECAY, ema_every=TRAIN_EMA_EVERY, merge_positions=bool(TRAIN_MERGE_POSITIONS),
+                       surprise_weighting=bool(TRAIN_SURPRISE_WEIGHTING), mirror=bool(TRAIN_MIRROR), epoch_rows=TRAIN_EPOCH_ROWS,
+                       weight_decay=TRAIN_WEIGHT_DECAY, max_grad_norm=TRAIN_MAX_GRAD_NORM)
+        record = dict(curve=self.curve, saved_epoch=self.best_epoch if self.keep_best else self.curve[-1]["epoch"],
+                      table=self.saved().as_dict(), split=self.counts, options=options)
+        return json.dumps(_finite_or_none(record))
+
+
+def _finite_or_none(x):
+    if isinstance(x, dict):
+        return {k: _finite_or_none(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_finite_or_none(v) for v in x]
+    if isinstance(x, float) and not np.isfinite(x):
+        return None
+    return x
 
 
 def trainer_for(model, max_batch=BATCH_SIZE):
@@ -834,11 +957,12 @@ def _train_loop(load, make_trainer, rank, world):
     from . import distributed as aqd
     dev = aqd.device()                                                             # this rank's GPU, explicitly
     model = load(PV_NETWORK_PATH + 'best.pth', dev)                                # GNNNetwork, or the shape best.pth holds
-    s, p, v, index = _training_rows(dev, model.board_size, model=model)
+    s, p, v, index, held = _update_rows(dev, model.board_size, model=model)
     n = s.shape[0] if index is None else index.shape[0]
     trainer = make_trainer(model, max_batch=BATCH_SIZE)
     # every rank keeps its own average of its own (identical) parameters: no collective
     average = None if TRAIN_EMA_DECAY is None else WeightAverage(trainer, decay=TRAIN_EMA_DECAY, every=TRAIN_EMA_EVERY)
+    holdout = None if held is None else _Holdout(held, model, average, load, dev)      # every rank validates and decides alike
     for epoch in range(NUM_EPOCH):
         lr = LEARNING_RATE * lr_lambda(epoch)                                      # LambdaLR, stepped once per epoch (:98)
         perm = torch.randperm(n, device=dev)                                    # DataLoader(shuffle=True), last batch kept
@@ -864,13 +988,22 @@ def _train_loop(load, make_trainer, rank, world):
                     pl, vl = trainer.step(*_augment_launch(model.board_size, s, p, v, idx.contiguous(), mirror), lr=lr)
                 epoch_policy_loss += pl
                 epoch_value_loss += vl
+        val = holdout.validate(epoch) if holdout is not None and holdout.due(epoch) else None
         if rank == 0:
-            print(_progress_line(epoch, epoch_policy_loss, epoch_value_loss, trainer), end='')
+            print(_progress_line(epoch, epoch_policy_loss, epoch_value_loss, trainer, val), end='')
     if rank == 0:
         print('')
         if average is not None:
             print(average.summary_line())
-        torch.save(model.state_dict() if average is None else average.state_dict(), PV_NETWORK_PATH + 'latest.pth')
+        if holdout is not None and NUM_EPOCH > 0:
+            print(holdout.report())
+            if TRAIN_HOLDOUT_LOG is not None:
+                with open(TRAIN_HOLDOUT_LOG, "a") as f:
+                    f.write(holdout.log_line() + "\n")
+        if holdout is not None and holdout.keep_best and holdout.snapshot is not None:
+            torch.save(holdout.snapshot, PV_NETWORK_PATH + 'latest.pth')
+        else:
+            torch.save(model.state_dict() if average is None else average.state_dict(), PV_NETWORK_PATH + 'latest.pth')
     if world > 1:
         dist.barrier()          # latest.pth is complete before any rank moves on to the evaluation stage
 

@@ -1193,6 +1193,64 @@ int aqg_replay_surprise_rows(int board_size, int policy_size, const float* net_p
 int aqg_replay_surprise_counts(const int32_t* q, const int64_t* index, const int64_t* total, int m, long long expected_rows,
                                double uniform_share, int max_copies, uint64_t seed, uint64_t update, int32_t* count, void* stream);
 
+/* ------------------------------------------------------------------ row metrics (additive to ABI 15; the reference has no held-out set)
+ *
+ * What a network scores on rows no update trains on, under one fixed definition (csrc/row_metrics.hip; validation.row_metrics and
+ * validation.holdout_split drive the entry points, replay.row_metrics_reference, replay.row_metrics_reduce_reference and
+ * replay.holdout_reference state them in numpy).  A row has a policy target t (f32 [A]) and a value target z (f32), the ply
+ * ply = rec[68] | rec[69] << 8 of its record, and the network's softmaxed policy p (f32 [A]) and tanh value v (f32) of that record.
+ * Everything below is float64 from the f32 inputs, no operation contracted:
+ *
+ *   ce  = -sum over {a : t_a > 0} of t_a * ln max(p_a, 2^-126)       the true cross-entropy
+ *   ent = -sum over {a : t_a > 0} of t_a * ln t_a                    the target's entropy; KL = ce - ent is formed by the caller
+ *   lp  = (sum_a t_a) * ln(sum_b exp(p_b)) - sum_a t_a p_a           the trainers' policy loss term (gcn_train_heads.hpp: the
+ *                                                                    reference's double softmax), so that the held-out number
+ *                                                                    compares with the line the loop prints
+ *   se  = (v - z)^2, the difference and the square in float64: exact up to one rounding
+ *   hit = 1 iff t[a*] == max_a t, a* the first maximum of p (the least index whose p equals the maximum): tied targets all count
+ *   the value sign is counted iff z != 0; it agrees iff (double)v * (double)z > 0
+ *   bucket = min(ply / bucket_plies, buckets - 1), 1 <= buckets <= 64, bucket_plies >= 1
+ *   A row is REJECTED -- it contributes to no sum and is counted in the extra bucket `buckets` -- if t, p, v or z has a non-finite
+ *   entry, t has a negative entry (-0.0 is not one), t has no positive entry, or its index entry is outside the ring (such a row is
+ *   not read).
+ *
+ * Summation order of a row: lane l of 64 adds its own entries a = l, l + 64, ... in ascending order to +0.0 (an entry that adds
+ * nothing adds +0.0), then the xor-shuffle wave reduction 32, 16, ..., 1 -- five sums: S_ce = sum t ln max(p, 2^-126) and S_ent = sum
+ * t ln t over t > 0, S_t = sum t, S_e = sum exp(p), S_tp = sum t p over all entries; ce = 0 - S_ce, ent = 0 - S_ent, lp = S_t *
+ * ln(S_e) - S_tp (a product, then a difference).  The first maximum is the wave maximum of the value, then the least index among the
+ * entries that hold it.
+ *
+ * aqg_replay_row_metrics: one chunk of n rows whose network outputs the caller has just computed -- net_policy f32 [n,A] and net_value
+ *   f32 [n], row i of the chunk being row offset + i of the m: its targets and record are row index[offset + i] of ring_pi f32
+ *   [rows,A], ring_z f32 [rows] and states72 u8 [rows,72] (index == NULL: row offset + i); vals[offset + i] = {ce, ent, lp, se} (f64
+ *   [m,4]; zeros for a rejected row) and tag[offset + i] (i32 [m]) = bucket in bits 0-7 (`buckets` for a rejected row), hit in bit 8,
+ *   sign counted in bit 9, sign agrees in bit 10.  The geometry is aqg_replay_surprise_rows': 16 rows per workgroup, 4 per wavefront,
+ *   all their loads in flight before the first use; no LDS, no atomics, no scratch.
+ *   Refused: an unsupported board size, a policy_size that is not the board's A, m < 0 or m > 2^24, rows < 0, m > rows without an
+ *   index, a chunk outside the m rows, buckets outside 1..64, bucket_plies < 1, a NULL array (with n > 0), an output overlapping a
+ *   source (of a gathered ring one row is assumed) or the other output.  n == 0 returns 0 without looking at a pointer.
+ * aqg_row_metrics_reduce: sums f64 [buckets+1,4] = the sums of vals per bucket, counts i64 [buckets+1,4] = rows, hits, signs counted,
+ *   signs agreeing per bucket (exact); row `buckets` of both is the rejected rows' (its sums are zeros).  A fixed-order sum without
+ *   atomics, two launches: (1) workgroup (c, b) of 256 lanes takes the 4,096 rows of chunk c; lane l adds the rows l, l + 256, ... in
+ *   ascending order whose tag names bucket b to +0.0; wave_xor_sum; the four wave results added in wave order ((w0 + w1) + w2) + w3;
+ *   partial[c][b] stored.  (2) one wavefront per bucket adds the chunk partials lane, lane + 64, ... ascending to +0.0, then
+ *   wave_xor_sum.  partial: aqg_row_metrics_workspace_doubles(m, buckets) doubles = ceil(m / 4096) * (buckets + 1) * 8 (0 for m == 0 or
+ *   an argument out of range).  m == 0 stores zero tables and needs neither vals, tag nor partial.
+ *   Refused: m < 0 or m > 2^24, buckets outside 1..64, sums or counts NULL, vals, tag or partial NULL with m > 0, an output
+ *   overlapping a source or another output.
+ * aqg_replay_holdout_mask: mask[i] (u8) = counter_uniform(stream_key(seed, AQG_HOLDOUT_STREAM), (uint64)keys[i]) < share, one lane per
+ *   row; keys i64 [n] from aqg_replay_position_keys, so a position lands on one side under a seed wherever and however often it
+ *   occurs.  Refused: n < 0, share outside (0, 1) or NaN, keys or mask NULL (with n > 0), mask overlapping keys.
+ * All three refuse on the host, before any launch (-1, aqg_last_error). */
+#define AQG_HOLDOUT_STREAM 0x686F6C646F7574ull      /* "holdout": the sub-stream of a seed that splits positions */
+int aqg_replay_row_metrics(int board_size, int policy_size, const float* net_policy, const float* net_value, const uint8_t* states72,
+                           const float* ring_pi, const float* ring_z, const int64_t* index, int rows, int m, int offset, int n,
+                           int bucket_plies, int buckets, double* vals, int32_t* tag, void* stream);
+size_t aqg_row_metrics_workspace_doubles(int m, int buckets);
+int aqg_row_metrics_reduce(const double* vals, const int32_t* tag, int m, int buckets, double* partial, double* sums, int64_t* counts,
+                           void* stream);
+int aqg_replay_holdout_mask(const int64_t* keys, int n, uint64_t seed, double share, uint8_t* mask, void* stream);
+
 /* ------------------------------------------------------------------ start positions (additive to ABI 15; the reference starts every game from the opening)
  *
  * Games that start from caller-given records: opening books, paired matches, forks of recorded positions.  Off by default: without
