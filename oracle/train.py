@@ -78,7 +78,7 @@ def train_steps(params, batches, lr=0.001, epoch_of_step=None):
                 gparam["lr"] = lr * lr_lambda(epoch_of_step[i])
         policy, value = model(recs)
         pl = ce(policy, torch.tensor(np.asarray(pi), dtype=torch.float64))
-        vl = mse(value.squeeze(), torch.tensor(np.asarray(z), dtype=torch.float64))
+        vl = mse(value.view(-1), torch.tensor(np.asarray(z), dtype=torch.float64))
         loss = pl + vl
         opt.zero_grad()
         loss.backward()

@@ -90,7 +90,7 @@ def _ref_step(net, recs, pi, z):
     p = {k: v.clone().requires_grad_(True) for k, v in _params64(net).items()}
     policy, value, _ = _ref_forward(p, net.num_gcn_layers, recs)
     pl = torch.nn.CrossEntropyLoss()(policy, torch.tensor(np.asarray(pi), dtype=torch.float64))
-    vl = torch.nn.MSELoss()(value.squeeze(), torch.tensor(np.asarray(z), dtype=torch.float64))
+    vl = torch.nn.MSELoss()(value.view(-1), torch.tensor(np.asarray(z), dtype=torch.float64))
     (pl + vl).backward()
     keys = [k for k, _ in net._ordered_params()]
     return [p[k].grad.numpy() for k in keys], float(pl.detach()), float(vl.detach())
