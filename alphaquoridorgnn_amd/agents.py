@@ -21,6 +21,7 @@ import random
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
+import torch
 
 from . import _lib
 from .constants import NUM_PLIES_FOR_DRAW, NUM_WALLS, board_params
@@ -177,7 +178,6 @@ def default_threads():
 
 def _records(states72):
     """[B,72] uint8 records from an array, a tensor, or a sequence of States / records (host or device, as given)."""
-    import torch
     if isinstance(states72, torch.Tensor):
         return states72.to(torch.uint8).reshape(-1, 72)
     if isinstance(states72, np.ndarray):
@@ -186,7 +186,6 @@ def _records(states72):
 
 
 def _device_batch(states72, device):
-    import torch
     dev = _lib.require_gpu(device)
     recs = _records(states72)
     d = (recs if isinstance(recs, torch.Tensor) else torch.from_numpy(recs)).to(dev).contiguous()
@@ -197,7 +196,6 @@ def _device_batch(states72, device):
 
 def _draw_source(uniforms, B, dev):
     """(table tensor or None, stride) of a call.  uniforms: None = the generator; else float64 [B, n], row b = the draws of state b."""
-    import torch
     if uniforms is None:
         return None, 0
     u = torch.as_tensor(np.asarray(uniforms, dtype=np.float64) if not isinstance(uniforms, torch.Tensor) else uniforms,
@@ -217,7 +215,6 @@ def _check_draws(draws, stride, what):
 
 def random_action_device(states, N, seed=0, uniforms=None):
     """aqg_agent_random on device records [B,72]: int32 [B] device tensor, -1 where a state has no legal action."""
-    import torch
     dev = states.device
     B = int(states.shape[0])
     u, stride = _draw_source(uniforms, B, dev)
@@ -238,7 +235,6 @@ def playout_batch(states72, seed=0, uniforms=None, return_final=False, device=No
     """playout() from every state at once (aqg_playouts): (value, plies, draws) int32 [B] numpy arrays -- the value from the START
     state's mover's view, the moves played, the draws consumed -- and the final records uint8 [B,72] with return_final.  Draws:
     row b of `uniforms` [B, n] in order, or draw_uniforms(seed, b, .)."""
-    import torch
     dev, d, N = _device_batch(states72, device)
     B = int(d.shape[0])
     u, stride = _draw_source(uniforms, B, dev)
@@ -278,7 +274,6 @@ _explore_dev = {}
 def mcts_action_device(states, N, evaluations=100, seed=0, uniforms=None):
     """aqg_agent_mcts on device records [B,72]: (action i32 [B], visits i32 [B,MAX_LEGAL], actions u8 [B,MAX_LEGAL], count i32 [B],
     draws i32 [B]) device tensors."""
-    import torch
     dev = states.device
     lib = _lib.load()
     B, E = int(states.shape[0]), int(evaluations)
@@ -324,7 +319,6 @@ ALPHA_BETA_DEVICE_MIN_STATES = 5
 def shortest_paths_batch(states72, device=None):
     """shortest_path of every state and of its flipped state (aqg_agent_shortest_paths): int32 [B,2] (numpy), column 0 the
     mover's plies to its goal row, column 1 the other side's; -1 = walled in."""
-    import torch
     dev, d, N = _device_batch(states72, device)
     out = torch.empty((int(d.shape[0]), 2), dtype=torch.int32, device=dev)
     _lib.check(_lib.load().aqg_agent_shortest_paths(N, _lib.ptr(d), int(d.shape[0]), _lib.ptr(out), _lib.stream_ptr(dev)),
@@ -353,7 +347,6 @@ def alpha_beta_action_device(states, N, max_depth=2, active=None, return_nodes=F
     """aqg_agent_alpha_beta on device records [B,72]: int32 [B] device tensor, -1 where a state has no legal action, 0 where
     `active` (uint8 [B] device tensor, an engine's game_active) is 0.  No host synchronisation.  With return_nodes also the
     positions visited per state, int64 [B]."""
-    import torch
     dev = states.device
     lib = _lib.load()
     B, depth = int(states.shape[0]), _check_depth(max_depth)
@@ -376,7 +369,6 @@ def alpha_beta_action_batch(states72, max_depth=2, threads=None, backend="host",
     backend 'host' (the default; no GPU needed): the native host search from a pool of `threads` threads (default
     default_threads(); ctypes releases the GIL during a search).  backend 'hip': the kernel (aqg_agent_alpha_beta, max_depth up to
     AB_MAX_DEPTH, one board size per call); the same actions."""
-    import torch
     if backend not in ("host", "hip"):
         raise ValueError(f"backend must be 'host' or 'hip', got {backend!r}")
     if backend == "hip":
