@@ -26,6 +26,7 @@ import datetime
 import os
 
 import torch
+import torch.distributed as dist
 
 _state = {"initialised_here": False, "seq": 0}
 
@@ -36,14 +37,14 @@ def device():
 
 
 def is_distributed():
-    import torch.distributed as dist
-    return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    return rank_world()[1] > 1
 
 
-def rank_world():
-    import torch.distributed as dist
+def rank_world(group=None):
+    """(this process's rank, the number of ranks) in `group` (None: the default process group) -- (0, 1) where torch.distributed
+    is not built or no process group is initialised.  The one place that asks."""
     if dist.is_available() and dist.is_initialized():
-        return dist.get_rank(), dist.get_world_size()
+        return dist.get_rank(group), dist.get_world_size(group)
     return 0, 1
 
 
@@ -51,7 +52,6 @@ def init_from_env(backend=None):
     """Bind this process to its GPU and join the process group described by torchrun's environment (RANK, WORLD_SIZE,
     LOCAL_RANK, MASTER_ADDR, MASTER_PORT).  A plain `python -m ...` start (no WORLD_SIZE, or WORLD_SIZE=1) stays single-process.
     Returns (rank, world_size)."""
-    import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -95,7 +95,6 @@ def shutdown(ok=True):
     """Leave the group.  ok=True (clean exit): all ranks meet in a barrier first.  ok=False (this rank is unwinding an exception):
     NO barrier -- the other ranks may never reach one -- the group is destroyed (aborted where the backend offers it) and the caller
     re-raises, so the launcher sees the failure at once."""
-    import torch.distributed as dist
     if _state["initialised_here"] and dist.is_initialized():
         if ok:
             dist.barrier()
@@ -113,12 +112,10 @@ def shutdown(ok=True):
 
 def collective_device():
     """Where the small control tensors of a collective live: the rank's GPU under RCCL, the host under gloo."""
-    import torch.distributed as dist
     return device() if dist.get_backend() == "nccl" else torch.device("cpu")
 
 
 def _store():
-    import torch.distributed as dist
     try:
         return dist.distributed_c10d._get_default_store()
     except Exception:

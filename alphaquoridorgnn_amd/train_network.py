@@ -1,24 +1,29 @@
 """Parameter update -- drop-in for the reference's train_network.py, on the GNN, with the whole optimisation step in HIP.
 
-Call surface kept (train_network.py:14-107): NUM_EPOCH, BATCH_SIZE, load_data, train_network.  One step = one C call
-(`aqg_gcn_train_step`, csrc/gcn_train.hip): forward, the reference's losses (CrossEntropyLoss on the already-softmaxed
-policy + MSELoss, train_network.py:54-55,85-86), backward, Adam (:56,:90-92), all fp32.  The parameters updated are the
-model's own state_dict tensors; torch is used for memory, shuffling and the .pth / .history files only.
+Call surface kept (train_network.py:14-107): NUM_EPOCH, BATCH_SIZE, load_data, train_network.  One step = one C call (trainers.py).
+The parameters updated are the model's own state_dict tensors; torch is used for memory, shuffling and the .pth / .history files only.
+
+What is here reads this module's settings (NUM_EPOCH, BATCH_SIZE, PV_NETWORK_PATH, TRAIN_*) when it is called: the rows of an update,
+the held-out side, the epoch loop.  What takes everything it needs as arguments lives beside it and is imported back, so every name
+is still found here: the trainers (trainers.py), the weight average (weight_average.py), the mirror launch (train_augment.py) and
+the numpy statements the tests compare with (train_reference.py).
 """
-import ctypes
 import pickle
 from pathlib import Path
 
 import numpy as np
 import torch
 
-from . import _lib
-from .constants import PV_NETWORK_PATH, BOARD_SIZE, num_actions
-from .pv_network_gnn import STATE_DICT_KEYS, HIDDEN_DIM, NUM_FEATURES, load_network, pack_states
+from . import distributed as aqd
+from .constants import PV_NETWORK_PATH, BOARD_SIZE  # noqa: F401
+from .pv_network_gnn import STATE_DICT_KEYS, HIDDEN_DIM, NUM_FEATURES, load_network, pack_states  # noqa: F401
+from .train_augment import draw_mirror_flips, _mirror_arguments, _augment_launch, augment_gather  # noqa: F401
+from .train_reference import (LEARNING_RATE, clip_coefficient, adam_reference, weight_average_reference,  # noqa: F401
+                              weight_average_due, check_average_controls, _checked_average_controls)
+from .trainers import BATCH_SIZE, default_decay_mask, grad_norm, _Trainer, GNNTrainer, GeneralTrainer, CNNTrainer  # noqa: F401
+from .weight_average import weight_average_table, WeightAverage  # noqa: F401
 
 NUM_EPOCH = 100    # train_network.py:14
-BATCH_SIZE = 128   # train_network.py:15
-LEARNING_RATE = 0.001   # train_network.py:56
 # Mirror-symmetry augmentation (the reference has none): every epoch trains on each position either as recorded or mirrored left
 # to right, drawn per (TRAIN_MIRROR_SEED, epoch, position) -- one fused gather + flip launch in place of the epoch's three gathers.
 TRAIN_MIRROR = False      # False = off: the reference's epochs
@@ -48,7 +53,7 @@ TRAIN_WEIGHT_DECAY = 0.0      # c of the AlphaZero loss term c * ||theta||^2, as
 TRAIN_DECOUPLED = True        # True: torch.optim.AdamW's decay; False: torch.optim.Adam(weight_decay=)'s
 TRAIN_MAX_GRAD_NORM = None    # M: torch.nn.utils.clip_grad_norm_(params, M) in front of every update; None = off
 # Weight averaging (the reference saves the last Adam iterate): an exponential moving average of the parameters, updated inside the
-# HIP steps (include/aqgnn.h "weight averaging", WeightAverage below) and saved as latest.pth in place of the last iterate.
+# HIP steps (include/aqgnn.h "weight averaging", weight_average.WeightAverage) and saved as latest.pth in place of the last iterate.
 TRAIN_EMA_DECAY = None        # d in [0, 1): e <- d e + (1 - d) p behind every TRAIN_EMA_EVERY-th Adam update; None = off, no object built
 TRAIN_EMA_EVERY = 1           # K >= 1: the updates are made at the Adam steps whose number is a multiple of K
 # Held-out validation (validation.row_metrics / holdout_split; the reference has no held-out set): a share of the POSITIONS -- a
@@ -88,9 +93,8 @@ def _update_rows(dev, board_size, model=None):
     draw, which -- like TRAIN_EPOCH_ROWS, the mirror and the trainers -- then act on the training side alone; held = dict(rows=(s, p,
     v) as recorded, index=the held-out rows of them in input order, one per occurrence, counts=dict(rows, held, train, distinct)).
     Every rank splits alike, with no collective.  An empty side is a ValueError naming the share."""
-    import torch.distributed as dist
     s, p, v, index = _recorded_rows(dev, board_size)
-    rank0 = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+    rank0 = aqd.rank_world()[0] == 0
     held = None
     if TRAIN_HOLDOUT_SHARE is not None:
         index, held = _held_out_rows(s, p, v, index, board_size, rank0)
@@ -135,7 +139,7 @@ def _surprise_rows(model, s, p, index, rank0):
     from .replay import surprise_index
     if model is None:
         raise ValueError("TRAIN_SURPRISE_WEIGHTING: _training_rows needs the network the update starts from (model=)")
-    window = TRAIN_WINDOW if TRAIN_WINDOW is not None and len(TRAIN_WINDOW) > 0 else None
+    window = _active_window()
     if window is not None:
         update = window.surprise_updates
         window.surprise_updates += 1
@@ -151,10 +155,15 @@ def _surprise_rows(model, s, p, index, rank0):
     return index
 
 
+def _active_window():
+    """TRAIN_WINDOW when it holds a row, else None: an empty window is the file route."""
+    return TRAIN_WINDOW if TRAIN_WINDOW is not None and len(TRAIN_WINDOW) > 0 else None
+
+
 def _recorded_rows(dev, board_size):
     """_training_rows before any merge: one row per occurrence."""
     from .replay import ReplayWindow
-    window = TRAIN_WINDOW if TRAIN_WINDOW is not None and len(TRAIN_WINDOW) > 0 else None
+    window = _active_window()
     if window is None and TRAIN_GENERATIONS > 1:
         window = ReplayWindow(board_size, max_generations=TRAIN_GENERATIONS, device=dev)
         window.extend_from_files(sorted(Path('./data').glob('*.history'))[-TRAIN_GENERATIONS:])
@@ -187,622 +196,6 @@ def lr_lambda(epoch):
         return 0.5
     return 1.0
 
-
-def draw_mirror_flips(seed, epoch, n):
-    """The flips of source rows 0 .. n-1 in epoch `epoch` under `seed`, uint8 [n] -- the seeded draw of aqg_augment_gather in numpy
-    (include/aqgnn.h): row r is mirrored iff f(K(seed, epoch), r) < 0.5 with the counter-based generator of agents.draw_uniforms.
-    A pure function of (seed, epoch, r): a prefix of a longer draw is the shorter draw."""
-    from .agents import draw_uniforms
-    return (draw_uniforms(seed, epoch, n) < 0.5).astype(np.uint8)
-
-
-def _mirror_arguments(mirror, rows, dev):
-    """(flips tensor or None, use_seed, seed, epoch) of a `mirror` argument: a uint8 [rows] device table indexed by source row, or
-    (seed, epoch).  Shapes and types only -- nothing is read back from the device."""
-    if isinstance(mirror, torch.Tensor):
-        if mirror.dtype != torch.uint8 or mirror.dim() != 1 or mirror.shape[0] != rows or mirror.device != dev:
-            raise ValueError(f"a mirror table is a uint8 [{rows}] tensor on {dev}, one entry per source row")
-        return mirror.contiguous(), 0, 0, 0
-    try:
-        seed, epoch = mirror
-        seed, epoch = int(seed), int(epoch)
-    except (TypeError, ValueError):
-        raise ValueError("mirror is None, a uint8 device table indexed by source row, or (seed, epoch)") from None
-    if epoch < 0:
-        raise ValueError("mirror: the epoch must be >= 0")
-    return None, 1, seed & ((1 << 64) - 1), epoch
-
-
-def _augment_launch(board_size, states72, pi, z, order, mirror):
-    """The fused launch on contiguous device tensors of one device: (out72, out_pi, out_z), None where the input is None.  order:
-    int64 source rows, NOT checked here (augment_gather checks them); mirror: as _mirror_arguments, or None for a plain gather."""
-    src = next(x for x in (states72, pi, z) if x is not None)
-    dev, rows = src.device, int(src.shape[0])
-    n = rows if order is None else int(order.shape[0])
-    flips, use_seed, seed, epoch = (None, 0, 0, 0) if mirror is None else _mirror_arguments(mirror, rows, dev)
-    outs = [None if x is None else torch.empty((n,) + tuple(x.shape[1:]), dtype=x.dtype, device=dev) for x in (states72, pi, z)]
-    A = num_actions(board_size)
-    _lib.check(_lib.load().aqg_augment_gather(board_size, A, _lib.ptr(states72), _lib.ptr(pi), _lib.ptr(z), _lib.ptr(order),
-                                              _lib.ptr(flips), use_seed, seed, epoch, n, _lib.ptr(outs[0]), _lib.ptr(outs[1]),
-                                              _lib.ptr(outs[2]), _lib.stream_ptr(dev)), "aqg_augment_gather")
-    return tuple(outs)
-
-
-def augment_gather(states72, pi, z, order=None, flips=None, seed=None, epoch=0, board_size=BOARD_SIZE):
-    """Gather and mirror training rows in one launch (aqg_augment_gather): output row i is source row order[i] (None: row i),
-    mirrored iff flips[that source row] is set -- or, with flips None and a seed, iff draw_mirror_flips(seed, epoch, rows) says so.
-    With neither it is a plain gather.  states72 uint8 [rows,72], pi float32 [rows,A], z float32 [rows]: device tensors, each may be
-    None (and so is its output).  Returns (out72, out_pi, out_z), freshly allocated, with len(order) rows (any number, none
-    included).  order is checked against the row count with one host read."""
-    given = [x for x in (states72, pi, z) if x is not None]
-    if not given:
-        raise ValueError("augment_gather: at least one of states72, pi, z is needed")
-    dev = _lib.require_gpu(given[0].device)
-    rows = int(given[0].shape[0])
-    A = num_actions(board_size)
-    for x, name, dtype, tail in ((states72, "states72", torch.uint8, (72,)), (pi, "pi", torch.float32, (A,)), (z, "z", torch.float32, ())):
-        if x is not None and (x.device != dev or x.dtype != dtype or tuple(x.shape) != (rows,) + tail):
-            raise ValueError(f"augment_gather: {name} must be a {dtype} {[rows, *tail]} tensor on {dev} ({board_size}x{board_size} board)")
-    states72, pi, z = (None if x is None else x.contiguous() for x in (states72, pi, z))
-    if order is not None:
-        order = order.to(dev, torch.int64).contiguous()
-        if order.dim() != 1:
-            raise ValueError("augment_gather: order is a 1-D tensor of source rows")
-        if order.numel():
-            lo, hi = torch.stack((order.min(), order.max())).tolist()          # the one host read
-            if lo < 0 or hi >= rows:
-                raise ValueError(f"augment_gather: order holds a row outside 0..{rows - 1}")
-    if flips is not None and seed is not None:
-        raise ValueError("augment_gather: give flips or seed, not both")
-    mirror = flips if flips is not None else None if seed is None else (seed, epoch)
-    return _augment_launch(board_size, states72, pi, z, order, mirror)
-
-
-def clip_coefficient(norm, max_norm):
-    """The factor torch.nn.utils.clip_grad_norm_(params, max_norm) multiplies every gradient by, in float32 as the kernels take it:
-    min(1, max_norm / (norm + 1e-6)) -- exactly 1.0 when nothing is clipped; a NaN norm gives NaN (torch.clamp's minimum)."""
-    c = np.float32(max_norm) / (np.float32(norm) + np.float32(1e-6))
-    return np.float32(1.0) if c > np.float32(1.0) else np.float32(c)
-
-
-def adam_reference(p, g, m, v, step, lr=LEARNING_RATE, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, coef=1.0):
-    """One update of one tensor as the finish kernels take it (csrc/train_adam.hpp), in numpy float32: clip (g <- coef g), weight
-    decay (decoupled, torch.optim.AdamW: p <- p (1 - lr wd); coupled, torch.optim.Adam(weight_decay=): g <- g + wd p), then
-    torch.optim.Adam's update with the bias corrections of `step` (1-based) computed in float64.  Returns (p, m, v), new arrays."""
-    f = np.float32
-    p, g, m, v = (np.asarray(x, dtype=f) for x in (p, g, m, v))
-    lr, b1, b2, eps, wd = f(lr), f(betas[0]), f(betas[1]), f(eps), f(weight_decay)
-    g = f(coef) * g
-    if wd != 0:
-        if decoupled:
-            p = p * (f(1) - lr * wd)
-        else:
-            g = g + wd * p
-    bc1 = f(1.0 - float(b1) ** step)
-    bc2_sqrt = f(np.sqrt(1.0 - float(b2) ** step))
-    m = b1 * m + (f(1) - b1) * g
-    v = b2 * v + (f(1) - b2) * g * g
-    denom = np.sqrt(v) / bc2_sqrt + eps
-    return p - (lr / bc1) * (m / denom), m, v
-
-
-def default_decay_mask(params, decay_all=False):
-    """Which tensors weight decay applies to: those of two or more dimensions (GCN and linear weights, conv kernels) -- not biases,
-    not BatchNorm weight and bias -- unless decay_all."""
-    return [bool(decay_all) or p.dim() >= 2 for p in params]
-
-
-def grad_norm(t):
-    """The L2 norm of a contiguous float32 device tensor (or view), as a 0-dim device tensor: the deterministic two-stage reduction
-    of gradient clipping (aqg_grad_norm, csrc/grad_norm.hip), no host read."""
-    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < 1:
-        raise ValueError("grad_norm takes a non-empty contiguous float32 tensor")
-    dev = _lib.require_gpu(t.device)
-    lib = _lib.load()
-    n = int(t.numel())
-    nws = int(lib.aqg_optim_workspace_floats(n))
-    if nws == 0:
-        _lib.check(-1, "aqg_optim_workspace_floats (more elements than the reduction takes)")
-    ws = torch.empty((nws,), dtype=torch.float32, device=dev)
-    out = torch.empty((1,), dtype=torch.float32, device=dev)
-    _lib.check(lib.aqg_grad_norm(_lib.ptr(t), n, _lib.ptr(out), _lib.ptr(ws), nws, _lib.stream_ptr(dev)), "aqg_grad_norm")
-    return out[0]
-
-
-def weight_average_reference(avg, src, decay):
-    """One update of the weight average (include/aqgnn.h "weight averaging") in numpy float32: with d = float32(decay) and
-    w = float32(1.0 - float(d)), e' = f32(d * e) + f32(w * p) -- two rounded products and one rounded sum, bit for bit
-    torch.optim.swa_utils.get_ema_avg_fn(float(d)) on CPU tensors.  Returns a new array."""
-    f = np.float32
-    d = f(decay)
-    w = f(1.0 - float(d))
-    return d * np.asarray(avg, dtype=f) + w * np.asarray(src, dtype=f)
-
-
-def weight_average_due(step, every):
-    """Whether the average is updated behind the Adam update of 1-based step `step`: at the multiples of `every`, wherever an epoch
-    or a library call ends."""
-    return int(step) % int(every) == 0
-
-
-def weight_average_table(averages, sources):
-    """The launch's tensor table (include/aqgnn.h "weight averaging") of device tensors averages[i] <- sources[i]: (the host copy, a
-    ctypes int64 array of 4 T + 1 words; the device copy, an int64 tensor; the total number of chunks).  Pointers, element counts
-    and the prefix of the per-tensor chunk counts, a chunk being 4,096 floats of the 16-byte grid the average's base sits in."""
-    T, C = len(averages), _lib.WEIGHT_AVERAGE_CHUNK
-    prefix = [0]
-    for e in averages:
-        prefix.append(prefix[-1] + (e.numel() + ((e.data_ptr() >> 2) & 3) + C - 1) // C)
-    words = [e.data_ptr() for e in averages] + [p.data_ptr() for p in sources] + [p.numel() for p in sources] + prefix
-    return (ctypes.c_int64 * (4 * T + 1))(*words), torch.tensor(words, dtype=torch.int64, device=averages[0].device), prefix[-1]
-
-
-def _checked_average_controls(decay, every):
-    """(decay as the float32 the kernel takes, every as int), refused as the library refuses them."""
-    try:
-        d = np.float32(decay)
-    except (TypeError, ValueError):
-        raise ValueError("the weight average's decay is a number in [0, 1)") from None
-    if not (d >= 0 and d < 1):                               # a NaN fails both; a decay that rounds to 1.0f is refused too
-        raise ValueError(f"the weight average's decay must be in [0, 1) as a float32 (got {decay!r})")
-    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
-        raise ValueError(f"the weight average's every must be an integer >= 1 (got {every!r})")
-    return float(d), int(every)
-
-
-class _Trainer:
-    """What the three trainers share: the Adam state and the flat gradient buffer, the optimiser controls, step() (single process or
-    data parallel), outputs() and run_epoch().  A subclass names its library calls (_STEP, _STEPS) and provides the batch-mean losses
-    of a single-process step (_batch_losses) and what an update must tell the model (_updated).
-
-    Optimiser controls (all off by default: the plain entry points, the same launches as ever): weight_decay (torch's coefficient) on
-    the tensors default_decay_mask picks (every tensor with decay_all), decoupled as torch.optim.AdamW (True) or coupled as
-    torch.optim.Adam(weight_decay=) (False), and max_grad_norm = torch.nn.utils.clip_grad_norm_'s max_norm (None or 0 = off).  They
-    are plain attributes read at every call, so a schedule may change them between steps.  With clipping on, last_grad_norm is the
-    unclipped global gradient norm of the last step (0-dim device tensor) and grad_norms that of every step of the last run_epoch
-    (device tensor [steps]); neither is read by the host."""
-
-    _GPU_REFUSAL = None       # a subclass's own words for a model that is not on the GPU (raised in front of require_gpu's)
-
-    def _setup(self, model, params, max_batch, betas, eps, controls, buffers=(), workspace=None):
-        """The constructors' shared part: the checks of `params` (and `buffers`, tensors the kernels write besides them), the Adam
-        state with every gradient a view of ONE flat buffer (the data-parallel exchange is a single all-reduce), the optimiser
-        controls and the counters.  workspace, for the two workspace trainers: (the library's workspace-size call, its shape
-        arguments in front of the batch); their outputs and workspace are allocated here."""
-        self.model, self.lib, self.params, self.buffers = model, _lib.load(), list(params), list(buffers)
-        what = "parameters and running statistics" if self.buffers else "parameters"
-        for x in self.params + self.buffers:
-            if x.dtype != torch.float32 or not x.is_contiguous():
-                raise ValueError(f"training needs contiguous float32 {what}")
-        if self._GPU_REFUSAL and self.params[0].device.type != "cuda":
-            raise ValueError(self._GPU_REFUSAL)
-        self.dev = _lib.require_gpu(self.params[0].device)
-        if any(x.device != self.dev for x in self.params + self.buffers):
-            raise ValueError(f"every {'parameter and running statistic' if self.buffers else 'parameter'} must be on the trainer's GPU")
-        self.flat_grads = torch.zeros((sum(p.numel() for p in self.params),), dtype=torch.float32, device=self.dev)
-        self.grads, off = [], 0
-        for p in self.params:
-            self.grads.append(self.flat_grads[off:off + p.numel()].view_as(p))
-            off += p.numel()
-        self.adam_m = [torch.zeros_like(p) for p in self.params]
-        self.adam_v = [torch.zeros_like(p) for p in self.params]
-        self.weight_decay, self.decoupled, self.decay_all, self.max_grad_norm = controls
-        self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=self.dev)
-        self.grad_norms = torch.zeros((0,), dtype=torch.float32, device=self.dev)
-        self._optim_ws = None
-        self.average = None                       # a WeightAverage attaches itself here: the calls then take their _avg forms
-        self.N, self.A = model.board_size, model.policy_output_size
-        self.max_batch, self.step_count = int(max_batch), 0
-        self.betas, self.eps = betas, eps
-        if workspace is not None:
-            if self.max_batch < 1:
-                raise ValueError("max_batch must be >= 1")
-            name, shape = workspace
-            nws = int(getattr(self.lib, name)(self.N, *shape, self.A, self.max_batch))
-            if nws == 0:
-                _lib.check(-1, f"{name} (shape or board size outside the kernels' limits)")
-            f = dict(dtype=torch.float32, device=self.dev)
-            self.ws = dict(workspace=torch.empty((nws,), **f), pol=torch.empty((self.max_batch, self.A), **f),
-                           val=torch.empty((self.max_batch,), **f), loss=torch.empty((self.max_batch, 2), **f),
-                           loss_mean=torch.zeros((2,), **f))
-
-    def _fill(self, t):
-        """What every trainer's struct takes the same way: the board, Adam's constants, the params / grads / adam_m / adam_v pointer
-        arrays where the struct has them, and the workspace trainers' outputs and workspace."""
-        self.t = t
-        t.board_size, t.policy_size = self.N, self.A
-        t.beta1, t.beta2, t.eps = float(self.betas[0]), float(self.betas[1]), float(self.eps)
-        for name in ("params", "grads", "adam_m", "adam_v"):
-            for i, x in enumerate(getattr(self, name) if hasattr(t, name) else ()):
-                getattr(t, name)[i] = x.data_ptr()
-        if "workspace" in self.ws:
-            t.policy, t.value, t.loss, t.loss_mean = (self.ws[k].data_ptr() for k in ("pol", "val", "loss", "loss_mean"))
-            t.workspace, t.workspace_floats = self.ws["workspace"].data_ptr(), self.ws["workspace"].numel()
-
-    def _optim(self, steps):
-        """(aqg_optim for a call of `steps` steps, the device tensor its norms go to) -- (None, None) with every control off."""
-        wd = float(self.weight_decay or 0.0)
-        clip = float(self.max_grad_norm or 0.0)
-        if wd == 0.0 and clip == 0.0:
-            return None, None
-        o = _lib.OptimStruct()
-        o.decoupled = 1 if self.decoupled else 0
-        if wd != 0.0:
-            mask = default_decay_mask(self.params, self.decay_all)
-            o.num_tensors = len(mask)
-            o._wd = (ctypes.c_float * len(mask))(*[wd if d else 0.0 for d in mask])       # kept alive by the struct object
-            o.weight_decay = ctypes.cast(o._wd, ctypes.POINTER(ctypes.c_float))
-        norms = None
-        if clip != 0.0:
-            if self._optim_ws is None:
-                nws = int(self.lib.aqg_optim_workspace_floats(self.flat_grads.numel()))
-                self._optim_ws = torch.empty((nws,), dtype=torch.float32, device=self.dev)
-            norms = torch.zeros((steps,), dtype=torch.float32, device=self.dev)
-            o.max_grad_norm = clip
-            o.grad_norm = norms.data_ptr()
-            o.workspace, o.workspace_floats = self._optim_ws.data_ptr(), self._optim_ws.numel()
-        return o, norms
-
-    def _invoke(self, name, args, steps, plain=False, updating=True):
-        """One library call of `steps` steps: `name` itself when plain or with every control off (no aqg_optim is built), its
-        _optim form otherwise -- or, with a weight average attached and a call that updates, its _avg form (the controls' struct or
-        NULL beside the average's).  Returns the device tensor the call's norms went to, or None."""
-        o, norms = (None, None) if plain else self._optim(steps)
-        average = None if plain or not updating else self.average
-        if average is not None:
-            a = average._struct()
-            name, controls = name + "_avg", (None if o is None else ctypes.byref(o), ctypes.byref(a))
-        else:
-            name, controls = (name, ()) if o is None else (name + "_optim", (ctypes.byref(o),))
-        _lib.check(getattr(self.lib, name)(ctypes.byref(self.t), *args, *controls, _lib.stream_ptr(self.dev)), name)
-        if average is not None:
-            average._stepped(int(self.t.step), steps, a.every)
-        return norms
-
-    def _call(self, states72, pi_target, z_target, mode, plain=False):
-        norms = self._invoke(self._STEP, (_lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target), mode), 1, plain,
-                             updating=mode >= 1)
-        if norms is not None:
-            self.last_grad_norm = norms[0]
-
-    def step(self, states72, pi_target, z_target, lr=LEARNING_RATE, update=True, group=None, mirror=None):
-        """One optimisation step.  states72 uint8 [B,72], pi_target float32 [B,A], z_target float32 [B] (device tensors).
-        Returns (policy_loss, value_loss) as 0-dim device tensors -- no host synchronisation.
-        mirror (None = off): a uint8 [B] device table, or (seed, epoch) for the seeded draw keyed by the row's index in THIS batch:
-        the step trains on the batch with those rows mirrored left to right (one launch in front of it, aqg_augment_gather).
-
-        Data parallel (torch.distributed initialised, world > 1): every rank passes ITS shard of the global batch; the
-        local mean-loss gradients are weighted by B_local / B_global, summed with ONE all-reduce of the flat gradient buffer
-        (RCCL over xGMI with backend nccl) and applied by every rank, so all replicas take the step a single process would
-        take on the whole batch (up to fp32 summation order)."""
-        import torch.distributed as dist
-        B = int(states72.shape[0])
-        if B > self.max_batch:
-            raise ValueError("batch larger than the trainer's workspace")
-        states72 = states72.to(self.dev, torch.uint8).contiguous()
-        pi_target = pi_target.to(self.dev, torch.float32).contiguous()
-        z_target = z_target.to(self.dev, torch.float32).contiguous()
-        if mirror is not None:
-            states72, pi_target, z_target = _augment_launch(self.N, states72, pi_target, z_target, None, mirror)
-        world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
-        if update:
-            self.step_count += 1
-        self.t.batch, self.t.step, self.t.lr = B, max(self.step_count, 1), float(lr)
-        if world == 1:
-            self._call(states72, pi_target, z_target, 1 if update else 0)
-            loss = self._batch_losses(B) if B else torch.zeros((2,), device=self.dev)
-        else:
-            if B:
-                self._call(states72, pi_target, z_target, 0, plain=True)      # the norm that counts is the all-reduced gradient's
-                lsum = self.ws["loss"][:B].sum(dim=0)
-            else:                                                  # a rank may hold no position of a ragged last batch
-                self.flat_grads.zero_()
-                lsum = torch.zeros((2,), device=self.dev)
-            tot = torch.cat([lsum, torch.tensor([float(B)], device=self.dev)])
-            dist.all_reduce(tot, group=group)                      # global loss sums and global batch size
-            self.flat_grads.mul_(float(B) / tot[2])                # local mean-loss gradient -> its share of the global mean
-            dist.all_reduce(self.flat_grads, group=group)
-            if update:
-                self._call(states72, pi_target, z_target, 2)
-            loss = tot[:2] / tot[2]
-        if update:
-            self._updated()
-        return loss[0], loss[1]
-
-    def outputs(self, B):
-        """(policy [B,A], value [B]) of the last step's forward pass."""
-        return self.ws["pol"][:B], self.ws["val"][:B]
-
-    def run_epoch(self, states72, pi_target, z_target, order, lr=LEARNING_RATE, batch=None, pre_shuffle=True, mirror=None):
-        """All optimisation steps of one epoch in ONE library call (single process): step i trains on the positions
-        order[i*batch:(i+1)*batch] of the resident device arrays (train_network.py:72-95; the short last batch is kept, as
-        DataLoader does).  Returns the epoch's summed (policy_loss, value_loss) as a device tensor [2] -- no host sync.
-        mirror (None = off): a uint8 device table with one entry per row of states72, or (seed, epoch) for the seeded draw
-        (draw_mirror_flips): the rows it selects are trained on mirrored left to right.  The epoch's three gathers become one fused
-        gather + flip launch (aqg_augment_gather), so a mirrored epoch needs pre_shuffle=True."""
-        if mirror is not None and not pre_shuffle:
-            raise ValueError("a mirrored epoch trains on the shuffled and flipped copies: it needs pre_shuffle=True")
-        batch = self.max_batch if batch is None else int(batch)
-        if batch > self.max_batch:
-            raise ValueError("batch larger than the trainer's workspace")
-        n = int(order.shape[0])
-        sums = torch.zeros((2,), dtype=torch.float32, device=self.dev)
-        if n == 0:
-            return sums
-        # The shuffle is applied ONCE per epoch (three gathers, ~1 KB per position) and the steps then index the shuffled
-        # copies directly: every kernel of a step starts with cold loads, and reading order[] first would put one more
-        # HBM round trip in front of each of them.  (The C entry points also take the order itself: order != NULL.)
-        order = order.to(self.dev, torch.int64).contiguous()
-        states72 = states72.to(self.dev, torch.uint8).contiguous()
-        pi_target = pi_target.to(self.dev, torch.float32).contiguous()
-        z_target = z_target.to(self.dev, torch.float32).contiguous()
-        if mirror is not None:
-            states72, pi_target, z_target = _augment_launch(self.N, states72, pi_target, z_target, order, mirror)
-        elif pre_shuffle:
-            states72, pi_target, z_target = (x.index_select(0, order).contiguous() for x in (states72, pi_target, z_target))
-        self.t.batch, self.t.step, self.t.lr = batch, self.step_count + 1, float(lr)
-        steps = (n + batch - 1) // batch
-        norms = self._invoke(self._STEPS, (_lib.ptr(states72), _lib.ptr(pi_target), _lib.ptr(z_target),
-                                           _lib.ptr(None if pre_shuffle else order), n, _lib.ptr(sums)), steps)
-        if norms is not None:
-            self.grad_norms, self.last_grad_norm = norms, norms[-1]
-        self.step_count += steps
-        self._updated()
-        return sums
-
-
-class GNNTrainer(_Trainer):
-    """Adam state + workspace for optimisation steps of up to `max_batch` positions on `model` (a GNNNetwork on the GPU)."""
-
-    _STEP, _STEPS = "aqg_gcn_train_step", "aqg_gcn_train_steps"
-
-    def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, decay_all=False,
-                 max_grad_norm=None):
-        if not getattr(model, "fused", True):
-            model._require_fused("GNNTrainer (the fused training kernels)")
-        sd = model.state_dict()
-        self._setup(model, [sd[k] for k in STATE_DICT_KEYS], max_batch, betas, eps, (weight_decay, decoupled, decay_all, max_grad_norm))
-        self.V = self.N * self.N
-        B, A, H = self.max_batch, self.A, HIDDEN_DIM
-        f = dict(dtype=torch.float32, device=self.dev)
-        self.ws = dict(
-            h1=torch.empty((B * 96, H), **f), h2=torch.empty((B * 96, H), **f),    # 96 rows per position: include/aqgnn.h
-            g=torch.empty((B, H), **f), hp=torch.empty((B, H // 2), **f),
-            hv=torch.empty((B, H // 2), **f), dhp=torch.empty((B, H // 2), **f), dhv=torch.empty((B, H // 2), **f),
-            lg=torch.empty((B, A), **f), pol=torch.empty((B, A), **f), vp=torch.empty((B,), **f), val=torch.empty((B,), **f),
-            loss=torch.empty((B, 2), **f), part=torch.empty((B * _lib.TRAIN_PART_FLOATS,), **f))
-        self._fill(_lib.TrainStruct())
-        for name, x in self.ws.items():
-            setattr(self.t, name, x.data_ptr())
-
-    def _batch_losses(self, B):
-        return self.ws["loss"][:B].mean(dim=0)
-
-    def positions_redone_in_f32(self, reset=False):
-        """How many positions the split-precision step (9x9, train_fused 2) has handed to its f32 body since the count was last reset
-        (aqg_gcn_train_fallbacks; one count per process, not per trainer).  Zero for weights of ordinary scale.  A count that grows
-        by the batch size every step means the weights left the split's range -- a value beyond 65504, or 16 consecutive output
-        features of a GCN layer with no weight of 2^-6 or more, as weight decay can leave them -- and every step runs both bodies:
-        correct, and about twice the time.  One host read (a device synchronise)."""
-        return int(self.lib.aqg_gcn_train_fallbacks(1 if reset else 0))
-
-    def _updated(self):
-        self.model.invalidate_packed()
-
-
-class GeneralTrainer(_Trainer):
-    """Adam state + workspace for optimisation steps of up to `max_batch` positions on a GraphPolicyValueNetwork of ANY shape with
-    6 input features (the default 6/128/3 included) -- aqg_gcn_train_step_general (csrc/gcn_train_general.hip): the arithmetic
-    of GNNTrainer's step on the width-generic kernels.  The surface is GNNTrainer's.  The module's own parameters are updated in
-    place (and their version counters advanced), so an engine built with evaluator='general' only needs refresh_weights() to
-    search with the new weights -- its evaluation cache included."""
-
-    _STEP, _STEPS = "aqg_gcn_train_step_general", "aqg_gcn_train_steps_general"
-
-    def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, decay_all=False,
-                 max_grad_norm=None):
-        if getattr(model, "num_features", NUM_FEATURES) != NUM_FEATURES:
-            raise ValueError(f"GeneralTrainer trains on board records, which have {NUM_FEATURES} feature planes; this network takes "
-                             f"num_features={model.num_features}")
-        self._setup(model, [p for _, p in model._ordered_params()], max_batch, betas, eps,
-                    (weight_decay, decoupled, decay_all, max_grad_norm),
-                    workspace=("aqg_gcn_train_general_workspace_floats", (model.hidden_dim, model.num_gcn_layers)))
-        self._fill(_lib.TrainGeneralStruct())
-        self.t.num_features, self.t.hidden, self.t.num_layers = NUM_FEATURES, model.hidden_dim, model.num_gcn_layers
-
-    def _batch_losses(self, B):
-        return self.ws["loss_mean"].clone()          # summed in position order by the library
-
-    def _updated(self):
-        # The kernels wrote the parameters behind torch's back: advance their version counters, which general_weights_key()
-        # (and with it a 'general' engine's refresh_weights(), evaluation cache included) reads; drop any packed copy.
-        torch.autograd.graph.increment_version(self.params)
-        if hasattr(self.model, "invalidate_packed"):
-            self.model.invalidate_packed()
-
-
-CNN_TRAINING_NOT_BUILT = ("training the residual CNN through train_network() / trainer_for(), the GNN entry points, is not built "
-                          "yet: use CNNTrainer / train_cnn_network(), or train_cycle, which dispatches")
-
-
-class CNNTrainer(_Trainer):
-    """Adam state + workspace for optimisation steps of up to `max_batch` positions on a CNNNetwork (pv_network_cnn.py) on the GPU --
-    aqg_cnn_train_step (csrc/cnn_train.hip): the reference's step (train_network.py:26-107) with every BatchNorm2d in train mode.
-    The surface is GeneralTrainer's.  A step always normalises with the batch statistics, whatever model.training is (the mode is
-    left as it was), and updates every running_mean / running_var in place and num_batches_tracked by one, as the module's own
-    train-mode forward does; parameters are updated in place.  Version counters are advanced, so packed_weights() and a 'cnn'
-    engine's refresh_weights() pick up the new weights.  BatchNorm statistics over a sharded batch would need synchronised
-    BatchNorm: a step under a process group of more than one rank raises ValueError."""
-
-    _STEP, _STEPS = "aqg_cnn_train_step", "aqg_cnn_train_steps"
-    _GPU_REFUSAL = "CNNTrainer trains a model on the GPU: move it there first (model.to('cuda'))"
-
-    def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, decay_all=False,
-                 max_grad_norm=None):
-        from .pv_network_cnn import CNNNetwork
-        if not isinstance(model, CNNNetwork):
-            raise ValueError("CNNTrainer trains a pv_network_cnn.CNNNetwork")
-        self.bns = [cb.bn for cb in model._convs()]
-        for bn in self.bns:
-            if bn.momentum is None:
-                raise ValueError("BatchNorm2d(momentum=None) (a cumulative moving average) is not supported")
-            if not bn.track_running_stats or bn.running_mean is None:
-                raise ValueError("BatchNorm2d(track_running_stats=False) is not supported")
-        self._setup(model, model.parameters(), max_batch, betas, eps, (weight_decay, decoupled, decay_all, max_grad_norm),
-                    buffers=[b for bn in self.bns for b in (bn.running_mean, bn.running_var)],
-                    workspace=("aqg_cnn_train_workspace_floats", (model.num_filters, model.num_residual_blocks)))
-        # the Adam launch's tensor table, on the device: params | grads | adam_m | adam_v
-        self.table = torch.tensor([x.data_ptr() for x in self.params + self.grads + self.adam_m + self.adam_v], dtype=torch.int64,
-                                  device=self.dev)
-        t = _lib.CnnTrainStruct()
-        self._fill(t)
-        t.num_filters, t.num_blocks, t.adam_table = model.num_filters, model.num_residual_blocks, self.table.data_ptr()
-        for i, bn in enumerate(self.bns):
-            t.bn_eps[i], t.bn_momentum[i] = float(bn.eps), float(bn.momentum)
-            t.running_mean[i], t.running_var[i] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-
-    def step(self, states72, pi_target, z_target, lr=LEARNING_RATE, update=True, group=None, mirror=None):
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-            raise ValueError("CNNTrainer.step: data-parallel CNN training would need synchronised BatchNorm, which is not built; "
-                             "train on one rank")
-        out = super().step(states72, pi_target, z_target, lr=lr, update=update, group=group, mirror=mirror)
-        if int(states72.shape[0]) > 0:
-            self._forwarded(1)
-        return out
-
-    def run_epoch(self, states72, pi_target, z_target, order, lr=LEARNING_RATE, batch=None, pre_shuffle=True, mirror=None):
-        sums = super().run_epoch(states72, pi_target, z_target, order, lr=lr, batch=batch, pre_shuffle=pre_shuffle, mirror=mirror)
-        batch = self.max_batch if batch is None else int(batch)
-        self._forwarded((int(order.shape[0]) + batch - 1) // batch)
-        return sums
-
-    def _batch_losses(self, B):
-        return self.ws["loss_mean"].clone()          # summed in position order by the library
-
-    def _updated(self):
-        # the kernels wrote the parameters behind torch's back: advance their version counters (CNNNetwork.weights_key())
-        torch.autograd.graph.increment_version(self.params)
-        self.model.invalidate_packed()
-
-    def _forwarded(self, steps):
-        # every train-mode forward updated the running statistics in place and counts in num_batches_tracked
-        torch.autograd.graph.increment_version(self.buffers)
-        for bn in self.bns:
-            bn.num_batches_tracked.add_(steps)
-        self.model.invalidate_packed()
-
-
-class WeightAverage:
-    """An exponential moving average of a trainer's parameters, updated inside its HIP steps (include/aqgnn.h "weight averaging",
-    csrc/weight_average.hip): e <- f32(d e) + f32(w p) with d = float32(decay), w = float32(1 - d), behind the Adam update of every
-    step whose 1-based number is a multiple of `every` -- weight_average_reference in numpy, torch.optim.swa_utils.AveragedModel
-    (get_ema_avg_fn, use_buffers=True) in torch.  The average starts as a copy of the parameters: no bias correction, no warm-up.
-
-    WeightAverage(trainer) allocates the shadow tensors, builds the launch's tensor table once and attaches itself as
-    trainer.average; from then on step(update=True) and run_epoch call the library's _avg entry points.  For a CNNTrainer every
-    running_mean / running_var is shadowed too, with the same d.  decay and every are plain attributes read at every call.
-    Nothing the trainer computes changes: parameters, moments and losses are those of a trainer without an average."""
-
-    def __init__(self, trainer, decay=0.999, every=1):
-        if getattr(trainer, "average", None) is not None:
-            raise ValueError("this trainer already keeps a weight average (trainer.average)")
-        self._build(trainer.model, list(trainer.params) + list(trainer.buffers), decay, every)
-        self.trainer = trainer
-        trainer.average = self
-
-    @classmethod
-    def for_module(cls, module, decay=0.999, every=1):
-        """The average of any module's float32 parameters, updated by update() alone (every call is an update; `every` is kept for
-        the caller's own schedule).  A module on the GPU is averaged by the HIP launch, a CPU module by weight_average_reference."""
-        self = cls.__new__(cls)
-        sources = [p.detach() for p in module.parameters() if p.dtype == torch.float32]
-        if not sources:
-            raise ValueError("WeightAverage.for_module: the module has no float32 parameter")
-        self._build(module, sources, decay, every)
-        self.trainer = None
-        return self
-
-    def _build(self, model, sources, decay, every):
-        self.decay, self.every = decay, every
-        _checked_average_controls(decay, every)
-        if not 1 <= len(sources) <= _lib.WEIGHT_AVERAGE_MAX_TENSORS:
-            raise ValueError(f"a weight average takes 1..{_lib.WEIGHT_AVERAGE_MAX_TENSORS} tensors (got {len(sources)})")
-        for x in sources:
-            if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < 1:
-                raise ValueError("a weight average takes non-empty contiguous float32 tensors")
-        if any(x.device != sources[0].device for x in sources):
-            raise ValueError("every tensor of a weight average must be on one device")
-        names = {t.data_ptr(): k for k, t in model.state_dict().items() if t.numel()}
-        self.keys = [names.get(x.data_ptr()) for x in sources]
-        if any(k is None for k in self.keys) or len(set(self.keys)) != len(self.keys):
-            raise ValueError("every averaged tensor must be an entry of the model's state_dict, each once")
-        self.model, self.sources, self.dev, self.updates = model, sources, sources[0].device, 0
-        self.shadows = [x.detach().clone() for x in sources]
-        self.host = self.dev.type != "cuda"                    # the numpy statement as the backend of a CPU module
-        if self.host:
-            return
-        self.lib = _lib.load()
-        _lib.require_gpu(self.dev)
-        self._host_table, self.table, self.total_chunks = weight_average_table(self.shadows, sources)
-
-    def _struct(self):
-        """aqg_weight_average of the next call, with decay and every as they are now."""
-        d, k = _checked_average_controls(self.decay, self.every)
-        a = _lib.WeightAverageStruct()
-        a.table, a.host_table = self.table.data_ptr(), ctypes.cast(self._host_table, ctypes.POINTER(ctypes.c_int64))
-        a.num_tensors, a.every, a.total_chunks, a.decay = len(self.shadows), k, self.total_chunks, d
-        return a
-
-    def _stepped(self, first_step, steps, every):
-        """Count the averaging launches of a library call over the steps first_step .. first_step + steps - 1."""
-        self.updates += (first_step + steps - 1) // every - (first_step - 1) // every
-
-    def update(self):
-        """The stand-alone update, now: one launch over all tensors (aqg_weight_average_update), or numpy for a CPU module."""
-        if self.host:
-            d, _ = _checked_average_controls(self.decay, self.every)
-            for e, p in zip(self.shadows, self.sources):
-                e.copy_(torch.from_numpy(weight_average_reference(e.numpy(), p.detach().numpy(), d)))
-        else:
-            a = self._struct()
-            _lib.check(self.lib.aqg_weight_average_update(ctypes.byref(a), _lib.stream_ptr(self.dev)), "aqg_weight_average_update")
-        self.updates += 1
-
-    def tensors(self):
-        """The shadow tensors, in the order of the trainer's parameters (then its running statistics)."""
-        return list(self.shadows)
-
-    def state_dict(self):
-        """The model's state_dict with every shadowed entry replaced by a copy of its average -- same keys, same order; what is not
-        averaged (a BatchNorm's num_batches_tracked) is copied from the model as it is now."""
-        from collections import OrderedDict
-        shadow = dict(zip(self.keys, self.shadows))
-        return OrderedDict((k, (shadow[k] if k in shadow else v).detach().clone()) for k, v in self.model.state_dict().items())
-
-    def copy_to(self, model):
-        """Write the average into `model`, a module of the averaged model's shape (the averaged model itself included); entries that
-        are not averaged are left alone.  Version counters advance and any packed copy of the weights is dropped, as after a step."""
-        target = model.state_dict()
-        for k, e in zip(self.keys, self.shadows):
-            if k not in target or tuple(target[k].shape) != tuple(e.shape) or target[k].dtype != e.dtype:
-                raise ValueError(f"copy_to: the module has no float32 entry {k!r} of shape {tuple(e.shape)}")
-        with torch.no_grad():
-            for k, e in zip(self.keys, self.shadows):
-                target[k].copy_(e)                               # (an in-place torch op: the version counter advances)
-        if hasattr(model, "invalidate_packed"):
-            model.invalidate_packed()
-
-    def distance(self):
-        """|avg - raw| / |raw| over all averaged tensors, as a float: one host read."""
-        with torch.no_grad():
-            diff = torch.stack([(e - p).double().pow(2).sum() for e, p in zip(self.shadows, self.sources)]).sum()
-            raw = torch.stack([p.double().pow(2).sum() for p in self.sources]).sum()
-            return float((diff / raw).sqrt())
-
-    def summary_line(self):
-        d, k = _checked_average_controls(self.decay, self.every)
-        return f"weight average: decay {d:g}, every {k}, {self.updates} updates, |avg - raw| / |raw| = {self.distance():.3e}"
 
 
 def _configured_controls():
@@ -898,6 +291,10 @@ def _finite_or_none(x):
     return x
 
 
+CNN_TRAINING_NOT_BUILT = ("training the residual CNN through train_network() / trainer_for(), the GNN entry points, is not built "
+                          "yet: use CNNTrainer / train_cnn_network(), or train_cycle, which dispatches")
+
+
 def trainer_for(model, max_batch=BATCH_SIZE):
     """GNNTrainer for the default 6/128/3 network (the fused step), GeneralTrainer for every other shape, with the configured
     optimiser controls (TRAIN_WEIGHT_DECAY, TRAIN_DECOUPLED, TRAIN_MAX_GRAD_NORM)."""
@@ -936,10 +333,9 @@ def _train(load, make_trainer, data_parallel):
     """The epochs of _train_loop on this process alone, on every rank of the process group (data_parallel), or else on rank 0 ALONE
     while the other ranks wait."""
     import torch.distributed as dist
-    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
+    rank, world = aqd.rank_world()
     if world == 1 or data_parallel:
         return _train_loop(load, make_trainer, rank, world)
-    from . import distributed as aqd
     tag = aqd.next_tag("train")
     if rank == 0:
         with aqd.single_rank_stage(tag):       # published on failure too (value b"fail"): the idle ranks raise instead of waiting
@@ -954,7 +350,6 @@ def _train_loop(load, make_trainer, rank, world):
     """best.pth through `load`, NUM_EPOCH epochs on the trainer `make_trainer(model, max_batch=)` gives, latest.pth.  world > 1: the
     data-parallel form, every batch dealt out over the ranks."""
     import torch.distributed as dist
-    from . import distributed as aqd
     dev = aqd.device()                                                             # this rank's GPU, explicitly
     model = load(PV_NETWORK_PATH + 'best.pth', dev)                                # GNNNetwork, or the shape best.pth holds
     s, p, v, index, held = _update_rows(dev, model.board_size, model=model)

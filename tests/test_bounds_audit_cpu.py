@@ -169,7 +169,7 @@ def test_module_scan():
     print("local `import torch` that makes tensors:", local)
     assert unwrappable == []
     for m in ("engine", "pv_network_gnn", "pv_network_cnn", "game_logic", "agents", "train_network", "validation", "replay",
-              "replay_merge", "replay_surprise", "openings", "pv_mcts"):
+              "replay_merge", "replay_surprise", "openings", "pv_mcts", "trainers", "train_augment"):
         assert m in wrappable, m
     assert set(local) == BLIND_SPOTS, local
     # none of the blind spots allocates with the intercepted functions: they copy host arrays over
