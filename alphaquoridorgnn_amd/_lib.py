@@ -147,6 +147,12 @@ class WeightAverageStruct(_c.Structure):
                 ("total_chunks", _c.c_int64), ("decay", _f32)]
 
 
+class LossStruct(_c.Structure):
+    """Mirror of `struct aqg_loss` (include/aqgnn.h, "loss form"): the option beside a trainer struct.  policy_form 0 = the
+    reference's loss, 1 = the cross-entropy on the logits; value_weight scales the value term's gradient."""
+    _fields_ = [("policy_form", _i32), ("value_weight", _f32)]
+
+
 WEIGHT_AVERAGE_CHUNK = 4096          # AQG_WEIGHT_AVERAGE_CHUNK
 WEIGHT_AVERAGE_MAX_TENSORS = 1024    # AQG_WEIGHT_AVERAGE_MAX_TENSORS
 
@@ -266,6 +272,20 @@ SIGNATURES = {
                                           _c.POINTER(WeightAverageStruct), _vp]),
     "aqg_cnn_train_steps_avg": (_c.c_int, [_c.POINTER(CnnTrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _c.POINTER(OptimStruct),
                                            _c.POINTER(WeightAverageStruct), _vp]),
+    "aqg_policy_value_loss": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.POINTER(LossStruct), _vp, _vp, _vp, _vp]),
+    "aqg_gcn_train_step_loss": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _c.c_int, _c.POINTER(OptimStruct),
+                                           _c.POINTER(WeightAverageStruct), _c.POINTER(LossStruct), _vp]),
+    "aqg_gcn_train_steps_loss": (_c.c_int, [_c.POINTER(TrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _c.POINTER(OptimStruct),
+                                            _c.POINTER(WeightAverageStruct), _c.POINTER(LossStruct), _vp]),
+    "aqg_gcn_train_step_general_loss": (_c.c_int, [_c.POINTER(TrainGeneralStruct), _vp, _vp, _vp, _c.c_int, _c.POINTER(OptimStruct),
+                                                   _c.POINTER(WeightAverageStruct), _c.POINTER(LossStruct), _vp]),
+    "aqg_gcn_train_steps_general_loss": (_c.c_int, [_c.POINTER(TrainGeneralStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp,
+                                                    _c.POINTER(OptimStruct), _c.POINTER(WeightAverageStruct), _c.POINTER(LossStruct),
+                                                    _vp]),
+    "aqg_cnn_train_step_loss": (_c.c_int, [_c.POINTER(CnnTrainStruct), _vp, _vp, _vp, _c.c_int, _c.POINTER(OptimStruct),
+                                           _c.POINTER(WeightAverageStruct), _c.POINTER(LossStruct), _vp]),
+    "aqg_cnn_train_steps_loss": (_c.c_int, [_c.POINTER(CnnTrainStruct), _vp, _vp, _vp, _vp, _c.c_longlong, _vp, _c.POINTER(OptimStruct),
+                                            _c.POINTER(WeightAverageStruct), _c.POINTER(LossStruct), _vp]),
     "aqg_augment_gather": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_int, _vp, _vp, _vp,
                                       _vp]),
     "aqg_replay_append": (_c.c_int, [_c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),

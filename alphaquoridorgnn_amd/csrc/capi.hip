@@ -63,6 +63,21 @@ static int check_steps(const Net* t, const uint8_t* states72, const float* pi, c
     return check_net(*t, true, what);
 }
 
+// the loss form of a _loss call (include/aqgnn.h "loss form")
+static int check_loss_form(const aqg_loss* lf, const char* what) {
+    if (!lf) return 0;
+    if (lf->policy_form != 0 && lf->policy_form != 1) return fail(what, "policy_form must be 0 (reference) or 1 (cross-entropy)");
+    if (!(lf->value_weight >= 0.f) || !std::isfinite(lf->value_weight)) return fail(what, "value_weight must be finite and >= 0");
+    return 0;
+}
+static bool loss_form_is_default(const aqg_loss* lf) { return !lf || (lf->policy_form == 0 && lf->value_weight == 1.f); }
+template <class Net>
+static int check_loss_call(const Net* t, const aqg_optim* optim, const aqg_weight_average* avg, const char* what, OptimPlan* plan,
+                           bool* on) {
+    if (int r = plan_optim(*t, optim, what, plan, on)) return r;
+    return avg ? check_weight_average(avg, what) : 0;
+}
+
 extern "C" {
 
 int aqg_abi_version(void) { return AQG_ABI_VERSION; }
@@ -641,6 +656,92 @@ int aqg_cnn_train_steps_avg(const aqg_cnn_train* t, const uint8_t* states72, con
     if (int r = plan_optim(*t, optim, what, &plan, &on)) return r;
     if (int r = check_weight_average(avg, what)) return r;
     return cnn_train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream, on ? &plan : nullptr, avg);
+}
+
+// The _loss entry points (include/aqgnn.h "loss form"): the form's own refusals first; a NULL or default form is the _avg call
+// itself; otherwise the call's checks, the controls' and the average's (either may be NULL), all in front of the first launch.
+int aqg_policy_value_loss(int B, int A, const float* logits, const float* value, const float* pi, const float* z, const int64_t* order,
+                          int first, const aqg_loss* lf, float* loss, float* dlogits, float* dvpre, void* stream) {
+    const char* what = "aqg_policy_value_loss";
+    if (B < 0 || A < 1 || A > 4096 || first < 0) return fail(what, "bad argument");
+    if (!lf || !logits || !value || !pi || !z || !loss || !dlogits || !dvpre) return fail(what, "null argument");
+    if (int r = check_loss_form(lf, what)) return r;
+    if (lf->policy_form != 1) return fail(what, "policy_form must be 1 (cross-entropy)");
+    return launch_policy_value_loss(B, A, logits, value, pi, z, order, first, lf->value_weight, loss, dlogits, dvpre, (hipStream_t)stream);
+}
+int aqg_gcn_train_step_loss(const aqg_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                            const aqg_optim* optim, const aqg_weight_average* avg, const aqg_loss* lf, void* stream) {
+    const char* what = "aqg_gcn_train_step_loss";
+    if (int r = check_loss_form(lf, what)) return r;
+    if (loss_form_is_default(lf)) return aqg_gcn_train_step_avg(t, states72, pi_target, z_target, mode, optim, avg, stream);
+    OptimPlan plan;
+    bool on;
+    if (int r = check_step(t, states72, pi_target, z_target, mode, what)) return r;
+    if (int r = check_loss_call(t, optim, avg, what, &plan, &on)) return r;
+    return train_step(*t, states72, pi_target, z_target, mode, (hipStream_t)stream, on ? &plan : nullptr, avg, lf);
+}
+int aqg_gcn_train_steps_loss(const aqg_train* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                             const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim,
+                             const aqg_weight_average* avg, const aqg_loss* lf, void* stream) {
+    const char* what = "aqg_gcn_train_steps_loss";
+    if (int r = check_loss_form(lf, what)) return r;
+    if (loss_form_is_default(lf))
+        return aqg_gcn_train_steps_avg(t, states72, pi_target, z_target, order, positions, loss_sums, optim, avg, stream);
+    OptimPlan plan;
+    bool on;
+    if (int r = check_steps(t, states72, pi_target, z_target, positions, what)) return r;
+    if (int r = check_loss_call(t, optim, avg, what, &plan, &on)) return r;
+    return train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream, on ? &plan : nullptr, avg, lf);
+}
+int aqg_gcn_train_step_general_loss(const aqg_train_general* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                                    int mode, const aqg_optim* optim, const aqg_weight_average* avg, const aqg_loss* lf, void* stream) {
+    const char* what = "aqg_gcn_train_step_general_loss";
+    if (int r = check_loss_form(lf, what)) return r;
+    if (loss_form_is_default(lf)) return aqg_gcn_train_step_general_avg(t, states72, pi_target, z_target, mode, optim, avg, stream);
+    OptimPlan plan;
+    bool on;
+    if (int r = check_step(t, states72, pi_target, z_target, mode, what)) return r;
+    if (int r = check_loss_call(t, optim, avg, what, &plan, &on)) return r;
+    return train_step_general(*t, states72, pi_target, z_target, mode, (hipStream_t)stream, on ? &plan : nullptr, avg, lf);
+}
+int aqg_gcn_train_steps_general_loss(const aqg_train_general* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                                     const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim,
+                                     const aqg_weight_average* avg, const aqg_loss* lf, void* stream) {
+    const char* what = "aqg_gcn_train_steps_general_loss";
+    if (int r = check_loss_form(lf, what)) return r;
+    if (loss_form_is_default(lf))
+        return aqg_gcn_train_steps_general_avg(t, states72, pi_target, z_target, order, positions, loss_sums, optim, avg, stream);
+    OptimPlan plan;
+    bool on;
+    if (int r = check_steps(t, states72, pi_target, z_target, positions, what)) return r;
+    if (int r = check_loss_call(t, optim, avg, what, &plan, &on)) return r;
+    return train_steps_general(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream, on ? &plan : nullptr,
+                               avg, lf);
+}
+int aqg_cnn_train_step_loss(const aqg_cnn_train* t, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                            const aqg_optim* optim, const aqg_weight_average* avg, const aqg_loss* lf, void* stream) {
+    const char* what = "aqg_cnn_train_step_loss";
+    if (int r = check_loss_form(lf, what)) return r;
+    if (loss_form_is_default(lf)) return aqg_cnn_train_step_avg(t, states72, pi_target, z_target, mode, optim, avg, stream);
+    OptimPlan plan;
+    bool on;
+    if (int r = check_step(t, states72, pi_target, z_target, mode, what)) return r;
+    if (int r = check_loss_call(t, optim, avg, what, &plan, &on)) return r;
+    return cnn_train_step(*t, states72, pi_target, z_target, mode, (hipStream_t)stream, on ? &plan : nullptr, avg, lf);
+}
+int aqg_cnn_train_steps_loss(const aqg_cnn_train* t, const uint8_t* states72, const float* pi_target, const float* z_target,
+                             const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim,
+                             const aqg_weight_average* avg, const aqg_loss* lf, void* stream) {
+    const char* what = "aqg_cnn_train_steps_loss";
+    if (int r = check_loss_form(lf, what)) return r;
+    if (loss_form_is_default(lf))
+        return aqg_cnn_train_steps_avg(t, states72, pi_target, z_target, order, positions, loss_sums, optim, avg, stream);
+    OptimPlan plan;
+    bool on;
+    if (int r = check_steps(t, states72, pi_target, z_target, positions, what)) return r;
+    if (int r = check_loss_call(t, optim, avg, what, &plan, &on)) return r;
+    return cnn_train_steps(*t, states72, pi_target, z_target, order, positions, loss_sums, (hipStream_t)stream, on ? &plan : nullptr, avg,
+                           lf);
 }
 
 int aqg_augment_gather(int board_size, int policy_size, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,

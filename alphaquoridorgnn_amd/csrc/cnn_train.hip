@@ -293,7 +293,7 @@ int launch_im2col(int N, int B, int Cin, const float* X, float* col, hipStream_t
 // forward, losses and backward of B positions (rows order[first ..] or first ..): gradients into t.grads, the running statistics
 // updated, per-position losses
 int forward_backward(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, int first,
-                     int B, const CnnTrainWorkspace& ws, float* policy, float* value, float* loss, hipStream_t st) {
+                     int B, const CnnTrainWorkspace& ws, float* policy, float* value, float* loss, hipStream_t st, const aqg_loss* lf) {
     const int N = t.board_size, V = N * N, F = t.num_filters, L = t.num_blocks, A = t.policy_size, C = 2 * L + 1;
     const int R = B * V, Fp = (int)ws.fp;
     const size_t RFn = (size_t)R * F;
@@ -328,8 +328,9 @@ int forward_backward(const aqg_cnn_train& t, const uint8_t* states72, const floa
     if (int r = launch_gen_linear(B, F, 1, ws.pooled, p[h + 2], p[h + 3], nullptr, 0, ws.vpre, st)) return r;
     if (int r = launch_gen_heads(B, A, ws.logits, ws.vpre, policy, value, st, nullptr)) return r;
     // losses, the heads' backward and d loss / d pooled
-    if (int r = launch_train_general_loss(B, A, policy, value, pi, z, order, first, loss, ws.dpol, ws.dval, st)) return r;
-    if (int r = launch_gen_heads_backward(B, A, policy, ws.dpol, value, ws.dval, ws.dlogits, ws.dvpre, st)) return r;
+    if (int r = launch_train_losses(B, A, ws.logits, policy, value, pi, z, order, first, lf, loss, ws.dpol, ws.dval, ws.dlogits,
+                                    ws.dvpre, st))
+        return r;
     float* part = ws.part;
     const size_t pf = ws.part_floats;
     if (int r = launch_gen_linear_grad(B, F, A, ws.dlogits, ws.pooled, nullptr, part, pf, g[h], g[h + 1], st)) return r;
@@ -447,13 +448,13 @@ struct CnnKind {
 };
 
 int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
-                   const OptimPlan* plan, const aqg_weight_average* avg) {
-    return train_driver_step<CnnKind>(t, states72, pi, z, mode, st, plan, avg);
+                   const OptimPlan* plan, const aqg_weight_average* avg, const aqg_loss* lf) {
+    return train_driver_step<CnnKind>(t, states72, pi, z, mode, st, plan, avg, lf);
 }
 int cnn_train_steps(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
                     long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan,
-                    const aqg_weight_average* avg) {
-    return train_driver_steps<CnnKind>(t, states72, pi, z, order, positions, loss_sums, st, plan, avg);
+                    const aqg_weight_average* avg, const aqg_loss* lf) {
+    return train_driver_steps<CnnKind>(t, states72, pi, z, order, positions, loss_sums, st, plan, avg, lf);
 }
 
 }  // namespace aqg

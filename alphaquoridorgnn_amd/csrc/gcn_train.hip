@@ -6,6 +6,7 @@
 //   forward   Z = H W^T, P = A_hat Z + b, H' = relu(P)   x3;  g = mean_nodes H3;  heads;  pol = softmax, val = tanh
 //   loss      Lp = mean_b -sum_a t_a log_softmax(pol)_a   (the reference's double softmax, kept on purpose)
 //             Lv = mean_b (val - z)^2
+//             (the _loss entry points: the cross-entropy on the logits and a value weight, include/aqgnn.h "loss form")
 //   backward  dP = dH' (.) [H' > 0];  db = colsum dP;  dZ = A_hat dP (A_hat symmetric);  dW = dZ^T H;  dH = dZ W
 //   update    torch.optim.Adam (lr, betas, eps; bias-corrected; no amsgrad); weight decay and global-norm clipping are options of
 //             the _optim entry points (train_adam.hpp, final_optim below), off in every other call
@@ -49,10 +50,10 @@ namespace aqg {
 int g_train_fused = 2;
 
 static int forward_backward(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, int first,
-                            int B, hipStream_t st) {
+                            int B, hipStream_t st, const aqg_loss* lf) {
     if (t.board_size == 9 && g_train_fused >= 2)
-        return launch_train_board_split(t, states72, pi, z, order, first, B, g_train_fused == 3 ? 1 : 0, st);
-    return launch_train_board_exact(t, states72, pi, z, order, first, B, st);
+        return launch_train_board_split(t, states72, pi, z, order, first, B, g_train_fused == 3 ? 1 : 0, st, lf);
+    return launch_train_board_exact(t, states72, pi, z, order, first, B, st, lf);
 }
 
 static int validate(const aqg_train& t) {
@@ -83,10 +84,10 @@ static int final_optim(const aqg_train& t, int B, bool compute, int step, int st
 
 // mode 0 = gradients only, 1 = gradients + Adam, 2 = Adam only (data-parallel: local gradients, all-reduce, update)
 static int train_step_launches(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
-                               const OptimPlan* plan) {
+                               const OptimPlan* plan, const aqg_loss* lf) {
     const int B = t.batch;
     if (mode != 2 && B > 0) {
-        if (int r = forward_backward(t, states72, pi, z, nullptr, 0, B, st)) return r;
+        if (int r = forward_backward(t, states72, pi, z, nullptr, 0, B, st, lf)) return r;
         if (plan && mode == 1) return final_optim(t, B, true, t.step, 0, nullptr, *plan, st);
         if (int r = launch_train_final(t, B, true, mode == 1, t.step, nullptr, st)) return r;
         return plan ? optim_norm_only(*plan, st) : 0;
@@ -95,10 +96,11 @@ static int train_step_launches(const aqg_train& t, const uint8_t* states72, cons
     return plan ? optim_norm_only(*plan, st) : 0;
 }
 // avg (may be null; include/aqgnn.h "weight averaging"): the averaging launch behind the last launch of an updating step
+// lf (may be null; include/aqgnn.h "loss form"): the board launch's second (cross-entropy) or third (value weight alone) instantiation
 int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
-               const OptimPlan* plan, const aqg_weight_average* avg) {
+               const OptimPlan* plan, const aqg_weight_average* avg, const aqg_loss* lf) {
     if (int r = validate(t)) return r;
-    if (int r = train_step_launches(t, states72, pi, z, mode, st, plan)) return r;
+    if (int r = train_step_launches(t, states72, pi, z, mode, st, plan, lf)) return r;
     return mode >= 1 ? average_after_update(avg, t.step, st) : 0;
 }
 
@@ -107,13 +109,13 @@ int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, con
 // resident arrays, t.step counts up from its entry value, and each step's loss terms are added to loss_sums[2]
 // (policy, value: the per-step batch means, what train_network.py:89-90 accumulates per epoch).
 int train_steps(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, long long positions,
-                float* loss_sums, hipStream_t st, const OptimPlan* plan, const aqg_weight_average* avg) {
+                float* loss_sums, hipStream_t st, const OptimPlan* plan, const aqg_weight_average* avg, const aqg_loss* lf) {
     if (int r = validate(t)) return r;
     if (t.batch < 1) return fail("aqg_gcn_train_steps: batch must be >= 1");
     int step = t.step;
     for (long long first = 0; first < positions; first += t.batch, ++step) {
         const int B = (int)(positions - first < t.batch ? positions - first : t.batch);
-        if (int r = forward_backward(t, states72, pi, z, order, (int)first, B, st)) return r;
+        if (int r = forward_backward(t, states72, pi, z, order, (int)first, B, st, lf)) return r;
         if (plan) { if (int r = final_optim(t, B, true, step, step - t.step, loss_sums, *plan, st)) return r; }
         else if (int r = launch_train_final(t, B, true, true, step, loss_sums, st)) return r;
         if (int r = average_after_update(avg, step, st)) return r;

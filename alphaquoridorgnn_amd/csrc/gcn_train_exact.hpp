@@ -137,7 +137,8 @@ struct TrunkParams { const float* p[6]; };       // state_dict tensors 0..5
 // (the body is a device function over ONE raw LDS block so that the split-precision kernel (gcn_train_split.hip) can fall back to it for a board
 //  whose values leave fp16 range without owning two sets of static LDS arrays; `hrows` = rows per board of the h1 / h2 buffers)
 constexpr int F32_BODY_SMEM = (int)(sizeof(float) * (2 * 96 * SA + 84 * SB + 4 * TH) + sizeof(BoardGraph));
-template <int N>
+// LF, vw: the loss form and value weight of heads_board (gcn_train_heads.hpp), handed through
+template <int N, int LF = LOSS_PLAIN>
 __device__ __forceinline__ void train_board_f32_body(unsigned char* __restrict__ smem, const uint8_t* __restrict__ states72,
                                                      const int64_t* __restrict__ order, int first,
                                                      const TrunkParams& tp, const HeadParams& hpm, const float* __restrict__ pi_all,
@@ -147,7 +148,7 @@ __device__ __forceinline__ void train_board_f32_body(unsigned char* __restrict__
                                                      float* __restrict__ pol, float* __restrict__ vp, float* __restrict__ val,
                                                      float* __restrict__ loss, float* __restrict__ dhp, float* __restrict__ dhv,
                                                      float* __restrict__ part_dW3, float* __restrict__ part_dW2,
-                                                     float* __restrict__ part_dW1, float* __restrict__ part_db) {
+                                                     float* __restrict__ part_dW1, float* __restrict__ part_db, float vw = 1.f) {
     constexpr int V = N * N, RT = (V + 15) / 16, VK = (V + 3) / 4 * 4, NIT = (V + 15) / 16;
     float* const Hs = reinterpret_cast<float*>(smem);
     float* const Zs = Hs + 96 * SA;
@@ -263,7 +264,7 @@ __device__ __forceinline__ void train_board_f32_body(unsigned char* __restrict__
     }
     TS(2, 5)
     // ---- heads, losses, head gradients (its first barrier publishes gs)
-    heads_board(hsm, b, hpm, pi_all, z_all, order, first, A, B, hp, hv, lg, pol, vp, val, loss, dhp, dhv);
+    heads_board<LF>(hsm, b, hpm, pi_all, z_all, order, first, A, B, hp, hv, lg, pol, vp, val, loss, dhp, dhv, vw);
     TS(2, 6)
     load_bfrag(bw, W3, TH, 1, col, q);                               // the data gradient's fragments of W3 (B[j][k] = W3[j][k]): land under layer 3's backward
     // ---- backward.  One layer: dP (accumulator layout) -> Zs;  dZ = A_hat dP -> Hs;  dW partial = dZ^T H_{l-1} (Hb)

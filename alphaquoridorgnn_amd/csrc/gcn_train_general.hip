@@ -5,7 +5,8 @@
 //   prep       train_general_prep_kernel: the mean pool's graph pointer (and, with an order, this step's records gathered)
 //   forward    featuriser, board_gcn_layer_kernel per layer with H_l kept, gen_mean_pool, gen_linear x 4, gen_heads: the policy and
 //              value are bit for bit those of aqg_gcn_forward_boards_general (the same kernels; the pool sums in the same order)
-//   loss       train_general_loss_kernel: both loss terms of each position, d loss / d policy and d loss / d value
+//   loss       train_general_loss_kernel: both loss terms of each position, d loss / d policy and d loss / d value; with the
+//              cross-entropy form (include/aqgnn.h "loss form") policy_value_loss_kernel, which also does gen_heads_backward's work
 //   heads      gen_heads_backward, gen_linear (W [K,N], ReLU mask) and gen_linear_grad for the four head layers
 //   trunk      gen_mean_pool_backward (mask H_L > 0) -> dP_L; per layer l = L .. 1 ONE launch of board_gcn_layer_backward_kernel:
 //              dZ_l = A_hat dP_l (A_hat is symmetric on the board graph) and dP_{l-1} = (dZ_l W_l) x [H_{l-1} > 0], then
@@ -89,6 +90,61 @@ __global__ __launch_bounds__(256) void train_general_loss_kernel(int B, int A, c
         loss[2 * b + 1] = dv * dv;
         dval[b] = 2.f * dv * inv_b;
     }
+}
+
+// max over the workgroup's 256 threads (block_sum's shape)
+__device__ __forceinline__ float block_max(float v, float* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// The cross-entropy form of the loss (include/aqgnn.h "loss form", policy_form 1) in ONE launch, in place of train_general_loss_kernel
+// + gen_heads_backward_kernel: one workgroup per position b, from the LOGITS x = logits[b] (never from ln p: exp(x_a - m) may
+// underflow, (m - x_a) + ln se does not), the tanh value v and the targets of row order[first + b] (or first + b):
+//   loss[b] = { sum_a t_a ((m - x_a) + ln se),  (v - z)^2 },  dlogits[b][a] = (exp(x_a - m) / se  T - t_a) / B,
+//   dvpre[b] = w 2 (v - z) / B (1 - v^2)                      with m = max x, se = sum_a exp(x_a - m), T = sum_a t_a.
+// Three passes over the row, every loop bounded by A (any A >= 1); the sums in block_sum's fixed order, no atomics.
+__global__ __launch_bounds__(256) void policy_value_loss_kernel(int B, int A, const float* __restrict__ logits,
+                                                                const float* __restrict__ value, const float* __restrict__ pi,
+                                                                const float* __restrict__ z, const int64_t* __restrict__ order, int first,
+                                                                float vw, float* __restrict__ loss, float* __restrict__ dlogits,
+                                                                float* __restrict__ dvpre) {
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const size_t src = row_of(order, first, b);
+    const float* x = logits + (size_t)b * A;
+    const float* t = pi + src * A;
+    float mx = -INFINITY, ts = 0.f;
+    for (int a = tid; a < A; a += 256) { mx = fmaxf(mx, x[a]); ts += t[a]; }
+    const float m = block_max(mx, red);
+    ts = block_sum(ts, red);
+    float se = 0.f;
+    for (int a = tid; a < A; a += 256) se += expf(x[a] - m);
+    se = block_sum(se, red);
+    const float lse = logf(se), inv_b = 1.f / (float)B;
+    float lp = 0.f;
+    for (int a = tid; a < A; a += 256) {
+        const float xa = x[a], ta = t[a];
+        dlogits[(size_t)b * A + a] = ((expf(xa - m) / se) * ts - ta) * inv_b;
+        lp += ta * ((m - xa) + lse);
+    }
+    lp = block_sum(lp, red);
+    if (tid == 0) {
+        const float v = value[b], dv = v - z[src];
+        loss[2 * b] = lp;
+        loss[2 * b + 1] = dv * dv;
+        dvpre[b] = vw * (2.f * dv * inv_b) * (1.f - v * v);
+    }
+}
+
+// form 0 with a value weight: d loss / d value of train_general_loss_kernel scaled in place, between the two launches
+__global__ __launch_bounds__(256) void scale_dval_kernel(int B, float vw, float* __restrict__ dval) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < B) dval[i] *= vw;
 }
 
 // The layer backward of P_l = A_hat (H_{l-1} W_l^T) + b_l, H_l = relu(P_l), given dP_l [B V, Hd] (ReLU already applied):
@@ -276,7 +332,7 @@ int launch_layer_backward(int N, int B, int Hd, int K, const float* dP, const fl
 
 // forward, losses and backward of B positions (rows order[first ..] or first ..): gradients into t.grads, per-position losses
 int forward_backward(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, int first,
-                     int B, const TrainWorkspace& ws, float* policy, float* value, float* loss, hipStream_t st) {
+                     int B, const TrainWorkspace& ws, float* policy, float* value, float* loss, hipStream_t st, const aqg_loss* lf) {
     const int N = t.board_size, V = N * N, Hd = t.hidden, L = t.num_layers, A = t.policy_size, Hh = Hd / 2, R = B * V;
     float* const* p = t.params;
     float* const* g = t.grads;
@@ -297,8 +353,9 @@ int forward_backward(const aqg_train_general& t, const uint8_t* states72, const 
     if (int r = launch_gen_linear(B, Hh, 1, ws.hv, p[o + 6], p[o + 7], nullptr, 0, ws.vpre, st)) return r;
     if (int r = launch_gen_heads(B, A, ws.logits, ws.vpre, policy, value, st, nullptr)) return r;
     // losses and the way back to the logits / the pre-tanh value
-    if (int r = launch_train_general_loss(B, A, policy, value, pi, z, order, first, loss, ws.dpol, ws.dval, st)) return r;
-    if (int r = launch_gen_heads_backward(B, A, policy, ws.dpol, value, ws.dval, ws.dlogits, ws.dvpre, st)) return r;
+    if (int r = launch_train_losses(B, A, ws.logits, policy, value, pi, z, order, first, lf, loss, ws.dpol, ws.dval, ws.dlogits,
+                                    ws.dvpre, st))
+        return r;
     // heads: second layers, the hidden layers' gradients (ReLU mask = the saved activations), first layers, d loss / d pooled
     float* part = ws.part;
     const size_t pf = ws.part_floats;
@@ -389,6 +446,29 @@ int launch_train_general_loss(int B, int A, const float* policy, const float* va
     return check_launch("train_general_loss_kernel");
 }
 
+int launch_policy_value_loss(int B, int A, const float* logits, const float* value, const float* pi, const float* z, const int64_t* order,
+                             int first, float value_weight, float* loss, float* dlogits, float* dvpre, hipStream_t st) {
+    if (B <= 0) return 0;
+    hipLaunchKernelGGL(policy_value_loss_kernel, dim3(B), dim3(256), 0, st, B, A, logits, value, pi, z, order, first, value_weight, loss,
+                       dlogits, dvpre);
+    return check_launch("policy_value_loss_kernel");
+}
+
+// both loss terms of B positions and the way back to the logits / the pre-tanh value, in the form lf asks for (null = the
+// reference's, weight 1: the two launches there have always been)
+int launch_train_losses(int B, int A, const float* logits, const float* policy, const float* value, const float* pi, const float* z,
+                        const int64_t* order, int first, const aqg_loss* lf, float* loss, float* dpol, float* dval, float* dlogits,
+                        float* dvpre, hipStream_t st) {
+    if (lf && lf->policy_form == 1)
+        return launch_policy_value_loss(B, A, logits, value, pi, z, order, first, lf->value_weight, loss, dlogits, dvpre, st);
+    if (int r = launch_train_general_loss(B, A, policy, value, pi, z, order, first, loss, dpol, dval, st)) return r;
+    if (lf && lf->value_weight != 1.f) {
+        hipLaunchKernelGGL(scale_dval_kernel, dim3(blocks_of(B, 256)), dim3(256), 0, st, B, lf->value_weight, dval);
+        if (int r = check_launch("scale_dval_kernel")) return r;
+    }
+    return launch_gen_heads_backward(B, A, policy, dpol, value, dval, dlogits, dvpre, st);
+}
+
 size_t train_general_workspace_floats(int N, int hidden, int num_layers, int policy_size, int max_batch) {
     if (!board_size_supported(N) || hidden < 2 || hidden > 1024 || num_layers < 1 || num_layers > AQG_GENERAL_MAX_LAYERS ||
         policy_size < 1 || policy_size > 4096 || max_batch < 1)
@@ -411,13 +491,13 @@ struct GeneralKind {
 };
 
 int train_step_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
-                       const OptimPlan* plan, const aqg_weight_average* avg) {
-    return train_driver_step<GeneralKind>(t, states72, pi, z, mode, st, plan, avg);
+                       const OptimPlan* plan, const aqg_weight_average* avg, const aqg_loss* lf) {
+    return train_driver_step<GeneralKind>(t, states72, pi, z, mode, st, plan, avg, lf);
 }
 int train_steps_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
                         long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan,
-                        const aqg_weight_average* avg) {
-    return train_driver_steps<GeneralKind>(t, states72, pi, z, order, positions, loss_sums, st, plan, avg);
+                        const aqg_weight_average* avg, const aqg_loss* lf) {
+    return train_driver_steps<GeneralKind>(t, states72, pi, z, order, positions, loss_sums, st, plan, avg, lf);
 }
 
 }  // namespace aqg

@@ -50,12 +50,20 @@ __device__ __forceinline__ float dot4(const f32x4 a, const f32x4 b) { return fma
 //                                                     quarter waves are added up through LDS in a fixed order.
 // (Before: one row per wave instruction with a 64-lane reduction per row, policy_head.2 and both first layers read twice, the
 //  second time with 4-byte strided loads -- 180 vector-memory instructions and ~100 weight registers per lane; now 15 and 60.)
+//
+// LF, the loss form (include/aqgnn.h "loss form"): LOSS_PLAIN = the reference's, as this body has always been (vw is not looked at);
+// LOSS_CE = the cross-entropy taken from the logits wave 0 already holds -- no second exponential round, no s2 / ls2, no dot
+// reduction -- with the value weight vw; LOSS_REF_W = the reference's policy term with the value weight.  Everything behind dl[]
+// and dvp is the same in all three.
+constexpr int LOSS_PLAIN = 0, LOSS_CE = 1, LOSS_REF_W = 2;
+template <int LF = LOSS_PLAIN>
 __device__ __forceinline__ void heads_board(TrainHeadsSmem& sm, int b, const HeadParams& Pm,
                                             const float* __restrict__ pi_all, const float* __restrict__ z_all,
                                             const int64_t* __restrict__ order, int first, int A, int B,
                                             float* __restrict__ hp, float* __restrict__ hv, float* __restrict__ lg,
                                             float* __restrict__ pol, float* __restrict__ vp, float* __restrict__ val,
-                                            float* __restrict__ loss, float* __restrict__ dhp, float* __restrict__ dhv) {
+                                            float* __restrict__ loss, float* __restrict__ dhp, float* __restrict__ dhv,
+                                            float vw = 1.f) {
     float (&gs)[TH] = sm.gs; float (&hs)[TH] = sm.hs; float (&dhs)[TH] = sm.dhs; float (&dl)[256] = sm.dl;
     float (&red)[2][8][2] = sm.red;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, rg = lane >> 4, l = lane & 15;
@@ -139,30 +147,46 @@ __device__ __forceinline__ void heads_board(TrainHeadsSmem& sm, int b, const Hea
         for (int j = 0; j < 4; ++j) { pv[j] = lane + 64 * j < A ? expf(lgv[j] - m) : 0.f; se += pv[j]; }
         se = wave_sum(se);
         const float tsum = wave_sum(ts);
-        float s2 = 0.f, e2[4];
+        float lp = 0.f;
+        if constexpr (LF == LOSS_CE) {
+            const float lse0 = logf(se);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            pv[j] = pv[j] / se;                                  // first softmax (the network's own, pv_network_gnn.py:42)
-            e2[j] = lane + 64 * j < A ? expf(pv[j]) : 0.f;       // second softmax inside CrossEntropyLoss; p in [0,1]: no shift needed
-            s2 += e2[j];
+            for (int j = 0; j < 4; ++j) {
+                const bool ok = lane + 64 * j < A;
+                pv[j] = pv[j] / se;                                  // the network's softmax (pv_network_gnn.py:42)
+                dp[j] = ok ? (pv[j] * tsum - tg[j]) / (float)B : 0.f;    // d(mean_b l_b) / d logit
+                lp += ok ? tg[j] * ((m - lgv[j]) + lse0) : 0.f;          // t (lse - x), from the logits: finite where pv underflows
+            }
+            lp = wave_sum(lp);
         }
-        s2 = wave_sum(s2);
-        const float ls2 = logf(s2);
-        float lp = 0.f, dot = 0.f;
+        float dot = 0.f;
+        if constexpr (LF != LOSS_CE) {
+            float s2 = 0.f, e2[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool ok = lane + 64 * j < A;
-            dp[j] = ok ? ((e2[j] / s2) * tsum - tg[j]) / (float)B : 0.f;   // d(mean_b l_b) / d pol
-            lp += ok ? -tg[j] * (pv[j] - ls2) : 0.f;
-            dot += dp[j] * pv[j];
+            for (int j = 0; j < 4; ++j) {
+                pv[j] = pv[j] / se;                                  // first softmax (the network's own, pv_network_gnn.py:42)
+                e2[j] = lane + 64 * j < A ? expf(pv[j]) : 0.f;       // second softmax inside CrossEntropyLoss; p in [0,1]: no shift needed
+                s2 += e2[j];
+            }
+            s2 = wave_sum(s2);
+            const float ls2 = logf(s2);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool ok = lane + 64 * j < A;
+                dp[j] = ok ? ((e2[j] / s2) * tsum - tg[j]) / (float)B : 0.f;   // d(mean_b l_b) / d pol
+                lp += ok ? -tg[j] * (pv[j] - ls2) : 0.f;
+                dot += dp[j] * pv[j];
+            }
+            lp = wave_sum(lp);
+            dot = wave_sum(dot);
         }
-        lp = wave_sum(lp);
-        dot = wave_sum(dot);
         const float vsum = wave_sum(wv2q * hs[HH + lane]);       // the value head's 64-term dot product
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int a = lane + 64 * j;
-            const float dlogit = a < A ? pv[j] * (dp[j] - dot) : 0.f;   // back through the first softmax
+            float dlogit;
+            if constexpr (LF == LOSS_CE) dlogit = dp[j];
+            else dlogit = a < A ? pv[j] * (dp[j] - dot) : 0.f;          // back through the first softmax
             dl[a] = dlogit;                                             // (zero for the rows A..255 of the padded row groups)
             if (a < A) {
                 pol[(size_t)b * A + a] = pv[j];
@@ -171,7 +195,8 @@ __device__ __forceinline__ void heads_board(TrainHeadsSmem& sm, int b, const Hea
         }
         const float v = tanhf(vsum + bvq);
         const float dv = v - ztq;
-        const float dvp0 = (2.f * dv / (float)B) * (1.f - v * v);
+        float dvp0 = (2.f * dv / (float)B) * (1.f - v * v);
+        if constexpr (LF != LOSS_PLAIN) dvp0 *= vw;
         if (lane == 0) {
             red[0][0][0] = dvp0;
             val[b] = v;

@@ -166,19 +166,24 @@ __device__ __forceinline__ void aggregate_tr(const unsigned int (&AF)[2][AF_BLOC
 typedef __attribute__((address_space(3))) TrainHeadsSmem TrainHeadsSmemLds;
 typedef const __attribute__((address_space(1))) float* gcf;           // pointer arguments in the global address space: global_, not flat_
 typedef __attribute__((address_space(1))) float* gf;
+//  (LF: the loss form of heads_board; the plain form's arguments are what they have always been, any other form's value weight
+//  travels as one more register argument)
+template <int LF = LOSS_PLAIN, class... VW>
 __device__ __attribute__((noinline)) void heads_board_call(unsigned int sm_lds, int b, gcf w0, gcf w1, gcf w2, gcf w3, gcf w4, gcf w5, gcf w6, gcf w7,
                                                            gcf pi_all, gcf z_all, const __attribute__((address_space(1))) int64_t* order, int first,
-                                                           int A, int B, gf hp, gf hv, gf lg, gf pol, gf vp, gf val, gf loss, gf dhp, gf dhv) {
+                                                           int A, int B, gf hp, gf hv, gf lg, gf pol, gf vp, gf val, gf loss, gf dhp, gf dhv, VW... vw) {
+    static_assert(sizeof...(VW) == (LF == LOSS_PLAIN ? 0 : 1), "a value weight with every form but the plain one");
     TrainHeadsSmem& sm = *(TrainHeadsSmem*)reinterpret_cast<TrainHeadsSmemLds*>((size_t)sm_lds);
     HeadParams Pg;
     Pg.p[0] = (const float*)w0; Pg.p[1] = (const float*)w1; Pg.p[2] = (const float*)w2; Pg.p[3] = (const float*)w3;
     Pg.p[4] = (const float*)w4; Pg.p[5] = (const float*)w5; Pg.p[6] = (const float*)w6; Pg.p[7] = (const float*)w7;
-    heads_board(sm, b, Pg, (const float*)pi_all, (const float*)z_all, (const int64_t*)order, first, A, B, (float*)hp, (float*)hv, (float*)lg,
-                (float*)pol, (float*)vp, (float*)val, (float*)loss, (float*)dhp, (float*)dhv);
+    heads_board<LF>(sm, b, Pg, (const float*)pi_all, (const float*)z_all, (const int64_t*)order, first, A, B, (float*)hp, (float*)hv,
+                    (float*)lg, (float*)pol, (float*)vp, (float*)val, (float*)loss, (float*)dhp, (float*)dhv, vw...);
 }
 
 // returns false (to every thread of the workgroup) if a value left fp16 range or a block of weights sits below the split's scale
 // (header): the caller redoes the board with the f32 body
+template <int LF = LOSS_PLAIN, class... VW>
 __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict__ smem, const uint8_t* __restrict__ states72,
                                                        const int64_t* __restrict__ order, int first,
                                                        const TrunkParams& tp, const HeadParams& hpm, const float* __restrict__ pi_all,
@@ -188,7 +193,7 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
                                                        float* __restrict__ pol, float* __restrict__ vp, float* __restrict__ val,
                                                        float* __restrict__ loss, float* __restrict__ dhp, float* __restrict__ dhv,
                                                        float* __restrict__ part_dW3, float* __restrict__ part_dW2,
-                                                       float* __restrict__ part_dW1, float* __restrict__ part_db) {
+                                                       float* __restrict__ part_dW1, float* __restrict__ part_db, VW... vw) {
     constexpr int N = 9, V = 81;
     SplitSmem& sm = *reinterpret_cast<SplitSmem*>(smem);
     TrainHeadsSmem& hsm = *reinterpret_cast<TrainHeadsSmem*>(&sm.FR[0][0][0][0][0]);
@@ -406,9 +411,9 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
     };
     TS(3, 5)
     // ---- heads, losses, head gradients (its first barrier publishes gs)
-    heads_board_call((unsigned int)(size_t)(TrainHeadsSmemLds*)&hsm, b, (gcf)hpm.p[0], (gcf)hpm.p[1], (gcf)hpm.p[2], (gcf)hpm.p[3], (gcf)hpm.p[4], (gcf)hpm.p[5],
+    heads_board_call<LF>((unsigned int)(size_t)(TrainHeadsSmemLds*)&hsm, b, (gcf)hpm.p[0], (gcf)hpm.p[1], (gcf)hpm.p[2], (gcf)hpm.p[3], (gcf)hpm.p[4], (gcf)hpm.p[5],
                      (gcf)hpm.p[6], (gcf)hpm.p[7], (gcf)pi_all, (gcf)z_all, (const __attribute__((address_space(1))) int64_t*)order, first, A, B,
-                     (gf)hp, (gf)hv, (gf)lg, (gf)pol, (gf)vp, (gf)val, (gf)loss, (gf)dhp, (gf)dhv);
+                     (gf)hp, (gf)hv, (gf)lg, (gf)pol, (gf)vp, (gf)val, (gf)loss, (gf)dhp, (gf)dhv, vw...);
     TS(3, 6)
     {
         // (requested BEHIND the call: hoisted above it -- which the compiler does unless the base pointers pass through this empty
@@ -563,6 +568,8 @@ __device__ __forceinline__ bool train_board_split_body(unsigned char* __restrict
 }
 
 // option "train_fused" = 3 forces the fallback for every board (tests)
+// (LF, vw: as train_board_kernel's -- the plain form takes no further argument)
+template <int LF = LOSS_PLAIN, class... VW>
 __global__ __launch_bounds__(512) void train_board_split_kernel(const uint8_t* __restrict__ states72, const int64_t* __restrict__ order, int first,
                                                                 TrunkParams tp, HeadParams hpm, const float* __restrict__ pi_all,
                                                                 const float* __restrict__ z_all, int A, int B, int force_fallback,
@@ -571,15 +578,15 @@ __global__ __launch_bounds__(512) void train_board_split_kernel(const uint8_t* _
                                                                 float* __restrict__ pol, float* __restrict__ vp, float* __restrict__ val,
                                                                 float* __restrict__ loss, float* __restrict__ dhp, float* __restrict__ dhv,
                                                                 float* __restrict__ part_dW3, float* __restrict__ part_dW2,
-                                                                float* __restrict__ part_dW1, float* __restrict__ part_db) {
+                                                                float* __restrict__ part_dW1, float* __restrict__ part_db, VW... vw) {
     __shared__ __align__(16) unsigned char smem[SPLIT_KERNEL_SMEM];
-    const bool ok = train_board_split_body(smem, states72, order, first, tp, hpm, pi_all, z_all, A, B, h1, h2, g_out, hp, hv, lg, pol, vp, val,
-                                           loss, dhp, dhv, part_dW3, part_dW2, part_dW1, part_db);
+    const bool ok = train_board_split_body<LF>(smem, states72, order, first, tp, hpm, pi_all, z_all, A, B, h1, h2, g_out, hp, hv, lg, pol, vp,
+                                               val, loss, dhp, dhv, part_dW3, part_dW2, part_dW1, part_db, vw...);
     if (ok && !force_fallback) return;
     if (threadIdx.x == 0) atomicAdd(&g_train_fallbacks, 1u);
     __syncthreads();
-    train_board_f32_body<9>(smem, states72, order, first, tp, hpm, pi_all, z_all, A, B, 96, h1, h2, g_out, hp, hv, lg, pol, vp, val, loss,
-                            dhp, dhv, part_dW3, part_dW2, part_dW1, part_db);
+    train_board_f32_body<9, LF>(smem, states72, order, first, tp, hpm, pi_all, z_all, A, B, 96, h1, h2, g_out, hp, hv, lg, pol, vp, val, loss,
+                                dhp, dhv, part_dW3, part_dW2, part_dW1, part_db, vw...);
 }
 
 long long train_fallbacks(int reset) {
@@ -593,14 +600,23 @@ AQG_TRAIN_DEBUG_SETTER(train_debug_buf_split)
 
 // 9x9 only; h1 / h2 hold 96 rows per board here: the parked fragments (and the fallback's rows)
 int launch_train_board_split(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, int first,
-                             int B, int force_fallback, hipStream_t st) {
+                             int B, int force_fallback, hipStream_t st, const aqg_loss* lf) {
     TrunkParams tp;
     for (int i = 0; i < 6; ++i) tp.p[i] = t.params[i];
     HeadParams hp;
     for (int i = 0; i < 8; ++i) hp.p[i] = t.params[6 + i];
     float *pdW3 = t.part, *pdW2 = pdW3 + (size_t)B * TH * TH, *pdW1 = pdW2 + (size_t)B * TH * TH, *pdb = pdW1 + (size_t)B * TH * TF;
-    hipLaunchKernelGGL(train_board_split_kernel, dim3(B), dim3(512), 0, st, states72, order, first, tp, hp, pi, z, t.policy_size, B,
-                       force_fallback, t.h1, t.h2, t.g, t.hp, t.hv, t.lg, t.pol, t.vp, t.val, t.loss, t.dhp, t.dhv, pdW3, pdW2, pdW1, pdb);
+    if (lf && lf->policy_form == 1)
+        hipLaunchKernelGGL((train_board_split_kernel<LOSS_CE, float>), dim3(B), dim3(512), 0, st, states72, order, first, tp, hp, pi, z,
+                           t.policy_size, B, force_fallback, t.h1, t.h2, t.g, t.hp, t.hv, t.lg, t.pol, t.vp, t.val, t.loss, t.dhp, t.dhv, pdW3,
+                           pdW2, pdW1, pdb, lf->value_weight);
+    else if (lf)
+        hipLaunchKernelGGL((train_board_split_kernel<LOSS_REF_W, float>), dim3(B), dim3(512), 0, st, states72, order, first, tp, hp, pi, z,
+                           t.policy_size, B, force_fallback, t.h1, t.h2, t.g, t.hp, t.hv, t.lg, t.pol, t.vp, t.val, t.loss, t.dhp, t.dhv, pdW3,
+                           pdW2, pdW1, pdb, lf->value_weight);
+    else
+        hipLaunchKernelGGL(train_board_split_kernel<>, dim3(B), dim3(512), 0, st, states72, order, first, tp, hp, pi, z, t.policy_size, B,
+                           force_fallback, t.h1, t.h2, t.g, t.hp, t.hv, t.lg, t.pol, t.vp, t.val, t.loss, t.dhp, t.dhv, pdW3, pdW2, pdW1, pdb);
     return check_launch("training forward/backward kernels");
 }
 

@@ -199,19 +199,20 @@ inline int average_after_update(const aqg_weight_average* avg, int step, hipStre
     return avg && step % avg->every == 0 ? launch_weight_average(*avg, st) : 0;
 }
 
-// ---- gcn_train.hip  (plan: null = the step as it has always been; avg: null = no average is kept)
+// ---- gcn_train.hip  (plan: null = the step as it has always been; avg: null = no average is kept; lf: null = the reference's loss)
 extern int g_train_fused;
 int train_step(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
-               const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr);
+               const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr, const aqg_loss* lf = nullptr);
 int train_steps(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, long long positions,
-                float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr);
+                float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr,
+                const aqg_loss* lf = nullptr);
 void train_tensor_sizes(const aqg_train& t, size_t* numel);
 
 // ---- gcn_train_exact.hip, gcn_train_split.hip, gcn_train_final.hip: the two launches of a fused training step
 int launch_train_board_exact(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, int first,
-                             int B, hipStream_t st);
+                             int B, hipStream_t st, const aqg_loss* lf = nullptr);
 int launch_train_board_split(const aqg_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order, int first,
-                             int B, int force_fallback, hipStream_t st);
+                             int B, int force_fallback, hipStream_t st, const aqg_loss* lf = nullptr);
 long long train_fallbacks(int reset);
 int launch_train_final(const aqg_train& t, int B, bool compute, bool update, int step, float* loss_sums, hipStream_t st,
                        const OptimLaunch* ol = nullptr);
@@ -230,20 +231,27 @@ int launch_train_general_prep(int V, int B, const uint8_t* states72, const int64
                               hipStream_t st);
 int launch_train_general_loss(int B, int A, const float* policy, const float* value, const float* pi, const float* z,
                               const int64_t* order, int first, float* loss, float* dpol, float* dval, hipStream_t st);
+int launch_policy_value_loss(int B, int A, const float* logits, const float* value, const float* pi, const float* z, const int64_t* order,
+                             int first, float value_weight, float* loss, float* dlogits, float* dvpre, hipStream_t st);
+int launch_train_losses(int B, int A, const float* logits, const float* policy, const float* value, const float* pi, const float* z,
+                        const int64_t* order, int first, const aqg_loss* lf, float* loss, float* dpol, float* dval, float* dlogits,
+                        float* dvpre, hipStream_t st);
 size_t train_general_workspace_floats(int N, int hidden, int num_layers, int policy_size, int max_batch);
 int train_step_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
-                       const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr);
+                       const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr, const aqg_loss* lf = nullptr);
 int train_steps_general(const aqg_train_general& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
-                        long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr);
+                        long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr,
+                        const aqg_loss* lf = nullptr);
 void train_general_tensor_sizes(const aqg_train_general& t, size_t* numel);
 
 // ---- cnn_train.hip
 size_t cnn_train_workspace_floats(int N, int F, int L, int A, int max_batch);
 int check_cnn_train(const aqg_cnn_train& t, bool adam, const char* what);
 int cnn_train_step(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, int mode, hipStream_t st,
-                   const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr);
+                   const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr, const aqg_loss* lf = nullptr);
 int cnn_train_steps(const aqg_cnn_train& t, const uint8_t* states72, const float* pi, const float* z, const int64_t* order,
-                    long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr);
+                    long long positions, float* loss_sums, hipStream_t st, const OptimPlan* plan = nullptr, const aqg_weight_average* avg = nullptr,
+                    const aqg_loss* lf = nullptr);
 void cnn_train_tensor_sizes(const aqg_cnn_train& t, size_t* numel);
 
 // ---- augment.hip

@@ -12,7 +12,7 @@ from .reanalyse import check_reanalyse_options
 from .replay import ReplayWindow, check_holdout_options, check_surprise_options, check_value_blend
 from .selfplay_options import (check_policy_record, check_policy_target, check_resign, check_target_options, check_tree_reuse,
                                check_value_lambda)
-from .train_reference import check_average_controls
+from .train_reference import check_average_controls, check_loss_controls
 
 DESCRIPTION = """`python -m alphaquoridorgnn_amd.train_cycle` -- also the per-rank program of
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P -m
@@ -86,6 +86,13 @@ def _parser():
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="M",
                     help="parameter update: scale every step's gradient to a global L2 norm of at most M, as "
                          "torch.nn.utils.clip_grad_norm_ (default TRAIN_MAX_GRAD_NORM = None: off)")
+    ap.add_argument("--policy-loss", choices=("reference", "cross-entropy"), default=None,
+                    help="parameter update: the policy loss -- 'reference', CrossEntropyLoss on the already-softmaxed policy, or "
+                         "'cross-entropy', the cross-entropy between the target and softmax(logits), taken from the logits inside the "
+                         "HIP step (default TRAIN_POLICY_LOSS = 'reference')")
+    ap.add_argument("--value-loss-weight", type=_value_loss_weight, default=None, metavar="W",
+                    help="parameter update: weight W >= 0 of the value term, the loss minimised being policy + W * value (default "
+                         "TRAIN_VALUE_LOSS_WEIGHT = 1)")
     ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
                     help="parameter update: keep an exponential moving average of the parameters with decay D in [0, 1), updated "
                          "inside the HIP steps, and save IT as latest.pth (default TRAIN_EMA_DECAY = None: off, the last iterate)")
@@ -430,6 +437,22 @@ def _set_optimiser_options(args):
         tn.TRAIN_MAX_GRAD_NORM = args.max_grad_norm
 
 
+def _value_loss_weight(text):
+    """argparse type of --value-loss-weight: a finite number >= 0, refused at parse time in the library's words."""
+    try:
+        return check_loss_controls("reference", float(text))[1]
+    except ValueError as err:
+        raise argparse.ArgumentTypeError(str(err)) from None
+
+
+def _set_loss_options(args):
+    """--policy-loss / --value-loss-weight onto train_network's constants."""
+    if args.policy_loss is not None:
+        tn.TRAIN_POLICY_LOSS = args.policy_loss.replace("-", "_")
+    if args.value_loss_weight is not None:
+        tn.TRAIN_VALUE_LOSS_WEIGHT = args.value_loss_weight
+
+
 def _check_average_args(args):
     """--ema-decay / --ema-every, refused as the library refuses them."""
     if args.ema_decay is None:
@@ -473,7 +496,7 @@ def apply_args(args):
     if args.epochs is not None:
         tn.NUM_EPOCH = args.epochs
     for set_options in (_set_target_options, _set_tree_reuse_options, _set_resign_options, _set_mirror_options, _set_optimiser_options,
-                        _set_average_options, _set_replay_options, _set_surprise_options, _set_holdout_options,
+                        _set_loss_options, _set_average_options, _set_replay_options, _set_surprise_options, _set_holdout_options,
                         _set_reanalyse_options, _set_policy_options, _set_start_options):
         set_options(args)
     if args.eval_games is not None:

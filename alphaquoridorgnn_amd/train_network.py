@@ -19,7 +19,8 @@ from .constants import PV_NETWORK_PATH, BOARD_SIZE  # noqa: F401
 from .pv_network_gnn import STATE_DICT_KEYS, HIDDEN_DIM, NUM_FEATURES, load_network, pack_states  # noqa: F401
 from .train_augment import draw_mirror_flips, _mirror_arguments, _augment_launch, augment_gather  # noqa: F401
 from .train_reference import (LEARNING_RATE, clip_coefficient, adam_reference, weight_average_reference,  # noqa: F401
-                              weight_average_due, check_average_controls, _checked_average_controls)
+                              weight_average_due, check_average_controls, _checked_average_controls, check_loss_controls,
+                              loss_reference)
 from .trainers import BATCH_SIZE, default_decay_mask, grad_norm, _Trainer, GNNTrainer, GeneralTrainer, CNNTrainer  # noqa: F401
 from .weight_average import weight_average_table, WeightAverage  # noqa: F401
 
@@ -65,6 +66,10 @@ TRAIN_HOLDOUT_SEED = 0
 TRAIN_HOLDOUT_EVERY = 1           # V >= 1: validate after every V-th epoch, and always after the last
 TRAIN_HOLDOUT_KEEP_BEST = False   # True: save the snapshot of the validated epoch with the least policy_loss + value_mse (first minimum)
 TRAIN_HOLDOUT_LOG = None          # a path: one JSON line per update is appended (curve, table, counts, options)
+# Loss form (the reference applies CrossEntropyLoss to the already-softmaxed policy; include/aqgnn.h "loss form"): the cross-entropy
+# between the target and softmax(logits), taken from the logits inside the HIP steps, and a weight on the value term's gradient.
+TRAIN_POLICY_LOSS = 'reference'   # 'reference' = the reference's double softmax; 'cross_entropy' = the AlphaZero policy loss
+TRAIN_VALUE_LOSS_WEIGHT = 1.0     # w >= 0: the loss minimised is policy + w * value (the value loss printed stays unweighted)
 
 
 def load_data():
@@ -203,14 +208,39 @@ def _configured_controls():
     return dict(weight_decay=TRAIN_WEIGHT_DECAY, decoupled=TRAIN_DECOUPLED, max_grad_norm=TRAIN_MAX_GRAD_NORM)
 
 
+def _configured_loss():
+    """The trainers' loss keyword arguments from TRAIN_POLICY_LOSS and TRAIN_VALUE_LOSS_WEIGHT, passed beside the controls'."""
+    return dict(policy_loss=TRAIN_POLICY_LOSS, value_loss_weight=TRAIN_VALUE_LOSS_WEIGHT)
+
+
+def _loss_form(trainer):
+    """(policy form 0 / 1, value weight) of `trainer`; one that does not know the option (None included) has the reference's."""
+    return check_loss_controls(getattr(trainer, "policy_loss", "reference"), getattr(trainer, "value_loss_weight", 1.0))
+
+
+def _cross_entropy(trainer):
+    """Whether `trainer` minimises the cross-entropy form (what the progress line and the validation then print and score)."""
+    return _loss_form(trainer)[0] == 1
+
+
+def _validation_loss(metrics, trainer):
+    """(the held-out policy loss in the form `trainer` minimises, the score of TRAIN_HOLDOUT_KEEP_BEST = the loss the update
+    minimises) of a validation.Metrics: policy_loss and policy_loss + value_mse with the reference's form and weight 1, as always;
+    under the cross-entropy the table's ce column and ce + w * value_mse."""
+    form, w = _loss_form(trainer)
+    policy = metrics.policy_ce if form == 1 else metrics.policy_loss
+    return policy, (policy + metrics.value_mse if w == 1.0 else policy + w * metrics.value_mse)
+
+
 def _progress_line(epoch, policy_loss, value_loss, trainer, val=None):
     """The per-epoch progress line (train_network.py:100); with clipping on, the epoch's mean gradient norm beside it (one host read of
     grad_norms per epoch); val (a validation.Metrics of this epoch): the held-out numbers behind it."""
-    line = f"\rEpoch {epoch + 1}/{NUM_EPOCH} | Policy Loss: {float(policy_loss):.4f} | Value Loss: {float(value_loss):.4f}"
+    name = "Policy Loss (CE)" if _cross_entropy(trainer) else "Policy Loss"
+    line = f"\rEpoch {epoch + 1}/{NUM_EPOCH} | {name}: {float(policy_loss):.4f} | Value Loss: {float(value_loss):.4f}"
     if trainer.max_grad_norm and trainer.grad_norms.numel():
         line += f" | Grad Norm: {float(trainer.grad_norms.mean()):.4f}"
     if val is not None:
-        line += f" | Val Loss: {val.policy_loss:.4f} / {val.value_mse:.4f} | Val KL: {val.kl:.4f} | Top-1: {val.top1:.3f}"
+        line += f" | Val Loss: {_validation_loss(val, trainer)[0]:.4f} / {val.value_mse:.4f} | Val KL: {val.kl:.4f} | Top-1: {val.top1:.3f}"
     return line
 
 
@@ -220,8 +250,9 @@ class _Holdout:
     module, built once through `load` and filled by average.copy_to(twin) at every validation; otherwise the model itself.  Every rank
     holds one and decides alike: no collective."""
 
-    def __init__(self, held, model, average, load, dev):
+    def __init__(self, held, model, average, load, dev, trainer=None):
         from .replay_reference import check_holdout_options
+        self.trainer = trainer                  # its loss form decides the score; None: the reference's
         self.share, self.seed, self.every = check_holdout_options(TRAIN_HOLDOUT_SHARE, TRAIN_HOLDOUT_SEED, TRAIN_HOLDOUT_EVERY)
         self.keep_best = bool(TRAIN_HOLDOUT_KEEP_BEST)
         self.rows, self.index, self.counts = held["rows"], held["index"], held["counts"]
@@ -240,7 +271,7 @@ class _Holdout:
             self.average.copy_to(self.twin)
             target = self.twin
         self.last = row_metrics(target, *self.rows, self.index)
-        score = self.last.policy_loss + self.last.value_mse             # the loss the update minimises
+        score = _validation_loss(self.last, self.trainer)[1]            # the loss the update minimises, in the trainer's form
         self.curve.append(dict(epoch=epoch + 1, score=score, **self.last.totals()))
         if self.best_score is None or score < self.best_score:          # on ties the first minimum stays
             self.best, self.best_epoch, self.best_score = self.last, epoch + 1, score
@@ -264,7 +295,11 @@ class _Holdout:
     def report(self):
         lines = []
         if self.keep_best:
-            lines.append(f"kept epoch {self.best_epoch}/{NUM_EPOCH}: held-out policy loss + value MSE = {self.best_score:.4f}")
+            form, w = _loss_form(self.trainer)
+            what = "policy loss + value MSE"
+            if (form, w) != (0, 1.0):
+                what = f"{'policy CE' if form == 1 else 'policy loss'} + {w:g} x value MSE"
+            lines.append(f"kept epoch {self.best_epoch}/{NUM_EPOCH}: held-out {what} = {self.best_score:.4f}")
         lines.append(self.saved().table())
         return "\n".join(lines)
 
@@ -276,6 +311,9 @@ class _Holdout:
                        ema_decay=TRAIN_EMA_DECAY, ema_every=TRAIN_EMA_EVERY, merge_positions=bool(TRAIN_MERGE_POSITIONS),
                        surprise_weighting=bool(TRAIN_SURPRISE_WEIGHTING), mirror=bool(TRAIN_MIRROR), epoch_rows=TRAIN_EPOCH_ROWS,
                        weight_decay=TRAIN_WEIGHT_DECAY, max_grad_norm=TRAIN_MAX_GRAD_NORM)
+        form, w = _loss_form(self.trainer)
+        if (form, w) != (0, 1.0):                                         # (the line is what it was with the option off)
+            options.update(policy_loss="cross_entropy" if form == 1 else "reference", value_loss_weight=w)
         record = dict(curve=self.curve, saved_epoch=self.best_epoch if self.keep_best else self.curve[-1]["epoch"],
                       table=self.saved().as_dict(), split=self.counts, options=options)
         return json.dumps(_finite_or_none(record))
@@ -297,12 +335,13 @@ CNN_TRAINING_NOT_BUILT = ("training the residual CNN through train_network() / t
 
 def trainer_for(model, max_batch=BATCH_SIZE):
     """GNNTrainer for the default 6/128/3 network (the fused step), GeneralTrainer for every other shape, with the configured
-    optimiser controls (TRAIN_WEIGHT_DECAY, TRAIN_DECOUPLED, TRAIN_MAX_GRAD_NORM)."""
+    optimiser controls (TRAIN_WEIGHT_DECAY, TRAIN_DECOUPLED, TRAIN_MAX_GRAD_NORM) and loss form (TRAIN_POLICY_LOSS,
+    TRAIN_VALUE_LOSS_WEIGHT)."""
     from .pv_network_cnn import CNNNetwork
     if isinstance(model, CNNNetwork):
         raise NotImplementedError(CNN_TRAINING_NOT_BUILT)
     kind = GNNTrainer if getattr(model, "fused", False) else GeneralTrainer
-    return kind(model, max_batch=max_batch, **_configured_controls())
+    return kind(model, max_batch=max_batch, **_configured_controls(), **_configured_loss())
 
 
 def train_network():
@@ -326,7 +365,8 @@ def train_cnn_network():
     newest .history, every step on HIP (CNNTrainer) -> latest.pth with every state_dict key (202 at 128 filters x 16 blocks).
     Under torch.distributed rank 0 trains alone and the others wait (synchronised BatchNorm is not built)."""
     from .pv_network_cnn import load_network as load_cnn
-    _train(load_cnn, lambda model, max_batch: CNNTrainer(model, max_batch=max_batch, **_configured_controls()), data_parallel=False)
+    _train(load_cnn, lambda model, max_batch: CNNTrainer(model, max_batch=max_batch, **_configured_controls(), **_configured_loss()),
+           data_parallel=False)
 
 
 def _train(load, make_trainer, data_parallel):
@@ -357,7 +397,7 @@ def _train_loop(load, make_trainer, rank, world):
     trainer = make_trainer(model, max_batch=BATCH_SIZE)
     # every rank keeps its own average of its own (identical) parameters: no collective
     average = None if TRAIN_EMA_DECAY is None else WeightAverage(trainer, decay=TRAIN_EMA_DECAY, every=TRAIN_EMA_EVERY)
-    holdout = None if held is None else _Holdout(held, model, average, load, dev)      # every rank validates and decides alike
+    holdout = None if held is None else _Holdout(held, model, average, load, dev, trainer)      # every rank validates and decides alike
     for epoch in range(NUM_EPOCH):
         lr = LEARNING_RATE * lr_lambda(epoch)                                      # LambdaLR, stepped once per epoch (:98)
         perm = torch.randperm(n, device=dev)                                    # DataLoader(shuffle=True), last batch kept

@@ -1,5 +1,6 @@
-"""The numpy statements of the parameter update: what the tests hold the HIP optimiser steps and the weight average to, and the one
-check of the average's controls.  numpy only -- no torch, no library -- so a test or a tool may import it without either."""
+"""The numpy statements of the parameter update and of the loss forms: what the tests hold the HIP optimiser steps, the weight
+average and the losses to, and the one check of the average's controls and of the loss controls.  numpy only -- no torch, no
+library -- so a test or a tool may import it without either."""
 import numpy as np
 
 LEARNING_RATE = 0.001   # train_network.py:56
@@ -63,3 +64,60 @@ def check_average_controls(decay, every):
 
 
 _checked_average_controls = check_average_controls          # the name it had in train_network
+
+
+POLICY_LOSS_FORMS = {"reference": 0, "cross_entropy": 1}    # aqg_loss.policy_form (include/aqgnn.h "loss form")
+
+
+def check_loss_controls(policy_loss, value_loss_weight):
+    """(policy_form as the int the library takes, value weight as float), refused in the library's words."""
+    form = policy_loss if isinstance(policy_loss, (int, np.integer)) and not isinstance(policy_loss, bool) \
+        else POLICY_LOSS_FORMS.get(policy_loss, -1)
+    if form not in (0, 1):
+        raise ValueError(f"policy_form must be 0 (reference) or 1 (cross-entropy): policy_loss is 'reference' or 'cross_entropy' "
+                         f"(got {policy_loss!r})")
+    try:
+        w = float(np.float32(value_loss_weight))
+    except (TypeError, ValueError):
+        raise ValueError("value_weight must be finite and >= 0") from None
+    if not (w >= 0 and np.isfinite(w)):
+        raise ValueError(f"value_weight must be finite and >= 0 (got {value_loss_weight!r})")
+    return int(form), w
+
+
+def loss_reference(logits, value, pi, z, policy_form=1, value_weight=1.0):
+    """Both loss terms of a batch and their gradients at the logits and at the pre-tanh value (include/aqgnn.h "loss form"), in
+    numpy float64.  logits [B, A], value [B] (the tanh output), pi [B, A] (targets, not renormalised), z [B].
+    Returns (loss [B, 2], dlogits [B, A], dvpre [B]): loss[b] = (l_b in the chosen form, the unweighted (v - z)^2); the gradients
+    are those of mean_b l_b + value_weight mean_b (v - z)^2.
+      policy_form 1: m = max x, lse = m + ln sum exp(x - m), l_b = T lse - sum_a t_a x_a (summed as t_a (lse - x_a)),
+                     dlogit = (softmax(x) T - t) / B  -- torch.nn.CrossEntropyLoss()(logits, t) with probability targets
+      policy_form 0: the reference's, the same expression on p = softmax(x) in place of x, then back through the softmax."""
+    x = np.asarray(logits, dtype=np.float64)
+    v = np.asarray(value, dtype=np.float64)
+    t = np.asarray(pi, dtype=np.float64)
+    z = np.asarray(z, dtype=np.float64)
+    B = x.shape[0]
+    T = t.sum(axis=1, keepdims=True)
+
+    def lse_of(y):
+        m = y.max(axis=1, keepdims=True)
+        e = np.exp(y - m)
+        s = e.sum(axis=1, keepdims=True)
+        return m + np.log(s), e / s
+
+    lse, p = lse_of(x)
+    if policy_form == 1:
+        lp = (t * (lse - x)).sum(axis=1)
+        dlogits = (p * T - t) / B
+    elif policy_form == 0:
+        lse2, p2 = lse_of(p)
+        lp = (t * (lse2 - p)).sum(axis=1)
+        dp = (p2 * T - t) / B
+        dlogits = p * (dp - (dp * p).sum(axis=1, keepdims=True))
+    else:
+        raise ValueError("policy_form must be 0 (reference) or 1 (cross-entropy)")
+    dv = v - z
+    loss = np.stack([lp, dv * dv], axis=1)
+    dvpre = float(value_weight) * 2.0 * dv / B * (1.0 - v * v)
+    return loss, dlogits, dvpre

@@ -11,7 +11,7 @@ from . import _lib
 from .distributed import rank_world
 from .pv_network_gnn import STATE_DICT_KEYS, HIDDEN_DIM, NUM_FEATURES
 from .train_augment import _augment_launch
-from .train_reference import LEARNING_RATE
+from .train_reference import LEARNING_RATE, check_loss_controls
 
 BATCH_SIZE = 128   # train_network.py:15
 
@@ -55,13 +55,21 @@ class _Trainer:
     torch.optim.Adam(weight_decay=) (False), and max_grad_norm = torch.nn.utils.clip_grad_norm_'s max_norm (None or 0 = off).  They
     are plain attributes read at every call, so a schedule may change them between steps.  With clipping on, last_grad_norm is the
     unclipped global gradient norm of the last step (0-dim device tensor) and grad_norms that of every step of the last run_epoch
-    (device tensor [steps]); neither is read by the host."""
+    (device tensor [steps]); neither is read by the host.
+
+    Loss form (include/aqgnn.h "loss form"; off by default: the calls above, by the names they have always had): policy_loss =
+    'reference' (CrossEntropyLoss on the already-softmaxed policy, train_network.py:54,85) or 'cross_entropy' (the cross-entropy
+    between the target and softmax(logits), taken from the logits inside the HIP steps), and value_loss_weight = w >= 0, which scales
+    the value term's gradient (the loss minimised is Lp + w Lv; the value loss REPORTED stays the unweighted mean squared error).
+    Plain attributes read at every call, as the controls are."""
 
     _GPU_REFUSAL = None       # a subclass's own words for a model that is not on the GPU (raised in front of require_gpu's)
 
     def __init__(self, model, max_batch=BATCH_SIZE, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, decay_all=False,
-                 max_grad_norm=None):
+                 max_grad_norm=None, policy_loss="reference", value_loss_weight=1.0):
         self.max_batch, self.betas, self.eps = max_batch, betas, eps
+        self.policy_loss, self.value_loss_weight = policy_loss, value_loss_weight
+        check_loss_controls(policy_loss, value_loss_weight)
         self.weight_decay, self.decoupled, self.decay_all, self.max_grad_norm = weight_decay, decoupled, decay_all, max_grad_norm
         self._build(model)
 
@@ -142,13 +150,28 @@ class _Trainer:
             o.workspace, o.workspace_floats = self._optim_ws.data_ptr(), self._optim_ws.numel()
         return o, norms
 
+    def _loss(self):
+        """aqg_loss of the trainer's loss form -- None with the default form (the reference's loss, weight 1)."""
+        form, w = check_loss_controls(self.policy_loss, self.value_loss_weight)
+        if form == 0 and w == 1.0:
+            return None
+        s = _lib.LossStruct()
+        s.policy_form, s.value_weight = form, w
+        return s
+
     def _invoke(self, name, args, steps, plain=False, updating=True):
         """One library call of `steps` steps: `name` itself when plain or with every control off (no aqg_optim is built), its
         _optim form otherwise -- or, with a weight average attached and a call that updates, its _avg form (the controls' struct or
-        NULL beside the average's).  Returns the device tensor the call's norms went to, or None."""
+        NULL beside the average's).  With a loss form that is not the default, the _loss form of any of these (the controls' and the
+        average's structs or NULL in front of the form's).  Returns the device tensor the call's norms went to, or None."""
         o, norms = (None, None) if plain else self._optim(steps)
         average = None if plain or not updating else self.average
-        if average is not None:
+        form = self._loss()
+        if form is not None:
+            a = None if average is None else average._struct()
+            name, controls = name + "_loss", (None if o is None else ctypes.byref(o), None if a is None else ctypes.byref(a),
+                                              ctypes.byref(form))
+        elif average is not None:
             a = average._struct()
             name, controls = name + "_avg", (None if o is None else ctypes.byref(o), ctypes.byref(a))
         else:
@@ -182,6 +205,7 @@ class _Trainer:
         B = int(states72.shape[0])
         if B > self.max_batch:
             raise ValueError("batch larger than the trainer's workspace")
+        check_loss_controls(self.policy_loss, self.value_loss_weight)       # refused before anything is counted or launched
         states72, pi_target, z_target = self._resident(states72, pi_target, z_target)
         if mirror is not None:
             states72, pi_target, z_target = _augment_launch(self.N, states72, pi_target, z_target, None, mirror)
@@ -229,6 +253,7 @@ class _Trainer:
         batch = self.max_batch if batch is None else int(batch)
         if batch > self.max_batch:
             raise ValueError("batch larger than the trainer's workspace")
+        check_loss_controls(self.policy_loss, self.value_loss_weight)
         n = int(order.shape[0])
         sums = torch.zeros((2,), dtype=torch.float32, device=self.dev)
         if n == 0:

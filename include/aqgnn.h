@@ -940,6 +940,56 @@ int aqg_cnn_train_steps_avg(const aqg_cnn_train* t_host, const uint8_t* states72
                             const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim,
                             const aqg_weight_average* avg, void* stream);
 
+/* ------------------------------------------------------------------ loss form (additive to ABI 15; the reference has one form)
+ *
+ * The policy loss of the three training steps above, as an option.  Per position b, with x the policy LOGITS, p = softmax(x) the
+ * network's policy, t the target row, T = sum_a t_a (targets are not renormalised), v the tanh value, z its target, B the batch:
+ *   policy_form 0, the reference's (train_network.py:54,85: CrossEntropyLoss applied to the ALREADY softmaxed policy):
+ *       l_b = -sum_a t_a log_softmax(p)_a,   dlogit = p (.) (dp - p . dp),  dp = (softmax(p) T - t) / B
+ *   policy_form 1, the cross-entropy between the target and softmax(x), taken from the logits:
+ *       m = max x,  lse = m + ln sum_a exp(x_a - m),  l_b = T lse - sum_a t_a x_a,   dlogit_a = (softmax(x)_a T - t_a) / B
+ *     -- loss and gradient of torch.nn.CrossEntropyLoss()(logits, t) with probability targets.  The loss is formed from the logits,
+ *     never from ln p: a target entry on an action whose p underflows gives a finite term.  An all-zero target row gives l_b = 0 and
+ *     a zero policy gradient.
+ *   value term, both forms: (v - z)^2.  value_weight = w (finite, >= 0; 1 = the reference) scales its gradient,
+ *       dvpre = w 2 (v - z) / B (1 - v^2),
+ *     so that the loss minimised is Lp + w Lv.  Reported terms: loss[2 b] = l_b in the chosen form, loss[2 b + 1] = the UNWEIGHTED
+ *     (v - z)^2 (the batch means and loss_sums likewise).
+ * Form 1 runs inside the steps: a second instantiation of the fused 6/128/3 board kernels whose wave-0 section has no second
+ * exponential round; in the general and CNN steps ONE kernel (policy_value_loss_kernel, csrc/gcn_train_general.hip) in place of the
+ * loss launch and the heads' backward launch.  Form 0 with w != 1: the fused step's third instantiation; the general and CNN steps
+ * keep their two launches and scale d loss / d value by w in one small launch between them.
+ *
+ * The six _loss entry points take the _avg call's arguments plus the form.  optim and avg may be NULL as there.  loss == NULL, or
+ *   {0, 1.0f}, IS the _avg call: the same launches.  Modes 0 and 1 use the option; mode 2 (update only) does not look at it beyond
+ *   the refusals.  Refused on the host before any launch (-1, aqg_last_error), besides all the _avg call refuses: a policy_form
+ *   other than 0 or 1, a negative or non-finite value_weight.
+ * aqg_policy_value_loss: form 1's kernel alone (policy_form must be 1).  B rows of A = 1 .. 4096 logits; the target row of position
+ *   b is row order[first + b] (order NULL: first + b) of pi [.][A] and z [.]; writes loss [B][2], dlogits [B][A], dvpre [B] and
+ *   nothing else.  One workgroup per row, sums in a fixed order, no atomics. */
+typedef struct aqg_loss {
+    int32_t policy_form;
+    float value_weight;
+} aqg_loss;
+int aqg_policy_value_loss(int B, int A, const float* logits, const float* value, const float* pi, const float* z, const int64_t* order,
+                          int first, const aqg_loss* loss_form, float* loss, float* dlogits, float* dvpre, void* stream);
+int aqg_gcn_train_step_loss(const aqg_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                            const aqg_optim* optim, const aqg_weight_average* avg, const aqg_loss* loss_form, void* stream);
+int aqg_gcn_train_steps_loss(const aqg_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target,
+                             const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim,
+                             const aqg_weight_average* avg, const aqg_loss* loss_form, void* stream);
+int aqg_gcn_train_step_general_loss(const aqg_train_general* t_host, const uint8_t* states72, const float* pi_target,
+                                    const float* z_target, int mode, const aqg_optim* optim, const aqg_weight_average* avg,
+                                    const aqg_loss* loss_form, void* stream);
+int aqg_gcn_train_steps_general_loss(const aqg_train_general* t_host, const uint8_t* states72, const float* pi_target,
+                                     const float* z_target, const int64_t* order, long long positions, float* loss_sums,
+                                     const aqg_optim* optim, const aqg_weight_average* avg, const aqg_loss* loss_form, void* stream);
+int aqg_cnn_train_step_loss(const aqg_cnn_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target, int mode,
+                            const aqg_optim* optim, const aqg_weight_average* avg, const aqg_loss* loss_form, void* stream);
+int aqg_cnn_train_steps_loss(const aqg_cnn_train* t_host, const uint8_t* states72, const float* pi_target, const float* z_target,
+                             const int64_t* order, long long positions, float* loss_sums, const aqg_optim* optim,
+                             const aqg_weight_average* avg, const aqg_loss* loss_form, void* stream);
+
 /* ------------------------------------------------------------------ training augmentation (additive to ABI 15; the reference has none)
  *
  * Quoridor is symmetric under the left-right mirror of the board: column y -> N - 1 - y in each player's own frame.  The mirror of a
