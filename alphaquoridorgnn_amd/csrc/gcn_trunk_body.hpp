@@ -52,6 +52,11 @@ struct alignas(16) TrunkSmemM {
     alignas(16) float dinvtab[8];                      // 1 / (81 CQ sqrt(deg)), deg = 1..5: the mean pool's weights, read by (deg - 1) * 4 (set once per workgroup)
     alignas(16) float dinv1[NWV][8];                   // 1 / sqrt(deg): the layer-1 input rows' weights, one copy per wave (written and
                                                        // read by the same wave: no barrier between kernel start and the first board's setup)
+    // the aggregation's bias rows, PackedLayout::TB regrouped per wave (set once per workgroup): a wave only ever reads its own 64 bytes
+    // of a row, so its five degrees' rows lie 64 bytes apart -- 320 bytes span 80 banks: degree 5 meets degree 1, every other pair of
+    // rows sits on banks of its own, and lanes of one (deg, q) read one address.  At most two-way conflicts for any mix of degrees
+    // (TB's own stride of 512 bytes would put all five rows on the same banks).
+    alignas(16) float BR[3][NWV][5][16];
 };
 static_assert(2 * sizeof(TrunkSmemM) <= 160 * 1024, "two 8-wave workgroups per CU");
 
@@ -140,10 +145,7 @@ __device__ __forceinline__ void split_tile_piece(const f32x4 z, int m, int piece
 // U = Q W~ for this wave's columns: six 16-row tiles (tile 5 = row 80 repeated) x four 32-deep k blocks, A fragments
 // double-buffered from the planes, three fp16 terms per block (smallest first).  The fp16 split of tile m - 1 (six vector
 // instructions per feature tile) is issued between the MFMA groups of tile m: it costs no time of its own.
-// mid() is called in front of step 0: the kernel requests the aggregation's bias rows there.
-struct NoMid { __device__ __forceinline__ void operator()() const {} };
-template <class Mid = NoMid>
-__device__ __forceinline__ void linear_split(const TrunkSmemM& sm, const u32x4 (&Bf)[2][4], int lane, u32x4 (&zh)[3], u32x4 (&zl)[3], Mid mid = Mid(),
+__device__ __forceinline__ void linear_split(const TrunkSmemM& sm, const u32x4 (&Bf)[2][4], int lane, u32x4 (&zh)[3], u32x4 (&zl)[3],
                                              float* zmax = nullptr) {
     const int c = lane & 15, q = lane >> 4;
     // the fragments of step s + 1 are requested while step s multiplies (two register pairs).  One step ahead is enough with four
@@ -164,7 +166,6 @@ __device__ __forceinline__ void linear_split(const TrunkSmemM& sm, const u32x4 (
 #pragma unroll
     for (int step = 0; step < 24; ++step) {
         const int m = step >> 2, kb = step & 3;
-        if (step == 0) mid();
         if (step + 1 < 24) request(step + 1);
         __builtin_amdgcn_sched_barrier(0);
         const u32x4 hi = ring[step & 1][0], lo = ring[step & 1][1];
@@ -183,12 +184,17 @@ __device__ __forceinline__ void linear_split(const TrunkSmemM& sm, const u32x4 (
 
 // The aggregation accumulators start from the bias: out[nt] = TB[layer][deg(node) - 1][this lane's 4 features] = CQ b sqrt(deg),
 // so that relu(out) IS the next plane image -- no multiply, no add on the vector unit.  `toff` packs (deg - 1) * 512 + 16 q per
-// node tile of this lane, 16 bits each.  Requested a whole phase ahead of their use (before the linear map).
-__device__ __forceinline__ void request_bias(f32x4 (&out)[6], __amdgpu_buffer_rsrc_t rs, int layer, const int (&toff)[3], int wave) {
+// node tile of this lane, 16 bits each.  The rows come from the workgroup's LDS image (TrunkSmemM::BR, rows 64 bytes apart: the row
+// offset moves from bit 9 to bit 6, for both tiles of a register at once), one ds_read_b128 per node tile: requested right in front
+// of the MFMAs that accumulate on them -- an LDS latency ahead, not a phase ahead, so `out` is not live across a linear map.
+__device__ __forceinline__ void request_bias(f32x4 (&out)[6], const TrunkSmemM& sm, int layer, const int (&toff)[3], int wave) {
+    const unsigned char* rows = reinterpret_cast<const unsigned char*>(&sm.BR[layer][wave][0][0]);
 #pragma unroll
-    for (int nt = 0; nt < 6; ++nt) {
-        const int vo = (nt & 1) ? (int)((unsigned)toff[nt >> 1] >> 16) : (toff[nt >> 1] & 0xFFFF);
-        out[nt] = __builtin_bit_cast(f32x4, load_frag16(rs, vo, (int)((PackedLayout::TB + (size_t)layer * 5 * HID) * sizeof(float)) + 64 * wave));
+    for (int p = 0; p < 3; ++p) {
+        const uint32_t t = (uint32_t)toff[p];
+        const uint32_t r = ((t >> 3) & 0x01C001C0u) | (t & 0x00300030u);          // (deg - 1) * 64 + 16 q, twice
+        out[2 * p] = *reinterpret_cast<const f32x4*>(rows + (r & 0xFFFFu));
+        out[2 * p + 1] = *reinterpret_cast<const f32x4*>(rows + (r >> 16));
     }
 }
 
@@ -566,17 +572,24 @@ __device__ __forceinline__ void trunk_boards_body(TrunkSmemM& sm, const unsigned
             if (b < B) fetch_record(b, rec0, rec1);
         }
     }
-    // once per workgroup: the k-slots 6, 7 of the hi and lo halves of every G' row, which no board ever writes.  No barrier here:
-    // their first reader sits behind the first board's setup barrier.
+    const __amdgpu_buffer_rsrc_t rs = packed_rsrc(pk);
+    // once per workgroup: the k-slots 6, 7 of the hi and lo halves of every G' row, which no board ever writes, and the bias rows of
+    // the three layers (one coalesced pass over the 7,680 bytes of PackedLayout::TB, 16 bytes per thread, into the per-wave grouping
+    // of TrunkSmemM::BR).  No barrier here: their first reader sits behind the first board's setup barrier.
     {
         const int t0 = (int)threadIdx.x;
+        constexpr int TB_WORDS = 3 * 5 * HID / 4;                        // 16-byte words of the table: [layer][deg - 1][wave][4]
+        if (t0 < TB_WORDS) {
+            const u32x4 row = load_frag16(rs, t0 * 16, (int)(PackedLayout::TB * sizeof(float)));
+            const int layer = t0 / (5 * HID / 4), r = t0 % (5 * HID / 4);
+            *reinterpret_cast<u32x4*>(&sm.BR[layer][(r >> 2) & (NWV - 1)][r >> 5][4 * (r & 3)]) = row;
+        }
         for (int i = t0; i < 81 * 2; i += 64 * NWV)
             *reinterpret_cast<unsigned int*>(&sm.G16[0][0] + 16 * (i >> 1) + 6 + 8 * (i & 1)) = 0u;
         if (t0 < 8) sm.dinvtab[t0] = dinv_of_dm((uint32_t)t0) * (float)(1.0 / (81.0 * CQ));      // (first read behind the layer-3 barriers)
         if ((t0 & 63) < 8) sm.dinv1[t0 >> 6][t0 & 63] = dinv_of_dm((uint32_t)(t0 & 63));           // each wave its own copy: no barrier here
     }
     u32x4 Bf[2][4];
-    const __amdgpu_buffer_rsrc_t rs = packed_rsrc(pk);
     const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(pooled, 0, B * (HID * 4), 0x00020000);
 
     auto build_inputs = [&](uint64_t hw, uint64_t vw, uint32_t hd, int what) {
@@ -603,7 +616,6 @@ __device__ __forceinline__ void trunk_boards_body(TrunkSmemM& sm, const unsigned
         trunk_bias_offsets(hw, vw, c, q, toff);
         f32x4 out[6];
         u32x4 zh[3], zl[3];
-        request_bias(out, rs, 0, toff, wave);                            // lands under the input build + barrier
         AQG_STAMP_AT(6)
         build_inputs(hw, vw, hd, 1);                                     // the layer-1 input rows G'
         int bn;
@@ -613,6 +625,7 @@ __device__ __forceinline__ void trunk_boards_body(TrunkSmemM& sm, const unsigned
         AQG_STAMP_AT(0)
         phase_prio(1);
         // ---- layer 1: one MFMA per node tile on top of the bias rows, relu, planes
+        request_bias(out, sm, 0, toff, wave);
         if (TRACK == 0 && (((hd >> 8) & 0xffu) > AQG_GNN_PROVEN_MAX_WALLS || (hd >> 24) > AQG_GNN_PROVEN_MAX_WALLS)) report_saturation(true, saturated);
         layer1_store<TRACK>(sm, sm.G16, w1f, out, wave, lane, saturated);
         AQG_STAMP_AT(8)
@@ -628,7 +641,7 @@ __device__ __forceinline__ void trunk_boards_body(TrunkSmemM& sm, const unsigned
         phase_prio(3);
         {
             float zmax = 0.f;
-            linear_split(sm, Bf, lane, zh, zl, [&]() { request_bias(out, rs, 1, toff, wave); }, TRACK == 2 ? &zmax : nullptr);
+            linear_split(sm, Bf, lane, zh, zl, TRACK == 2 ? &zmax : nullptr);
             if (TRACK == 2) report_saturation(!(zmax <= pk[PackedLayout::GUARD + 0]), saturated);
         }
         AQG_STAMP_AT(2)
@@ -642,6 +655,7 @@ __device__ __forceinline__ void trunk_boards_body(TrunkSmemM& sm, const unsigned
         AQG_BOARD_BARRIER();                                                    // every wave is done reading the planes
         AQG_STAMP_AT(13)
         phase_prio(4);
+        request_bias(out, sm, 1, toff, wave);
         aggregate_store<false>(sm, sm.AF, zh, zl, out, wave, lane, toff, prs, 0);
         AQG_STAMP_AT(14)
         AQG_BOARD_BARRIER();
@@ -651,12 +665,13 @@ __device__ __forceinline__ void trunk_boards_body(TrunkSmemM& sm, const unsigned
         AQG_STAMP_AT(10)
         {
             float zmax = 0.f;
-            linear_split(sm, Bf, lane, zh, zl, [&]() { request_bias(out, rs, 2, toff, wave); }, TRACK == 2 ? &zmax : nullptr);
+            linear_split(sm, Bf, lane, zh, zl, TRACK == 2 ? &zmax : nullptr);
             if (TRACK == 2) report_saturation(!(zmax <= pk[PackedLayout::GUARD + 1]), saturated);
         }
         AQG_STAMP_AT(4)
         AQG_STAMP_AT(15)
         phase_prio(6);
+        request_bias(out, sm, 2, toff, wave);
         aggregate_store<true>(sm, sm.AF, zh, zl, out, wave, lane, toff, prs, b * (HID * 4));
         rec0 = nrec0; rec1 = nrec1;
         // (No barrier at the end of a board: what the next board writes in front of its top barrier -- the G' rows, wave-private

@@ -3,8 +3,10 @@
     OUT=/tmp/parent/libaqgnn_hip.so <checkout of the parent commit>/alphaquoridorgnn_amd/csrc/build.sh
     python tools/compare_libs.py /tmp/parent/libaqgnn_hip.so alphaquoridorgnn_amd/libaqgnn_hip.so
 
-Each library runs in its own process (AQG_LIB_PATH): the GNN forward at 300 / 4,096 / 1,001 boards in both guard modes, a masked engine
-launch inside a 64-game GNN-evaluated generation (history rows), three training steps, and then every trainer (GeneralTrainer (6, 32, 2)
+Each library runs in its own process (AQG_LIB_PATH): the GNN forward at 300 / 4,096 / 1,001 boards in both guard modes (non-zero GCN
+biases), masked engine launches inside 64-game GNN-evaluated generations (history rows; a weight set inside the static fp16 bound and
+one outside it: both builds of the evaluation launch), three moves of 640 games with the evaluation cache on for both sets (the
+trunk's compact-list builds), three training steps, and then every trainer (GeneralTrainer (6, 32, 2)
 and CNNTrainer 8 filters x 1 block on 5x5, GNNTrainer on 9x9 and on 5x5) at max_batch 4 through steps of 4, 4 and 3 positions, a shuffled
 epoch of 10, both again with weight decay and clipping on, and a mode-0 then a mode-2 call: parameters, Adam moments, losses, gradient
 norms and running statistics.  Prints one line per item; exit code 1 on any difference."""
@@ -30,7 +32,16 @@ dev = torch.device("cuda", 0)
 lib = _lib.load()
 out = {}
 torch.manual_seed(0)
-model = GNNNetwork().to(dev).eval()
+def with_biases(m, scale=1.0):
+    # PyG initialises the GCN biases to zero: non-zero ones, so that the trunk's per-degree bias rows matter; `scale` on the trunk's
+    # weights takes the set out of the static fp16 bound (the tracking builds serve it)
+    sd = m.state_dict()
+    for l in range(3):
+        sd[f"gcn_layers.{l}.bias"] = torch.linspace(-0.3, 0.5, 128) * (1 + l)
+        sd[f"gcn_layers.{l}.lin.weight"] = sd[f"gcn_layers.{l}.lin.weight"] * scale
+    m.load_state_dict(sd)
+    return m
+model = with_biases(GNNNetwork()).to(dev).eval()
 pk = model.packed_weights(dev)
 for B in (300, 4096, 1001):
     st = synth_states(B, seed=B, dev=dev)
@@ -44,6 +55,23 @@ eng = BatchedSelfPlay(model, num_games=64, sims=24, seed=11)
 eng.play_generation()
 s, v, z = eng.history_tensors()
 out["hist_s"], out["hist_v"], out["hist_z"] = s.cpu().numpy(), v.cpu().numpy(), z.cpu().numpy()
+# the evaluation launch's tracking build (a 64-game generation of a weight set outside the static bound), and the compact-list builds of
+# both guard modes (640 games with the evaluation cache on, three moves)
+x3 = with_biases(GNNNetwork(), 3.0).to(dev).eval()
+assert model.gnn_flags(dev) == _lib.GNN_RANGE_PROVEN and x3.gnn_flags(dev) == 0
+eng = BatchedSelfPlay(x3, num_games=64, sims=24, seed=11)
+eng.play_generation()
+assert eng.e.gnn_flags == 0
+s, v, z = eng.history_tensors()
+out["x3_hist_s"], out["x3_hist_v"], out["x3_hist_z"] = s.cpu().numpy(), v.cpu().numpy(), z.cpu().numpy()
+for tag, m in (("proven", model), ("x3", x3)):
+    eng = BatchedSelfPlay(m, num_games=640, sims=6, seed=5, eval_cache_slots=256)
+    for _ in range(3):
+        eng.move()
+    assert int(eng.t["eval_count"].sum()) > 0 and eng.e.gnn_flags == m.gnn_flags(dev)
+    out[f"list_{tag}_pooled"], out[f"list_{tag}_count"] = eng.t["pooled"].cpu().numpy(), eng.t["eval_count"].cpu().numpy()
+    s, v, z = eng.history_tensors()
+    out[f"list_{tag}_hist_s"], out[f"list_{tag}_hist_v"] = s.cpu().numpy(), v.cpu().numpy()
 tm = GNNNetwork()
 tm.load_state_dict({k: torch.from_numpy(x.copy()) for k, x in og.init_params(3).items()})
 tm = tm.to(dev)
