@@ -90,6 +90,12 @@ class StartTableStruct(_c.Structure):
     _fields_ = [("states72", _vp), ("index", _vp), ("count", _i32)]
 
 
+class GumbelStruct(_c.Structure):
+    """Mirror of `struct aqg_gumbel` (include/aqgnn.h, "Gumbel root search"): the option beside the engine struct."""
+    _fields_ = [("table", _vp), ("seed", _c.c_uint64), ("scale", _c.c_double), ("considered", _i32), ("c_visit", _f32), ("c_scale", _f32),
+                ("schedule", _vp), ("m", _vp)]
+
+
 # the checker's flag bits (AQG_CHECK_*)
 CHECK_BOARD, CHECK_WALLS, CHECK_WALL_COUNT, CHECK_SAME_SQUARE, CHECK_OVER, CHECK_ODD_PLY, CHECK_NO_PATH = 1, 2, 4, 8, 16, 32, 64
 
@@ -230,6 +236,15 @@ SIGNATURES = {
     "aqg_engine_finish_move_start": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _c.POINTER(TreeReuseStruct),
                                                 _c.POINTER(ResignStruct), _c.POINTER(PolicyRecordStruct), _c.POINTER(StartTableStruct), _vp]),
     "aqg_engine_apply_actions_start": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _c.POINTER(StartTableStruct), _vp]),
+    "aqg_engine_move_gumbel": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _c.POINTER(TreeReuseStruct),
+                                          _c.POINTER(ResignStruct), _c.POINTER(PolicyRecordStruct), _c.POINTER(StartTableStruct),
+                                          _c.POINTER(GumbelStruct), _vp]),
+    "aqg_engine_finish_move_gumbel": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _i32, _vp, _c.POINTER(TreeReuseStruct),
+                                                 _c.POINTER(ResignStruct), _c.POINTER(PolicyRecordStruct), _c.POINTER(StartTableStruct),
+                                                 _c.POINTER(GumbelStruct), _vp]),
+    "aqg_engine_search_gumbel": (_c.c_int, [_c.POINTER(EngineStructGeneral), _vp, _c.POINTER(GumbelStruct), _vp]),
+    "aqg_engine_gumbel_root": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.POINTER(GumbelStruct), _vp]),
+    "aqg_engine_root_gumbel": (_c.c_int, [_c.POINTER(EngineStructGeneral), _c.POINTER(GumbelStruct), _vp, _vp, _vp, _vp]),
     "aqg_agent_random": (_c.c_int, [_c.c_int, _vp, _c.c_int, _vp, _c.c_int, _c.c_uint64, _vp, _vp]),
     "aqg_playouts": (_c.c_int, [_c.c_int, _vp, _c.c_int, _c.c_int, _vp, _c.c_int, _c.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "aqg_agent_mcts_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),

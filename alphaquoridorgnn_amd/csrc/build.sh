@@ -19,7 +19,7 @@ fi
 objs=()
 pids=()
 replaced=0
-for f in legal_mask state_check board_featuriser gcn_pack gcn_trunk_split gcn_trunk_exact gcn_boards_plain gcn_forward gcn_general gcn_boards_general gcn_train gcn_train_exact gcn_train_split gcn_train_final gcn_train_general grad_norm weight_average cnn_forward cnn_train mcts mcts_step mcts_eval mcts_move mcts_reuse mcts_improve mcts_record agents augment replay replay_refresh replay_merge replay_surprise row_metrics value_targets capi; do
+for f in legal_mask state_check board_featuriser gcn_pack gcn_trunk_split gcn_trunk_exact gcn_boards_plain gcn_forward gcn_general gcn_boards_general gcn_train gcn_train_exact gcn_train_split gcn_train_final gcn_train_general grad_norm weight_average cnn_forward cnn_train mcts mcts_step mcts_eval mcts_move mcts_gumbel mcts_reuse mcts_improve mcts_record agents augment replay replay_refresh replay_merge replay_surprise row_metrics value_targets capi; do
   src=$f.hip
   for pair in ${AQG_REPLACE:-}; do
     if [ "${pair%%=*}" = "$f" ]; then src=${pair#*=}; replaced=$((replaced + 1)); fi
@@ -64,6 +64,12 @@ awk '/Function Name:/ { k = ($0 ~ /engine_step_fast_kernelILi9ELb[01]ELb1E/) ? $
      k != "" && / VGPRs: / { n++; v = $0; sub(/.* VGPRs: /, "", v); if (v + 0 > 128) { print "build.sh: over 128 VGPRs: " k > "/dev/stderr"; bad = 1 } }
      k != "" && /ScratchSize/ { v = $0; sub(/.*: /, "", v); if (v + 0 != 0) { print "build.sh: scratch in use: " k > "/dev/stderr"; bad = 1 } }
      END { if (n != 4) { print "build.sh: expected four fused step kernels in the resource remarks, found " n + 0 > "/dev/stderr"; bad = 1 } exit bad }' \
+  "${OBJDIR}/aqg_mcts_step.remarks" || exit 1
+# The Gumbel instantiations of the plain step kernel (engine_step_fast_kernel<N, CACHE, false, false, false, GumbelStep>, four boards with and
+# without the evaluation cache): the score of rule 3 adds three logits, three q and a wave maximum to level 0's registers -- no scratch.
+awk '/Function Name:/ { k = ($0 ~ /engine_step_fast_kernelILi[3579]ELb[01]ELb0ELb0ELb0EJNS_10GumbelStepE/) ? $0 : "" }
+     k != "" && /ScratchSize/ { n++; v = $0; sub(/.*: /, "", v); if (v + 0 != 0) { print "build.sh: scratch in use: " k > "/dev/stderr"; bad = 1 } }
+     END { if (n != 8) { print "build.sh: expected eight Gumbel step kernels in the resource remarks, found " n + 0 > "/dev/stderr"; bad = 1 } exit bad }' \
   "${OBJDIR}/aqg_mcts_step.remarks" || exit 1
 # The same budget for the evaluation launch (engine_eval_kernel<TRACK>, mcts_eval.hip): its board workgroups are the trunk's, two per CU.
 awk '/Function Name:/ { k = ($0 ~ /engine_eval_kernelILi[02]E/) ? $0 : "" }

@@ -418,6 +418,36 @@ int aqg_engine_apply_actions_start(const aqg_engine* e, const int32_t* actions, 
     return engine_apply_actions(*e, actions, (hipStream_t)stream, start);
 }
 
+// Gumbel root search (include/aqgnn.h, "Gumbel root search"): no uniform is read, so `uniforms` may be NULL
+int aqg_engine_move_gumbel(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                           const aqg_tree_reuse* reuse, const aqg_resign* resign, const aqg_policy_record* policy,
+                           const aqg_start_table* start, const aqg_gumbel* gumbel, void* stream) {
+    if (!e || !gumbel) return fail("aqg_engine_move_gumbel: null argument");
+    MoveOptions o{temperature_plies, hist_value, reuse, resign, policy, start};
+    o.gumbel = gumbel;
+    return engine_move(*e, uniforms, o, (hipStream_t)stream);
+}
+int aqg_engine_finish_move_gumbel(const aqg_engine* e, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                                  const aqg_tree_reuse* reuse, const aqg_resign* resign, const aqg_policy_record* policy,
+                                  const aqg_start_table* start, const aqg_gumbel* gumbel, void* stream) {
+    if (!e || !gumbel) return fail("aqg_engine_finish_move_gumbel: null argument");
+    MoveOptions o{temperature_plies, hist_value, reuse, resign, policy, start};
+    o.gumbel = gumbel;
+    return engine_finish_move(*e, uniforms, o, (hipStream_t)stream);
+}
+int aqg_engine_search_gumbel(const aqg_engine* e, const uint8_t* root_states72, const aqg_gumbel* gumbel, void* stream) {
+    if (!e || !root_states72 || !gumbel) return fail("aqg_engine_search_gumbel: null argument");
+    return engine_search_gumbel(*e, root_states72, *gumbel, (hipStream_t)stream);
+}
+int aqg_engine_gumbel_root(const aqg_engine* e, const aqg_gumbel* gumbel, void* stream) {
+    if (!e || !gumbel) return fail("aqg_engine_gumbel_root: null argument");
+    return engine_gumbel_root(*e, *gumbel, (hipStream_t)stream);
+}
+int aqg_engine_root_gumbel(const aqg_engine* e, const aqg_gumbel* gumbel, float* gl, int32_t* m, int32_t* winner, void* stream) {
+    if (!e || !gumbel || !gl || !m || !winner) return fail("aqg_engine_root_gumbel: null argument");
+    return engine_root_gumbel(*e, *gumbel, gl, m, winner, (hipStream_t)stream);
+}
+
 static int check_draw_source(const char* what, const double* uniforms, int uniforms_stride) {
     if (uniforms && uniforms_stride < 0) return fail(what, "negative uniforms_stride");
     return 0;

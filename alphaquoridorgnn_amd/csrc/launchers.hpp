@@ -105,6 +105,16 @@ struct MoveOptions {
     const aqg_resign* resign;
     const aqg_policy_record* policy = nullptr;
     const aqg_start_table* start = nullptr;      // the refill behind the move starts its games from the table (aqgnn.h, "start positions")
+    const aqg_gumbel* gumbel = nullptr;          // the root is searched by sequential halving over Gumbel top-m actions (aqgnn.h, "Gumbel root search")
+};
+// what a selecting step launch of a Gumbel search is handed beside the engine struct (aqgnn.h, "Gumbel root search"): the schedule
+// table T[0 .. considered][0 .. stride), the per-slot words m_g, the f32 constants of the score and `sim`, the simulation the launch
+// selects for (1 .. sims - 1: the root's children are then scored against T[m_g][sim - 1])
+struct GumbelStep {
+    const int32_t* schedule;
+    int32_t* m;
+    float c_visit, c_scale;
+    int32_t considered, stride, sim;
 };
 int engine_reset(const aqg_engine& e, hipStream_t st, const aqg_start_table* start = nullptr);
 int validate_start_table(const aqg_engine& e, const aqg_start_table* start, const char* what);
@@ -126,12 +136,15 @@ int engine_record_improved_policy(const aqg_engine& e, const aqg_policy_record& 
 int engine_keep_subtrees(const aqg_engine& e, const aqg_tree_reuse& ru, const int32_t* child_index, hipStream_t st);
 int engine_reset_reuse(const aqg_engine& e, const aqg_tree_reuse& ru, hipStream_t st);
 int engine_reset_resign(const aqg_engine& e, const aqg_resign& rs, hipStream_t st);
+int engine_search_gumbel(const aqg_engine& e, const uint8_t* roots72, const aqg_gumbel& gb, hipStream_t st);
+int engine_gumbel_root(const aqg_engine& e, const aqg_gumbel& gb, hipStream_t st);
+int engine_root_gumbel(const aqg_engine& e, const aqg_gumbel& gb, float* gl, int32_t* m, int32_t* winner, hipStream_t st);
 
 // ---- mcts_step.hip  (launchers of the engine's kernels only enqueue: the entry point checks the launch)
 extern int g_step_waves, g_step_prio, g_step_fast_depth, g_step_heads;
 int set_trace_mcts(void* buf, unsigned int cap);
 int launch_engine_step(const aqg_engine& e, int do_expand, int do_select, hipStream_t st, int list_sim, bool heads, bool defer_legal = false,
-                       bool policy_beside = false);
+                       bool policy_beside = false, const GumbelStep* gumbel = nullptr);
 
 // ---- mcts_eval.hip
 extern int g_legal_beside_trunk, g_policy_beside_step;
@@ -161,6 +174,11 @@ void launch_engine_root_improved_policy(const aqg_engine& e, double c_visit, dou
 
 // ---- mcts_record.hip
 int launch_engine_record_improved_policy(const aqg_engine& e, const aqg_policy_record& pr, hipStream_t st);
+
+// ---- mcts_gumbel.hip
+void launch_engine_gumbel_root(const aqg_engine& e, const aqg_gumbel& gb, hipStream_t st);
+int launch_engine_finish_move_gumbel(const aqg_engine& e, const MoveOptions& opts, hipStream_t st);
+void launch_engine_root_gumbel(const aqg_engine& e, const aqg_gumbel& gb, float* gl, int32_t* m, int32_t* winner, hipStream_t st);
 
 // ---- mcts_reuse.hip
 void launch_engine_keep_subtrees(const aqg_engine& e, const aqg_tree_reuse& ru, const int32_t* child_index, hipStream_t st);

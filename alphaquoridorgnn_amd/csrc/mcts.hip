@@ -26,6 +26,9 @@
 //   mcts_move.hip   once per move or once per engine: reset, set_roots, begin_move, the `fake` evaluator, root noise, finish_move and
 //                   apply_actions (one engine_transition behind both), refill, root_visits / root_priors / root_states72; one plain
 //                   launcher per kernel.
+//   mcts_gumbel.hip the Gumbel root search outside the step kernel: engine_gumbel_root_kernel (Gumbel logits into the root's children, m_g),
+//                   engine_finish_move_gumbel_kernel (the survivor is played), engine_root_gumbel_kernel (read-out); the shared score is
+//                   mcts_gumbel_row.hpp's, which the step kernel's GUMBEL instantiations evaluate at level 0.
 //   mcts_reuse.hip  tree reuse: engine_keep_subtrees_kernel, the in-place re-rooting of a pool at the chosen child, and its launcher.
 //   mcts_improve.hip  the completed-Q improved policy of the roots: engine_root_improved_policy_kernel, a read-out of the pool in
 //                   float64 (aqgnn.h, "completed-Q policy targets"), and its launcher.  It changes nothing the search reads.
@@ -136,10 +139,29 @@ int validate_start_table(const aqg_engine& e, const aqg_start_table* start, cons
     return 0;
 }
 
+// what the Gumbel entry points refuse, before anything is launched and in this order (aqgnn.h, "Gumbel root search")
+static int validate_gumbel(const aqg_engine& e, const MoveOptions& o) {
+    const aqg_gumbel& gb = *o.gumbel;
+    if (e.sims < 2) return fail("Gumbel root search: sims must be >= 2 (simulation 0 evaluates the root)");
+    if (gb.considered < 1 || gb.considered > 64) return fail("Gumbel root search: considered must be in 1..64");
+    if (!(gb.scale >= 0.0) || std::isinf(gb.scale)) return fail("Gumbel root search: scale must be finite and >= 0");      // NaN fails the first
+    if (e.root_noise_eps > 0.f) return fail("Gumbel root search: not with root noise (the Gumbel variates are the exploration)");
+    if (o.reuse) return fail("Gumbel root search: not with tree reuse (a kept root's children hold no Gumbel logits)");
+    if (o.resign) return fail("Gumbel root search: not with resignation");
+    if (o.temperature_plies > 0) return fail("Gumbel root search: not with temperature_plies (the move is the survivor, no temperature is read)");
+    if (e.prior_mode == 2) return fail("Gumbel root search: not with prior_mode 2 (the external evaluator)");
+    if (!(gb.c_visit >= 0.f) || std::isinf(gb.c_visit)) return fail("Gumbel root search: c_visit must be finite and >= 0");
+    if (!(gb.c_scale >= 0.f) || std::isinf(gb.c_scale)) return fail("Gumbel root search: c_scale must be finite and >= 0");
+    if (!gb.schedule || !gb.m) return fail("Gumbel root search: schedule and m are required");
+    return 0;
+}
+
 // Everything a move refuses, before anything is launched.  The order is part of the interface -- the first failing check names the
-// error: the engine, the two targets, tree reuse if it is on, resignation if it is on, the policy record if it is on.
+// error: the engine, the Gumbel root search if it is on, the two targets, tree reuse if it is on, resignation if it is on, the
+// policy record if it is on.
 static int validate_move(const aqg_engine& e, const MoveOptions& o) {
     if (int r = validate(e)) return r;
+    if (o.gumbel) if (int r = validate_gumbel(e, o)) return r;
     if (o.temperature_plies < 0) return fail("temperature_plies must be >= 0");
     if (o.hist_value && e.max_plies <= 0) return fail("hist_value needs a history (max_plies > 0)");
     if (o.reuse) if (int r = validate_reuse(e, *o.reuse)) return r;
@@ -153,7 +175,10 @@ static int validate_move(const aqg_engine& e, const MoveOptions& o) {
 // children in front of simulation 0's step, and the step launches get `es`, the struct with sims = keep_visits + sims: the stride of
 // e.path and the bound of the path lanes, which is all the step kernel reads `sims` for.  Every other reader of `sims` -- begin_move's
 // eval_count, this loop, list_sim -- sees the real count.
-static int enqueue_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reuse* reuse = nullptr) {
+// `gumbel` != nullptr (Gumbel root search, aqgnn.h): the three-launch simulation form around the root launch -- step(0, 1), evaluate;
+// step(1, 0), the root's expansion and backup in memory; the root launch; then per simulation step<GUMBEL>, evaluate; the last
+// expansion.  Two launches more per move than the three-launch PUCT form; no step_heads, no legal_beside_trunk, no policy_beside_step.
+static int enqueue_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reuse* reuse = nullptr, const aqg_gumbel* gumbel = nullptr) {
     if (e.prior_mode == 2) return fail("prior_mode 2 (external evaluator): drive the move with aqg_engine_begin_move / _step / _finish_move");
     const int N = e.board_size;
     aqg_engine es = e;
@@ -165,7 +190,7 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reus
     // heads inside the step (option "step_heads"): the 9x9 split network with eight games per step workgroup -- the NEXT step launch
     // computes policy and value of this simulation's leaves from the pooled rows, so the simulation is two launches, step -> trunk.
     // Everything else keeps the heads launch: other boards and evaluators, step_waves != 8, the exact kernels behind a range-guard report.
-    const bool step_heads = g_step_heads && e.prior_mode == 0 && N == 9 && g_trunk_variant >= 3 && !(e.gnn_flags & AQG_GNN_EXACT_F32) && g_step_waves == 8;
+    const bool step_heads = !gumbel && g_step_heads && e.prior_mode == 0 && N == 9 && g_trunk_variant >= 3 && !(e.gnn_flags & AQG_GNN_EXACT_F32) && g_step_waves == 8;
     // legal moves beside the trunk (option "legal_beside_trunk"; cache off): such a step ends on its leaf, and the evaluation launch behind
     // it carries the leaves' legal-move searches in front of the trunk's board workgroups (mcts_eval.hip) -- still two launches, one chain.
     // Simulation 0's step does not expand, so it is not the form with the heads inside: it searches itself and the plain trunk follows.
@@ -174,9 +199,8 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reus
     // the step launch behind it -- simulations 2 .. sims - 1 and the last expansion -- expands them in policy workgroups beside its step
     // workgroups.  Simulation 1's step follows the plain trunk and searched its leaf (the root) itself: no job, today's form.
     const bool policy_beside = engine_policy_beside_step(e, defer_legal);
-    for (int sim = 0; sim < e.sims; ++sim) {
-        const bool defer = defer_legal && sim > 0;
-        if (int r = launch_engine_step(es, sim > 0 ? 1 : 0, 1, st, use_list ? sim : -1, step_heads, defer, policy_beside && sim > 1)) return r;
+    // the evaluation of simulation `sim`'s leaves, behind its step launch
+    auto evaluate = [&](int sim, bool defer) -> int {
         if (defer) {
             if (int r = launch_engine_eval(e, st, policy_beside)) return r;
         } else if (e.prior_mode == 0) {
@@ -210,6 +234,26 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reus
         } else {
             if (int r = launch_engine_fake_eval(e, st)) return r;
         }
+        return 0;
+    };
+    if (gumbel) {
+        GumbelStep gs{gumbel->schedule, gumbel->m, gumbel->c_visit, gumbel->c_scale, gumbel->considered, e.sims - 1, 0};
+        if (int r = launch_engine_step(es, 0, 1, st, use_list ? 0 : -1, false)) return r;
+        if (int r = evaluate(0, false)) return r;
+        if (int r = launch_engine_step(es, 1, 0, st, -1, false)) return r;           // the root's expansion and backup, in memory
+        launch_engine_gumbel_root(e, *gumbel, st);
+        for (int sim = 1; sim < e.sims; ++sim) {
+            gs.sim = sim;
+            if (int r = launch_engine_step(es, sim > 1 ? 1 : 0, 1, st, use_list ? sim : -1, false, false, false, &gs)) return r;
+            if (int r = evaluate(sim, false)) return r;
+        }
+        if (int r = launch_engine_step(es, 1, 0, st, -1, false)) return r;
+        return check_launch("engine simulation kernels");
+    }
+    for (int sim = 0; sim < e.sims; ++sim) {
+        const bool defer = defer_legal && sim > 0;
+        if (int r = launch_engine_step(es, sim > 0 ? 1 : 0, 1, st, use_list ? sim : -1, step_heads, defer, policy_beside && sim > 1)) return r;
+        if (int r = evaluate(sim, defer)) return r;
         if (sim == 0 && e.root_noise_eps > 0.f)                                    // the root's priors, before simulation 1 expands it
             if (int r = launch_engine_root_noise(e, st)) return r;
     }
@@ -217,7 +261,8 @@ static int enqueue_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reus
     return check_launch("engine simulation kernels");
 }
 
-// One move's search is 3 * sims + 2 launches (2 * sims + 3 with the heads inside the step; one more with root noise on, and with tree reuse a second one for the kept roots) with constant arguments: on a capturable (non-default) stream it is
+// One move's search is 3 * sims + 2 launches (2 * sims + 3 with the heads inside the step; one more with root noise on, and with tree reuse a second one for the kept roots;
+// 3 * sims + 4 with the Gumbel root search: the three-launch form, the root's own step(1, 0) and the root launch) with constant arguments: on a capturable (non-default) stream it is
 // captured once into a hipGraph and replayed per move, so the host cost per move is one graph launch instead of ~600
 // kernel launches (with several game sets on several streams the host is otherwise the bottleneck).  The cache key is
 // the engine struct itself plus the trunk options the launches read.
@@ -228,6 +273,8 @@ struct SimGraph {
     int opts[7];
     const uint8_t* kept;      // tree reuse: the two arguments its captured launches bake in (nullptr, 0 = a plain move)
     int keep_visits;
+    bool has_gumbel;          // Gumbel root search: the struct its captured launches bake in, field by field (padding is not compared)
+    aqg_gumbel gumbel;
     hipGraphExec_t exec;
     hipEvent_t last;          // recorded behind every replay: eviction waits for THIS graph's last replay, not for the device
 };
@@ -240,19 +287,27 @@ static int replay(SimGraph& g, hipStream_t st) {
     return 0;
 }
 
-static int run_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reuse* reuse = nullptr) {
-    if (!g_use_graph || g_profile_trunk || st == nullptr || e.sims < 4) return enqueue_sims(e, st, reuse);
+static bool same_gumbel(const SimGraph& g, const aqg_gumbel* gb) {
+    if (g.has_gumbel != (gb != nullptr)) return false;
+    if (!gb) return true;
+    const aqg_gumbel& a = g.gumbel;
+    return a.table == gb->table && a.seed == gb->seed && !memcmp(&a.scale, &gb->scale, sizeof(double)) && a.considered == gb->considered &&
+           !memcmp(&a.c_visit, &gb->c_visit, sizeof(float)) && !memcmp(&a.c_scale, &gb->c_scale, sizeof(float)) && a.schedule == gb->schedule && a.m == gb->m;
+}
+
+static int run_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reuse* reuse = nullptr, const aqg_gumbel* gumbel = nullptr) {
+    if (!g_use_graph || g_profile_trunk || st == nullptr || e.sims < 4) return enqueue_sims(e, st, reuse, gumbel);
     const uint8_t* kept = reuse ? reuse->kept : nullptr;
     const int keep_visits = reuse ? reuse->keep_visits : 0;
     // every option a captured launch bakes in is part of the key: a changed option must never replay a stale graph
     const int opts[7] = {g_trunk_variant, g_trunk_grid, g_trunk_phase_delay, g_trunk_delay_min_boards, e.board_size, g_step_fast_depth, ((g_trunk_prio & 0xff) << 8) | (g_step_waves << 16) | (g_step_prio << 24) | (g_heads_prio << 28) | (g_step_heads & 1) | ((g_legal_beside_trunk & 1) << 1) | ((g_policy_beside_step & 1) << 2)};
     for (SimGraph& g : g_sim_graphs)
-        if (!memcmp(&g.e, &e, sizeof(aqg_engine)) && !memcmp(g.opts, opts, sizeof(opts)) && g.kept == kept && g.keep_visits == keep_visits) return replay(g, st);
+        if (!memcmp(&g.e, &e, sizeof(aqg_engine)) && !memcmp(g.opts, opts, sizeof(opts)) && g.kept == kept && g.keep_visits == keep_visits && same_gumbel(g, gumbel)) return replay(g, st);
     if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
         (void)hipGetLastError();
-        return enqueue_sims(e, st, reuse);                   // stream not capturable: plain launches
+        return enqueue_sims(e, st, reuse, gumbel);           // stream not capturable: plain launches
     }
-    const int r = enqueue_sims(e, st, reuse);
+    const int r = enqueue_sims(e, st, reuse, gumbel);
     hipGraph_t graph = nullptr;
     const hipError_t ec = hipStreamEndCapture(st, &graph);
     if (r) { if (graph) (void)hipGraphDestroy(graph); return r; }
@@ -261,6 +316,8 @@ static int run_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reuse* r
     memcpy(&g.e, &e, sizeof(aqg_engine));
     memcpy(g.opts, opts, sizeof(opts));
     g.kept = kept; g.keep_visits = keep_visits;
+    g.has_gumbel = gumbel != nullptr;
+    g.gumbel = gumbel ? *gumbel : aqg_gumbel{};
     const hipError_t ei = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (ei != hipSuccess) return fail("hipGraphInstantiate");
@@ -284,7 +341,8 @@ static int run_sims(const aqg_engine& e, hipStream_t st, const aqg_tree_reuse* r
 // (policy record: one launch in front of the finish-move launch, which still sees the slot active and its ply unchanged)
 static int finish_and_refill(const aqg_engine& e, const double* uniforms, const MoveOptions& o, hipStream_t st) {
     if (o.policy) if (int r = launch_engine_record_improved_policy(e, *o.policy, st)) return r;
-    if (int r = launch_engine_finish_move(e, uniforms, o, st)) return r;
+    if (o.gumbel) { if (int r = launch_engine_finish_move_gumbel(e, o, st)) return r; }      // (rule 4: no uniform is read)
+    else if (int r = launch_engine_finish_move(e, uniforms, o, st)) return r;
     if (o.reuse) launch_engine_keep_subtrees(e, *o.reuse, o.reuse->child_index, st);
     if (e.quota > e.num_games) launch_engine_refill(e, st, o.start);
     return check_launch("engine_finish_move_kernel");
@@ -329,7 +387,7 @@ int engine_reset(const aqg_engine& e, hipStream_t st, const aqg_start_table* sta
 
 int engine_move(const aqg_engine& e, const double* uniforms, const MoveOptions& o, hipStream_t st) {
     if (int r = validate_move(e, o)) return r;
-    if (int r = run_sims(e, st, o.reuse)) return r;
+    if (int r = run_sims(e, st, o.reuse, o.gumbel)) return r;
     return finish_and_refill(e, uniforms, o, st);
 }
 
@@ -365,6 +423,33 @@ int engine_search(const aqg_engine& e, const uint8_t* roots72, hipStream_t st) {
     if (int r = validate(e)) return r;
     launch_engine_set_roots(e, roots72, st);
     return run_sims(e, st);
+}
+
+// the Gumbel root search without a move (aqgnn.h, "Gumbel root search"): the search of caller-given roots, the root launch alone and
+// the read-out.  Each refuses what a move with the option refuses.
+static int validate_gumbel_alone(const aqg_engine& e, const aqg_gumbel& gb) {
+    if (int r = validate(e)) return r;
+    MoveOptions o{};
+    o.gumbel = &gb;
+    return validate_gumbel(e, o);
+}
+
+int engine_search_gumbel(const aqg_engine& e, const uint8_t* roots72, const aqg_gumbel& gb, hipStream_t st) {
+    if (int r = validate_gumbel_alone(e, gb)) return r;
+    launch_engine_set_roots(e, roots72, st);
+    return run_sims(e, st, nullptr, &gb);
+}
+
+int engine_gumbel_root(const aqg_engine& e, const aqg_gumbel& gb, hipStream_t st) {
+    if (int r = validate_gumbel_alone(e, gb)) return r;
+    launch_engine_gumbel_root(e, gb, st);
+    return check_launch("engine_gumbel_root_kernel");
+}
+
+int engine_root_gumbel(const aqg_engine& e, const aqg_gumbel& gb, float* gl, int32_t* m, int32_t* winner, hipStream_t st) {
+    if (int r = validate_gumbel_alone(e, gb)) return r;
+    launch_engine_root_gumbel(e, gb, gl, m, winner, st);
+    return check_launch("engine_root_gumbel_kernel");
 }
 
 // the noise launch alone: behind the caller's own evaluation of simulation 0 (prior_mode 2), and for tests

@@ -12,6 +12,8 @@
 // PUCT scores must be evaluated exactly as written (no fma contraction, IEEE divide/sqrt).
 #pragma clang fp contract(off)
 #include "mcts_tree.hpp"
+#include "mcts_gumbel_row.hpp"
+#include <type_traits>
 
 namespace aqg {
 
@@ -201,10 +203,19 @@ __device__ __forceinline__ void step_round1(const aqg_engine& e, int g, int lane
 // workgroups, memory ends as the one-workgroup form leaves it.  No value the step uses is loaded from those records: past the
 // hand-over to memory, too, the old leaf is recognised by its node index and its first child taken without a look at the records.
 // A leaf_flag 2 leaf (never seen behind an evaluation launch) has no job and is expanded here as ever.
-template <int N, bool CACHE, bool HEADS, bool DEFER = false, bool PB = false>
+// GUMBEL (the plain forms only; aqgnn.h, "Gumbel root search"): level 0 scores the root's children by rule 3 -- gl_i travels in their
+// `cp` word, m_g and the lanes' schedule entries came with round 1 (GumbelRound1) -- and every other level is PUCT as ever.  The
+// pending backup's patched neff / pqv are used exactly as PUCT uses them; nmax is one more wave maximum over neff.
+struct GumbelRound1 {
+    int m, vrow;                 // the slot's m_g; T[min(lane + 1, considered)][sim - 1]: row m' >= 1 sits in lane m' - 1
+    float c_visit, c_scale;
+    int32_t* mword;              // the slot's word (written only by the branch that cannot occur)
+};
+template <int N, bool CACHE, bool HEADS, bool DEFER = false, bool PB = false, bool GUMBEL = false>
 __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int lane, int do_expand, int do_select, int fast_depth,
                                                float* __restrict__ polbuf /* this wave's 256 floats of LDS */, int list_sim,
-                                               const StepRound1& r1, float head_value) {
+                                               const StepRound1& r1, float head_value, const GumbelRound1& gz = GumbelRound1{}) {
+    static_assert(!GUMBEL || (!HEADS && !DEFER && !PB), "Gumbel root search: the plain forms only");
     constexpr int A = Geo<N>::A;
     NodeRec* __restrict__ nodes = game_nodes(e, g);
     int* path = e.path + (size_t)g * (e.sims + 2);
@@ -399,7 +410,7 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
     // One level's selection (pv_mcts.py:69-78) from the children's records `hot` / `cold`; results in the scalars below.  The records
     // are never modified in registers: the pending backup's patch goes into temporaries.
     uint32_t kids_n = 0u; int action = 0, cn = 0, besti = 0; double cw = 0.0;
-    auto select_level = [&](const u32x4 (&hot)[3], const u32x4 (&cold)[3]) {
+    auto select_level = [&](const u32x4 (&hot)[3], const u32x4 (&cold)[3], auto root_level) {
         const int cnt = (int)(kids >> 24), first = (int)(kids & 0xFFFFFF);
         // the old path's child of this node: its index among these children, and its exploitation term after the pending backup --
         // lane depth + 1 computed it from that node's own record (one division per step, started before the descent); at the root
@@ -442,7 +453,32 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
             const float u = (__builtin_bit_cast(float, cb) * st) / (float)(1 + neff[r]);
             sc[r] = (lane + 64 * r < cnt) ? q + u : -INFINITY;
         };
-        if (cnt <= 64) {
+        if constexpr (GUMBEL && decltype(root_level)::value) {
+            // rule 3 of aqgnn.h: v = T[m_g][sim - 1] by v_readlane from the row the lanes loaded in round 1 (no dependent load);
+            // the statistics first, then nmax over the node's children, then the scores
+            const int mg = __builtin_amdgcn_readfirstlane(gz.m);
+            const int v = __builtin_amdgcn_readlane(gz.vrow, (max(mg, 1) - 1) & 63);
+            float gl[3], qe[3];
+            auto stat = [&](int r) {
+                const uint32_t nb = hot[r][0], kb = hot[r][1], qb = hot[r][2], cb = hot[r][3];
+                const bool me = patch && (lane + 64 * r == pidx);
+                neff[r] = (int)nb + (me ? 1 : 0);
+                keff[r] = (me && leafnext) ? kids_new : kb;
+                qe[r] = me ? pqv : __builtin_bit_cast(float, qb);
+                gl[r] = __builtin_bit_cast(float, cb);
+            };
+            const int rounds = cnt <= 64 ? 1 : 3;
+            float nm = 0.f;                                     // (n < 2^24: exact in f32, and rule 3 wants float(nmax))
+            stat(0);
+            if (rounds == 3) { stat(1); stat(2); }
+            else { neff[1] = neff[2] = 0; keff[1] = keff[2] = 0u; gl[1] = gl[2] = -INFINITY; qe[1] = qe[2] = 0.f; }
+#pragma unroll
+            for (int r = 0; r < 3; ++r) if (r < rounds && lane + 64 * r < cnt) nm = fmaxf(nm, (float)neff[r]);
+            const float nmaxf = wave_max_dpp_asm(nm);
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+                sc[r] = (r < rounds && lane + 64 * r < cnt) ? gumbel_root_score(gl[r], neff[r], qe[r], nmaxf, gz.c_visit, gz.c_scale, v) : -INFINITY;
+        } else if (cnt <= 64) {
             score(0);
             sc[1] = sc[2] = -INFINITY; neff[1] = neff[2] = 0; keff[1] = keff[2] = 0u;
         } else {
@@ -514,7 +550,7 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
                 cold[r] = nhalf[2 * i]; hot[r] = nhalf[2 * i + 1];
             }
         }
-        select_level(hot, cold);          // level 0: the root's children came with round 1
+        select_level(hot, cold, std::bool_constant<GUMBEL>{});          // level 0: the root's children came with round 1
 #ifdef AQG_STAMP_LEVELS
         lv_prev = __builtin_readcyclecounter();
 #endif
@@ -561,13 +597,24 @@ __device__ __forceinline__ void game_step_fast(const aqg_engine& e, int g, int l
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             LEVEL_STAMP(9)                                   // ... -> children arrived (what is left of the load latency)
 #endif
-            select_level(h, c);
+            select_level(h, c, std::false_type{});
 #ifdef AQG_STAMP_LEVELS
             LEVEL_STAMP(10)                                  // ... -> child chosen (scores, arg-max, the winner's fields)
 #endif
         }
     }
     at_old_leaf = stop == 3;
+    if (GUMBEL && at_old_leaf && depth == 0) {
+        // The root is the pending leaf: its children were written by this very launch and carry no Gumbel logits yet (their cp is
+        // c_puct * p).  enqueue_sims never launches this form in front of the root launch; if somebody does, the simulation is
+        // dropped and the slot's word says so (-1, aqg_engine_root_gumbel shows it; it stays -1 for the rest of the search)
+        // instead of child 0 being taken without a word.  The early return leaves path[] and path_len unwritten with
+        // leaf_flag = 0, and the next expanding step relies on exactly that: it reads leaf_flag first and, finding 0, neither
+        // expands nor backs up, so the stale path is never followed.
+        flush_old();
+        if (lane == 0) gz.mword[g] = -1;
+        return;
+    }
     if (at_old_leaf) {
         // The descent has followed the old path down to the old leaf, whose children are the records built above (n = 0, q = 0).  Their
         // visit counts sum to t = 0, so every score is 0 + (cp * 0) / 1 = 0 (or NaN for a NaN prior: never the maximum) and np.argmax
@@ -795,9 +842,14 @@ __device__ __forceinline__ void policy_beside_role(const aqg_engine& e, int blk,
 // layer, the softmax with its barriers, the gather and the child records to workgroups [gridDim.x / 2, gridDim.x), one per eight games
 // in the same grouping (policy_beside_role): nothing of that is on the way to the next leaf.  The step workgroups come first, so that
 // they start at once.
-template <int N, bool CACHE, bool HEADS, bool DEFER = false, bool PB = false>
-__global__ __launch_bounds__(512, HEADS ? 4 : 1) void engine_step_fast_kernel(aqg_engine e, int do_expand, int do_select, int fast_depth, int list_sim) {
+// GUMBEL (aqgnn.h, "Gumbel root search"; <N, CACHE, false, false, false, GumbelStep>, the plain forms only): the launch takes the GumbelStep
+// as one more argument -- the other instantiations have none, they are the kernels as they were -- and game_step_fast scores level 0 by
+// rule 3.  The two words it adds to round 1 (m_g, the lane's schedule entry) have addresses that follow from (game, lane) alone.
+template <int N, bool CACHE, bool HEADS, bool DEFER = false, bool PB = false, class... Gumbel>
+__global__ __launch_bounds__(512, HEADS ? 4 : 1) void engine_step_fast_kernel(aqg_engine e, int do_expand, int do_select, int fast_depth, int list_sim,
+                                                                              Gumbel... gumbel) {
     static_assert(!PB || (HEADS && !CACHE), "policy workgroups: the cache-less form with the heads inside");
+    static_assert(sizeof...(Gumbel) == 0 || (sizeof...(Gumbel) == 1 && !HEADS && !DEFER && !PB), "Gumbel root search: the plain forms only");
     __shared__ float polbuf[8][256];
     AQG_TRACE_BEGIN
     const int lane = threadIdx.x & 63;
@@ -834,7 +886,15 @@ __global__ __launch_bounds__(512, HEADS ? 4 : 1) void engine_step_fast_kernel(aq
         if (g < e.num_games) game_step_fast<N, CACHE, true, DEFER>(e, g, lane, do_expand, do_select, fast_depth, polbuf[wave], list_sim, r1, hval[wave]);
     } else if (g < e.num_games) {
         step_round1<N, CACHE, false>(e, g, lane, do_expand, r1);
-        game_step_fast<N, CACHE, false>(e, g, lane, do_expand, do_select, fast_depth, polbuf[threadIdx.x >> 6], list_sim, r1, 0.f);
+        if constexpr (sizeof...(Gumbel) != 0) {
+            const GumbelStep gs = (gumbel, ...);
+            GumbelRound1 gz;
+            gz.m = gs.m[g];
+            gz.vrow = gs.schedule[(size_t)min(lane + 1, gs.considered) * gs.stride + (gs.sim - 1)];
+            gz.c_visit = gs.c_visit; gz.c_scale = gs.c_scale; gz.mword = gs.m;
+            game_step_fast<N, CACHE, false, false, false, true>(e, g, lane, do_expand, do_select, fast_depth, polbuf[threadIdx.x >> 6], list_sim, r1, 0.f, gz);
+        } else
+            game_step_fast<N, CACHE, false>(e, g, lane, do_expand, do_select, fast_depth, polbuf[threadIdx.x >> 6], list_sim, r1, 0.f);
     }
     AQG_TRACE_END(1, (unsigned long long)(uintptr_t)e.pooled)
 }
@@ -847,7 +907,7 @@ AQG_TRACE_SETTER(set_trace_mcts)
 // `policy_beside`: the launch in front was engine_eval_kernel with the expansion jobs (the caller has checked that the form applies): the
 // fused cache-less launch gets its policy workgroups behind the step's.
 int launch_engine_step(const aqg_engine& e_in, int do_expand, int do_select, hipStream_t st, int list_sim, bool heads, bool defer_legal,
-                       bool policy_beside) {
+                       bool policy_beside, const GumbelStep* gumbel) {
     // prior_mode 3 and 4 leave the network's dense [G,A] policy in e.policy exactly like prior_mode 0: the step kernels gather,
     // renormalise and cache it as mode 0 -- they are handed the struct with prior_mode 0, so no step kernel knows mode 3 or 4
     aqg_engine e = e_in;
@@ -861,7 +921,7 @@ int launch_engine_step(const aqg_engine& e_in, int do_expand, int do_select, hip
         constexpr int N = decltype(n)::value;
         if (g_profile_trunk == 2) profile_mark(st, e.num_games);       // measurement mode 2: the event pairs bracket the step launches
         bool fused = false;
-        if constexpr (N == 9) fused = heads && do_expand && wpb == 8 && e.prior_mode == 0;      // (the only board with HEADS instantiations)
+        if constexpr (N == 9) fused = heads && do_expand && wpb == 8 && e.prior_mode == 0 && !gumbel;      // (the only board with HEADS instantiations)
         auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, sg, sb, 0, st, e, do_expand, do_select, fd, list_sim); };
         if constexpr (N == 9) {
             if (fused) {
@@ -872,7 +932,10 @@ int launch_engine_step(const aqg_engine& e_in, int do_expand, int do_select, hip
                 else launch(engine_step_fast_kernel<N, false, true>);
             }
         }
-        if (!fused) { if (cache) launch(engine_step_fast_kernel<N, true, false>); else launch(engine_step_fast_kernel<N, false, false>); }
+        if (gumbel) {                    // (the caller asks for neither `heads` nor the forms beside it: aqgnn.h, "Gumbel root search")
+            if (cache) hipLaunchKernelGGL((engine_step_fast_kernel<N, true, false, false, false, GumbelStep>), sg, sb, 0, st, e, do_expand, do_select, fd, list_sim, *gumbel);
+            else hipLaunchKernelGGL((engine_step_fast_kernel<N, false, false, false, false, GumbelStep>), sg, sb, 0, st, e, do_expand, do_select, fd, list_sim, *gumbel);
+        } else if (!fused) { if (cache) launch(engine_step_fast_kernel<N, true, false>); else launch(engine_step_fast_kernel<N, false, false>); }
         if (g_profile_trunk == 2) profile_mark(st, -1);
         return 0;
     });

@@ -1,5 +1,6 @@
 // mcts_tree.hpp -- what the engine's units (mcts_step.hip, mcts_eval.hip, mcts_move.hip) share: of a game's tree pool the node record,
-// its accessors and the wave sums (wave_ops.hpp); the initial position; a game's state as wave-uniform scalars (uniform_state).  __forceinline__ device code and declarations only.  The including unit
+// its accessors and the wave sums (wave_ops.hpp); the initial position; a game's state as wave-uniform scalars (uniform_state); the one
+// move transition (engine_transition: mcts_move.hip's finish_move / apply_actions and mcts_gumbel.hip's finish launch end in it).  __forceinline__ device code and declarations only.  The including unit
 // sets `#pragma clang fp contract(off)` in front of this header: q_of and the backup are PUCT arithmetic.
 #pragma once
 #include "aqg_common.hpp"
@@ -77,6 +78,42 @@ __device__ __forceinline__ QState uniform_state(const QState& v) {
     s.ppos = (uint8_t)(m & 0xff); s.pwl = (uint8_t)((m >> 8) & 0xff); s.epos = (uint8_t)((m >> 16) & 0xff); s.ewl = (uint8_t)(m >> 24);
     s.plies = (uint16_t)__builtin_amdgcn_readfirstlane((int)v.plies); s.pad = 0;
     return s;
+}
+
+// ------------------------------------------------------------------------------------------------
+// One move of the game in slot g (game k, at ply `ply`, position s), by lane 0 of the slot's wave: what a searched move
+// (engine_finish_move_kernel) and a caller-given one (engine_apply_actions_kernel) have in common, so that matches and
+// self-play record games the same way.  hist_action, next(), plies, lose / draw / z, the counters, game_active.
+// ------------------------------------------------------------------------------------------------
+// `resigned` (aqgnn.h, "resignation"): the mover gives up at s -- the row's action is 0xFF, no move is applied, and s itself is the
+// ended position, lost for its mover.
+template <int N>
+__device__ __forceinline__ void engine_transition(const aqg_engine& e, int g, int k, int ply, const QState& s, int chosen,
+                                                  bool resigned = false) {
+    if (chosen < 0) {
+        // Dead end: legal_actions() is empty.  The reference would re-predict forever-leaf and np.random.choice([])
+        // raises; we abort the game as a draw and count it.
+        e.game_active[g] = 0; e.game_result[k] = 0; e.game_done[k] = 1;
+        atomicAdd(&e.counters[2], 1); atomicAdd(&e.counters[1], 1); atomicSub(&e.counters[0], 1);
+        return;
+    }
+    if (ply < e.max_plies) e.hist_action[(size_t)k * e.max_plies + ply] = resigned ? (uint8_t)0xFF : (uint8_t)chosen;
+    QState t = s;
+    if (!resigned) {
+        t = next_state<N>(s, chosen);
+        store_state(e.root_state, g, t);
+    }
+    e.game_plies[k] = ply + 1;
+    const bool lose = resigned || is_lose<N>(t), draw = !resigned && is_draw(t, e.plies_for_draw);
+    if (lose || draw) {
+        // first_player_value (self_play.py:22-27): ended state's mover lost; z of ply 0, alternating afterwards (:63-66)
+        int z = 0;
+        if (lose) z = ((t.plies % 2) == 0) ? -1 : 1;
+        e.game_result[k] = (int8_t)z;
+        e.game_done[k] = 1;
+        e.game_active[g] = 0;                  // engine_refill_kernel may hand the slot its next game
+        atomicAdd(&e.counters[1], 1); atomicSub(&e.counters[0], 1);
+    }
 }
 
 }  // namespace aqg

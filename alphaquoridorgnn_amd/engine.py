@@ -26,9 +26,10 @@ from .counter_rng import GOLDEN as _GOLDEN, MASK64, mix64 as _mix64_int  # noqa:
 from .device_reference import (NODE_DTYPE, draw_resign_enabled, draw_root_noise, improved_policy_reference,  # noqa: F401
                                keep_subtree_reference, lambda_values_reference, root_improved_policy_reference, root_noise_stream_key)
 from .resign_calibration import resign_false_positives, resign_stats_of, suggest_from_arrays, suggest_resign_threshold  # noqa: F401
-from .selfplay_options import (ROOT_NOISE_ATTEMPTS, check_completed_q, check_policy_record, check_resign, check_root_noise, check_target_options,  # noqa: F401
-                               check_start_table, check_temperature, check_tree_reuse, check_value_lambda, default_resign_seed, default_root_noise_alpha,
-                               default_root_noise_seed, set_noise_seeds, set_start_indices)
+from .gumbel import (considered_visits, draw_gumbel, gumbel_logits_reference, gumbel_winner_reference, root_score_reference)  # noqa: F401
+from .selfplay_options import (ROOT_NOISE_ATTEMPTS, check_completed_q, check_gumbel, check_policy_record, check_resign, check_root_noise, check_target_options,  # noqa: F401
+                               check_start_table, check_temperature, check_tree_reuse, check_value_lambda, default_gumbel_seed, default_resign_seed,
+                               default_root_noise_alpha, default_root_noise_seed, set_noise_seeds, set_start_indices)
 from .two_engine_match import TwoEngineMatch  # noqa: F401
 
 
@@ -37,7 +38,8 @@ class BatchedSelfPlay:
                  c_puct=1.25, evaluator="gnn", fake_bias=0, seed=0, record_history=True, quota=None, eval_cache_slots=None,
                  root_noise_eps=0.0, root_noise_alpha=None, root_noise_seed=None, temperature_plies=0, record_search_value=False,
                  tree_reuse=False, tree_reuse_visits=None, resign_threshold=None, resign_min_ply=0, resign_disable_fraction=0.1,
-                 resign_seed=None, policy_target="visits", policy_c_visit=50.0, policy_c_scale=1.0, start_states=None, start_index=None):
+                 resign_seed=None, policy_target="visits", policy_c_visit=50.0, policy_c_scale=1.0, start_states=None, start_index=None,
+                 gumbel_considered=0, gumbel_scale=1.0, gumbel_seed=None):
         """model: GraphPolicyValueNetwork/GNNNetwork (evaluator='gnn'); evaluator='fake' runs the integer-hash
         evaluator used by the parity tests (oracle/mcts.py FakeModel); evaluator='external' calls `model.predict(state,
         device)` -- ANY object honouring the reference's BaseNetwork contract (BaseNetwork.py:36-40), e.g. a stock CNN --
@@ -86,7 +88,20 @@ class BatchedSelfPlay:
         row k % S.  The table goes through the checker here (game_logic.check_states_batch: one device-to-host read, in the
         constructor only) and any flagged row raises ValueError; so does an index that is short, long or out of range.  A start
         record has an even ply counter.  game_plies, the history rows, temperature_plies and resign_min_ply count the plies played in
-        the game; the draw rule reads the record's own counter.  reset() and every refill start from the table; search() refuses it."""
+        the game; the draw rule reads the record's own counter.  reset() and every refill start from the table; search() refuses it.
+        gumbel_considered M (0 = off, the default: every call is the one made today; 1..64; include/aqgnn.h, "Gumbel root search"): the
+        root samples M actions without replacement (Gumbel top-M over the stored priors), spends the sims - 1 root selections on them
+        by sequential halving and move() plays the survivor with the largest g + log p + sigma(q) -- no uniform is consumed and
+        `temperature` is not read.  Below the root the search is PUCT as ever.  sigma uses policy_c_visit / policy_c_scale as float32,
+        the transform of policy_target='completed_q', which is the matching training target (the visit rows are still written, but a
+        visit row is not a target under sequential halving).  gumbel_scale (finite, >= 0; 0 = a deterministic search) multiplies the
+        variates; gumbel_seed None = derived from `seed`.  A root's variates are keyed by (seed, game index, ply) -- draw_gumbel is the
+        generator in numpy -- unless move() / search() are given a table.  Needs sims >= 2; not with root noise, tree reuse,
+        resignation, temperature_plies or evaluator='external' (check_gumbel).  Two launches more per move than the three-launch form;
+        the fused step forms (step_heads and the options beside it) do not apply.  root_gumbel() reads the logits out."""
+        self.gumbel_options = check_gumbel(gumbel_considered, gumbel_scale, sims, root_noise_eps, tree_reuse, resign_threshold,
+                                           temperature_plies, evaluator)
+        self.gumbel_seed = default_gumbel_seed(seed) if gumbel_seed is None else int(gumbel_seed) & MASK64
         self.policy_target, self.policy_c_visit, self.policy_c_scale = check_policy_record(policy_target, policy_c_visit, policy_c_scale,
                                                                                            record_history)
         self.resign_options = check_resign(resign_threshold, resign_min_ply, resign_disable_fraction, record_history)
@@ -219,6 +234,15 @@ class BatchedSelfPlay:
             if index is not None:
                 t["start_index"] = index
                 st.index = index.data_ptr()
+        self.gumbel = None
+        if self.gumbel_options:
+            considered, scale = self.gumbel_options
+            t["gumbel_schedule"] = torch.from_numpy(considered_visits(considered, self.sims)).to(dev).contiguous()      # uploaded once
+            t["gumbel_m"] = z((G,), torch.int32)
+            gb = self.gumbel = _lib.GumbelStruct()
+            gb.seed, gb.scale, gb.considered = self.gumbel_seed, scale, considered
+            gb.c_visit, gb.c_scale = self.policy_c_visit, self.policy_c_scale          # (the struct's fields are f32)
+            gb.schedule, gb.m = t["gumbel_schedule"].data_ptr(), t["gumbel_m"].data_ptr()
         # every tensor is pointed at the struct field of its name (hist_value has none: it is an argument of the move; an absent
         # tensor -- gnn_workspace, the cache's -- leaves its field NULL)
         for name, tensor in t.items():
@@ -314,10 +338,56 @@ class BatchedSelfPlay:
         self.t["root_noise"].copy_(table)        # stream-ordered behind the previous move's reads
         self.e.root_noise = self.t["root_noise"].data_ptr()
 
-    def move(self, uniforms=None, root_noise=None):
+    def _set_gumbel(self, table):
+        """Table mode of the Gumbel root search: the variates of this move's roots, float64 [G, MAX_LEGAL] (None = the generator).
+        Copied into one buffer the engine keeps, like the root-noise table: the struct is part of the captured graph's key."""
+        if self.gumbel is None:
+            if table is not None:
+                raise ValueError("a gumbel table needs gumbel_considered > 0")
+            return
+        if table is None:
+            self.gumbel.table = None
+            return
+        table = torch.as_tensor(table, dtype=torch.float64).to(self.dev).contiguous().view(self.G, _lib.MAX_LEGAL)
+        if "gumbel_table" not in self.t:
+            self.t["gumbel_table"] = torch.zeros((self.G, _lib.MAX_LEGAL), dtype=torch.float64, device=self.dev)
+        self.t["gumbel_table"].copy_(table)      # stream-ordered behind the previous move's reads
+        self.gumbel.table = self.t["gumbel_table"].data_ptr()
+
+    def _move_gumbel(self):
+        """move() with the Gumbel root search on: one entry point, which takes every option struct that may be on beside it."""
+        _lib.check(self.lib.aqg_engine_move_gumbel(ctypes.byref(self.e), None, self.temperature_plies, _lib.ptr(self.t.get("hist_value")),
+                                                   None, None,
+                                                   ctypes.byref(self.policy_record) if self.policy_record is not None else None,
+                                                   ctypes.byref(self.start) if self.start is not None else None,
+                                                   ctypes.byref(self.gumbel), self._stream()), "aqg_engine_move_gumbel")
+        self.moves_done += 1
+
+    def root_gumbel(self):
+        """The Gumbel root search's state of every slot's root, read out of the tree pool (needs gumbel_considered; valid behind
+        search() and in front of a finish-move): (gl f32 [G, MAX_LEGAL] -- the Gumbel logits f32(scale * g + log p) in legal_actions()
+        order, -inf for an action that was not sampled and past the count --, m i32 [G] -- min(gumbel_considered, sampled actions) --,
+        winner i32 [G] -- the index of the child move() would play, -1 without children).  One launch that changes nothing."""
+        if self.gumbel is None:
+            raise ValueError("root_gumbel needs gumbel_considered > 0")
+        gl = torch.empty((self.G, _lib.MAX_LEGAL), dtype=torch.float32, device=self.dev)
+        m = torch.empty((self.G,), dtype=torch.int32, device=self.dev)
+        winner = torch.empty((self.G,), dtype=torch.int32, device=self.dev)
+        _lib.check(self.lib.aqg_engine_root_gumbel(ctypes.byref(self.e), ctypes.byref(self.gumbel), _lib.ptr(gl), _lib.ptr(m), _lib.ptr(winner),
+                                                   self._stream()), "aqg_engine_root_gumbel")
+        return gl, m, winner
+
+    def move(self, uniforms=None, root_noise=None, gumbel=None):
         """One move for every active game.  uniforms: float64 [G] in [0,1) (default: device RNG stream).  root_noise: float64
-        [G, MAX_LEGAL] gamma variates of this move's roots (default: the counter-based generator; needs root_noise_eps > 0)."""
+        [G, MAX_LEGAL] gamma variates of this move's roots (default: the counter-based generator; needs root_noise_eps > 0).
+        gumbel: float64 [G, MAX_LEGAL] Gumbel variates of this move's roots (default: the generator; needs gumbel_considered > 0);
+        with the Gumbel root search on no uniform is consumed, and giving some is a mistake (ValueError)."""
+        if self.gumbel is not None and uniforms is not None:
+            raise ValueError("move(uniforms=) with gumbel_considered > 0: the move is the survivor of sequential halving, no uniform is consumed")
         self._set_root_noise(root_noise)
+        self._set_gumbel(gumbel)
+        if self.gumbel is not None:
+            return self._move_gumbel()
         if uniforms is None:
             uniforms = torch.rand((self.G,), dtype=torch.float64, device=self.dev, generator=self.gen)
         else:
@@ -450,14 +520,15 @@ class BatchedSelfPlay:
         elif self.eval_cache_slots:
             self._clear_eval_cache()
 
-    def play_generation(self, uniforms=None, check_every=4, root_noise=None):
+    def play_generation(self, uniforms=None, check_every=4, root_noise=None, gumbel=None):
         """Play the whole quota (== every slot once when quota == num_games: one self_play generation's worth of games
-        on this rank).  uniforms: optional float64 [moves, G]; root_noise: optional float64 [moves, G, MAX_LEGAL] gamma variates
-        (parity tests).  Returns the counters dict."""
+        on this rank).  uniforms: optional float64 [moves, G]; root_noise: optional float64 [moves, G, MAX_LEGAL] gamma variates,
+        gumbel: optional float64 [moves, G, MAX_LEGAL] Gumbel variates (parity tests).  Returns the counters dict."""
         ply = 0
         limit = self.max_plies * (-(-self.quota // self.G))          # every slot plays at most ceil(quota / G) games
         while True:
-            self.move(None if uniforms is None else uniforms[ply], None if root_noise is None else root_noise[ply])
+            self.move(None if uniforms is None else uniforms[ply], None if root_noise is None else root_noise[ply],
+                      None if gumbel is None else gumbel[ply])
             ply += 1
             if ply >= limit or ply % check_every == 0:
                 c = self.counters()
@@ -470,9 +541,11 @@ class BatchedSelfPlay:
         return self.counters()
 
     # ------------------------------------------------------------------ search only (pv_mcts_policy)
-    def search(self, root_states72, check_saturation=True, root_noise=None):
+    def search(self, root_states72, check_saturation=True, root_noise=None, gumbel=None):
         """pv_mcts_policy for G roots at once: (visits i32 [G, MAX_LEGAL], actions u8, count i32).
         root_noise: float64 [G, MAX_LEGAL] gamma variates of the roots (root_noise_eps > 0; default: the generator, keyed by slot).
+        gumbel: float64 [G, MAX_LEGAL] Gumbel variates of the roots (gumbel_considered > 0; default: the generator, keyed by slot); with
+        the Gumbel root search on, the visit counts are sequential halving's and root_gumbel() names the child a move would play.
         check_saturation (GNN evaluator): the fp16-range guard's word (counters[5]) is cleared before the search and read back after it
         (one 4-byte copy: the callers read the visit counts back anyway); if a launch of this search met a value outside fp16 range its
         evaluations were finite but not the network's, so the weight set is marked (model.mark_saturated), the engine switches to the
@@ -489,6 +562,7 @@ class BatchedSelfPlay:
         roots = torch.as_tensor(root_states72, dtype=torch.uint8).to(self.dev).contiguous().view(self.G, 72)
         self._roots = roots
         self._set_root_noise(root_noise)
+        self._set_gumbel(gumbel)
         for attempt in range(2):
             guarded = check_saturation and self.binding.guarded and not (self.e.gnn_flags & _lib.GNN_EXACT_F32)
             if guarded:
@@ -496,6 +570,9 @@ class BatchedSelfPlay:
             if self.evaluator == "external":
                 _lib.check(self.lib.aqg_engine_set_roots(ctypes.byref(self.e), _lib.ptr(roots), self._stream()), "aqg_engine_set_roots")
                 self._external_sims()
+            elif self.gumbel is not None:
+                _lib.check(self.lib.aqg_engine_search_gumbel(ctypes.byref(self.e), _lib.ptr(roots), ctypes.byref(self.gumbel), self._stream()),
+                           "aqg_engine_search_gumbel")
             else:
                 _lib.check(self.lib.aqg_engine_search(ctypes.byref(self.e), _lib.ptr(roots), self._stream()), "aqg_engine_search")
             if not guarded or int(self.t["counters"][5].item()) == 0:
@@ -629,11 +706,13 @@ class MultiSetSelfPlay:
     streams, which every engine of the process reuses -- see _SET_STREAMS)."""
 
     def __init__(self, model=None, num_games=2048, sims=50, num_sets=None, seed=0, device=None, quota=None, root_noise_seed=None,
-                 resign_seed=None, start_states=None, start_index=None, **kw):
+                 resign_seed=None, start_states=None, start_index=None, gumbel_seed=None, **kw):
         check_resign(kw.get("resign_threshold"), kw.get("resign_min_ply", 0), kw.get("resign_disable_fraction", 0.1),
                      kw.get("record_history", True))          # before anything is allocated
         check_policy_record(kw.get("policy_target", "visits"), kw.get("policy_c_visit", 50.0), kw.get("policy_c_scale", 1.0),
                             kw.get("record_history", True))
+        check_gumbel(kw.get("gumbel_considered", 0), kw.get("gumbel_scale", 1.0), sims, kw.get("root_noise_eps", 0.0), kw.get("tree_reuse", False),
+                     kw.get("resign_threshold"), kw.get("temperature_plies", 0), kw.get("evaluator", "gnn"))
         self.dev = _lib.require_gpu(device)
         if num_sets is None:                      # one hardware queue per set + the default stream, or fall back to 2
             queues = os.environ.get("GPU_MAX_HW_QUEUES")
@@ -656,6 +735,9 @@ class MultiSetSelfPlay:
         # the sets' games are numbered through for the enabled / disabled draw as they are for the noise: the numbering rides in the seed
         resign_seeds = set_noise_seeds(seed, default_resign_seed(seed) if resign_seed is None else resign_seed, sizes,
                                        [max(q, g) for q, g in zip(quotas, sizes)])
+        # ... and for the Gumbel variates: a game's do not depend on the set count
+        gumbel_seeds = set_noise_seeds(seed, default_gumbel_seed(seed) if gumbel_seed is None else gumbel_seed, sizes,
+                                       [max(q, g) for q, g in zip(quotas, sizes)])
         # start positions: set i plays the games [sum of the quotas before it, + its own quota) of history_tensors()' order, and is handed
         # that slice of the index -- of the caller's, or of the default k % S written out, so that a game's start never depends on the sets
         set_quotas = [max(q, g) for q, g in zip(quotas, sizes)]
@@ -669,7 +751,7 @@ class MultiSetSelfPlay:
                 self.streams[i].wait_event(ready)
                 self.sets.append(BatchedSelfPlay(model, num_games=g, sims=sims, seed=int(seed) * 64 + i, device=self.dev,
                                                  quota=max(quotas[i], g),
-                                                 root_noise_seed=noise_seeds[i], resign_seed=resign_seeds[i],
+                                                 root_noise_seed=noise_seeds[i], resign_seed=resign_seeds[i], gumbel_seed=gumbel_seeds[i],
                                                  **(dict(kw, start_index=start_indices[i]) if start_states is not None else kw)))
         self.G, self.sims = int(num_games), int(sims)
         self.quota = self.G if quota is None else int(quota)

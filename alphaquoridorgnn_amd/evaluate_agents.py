@@ -80,11 +80,12 @@ class BatchedAgentMatch(TwoEngineMatch):
     def __init__(self, model, agent, num_games, sims=None, board_size=BOARD_SIZE, temperature=0.0, evaluator="gnn", seed=0,
                  device=None, agent_kwargs=None, root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None,
                  tree_reuse=None, tree_reuse_visits=None, resign_threshold=None, resign_min_ply=None,
-                 resign_disable_fraction=None, resign_seed=None):
+                 resign_disable_fraction=None, resign_seed=None, gumbel_considered=None, gumbel_scale=None, gumbel_seed=None):
         # (a strength measurement plays the network as it is: root exploration noise is a self-play option and is refused)
         refuse_self_play_options("BatchedAgentMatch", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed,
                                  tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits, resign_threshold=resign_threshold,
-                                 resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
+                                 resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed,
+                                 gumbel_considered=gumbel_considered, gumbel_scale=gumbel_scale, gumbel_seed=gumbel_seed)
         if not callable(agent) and agent not in AGENTS:
             raise ValueError(f"agent must be one of {AGENTS} or a callable state -> action")
         if evaluator not in BINDINGS:
@@ -173,13 +174,14 @@ _BOARD_OF_POLICY = {n * n + 2 * (n - 1) * (n - 1): n for n in (3, 5, 7, 9)}
 
 def evaluate_best_player(games=None, agents=AGENTS, seed=None, root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None,
                          tree_reuse=None, tree_reuse_visits=None, resign_threshold=None, resign_min_ply=None,
-                         resign_disable_fraction=None, resign_seed=None):
+                         resign_disable_fraction=None, resign_seed=None, gumbel_considered=None, gumbel_scale=None, gumbel_seed=None):
     """Evaluation of the best player (evaluate_agents.py:62-89): best.pth -- a GNN of any shape or the residual CNN, on the board its
     policy head is sized for -- against each of `agents`, `games` games each (default EP_GAME_COUNT), all games of a match at once.
     Prints the reference's lines (label, average point) and returns {label: average point}."""
     refuse_self_play_options("evaluate_best_player", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed,
                              tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits, resign_threshold=resign_threshold,
-                             resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
+                             resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed,
+                             gumbel_considered=gumbel_considered, gumbel_scale=gumbel_scale, gumbel_seed=gumbel_seed)
     from .pv_network_cnn import CNNNetwork
     from .pv_network_gnn import GNNNetwork, load_network
     games = EP_GAME_COUNT if games is None else int(games)

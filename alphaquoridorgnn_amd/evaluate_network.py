@@ -76,14 +76,16 @@ class BatchedMatch(TwoEngineMatch):
     def __init__(self, players, num_games, sims=None, board_size=BOARD_SIZE, temperature=EN_TEMPERATURE,
                  evaluator="gnn", seed=0, device=None, root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None,
                  tree_reuse=None, tree_reuse_visits=None, resign_threshold=None, resign_min_ply=None,
-                 resign_disable_fraction=None, resign_seed=None, openings=None):
+                 resign_disable_fraction=None, resign_seed=None, gumbel_considered=None, gumbel_scale=None, gumbel_seed=None,
+                 openings=None):
         """openings (None = off: the match as it always was): a uint8 [S, 72] book (openings.random_book); num_games must then be
         even, games 2j and 2j + 1 both start from openings[j % S] -- game 2j with player 0 moving first, game 2j + 1 with player 1 --
         and report() is openings.pair_report of the last play().  `temperature` stays the caller's (0 = no sampling noise)."""
         # (an evaluation match measures the networks as they are: root exploration noise is a self-play option and is refused)
         refuse_self_play_options("BatchedMatch", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed,
                                  tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits, resign_threshold=resign_threshold,
-                                 resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
+                                 resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed,
+                                 gumbel_considered=gumbel_considered, gumbel_scale=gumbel_scale, gumbel_seed=gumbel_seed)
         if evaluator == "external":
             raise ValueError("BatchedMatch has no evaluator='external': an engine asks one model, eng.model, from the host")
         self.players, self.evaluator, self.binding = players, evaluator, BINDINGS[evaluator]
@@ -138,14 +140,16 @@ class BatchedMatch(TwoEngineMatch):
 
 
 def evaluate_network(root_noise_eps=None, root_noise_alpha=None, root_noise_seed=None, tree_reuse=None, tree_reuse_visits=None, resign_threshold=None,
-                     resign_min_ply=None, resign_disable_fraction=None, resign_seed=None):
+                     resign_min_ply=None, resign_disable_fraction=None, resign_seed=None, gumbel_considered=None, gumbel_scale=None,
+                     gumbel_seed=None):
     """Network evaluation (evaluate_network.py:52-94): latest vs best, promote when the average point exceeds 0.5.  Two
     default 6/128/3 networks play on the engine's fused evaluator ('gnn'); when either file holds another shape, both play on
     its any-shape evaluator ('general').  Two CNNs (pv_network_cnn.py) play on the engine's CNN evaluator ('cnn'); a CNN against
     a GNN is refused (ValueError)."""
     refuse_self_play_options("evaluate_network", root_noise_eps=root_noise_eps, root_noise_alpha=root_noise_alpha, root_noise_seed=root_noise_seed,
                              tree_reuse=tree_reuse, tree_reuse_visits=tree_reuse_visits, resign_threshold=resign_threshold,
-                             resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed)
+                             resign_min_ply=resign_min_ply, resign_disable_fraction=resign_disable_fraction, resign_seed=resign_seed,
+                             gumbel_considered=gumbel_considered, gumbel_scale=gumbel_scale, gumbel_seed=gumbel_seed)
     model0 = load_network(PV_NETWORK_PATH + 'latest.pth')
     model1 = load_network(PV_NETWORK_PATH + 'best.pth')
     cnn = [isinstance(m, CNNNetwork) for m in (model0, model1)]

@@ -78,6 +78,12 @@ SP_REANALYSE_C_SCALE = 1.0
 SP_POLICY_TARGET = 'visits'  # the reference's rows
 SP_POLICY_C_VISIT = 50.0
 SP_POLICY_C_SCALE = 1.0
+# Gumbel root search (the reference has none; engine.BatchedSelfPlay, include/aqgnn.h "Gumbel root search"): every root samples
+# SP_GUMBEL_CONSIDERED actions without replacement, spends the simulations on them by sequential halving and plays the survivor.  The
+# matching policy target is the completed-Q row: SP_POLICY_TARGET must be 'completed_q' (a visit row is no target under halving).
+SP_GUMBEL_CONSIDERED = 0     # 0 = off: PUCT at the root and a draw from the visit counts
+SP_GUMBEL_SCALE = 1.0        # factor on the Gumbel variates; 0 = a deterministic search
+SP_GUMBEL_SEED = None        # None = derived from the generation's seed
 # Forked self-play (the reference has none; openings.fork_table, include/aqgnn.h "start positions"): a share of every generation's games
 # starts from positions the replay window already holds instead of from the opening record.  Which games, and from which row, is drawn
 # per (seed, generation, game index over all ranks): every rank builds the same table from its own window, with no collective.
@@ -173,6 +179,16 @@ def _after_resign_generation(arrays, threshold, rank):
                  f'; next threshold: {"none (the next generation only collects)" if nxt is None else format(nxt, ".4f")}'))
 
 
+def _gumbel_options(target):
+    """The engine's keyword arguments of the Gumbel root search -- {} when it is off; refused without the completed-Q target."""
+    if not SP_GUMBEL_CONSIDERED:
+        return {}
+    if target != "completed_q":
+        raise ValueError("SP_GUMBEL_CONSIDERED needs SP_POLICY_TARGET = 'completed_q': a visit row is not a policy target under "
+                         "sequential halving")
+    return dict(gumbel_considered=SP_GUMBEL_CONSIDERED, gumbel_scale=SP_GUMBEL_SCALE, gumbel_seed=SP_GUMBEL_SEED)
+
+
 def _value_lambda(blend):
     """SP_VALUE_LAMBDA as a float, or None when it is off; refused without a value blend, because nothing would read it."""
     if SP_VALUE_LAMBDA is None:
@@ -200,7 +216,8 @@ def play(model, device=None, uniforms=None):
                           evaluator=pv_mcts.evaluator_of(model), root_noise_eps=SP_ROOT_NOISE_EPS,
                           root_noise_alpha=SP_ROOT_NOISE_ALPHA, temperature_plies=SP_TEMPERATURE_PLIES,
                           record_search_value=blend > 0.0, tree_reuse=SP_TREE_REUSE, tree_reuse_visits=SP_TREE_REUSE_VISITS,
-                          policy_target=target, policy_c_visit=c_visit, policy_c_scale=c_scale, **_resign_options()[0])
+                          policy_target=target, policy_c_visit=c_visit, policy_c_scale=c_scale, **_resign_options()[0],
+                          **_gumbel_options(target))
     eng.play_generation(uniforms=uniforms, check_every=1)
     if blend > 0.0:
         return _history_rows(*eng.history_tensors(), BOARD_SIZE, _search_values(eng, lam), blend,
@@ -237,6 +254,7 @@ def self_play(model=None, games=None, seed=None):
     target, c_visit, c_scale = check_policy_record(SP_POLICY_TARGET, SP_POLICY_C_VISIT, SP_POLICY_C_SCALE)
     blend = check_value_blend(SP_VALUE_BLEND)
     lam = _value_lambda(blend)
+    gumbel_kw = _gumbel_options(target)
     if model is None:
         model = load_network(PV_NETWORK_PATH + 'best.pth')       # GNNNetwork (prep_for_inference's path), or the network best.pth holds
         if isinstance(model, (GNNNetwork, CNNNetwork)) and torch.cuda.is_available():
@@ -279,9 +297,10 @@ def self_play(model=None, games=None, seed=None):
                                evaluator=evaluator, root_noise_eps=SP_ROOT_NOISE_EPS, root_noise_alpha=SP_ROOT_NOISE_ALPHA,
                                temperature_plies=SP_TEMPERATURE_PLIES, record_search_value=blend > 0.0,
                                tree_reuse=SP_TREE_REUSE, tree_reuse_visits=SP_TREE_REUSE_VISITS,
-                               policy_target=target, policy_c_visit=c_visit, policy_c_scale=c_scale, **resign_kw, **start_kw)
+                               policy_target=target, policy_c_visit=c_visit, policy_c_scale=c_scale, **resign_kw, **start_kw, **gumbel_kw)
         c = eng.play_generation()
         print(f'\rSelf-play (rank {rank}: {c["finished"]}/{mine} games, policy target: {target}'
+              + (f', search: Gumbel root, {SP_GUMBEL_CONSIDERED} considered' if gumbel_kw else ', search: PUCT')
               + (f', value lambda: {lam:g}' if lam is not None else '')
               + (f', {SP_FORKED_LAST}/{total} games forked from the window' if start_kw else '') + ')', end='')
         st, vis, z = eng.history_tensors()

@@ -146,6 +146,43 @@ def check_resign(resign_threshold, resign_min_ply=0, resign_disable_fraction=0.1
     return thr, int(resign_min_ply), frac
 
 
+def check_gumbel(gumbel_considered=0, gumbel_scale=1.0, sims=2, root_noise_eps=0.0, tree_reuse=False, resign_threshold=None,
+                 temperature_plies=0, evaluator="gnn"):
+    """Validate the Gumbel root search as the library does (include/aqgnn.h, "Gumbel root search"), in the library's order: sims >= 2;
+    gumbel_considered in 1..64; gumbel_scale finite and >= 0; then not with root noise, tree reuse, resignation, temperature_plies > 0
+    or evaluator='external'.  Returns (considered, scale), or None when the option is off (gumbel_considered 0)."""
+    if isinstance(gumbel_considered, bool) or not isinstance(gumbel_considered, (int, np.integer)):
+        raise ValueError(f"gumbel_considered must be an integer in 0..64 (0 = off), not {gumbel_considered!r}")
+    considered = int(gumbel_considered)
+    if considered == 0:
+        return None
+    if int(sims) < 2:
+        raise ValueError("gumbel_considered needs sims >= 2: simulation 0 evaluates the root, the root is selected from sims - 1 times")
+    if not 1 <= considered <= 64:
+        raise ValueError(f"gumbel_considered must be in 1..64 (0 = off), not {gumbel_considered!r}")
+    if isinstance(gumbel_scale, (bool, str)) or not isinstance(gumbel_scale, (int, float, np.integer, np.floating)):
+        raise ValueError(f"gumbel_scale must be a finite number >= 0, not {gumbel_scale!r}")
+    scale = float(gumbel_scale)
+    if not (scale >= 0.0 and scale != float("inf")):             # NaN fails the first
+        raise ValueError(f"gumbel_scale must be a finite number >= 0, not {gumbel_scale!r}")
+    if root_noise_eps:
+        raise ValueError("gumbel_considered is not offered with root noise: the Gumbel variates are the root's exploration")
+    if tree_reuse:
+        raise ValueError("gumbel_considered is not offered with tree_reuse: a kept root's children hold no Gumbel logits")
+    if resign_threshold is not None:
+        raise ValueError("gumbel_considered is not offered with resignation")
+    if temperature_plies:
+        raise ValueError("gumbel_considered is not offered with temperature_plies: the move is the survivor, no temperature is read")
+    if evaluator == "external":
+        raise ValueError("gumbel_considered is not offered with evaluator='external': its host loop has no root launch")
+    return considered, scale
+
+
+def default_gumbel_seed(seed):
+    """The Gumbel seed of an engine that was given none: `seed` through the mixer (see default_root_noise_seed)."""
+    return mix64((int(seed) & MASK64) ^ 0x47554D42454C5F5F)
+
+
 def default_root_noise_seed(seed):
     """The noise seed of an engine that was given none: `seed` through the mixer.  NOT a linear map: the generator's stream of game
     k is keyed by mix(noise_seed + GOLDEN * (k + 1)), so noise seeds that differ by a multiple of GOLDEN -- what any affine map of
@@ -234,9 +271,11 @@ def set_start_indices(start_states, start_index, set_quotas):
 # Matches, evaluation paths and single searches add no noise (they measure strength), search from a fresh tree every move (two
 # alternating searchers would need a two-ply descent into per-model trees) and play every game to its rule end.
 _NOISE, _REUSE, _RESIGN = "never adds root exploration noise", "never keeps a subtree between moves", "never resigns a game"
+_GUMBEL = "never samples its root's actions (the Gumbel root search)"
 SELF_PLAY_ONLY = {"root_noise_eps": _NOISE, "root_noise_alpha": _NOISE, "root_noise_seed": _NOISE,
                   "tree_reuse": _REUSE, "tree_reuse_visits": _REUSE,
-                  "resign_threshold": _RESIGN, "resign_min_ply": _RESIGN, "resign_disable_fraction": _RESIGN, "resign_seed": _RESIGN}
+                  "resign_threshold": _RESIGN, "resign_min_ply": _RESIGN, "resign_disable_fraction": _RESIGN, "resign_seed": _RESIGN,
+                  "gumbel_considered": _GUMBEL, "gumbel_scale": _GUMBEL, "gumbel_seed": _GUMBEL}
 
 
 def refuse_self_play_options(what, **options):

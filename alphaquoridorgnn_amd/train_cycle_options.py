@@ -10,7 +10,7 @@ from . import distributed as aqd
 from .openings import check_window_share
 from .reanalyse import check_reanalyse_options
 from .replay import ReplayWindow, check_holdout_options, check_surprise_options, check_value_blend
-from .selfplay_options import (check_policy_record, check_policy_target, check_resign, check_target_options, check_tree_reuse,
+from .selfplay_options import (check_gumbel, check_policy_record, check_policy_target, check_resign, check_target_options, check_tree_reuse,
                                check_value_lambda)
 from .train_reference import check_average_controls, check_loss_controls
 
@@ -168,6 +168,16 @@ def _parser():
                     help="self-play, with --policy-target completed-q: c_visit of the transform, >= 0 (default SP_POLICY_C_VISIT = 50)")
     ap.add_argument("--policy-c-scale", type=float, default=None, metavar="Y",
                     help="self-play, with --policy-target completed-q: c_scale of the transform, >= 0 (default SP_POLICY_C_SCALE = 1)")
+    ap.add_argument("--gumbel-considered", type=int, default=None, metavar="M",
+                    help="self-play: Gumbel root search -- every root samples M actions without replacement (1..64), spends the "
+                         "simulations on them by sequential halving and plays the survivor; needs --policy-target completed-q, the "
+                         "matching training target (default SP_GUMBEL_CONSIDERED = 0: off, PUCT at the root and a draw from the visits)")
+    ap.add_argument("--gumbel-scale", type=float, default=None, metavar="S",
+                    help="self-play, with --gumbel-considered: factor S >= 0 on the Gumbel variates, 0 = a deterministic search "
+                         "(default SP_GUMBEL_SCALE = 1)")
+    ap.add_argument("--gumbel-seed", type=int, default=None, metavar="K",
+                    help="self-play, with --gumbel-considered: seed of the variates (default SP_GUMBEL_SEED = None: derived from the "
+                         "generation's seed)")
     ap.add_argument("--eval-opening-plies", type=int, default=None, metavar="K",
                     help="evaluation: play the match from a book of paired openings K random plies deep (K even, an even game count), "
                          "each opening twice with the colours exchanged, and print the paired report (default EN_OPENING_PLIES = 0: off)")
@@ -226,6 +236,40 @@ def _check_policy_args(args):
         return check_policy_record(*(d if x is None else x for x, d in zip(given, ("visits", sp.SP_POLICY_C_VISIT, sp.SP_POLICY_C_SCALE))))
     except ValueError as err:
         raise ValueError(f"--policy-target / --policy-c-visit / --policy-c-scale: {err}") from None
+
+
+def _check_gumbel_args(args):
+    """--gumbel-considered / --gumbel-scale / --gumbel-seed, refused at parse time: the two dependent flags without the first, the
+    option without --policy-target completed-q (a visit row is not a target under sequential halving), and everything the library
+    refuses -- M outside 1..64, a bad scale, fewer than two simulations, and the option beside root noise, tree reuse, resignation or
+    --temperature-plies.  Returns (considered, scale, seed or None), or None when the option is off."""
+    if args.gumbel_considered is None:
+        if args.gumbel_scale is not None or args.gumbel_seed is not None:
+            raise ValueError("--gumbel-scale and --gumbel-seed need --gumbel-considered")
+        return None
+    if args.gumbel_considered < 1:
+        raise ValueError("--gumbel-considered must be in 1..64")
+    target = args.policy_target if args.policy_target is not None else sp.SP_POLICY_TARGET
+    if str(target).replace("-", "_") != "completed_q":
+        raise ValueError("--gumbel-considered needs --policy-target completed-q: a visit row is not a policy target under sequential halving")
+    sims = pv_mcts.PV_EVALUATE_COUNT if args.sims is None else args.sims
+    eps = sp.SP_ROOT_NOISE_EPS if args.root_noise_eps is None else args.root_noise_eps
+    plies = sp.SP_TEMPERATURE_PLIES if args.temperature_plies is None else args.temperature_plies
+    reuse = bool(args.tree_reuse or args.tree_reuse_visits is not None or sp.SP_TREE_REUSE)
+    resign = args.resign_threshold if args.resign_threshold is not None else sp.SP_RESIGN_THRESHOLD
+    try:
+        considered, scale = check_gumbel(args.gumbel_considered, sp.SP_GUMBEL_SCALE if args.gumbel_scale is None else args.gumbel_scale,
+                                         sims, eps, reuse, resign, plies)
+    except ValueError as err:
+        raise ValueError(f"--gumbel-considered / --gumbel-scale: {err}") from None
+    return considered, scale, args.gumbel_seed
+
+
+def _set_gumbel_options(args):
+    """The checked Gumbel flags onto self_play's constants."""
+    checked = _check_gumbel_args(args)
+    if checked is not None:
+        sp.SP_GUMBEL_CONSIDERED, sp.SP_GUMBEL_SCALE, sp.SP_GUMBEL_SEED = checked
 
 
 def _set_policy_options(args):
@@ -478,7 +522,7 @@ def check_args(args):
     """Every check of the parsed flags that needs no device, the first bad flag raising ValueError: what main() runs in front of
     anything that touches a GPU or the process group."""
     for check in (_check_reanalyse_args, _check_reanalyse_policy_args, _check_policy_args, _check_surprise_args, _check_holdout_args,
-                  _check_start_args, _check_value_lambda_args, _check_average_args):
+                  _check_start_args, _check_value_lambda_args, _check_average_args, _check_gumbel_args):
         check(args)
 
 
@@ -497,7 +541,7 @@ def apply_args(args):
         tn.NUM_EPOCH = args.epochs
     for set_options in (_set_target_options, _set_tree_reuse_options, _set_resign_options, _set_mirror_options, _set_optimiser_options,
                         _set_loss_options, _set_average_options, _set_replay_options, _set_surprise_options, _set_holdout_options,
-                        _set_reanalyse_options, _set_policy_options, _set_start_options):
+                        _set_reanalyse_options, _set_policy_options, _set_start_options, _set_gumbel_options):
         set_options(args)
     if args.eval_games is not None:
         en.EN_GAME_COUNT = args.eval_games

@@ -1371,6 +1371,67 @@ int aqg_engine_finish_move_start(const aqg_engine* e_host, const double* uniform
                                  const aqg_start_table* start, void* stream);
 int aqg_engine_apply_actions_start(const aqg_engine* e_host, const int32_t* actions, const aqg_start_table* start, void* stream);
 
+/* ------------------------------------------------------------------ Gumbel root search
+ * The other half of "Policy improvement by planning with Gumbel" (Danihelka et al., ICLR 2022; the completed-Q target above is the
+ * first): the root samples m actions without replacement (Gumbel top-m), spends the simulations on them by sequential halving and
+ * plays the survivor with the largest g + logit + sigma(q).  Below the root the search is the reference's PUCT, untouched.  Off (a
+ * NULL aqg_gumbel*) every entry point launches what it always launched.  The engine struct and AQG_ABI_VERSION stay.
+ * A root has cnt children in legal_actions() order with stored priors p_i; `sims` is the engine's simulation count (>= 2 with the
+ * option): simulation 0 evaluates the root, so the root is selected from sims - 1 times.
+ * 1. Gumbel logits.  gl_i = f32(scale * g_i + log(p_i)), formed in float64 without contraction and rounded once; gl_i = -inf where
+ *    p_i is not > 0 (NaN included).  g_i: table mode (table != NULL) g_i = table[g][i], a non-finite entry reads 0; generator mode
+ *    u = f(key, 0) of the counter generator above, e = -log(1 - u), e = DBL_MIN if that is 0, g_i = -log(e), with
+ *    key = K(K(K(seed, k), ply), i), k = slot_game[g] (the GAME's index; the slot in the search-only entry point) and ply the root
+ *    record's counter -- root noise's keying, so a game's variates do not depend on slot, refill or set count.
+ *    m_g = min(considered, number of children with gl_i > -inf).
+ * 2. The visit schedule T[m'][0 .. sims - 2], m' = 0 .. considered: the considered visit counts of sequential halving.  m' <= 1:
+ *    T[m'][j] = j.  Otherwise L = ceil(log2 m'), visits = [0] * m', k = m'; until sims - 1 entries exist: x = max(1, floor((sims - 1) /
+ *    (L * k))); x times: append visits[:k], then add 1 to each of visits[:k]; then k = max(2, k / 2).  Cut to sims - 1 entries.  Built
+ *    on the host (gumbel.considered_visits), uploaded once: schedule[m' * (sims - 1) + j].
+ * 3. Root selection of simulation s = 1 .. sims - 1.  v = T[m_g][s - 1]; n_i, q_i = the children's visit counts and stored q after
+ *    every earlier simulation's backup; nmax = max_i n_i.  In float32, left to right, no contraction:
+ *        S_i = gl_i + (n_i > 0 ? ((c_visit + float(nmax)) * c_scale) * ((q_i + 1.0f) * 0.5f) : 0.0f)
+ *        S_i = -inf where n_i != v or gl_i is -inf
+ *    The chosen child is the first index of the maximum; if nothing equals the maximum, child 0 (as the PUCT arg-max).  c_visit and
+ *    c_scale are the f32 values of the policy record's constants, so selection and the recorded target use one transform.
+ * 4. The move.  v* = max n_i over the children with gl_i > -inf; the move is the action of the first arg-max of S_i with v = v*.  No
+ *    uniform is consumed and `temperature` is not read.
+ * Where it lives.  gl_i travels in the `cp` word of the ROOT's children (nothing but root selection reads it); m_g is a per-slot word.
+ * A move's launches: step(0, 1), evaluate; step(1, 0) -- the root's expansion and backup, in memory; the root launch
+ * (csrc/mcts_gumbel.hip engine_gumbel_root_kernel: one wavefront per slot, writes gl_i and m_g; a count above AQG_MAX_LEGAL or a
+ * child range that leaves the pool writes nothing and sets m_g = 0); then per simulation the plain three-launch form with the step
+ * kernel's GUMBEL instantiation (csrc/mcts_step.hip: level 0 scores by rule 3, every other level is PUCT) -- two launches more per
+ * move than the three-launch PUCT form; step_heads, legal_beside_trunk and policy_beside_step do not apply.  The finish launch
+ * (engine_finish_move_gumbel_kernel) is engine_finish_move_kernel's history row with rule 4 in place of the draw.
+ * A root that is the pending leaf of a GUMBEL step cannot occur in that order; the kernel then drops the simulation and leaves
+ * m_g = -1 for the read-out to show.
+ * Refused before any launch, in this order: sims < 2; considered outside 1..64; a non-finite or negative scale; root noise; tree
+ * reuse; resignation; temperature_plies > 0; prior_mode 2.  The evaluation cache, the policy record and the start table stay allowed.
+ * The struct's contents are part of the hipGraph cache key. */
+typedef struct aqg_gumbel {
+    const double* table;            /* f64 [G, AQG_MAX_LEGAL] variates of this move's roots, or NULL = the generator */
+    uint64_t seed;                  /* the generator's seed */
+    double scale;                   /* finite, >= 0; 0 = a deterministic search */
+    int32_t considered;             /* M, 1..64 */
+    float c_visit, c_scale;         /* the f32 constants of sigma */
+    const int32_t* schedule;        /* T, i32 [considered + 1, sims - 1] */
+    int32_t* m;                     /* m_g, i32 [G] */
+} aqg_gumbel;
+/* aqg_engine_move_start / aqg_engine_finish_move_start with the option (uniforms may be NULL: none is read) */
+int aqg_engine_move_gumbel(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                           const aqg_tree_reuse* reuse, const aqg_resign* resign, const aqg_policy_record* policy,
+                           const aqg_start_table* start, const aqg_gumbel* gumbel, void* stream);
+int aqg_engine_finish_move_gumbel(const aqg_engine* e_host, const double* uniforms, int32_t temperature_plies, float* hist_value,
+                                  const aqg_tree_reuse* reuse, const aqg_resign* resign, const aqg_policy_record* policy,
+                                  const aqg_start_table* start, const aqg_gumbel* gumbel, void* stream);
+/* aqg_engine_search with the option (keys by slot) */
+int aqg_engine_search_gumbel(const aqg_engine* e_host, const uint8_t* root_states72, const aqg_gumbel* gumbel, void* stream);
+/* the root launch alone: gl_i into the expanded roots' children, m_g into the words */
+int aqg_engine_gumbel_root(const aqg_engine* e_host, const aqg_gumbel* gumbel, void* stream);
+/* the read-out: gl f32 [G, AQG_MAX_LEGAL] (-inf past the count), m i32 [G], the winner's child index by rule 4 i32 [G] (-1 without
+ * children).  It changes nothing. */
+int aqg_engine_root_gumbel(const aqg_engine* e_host, const aqg_gumbel* gumbel, float* gl, int32_t* m, int32_t* winner, void* stream);
+
 /* ------------------------------------------------------------------ CPU baseline agents (agents.py) -- HOST pointers, host code */
 
 /* The reference's baseline opponents (agents.py:14-214) are CPU code; so are these: the host instantiation of the rule header
